@@ -1,7 +1,7 @@
 #!/usr/bin/env python
-"""Headline benchmark: LTX-2 19B distilled, 768x512x65, bf16 -- denoise steps/s (+ VAE-decode frames/s).
+"""Headline benchmark: LTX-2 19B distilled, 768x512x65, bf16 -- denoise steps/s (+ VAE-decode frames/s with --full).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 With N > 1 and no torchrun environment the script re-launches itself under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` (one rank per GPU, RCCL); under a
@@ -11,8 +11,16 @@ A "step" is one denoise step of the hot path over one prompt's latent: LTXModel 
 (48 blocks, D=4096, N=3456 video tokens, S=1024 text tokens) + x0 + Euler update, with inputs
 and weights resident in HBM.  Each rank runs its own (prompt, seed); weights are broadcast once
 from rank 0 over RCCL; there is no per-step communication (weak scaling over prompts).
-The headline K steps are timed with NO instrumentation; the dominant GEMM's launch time comes from a second,
-untimed pass of K steps with HIP events around every launch of that kernel.  Prints ONE JSON line on rank 0.
+The headline K steps are timed with NO instrumentation.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line (plus --dump-outputs).  Everything else it can measure runs
+only with --full, after the timed region: the dominant GEMM's launch time from a second, untimed pass of K steps with HIP events
+around every launch of that kernel, the fold_norms A/B, the hipGraph form, socket power, the VAE decode, the secondary
+configurations, the checkpoint loader and the CPU baseline.
+
+--dump-outputs DIR: after the timed steps, the latent the last timed step left (what a caller of denoise_step_ receives; float32,
+3456 x 128 at the headline size) is written to DIR/latent.npy (rank r > 0: DIR/latent_rank<r>.npy).  Weights, noise and context are
+seeded, so the same arguments give the same inputs on every run.
 """
 import argparse
 import json
@@ -26,6 +34,7 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 PEAK_BF16_TFLOPS = 2500.0      # MI355X dense bf16 MFMA (MI355X_MICROARCH.md)
@@ -413,7 +422,12 @@ def main():
                     "(8 = 4.3 GB, bounded for the default run; 48 = the full 25.8 GB file)")
     ap.add_argument("--no-loader", action="store_true", help="skip the checkpoint-loader throughput leg")
     ap.add_argument("--fold", type=int, default=None, help="engine option fold_norms for the headline model (0 = round 5's norm passes; default: the engine's, 1)")
+    ap.add_argument("--full", action="store_true", help="after the headline, run every other leg (kernel pass, fold A/B, hipGraph form, power, VAE decode, "
+                    "secondary configurations, loader, CPU baseline); a plain run does only what the headline needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the latent of the last timed step to DIR/latent.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(relaunch_under_torchrun(args.gpus))
 
@@ -505,7 +519,8 @@ def main():
         return mine, D.max_over_ranks(time.perf_counter() - t_start, dev)
 
     # set-up first (one eager step so every lazily sized buffer exists, then the capture), the W warm-up steps LAST: the timed region starts on a socket
-    # that has just been running the same kernels (a timed region that follows the capture's idle time directly reads ~1 % slow)
+    # that has just been running the same kernels (a timed region that follows the capture's idle time directly reads ~1 % slow).  A plain run captures
+    # and replays too: the headline has always been timed after this sequence (same-box A/B without it: +0.4-0.5 ms per step)
     run_steps(1)
     torch.cuda.synchronize()
     graph_err = None
@@ -577,6 +592,12 @@ def main():
             return None
 
     try:
+        if args.dump_outputs:
+            # the timed path's result, before any --full leg runs more steps over `lat`
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "latent.npy" if rank == 0 else f"latent_rank{rank}.npy"), lat.float().cpu().numpy())
+        if not args.full:
+            return
         # ---------------- second pass (not part of `value`): HIP events around every launch of the dominant GEMM ----------------
         DOM_EPI = nv.EPI_RESID_GATE_F32     # gemm_v4_kernel<EPI_RESID_GATE_F32, 3, 224>: attn1.to_out, attn2.to_out, ff.net.2
 
@@ -718,7 +739,7 @@ def main():
                 return loader_throughput(dev, args.loader_layers)
             out["loader"] = leg("loader", loader_leg)
         if world == 1 and not args.no_cpu_baseline:        # the CPU leg is reported at N = 1 only (rank 0's host cores)
-            out["cpu_baseline"] = leg("cpu_baseline", lambda: cpu_baseline(min(CPU_THREADS, os.cpu_count() or 1)))
+            out["cpu_baseline"] = leg("cpu_baseline", lambda: cpu_baseline(min(CPU_THREADS, os.cpu_count() or 1, int(os.environ.get("OMP_NUM_THREADS") or CPU_THREADS))))
     finally:
         emit()
 

@@ -60,7 +60,7 @@ def test_bench_multi_rank_rehearsal(dev, world, bcast):
     env = dict(os.environ, LTX2_DIST_BACKEND="gloo", LTX2_LOCAL_DEVICE="0", LTX2_BCAST=bcast)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(29533 + world), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "8", "--warmup", "1", "--layers", "2",
-           "--no-vae", "--no-cpu-baseline", "--no-power"]
+           "--full", "--no-vae", "--no-cpu-baseline", "--no-power"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
@@ -82,7 +82,7 @@ def test_bench_self_launch(dev):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(LTX2_DIST_BACKEND="gloo", LTX2_LOCAL_DEVICE="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "1", "--layers", "2",
-                        "--no-vae", "--no-graph"], capture_output=True, text=True, env=env, timeout=900)
+                        "--full", "--no-vae", "--no-graph"], capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -97,8 +97,8 @@ def test_bench_single_gpu_line(dev):
     (2 layers so the test stays short)."""
     import json
     import subprocess
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8", "--warmup", "1", "--layers", "2", "--no-vae", "--no-extra",
-                        "--no-loader", "--no-power"], capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8", "--warmup", "1", "--layers", "2", "--full", "--no-vae",
+                        "--no-extra", "--no-loader", "--no-power"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1 and lines[0].startswith('{"metric"'), r.stdout[-2000:]
@@ -109,12 +109,12 @@ def test_bench_single_gpu_line(dev):
 
 
 def test_bench_driver_command(dev):
-    """The driver's exact argv (`--gpus 1 --steps 20 --warmup 5`: 20 is NOT a multiple of 8) plus only `--layers 2 --loader-layers 1`, with every leg the
-    driver's run takes: kernel pass, the hipGraph form for the record, the power probe, the VAE decode, the secondary configurations, the loader and the
+    """The driver's argv (`--gpus 1 --steps 20 --warmup 5`: 20 is NOT a multiple of 8) plus only `--full --layers 2 --loader-layers 1`, with every leg the
+    full run takes: kernel pass, the hipGraph form for the record, the power probe, the VAE decode, the secondary configurations, the loader and the
     CPU baseline.  Round 4's line was lost to an exception in a leg AFTER the timed region; this is the run that would have caught it."""
     import json
     import subprocess
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--layers", "2", "--loader-layers", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--layers", "2", "--loader-layers", "1"],
                        capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -134,14 +134,36 @@ def test_bench_driver_command(dev):
     assert out["loader"]["first_load"]["file_to_hbm_gbps"] > 0
 
 
+def test_bench_plain_run_and_dump_outputs(dev, tmp_path):
+    """A plain run (no --full) times the K steps and prints the headline only; --dump-outputs writes the latent of the last timed step, and the same
+    argv twice gives the same inputs, hence bit-identical outputs (no kernel on the step uses atomics)."""
+    import json
+    import subprocess
+    outs = []
+    for tag in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "9", "--warmup", "2", "--layers", "2",
+                            "--dump-outputs", str(tmp_path / tag)], capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1 and lines[0].startswith('{"metric"'), r.stdout[-2000:]
+        out = json.loads(lines[0])
+        assert out["metric"] == "denoise_steps_per_sec" and out["unit"] == "steps/s" and out["higher_is_better"] is True and out["dtype"] == "bf16"
+        assert out["steps"] == 9 and out["warmup"] == 2 and abs(out["value"] - 1e3 / out["ms_per_step"]) < 1e-2 * out["value"]
+        assert not {"roofline", "hipgraph_ms_per_step", "vae_decode_ms", "extra_configs", "loader", "cpu_baseline"} & set(out), sorted(out)
+        assert sorted(os.listdir(tmp_path / tag)) == ["latent.npy"]
+        outs.append(np.load(tmp_path / tag / "latent.npy"))
+    assert outs[0].shape == (3456, 128) and outs[0].dtype == np.float32 and np.isfinite(outs[0]).all() and np.abs(outs[0]).max() > 0
+    assert np.array_equal(outs[0], outs[1])
+
+
 def test_bench_line_survives_a_failing_leg(dev):
     """A leg that raises after the timed region costs its own fields only: LTX2_BENCH_FAIL_LEG makes the VAE leg raise; the line still
     carries the headline, the roofline object and `vae_error`, rc 0."""
     import json
     import subprocess
     env = dict(os.environ, LTX2_BENCH_FAIL_LEG="vae")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "9", "--warmup", "1", "--layers", "2", "--no-extra", "--no-loader",
-                        "--no-cpu-baseline", "--no-power"], capture_output=True, text=True, timeout=900, env=env)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "9", "--warmup", "1", "--layers", "2", "--full", "--no-extra",
+                        "--no-loader", "--no-cpu-baseline", "--no-power"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][0])
     assert out["value"] > 0 and out["roofline"]["frac"] is not None and out["hipgraph_ms_per_step"] > 0

@@ -36,7 +36,7 @@ for k, c in agg.items():
                  fetch / 1e6, write / 1e6, (fetch + write) / t_ns))
 rows.sort(reverse=True)
 with open(out_path, "w") as f:
-    f.write("Per-kernel PMC summary of `bench.py --steps 2 --warmup 1 --no-extra --no-cpu-baseline [--no-graph]` (tools/pmc_bench.sh: three\n"
+    f.write("Per-kernel PMC summary of `bench.py --full --steps 2 --warmup 1 --no-extra --no-cpu-baseline [--no-graph]` (tools/pmc_bench.sh: three\n"
             "separate rocprofv3 --pmc passes with --kernel-trace only).  eff. clock = GRBM_GUI_ACTIVE / 8 XCDs / wall (short kernels\n"
             "over-read: wall excludes ramp); MFMA-pipe busy = SQ_VALU_MFMA_BUSY_CYCLES / (active cycles x 1024 matrix pipes), i.e. the\n"
             "fraction of the peak AT THE CLOCK THE CHIP ACTUALLY RAN; read/write = FETCH_SIZE x2 (gfx950 correction) / WRITE_SIZE, KB x 1024,\n"

@@ -3,7 +3,7 @@
 # usage: tools/power_trace.sh <tag> [bench args]   -> gpurun_out/<tag>/{power.csv,bench.json}
 tag=${1:-power}; shift
 out=gpurun_out/$tag; mkdir -p $out
-python bench.py --steps 240 --warmup 4 --no-extra --no-cpu-baseline --no-vae --no-kernel-pass "$@" > $out/bench.log 2>&1 &
+python bench.py --full --steps 240 --warmup 4 --no-extra --no-cpu-baseline --no-vae --no-kernel-pass "$@" > $out/bench.log 2>&1 &
 bpid=$!
 rm -f $out/power_raw.csv
 t0=$(date +%s%3N)

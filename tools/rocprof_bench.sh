@@ -9,7 +9,7 @@ OUT=$REPO/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/rp_$TAG
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rp_$TAG -o bench -- python "$REPO/bench.py" "$@" > "$OUT/bench_stdout.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rp_$TAG -o bench -- python "$REPO/bench.py" --full "$@" > "$OUT/bench_stdout.log" 2>&1
 grep '^{"metric"' "$OUT/bench_stdout.log" > "$OUT/bench.json" || true
 for f in $(find /tmp/rp_$TAG -name "*kernel_stats.csv"); do cp "$f" "$OUT/kernel_stats.csv"; done
 ls -la "$OUT"
