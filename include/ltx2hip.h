@@ -467,6 +467,31 @@ int ltx2_vae_decode(ltx2_vae* ctx, const float* latent, int T, int H, int W, flo
 /* output frame count of one decode call for T latent frames */
 int ltx2_vae_out_frames(const ltx2_vae* ctx, int T);
 
+/* ---- Gemma-3 text encoder (prefill only; model/text_encoder/gemma3.py).  Additive entries: the DiT / VAE ABI above is unchanged.
+ * Gemma runs on the bfloat16 build for both compute dtypes (the reference runs it in fp32; fp16 overflows, scripts/generate.py:376-378).
+ * Causal / sliding-window / non-causal GQA flash attention at head_dim 256 (gemma3.py:186-241, masks :362-382):
+ *   out[q, h*256:(h+1)*256] = softmax(scale * Q_h K_{h / (heads / kv_heads)}^T + mask) V_{h / (heads / kv_heads)}
+ * key j visible from query i when j < Tkv and, with causal != 0, j <= i and (window == 0 or i - j < window).  causal == 0: no mask at
+ * all (the reference's attention_mask=None); window must then be 0.  Q / K / V / out: bf16 row-major, query head h at columns h*256 of q,
+ * kv head g at columns g*256 of k and v; 16-byte aligned rows.  A query row that sees no key is written as zeros. */
+int ltx2_gemma_attn(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* out, int64_t ldo, int Tq,
+                    int Tkv, int heads, int kv_heads, int causal, int window, float scale, void* stream);
+/* In place on the fused QKV rows (q heads then kv heads, 256 wide, from column 0): per head y = rms_norm(x) * (1 + w) (w = q_w for the
+ * q heads, k_w for the k heads; fp32 [256]), then rotate-half RoPE with cos / sin fp32 [rows][128] (gemma3.py:117-138, :206-224). */
+int ltx2_gemma_qknorm_rope(void* qkv, int64_t ld, int rows, int q_heads, int kv_heads, const float* q_w, const float* k_w, float eps,
+                           const float* cos, const float* sin, void* stream);
+/* One row pass (gemma3.py:258-293): x = x_in + rms_norm(y) * (1 + w_post) (y NULL: x = x_in); n = rms_norm(x) * (1 + w_next);
+ * x_out (fp32) = x, h_out (bf16) = n, hf_out (fp32) = n -- each output may be NULL.  D % 4 == 0, D <= 8192. */
+int ltx2_gemma_resid_norm(const float* x_in, int64_t ldx, const void* y, int64_t ldy, const float* w_post, const float* w_next, float* x_out,
+                          int64_t ld_xout, void* h_out, int64_t ldh, float* hf_out, int64_t ldhf, int rows, int D, float eps, void* stream);
+/* out[r][i] = act(gu[r][i]) * gu[r][inter + i] (bf16; gate | up of one GEMM, gemma3.py:244-255); act 0 = silu (the reference),
+ * 1 = gelu_pytorch_tanh (the released checkpoints' hidden_activation).  inter % 8 == 0. */
+#define LTX2_GEMMA_ACT_SILU 0
+#define LTX2_GEMMA_ACT_GELU_TANH 1
+int ltx2_gemma_gated_act(const void* gu, int64_t ldgu, void* out, int64_t ldo, int rows, int inter, int act, void* stream);
+/* x[r][:] = fp32(table[ids[r]][:]) * scale (gemma3.py:312, :352); an id outside [0, vocab) gives a zero row.  D % 4 == 0. */
+int ltx2_gemma_embed(const int32_t* ids, int rows, const void* table, int vocab, int D, float scale, float* x, int64_t ldx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

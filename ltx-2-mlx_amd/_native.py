@@ -25,6 +25,7 @@ MODEL_VIDEO_ONLY, MODEL_AUDIO_VIDEO = 0, 1
 EPI_BF16, EPI_GELU_BF16, EPI_SILU_BF16, EPI_F32, EPI_RESID_GATE_F32, EPI_ADD_BF16 = range(6)
 ROUTE_SKINNY, ROUTE_V4_224, ROUTE_V4_256, ROUTE_V4_W8_224, ROUTE_V4_W8_256, ROUTE_V4_F8_224, ROUTE_V4_F8_256, ROUTE_PP, ROUTE_SMALL, ROUTE_NARROW = range(10)
 VAE_RES, VAE_UPSAMPLE = 0, 1
+GEMMA_ACT_SILU, GEMMA_ACT_GELU_TANH = 0, 1
 VAE_MAX_BLOCKS = 16
 
 vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_float
@@ -118,6 +119,12 @@ SIGNATURES = {
     "ltx2_vae_bind_workspace": (i32, [vp, vp, i64]),
     "ltx2_vae_decode": (i32, [vp, vp, i32, i32, i32, f32, vp, i32, vp, vp]),
     "ltx2_vae_out_frames": (i32, [vp, i32]),
+    # Gemma-3 text encoder (additive entries of ABI version 3)
+    "ltx2_gemma_attn": (i32, [vp, i64, vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, f32, vp]),
+    "ltx2_gemma_qknorm_rope": (i32, [vp, i64, i32, i32, i32, vp, vp, f32, vp, vp, vp]),
+    "ltx2_gemma_resid_norm": (i32, [vp, i64, vp, i64, vp, vp, vp, i64, vp, i64, vp, i64, i32, i32, f32, vp]),
+    "ltx2_gemma_gated_act": (i32, [vp, i64, vp, i64, i32, i32, i32, vp]),
+    "ltx2_gemma_embed": (i32, [vp, i32, vp, i32, i32, f32, vp, i64, vp]),
 }
 
 _libs: dict = {}

@@ -6,6 +6,7 @@
 #include "../../include/ltx2hip.h"
 #include "attention.h"
 #include "gemm.h"
+#include "gemma.h"
 #include "rowops.h"
 
 static thread_local char g_err[512] = "";
@@ -491,6 +492,31 @@ int ltx2_tile_blend_finish(float* out, const float* wsum, int64_t plane, void* s
 int ltx2_video_to_uint8(const float* video, uint8_t* frames, int T, int H, int W, void* stream) {
     LTX2_CHECK_ARG(video && frames, "video_to_uint8: null operand");
     return video_to_uint8_launch(video, frames, T, H, W, (hipStream_t)stream);
+}
+
+int ltx2_gemma_attn(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* out, int64_t ldo, int Tq,
+                    int Tkv, int heads, int kv_heads, int causal, int window, float scale, void* stream) {
+    return gemma_attn_launch((const bf16*)q, (long)ldq, (const bf16*)k, (long)ldk, (const bf16*)v, (long)ldv, (bf16*)out, (long)ldo, Tq, Tkv,
+                             heads, kv_heads, causal, window, scale, (hipStream_t)stream);
+}
+
+int ltx2_gemma_qknorm_rope(void* qkv, int64_t ld, int rows, int q_heads, int kv_heads, const float* q_w, const float* k_w, float eps,
+                           const float* cos, const float* sin, void* stream) {
+    return gemma_qknorm_rope_launch((bf16*)qkv, (long)ld, rows, q_heads, kv_heads, q_w, k_w, eps, cos, sin, (hipStream_t)stream);
+}
+
+int ltx2_gemma_resid_norm(const float* x_in, int64_t ldx, const void* y, int64_t ldy, const float* w_post, const float* w_next, float* x_out,
+                          int64_t ld_xout, void* h_out, int64_t ldh, float* hf_out, int64_t ldhf, int rows, int D, float eps, void* stream) {
+    return gemma_resid_norm_launch(x_in, (long)ldx, (const bf16*)y, (long)ldy, w_post, w_next, x_out, (long)ld_xout, (bf16*)h_out, (long)ldh,
+                                   hf_out, (long)ldhf, rows, D, eps, (hipStream_t)stream);
+}
+
+int ltx2_gemma_gated_act(const void* gu, int64_t ldgu, void* out, int64_t ldo, int rows, int inter, int act, void* stream) {
+    return gemma_gated_act_launch((const bf16*)gu, (long)ldgu, (bf16*)out, (long)ldo, rows, inter, act, (hipStream_t)stream);
+}
+
+int ltx2_gemma_embed(const int32_t* ids, int rows, const void* table, int vocab, int D, float scale, float* x, int64_t ldx, void* stream) {
+    return gemma_embed_launch((const int*)ids, rows, (const bf16*)table, vocab, D, scale, x, (long)ldx, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -539,3 +539,68 @@ def video_to_uint8(video: torch.Tensor) -> torch.Tensor:
     out = torch.empty(T, H, W, 3, device=video.device, dtype=torch.uint8)
     nv.check(nv.lib().ltx2_video_to_uint8(nv.ptr(video), nv.ptr(out), T, H, W, nv.stream()))
     return out
+
+
+# ---------------------------------------------------------------------------------------------- Gemma-3 text encoder (gemma.hip)
+# Gemma always runs on the bfloat16 build (model/text_encoder/gemma3.py), whatever the DiT's compute dtype.
+
+def gemma_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, kv_heads: int, causal: bool = True, window: int = 0,
+               scale: Optional[float] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """q [Tq, >= heads*256], k / v [Tkv, >= kv_heads*256] bf16 (row-strided column views of the fused QKV rows are fine) ->
+    out [Tq, heads*256] bf16: causal (window > 0: sliding) or, causal=False, unmasked GQA attention at head_dim 256."""
+    assert q.dtype == BF16 and k.dtype == BF16 and v.dtype == BF16 and q.stride(1) == 1 and k.stride(1) == 1 and v.stride(1) == 1
+    tq, tkv = q.shape[0], k.shape[0]
+    if out is None:
+        out = torch.empty(tq, heads * 256, device=q.device, dtype=BF16)
+    if scale is None:
+        scale = 256 ** -0.5
+    nv.check(nv.lib().ltx2_gemma_attn(nv.ptr(q), q.stride(0), nv.ptr(k), k.stride(0), nv.ptr(v), v.stride(0), nv.ptr(out), out.stride(0),
+                                      tq, tkv, heads, kv_heads, int(bool(causal)), int(window), float(scale), nv.stream()))
+    return out
+
+
+def gemma_qknorm_rope_(qkv: torch.Tensor, q_heads: int, kv_heads: int, q_w: torch.Tensor, k_w: torch.Tensor, cos: torch.Tensor,
+                       sin: torch.Tensor, eps: float = 1e-6) -> torch.Tensor:
+    """In place on the fused QKV rows [T, >= (q_heads + kv_heads)*256] bf16: per-head RMSNorm(1 + w) then rotate-half RoPE
+    (cos / sin fp32 [T, 128]); the V columns are not touched."""
+    assert qkv.dtype == BF16 and qkv.stride(1) == 1 and cos.dtype == torch.float32 and sin.dtype == torch.float32
+    assert cos.shape == (qkv.shape[0], 128) and sin.shape == cos.shape and cos.is_contiguous() and sin.is_contiguous()
+    nv.check(nv.lib().ltx2_gemma_qknorm_rope(nv.ptr(qkv), qkv.stride(0), qkv.shape[0], q_heads, kv_heads, nv.ptr(_c(q_w.float())),
+                                             nv.ptr(_c(k_w.float())), float(eps), nv.ptr(cos), nv.ptr(sin), nv.stream()))
+    return qkv
+
+
+def gemma_resid_norm(x_in: torch.Tensor, y: Optional[torch.Tensor], w_post: Optional[torch.Tensor], w_next: Optional[torch.Tensor],
+                     x_out: Optional[torch.Tensor] = None, h_out: Optional[torch.Tensor] = None, hf_out: Optional[torch.Tensor] = None,
+                     eps: float = 1e-6) -> None:
+    """x = x_in + rms_norm(y) * (1 + w_post) (y None: x = x_in); n = rms_norm(x) * (1 + w_next); writes x_out (fp32) = x,
+    h_out (bf16) = n, hf_out (fp32) = n -- whichever are given."""
+    assert x_in.dtype == torch.float32 and x_in.stride(1) == 1
+    rows, d = x_in.shape
+    for t in (x_out, hf_out):
+        assert t is None or (t.dtype == torch.float32 and t.shape == (rows, d) and t.stride(1) == 1)
+    assert h_out is None or (h_out.dtype == BF16 and h_out.shape == (rows, d) and h_out.stride(1) == 1)
+    assert y is None or (y.dtype == BF16 and y.shape == (rows, d) and y.stride(1) == 1)
+    nv.check(nv.lib().ltx2_gemma_resid_norm(nv.ptr(x_in), x_in.stride(0), nv.ptr(y), y.stride(0) if y is not None else 0, nv.ptr(w_post),
+                                            nv.ptr(w_next), nv.ptr(x_out), x_out.stride(0) if x_out is not None else 0, nv.ptr(h_out),
+                                            h_out.stride(0) if h_out is not None else 0, nv.ptr(hf_out),
+                                            hf_out.stride(0) if hf_out is not None else 0, rows, d, float(eps), nv.stream()))
+
+
+def gemma_gated_act(gu: torch.Tensor, inter: int, act: int = nv.GEMMA_ACT_SILU, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gu [rows, >= 2*inter] bf16 (gate columns [0, inter), up columns [inter, 2*inter)) -> act(gate) * up, bf16 [rows, inter]."""
+    assert gu.dtype == BF16 and gu.stride(1) == 1
+    if out is None:
+        out = torch.empty(gu.shape[0], inter, device=gu.device, dtype=BF16)
+    nv.check(nv.lib().ltx2_gemma_gated_act(nv.ptr(gu), gu.stride(0), nv.ptr(out), out.stride(0), gu.shape[0], inter, int(act), nv.stream()))
+    return out
+
+
+def gemma_embed(ids: torch.Tensor, table: torch.Tensor, scale: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ids int32 [rows] -> fp32 [rows, D] = table[ids] * scale (table bf16 [vocab, D])."""
+    assert table.dtype == BF16 and table.is_contiguous() and ids.dtype == torch.int32 and ids.is_contiguous()
+    vocab, d = table.shape
+    if out is None:
+        out = torch.empty(ids.shape[0], d, device=table.device, dtype=torch.float32)
+    nv.check(nv.lib().ltx2_gemma_embed(nv.ptr(ids), ids.shape[0], nv.ptr(table), vocab, d, float(scale), nv.ptr(out), out.stride(0), nv.stream()))
+    return out

@@ -1,6 +1,6 @@
 """Text-side per-prompt path behind the reference's API (LTX_2_MLX/model/text_encoder/encoder.py:13-32 output records,
 :65-253 VideoGemmaTextEncoderModel, :255-370 AudioVideoGemmaTextEncoderModel, :373-413 create_text_encoder,
-:415-560 load_text_encoder_weights).  Gemma itself is outside this build: the entry points take its hidden states
+:415-560 load_text_encoder_weights).  Gemma itself is gemma3.py; the entry points here take its hidden states
 (`encode_from_hidden_states`) or already-projected features (`encode_projected`).  The caption projection
 3840 -> 4096 stays in the transformer (`ltx2_dit_prepare`), as in the reference."""
 from __future__ import annotations

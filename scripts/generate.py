@@ -4,11 +4,13 @@
 Keeps the flag names and `generate_video(...)` keyword names of the reference's
 scripts/generate.py (argparse block :2364-2641, `generate_video` :933-997) for this path:
 standard single-stage distilled loop (reference :1764-1984) followed by `decode_latent` (:2080-2091).
-Out of this path (and rejected with a clear message): Gemma text encoding, audio VAE / vocoder / muxing, CFG/STG guidance.
+Gemma-3 encodes the prompt on the GPU when `--gemma-path` holds its weights (model/text_encoder/gemma3.py; reference
+encode_with_gemma :340-486, encode_av_gemma_batch :511-640).  Out of this path (and rejected with a clear message): audio VAE /
+vocoder / muxing, STG guidance, CFG in the video-only loop.
 `--pipeline distilled --spatial-upscaler-weights W` runs the two-stage DistilledPipeline; adding `--generate-audio` runs it on
 the AudioVideo transformer and saves the audio LATENT beside the frames.
 `save_video` keeps the reference's ffmpeg settings (frames piped as raw RGB; PNG frames when no ffmpeg binary exists).  `--lora` fuses an adapter into the checkpoint weights at load.  `--image` conditions latent frame 0 on an image through the VAE encoder (the reference
-routes that through its pipelines, scripts/generate.py:1711-1731).  Text embeddings come from `--embedding file.npz` (keys
+routes that through its pipelines, scripts/generate.py:1711-1731).  Without Gemma weights, text embeddings come from `--embedding file.npz` (keys
 `embedding`, `attention_mask`, as the reference's `load_text_embedding` :730-750) or the reference's
 dummy encoder (`--no-gemma`, :642-661).  Frames are written as `<output>.npz` (uint8 T,H,W,3) and
 the final latent as `<output>_latent.npz` like the reference (:1994-1996).
@@ -118,6 +120,110 @@ def encode_text_features(path: str, weights_path=None, device="cuda", seed: int 
         mask = torch.ones(feats.shape[:2]) if mask is None else mask
         out = enc.encode_projected(feats.to(device), mask.to(device))
     return out.video_encoding, out.attention_mask.float()
+
+
+def _gemma_text_encoder(gemma_cfg, ltx_weights_path, device, seed: int = 0, audio_video: bool = False):
+    """Feature extractor + connector(s) for a Gemma of `gemma_cfg`: from the LTX checkpoint when given (its text_embedding_projection must
+    take (hidden, layers + 1) hidden states: raises naming both shapes otherwise), else randomly initialised at that size."""
+    import math
+    from ltx_2_mlx_amd.model.text_encoder import (AudioVideoGemmaTextEncoderModel, Embeddings1DConnector, GemmaFeaturesExtractorProjLinear,
+                                                  VideoGemmaTextEncoderModel, load_text_encoder_weights)
+    hidden, nl = gemma_cfg.hidden_size, gemma_cfg.num_hidden_layers + 1
+    fe = GemmaFeaturesExtractorProjLinear(hidden_dim=hidden, num_layers=nl, device=device)
+    conns = [Embeddings1DConnector(device=device) for _ in range(2 if audio_video else 1)]
+    enc = AudioVideoGemmaTextEncoderModel(fe, conns[0], conns[1]) if audio_video else VideoGemmaTextEncoderModel(fe, conns[0])
+    if ltx_weights_path:
+        from safetensors import safe_open
+        with safe_open(ltx_weights_path, framework="pt") as f:
+            key = "text_embedding_projection.aggregate_embed.weight"
+            have = tuple(f.get_slice(key).get_shape()) if key in f.keys() else None
+        if have is not None and have != (hidden, hidden * nl):
+            raise ValueError(f"the Gemma at hand gives (hidden, layers + 1) = {(hidden, nl)}, i.e. a text_embedding_projection of "
+                             f"{(hidden, hidden * nl)}, but the LTX checkpoint's is {have}")
+        load_text_encoder_weights(enc, ltx_weights_path)
+    else:
+        g = torch.Generator().manual_seed(seed)
+        fe.load_state_dict({"aggregate_embed.weight": torch.randn(hidden, hidden * nl, generator=g) / math.sqrt(hidden * nl)})
+        for i, c in enumerate(conns):
+            c.init_random_weights(seed + 1 + i)
+    return enc
+
+
+def _load_gemma(gemma_path: str, device):
+    from ltx_2_mlx_amd.model.text_encoder.gemma3 import create_gemma3_model, load_gemma_tokenizer
+    print(f"  Loading tokenizer from {gemma_path}...")
+    tokenizer = load_gemma_tokenizer(gemma_path)
+    print("  Loading Gemma 3 model (bfloat16 operands, fp32 residual stream)...")
+    t0 = time.time()
+    gemma = create_gemma3_model(gemma_path, device=device)
+    torch.cuda.synchronize()
+    print(f"  Gemma 3: {gemma.config.num_hidden_layers} layers x {gemma.config.hidden_size} loaded in {time.time() - t0:.1f} s")
+    return tokenizer, gemma
+
+
+def _gemma_hidden_states(gemma, tokenizer, prompt: str, max_length: int, device):
+    from ltx_2_mlx_amd.model.text_encoder.gemma3 import tokenize_prompt
+    ids, mask = tokenize_prompt(tokenizer, prompt, max_length)       # raw prompt, left padding, truncation (reference :384-393)
+    num_tokens = int(mask.sum())
+    if num_tokens == 0:
+        raise ValueError(f"prompt {prompt!r} gives no tokens")
+    print(f"  Token count: {num_tokens}/{max_length}")
+    _, states = gemma(torch.from_numpy(ids), attention_mask=torch.from_numpy(mask))
+    return states, torch.from_numpy(mask).to(device)
+
+
+def _free_gemma(gemma):
+    """Free Gemma before the DiT loads (reference :631-640)."""
+    gemma.free()
+    import gc
+    gc.collect()
+    torch.cuda.empty_cache()
+
+
+def encode_with_gemma(prompt: str, gemma_path: str, ltx_weights_path, max_length: int = 1024, use_early_layers_only: bool = False, *,
+                      device="cuda", seed: int = 0):
+    """Gemma 3 + the LTX-2 text encoder (feature extractor + connector) for one prompt (reference scripts/generate.py:340-486).
+    Returns (embedding [1, T', 3840], attention_mask [1, T']).  Without `ltx_weights_path` (keyword-compatible None) the text encoder is
+    randomly initialised at the Gemma's size."""
+    tokenizer, gemma = _load_gemma(gemma_path, device)
+    try:
+        print("  Running Gemma 3 forward pass...")
+        states, mask = _gemma_hidden_states(gemma, tokenizer, prompt, max_length, device)
+        if use_early_layers_only:                   # reference :437-451: layer 0 (the scaled embeddings), padding zeroed
+            return states[0] * mask[:, :, None].float(), mask.to(torch.int32)
+        enc = _gemma_text_encoder(gemma.config, ltx_weights_path, device, seed)
+        out = enc.encode_from_hidden_states(states, mask, padding_side="left")
+        return out.video_encoding, out.attention_mask
+    finally:
+        _free_gemma(gemma)
+
+
+def encode_av_gemma_batch(prompts: list, gemma_path: str, ltx_weights_path, max_length: int = 1024, *, device="cuda", seed: int = 0) -> list:
+    """Several prompts under ONE Gemma load with the AudioVideo text encoder (reference scripts/generate.py:511-640): the hidden states are
+    trimmed to the real tokens, later prompts are tokenised with max_length = the first encoding's length.  Returns
+    [(video_encoding, audio_encoding, attention_mask), ...]."""
+    if ltx_weights_path and is_v2_model(ltx_weights_path):
+        raise NotImplementedError("Gemma encoding for LTX-2.3 checkpoints (the V2 feature extractor and 8-layer connectors) is not built: "
+                                  "pass embedding_path with `embedding` / `audio_embedding` arrays")
+    tokenizer, gemma = _load_gemma(gemma_path, device)
+    try:
+        enc = _gemma_text_encoder(gemma.config, ltx_weights_path, device, seed, audio_video=True)
+        results = []
+        for i, prompt in enumerate(prompts):
+            print(f"  Running Gemma 3 forward pass (prompt {i + 1}/{len(prompts)})...")
+            states, mask = _gemma_hidden_states(gemma, tokenizer, prompt, max_length, device)
+            n, t = int(mask.sum()), mask.shape[1]
+            if n < t:                               # left padding: the real tokens are the last n (reference :587-595)
+                states = [h[:, -n:] for h in states]
+                mask = mask[:, -n:]
+            out = enc.encode_from_hidden_states(states, mask, padding_side="left")
+            results.append((out.video_encoding, out.audio_encoding, out.attention_mask))
+            del states
+            if i == 0:
+                max_length = out.video_encoding.shape[1]
+        return results
+    finally:
+        _free_gemma(gemma)
 
 
 def _read_checkpoint_config(checkpoint_path: str) -> dict:
@@ -355,7 +461,11 @@ def generate_video(
     given = dict(upscale_temporal=upscale_temporal, early_layers_only=early_layers_only,
                  enhance_prompt_flag=enhance_prompt_flag and use_gemma, cross_attn_scale=cross_attn_scale, distilled_lora=distilled_lora,
                  stg_scale=stg_scale, apg_scale=apg_scale, control_video=control_video, save_control=save_control, ge_gamma=ge_gamma,
-                 keyframes=keyframes, ic_lora_weights=ic_lora_weights, negative_prompt=negative_prompt)
+                 keyframes=keyframes, ic_lora_weights=ic_lora_weights)
+    # Gemma encodes the prompt (and the negative prompt) when its weights are there and no pre-computed encoding is given
+    gemma_encodes = bool(use_gemma and not (embedding_path or text_features_path) and gemma_path and os.path.exists(gemma_path))
+    if negative_prompt is not None and not gemma_encodes:
+        given["negative_prompt"] = negative_prompt
     for k, v in given.items():
         if v != _OUT_OF_PATH_DEFAULTS[k]:
             raise NotImplementedError(f"{k}={v!r} is outside the MI355X hot path (see DESIGN.md); leave it at its default {_OUT_OF_PATH_DEFAULTS[k]!r}")
@@ -388,7 +498,6 @@ def generate_video(
             print(f"\n  ERROR: Gemma weights not found at {gemma_path}\n  Use use_gemma=False (--no-gemma) for dummy embeddings, or pass "
                   f"embedding_path / text_features_path")
             return None
-        raise NotImplementedError("Gemma-3 text encoding is outside the hot path: pass embedding_path / text_features_path (or use_gemma=False)")
     if model_variant == "distilled" and cfg_scale > 1.2:
         print(f"  WARNING: Distilled model requires CFG=1.0 (no guidance). You requested {cfg_scale}.\n  Forcing CFG=1.0 (reference :1207-1216).")
         cfg_scale, guidance_rescale, audio_cfg_scale, rescale_scale = 1.0, 0.0, 1.0, 0.0
@@ -414,10 +523,10 @@ def generate_video(
     if _need_cfg and not _av_branch:
         raise NotImplementedError(f"cfg_scale={cfg_scale}: classifier-free guidance is built in OneStagePipeline (the AudioVideo / LTX-2.3 branch); the "
                                   "standard video-only loop of this script runs the distilled model's cfg = 1")
-    if _need_cfg and (negative_encoding is None or negative_audio_encoding is None):
-        raise NotImplementedError(f"cfg_scale={cfg_scale} / audio_cfg_scale={audio_cfg_scale}: classifier-free guidance needs the NEGATIVE prompt's encodings and the text "
-                                  "encoder is outside this build: add `negative_embedding` and `negative_audio_embedding` arrays to the --embedding file, or pass "
-                                  "cfg_scale=1.0, audio_cfg_scale=1.0 (what --model-variant distilled does)")
+    if _need_cfg and not gemma_encodes and (negative_encoding is None or negative_audio_encoding is None):
+        raise NotImplementedError(f"cfg_scale={cfg_scale} / audio_cfg_scale={audio_cfg_scale}: classifier-free guidance needs the NEGATIVE prompt's encodings: "
+                                  "let Gemma encode the prompts (gemma_path), add `negative_embedding` and `negative_audio_embedding` arrays to the --embedding "
+                                  "file, or pass cfg_scale=1.0, audio_cfg_scale=1.0 (what --model-variant distilled does)")
     if low_memory or fast_mode:
         print("  low_memory / fast_mode: no effect here (weights and caches stay resident in HBM, the loop is one hipGraph)")
     have_ckpt = bool(weights_path) and os.path.exists(weights_path)
@@ -433,6 +542,20 @@ def generate_video(
     text_audio_encoding = None
     if text_features_path:
         text_encoding, _ = encode_text_features(text_features_path, weights_path if have_ckpt else None, device, seed)
+    elif gemma_encodes and use_av_encoder:
+        if v2:
+            raise NotImplementedError("Gemma encoding for LTX-2.3 (the V2 feature extractor and 8-layer connectors) is not built: pass embedding_path "
+                                      "with `embedding` / `audio_embedding` arrays")
+        # prompt AND negative prompt under one Gemma load (reference :1096-1116); Gemma is freed before the transformer loads
+        results = encode_av_gemma_batch([prompt, negative_prompt or ""], gemma_path, weights_path if have_ckpt else None, device=device,
+                                        seed=seed)
+        text_encoding, text_audio_encoding, _ = results[0]
+        negative_encoding, negative_audio_encoding, _ = results[1]
+        print("  Encoded both prompts with Gemma 3 (AudioVideo, single load)")
+    elif gemma_encodes:
+        text_encoding, _ = encode_with_gemma(prompt, gemma_path, weights_path if have_ckpt else None, use_early_layers_only=early_layers_only,
+                                             device=device, seed=seed)
+        print("  Encoded with Gemma 3")
     elif embedding_path:
         text_encoding, _ = load_text_embedding(embedding_path, device)
         z = np.load(embedding_path)
