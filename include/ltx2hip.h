@@ -492,6 +492,40 @@ int ltx2_gemma_gated_act(const void* gu, int64_t ldgu, void* out, int64_t ldo, i
 /* x[r][:] = fp32(table[ids[r]][:]) * scale (gemma3.py:312, :352); an id outside [0, vocab) gives a zero row.  D % 4 == 0. */
 int ltx2_gemma_embed(const int32_t* ids, int rows, const void* table, int vocab, int D, float scale, float* x, int64_t ldx, void* stream);
 
+/* ---- audio VAE decoder / vocoder (model/audio_vae/: AudioDecoder, Vocoder, VocoderWithBWE).  Additive entries; fp32 end to end
+ * (operands, accumulation, activations), the same code in both builds.  Tensors are channels-last fp32: one row of C channels per time
+ * step (1-D) or per (h, w) pixel (2-D, h-major); ld* are row strides in elements.
+ * Convolution on the exact-f32 MFMA, M = h_out * w_out positions, N = c_out, K = kh * kw * c_in:
+ *   y[p][n] = act(alpha * (bias[n] + res[p][n] + sum_{i,j,c} pro(x[src(p,i,j)][c]) * w[(i*kw + j)*c_in + c][n]) + beta * y[p][n])
+ * p = (h, w) reads row h + upsample - pad_h + i and column w*stride + j*dilation - pad_w (zero outside the input); upsample != 0 reads
+ * the nearest x2 image of x and drops the first output row (Upsample2d, decoder.py:223-244).  w: [K][ldw], ldw % 4 == 0, ldw >= c_out,
+ * 16-byte aligned.  bias / res may be NULL; res may alias y.  1-D: h_in = h_out = kh = 1, pad_h = 0. */
+#define LTX2_AUDIO_PRO_NONE 0
+#define LTX2_AUDIO_PRO_LEAKY_RELU 1      /* v < 0 ? slope * v : v, on the operand as it is staged */
+#define LTX2_AUDIO_PRO_MAGNITUDE 2       /* sqrt(x[c]^2 + x[c + c_in]^2): |STFT| from its real | imaginary halves (ldx >= 2 c_in) */
+#define LTX2_AUDIO_ACT_NONE 0
+#define LTX2_AUDIO_ACT_TANH 1
+#define LTX2_AUDIO_ACT_CLIP 2            /* clip(v, -1, 1) */
+#define LTX2_AUDIO_ACT_LOG 3             /* log(max(v, 1e-5)) */
+int ltx2_audio_conv(const float* x, int64_t ldx, int h_in, int w_in, int c_in, const float* w, int64_t ldw, const float* bias, float* y,
+                    int64_t ldy, int h_out, int w_out, int c_out, int kh, int kw, int stride, int dilation, int pad_h, int pad_w, int upsample,
+                    int prologue, float slope, const float* res, int64_t ldres, float alpha, float beta, int act, void* stream);
+/* ConvTranspose1d(stride = rate, padding) as `rate` polyphase convolutions (vocoder.py:66-116); output length t_out.  w_phase:
+ * [rate][ceil(k / rate)][c_in][round_up(c_out, 4)], phase ph = (o + padding) % rate, tap t = kernel index ph + rate * (ntaps - 1 - t)
+ * (zero past k).  prologue: NONE or LEAKY_RELU. */
+int ltx2_audio_conv_transpose1d(const float* x, int64_t ldx, int t_in, int c_in, const float* w_phase, const float* bias, float* y, int64_t ldy,
+                                int t_out, int c_out, int k, int rate, int padding, int prologue, float slope, void* stream);
+/* y[r][:] = silu(x[r][:] / sqrt(mean(x[r][:]^2) + eps)): PixelNorm + SiLU (decoder.py:29-55).  c % 4 == 0, 16-byte aligned rows. */
+int ltx2_audio_pixnorm_silu(const float* x, int64_t ldx, float* y, int64_t ldy, int64_t rows, int c, float eps, void* stream);
+/* Activation1d(SnakeBeta) in one pass (vocoder.py:162-412): replicate pad, x2 upsample with up_filter, x + sin(x e^alpha)^2 / (e^beta + 1e-9),
+ * replicate pad, low-pass with down_filter, decimate by 2.  [t][c] -> [t][c], out of place.  up_k even, up_k and down_k <= 16. */
+int ltx2_audio_snake_aa(const float* x, int64_t ldx, int t, int c, const float* alpha, const float* beta, const float* up_filter, int up_k,
+                        const float* down_filter, int down_k, float* y, int64_t ldy, void* stream);
+/* UpSample1d (vocoder.py:304-367): y[u][c] = ratio * sum_k f[k] x[clamp((u + pad_left - k) / ratio - pad, 0, t_in - 1)][c] over the k with
+ * (u + pad_left - k) % ratio == 0, u < t_out.  Out of place. */
+int ltx2_audio_upsample(const float* x, int64_t ldx, int t_in, int c, const float* filter, int k, int ratio, int pad, int pad_left, float* y,
+                        int64_t ldy, int t_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,8 @@ EPI_BF16, EPI_GELU_BF16, EPI_SILU_BF16, EPI_F32, EPI_RESID_GATE_F32, EPI_ADD_BF1
 ROUTE_SKINNY, ROUTE_V4_224, ROUTE_V4_256, ROUTE_V4_W8_224, ROUTE_V4_W8_256, ROUTE_V4_F8_224, ROUTE_V4_F8_256, ROUTE_PP, ROUTE_SMALL, ROUTE_NARROW = range(10)
 VAE_RES, VAE_UPSAMPLE = 0, 1
 GEMMA_ACT_SILU, GEMMA_ACT_GELU_TANH = 0, 1
+AUDIO_PRO_NONE, AUDIO_PRO_LEAKY_RELU, AUDIO_PRO_MAGNITUDE = 0, 1, 2
+AUDIO_ACT_NONE, AUDIO_ACT_TANH, AUDIO_ACT_CLIP, AUDIO_ACT_LOG = 0, 1, 2, 3
 VAE_MAX_BLOCKS = 16
 
 vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_float
@@ -125,6 +127,13 @@ SIGNATURES = {
     "ltx2_gemma_resid_norm": (i32, [vp, i64, vp, i64, vp, vp, vp, i64, vp, i64, vp, i64, i32, i32, f32, vp]),
     "ltx2_gemma_gated_act": (i32, [vp, i64, vp, i64, i32, i32, i32, vp]),
     "ltx2_gemma_embed": (i32, [vp, i32, vp, i32, i32, f32, vp, i64, vp]),
+    # audio VAE decoder / vocoder (additive entries of ABI version 3; fp32)
+    "ltx2_audio_conv": (i32, [vp, i64, i32, i32, i32, vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp, i64,
+                              f32, f32, i32, vp]),
+    "ltx2_audio_conv_transpose1d": (i32, [vp, i64, i32, i32, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, f32, vp]),
+    "ltx2_audio_pixnorm_silu": (i32, [vp, i64, vp, i64, i64, i32, f32, vp]),
+    "ltx2_audio_snake_aa": (i32, [vp, i64, i32, i32, vp, vp, vp, i32, vp, i32, vp, i64, vp]),
+    "ltx2_audio_upsample": (i32, [vp, i64, i32, i32, vp, i32, i32, i32, i32, vp, i64, i32, vp]),
 }
 
 _libs: dict = {}

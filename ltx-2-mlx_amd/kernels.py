@@ -604,3 +604,122 @@ def gemma_embed(ids: torch.Tensor, table: torch.Tensor, scale: float, out: Optio
         out = torch.empty(ids.shape[0], d, device=table.device, dtype=torch.float32)
     nv.check(nv.lib().ltx2_gemma_embed(nv.ptr(ids), ids.shape[0], nv.ptr(table), vocab, d, float(scale), nv.ptr(out), out.stride(0), nv.stream()))
     return out
+
+
+# ---- audio VAE decoder / vocoder (fp32, csrc/audio.hip).  Channels-last fp32 tensors: [T, C] (1-D) or [H, W, C] (2-D); the row stride is
+# the stride of the position dimension.  Weights come packed by pack_conv_weight / pack_conv_transpose_weight.
+
+def _f32(*ts):
+    for t in ts:
+        assert t is None or (t.dtype == torch.float32 and t.is_cuda and t.stride(-1) == 1), "audio kernels take CUDA fp32 tensors with unit channel stride"
+
+
+def pack_conv_weight(w: torch.Tensor) -> torch.Tensor:
+    """PyTorch conv weight (out, in, k) or (out, in, kh, kw) -> fp32 [kh * kw * in, round_up(out, 4)] (k = (i * kw + j) * in + c)."""
+    w = w.float()
+    if w.dim() == 3:
+        w = w[:, :, None, :]
+    cout, cin, kh, kw = w.shape
+    packed = torch.zeros(kh * kw * cin, (cout + 3) // 4 * 4, device=w.device, dtype=torch.float32)
+    packed[:, :cout] = w.permute(2, 3, 1, 0).reshape(kh * kw * cin, cout)
+    return packed
+
+
+def pack_conv_transpose_weight(w: torch.Tensor, rate: int) -> torch.Tensor:
+    """PyTorch ConvTranspose1d weight (in, out, k) -> the polyphase layout [rate][ceil(k / rate)][in][round_up(out, 4)]:
+    phase ph, tap t holds kernel index ph + rate * (ntaps - 1 - t) (zero past k)."""
+    w = w.float()
+    cin, cout, k = w.shape
+    ntaps = (k + rate - 1) // rate
+    packed = torch.zeros(rate, ntaps, cin, (cout + 3) // 4 * 4, device=w.device, dtype=torch.float32)
+    for ph in range(rate):
+        for t in range(ntaps):
+            j = ph + rate * (ntaps - 1 - t)
+            if j < k:
+                packed[ph, t, :, :cout] = w[:, :, j]
+    return packed
+
+
+def audio_conv1d(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], c_out: int, k: int, *, stride: int = 1, dilation: int = 1,
+                 padding: int = 0, t_out: Optional[int] = None, out: Optional[torch.Tensor] = None, prologue: int = nv.AUDIO_PRO_NONE,
+                 slope: float = 0.0, res: Optional[torch.Tensor] = None, alpha: float = 1.0, beta: float = 0.0, act: int = nv.AUDIO_ACT_NONE,
+                 c_in: Optional[int] = None) -> torch.Tensor:
+    """x [T, >= C_in] -> out [T_out, c_out]: zero-padded (left `padding`) conv1d with the packed weight w [k * C_in, ldw] and the fused
+    prologue / epilogue of ltx2_audio_conv.  T_out defaults to the usual (T + 2 padding - dilation (k - 1) - 1) // stride + 1."""
+    c_in = x.shape[1] if c_in is None else c_in
+    T = x.shape[0]
+    if t_out is None:
+        t_out = (T + 2 * padding - dilation * (k - 1) - 1) // stride + 1
+    if out is None:
+        out = torch.empty(t_out, c_out, device=x.device, dtype=torch.float32)
+    _f32(x, w, bias, out, res)
+    assert w.shape[0] == k * c_in and out.shape[0] >= t_out
+    nv.check(nv.lib().ltx2_audio_conv(nv.ptr(x), x.stride(0), 1, T, c_in, nv.ptr(w), w.stride(0), nv.ptr(bias), nv.ptr(out), out.stride(0), 1, t_out,
+                                      c_out, 1, k, stride, dilation, 0, padding, 0, int(prologue), float(slope), nv.ptr(res),
+                                      res.stride(0) if res is not None else 0, float(alpha), float(beta), int(act), nv.stream()))
+    return out
+
+
+def audio_conv2d(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], c_out: int, kh: int, kw: int, pad_h: int, pad_w: int, *,
+                 upsample: bool = False, out: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [H, W, C_in] -> out [H_out, W_out, c_out] (stride 1), padded as CausalConv2d pads (pad_h rows on top only, pad_w columns each
+    side): [H, W] for 3x3 / 1x1; upsample=True reads the nearest x2 image and drops the first output row (Upsample2d): [2H - 1, 2W]."""
+    H, W, c_in = x.shape
+    if upsample:
+        h_out, w_out = 2 * H + pad_h - kh, 2 * W + 2 * pad_w - kw + 1
+    else:
+        h_out, w_out = H + pad_h - kh + 1, W + 2 * pad_w - kw + 1
+    if out is None:
+        out = torch.empty(h_out, w_out, c_out, device=x.device, dtype=torch.float32)
+    assert x.is_contiguous() and out.is_contiguous() and (res is None or res.is_contiguous())
+    _f32(x, w, bias, out, res)
+    nv.check(nv.lib().ltx2_audio_conv(nv.ptr(x), c_in, H, W, c_in, nv.ptr(w), w.stride(0), nv.ptr(bias), nv.ptr(out), c_out, h_out, w_out, c_out,
+                                      kh, kw, 1, 1, pad_h, pad_w, 1 if upsample else 0, nv.AUDIO_PRO_NONE, 0.0, nv.ptr(res),
+                                      c_out if res is not None else 0, 1.0, 0.0, nv.AUDIO_ACT_NONE, nv.stream()))
+    return out
+
+
+def audio_conv_transpose1d(x: torch.Tensor, w_phase: torch.Tensor, bias: Optional[torch.Tensor], c_out: int, k: int, rate: int, padding: int,
+                           prologue: int = nv.AUDIO_PRO_NONE, slope: float = 0.0) -> torch.Tensor:
+    """ConvTranspose1d(stride=rate, padding) of x [T, C_in] -> [(T - 1) rate + k - 2 padding, c_out] through the polyphase kernel."""
+    T, c_in = x.shape
+    t_out = (T - 1) * rate + k - 2 * padding
+    out = torch.empty(t_out, c_out, device=x.device, dtype=torch.float32)
+    _f32(x, w_phase, bias, out)
+    assert w_phase.is_contiguous() and tuple(w_phase.shape[:3]) == (rate, (k + rate - 1) // rate, c_in)
+    nv.check(nv.lib().ltx2_audio_conv_transpose1d(nv.ptr(x), x.stride(0), T, c_in, nv.ptr(w_phase), nv.ptr(bias), nv.ptr(out), out.stride(0), t_out,
+                                                  c_out, k, rate, padding, int(prologue), float(slope), nv.stream()))
+    return out
+
+
+def audio_pixnorm_silu(x: torch.Tensor, eps: float = 1e-6, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """silu(PixelNorm(x)) over the last dimension of a contiguous fp32 tensor."""
+    assert x.is_contiguous()
+    _f32(x)
+    c = x.shape[-1]
+    if out is None:
+        out = torch.empty_like(x)
+    nv.check(nv.lib().ltx2_audio_pixnorm_silu(nv.ptr(x), c, nv.ptr(out), c, x.numel() // c, c, float(eps), nv.stream()))
+    return out
+
+
+def audio_snake_aa(x: torch.Tensor, alpha: torch.Tensor, beta: torch.Tensor, up_filter: torch.Tensor, down_filter: torch.Tensor,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Activation1d(SnakeBeta) of x [T, C] (x2 up / down with the given filters) -> [T, C]."""
+    T, c = x.shape
+    if out is None:
+        out = torch.empty(T, c, device=x.device, dtype=torch.float32)
+    _f32(x, alpha, beta, up_filter, down_filter, out)
+    nv.check(nv.lib().ltx2_audio_snake_aa(nv.ptr(x), x.stride(0), T, c, nv.ptr(alpha), nv.ptr(beta), nv.ptr(up_filter), up_filter.numel(),
+                                          nv.ptr(down_filter), down_filter.numel(), nv.ptr(out), out.stride(0), nv.stream()))
+    return out
+
+
+def audio_upsample(x: torch.Tensor, filt: torch.Tensor, ratio: int, pad: int, pad_left: int, t_out: int) -> torch.Tensor:
+    """UpSample1d of x [T, C] -> [t_out, C]."""
+    T, c = x.shape
+    out = torch.empty(t_out, c, device=x.device, dtype=torch.float32)
+    _f32(x, filt, out)
+    nv.check(nv.lib().ltx2_audio_upsample(nv.ptr(x), x.stride(0), T, c, nv.ptr(filt), filt.numel(), ratio, pad, pad_left, nv.ptr(out), out.stride(0),
+                                          t_out, nv.stream()))
+    return out

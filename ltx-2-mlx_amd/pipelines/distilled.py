@@ -4,8 +4,8 @@ Mirrors reference LTX_2_MLX/pipelines/distilled.py:48-98 (DistilledConfig), :101
 (constructor), :198-272 (_denoise_loop_av, video branch) and :274-505 (__call__): stage 1 at half
 resolution with DISTILLED_SIGMA_VALUES (8 steps), optional latent 2x upscale + stage 2 with
 STAGE_2_DISTILLED_SIGMA_VALUES (3 steps), then VAE decode (tiled above 4000 latent voxels).
-The joint audio+video branch runs on AudioVideo transformers and returns the audio latent; audio VAE / vocoder
-decode is outside this path (scope table).  Image conditioning encodes the image with the VAE encoder
+The joint audio+video branch runs on AudioVideo transformers and returns the audio waveform when an audio_decoder and a
+vocoder are given (model/audio_vae/), the audio latent otherwise.  Image conditioning encodes the image with the VAE encoder
 and runs the per-token-sigma path of the DiT.
 """
 from __future__ import annotations
@@ -65,8 +65,8 @@ class DistilledPipeline:
         self.transformer = transformer if isinstance(transformer, X0Model) else X0Model(transformer)
         inner = self.transformer.velocity_model
         self.is_av_model = getattr(inner, "model_type", None) == LTXModelType.AudioVideo
-        if audio_decoder is not None or vocoder is not None:
-            raise NotImplementedError("audio VAE / vocoder decode is outside the MI355X hot path (the audio latent is returned)")
+        self.audio_decoder = audio_decoder
+        self.vocoder = vocoder
         self.video_encoder = video_encoder
         self.video_decoder = video_decoder
         self.spatial_upscaler = spatial_upscaler
@@ -99,8 +99,8 @@ class DistilledPipeline:
                  audio_encoding: Optional[torch.Tensor] = None, initial_noise: Optional[torch.Tensor] = None,
                  initial_audio_noise: Optional[torch.Tensor] = None, stage2_noise: Optional[torch.Tensor] = None):
         """Returns the decoded video (uint8 frames, or the final latent when no decoder is set); with
-        config.audio_enabled on an AudioVideo model, the tuple (video, audio_latent) -- the audio VAE / vocoder
-        that turn the (B, 8, T_a, 16) latent into a waveform are outside this path."""
+        config.audio_enabled on an AudioVideo model, the tuple (video, audio): the waveform (B, 2, samples) when both audio_decoder and
+        vocoder were given (the reference's _decode_audio, distilled.py:188-196), the (B, 8, T_a, 16) latent without them."""
         images = images or []
         dev = self.transformer.velocity_model.device
         gen = torch.Generator(device=dev).manual_seed(config.seed)
@@ -176,7 +176,16 @@ class DistilledPipeline:
                 video = torch.cat(chunks, dim=2) if len(chunks) > 1 else chunks[0]
             else:
                 video = decode_latent(final_latent, self.video_decoder)
+        if config.audio_enabled and audio_latent is not None:
+            audio = self._decode_audio(audio_latent)
+            return video, (audio if audio is not None else audio_latent)
         return (video, audio_latent) if config.audio_enabled else video
+
+    def _decode_audio(self, audio_latent: torch.Tensor) -> Optional[torch.Tensor]:
+        """Audio latent -> waveform (B, 2, samples) through the audio VAE decoder and the vocoder; None when either is missing."""
+        if self.audio_decoder is None or self.vocoder is None:
+            return None
+        return self.vocoder(self.audio_decoder(audio_latent))
 
 
 def create_distilled_pipeline(transformer, video_encoder, video_decoder, spatial_upscaler=None, audio_decoder=None, vocoder=None):

@@ -11,8 +11,9 @@ cfg_scale = audio_cfg_scale = 1, i.e. one transformer evaluation per step).
 Classifier-free guidance (round 3): `cfg_scale` / `audio_cfg_scale` != 1 evaluate the negative prompt too (a second engine context over the same
 weights) and combine the two predictions with CFGGuider or, for `rescale_scale > 0`, CFGStarRescalingGuider -- per modality, as :793-807.
 
-Outside the MI355X hot path, rejected with NotImplementedError: STG / APG guidance (`stg_scale`, `guider_override`), the Heun sampler, GE velocity correction, cross-attention scaling, the temporal upscaler, audio VAE /
-vocoder decode (with `audio_enabled` the audio LATENT is returned in place of the waveform).
+Outside the MI355X hot path, rejected with NotImplementedError: STG / APG guidance (`stg_scale`, `guider_override`), the Heun sampler, GE velocity correction, cross-attention scaling, the temporal upscaler.
+With `audio_enabled`, the audio waveform is returned when an audio_decoder and a vocoder are given (model/audio_vae/), the audio
+LATENT otherwise.
 """
 from __future__ import annotations
 
@@ -75,12 +76,10 @@ class OneStagePipeline:
         self.transformer = transformer if isinstance(transformer, X0Model) else X0Model(transformer)
         inner = self.transformer.velocity_model
         self.is_av_model = getattr(inner, "model_type", None) == LTXModelType.AudioVideo
-        if audio_decoder is not None or vocoder is not None:
-            raise NotImplementedError("audio VAE / vocoder decode is outside the MI355X hot path (the audio latent is returned)")
         self.video_encoder = video_encoder
         self.video_decoder = video_decoder
-        self.audio_decoder = None
-        self.vocoder = None
+        self.audio_decoder = audio_decoder
+        self.vocoder = vocoder
         self.patchifier = VideoLatentPatchifier(patch_size=1)
         self.audio_patchifier = AudioPatchifier(patch_size=1)
         self.diffusion_step = EulerDiffusionStep()
@@ -116,8 +115,9 @@ class OneStagePipeline:
                  ge_gamma: float = 0.0, sampler: str = "euler", temporal_upscaler=None, cross_attn_scale: float = 1.0,
                  cross_attn_start_block: int = 40, *, initial_noise: Optional[torch.Tensor] = None,
                  initial_audio_noise: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
-        """-> (video, audio): video uint8 frames (F, H, W, 3) (or the final latent when no decoder is set); audio = the audio
-        LATENT (B, 8, T_a, 16) when config.audio_enabled (the reference returns the vocoder's waveform), else None.
+        """-> (video, audio): video uint8 frames (F, H, W, 3) (or the final latent when no decoder is set); audio = the
+        waveform (B, 2, samples) when config.audio_enabled and both audio_decoder and vocoder were given (the reference's
+        _decode_audio), the audio LATENT (B, 8, T_a, 16) when config.audio_enabled without them, else None.
         The negative encodings are evaluated when a guider is enabled (cfg_scale / audio_cfg_scale != 1); unlike the reference
         (one_stage.py:776-780, which demands negative_audio_encoding whenever the audio branch runs) they may be None when no guider is.  initial_noise /
         initial_audio_noise (keyword-only, MI355X addition): supplied N(0,1) tensors of the patchified latent shapes, so
@@ -177,7 +177,16 @@ class OneStagePipeline:
         audio = None
         if config.audio_enabled and audio_state is not None:
             audio = audio_tools.unpatchify(audio_tools.clear_conditioning(audio_state)).latent
+            if self.audio_decoder is not None and self.vocoder is not None:
+                audio = self._decode_audio(audio)
         return video, audio
+
+    def _decode_audio(self, audio_latent: torch.Tensor) -> torch.Tensor:
+        """Audio latent (B, 8, T, 16) -> waveform (B, 2, samples) through the audio VAE decoder and the vocoder (reference
+        one_stage.py:184-205)."""
+        if self.audio_decoder is None or self.vocoder is None:
+            raise ValueError("Audio decoder and vocoder required for audio decoding")
+        return self.vocoder(self.audio_decoder(audio_latent))
 
 
 def create_one_stage_pipeline(transformer, video_encoder, video_decoder, audio_decoder=None, vocoder=None) -> OneStagePipeline:

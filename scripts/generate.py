@@ -5,10 +5,11 @@ Keeps the flag names and `generate_video(...)` keyword names of the reference's
 scripts/generate.py (argparse block :2364-2641, `generate_video` :933-997) for this path:
 standard single-stage distilled loop (reference :1764-1984) followed by `decode_latent` (:2080-2091).
 Gemma-3 encodes the prompt on the GPU when `--gemma-path` holds its weights (model/text_encoder/gemma3.py; reference
-encode_with_gemma :340-486, encode_av_gemma_batch :511-640).  Out of this path (and rejected with a clear message): audio VAE /
-vocoder / muxing, STG guidance, CFG in the video-only loop.
+encode_with_gemma :340-486, encode_av_gemma_batch :511-640).  Out of this path (and rejected with a clear message): STG guidance,
+CFG in the video-only loop.
 `--pipeline distilled --spatial-upscaler-weights W` runs the two-stage DistilledPipeline; adding `--generate-audio` runs it on
-the AudioVideo transformer and saves the audio LATENT beside the frames.
+the AudioVideo transformer and saves the audio LATENT beside the frames; `--decode-audio` (the default when the checkpoint holds the
+audio VAE decoder and vocoder) also decodes it to `<output>.wav` and muxes it into the mp4 (reference save_video_with_audio).
 `save_video` keeps the reference's ffmpeg settings (frames piped as raw RGB; PNG frames when no ffmpeg binary exists).  `--lora` fuses an adapter into the checkpoint weights at load.  `--image` conditions latent frame 0 on an image through the VAE encoder (the reference
 routes that through its pipelines, scripts/generate.py:1711-1731).  Without Gemma weights, text embeddings come from `--embedding file.npz` (keys
 `embedding`, `attention_mask`, as the reference's `load_text_embedding` :730-750) or the reference's
@@ -31,6 +32,67 @@ from ltx_2_mlx_amd.model.transformer import LTXModel, Modality, X0Model  # noqa:
 from ltx_2_mlx_amd.model.video_vae import SimpleVideoDecoder, TilingConfig, decode_latent, decode_tiled, load_vae_decoder_weights  # noqa: E402
 from ltx_2_mlx_amd.model.video_vae_encoder import SimpleVideoEncoder, load_vae_encoder_weights  # noqa: E402
 from ltx_2_mlx_amd.types import SpatioTemporalScaleFactors, VideoLatentShape  # noqa: E402
+
+
+def write_wav(path: str, waveform, sample_rate: int) -> str:
+    """waveform (B, 2, samples) or (2, samples) float in [-1, 1] -> 16-bit stereo PCM WAV of the first batch item, with the reference's
+    scaling (x 32767, clipped) and interleave (save_video_with_audio, :2270-2288)."""
+    import wave
+    a = waveform.float().cpu().numpy() if isinstance(waveform, torch.Tensor) else np.asarray(waveform, dtype=np.float32)
+    a = a[0] if a.ndim == 3 else a
+    pcm = (a * 32767).clip(-32768, 32767).astype(np.int16).T.flatten()
+    with wave.open(path, "wb") as f:
+        f.setnchannels(2)
+        f.setsampwidth(2)
+        f.setframerate(int(sample_rate))
+        f.writeframes(pcm.tobytes())
+    return path
+
+
+def audio_filters(speed: float = 1.0):
+    """The reference's atempo chain for a speed change (each stage within [0.5, 2.0], :2309-2320)."""
+    out, rem = [], speed
+    if speed != 1.0:
+        while rem > 2.0:
+            out.append("atempo=2.0")
+            rem /= 2.0
+        while rem < 0.5:
+            out.append("atempo=0.5")
+            rem /= 0.5
+        if rem != 1.0:
+            out.append(f"atempo={rem}")
+    return out
+
+
+def ffmpeg_av_command(width: int, height: int, wav_path: str, sample_rate: int, output_path: str, fps: int = 24, speed: float = 1.0):
+    """The reference's audio mux settings (:2323-2355: libx264 crf 18, aac 320k at the vocoder's rate, -shortest); the frames arrive as
+    raw RGB on stdin."""
+    cmd = ["ffmpeg", "-y", "-f", "rawvideo", "-pix_fmt", "rgb24", "-s", f"{width}x{height}", "-framerate", str(NATIVE_FPS), "-i", "-",
+           "-i", wav_path]
+    if video_filters(fps, speed):
+        cmd += ["-vf", ",".join(video_filters(fps, speed))]
+    if audio_filters(speed):
+        cmd += ["-af", ",".join(audio_filters(speed))]
+    return cmd + ["-c:v", "libx264", "-c:a", "aac", "-b:a", "320k", "-ar", str(sample_rate), "-pix_fmt", "yuv420p", "-crf", "18", "-shortest",
+                  "-loglevel", "error", output_path]
+
+
+def save_video_with_audio(frames, audio_waveform, output_path: str, audio_sample_rate: int, fps: int = 24, speed: float = 1.0):
+    """Writes `<output stem>.wav` (the reference's sidecar) and muxes it into output_path with ffmpeg; without an ffmpeg binary the
+    frames go to PNGs as in save_video and the .wav stays beside them.  Returns (video path or frames dir, wav path)."""
+    import shutil
+    import subprocess
+    wav_path = write_wav(os.path.splitext(output_path)[0] + ".wav", audio_waveform, audio_sample_rate)
+    n = (audio_waveform.shape[-1])
+    print(f"    Sidecar WAV: {wav_path} ({n} samples, {n / audio_sample_rate:.2f} s at {audio_sample_rate} Hz)")
+    if shutil.which("ffmpeg") is None:
+        return save_video(frames, output_path, fps=fps, speed=speed), wav_path
+    frames = np.ascontiguousarray(np.asarray(frames))
+    t, h, w, _ = frames.shape
+    result = subprocess.run(ffmpeg_av_command(w, h, wav_path, audio_sample_rate, output_path, fps, speed), input=frames.tobytes(), capture_output=True)
+    if result.returncode != 0:
+        raise RuntimeError(f"FFmpeg failed: {result.stderr.decode(errors='replace')}")
+    return output_path, wav_path
 
 
 def create_dummy_text_encoding(prompt: str, batch_size: int = 1, max_tokens: int = 256, embed_dim: int = 3840, device="cuda"):
@@ -236,6 +298,82 @@ def _read_checkpoint_config(checkpoint_path: str) -> dict:
         return json.loads(metadata.get("config", "{}"))
     except Exception:
         return {}
+
+
+def create_vocoder_for_checkpoint(checkpoint_path, compute_dtype=torch.float32, device="cuda") -> tuple:
+    """The plain HiFi-GAN Vocoder (LTX-2.0: no `bwe` in the metadata's vocoder config) or VocoderWithBWE (LTX-2.3), configured from
+    the checkpoint metadata as the reference's create_vocoder_for_checkpoint (:155-221).  Returns (vocoder, is_bwe)."""
+    from ltx_2_mlx_amd.model.audio_vae import MelSTFT, Vocoder, VocoderWithBWE
+    config = _read_checkpoint_config(checkpoint_path) if checkpoint_path and os.path.exists(checkpoint_path) else {}
+    vocoder_cfg = config.get("vocoder", {})
+    if "bwe" not in vocoder_cfg:
+        return Vocoder(compute_dtype=compute_dtype, device=device), False
+    inner_cfg = vocoder_cfg.get("vocoder", {})
+    bwe_cfg = vocoder_cfg["bwe"]
+    inner = Vocoder(
+        resblock_kernel_sizes=inner_cfg.get("resblock_kernel_sizes", [3, 7, 11]),
+        upsample_rates=inner_cfg.get("upsample_rates", [6, 5, 2, 2, 2]),
+        upsample_kernel_sizes=inner_cfg.get("upsample_kernel_sizes", [16, 15, 8, 4, 4]),
+        resblock_dilation_sizes=inner_cfg.get("resblock_dilation_sizes", [[1, 3, 5], [1, 3, 5], [1, 3, 5]]),
+        upsample_initial_channel=inner_cfg.get("upsample_initial_channel", 1024),
+        resblock=inner_cfg.get("resblock", "AMP1"),
+        output_sample_rate=bwe_cfg.get("input_sampling_rate", 24000),
+        activation=inner_cfg.get("activation", "snakebeta"),
+        use_tanh_at_final=inner_cfg.get("use_tanh_at_final", True),
+        compute_dtype=compute_dtype, device=device)
+    bwe = Vocoder(
+        resblock_kernel_sizes=bwe_cfg.get("resblock_kernel_sizes", [3, 7, 11]),
+        upsample_rates=bwe_cfg.get("upsample_rates", [2]),
+        upsample_kernel_sizes=bwe_cfg.get("upsample_kernel_sizes", [4]),
+        resblock_dilation_sizes=bwe_cfg.get("resblock_dilation_sizes", [[1, 3, 5], [1, 3, 5], [1, 3, 5]]),
+        upsample_initial_channel=bwe_cfg.get("upsample_initial_channel", 256),
+        resblock=bwe_cfg.get("resblock", "AMP1"),
+        output_sample_rate=bwe_cfg.get("output_sampling_rate", 48000),
+        activation=bwe_cfg.get("activation", "snakebeta"),
+        apply_final_activation=False,
+        use_tanh_at_final=bwe_cfg.get("use_tanh_at_final", True),
+        compute_dtype=compute_dtype, device=device)
+    mel_stft = MelSTFT(filter_length=bwe_cfg.get("n_fft", 2048), hop_length=bwe_cfg.get("hop_length", 240), win_length=bwe_cfg.get("n_fft", 2048),
+                       n_mel_channels=bwe_cfg.get("num_mels", 128), device=device)
+    return VocoderWithBWE(vocoder=inner, bwe_generator=bwe, mel_stft=mel_stft, input_sampling_rate=bwe_cfg.get("input_sampling_rate", 24000),
+                          output_sampling_rate=bwe_cfg.get("output_sampling_rate", 48000), hop_length=bwe_cfg.get("hop_length", 240)), True
+
+
+def checkpoint_has_audio_decoders(checkpoint_path) -> bool:
+    """True when the checkpoint carries `audio_vae.decoder.*` and `vocoder.*` tensors."""
+    if not checkpoint_path or not os.path.exists(checkpoint_path):
+        return False
+    from ltx_2_mlx_amd.loader.weight_converter import SafetensorsStream
+    keys = SafetensorsStream(checkpoint_path, "cpu").keys()
+    return any(k.startswith("audio_vae.decoder.") for k in keys) and any(k.startswith("vocoder.") for k in keys)
+
+
+def create_audio_decoders(decode_audio, weights_path, device="cuda", seed=0):
+    """(AudioDecoder, vocoder) for decode_audio: None decodes when the checkpoint holds the audio decoder and vocoder tensors (else None
+    with a note), True always decodes (random-initialised decoders without those tensors), False never.  The vocoder form follows the
+    checkpoint's metadata (create_vocoder_for_checkpoint); without a checkpoint that is the LTX-2.0 HiFi-GAN Vocoder (24 kHz) even when
+    model_version selects the LTX-2.3 transformer: no metadata says what BWE configuration a random LTX-2.3 vocoder would have."""
+    from ltx_2_mlx_amd.model.audio_vae import AudioDecoder, load_audio_decoder_weights, load_vocoder_weights, load_vocoder_with_bwe_weights
+    if decode_audio is False:
+        return None
+    if checkpoint_has_audio_decoders(weights_path):
+        dec = AudioDecoder(device=device)
+        load_audio_decoder_weights(dec, weights_path)
+        voc, is_bwe = create_vocoder_for_checkpoint(weights_path, device=device)
+        (load_vocoder_with_bwe_weights if is_bwe else load_vocoder_weights)(voc, weights_path)
+        return dec, voc
+    if decode_audio is None:
+        print("  note: no audio_vae.decoder.* / vocoder.* tensors in the checkpoint: the audio latent is kept (decode_audio=True / --decode-audio "
+              "decodes with random-initialised decoders)")
+        return None
+    print("  Audio decoder + vocoder: random init (no checkpoint tensors; the vocoder form follows the checkpoint metadata, "
+          "the LTX-2.0 HiFi-GAN Vocoder without one)")
+    dec = AudioDecoder(device=device)
+    dec.init_random_weights(seed)
+    voc, is_bwe = create_vocoder_for_checkpoint(weights_path, device=device)
+    for v in ((voc.vocoder, voc.bwe_generator) if is_bwe else (voc,)):
+        v.init_random_weights(seed + 1)
+    return dec, voc
 
 
 def detect_model_version(checkpoint_path: str) -> str:
@@ -444,6 +582,7 @@ def generate_video(
     model_version=None,
     compute_dtype=None,
     fp8_compute: bool = False,
+    decode_audio=None,
 ):
     """Generate video from a text prompt: denoise loop + VAE decode on MI355X behind the reference's signature.
 
@@ -457,7 +596,11 @@ def generate_video(
     the LTX-2.3 architecture without a checkpoint (random init, for tests and benchmarks); fp8_resident keeps fp8 checkpoint
     weights as codes in HBM; fp8_compute runs the video stream's projections fp8 x fp8 on the fp8 MFMA (BASELINE config 3; per-token /
     per-channel e4m3fn scales, not bit-identical to dequantise-at-load); vae_base_channels overrides the checkpoint's decoder_base_channels; compute_dtype="bfloat16" runs the
-    bfloat16 build instead of the reference's float16 default (use_fp16=True)."""
+    bfloat16 build instead of the reference's float16 default (use_fp16=True).
+    Audio (generate_audio / LTX-2.3): the audio latent is always written to `<stem>_audio_latent.npz`; decode_audio (keyword-only) turns
+    it into a waveform through AudioDecoder + the checkpoint's vocoder (create_vocoder_for_checkpoint) and writes `<stem>.wav`, muxed
+    into the mp4 when an ffmpeg binary exists.  None decodes when the checkpoint holds `audio_vae.decoder.*` and `vocoder.*` tensors,
+    True always (random-initialised decoders without them), False never."""
     given = dict(upscale_temporal=upscale_temporal, early_layers_only=early_layers_only,
                  enhance_prompt_flag=enhance_prompt_flag and use_gemma, cross_attn_scale=cross_attn_scale, distilled_lora=distilled_lora,
                  stg_scale=stg_scale, apg_scale=apg_scale, control_video=control_video, save_control=save_control, ge_gamma=ge_gamma,
@@ -616,10 +759,27 @@ def generate_video(
             load_spatial_upscaler_weights(up, spatial_upscaler_weights)
         return up
 
-    def finish(frames, extra=""):
+    def decode_audio_latent(audio_latent):
+        """the latent is always kept as <stem>_audio_latent.npz; with decoders it also becomes the waveform (a sidecar .wav)"""
+        np.savez(base + "_audio_latent.npz", latent=audio_latent.float().cpu().numpy())
+        decoders = create_audio_decoders(decode_audio, weights_path if have_ckpt else None, device=device, seed=seed + 3)
+        if decoders is None:
+            return None
+        t0 = time.time()
+        waveform = decoders[1](decoders[0](audio_latent))
+        torch.cuda.synchronize()
+        print(f"  audio decode: {(time.time() - t0):.3f} s -> {tuple(waveform.shape)} at {decoders[1].output_sample_rate} Hz")
+        return waveform, decoders[1].output_sample_rate
+
+    def finish(frames, extra="", audio=None):
         frames_np = frames.cpu().numpy()
         np.savez_compressed(base + ".npz", frames=frames_np)
-        if save_mp4:
+        if audio is not None and save_mp4:
+            video_out, wav = save_video_with_audio(frames_np, audio[0], output_path, audio[1], fps=fps, speed=speed)
+            print(f"  video: {video_out}, audio: {wav}")
+        elif audio is not None:
+            print(f"  audio: {write_wav(base + '.wav', audio[0], audio[1])}")
+        elif save_mp4:
             print(f"  video: {save_video(frames_np, output_path, fps=fps, speed=speed)}")
         print(f"Done in {time.time() - t_all:.1f} s: {base}.npz{extra}")
         return frames
@@ -647,12 +807,10 @@ def generate_video(
         t0 = time.time()
         out = pipe(text_encoding, None, conf, images=images, audio_encoding=text_audio_encoding)
         frames, audio_latent = out if generate_audio else (out, None)
-        if audio_latent is not None:
-            np.savez(base + "_audio_latent.npz", latent=audio_latent.float().cpu().numpy())     # audio VAE / vocoder are outside this path
         frames = _frames_from_video(frames)
         torch.cuda.synchronize()
         print(f"  two-stage: {(time.time() - t0):.3f} s -> {tuple(frames.shape)}")
-        return finish(frames)
+        return finish(frames, audio=decode_audio_latent(audio_latent) if audio_latent is not None else None)
 
     if use_av_encoder:
         # === AUDIO-VIDEO PIPELINE (reference :1638-1776): OneStagePipeline on the AudioVideo transformer; LTX-2.3 always ===
@@ -680,9 +838,7 @@ def generate_video(
         frames = _frames_from_video(video)
         torch.cuda.synchronize()
         print(f"  audio-video pipeline: {(time.time() - t0):.3f} s -> {tuple(frames.shape)}")
-        if audio_latent is not None:
-            np.savez(base + "_audio_latent.npz", latent=audio_latent.float().cpu().numpy())     # audio VAE / vocoder are outside this path
-        return finish(frames)
+        return finish(frames, audio=decode_audio_latent(audio_latent) if audio_latent is not None else None)
 
     # === STANDARD PIPELINE (one-stage, distilled, video-only; reference :1778-2095) ===
     print("[4/5] latent noise")
@@ -796,6 +952,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--upscale-temporal", action="store_true")
     p.add_argument("--temporal-upscaler-weights", type=str, default="weights/ltx-2/ltx-2-temporal-upscaler-x2-1.0.safetensors")
     p.add_argument("--generate-audio", action="store_true")
+    p.add_argument("--decode-audio", dest="decode_audio", action="store_true", default=None,
+                   help="decode the audio latent to a .wav (muxed into the mp4 with ffmpeg); default: when the checkpoint holds the audio decoder "
+                        "and vocoder, random-initialised decoders without a checkpoint")
+    p.add_argument("--no-decode-audio", dest="decode_audio", action="store_false", help="keep only the audio latent (.npz)")
     p.add_argument("--low-memory", action="store_true")
     p.add_argument("--fast-mode", action="store_true")
     p.add_argument("--image", type=str, default=None)
@@ -864,7 +1024,7 @@ def kwargs_from_args(a) -> dict:
         # MI355X extras
         text_features_path=a.text_features, use_hip_graph=not a.no_hip_graph, two_stage_distilled=a.two_stage_distilled,
         fp8_resident=a.fp8_resident, fp8_compute=a.fp8_compute, model_version=a.model_version, compute_dtype="bfloat16" if a.bf16 else None, num_layers=a.layers, num_heads=a.heads,
-        vae_base_channels=a.vae_base_channels, save_mp4=not a.no_video_file)
+        vae_base_channels=a.vae_base_channels, save_mp4=not a.no_video_file, decode_audio=a.decode_audio)
 
 
 def main(argv=None):

@@ -282,7 +282,13 @@ power = lambda a, b: Arr(torch.pow(_t(a, b), _t(b, a)))
 maximum = lambda a, b: Arr(torch.maximum(_t(a, b), _t(b, a)))
 minimum = lambda a, b: Arr(torch.minimum(_t(a, b), _t(b, a)))
 where = lambda c, a, b: Arr(torch.where(_t(c), _t(a, b), _t(b, a)))
-clip = lambda a, lo, hi: Arr(torch.clamp(_t(a), lo, hi))
+def clip(a, lo=None, hi=None, a_min=None, a_max=None):
+    """mx.clip(a, a_min, a_max), positional or by keyword; None leaves that side open."""
+    lo = a_min if lo is None else lo
+    hi = a_max if hi is None else hi
+    return Arr(torch.clamp(_t(a), None if lo is None else _unwrap(lo), None if hi is None else _unwrap(hi)))
+
+
 repeat = lambda a, n, axis=None: Arr(torch.repeat_interleave(_t(a), n, dim=axis))
 tile = lambda a, reps: Arr(_t(a).repeat(*reps))
 broadcast_to = lambda a, s: Arr(torch.broadcast_to(_t(a), tuple(s)))
@@ -319,6 +325,25 @@ def conv2d(x, w, stride=1, padding=0, dilation=1, groups=1):
     """MLX layout: x (N,H,W,Cin), w (Cout,kH,kW,Cin) -> (N,H',W',Cout)."""
     y = F.conv2d(_t(x).permute(0, 3, 1, 2), _t(w).permute(0, 3, 1, 2), stride=stride, padding=padding, dilation=dilation, groups=groups)
     return Arr(y.permute(0, 2, 3, 1))
+
+
+def conv1d(x, w, stride=1, padding=0, dilation=1, groups=1):
+    """MLX layout: x (N,T,Cin), w (Cout,K,Cin/groups) -> (N,T',Cout); cross-correlation, as PyTorch's conv1d."""
+    y = F.conv1d(_t(x).permute(0, 2, 1), _t(w).permute(0, 2, 1), stride=stride, padding=padding, dilation=dilation, groups=groups)
+    return Arr(y.permute(0, 2, 1))
+
+
+def conv_transpose1d(x, w, stride=1, padding=0, dilation=1, output_padding=0, groups=1):
+    """MLX layout: x (N,T,Cin), w (Cout,K,Cin) -> (N,T',Cout); out[i*stride + k*dilation - padding] += x[i] w[k], PyTorch's
+    conv_transpose1d with its (Cin, Cout, K) weight (MLX tests this op against torch with exactly that weight transpose)."""
+    assert groups == 1, "shim: conv_transpose1d groups"
+    y = F.conv_transpose1d(_t(x).permute(0, 2, 1), _t(w).permute(2, 0, 1), stride=stride, padding=padding, output_padding=output_padding,
+                           dilation=dilation)
+    return Arr(y.permute(0, 2, 1))
+
+
+einsum = lambda eq, *ops: Arr(torch.einsum(eq, *[_t(o) for o in ops]))
+arctan2 = lambda a, b: Arr(torch.atan2(_t(a, b), _t(b, a)))
 
 
 def compile(fn=None, **kw):  # noqa: A001
@@ -444,6 +469,7 @@ silu = lambda x: Arr(F.silu(_t(x)))
 gelu_approx = lambda x: Arr(F.gelu(_t(x), approximate="tanh"))
 gelu = lambda x: Arr(F.gelu(_t(x)))
 relu = lambda x: Arr(F.relu(_t(x)))
+leaky_relu = lambda x, negative_slope=0.01: Arr(F.leaky_relu(_t(x), negative_slope))
 
 
 class SiLU(_Act):
@@ -471,7 +497,7 @@ def install():
     mlx = types.ModuleType("mlx")
     core = types.ModuleType("mlx.core")
     for k, v in vars(me).items():
-        if not k.startswith("_") and k not in ("Module", "Linear", "LayerNorm", "RMSNorm", "SiLU", "GELU", "ReLU", "install"):
+        if not k.startswith("_") and k not in ("Module", "Linear", "LayerNorm", "RMSNorm", "SiLU", "GELU", "ReLU", "install", "leaky_relu"):
             setattr(core, k, v)
     core.fast = _Fast("mlx.core.fast")
     core.random = _Random("mlx.core.random")
@@ -481,7 +507,7 @@ def install():
     core.metal = types.SimpleNamespace(clear_cache=lambda: None, is_available=lambda: False)
     core.clear_cache = lambda: None
     nn = types.ModuleType("mlx.nn")
-    for k in ("Module", "Linear", "LayerNorm", "RMSNorm", "SiLU", "GELU", "ReLU", "silu", "gelu_approx", "gelu", "relu"):
+    for k in ("Module", "Linear", "LayerNorm", "RMSNorm", "SiLU", "GELU", "ReLU", "silu", "gelu_approx", "gelu", "relu", "leaky_relu"):
         setattr(nn, k, getattr(me, k))
     for k in ("Conv1d", "Conv2d", "Conv3d", "ConvTranspose1d", "ConvTranspose2d", "GroupNorm", "Embedding", "Dropout", "Sequential", "Identity"):
         setattr(nn, k, _Generic)
