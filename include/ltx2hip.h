@@ -491,6 +491,13 @@ int ltx2_gemma_resid_norm(const float* x_in, int64_t ldx, const void* y, int64_t
 int ltx2_gemma_gated_act(const void* gu, int64_t ldgu, void* out, int64_t ldo, int rows, int inter, int act, void* stream);
 /* x[r][:] = fp32(table[ids[r]][:]) * scale (gemma3.py:312, :352); an id outside [0, vocab) gives a zero row.  D % 4 == 0. */
 int ltx2_gemma_embed(const int32_t* ids, int rows, const void* table, int vocab, int D, float scale, float* x, int64_t ldx, void* stream);
+/* The LTX-2.3 (V2) feature extractor's GEMM operand in one pass over the L hidden states (feature_extractor.py:160-181):
+ *   out[t][l * D + d] = valid[t] ? hs[l * layer_stride + t * row_stride + d] * rsqrt(mean_d(hs[l, t, :]^2) + eps) : 0
+ * hs fp32 (strides in elements: the [L][T][D] buffer Gemma fills, or any such set of rows), valid int32 [T] or NULL (all valid), out in the
+ * build's 16-bit type [T][ldo] with layer l at columns [l * D, (l + 1) * D) -- the column order of the re-ordered aggregate_embed weights.
+ * fp32 sum, rounded once; pad rows are exact zeros; deterministic.  D % 8 == 0, D <= 8192, strides % 4 == 0, ldo % 8 == 0, ldo >= L * D. */
+int ltx2_gemma_features_rms(const float* hs, int64_t layer_stride, int64_t row_stride, const int32_t* valid, void* out, int64_t ldo, int T, int L,
+                            int D, float eps, void* stream);
 
 /* ---- audio VAE decoder / vocoder (model/audio_vae/: AudioDecoder, Vocoder, VocoderWithBWE).  Additive entries; fp32 end to end
  * (operands, accumulation, activations), the same code in both builds.  Tensors are channels-last fp32: one row of C channels per time

@@ -127,6 +127,7 @@ SIGNATURES = {
     "ltx2_gemma_resid_norm": (i32, [vp, i64, vp, i64, vp, vp, vp, i64, vp, i64, vp, i64, i32, i32, f32, vp]),
     "ltx2_gemma_gated_act": (i32, [vp, i64, vp, i64, i32, i32, i32, vp]),
     "ltx2_gemma_embed": (i32, [vp, i32, vp, i32, i32, f32, vp, i64, vp]),
+    "ltx2_gemma_features_rms": (i32, [vp, i64, i64, vp, vp, i64, i32, i32, i32, f32, vp]),
     # audio VAE decoder / vocoder (additive entries of ABI version 3; fp32)
     "ltx2_audio_conv": (i32, [vp, i64, i32, i32, i32, vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp, i64,
                               f32, f32, i32, vp]),

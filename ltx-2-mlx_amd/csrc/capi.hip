@@ -519,4 +519,10 @@ int ltx2_gemma_embed(const int32_t* ids, int rows, const void* table, int vocab,
     return gemma_embed_launch((const int*)ids, rows, (const bf16*)table, vocab, D, scale, x, (long)ldx, (hipStream_t)stream);
 }
 
+int ltx2_gemma_features_rms(const float* hs, int64_t layer_stride, int64_t row_stride, const int32_t* valid, void* out, int64_t ldo, int T, int L,
+                            int D, float eps, void* stream) {
+    return gemma_features_rms_launch(hs, (long)layer_stride, (long)row_stride, (const int*)valid, (bf16*)out, (long)ldo, T, L, D, eps,
+                                     (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -28,3 +28,10 @@ int gemma_gated_act_launch(const bf16* gu, long ldgu, bf16* out, long ldo, int r
 
 // x[r][:] = table[ids[r]][:] * scale (fp32 out); an id outside [0, vocab) writes zeros.  D % 4 == 0.
 int gemma_embed_launch(const int* ids, int rows, const bf16* table, int vocab, int D, float scale, float* x, long ldx, hipStream_t stream);
+
+// The V2 (LTX-2.3) feature extractor's GEMM operand (reference feature_extractor.py:160-181), one pass over Gemma's hidden states:
+//   out[t][l * D + d] = valid[t] ? hs[l * layer_stride + t * row_stride + d] * rsqrt(mean_d(hs[l, t, :]^2) + eps) : 0
+// hs fp32 (strides in elements, multiples of 4, 16-byte aligned base), valid int32 [T] or null (every token valid), out 16-bit
+// [T][ldo], ldo >= L * D, ldo % 8 == 0.  fp32 sum, one rounding.  D % 8 == 0, D <= 8192.
+int gemma_features_rms_launch(const float* hs, long layer_stride, long row_stride, const int* valid, bf16* out, long ldo, int T, int L, int D,
+                              float eps, hipStream_t stream);

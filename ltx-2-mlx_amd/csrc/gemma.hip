@@ -15,6 +15,8 @@
 //    writes the fp32 residual straight into the [49][T][D] hidden-state buffer.
 //  * gemma_gated_act_kernel: act(gate) * up of the fused gate|up GEMM (:244-255), SiLU (the reference) or tanh-GELU (the checkpoints).
 //  * gemma_embed_kernel: embedding gather * sqrt(hidden) (:312, :352).
+//  * gemma_features_rms_kernel: the [49][T][D] hidden states -> the LTX-2.3 feature extractor's per-token RMS-normalised, layer-major
+//    16-bit GEMM operand [T][49 * D] in one pass (feature_extractor.py:160-181).
 #include "gemma.h"
 
 namespace {
@@ -337,9 +339,74 @@ __global__ __launch_bounds__(256) void gemma_embed_kernel(const int* __restrict_
     }
 }
 
+// The V2 feature extractor's GEMM operand in one pass over the hidden states (reference feature_extractor.py:160-181): one wave per
+// (token, layer) row of D floats, held in registers between the sum of squares and the scale, so every fp32 element is read once and
+// every 16-bit element written once (two 16-byte loads and one 16-byte store per lane and chunk of 8).  No LDS, no barrier; the
+// reduction order is fixed by the butterfly, so two runs agree bit for bit.  A pad token's rows are written as zeros without a read.
+template <int NV>          // chunks of 8 per lane: D <= 512 * NV
+__global__ __launch_bounds__(256) void gemma_features_rms_kernel(const float* __restrict__ hs, long layer_stride, long row_stride,
+                                                                 const int* __restrict__ valid, bf16* __restrict__ out, long ldo, int T, int L,
+                                                                 int D, float eps) {
+    const long item = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (item >= (long)T * L) return;
+    const int lane = threadIdx.x & 63, t = (int)(item / L), l = (int)(item % L), n8 = D / 8;
+    bf16* orow = out + (long)t * ldo + (long)l * D;
+    if (valid && valid[t] == 0) {
+        const bf16x8 z = {};
+        for (int c = lane; c < n8; c += 64) *(bf16x8*)(orow + 8 * c) = z;
+        return;
+    }
+    const float4* xr = (const float4*)(hs + (long)l * layer_stride + (long)t * row_stride);
+    float4 xa[NV], xb[NV];
+    float ss = 0.f;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        const int c = lane + 64 * k;
+        if (c < n8) {
+            xa[k] = xr[2 * c];
+            xb[k] = xr[2 * c + 1];
+            ss += xa[k].x * xa[k].x + xa[k].y * xa[k].y + xa[k].z * xa[k].z + xa[k].w * xa[k].w;
+            ss += xb[k].x * xb[k].x + xb[k].y * xb[k].y + xb[k].z * xb[k].z + xb[k].w * xb[k].w;
+        }
+    }
+    const float r = rsqrtf(wave_sum(ss) / (float)D + eps);
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        const int c = lane + 64 * k;
+        if (c < n8) {
+            const bf16x8 o = {f2bf(xa[k].x * r), f2bf(xa[k].y * r), f2bf(xa[k].z * r), f2bf(xa[k].w * r),
+                              f2bf(xb[k].x * r), f2bf(xb[k].y * r), f2bf(xb[k].z * r), f2bf(xb[k].w * r)};
+            *(bf16x8*)(orow + 8 * c) = o;
+        }
+    }
+}
+
 bool aligned16(const void* ptr) { return ((uintptr_t)ptr & 15) == 0; }
 
 }  // namespace
+
+int gemma_features_rms_launch(const float* hs, long layer_stride, long row_stride, const int* valid, bf16* out, long ldo, int T, int L, int D,
+                              float eps, hipStream_t stream) {
+    LTX2_CHECK_ARG(hs && out, "gemma_features_rms: null operand");
+    LTX2_CHECK_ARG(T >= 0 && L > 0 && D > 0 && D % 8 == 0 && D <= 8192, "gemma_features_rms: T %d, L %d, D %d (a multiple of 8, at most 8192)", T, L,
+                   D);
+    LTX2_CHECK_ARG(row_stride >= D && row_stride % 4 == 0 && layer_stride >= 0 && layer_stride % 4 == 0 && ldo >= (long)L * D && ldo % 8 == 0 &&
+                       aligned16(hs) && aligned16(out),
+                   "gemma_features_rms: 16-byte rows needed (layer stride %ld, row stride %ld, ldo %ld for L * D = %ld)", layer_stride, row_stride, ldo,
+                   (long)L * D);
+    const long items = (long)T * L;
+    if (items == 0) return LTX2_OK;
+    LTX2_CHECK_ARG((items + 3) / 4 <= 0x7fffffffL, "gemma_features_rms: T * L = %ld rows exceed the grid", items);
+    const dim3 grid((unsigned)((items + 3) / 4));
+    if (D <= 512 * 2)
+        hipLaunchKernelGGL(gemma_features_rms_kernel<2>, grid, dim3(256), 0, stream, hs, layer_stride, row_stride, valid, out, ldo, T, L, D, eps);
+    else if (D <= 512 * 8)
+        hipLaunchKernelGGL(gemma_features_rms_kernel<8>, grid, dim3(256), 0, stream, hs, layer_stride, row_stride, valid, out, ldo, T, L, D, eps);
+    else
+        hipLaunchKernelGGL(gemma_features_rms_kernel<16>, grid, dim3(256), 0, stream, hs, layer_stride, row_stride, valid, out, ldo, T, L, D, eps);
+    LTX2_CHECK_LAUNCH("gemma_features_rms");
+    return LTX2_OK;
+}
 
 int gemma_attn_launch(const bf16* Q, long ldq, const bf16* K, long ldk, const bf16* V, long ldv, bf16* O, long ldo, int Tq, int Tkv,
                       int heads, int kv_heads, int causal, int window, float scale, hipStream_t stream) {

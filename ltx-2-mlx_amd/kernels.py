@@ -606,6 +606,48 @@ def gemma_embed(ids: torch.Tensor, table: torch.Tensor, scale: float, out: Optio
     return out
 
 
+def _layer_strides(states) -> Optional[Tuple[int, int]]:
+    """(layer stride, row stride) in elements when the L [T, D] fp32 tensors are equally spaced rows of one buffer (the views
+    Gemma3Model returns, sliced or not); None when they are not and have to be stacked."""
+    s0 = states[0]
+    if any(s.shape != s0.shape or s.dtype != torch.float32 or s.device != s0.device or s.stride() != s0.stride() for s in states):
+        return None
+    if s0.stride(1) != 1 or s0.stride(0) % 4 or s0.stride(0) < s0.shape[1]:
+        return None
+    if len(states) == 1:
+        return 0, s0.stride(0)
+    step = states[1].data_ptr() - s0.data_ptr()
+    if step <= 0 or step % 16 or any(states[i + 1].data_ptr() - states[i].data_ptr() != step for i in range(len(states) - 1)):
+        return None
+    same = s0.untyped_storage().data_ptr()
+    if any(s.untyped_storage().data_ptr() != same for s in states):
+        return None
+    return step // 4, s0.stride(0)
+
+
+def gemma_features_rms(hidden_states, valid: Optional[torch.Tensor] = None, eps: float = 1e-6, dtype: torch.dtype = BF16,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The V2 feature extractor's GEMM operand: hidden_states = L fp32 [T, D] tensors (or one [L, T, D] tensor), valid [T] (non-zero = a
+    real token; None = all) -> 16-bit [T, L * D], column l * D + d = x[l, t, d] * rsqrt(mean_d(x[l, t]^2) + eps), pad rows zero.  The
+    list is read in place when its entries are equally spaced views of one buffer, and stacked once otherwise."""
+    states = list(hidden_states.unbind(0)) if isinstance(hidden_states, torch.Tensor) else list(hidden_states)
+    assert states and all(s.dim() == 2 and s.is_cuda for s in states)
+    strides = _layer_strides(states)
+    if strides is None:
+        stacked = torch.stack([s.float() for s in states])
+        states, strides = list(stacked.unbind(0)), (stacked.stride(0), stacked.stride(1))
+    nl, (t, d) = len(states), states[0].shape
+    if out is None:
+        out = torch.empty(t, nl * d, device=states[0].device, dtype=dtype)
+    assert out.dtype == dtype and dtype in ACT16 and out.shape == (t, nl * d) and out.stride(1) == 1
+    if valid is not None:
+        valid = _c(valid.to(states[0].device, torch.int32).reshape(-1))
+        assert valid.shape[0] == t
+    nv.check(nv.lib(dtype).ltx2_gemma_features_rms(nv.ptr(states[0]), strides[0], strides[1], nv.ptr(valid), nv.ptr(out), out.stride(0), t, nl, d,
+                                                   float(eps), nv.stream()))
+    return out
+
+
 # ---- audio VAE decoder / vocoder (fp32, csrc/audio.hip).  Channels-last fp32 tensors: [T, C] (1-D) or [H, W, C] (2-D); the row stride is
 # the stride of the position dimension.  Weights come packed by pack_conv_weight / pack_conv_transpose_weight.
 

@@ -11,7 +11,11 @@ INTERLEAVED RoPE without a second rotation kernel: attention only sees q.k per h
 dimensions applied to BOTH q and k leaves it unchanged.  At load time the rows of to_q / to_k (and their biases and
 q_norm / k_norm weights) are permuted per head to [even dims | odd dims]; the reference's pair (2j, 2j+1) then sits at
 (j, j + 64) of the head, which is exactly the SPLIT layout `ltx2_qknorm_rope` rotates, with the table slot h*64 + j
-holding the frequency of interleaved pair h*64 + j (`ltx2_rope_tables` on the 1-D index grid)."""
+holding the frequency of interleaved pair h*64 + j (`ltx2_rope_tables` on the 1-D index grid).
+
+SPLIT RoPE (`rope_type="split"`, what a checkpoint's metadata may ask for; reference rope.py:92-144, :292-328) is the kernel's own
+layout: the reference reshapes the [T, inner_dim/2] frequencies to [heads, T, head_dim/2], so head h rotates its dimensions
+(j, j + head_dim/2) by frequency h*head_dim/2 + j -- the same table, and no row permutation at all."""
 from __future__ import annotations
 
 import math
@@ -34,16 +38,17 @@ def _split_perm(heads: int, head_dim: int, device) -> torch.Tensor:
 
 
 class Embeddings1DConnector:
-    """Constructor keywords as the reference (connector.py:114-126).  `rope_type` other than interleaved, and a run
-    without learnable registers on a padded prompt (which would need an attention mask), are rejected."""
+    """Constructor keywords as the reference (connector.py:114-126).  `rope_type` is "interleaved" or "split" (a string or an enum
+    with such a `.value`); a run without learnable registers on a padded prompt (which would need an attention mask) is rejected."""
 
     def __init__(self, attention_head_dim: int = 128, num_attention_heads: int = 30, num_layers: int = 2,
                  positional_embedding_theta: float = 10000.0, positional_embedding_max_pos: Optional[List[int]] = None,
                  num_learnable_registers: Optional[int] = 128, rope_type: str = "interleaved", norm_eps: float = 1e-6,
                  apply_gated_attention: bool = False, double_precision_rope: bool = False,
                  device: Union[str, torch.device] = "cuda"):
-        if str(getattr(rope_type, "value", rope_type)).lower() != "interleaved":
-            raise NotImplementedError("Embeddings1DConnector: only the INTERLEAVED RoPE of the released checkpoints is implemented")
+        self.rope_type = str(getattr(rope_type, "value", rope_type)).lower()
+        if self.rope_type not in ("interleaved", "split"):
+            raise ValueError(f"Embeddings1DConnector: rope_type {rope_type!r} is neither 'interleaved' nor 'split'")
         if attention_head_dim not in (64, 128):
             raise ValueError("attention_head_dim must be 128 or 64 (flash-attention kernel instantiations)")
         self.num_attention_heads, self.attention_head_dim, self.num_layers = num_attention_heads, attention_head_dim, num_layers
@@ -89,7 +94,10 @@ class Embeddings1DConnector:
             if k in sd and tuple(sd[k].shape) != shp:
                 raise ValueError(f"weight {k}: shape {tuple(sd[k].shape)} != expected {shp}")
         dev = self.device
-        perm = _split_perm(self.num_attention_heads, self.attention_head_dim, dev)
+        if self.rope_type == "split":               # already the layout ltx2_qknorm_rope rotates
+            perm = torch.arange(self.inner_dim, device=dev)
+        else:
+            perm = _split_perm(self.num_attention_heads, self.attention_head_dim, dev)
 
         def f(k):
             return sd[k].to(dev, torch.float32)
@@ -128,8 +136,9 @@ class Embeddings1DConnector:
 
     # ------------------------------------------------------------------ forward
     def _rope_tables(self, seq_len: int) -> Tuple[torch.Tensor, torch.Tensor]:
-        """cos, sin fp32 [T, inner_dim/2]: slot p = interleaved pair p, angle grid[p] * (2 t / max_pos - 1)
-        (reference rope.py:242-289,330-362 through connector.py:253-270)."""
+        """cos, sin fp32 [T, inner_dim/2]: slot p = interleaved pair p (INTERLEAVED) or dimension j = p % (head_dim/2) of head
+        p // (head_dim/2) (SPLIT), angle grid[p] * (2 t / max_pos - 1) in both (reference rope.py:242-289, :292-362 through
+        connector.py:253-270)."""
         if seq_len not in self._tables:
             d = self.inner_dim
             if d % 2:

@@ -5,7 +5,8 @@ The 49-layer stack [B, T, 3840, 49] is never materialised in the reference's int
 weight's input columns are re-ordered once at load time from (d * L + l) to (l * D + d), so the normalised states of
 layer l are simply columns [l*D, (l+1)*D) of the GEMM's A operand, and the 188 160-wide contraction runs on
 `ltx2_gemm_bf16`.  The per-(prompt, layer) statistics of the V1 normalisation are torch reductions (per prompt,
-outside the metric); the V2 per-token RMS normalisation is `ltx2_adaln_rmsnorm`."""
+outside the metric); the V2 per-token RMS normalisation of all layers is one launch of `ltx2_gemma_features_rms`, which reads
+Gemma's [L, T, D] hidden-state buffer in place and writes the layer-major 16-bit operand."""
 from __future__ import annotations
 
 import math
@@ -116,11 +117,12 @@ class GemmaFeaturesExtractorV2:
         if len(hidden_states) != self.num_layers:
             raise ValueError(f"expected {self.num_layers} hidden states, got {len(hidden_states)}")
         b, t, d = hidden_states[0].shape
-        valid = attention_mask.to(self.device).bool().reshape(b * t, 1)
+        if d != self.hidden_dim:
+            raise ValueError(f"hidden states are {d} wide, the extractor was built for {self.hidden_dim}")
+        valid = attention_mask.to(self.device).reshape(b, t)
         a = torch.empty(b * t, self.num_layers * d, device=self.device, dtype=BF16)
-        for l, hs in enumerate(hidden_states):                       # x * rsqrt(mean_D(x^2) + 1e-6) per token and layer
-            a[:, l * d:(l + 1) * d] = K.adaln_rmsnorm(hs.to(self.device, torch.float32).reshape(b * t, d), 1e-6)
-        a = torch.where(valid, a, torch.zeros_like(a))              # pad rows contribute the bias only
+        for bi in range(b):         # one pass of ltx2_gemma_features_rms per prompt: x * rsqrt(mean_D(x^2) + 1e-6), pad rows zero (bias only)
+            K.gemma_features_rms([hs[bi].to(self.device) for hs in hidden_states], valid[bi], 1e-6, out=a[bi * t:(bi + 1) * t])
         video = K.gemm(a, self._wv, self._bv, epilogue=K.nv.EPI_F32).reshape(b, t, self.video_inner_dim)
         audio = K.gemm(a, self._wa, self._ba, epilogue=K.nv.EPI_F32).reshape(b, t, self.audio_inner_dim)
         return video, audio

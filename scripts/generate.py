@@ -5,7 +5,8 @@ Keeps the flag names and `generate_video(...)` keyword names of the reference's
 scripts/generate.py (argparse block :2364-2641, `generate_video` :933-997) for this path:
 standard single-stage distilled loop (reference :1764-1984) followed by `decode_latent` (:2080-2091).
 Gemma-3 encodes the prompt on the GPU when `--gemma-path` holds its weights (model/text_encoder/gemma3.py; reference
-encode_with_gemma :340-486, encode_av_gemma_batch :511-640).  Out of this path (and rejected with a clear message): STG guidance,
+encode_with_gemma :340-486, encode_av_gemma_batch :511-640; an LTX-2.3 checkpoint gets the V2 text encoder, create_av_text_encoder_v2_from_checkpoint
+:548-551).  Out of this path (and rejected with a clear message): STG guidance,
 CFG in the video-only loop.
 `--pipeline distilled --spatial-upscaler-weights W` runs the two-stage DistilledPipeline; adding `--generate-audio` runs it on
 the AudioVideo transformer and saves the audio LATENT beside the frames; `--decode-audio` (the default when the checkpoint holds the
@@ -184,13 +185,51 @@ def encode_text_features(path: str, weights_path=None, device="cuda", seed: int 
     return out.video_encoding, out.attention_mask.float()
 
 
-def _gemma_text_encoder(gemma_cfg, ltx_weights_path, device, seed: int = 0, audio_video: bool = False):
+def _gemma_text_encoder(gemma_cfg, ltx_weights_path, device, seed: int = 0, audio_video: bool = False, model_version=None, num_heads: int = 32):
     """Feature extractor + connector(s) for a Gemma of `gemma_cfg`: from the LTX checkpoint when given (its text_embedding_projection must
-    take (hidden, layers + 1) hidden states: raises naming both shapes otherwise), else randomly initialised at that size."""
+    take (hidden, layers + 1) hidden states: raises naming both shapes otherwise), else randomly initialised at that size.  An LTX-2.3
+    checkpoint (`is_v2_model`; `model_version` overrides the metadata, as in generate_video), or `model_version` 2.3 without a checkpoint,
+    gets the V2 encoder (create_av_text_encoder_v2: per-token RMS
+    extractor to the transformer's widths num_heads * 128 / num_heads * 64, 8-block gated connectors)."""
     import math
     from ltx_2_mlx_amd.model.text_encoder import (AudioVideoGemmaTextEncoderModel, Embeddings1DConnector, GemmaFeaturesExtractorProjLinear,
-                                                  VideoGemmaTextEncoderModel, load_text_encoder_weights)
+                                                  VideoGemmaTextEncoderModel, create_av_text_encoder_v2,
+                                                  create_av_text_encoder_v2_from_checkpoint, load_av_text_encoder_v2_weights,
+                                                  load_text_encoder_weights)
     hidden, nl = gemma_cfg.hidden_size, gemma_cfg.num_hidden_layers + 1
+    if model_version is None:
+        model_version = detect_model_version(ltx_weights_path) if ltx_weights_path else ""
+    if str(model_version).startswith("2.3"):
+        if not ltx_weights_path:
+            video_dim, audio_dim = num_heads * 128, num_heads * 64
+            enc = create_av_text_encoder_v2(hidden_dim=hidden, num_gemma_layers=nl, video_inner_dim=video_dim, audio_inner_dim=audio_dim,
+                                            video_connector_heads=num_heads, audio_connector_heads=num_heads, device=device)
+            g = torch.Generator().manual_seed(seed)
+            enc.feature_extractor.load_state_dict({
+                "video_aggregate_embed.weight": torch.randn(video_dim, hidden * nl, generator=g) / math.sqrt(hidden * nl),
+                "video_aggregate_embed.bias": 0.02 * torch.randn(video_dim, generator=g),
+                "audio_aggregate_embed.weight": torch.randn(audio_dim, hidden * nl, generator=g) / math.sqrt(hidden * nl),
+                "audio_aggregate_embed.bias": 0.02 * torch.randn(audio_dim, generator=g)})
+            enc.embeddings_connector.init_random_weights(seed + 1)
+            enc.audio_embeddings_connector.init_random_weights(seed + 2)
+            return enc
+        from safetensors import safe_open
+        dims = {}
+        with safe_open(ltx_weights_path, framework="pt") as f:
+            for name in ("video_aggregate_embed", "audio_aggregate_embed"):
+                key = f"text_embedding_projection.{name}.weight"
+                if key not in f.keys():
+                    raise KeyError(f"{key} is not in the LTX-2.3 checkpoint {ltx_weights_path}")
+                have = tuple(f.get_slice(key).get_shape())
+                if have[1] != hidden * nl:
+                    raise ValueError(f"the Gemma at hand gives (hidden, layers + 1) = {(hidden, nl)}, i.e. a {key} of "
+                                     f"{(have[0], hidden * nl)}, but the LTX checkpoint's is {have}")
+                dims[name] = have[0]
+        enc = create_av_text_encoder_v2_from_checkpoint(ltx_weights_path, hidden_dim=hidden, num_gemma_layers=nl,
+                                                        video_inner_dim=dims["video_aggregate_embed"],
+                                                        audio_inner_dim=dims["audio_aggregate_embed"], device=device)
+        load_av_text_encoder_v2_weights(enc, ltx_weights_path)
+        return enc
     fe = GemmaFeaturesExtractorProjLinear(hidden_dim=hidden, num_layers=nl, device=device)
     conns = [Embeddings1DConnector(device=device) for _ in range(2 if audio_video else 1)]
     enc = AudioVideoGemmaTextEncoderModel(fe, conns[0], conns[1]) if audio_video else VideoGemmaTextEncoderModel(fe, conns[0])
@@ -260,16 +299,16 @@ def encode_with_gemma(prompt: str, gemma_path: str, ltx_weights_path, max_length
         _free_gemma(gemma)
 
 
-def encode_av_gemma_batch(prompts: list, gemma_path: str, ltx_weights_path, max_length: int = 1024, *, device="cuda", seed: int = 0) -> list:
+def encode_av_gemma_batch(prompts: list, gemma_path: str, ltx_weights_path, max_length: int = 1024, *, device="cuda", seed: int = 0,
+                          model_version=None, num_heads: int = 32) -> list:
     """Several prompts under ONE Gemma load with the AudioVideo text encoder (reference scripts/generate.py:511-640): the hidden states are
-    trimmed to the real tokens, later prompts are tokenised with max_length = the first encoding's length.  Returns
+    trimmed to the real tokens, later prompts are tokenised with max_length = the first encoding's length.  An LTX-2.3 checkpoint (or
+    model_version 2.3 without a checkpoint, at num_heads) gets the V2 encoder (reference :548-551).  Returns
     [(video_encoding, audio_encoding, attention_mask), ...]."""
-    if ltx_weights_path and is_v2_model(ltx_weights_path):
-        raise NotImplementedError("Gemma encoding for LTX-2.3 checkpoints (the V2 feature extractor and 8-layer connectors) is not built: "
-                                  "pass embedding_path with `embedding` / `audio_embedding` arrays")
     tokenizer, gemma = _load_gemma(gemma_path, device)
     try:
-        enc = _gemma_text_encoder(gemma.config, ltx_weights_path, device, seed, audio_video=True)
+        enc = _gemma_text_encoder(gemma.config, ltx_weights_path, device, seed, audio_video=True, model_version=model_version,
+                                  num_heads=num_heads)
         results = []
         for i, prompt in enumerate(prompts):
             print(f"  Running Gemma 3 forward pass (prompt {i + 1}/{len(prompts)})...")
@@ -686,12 +725,10 @@ def generate_video(
     if text_features_path:
         text_encoding, _ = encode_text_features(text_features_path, weights_path if have_ckpt else None, device, seed)
     elif gemma_encodes and use_av_encoder:
-        if v2:
-            raise NotImplementedError("Gemma encoding for LTX-2.3 (the V2 feature extractor and 8-layer connectors) is not built: pass embedding_path "
-                                      "with `embedding` / `audio_embedding` arrays")
-        # prompt AND negative prompt under one Gemma load (reference :1096-1116); Gemma is freed before the transformer loads
+        # prompt AND negative prompt under one Gemma load (reference :1096-1116); Gemma is freed before the transformer loads.  LTX-2.3
+        # gets the V2 encoder: encodings at the transformer's own widths (num_heads * 128 video, num_heads * 64 audio)
         results = encode_av_gemma_batch([prompt, negative_prompt or ""], gemma_path, weights_path if have_ckpt else None, device=device,
-                                        seed=seed)
+                                        seed=seed, model_version=version, num_heads=num_heads)
         text_encoding, text_audio_encoding, _ = results[0]
         negative_encoding, negative_audio_encoding, _ = results[1]
         print("  Encoded both prompts with Gemma 3 (AudioVideo, single load)")

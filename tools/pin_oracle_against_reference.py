@@ -277,6 +277,79 @@ def pin_text_connector():
     print("text_connector.npz", {k: v.shape for k, v in out.items()})
 
 
+# ------------------------------------------------------------------------------------------ LTX-2.3 ("V2") text encoder, assembled
+V2_PIN = dict(hidden=64, layers=5, heads=2, video_head_dim=128, audio_head_dim=64, blocks=2, registers=16, tokens=40, pad=10,
+              seed_fe=71, seed_video=72, seed_audio=73, seed_hidden=74)
+
+
+def v2_pin_inputs(c=V2_PIN):
+    """The seeded weights and hidden states of the text_encoder_v2 vectors (tests/test_text_encoder_v2_gpu.py rebuilds them from the
+    seeds stored in the file): (feature-extractor weights, video / audio connector weights, hidden states, binary mask)."""
+    k = c["hidden"] * c["layers"]
+    g = torch.Generator().manual_seed(int(c["seed_fe"]))
+    fe = {}
+    for name, n in (("video_aggregate_embed", c["heads"] * c["video_head_dim"]), ("audio_aggregate_embed", c["heads"] * c["audio_head_dim"])):
+        fe[name + ".weight"] = torch.randn(n, k, generator=g) / k ** 0.5
+        fe[name + ".bias"] = 0.1 * torch.randn(n, generator=g)
+    conn = {}
+    for tag, hd, seed in (("video", c["video_head_dim"], c["seed_video"]), ("audio", c["audio_head_dim"], c["seed_audio"])):
+        cfg = otc.ConnectorConfig(num_attention_heads=int(c["heads"]), attention_head_dim=int(hd), num_layers=int(c["blocks"]),
+                                  num_learnable_registers=int(c["registers"]), apply_gated_attention=True)
+        conn[tag] = otc.make_connector_weights(cfg, seed=int(seed))
+    g = torch.Generator().manual_seed(int(c["seed_hidden"]))
+    hs = [torch.randn(1, int(c["tokens"]), int(c["hidden"]), generator=g) * (1 + 0.5 * i) + 0.05 * i for i in range(int(c["layers"]))]
+    mask = torch.ones(1, int(c["tokens"]))
+    mask[:, :int(c["pad"])] = 0                 # left padding, as Gemma's tokenizer pads
+    return fe, conn["video"], conn["audio"], hs, mask
+
+
+def _load_ref_connector(conn, w):
+    conn.learnable_registers = A(w["learnable_registers"])
+    for i, blk in enumerate(conn.transformer_1d_blocks):
+        p = f"transformer_1d_blocks.{i}"
+        for n, attr in (("to_q", "to_q"), ("to_k", "to_k"), ("to_v", "to_v"), ("to_out.0", "to_out"), ("to_gate_logits", "to_gate_logits")):
+            lin = getattr(blk.attn1, attr)
+            lin.weight, lin.bias = A(w[f"{p}.attn1.{n}.weight"]), A(w[f"{p}.attn1.{n}.bias"])
+        blk.attn1.q_norm.weight, blk.attn1.k_norm.weight = A(w[f"{p}.attn1.q_norm.weight"]), A(w[f"{p}.attn1.k_norm.weight"])
+        blk.ff.project_in.proj.weight, blk.ff.project_in.proj.bias = A(w[f"{p}.ff.net.0.proj.weight"]), A(w[f"{p}.ff.net.0.proj.bias"])
+        blk.ff.project_out.weight, blk.ff.project_out.bias = A(w[f"{p}.ff.net.2.weight"]), A(w[f"{p}.ff.net.2.bias"])
+
+
+def pin_text_encoder_v2():
+    """The reference's own create_av_text_encoder_v2 (hidden 64, 5 layers, video 2 x 128, audio 2 x 64, 2 gated blocks, 16 registers) on
+    seeded weights and a left-padded 40-token prompt, once with INTERLEAVED and once with SPLIT RoPE.  Stores the seeds, the head and
+    tail rows of both encodings and the mask."""
+    from LTX_2_MLX.model.text_encoder.encoder import create_av_text_encoder_v2
+    import LTX_2_MLX.model.transformer.rope as ref_rope
+    from LTX_2_MLX.model.transformer.rope import LTXRopeType
+    ref_rope._HAS_FUSED_ROPE = False           # the fused variant is a Metal kernel; the reference's own fallback is the definition
+    c = V2_PIN
+    fe, wv, wa, hs, mask = v2_pin_inputs()
+    out = {"config_keys": np.array(list(c.keys())), "config": np.array(list(c.values()), dtype=np.int64)}
+    for tag, rt in (("interleaved", LTXRopeType.INTERLEAVED), ("split", LTXRopeType.SPLIT)):
+        enc = create_av_text_encoder_v2(hidden_dim=c["hidden"], num_gemma_layers=c["layers"], video_inner_dim=c["heads"] * c["video_head_dim"],
+                                        audio_inner_dim=c["heads"] * c["audio_head_dim"], video_connector_heads=c["heads"],
+                                        video_connector_head_dim=c["video_head_dim"], audio_connector_heads=c["heads"],
+                                        audio_connector_head_dim=c["audio_head_dim"], connector_layers=c["blocks"], num_registers=c["registers"],
+                                        rope_type=rt, connector_apply_gated_attention=True, double_precision_rope=True)
+        for name in ("video_aggregate_embed", "audio_aggregate_embed"):
+            lin = getattr(enc.feature_extractor, name)
+            lin.weight, lin.bias = A(fe[name + ".weight"]), A(fe[name + ".bias"])
+        _load_ref_connector(enc.embeddings_connector, wv)
+        _load_ref_connector(enc.audio_embeddings_connector, wa)
+        res = enc.encode_from_hidden_states([A(h) for h in hs], A(mask), padding_side="left")
+        for mod, y in (("video", tn(res.video_encoding.t)), ("audio", tn(res.audio_encoding.t))):
+            assert y.shape[1] == 1024 and np.isfinite(y).all()
+            out[f"{tag}_{mod}_head"], out[f"{tag}_{mod}_tail"] = y[:, :56], y[:, 992:]
+            out[f"{tag}_{mod}_stats"] = np.array([y.mean(), y.std(), np.abs(y).max()], dtype=np.float32)
+        out[f"{tag}_mask"] = tn(res.attention_mask.t).astype(np.int32)
+    d = float(np.abs(out["interleaved_video_head"] - out["split_video_head"]).mean())
+    print("  mean |interleaved - split| of the video head rows:", d)
+    assert d > 1e-3                            # the two rotations really differ on these inputs
+    np.savez_compressed(os.path.join(GOLD, "text_encoder_v2.npz"), **out)
+    print("text_encoder_v2.npz", {k: v.shape for k, v in out.items()})
+
+
 # ------------------------------------------------------------------------------------------ VAE encoder + conditioning
 def pin_vae_encoder():
     """The reference hard-wires the encoder widths (128..1024, 28 res blocks), so the full-size encoder runs on
@@ -486,6 +559,10 @@ if __name__ == "__main__":
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "text_connector":
         pin_text_connector()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "text_encoder_v2":
+        with torch.no_grad():
+            pin_text_encoder_v2()
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "dit":
         with torch.no_grad():
