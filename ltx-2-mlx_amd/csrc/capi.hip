@@ -18,6 +18,17 @@ void ltx2_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
+// The shared tail of the two *_qkv_vt entries: the V columns as attention's V^T operand from the GEMM's epilogue where the route can, else by a transpose pass behind it
+static int gemm_qkv_vt(GemmParams& p, void* vt, int vt_col0, int Npad, int head_dim, int* fused, hipStream_t stream) {
+    gemm_set_vt(p, vt, vt_col0, Npad, head_dim);
+    const bool f = gemm_vt_fused(p, EPI_BF16);
+    if (fused) *fused = f ? 1 : 0;
+    if (!f) p.vt = nullptr;
+    const int rc = gemm_launch(p, EPI_BF16, false, stream);
+    if (rc != LTX2_OK || f) return rc;
+    return vt_transpose_launch((const bf16*)p.out + vt_col0, p.ldo, (bf16*)vt, p.M, Npad, (p.N - vt_col0) / head_dim, stream, head_dim);
+}
+
 extern "C" {
 
 const char* ltx2_last_error(void) { return g_err; }
@@ -29,16 +40,7 @@ int ltx2_gemm_bf16(const void* A, int64_t lda, const void* W, const float* bias,
                    const void* res, int64_t ldres, void* stream) {
     LTX2_CHECK_ARG(epilogue >= 0 && epilogue <= LTX2_EPI_ADD_BF16, "gemm: epilogue %d out of range", epilogue);
     LTX2_CHECK_ARG(epilogue != LTX2_EPI_ADD_BF16 || res, "gemm: epilogue ADD_BF16 needs res");
-    GemmParams p{};
-    p.A = (const bf16*)A;
-    p.lda = lda;
-    p.W = (const bf16*)W;
-    p.bias = bias;
-    p.out = out;
-    p.ldo = ldo;
-    p.M = M;
-    p.N = N;
-    p.K = K;
+    GemmParams p = gemm_dense_params((const bf16*)A, lda, (const bf16*)W, bias, out, ldo, M, N, K);
     p.gate = gate;
     p.gate_stride = gate_stride;
     p.gate_table = gate_table;
@@ -59,16 +61,7 @@ int ltx2_adaln_rmsnorm2(const float* x, int64_t ldx, void* out0, void* out1, int
 int ltx2_gemm_bf16_rowss(const void* A, int64_t lda, const void* W, const float* bias, void* out, int64_t ldo, int M, int N, int K, float* rowss,
                          int* written, void* stream) {
     LTX2_CHECK_ARG(A && W && out && rowss && written, "gemm_bf16_rowss: null argument");
-    GemmParams p{};
-    p.A = (const bf16*)A;
-    p.lda = lda;
-    p.W = (const bf16*)W;
-    p.bias = bias;
-    p.out = out;
-    p.ldo = ldo;
-    p.M = M;
-    p.N = N;
-    p.K = K;
+    GemmParams p = gemm_dense_params((const bf16*)A, lda, (const bf16*)W, bias, out, ldo, M, N, K);
     *written = gemm_rowss_supported(p, EPI_BF16) ? 1 : 0;
     if (*written) p.rowss = rowss;
     return gemm_launch(p, EPI_BF16, false, (hipStream_t)stream);
@@ -79,16 +72,7 @@ int ltx2_gemm_bf16_fold(const void* A, int64_t lda, const void* W, const float* 
                         const float* rf_parts, int64_t rf_ld, int rf_nparts, int rf_dim, float rf_eps, int* supported, void* stream) {
     LTX2_CHECK_ARG(A && W && out && supported, "gemm_bf16_fold: null argument");
     LTX2_CHECK_ARG(epilogue == LTX2_EPI_BF16 || epilogue == LTX2_EPI_GELU_BF16 || epilogue == LTX2_EPI_RESID_GATE_F32, "gemm_bf16_fold: epilogue %d (BF16, GELU_BF16 or RESID_GATE_F32)", epilogue);
-    GemmParams p{};
-    p.A = (const bf16*)A;
-    p.lda = lda;
-    p.W = (const bf16*)W;
-    p.bias = bias;
-    p.out = out;
-    p.ldo = ldo;
-    p.M = M;
-    p.N = N;
-    p.K = K;
+    GemmParams p = gemm_dense_params((const bf16*)A, lda, (const bf16*)W, bias, out, ldo, M, N, K);
     p.gate_table = gate_table;
     p.shadow = (bf16*)shadow;
     p.ld_shadow = ld_shadow;
@@ -157,31 +141,12 @@ int ltx2_flash_attn_keymask(const void* Q, int64_t ldq, const void* K, int64_t l
 int ltx2_gemm_route(int M, int N, int K, int epilogue, int weights, int has_vt) {
     // host logic only: addresses are never dereferenced (16-byte aligned dummies satisfy the alignment checks)
     static const long dummy[2] = {0, 0};
-    GemmParams p{};
-    p.M = M;
-    p.N = N;
-    p.K = K;
-    p.lda = K;
-    p.ldo = N;
-    p.out = (void*)dummy;
-    if (weights == 2) {
-        p.A8 = (const unsigned char*)dummy;
-        p.ascale = (const float*)dummy;
-    } else {
-        p.A = (const bf16*)dummy;
-    }
-    if (weights >= 1) {
-        p.W8 = (const unsigned char*)dummy;
-        p.wscale = (const float*)dummy;
-    } else {
-        p.W = (const bf16*)dummy;
-    }
+    GemmParams p = gemm_dense_params((const bf16*)dummy, K, (const bf16*)dummy, nullptr, (void*)dummy, N, M, N, K);
+    if (weights >= 1) gemm_set_w8(p, dummy, (const float*)dummy);
+    if (weights == 2) gemm_set_a8(p, dummy, (const float*)dummy, K);
     const int r = gemm_route(p, epilogue, false);
     if (!has_vt || r < 0) return r;
-    p.vt = (bf16*)dummy;
-    p.vt_col0 = 2 * (N / 3);
-    p.vt_hd = (N / 3) % 128 == 0 ? 128 : 64;
-    p.vt_npad = (M + 63) / 64 * 64;
+    gemm_set_vt(p, (void*)dummy, 2 * (N / 3), (M + 63) / 64 * 64, (N / 3) % 128 == 0 ? 128 : 64);
     return r | (gemm_vt_fused(p, epilogue) ? 0x100 : 0);
 }
 
@@ -194,18 +159,9 @@ int ltx2_gemm_fp8(const void* A8, int64_t lda, const float* ascale, const void* 
                   int64_t ldo, int M, int N, int K, int epilogue, const float* gate, int64_t gate_stride, const float* gate_table,
                   void* stream) {
     LTX2_CHECK_ARG(A8 && ascale && W8 && wscale && out, "gemm_fp8: null operand");
-    GemmParams p{};
-    p.A8 = (const unsigned char*)A8;
-    p.ascale = ascale;
-    p.lda = lda;
-    p.W8 = (const unsigned char*)W8;
-    p.wscale = wscale;
-    p.bias = bias;
-    p.out = out;
-    p.ldo = ldo;
-    p.M = M;
-    p.N = N;
-    p.K = K;
+    GemmParams p = gemm_dense_params(nullptr, lda, nullptr, bias, out, ldo, M, N, K);
+    gemm_set_w8(p, W8, wscale);
+    gemm_set_a8(p, A8, ascale, lda);
     p.gate = gate;
     p.gate_stride = gate_stride;
     p.gate_table = gate_table;
@@ -217,27 +173,8 @@ int ltx2_gemm_qkv_vt(const void* A, int64_t lda, const void* W, const float* bia
     LTX2_CHECK_ARG(A && W && out && vt, "gemm_qkv_vt: null operand");
     LTX2_CHECK_ARG(head_dim == 64 || head_dim == 128, "gemm_qkv_vt: head_dim=%d, only 128 and 64 are implemented", head_dim);
     LTX2_CHECK_ARG(vt_col0 > 0 && vt_col0 < N && (N - vt_col0) % head_dim == 0 && Npad % 64 == 0 && Npad >= M, "gemm_qkv_vt: bad V column range / Npad");
-    GemmParams p{};
-    p.A = (const bf16*)A;
-    p.lda = lda;
-    p.W = (const bf16*)W;
-    p.bias = bias;
-    p.out = out;
-    p.ldo = ldo;
-    p.M = M;
-    p.N = N;
-    p.K = K;
-    p.vt = (bf16*)vt;
-    p.vt_col0 = vt_col0;
-    p.vt_npad = Npad;
-    p.vt_hd = head_dim;
-    p.vt_head_stride = (long)head_dim * Npad;
-    const bool f = gemm_vt_fused(p, EPI_BF16);
-    if (fused) *fused = f ? 1 : 0;
-    if (!f) p.vt = nullptr;
-    int rc = gemm_launch(p, EPI_BF16, false, (hipStream_t)stream);
-    if (rc != LTX2_OK || f) return rc;
-    return vt_transpose_launch((const bf16*)out + vt_col0, ldo, (bf16*)vt, M, Npad, (N - vt_col0) / head_dim, (hipStream_t)stream, head_dim);
+    GemmParams p = gemm_dense_params((const bf16*)A, lda, (const bf16*)W, bias, out, ldo, M, N, K);
+    return gemm_qkv_vt(p, vt, vt_col0, Npad, head_dim, fused, (hipStream_t)stream);
 }
 
 int ltx2_gemm_fp8_qkv_vt(const void* A8, int64_t lda, const float* ascale, const void* W8, const float* wscale, const float* bias, void* out,
@@ -245,45 +182,17 @@ int ltx2_gemm_fp8_qkv_vt(const void* A8, int64_t lda, const float* ascale, const
     LTX2_CHECK_ARG(A8 && ascale && W8 && wscale && out && vt, "gemm_fp8_qkv_vt: null operand");
     LTX2_CHECK_ARG(head_dim == 64 || head_dim == 128, "gemm_fp8_qkv_vt: head_dim=%d, only 128 and 64 are implemented", head_dim);
     LTX2_CHECK_ARG(vt_col0 > 0 && vt_col0 < N && (N - vt_col0) % head_dim == 0 && Npad % 64 == 0 && Npad >= M, "gemm_fp8_qkv_vt: bad V column range / Npad");
-    GemmParams p{};
-    p.A8 = (const unsigned char*)A8;
-    p.ascale = ascale;
-    p.lda = lda;
-    p.W8 = (const unsigned char*)W8;
-    p.wscale = wscale;
-    p.bias = bias;
-    p.out = out;
-    p.ldo = ldo;
-    p.M = M;
-    p.N = N;
-    p.K = K;
-    p.vt = (bf16*)vt;
-    p.vt_col0 = vt_col0;
-    p.vt_npad = Npad;
-    p.vt_hd = head_dim;
-    p.vt_head_stride = (long)head_dim * Npad;
-    const bool f = gemm_vt_fused(p, EPI_BF16);
-    if (fused) *fused = f ? 1 : 0;
-    if (!f) p.vt = nullptr;
-    int rc = gemm_launch(p, EPI_BF16, false, (hipStream_t)stream);
-    if (rc != LTX2_OK || f) return rc;
-    return vt_transpose_launch((const bf16*)out + vt_col0, ldo, (bf16*)vt, M, Npad, (N - vt_col0) / head_dim, (hipStream_t)stream, head_dim);
+    GemmParams p = gemm_dense_params(nullptr, lda, nullptr, bias, out, ldo, M, N, K);
+    gemm_set_w8(p, W8, wscale);
+    gemm_set_a8(p, A8, ascale, lda);
+    return gemm_qkv_vt(p, vt, vt_col0, Npad, head_dim, fused, (hipStream_t)stream);
 }
 
 int ltx2_gemm_w8a16(const void* A, int64_t lda, const void* W8, const float* wscale, const float* bias, void* out, int64_t ldo, int M,
                     int N, int K, int epilogue, const float* gate, int64_t gate_stride, const float* gate_table, void* stream) {
     LTX2_CHECK_ARG(A && W8 && wscale && out, "gemm_w8a16: null operand");
-    GemmParams p{};
-    p.A = (const bf16*)A;
-    p.lda = lda;
-    p.W8 = (const unsigned char*)W8;
-    p.wscale = wscale;
-    p.bias = bias;
-    p.out = out;
-    p.ldo = ldo;
-    p.M = M;
-    p.N = N;
-    p.K = K;
+    GemmParams p = gemm_dense_params((const bf16*)A, lda, nullptr, bias, out, ldo, M, N, K);
+    gemm_set_w8(p, W8, wscale);
     p.gate = gate;
     p.gate_stride = gate_stride;
     p.gate_table = gate_table;

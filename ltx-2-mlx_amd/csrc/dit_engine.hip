@@ -350,17 +350,9 @@ bool f8_route(ltx2_dit* c, const bf16* W, int M, int N, int K, int epi) {
     if (!c->fp8_compute || !c->m[0].a8 || M < 1024 || M > c->m[0].N || K > 4 * c->m[0].D) return false;
     auto f8 = c->fp8_scale.find((const void*)W);
     if (f8 == c->fp8_scale.end()) return false;
-    GemmParams q{};
-    q.A8 = c->m[0].a8;
-    q.ascale = c->m[0].a8s;
-    q.lda = K;
-    q.W8 = (const unsigned char*)W;
-    q.wscale = f8->second;
-    q.out = c->m[0].x;
-    q.ldo = 8;
-    q.M = M;
-    q.N = N;
-    q.K = K;
+    GemmParams q = gemm_dense_params(nullptr, K, nullptr, nullptr, c->m[0].x, 8, M, N, K);
+    gemm_set_w8(q, W, f8->second);
+    gemm_set_a8(q, c->m[0].a8, c->m[0].a8s, K);
     return gemm_v4_f8_supported(q, epi);
 }
 
@@ -371,26 +363,10 @@ bool text_qfold_ok(ltx2_dit* c, int k) {
     const Mod& m = c->m[k];
     if (m.D % 1024 != 0 || m.hd != 128) return false;
     const bf16* W = c->layers[0].m[k].text.q_w;
-    GemmParams q{};
-    q.M = m.N;
-    q.N = m.D;
-    q.K = m.D;
-    q.lda = m.D;
-    q.ldo = m.D;
-    q.out = m.x;
-    if (k == 0 && f8_route(c, W, m.N, m.D, m.D, EPI_BF16)) {
-        q.A8 = m.a8;
-        q.ascale = m.a8s;
-    } else {
-        q.A = m.h;
-    }
+    GemmParams q = gemm_dense_params(m.h, m.D, W, nullptr, m.x, m.D, m.N, m.D, m.D);
+    if (k == 0 && f8_route(c, W, m.N, m.D, m.D, EPI_BF16)) gemm_set_a8(q, m.a8, m.a8s, m.D);
     auto f8 = c->fp8_scale.find((const void*)W);
-    if (f8 != c->fp8_scale.end()) {
-        q.W8 = (const unsigned char*)W;
-        q.wscale = f8->second;
-    } else {
-        q.W = W;
-    }
+    if (f8 != c->fp8_scale.end()) gemm_set_w8(q, W, f8->second);
     return gemm_rowss_supported(q, EPI_BF16);
 }
 
@@ -405,30 +381,14 @@ int fold_supported(ltx2_dit* c, int k) {
     const Mod& m = c->m[k];
     if (!m.rss || m.D % 256 != 0 || m.D / 256 > GEMM_RF_MAX_PARTS) return 0;
     const BlockW& w = c->layers[0].m[k];
-    GemmParams q{};
-    q.A = m.h;
-    q.lda = m.D;
-    q.M = m.N;
-    q.K = m.D;
-    q.out = m.x;
     // producer: attn1.to_out; consumer: attn2.to_q
-    q.W = w.self.o_w;
-    q.N = m.D;
-    q.ldo = m.D;
+    GemmParams q = gemm_dense_params(m.h, m.D, w.self.o_w, nullptr, m.x, m.D, m.N, m.D, m.D);
     q.shadow = m.h;
     q.ld_shadow = m.D;
     q.shadow_ss = m.rss;
     q.ld_ss = m.rss_ld;
     if (!gemm_fold_supported(q, EPI_RESID_GATE_F32)) return 0;
-    GemmParams r{};
-    r.A = m.h;
-    r.lda = m.D;
-    r.M = m.N;
-    r.K = m.D;
-    r.N = m.D;
-    r.ldo = m.D;
-    r.out = m.qkv;
-    r.W = w.text.q_w;
+    GemmParams r = gemm_dense_params(m.h, m.D, w.text.q_w, nullptr, m.qkv, m.D, m.N, m.D, m.D);
     r.rf_parts = m.rss;
     r.rf_ld = m.rss_ld;
     r.rf_nparts = m.D / 256;
@@ -460,7 +420,7 @@ struct Fold {
 int dense(ltx2_dit* c, const bf16* A, long lda, const bf16* W, const float* bias, void* out, long ldo, int M, int N, int K, int epi,
           hipStream_t st, const float* gate = nullptr, long gate_stride = 0, const float* gate_table = nullptr,
           const VtOut* vt = nullptr, bool* vt_done = nullptr, bool preq = false, float* rowss = nullptr, const Fold* fold = nullptr) {
-    GemmParams p{};
+    GemmParams p = gemm_dense_params(A, lda, W, bias, out, ldo, M, N, K);
     if (fold) {
         p.shadow = fold->shadow;
         p.shadow_scale = fold->shadow_scale;
@@ -473,23 +433,10 @@ int dense(ltx2_dit* c, const bf16* A, long lda, const bf16* W, const float* bias
         p.rf_dim = fold->rf_dim;
         p.rf_eps = fold->rf_eps;
     }
-    p.A = A;
-    p.lda = lda;
-    p.W = W;
     if (!c->fp8_scale.empty()) {
         auto f8 = c->fp8_scale.find((const void*)W);
-        if (f8 != c->fp8_scale.end()) {      // fp8-resident: codes + per-row scale, expanded inside the GEMM
-            p.W = nullptr;
-            p.W8 = (const unsigned char*)W;
-            p.wscale = f8->second;
-        }
+        if (f8 != c->fp8_scale.end()) gemm_set_w8(p, W, f8->second);      // fp8-resident: codes + per-row scale, expanded inside the GEMM
     }
-    p.bias = bias;
-    p.out = out;
-    p.ldo = ldo;
-    p.M = M;
-    p.N = N;
-    p.K = K;
     p.gate = gate;
     p.gate_stride = gate_stride;
     p.gate_table = gate_table;
@@ -497,20 +444,13 @@ int dense(ltx2_dit* c, const bf16* A, long lda, const bf16* W, const float* bias
     // fp8 compute (opt-in): the video stream's big GEMMs on fp8-resident weights take per-token-quantised activations and the fp8 MFMA
     if (p.W8 && f8_route(c, W, M, N, K, epi)) {
         if (!preq) TRY(quant_rows_fp8_launch(A, lda, M, K, c->m[0].a8, K, c->m[0].a8s, st));
-        p.A8 = c->m[0].a8;
-        p.ascale = c->m[0].a8s;
-        p.lda = K;
-        p.A = nullptr;
+        gemm_set_a8(p, c->m[0].a8, c->m[0].a8s, K);
     } else if (preq) {
         ltx2_set_error("dit: a pre-quantised activation reached a GEMM that does not take the fp8 path");
         return LTX2_E_STATE;
     }
     if (vt) {
-        p.vt = vt->vt;
-        p.vt_col0 = vt->col0;
-        p.vt_npad = vt->npad;
-        p.vt_hd = vt->hd;
-        p.vt_head_stride = (long)vt->hd * vt->npad;
+        gemm_set_vt(p, vt->vt, vt->col0, vt->npad, vt->hd);
         *vt_done = gemm_vt_fused(p, epi);
         if (!*vt_done) p.vt = nullptr;
     }

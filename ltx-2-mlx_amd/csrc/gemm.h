@@ -60,8 +60,44 @@ struct GemmParams {
     int rf_nparts, rf_dim;     //   rf_nparts <= GEMM_RF_MAX_PARTS
     float rf_eps;
     int splitk;          // gemm_v4.hip: K split over this many blocks per tile (fp32 slabs + reduce); 0 / 1 = off
-    void* dbg;           // ping-pong kernel: optional device buffer for interval timestamps (debug)      // ping-pong kernel: which wave bit selects the staggered group (tuning knob)
+    void* dbg;           // ping-pong kernel: optional device buffer for interval timestamps (debug)
 };
+
+// ---- filling a GemmParams: dense operands and shape first, then what the call adds (everything else is set field by field) ----
+inline GemmParams gemm_dense_params(const bf16* A, long lda, const bf16* W, const float* bias, void* out, long ldo, int M, int N, int K) {
+    GemmParams p{};
+    p.A = A;
+    p.lda = lda;
+    p.W = W;
+    p.bias = bias;
+    p.out = out;
+    p.ldo = ldo;
+    p.M = M;
+    p.N = N;
+    p.K = K;
+    return p;
+}
+// fp8-resident weight: e4m3fn codes + one scale per output column in place of W
+inline void gemm_set_w8(GemmParams& p, const void* W8, const float* wscale) {
+    p.W = nullptr;
+    p.W8 = (const unsigned char*)W8;
+    p.wscale = wscale;
+}
+// fp8 compute: per-row quantised activations (codes [M][lda] + one scale per row) in place of A; needs gemm_set_w8 too
+inline void gemm_set_a8(GemmParams& p, const void* A8, const float* ascale, long lda) {
+    p.A = nullptr;
+    p.A8 = (const unsigned char*)A8;
+    p.ascale = ascale;
+    p.lda = lda;
+}
+// columns >= col0 go to vt[h][hd][npad] as attention's V^T operand (ask gemm_vt_fused() before the launch)
+inline void gemm_set_vt(GemmParams& p, void* vt, int col0, int npad, int hd) {
+    p.vt = (bf16*)vt;
+    p.vt_col0 = col0;
+    p.vt_npad = npad;
+    p.vt_hd = hd;
+    p.vt_head_stride = (long)hd * npad;
+}
 
 int gemm_launch(const GemmParams& p, int epilogue, bool conv, hipStream_t stream);
 inline bool gemm_v4_prefer_224(const GemmParams& p) {
@@ -70,8 +106,9 @@ inline bool gemm_v4_prefer_224(const GemmParams& p) {
     const long cost256 = (t256 + cus - 1) / cus * 256, cost224 = (t224 + cus - 1) / cus * 224;
     return p.A8 ? cost224 * 100 <= cost256 * 108 : cost224 < cost256;
 }
-// Which kernel gemm_launch hands this problem to (host logic only, nothing is launched): the dispatch is a parity surface, so
-// tests/test_host_cpu.py enumerates every GEMM the three models issue and pins its route.
+// Which kernel gemm_launch hands this problem to (host logic only, nothing is launched): gemm_route() is the only place that decides,
+// gemm_launch and the gemm_*_supported / gemm_vt_fused queries follow it.  The dispatch is a parity surface, so tests/test_host_cpu.py
+// enumerates every GEMM the three models issue and pins its route, and compares a grid of 47 520 problems with a recorded table.
 enum GemmRoute {
     ROUTE_INVALID = -1,
     ROUTE_SKINNY = 0,      // gemm_skinny.hip: M <= 128 rows (the audio stream), weight-streaming
@@ -79,12 +116,32 @@ enum GemmRoute {
     ROUTE_V4_256 = 2,      // gemm_v4.hip layout 3, 256-row tiles
     ROUTE_V4_W8_224 = 3,   // ... with fp8-resident weights expanded in the loop
     ROUTE_V4_W8_256 = 4,
-    ROUTE_V4_F8_224 = 5,   // gemm_v4.hip layout 5: fp8 compute
-    ROUTE_V4_F8_256 = 6,
+    ROUTE_V4_F8_224 = 5,   // gemm_v4.hip fp8 compute: layout 6 (16x16x128 blocks)
+    ROUTE_V4_F8_256 = 6,   //   layout 5 (32x32x64 blocks)
     ROUTE_PP = 7,          // gemm_pp.hip: 256x256 ping-pong (big grids the asm-loop kernel does not take; convs of the upscaler / encoder)
     ROUTE_SMALL = 8,       // gemm.hip 128x128
     ROUTE_NARROW = 9       // gemm.hip 128x64 (N <= 64)
 };
+// The 4-wave kernel of a ROUTE_V4_* route: gemm_v4_kernel<EPI, layout, bm, false, var> (bm = 0: not a 4-wave route).  var 30 = the
+// instantiations that implement a folded norm's producer / consumer half, var 20 = fp8-resident weights expanded in the K loop.
+struct GemmV4Kernel {
+    int layout, bm, var;
+};
+#ifndef LTX2_F8_FORCE_L5
+#define LTX2_F8_FORCE_L5 0          // (A/B builds: gemm.hip=-DLTX2_F8_FORCE_L5=1 keeps every fp8 GEMM on layout 5)
+#endif
+inline GemmV4Kernel gemm_v4_kernel_of(int route, const GemmParams& p) {
+    switch (route) {
+        case ROUTE_V4_224: return {3, 224, (p.shadow || p.rf_parts) ? 30 : 0};
+        case ROUTE_V4_256: return {3, 256, (p.shadow || p.rf_parts) ? 30 : 0};
+        case ROUTE_V4_W8_224: return {3, 224, 20};
+        case ROUTE_V4_W8_256: return {3, 256, 20};
+        // 224-row tiles: the 16x16x128 form (+16 % FLOP per joule on random e4m3 operands, tools/micro/mfma_fp8_power.hip)
+        case ROUTE_V4_F8_224: return {LTX2_F8_FORCE_L5 ? 5 : 6, 224, 0};
+        case ROUTE_V4_F8_256: return {5, 256, 0};
+        default: return {0, 0, 0};
+    }
+}
 int gemm_route(const GemmParams& p, int epilogue, bool conv);
 // p.vt set: will gemm_launch route this problem to the kernel that writes V^T from its epilogue?  (false: clear p.vt and run
 // vt_transpose_launch after the GEMM; gemm_launch rejects a p.vt it cannot honour.)
@@ -95,7 +152,7 @@ bool gemm_rowss_supported(const GemmParams& p, int epilogue);
 // gemm_launch rejects what it cannot honour.
 bool gemm_fold_supported(const GemmParams& p, int epilogue);
 constexpr int GEMM_RF_MAX_PARTS = 24;      // partial sums per row the consumer stages in LDS (a producer of up to 6144 columns)
-// fp8 compute (p.A8 / p.ascale / p.W8 / p.wscale set): can the fp8-MFMA kernel (gemm_v4.hip layout 5) take this problem?
+// fp8 compute (p.A8 / p.ascale / p.W8 / p.wscale set): can the fp8-MFMA kernel (gemm_v4.hip layouts 5 / 6) take this problem?
 bool gemm_v4_f8_supported(const GemmParams& p, int epilogue);
 
 // Skinny path (M <= 16 rows, fp32 activations, bf16 weights): out_f32 = act_out(in_act(a) @ W^T + b)

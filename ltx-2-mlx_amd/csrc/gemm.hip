@@ -7,10 +7,10 @@
 // (LTX_2_MLX/model/video_vae/simple_decoder.py:146-175).
 //
 // Structure: BM x BN x 64 block tile, WAVES_M x WAVES_N wave64 grid, each wave a grid of
-// v_mfma_f32_32x32x16_bf16 tiles.  Two configurations are instantiated:
-//   * 256x256, 8 waves (2x4, wave tile 128x64), 1 block/CU: large problems (128 FLOP per staged
-//     byte, keeps the L2->LDS stream well under the per-XCD L2 bandwidth);
-//   * 128x128, 4 waves (2x2, wave tile 64x64), 2 blocks/CU: small M / narrow N.
+// v_mfma_f32_32x32x16_bf16 tiles.  Two configurations are instantiated here (the large problems' 256x256
+// tile is gemm_pp.hip's ping-pong kernel, the DiT's big GEMMs run gemm_v4.hip; gemm_route() below decides):
+//   * 128x128, 4 waves (2x2, wave tile 64x64), 2 blocks/CU: small M;
+//   * 128x64, same waves: N <= 64.
 // Both operands are K-contiguous, so A and B fragments are single 16-byte LDS reads.  Tiles are
 // staged HBM->LDS with global_load_lds (16 B per lane, no VGPR round trip) into a double-buffered
 // ring; the LDS image is lane-linear, so the bank swizzle (16-B chunk index ^= (row>>1)&7 on
@@ -44,7 +44,6 @@ struct TileCfg {
     static constexpr int STAGE_BYTES = A_BYTES + B_BYTES;
     static constexpr int LDS_BYTES = 2 * STAGE_BYTES;
     static constexpr int A_LOADS = BM / 8 / NW, B_LOADS = BN / 8 / NW;   // 1-KiB glds per wave per tile
-    static constexpr int OCC = (NT == 512) ? 2 : 2;                // min waves/SIMD for launch bounds
 };
 
 template <class CFG, int EPI, bool CONV>
@@ -208,7 +207,6 @@ __global__ __launch_bounds__(CFG::NT, 2) void gemm_kernel(const GemmParams p) {
     }
 }
 
-using CfgBig = TileCfg<256, 256, 2, 4>;
 using CfgSmall = TileCfg<128, 128, 2, 2>;
 using CfgNarrow = TileCfg<128, 64, 2, 2>;      // N <= 64 (the decoder's 128 -> 48 conv_out): 1.19 -> 0.77 ms at 49x128x192 (a 256x64 tile measured the same)
 
@@ -244,33 +242,14 @@ inline bool v4_wins_medium_grid(const GemmParams& p) {
     return t_v4 < t_small;
 }
 
-// The whole dispatch, as data: gemm_launch follows it, ltx2_gemm_route reports it (round 3: the LTX2_GEMM_TILE / LTX2_V4_LAYOUT /
-// LTX2_PP_BM / LTX2_VT_FUSE overrides are gone -- same-box A/B runs load a second build through LTX2HIP_LIB instead).
-template <bool CONV>
-int route_of(const GemmParams& p, int epi) {
-    if (p.A8) return gemm_v4_f8_supported(p, epi) ? (gemm_v4_prefer_224(p) ? ROUTE_V4_F8_224 : ROUTE_V4_F8_256) : ROUTE_INVALID;
-    if (p.W8) {
-        if (CONV) return ROUTE_INVALID;
-        if (gemm_skinny_supported(p, epi)) return ROUTE_SKINNY;
-        return gemm_v4_w8_supported(p, epi) ? (gemm_v4_prefer_224(p) ? ROUTE_V4_W8_224 : ROUTE_V4_W8_256) : ROUTE_INVALID;
-    }
-    if (!CONV && epi != EPI_D2S_BF16 && gemm_skinny_supported(p, epi)) return ROUTE_SKINNY;      // M <= 128: the audio stream
-    if (!CONV && (use_big_tile(p) || v4_wins_medium_grid(p)) && gemm_v4_supported(p, epi, CONV)) return gemm_v4_prefer_224(p) ? ROUTE_V4_224 : ROUTE_V4_256;
-    if (use_big_tile(p)) return ROUTE_PP;
-    if (p.N <= 64 && p.M >= 4096) return ROUTE_NARROW;
-    return ROUTE_SMALL;
-}
-
-template <int EPI, bool CONV>
-int launch_t(const GemmParams& p, hipStream_t stream) {
-    switch (route_of<CONV>(p, EPI)) {
-        case ROUTE_SKINNY: return gemm_skinny_launch(p, EPI, stream);
-        case ROUTE_V4_224: return gemm_v4_launch(p, EPI, stream, 3, 224);
-        case ROUTE_V4_256: return gemm_v4_launch(p, EPI, stream, 3, 256);
-        case ROUTE_PP: return gemm_pp_launch(p, EPI, CONV, stream);
-        case ROUTE_NARROW: return launch_cfg<CfgNarrow, EPI, CONV>(p, stream);
-        default: return launch_cfg<CfgSmall, EPI, CONV>(p, stream);
-    }
+// this file's tile kernels (128x64 when `narrow`, else 128x128): every dense epilogue with and without the conv gather, and the conv-only depth-to-space scatter
+int launch_tile(const GemmParams& p, int epilogue, bool conv, bool narrow, hipStream_t stream) {
+    return gemm_epilogue_dispatch(epilogue, [&](auto E) {
+        constexpr int e = decltype(E)::value;
+        if (conv) return narrow ? launch_cfg<CfgNarrow, e, true>(p, stream) : launch_cfg<CfgSmall, e, true>(p, stream);
+        if constexpr (e != EPI_D2S_BF16) return narrow ? launch_cfg<CfgNarrow, e, false>(p, stream) : launch_cfg<CfgSmall, e, false>(p, stream);
+        else return (int)LTX2_E_INVALID;
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -323,25 +302,38 @@ __global__ __launch_bounds__(256) void gemv_kernel(const float* __restrict__ a, 
 
 }  // namespace
 
+// The whole dispatch, as data: gemm_launch follows it, ltx2_gemm_route reports it, the capability queries below derive from it (round 3:
+// the LTX2_GEMM_TILE / LTX2_V4_LAYOUT / LTX2_PP_BM / LTX2_VT_FUSE overrides are gone -- same-box A/B runs load a second build through LTX2HIP_LIB instead).
+int gemm_route(const GemmParams& p, int epi, bool conv) {
+    if (p.A8) return gemm_v4_f8_supported(p, epi) ? (gemm_v4_prefer_224(p) ? ROUTE_V4_F8_224 : ROUTE_V4_F8_256) : ROUTE_INVALID;
+    if (p.W8) {
+        if (conv) return ROUTE_INVALID;
+        if (gemm_skinny_supported(p, epi)) return ROUTE_SKINNY;
+        return gemm_v4_w8_supported(p, epi) ? (gemm_v4_prefer_224(p) ? ROUTE_V4_W8_224 : ROUTE_V4_W8_256) : ROUTE_INVALID;
+    }
+    if (!conv && epi != EPI_D2S_BF16 && gemm_skinny_supported(p, epi)) return ROUTE_SKINNY;      // M <= 128: the audio stream
+    if (!conv && (use_big_tile(p) || v4_wins_medium_grid(p)) && gemm_v4_supported(p, epi, conv)) return gemm_v4_prefer_224(p) ? ROUTE_V4_224 : ROUTE_V4_256;
+    if (use_big_tile(p)) return ROUTE_PP;
+    if (p.N <= 64 && p.M >= 4096) return ROUTE_NARROW;
+    return ROUTE_SMALL;
+}
+
 bool gemm_vt_fused(const GemmParams& p, int epilogue) {
     if (!p.vt || p.lda % 8 != 0) return false;
-    if (p.A8) return gemm_v4_vt_supported(p, epilogue, 5);
-    if (gemm_skinny_supported(p, epilogue)) return false;      // M <= 128 goes to the skinny kernel
-    if (p.W8) return gemm_v4_vt_supported(p, epilogue, 3);
-    return (use_big_tile(p) || v4_wins_medium_grid(p)) && gemm_v4_vt_supported(p, epilogue, 3);
+    const int bm = gemm_v4_kernel_of(gemm_route(p, epilogue, false), p).bm;
+    return bm && gemm_v4_vt_supported(p, epilogue, bm);
 }
 
 bool gemm_rowss_supported(const GemmParams& p, int epilogue) {
     if (epilogue != EPI_BF16 || p.vt || p.N % 64 != 0) return false;
-    const int r = route_of<false>(p, epilogue);
-    return r == ROUTE_V4_224 || r == ROUTE_V4_256 || r == ROUTE_V4_W8_224 || r == ROUTE_V4_W8_256 || r == ROUTE_V4_F8_224 || r == ROUTE_V4_F8_256;
+    return gemm_v4_kernel_of(gemm_route(p, epilogue, false), p).bm != 0;
 }
 
 bool gemm_fold_supported(const GemmParams& p, int epilogue) {
     if (p.W8 || p.A8 || !p.W) return false;
-    const int r = route_of<false>(p, epilogue);
+    const int r = gemm_route(p, epilogue, false);
     if (r != ROUTE_V4_224 && r != ROUTE_V4_256) return false;
-    const int bm = r == ROUTE_V4_224 ? 224 : 256;
+    const int bm = gemm_v4_kernel_of(r, p).bm;
     if (p.shadow) {         // producer: the gated-residual epilogue with a row-invariant gate
         if (epilogue != EPI_RESID_GATE_F32 || (p.gate && p.gate_stride != 0) || !p.shadow_ss || p.ld_shadow % 4 != 0 || ((uintptr_t)p.shadow & 7)) return false;
         if (p.ld_ss % 4 != 0 || p.ld_ss < (long)((p.M + bm - 1) / bm) * bm || ((uintptr_t)p.shadow_ss & 15)) return false;
@@ -354,54 +346,44 @@ bool gemm_fold_supported(const GemmParams& p, int epilogue) {
     return true;
 }
 
-int gemm_route(const GemmParams& p, int epilogue, bool conv) { return conv ? route_of<true>(p, epilogue) : route_of<false>(p, epilogue); }
-
 int gemm_launch(const GemmParams& p, int epilogue, bool conv, hipStream_t stream) {
     LTX2_CHECK_ARG(p.M > 0 && p.N > 0 && p.K > 0, "gemm: empty problem M=%d N=%d K=%d", p.M, p.N, p.K);
     LTX2_CHECK_ARG(!p.vt || (!conv && gemm_vt_fused(p, epilogue)), "gemm: a fused V^T output needs the 4-wave layout-3 / layout-5 kernel (ask gemm_vt_fused first)");
     LTX2_CHECK_ARG(p.K % BK == 0, "gemm: K=%d must be a multiple of %d", p.K, BK);
     LTX2_CHECK_ARG(!p.rowss || (!conv && gemm_rowss_supported(p, epilogue)), "gemm: row partial sums need the 4-wave kernel's bf16 epilogue (ask gemm_rowss_supported first)");
     LTX2_CHECK_ARG(!(p.shadow || p.rf_parts) || (!conv && gemm_fold_supported(p, epilogue)), "gemm: a folded norm (shadow / rf_parts) needs the 4-wave layout-3 kernel on dense bf16 weights (ask gemm_fold_supported first)");
-    if (p.A8) {     // fp8 compute: both operands e4m3fn codes + scales, fp8 MFMA (gemm_v4.hip layout 5)
+    if (p.A8) {             // fp8 compute: both operands e4m3fn codes + scales, fp8 MFMA
         LTX2_CHECK_ARG(!conv && p.out, "gemm: fp8 compute is dense-only");
-        return gemm_v4_launch(p, epilogue, stream, 0, 0);        // layout 6 (16x16x128 blocks) for 224-row tiles, 5 (32x32x64) for 256-row ones
-    }
-    LTX2_CHECK_ARG(p.A && (p.W || p.W8) && p.out, "gemm: null operand");
-    if (p.W8) {     // fp8-resident weights: the 4-wave asm-loop kernel, or the skinny-M kernel where the bf16 path would take it too
+    } else if (p.W8) {      // fp8-resident weights: the 4-wave asm-loop kernel, or the skinny-M kernel where the bf16 path would take it too
+        LTX2_CHECK_ARG(p.A && p.out, "gemm: null operand");
         LTX2_CHECK_ARG(!conv && p.lda % 8 == 0, "gemm: fp8-resident weights are dense-only");
-        if (gemm_skinny_supported(p, epilogue)) return gemm_skinny_launch(p, epilogue, stream);
-        return gemm_v4_launch(p, epilogue, stream, 3, 0);
+    } else {                // dense bf16 operands (the vector epilogue's alignment rules belong to this path only)
+        LTX2_CHECK_ARG(p.A && p.W && p.out, "gemm: null operand");
+        LTX2_CHECK_ARG(p.N % 4 == 0 && p.ldo % 4 == 0 && p.ldres % 4 == 0 && p.gate_stride % 4 == 0,
+                       "gemm: N, ldo, ldres and gate_stride must be multiples of 4 (vector epilogue)");
+        if (conv) {
+            LTX2_CHECK_ARG(p.Cin >= 64 && (p.Cin & (p.Cin - 1)) == 0, "conv3d: Cin=%d must be a power of two >= 64", p.Cin);
+            LTX2_CHECK_ARG(p.taps_t == 3 || p.taps_t == 1, "conv3d: temporal kernel size %d (3 or 1)", p.taps_t);
+            LTX2_CHECK_ARG(p.K == 9 * p.taps_t * p.Cin, "conv3d: K=%d != 9*kt*Cin", p.K);
+            LTX2_CHECK_ARG(p.T >= 1 && (p.pad_zero || (p.H >= 2 && p.Wd >= 2)), "conv3d: reflect padding needs H,W >= 2");
+            LTX2_CHECK_ARG((long)p.T * p.H * p.Wd == p.M, "conv3d: M != T*H*W");
+            LTX2_CHECK_ARG((long)p.M * p.Cin * 2 < (1L << 31), "conv3d: activation volume must be < 2 GiB (32-bit tap offsets); decode in tiles");
+        } else {
+            LTX2_CHECK_ARG(p.lda % 8 == 0, "gemm: lda must be a multiple of 8 elements (16-byte rows)");
+        }
+        LTX2_CHECK_ARG(epilogue >= 0 && epilogue < EPI_COUNT, "gemm: unknown epilogue %d", epilogue);
+        LTX2_CHECK_ARG(epilogue != EPI_D2S_BF16 || conv, "EPI_D2S_BF16 is conv-only");
     }
-    LTX2_CHECK_ARG(p.N % 4 == 0 && p.ldo % 4 == 0 && p.ldres % 4 == 0 && p.gate_stride % 4 == 0,
-                   "gemm: N, ldo, ldres and gate_stride must be multiples of 4 (vector epilogue)");
-    if (conv) {
-        LTX2_CHECK_ARG(p.Cin >= 64 && (p.Cin & (p.Cin - 1)) == 0, "conv3d: Cin=%d must be a power of two >= 64", p.Cin);
-        LTX2_CHECK_ARG(p.taps_t == 3 || p.taps_t == 1, "conv3d: temporal kernel size %d (3 or 1)", p.taps_t);
-        LTX2_CHECK_ARG(p.K == 9 * p.taps_t * p.Cin, "conv3d: K=%d != 9*kt*Cin", p.K);
-        LTX2_CHECK_ARG(p.T >= 1 && (p.pad_zero || (p.H >= 2 && p.Wd >= 2)), "conv3d: reflect padding needs H,W >= 2");
-        LTX2_CHECK_ARG((long)p.T * p.H * p.Wd == p.M, "conv3d: M != T*H*W");
-        LTX2_CHECK_ARG((long)p.M * p.Cin * 2 < (1L << 31), "conv3d: activation volume must be < 2 GiB (32-bit tap offsets); decode in tiles");
-    } else {
-        LTX2_CHECK_ARG(p.lda % 8 == 0, "gemm: lda must be a multiple of 8 elements (16-byte rows)");
+    const int route = gemm_route(p, epilogue, conv);
+    switch (route) {
+        case ROUTE_SKINNY: return gemm_skinny_launch(p, epilogue, stream);
+        case ROUTE_V4_224: case ROUTE_V4_256: case ROUTE_V4_W8_224: case ROUTE_V4_W8_256: case ROUTE_V4_F8_224: case ROUTE_V4_F8_256:
+            return gemm_v4_launch(p, epilogue, stream, gemm_v4_kernel_of(route, p));
+        case ROUTE_PP: return gemm_pp_launch(p, epilogue, conv, stream);
+        case ROUTE_NARROW: case ROUTE_SMALL: return launch_tile(p, epilogue, conv, route == ROUTE_NARROW, stream);
+        default:            // ROUTE_INVALID: fp8 operands no kernel takes (dense bf16 operands always have a route); the 4-wave launcher's precondition check says what they lack
+            return gemm_v4_launch(p, epilogue, stream, gemm_v4_kernel_of(p.A8 ? ROUTE_V4_F8_256 : ROUTE_V4_W8_256, p));
     }
-#define CASE(E)                                                       \
-    case E:                                                           \
-        return conv ? launch_t<E, true>(p, stream) : launch_t<E, false>(p, stream);
-    switch (epilogue) {
-        CASE(EPI_BF16)
-        CASE(EPI_GELU_BF16)
-        CASE(EPI_SILU_BF16)
-        CASE(EPI_F32)
-        CASE(EPI_RESID_GATE_F32)
-        CASE(EPI_ADD_BF16)
-        case EPI_D2S_BF16:
-            LTX2_CHECK_ARG(conv, "EPI_D2S_BF16 is conv-only");
-            return launch_t<EPI_D2S_BF16, true>(p, stream);
-        default:
-            ltx2_set_error("gemm: unknown epilogue %d", epilogue);
-            return LTX2_E_INVALID;
-    }
-#undef CASE
 }
 
 int gemv_launch(const float* a, long lda, const bf16* W, const float* bias, float* out, long ldo, int M, int N, int K,

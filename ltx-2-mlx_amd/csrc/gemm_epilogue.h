@@ -182,13 +182,29 @@ int gemm_pp_launch(const GemmParams& p, int epilogue, bool conv, hipStream_t str
 bool gemm_skinny_supported(const GemmParams& p, int epilogue);
 int gemm_skinny_launch(const GemmParams& p, int epilogue, hipStream_t stream);
 
+// Host: the launchers' one switch over GemmEpilogue -- f(std::integral_constant<int, E>{}) for E == epilogue
+template <class F>
+int gemm_epilogue_dispatch(int epilogue, F&& f) {
+    switch (epilogue) {
+        case EPI_BF16: return f(std::integral_constant<int, EPI_BF16>{});
+        case EPI_GELU_BF16: return f(std::integral_constant<int, EPI_GELU_BF16>{});
+        case EPI_SILU_BF16: return f(std::integral_constant<int, EPI_SILU_BF16>{});
+        case EPI_F32: return f(std::integral_constant<int, EPI_F32>{});
+        case EPI_RESID_GATE_F32: return f(std::integral_constant<int, EPI_RESID_GATE_F32>{});
+        case EPI_ADD_BF16: return f(std::integral_constant<int, EPI_ADD_BF16>{});
+        case EPI_D2S_BF16: return f(std::integral_constant<int, EPI_D2S_BF16>{});
+        default: return LTX2_E_INVALID;
+    }
+}
+
 // 4-wave kernel with the generated asm K loop (gemm_v4.hip): dense, N % 256 == 0, K % 128 == 0, K >= 256.
-// layout 0: 1x4 waves, 32x32x16 MFMA; 1: 2x2 waves, 32x32x16; 2: 2x2 waves, 16x16x32; 3: 1x4 waves, 16x16x32 (default);
-// 4: BN = 128, 4x1 waves, 16x16x32.  bm: 0 = pick, 224 | 256 (448 | 512 for layout 4).
+// layout 3: 1x4 waves, 16x16x32 MFMA, bm 224 | 256 (var 0 dense bf16, 20 fp8-resident weights, 30 a folded norm's halves);
+// 4: BN = 128, 4x1 waves, 16x16x32, bm 448 | 512; 5 / 6: fp8 compute on 32x32x64 (bm 224 | 256) / 16x16x128 (bm 224) blocks.
 bool gemm_v4_supported(const GemmParams& p, int epilogue, bool conv);
-bool gemm_v4_w8_supported(const GemmParams& p, int epilogue);
-bool gemm_v4_vt_supported(const GemmParams& p, int epilogue, int layout);   // p.vt set: V^T written by the epilogue     // p.W8 / p.wscale set: fp8-resident weights
-int gemm_v4_launch(const GemmParams& p, int epilogue, hipStream_t stream, int layout, int bm);
+bool gemm_v4_w8_supported(const GemmParams& p, int epilogue);                // p.W8 / p.wscale set: fp8-resident weights
+bool gemm_v4_vt_supported(const GemmParams& p, int epilogue, int bm);        // p.vt set: V^T written by the epilogue of the route's 4-wave kernel with bm-row tiles
+// launches exactly the kernel it is handed (gemm.h: gemm_v4_kernel_of); the choice is gemm_route()'s
+int gemm_v4_launch(const GemmParams& p, int epilogue, hipStream_t stream, GemmV4Kernel k);
 // implicit-GEMM conv over a PADDED activation volume (p.A = [T+2][H+2][Wd+2][Cin], padding rule applied by the producer;
 // p.T / p.H / p.Wd = output extent): EPI_BF16 / EPI_ADD_BF16, Cin >= 128, Cout % 128 == 0
 bool gemm_v4_conv_supported(const GemmParams& p, int epilogue);

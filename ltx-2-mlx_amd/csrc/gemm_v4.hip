@@ -793,6 +793,36 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
     }
 }
 
+constexpr unsigned epi_bit(int e) { return 1u << e; }
+constexpr unsigned EPIS_DENSE = epi_bit(EPI_BF16) | epi_bit(EPI_GELU_BF16) | epi_bit(EPI_SILU_BF16) | epi_bit(EPI_F32) | epi_bit(EPI_RESID_GATE_F32) | epi_bit(EPI_ADD_BF16);
+constexpr unsigned EPIS_FP8 = epi_bit(EPI_BF16) | epi_bit(EPI_GELU_BF16) | epi_bit(EPI_F32) | epi_bit(EPI_RESID_GATE_F32);      // fp8-resident weights, fp8 compute
+constexpr unsigned EPIS_FOLD = epi_bit(EPI_BF16) | epi_bit(EPI_GELU_BF16) | epi_bit(EPI_RESID_GATE_F32);
+constexpr unsigned EPIS_L4 = epi_bit(EPI_BF16) | epi_bit(EPI_ADD_BF16);
+
+// the dense instantiations of one kernel identity: gemm_v4_kernel<E, LAYOUT, BM, false, VAR> for every epilogue E in EPIS
+template <int LAYOUT, int BM, int VAR, unsigned EPIS>
+int launch_v4_dense(const GemmParams& p, int epilogue, hipStream_t stream) {
+    return gemm_epilogue_dispatch(epilogue, [&](auto E) {
+        constexpr int e = decltype(E)::value;
+        if constexpr ((EPIS >> e) & 1) return launch_v4<e, LAYOUT, BM, false, VAR>(p, stream);
+        else return (int)LTX2_E_INVALID;
+    });
+}
+
+struct V4Dense {
+    GemmV4Kernel k;
+    unsigned epis;
+    int (*launch)(const GemmParams&, int, hipStream_t);
+};
+template <int LAYOUT, int BM, int VAR, unsigned EPIS>
+constexpr V4Dense v4_dense() { return {{LAYOUT, BM, VAR}, EPIS, launch_v4_dense<LAYOUT, BM, VAR, EPIS>}; }
+// every dense kernel identity that is instantiated (layout 4 is reached by tools/micro/gemm_v4_probe.hip only: the product's 128-column tiles are convs)
+const V4Dense V4_DENSE[] = {
+    v4_dense<3, 224, 0, EPIS_DENSE>(), v4_dense<3, 256, 0, EPIS_DENSE>(), v4_dense<3, 224, 30, EPIS_FOLD>(), v4_dense<3, 256, 30, EPIS_FOLD>(),
+    v4_dense<3, 224, 20, EPIS_FP8>(),  v4_dense<3, 256, 20, EPIS_FP8>(),  v4_dense<4, 448, 0, EPIS_L4>(),    v4_dense<4, 512, 0, EPIS_L4>(),
+    v4_dense<5, 224, 0, EPIS_FP8>(),   v4_dense<5, 256, 0, EPIS_FP8>(),   v4_dense<6, 224, 0, EPIS_FP8>(),
+};
+
 }  // namespace
 
 bool gemm_v4_supported(const GemmParams& p, int epilogue, bool conv) {
@@ -804,14 +834,13 @@ bool gemm_v4_supported(const GemmParams& p, int epilogue, bool conv) {
     return true;
 }
 
-// Fused V^T output (GemmParams::vt): layout 3, dense, EPI_BF16; V columns start on a tile boundary, a wave's 64 columns stay
-// inside one head, and the row tiles reach vt_npad (the zero padding of the last 64-key block is written by the last tile).
-bool gemm_v4_vt_supported(const GemmParams& p, int epilogue, int layout) {
-    if (epilogue != EPI_BF16 || (layout != 3 && layout != 5) || !p.vt) return false;
-    if (!(p.A8 ? gemm_v4_f8_supported(p, epilogue) : p.W8 ? gemm_v4_w8_supported(p, epilogue) : gemm_v4_supported(p, epilogue, false))) return false;
+// Fused V^T output (GemmParams::vt) of a problem gemm_route() sends to this kernel with bm-row tiles: EPI_BF16; V columns start on a tile
+// boundary, a wave's 64 columns stay inside one head, and the row tiles reach vt_npad (the zero padding of the last 64-key block is
+// written by the last tile).
+bool gemm_v4_vt_supported(const GemmParams& p, int epilogue, int bm) {
+    if (epilogue != EPI_BF16 || !p.vt) return false;
     if (p.vt_col0 % 256 != 0 || (p.vt_hd != 64 && p.vt_hd != 128) || (p.N - p.vt_col0) % p.vt_hd != 0) return false;
     if (p.vt_npad % 64 != 0 || p.vt_npad < p.M) return false;
-    const int bm = gemm_v4_prefer_224(p) ? 224 : 256;
     return (long)((p.M + bm - 1) / bm) * bm >= p.vt_npad;
 }
 
@@ -832,86 +861,22 @@ bool gemm_v4_f8_supported(const GemmParams& p, int epilogue) {
     return true;
 }
 
-// layout: 3 | 4 | 5 (see the file comment); bm: 0 = pick, 224 | 256 (layouts 3, 5), 448 | 512 (layout 4)
-int gemm_v4_launch(const GemmParams& p, int epilogue, hipStream_t stream, int layout, int bm) {
-    if (p.A8) {     // fp8 compute: layout 5
+int gemm_v4_launch(const GemmParams& p, int epilogue, hipStream_t stream, GemmV4Kernel k) {
+    // the preconditions of the kernel handed in
+    if (k.layout == 5 || k.layout == 6)
         LTX2_CHECK_ARG(gemm_v4_f8_supported(p, epilogue), "gemm_v4: fp8 compute needs A8 + ascale + W8 + wscale, N %% 256 == 0, K %% 256 == 0, K >= 512, a dense bf16/gelu/f32/residual epilogue (N=%d K=%d epilogue=%d)", p.N, p.K, epilogue);
-        const bool b224 = bm ? bm == 224 : gemm_v4_prefer_224(p);
-#ifndef LTX2_F8_FORCE_L5
-#define LTX2_F8_FORCE_L5 0          // (A/B builds: -DLTX2_F8_FORCE_L5=1 keeps every fp8 GEMM on layout 5)
-#endif
-        const bool l5 = layout == 5 || LTX2_F8_FORCE_L5;
-        // 224-row tiles: the 16x16x128 form (layout 6; +16 % FLOP per joule on random e4m3 operands, tools/micro/mfma_fp8_power.hip); layout 5 keeps
-        // the 256-row tiles (and the 224-row ones when asked for by `layout`)
-#define CASEF(E) \
-    case E:      \
-        return b224 ? (l5 ? launch_v4<E, 5, 224>(p, stream) : launch_v4<E, 6, 224>(p, stream)) : launch_v4<E, 5, 256>(p, stream);
-        switch (epilogue) {
-            CASEF(EPI_BF16)
-            CASEF(EPI_GELU_BF16)
-            CASEF(EPI_F32)
-            CASEF(EPI_RESID_GATE_F32)
-        }
-#undef CASEF
-        return LTX2_E_INVALID;
-    }
-    if (p.W8) {     // fp8-resident weights: layout 3 only
+    else if (k.var == 20)
         LTX2_CHECK_ARG(p.wscale && gemm_v4_w8_supported(p, epilogue), "gemm_v4: fp8-resident weights need N %% 256 == 0, K %% 128 == 0, K >= 256, a dense bf16/gelu/f32/residual epilogue (N=%d K=%d epilogue=%d)", p.N, p.K, epilogue);
-        const bool b224 = bm ? bm == 224 : gemm_v4_prefer_224(p);
-#define CASE8(E) \
-    case E:      \
-        return b224 ? launch_v4<E, 3, 224, false, 20>(p, stream) : launch_v4<E, 3, 256, false, 20>(p, stream);
-        switch (epilogue) {
-            CASE8(EPI_BF16)
-            CASE8(EPI_GELU_BF16)
-            CASE8(EPI_F32)
-            CASE8(EPI_RESID_GATE_F32)
-        }
-#undef CASE8
+    else if (k.layout == 4)
+        LTX2_CHECK_ARG(p.N % 128 == 0, "gemm_v4 layout 4: N %% 128");
+    for (const V4Dense& d : V4_DENSE) {
+        if (d.k.layout != k.layout || d.k.bm != k.bm || d.k.var != k.var) continue;
+        if (epilogue >= 0 && epilogue < EPI_COUNT && ((d.epis >> epilogue) & 1)) return d.launch(p, epilogue, stream);
+        ltx2_set_error(k.layout == 4 ? "gemm_v4 layout 4: unsupported epilogue %d" : k.var == 30 ? "gemm_v4: a folded norm on epilogue %d" : "gemm_v4: unsupported epilogue %d", epilogue);
         return LTX2_E_INVALID;
     }
-    if (layout == 4) {
-        LTX2_CHECK_ARG(p.N % 128 == 0, "gemm_v4 layout 4: N %% 128");
-        const bool b448 = bm == 448;
-#define CASE4(E) \
-    case E:      \
-        return b448 ? launch_v4<E, 4, 448>(p, stream) : launch_v4<E, 4, 512>(p, stream);
-        switch (epilogue) {
-            CASE4(EPI_BF16)
-            CASE4(EPI_ADD_BF16)
-            default:
-                ltx2_set_error("gemm_v4 layout 4: unsupported epilogue %d", epilogue);
-                return LTX2_E_INVALID;
-        }
-#undef CASE4
-    }
-    const bool b224 = bm ? bm == 224 : gemm_v4_prefer_224(p);
-    LTX2_CHECK_ARG(layout == 3, "gemm_v4: wave layout %d (3 = bf16 dense, 4 = 128-column convs, 5 = fp8 compute)", layout);
-    if (p.shadow || p.rf_parts) {      // a folded norm's producer / consumer half: the VAR = 30 instantiations
-        switch (epilogue) {
-            case EPI_BF16: return b224 ? launch_v4<EPI_BF16, 3, 224, false, 30>(p, stream) : launch_v4<EPI_BF16, 3, 256, false, 30>(p, stream);
-            case EPI_GELU_BF16: return b224 ? launch_v4<EPI_GELU_BF16, 3, 224, false, 30>(p, stream) : launch_v4<EPI_GELU_BF16, 3, 256, false, 30>(p, stream);
-            case EPI_RESID_GATE_F32: return b224 ? launch_v4<EPI_RESID_GATE_F32, 3, 224, false, 30>(p, stream) : launch_v4<EPI_RESID_GATE_F32, 3, 256, false, 30>(p, stream);
-            default:
-                ltx2_set_error("gemm_v4: a folded norm on epilogue %d", epilogue);
-                return LTX2_E_INVALID;
-        }
-    }
-#define CASE(E) \
-    case E:     \
-        return b224 ? launch_v4<E, 3, 224>(p, stream) : launch_v4<E, 3, 256>(p, stream);
-    switch (epilogue) {
-        CASE(EPI_BF16)
-        CASE(EPI_GELU_BF16)
-        CASE(EPI_SILU_BF16)
-        CASE(EPI_F32)
-        CASE(EPI_RESID_GATE_F32)
-        CASE(EPI_ADD_BF16)
-        default:
-            ltx2_set_error("gemm_v4: unsupported epilogue %d", epilogue);
-            return LTX2_E_INVALID;
-    }
-#undef CASE
+    ltx2_set_error("gemm_v4: wave layout %d (3 = bf16 dense, 4 = 128-column convs, 5 = fp8 compute)", k.layout);
+    return LTX2_E_INVALID;
 }
 
 // Implicit-GEMM 3x3x3 (or per-frame 3x3) conv over a PADDED channels-last activation volume: p.A = [T+2][H+2][Wd+2][Cin] with
@@ -1011,9 +976,11 @@ int gemm_v4_conv_launch(const GemmParams& p_in, int epilogue, hipStream_t stream
 
 #ifdef LTX2_V4_PROBE
 // ablations of the 256-row DiT kernel: var 1 = no DMA in the loop, 2 = no fragment reads, 9 = direct (untransposed) epilogue
-int gemm_v4_probe_launch(const GemmParams& p, int layout, int var, hipStream_t stream) {
-    (void)layout;
-    if (var == 9) return launch_v4<EPI_BF16, 3, 224, false, 9>(p, stream);
-    return var == 1 ? launch_v4<EPI_BF16, 3, 256, false, 1>(p, stream) : launch_v4<EPI_BF16, 3, 256, false, 2>(p, stream);
+int gemm_v4_probe_launch(const GemmParams& p, GemmV4Kernel k, hipStream_t stream) {
+    if (k.layout == 3 && k.bm == 224 && k.var == 9) return launch_v4<EPI_BF16, 3, 224, false, 9>(p, stream);
+    if (k.layout == 3 && k.bm == 256 && k.var == 1) return launch_v4<EPI_BF16, 3, 256, false, 1>(p, stream);
+    if (k.layout == 3 && k.bm == 256 && k.var == 2) return launch_v4<EPI_BF16, 3, 256, false, 2>(p, stream);
+    ltx2_set_error("gemm_v4 probe: no ablation kernel of layout %d, %d rows, variant %d", k.layout, k.bm, k.var);
+    return LTX2_E_INVALID;
 }
 #endif

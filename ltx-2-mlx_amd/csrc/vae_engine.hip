@@ -84,7 +84,7 @@ Plan plan_sizes(const ltx2_vae_config& cfg, int T, int H, int W) {
 bool vae_v4_enabled() { return true; }     // (round 2's LTX2_VAE_V4=0 switch back to the tap-iterator kernels is gone)
 
 GemmParams conv_params(const bf16* x, const bf16* w, const float* b, void* out, int T, int H, int W, int Cin, int Cout, int causal,
-                       const bf16* res) {
+                       const bf16* res, int taps_t = 3) {
     GemmParams p{};
     p.A = x;
     p.W = w;
@@ -92,8 +92,8 @@ GemmParams conv_params(const bf16* x, const bf16* w, const float* b, void* out, 
     p.out = out;
     p.M = T * H * W;
     p.N = Cout;
-    p.K = 27 * Cin;
-    p.taps_t = 3;
+    p.K = 9 * taps_t * Cin;
+    p.taps_t = taps_t;
     p.ldo = Cout;
     p.res = res;
     p.ldres = Cout;
@@ -102,7 +102,7 @@ GemmParams conv_params(const bf16* x, const bf16* w, const float* b, void* out, 
     p.Wd = W;
     p.Cin = Cin;
     p.cin_shift = ilog2(Cin);
-    p.pad_front = causal ? 2 : 1;
+    p.pad_front = taps_t == 1 ? 0 : (causal ? 2 : 1);
     return p;
 }
 
@@ -115,25 +115,8 @@ bool conv_on_v4(int T, int H, int W, int Cin, int Cout, int epi, void* out) {
 
 int conv(const bf16* x, const bf16* w, const float* b, void* out, int T, int H, int W, int Cin, int Cout, int causal,
          int epi, const bf16* res, int ft, int fh, int fw, int residual, hipStream_t st, int pad_zero = 0, int taps_t = 3) {
-    GemmParams p{};
-    p.A = x;
-    p.W = w;
-    p.bias = b;
-    p.out = out;
-    p.M = T * H * W;
-    p.N = Cout;
-    p.K = 9 * taps_t * Cin;
-    p.taps_t = taps_t;
+    GemmParams p = conv_params(x, w, b, out, T, H, W, Cin, Cout, causal, res, taps_t);
     p.pad_zero = pad_zero;
-    p.ldo = Cout;
-    p.res = res;
-    p.ldres = Cout;
-    p.T = T;
-    p.H = H;
-    p.Wd = W;
-    p.Cin = Cin;
-    p.cin_shift = ilog2(Cin);
-    p.pad_front = taps_t == 1 ? 0 : (causal ? 2 : 1);
     if (epi == EPI_D2S_BF16) {
         const int sp = ft * fh * fw;
         LTX2_CHECK_ARG(Cout % sp == 0, "conv3d d2s: Cout=%d not divisible by stride product %d", Cout, sp);

@@ -711,6 +711,44 @@ def test_gemm_dispatch_routes_of_every_model_gemm():
     assert set(re.findall(r'getenv\("(\w+)"\)', src)) == set(), "tuning switches belong in A/B builds (tools/ab_build.py + LTX2HIP_LIB), not in the product"
 
 
+_ROUTE_GRID = ((1, 16, 64, 128, 129, 512, 1023, 1024, 1100, 3456, 4096, 13824),                 # M
+               (48, 64, 128, 200, 256, 2048, 4096, 8192, 10240, 12288, 16384),                  # N
+               (64, 128, 192, 256, 384, 512, 3840, 4096, 16384, 188160),                        # K
+               range(6), range(3), range(2))                                                    # epilogue, weights, has_vt
+_ROUTE_GOLDEN = os.path.join(ROOT, "tests", "golden", "gemm_routes.txt")
+
+
+def _gemm_route_table(L):
+    """One character per cell of the full cross product of _ROUTE_GRID, has_vt fastest: 'A' + (route + 1) + 11 * fused (ROUTE_INVALID = -1)."""
+    import itertools
+    out = []
+    for cell in itertools.product(*_ROUTE_GRID):
+        r = L.ltx2_gemm_route(*cell)
+        out.append(chr(65 + (r & 0xff) + 1 + (11 if r & 0x100 else 0)) if r >= 0 else "A")
+    return "".join(out)
+
+
+def test_gemm_route_table_matches_the_recorded_dispatch():
+    """The whole dispatch surface against a table recorded BEFORE gemm_route() became the launcher's only decider: every (M, N, K,
+    epilogue, weights, has_vt) of _ROUTE_GRID (47 520 cells, none skipped), route byte and fused-V^T bit.  tests/golden/gemm_routes.txt was
+    written from a library built at the parent commit of that change (never from the code under test), by
+        LTX2HIP_LIB=<parent build>/libltx2hip.so python -c "from tests import test_host_cpu as t; from ltx_2_mlx_amd import _native as nv;
+        open(t._ROUTE_GOLDEN, 'w').write(t._gemm_route_table(nv.lib()))"
+    A deliberate re-plan of a route re-records the table the same way, from the build that carries the new plan."""
+    import itertools
+    import torch
+    from ltx_2_mlx_amd import _native as nv
+    want = open(_ROUTE_GOLDEN).read()
+    cells = list(itertools.product(*_ROUTE_GRID))
+    assert len(want) == len(cells) == 47520
+    dec = lambda ch: ((ord(ch) - 65) % 11 - 1, (ord(ch) - 65) // 11)      # (route, fused)
+    for dt in (torch.bfloat16, torch.float16):          # both builds carry the same host logic
+        got = _gemm_route_table(nv.lib(dt))
+        if got != want:
+            i = next(j for j in range(len(cells)) if got[j] != want[j])
+            raise AssertionError(f"{dt}: (M, N, K, epilogue, weights, vt) = {cells[i]}: (route, fused) = {dec(got[i])}, recorded {dec(want[i])}")
+
+
 def _binding_kinds(fn_node):
     """name -> set of kinds it is bound to inside one function body (nested functions are their own scope).  kind: "ctor:<dotted call>" when the
     value is a call whose last attribute is Capitalised (torch.Generator(...), torch.cuda.Stream(), LTXModel(...)), else a coarse tag."""

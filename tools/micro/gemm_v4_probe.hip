@@ -32,12 +32,12 @@ static float time_launch(int (*fn)(const GemmParams&, void*), const GemmParams& 
     hipEventDestroy(e0); hipEventDestroy(e1);
     return ms / iters * 1e3f;
 }
-struct Ctx { int kind, layout, arg, epi; };     // kind 0: ping-pong; 1: ablation (arg = variant); 2: v4 (arg = bm, 0 = auto)
+struct Ctx { int kind; GemmV4Kernel k; int epi; };     // kind 0: ping-pong; 1: ablation kernel k; 2: v4 kernel k (layout, rows per tile, variant)
 static int run(const GemmParams& p, void* c) {
     const Ctx* x = (const Ctx*)c;
     if (x->kind == 0) return gemm_pp_launch(p, x->epi, false, 0);
-    if (x->kind == 1) return gemm_v4_probe_launch(p, x->layout, x->arg, 0);
-    return gemm_v4_launch(p, x->epi, 0, x->layout, x->arg);
+    if (x->kind == 1) return gemm_v4_probe_launch(p, x->k, 0);
+    return gemm_v4_launch(p, x->epi, 0, x->k);
 }
 
 static void one_shape(int M, int N, int K, bool ablations) {
@@ -52,20 +52,20 @@ static void one_shape(int M, int N, int K, bool ablations) {
     hipMalloc(&x0, no * 4); hipMalloc(&x1, no * 4); hipMalloc(&gate, (size_t)N * 4);
     hipMemcpy(a, ha.data(), na * 2, hipMemcpyHostToDevice); hipMemcpy(w, hw.data(), nw * 2, hipMemcpyHostToDevice);
     { std::vector<float> g(N); for (auto& v : g) v = r.gauss(); hipMemcpy(gate, g.data(), (size_t)N * 4, hipMemcpyHostToDevice); }
-    GemmParams p{};
-    p.A = a; p.W = w; p.lda = K; p.ldo = N; p.M = M; p.N = N; p.K = K;
+    GemmParams p = gemm_dense_params(a, K, w, nullptr, nullptr, N, M, N, K);
+    const int ab = gemm_v4_prefer_224(p) ? 224 : 256;       // "auto": the tile height gemm_route() would take
     const double flop = 2.0 * M * N * K;
     printf("== M=%d N=%d K=%d  (%.1f GF)\n", M, N, K, flop / 1e9);
 
     // ---- correctness: v4 (both row-block counts) vs ping-pong, bit for bit, plus sampled fp64 host check ----
     std::vector<unsigned short> href(no), hnew(no);
     p.out = o_ref; hipMemset(o_ref, 0, no * 2);
-    Ctx cpp{0, 0, 0, EPI_BF16}; run(p, &cpp); hipDeviceSynchronize();
+    Ctx cpp{0, {}, EPI_BF16}; run(p, &cpp); hipDeviceSynchronize();
     hipMemcpy(href.data(), o_ref, no * 2, hipMemcpyDeviceToHost);
     for (int cfg = 0; cfg < 8; ++cfg) {
         const int layout = cfg >> 1, rb = (cfg & 1) ? 256 : 224;
         p.out = o_new; hipMemset(o_new, 0xff, no * 2);
-        Ctx c{2, layout, rb, EPI_BF16}; int rc = run(p, &c); hipError_t e = hipDeviceSynchronize();
+        Ctx c{2, {layout, rb, 0}, EPI_BF16}; int rc = run(p, &c); hipError_t e = hipDeviceSynchronize();
         hipMemcpy(hnew.data(), o_new, no * 2, hipMemcpyDeviceToHost);
         size_t bad = 0; double maxd = 0; size_t first = (size_t)-1;
         for (size_t i = 0; i < no; ++i) if (href[i] != hnew[i]) { if (!bad) first = i; ++bad; maxd = std::max(maxd, (double)fabsf(bf2f_host(href[i]) - bf2f_host(hnew[i]))); }
@@ -85,8 +85,8 @@ static void one_shape(int M, int N, int K, bool ablations) {
         std::vector<float> hx(no); for (auto& v : hx) v = r.gauss();
         hipMemcpy(x0, hx.data(), no * 4, hipMemcpyHostToDevice); hipMemcpy(x1, hx.data(), no * 4, hipMemcpyHostToDevice);
         GemmParams q = p; q.gate_table = gate;
-        q.out = x0; Ctx c0{0, 0, 0, EPI_RESID_GATE_F32}; run(q, &c0);
-        q.out = x1; Ctx c1{2, 1, 0, EPI_RESID_GATE_F32}; run(q, &c1);
+        q.out = x0; Ctx c0{0, {}, EPI_RESID_GATE_F32}; run(q, &c0);
+        q.out = x1; Ctx c1{2, {1, ab, 0}, EPI_RESID_GATE_F32}; run(q, &c1);
         hipDeviceSynchronize();
         std::vector<float> h0(no), h1(no);
         hipMemcpy(h0.data(), x0, no * 4, hipMemcpyDeviceToHost); hipMemcpy(h1.data(), x1, no * 4, hipMemcpyDeviceToHost);
@@ -98,27 +98,25 @@ static void one_shape(int M, int N, int K, bool ablations) {
     struct V { const char* name; Ctx c; void* out; std::vector<float> t; unsigned long long cyc[3] = {0, 0, 0}; };
     if (!g_dbg) hipMalloc(&g_dbg, 64);
     std::vector<V> vs;
-    vs.push_back({"pp  auto  bf16", {0, 0, 0, EPI_BF16}, o_ref});
-    vs.push_back({"v4 L14 auto bf16", {2, 0, 0, EPI_BF16}, o_new});
-    vs.push_back({"v4 L22 auto bf16", {2, 1, 0, EPI_BF16}, o_new});
-    vs.push_back({"v4 L22 256  bf16", {2, 1, 256, EPI_BF16}, o_new});
-    vs.push_back({"v4 M16 auto bf16", {2, 2, 0, EPI_BF16}, o_new});
-    vs.push_back({"v4 M16 256  bf16", {2, 2, 256, EPI_BF16}, o_new});
-    vs.push_back({"v4 M16x14 auto bf16", {2, 3, 0, EPI_BF16}, o_new});
-    vs.push_back({"v4 M16x14 256 bf16", {2, 3, 256, EPI_BF16}, o_new});
-    vs.push_back({"pp  auto  gelu", {0, 0, 0, EPI_GELU_BF16}, o_ref});
-    vs.push_back({"v4 M16x14 auto gelu", {2, 3, 0, EPI_GELU_BF16}, o_new});
-    vs.push_back({"pp  auto  resid", {0, 0, 0, EPI_RESID_GATE_F32}, x0});
-    vs.push_back({"v4 L14 auto resid", {2, 0, 0, EPI_RESID_GATE_F32}, x1});
-    vs.push_back({"v4 L22 auto resid", {2, 1, 0, EPI_RESID_GATE_F32}, x1});
-    vs.push_back({"v4 M16 auto resid", {2, 2, 0, EPI_RESID_GATE_F32}, x1});
-    vs.push_back({"v4 M16x14 auto resid", {2, 3, 0, EPI_RESID_GATE_F32}, x1});
+    vs.push_back({"pp  auto  bf16", {0, {}, EPI_BF16}, o_ref});
+    vs.push_back({"v4 L14 auto bf16", {2, {0, ab, 0}, EPI_BF16}, o_new});
+    vs.push_back({"v4 L22 auto bf16", {2, {1, ab, 0}, EPI_BF16}, o_new});
+    vs.push_back({"v4 L22 256  bf16", {2, {1, 256, 0}, EPI_BF16}, o_new});
+    vs.push_back({"v4 M16 auto bf16", {2, {2, ab, 0}, EPI_BF16}, o_new});
+    vs.push_back({"v4 M16 256  bf16", {2, {2, 256, 0}, EPI_BF16}, o_new});
+    vs.push_back({"v4 M16x14 auto bf16", {2, {3, ab, 0}, EPI_BF16}, o_new});
+    vs.push_back({"v4 M16x14 256 bf16", {2, {3, 256, 0}, EPI_BF16}, o_new});
+    vs.push_back({"pp  auto  gelu", {0, {}, EPI_GELU_BF16}, o_ref});
+    vs.push_back({"v4 M16x14 auto gelu", {2, {3, ab, 0}, EPI_GELU_BF16}, o_new});
+    vs.push_back({"pp  auto  resid", {0, {}, EPI_RESID_GATE_F32}, x0});
+    vs.push_back({"v4 L14 auto resid", {2, {0, ab, 0}, EPI_RESID_GATE_F32}, x1});
+    vs.push_back({"v4 L22 auto resid", {2, {1, ab, 0}, EPI_RESID_GATE_F32}, x1});
+    vs.push_back({"v4 M16 auto resid", {2, {2, ab, 0}, EPI_RESID_GATE_F32}, x1});
+    vs.push_back({"v4 M16x14 auto resid", {2, {3, ab, 0}, EPI_RESID_GATE_F32}, x1});
     if (ablations) {
-        vs.push_back({"v4 M16 256 no-DMA", {1, 2, 1, EPI_BF16}, o_new});
-        vs.push_back({"v4 M16 256 no-read", {1, 2, 2, EPI_BF16}, o_new});
-        vs.push_back({"v4 M16x14 224 direct epi", {1, 3, 9, EPI_BF16}, o_new});
-        vs.push_back({"v4 M16x14 224 rd/2", {1, 3, 10, EPI_BF16}, o_new});
-        vs.push_back({"v4 M16x14 224 dma/4", {1, 3, 11, EPI_BF16}, o_new});
+        vs.push_back({"v4 M16 256 no-DMA", {1, {3, 256, 1}, EPI_BF16}, o_new});
+        vs.push_back({"v4 M16 256 no-read", {1, {3, 256, 2}, EPI_BF16}, o_new});
+        vs.push_back({"v4 M16x14 224 direct epi", {1, {3, 224, 9}, EPI_BF16}, o_new});
     }
     for (int round = 0; round < 5; ++round)
         for (auto& v : vs) {
