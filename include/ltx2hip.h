@@ -184,6 +184,17 @@ int ltx2_conv3d_fused(const void* x, const void* w, const float* bias, void* out
 int ltx2_groupnorm_silu(const void* x, const void* res, void* y, int64_t P, int C, int groups, float eps,
                         const float* gamma, const float* beta, float* scratch, int act, void* stream);
 
+/* Per-frame GroupNorm of the temporal upscaler (upscaler/temporal.py:128-147, 278-285: reshape to (B*T, H, W, C), then
+ * mlx.nn.GroupNorm): x[frames][P_frame][C] channels-last 16-bit, statistics per (frame, group), fused with the affine, an
+ * optional residual add and SiLU as above.  interleaved != 0: group of channel c is c % groups (mlx.nn.GroupNorm without
+ * pytorch_compatible, what the reference constructs); interleaved == 0: c / (C/groups) (torch.nn.GroupNorm).  One launch;
+ * a frame's slab of groups stays in registers between the sums and the apply where it fits, otherwise x is read twice.
+ * Statistics and the affine are fp64, in a fixed order without atomics (bit-reproducible).  scratch is unused (may be
+ * null): it keeps the call shape of ltx2_groupnorm_silu.  Accepts every (C, groups) that entry accepts.          */
+int ltx2_groupnorm_frames_silu(const void* x, const void* res, void* y, int frames, int64_t P_frame, int C, int groups,
+                               int interleaved, float eps, const float* gamma, const float* beta, float* scratch, int act,
+                               void* stream);
+
 /* VAE encoder SpaceToDepthDownsample3d tail (simple_encoder.py:183-257): y = conv(x') [T][H][W][Cc] and the conv
  * input x' [T][H][W][Cin] (first frame already duplicated when st = 2) ->
  * out[T/st][H/sh][W/sw][Cc*sp] = space_to_depth(y) + group_mean(space_to_depth(x')), sp = st*sh*sw,

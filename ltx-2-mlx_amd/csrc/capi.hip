@@ -332,6 +332,12 @@ int ltx2_groupnorm_silu(const void* x, const void* res, void* y, int64_t P, int 
     return groupnorm_silu_launch((const bf16*)x, (const bf16*)res, (bf16*)y, P, C, groups, eps, gamma, beta, scratch, act, (hipStream_t)stream);
 }
 
+int ltx2_groupnorm_frames_silu(const void* x, const void* res, void* y, int frames, int64_t P_frame, int C, int groups, int interleaved,
+                               float eps, const float* gamma, const float* beta, float* scratch, int act, void* stream) {
+    return groupnorm_frames_silu_launch((const bf16*)x, (const bf16*)res, (bf16*)y, frames, P_frame, C, groups, interleaved, eps, gamma, beta,
+                                        scratch, act, (hipStream_t)stream);
+}
+
 int ltx2_s2d_downsample(const void* y, const void* x, void* out, int T, int H, int W, int Cc, int Cin, int st, int sh,
                         int sw, void* stream) {
     return s2d_downsample_launch((const bf16*)y, (const bf16*)x, (bf16*)out, T, H, W, Cc, Cin, st, sh, sw, (hipStream_t)stream);

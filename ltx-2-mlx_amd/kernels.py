@@ -328,6 +328,20 @@ def groupnorm_silu(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, gro
     return y
 
 
+def groupnorm_frames_silu(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, groups: int = 32, eps: float = 1e-5,
+                          res: Optional[torch.Tensor] = None, act: bool = True, interleaved: bool = True) -> torch.Tensor:
+    """y = [silu](GroupNorm(x[f] over (group, H, W)) * gamma + beta + res) per frame f of channels-last 16-bit x [F, ..., C]
+    (temporal upscaler, upscaler/temporal.py:128-147).  interleaved: group of channel c is c % groups (mlx.nn.GroupNorm's
+    default, what the reference runs); otherwise c // (C // groups) as in torch.nn.GroupNorm."""
+    assert x.dtype in ACT16 and x.is_contiguous() and x.dim() >= 2
+    assert res is None or (res.dtype == x.dtype and res.shape == x.shape and res.is_contiguous())
+    frames, C = x.shape[0], x.shape[-1]
+    y = torch.empty_like(x)
+    nv.check(_L(x).ltx2_groupnorm_frames_silu(nv.ptr(x), nv.ptr(res), nv.ptr(y), frames, x.numel() // (frames * C), C, groups, int(interleaved), eps,
+                                              nv.ptr(_c(gamma.float())), nv.ptr(_c(beta.float())), None, int(act), nv.stream()))
+    return y
+
+
 def s2d_downsample(y: torch.Tensor, x: torch.Tensor, stride: Tuple[int, int, int]) -> torch.Tensor:
     """space_to_depth(y) + group_mean(space_to_depth(x)) on channels-last bf16 [T,H,W,C] (VAE encoder downsample)."""
     assert y.dtype in ACT16 and x.dtype == y.dtype and y.shape[:3] == x.shape[:3]

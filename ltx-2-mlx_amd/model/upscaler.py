@@ -1,4 +1,4 @@
-"""Spatial x2 latent upscaler on MI355X behind the reference's API
+"""Spatial x2 and temporal x2 latent upscalers on MI355X behind the reference's API
 (LTX_2_MLX/model/upscaler/spatial.py:131-181 ResBlock3d, :267-323 SpatialRationalResampler, :326-411
 SpatialUpscaler, :414-538 load_spatial_upscaler_weights; call site pipelines/distilled.py:394-405).
 
@@ -6,7 +6,12 @@ conv3d (zero padding) and the per-frame conv2d + PixelShuffle run on the implici
 (`ltx2_conv3d_fused` with pad_zero / kt=1 / depth-to-space epilogue); GroupNorm(32) + affine (+ residual)
 + SiLU is one statistics pass and one apply pass (`ltx2_groupnorm_silu`).  Activations are channels-last
 bf16 in HBM; the un-normalize / normalize bracket of the call site is fused into the layout changes at
-both ends (`upscale_latent`)."""
+both ends (`upscale_latent`).
+
+TemporalUpscaler (LTX_2_MLX/model/upscaler/temporal.py:94-149 ResBlock3d, :152-215 TemporalPixelShuffle, :218-307
+TemporalUpscaler, :310-416 load_temporal_upscaler_weights; call site scripts/generate.py:2039-2077) shares the conv kernel
+(the temporal shuffle with the dropped first frame is its mode-2 epilogue with stride (2, 1, 1)); its GroupNorm takes
+statistics per FRAME over interleaved groups, one launch of `ltx2_groupnorm_frames_silu`."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional, Union
@@ -148,3 +153,120 @@ def load_spatial_upscaler_weights(upscaler: SpatialUpscaler, weights_path: str) 
         for k in f.keys():
             sd[k] = f.get_tensor(k)
     upscaler.load_state_dict(sd, strict=True)
+
+
+class TemporalUpscaler:
+    """latent (B, 128, F, H, W) -> (B, 128, 2F - 1, H, W).  Constructor keywords as reference temporal.py:234-240.
+
+    checkpoint_semantics=False (default) computes what the reference computes: GroupNorm per frame with MLX's default
+    grouping (group of channel c = c % num_groups, temporal.py:131-134 + mlx.nn.GroupNorm without pytorch_compatible), and
+    the temporal shuffle reading input channel p * C + c for output frame 2t + p (temporal.py:204-213).
+    checkpoint_semantics=True computes what the upstream PyTorch model the checkpoint was trained as computes:
+    torch.nn.GroupNorm on the 5-D tensor (whole clip, contiguous groups) and the shuffle "b (c p1) f h w" (channel 2c + p).
+    Which of the two the released weights want is not verified: no temporal-upscaler checkpoint was available."""
+
+    def __init__(self, latent_channels: int = 128, hidden_channels: int = 512, num_res_blocks: int = 4, num_groups: int = 32,
+                 device: Union[str, torch.device] = "cuda", checkpoint_semantics: bool = False):
+        self.latent_channels, self.hidden_channels, self.num_groups = latent_channels, hidden_channels, num_groups
+        self.num_res_blocks = num_res_blocks
+        self.checkpoint_semantics = bool(checkpoint_semantics)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("TemporalUpscaler runs on the MI355X only (no CPU fallback); got device " + str(device))
+        self._w: Dict[str, torch.Tensor] = {}
+        self._loaded = False
+
+    # ------------------------------------------------------------------ weights
+    def expected_weight_shapes(self) -> Dict[str, tuple]:
+        c, m = self.latent_channels, self.hidden_channels
+        s = {"initial_conv.weight": (m, c, 3, 3, 3), "initial_conv.bias": (m,), "initial_norm.weight": (m,), "initial_norm.bias": (m,),
+             "upsampler.0.weight": (2 * m, m, 3, 3, 3), "upsampler.0.bias": (2 * m,),
+             "final_conv.weight": (c, m, 3, 3, 3), "final_conv.bias": (c,)}
+        for stage in ("res_blocks", "post_upsample_res_blocks"):
+            for i in range(self.num_res_blocks):
+                for cv in ("conv1", "conv2"):
+                    s[f"{stage}.{i}.{cv}.weight"] = (m, m, 3, 3, 3)
+                    s[f"{stage}.{i}.{cv}.bias"] = (m,)
+                for nm in ("norm1", "norm2"):
+                    s[f"{stage}.{i}.{nm}.weight"] = (m,)
+                    s[f"{stage}.{i}.{nm}.bias"] = (m,)
+        return s
+
+    def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True) -> None:
+        """Checkpoint keys of ltx-2-temporal-upscaler-x2 (temporal.py:345-376)."""
+        exp = self.expected_weight_shapes()
+        missing = [k for k in exp if k not in sd]
+        if missing and strict:
+            raise KeyError(f"missing {len(missing)} temporal upscaler weights, e.g. {missing[:4]}")
+        for k, shp in exp.items():
+            if k in sd and tuple(sd[k].shape) != shp:
+                raise ValueError(f"weight {k}: shape {tuple(sd[k].shape)} != expected {shp}")
+        dev = self.device
+        # the reference's shuffle packing p * C + c is the engine's own row order n' = s * Cf + c; the upstream packing 2c + p is permuted to it
+        d2s = (2, 1, 1) if self.checkpoint_semantics else None
+        for k in exp:
+            if k not in sd:
+                continue
+            t = sd[k].to(dev)
+            if k == "upsampler.0.weight":
+                self._w[k] = K.conv_weight_to_engine(t, d2s_stride=d2s)
+            elif k == "upsampler.0.bias":
+                self._w[k] = K.conv_bias_to_engine(t, d2s)
+            elif t.dim() == 5:
+                self._w[k] = K.conv_weight_to_engine(t)
+            else:
+                self._w[k] = t.to(torch.float32).contiguous()
+        self._loaded = True
+
+    init_random_weights = SpatialUpscaler.init_random_weights
+
+    # ------------------------------------------------------------------ forward
+    def _norm(self, x: torch.Tensor, name: str, res: Optional[torch.Tensor] = None) -> torch.Tensor:
+        w, G = self._w, self.num_groups
+        if self.checkpoint_semantics:
+            return K.groupnorm_silu(x, w[name + ".weight"], w[name + ".bias"], G, res=res)
+        return K.groupnorm_frames_silu(x, w[name + ".weight"], w[name + ".bias"], G, res=res, interleaved=True)
+
+    def _res_block(self, x: torch.Tensor, prefix: str) -> torch.Tensor:
+        """conv1 -> norm1 -> SiLU -> conv2 -> norm2 -> SiLU(x + residual)  (temporal.py:117-149)."""
+        w = self._w
+        h = K.conv3d(x, w[prefix + ".conv1.weight"], w[prefix + ".conv1.bias"], pad_zero=True)
+        h = self._norm(h, prefix + ".norm1")
+        h = K.conv3d(h, w[prefix + ".conv2.weight"], w[prefix + ".conv2.bias"], pad_zero=True)
+        return self._norm(h, prefix + ".norm2", res=x)
+
+    def forward_nhwc(self, x: torch.Tensor) -> torch.Tensor:
+        """x bf16 [F,H,W,C] channels-last -> bf16 [2F-1,H,W,C]  (temporal.py:265-307)."""
+        if not self._loaded:
+            raise RuntimeError("TemporalUpscaler: weights not loaded")
+        w = self._w
+        x = K.conv3d(x, w["initial_conv.weight"], w["initial_conv.bias"], pad_zero=True)
+        x = self._norm(x, "initial_norm")
+        for i in range(self.num_res_blocks):
+            x = self._res_block(x, f"res_blocks.{i}")
+        # conv3d C -> 2C, temporal shuffle, first frame dropped (temporal.py:184-188, 293-296): the conv's depth-to-space epilogue
+        x = K.conv3d(x, w["upsampler.0.weight"], w["upsampler.0.bias"], mode=2, stride=(2, 1, 1), pad_zero=True)
+        for i in range(self.num_res_blocks):
+            x = self._res_block(x, f"post_upsample_res_blocks.{i}")
+        return K.conv3d(x, w["final_conv.weight"], w["final_conv.bias"], pad_zero=True)
+
+    def __call__(self, x: torch.Tensor) -> torch.Tensor:
+        """x (1, C, F, H, W) float -> (1, C, 2F - 1, H, W) fp32."""
+        if x.dim() != 5 or x.shape[0] != 1 or x.shape[1] != self.latent_channels:
+            raise ValueError(f"expected (1, {self.latent_channels}, F, H, W), got {tuple(x.shape)}")
+        dev = self.device
+        one, zero = torch.ones(self.latent_channels, device=dev), torch.zeros(self.latent_channels, device=dev)
+        y = self.forward_nhwc(K.latent_unnormalize_nhwc(x[0].to(dev, torch.float32), zero, one))
+        return K.latent_normalize_nchw(y, zero, one)[None]
+
+
+def upscale_latent_temporal(latent: torch.Tensor, upscaler: TemporalUpscaler, mean_of_means: torch.Tensor,
+                            std_of_means: torch.Tensor) -> torch.Tensor:
+    """un_normalize -> TemporalUpscaler -> normalize (reference scripts/generate.py:2052-2066), fused into the layout changes
+    as in upscale_latent."""
+    return upscale_latent(latent, upscaler, mean_of_means, std_of_means)
+
+
+def load_temporal_upscaler_weights(upscaler: TemporalUpscaler, weights_path: str) -> None:
+    """safetensors -> TemporalUpscaler (reference temporal.py:310-378)."""
+    load_spatial_upscaler_weights(upscaler, weights_path)

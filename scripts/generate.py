@@ -529,7 +529,7 @@ def euler_step_x0(sample, denoised, sigma, sigma_next):
 # the reference can switch without touching its call site.  Options outside the MI355X hot path are accepted at their
 # reference defaults and raise NotImplementedError only when set to something else.
 _OUT_OF_PATH_DEFAULTS = dict(
-    upscale_temporal=False, early_layers_only=False, enhance_prompt_flag=False,
+    early_layers_only=False, enhance_prompt_flag=False,
     cross_attn_scale=1.0, distilled_lora=None, stg_scale=0.0, apg_scale=1.0, control_video=None, save_control=False,
     ge_gamma=0.0, keyframes=None, ic_lora_weights=None, negative_prompt=None)
 # pipelines whose algorithm is not built: "two-stage" is the dev model's CFG stage 1 + distilled-LoRA stage 2 (TwoStageCFGConfig,
@@ -622,6 +622,7 @@ def generate_video(
     compute_dtype=None,
     fp8_compute: bool = False,
     decode_audio=None,
+    temporal_upscaler_checkpoint_semantics: bool = False,
 ):
     """Generate video from a text prompt: denoise loop + VAE decode on MI355X behind the reference's signature.
 
@@ -639,8 +640,12 @@ def generate_video(
     Audio (generate_audio / LTX-2.3): the audio latent is always written to `<stem>_audio_latent.npz`; decode_audio (keyword-only) turns
     it into a waveform through AudioDecoder + the checkpoint's vocoder (create_vocoder_for_checkpoint) and writes `<stem>.wav`, muxed
     into the mp4 when an ffmpeg binary exists.  None decodes when the checkpoint holds `audio_vae.decoder.*` and `vocoder.*` tensors,
-    True always (random-initialised decoders without them), False never."""
-    given = dict(upscale_temporal=upscale_temporal, early_layers_only=early_layers_only,
+    True always (random-initialised decoders without them), False never.
+    upscale_temporal (video-only branch) doubles the denoised latent in time before decoding (F -> 2F - 1 latent frames, after the spatial
+    upscale when both are set; same output fps).  temporal_upscaler_checkpoint_semantics (keyword-only): False computes what the reference's
+    TemporalUpscaler computes, True what the upstream PyTorch model does (see model/upscaler.py; which one the released weights want is
+    not verified)."""
+    given = dict(early_layers_only=early_layers_only,
                  enhance_prompt_flag=enhance_prompt_flag and use_gemma, cross_attn_scale=cross_attn_scale, distilled_lora=distilled_lora,
                  stg_scale=stg_scale, apg_scale=apg_scale, control_video=control_video, save_control=save_control, ge_gamma=ge_gamma,
                  keyframes=keyframes, ic_lora_weights=ic_lora_weights)
@@ -702,6 +707,9 @@ def generate_video(
         (bool(weights_path) and os.path.exists(weights_path) and model_version is None and detect_model_version(weights_path).startswith("2.3"))
     # the video-only loop of the reference guides only for cfg_scale > 1 (:1935); OneStagePipeline's guiders are enabled for any scale != 1
     _need_cfg = (cfg_scale != 1.0 or audio_cfg_scale != 1.0) if _av_branch else cfg_scale > 1.0
+    if upscale_temporal and (_av_branch or two_stage_distilled):         # before any model is loaded
+        raise NotImplementedError("upscale_temporal with the " + ("AudioVideo pipeline (the reference's AV branch returns before its upscalers)" if _av_branch
+                                  else "two-stage DistilledPipeline (it returns before the post-denoise upscalers)"))
     if _need_cfg and not _av_branch:
         raise NotImplementedError(f"cfg_scale={cfg_scale}: classifier-free guidance is built in OneStagePipeline (the AudioVideo / LTX-2.3 branch); the "
                                   "standard video-only loop of this script runs the distilled model's cfg = 1")
@@ -794,6 +802,20 @@ def generate_video(
         else:
             up = SpatialUpscaler(mid_channels=mid, device=device)
             load_spatial_upscaler_weights(up, spatial_upscaler_weights)
+        return up
+
+    def make_temporal_upscaler():
+        from ltx_2_mlx_amd.model.upscaler import TemporalUpscaler, load_temporal_upscaler_weights
+        hid = 64 if toy else 512
+        kw = dict(checkpoint_semantics=temporal_upscaler_checkpoint_semantics, device=device)
+        if temporal_upscaler_weights == "random" or not os.path.exists(str(temporal_upscaler_weights)):
+            if temporal_upscaler_weights != "random":
+                print(f"  Warning: Weights not found at {temporal_upscaler_weights}, using random init")
+            up = TemporalUpscaler(hidden_channels=hid, num_res_blocks=4 if hid == 512 else 1, **kw)
+            up.init_random_weights(seed=seed + 4)
+        else:
+            up = TemporalUpscaler(hidden_channels=hid, **kw)
+            load_temporal_upscaler_weights(up, temporal_upscaler_weights)
         return up
 
     def decode_audio_latent(audio_latent):
@@ -938,6 +960,20 @@ def generate_video(
         else:
             print("  WARNING: No VAE decoder for normalization - output may have wrong range")
             latent = upscale_latent(latent, up, torch.zeros(128, device=device), torch.ones(128, device=device))
+        print(f"  Upscaled latent: {tuple(latent.shape)}")
+        np.savez(base + "_latent.npz", latent=latent.float().cpu().numpy())
+    if upscale_temporal and temporal_upscaler_weights:
+        # post-denoise 2x temporal latent upscale (reference :2039-2077), after the spatial one: the same un-normalise / re-normalise
+        # bracket; F latent frames become 2F - 1, decoded to 8 * (2F - 2) + 1 video frames saved at the unchanged output fps (:2140)
+        from ltx_2_mlx_amd.model.upscaler import upscale_latent_temporal
+        print(f"\nApplying 2x temporal upscaling...\n  Input latent: {tuple(latent.shape)}")
+        tup = make_temporal_upscaler()
+        if vae_decoder is not None:
+            stats = vae_decoder.per_channel_statistics
+            latent = upscale_latent_temporal(latent, tup, stats.mean_of_means, stats.std_of_means)
+        else:
+            print("  WARNING: No VAE decoder for normalization - output may have wrong range")
+            latent = upscale_latent_temporal(latent, tup, torch.zeros(128, device=device), torch.ones(128, device=device))
         print(f"  Upscaled latent: {tuple(latent.shape)}")
         np.savez(base + "_latent.npz", latent=latent.float().cpu().numpy())
     frames = None

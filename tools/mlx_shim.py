@@ -450,6 +450,35 @@ class LayerNorm(Module):
         return Arr(y)
 
 
+class GroupNorm(Module):
+    """mlx.nn.GroupNorm(num_groups, dims, eps=1e-5, affine=True, pytorch_compatible=False), after MLX's definition
+    (python/mlx/nn/layers/normalization.py, GroupNorm._group_norm / _pytorch_compatible_group_norm): input (batch, ..., dims);
+    the default reshapes to (batch, -1, num_groups) and normalises over axis 1 with the biased variance, so group g holds the
+    channels c with c % num_groups == g; pytorch_compatible reshapes to (batch, -1, num_groups, group_size) and normalises
+    each group's (positions x group_size) block, i.e. contiguous groups as torch.nn.GroupNorm.  Then weight * x + bias."""
+
+    def __init__(self, num_groups, dims, eps=1e-5, affine=True, pytorch_compatible=False):
+        self.num_groups, self.dims, self.eps, self.pytorch_compatible = num_groups, dims, eps, pytorch_compatible
+        if affine:
+            self.weight, self.bias = ones((dims,)), zeros((dims,))
+
+    def __call__(self, x):
+        t = _t(x)
+        shape, batch, G = t.shape, t.shape[0], self.num_groups
+        if self.pytorch_compatible:
+            g = t.reshape(batch, -1, G, self.dims // G)
+            dims = (1, 3)
+        else:
+            g = t.reshape(batch, -1, G)
+            dims = (1,)
+        mean = g.mean(dim=dims, keepdim=True)
+        var = g.var(dim=dims, keepdim=True, unbiased=False)
+        y = ((g - mean) * torch.rsqrt(var + self.eps)).reshape(shape)
+        if getattr(self, "weight", None) is not None:
+            y = _t(self.weight).to(y.dtype) * y + _t(self.bias).to(y.dtype)
+        return Arr(y)
+
+
 class RMSNorm(Module):
     def __init__(self, dims, eps=1e-5):
         self.weight, self.eps = ones((dims,)), eps
@@ -497,7 +526,7 @@ def install():
     mlx = types.ModuleType("mlx")
     core = types.ModuleType("mlx.core")
     for k, v in vars(me).items():
-        if not k.startswith("_") and k not in ("Module", "Linear", "LayerNorm", "RMSNorm", "SiLU", "GELU", "ReLU", "install", "leaky_relu"):
+        if not k.startswith("_") and k not in ("Module", "Linear", "LayerNorm", "GroupNorm", "RMSNorm", "SiLU", "GELU", "ReLU", "install", "leaky_relu"):
             setattr(core, k, v)
     core.fast = _Fast("mlx.core.fast")
     core.random = _Random("mlx.core.random")
@@ -507,9 +536,9 @@ def install():
     core.metal = types.SimpleNamespace(clear_cache=lambda: None, is_available=lambda: False)
     core.clear_cache = lambda: None
     nn = types.ModuleType("mlx.nn")
-    for k in ("Module", "Linear", "LayerNorm", "RMSNorm", "SiLU", "GELU", "ReLU", "silu", "gelu_approx", "gelu", "relu", "leaky_relu"):
+    for k in ("Module", "Linear", "LayerNorm", "GroupNorm", "RMSNorm", "SiLU", "GELU", "ReLU", "silu", "gelu_approx", "gelu", "relu", "leaky_relu"):
         setattr(nn, k, getattr(me, k))
-    for k in ("Conv1d", "Conv2d", "Conv3d", "ConvTranspose1d", "ConvTranspose2d", "GroupNorm", "Embedding", "Dropout", "Sequential", "Identity"):
+    for k in ("Conv1d", "Conv2d", "Conv3d", "ConvTranspose1d", "ConvTranspose2d", "Embedding", "Dropout", "Sequential", "Identity"):
         setattr(nn, k, _Generic)
     utils = types.ModuleType("mlx.utils")
     utils.tree_flatten = lambda t: []
