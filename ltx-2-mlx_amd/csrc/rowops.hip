@@ -1046,6 +1046,22 @@ __global__ void video_to_uint8_kernel(const float* __restrict__ video, unsigned 
     }
 }
 
+// Individually rounded fp32 operations for the kernels below that replace separate torch ops bit for bit.  HIP's __fmul_rn / __fadd_rn /
+// __fsub_rn are plain operators in the headers, and once inlined hipcc contracts them into FMAs like any other a * b + c (the tile blend
+// then differed from the three torch statements in the last bit); operators compiled under contract(off) carry no such licence.
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ float add_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+__device__ __forceinline__ float sub_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a - b;
+}
+
 // One temporal chunk of decode_latent -> uint8 frames, cross-faded with the previous chunk on the first `ov` frames
 // (simple_decoder.py:760-798): frame j of `cur` lands on output frame t_dst0 + j; for j < ov the value is
 // prev[prev_T - ov + j] * (1 - ramp[j]) + cur[j] * ramp[j] with torch.linspace's ramp, rounded exactly like the separate torch
@@ -1065,7 +1081,7 @@ __global__ void video_chunk_to_uint8_kernel(const float* __restrict__ cur, const
             if (prev && j < ov) {
                 const float r = ramp[j];
                 const float a = prev[c * pplane + (long)(prev_T - ov + j) * hw + px];
-                v = __fadd_rn(__fmul_rn(a, __fsub_rn(1.0f, r)), __fmul_rn(v, r));
+                v = add_rn(mul_rn(a, sub_rn(1.0f, r)), mul_rn(v, r));
             }
             v = (v + 1.f) * 0.5f;
             v = fminf(fmaxf(v, 0.f), 1.f) * 255.f;
@@ -1084,13 +1100,13 @@ __global__ void tile_blend_accumulate_kernel(const float* __restrict__ tile, int
         const int w = (int)(i % nw);
         const long r = i / nw;
         const int h = (int)(r % nh), t = (int)(r / nh);
-        const float m = __fmul_rn(__fmul_rn(mt[t], mh[h]), mw[w]);
+        const float m = mul_rn(mul_rn(mt[t], mh[h]), mw[w]);
         const long o = ((long)(t0 + t) * OH + (h0 + h)) * OW + (w0 + w);
-        wsum[o] = __fadd_rn(wsum[o], m);
+        wsum[o] = add_rn(wsum[o], m);
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const long oc = (long)c * OT * OH * OW + o;
-            out[oc] = __fadd_rn(out[oc], __fmul_rn(tile[((long)c * dt + t) * dh * dw + (long)h * dw + w], m));
+            out[oc] = add_rn(out[oc], mul_rn(tile[((long)c * dt + t) * dh * dw + (long)h * dw + w], m));
         }
     }
 }
