@@ -528,6 +528,19 @@ int ltx2_gemma_features_rms(const float* hs, int64_t layer_stride, int64_t row_s
 int ltx2_audio_conv(const float* x, int64_t ldx, int h_in, int w_in, int c_in, const float* w, int64_t ldw, const float* bias, float* y,
                     int64_t ldy, int h_out, int w_out, int c_out, int kh, int kw, int stride, int dilation, int pad_h, int pad_w, int upsample,
                     int prologue, float slope, const float* res, int64_t ldres, float alpha, float beta, int act, void* stream);
+/* Audio VAE encoder (model/audio_vae/encoder.py).  The same convolution strided along both axes: p = (h, w) reads row h*stride_h - pad_h + i
+ * and column w*stride_w - pad_w + j, so Downsample2d (CausalConv2d(k = 3, stride = 2), encoder.py:23-33: pad_h = 2, pad_w = 1,
+ * h_out = (h_in - 1) / 2 + 1, w_out = (w_in - 1) / 2 + 1) computes only the outputs it keeps.  No prologue, dilation 1, alpha 1, beta 0;
+ * act: NONE or SILU (applied after bias and res: the encoder's silu(h) before conv_out, folded into mid.block_2.conv2).  ltx2_audio_conv
+ * itself accepts acts 0..3 only. */
+#define LTX2_AUDIO_ACT_SILU 4            /* v * sigmoid(v) */
+int ltx2_audio_conv2d_strided(const float* x, int64_t ldx, int h_in, int w_in, int c_in, const float* w, int64_t ldw, const float* bias, float* y,
+                              int64_t ldy, int h_out, int w_out, int c_out, int kh, int kw, int stride_h, int stride_w, int pad_h, int pad_w,
+                              const float* res, int64_t ldres, int act, void* stream);
+/* Encoder latent normalisation (encoder.py:172-203, patchify -> normalize -> unpatchify on the mean half) in one pass: channels-last
+ * h [t][f][ld] (ld >= z; ld = 2z with double_z) -> out (z, t, f) fp32, out[c][t][f] = (h[t][f][c] - mean[c*f_dim + f]) / std[c*f_dim + f].
+ * One IEEE subtract and one IEEE divide per element: equal to fp32 torch bit for bit. */
+int ltx2_audio_latent_normalize(const float* h, int64_t ld, const float* mean, const float* std, float* out, int t, int f, int z, void* stream);
 /* ConvTranspose1d(stride = rate, padding) as `rate` polyphase convolutions (vocoder.py:66-116); output length t_out.  w_phase:
  * [rate][ceil(k / rate)][c_in][round_up(c_out, 4)], phase ph = (o + padding) % rate, tap t = kernel index ph + rate * (ntaps - 1 - t)
  * (zero past k).  prologue: NONE or LEAKY_RELU. */

@@ -27,7 +27,7 @@ ROUTE_SKINNY, ROUTE_V4_224, ROUTE_V4_256, ROUTE_V4_W8_224, ROUTE_V4_W8_256, ROUT
 VAE_RES, VAE_UPSAMPLE = 0, 1
 GEMMA_ACT_SILU, GEMMA_ACT_GELU_TANH = 0, 1
 AUDIO_PRO_NONE, AUDIO_PRO_LEAKY_RELU, AUDIO_PRO_MAGNITUDE = 0, 1, 2
-AUDIO_ACT_NONE, AUDIO_ACT_TANH, AUDIO_ACT_CLIP, AUDIO_ACT_LOG = 0, 1, 2, 3
+AUDIO_ACT_NONE, AUDIO_ACT_TANH, AUDIO_ACT_CLIP, AUDIO_ACT_LOG, AUDIO_ACT_SILU = 0, 1, 2, 3, 4
 VAE_MAX_BLOCKS = 16
 
 vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_float
@@ -136,6 +136,9 @@ SIGNATURES = {
     "ltx2_audio_pixnorm_silu": (i32, [vp, i64, vp, i64, i64, i32, f32, vp]),
     "ltx2_audio_snake_aa": (i32, [vp, i64, i32, i32, vp, vp, vp, i32, vp, i32, vp, i64, vp]),
     "ltx2_audio_upsample": (i32, [vp, i64, i32, i32, vp, i32, i32, i32, i32, vp, i64, i32, vp]),
+    # audio VAE encoder (additive)
+    "ltx2_audio_conv2d_strided": (i32, [vp, i64, i32, i32, i32, vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i64, i32, vp]),
+    "ltx2_audio_latent_normalize": (i32, [vp, i64, vp, vp, vp, i32, i32, i32, vp]),
 }
 
 _libs: dict = {}

@@ -13,8 +13,10 @@ bool aligned16(const void* ptr) { return ((uintptr_t)ptr & 15) == 0; }
 
 // ------------------------------------------------------------------------------------------------------------------------------
 // Implicit-GEMM convolution.  M = output positions (h_out * w_out), N = c_out, K = ntaps * c_in with k = tap * c_in + c and
-// tap = i * kw + j.  Output position p = (h, w) reads source row vh = h + up - pad_h + i and column vw = w * stride + j * dil - pad_w;
-// with up != 0 the source is the nearest x2 image of the input (Upsample2d, whose first output row is dropped: the `+ up`).
+// tap = i * kw + j.  Output position p = (h, w) reads source row vh = h * stride_h + up - pad_h + i and column
+// vw = w * stride + j * dil - pad_w (stride_h = 1 everywhere but the encoder's Downsample2d, which keeps every second row and column: only
+// the kept outputs are rows of M); with up != 0 the source is the nearest x2 image of the input (Upsample2d, whose first output row is
+// dropped: the `+ up`).
 // Block: 256 threads = 2 x 2 waves over a (32 FM) x (32 FN) tile, each wave FM x FN 16x16 MFMA blocks; K steps of 16.
 // ------------------------------------------------------------------------------------------------------------------------------
 struct AudioConvParams {
@@ -28,7 +30,7 @@ struct AudioConvParams {
     long ldy;
     long M;
     int w_out, c_out, K;
-    int kw, ntaps, stride, dil, pad_h, pad_w, up;
+    int kw, ntaps, stride, stride_h, dil, pad_h, pad_w, up;
     int pro;
     float slope;
     const float* res;
@@ -63,7 +65,7 @@ __global__ __launch_bounds__(256) void audio_conv_kernel(AudioConvParams p) {
         rok[i] = m < p.M;
         const long mm = rok[i] ? m : 0;
         const int h = (int)(mm / p.w_out), w = (int)(mm - (long)h * p.w_out);
-        vh0[i] = h + p.up - p.pad_h;
+        vh0[i] = h * p.stride_h + p.up - p.pad_h;
         vw0[i] = w * p.stride - p.pad_w;
     }
     int tap[NE], cc[NE];
@@ -190,6 +192,7 @@ __global__ __launch_bounds__(256) void audio_conv_kernel(AudioConvParams p) {
                 if (p.act == 1) v = tanhf(v);
                 else if (p.act == 2) v = fminf(fmaxf(v, -1.f), 1.f);
                 else if (p.act == 3) v = logf(fmaxf(v, 1e-5f));
+                else if (p.act == 4) v = v * (1.f / (1.f + expf(-v)));
                 *dst = v;
             }
         }
@@ -317,19 +320,32 @@ __global__ __launch_bounds__(256) void audio_pixnorm_silu_kernel(const float* __
     }
 }
 
-}  // namespace
+// Encoder latent normalisation (encoder.py:172-203: patchify -> (x - mean) / std -> unpatchify on the mean half of conv_out) in one pass:
+// channels-last h [T][F][ld] -> out (z, T, F), statistic index c * F + f.  One IEEE subtract and one IEEE divide per element, as torch does.
+__global__ __launch_bounds__(256) void audio_latent_normalize_kernel(const float* __restrict__ h, long ld, const float* __restrict__ mean,
+                                                                     const float* __restrict__ stdv, float* __restrict__ out, int T, int F, int z) {
+#pragma clang fp contract(off)
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    const long tf = (long)T * F;
+    if (idx >= tf * z) return;
+    const int c = (int)(idx / tf);
+    const long r = idx - (long)c * tf;                  // t * F + f
+    const int f = (int)(r % F);
+    const float d = h[r * ld + c] - mean[c * F + f];
+    out[idx] = d / stdv[c * F + f];
+}
 
-extern "C" {
-
-int ltx2_audio_conv(const float* x, int64_t ldx, int h_in, int w_in, int c_in, const float* w, int64_t ldw, const float* bias, float* y,
-                    int64_t ldy, int h_out, int w_out, int c_out, int kh, int kw, int stride, int dilation, int pad_h, int pad_w, int upsample,
-                    int prologue, float slope, const float* res, int64_t ldres, float alpha, float beta, int act, void* stream) {
+// the argument checks and parameter block shared by ltx2_audio_conv (stride_h = 1, act <= LOG) and ltx2_audio_conv2d_strided
+int audio_conv_checked(const float* x, int64_t ldx, int h_in, int w_in, int c_in, const float* w, int64_t ldw, const float* bias, float* y,
+                       int64_t ldy, int h_out, int w_out, int c_out, int kh, int kw, int stride_h, int stride, int dilation, int pad_h, int pad_w,
+                       int upsample, int prologue, float slope, const float* res, int64_t ldres, float alpha, float beta, int act, int act_max,
+                       void* stream) {
     LTX2_CHECK_ARG(x && w && y, "audio_conv: null operand");
     LTX2_CHECK_ARG(h_in > 0 && w_in > 0 && c_in > 0 && h_out >= 0 && w_out >= 0 && c_out > 0 && kh > 0 && kw > 0 && stride > 0 && dilation > 0,
                    "audio_conv: h_in %d w_in %d c_in %d h_out %d w_out %d c_out %d kh %d kw %d stride %d dilation %d", h_in, w_in, c_in, h_out,
                    w_out, c_out, kh, kw, stride, dilation);
     LTX2_CHECK_ARG((long)kh * kw * c_in < (1L << 30) && (long)h_out * w_out < (1L << 37), "audio_conv: problem too large");
-    LTX2_CHECK_ARG(prologue >= 0 && prologue <= 2 && act >= 0 && act <= 3, "audio_conv: prologue %d (0..2) / act %d (0..3)", prologue, act);
+    LTX2_CHECK_ARG(prologue >= 0 && prologue <= 2 && act >= 0 && act <= act_max, "audio_conv: prologue %d (0..2) / act %d (0..%d)", prologue, act, act_max);
     LTX2_CHECK_ARG(ldw % 4 == 0 && ldw >= c_out && aligned16(w), "audio_conv: the weight rows must be 16-byte aligned with ldw %ld >= c_out %d",
                    (long)ldw, c_out);
     LTX2_CHECK_ARG(ldx >= (prologue == 2 ? 2L * c_in : (long)c_in) && ldy >= c_out && (!res || ldres >= c_out),
@@ -354,6 +370,7 @@ int ltx2_audio_conv(const float* x, int64_t ldx, int h_in, int w_in, int c_in, c
     p.kw = kw;
     p.ntaps = kh * kw;
     p.stride = stride;
+    p.stride_h = stride_h;
     p.dil = dilation;
     p.pad_h = pad_h;
     p.pad_w = pad_w;
@@ -366,6 +383,43 @@ int ltx2_audio_conv(const float* x, int64_t ldx, int h_in, int w_in, int c_in, c
     p.beta = beta;
     p.act = act;
     return conv_launch(p, (hipStream_t)stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+int ltx2_audio_conv(const float* x, int64_t ldx, int h_in, int w_in, int c_in, const float* w, int64_t ldw, const float* bias, float* y,
+                    int64_t ldy, int h_out, int w_out, int c_out, int kh, int kw, int stride, int dilation, int pad_h, int pad_w, int upsample,
+                    int prologue, float slope, const float* res, int64_t ldres, float alpha, float beta, int act, void* stream) {
+    return audio_conv_checked(x, ldx, h_in, w_in, c_in, w, ldw, bias, y, ldy, h_out, w_out, c_out, kh, kw, 1, stride, dilation, pad_h, pad_w, upsample,
+                              prologue, slope, res, ldres, alpha, beta, act, LTX2_AUDIO_ACT_LOG, stream);
+}
+
+int ltx2_audio_conv2d_strided(const float* x, int64_t ldx, int h_in, int w_in, int c_in, const float* w, int64_t ldw, const float* bias, float* y,
+                              int64_t ldy, int h_out, int w_out, int c_out, int kh, int kw, int stride_h, int stride_w, int pad_h, int pad_w,
+                              const float* res, int64_t ldres, int act, void* stream) {
+    LTX2_CHECK_ARG(stride_h > 0 && stride_w > 0, "audio_conv2d_strided: stride_h %d stride_w %d", stride_h, stride_w);
+    // every source row and column an output reads lies inside the padded image: the last output's first tap starts at or before the last row
+    LTX2_CHECK_ARG((long)(h_out - 1) * stride_h - pad_h < h_in && (long)(w_out - 1) * stride_w - pad_w < w_in,
+                   "audio_conv2d_strided: h_out %d / w_out %d reach past the %d x %d input at stride (%d, %d), pad (%d, %d)", h_out, w_out, h_in, w_in,
+                   stride_h, stride_w, pad_h, pad_w);
+    LTX2_CHECK_ARG(act == LTX2_AUDIO_ACT_NONE || act == LTX2_AUDIO_ACT_SILU, "audio_conv2d_strided: act %d (NONE or SILU)", act);
+    return audio_conv_checked(x, ldx, h_in, w_in, c_in, w, ldw, bias, y, ldy, h_out, w_out, c_out, kh, kw, stride_h, stride_w, 1, pad_h, pad_w, 0,
+                              LTX2_AUDIO_PRO_NONE, 0.f, res, ldres, 1.f, 0.f, act, LTX2_AUDIO_ACT_SILU, stream);
+}
+
+int ltx2_audio_latent_normalize(const float* h, int64_t ld, const float* mean, const float* std, float* out, int t, int f, int z, void* stream) {
+    LTX2_CHECK_ARG(h && mean && std && out, "audio_latent_normalize: null operand");
+    LTX2_CHECK_ARG(t >= 0 && f > 0 && z > 0 && ld >= z && (long)t * f * z < (1L << 40), "audio_latent_normalize: t %d f %d z %d ld %ld", t, f, z, (long)ld);
+    LTX2_CHECK_ARG(((uintptr_t)h & 3) == 0 && ((uintptr_t)out & 3) == 0 && ((uintptr_t)mean & 3) == 0 && ((uintptr_t)std & 3) == 0,
+                   "audio_latent_normalize: misaligned fp32 operand");
+    const long n = (long)t * f * z;
+    if (n == 0) return LTX2_OK;
+    hipLaunchKernelGGL(audio_latent_normalize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, h, (long)ld, mean, std, out, t,
+                       f, z);
+    LTX2_CHECK_LAUNCH("audio_latent_normalize");
+    return LTX2_OK;
 }
 
 int ltx2_audio_conv_transpose1d(const float* x, int64_t ldx, int t_in, int c_in, const float* w_phase, const float* bias, float* y, int64_t ldy,
@@ -402,6 +456,7 @@ int ltx2_audio_conv_transpose1d(const float* x, int64_t ldx, int t_in, int c_in,
         p.kw = ntaps;
         p.ntaps = ntaps;
         p.stride = 1;
+        p.stride_h = 1;
         p.dil = 1;
         p.pad_h = 0;
         p.pad_w = ntaps - 1 - q0;                                      // tap t reads input n + t - (ntaps - 1 - q0)

@@ -735,6 +735,36 @@ def audio_conv2d(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor],
     return out
 
 
+def audio_conv2d_strided(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], c_out: int, kh: int, kw: int, pad_h: int, pad_w: int, *,
+                         stride: Tuple[int, int] = (1, 1), out: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None,
+                         act: int = nv.AUDIO_ACT_NONE) -> torch.Tensor:
+    """x [H, W, C_in] -> out [H_out, W_out, c_out] with stride (stride_h, stride_w), padded as CausalConv2d pads (pad_h rows on top only,
+    pad_w columns each side): only the kept outputs are computed.  Downsample2d is kh = kw = 3, pad (2, 1), stride (2, 2):
+    [(H - 1) // 2 + 1, (W - 1) // 2 + 1].  act: AUDIO_ACT_NONE or AUDIO_ACT_SILU (after bias and res)."""
+    H, W, c_in = x.shape
+    sh, sw = stride
+    h_out, w_out = (H + pad_h - kh) // sh + 1, (W + 2 * pad_w - kw) // sw + 1
+    if out is None:
+        out = torch.empty(h_out, w_out, c_out, device=x.device, dtype=torch.float32)
+    assert x.is_contiguous() and out.is_contiguous() and (res is None or res.is_contiguous())
+    assert tuple(out.shape) == (h_out, w_out, c_out) and (res is None or tuple(res.shape) == (h_out, w_out, c_out)) and w.shape[0] == kh * kw * c_in
+    _f32(x, w, bias, out, res)
+    nv.check(nv.lib().ltx2_audio_conv2d_strided(nv.ptr(x), c_in, H, W, c_in, nv.ptr(w), w.stride(0), nv.ptr(bias), nv.ptr(out), c_out, h_out, w_out,
+                                                c_out, kh, kw, sh, sw, pad_h, pad_w, nv.ptr(res), c_out if res is not None else 0, int(act),
+                                                nv.stream()))
+    return out
+
+
+def audio_latent_normalize(h: torch.Tensor, mean: torch.Tensor, std: torch.Tensor, z: int) -> torch.Tensor:
+    """Encoder conv_out h [T, F, ld] (channels-last, ld >= z) -> (z, T, F): (h[t, f, c] - mean[c * F + f]) / std[c * F + f]."""
+    T, F, ld = h.shape
+    assert h.is_contiguous() and mean.is_contiguous() and std.is_contiguous() and mean.numel() == z * F == std.numel() and ld >= z
+    out = torch.empty(z, T, F, device=h.device, dtype=torch.float32)
+    _f32(h, mean, std, out)
+    nv.check(nv.lib().ltx2_audio_latent_normalize(nv.ptr(h), ld, nv.ptr(mean), nv.ptr(std), nv.ptr(out), T, F, z, nv.stream()))
+    return out
+
+
 def audio_conv_transpose1d(x: torch.Tensor, w_phase: torch.Tensor, bias: Optional[torch.Tensor], c_out: int, k: int, rate: int, padding: int,
                            prologue: int = nv.AUDIO_PRO_NONE, slope: float = 0.0) -> torch.Tensor:
     """ConvTranspose1d(stride=rate, padding) of x [T, C_in] -> [(T - 1) rate + k - 2 padding, c_out] through the polyphase kernel."""

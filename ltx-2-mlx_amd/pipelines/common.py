@@ -128,7 +128,10 @@ def joint_denoise_loop(transformer, is_av_model: bool, video_state: LatentState,
     if is_av_model and not joint:
         model = model._video_twin()        # no audio tokens: the video half alone (reference model.py:829-840), same weights
     states = [video_state] + ([audio_state] if joint else [])
-    uniform = all(bool((st.denoise_mask == 1).all()) for st in states)        # no conditioning tokens
+    # a modality whose mask is all ones takes the uniform form (one timestep, the broadcast AdaLN path) in both executions below, whatever the
+    # other modality's mask is: the per-token AdaLN path rounds differently, so graph == eager needs the same choice per modality
+    unif = [bool((st.denoise_mask == 1).all()) for st in states] + [True]
+    uniform = all(unif)                                                       # no conditioning tokens
     # classifier-free guidance (pipelines/one_stage.py:224-330 video, :466-568 joint): a second evaluation with the negative prompt whenever a
     # guider is enabled(); BOTH modalities are then guided by their own guider (a guider at scale 1 returns cond).  The negative prompt runs
     # through a second engine context over the same weights, so each context keeps its own per-prompt text K / V.
@@ -167,16 +170,16 @@ def joint_denoise_loop(transformer, is_av_model: bool, video_state: LatentState,
             audio_state = audio_state.replace(latent=alat[None].to(audio_state.latent.dtype))
         return video_state, audio_state
     for i in range(n):
-        vm = modality_from_state(video_state, video_context, sig[i], uniform=uniform)
+        vm = modality_from_state(video_state, video_context, sig[i], uniform=unif[0])
         if joint:
-            vx0, ax0 = transformer(vm, audio_modality_from_state(audio_state, audio_context, sig[i], uniform=uniform))
+            vx0, ax0 = transformer(vm, audio_modality_from_state(audio_state, audio_context, sig[i], uniform=unif[1]))
         else:
             out = transformer(vm)
             vx0, ax0 = (out[0] if isinstance(out, tuple) else out), None
         if need_cfg:
-            nvm = modality_from_state(video_state, negative_video_context, sig[i], uniform=uniform)
+            nvm = modality_from_state(video_state, negative_video_context, sig[i], uniform=unif[0])
             if joint:
-                nvx0, nax0 = neg(nvm, audio_modality_from_state(audio_state, negative_audio_context, sig[i], uniform=uniform))
+                nvx0, nax0 = neg(nvm, audio_modality_from_state(audio_state, negative_audio_context, sig[i], uniform=unif[1]))
                 ax0 = audio_guider.guide(ax0, nax0) if audio_guider is not None else ax0
             else:
                 nvx0 = neg(nvm)

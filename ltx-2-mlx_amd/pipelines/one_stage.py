@@ -114,14 +114,19 @@ class OneStagePipeline:
                  stg_scale: float = 0.0, stg_blocks: Optional[List[int]] = None, stg_cutoff: float = 1.0, guider_override=None,
                  ge_gamma: float = 0.0, sampler: str = "euler", temporal_upscaler=None, cross_attn_scale: float = 1.0,
                  cross_attn_start_block: int = 40, *, initial_noise: Optional[torch.Tensor] = None,
-                 initial_audio_noise: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+                 initial_audio_noise: Optional[torch.Tensor] = None,
+                 initial_audio_latent: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         """-> (video, audio): video uint8 frames (F, H, W, 3) (or the final latent when no decoder is set); audio = the
         waveform (B, 2, samples) when config.audio_enabled and both audio_decoder and vocoder were given (the reference's
         _decode_audio), the audio LATENT (B, 8, T_a, 16) when config.audio_enabled without them, else None.
         The negative encodings are evaluated when a guider is enabled (cfg_scale / audio_cfg_scale != 1); unlike the reference
         (one_stage.py:776-780, which demands negative_audio_encoding whenever the audio branch runs) they may be None when no guider is.  initial_noise /
         initial_audio_noise (keyword-only, MI355X addition): supplied N(0,1) tensors of the patchified latent shapes, so
-        results can be compared with the oracle loop (MLX's RNG stream is not reproducible here)."""
+        results can be compared with the oracle loop (MLX's RNG stream is not reproducible here).
+        initial_audio_latent (keyword-only): an encoded audio latent (1, 8, T_a, 16) (model/audio_vae AudioEncoder) the video is generated
+        TO: the audio state starts from it with denoise_mask = 0 and is not noised, so every step leaves it as it is and only the video is
+        denoised (reference pipelines/a2vid_two_stage.py:338-357).  Needs an AudioVideo transformer.  The returned audio is then this
+        latent, never VAE-decoded (the reference returns the original waveform)."""
         images = images or []
         internal_audio_active = self.is_av_model and (config.use_internal_audio_branch or config.audio_enabled)
         if config.audio_enabled or internal_audio_active:
@@ -129,6 +134,8 @@ class OneStagePipeline:
                 raise ValueError("Audio encoding required for AudioVideo generation. Provide positive_audio_encoding and negative_audio_encoding.")
         if config.audio_enabled and not self.is_av_model:
             raise ValueError("audio_enabled needs an AudioVideo transformer")
+        if initial_audio_latent is not None and not internal_audio_active:
+            raise ValueError("initial_audio_latent needs an AudioVideo transformer (the audio branch carries the frozen latent)")
         self._require_no_guidance(stg_scale, guider_override, ge_gamma, sampler, temporal_upscaler, cross_attn_scale)
 
         dev = self.transformer.velocity_model.device
@@ -148,7 +155,12 @@ class OneStagePipeline:
                 pixel_shape, channels=config.audio_vae_channels, mel_bins=config.audio_mel_bins, sample_rate=config.audio_sample_rate,
                 hop_length=config.audio_hop_length, audio_latent_downsample_factor=config.audio_downsample_factor)
             audio_tools = self._create_audio_tools(audio_shape)
-            audio_state = noiser(audio_tools.create_initial_state(dtype=config.dtype, device=dev), noise_scale=1.0, noise=initial_audio_noise)
+            if initial_audio_latent is not None:
+                # frozen: denoise_mask = 0, no noise (a2vid_two_stage.py:347-357); the loops' non-uniform path carries it
+                audio_state = audio_tools.create_initial_state(dtype=config.dtype, initial_latent=initial_audio_latent.to(dev, config.dtype))
+                audio_state = audio_state.replace(denoise_mask=torch.zeros_like(audio_state.denoise_mask))
+            else:
+                audio_state = noiser(audio_tools.create_initial_state(dtype=config.dtype, device=dev), noise_scale=1.0, noise=initial_audio_noise)
 
         actx = positive_audio_encoding.to(dev) if (internal_audio_active and positive_audio_encoding is not None) else None
         # one guider per modality (one_stage.py:793-807)
@@ -175,7 +187,9 @@ class OneStagePipeline:
             else:
                 video = decode_latent(final_video_latent, self.video_decoder)
         audio = None
-        if config.audio_enabled and audio_state is not None:
+        if initial_audio_latent is not None:
+            audio = audio_tools.unpatchify(audio_tools.clear_conditioning(audio_state)).latent          # the latent given, kept by every step
+        elif config.audio_enabled and audio_state is not None:
             audio = audio_tools.unpatchify(audio_tools.clear_conditioning(audio_state)).latent
             if self.audio_decoder is not None and self.vocoder is not None:
                 audio = self._decode_audio(audio)

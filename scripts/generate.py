@@ -11,6 +11,8 @@ CFG in the video-only loop.
 `--pipeline distilled --spatial-upscaler-weights W` runs the two-stage DistilledPipeline; adding `--generate-audio` runs it on
 the AudioVideo transformer and saves the audio LATENT beside the frames; `--decode-audio` (the default when the checkpoint holds the
 audio VAE decoder and vocoder) also decodes it to `<output>.wav` and muxes it into the mp4 (reference save_video_with_audio).
+`--audio FILE` (with `--generate-audio` or an LTX-2.3 checkpoint) generates the video TO that audio: the audio VAE encoder's latent stays
+frozen in the joint loop, and the original audio is muxed into the mp4.
 `save_video` keeps the reference's ffmpeg settings (frames piped as raw RGB; PNG frames when no ffmpeg binary exists).  `--lora` fuses an adapter into the checkpoint weights at load.  `--image` conditions latent frame 0 on an image through the VAE encoder (the reference
 routes that through its pipelines, scripts/generate.py:1711-1731).  Without Gemma weights, text embeddings come from `--embedding file.npz` (keys
 `embedding`, `attention_mask`, as the reference's `load_text_embedding` :730-750) or the reference's
@@ -415,6 +417,49 @@ def create_audio_decoders(decode_audio, weights_path, device="cuda", seed=0):
     return dec, voc
 
 
+def checkpoint_has_audio_encoder(checkpoint_path) -> bool:
+    if not checkpoint_path or not os.path.exists(checkpoint_path):
+        return False
+    from ltx_2_mlx_amd.loader.weight_converter import SafetensorsStream
+    with SafetensorsStream(checkpoint_path, "cpu") as st:
+        return any(k.startswith("audio_vae.encoder.") for k in st.keys())
+
+
+def fit_audio_latent(latent, frames: int):
+    """Encoded latent (1, C, T, F) -> exactly `frames` latent frames: a surplus trailing frame (the waveform's last, partly padded one) is
+    cropped; a latent that comes out short is an error, it is not padded."""
+    if latent.shape[2] < frames:
+        raise ValueError(f"the encoded audio has {latent.shape[2]} latent frames, the video needs {frames}")
+    return latent[:, :, :frames].contiguous()
+
+
+def encode_audio_for_video(audio_path, num_frames: int, fps: float, weights_path=None, device="cuda", seed=0, start_time: float = 0.0,
+                           max_duration=None):
+    """Audio file -> (frozen audio latent (1, 8, T_a, 16) for a num_frames / fps video, the fitted waveform [C, samples], its rate):
+    load_audio_file (start / duration trim, resample to 16 kHz), cut or right-padded with silence to the video's length,
+    AudioProcessor.waveform_to_mel, AudioEncoder.  Encoder weights from the checkpoint when it has `audio_vae.encoder.*`, random init
+    otherwise."""
+    from ltx_2_mlx_amd.model.audio_vae import AudioEncoder, AudioProcessor, encode_audio, load_audio_encoder_weights, load_audio_file
+    from ltx_2_mlx_amd.types import AudioLatentShape, VideoPixelShape
+    waveform, sr = load_audio_file(audio_path, 16000, start_time, max_duration)
+    print(f"  Audio: {waveform.shape[1] / sr:.1f}s, {sr}Hz, {waveform.shape[0]}ch")
+    proc = AudioProcessor(sample_rate=sr, device=device)
+    waveform = proc.fit_waveform(waveform[:2], proc.samples_for_video(num_frames, fps))
+    enc = AudioEncoder(device=device)
+    if checkpoint_has_audio_encoder(weights_path):
+        load_audio_encoder_weights(enc, weights_path)
+    else:
+        print("  note: no audio_vae.encoder.* tensors in the checkpoint: RANDOM audio encoder (test mode)")
+        enc.init_random_weights(seed=seed)
+    t0 = time.time()
+    latent = encode_audio(proc.waveform_to_mel(waveform, sr), enc)
+    target = AudioLatentShape.from_video_pixel_shape(VideoPixelShape(batch=1, frames=num_frames, height=32, width=32, fps=fps))
+    latent = fit_audio_latent(latent, target.frames)
+    torch.cuda.synchronize()
+    print(f"  audio encode: {(time.time() - t0):.3f} s -> {tuple(latent.shape)}")
+    return latent, waveform, sr
+
+
 def detect_model_version(checkpoint_path: str) -> str:
     """`model_version` of the safetensors metadata, e.g. "2.3.0"; "" if unknown (reference :224-236)."""
     try:
@@ -623,6 +668,9 @@ def generate_video(
     fp8_compute: bool = False,
     decode_audio=None,
     temporal_upscaler_checkpoint_semantics: bool = False,
+    audio_path=None,
+    audio_start_time: float = 0.0,
+    audio_max_duration=None,
 ):
     """Generate video from a text prompt: denoise loop + VAE decode on MI355X behind the reference's signature.
 
@@ -644,7 +692,12 @@ def generate_video(
     upscale_temporal (video-only branch) doubles the denoised latent in time before decoding (F -> 2F - 1 latent frames, after the spatial
     upscale when both are set; same output fps).  temporal_upscaler_checkpoint_semantics (keyword-only): False computes what the reference's
     TemporalUpscaler computes, True what the upstream PyTorch model does (see model/upscaler.py; which one the released weights want is
-    not verified)."""
+    not verified).
+    audio_path (keyword-only; AudioVideo branch: generate_audio=True or LTX-2.3): the video is generated TO this audio file.  It is
+    loaded (audio_start_time / audio_max_duration trim), cut or right-padded with silence to num_frames / fps seconds, turned into a log-mel
+    and encoded by AudioEncoder; the latent stays frozen through the denoise loop (denoise_mask = 0, reference
+    pipelines/a2vid_two_stage.py:338-357) and is written to `<stem>_audio_latent.npz`; the original audio, not a decode of the latent,
+    is muxed into the mp4 when an ffmpeg binary exists."""
     given = dict(early_layers_only=early_layers_only,
                  enhance_prompt_flag=enhance_prompt_flag and use_gemma, cross_attn_scale=cross_attn_scale, distilled_lora=distilled_lora,
                  stg_scale=stg_scale, apg_scale=apg_scale, control_video=control_video, save_control=save_control, ge_gamma=ge_gamma,
@@ -707,6 +760,14 @@ def generate_video(
         (bool(weights_path) and os.path.exists(weights_path) and model_version is None and detect_model_version(weights_path).startswith("2.3"))
     # the video-only loop of the reference guides only for cfg_scale > 1 (:1935); OneStagePipeline's guiders are enabled for any scale != 1
     _need_cfg = (cfg_scale != 1.0 or audio_cfg_scale != 1.0) if _av_branch else cfg_scale > 1.0
+    if audio_path:                                                       # before any model is loaded
+        if two_stage_distilled:
+            raise NotImplementedError("audio_path (--audio) with two_stage_distilled: DistilledPipeline with a given audio latent is not built")
+        if not _av_branch:
+            raise ValueError("audio_path (--audio) needs the AudioVideo branch: pass generate_audio=True (--generate-audio) or an LTX-2.3 checkpoint; "
+                             "the video-only transformer has no audio stream to condition on")
+        if not os.path.exists(audio_path):
+            raise FileNotFoundError(f"audio file not found: {audio_path}")
     if upscale_temporal and (_av_branch or two_stage_distilled):         # before any model is loaded
         raise NotImplementedError("upscale_temporal with the " + ("AudioVideo pipeline (the reference's AV branch returns before its upscalers)" if _av_branch
                                   else "two-stage DistilledPipeline (it returns before the post-denoise upscalers)"))
@@ -889,14 +950,26 @@ def generate_video(
             num_inference_steps=num_steps, cfg_scale=cfg_scale,
             audio_cfg_scale=audio_cfg_scale, rescale_scale=rescale_scale,
             audio_enabled=generate_audio, use_hip_graph=use_hip_graph, tiling_config=TilingConfig.default() if tiled_vae else None)
+        given_audio = None
+        if audio_path:
+            print(f"  Encoding audio: {audio_path}")
+            given_audio = encode_audio_for_video(audio_path, num_frames, av_config.fps, weights_path if have_ckpt else None, device=device,
+                                                 seed=seed + 5, start_time=audio_start_time, max_duration=audio_max_duration)
         print(f"[5/5] Running audio-video generation ({num_steps} steps)...")
         t0 = time.time()
         video, audio_latent = av_pipeline(positive_encoding=text_encoding, negative_encoding=negative_encoding if _need_cfg else None, config=av_config,
                                           images=images, positive_audio_encoding=text_audio_encoding,
-                                          negative_audio_encoding=negative_audio_encoding if _need_cfg else None)
+                                          negative_audio_encoding=negative_audio_encoding if _need_cfg else None,
+                                          initial_audio_latent=given_audio[0] if given_audio else None)
         frames = _frames_from_video(video)
         torch.cuda.synchronize()
         print(f"  audio-video pipeline: {(time.time() - t0):.3f} s -> {tuple(frames.shape)}")
+        if given_audio:
+            # the frozen latent is kept; the ORIGINAL audio goes into the mp4 (the reference returns the original waveform, not a decode)
+            import shutil
+            np.savez(base + "_audio_latent.npz", latent=audio_latent.float().cpu().numpy())
+            wav = np.repeat(given_audio[1], 2, axis=0) if given_audio[1].shape[0] == 1 else given_audio[1]
+            return finish(frames, audio=(wav, given_audio[2]) if (save_mp4 and shutil.which("ffmpeg")) else None)
         return finish(frames, audio=decode_audio_latent(audio_latent) if audio_latent is not None else None)
 
     # === STANDARD PIPELINE (one-stage, distilled, video-only; reference :1778-2095) ===
@@ -1068,6 +1141,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--heads", type=int, default=32, help="debug: attention heads (x128) for random-weight runs")
     p.add_argument("--vae-base-channels", type=int, default=None, help="debug: override the checkpoint's decoder_base_channels")
     p.add_argument("--no-video-file", action="store_true", help="keep only the .npz outputs (skip ffmpeg / PNG frames)")
+    p.add_argument("--audio", type=str, default=None, help="generate the video TO this audio file (with --generate-audio or an LTX-2.3 checkpoint): it is "
+                   "encoded by the audio VAE encoder and stays frozen while the video is denoised; the original audio is muxed into the mp4")
+    p.add_argument("--audio-start", type=float, default=0.0, help="seconds into --audio to start from")
+    p.add_argument("--audio-duration", type=float, default=None, help="at most this many seconds of --audio (the rest of the video's length is silence)")
     return p
 
 
@@ -1097,7 +1174,8 @@ def kwargs_from_args(a) -> dict:
         # MI355X extras
         text_features_path=a.text_features, use_hip_graph=not a.no_hip_graph, two_stage_distilled=a.two_stage_distilled,
         fp8_resident=a.fp8_resident, fp8_compute=a.fp8_compute, model_version=a.model_version, compute_dtype="bfloat16" if a.bf16 else None, num_layers=a.layers, num_heads=a.heads,
-        vae_base_channels=a.vae_base_channels, save_mp4=not a.no_video_file, decode_audio=a.decode_audio)
+        vae_base_channels=a.vae_base_channels, save_mp4=not a.no_video_file, decode_audio=a.decode_audio,
+        audio_path=a.audio, audio_start_time=a.audio_start, audio_max_duration=a.audio_duration)
 
 
 def main(argv=None):
