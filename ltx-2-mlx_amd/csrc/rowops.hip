@@ -830,7 +830,7 @@ __global__ void dequant_fp8_kernel(const unsigned char* __restrict__ in, float s
 
 // Per-row e4m3fn quantiser of the fp8 compute path: one workgroup per row.
 //   amax = max_k |x[k]| ; scale = amax / 448 (1 when the row is all zeros) ; inv = 1 / scale (IEEE) ; code[k] = e4m3fn_rne(x[k] * inv)
-// The row stays in registers between the two passes (K <= 16384: 8 x 16 bytes per thread).  v_cvt_pk_fp8_f32 is the OCP conversion
+// The row stays in registers between the two passes (K <= 32768: NIT = 2, 8 or 16 x 16 bytes per thread).  v_cvt_pk_fp8_f32 is the OCP conversion
 // (round to nearest even, subnormals kept); |x * inv| <= 448 (1 + 2^-23) never reaches the overflow threshold (464).
 template <int NIT>
 __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const bf16* __restrict__ x, long ldx, int K, unsigned char* __restrict__ out, long ldo,
