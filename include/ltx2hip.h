@@ -286,6 +286,17 @@ int ltx2_x0_from_velocity(const float* latent, const float* velocity, const floa
 int ltx2_euler_step(const float* x, const float* x0, const float* mask, const float* clean, float sigma,
                     float sigma_next, float* out, int rows, int C, void* stream);
 
+/* One classifier-free-guided sampling step in ONE pass over [rows][C] fp32 (pipelines/one_stage.py:224-330 with CFGGuider): the two
+ * x0_from_velocity launches, the guider's three ops, post_process_latent's four and the Euler update.  Per element, every operation
+ * individually rounded (no FMA contraction), so the result equals the separate fp32 torch ops bit for bit:
+ *   t = ts[row * ts_stride];  a = x - t*vel_cond;  b = x - t*vel_uncond;  g = a + (cfg_scale - 1)*(a - b);
+ *   d = mask ? g*mask[row] + clean*(1 - mask[row]) : g;  out = x + ((x - d) * (1/sigma)) * (sigma_next - sigma)
+ * ts_stride: 0 = one timestep, 1 = one per row.  mask [rows] and clean [rows][C] are both NULL or both set.  out may equal x.
+ * sigma == 0 -> LTX2_E_INVALID with message "Sigma can't be 0.0".  (additive entry of ABI version 3)                          */
+int ltx2_guided_euler_step(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, int64_t ts_stride,
+                           const float* mask, const float* clean, float cfg_scale, float sigma, float sigma_next,
+                           float* out, int rows, int C, void* stream);
+
 /* VAE elementwise glue (simple_decoder.py:492-498, 228-238/339-342, ops.py:109-125, :792-798)  */
 int ltx2_vae_prepare_latent(const float* latent, const float* std, const float* mean, const float* noise,
                             float noise_scale, void* out_bf16, int C, int64_t P, void* stream);
@@ -406,6 +417,20 @@ int ltx2_dit_graph_capture_cond(ltx2_dit* ctx, float* latent, const float* host_
                                 int64_t n_clean, void* stream);
 int ltx2_dit_graph_capture_cond_av(ltx2_dit* ctx, float* v_latent, float* a_latent, const float* host_sigmas, int n_steps, const float* v_mask, int64_t n_v_mask,
                                    const float* v_clean, int64_t n_v_clean, const float* a_mask, int64_t n_a_mask, const float* a_clean, int64_t n_a_clean, void* stream);
+
+/* One classifier-free-guided step on the VideoOnly engine (keyframe interpolation's stage 1; pipelines/one_stage.py:224-330): forward(ctx)
+ * and forward(neg) from the same latent and the same timestep pointer, each into its own context's velocity buffer, then
+ * ltx2_guided_euler_step in place on `latent` -- enqueued one after the other on the caller's stream (no fork: each evaluation fills the
+ * device).  `neg` is a second context over the same weights, prepared with the negative prompt.  LTX2_E_INVALID when either context is
+ * AudioVideo or not prepared, ctx == neg, the two differ in N or out_channels, or n_timesteps > 1 and either workspace was not bound with
+ * per_token = 1.  sigma_dev as in ltx2_dit_denoise_step.  (additive entries of ABI version 3)                                          */
+int ltx2_dit_guided_step(ltx2_dit* ctx, ltx2_dit* neg, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev,
+                         const float* mask, const float* clean, float cfg_scale, float sigma, float sigma_next, void* stream);
+/* ltx2_dit_graph_capture_cond with that step as its body: a linear chain of n_steps guided steps.  mask may be NULL (the uniform form, clean
+ * then NULL too); otherwise the per-token timesteps mask * sigma_i are formed into ctx's buffer and both contexts read them.  The graph
+ * belongs to ctx: ltx2_dit_graph_launch(ctx) replays it.                                                                               */
+int ltx2_dit_graph_capture_guided(ltx2_dit* ctx, ltx2_dit* neg, float* latent, const float* host_sigmas, int n_steps,
+                                  const float* mask, int64_t n_mask, const float* clean, int64_t n_clean, float cfg_scale, void* stream);
 int ltx2_dit_graph_capture_av(ltx2_dit* ctx, float* v_latent, float* a_latent, const float* host_sigmas, int n_steps,
                               void* stream);
 int ltx2_dit_graph_launch(ltx2_dit* ctx, void* stream);

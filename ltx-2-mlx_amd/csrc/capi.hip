@@ -369,6 +369,13 @@ int ltx2_euler_step(const float* x, const float* x0, const float* mask, const fl
     return euler_step_launch(x, x0, mask, clean, sigma, sigma_next, out, rows, C, (hipStream_t)stream);
 }
 
+int ltx2_guided_euler_step(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, int64_t ts_stride,
+                           const float* mask, const float* clean, float cfg_scale, float sigma, float sigma_next,
+                           float* out, int rows, int C, void* stream) {
+    return guided_euler_step_launch(x, vel_cond, vel_uncond, ts, (long)ts_stride, mask, clean, cfg_scale, sigma, sigma_next, out, rows, C,
+                                    (hipStream_t)stream);
+}
+
 int ltx2_vae_prepare_latent(const float* latent, const float* std, const float* mean, const float* noise,
                             float noise_scale, void* out_bf16, int C, int64_t P, void* stream) {
     LTX2_CHECK_ARG(latent && std && mean && out_bf16, "vae_prepare_latent: null operand");

@@ -1272,6 +1272,62 @@ int ltx2_dit_graph_capture_cond(ltx2_dit* c, float* latent, const float* host_si
     return end_capture(c, rc, st);
 }
 
+// Classifier-free guidance on the VideoOnly engine (keyframe interpolation's stage 1): two evaluations per step, the positive prompt through `c`
+// and the negative one through `neg` (a second context over the same weights), then ONE element-wise pass.  Everything goes onto the caller's
+// stream in order: each evaluation already fills the device, so a captured loop is a linear chain.
+namespace {
+int guided_ready(ltx2_dit* c, ltx2_dit* neg, int n_ts, const char* who) {
+    LTX2_CHECK_ARG(c && neg, "%s: null context", who);
+    LTX2_CHECK_ARG(c != neg, "%s: the negative prompt needs a context of its own (ctx == neg)", who);
+    LTX2_CHECK_ARG(!c->av && !neg->av, "%s: guidance runs on VideoOnly contexts (the video twin of an AudioVideo model)", who);
+    LTX2_CHECK_ARG(c->prepared && neg->prepared, "%s: ltx2_dit_prepare has not been called on both contexts", who);
+    LTX2_CHECK_ARG(c->m[0].N == neg->m[0].N && c->m[0].Cout == neg->m[0].Cout, "%s: the contexts differ: %d tokens x %d channels against %d x %d", who,
+                   c->m[0].N, c->m[0].Cout, neg->m[0].N, neg->m[0].Cout);
+    LTX2_CHECK_ARG(n_ts == 1 || (c->per_token && neg->per_token), "%s: a workspace was not bound for per-token timesteps", who);
+    return LTX2_OK;
+}
+
+int guided_step(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* ts, int n_ts, const float* sigma_dev, const float* mask,
+                const float* clean, float cfg_scale, float sigma, float sigma_next, hipStream_t st) {
+    LTX2_CHECK_ARG(sigma != 0.f, "Sigma can't be 0.0");
+    LTX2_CHECK_ARG((mask == nullptr) == (clean == nullptr), "dit_guided_step: mask and clean go together");
+    const Mod& m = c->m[0];
+    const ModIn pos[1] = {{latent, ts, n_ts, sigma_dev, m.vel}};
+    const ModIn ngt[1] = {{latent, ts, n_ts, sigma_dev, neg->m[0].vel}};
+    TRY(forward(c, pos, st));
+    TRY(forward(neg, ngt, st));
+    return guided_euler_step_launch(latent, m.vel, neg->m[0].vel, ts, n_ts == 1 ? 0 : 1, mask, clean, cfg_scale, sigma, sigma_next, latent,
+                                    m.N, m.Cout, st);
+}
+}  // namespace
+
+int ltx2_dit_guided_step(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev,
+                         const float* mask, const float* clean, float cfg_scale, float sigma, float sigma_next, void* stream) {
+    LTX2_CHECK_ARG(latent && timesteps, "dit_guided_step: null argument");
+    TRY(guided_ready(c, neg, n_timesteps, "dit_guided_step"));
+    return guided_step(c, neg, latent, timesteps, n_timesteps, sigma_dev ? sigma_dev : timesteps, mask, clean, cfg_scale, sigma, sigma_next,
+                       (hipStream_t)stream);
+}
+
+int ltx2_dit_graph_capture_guided(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* host_sigmas, int n_steps, const float* mask,
+                                  int64_t n_mask, const float* clean, int64_t n_clean, float cfg_scale, void* stream) {
+    LTX2_CHECK_ARG(latent && host_sigmas && n_steps > 0 && n_steps < 64, "dit_graph_capture_guided: bad argument");
+    TRY(guided_ready(c, neg, mask ? c->m[0].N : 1, "dit_graph_capture_guided"));
+    LTX2_CHECK_ARG((mask == nullptr) == (clean == nullptr), "dit_graph_capture_guided: mask and clean go together");
+    hipStream_t st = (hipStream_t)stream;
+    TRY(begin_capture(c, host_sigmas, n_steps, st));
+    int rc = LTX2_OK;
+    for (int i = 0; i < n_steps && rc == LTX2_OK; ++i) {
+        ModIn in[1] = {{latent, c->sigmas_dev + i, 1, c->sigmas_dev + i, nullptr}};
+        StepIo io[1] = {{latent, nullptr, nullptr, nullptr}};
+        rc = cond_modality(c, 0, mask, n_mask, clean, n_clean, c->sigmas_dev + i, in[0], io[0], st);      // ts = mask * sigma_i into c's buffer; both contexts read it
+        if (rc == LTX2_OK)
+            rc = guided_step(c, neg, latent, in[0].ts, in[0].n_ts, c->sigmas_dev + i, io[0].mask, io[0].clean, cfg_scale, host_sigmas[i],
+                             host_sigmas[i + 1], st);
+    }
+    return end_capture(c, rc, st);
+}
+
 int ltx2_dit_graph_capture_cond_av(ltx2_dit* c, float* v_latent, float* a_latent, const float* host_sigmas, int n_steps, const float* v_mask, int64_t n_v_mask,
                                    const float* v_clean, int64_t n_v_clean, const float* a_mask, int64_t n_a_mask, const float* a_clean, int64_t n_a_clean, void* stream) {
     LTX2_CHECK_ARG(v_latent && a_latent && host_sigmas && n_steps > 0 && n_steps < 64, "dit_graph_capture_cond_av: bad argument");

@@ -69,6 +69,13 @@ int x0_from_velocity_launch(const float* latent, const float* vel, const float* 
 int euler_step_launch(const float* x, const float* x0, const float* mask, const float* clean, float sigma,
                       float sigma_next, float* out, int rows, int C, hipStream_t stream);
 
+// One classifier-free-guided step in one pass, every operation individually rounded (the separate fp32 torch ops, bit for bit):
+// a = x - t*vc, b = x - t*vu, g = a + (cfg_scale - 1)*(a - b), d = mask ? g*m + clean*(1 - m) : g, out = x + ((x - d)/sigma)*(sigma_next - sigma);
+// t = ts[row * ts_stride] with ts_stride 0 or 1; out may equal x
+int guided_euler_step_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride,
+                             const float* mask, const float* clean, float cfg_scale, float sigma, float sigma_next, float* out,
+                             int rows, int C, hipStream_t stream);
+
 // ---- spatial upscaler (channels-last bf16 [P][C]) ----
 // y = [silu]( GroupNorm_G(x over (C/G, all positions)) * gamma + beta + res );  scratch: 2*G*(1 + ceil(P/16)) floats
 int groupnorm_silu_launch(const bf16* x, const bf16* res, bf16* y, long P, int C, int G, float eps, const float* gamma,

@@ -1119,6 +1119,44 @@ __global__ void tile_blend_finish_kernel(float* __restrict__ out, const float* _
     }
 }
 
+// One classifier-free-guided sampling step in one pass (pipelines/one_stage.py:224-330): the two x0_from_velocity launches, CFGGuider.guide,
+// post_process_latent and the Euler update, every operation rounded on its own so the result is, bit for bit, the separate fp32 torch ops
+// in that order.  V elements per thread (V divides C, so a vector never straddles a row); x and out may be the same buffer.
+__device__ __forceinline__ float guided_euler_one(float x, float vc, float vu, float t, float s1, bool blend, float m, float one_minus_m,
+                                                  float cl, float inv, float dt) {
+    const float a = sub_rn(x, mul_rn(t, vc));
+    const float b = sub_rn(x, mul_rn(t, vu));
+    float d = add_rn(a, mul_rn(s1, sub_rn(a, b)));
+    if (blend) d = add_rn(mul_rn(d, m), mul_rn(cl, one_minus_m));
+    return add_rn(x, mul_rn(mul_rn(sub_rn(x, d), inv), dt));
+}
+
+template <int V>
+__global__ void guided_euler_step_kernel(const float* x, const float* __restrict__ vc, const float* __restrict__ vu,
+                                         const float* __restrict__ ts, long ts_stride, const float* __restrict__ mask,
+                                         const float* __restrict__ clean, float s1, float inv, float dt, float* out, long n, int C) {
+    const long nv = n / V;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
+        const long e = i * V, row = e / C;
+        const float t = ts[row * ts_stride];
+        const bool blend = mask != nullptr;
+        const float m = blend ? mask[row] : 1.f, om = sub_rn(1.0f, m);
+        if constexpr (V == 4) {
+            const float4 xv = *(const float4*)(x + e), c4 = *(const float4*)(vc + e), u4 = *(const float4*)(vu + e);
+            float4 cl = {0.f, 0.f, 0.f, 0.f};
+            if (blend) cl = *(const float4*)(clean + e);
+            float4 o;
+            o.x = guided_euler_one(xv.x, c4.x, u4.x, t, s1, blend, m, om, cl.x, inv, dt);
+            o.y = guided_euler_one(xv.y, c4.y, u4.y, t, s1, blend, m, om, cl.y, inv, dt);
+            o.z = guided_euler_one(xv.z, c4.z, u4.z, t, s1, blend, m, om, cl.z, inv, dt);
+            o.w = guided_euler_one(xv.w, c4.w, u4.w, t, s1, blend, m, om, cl.w, inv, dt);
+            *(float4*)(out + e) = o;
+        } else {
+            out[e] = guided_euler_one(x[e], vc[e], vu[e], t, s1, blend, m, om, blend ? clean[e] : 0.f, inv, dt);
+        }
+    }
+}
+
 inline int grid_for(long n, int block, int cap = 4096) {
     long g = (n + block - 1) / block;
     return (int)(g < 1 ? 1 : (g > cap ? cap : g));
@@ -1411,6 +1449,27 @@ int euler_step_launch(const float* x, const float* x0, const float* mask, const 
     hipLaunchKernelGGL(euler_step_kernel, dim3(grid_for((long)rows * C, 256)), dim3(256), 0, stream, x, x0, mask, clean,
                        1.0f / sigma, sigma_next - sigma, out, rows, C);
     LTX2_CHECK_LAUNCH("euler_step_kernel");
+    return LTX2_OK;
+}
+
+int guided_euler_step_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride,
+                             const float* mask, const float* clean, float cfg_scale, float sigma, float sigma_next, float* out,
+                             int rows, int C, hipStream_t stream) {
+    LTX2_CHECK_ARG(sigma != 0.f, "Sigma can't be 0.0");   // reference core_utils.py:54-55
+    LTX2_CHECK_ARG(x && vel_cond && vel_uncond && ts && out && rows > 0 && C > 0, "guided_euler_step: null operand or empty shape");
+    LTX2_CHECK_ARG(ts_stride == 0 || ts_stride == 1, "guided_euler_step: ts_stride is 0 (one timestep) or 1 (one per row)");
+    LTX2_CHECK_ARG((mask == nullptr) == (clean == nullptr), "guided_euler_step: mask and clean go together");
+    const long n = (long)rows * C;
+    const float s1 = cfg_scale - 1.0f, inv = 1.0f / sigma, dt = sigma_next - sigma;
+    // 16-byte accesses need every [rows][C] operand on a 16-byte boundary as well as C % 4 == 0
+    const uintptr_t al = (uintptr_t)x | (uintptr_t)vel_cond | (uintptr_t)vel_uncond | (uintptr_t)out | (uintptr_t)clean;
+    if (C % 4 == 0 && (al & 15) == 0)
+        hipLaunchKernelGGL(guided_euler_step_kernel<4>, dim3(grid_for(n / 4, 256)), dim3(256), 0, stream, x, vel_cond, vel_uncond, ts, ts_stride,
+                           mask, clean, s1, inv, dt, out, n, C);
+    else
+        hipLaunchKernelGGL(guided_euler_step_kernel<1>, dim3(grid_for(n, 256)), dim3(256), 0, stream, x, vel_cond, vel_uncond, ts, ts_stride,
+                           mask, clean, s1, inv, dt, out, n, C);
+    LTX2_CHECK_LAUNCH("guided_euler_step_kernel");
     return LTX2_OK;
 }
 

@@ -505,6 +505,28 @@ def euler_step(x: torch.Tensor, x0: torch.Tensor, sigma: float, sigma_next: floa
     return out
 
 
+def guided_euler_step(x: torch.Tensor, vel_cond: torch.Tensor, vel_uncond: torch.Tensor, timesteps: torch.Tensor, cfg_scale: float, sigma: float,
+                      sigma_next: float, mask: Optional[torch.Tensor] = None, clean: Optional[torch.Tensor] = None,
+                      out: Optional[torch.Tensor] = None, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """One classifier-free-guided step over fp32 [N, C] (ltx2_guided_euler_step): x0 of both velocities, CFGGuider.guide, the mask / clean
+    blend and the Euler update in one pass, every operation individually rounded.  timesteps: 1 or N elements; `out` may be `x`;
+    `dtype` picks the library build (the kernel is fp32 in both)."""
+    n, c = x.shape
+    timesteps = _c(timesteps.float())
+    if timesteps.numel() not in (1, n):
+        raise ValueError(f"timesteps has {timesteps.numel()} elements; expected 1 or N={n}")
+    if out is None:
+        out = torch.empty_like(x)
+    for t in (x, vel_cond, vel_uncond, out) + ((mask, clean) if mask is not None else ()):
+        assert t is not None and t.dtype == torch.float32 and t.is_contiguous()
+    assert vel_cond.shape == x.shape and vel_uncond.shape == x.shape and out.shape == x.shape
+    assert mask is None or (mask.numel() == n and clean.shape == x.shape)
+    nv.check(nv.lib(dtype).ltx2_guided_euler_step(nv.ptr(x), nv.ptr(vel_cond), nv.ptr(vel_uncond), nv.ptr(timesteps), 0 if timesteps.numel() == 1 else 1,
+                                                  nv.ptr(mask), nv.ptr(clean), float(cfg_scale), float(sigma), float(sigma_next), nv.ptr(out), n, c,
+                                                  nv.stream()))
+    return out
+
+
 def pixnorm_mod_silu(x: torch.Tensor, table: torch.Tensor, te: Optional[torch.Tensor], shift_row: int, scale_row: int,
                      eps: float = 1e-6) -> torch.Tensor:
     assert x.dtype in ACT16

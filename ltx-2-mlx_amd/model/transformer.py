@@ -644,6 +644,54 @@ class LTXModel:
         else:
             nv.check(self._L.ltx2_dit_graph_capture(self._h, nv.ptr(latent), arr, len(sigmas) - 1, st.cuda_stream))
 
+    # ------------------------------------------------------------------ classifier-free guidance (video-only engine)
+    def _guided_pair(self, neg: "LTXModel") -> Tuple["LTXModel", "LTXModel"]:
+        """(positive, negative) VideoOnly contexts of a guided step: an AudioVideo model is used through its video twin."""
+        if not isinstance(neg, LTXModel):
+            raise ValueError("guidance needs a second LTXModel context (clone_sharing_weights()) for the negative prompt")
+        return (self._video_twin() if self.is_av else self), (neg._video_twin() if neg.is_av else neg)
+
+    def guided_step_(self, neg: "LTXModel", latent: torch.Tensor, video: Modality, sigma: float, sigma_next: float, cfg_scale: float,
+                     denoise_mask: Optional[torch.Tensor] = None, clean_latent: Optional[torch.Tensor] = None) -> None:
+        """In-place: latent (N, C) fp32 <- one classifier-free-guided Euler step -- the positive prompt through this context, the negative one
+        through `neg` (clone_sharing_weights(), prepared by the caller with the negative context), then x0 x 2 + CFGGuider.guide +
+        post_process_latent + Euler in one kernel, all enqueued by ONE C call (ltx2_dit_guided_step)."""
+        pos, ng = self._guided_pair(neg)
+        ts, n_ts = pos._timesteps(video)
+        assert latent.dtype == torch.float32 and latent.is_contiguous() and latent.dim() == 2
+        pos._ensure_prepared(video, per_token=(n_ts != 1))
+        pos._apply_context_masks(video)
+        sg = pos._sigma_scalar(sigma) if pos.cross_attention_adaln else None
+        nv.check(pos._L.ltx2_dit_guided_step(pos._h, ng._h, nv.ptr(latent), nv.ptr(ts), n_ts, nv.ptr(sg), nv.ptr(denoise_mask), nv.ptr(clean_latent),
+                                             float(cfg_scale), float(sigma), float(sigma_next), nv.stream()))
+
+    def capture_guided_graph(self, neg: "LTXModel", latent: torch.Tensor, sigmas: Sequence[float], cfg_scale: float,
+                             denoise_mask: Optional[torch.Tensor] = None, clean_latent: Optional[torch.Tensor] = None) -> None:
+        """hipGraph-capture len(sigmas)-1 guided steps over `latent` (N, C fp32), a linear chain of forward(self), forward(neg) and the guided
+        Euler kernel per step (ltx2_dit_graph_capture_guided).  Both contexts are prepared first (per_token=True when a mask is given); the
+        graph belongs to this context and replay_denoise_graph() replays it.  The tensors must stay alive while it is replayed."""
+        pos, ng = self._guided_pair(neg)
+        assert pos._prep_key is not None and ng._prep_key is not None, "call prepare() on both contexts first"
+        arr = (C.c_float * len(sigmas))(*[float(s) for s in sigmas])
+        st = torch.cuda.current_stream()
+        if st.cuda_stream == 0:
+            raise RuntimeError("graph capture needs a non-default stream: use `with torch.cuda.stream(torch.cuda.Stream()):`")
+        if denoise_mask is not None:
+            assert clean_latent is not None and denoise_mask.dtype == torch.float32 and clean_latent.dtype == torch.float32
+            assert denoise_mask.is_contiguous() and clean_latent.is_contiguous() and denoise_mask.dim() == 1
+        n_el = lambda t: 0 if t is None else t.numel()
+        pos._graph_refs = (latent, denoise_mask, clean_latent, ng)
+        nv.check(pos._L.ltx2_dit_graph_capture_guided(pos._h, ng._h, nv.ptr(latent), arr, len(sigmas) - 1, nv.ptr(denoise_mask), n_el(denoise_mask),
+                                                      nv.ptr(clean_latent), n_el(clean_latent), float(cfg_scale), st.cuda_stream))
+        self._guided_graph_owner = pos
+
+    def replay_guided_graph(self) -> None:
+        """Replay the graph captured by capture_guided_graph (it belongs to the VideoOnly context that ran the capture)."""
+        owner = getattr(self, "_guided_graph_owner", None)
+        if owner is None:
+            raise RuntimeError("no guided graph captured")
+        nv.check(owner._L.ltx2_dit_graph_launch(owner._h, nv.stream()))
+
     def replay_denoise_graph(self) -> None:
         nv.check(self._L.ltx2_dit_graph_launch(self._h, nv.stream()))
 

@@ -192,3 +192,46 @@ def joint_denoise_loop(transformer, is_av_model: bool, video_state: LatentState,
         if callback:
             callback(i + 1, n)
     return video_state, audio_state
+
+
+def guided_denoise_loop(transformer, video_state: LatentState, sigmas, context: torch.Tensor, negative_context: Optional[torch.Tensor],
+                        guider, stepper, callback=None, use_hip_graph: bool = True) -> LatentState:
+    """Classifier-free guidance on the video-only model that does not leave the device (the reference's keyframe stage 1,
+    pipelines/keyframe_interpolation.py:223-296, and the video branch of pipelines/one_stage.py:224-330).  With a plain CFGGuider that is
+    enabled(), every step is ONE C call -- forward(positive), forward(negative), then x0 x 2 + guide + post_process_latent + Euler in one
+    kernel (LTXModel.guided_step_) -- and with no callback and fewer than 64 steps the whole loop is one captured graph.  A guider that is
+    not enabled, or any other guider class (CFGStarRescalingGuider's projection is a reduction over the latent), goes through
+    joint_denoise_loop.  `transformer` is an X0Model; an AudioVideo model is used through its video twin.  Returns the video state."""
+    from ..components.guiders import CFGGuider
+    model = transformer.velocity_model
+    if type(guider) is not CFGGuider or not guider.enabled():
+        return joint_denoise_loop(transformer, model.is_av, video_state, None, sigmas, context, None, stepper, callback, use_hip_graph,
+                                  negative_video_context=negative_context, video_guider=guider)[0]
+    if negative_context is None:
+        raise ValueError("guidance needs the negative prompt's encoding")
+    sig = [float(s) for s in sigmas]
+    n = len(sig) - 1
+    if model.is_av:
+        model = model._video_twin()
+    neg = model.clone_sharing_weights()
+    uniform = bool((video_state.denoise_mask == 1).all())
+    lat = video_state.latent[0].float().clone(memory_format=torch.contiguous_format)      # stepped in place: never the caller's tensor
+    mask = None if uniform else video_state.denoise_mask[0].reshape(-1).float().contiguous()
+    clean = None if uniform else video_state.clean_latent[0].float().contiguous()
+    model.prepare(context, video_state.positions, per_token=not uniform)
+    neg.prepare(negative_context, video_state.positions, per_token=not uniform)
+    if use_hip_graph and callback is None and n < 64:
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            model.capture_guided_graph(neg, lat, sig, guider.scale, denoise_mask=mask, clean_latent=clean)
+            model.replay_guided_graph()
+        torch.cuda.current_stream().wait_stream(side)
+    else:
+        for i in range(n):
+            st = video_state.replace(latent=lat[None])
+            model.guided_step_(neg, lat, modality_from_state(st, context, sig[i], uniform=uniform), sig[i], sig[i + 1], guider.scale,
+                               denoise_mask=mask, clean_latent=clean)
+            if callback:
+                callback(i + 1, n)
+    return video_state.replace(latent=lat[None].to(video_state.latent.dtype))

@@ -578,9 +578,21 @@ _OUT_OF_PATH_DEFAULTS = dict(
     cross_attn_scale=1.0, distilled_lora=None, stg_scale=0.0, apg_scale=1.0, control_video=None, save_control=False,
     ge_gamma=0.0, keyframes=None, ic_lora_weights=None, negative_prompt=None)
 # pipelines whose algorithm is not built: "two-stage" is the dev model's CFG stage 1 + distilled-LoRA stage 2 (TwoStageCFGConfig,
-# reference :1276-1431), "ic-lora" / "keyframe-interpolation" condition on control videos / keyframes (:1434-1636)
+# reference :1276-1431), "ic-lora" conditions on control videos (:1434-1549).  "keyframe-interpolation" (:1552-1637) is built, but only WITH
+# keyframes: without them it is refused like the other two (the reference raises ValueError there)
 _PIPELINES_BUILT = ("text-to-video", "distilled", "one-stage")
 _PIPELINES_KNOWN = _PIPELINES_BUILT + ("two-stage", "ic-lora", "keyframe-interpolation")
+
+
+def parse_keyframe(spec):
+    """'path:frame_index[:strength]' (one --keyframe argument) -> Keyframe; a Keyframe passes through (reference :1558-1568)."""
+    from ltx_2_mlx_amd.pipelines import Keyframe
+    if isinstance(spec, Keyframe):
+        return spec
+    parts = str(spec).split(":")
+    if len(parts) < 2:
+        raise ValueError(f"Invalid keyframe format: {spec}. Use 'path:frame_index' or 'path:frame_index:strength'")
+    return Keyframe(image_path=parts[0], frame_index=int(parts[1]), strength=float(parts[2]) if len(parts) > 2 else 0.95)
 
 
 def _frames_from_video(video):
@@ -678,7 +690,13 @@ def generate_video(
     safetensors metadata) or generate_audio=True runs the AudioVideo transformer through OneStagePipeline (fps 25,
     LTX2Scheduler over num_steps); everything else the standard video-only loop on the distilled sigma table; the VAE decoder is
     built from the checkpoint's `config.vae` record; upscale_spatial doubles the denoised latent before decoding (2W x 2H output).
-    pipeline_type "two-stage" / "ic-lora" / "keyframe-interpolation" raise NotImplementedError.
+    pipeline_type "two-stage" / "ic-lora" raise NotImplementedError, and so does "keyframe-interpolation" without keyframes.
+    pipeline_type="keyframe-interpolation" with keyframes (a list of 'path:frame_index[:strength]' strings, one per --keyframe) runs
+    KeyframeInterpolationPipeline (reference :1552-1637): stage 1 at half resolution over num_steps with classifier-free guidance at cfg_scale
+    (model_variant="distilled" forces 1), x2 spatial upscale, 3 refinement steps; the VAE encoder and the spatial upscaler are loaded
+    (random-initialised with a warning when the file is missing).  The negative encoding is Gemma's of `negative_prompt or ""` when Gemma
+    encodes, else `negative_embedding` of the --embedding file, else zeros.  Not combined with generate_audio, audio_path,
+    two_stage_distilled, upscale_temporal or image_path.
     MI355X extras: two_stage_distilled=True runs the reference's DistilledPipeline class (8 steps at half resolution, x2
     upscale, 3 steps; pipelines/distilled.py:274-505), which the reference's own CLI never wires; model_version="2.3" builds
     the LTX-2.3 architecture without a checkpoint (random init, for tests and benchmarks); fp8_resident keeps fp8 checkpoint
@@ -698,10 +716,11 @@ def generate_video(
     and encoded by AudioEncoder; the latent stays frozen through the denoise loop (denoise_mask = 0, reference
     pipelines/a2vid_two_stage.py:338-357) and is written to `<stem>_audio_latent.npz`; the original audio, not a decode of the latent,
     is muxed into the mp4 when an ffmpeg binary exists."""
+    kf_pipeline = pipeline_type == "keyframe-interpolation" and bool(keyframes)
     given = dict(early_layers_only=early_layers_only,
                  enhance_prompt_flag=enhance_prompt_flag and use_gemma, cross_attn_scale=cross_attn_scale, distilled_lora=distilled_lora,
                  stg_scale=stg_scale, apg_scale=apg_scale, control_video=control_video, save_control=save_control, ge_gamma=ge_gamma,
-                 keyframes=keyframes, ic_lora_weights=ic_lora_weights)
+                 keyframes=None if kf_pipeline else keyframes, ic_lora_weights=ic_lora_weights)
     # Gemma encodes the prompt (and the negative prompt) when its weights are there and no pre-computed encoding is given
     gemma_encodes = bool(use_gemma and not (embedding_path or text_features_path) and gemma_path and os.path.exists(gemma_path))
     if negative_prompt is not None and not gemma_encodes:
@@ -711,10 +730,26 @@ def generate_video(
             raise NotImplementedError(f"{k}={v!r} is outside the MI355X hot path (see DESIGN.md); leave it at its default {_OUT_OF_PATH_DEFAULTS[k]!r}")
     if pipeline_type not in _PIPELINES_KNOWN:
         raise ValueError(f"unknown pipeline_type {pipeline_type!r}; the reference knows {_PIPELINES_KNOWN}")
-    if pipeline_type not in _PIPELINES_BUILT:
+    if pipeline_type not in _PIPELINES_BUILT and not kf_pipeline:
         raise NotImplementedError(f"pipeline_type={pipeline_type!r} is outside the MI355X hot path (see DESIGN.md): 'two-stage' is the dev "
                                   "model's CFG stage 1 + distilled-LoRA stage 2; for the distilled two-stage DistilledPipeline pass "
-                                  "two_stage_distilled=True (--two-stage-distilled)")
+                                  "two_stage_distilled=True (--two-stage-distilled); 'keyframe-interpolation' is built and needs its "
+                                  "images: pass keyframes / --keyframe path:frame_index[:strength]")
+    parsed_keyframes = []
+    if kf_pipeline:                                                      # before any model is loaded
+        for k, v in dict(generate_audio=generate_audio, audio_path=audio_path, two_stage_distilled=two_stage_distilled,
+                         upscale_temporal=upscale_temporal, image_path=image_path).items():
+            if v:
+                raise NotImplementedError(f"{k} with keyframes: the keyframe interpolation pipeline is video-only, conditions on its keyframes "
+                                          "alone and ends with its own x2 spatial stage")
+        from ltx_2_mlx_amd.pipelines import KeyframeInterpolationConfig
+        KeyframeInterpolationConfig(height=height, width=width, num_frames=num_frames)          # its ValueErrors (8k + 1 frames, multiples of 64)
+        parsed_keyframes = [parse_keyframe(k) for k in keyframes]
+        for kf in parsed_keyframes:
+            if not 0 <= kf.frame_index < num_frames:
+                raise ValueError(f"keyframe frame_index {kf.frame_index} is outside [0, {num_frames})")
+            if kf.image is None and not os.path.exists(kf.image_path):
+                raise FileNotFoundError(f"keyframe image not found: {kf.image_path}")
     output_dir = os.path.dirname(output_path)
     if output_dir:
         os.makedirs(output_dir, exist_ok=True)          # reference :1000-1003
@@ -771,6 +806,8 @@ def generate_video(
     if upscale_temporal and (_av_branch or two_stage_distilled):         # before any model is loaded
         raise NotImplementedError("upscale_temporal with the " + ("AudioVideo pipeline (the reference's AV branch returns before its upscalers)" if _av_branch
                                   else "two-stage DistilledPipeline (it returns before the post-denoise upscalers)"))
+    if kf_pipeline:
+        _need_cfg = False                   # guided by KeyframeInterpolationPipeline itself; a missing negative encoding becomes zeros there
     if _need_cfg and not _av_branch:
         raise NotImplementedError(f"cfg_scale={cfg_scale}: classifier-free guidance is built in OneStagePipeline (the AudioVideo / LTX-2.3 branch); the "
                                   "standard video-only loop of this script runs the distilled model's cfg = 1")
@@ -805,6 +842,9 @@ def generate_video(
         text_encoding, _ = encode_with_gemma(prompt, gemma_path, weights_path if have_ckpt else None, use_early_layers_only=early_layers_only,
                                              device=device, seed=seed)
         print("  Encoded with Gemma 3")
+        if kf_pipeline and cfg_scale != 1.0:
+            negative_encoding, _ = encode_with_gemma(negative_prompt or "", gemma_path, weights_path if have_ckpt else None, device=device, seed=seed)
+            print("  Encoded the negative prompt with Gemma 3")
     elif embedding_path:
         text_encoding, _ = load_text_embedding(embedding_path, device)
         z = np.load(embedding_path)
@@ -909,6 +949,36 @@ def generate_video(
         from ltx_2_mlx_amd.pipelines import ImageCondition
         print(f"  Image conditioning: {image_path} (strength={image_strength})")
         images = [ImageCondition(image_path=image_path, frame_index=0, strength=image_strength)]
+
+    if kf_pipeline:
+        # === KEYFRAME INTERPOLATION PIPELINE (reference :1552-1637) ===
+        print("\n=== Using Keyframe Interpolation Pipeline ===")
+        for kf in parsed_keyframes:
+            print(f"  Keyframe: {kf.image_path} at frame {kf.frame_index} (strength={kf.strength})")
+        if model is None:
+            if use_placeholder:
+                print("  Keyframe interpolation requires model - cannot use placeholder mode")
+                return None
+            raise ValueError("Keyframe interpolation pipeline requires a loaded model")
+        if vae_decoder is None:
+            raise ValueError("Keyframe interpolation pipeline requires VAE decoder")
+        from ltx_2_mlx_amd.pipelines import KeyframeInterpolationConfig, KeyframeInterpolationPipeline
+        conf = KeyframeInterpolationConfig(height=height, width=width, num_frames=num_frames, seed=seed, fps=24.0, num_inference_steps=num_steps,
+                                           cfg_scale=cfg_scale, use_hip_graph=use_hip_graph, tiling_config=TilingConfig.default() if tiled_vae else None)
+        print("[3.5/5] VAE encoder")
+        if not have_ckpt:
+            print("  Warning: no checkpoint, the VAE encoder is random-initialised")
+        print("[3.6/5] spatial upscaler")
+        spatial_upscaler_weights = spatial_upscaler_weights or "weights/ltx-2/ltx-2-spatial-upscaler-x2-1.0.safetensors"
+        pipe = KeyframeInterpolationPipeline(model, make_encoder(), vae_decoder, spatial_upscaler=make_upscaler())
+        if conf.cfg_scale != 1.0 and negative_encoding is None:
+            print("  Negative prompt: no encoding given, using zeros of the context's shape (the reference's null text encoding)")
+        print(f"[5/5] Running keyframe interpolation ({num_steps} steps)...")
+        t0 = time.time()
+        frames = _frames_from_video(pipe(text_encoding, None, parsed_keyframes, conf, negative_text_encoding=negative_encoding))
+        torch.cuda.synchronize()
+        print(f"  keyframe interpolation: {(time.time() - t0):.3f} s -> {tuple(frames.shape)}, DiT tokens per stage {pipe.token_counts}")
+        return finish(frames)
 
     if two_stage_distilled:
         # MI355X extra: the reference's DistilledPipeline class (pipelines/distilled.py:274-505): 8 steps at half resolution, x2

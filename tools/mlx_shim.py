@@ -241,8 +241,8 @@ def ones(shape, dtype=float32):
     return Arr(torch.ones(_shape(shape), dtype=_td(dtype)))
 
 
-def full(shape, v, dtype=float32):
-    return Arr(torch.full(_shape(shape), float(_unwrap(v)) if not isinstance(_unwrap(v), torch.Tensor) else _unwrap(v).item(), dtype=_td(dtype)))
+def full(shape, vals, dtype=float32):        # MLX's own parameter name: the reference passes it by keyword
+    return Arr(torch.full(_shape(shape), float(_unwrap(vals)) if not isinstance(_unwrap(vals), torch.Tensor) else _unwrap(vals).item(), dtype=_td(dtype)))
 
 
 zeros_like = lambda a: Arr(torch.zeros_like(a.t))
