@@ -108,11 +108,12 @@ int ltx2_flash_attn_rowscale(const void* Q, int64_t ldq, const void* K, int64_t 
  * ltx2_gemm_bf16_fold: ltx2_gemm_bf16 with the producer / consumer half of that identity:
  *   epilogue RESID_GATE_F32 (x += gate_table * (acc + bias), row-invariant gate): shadow[m][n] = 16-bit(x_new[m][n] * (1 + shadow_scale[n]))
  *     (row stride ld_shadow; shadow_scale null: * 1) and shadow_ss[(n / 256) * ld_ss + m] = the sum of x_new[m][n]^2 over each 256-column tile
- *     (ld_ss >= the row tiles' extent: M rounded up to a multiple of 256 is always enough; % 4 == 0);
+ *     (ld_ss >= the row tiles' extent: M rounded up to a multiple of 256 is always enough; % 4 == 0); shadow_scale 16-byte aligned (the epilogue loads
+ *     four floats at a time) and ld_shadow >= N (narrower rows would overlap), else *supported = 0;
  *   epilogue BF16 / GELU_BF16: out = epilogue(r[m] * acc + bias) with r[m] = rsqrt(sum_{j < rf_nparts} rf_parts[j * rf_ld + m] / rf_dim + rf_eps)
  *     formed inside the kernel (rf_parts = a producer's shadow_ss, rf_nparts <= 24).
  *   *supported = 0 (nothing launched) when the 4-wave layout-3 kernel does not take the problem (M >= 1024, N % 256 == 0, K % 128 == 0, dense 16-bit
- *   weights) or neither half is asked for.                                                                                                         */
+ *   weights, the bfloat16 build) or neither half is asked for.                                                                                      */
 int ltx2_gemm_bf16_fold(const void* A, int64_t lda, const void* W, const float* bias, void* out, int64_t ldo, int M, int N, int K, int epilogue,
                         const float* gate_table, void* shadow, int64_t ld_shadow, const float* shadow_scale, float* shadow_ss, int64_t ld_ss,
                         const float* rf_parts, int64_t rf_ld, int rf_nparts, int rf_dim, float rf_eps, int* supported, void* stream);

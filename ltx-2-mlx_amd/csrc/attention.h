@@ -31,5 +31,41 @@ struct AttnParams {
     const float* gate_bias;
 };
 
+// ---- filling an AttnParams: operands and shape first, then what the call adds (kmask is one field: assign it) ----
+// scale_log2e is taken as given: callers form it by expressions of their own, which need not round alike
+inline AttnParams attn_params(const void* Q, long ldq, const void* K, long ldk, const void* VT, int Npad, void* O, long ldo, int Nq, int Nkv, int H,
+                              int head_dim, float scale_log2e) {
+    AttnParams a{};
+    a.Q = (const bf16*)Q;
+    a.ldq = ldq;
+    a.K = (const bf16*)K;
+    a.ldk = ldk;
+    a.VT = (const bf16*)VT;
+    a.vt_head_stride = (long)head_dim * Npad;
+    a.Npad = Npad;
+    a.O = (bf16*)O;
+    a.ldo = ldo;
+    a.Nq = Nq;
+    a.Nkv = Nkv;
+    a.H = H;
+    a.head_dim = head_dim;
+    a.scale_log2e = scale_log2e;
+    return a;
+}
+// q's RMS normalisation over q_norm_dim columns as a per-row softmax scale, from q_ss_ld partial sums of squares per row
+inline void attn_set_rowscale(AttnParams& a, const float* q_ss, int q_ss_ld, int q_norm_dim, float q_eps) {
+    a.q_ss = q_ss;
+    a.q_ss_ld = q_ss_ld;
+    a.q_norm_dim = q_norm_dim;
+    a.q_eps = q_eps;
+}
+// per-head output gates from logits [Nq][gate_ld]; parts > 1: that many partial logit arrays, bias[H] added to their sum
+inline void attn_set_gate(AttnParams& a, const float* gate, int gate_ld, int parts = 1, const float* bias = nullptr) {
+    a.gate = gate;
+    a.gate_ld = gate_ld;
+    a.gate_parts = parts;
+    a.gate_bias = bias;
+}
+
 int attn_launch(const AttnParams& p, hipStream_t stream);
 int vt_transpose_launch(const bf16* V, long ld, bf16* VT, int Nkv, int Npad, int H, hipStream_t stream, int head_dim = 128);

@@ -41,9 +41,7 @@ int ltx2_gemm_bf16(const void* A, int64_t lda, const void* W, const float* bias,
     LTX2_CHECK_ARG(epilogue >= 0 && epilogue <= LTX2_EPI_ADD_BF16, "gemm: epilogue %d out of range", epilogue);
     LTX2_CHECK_ARG(epilogue != LTX2_EPI_ADD_BF16 || res, "gemm: epilogue ADD_BF16 needs res");
     GemmParams p = gemm_dense_params((const bf16*)A, lda, (const bf16*)W, bias, out, ldo, M, N, K);
-    p.gate = gate;
-    p.gate_stride = gate_stride;
-    p.gate_table = gate_table;
+    gemm_set_gate(p, gate, gate_stride, gate_table);
     p.res = (const bf16*)res;
     p.ldres = ldres;
     return gemm_launch(p, epilogue, false, (hipStream_t)stream);
@@ -73,17 +71,9 @@ int ltx2_gemm_bf16_fold(const void* A, int64_t lda, const void* W, const float* 
     LTX2_CHECK_ARG(A && W && out && supported, "gemm_bf16_fold: null argument");
     LTX2_CHECK_ARG(epilogue == LTX2_EPI_BF16 || epilogue == LTX2_EPI_GELU_BF16 || epilogue == LTX2_EPI_RESID_GATE_F32, "gemm_bf16_fold: epilogue %d (BF16, GELU_BF16 or RESID_GATE_F32)", epilogue);
     GemmParams p = gemm_dense_params((const bf16*)A, lda, (const bf16*)W, bias, out, ldo, M, N, K);
-    p.gate_table = gate_table;
-    p.shadow = (bf16*)shadow;
-    p.ld_shadow = ld_shadow;
-    p.shadow_scale = shadow_scale;
-    p.shadow_ss = shadow_ss;
-    p.ld_ss = ld_ss;
-    p.rf_parts = rf_parts;
-    p.rf_ld = rf_ld;
-    p.rf_nparts = rf_nparts;
-    p.rf_dim = rf_dim;
-    p.rf_eps = rf_eps;
+    gemm_set_gate(p, nullptr, 0, gate_table);
+    gemm_set_fold_producer(p, shadow, ld_shadow, shadow_scale, shadow_ss, ld_ss);
+    gemm_set_fold_consumer(p, rf_parts, rf_ld, rf_nparts, rf_dim, rf_eps);
     *supported = ((p.shadow || p.rf_parts) && gemm_fold_supported(p, epilogue)) ? 1 : 0;
     if (!*supported) return LTX2_OK;
     return gemm_launch(p, epilogue, false, (hipStream_t)stream);
@@ -93,25 +83,8 @@ int ltx2_flash_attn_rowscale(const void* Q, int64_t ldq, const void* K, int64_t 
                              int H, int head_dim, float scale, const float* q_ss, int q_ss_ld, int q_norm_dim, float q_eps, void* stream) {
     LTX2_CHECK_ARG(Q && K && VT && out && q_ss, "flash_attn_rowscale: null operand");
     LTX2_CHECK_ARG(head_dim == 128, "flash_attn_rowscale: head_dim=%d, only 128 is implemented", head_dim);
-    AttnParams a{};
-    a.Q = (const bf16*)Q;
-    a.ldq = ldq;
-    a.K = (const bf16*)K;
-    a.ldk = ldk;
-    a.VT = (const bf16*)VT;
-    a.vt_head_stride = (long)head_dim * Npad;
-    a.head_dim = head_dim;
-    a.O = (bf16*)out;
-    a.ldo = ldo;
-    a.Nq = Nq;
-    a.Nkv = Nkv;
-    a.Npad = Npad;
-    a.H = H;
-    a.scale_log2e = scale * 1.4426950408889634f;
-    a.q_ss = q_ss;
-    a.q_ss_ld = q_ss_ld;
-    a.q_norm_dim = q_norm_dim;
-    a.q_eps = q_eps;
+    AttnParams a = attn_params(Q, ldq, K, ldk, VT, Npad, out, ldo, Nq, Nkv, H, head_dim, scale * 1.4426950408889634f);
+    attn_set_rowscale(a, q_ss, q_ss_ld, q_norm_dim, q_eps);
     return attn_launch(a, (hipStream_t)stream);
 }
 
@@ -119,21 +92,7 @@ int ltx2_flash_attn_keymask(const void* Q, int64_t ldq, const void* K, int64_t l
                             int H, int head_dim, float scale, const float* mask, void* words, void* stream) {
     LTX2_CHECK_ARG(Q && K && VT && out && mask && words, "flash_attn_keymask: null operand");
     if (const int rc = keymask_words_launch(mask, Nkv, (unsigned long long*)words, Npad / 64, (hipStream_t)stream)) return rc;
-    AttnParams a{};
-    a.Q = (const bf16*)Q;
-    a.ldq = ldq;
-    a.K = (const bf16*)K;
-    a.ldk = ldk;
-    a.VT = (const bf16*)VT;
-    a.vt_head_stride = (long)head_dim * Npad;
-    a.head_dim = head_dim;
-    a.O = (bf16*)out;
-    a.ldo = ldo;
-    a.Nq = Nq;
-    a.Nkv = Nkv;
-    a.Npad = Npad;
-    a.H = H;
-    a.scale_log2e = scale * 1.4426950408889634f;
+    AttnParams a = attn_params(Q, ldq, K, ldk, VT, Npad, out, ldo, Nq, Nkv, H, head_dim, scale * 1.4426950408889634f);
     a.kmask = (const unsigned long long*)words;
     return attn_launch(a, (hipStream_t)stream);
 }
@@ -162,9 +121,7 @@ int ltx2_gemm_fp8(const void* A8, int64_t lda, const float* ascale, const void* 
     GemmParams p = gemm_dense_params(nullptr, lda, nullptr, bias, out, ldo, M, N, K);
     gemm_set_w8(p, W8, wscale);
     gemm_set_a8(p, A8, ascale, lda);
-    p.gate = gate;
-    p.gate_stride = gate_stride;
-    p.gate_table = gate_table;
+    gemm_set_gate(p, gate, gate_stride, gate_table);
     return gemm_launch(p, epilogue, false, (hipStream_t)stream);
 }
 
@@ -193,9 +150,7 @@ int ltx2_gemm_w8a16(const void* A, int64_t lda, const void* W8, const float* wsc
     LTX2_CHECK_ARG(A && W8 && wscale && out, "gemm_w8a16: null operand");
     GemmParams p = gemm_dense_params((const bf16*)A, lda, nullptr, bias, out, ldo, M, N, K);
     gemm_set_w8(p, W8, wscale);
-    p.gate = gate;
-    p.gate_stride = gate_stride;
-    p.gate_table = gate_table;
+    gemm_set_gate(p, gate, gate_stride, gate_table);
     return gemm_launch(p, epilogue, false, (hipStream_t)stream);
 }
 
@@ -247,23 +202,8 @@ int ltx2_flash_attn_gated(const void* Q, int64_t ldq, const void* K, int64_t ldk
                           int H, int head_dim, float scale, const float* gate_logits, int gate_ld, void* stream) {
     LTX2_CHECK_ARG(Q && K && VT && out && gate_logits && gate_ld >= H, "flash_attn_gated: null operand / gate_ld < H");
     LTX2_CHECK_ARG(head_dim == 128 || head_dim == 64, "flash_attn_gated: head_dim=%d, only 128 and 64 are implemented", head_dim);
-    AttnParams a{};
-    a.Q = (const bf16*)Q;
-    a.ldq = ldq;
-    a.K = (const bf16*)K;
-    a.ldk = ldk;
-    a.VT = (const bf16*)VT;
-    a.vt_head_stride = (long)head_dim * Npad;
-    a.head_dim = head_dim;
-    a.O = (bf16*)out;
-    a.ldo = ldo;
-    a.Nq = Nq;
-    a.Nkv = Nkv;
-    a.Npad = Npad;
-    a.H = H;
-    a.scale_log2e = scale * 1.4426950408889634f;
-    a.gate = gate_logits;
-    a.gate_ld = gate_ld;
+    AttnParams a = attn_params(Q, ldq, K, ldk, VT, Npad, out, ldo, Nq, Nkv, H, head_dim, scale * 1.4426950408889634f);
+    attn_set_gate(a, gate_logits, gate_ld);
     return attn_launch(a, (hipStream_t)stream);
 }
 
@@ -273,25 +213,8 @@ int ltx2_flash_attn_gated_parts(const void* Q, int64_t ldq, const void* K, int64
     LTX2_CHECK_ARG(Q && K && VT && out && x && gate_w && gate_b && parts, "flash_attn_gated_parts: null operand");
     LTX2_CHECK_ARG(head_dim == 128 || head_dim == 64, "flash_attn_gated_parts: head_dim=%d, only 128 and 64 are implemented", head_dim);
     if (const int rc = gate_logits_parts_launch((const bf16*)x, ldx, (const bf16*)gate_w, parts, Nq, Dq, H, (hipStream_t)stream)) return rc;
-    AttnParams a{};
-    a.Q = (const bf16*)Q;
-    a.ldq = ldq;
-    a.K = (const bf16*)K;
-    a.ldk = ldk;
-    a.VT = (const bf16*)VT;
-    a.vt_head_stride = (long)head_dim * Npad;
-    a.head_dim = head_dim;
-    a.O = (bf16*)out;
-    a.ldo = ldo;
-    a.Nq = Nq;
-    a.Nkv = Nkv;
-    a.Npad = Npad;
-    a.H = H;
-    a.scale_log2e = scale * 1.4426950408889634f;
-    a.gate = parts;
-    a.gate_ld = H;
-    a.gate_parts = GATE_LOGIT_PARTS;
-    a.gate_bias = gate_b;
+    AttnParams a = attn_params(Q, ldq, K, ldk, VT, Npad, out, ldo, Nq, Nkv, H, head_dim, scale * 1.4426950408889634f);
+    attn_set_gate(a, parts, H, GATE_LOGIT_PARTS, gate_b);
     return attn_launch(a, (hipStream_t)stream);
 }
 
@@ -299,21 +222,7 @@ int ltx2_flash_attn(const void* Q, int64_t ldq, const void* K, int64_t ldk, cons
                     int64_t ldo, int Nq, int Nkv, int H, int head_dim, float scale, void* stream) {
     LTX2_CHECK_ARG(Q && K && VT && out, "flash_attn: null operand");
     LTX2_CHECK_ARG(head_dim == 128 || head_dim == 64, "flash_attn: head_dim=%d, only 128 and 64 are implemented", head_dim);
-    AttnParams a{};
-    a.Q = (const bf16*)Q;
-    a.ldq = ldq;
-    a.K = (const bf16*)K;
-    a.ldk = ldk;
-    a.VT = (const bf16*)VT;
-    a.vt_head_stride = (long)head_dim * Npad;
-    a.head_dim = head_dim;
-    a.O = (bf16*)out;
-    a.ldo = ldo;
-    a.Nq = Nq;
-    a.Nkv = Nkv;
-    a.Npad = Npad;
-    a.H = H;
-    a.scale_log2e = scale * 1.4426950408889634f;
+    AttnParams a = attn_params(Q, ldq, K, ldk, VT, Npad, out, ldo, Nq, Nkv, H, head_dim, scale * 1.4426950408889634f);
     return attn_launch(a, (hipStream_t)stream);
 }
 

@@ -11,6 +11,9 @@
 // A model is two "modalities" (video m[0], audio m[1]; audio absent for VideoOnly) that run the
 // same per-block program (self-attention, text cross-attention, feed-forward) on their own widths,
 // plus the audio<->video cross-modal attention between them.
+//
+// Every GEMM and attention is enqueued the same way: build the parameter block from the operands (gemm_dense_params / attn_params), add what
+// the call needs through the named setters of gemm.h / attention.h, then hand it to dense() / attend().
 #include <math.h>
 #include <string.h>
 
@@ -338,20 +341,19 @@ int resolve(ltx2_dit* c) {
 
 thread_local ltx2_dit* g_prof_ctx = nullptr;
 
-// vt (optional): where the V third of a fused QKV projection goes as attention's V^T operand; *vt_done says whether the
-// GEMM's epilogue wrote it (else the caller runs vt_transpose_launch on the V columns of `out`).
-struct VtOut {
-    bf16* vt;
-    int col0, npad, hd;
-};
+// fp8-resident weight: p.W then holds the codes pointer; hand the GEMM (codes, per-row scale) instead, expanded inside the kernel.  false: dense 16-bit weights
+bool resident_fp8(ltx2_dit* c, GemmParams& p) {
+    auto f8 = c->fp8_scale.find((const void*)p.W);
+    if (f8 == c->fp8_scale.end()) return false;
+    gemm_set_w8(p, p.W, f8->second);
+    return true;
+}
 
 // fp8 compute (opt-in): would dense() send this GEMM to the fp8 MFMA?  (the video stream's big GEMMs on fp8-resident weights)
 bool f8_route(ltx2_dit* c, const bf16* W, int M, int N, int K, int epi) {
     if (!c->fp8_compute || !c->m[0].a8 || M < 1024 || M > c->m[0].N || K > 4 * c->m[0].D) return false;
-    auto f8 = c->fp8_scale.find((const void*)W);
-    if (f8 == c->fp8_scale.end()) return false;
-    GemmParams q = gemm_dense_params(nullptr, K, nullptr, nullptr, c->m[0].x, 8, M, N, K);
-    gemm_set_w8(q, W, f8->second);
+    GemmParams q = gemm_dense_params(nullptr, K, W, nullptr, c->m[0].x, 8, M, N, K);
+    if (!resident_fp8(c, q)) return false;
     gemm_set_a8(q, c->m[0].a8, c->m[0].a8s, K);
     return gemm_v4_f8_supported(q, epi);
 }
@@ -364,38 +366,27 @@ bool text_qfold_ok(ltx2_dit* c, int k) {
     if (m.D % 1024 != 0 || m.hd != 128) return false;
     const bf16* W = c->layers[0].m[k].text.q_w;
     GemmParams q = gemm_dense_params(m.h, m.D, W, nullptr, m.x, m.D, m.N, m.D, m.D);
+    resident_fp8(c, q);
     if (k == 0 && f8_route(c, W, m.N, m.D, m.D, EPI_BF16)) gemm_set_a8(q, m.a8, m.a8s, m.D);
-    auto f8 = c->fp8_scale.find((const void*)W);
-    if (f8 != c->fp8_scale.end()) gemm_set_w8(q, W, f8->second);
     return gemm_rowss_supported(q, EPI_BF16);
 }
 
 // round 6: can the text cross-attention's pre-norm of this modality's blocks be folded around attn1.to_out / attn2.to_q (block_attention())?  VideoOnly non-V2.3
-// ungated models on dense bf16 weights in the bfloat16 build (the un-normalised shadow is not safe in IEEE half), both GEMMs on the 4-wave layout-3 kernel
+// ungated models on dense bf16 weights in the bfloat16 build (the un-normalised shadow is not safe in IEEE half: gemm_fold_supported() refuses the float16 build),
+// both GEMMs on the 4-wave layout-3 kernel
 int fold_supported(ltx2_dit* c, int k) {
-#ifdef LTX2_F16
-    (void)c; (void)k;
-    return 0;
-#else
     if (c->av || c->v2 || c->gated || c->fp8_compute || !c->fp8_scale.empty() || k != 0) return 0;
     const Mod& m = c->m[k];
     if (!m.rss || m.D % 256 != 0 || m.D / 256 > GEMM_RF_MAX_PARTS) return 0;
     const BlockW& w = c->layers[0].m[k];
     // producer: attn1.to_out; consumer: attn2.to_q
     GemmParams q = gemm_dense_params(m.h, m.D, w.self.o_w, nullptr, m.x, m.D, m.N, m.D, m.D);
-    q.shadow = m.h;
-    q.ld_shadow = m.D;
-    q.shadow_ss = m.rss;
-    q.ld_ss = m.rss_ld;
+    gemm_set_fold_producer(q, m.h, m.D, nullptr, m.rss, m.rss_ld);
     if (!gemm_fold_supported(q, EPI_RESID_GATE_F32)) return 0;
     GemmParams r = gemm_dense_params(m.h, m.D, w.text.q_w, nullptr, m.qkv, m.D, m.N, m.D, m.D);
-    r.rf_parts = m.rss;
-    r.rf_ld = m.rss_ld;
-    r.rf_nparts = m.D / 256;
-    r.rf_dim = m.D;
+    gemm_set_fold_consumer(r, m.rss, m.rss_ld, m.D / 256, m.D, c->cfg.norm_eps);
     if (!gemm_fold_supported(r, EPI_BF16)) return 0;
     return 1;
-#endif
 }
 
 __global__ void vec_mul_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out, int n) {
@@ -403,54 +394,24 @@ __global__ void vec_mul_kernel(const float* __restrict__ a, const float* __restr
     if (i < n) out[i] = a[i] * b[i];
 }
 
-// A folded norm's share of one GEMM (GemmParams, "round 6"): producer fields for a gated-residual GEMM, consumer fields for the projection behind it
-struct Fold {
-    bf16* shadow = nullptr;
-    const float* shadow_scale = nullptr;
-    float* shadow_ss = nullptr;
-    long ld_shadow = 0;
-    const float* rf_parts = nullptr;
-    long ld_ss = 0;         // row stride of shadow_ss / rf_parts
-    int rf_nparts = 0, rf_dim = 0;
-    float rf_eps = 0.f;
-};
-
+// One GEMM of the engine.  The caller builds p (gemm_dense_params, then gemm_set_gate / gemm_set_vt / gemm_set_fold_* / p.rowss as the call needs); dense()
+// adds what only the engine knows: fp8-resident weights, the fp8-compute route, whether the epilogue can write a requested V^T, and the profiling bracket.
 // preq: the kernel that produced A already left its per-token e4m3fn codes + scales in m[0].a8 / a8s (norm_mod_launch's q8 output);
 // only valid when f8_route() says yes for this GEMM
-int dense(ltx2_dit* c, const bf16* A, long lda, const bf16* W, const float* bias, void* out, long ldo, int M, int N, int K, int epi,
-          hipStream_t st, const float* gate = nullptr, long gate_stride = 0, const float* gate_table = nullptr,
-          const VtOut* vt = nullptr, bool* vt_done = nullptr, bool preq = false, float* rowss = nullptr, const Fold* fold = nullptr) {
-    GemmParams p = gemm_dense_params(A, lda, W, bias, out, ldo, M, N, K);
-    if (fold) {
-        p.shadow = fold->shadow;
-        p.shadow_scale = fold->shadow_scale;
-        p.shadow_ss = fold->shadow_ss;
-        p.ld_shadow = fold->ld_shadow;
-        p.ld_ss = fold->ld_ss;
-        p.rf_parts = fold->rf_parts;
-        p.rf_ld = fold->ld_ss;
-        p.rf_nparts = fold->rf_nparts;
-        p.rf_dim = fold->rf_dim;
-        p.rf_eps = fold->rf_eps;
-    }
-    if (!c->fp8_scale.empty()) {
-        auto f8 = c->fp8_scale.find((const void*)W);
-        if (f8 != c->fp8_scale.end()) gemm_set_w8(p, W, f8->second);      // fp8-resident: codes + per-row scale, expanded inside the GEMM
-    }
-    p.gate = gate;
-    p.gate_stride = gate_stride;
-    p.gate_table = gate_table;
-    p.rowss = rowss;
+// vt_done (with gemm_set_vt): whether the GEMM's epilogue wrote V^T (else the caller runs vt_transpose_launch on the V columns of `out`)
+int dense(ltx2_dit* c, GemmParams p, int epi, hipStream_t st, bool preq = false, bool* vt_done = nullptr) {
+    const bf16* const A = p.A;
+    const bf16* const W = p.W;
+    if (!c->fp8_scale.empty()) resident_fp8(c, p);
     // fp8 compute (opt-in): the video stream's big GEMMs on fp8-resident weights take per-token-quantised activations and the fp8 MFMA
-    if (p.W8 && f8_route(c, W, M, N, K, epi)) {
-        if (!preq) TRY(quant_rows_fp8_launch(A, lda, M, K, c->m[0].a8, K, c->m[0].a8s, st));
-        gemm_set_a8(p, c->m[0].a8, c->m[0].a8s, K);
+    if (p.W8 && f8_route(c, W, p.M, p.N, p.K, epi)) {
+        if (!preq) TRY(quant_rows_fp8_launch(A, p.lda, p.M, p.K, c->m[0].a8, p.K, c->m[0].a8s, st));
+        gemm_set_a8(p, c->m[0].a8, c->m[0].a8s, p.K);
     } else if (preq) {
         ltx2_set_error("dit: a pre-quantised activation reached a GEMM that does not take the fp8 path");
         return LTX2_E_STATE;
     }
-    if (vt) {
-        gemm_set_vt(p, vt->vt, vt->col0, vt->npad, vt->hd);
+    if (p.vt) {
         *vt_done = gemm_vt_fused(p, epi);
         if (!*vt_done) p.vt = nullptr;
     }
@@ -468,7 +429,7 @@ int dense(ltx2_dit* c, const bf16* A, long lda, const bf16* W, const float* bias
     if (prof) {
         (void)hipEventRecord(pc->prof_ev[pc->prof_used + 1], st);
         pc->prof_used += 2;
-        pc->prof_flops += 2.0 * M * N * K;
+        pc->prof_flops += 2.0 * p.M * p.N * p.K;
     }
     return rc;
 }
@@ -497,11 +458,11 @@ int adaln_chain(ltx2_dit* c, Mod& m, const AdaW& a, const float* ts, long t_stri
         TRY(gemv_launch(e, D, a.lin_w, a.lin_b, emb, (long)a.rows * D, 1, a.rows * D, D, 1, 0, st));
     } else {
         TRY(timestep_sinusoid_launch(ts, t_stride, 0.f, mult, T, 256, nullptr, m.sin_b, st));
-        TRY(dense(c, m.sin_b, 256, a.t1_w, a.t1_b, m.e1_b, D, T, D, 256, EPI_SILU_BF16, st));
-        TRY(dense(c, m.e1_b, D, a.t2_w, a.t2_b, e_out, D, T, D, D, EPI_F32, st));
+        TRY(dense(c, gemm_dense_params(m.sin_b, 256, a.t1_w, a.t1_b, m.e1_b, D, T, D, 256), EPI_SILU_BF16, st));
+        TRY(dense(c, gemm_dense_params(m.e1_b, D, a.t2_w, a.t2_b, e_out, D, T, D, D), EPI_F32, st));
         hipLaunchKernelGGL(silu_cast_kernel, dim3(2048), dim3(256), 0, st, e_out, m.es_b, (long)T * D);
         LTX2_CHECK_LAUNCH("silu_cast_kernel");
-        TRY(dense(c, m.es_b, D, a.lin_w, a.lin_b, emb, (long)a.rows * D, T, a.rows * D, D, EPI_F32, st));
+        TRY(dense(c, gemm_dense_params(m.es_b, D, a.lin_w, a.lin_b, emb, (long)a.rows * D, T, a.rows * D, D), EPI_F32, st));
     }
     return LTX2_OK;
 }
@@ -512,35 +473,11 @@ struct GateRef {
     int parts = 1;
     const float* bias = nullptr;
 };
-int attend(const bf16* q, long ldq, const bf16* k, long ldk, const bf16* vt, int npad, bf16* out, long ldo, int nq,
-           int nkv, int H, int hd, hipStream_t st, const float* q_ss = nullptr, float q_eps = 0.f,
-           const unsigned long long* kmask = nullptr, GateRef gate = GateRef{}) {
-    AttnParams a{};
-    a.kmask = kmask;
-    a.gate = gate.p;        // per-head gate logits [nq][H] (V2.3): out *= 2 sigmoid(.) in the kernel's epilogue
-    a.gate_ld = H;
-    a.gate_parts = gate.parts;
-    a.gate_bias = gate.bias;
-    if (q_ss) {         // q_norm as a per-row softmax scale from the projection's partial sums (text cross-attention)
-        a.q_ss = q_ss;
-        a.q_ss_ld = H * hd / 64;
-        a.q_norm_dim = H * hd;
-        a.q_eps = q_eps;
-    }
-    a.Q = q;
-    a.ldq = ldq;
-    a.K = k;
-    a.ldk = ldk;
-    a.VT = vt;
-    a.vt_head_stride = (long)hd * npad;
-    a.O = out;
-    a.ldo = ldo;
-    a.Nq = nq;
-    a.Nkv = nkv;
-    a.Npad = npad;
-    a.H = H;
-    a.head_dim = hd;
-    a.scale_log2e = 1.4426950408889634f / sqrtf((float)hd);
+// the engine's softmax scale (1 / sqrt(d)) * log2(e), as attn_params() takes it
+inline float scale_log2e(int hd) { return 1.4426950408889634f / sqrtf((float)hd); }
+// One attention of the engine: a from attn_params() (+ attn_set_rowscale / a.kmask); gate = glog(): per-head gate logits [Nq][H] (V2.3), out *= 2 sigmoid(.) in the kernel's epilogue
+int attend(AttnParams a, GateRef gate, hipStream_t st) {
+    attn_set_gate(a, gate.p, a.H, gate.parts, gate.bias);
     return attn_launch(a, st);
 }
 
@@ -598,17 +535,18 @@ int gate_logits(ltx2_dit* c, Mod& m, const AttnW& w, const bf16* xin, int Dq, in
 // the gate logits gate_logits() left for the attention that follows (null for ungated models): the kernel's epilogue applies 2 sigmoid(.) per head
 GateRef glog(ltx2_dit* c, const Mod& m) { return c->gated ? GateRef{m.glog, m.glog_parts, m.glog_bias} : GateRef{}; }
 
-// K (k_norm applied, optional RoPE) and V^T of a text / cross-modal context
-int project_kv(ltx2_dit* c, const bf16* ctx, int rows, int Dc, const AttnW& w, int Di, int H, int hd, float eps, const float* cosb,
-               const float* sinb, bf16* kv, bf16* vt, int npad, hipStream_t st, const float* k_weight = nullptr) {
-    const VtOut vo{vt, Di, npad, hd};
+// K (k_norm applied, optional RoPE) and V^T of a text / cross-modal context.  p: the fused K | V projection (N = 2 Di, heads of hd); kn: the K half's norm weight
+int project_kv(ltx2_dit* c, GemmParams p, bf16* vt, int npad, int hd, const float* kn, const float* cosb, const float* sinb, hipStream_t st) {
+    const int Di = p.N / 2;
+    bf16* const kv = (bf16*)p.out;
+    gemm_set_vt(p, vt, Di, npad, hd);
     bool vt_done = false;           // V^T straight from the K/V GEMM's epilogue where the 4-wave kernel takes the shape
-    TRY(dense(c, ctx, Dc, w.kv_w, w.kv_b, kv, 2 * Di, rows, 2 * Di, Dc, EPI_BF16, st, nullptr, 0, nullptr, &vo, &vt_done));
+    TRY(dense(c, p, EPI_BF16, st, /*preq=*/false, &vt_done));
     const int offs[1] = {0};
-    const float* wts[1] = {k_weight ? k_weight : w.kn};
-    TRY(qknorm_rope_launch(kv, 2 * Di, rows, Di, hd, 1, offs, wts, eps, cosb, sinb, st));
+    const float* wts[1] = {kn};
+    TRY(qknorm_rope_launch(kv, 2 * Di, p.M, Di, hd, 1, offs, wts, c->cfg.norm_eps, cosb, sinb, st));
     if (vt_done) return LTX2_OK;
-    return vt_transpose_launch(kv + Di, 2 * Di, vt, rows, npad, H, st, hd);
+    return vt_transpose_launch(kv + Di, 2 * Di, vt, p.M, npad, Di / hd, st, hd);
 }
 
 // V2.3: the prompt-AdaLN-modulated text context of layer l and its K / V^T (transformer.py:427-455) -- a function of the prompt and sigma only
@@ -617,7 +555,8 @@ int text_kv(ltx2_dit* c, int k, int l, hipStream_t st) {
     const BlockW& w = c->layers[l].m[k];
     const int D = m.D;
     TRY(ctx_mod_launch(m.ctx, m.ctxm, m.S, D, w.prompt_sst + D, w.prompt_sst, m.prompt_emb + D, m.prompt_emb, st));
-    return project_kv(c, m.ctxm, m.S, D, w.text, D, m.H, m.hd, c->cfg.norm_eps, nullptr, nullptr, m.kv2, m.vt2, m.Spad, st, m.qfold ? m.knq + (long)l * D : nullptr);
+    return project_kv(c, gemm_dense_params(m.ctxm, D, w.text.kv_w, w.text.kv_b, m.kv2, 2 * D, m.S, 2 * D, D), m.vt2, m.Spad, m.hd,
+                      m.qfold ? m.knq + (long)l * D : w.text.kn, nullptr, nullptr, st);
 }
 
 // ---- round 6: the text cross-attention's plain RMS pre-norm folded around the two GEMMs beside it ----------------------------------------------------
@@ -629,20 +568,17 @@ int text_kv(ltx2_dit* c, int k, int l, hipStream_t st) {
 // one step ahead by the projection itself from an extra operand row.  That was built and measured in this round (git history: "fold: its own kernel
 // instantiations"): every kernel-level figure favoured it (three norm passes, 52 us per layer, for ~20 us of epilogue work), the step did not -- +0.3 ... +0.5 ms:
 // the GEMMs on both sides run 4-5 % slower inside the step than their stand-alone A/B says (profiles/r06_fold_norms.md).  Only this one stayed.
-// the two halves on a Fold: the producer writes x's shadow into h and its partial sums into rss; the consumer reads them back
-inline void fold_produce(Fold& f, Mod& m, const float* scale) {
-    f.shadow = m.h;
-    f.ld_shadow = m.D;
-    f.shadow_ss = m.rss;
-    f.ld_ss = m.rss_ld;
-    f.shadow_scale = scale;
-}
-inline void fold_consume(Fold& f, const Mod& m, float eps) {
-    f.rf_parts = m.rss;
-    f.ld_ss = m.rss_ld;
-    f.rf_nparts = m.D / 256;
-    f.rf_dim = m.D;
-    f.rf_eps = eps;
+
+// AdaLN rows of layer l: table row r + embedding row r; with one timestep per modality the sum was formed for every layer at the top of forward()
+// (tab = the sums, no embedding rows)
+struct AdaRows {
+    const float* tab;
+    const float* emb0;
+    int D;
+    const float* E(int r) const { return emb0 ? emb0 + (long)r * D : nullptr; }
+};
+AdaRows ada_rows(const ltx2_dit* c, const Mod& m, const BlockW& w, int l) {
+    return {m.use_comb ? m.comb + (long)l * (c->v2 ? 9 : 6) * m.D : w.sst, m.use_comb ? nullptr : m.emb, m.D};
 }
 
 // Self-attention, text cross-attention of one modality (transformer.py:503-554 / 191-226)
@@ -651,30 +587,35 @@ int block_attention(ltx2_dit* c, int k, int l, long es, hipStream_t st, int fold
     const BlockW& w = c->layers[l].m[k];
     const int N = m.N, D = m.D, H = m.H, hd = m.hd;
     const float eps = c->cfg.norm_eps;
-    // AdaLN rows: table row r + embedding row r; with one timestep per modality the sum was formed for every layer at the top of forward()
-    const float* const tab = m.use_comb ? m.comb + (long)l * (c->v2 ? 9 : 6) * D : w.sst;
-    const float* const emb0 = m.use_comb ? nullptr : m.emb;
-    auto E = [&](int r) { return emb0 ? emb0 + (long)r * D : nullptr; };
+    const AdaRows ada = ada_rows(c, m, w, l);
+    const float* const tab = ada.tab;
     // self-attention: AdaLN rows (shift, scale, gate) = sst[0:3] + emb[0:3]
     // fp8 compute: the norm kernels hand the following GEMM per-token e4m3fn codes directly (and skip the bf16 copy nobody else reads)
     const bool q1 = k == 0 && f8_route(c, w.self.qkv_w, N, 3 * D, D, EPI_BF16);
     const int fl = k == 0 ? fold : 0;
-    TRY(norm_mod_launch(m.x, D, (q1 && !c->gated) ? nullptr : m.h, D, N, D, eps, 0, tab + D, tab, E(1), E(0), es, st, q1 ? m.a8 : nullptr, D,
+    TRY(norm_mod_launch(m.x, D, (q1 && !c->gated) ? nullptr : m.h, D, N, D, eps, 0, tab + D, tab, ada.E(1), ada.E(0), es, st, q1 ? m.a8 : nullptr, D,
                         q1 ? m.a8s : nullptr));
     TRY(gate_logits(c, m, w.self, m.h, D, N, H, st));
-    const VtOut vo{m.vt, 2 * D, m.Npad, hd};
     bool vt_done = false;           // the QKV GEMM's epilogue writes V^T itself where it can (gemm_v4.hip)
-    TRY(dense(c, m.h, D, w.self.qkv_w, w.self.qkv_b, m.qkv, 3 * D, N, 3 * D, D, EPI_BF16, st, nullptr, 0, nullptr, &vo, &vt_done, q1));
+    {
+        GemmParams p = gemm_dense_params(m.h, D, w.self.qkv_w, w.self.qkv_b, m.qkv, 3 * D, N, 3 * D, D);
+        gemm_set_vt(p, m.vt, 2 * D, m.Npad, hd);
+        TRY(dense(c, p, EPI_BF16, st, q1, &vt_done));
+    }
     {
         const int offs[2] = {0, D};
         const float* wts[2] = {w.self.qn, w.self.kn};
         TRY(qknorm_rope_launch(m.qkv, 3 * D, N, D, hd, 2, offs, wts, eps, m.cosb, m.sinb, st));
     }
     if (!vt_done) TRY(vt_transpose_launch(m.qkv + 2 * D, 3 * D, m.vt, N, m.Npad, H, st, hd));
-    TRY(attend(m.qkv, 3 * D, m.qkv + D, 3 * D, m.vt, m.Npad, m.att, D, N, N, H, hd, st, nullptr, 0.f, nullptr, glog(c, m)));
-    Fold fo{};
-    if (fl >= 1) fold_produce(fo, m, nullptr);          // the new residual rows also leave as the cross-attention query projection's operand (plain RMS norm: no scale, no shift)
-    TRY(dense(c, m.att, D, w.self.o_w, w.self.o_b, m.x, D, N, D, D, EPI_RESID_GATE_F32, st, E(2), es, tab + 2 * D, nullptr, nullptr, false, nullptr, fl >= 1 ? &fo : nullptr));
+    TRY(attend(attn_params(m.qkv, 3 * D, m.qkv + D, 3 * D, m.vt, m.Npad, m.att, D, N, N, H, hd, scale_log2e(hd)), glog(c, m), st));
+    {
+        GemmParams p = gemm_dense_params(m.att, D, w.self.o_w, w.self.o_b, m.x, D, N, D, D);
+        gemm_set_gate(p, ada.E(2), es, tab + 2 * D);
+        // the new residual rows also leave as the cross-attention query projection's operand (plain RMS norm: no scale, no shift): their shadow into h, its partial sums into rss
+        if (fl >= 1) gemm_set_fold_producer(p, m.h, D, nullptr, m.rss, m.rss_ld);
+        TRY(dense(c, p, EPI_RESID_GATE_F32, st));
+    }
 
     // text cross-attention: no RoPE, no mask.  V1: plain RMSNorm on x, K/V cached per prompt.
     // V2.3 (transformer.py:427-455): q side modulated by rows (6,7) and gated by row 8; the context
@@ -686,7 +627,7 @@ int block_attention(ltx2_dit* c, int k, int l, long es, hipStream_t st, int fold
     unsigned char* a8q = q2 ? m.a8 : nullptr;
     float* a8sq = q2 ? m.a8s : nullptr;
     if (c->v2) {
-        TRY(norm_mod_launch(m.x, D, h2, D, N, D, eps, 0, tab + 7 * D, tab + 6 * D, E(7), E(6), es, st, a8q, D, a8sq));
+        TRY(norm_mod_launch(m.x, D, h2, D, N, D, eps, 0, tab + 7 * D, tab + 6 * D, ada.E(7), ada.E(6), es, st, a8q, D, a8sq));
         if (k == 0 && c->text_kv_ev) {      // projected ahead on the side stream (forward()): wait for it here
             TRY(event_wait(c->text_kv_ev, st));
             c->text_kv_ev = nullptr;
@@ -703,21 +644,26 @@ int block_attention(ltx2_dit* c, int k, int l, long es, hipStream_t st, int fold
     TRY(gate_logits(c, m, w.text, m.h, D, N, H, st));
     // q_norm folded (m.qfold): the projection's epilogue leaves the partial sums of squares of its rows; q_norm.weight already sits on the keys
     // (k_norm.weight * q_norm.weight, prepare) and the row's RMS factor becomes its softmax scale -- no pass over q between GEMM and attention
-    Fold fc{};
-    fold_consume(fc, m, eps);
-    TRY(dense(c, m.h, D, w.text.q_w, w.text.q_b, m.qkv, D, N, D, D, EPI_BF16, st, nullptr, 0, nullptr, nullptr, nullptr, q2, m.qfold ? m.qss : nullptr, fl >= 1 ? &fc : nullptr));
+    {
+        GemmParams p = gemm_dense_params(m.h, D, w.text.q_w, w.text.q_b, m.qkv, D, N, D, D);
+        if (m.qfold) p.rowss = m.qss;
+        if (fl >= 1) gemm_set_fold_consumer(p, m.rss, m.rss_ld, D / 256, D, eps);          // h holds the shadow: the row factors come from rss
+        TRY(dense(c, p, EPI_BF16, st, q2));
+    }
     if (!m.qfold) {
         const int offs[1] = {0};
         const float* wts[1] = {w.text.qn};
         TRY(qknorm_rope_launch(m.qkv, D, N, D, hd, 1, offs, wts, eps, nullptr, nullptr, st));
     }
-    TRY(attend(m.qkv, D, kk, 2 * D, vt, m.Spad, m.att, D, N, m.S, H, hd, st, m.qfold ? m.qss : nullptr, eps,
-               m.has_kmask ? m.kmask : nullptr, glog(c, m)));
-    if (c->v2)
-        TRY(dense(c, m.att, D, w.text.o_w, w.text.o_b, m.x, D, N, D, D, EPI_RESID_GATE_F32, st, E(8), es, tab + 8 * D));
-    else
-        TRY(dense(c, m.att, D, w.text.o_w, w.text.o_b, m.x, D, N, D, D, EPI_RESID_GATE_F32, st));
-    return LTX2_OK;
+    {
+        AttnParams a = attn_params(m.qkv, D, kk, 2 * D, vt, m.Spad, m.att, D, N, m.S, H, hd, scale_log2e(hd));
+        if (m.qfold) attn_set_rowscale(a, m.qss, D / 64, D, eps);          // q_norm as a per-row softmax scale from the projection's partial sums
+        if (m.has_kmask) a.kmask = m.kmask;
+        TRY(attend(a, glog(c, m), st));
+    }
+    GemmParams po = gemm_dense_params(m.att, D, w.text.o_w, w.text.o_b, m.x, D, N, D, D);
+    if (c->v2) gemm_set_gate(po, ada.E(8), es, tab + 8 * D);
+    return dense(c, po, EPI_RESID_GATE_F32, st);
 }
 
 // Feed-forward: AdaLN rows 3..5 (transformer.py:229-236,622-642); Linear -> GELU(tanh) -> Linear
@@ -725,15 +671,15 @@ int block_ffn(ltx2_dit* c, int k, int l, long es, hipStream_t st) {
     Mod& m = c->m[k];
     const BlockW& w = c->layers[l].m[k];
     const int N = m.N, D = m.D;
-    const float* const tab = m.use_comb ? m.comb + (long)l * (c->v2 ? 9 : 6) * D : w.sst;
-    const float* const emb0 = m.use_comb ? nullptr : m.emb;
-    auto E = [&](int r) { return emb0 ? emb0 + (long)r * D : nullptr; };
+    const AdaRows ada = ada_rows(c, m, w, l);
+    const float* const tab = ada.tab;
     const bool q3 = k == 0 && f8_route(c, w.ff1_w, N, 4 * D, D, EPI_GELU_BF16);
-    TRY(norm_mod_launch(m.x, D, q3 ? nullptr : m.h, D, N, D, c->cfg.norm_eps, 0, tab + 4 * D, tab + 3 * D, E(4), E(3), es, st,
+    TRY(norm_mod_launch(m.x, D, q3 ? nullptr : m.h, D, N, D, c->cfg.norm_eps, 0, tab + 4 * D, tab + 3 * D, ada.E(4), ada.E(3), es, st,
                         q3 ? m.a8 : nullptr, D, q3 ? m.a8s : nullptr));
-    TRY(dense(c, m.h, D, w.ff1_w, w.ff1_b, m.ff, 4 * D, N, 4 * D, D, EPI_GELU_BF16, st, nullptr, 0, nullptr, nullptr, nullptr, q3));
-    TRY(dense(c, m.ff, 4 * D, w.ff2_w, w.ff2_b, m.x, D, N, D, 4 * D, EPI_RESID_GATE_F32, st, E(5), es, tab + 5 * D));
-    return LTX2_OK;
+    TRY(dense(c, gemm_dense_params(m.h, D, w.ff1_w, w.ff1_b, m.ff, 4 * D, N, 4 * D, D), EPI_GELU_BF16, st, q3));
+    GemmParams p2 = gemm_dense_params(m.ff, 4 * D, w.ff2_w, w.ff2_b, m.x, D, N, D, 4 * D);
+    gemm_set_gate(p2, ada.E(5), es, tab + 5 * D);
+    return dense(c, p2, EPI_RESID_GATE_F32, st);
 }
 
 // Audio <-> video cross-modal attention (transformer.py:556-620).  Table rows
@@ -775,11 +721,10 @@ int block_cross_modal(ltx2_dit* c, int l, hipStream_t st, hipStream_t sa) {
     // A/B of the LTX-2.3 step, hipGraph: 104.0 ms against 106.0 with both projections in ONE launch on the main stream (128 + 256 tiles are two rounds
     // of the 256 CUs whichever way they are launched; on two streams the second round overlaps the a2v chain's small kernels)
     bool vt_done = false;
-    const VtOut vo{v.vt, Da, v.Npad, hd};
     hipEvent_t video_norm = event_record(c, st);
     if (!video_norm) return LTX2_E_HIP;
     TRY(gate_logits(c, v, w.a2v, v.h, Dv, v.N, H, st));
-    TRY(dense(c, v.h, Dv, w.a2v.q_w, w.a2v.q_b, v_q, Da, v.N, Da, Dv, EPI_BF16, st));
+    TRY(dense(c, gemm_dense_params(v.h, Dv, w.a2v.q_w, w.a2v.q_b, v_q, Da, v.N, Da, Dv), EPI_BF16, st));
     {
         const float* wts[1] = {w.a2v.qn};
         TRY(qknorm_rope_launch(v_q, Da, v.N, Da, hd, 1, offs, wts, eps, v.ccos, v.csin, st));
@@ -792,30 +737,39 @@ int block_cross_modal(ltx2_dit* c, int l, hipStream_t st, hipStream_t sa) {
         const float* she[2] = {comb ? nullptr : a.cross_ss + Da, comb ? nullptr : a.cross_ss + 3 * Da};
         TRY(norm_mod2_launch(a.x, Da, a.h, a.h2, Da, a.N, Da, eps, sct, sht, sce, she, sa));       // a2v context side | v2a query side
     }
-    TRY(project_kv(c, a.h, a.N, Da, w.a2v, Da, H, hd, eps, a.ccos, a.csin, a_kv, a.vt, a.Npad, sa));
+    TRY(project_kv(c, gemm_dense_params(a.h, Da, w.a2v.kv_w, w.a2v.kv_b, a_kv, 2 * Da, a.N, 2 * Da, Da), a.vt, a.Npad, hd, w.a2v.kn, a.ccos, a.csin, sa));
     hipEvent_t audio_kv = event_record(c, sa);
     if (!audio_kv) return LTX2_E_HIP;
     TRY(gate_logits(c, a, w.v2a, a.h2, Da, a.N, H, sa));
-    TRY(dense(c, a.h2, Da, w.v2a.q_w, w.v2a.q_b, a_q, Da, a.N, Da, Da, EPI_BF16, sa));
+    TRY(dense(c, gemm_dense_params(a.h2, Da, w.v2a.q_w, w.v2a.q_b, a_q, Da, a.N, Da, Da), EPI_BF16, sa));
     {
         const float* wts[1] = {w.v2a.qn};
         TRY(qknorm_rope_launch(a_q, Da, a.N, Da, hd, 1, offs, wts, eps, a.ccos, a.csin, sa));
     }
     // ---- audio -> video attention (main): Q from video, K / V from audio ----
     TRY(event_wait(audio_kv, st));
-    TRY(attend(v_q, Da, a_kv, 2 * Da, a.vt, a.Npad, v.att, Da, v.N, a.N, H, hd, st, nullptr, 0.f, nullptr, glog(c, v)));
-    TRY(dense(c, v.att, Da, w.a2v.o_w, w.a2v.o_b, v.x, Dv, v.N, Dv, Da, EPI_RESID_GATE_F32, st, comb ? nullptr : v.cross_gate, 0, tv + 4 * Dv));
+    TRY(attend(attn_params(v_q, Da, a_kv, 2 * Da, a.vt, a.Npad, v.att, Da, v.N, a.N, H, hd, scale_log2e(hd)), glog(c, v), st));
+    {
+        GemmParams p = gemm_dense_params(v.att, Da, w.a2v.o_w, w.a2v.o_b, v.x, Dv, v.N, Dv, Da);
+        gemm_set_gate(p, comb ? nullptr : v.cross_gate, 0, tv + 4 * Dv);
+        TRY(dense(c, p, EPI_RESID_GATE_F32, st));
+    }
     // ---- video -> audio attention (side): Q from audio, K / V from video ----
     TRY(event_wait(video_norm, sa));
-    TRY(dense(c, v.h2, Dv, w.v2a.kv_w, w.v2a.kv_b, v_kv, 2 * Da, v.N, 2 * Da, Dv, EPI_BF16, sa, nullptr, 0, nullptr, &vo, &vt_done));
+    {
+        GemmParams p = gemm_dense_params(v.h2, Dv, w.v2a.kv_w, w.v2a.kv_b, v_kv, 2 * Da, v.N, 2 * Da, Dv);
+        gemm_set_vt(p, v.vt, Da, v.Npad, hd);
+        TRY(dense(c, p, EPI_BF16, sa, /*preq=*/false, &vt_done));
+    }
     {
         const float* wts[1] = {w.v2a.kn};
         TRY(qknorm_rope_launch(v_kv, 2 * Da, v.N, Da, hd, 1, offs, wts, eps, v.ccos, v.csin, sa));
     }
     if (!vt_done) TRY(vt_transpose_launch(v_kv + Da, 2 * Da, v.vt, v.N, v.Npad, H, sa, hd));
-    TRY(attend(a_q, Da, v_kv, 2 * Da, v.vt, v.Npad, a.att, Da, a.N, v.N, H, hd, sa, nullptr, 0.f, nullptr, glog(c, a)));     // few queries, long KV (side stream)
-    TRY(dense(c, a.att, Da, w.v2a.o_w, w.v2a.o_b, a.x, Da, a.N, Da, Da, EPI_RESID_GATE_F32, sa, comb ? nullptr : a.cross_gate, 0, ta + 4 * Da));
-    return LTX2_OK;
+    TRY(attend(attn_params(a_q, Da, v_kv, 2 * Da, v.vt, v.Npad, a.att, Da, a.N, v.N, H, hd, scale_log2e(hd)), glog(c, a), sa));     // few queries, long KV (side stream)
+    GemmParams po = gemm_dense_params(a.att, Da, w.v2a.o_w, w.v2a.o_b, a.x, Da, a.N, Da, Da);
+    gemm_set_gate(po, comb ? nullptr : a.cross_gate, 0, ta + 4 * Da);
+    return dense(c, po, EPI_RESID_GATE_F32, sa);
 }
 
 struct ModIn {
@@ -837,7 +791,7 @@ int forward(ltx2_dit* c, const ModIn* in, hipStream_t st, bool rewind_events = t
         LTX2_CHECK_ARG(in[k].n_ts == 1 || c->per_token, "dit_forward: workspace was not sized for per-token timesteps");
         // patchify_proj (model.py:242) -> fp32 residual stream
         TRY(cast_f32_bf16_launch(in[k].latent, m.lat, (long)m.N * m.Cin, st));
-        TRY(dense(c, m.lat, m.Cin, w.patch_w, w.patch_b, m.x, m.D, m.N, m.D, m.Cin, EPI_F32, st));
+        TRY(dense(c, gemm_dense_params(m.lat, m.Cin, w.patch_w, w.patch_b, m.x, m.D, m.N, m.D, m.Cin), EPI_F32, st));
         // AdaLN-single (model.py:113-140)
         TRY(adaln_chain(c, m, w.ada, in[k].ts, 1, in[k].n_ts, c->cfg.timestep_scale, m.emb, m.e_f, st));
         if (in[k].n_ts > 1) {
@@ -892,7 +846,7 @@ int forward(ltx2_dit* c, const ModIn* in, hipStream_t st, bool rewind_events = t
         Mod& m = c->m[k];
         const ModW& w = c->mw[k];
         TRY(norm_mod_launch(m.x, m.D, m.h, m.D, m.N, m.D, c->cfg.norm_eps, 1, w.sst_out + m.D, w.sst_out, m.e_f, m.e_f, ee[k], st));
-        TRY(dense(c, m.h, m.D, w.proj_w, w.proj_b, in[k].velocity, m.Cout, m.N, m.Cout, m.D, EPI_F32, st));
+        TRY(dense(c, gemm_dense_params(m.h, m.D, w.proj_w, w.proj_b, in[k].velocity, m.Cout, m.N, m.Cout, m.D), EPI_F32, st));
     }
     return LTX2_OK;
 }
@@ -944,8 +898,8 @@ int prepare_modality(ltx2_dit* c, int k, const float* context, int S, const floa
     TRY(cast_f32_bf16_launch(context, m.ctx_in, (long)S * Cctx, st));
     m.ctx = m.ctx_in;
     if (c->cfg.caption_channels > 0) {   // PixArtAlphaTextProjection (model.py:52-56)
-        TRY(dense(c, m.ctx_in, Cctx, w.cap1_w, w.cap1_b, m.c1, D, S, D, Cctx, EPI_GELU_BF16, st));
-        TRY(dense(c, m.c1, D, w.cap2_w, w.cap2_b, m.ctxp, D, S, D, D, EPI_BF16, st));
+        TRY(dense(c, gemm_dense_params(m.ctx_in, Cctx, w.cap1_w, w.cap1_b, m.c1, D, S, D, Cctx), EPI_GELU_BF16, st));
+        TRY(dense(c, gemm_dense_params(m.c1, D, w.cap2_w, w.cap2_b, m.ctxp, D, S, D, D), EPI_BF16, st));
         m.ctx = m.ctxp;
     }
     {   // every layer's scale_shift_table side by side: forward() adds the step's timestep embedding to all of them in one launch
@@ -970,9 +924,11 @@ int prepare_modality(ltx2_dit* c, int k, const float* context, int S, const floa
             hipLaunchKernelGGL(vec_mul_kernel, dim3((D + 255) / 256), dim3(256), 0, st, tw.kn, tw.qn, m.knq + (long)l * D, D);
         }
     if (!c->v2)
-        for (int l = 0; l < c->cfg.num_layers; ++l)
-            TRY(project_kv(c, m.ctx, S, D, c->layers[l].m[k].text, D, m.H, m.hd, c->cfg.norm_eps, nullptr, nullptr,
-                           m.kv2 + (long)l * S * 2 * D, m.vt2 + (long)l * D * m.Spad, m.Spad, st, m.qfold ? m.knq + (long)l * D : nullptr));
+        for (int l = 0; l < c->cfg.num_layers; ++l) {
+            const AttnW& tw = c->layers[l].m[k].text;
+            TRY(project_kv(c, gemm_dense_params(m.ctx, D, tw.kv_w, tw.kv_b, m.kv2 + (long)l * S * 2 * D, 2 * D, S, 2 * D, D), m.vt2 + (long)l * D * m.Spad,
+                           m.Spad, m.hd, m.qfold ? m.knq + (long)l * D : tw.kn, nullptr, nullptr, st));
+        }
     return LTX2_OK;
 }
 
@@ -1218,64 +1174,39 @@ int ltx2_dit_denoise_step_av(ltx2_dit* c, float* v_latent, float* a_latent, cons
     return denoise_step(c, in, io, sigma, sigma_next, (hipStream_t)stream);
 }
 
-int ltx2_dit_graph_capture(ltx2_dit* c, float* latent, const float* host_sigmas, int n_steps, void* stream) {
-    LTX2_CHECK_ARG(latent && host_sigmas && n_steps > 0 && n_steps < 64, "dit_graph_capture: bad argument");
-    TRY(check_ready(c, "dit_graph_capture", false));
-    hipStream_t st = (hipStream_t)stream;
-    TRY(begin_capture(c, host_sigmas, n_steps, st));
-    int rc = LTX2_OK;
-    for (int i = 0; i < n_steps && rc == LTX2_OK; ++i) {
-        ModIn in[1] = {{latent, c->sigmas_dev + i, 1, c->sigmas_dev + i, nullptr}};
-        const StepIo io[1] = {{latent, nullptr, nullptr, nullptr}};
-        rc = denoise_step(c, in, io, host_sigmas[i], host_sigmas[i + 1], st, i == 0);
-    }
-    return end_capture(c, rc, st);
-}
-
 // Conditioned loops (image-to-video: some tokens carry a denoise mask < 1): per step the timesteps are mask * sigma_i, formed on the device
 // inside the captured step, and the Euler update blends x0 with the clean latent as ltx2_dit_denoise_step does.
 namespace {
-int cond_modality(ltx2_dit* c, int k, const float* mask, long n_mask, const float* clean, long n_clean, const float* sigma_i, ModIn& in, StepIo& io, hipStream_t st) {
+struct Cond {       // one modality's conditioning of a captured loop; mask == nullptr: none (the uniform form)
+    const float* mask;
+    long n_mask;
+    const float* clean;
+    long n_clean;
+};
+
+int cond_modality(ltx2_dit* c, int k, const Cond& cd, const float* sigma_i, ModIn& in, StepIo& io, hipStream_t st) {
     Mod& m = c->m[k];
-    if (!mask) return LTX2_OK;           // this modality has no conditioning tokens: the uniform form
-    LTX2_CHECK_ARG(clean, "dit_graph_capture_cond: a denoise mask needs the clean latent");
+    if (!cd.mask) return LTX2_OK;
+    LTX2_CHECK_ARG(cd.clean, "dit_graph_capture_cond: a denoise mask needs the clean latent");
     // the replayed kernels read N mask elements and N * C clean-latent elements on every step: a buffer of another modality's length would be an
     // out-of-bounds device read, not an error
-    LTX2_CHECK_ARG(n_mask == m.N && n_clean == (long)m.N * m.Cout, "dit_graph_capture_cond: modality %d has %d tokens x %d channels, got a mask of %ld and a clean latent of %ld elements", k, m.N, m.Cout, n_mask, n_clean);
+    LTX2_CHECK_ARG(cd.n_mask == m.N && cd.n_clean == (long)m.N * m.Cout, "dit_graph_capture_cond: modality %d has %d tokens x %d channels, got a mask of %ld and a clean latent of %ld elements", k, m.N, m.Cout, cd.n_mask, cd.n_clean);
     if (!c->per_token || !m.ts_tok) {
         ltx2_set_error("dit_graph_capture_cond: the workspace was not bound for per-token timesteps");
         return LTX2_E_STATE;
     }
-    hipLaunchKernelGGL(mask_sigma_kernel, dim3((m.N + 255) / 256), dim3(256), 0, st, mask, sigma_i, m.ts_tok, m.N);
+    hipLaunchKernelGGL(mask_sigma_kernel, dim3((m.N + 255) / 256), dim3(256), 0, st, cd.mask, sigma_i, m.ts_tok, m.N);
     LTX2_CHECK_LAUNCH("mask_sigma_kernel");
     in.ts = m.ts_tok;
     in.n_ts = m.N;
-    io.mask = mask;
-    io.clean = clean;
+    io.mask = cd.mask;
+    io.clean = cd.clean;
     return LTX2_OK;
-}
-}  // namespace
-
-int ltx2_dit_graph_capture_cond(ltx2_dit* c, float* latent, const float* host_sigmas, int n_steps, const float* mask, int64_t n_mask, const float* clean,
-                                int64_t n_clean, void* stream) {
-    LTX2_CHECK_ARG(latent && host_sigmas && n_steps > 0 && n_steps < 64, "dit_graph_capture_cond: bad argument");
-    TRY(check_ready(c, "dit_graph_capture_cond", false));
-    hipStream_t st = (hipStream_t)stream;
-    TRY(begin_capture(c, host_sigmas, n_steps, st));
-    int rc = LTX2_OK;
-    for (int i = 0; i < n_steps && rc == LTX2_OK; ++i) {
-        ModIn in[1] = {{latent, c->sigmas_dev + i, 1, c->sigmas_dev + i, nullptr}};
-        StepIo io[1] = {{latent, nullptr, nullptr, nullptr}};
-        rc = cond_modality(c, 0, mask, n_mask, clean, n_clean, c->sigmas_dev + i, in[0], io[0], st);
-        if (rc == LTX2_OK) rc = denoise_step(c, in, io, host_sigmas[i], host_sigmas[i + 1], st, i == 0);
-    }
-    return end_capture(c, rc, st);
 }
 
 // Classifier-free guidance on the VideoOnly engine (keyframe interpolation's stage 1): two evaluations per step, the positive prompt through `c`
 // and the negative one through `neg` (a second context over the same weights), then ONE element-wise pass.  Everything goes onto the caller's
 // stream in order: each evaluation already fills the device, so a captured loop is a linear chain.
-namespace {
 int guided_ready(ltx2_dit* c, ltx2_dit* neg, int n_ts, const char* who) {
     LTX2_CHECK_ARG(c && neg, "%s: null context", who);
     LTX2_CHECK_ARG(c != neg, "%s: the negative prompt needs a context of its own (ctx == neg)", who);
@@ -1287,26 +1218,68 @@ int guided_ready(ltx2_dit* c, ltx2_dit* neg, int n_ts, const char* who) {
     return LTX2_OK;
 }
 
-int guided_step(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* ts, int n_ts, const float* sigma_dev, const float* mask,
-                const float* clean, float cfg_scale, float sigma, float sigma_next, hipStream_t st) {
+// in: (latent, timesteps, sigma) of the step, read by both contexts; io: the latent it updates and its conditioning
+int guided_step(ltx2_dit* c, ltx2_dit* neg, const ModIn& in, const StepIo& io, float cfg_scale, float sigma, float sigma_next, hipStream_t st) {
     LTX2_CHECK_ARG(sigma != 0.f, "Sigma can't be 0.0");
-    LTX2_CHECK_ARG((mask == nullptr) == (clean == nullptr), "dit_guided_step: mask and clean go together");
+    LTX2_CHECK_ARG((io.mask == nullptr) == (io.clean == nullptr), "dit_guided_step: mask and clean go together");
     const Mod& m = c->m[0];
-    const ModIn pos[1] = {{latent, ts, n_ts, sigma_dev, m.vel}};
-    const ModIn ngt[1] = {{latent, ts, n_ts, sigma_dev, neg->m[0].vel}};
+    const ModIn pos[1] = {{in.latent, in.ts, in.n_ts, in.sigma, m.vel}};
+    const ModIn ngt[1] = {{in.latent, in.ts, in.n_ts, in.sigma, neg->m[0].vel}};
     TRY(forward(c, pos, st));
     TRY(forward(neg, ngt, st));
-    return guided_euler_step_launch(latent, m.vel, neg->m[0].vel, ts, n_ts == 1 ? 0 : 1, mask, clean, cfg_scale, sigma, sigma_next, latent,
+    return guided_euler_step_launch(in.latent, m.vel, neg->m[0].vel, in.ts, in.n_ts == 1 ? 0 : 1, io.mask, io.clean, cfg_scale, sigma, sigma_next, io.latent,
                                     m.N, m.Cout, st);
 }
+
+// The one captured sampling loop behind every ltx2_dit_graph_capture* entry: per step, sigma_i read on the device, each modality's timesteps (sigma_i, or
+// mask * sigma_i where it is conditioned), then a denoise step -- or, with a negative context, a guided step (VideoOnly: latent[0] / cond[0] only).
+// The event pool is rewound on step 0 only, so no event is re-recorded inside the capture; a guided step forms ts = mask * sigma_i in c's buffer and
+// both contexts read it.
+int capture_loop(ltx2_dit* c, ltx2_dit* neg, float cfg_scale, float* const latent[2], const Cond cond[2], const float* host_sigmas, int n_steps, hipStream_t st) {
+    const int nm = c->av ? 2 : 1;
+    TRY(begin_capture(c, host_sigmas, n_steps, st));
+    int rc = LTX2_OK;
+    for (int i = 0; i < n_steps && rc == LTX2_OK; ++i) {
+        const float* s = c->sigmas_dev + i;
+        ModIn in[2];
+        StepIo io[2];
+        for (int k = 0; k < nm && rc == LTX2_OK; ++k) {
+            in[k] = {latent[k], s, 1, s, nullptr};
+            io[k] = {latent[k], nullptr, nullptr, nullptr};
+            rc = cond_modality(c, k, cond[k], s, in[k], io[k], st);
+        }
+        if (rc != LTX2_OK) break;
+        rc = neg ? guided_step(c, neg, in[0], io[0], cfg_scale, host_sigmas[i], host_sigmas[i + 1], st)
+                 : denoise_step(c, in, io, host_sigmas[i], host_sigmas[i + 1], st, i == 0);
+    }
+    return end_capture(c, rc, st);
+}
 }  // namespace
+
+int ltx2_dit_graph_capture(ltx2_dit* c, float* latent, const float* host_sigmas, int n_steps, void* stream) {
+    LTX2_CHECK_ARG(latent && host_sigmas && n_steps > 0 && n_steps < 64, "dit_graph_capture: bad argument");
+    TRY(check_ready(c, "dit_graph_capture", false));
+    float* const lat[2] = {latent, nullptr};
+    const Cond none[2] = {};
+    return capture_loop(c, nullptr, 0.f, lat, none, host_sigmas, n_steps, (hipStream_t)stream);
+}
+
+int ltx2_dit_graph_capture_cond(ltx2_dit* c, float* latent, const float* host_sigmas, int n_steps, const float* mask, int64_t n_mask, const float* clean,
+                                int64_t n_clean, void* stream) {
+    LTX2_CHECK_ARG(latent && host_sigmas && n_steps > 0 && n_steps < 64, "dit_graph_capture_cond: bad argument");
+    TRY(check_ready(c, "dit_graph_capture_cond", false));
+    float* const lat[2] = {latent, nullptr};
+    const Cond cond[2] = {{mask, (long)n_mask, clean, (long)n_clean}, {}};
+    return capture_loop(c, nullptr, 0.f, lat, cond, host_sigmas, n_steps, (hipStream_t)stream);
+}
 
 int ltx2_dit_guided_step(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev,
                          const float* mask, const float* clean, float cfg_scale, float sigma, float sigma_next, void* stream) {
     LTX2_CHECK_ARG(latent && timesteps, "dit_guided_step: null argument");
     TRY(guided_ready(c, neg, n_timesteps, "dit_guided_step"));
-    return guided_step(c, neg, latent, timesteps, n_timesteps, sigma_dev ? sigma_dev : timesteps, mask, clean, cfg_scale, sigma, sigma_next,
-                       (hipStream_t)stream);
+    const ModIn in = {latent, timesteps, n_timesteps, sigma_dev ? sigma_dev : timesteps, nullptr};
+    const StepIo io = {latent, mask, clean, nullptr};
+    return guided_step(c, neg, in, io, cfg_scale, sigma, sigma_next, (hipStream_t)stream);
 }
 
 int ltx2_dit_graph_capture_guided(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* host_sigmas, int n_steps, const float* mask,
@@ -1314,52 +1287,27 @@ int ltx2_dit_graph_capture_guided(ltx2_dit* c, ltx2_dit* neg, float* latent, con
     LTX2_CHECK_ARG(latent && host_sigmas && n_steps > 0 && n_steps < 64, "dit_graph_capture_guided: bad argument");
     TRY(guided_ready(c, neg, mask ? c->m[0].N : 1, "dit_graph_capture_guided"));
     LTX2_CHECK_ARG((mask == nullptr) == (clean == nullptr), "dit_graph_capture_guided: mask and clean go together");
-    hipStream_t st = (hipStream_t)stream;
-    TRY(begin_capture(c, host_sigmas, n_steps, st));
-    int rc = LTX2_OK;
-    for (int i = 0; i < n_steps && rc == LTX2_OK; ++i) {
-        ModIn in[1] = {{latent, c->sigmas_dev + i, 1, c->sigmas_dev + i, nullptr}};
-        StepIo io[1] = {{latent, nullptr, nullptr, nullptr}};
-        rc = cond_modality(c, 0, mask, n_mask, clean, n_clean, c->sigmas_dev + i, in[0], io[0], st);      // ts = mask * sigma_i into c's buffer; both contexts read it
-        if (rc == LTX2_OK)
-            rc = guided_step(c, neg, latent, in[0].ts, in[0].n_ts, c->sigmas_dev + i, io[0].mask, io[0].clean, cfg_scale, host_sigmas[i],
-                             host_sigmas[i + 1], st);
-    }
-    return end_capture(c, rc, st);
+    float* const lat[2] = {latent, nullptr};
+    const Cond cond[2] = {{mask, (long)n_mask, clean, (long)n_clean}, {}};
+    return capture_loop(c, neg, cfg_scale, lat, cond, host_sigmas, n_steps, (hipStream_t)stream);
 }
 
 int ltx2_dit_graph_capture_cond_av(ltx2_dit* c, float* v_latent, float* a_latent, const float* host_sigmas, int n_steps, const float* v_mask, int64_t n_v_mask,
                                    const float* v_clean, int64_t n_v_clean, const float* a_mask, int64_t n_a_mask, const float* a_clean, int64_t n_a_clean, void* stream) {
     LTX2_CHECK_ARG(v_latent && a_latent && host_sigmas && n_steps > 0 && n_steps < 64, "dit_graph_capture_cond_av: bad argument");
     TRY(check_ready(c, "dit_graph_capture_cond_av", true));
-    hipStream_t st = (hipStream_t)stream;
-    TRY(begin_capture(c, host_sigmas, n_steps, st));
-    int rc = LTX2_OK;
-    for (int i = 0; i < n_steps && rc == LTX2_OK; ++i) {
-        const float* s = c->sigmas_dev + i;
-        ModIn in[2] = {{v_latent, s, 1, s, nullptr}, {a_latent, s, 1, s, nullptr}};
-        StepIo io[2] = {{v_latent, nullptr, nullptr, nullptr}, {a_latent, nullptr, nullptr, nullptr}};
-        rc = cond_modality(c, 0, v_mask, n_v_mask, v_clean, n_v_clean, s, in[0], io[0], st);
-        if (rc == LTX2_OK) rc = cond_modality(c, 1, a_mask, n_a_mask, a_clean, n_a_clean, s, in[1], io[1], st);
-        if (rc == LTX2_OK) rc = denoise_step(c, in, io, host_sigmas[i], host_sigmas[i + 1], st, i == 0);
-    }
-    return end_capture(c, rc, st);
+    float* const lat[2] = {v_latent, a_latent};
+    const Cond cond[2] = {{v_mask, (long)n_v_mask, v_clean, (long)n_v_clean}, {a_mask, (long)n_a_mask, a_clean, (long)n_a_clean}};
+    return capture_loop(c, nullptr, 0.f, lat, cond, host_sigmas, n_steps, (hipStream_t)stream);
 }
 
 int ltx2_dit_graph_capture_av(ltx2_dit* c, float* v_latent, float* a_latent, const float* host_sigmas, int n_steps,
                               void* stream) {
     LTX2_CHECK_ARG(v_latent && a_latent && host_sigmas && n_steps > 0 && n_steps < 64, "dit_graph_capture_av: bad argument");
     TRY(check_ready(c, "dit_graph_capture_av", true));
-    hipStream_t st = (hipStream_t)stream;
-    TRY(begin_capture(c, host_sigmas, n_steps, st));
-    int rc = LTX2_OK;
-    for (int i = 0; i < n_steps && rc == LTX2_OK; ++i) {
-        const float* s = c->sigmas_dev + i;
-        ModIn in[2] = {{v_latent, s, 1, s, nullptr}, {a_latent, s, 1, s, nullptr}};
-        const StepIo io[2] = {{v_latent, nullptr, nullptr, nullptr}, {a_latent, nullptr, nullptr, nullptr}};
-        rc = denoise_step(c, in, io, host_sigmas[i], host_sigmas[i + 1], st, i == 0);
-    }
-    return end_capture(c, rc, st);
+    float* const lat[2] = {v_latent, a_latent};
+    const Cond none[2] = {};
+    return capture_loop(c, nullptr, 0.f, lat, none, host_sigmas, n_steps, (hipStream_t)stream);
 }
 
 int ltx2_dit_profile_begin(ltx2_dit* c, int epilogue) {

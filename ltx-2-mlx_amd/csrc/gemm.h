@@ -98,6 +98,28 @@ inline void gemm_set_vt(GemmParams& p, void* vt, int col0, int npad, int hd) {
     p.vt_hd = hd;
     p.vt_head_stride = (long)hd * npad;
 }
+// EPI_RESID_GATE_F32: per-row part gate[m * gate_stride + n] and broadcast part gate_table[n] (either may be null)
+inline void gemm_set_gate(GemmParams& p, const float* gate, long gate_stride, const float* gate_table) {
+    p.gate = gate;
+    p.gate_stride = gate_stride;
+    p.gate_table = gate_table;
+}
+// a folded norm's producer half (EPI_RESID_GATE_F32): the new rows' 16-bit shadow and their partial sums of squares (ask gemm_fold_supported())
+inline void gemm_set_fold_producer(GemmParams& p, void* shadow, long ld_shadow, const float* shadow_scale, float* shadow_ss, long ld_ss) {
+    p.shadow = (bf16*)shadow;
+    p.ld_shadow = ld_shadow;
+    p.shadow_scale = shadow_scale;
+    p.shadow_ss = shadow_ss;
+    p.ld_ss = ld_ss;
+}
+// ... and its consumer half (EPI_BF16 / EPI_GELU_BF16): row factors from a producer's shadow_ss (rf_ld = its ld_ss)
+inline void gemm_set_fold_consumer(GemmParams& p, const float* rf_parts, long rf_ld, int rf_nparts, int rf_dim, float rf_eps) {
+    p.rf_parts = rf_parts;
+    p.rf_ld = rf_ld;
+    p.rf_nparts = rf_nparts;
+    p.rf_dim = rf_dim;
+    p.rf_eps = rf_eps;
+}
 
 int gemm_launch(const GemmParams& p, int epilogue, bool conv, hipStream_t stream);
 inline bool gemm_v4_prefer_224(const GemmParams& p) {

@@ -330,6 +330,10 @@ bool gemm_rowss_supported(const GemmParams& p, int epilogue) {
 }
 
 bool gemm_fold_supported(const GemmParams& p, int epilogue) {
+#ifdef LTX2_F16
+    (void)p; (void)epilogue;
+    return false;           // the un-normalised shadow is not safe in IEEE half: the fold belongs to the bfloat16 build
+#else
     if (p.W8 || p.A8 || !p.W) return false;
     const int r = gemm_route(p, epilogue, false);
     if (r != ROUTE_V4_224 && r != ROUTE_V4_256) return false;
@@ -337,6 +341,8 @@ bool gemm_fold_supported(const GemmParams& p, int epilogue) {
     if (p.shadow) {         // producer: the gated-residual epilogue with a row-invariant gate
         if (epilogue != EPI_RESID_GATE_F32 || (p.gate && p.gate_stride != 0) || !p.shadow_ss || p.ld_shadow % 4 != 0 || ((uintptr_t)p.shadow & 7)) return false;
         if (p.ld_ss % 4 != 0 || p.ld_ss < (long)((p.M + bm - 1) / bm) * bm || ((uintptr_t)p.shadow_ss & 15)) return false;
+        // the epilogue loads shadow_scale as f32x4; shadow rows narrower than N would overlap
+        if (((uintptr_t)p.shadow_scale & 15) || p.ld_shadow < p.N) return false;
     }
     if (p.rf_parts) {
         if (epilogue != EPI_BF16 && epilogue != EPI_GELU_BF16) return false;
@@ -344,6 +350,7 @@ bool gemm_fold_supported(const GemmParams& p, int epilogue) {
                            ((uintptr_t)p.rf_parts & 15) || (long)p.rf_nparts * p.rf_ld * 4 >= (1L << 31))) return false;
     }
     return true;
+#endif
 }
 
 int gemm_launch(const GemmParams& p, int epilogue, bool conv, hipStream_t stream) {

@@ -904,3 +904,36 @@ def test_norm_folded_around_the_gemms(dev, M, D, NO, must):
         og = KK.gemm_fold(y, wp, bp, nv.EPI_GELU_BF16, rf_parts=ss, rf_dim=D, eps=eps)
         eg = torch.nn.functional.gelu(exact.float(), approximate="tanh")
         assert rel_l2(og.float().cpu(), eg.cpu()) < 8e-3
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+def test_gemm_fold_refuses_a_misaligned_scale_and_overlapping_shadow_rows(dev, dtype):
+    """gemm_fold_supported(): the producer epilogue loads shadow_scale four floats at a time (16-byte aligned) and writes shadow rows of N elements at
+    stride ld_shadow (>= N, else rows overlap) -- ltx2_gemm_bf16_fold refuses both (*supported = 0, nothing launched, nothing written).  The fold belongs
+    to the bfloat16 build: the float16 build refuses every call."""
+    import ltx_2_mlx_amd.kernels as KK
+    from ltx_2_mlx_amd import _native as nv
+    M, D, PAD = 3456, 4096, 64
+    g = torch.Generator().manual_seed(607)
+    att = torch.randn(M, D, generator=g).to(dtype).to(dev)
+    wo = (torch.randn(D, D, generator=g) / math.sqrt(D)).to(dtype).to(dev)
+    bo = (0.1 * torch.randn(D, generator=g)).to(dev)
+    gate = (1.0 + 0.2 * torch.randn(D, generator=g)).to(dev)
+    sc = (0.3 * torch.randn(D + 4, generator=g)).to(dev)
+    xbuf = torch.randn(M * D + PAD, generator=g).to(dev)                    # `out` and a sentinel behind it
+    ybuf = torch.full((M * D + PAD,), 3.0, device=dev, dtype=dtype)          # the shadow and a sentinel behind it
+    x0, y0 = xbuf.clone(), ybuf.clone()
+    x = xbuf[:M * D].view(M, D)
+    assert sc.data_ptr() % 16 == 0 and sc[1:].data_ptr() % 16 == 4 and ybuf.data_ptr() % 16 == 0
+    refused = [dict(shadow=ybuf[:M * D].view(M, D), shadow_scale=sc[1:D + 1]),                                    # scale advanced by one float
+               dict(shadow=ybuf.as_strided((M, D), (D - 8, 1)), shadow_scale=sc[:D])]                              # ld_shadow = N - 8
+    for kw in refused:
+        assert KK.gemm_fold(att, wo, bo, nv.EPI_RESID_GATE_F32, out=x, gate_table=gate, **kw) is None
+        assert torch.equal(xbuf, x0) and torch.equal(ybuf, y0)
+    r = KK.gemm_fold(att, wo, bo, nv.EPI_RESID_GATE_F32, out=x, gate_table=gate, shadow=ybuf[:M * D].view(M, D), shadow_scale=sc[:D])
+    if dtype == torch.float16:
+        assert r is None and torch.equal(xbuf, x0) and torch.equal(ybuf, y0)
+        return
+    assert r is not None                                                    # the same call with aligned operands runs ...
+    assert torch.equal(xbuf[M * D:], x0[M * D:]) and torch.equal(ybuf[M * D:], y0[M * D:])      # ... inside its buffers
+    assert not torch.equal(xbuf, x0) and not torch.equal(ybuf, y0)
