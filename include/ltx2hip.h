@@ -298,6 +298,25 @@ int ltx2_guided_euler_step(const float* x, const float* vel_cond, const float* v
                            const float* mask, const float* clean, float cfg_scale, float sigma, float sigma_next,
                            float* out, int rows, int C, void* stream);
 
+/* The res_2s second-order exponential-integrator step (pipelines/ti2vid_hq.py:153-273) as two passes over [rows][C] fp32, every operation
+ * individually rounded (no FMA contraction), so each equals the separate fp32 array ops of the reference bit for bit.  The guided, blended
+ * x0 of a pair of velocities, in the HQ pipeline's own order (:315, not CFGGuider's):
+ *   t = ts[row * ts_stride];  a = x - t*vel_cond;  b = x - t*vel_uncond;  g = b + cfg_scale*(a - b)   (g = a when vel_uncond is NULL)
+ *   d = mask ? g*mask[row] + clean*(1 - mask[row]) : g
+ * ltx2_res2s_midpoint:  an = x;  e = d - an;  xm = an + c*e;  n_bong times { an = xm - c*e;  e = d - an };  x_mid = xm, anchor = an, eps1 = e.
+ *   c = fp32(h * a21), n_bong = 100 when h < 0.5 and sigma > 0.03 else 0 (the caller decides; any n_bong >= 0).  x_mid may equal x.
+ *   anchor == eps1 == NULL: the reference's final-step branch (h == 0 or sigma_next <= 0.001): x_mid = d and nothing else is written.
+ * ltx2_res2s_combine:   d2 as d from (x_mid, velocities, ts at the sub-sigma);  e2 = d2 - anchor;  out = anchor + h*(b1*eps1 + b2*e2).
+ *   out may equal any [rows][C] operand.
+ * ts_stride: 0 = one timestep, 1 = one per row.  mask [rows] and clean [rows][C] are both NULL or both set.  16-byte accesses when C % 4 == 0
+ * and every [rows][C] operand is 16-byte aligned, element-wise otherwise.  (additive entries of ABI version 3)                          */
+int ltx2_res2s_midpoint(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, int64_t ts_stride, const float* mask,
+                        const float* clean, float cfg_scale, float c, int n_bong, float* x_mid, float* anchor, float* eps1, int rows, int C,
+                        void* stream);
+int ltx2_res2s_combine(const float* x_mid, const float* vel_cond, const float* vel_uncond, const float* ts, int64_t ts_stride, const float* mask,
+                       const float* clean, float cfg_scale, const float* anchor, const float* eps1, float h, float b1, float b2, float* out,
+                       int rows, int C, void* stream);
+
 /* VAE elementwise glue (simple_decoder.py:492-498, 228-238/339-342, ops.py:109-125, :792-798)  */
 int ltx2_vae_prepare_latent(const float* latent, const float* std, const float* mean, const float* noise,
                             float noise_scale, void* out_bf16, int C, int64_t P, void* stream);
@@ -432,6 +451,23 @@ int ltx2_dit_guided_step(ltx2_dit* ctx, ltx2_dit* neg, float* latent, const floa
  * belongs to ctx: ltx2_dit_graph_launch(ctx) replays it.                                                                               */
 int ltx2_dit_graph_capture_guided(ltx2_dit* ctx, ltx2_dit* neg, float* latent, const float* host_sigmas, int n_steps,
                                   const float* mask, int64_t n_mask, const float* clean, int64_t n_clean, float cfg_scale, void* stream);
+/* One res_2s step on the VideoOnly engine (pipelines/ti2vid_hq.py:185-273), enqueued in order on the caller's stream: forward(ctx) and
+ * forward(neg) from `latent` at `timesteps`, ltx2_res2s_midpoint into workspaces owned by ctx, forward(ctx) and forward(neg) from x_mid at
+ * `ts_sub` (the timesteps of the sub-sigma sqrt(sigma * sigma_next)), ltx2_res2s_combine into `latent`.  neg may be NULL: no guidance, two
+ * evaluations.  h = -log(sigma_next / sigma) and (a21, b1, b2) are computed on the host in double exactly as components/res2s.py does;
+ * n_bong = 100 when h < 0.5 and sigma > 0.03.  When h == 0 or sigma_next <= 0.001 the step is the reference's final one: one pair of
+ * evaluations and latent = d (ts_sub is not read).  n_timesteps (1 or N) counts both `timesteps` and `ts_sub`; sigma_dev / sub_sigma_dev as
+ * sigma_dev in ltx2_dit_denoise_step (NULL: the first timestep).  The three [N][out_channels] fp32 workspaces are allocated on first use
+ * for the bound N and freed with ctx.  LTX2_E_INVALID as ltx2_dit_guided_step, and when sigma <= 0 or sigma_next < 0.
+ * (additive entries of ABI version 3)                                                                                                  */
+int ltx2_dit_res2s_step(ltx2_dit* ctx, ltx2_dit* neg, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev,
+                        const float* ts_sub, const float* sub_sigma_dev, const float* mask, const float* clean, float cfg_scale, float sigma,
+                        float sigma_next, void* stream);
+/* n_steps res_2s steps as one captured linear chain (it ends after a final step).  The sub-sigmas are uploaded beside the sigmas; with a mask
+ * the per-token timesteps mask * sigma_i are formed into ctx's buffer before the first pair of evaluations and mask * sub_sigma_i into the
+ * same buffer after the midpoint kernel.  The graph belongs to ctx: ltx2_dit_graph_launch(ctx) replays it.                              */
+int ltx2_dit_graph_capture_res2s(ltx2_dit* ctx, ltx2_dit* neg, float* latent, const float* host_sigmas, int n_steps, const float* mask,
+                                 int64_t n_mask, const float* clean, int64_t n_clean, float cfg_scale, void* stream);
 int ltx2_dit_graph_capture_av(ltx2_dit* ctx, float* v_latent, float* a_latent, const float* host_sigmas, int n_steps,
                               void* stream);
 int ltx2_dit_graph_launch(ltx2_dit* ctx, void* stream);

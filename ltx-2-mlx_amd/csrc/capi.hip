@@ -285,6 +285,20 @@ int ltx2_guided_euler_step(const float* x, const float* vel_cond, const float* v
                                     (hipStream_t)stream);
 }
 
+int ltx2_res2s_midpoint(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, int64_t ts_stride, const float* mask,
+                        const float* clean, float cfg_scale, float c, int n_bong, float* x_mid, float* anchor, float* eps1, int rows, int C,
+                        void* stream) {
+    return res2s_midpoint_launch(x, vel_cond, vel_uncond, ts, (long)ts_stride, mask, clean, cfg_scale, c, n_bong, x_mid, anchor, eps1, rows, C,
+                                 (hipStream_t)stream);
+}
+
+int ltx2_res2s_combine(const float* x_mid, const float* vel_cond, const float* vel_uncond, const float* ts, int64_t ts_stride, const float* mask,
+                       const float* clean, float cfg_scale, const float* anchor, const float* eps1, float h, float b1, float b2, float* out,
+                       int rows, int C, void* stream) {
+    return res2s_combine_launch(x_mid, vel_cond, vel_uncond, ts, (long)ts_stride, mask, clean, cfg_scale, anchor, eps1, h, b1, b2, out, rows, C,
+                                (hipStream_t)stream);
+}
+
 int ltx2_vae_prepare_latent(const float* latent, const float* std, const float* mean, const float* noise,
                             float noise_scale, void* out_bf16, int C, int64_t P, void* stream) {
     LTX2_CHECK_ARG(latent && std && mean && out_bf16, "vae_prepare_latent: null operand");

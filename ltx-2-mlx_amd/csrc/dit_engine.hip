@@ -15,6 +15,7 @@
 // Every GEMM and attention is enqueued the same way: build the parameter block from the operands (gemm_dense_params / attn_params), add what
 // the call needs through the named setters of gemm.h / attention.h, then hand it to dense() / attend().
 #include <math.h>
+#include <cmath>
 #include <string.h>
 
 #include <string>
@@ -110,7 +111,9 @@ struct ltx2_dit {
     char* ws = nullptr;
     long ws_bytes = 0;
     int per_token = 0;
-    float* sigmas_dev = nullptr;
+    float* sigmas_dev = nullptr;       // 64 sigmas of a captured loop, then 64 sub-sigmas (the res_2s loop)
+    float* r2s = nullptr;              // res_2s: x_mid | anchor | eps1, three [N][Cout] fp32 workspaces allocated on first use, freed with the context
+    long r2s_each = 0;                 //   elements of each
     // fp8-resident linear weights: the typed `const bf16*` fields of the weight structs then hold the CODES pointer; dense() looks it
     // up here to hand the GEMM (codes, per-row scale) instead of bf16 weights.  Per context (a second context over the same tensors
     // -- the video twin of an AudioVideo model -- keeps its own entries); rebuilt whenever the weights are resolved again.
@@ -147,7 +150,7 @@ long carve(ltx2_dit* c, char* base, int N, int S, int Na, int Sa, int per_token)
         off += align_up(bytes);
         return p;
     };
-    c->sigmas_dev = (float*)take(4L * 64);
+    c->sigmas_dev = (float*)take(4L * 128);
     for (int k = 0; k < (c->av ? 2 : 1); ++k) {
         Mod& m = c->m[k];
         const long n = k ? Na : N, s = k ? Sa : S;
@@ -932,10 +935,12 @@ int prepare_modality(ltx2_dit* c, int k, const float* context, int S, const floa
     return LTX2_OK;
 }
 
-int begin_capture(ltx2_dit* c, const float* host_sigmas, int n_steps, hipStream_t st) {
+// host_sub: n_steps sub-sigmas uploaded behind the 64 sigma slots (the res_2s loop), or nullptr
+int begin_capture(ltx2_dit* c, const float* host_sigmas, int n_steps, hipStream_t st, const float* host_sub = nullptr) {
     LTX2_CHECK_ARG(st != nullptr, "dit_graph_capture: needs a non-default stream");
     for (int i = 0; i < n_steps; ++i) LTX2_CHECK_ARG(host_sigmas[i] != 0.f, "Sigma can't be 0.0");
     if (hipMemcpyAsync(c->sigmas_dev, host_sigmas, 4L * (n_steps + 1), hipMemcpyHostToDevice, st) != hipSuccess ||
+        (host_sub && hipMemcpyAsync(c->sigmas_dev + 64, host_sub, 4L * n_steps, hipMemcpyHostToDevice, st) != hipSuccess) ||
         hipStreamSynchronize(st) != hipSuccess) {
         ltx2_set_error("dit_graph_capture: sigma upload failed");
         return LTX2_E_HIP;
@@ -1058,6 +1063,7 @@ void ltx2_dit_destroy(ltx2_dit* c) {
     if (!c) return;
     for (hipEvent_t e : c->sync_ev) (void)hipEventDestroy(e);
     if (c->side) (void)hipStreamDestroy(c->side);
+    if (c->r2s) (void)hipFree(c->r2s);
     if (c->exec) (void)hipGraphExecDestroy(c->exec);
     if (c->graph) (void)hipGraphDestroy(c->graph);
     for (hipEvent_t e : c->prof_ev) (void)hipEventDestroy(e);
@@ -1290,6 +1296,143 @@ int ltx2_dit_graph_capture_guided(ltx2_dit* c, ltx2_dit* neg, float* latent, con
     float* const lat[2] = {latent, nullptr};
     const Cond cond[2] = {{mask, (long)n_mask, clean, (long)n_clean}, {}};
     return capture_loop(c, neg, cfg_scale, lat, cond, host_sigmas, n_steps, (hipStream_t)stream);
+}
+
+// The res_2s second-order step (reference pipelines/ti2vid_hq.py:185-273; HQ pipeline stage 1): per step two pairs of evaluations, the second
+// from a midpoint latent at the geometric-mean sub-sigma, and two element-wise passes.  Linear on the caller's stream like the guided step.
+namespace {
+// phi_j(z) and the res_2s coefficients exactly as components/res2s.py computes them, in double
+double res2s_phi(int j, double z) {
+    double fact = 1;
+    for (int k = 2; k <= j; ++k) fact *= k;
+    if (std::fabs(z) < 1e-10) return 1.0 / fact;
+    double rem = 0, kf = 1;
+    for (int k = 0; k < j; ++k) {
+        if (k > 0) kf *= k;
+        rem += std::pow(z, k) / kf;
+    }
+    return (std::exp(z) - rem) / std::pow(z, j);
+}
+
+struct Res2sPlan {      // what one step does, decided on the host from (sigma, sigma_next)
+    bool last;          // the final-step branch: latent = d
+    float c, h, b1, b2, sub_sigma;
+    int n_bong;
+};
+
+int res2s_plan(float sigma_f, float sigma_next_f, Res2sPlan& p) {
+    LTX2_CHECK_ARG(sigma_f > 0.f && sigma_next_f >= 0.f, "dit_res2s_step: sigma=%g must be > 0 and sigma_next=%g >= 0", sigma_f, sigma_next_f);
+    const double sigma = sigma_f, sigma_next = sigma_next_f, c2 = 0.5;
+    const double h = sigma_next > 0 ? -std::log(sigma_next / sigma) : 0.0;
+    p = Res2sPlan{h == 0.0 || sigma_next <= 0.001, 0.f, 0.f, 0.f, 0.f, 0.f, 0};
+    if (p.last) return LTX2_OK;
+    const double a21 = c2 * res2s_phi(1, -h * c2), b2 = res2s_phi(2, -h) / c2, b1 = res2s_phi(1, -h) - b2;
+    p.c = (float)(h * a21);
+    p.h = (float)h;
+    p.b1 = (float)b1;
+    p.b2 = (float)b2;
+    p.sub_sigma = (float)std::sqrt(sigma * sigma_next);
+    p.n_bong = (h < 0.5 && sigma > 0.03) ? 100 : 0;
+    return LTX2_OK;
+}
+
+int res2s_ready(ltx2_dit* c, ltx2_dit* neg, int n_ts, const char* who) {
+    if (neg) return guided_ready(c, neg, n_ts, who);
+    LTX2_CHECK_ARG(c, "%s: null context", who);
+    LTX2_CHECK_ARG(!c->av, "%s: the res_2s step runs on VideoOnly contexts (the video twin of an AudioVideo model)", who);
+    LTX2_CHECK_ARG(c->prepared, "%s: ltx2_dit_prepare has not been called", who);
+    LTX2_CHECK_ARG(n_ts == 1 || c->per_token, "%s: a workspace was not bound for per-token timesteps", who);
+    return LTX2_OK;
+}
+
+// x_mid | anchor | eps1 for the bound N; never called while a stream is capturing
+int res2s_workspace(ltx2_dit* c) {
+    const long each = align_up((long)c->m[0].N * c->m[0].Cout, 64);
+    if (c->r2s && c->r2s_each == each) return LTX2_OK;
+    if (c->r2s) (void)hipFree(c->r2s);
+    c->r2s = nullptr;
+    c->r2s_each = 0;
+    if (hipMalloc((void**)&c->r2s, 4L * 3 * each) != hipSuccess) {
+        ltx2_set_error("dit_res2s_step: allocating %ld bytes of workspace failed", 4L * 3 * each);
+        return LTX2_E_HIP;
+    }
+    c->r2s_each = each;
+    return LTX2_OK;
+}
+
+// in: (latent, timesteps, sigma) of the step; ts_sub / sub_sigma: the same at the sub-sigma.  cond_sub: in a captured conditioned loop, the
+// mask from which ts_sub = mask * sub_sigma is formed into the buffer `in.ts` points at, after the midpoint kernel has read it (one stream, in order).
+int res2s_step(ltx2_dit* c, ltx2_dit* neg, const ModIn& in, const float* ts_sub, const float* sub_sigma, const Cond* cond_sub, const StepIo& io,
+               float cfg_scale, const Res2sPlan& p, hipStream_t st) {
+    LTX2_CHECK_ARG((io.mask == nullptr) == (io.clean == nullptr), "dit_res2s_step: mask and clean go together");
+    LTX2_CHECK_ARG(c->r2s && c->r2s_each >= (long)c->m[0].N * c->m[0].Cout, "dit_res2s_step: workspace missing");
+    const Mod& m = c->m[0];
+    float *x_mid = c->r2s, *anchor = c->r2s + c->r2s_each, *eps1 = c->r2s + 2 * c->r2s_each;
+    const float* vu = neg ? neg->m[0].vel : nullptr;
+    const long stride = in.n_ts == 1 ? 0 : 1;
+    auto evaluate = [&](const float* latent, const float* ts, const float* sg) -> int {
+        const ModIn pos[1] = {{latent, ts, in.n_ts, sg, m.vel}};
+        TRY(forward(c, pos, st));
+        if (neg) {
+            const ModIn ngt[1] = {{latent, ts, in.n_ts, sg, neg->m[0].vel}};
+            TRY(forward(neg, ngt, st));
+        }
+        return LTX2_OK;
+    };
+    TRY(evaluate(in.latent, in.ts, in.sigma));
+    if (p.last)
+        return res2s_midpoint_launch(in.latent, m.vel, vu, in.ts, stride, io.mask, io.clean, cfg_scale, 0.f, 0, io.latent, nullptr, nullptr, m.N, m.Cout, st);
+    TRY(res2s_midpoint_launch(in.latent, m.vel, vu, in.ts, stride, io.mask, io.clean, cfg_scale, p.c, p.n_bong, x_mid, anchor, eps1, m.N, m.Cout, st));
+    if (cond_sub && cond_sub->mask) {
+        hipLaunchKernelGGL(mask_sigma_kernel, dim3((m.N + 255) / 256), dim3(256), 0, st, cond_sub->mask, sub_sigma, m.ts_tok, m.N);
+        LTX2_CHECK_LAUNCH("mask_sigma_kernel");
+        ts_sub = m.ts_tok;
+    }
+    LTX2_CHECK_ARG(ts_sub && sub_sigma, "dit_res2s_step: the sub-sigma timesteps are missing");
+    TRY(evaluate(x_mid, ts_sub, sub_sigma));
+    return res2s_combine_launch(x_mid, m.vel, vu, ts_sub, stride, io.mask, io.clean, cfg_scale, anchor, eps1, p.h, p.b1, p.b2, io.latent, m.N, m.Cout, st);
+}
+}  // namespace
+
+int ltx2_dit_res2s_step(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev,
+                        const float* ts_sub, const float* sub_sigma_dev, const float* mask, const float* clean, float cfg_scale, float sigma,
+                        float sigma_next, void* stream) {
+    LTX2_CHECK_ARG(latent && timesteps, "dit_res2s_step: null argument");
+    TRY(res2s_ready(c, neg, n_timesteps, "dit_res2s_step"));
+    Res2sPlan p;
+    TRY(res2s_plan(sigma, sigma_next, p));
+    LTX2_CHECK_ARG(p.last || ts_sub, "dit_res2s_step: ts_sub is needed unless the step is the final one");
+    TRY(res2s_workspace(c));
+    const ModIn in = {latent, timesteps, n_timesteps, sigma_dev ? sigma_dev : timesteps, nullptr};
+    const StepIo io = {latent, mask, clean, nullptr};
+    return res2s_step(c, neg, in, ts_sub, sub_sigma_dev ? sub_sigma_dev : ts_sub, nullptr, io, cfg_scale, p, (hipStream_t)stream);
+}
+
+int ltx2_dit_graph_capture_res2s(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* host_sigmas, int n_steps, const float* mask,
+                                 int64_t n_mask, const float* clean, int64_t n_clean, float cfg_scale, void* stream) {
+    LTX2_CHECK_ARG(latent && host_sigmas && n_steps > 0 && n_steps < 64, "dit_graph_capture_res2s: bad argument");
+    TRY(res2s_ready(c, neg, mask ? c->m[0].N : 1, "dit_graph_capture_res2s"));
+    LTX2_CHECK_ARG((mask == nullptr) == (clean == nullptr), "dit_graph_capture_res2s: mask and clean go together");
+    Res2sPlan plan[64];
+    float sub[64];
+    for (int i = 0; i < n_steps; ++i) {
+        TRY(res2s_plan(host_sigmas[i], host_sigmas[i + 1], plan[i]));
+        sub[i] = plan[i].sub_sigma;
+    }
+    TRY(res2s_workspace(c));
+    hipStream_t st = (hipStream_t)stream;
+    const Cond cond = {mask, (long)n_mask, clean, (long)n_clean};
+    TRY(begin_capture(c, host_sigmas, n_steps, st, sub));
+    int rc = LTX2_OK;
+    for (int i = 0; i < n_steps && rc == LTX2_OK; ++i) {
+        const float *s = c->sigmas_dev + i, *ss = c->sigmas_dev + 64 + i;
+        ModIn in = {latent, s, 1, s, nullptr};
+        StepIo io = {latent, nullptr, nullptr, nullptr};
+        rc = cond_modality(c, 0, cond, s, in, io, st);          // ts = mask * sigma_i into c's buffer; both contexts read it
+        if (rc == LTX2_OK) rc = res2s_step(c, neg, in, ss, ss, &cond, io, cfg_scale, plan[i], st);
+        if (plan[i].last) break;                                // the reference's loop ends on its final step
+    }
+    return end_capture(c, rc, st);
 }
 
 int ltx2_dit_graph_capture_cond_av(ltx2_dit* c, float* v_latent, float* a_latent, const float* host_sigmas, int n_steps, const float* v_mask, int64_t n_v_mask,

@@ -76,6 +76,18 @@ int guided_euler_step_launch(const float* x, const float* vel_cond, const float*
                              const float* mask, const float* clean, float cfg_scale, float sigma, float sigma_next, float* out,
                              int rows, int C, hipStream_t stream);
 
+// The res_2s second-order step as two passes, every operation individually rounded; d(x, vc, vu) = the guided, mask-blended x0 in the HQ pipeline's
+// order: a = x - t*vc, b = x - t*vu, g = b + cfg*(a - b) (g = a when vu is NULL), d = mask ? g*m + clean*(1 - m) : g.
+// midpoint: an = x, e = d - an, xm = an + c*e, n_bong x {an = xm - c*e, e = d - an}; stores x_mid, anchor, eps1 (x_mid may be x).
+// anchor == eps1 == NULL: the final-step form, x_mid = d and nothing else.
+int res2s_midpoint_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride, const float* mask,
+                          const float* clean, float cfg_scale, float c, int n_bong, float* x_mid, float* anchor, float* eps1, int rows, int C,
+                          hipStream_t stream);
+// combine: e2 = d(x_mid, vc, vu) - anchor, out = anchor + h*(b1*eps1 + b2*e2); out may be any [rows][C] operand
+int res2s_combine_launch(const float* x_mid, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride, const float* mask,
+                         const float* clean, float cfg_scale, const float* anchor, const float* eps1, float h, float b1, float b2, float* out,
+                         int rows, int C, hipStream_t stream);
+
 // ---- spatial upscaler (channels-last bf16 [P][C]) ----
 // y = [silu]( GroupNorm_G(x over (C/G, all positions)) * gamma + beta + res );  scratch: 2*G*(1 + ceil(P/16)) floats
 int groupnorm_silu_launch(const bf16* x, const bf16* res, bf16* y, long P, int C, int G, float eps, const float* gamma,

@@ -1157,6 +1157,115 @@ __global__ void guided_euler_step_kernel(const float* x, const float* __restrict
     }
 }
 
+// The res_2s second-order step (reference pipelines/ti2vid_hq.py:153-273) as two passes over [rows][C], every operation rounded on its own
+// like the guided Euler step above.  The guided, mask-blended x0 of one pair of velocities, in the HQ pipeline's own order (:315):
+// a = x - t*vc, b = x - t*vu, g = b + cfg*(a - b) (g = a without vu), d = blend ? g*m + clean*(1 - m) : g.
+__device__ __forceinline__ float res2s_denoised(float x, float vc, float vu, bool guide, float t, float cfg, bool blend, float m, float one_minus_m,
+                                                float cl) {
+    float d = sub_rn(x, mul_rn(t, vc));
+    if (guide) {
+        const float b = sub_rn(x, mul_rn(t, vu));
+        d = add_rn(b, mul_rn(cfg, sub_rn(d, b)));
+    }
+    if (blend) d = add_rn(mul_rn(d, m), mul_rn(cl, one_minus_m));
+    return d;
+}
+
+// anchor = x, eps1 = d - anchor, x_mid = anchor + c*eps1, then the "bong" iteration (:232-238) n_bong times in registers:
+// anchor = x_mid - c*eps1, eps1 = d - anchor.  anchor == nullptr: the final-step form, x_mid = d and nothing else.
+__device__ __forceinline__ void res2s_midpoint_one(float x, float d, float c, int n_bong, float& xm, float& an, float& e) {
+    an = x;
+    e = sub_rn(d, an);
+    xm = add_rn(an, mul_rn(c, e));
+    for (int k = 0; k < n_bong; ++k) {
+        an = sub_rn(xm, mul_rn(c, e));
+        e = sub_rn(d, an);
+    }
+}
+
+// No __restrict__ on the [rows][C] operands: x_mid may be x.  A thread reads its own V elements of every operand before it stores any.
+template <int V>
+__global__ void res2s_midpoint_kernel(const float* x, const float* vc, const float* vu, const float* __restrict__ ts, long ts_stride,
+                                      const float* __restrict__ mask, const float* clean, float cfg, float c, int n_bong, float* x_mid,
+                                      float* anchor, float* eps1, long n, int C) {
+    const long nv = n / V;
+    const bool guide = vu != nullptr, blend = mask != nullptr, last = anchor == nullptr;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
+        const long e = i * V, row = e / C;
+        const float t = ts[row * ts_stride];
+        const float m = blend ? mask[row] : 1.f, om = sub_rn(1.0f, m);
+        alignas(16) float xs[V], cs[V], us[V], cl[V], xm[V], an[V], ep[V];
+        if constexpr (V == 4) {
+            *(float4*)xs = *(const float4*)(x + e);
+            *(float4*)cs = *(const float4*)(vc + e);
+            *(float4*)us = guide ? *(const float4*)(vu + e) : float4{0.f, 0.f, 0.f, 0.f};
+            *(float4*)cl = blend ? *(const float4*)(clean + e) : float4{0.f, 0.f, 0.f, 0.f};
+        } else {
+            xs[0] = x[e];
+            cs[0] = vc[e];
+            us[0] = guide ? vu[e] : 0.f;
+            cl[0] = blend ? clean[e] : 0.f;
+        }
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            const float d = res2s_denoised(xs[j], cs[j], us[j], guide, t, cfg, blend, m, om, cl[j]);
+            if (last) xm[j] = d;
+            else res2s_midpoint_one(xs[j], d, c, n_bong, xm[j], an[j], ep[j]);
+        }
+        if constexpr (V == 4) {
+            *(float4*)(x_mid + e) = *(const float4*)xm;
+            if (!last) {
+                *(float4*)(anchor + e) = *(const float4*)an;
+                *(float4*)(eps1 + e) = *(const float4*)ep;
+            }
+        } else {
+            x_mid[e] = xm[0];
+            if (!last) {
+                anchor[e] = an[0];
+                eps1[e] = ep[0];
+            }
+        }
+    }
+}
+
+// d2 from (x_mid, velocities at the sub-sigma) as above, e2 = d2 - anchor, out = anchor + h*(b1*eps1 + b2*e2).  out may be any [rows][C] operand.
+template <int V>
+__global__ void res2s_combine_kernel(const float* x_mid, const float* vc, const float* vu, const float* __restrict__ ts, long ts_stride,
+                                     const float* __restrict__ mask, const float* clean, float cfg, const float* anchor, const float* eps1,
+                                     float h, float b1, float b2, float* out, long n, int C) {
+    const long nv = n / V;
+    const bool guide = vu != nullptr, blend = mask != nullptr;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
+        const long e = i * V, row = e / C;
+        const float t = ts[row * ts_stride];
+        const float m = blend ? mask[row] : 1.f, om = sub_rn(1.0f, m);
+        alignas(16) float xs[V], cs[V], us[V], cl[V], an[V], ep[V], o[V];
+        if constexpr (V == 4) {
+            *(float4*)xs = *(const float4*)(x_mid + e);
+            *(float4*)cs = *(const float4*)(vc + e);
+            *(float4*)us = guide ? *(const float4*)(vu + e) : float4{0.f, 0.f, 0.f, 0.f};
+            *(float4*)cl = blend ? *(const float4*)(clean + e) : float4{0.f, 0.f, 0.f, 0.f};
+            *(float4*)an = *(const float4*)(anchor + e);
+            *(float4*)ep = *(const float4*)(eps1 + e);
+        } else {
+            xs[0] = x_mid[e];
+            cs[0] = vc[e];
+            us[0] = guide ? vu[e] : 0.f;
+            cl[0] = blend ? clean[e] : 0.f;
+            an[0] = anchor[e];
+            ep[0] = eps1[e];
+        }
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            const float d2 = res2s_denoised(xs[j], cs[j], us[j], guide, t, cfg, blend, m, om, cl[j]);
+            const float e2 = sub_rn(d2, an[j]);
+            o[j] = add_rn(an[j], mul_rn(h, add_rn(mul_rn(b1, ep[j]), mul_rn(b2, e2))));
+        }
+        if constexpr (V == 4) *(float4*)(out + e) = *(const float4*)o;
+        else out[e] = o[0];
+    }
+}
+
 inline int grid_for(long n, int block, int cap = 4096) {
     long g = (n + block - 1) / block;
     return (int)(g < 1 ? 1 : (g > cap ? cap : g));
@@ -1470,6 +1579,45 @@ int guided_euler_step_launch(const float* x, const float* vel_cond, const float*
         hipLaunchKernelGGL(guided_euler_step_kernel<1>, dim3(grid_for(n, 256)), dim3(256), 0, stream, x, vel_cond, vel_uncond, ts, ts_stride,
                            mask, clean, s1, inv, dt, out, n, C);
     LTX2_CHECK_LAUNCH("guided_euler_step_kernel");
+    return LTX2_OK;
+}
+
+int res2s_midpoint_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride, const float* mask,
+                          const float* clean, float cfg_scale, float c, int n_bong, float* x_mid, float* anchor, float* eps1, int rows, int C,
+                          hipStream_t stream) {
+    LTX2_CHECK_ARG(x && vel_cond && ts && x_mid && rows > 0 && C > 0, "res2s_midpoint: null operand or empty shape");
+    LTX2_CHECK_ARG(ts_stride == 0 || ts_stride == 1, "res2s_midpoint: ts_stride is 0 (one timestep) or 1 (one per row)");
+    LTX2_CHECK_ARG((mask == nullptr) == (clean == nullptr), "res2s_midpoint: mask and clean go together");
+    LTX2_CHECK_ARG((anchor == nullptr) == (eps1 == nullptr), "res2s_midpoint: anchor and eps1 go together (both NULL: the final-step form)");
+    LTX2_CHECK_ARG(n_bong >= 0, "res2s_midpoint: n_bong=%d", n_bong);
+    const long n = (long)rows * C;
+    // 16-byte accesses need every [rows][C] operand on a 16-byte boundary as well as C % 4 == 0 (a NULL operand contributes no bits)
+    const uintptr_t al = (uintptr_t)x | (uintptr_t)vel_cond | (uintptr_t)vel_uncond | (uintptr_t)clean | (uintptr_t)x_mid | (uintptr_t)anchor | (uintptr_t)eps1;
+    if (C % 4 == 0 && (al & 15) == 0)
+        hipLaunchKernelGGL(res2s_midpoint_kernel<4>, dim3(grid_for(n / 4, 256)), dim3(256), 0, stream, x, vel_cond, vel_uncond, ts, ts_stride, mask,
+                           clean, cfg_scale, c, n_bong, x_mid, anchor, eps1, n, C);
+    else
+        hipLaunchKernelGGL(res2s_midpoint_kernel<1>, dim3(grid_for(n, 256)), dim3(256), 0, stream, x, vel_cond, vel_uncond, ts, ts_stride, mask,
+                           clean, cfg_scale, c, n_bong, x_mid, anchor, eps1, n, C);
+    LTX2_CHECK_LAUNCH("res2s_midpoint_kernel");
+    return LTX2_OK;
+}
+
+int res2s_combine_launch(const float* x_mid, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride, const float* mask,
+                         const float* clean, float cfg_scale, const float* anchor, const float* eps1, float h, float b1, float b2, float* out,
+                         int rows, int C, hipStream_t stream) {
+    LTX2_CHECK_ARG(x_mid && vel_cond && ts && anchor && eps1 && out && rows > 0 && C > 0, "res2s_combine: null operand or empty shape");
+    LTX2_CHECK_ARG(ts_stride == 0 || ts_stride == 1, "res2s_combine: ts_stride is 0 (one timestep) or 1 (one per row)");
+    LTX2_CHECK_ARG((mask == nullptr) == (clean == nullptr), "res2s_combine: mask and clean go together");
+    const long n = (long)rows * C;
+    const uintptr_t al = (uintptr_t)x_mid | (uintptr_t)vel_cond | (uintptr_t)vel_uncond | (uintptr_t)clean | (uintptr_t)anchor | (uintptr_t)eps1 | (uintptr_t)out;
+    if (C % 4 == 0 && (al & 15) == 0)
+        hipLaunchKernelGGL(res2s_combine_kernel<4>, dim3(grid_for(n / 4, 256)), dim3(256), 0, stream, x_mid, vel_cond, vel_uncond, ts, ts_stride, mask,
+                           clean, cfg_scale, anchor, eps1, h, b1, b2, out, n, C);
+    else
+        hipLaunchKernelGGL(res2s_combine_kernel<1>, dim3(grid_for(n, 256)), dim3(256), 0, stream, x_mid, vel_cond, vel_uncond, ts, ts_stride, mask,
+                           clean, cfg_scale, anchor, eps1, h, b1, b2, out, n, C);
+    LTX2_CHECK_LAUNCH("res2s_combine_kernel");
     return LTX2_OK;
 }
 

@@ -527,6 +527,55 @@ def guided_euler_step(x: torch.Tensor, vel_cond: torch.Tensor, vel_uncond: torch
     return out
 
 
+def _res2s_operands(x, vel_cond, vel_uncond, timesteps, mask, clean, extra):
+    n, c = x.shape
+    timesteps = _c(timesteps.float())
+    if timesteps.numel() not in (1, n):
+        raise ValueError(f"timesteps has {timesteps.numel()} elements; expected 1 or N={n}")
+    for t in (x, vel_cond) + tuple(extra) + ((vel_uncond,) if vel_uncond is not None else ()) + ((mask, clean) if mask is not None else ()):
+        assert t is not None and t.dtype == torch.float32 and t.is_contiguous()
+    for t in (vel_cond, vel_uncond, clean) + tuple(extra):
+        assert t is None or t.shape == x.shape
+    assert mask is None or mask.numel() == n
+    return n, c, timesteps
+
+
+def res2s_midpoint(x: torch.Tensor, vel_cond: torch.Tensor, vel_uncond: Optional[torch.Tensor], timesteps: torch.Tensor, cfg_scale: float, c: float,
+                   n_bong: int, mask: Optional[torch.Tensor] = None, clean: Optional[torch.Tensor] = None, x_mid: Optional[torch.Tensor] = None,
+                   anchor: Optional[torch.Tensor] = None, eps1: Optional[torch.Tensor] = None, final: bool = False,
+                   dtype: Optional[torch.dtype] = None):
+    """First pass of a res_2s step over fp32 [N, C] (ltx2_res2s_midpoint): the guided, blended x0 `d` of the two velocities, then
+    anchor = x, eps1 = d - anchor, x_mid = anchor + c*eps1 and n_bong "bong" iterations, every operation individually rounded.
+    -> (x_mid, anchor, eps1); `x_mid` may be `x`.  final=True: the reference's final-step branch, x_mid = d -> (x_mid, None, None).
+    vel_uncond None: no guidance.  timesteps: 1 or N elements; `dtype` picks the library build (the kernel is fp32 in both)."""
+    if x_mid is None:
+        x_mid = torch.empty_like(x)
+    if not final:
+        anchor = torch.empty_like(x) if anchor is None else anchor
+        eps1 = torch.empty_like(x) if eps1 is None else eps1
+    else:
+        anchor = eps1 = None
+    n, ch, timesteps = _res2s_operands(x, vel_cond, vel_uncond, timesteps, mask, clean, (x_mid,) + (() if final else (anchor, eps1)))
+    nv.check(nv.lib(dtype).ltx2_res2s_midpoint(nv.ptr(x), nv.ptr(vel_cond), nv.ptr(vel_uncond), nv.ptr(timesteps), 0 if timesteps.numel() == 1 else 1,
+                                               nv.ptr(mask), nv.ptr(clean), float(cfg_scale), float(c), int(n_bong), nv.ptr(x_mid), nv.ptr(anchor),
+                                               nv.ptr(eps1), n, ch, nv.stream()))
+    return x_mid, anchor, eps1
+
+
+def res2s_combine(x_mid: torch.Tensor, vel_cond: torch.Tensor, vel_uncond: Optional[torch.Tensor], timesteps: torch.Tensor, cfg_scale: float,
+                  anchor: torch.Tensor, eps1: torch.Tensor, h: float, b1: float, b2: float, mask: Optional[torch.Tensor] = None,
+                  clean: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """Second pass of a res_2s step (ltx2_res2s_combine): d2 from (x_mid, velocities at the sub-sigma) as in res2s_midpoint,
+    e2 = d2 - anchor, out = anchor + h*(b1*eps1 + b2*e2), every operation individually rounded.  `out` may be any [N, C] operand."""
+    if out is None:
+        out = torch.empty_like(x_mid)
+    n, ch, timesteps = _res2s_operands(x_mid, vel_cond, vel_uncond, timesteps, mask, clean, (anchor, eps1, out))
+    nv.check(nv.lib(dtype).ltx2_res2s_combine(nv.ptr(x_mid), nv.ptr(vel_cond), nv.ptr(vel_uncond), nv.ptr(timesteps), 0 if timesteps.numel() == 1 else 1,
+                                              nv.ptr(mask), nv.ptr(clean), float(cfg_scale), nv.ptr(anchor), nv.ptr(eps1), float(h), float(b1), float(b2),
+                                              nv.ptr(out), n, ch, nv.stream()))
+    return out
+
+
 def pixnorm_mod_silu(x: torch.Tensor, table: torch.Tensor, te: Optional[torch.Tensor], shift_row: int, scale_row: int,
                      eps: float = 1e-6) -> torch.Tensor:
     assert x.dtype in ACT16

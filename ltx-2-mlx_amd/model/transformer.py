@@ -692,6 +692,76 @@ class LTXModel:
             raise RuntimeError("no guided graph captured")
         nv.check(owner._L.ltx2_dit_graph_launch(owner._h, nv.stream()))
 
+    # ------------------------------------------------------------------ res_2s second-order sampling (video-only engine)
+    def _res2s_pair(self, neg: Optional["LTXModel"]) -> Tuple["LTXModel", Optional["LTXModel"]]:
+        """(positive, negative or None) VideoOnly contexts of a res_2s step: an AudioVideo model is used through its video twin."""
+        if neg is None:
+            return (self._video_twin() if self.is_av else self), None
+        return self._guided_pair(neg)
+
+    def res2s_step_(self, neg: Optional["LTXModel"], latent: torch.Tensor, video: Modality, video_sub: Optional[Modality], sigma: float,
+                    sigma_next: float, cfg_scale: float, denoise_mask: Optional[torch.Tensor] = None,
+                    clean_latent: Optional[torch.Tensor] = None) -> None:
+        """In-place: latent (N, C) fp32 <- one res_2s step (reference pipelines/ti2vid_hq.py:185-273) by ONE C call (ltx2_dit_res2s_step):
+        forward(self) and forward(neg) at `video`'s timesteps, the midpoint kernel, both again from the midpoint latent at `video_sub`'s
+        timesteps (those of the sub-sigma sqrt(sigma * sigma_next)), the combine kernel.  neg None: no guidance.  video_sub may be None
+        only for the final step (sigma_next <= 0.001), which is one pair of evaluations and latent = d.  Both contexts are prepared by the
+        caller (neg with the negative context)."""
+        pos, ng = self._res2s_pair(neg)
+        ts, n_ts = pos._timesteps(video)
+        assert latent.dtype == torch.float32 and latent.is_contiguous() and latent.dim() == 2
+        pos._ensure_prepared(video, per_token=(n_ts != 1))
+        pos._apply_context_masks(video)
+        ts_sub = sg_sub = None
+        if video_sub is not None:
+            ts_sub, n_sub = pos._timesteps(video_sub)
+            assert n_sub == n_ts, "both evaluations take one timestep, or one per token"
+        adaln = pos.cross_attention_adaln
+        sg = pos._sigma_scalar(sigma) if adaln else None
+        if adaln and video_sub is not None:
+            sg_sub = pos._sigma(video_sub)
+        nv.check(pos._L.ltx2_dit_res2s_step(pos._h, None if ng is None else ng._h, nv.ptr(latent), nv.ptr(ts), n_ts, nv.ptr(sg), nv.ptr(ts_sub),
+                                            nv.ptr(sg_sub), nv.ptr(denoise_mask), nv.ptr(clean_latent), float(cfg_scale), float(sigma),
+                                            float(sigma_next), nv.stream()))
+
+    def capture_res2s_graph(self, neg: Optional["LTXModel"], latent: torch.Tensor, sigmas: Sequence[float], cfg_scale: float,
+                            denoise_mask: Optional[torch.Tensor] = None, clean_latent: Optional[torch.Tensor] = None) -> None:
+        """hipGraph-capture len(sigmas)-1 res_2s steps over `latent` (N, C fp32) as one linear chain (ltx2_dit_graph_capture_res2s).  Both
+        contexts are prepared first (per_token=True when a mask is given); the graph belongs to the positive VideoOnly context and
+        replay_res2s_graph() replays it.  The tensors must stay alive while it is replayed."""
+        pos, ng = self._res2s_pair(neg)
+        assert pos._prep_key is not None and (ng is None or ng._prep_key is not None), "call prepare() on both contexts first"
+        arr = (C.c_float * len(sigmas))(*[float(s) for s in sigmas])
+        st = torch.cuda.current_stream()
+        if st.cuda_stream == 0:
+            raise RuntimeError("graph capture needs a non-default stream: use `with torch.cuda.stream(torch.cuda.Stream()):`")
+        if denoise_mask is not None:
+            assert clean_latent is not None and denoise_mask.dtype == torch.float32 and clean_latent.dtype == torch.float32
+            assert denoise_mask.is_contiguous() and clean_latent.is_contiguous() and denoise_mask.dim() == 1
+        n_el = lambda t: 0 if t is None else t.numel()
+        pos._graph_refs = (latent, denoise_mask, clean_latent, ng)
+        nv.check(pos._L.ltx2_dit_graph_capture_res2s(pos._h, None if ng is None else ng._h, nv.ptr(latent), arr, len(sigmas) - 1, nv.ptr(denoise_mask),
+                                                     n_el(denoise_mask), nv.ptr(clean_latent), n_el(clean_latent), float(cfg_scale), st.cuda_stream))
+        self._res2s_graph_owner = pos
+
+    def replay_res2s_graph(self) -> None:
+        """Replay the graph captured by capture_res2s_graph (it belongs to the VideoOnly context that ran the capture)."""
+        owner = getattr(self, "_res2s_graph_owner", None)
+        if owner is None:
+            raise RuntimeError("no res_2s graph captured")
+        nv.check(owner._L.ltx2_dit_graph_launch(owner._h, nv.stream()))
+
+    def replace_weights(self, tensors: Dict[str, torch.Tensor]) -> None:
+        """Re-register engine-layout tensors (names of weight_tensors()) in place of the ones held now -- the HQ pipeline's LoRA fusion for
+        its second stage and the restore after it.  Contexts built over the old tensors (video twin, clone) are rebuilt on demand."""
+        for k, v in tensors.items():
+            if k not in self._w or self._w[k].shape != v.shape or self._w[k].dtype != v.dtype:
+                raise ValueError(f"{k}: not a registered weight of this shape and dtype")
+            self._register(k, v)
+        self._prep_key = None
+        self._twin = None
+        self._clone = None
+
     def replay_denoise_graph(self) -> None:
         nv.check(self._L.ltx2_dit_graph_launch(self._h, nv.stream()))
 

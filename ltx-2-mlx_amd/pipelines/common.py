@@ -1,6 +1,7 @@
 """Loop and conditioning helpers shared by the pipelines.  Mirrors reference LTX_2_MLX/pipelines/common.py:23-262."""
 from __future__ import annotations
 
+import math
 import os
 from dataclasses import dataclass
 from typing import List, Optional
@@ -232,6 +233,56 @@ def guided_denoise_loop(transformer, video_state: LatentState, sigmas, context: 
             st = video_state.replace(latent=lat[None])
             model.guided_step_(neg, lat, modality_from_state(st, context, sig[i], uniform=uniform), sig[i], sig[i + 1], guider.scale,
                                denoise_mask=mask, clean_latent=clean)
+            if callback:
+                callback(i + 1, n)
+    return video_state.replace(latent=lat[None].to(video_state.latent.dtype))
+
+
+def res2s_denoise_loop(transformer, video_state: LatentState, sigmas, context: torch.Tensor, negative_context: Optional[torch.Tensor],
+                       cfg_scale: float, audio_cfg_scale: float = 7.0, callback=None, use_hip_graph: bool = True) -> LatentState:
+    """The HQ pipeline's res_2s loop on the video-only model (reference pipelines/ti2vid_hq.py:153-273), without leaving the device: every
+    step is ONE C call -- two pairs of evaluations, the midpoint and the combine kernel (LTXModel.res2s_step_) -- and with no callback
+    and fewer than 64 steps the whole loop is one captured graph.
+    The reference's sigma handling is kept verbatim: the step count is len(sigmas) - 1, taken BEFORE a trailing 0.0 is replaced by
+    [0.0011, 0.0], so a scheduler table's last step lands on sigma = 0.0011 and the final-step branch (sigma_next <= 0.001 or h == 0:
+    latent = denoised, loop ends, no callback) is reached only by tables that end otherwise.  The negative evaluation runs under the
+    reference's condition, (cfg_scale > 1 or audio_cfg_scale > 1) and negative_context is not None.  The sigmas are rounded to fp32 (the
+    engine's scalar type, 0.0011 included) and the latent is held in fp32 across the loop, as guided_denoise_loop holds it; the
+    reference's per-step cast to the state dtype is not reproduced.  `transformer` is an X0Model; an AudioVideo model is used through its
+    video twin (the joint audio branch is not built).  Returns the video state."""
+    sig = [float(s) for s in sigmas]
+    n = len(sig) - 1
+    if sig[-1] == 0.0:
+        sig = sig[:-1] + [0.0011, 0.0]
+    sig = torch.tensor(sig[: n + 1], dtype=torch.float32).tolist()             # the n steps read sigma_0 .. sigma_n only
+    model = transformer.velocity_model
+    if model.is_av:
+        model = model._video_twin()
+    guide = (cfg_scale > 1.0 or audio_cfg_scale > 1.0) and negative_context is not None
+    neg = model.clone_sharing_weights() if guide else None
+    uniform = bool((video_state.denoise_mask == 1).all())
+    lat = video_state.latent[0].float().clone(memory_format=torch.contiguous_format)      # stepped in place: never the caller's tensor
+    mask = None if uniform else video_state.denoise_mask[0].reshape(-1).float().contiguous()
+    clean = None if uniform else video_state.clean_latent[0].float().contiguous()
+    model.prepare(context, video_state.positions, per_token=not uniform)
+    if guide:
+        neg.prepare(negative_context, video_state.positions, per_token=not uniform)
+    if use_hip_graph and callback is None and n < 64:
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            model.capture_res2s_graph(neg, lat, sig, cfg_scale, denoise_mask=mask, clean_latent=clean)
+            model.replay_res2s_graph()
+        torch.cuda.current_stream().wait_stream(side)
+    else:
+        for i in range(n):
+            final = sig[i + 1] <= 0.001 or sig[i + 1] == sig[i]
+            st = video_state.replace(latent=lat[None])
+            sub = None if final else modality_from_state(st, context, math.sqrt(sig[i] * sig[i + 1]), uniform=uniform)
+            model.res2s_step_(neg, lat, modality_from_state(st, context, sig[i], uniform=uniform), sub, sig[i], sig[i + 1], cfg_scale,
+                              denoise_mask=mask, clean_latent=clean)
+            if final:
+                break
             if callback:
                 callback(i + 1, n)
     return video_state.replace(latent=lat[None].to(video_state.latent.dtype))

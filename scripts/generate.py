@@ -581,7 +581,10 @@ _OUT_OF_PATH_DEFAULTS = dict(
 # reference :1276-1431), "ic-lora" conditions on control videos (:1434-1549).  "keyframe-interpolation" (:1552-1637) is built, but only WITH
 # keyframes: without them it is refused like the other two (the reference raises ValueError there)
 _PIPELINES_BUILT = ("text-to-video", "distilled", "one-stage")
-_PIPELINES_KNOWN = _PIPELINES_BUILT + ("two-stage", "ic-lora", "keyframe-interpolation")
+_PIPELINES_CLI = _PIPELINES_BUILT + ("two-stage", "ic-lora", "keyframe-interpolation")      # the reference parser's --pipeline choices, verbatim
+# "ti2vid-hq" is an addition: the reference has pipelines/ti2vid_hq.py (res_2s second-order sampler, 15 steps) but its own generate.py never
+# reaches it.  Here pipeline_type="ti2vid-hq" (--ti2vid-hq on the command line) runs TI2VidHQPipeline.
+_PIPELINES_KNOWN = _PIPELINES_CLI + ("ti2vid-hq",)
 
 
 def parse_keyframe(spec):
@@ -717,10 +720,11 @@ def generate_video(
     pipelines/a2vid_two_stage.py:338-357) and is written to `<stem>_audio_latent.npz`; the original audio, not a decode of the latent,
     is muxed into the mp4 when an ffmpeg binary exists."""
     kf_pipeline = pipeline_type == "keyframe-interpolation" and bool(keyframes)
+    hq_pipeline = pipeline_type == "ti2vid-hq"
     given = dict(early_layers_only=early_layers_only,
-                 enhance_prompt_flag=enhance_prompt_flag and use_gemma, cross_attn_scale=cross_attn_scale, distilled_lora=distilled_lora,
+                 enhance_prompt_flag=enhance_prompt_flag and use_gemma, cross_attn_scale=cross_attn_scale, distilled_lora=None if hq_pipeline else distilled_lora,
                  stg_scale=stg_scale, apg_scale=apg_scale, control_video=control_video, save_control=save_control, ge_gamma=ge_gamma,
-                 keyframes=None if kf_pipeline else keyframes, ic_lora_weights=ic_lora_weights)
+                 keyframes=None if (kf_pipeline or hq_pipeline) else keyframes, ic_lora_weights=ic_lora_weights)
     # Gemma encodes the prompt (and the negative prompt) when its weights are there and no pre-computed encoding is given
     gemma_encodes = bool(use_gemma and not (embedding_path or text_features_path) and gemma_path and os.path.exists(gemma_path))
     if negative_prompt is not None and not gemma_encodes:
@@ -730,7 +734,7 @@ def generate_video(
             raise NotImplementedError(f"{k}={v!r} is outside the MI355X hot path (see DESIGN.md); leave it at its default {_OUT_OF_PATH_DEFAULTS[k]!r}")
     if pipeline_type not in _PIPELINES_KNOWN:
         raise ValueError(f"unknown pipeline_type {pipeline_type!r}; the reference knows {_PIPELINES_KNOWN}")
-    if pipeline_type not in _PIPELINES_BUILT and not kf_pipeline:
+    if pipeline_type not in _PIPELINES_BUILT and not kf_pipeline and not hq_pipeline:
         raise NotImplementedError(f"pipeline_type={pipeline_type!r} is outside the MI355X hot path (see DESIGN.md): 'two-stage' is the dev "
                                   "model's CFG stage 1 + distilled-LoRA stage 2; for the distilled two-stage DistilledPipeline pass "
                                   "two_stage_distilled=True (--two-stage-distilled); 'keyframe-interpolation' is built and needs its "
@@ -750,6 +754,24 @@ def generate_video(
                 raise ValueError(f"keyframe frame_index {kf.frame_index} is outside [0, {num_frames})")
             if kf.image is None and not os.path.exists(kf.image_path):
                 raise FileNotFoundError(f"keyframe image not found: {kf.image_path}")
+    hq_lora = None
+    if hq_pipeline:                                                      # before any model is loaded
+        for k, v in dict(generate_audio=generate_audio, audio_path=audio_path, two_stage_distilled=two_stage_distilled,
+                         upscale_temporal=upscale_temporal, keyframes=keyframes).items():
+            if v:
+                raise NotImplementedError(f"{k} with pipeline_type='ti2vid-hq': TI2VidHQPipeline is video-only (the joint audio branch of the "
+                                          "res_2s loop is not built), conditions on image_path alone and ends with its own x2 spatial stage")
+        if not spatial_upscaler_weights:
+            raise ValueError("pipeline_type='ti2vid-hq' needs --spatial-upscaler-weights (its second stage runs at twice the resolution)")
+        from ltx_2_mlx_amd.pipelines import TI2VidHQConfig
+        TI2VidHQConfig(height=height, width=width, num_frames=num_frames)          # its ValueErrors (8k + 1 frames, multiples of 64)
+        if distilled_lora:
+            if fp8_resident:
+                raise NotImplementedError("LoRA fusion needs dequantised weights: drop fp8_resident")
+            if not os.path.exists(distilled_lora):
+                raise FileNotFoundError(f"distilled LoRA not found: {distilled_lora}")
+            from ltx_2_mlx_amd.loader.lora_loader import LoRAConfig
+            hq_lora = LoRAConfig(distilled_lora, distilled_lora_scale)
     output_dir = os.path.dirname(output_path)
     if output_dir:
         os.makedirs(output_dir, exist_ok=True)          # reference :1000-1003
@@ -806,8 +828,8 @@ def generate_video(
     if upscale_temporal and (_av_branch or two_stage_distilled):         # before any model is loaded
         raise NotImplementedError("upscale_temporal with the " + ("AudioVideo pipeline (the reference's AV branch returns before its upscalers)" if _av_branch
                                   else "two-stage DistilledPipeline (it returns before the post-denoise upscalers)"))
-    if kf_pipeline:
-        _need_cfg = False                   # guided by KeyframeInterpolationPipeline itself; a missing negative encoding becomes zeros there
+    if kf_pipeline or hq_pipeline:
+        _need_cfg = False                   # guided by the pipeline itself; a missing negative encoding becomes zeros
     if _need_cfg and not _av_branch:
         raise NotImplementedError(f"cfg_scale={cfg_scale}: classifier-free guidance is built in OneStagePipeline (the AudioVideo / LTX-2.3 branch); the "
                                   "standard video-only loop of this script runs the distilled model's cfg = 1")
@@ -842,7 +864,7 @@ def generate_video(
         text_encoding, _ = encode_with_gemma(prompt, gemma_path, weights_path if have_ckpt else None, use_early_layers_only=early_layers_only,
                                              device=device, seed=seed)
         print("  Encoded with Gemma 3")
-        if kf_pipeline and cfg_scale != 1.0:
+        if (kf_pipeline or hq_pipeline) and cfg_scale != 1.0:
             negative_encoding, _ = encode_with_gemma(negative_prompt or "", gemma_path, weights_path if have_ckpt else None, device=device, seed=seed)
             print("  Encoded the negative prompt with Gemma 3")
     elif embedding_path:
@@ -945,7 +967,7 @@ def generate_video(
         return frames
 
     images = []
-    if image_path and (two_stage_distilled or use_av_encoder):
+    if image_path and (two_stage_distilled or use_av_encoder or hq_pipeline):
         from ltx_2_mlx_amd.pipelines import ImageCondition
         print(f"  Image conditioning: {image_path} (strength={image_strength})")
         images = [ImageCondition(image_path=image_path, frame_index=0, strength=image_strength)]
@@ -978,6 +1000,32 @@ def generate_video(
         frames = _frames_from_video(pipe(text_encoding, None, parsed_keyframes, conf, negative_text_encoding=negative_encoding))
         torch.cuda.synchronize()
         print(f"  keyframe interpolation: {(time.time() - t0):.3f} s -> {tuple(frames.shape)}, DiT tokens per stage {pipe.token_counts}")
+        return finish(frames)
+
+    if hq_pipeline:
+        # === HQ TWO-STAGE PIPELINE (reference pipelines/ti2vid_hq.py; its own CLI never reaches it) ===
+        print("\n=== Using TI2Vid HQ Pipeline (res_2s) ===")
+        if model is None:
+            raise ValueError("TI2Vid HQ pipeline requires a loaded model")
+        if vae_decoder is None:
+            raise ValueError("TI2Vid HQ pipeline requires VAE decoder")
+        from ltx_2_mlx_amd.pipelines import TI2VidHQConfig, TI2VidHQPipeline
+        conf = TI2VidHQConfig(height=height, width=width, num_frames=num_frames, seed=seed, num_inference_steps=num_steps,
+                              cfg_scale=cfg_scale, audio_cfg_scale=audio_cfg_scale, distilled_lora_config=hq_lora, use_hip_graph=use_hip_graph,
+                              tiling_config=TilingConfig.default() if tiled_vae else None)
+        print("[3.5/5] VAE encoder")
+        if not have_ckpt:
+            print("  Warning: no checkpoint, the VAE encoder is random-initialised")
+        print("[3.6/5] spatial upscaler")
+        pipe = TI2VidHQPipeline(model, make_encoder(), vae_decoder, make_upscaler())
+        if (cfg_scale > 1.0 or audio_cfg_scale > 1.0) and negative_encoding is None:
+            print("  Negative prompt: no encoding given, using zeros of the context's shape (the reference's null text encoding)")
+            negative_encoding = torch.zeros_like(text_encoding)
+        print(f"[5/5] Running TI2Vid HQ ({num_steps} res_2s steps at {width // 2}x{height // 2}, then 3 at {width}x{height})...")
+        t0 = time.time()
+        frames = _frames_from_video(pipe(text_encoding, negative_encoding, conf, images=images))
+        torch.cuda.synchronize()
+        print(f"  ti2vid-hq: {(time.time() - t0):.3f} s -> {tuple(frames.shape)}")
         return finish(frames)
 
     if two_stage_distilled:
@@ -1192,7 +1240,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--control-strength", type=float, default=0.95)
     p.add_argument("--save-control", action="store_true")
     p.add_argument("--tiled-vae", action="store_true")
-    p.add_argument("--pipeline", type=str, choices=list(_PIPELINES_KNOWN), default="text-to-video")
+    p.add_argument("--pipeline", type=str, choices=list(_PIPELINES_CLI), default="text-to-video")
     p.add_argument("--keyframe", type=str, action="append", default=None)
     p.add_argument("--ic-lora-weights", type=str, default=None)
     p.add_argument("--early-layers-only", action="store_true")
@@ -1201,6 +1249,9 @@ def build_parser() -> argparse.ArgumentParser:
     # --- MI355X extras (no counterpart in the reference) ---
     p.add_argument("--text-features", type=str, default=None, help="npz with Gemma `features` [T,3840] (or `hidden_states` [L,T,3840]) + `attention_mask`: run the text connector on the GPU")
     p.add_argument("--no-hip-graph", action="store_true", help="run the step loop eagerly instead of replaying the captured hipGraph")
+    p.add_argument("--ti2vid-hq", action="store_true", help="TI2VidHQPipeline (pipeline_type='ti2vid-hq'): --steps res_2s second-order steps at half resolution with "
+                   "classifier-free guidance, x2 latent upscale (--spatial-upscaler-weights), 3 distilled steps, optionally under --distilled-lora.  An addition: "
+                   "the reference ships this pipeline but its own command line never reaches it, so --pipeline keeps the reference's choices")
     p.add_argument("--two-stage-distilled", action="store_true", help="DistilledPipeline: 8 steps at half resolution, x2 latent upscale (--spatial-upscaler-weights), 3 steps")
     p.add_argument("--fp8-resident", action="store_true", help="keep fp8 checkpoint weights as codes in HBM (bit-identical to dequantising at load)")
     p.add_argument("--fp8-compute", action="store_true", help="BASELINE config 3: the video stream's projections fp8 x fp8 on the CDNA4 fp8 MFMA (per-token / per-channel e4m3fn scales; "
@@ -1235,7 +1286,7 @@ def kwargs_from_args(a) -> dict:
         spatial_upscaler_weights=a.spatial_upscaler_weights, upscale_temporal=a.upscale_temporal,
         temporal_upscaler_weights=a.temporal_upscaler_weights, generate_audio=a.generate_audio, low_memory=a.low_memory, fast_mode=a.fast_mode,
         image_path=a.image, image_strength=a.image_strength, lora_path=a.lora, lora_strength=a.lora_strength, tiled_vae=a.tiled_vae,
-        pipeline_type=a.pipeline, early_layers_only=a.early_layers_only, enhance_prompt_flag=a.enhance_prompt, cross_attn_scale=a.cross_attn_scale,
+        pipeline_type="ti2vid-hq" if a.ti2vid_hq else a.pipeline, early_layers_only=a.early_layers_only, enhance_prompt_flag=a.enhance_prompt, cross_attn_scale=a.cross_attn_scale,
         steps_stage1=a.steps_stage1, steps_stage2=a.steps_stage2, cfg_stage1=a.cfg_stage1, stg_scale=a.stg_scale, stg_mode=a.stg_mode,
         apg_scale=a.apg_scale, apg_eta=a.apg_eta, apg_norm_threshold=a.apg_norm_threshold, apg_momentum=a.apg_momentum,
         control_video=a.control_video, control_type=a.control_type, canny_low=a.canny_low, canny_high=a.canny_high,
