@@ -619,6 +619,34 @@ int ltx2_audio_snake_aa(const float* x, int64_t ldx, int t, int c, const float* 
 int ltx2_audio_upsample(const float* x, int64_t ldx, int t_in, int c, const float* filter, int k, int ratio, int pad, int pad_left, float* y,
                         int64_t ldy, int t_out, void* stream);
 
+/* ---- control-video path of the IC-LoRA pipeline (pipelines/ic_lora.py).  Additive entries; integer arithmetic except frames_to_patches.
+ * Canny edges of F uint8 RGB frames: edges[f][y][x] = 255 on an edge, 0 elsewhere.  The definition is OpenCV's Canny with apertureSize 3 and
+ * L2gradient false, written out (no OpenCV binary was at hand to check it against: the gray weights and the tie rules are unverified):
+ *   gray = (R*9798 + G*19235 + B*3735 + 16384) >> 15;  gx, gy = the 3x3 Sobel operators on gray with a replicated border, in integers;
+ *   mag = |gx| + |gy|, 0 outside the image;  low, high are floored to integers and swapped if low > high.
+ *   A pixel with mag > low is kept if it passes non-maximum suppression along its quantised direction: x = |gx|, y = |gy| << 15,
+ *   t22 = x * 13573;  y < t22: horizontal, keep when mag > left && mag >= right;  else t67 = t22 + (x << 16);  y > t67: vertical, keep when
+ *   mag > up && mag >= down;  otherwise diagonal with s = -1 if (gx ^ gy) < 0 else +1, keep when mag > mag[y-1][x-s] && mag > mag[y+1][x+s].
+ *   A kept pixel with mag > high is strong (2), any other kept pixel weak (1).  Hysteresis: 255 for every strong pixel and for every weak
+ *   pixel 8-connected to a strong one through weak or strong pixels; frames are independent.
+ * ltx2_canny_hysteresis is the second stage alone on a given map of {0, 1, 2}.  It runs passes over LTX2_CANNY_TILE_H x LTX2_CANNY_TILE_W
+ * tiles (a fixpoint per tile in LDS; no block waits on another) and reads one int back per pass until a pass promotes nothing on a tile
+ * rim; more than H * W relaunches is LTX2_E_STATE.  Both calls therefore synchronise `stream` and cannot be captured into a graph.
+ * *passes (may be NULL) receives the number of passes.  workspace: device memory, 4-byte aligned, LTX2_CANNY_FLAG_BYTES for the hysteresis
+ * alone, LTX2_CANNY_FLAG_BYTES + F * H * W for ltx2_canny_u8 (the map).  map and edges must not alias. */
+#define LTX2_CANNY_TILE_H 32
+#define LTX2_CANNY_TILE_W 64
+#define LTX2_CANNY_FLAG_BYTES 16
+int ltx2_canny_u8(const uint8_t* rgb, int F, int H, int W, float low, float high, uint8_t* edges, void* workspace, int64_t workspace_bytes,
+                  int* passes, void* stream);
+int ltx2_canny_hysteresis(const uint8_t* map, int F, int H, int W, uint8_t* edges, void* workspace, int64_t workspace_bytes, int* passes,
+                          void* stream);
+/* uint8 frames [F][H][W][Cin] (Cin 3, or 1 replicated to three colours) -> the VAE encoder's patchified operand [F][H/4][W/4][64] in the
+ * build's 16-bit type: channel (c*4 + r_w)*4 + r_h = pixel (4 hq + r_h, 4 wq + r_w) of colour c as x / 127.5f - 1.0f (one IEEE divide and
+ * one subtract in fp32, rounded once), channels 48..63 zero: what patchify_video makes of the fp32 clip, in one pass.  H, W multiples of 4;
+ * frames 4-byte and out 16-byte aligned. */
+int ltx2_frames_to_patches(const uint8_t* frames, int F, int H, int W, int Cin, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

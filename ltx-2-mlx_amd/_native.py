@@ -29,6 +29,7 @@ GEMMA_ACT_SILU, GEMMA_ACT_GELU_TANH = 0, 1
 AUDIO_PRO_NONE, AUDIO_PRO_LEAKY_RELU, AUDIO_PRO_MAGNITUDE = 0, 1, 2
 AUDIO_ACT_NONE, AUDIO_ACT_TANH, AUDIO_ACT_CLIP, AUDIO_ACT_LOG, AUDIO_ACT_SILU = 0, 1, 2, 3, 4
 VAE_MAX_BLOCKS = 16
+CANNY_TILE_H, CANNY_TILE_W, CANNY_FLAG_BYTES = 32, 64, 16      # LTX2_CANNY_TILE_H / _W / LTX2_CANNY_FLAG_BYTES
 
 vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_float
 
@@ -146,6 +147,10 @@ SIGNATURES = {
     # audio VAE encoder (additive)
     "ltx2_audio_conv2d_strided": (i32, [vp, i64, i32, i32, i32, vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i64, i32, vp]),
     "ltx2_audio_latent_normalize": (i32, [vp, i64, vp, vp, vp, i32, i32, i32, vp]),
+    # control-video path of the IC-LoRA pipeline (additive)
+    "ltx2_canny_u8": (i32, [vp, i32, i32, i32, f32, f32, vp, vp, i64, C.POINTER(i32), vp]),
+    "ltx2_canny_hysteresis": (i32, [vp, i32, i32, i32, vp, vp, i64, C.POINTER(i32), vp]),
+    "ltx2_frames_to_patches": (i32, [vp, i32, i32, i32, i32, vp, vp]),
 }
 
 _libs: dict = {}

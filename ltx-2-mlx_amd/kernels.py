@@ -626,6 +626,67 @@ def video_to_uint8(video: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# ---------------------------------------------------------------------- control-video path (IC-LoRA): Canny edges, uint8 -> patchified operand
+CANNY_TILE = (nv.CANNY_TILE_H, nv.CANNY_TILE_W)          # the hysteresis kernel's tile (rows, columns): tests size their maps from it
+
+
+def _u8_frames(t: torch.Tensor, name: str, dims) -> torch.Tensor:
+    if t.dtype != torch.uint8 or t.dim() not in dims:
+        raise ValueError(f"{name}: expected a uint8 tensor of {' or '.join(str(d) for d in dims)} dimensions, got {t.dtype} {tuple(t.shape)}")
+    return _c(t)
+
+
+def _out_like(out: Optional[torch.Tensor], name: str, shape, dtype: torch.dtype, device) -> torch.Tensor:
+    """A caller's output buffer must be exactly what the kernel writes: the kernel trusts the shape it is given."""
+    if out is None:
+        return torch.empty(shape, device=device, dtype=dtype)
+    if out.device != device or out.dtype != dtype or tuple(out.shape) != tuple(shape) or not out.is_contiguous():
+        raise ValueError(f"{name}: out must be a contiguous {dtype} tensor of shape {tuple(shape)} on {device}, got {out.dtype} "
+                         f"{tuple(out.shape)} on {out.device}" + ("" if out.is_contiguous() else " (not contiguous)"))
+    return out
+
+
+def canny_hysteresis(cmap: torch.Tensor, out: Optional[torch.Tensor] = None, return_passes: bool = False):
+    """Second stage of Canny alone: map uint8 (F, H, W) of {0, 1 = weak, 2 = strong} -> edges uint8 (F, H, W), 255 on every strong pixel and
+    every weak pixel 8-connected to one.  Synchronises the stream (one flag read per pass); RuntimeError past H * W relaunches."""
+    cmap = _u8_frames(cmap, "canny_hysteresis", (3,))
+    F, H, W = cmap.shape
+    out = _out_like(out, "canny_hysteresis", cmap.shape, torch.uint8, cmap.device)
+    ws = torch.empty(nv.CANNY_FLAG_BYTES, device=cmap.device, dtype=torch.uint8)
+    n = nv.i32(0)
+    nv.check(nv.lib().ltx2_canny_hysteresis(nv.ptr(cmap), F, H, W, nv.ptr(out), nv.ptr(ws), ws.numel(), nv.C.byref(n), nv.stream()))
+    return (out, n.value) if return_passes else out
+
+
+def canny(frames: torch.Tensor, low: float = 100.0, high: float = 200.0, out: Optional[torch.Tensor] = None, return_passes: bool = False):
+    """uint8 RGB frames (F, H, W, 3) -> edges uint8 (F, H, W), 255 / 0: the Canny definition written out in include/ltx2hip.h (OpenCV's with
+    apertureSize 3, L2gradient false).  Synchronises the stream, as canny_hysteresis does."""
+    frames = _u8_frames(frames, "canny", (4,))
+    F, H, W, ch = frames.shape
+    if ch != 3:
+        raise ValueError(f"canny: expected RGB frames (F, H, W, 3), got {tuple(frames.shape)}")
+    out = _out_like(out, "canny", (F, H, W), torch.uint8, frames.device)
+    ws = torch.empty(nv.CANNY_FLAG_BYTES + F * H * W, device=frames.device, dtype=torch.uint8)
+    n = nv.i32(0)
+    nv.check(nv.lib().ltx2_canny_u8(nv.ptr(frames), F, H, W, float(low), float(high), nv.ptr(out), nv.ptr(ws), ws.numel(), nv.C.byref(n), nv.stream()))
+    return (out, n.value) if return_passes else out
+
+
+def frames_to_patches(frames: torch.Tensor, dtype: torch.dtype = BF16, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 frames (F, H, W, 3), (F, H, W, 1) or (F, H, W) -> the VAE encoder's patchified operand [F, H/4, W/4, 64] in `dtype`:
+    patchify_video(frames / 127.5 - 1) in one pass, bit for bit; a single channel is replicated to three."""
+    frames = _u8_frames(frames, "frames_to_patches", (3, 4))
+    F, H, W = frames.shape[:3]
+    cin = frames.shape[3] if frames.dim() == 4 else 1
+    if dtype not in ACT16:
+        raise ValueError(f"frames_to_patches: dtype {dtype} (bfloat16 or float16: the library builds)")
+    if H % 4 or W % 4:
+        raise ValueError(f"frames_to_patches: H {H} and W {W} must be multiples of 4")
+    out = _out_like(out, "frames_to_patches", (F, H // 4, W // 4, 64), dtype, frames.device)
+    nv.check(nv.lib(dtype).ltx2_frames_to_patches(nv.ptr(frames), F, H, W, cin, nv.ptr(out), nv.stream()))
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- Gemma-3 text encoder (gemma.hip)
 # Gemma always runs on the bfloat16 build (model/text_encoder/gemma3.py), whatever the DiT's compute dtype.
 

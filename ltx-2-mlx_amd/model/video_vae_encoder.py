@@ -126,7 +126,18 @@ class SimpleVideoEncoder:
             raise ValueError(f"Invalid number of frames: {f}. Encoder input must have 1 + 8*k frames (e.g., 1, 9, 17, 25, 33...).")
         if h % 32 or w % 32:
             raise ValueError(f"Resolution ({h}x{w}) must be divisible by 32")
-        x = patchify_video(video[0].to(self.device, torch.float32))
+        return self.encode_patches(patchify_video(video[0].to(self.device, torch.float32)))
+
+    def encode_patches(self, x: torch.Tensor) -> torch.Tensor:
+        """The encoder after patchify_video: channels-last bf16 [F, H/4, W/4, 64] (48 patchified channels + 16 zeros), F = 1 + 8k, H/4 and
+        W/4 multiples of 8 -> normalised latent (1, 128, 1 + k, H/32, W/32) fp32.  kernels.frames_to_patches builds this operand from uint8
+        frames in one pass (the control videos of pipelines/ic_lora.py)."""
+        if not self._loaded:
+            raise RuntimeError("SimpleVideoEncoder: weights not loaded")
+        if x.dim() != 4 or x.shape[3] != 64 or x.dtype != BF16 or not x.is_contiguous():
+            raise ValueError(f"expected contiguous bfloat16 patches [F, H/4, W/4, 64], got {x.dtype} {tuple(x.shape)}")
+        if (x.shape[0] - 1) % 8 != 0 or x.shape[1] % 8 or x.shape[2] % 8:
+            raise ValueError(f"patches {tuple(x.shape)}: 1 + 8*k frames and a resolution divisible by 32 (H/4, W/4 multiples of 8)")
         x = self._conv(x, "vae.encoder.conv_in.conv")
         for i, (kind, arg) in enumerate(self.blocks):
             p = f"vae.encoder.down_blocks.{i}"

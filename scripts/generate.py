@@ -578,8 +578,8 @@ _OUT_OF_PATH_DEFAULTS = dict(
     cross_attn_scale=1.0, distilled_lora=None, stg_scale=0.0, apg_scale=1.0, control_video=None, save_control=False,
     ge_gamma=0.0, keyframes=None, ic_lora_weights=None, negative_prompt=None)
 # pipelines whose algorithm is not built: "two-stage" is the dev model's CFG stage 1 + distilled-LoRA stage 2 (TwoStageCFGConfig,
-# reference :1276-1431), "ic-lora" conditions on control videos (:1434-1549).  "keyframe-interpolation" (:1552-1637) is built, but only WITH
-# keyframes: without them it is refused like the other two (the reference raises ValueError there)
+# reference :1276-1431).  "keyframe-interpolation" (:1552-1637) is built, but only WITH keyframes, and "ic-lora" (:1434-1549) only WITH a
+# control video and / or an image: without them they are refused like "two-stage" (the reference raises ValueError there)
 _PIPELINES_BUILT = ("text-to-video", "distilled", "one-stage")
 _PIPELINES_CLI = _PIPELINES_BUILT + ("two-stage", "ic-lora", "keyframe-interpolation")      # the reference parser's --pipeline choices, verbatim
 # "ti2vid-hq" is an addition: the reference has pipelines/ti2vid_hq.py (res_2s second-order sampler, 15 steps) but its own generate.py never
@@ -693,7 +693,15 @@ def generate_video(
     safetensors metadata) or generate_audio=True runs the AudioVideo transformer through OneStagePipeline (fps 25,
     LTX2Scheduler over num_steps); everything else the standard video-only loop on the distilled sigma table; the VAE decoder is
     built from the checkpoint's `config.vae` record; upscale_spatial doubles the denoised latent before decoding (2W x 2H output).
-    pipeline_type "two-stage" / "ic-lora" raise NotImplementedError, and so does "keyframe-interpolation" without keyframes.
+    pipeline_type "two-stage" raises NotImplementedError, and so do "keyframe-interpolation" without keyframes and "ic-lora" without a
+    control video or an image.
+    pipeline_type="ic-lora" with control_video and / or image_path runs ICLoraPipeline (reference :1434-1549): the control video (a .npy / .npz
+    array of uint8 frames, a directory of image frames, or a video file when an ffmpeg binary exists) is preprocessed on the device
+    (control_type "canny": Canny edges between canny_low and canny_high, written with save_control to `<control video's base name>_canny.mp4`
+    in output_path's directory; "raw": as it is), encoded and appended to the sequence at control_strength; stage 1 runs num_steps distilled steps at half resolution under
+    ic_lora_weights (a LoRA file fused for that stage only), then the x2 spatial upscale and 3 refinement steps on the base weights; the
+    image sits at frame 0 with image_strength.  spatial_upscaler_weights is required ("random" for a random-initialised one).  Not combined
+    with generate_audio, audio_path, two_stage_distilled, upscale_temporal or keyframes, nor ic_lora_weights with fp8_resident.
     pipeline_type="keyframe-interpolation" with keyframes (a list of 'path:frame_index[:strength]' strings, one per --keyframe) runs
     KeyframeInterpolationPipeline (reference :1552-1637): stage 1 at half resolution over num_steps with classifier-free guidance at cfg_scale
     (model_variant="distilled" forces 1), x2 spatial upscale, 3 refinement steps; the VAE encoder and the spatial upscaler are loaded
@@ -721,10 +729,12 @@ def generate_video(
     is muxed into the mp4 when an ffmpeg binary exists."""
     kf_pipeline = pipeline_type == "keyframe-interpolation" and bool(keyframes)
     hq_pipeline = pipeline_type == "ti2vid-hq"
+    ic_pipeline = pipeline_type == "ic-lora" and bool(control_video or image_path)
     given = dict(early_layers_only=early_layers_only,
                  enhance_prompt_flag=enhance_prompt_flag and use_gemma, cross_attn_scale=cross_attn_scale, distilled_lora=None if hq_pipeline else distilled_lora,
-                 stg_scale=stg_scale, apg_scale=apg_scale, control_video=control_video, save_control=save_control, ge_gamma=ge_gamma,
-                 keyframes=None if (kf_pipeline or hq_pipeline) else keyframes, ic_lora_weights=ic_lora_weights)
+                 stg_scale=stg_scale, apg_scale=apg_scale, control_video=None if ic_pipeline else control_video,
+                 save_control=False if ic_pipeline else save_control, ge_gamma=ge_gamma,
+                 keyframes=None if (kf_pipeline or hq_pipeline or ic_pipeline) else keyframes, ic_lora_weights=None if ic_pipeline else ic_lora_weights)
     # Gemma encodes the prompt (and the negative prompt) when its weights are there and no pre-computed encoding is given
     gemma_encodes = bool(use_gemma and not (embedding_path or text_features_path) and gemma_path and os.path.exists(gemma_path))
     if negative_prompt is not None and not gemma_encodes:
@@ -734,11 +744,12 @@ def generate_video(
             raise NotImplementedError(f"{k}={v!r} is outside the MI355X hot path (see DESIGN.md); leave it at its default {_OUT_OF_PATH_DEFAULTS[k]!r}")
     if pipeline_type not in _PIPELINES_KNOWN:
         raise ValueError(f"unknown pipeline_type {pipeline_type!r}; the reference knows {_PIPELINES_KNOWN}")
-    if pipeline_type not in _PIPELINES_BUILT and not kf_pipeline and not hq_pipeline:
+    if pipeline_type not in _PIPELINES_BUILT and not kf_pipeline and not hq_pipeline and not ic_pipeline:
         raise NotImplementedError(f"pipeline_type={pipeline_type!r} is outside the MI355X hot path (see DESIGN.md): 'two-stage' is the dev "
                                   "model's CFG stage 1 + distilled-LoRA stage 2; for the distilled two-stage DistilledPipeline pass "
                                   "two_stage_distilled=True (--two-stage-distilled); 'keyframe-interpolation' is built and needs its "
-                                  "images: pass keyframes / --keyframe path:frame_index[:strength]")
+                                  "images: pass keyframes / --keyframe path:frame_index[:strength]; 'ic-lora' is built and needs its control "
+                                  "video and / or an image: pass control_video / --control-video (--image)")
     parsed_keyframes = []
     if kf_pipeline:                                                      # before any model is loaded
         for k, v in dict(generate_audio=generate_audio, audio_path=audio_path, two_stage_distilled=two_stage_distilled,
@@ -772,6 +783,27 @@ def generate_video(
                 raise FileNotFoundError(f"distilled LoRA not found: {distilled_lora}")
             from ltx_2_mlx_amd.loader.lora_loader import LoRAConfig
             hq_lora = LoRAConfig(distilled_lora, distilled_lora_scale)
+    ic_loras = []
+    if ic_pipeline:                                                      # before any model is loaded
+        for k, v in dict(generate_audio=generate_audio, audio_path=audio_path, two_stage_distilled=two_stage_distilled,
+                         upscale_temporal=upscale_temporal, keyframes=keyframes).items():
+            if v:
+                raise NotImplementedError(f"{k} with pipeline_type='ic-lora': ICLoraPipeline is video-only, conditions on its control video and "
+                                          "image_path alone and ends with its own x2 spatial stage")
+        if not spatial_upscaler_weights:
+            raise ValueError("pipeline_type='ic-lora' needs --spatial-upscaler-weights (its second stage runs at twice the resolution)")
+        from ltx_2_mlx_amd.pipelines import ControlType, ICLoraConfig
+        ICLoraConfig(height=height, width=width, num_frames=num_frames)          # its ValueErrors (8k + 1 frames, multiples of 64)
+        ControlType(control_type)                                                # ValueError for anything but "canny" / "raw"
+        if control_video and not os.path.exists(control_video):
+            raise FileNotFoundError(f"control video not found: {control_video}")
+        if ic_lora_weights:
+            if fp8_resident:
+                raise NotImplementedError("LoRA fusion needs dequantised weights: drop fp8_resident")
+            if not os.path.exists(ic_lora_weights):
+                raise FileNotFoundError(f"IC-LoRA weights not found: {ic_lora_weights}")
+            from ltx_2_mlx_amd.loader.lora_loader import LoRAConfig
+            ic_loras = [LoRAConfig(ic_lora_weights, 1.0)]
     output_dir = os.path.dirname(output_path)
     if output_dir:
         os.makedirs(output_dir, exist_ok=True)          # reference :1000-1003
@@ -828,8 +860,8 @@ def generate_video(
     if upscale_temporal and (_av_branch or two_stage_distilled):         # before any model is loaded
         raise NotImplementedError("upscale_temporal with the " + ("AudioVideo pipeline (the reference's AV branch returns before its upscalers)" if _av_branch
                                   else "two-stage DistilledPipeline (it returns before the post-denoise upscalers)"))
-    if kf_pipeline or hq_pipeline:
-        _need_cfg = False                   # guided by the pipeline itself; a missing negative encoding becomes zeros
+    if kf_pipeline or hq_pipeline or ic_pipeline:
+        _need_cfg = False                   # guided by the pipeline itself (ic-lora: not at all); a missing negative encoding becomes zeros
     if _need_cfg and not _av_branch:
         raise NotImplementedError(f"cfg_scale={cfg_scale}: classifier-free guidance is built in OneStagePipeline (the AudioVideo / LTX-2.3 branch); the "
                                   "standard video-only loop of this script runs the distilled model's cfg = 1")
@@ -967,7 +999,7 @@ def generate_video(
         return frames
 
     images = []
-    if image_path and (two_stage_distilled or use_av_encoder or hq_pipeline):
+    if image_path and (two_stage_distilled or use_av_encoder or hq_pipeline or ic_pipeline):
         from ltx_2_mlx_amd.pipelines import ImageCondition
         print(f"  Image conditioning: {image_path} (strength={image_strength})")
         images = [ImageCondition(image_path=image_path, frame_index=0, strength=image_strength)]
@@ -1026,6 +1058,36 @@ def generate_video(
         frames = _frames_from_video(pipe(text_encoding, negative_encoding, conf, images=images))
         torch.cuda.synchronize()
         print(f"  ti2vid-hq: {(time.time() - t0):.3f} s -> {tuple(frames.shape)}")
+        return finish(frames)
+
+    if ic_pipeline:
+        # === IC-LORA PIPELINE (reference :1434-1549) ===
+        print("\n=== Using IC-LoRA Pipeline ===")
+        if model is None:
+            raise ValueError("IC-LoRA pipeline requires a loaded model")
+        if vae_decoder is None:
+            raise ValueError("IC-LoRA pipeline requires VAE decoder")
+        from ltx_2_mlx_amd.pipelines import ControlType, ICLoraConfig, ICLoraPipeline, VideoCondition
+        conf = ICLoraConfig(height=height, width=width, num_frames=num_frames, seed=seed, fps=24.0, stage_1_steps=num_steps,
+                            use_hip_graph=use_hip_graph, tiling_config=TilingConfig.default() if tiled_vae else None)
+        videos = []
+        if control_video:
+            print(f"  Control video: {control_video} (type={control_type}, strength={control_strength})")
+            videos = [VideoCondition(video_path=control_video, strength=control_strength, control_type=ControlType(control_type),
+                                     canny_low=canny_low, canny_high=canny_high, save_control=save_control)]
+        if not ic_loras:
+            print("  Warning: no --ic-lora-weights, stage 1 runs on the base weights")
+        print("[3.5/5] VAE encoder")
+        if not have_ckpt:
+            print("  Warning: no checkpoint, the VAE encoder is random-initialised")
+        print("[3.6/5] spatial upscaler")
+        pipe = ICLoraPipeline(model, make_encoder(), vae_decoder, make_upscaler(), lora_configs=ic_loras, save_video=save_video,
+                              save_dir=output_dir or ".")
+        print(f"[5/5] Running IC-LoRA ({num_steps} steps at {width // 2}x{height // 2}, then {conf.stage_2_steps} at {width}x{height})...")
+        t0 = time.time()
+        frames = _frames_from_video(pipe(text_encoding, None, conf, images=images, video_conditioning=videos))
+        torch.cuda.synchronize()
+        print(f"  ic-lora: {(time.time() - t0):.3f} s -> {tuple(frames.shape)}, DiT tokens per stage {pipe.token_counts}")
         return finish(frames)
 
     if two_stage_distilled:
