@@ -647,6 +647,23 @@ int ltx2_canny_hysteresis(const uint8_t* map, int F, int H, int W, uint8_t* edge
  * frames 4-byte and out 16-byte aligned. */
 int ltx2_frames_to_patches(const uint8_t* frames, int F, int H, int W, int Cin, void* out, void* stream);
 
+/* ---- source-clip glue of the retake pipeline (pipelines/retake.py).  Additive entries.
+ * encoded: the VAE encoder's latent, channel-major fp32 [C][F][H][W]; noise: token-major fp32 [F*H*W][C].  One pass writes
+ *   clean[p][c]  = encoded[c][p]                                   (VideoLatentPatchifier(patch_size = 1).patchify),
+ *   mask[p]      = 1.0f for the tokens of the latent frames [f0, f1), 0.0f elsewhere   (TemporalRegionMask),
+ *   latent[p][c] = noise[p][c] * sm + clean[p][c] * (1.0f - sm),  sm = mask[p] * noise_scale   (GaussianNoiser),
+ * each multiplication, the subtraction and the addition rounded on its own (no FMA), so the three outputs equal the separate fp32 torch
+ * statements bit for bit.  0 <= f0 <= f1 <= F; out of place: no output may overlap an input or another output. */
+int ltx2_retake_prepare(const float* encoded, const float* noise, int C, int F, int H, int W, int f0, int f1, float noise_scale, float* clean,
+                        float* mask, float* latent, void* stream);
+/* uint8 clips [T][H][W][3]: out = decoded on the pixel frames [p0, p1).  A frame t outside the window lies at distance d = p0 - t (before)
+ * or t - p1 + 1 (after); with R = ramp + 1 and a = max(R - d, 0) every byte of it is (decoded * a + source * (R - a) + R / 2) / R in
+ * integers: a linear fade over `ramp` frames OUTSIDE the window, the source's own bytes beyond it (ramp = 0: on every frame outside).
+ * 0 <= p0 <= p1 <= T, 0 <= ramp <= LTX2_RETAKE_MAX_RAMP; out may not overlap an input.  16 bytes per lane when all three clips are
+ * 16-byte aligned, one byte per lane otherwise and for the last T*H*W*3 % 16 bytes. */
+#define LTX2_RETAKE_MAX_RAMP 65535
+int ltx2_retake_composite(const uint8_t* decoded, const uint8_t* source, int T, int H, int W, int p0, int p1, int ramp, uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

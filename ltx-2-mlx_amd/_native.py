@@ -30,6 +30,7 @@ AUDIO_PRO_NONE, AUDIO_PRO_LEAKY_RELU, AUDIO_PRO_MAGNITUDE = 0, 1, 2
 AUDIO_ACT_NONE, AUDIO_ACT_TANH, AUDIO_ACT_CLIP, AUDIO_ACT_LOG, AUDIO_ACT_SILU = 0, 1, 2, 3, 4
 VAE_MAX_BLOCKS = 16
 CANNY_TILE_H, CANNY_TILE_W, CANNY_FLAG_BYTES = 32, 64, 16      # LTX2_CANNY_TILE_H / _W / LTX2_CANNY_FLAG_BYTES
+RETAKE_MAX_RAMP = 65535                                        # LTX2_RETAKE_MAX_RAMP
 
 vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_float
 
@@ -151,6 +152,9 @@ SIGNATURES = {
     "ltx2_canny_u8": (i32, [vp, i32, i32, i32, f32, f32, vp, vp, i64, C.POINTER(i32), vp]),
     "ltx2_canny_hysteresis": (i32, [vp, i32, i32, i32, vp, vp, i64, C.POINTER(i32), vp]),
     "ltx2_frames_to_patches": (i32, [vp, i32, i32, i32, i32, vp, vp]),
+    # source-clip glue of the retake pipeline (additive)
+    "ltx2_retake_prepare": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp]),
+    "ltx2_retake_composite": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
 }
 
 _libs: dict = {}

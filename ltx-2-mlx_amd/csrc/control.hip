@@ -1,6 +1,8 @@
 // Control-video path of the IC-LoRA pipeline (pipelines/ic_lora.py): Canny edges on uint8 frames and the uint8 -> patchified 16-bit
 // operand of the VAE encoder, with their ltx2_canny_* / ltx2_frames_to_patches C entry points (declared in include/ltx2hip.h).
 // Canny is integer arithmetic throughout (the definition is written out in the header); only frames_to_patches depends on LTX2_F16.
+// The source-clip glue of the retake pipeline (pipelines/retake.py) lives here too: ltx2_retake_prepare (the encoded clip -> clean tokens,
+// temporal mask and noised latent in one pass) and ltx2_retake_composite (the untouched frames put back, in integers).
 #include <math.h>
 
 #include "../../include/ltx2hip.h"
@@ -207,6 +209,122 @@ __global__ __launch_bounds__(256) void frames_to_patches_kernel(const unsigned c
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------
+// Retake: the encoder's channel-major latent [C][P] (P = F*HW positions) -> token-major clean [P][C], mask [P] (1 on the tokens of the
+// latent frames [f0, f1), 0 elsewhere) and latent = noise*sm + clean*(1 - sm) with sm = mask*noise_scale: the patchify, the
+// TemporalRegionMask and the GaussianNoiser of the torch path in one pass.  Every operation is rounded on its own (contract(off): hipcc
+// would fuse a*b + c into an FMA, which torch's separate statements are not), so the result is theirs bit for bit.
+// A block transposes a 32 x 32 tile through LDS as vae_prepare_latent_kernel does: reads run along positions, writes along channels.
+// ------------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ float add_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+__device__ __forceinline__ float sub_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a - b;
+}
+
+__global__ __launch_bounds__(256) void retake_prepare_kernel(const float* __restrict__ encoded, const float* __restrict__ noise, int C, long P,
+                                                             long tok0, long tok1, float noise_scale, float* __restrict__ clean,
+                                                             float* __restrict__ mask, float* __restrict__ latent) {
+    __shared__ float tile[32][33];
+    const long p0 = (long)blockIdx.x * 32;
+    const int c0 = blockIdx.y * 32;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;      // 256 threads: ty 0..7
+    for (int k = ty; k < 32; k += 8) {
+        const int c = c0 + k;
+        const long pp = p0 + tx;
+        tile[k][tx] = (c < C && pp < P) ? encoded[(long)c * P + pp] : 0.f;
+    }
+    __syncthreads();
+    if (blockIdx.y == 0 && ty == 0 && p0 + tx < P) mask[p0 + tx] = (p0 + tx >= tok0 && p0 + tx < tok1) ? 1.f : 0.f;
+    for (int k = ty; k < 32; k += 8) {
+        const long pp = p0 + k;
+        const int c = c0 + tx;
+        if (c < C && pp < P) {
+            const float m = (pp >= tok0 && pp < tok1) ? 1.f : 0.f;
+            const float sm = mul_rn(m, noise_scale), om = sub_rn(1.0f, sm);
+            const float v = tile[tx][k];
+            clean[pp * C + c] = v;
+            latent[pp * C + c] = add_rn(mul_rn(noise[pp * C + c], sm), mul_rn(v, om));
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Retake: out = decoded inside the pixel-frame window [p0, p1); a frame at distance d outside it (p0 - t before, t - p1 + 1 after) is
+// (decoded*a + source*(R - a) + R/2) / R with R = ramp + 1, a = max(R - d, 0), in integers: a == R is decoded, a == 0 the source's bytes.
+// The clip is walked as one run of bytes, 16 per lane; a vector that lies in one frame takes one weight (and loads only the clip it
+// needs when that weight is R or 0), one across a frame boundary a weight per byte, and the last total % 16 bytes go one byte per lane.
+// ------------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ unsigned composite_weight(long t, int p0, int p1, unsigned R) {
+    if (t >= p0 && t < p1) return R;
+    const long d = t < p0 ? p0 - t : t - p1 + 1;
+    return d >= (long)R ? 0u : R - (unsigned)d;
+}
+
+__device__ __forceinline__ unsigned composite_byte(unsigned d, unsigned s, unsigned a, unsigned R) { return (d * a + s * (R - a) + (R >> 1)) / R; }
+
+__device__ __forceinline__ unsigned composite_dword(unsigned d, unsigned s, unsigned a, unsigned R) {
+    unsigned o = 0;
+#pragma unroll
+    for (int k = 0; k < 32; k += 8) o |= composite_byte((d >> k) & 255u, (s >> k) & 255u, a, R) << k;
+    return o;
+}
+
+__global__ __launch_bounds__(256) void retake_composite_kernel(const unsigned char* __restrict__ decoded, const unsigned char* __restrict__ source,
+                                                               unsigned char* __restrict__ out, long frame_bytes, long nvec, long total, int p0,
+                                                               int p1, unsigned R) {
+    const long items = nvec + (total - nvec * 16);
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < items; i += (long)gridDim.x * blockDim.x) {
+        if (i >= nvec) {                                                  // the scalar tail
+            const long b = nvec * 16 + (i - nvec);
+            const unsigned a = composite_weight(b / frame_bytes, p0, p1, R);
+            out[b] = a == R ? decoded[b] : (a == 0 ? source[b] : (unsigned char)composite_byte(decoded[b], source[b], a, R));
+            continue;
+        }
+        const long b = i * 16;
+        const long t_first = b / frame_bytes;
+        uint4 o;
+        if (b - t_first * frame_bytes + 15 < frame_bytes) {               // the whole vector lies in frame t_first
+            const unsigned a = composite_weight(t_first, p0, p1, R);
+            if (a == R) {
+                o = *(const uint4*)(decoded + b);
+            } else if (a == 0) {
+                o = *(const uint4*)(source + b);
+            } else {
+                const uint4 d = *(const uint4*)(decoded + b), s = *(const uint4*)(source + b);
+                o.x = composite_dword(d.x, s.x, a, R);
+                o.y = composite_dword(d.y, s.y, a, R);
+                o.z = composite_dword(d.z, s.z, a, R);
+                o.w = composite_dword(d.w, s.w, a, R);
+            }
+        } else {                                                          // across a frame boundary: one weight per byte
+            const uint4 d = *(const uint4*)(decoded + b), s = *(const uint4*)(source + b);
+            const unsigned dd[4] = {d.x, d.y, d.z, d.w}, ss[4] = {s.x, s.y, s.z, s.w};
+            unsigned oo[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                const unsigned ak = composite_weight((b + k) / frame_bytes, p0, p1, R);
+                const int sh = (k & 3) * 8;
+                oo[k >> 2] |= composite_byte((dd[k >> 2] >> sh) & 255u, (ss[k >> 2] >> sh) & 255u, ak, R) << sh;
+            }
+            o = make_uint4(oo[0], oo[1], oo[2], oo[3]);
+        }
+        *(uint4*)(out + b) = o;
+    }
+}
+
+bool ranges_overlap(const void* a, int64_t na, const void* b, int64_t nb) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + (uintptr_t)nb && b0 < a0 + (uintptr_t)na;
+}
+
 bool canny_shape_ok(int F, int H, int W) { return F > 0 && H > 0 && W > 0 && F <= 65535 && (H + CN_TH - 1) / CN_TH <= 65535; }
 
 }  // namespace
@@ -284,6 +402,48 @@ int ltx2_frames_to_patches(const uint8_t* frames, int F, int H, int W, int Cin, 
     else
         hipLaunchKernelGGL(frames_to_patches_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, frames, (bf16*)out, H, W);
     LTX2_CHECK_LAUNCH("frames_to_patches_kernel");
+    return LTX2_OK;
+}
+
+int ltx2_retake_prepare(const float* encoded, const float* noise, int C, int F, int H, int W, int f0, int f1, float noise_scale, float* clean,
+                        float* mask, float* latent, void* stream) {
+    LTX2_CHECK_ARG(encoded && noise && clean && mask && latent, "retake_prepare: null operand");
+    LTX2_CHECK_ARG(C > 0 && F > 0 && H > 0 && W > 0 && (C + 31) / 32 <= 65535, "retake_prepare: C %d F %d H %d W %d", C, F, H, W);
+    LTX2_CHECK_ARG(0 <= f0 && f0 <= f1 && f1 <= F, "retake_prepare: latent-frame window [%d, %d) is not within 0 <= f0 <= f1 <= F = %d", f0, f1, F);
+    LTX2_CHECK_ARG(noise_scale == noise_scale && fabsf(noise_scale) <= 1e9f, "retake_prepare: noise_scale %f", noise_scale);
+    const int64_t hw = (int64_t)H * W, P = hw * F;
+    LTX2_CHECK_ARG((P + 31) / 32 <= 0x7fffffffLL, "retake_prepare: %ld positions", (long)P);
+    const int64_t nb = P * C * (int64_t)sizeof(float), mb = P * (int64_t)sizeof(float);
+    const void* ins[2] = {encoded, noise};
+    void* outs[3] = {clean, mask, latent};
+    const int64_t obytes[3] = {nb, mb, nb};
+    for (int o = 0; o < 3; ++o) {
+        for (int i = 0; i < 2; ++i)
+            LTX2_CHECK_ARG(!ranges_overlap(outs[o], obytes[o], ins[i], nb), "retake_prepare: an output overlaps an input (out of place only)");
+        for (int q = o + 1; q < 3; ++q)
+            LTX2_CHECK_ARG(!ranges_overlap(outs[o], obytes[o], outs[q], obytes[q]), "retake_prepare: two outputs overlap");
+    }
+    const dim3 grid((unsigned)((P + 31) / 32), (C + 31) / 32);
+    hipLaunchKernelGGL(retake_prepare_kernel, grid, dim3(256), 0, (hipStream_t)stream, encoded, noise, C, (long)P, (long)(f0 * hw), (long)(f1 * hw),
+                       noise_scale, clean, mask, latent);
+    LTX2_CHECK_LAUNCH("retake_prepare_kernel");
+    return LTX2_OK;
+}
+
+int ltx2_retake_composite(const uint8_t* decoded, const uint8_t* source, int T, int H, int W, int p0, int p1, int ramp, uint8_t* out, void* stream) {
+    LTX2_CHECK_ARG(decoded && source && out, "retake_composite: null operand");
+    LTX2_CHECK_ARG(T > 0 && H > 0 && W > 0, "retake_composite: T %d H %d W %d", T, H, W);
+    LTX2_CHECK_ARG(0 <= p0 && p0 <= p1 && p1 <= T, "retake_composite: pixel-frame window [%d, %d) is not within 0 <= p0 <= p1 <= T = %d", p0, p1, T);
+    LTX2_CHECK_ARG(ramp >= 0 && ramp <= LTX2_RETAKE_MAX_RAMP, "retake_composite: ramp %d (0 .. %d)", ramp, LTX2_RETAKE_MAX_RAMP);
+    const int64_t frame_bytes = (int64_t)H * W * 3, total = frame_bytes * T;
+    LTX2_CHECK_ARG(!ranges_overlap(out, total, decoded, total) && !ranges_overlap(out, total, source, total),
+                   "retake_composite: out overlaps an input (out of place only)");
+    const bool aligned = (((uintptr_t)decoded | (uintptr_t)source | (uintptr_t)out) & 15) == 0;
+    const int64_t nvec = aligned ? total / 16 : 0, items = nvec + (total - nvec * 16);
+    const int64_t blocks = (items + 255) / 256;
+    hipLaunchKernelGGL(retake_composite_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, (hipStream_t)stream, decoded, source,
+                       out, (long)frame_bytes, (long)nvec, (long)total, p0, p1, (unsigned)(ramp + 1));
+    LTX2_CHECK_LAUNCH("retake_composite_kernel");
     return LTX2_OK;
 }
 

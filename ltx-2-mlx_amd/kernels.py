@@ -687,6 +687,64 @@ def frames_to_patches(frames: torch.Tensor, dtype: torch.dtype = BF16, out: Opti
     return out
 
 
+# ---------------------------------------------------------------------- source-clip glue of the retake pipeline (control.hip)
+def _dense(t: torch.Tensor, name: str, what: str, dtype: torch.dtype, shape, device) -> torch.Tensor:
+    """An operand the kernel reads as it lies: exactly this dtype, shape and device, contiguous (no silent copy or cast)."""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or t.device != device or not t.is_contiguous():
+        got = f"{t.dtype} {tuple(t.shape)} on {t.device}" + ("" if t.is_contiguous() else " (not contiguous)") if isinstance(t, torch.Tensor) else repr(type(t))
+        raise ValueError(f"{name}: {what} must be a contiguous {dtype} tensor of shape {tuple(shape)} on {device}, got {got}")
+    return t
+
+
+def retake_prepare(encoded: torch.Tensor, noise: torch.Tensor, f0: int, f1: int, noise_scale: float = 1.0,
+                   out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None):
+    """The retake pipeline's state from the encoded source clip in one pass (ltx2_retake_prepare): encoded fp32 (1, C, F, H, W), noise fp32
+    (N, C) with N = F*H*W, the latent-frame window 0 <= f0 <= f1 <= F -> (clean (N, C), mask (N,), latent (N, C)), fp32:
+    clean = VideoLatentPatchifier(1).patchify(encoded), mask = 1 on the tokens of frames [f0, f1) (TemporalRegionMask), latent =
+    noise*sm + clean*(1 - sm) with sm = mask*noise_scale (GaussianNoiser), bit for bit what those torch statements give.
+    out: the three output tensors, exactly those shapes; nothing may overlap."""
+    if not isinstance(encoded, torch.Tensor) or encoded.dim() != 5 or encoded.shape[0] != 1 or not encoded.is_cuda:
+        raise ValueError(f"retake_prepare: encoded must be a GPU tensor (1, C, F, H, W), got "
+                         f"{tuple(encoded.shape)} on {encoded.device}" if isinstance(encoded, torch.Tensor) else "retake_prepare: encoded must be a tensor")
+    _, ch, F, H, W = encoded.shape
+    dev, n = encoded.device, F * H * W
+    _dense(encoded, "retake_prepare", "encoded", torch.float32, encoded.shape, dev)
+    _dense(noise, "retake_prepare", "noise", torch.float32, (n, ch), dev)
+    f0, f1 = int(f0), int(f1)
+    if not 0 <= f0 <= f1 <= F:
+        raise ValueError(f"retake_prepare: latent-frame window [{f0}, {f1}) is not within 0 <= f0 <= f1 <= F = {F}")
+    if out is not None and len(out) != 3:
+        raise ValueError("retake_prepare: out must be the three tensors (clean, mask, latent)")
+    oc, om, ol = out if out is not None else (None, None, None)
+    oc = _out_like(oc, "retake_prepare (clean)", (n, ch), torch.float32, dev)
+    om = _out_like(om, "retake_prepare (mask)", (n,), torch.float32, dev)
+    ol = _out_like(ol, "retake_prepare (latent)", (n, ch), torch.float32, dev)
+    nv.check(nv.lib().ltx2_retake_prepare(nv.ptr(encoded), nv.ptr(noise), ch, F, H, W, f0, f1, float(noise_scale), nv.ptr(oc), nv.ptr(om),
+                                          nv.ptr(ol), nv.stream()))
+    return oc, om, ol
+
+
+def retake_composite(decoded: torch.Tensor, source: torch.Tensor, p0: int, p1: int, ramp: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 clips (T, H, W, 3) -> uint8 (T, H, W, 3): `decoded` on the pixel frames [p0, p1), a linear fade into `source` over `ramp`
+    frames outside the window and the source's own bytes beyond it (ltx2_retake_composite, integer arithmetic).  out may not alias an input."""
+    for name, t in (("decoded", decoded), ("source", source)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3 or not t.is_cuda:
+            raise ValueError(f"retake_composite: {name} must be a uint8 GPU tensor (T, H, W, 3), got "
+                             f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else f"retake_composite: {name} must be a tensor")
+    dev = decoded.device
+    _dense(decoded, "retake_composite", "decoded", torch.uint8, decoded.shape, dev)
+    _dense(source, "retake_composite", "source", torch.uint8, decoded.shape, dev)
+    T, H, W, _ = decoded.shape
+    p0, p1, ramp = int(p0), int(p1), int(ramp)
+    if not 0 <= p0 <= p1 <= T:
+        raise ValueError(f"retake_composite: pixel-frame window [{p0}, {p1}) is not within 0 <= p0 <= p1 <= T = {T}")
+    if not 0 <= ramp <= nv.RETAKE_MAX_RAMP:
+        raise ValueError(f"retake_composite: ramp {ramp} (0 .. {nv.RETAKE_MAX_RAMP})")
+    out = _out_like(out, "retake_composite", decoded.shape, torch.uint8, dev)
+    nv.check(nv.lib().ltx2_retake_composite(nv.ptr(decoded), nv.ptr(source), T, H, W, p0, p1, ramp, nv.ptr(out), nv.stream()))
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- Gemma-3 text encoder (gemma.hip)
 # Gemma always runs on the bfloat16 build (model/text_encoder/gemma3.py), whatever the DiT's compute dtype.
 

@@ -6,6 +6,7 @@ from .ic_lora import (ControlType, ICLoraConfig, ICLoraPipeline, VideoCondition,
 from .keyframe_interpolation import (Keyframe, KeyframeInterpolationConfig, KeyframeInterpolationPipeline, create_keyframe_conditionings,
                                      create_keyframe_pipeline, load_image_as_tensor)
 from .one_stage import OneStageCFGConfig, OneStagePipeline, create_one_stage_pipeline
+from .retake import RetakeConfig, RetakePipeline, TemporalRegionMask, create_retake_pipeline, end_of_clip, get_video_metadata, load_video_frames
 from .ti2vid_hq import TI2VidHQConfig, TI2VidHQPipeline, create_ti2vid_hq_pipeline
 
 __all__ = ["ImageCondition", "apply_conditionings", "create_image_conditionings", "load_image_tensor", "joint_denoise_loop",
@@ -14,4 +15,5 @@ __all__ = ["ImageCondition", "apply_conditionings", "create_image_conditionings"
            "KeyframeInterpolationConfig", "KeyframeInterpolationPipeline", "create_keyframe_conditionings", "create_keyframe_pipeline",
            "load_image_as_tensor", "res2s_denoise_loop", "TI2VidHQConfig", "TI2VidHQPipeline", "create_ti2vid_hq_pipeline", "ControlType", "ICLoraConfig",
            "ICLoraPipeline", "VideoCondition", "create_ic_lora_pipeline", "create_video_conditionings", "load_control_frames",
-           "load_control_signal_tensor"]
+           "load_control_signal_tensor", "RetakeConfig", "RetakePipeline", "TemporalRegionMask", "create_retake_pipeline", "end_of_clip", "get_video_metadata",
+           "load_video_frames"]

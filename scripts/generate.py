@@ -107,28 +107,29 @@ def create_dummy_text_encoding(prompt: str, batch_size: int = 1, max_tokens: int
 NATIVE_FPS = 24     # the model generates motion at 24 fps
 
 
-def video_filters(fps: int = 24, speed: float = 1.0):
+def video_filters(fps=24, speed: float = 1.0, input_fps=NATIVE_FPS):
     """ffmpeg -vf chain of the reference's save_video (scripts/generate.py:2178-2194): speed first (setpts), then
-    motion-compensated interpolation when the target frame rate exceeds the native 24 fps."""
+    motion-compensated interpolation when the target frame rate exceeds the rate the frames arrive at (the native 24 fps, or a retake
+    source's own rate)."""
     filters = []
     if speed != 1.0:
         filters.append(f"setpts={1.0 / speed}*PTS")
-    if fps > NATIVE_FPS:
+    if fps > input_fps:
         filters.append(f"minterpolate=fps={fps}:mi_mode=mci:mc_mode=aobmc:me_mode=bidir:vsbmc=1")
     return filters
 
 
-def ffmpeg_command(width: int, height: int, output_path: str, fps: int = 24, speed: float = 1.0):
+def ffmpeg_command(width: int, height: int, output_path: str, fps=24, speed: float = 1.0, input_fps=NATIVE_FPS):
     """Same encoder settings as the reference (:2201-2222: libx264, yuv420p, crf 18, input at the native 24 fps); the
-    frames arrive as raw RGB on stdin instead of a directory of PNGs."""
-    cmd = ["ffmpeg", "-y", "-f", "rawvideo", "-pix_fmt", "rgb24", "-s", f"{width}x{height}", "-framerate", str(NATIVE_FPS), "-i", "-"]
-    filters = video_filters(fps, speed)
+    frames arrive as raw RGB on stdin instead of a directory of PNGs.  input_fps: the rate the frames are played at (a retake source's own)."""
+    cmd = ["ffmpeg", "-y", "-f", "rawvideo", "-pix_fmt", "rgb24", "-s", f"{width}x{height}", "-framerate", f"{input_fps:g}", "-i", "-"]
+    filters = video_filters(fps, speed, input_fps)
     if filters:
         cmd += ["-vf", ",".join(filters)]
     return cmd + ["-c:v", "libx264", "-pix_fmt", "yuv420p", "-crf", "18", "-loglevel", "error", output_path]
 
 
-def save_video(frames, output_path: str, fps: int = 24, speed: float = 1.0):
+def save_video(frames, output_path: str, fps=24, speed: float = 1.0, input_fps=NATIVE_FPS):
     """frames: uint8 (T, H, W, 3) array or list of (H, W, 3) arrays -> output_path via ffmpeg (reference :2153-2226).
     Without an ffmpeg binary the frames are written as PNGs into `<output stem>_frames/` and that directory is returned
     (the reference raises there; on a GPU box without ffmpeg the frames are still wanted)."""
@@ -146,7 +147,7 @@ def save_video(frames, output_path: str, fps: int = 24, speed: float = 1.0):
             Image.fromarray(frames[i]).save(os.path.join(out_dir, f"frame_{i:04d}.png"))
         print(f"  ffmpeg not found: wrote {t} PNG frames to {out_dir}/")
         return out_dir
-    result = subprocess.run(ffmpeg_command(w, h, output_path, fps, speed), input=frames.tobytes(), capture_output=True)
+    result = subprocess.run(ffmpeg_command(w, h, output_path, fps, speed, input_fps), input=frames.tobytes(), capture_output=True)
     if result.returncode != 0:
         raise RuntimeError(f"FFmpeg failed: {result.stderr.decode(errors='replace')}")
     return output_path
@@ -686,6 +687,10 @@ def generate_video(
     audio_path=None,
     audio_start_time: float = 0.0,
     audio_max_duration=None,
+    retake_video=None,
+    retake_start_time: float = 0.0,
+    retake_end_time=None,
+    retake_composite: bool = False,
 ):
     """Generate video from a text prompt: denoise loop + VAE decode on MI355X behind the reference's signature.
 
@@ -726,7 +731,46 @@ def generate_video(
     loaded (audio_start_time / audio_max_duration trim), cut or right-padded with silence to num_frames / fps seconds, turned into a log-mel
     and encoded by AudioEncoder; the latent stays frozen through the denoise loop (denoise_mask = 0, reference
     pipelines/a2vid_two_stage.py:338-357) and is written to `<stem>_audio_latent.npz`; the original audio, not a decode of the latent,
-    is muxed into the mp4 when an ffmpeg binary exists."""
+    is muxed into the mp4 when an ffmpeg binary exists.
+    retake_video (keyword-only; RetakePipeline, reference pipelines/retake.py, which the reference's own CLI never reaches): the source clip
+    (a .npy / .npz array of uint8 frames or a directory of image frames, played at output_fps; a video file when ffmpeg and ffprobe exist, at
+    its own frame rate) is kept and the seconds [retake_start_time, retake_end_time) of it are regenerated from the prompt (retake_end_time
+    None: to the end of the clip, taken as half a frame past its last one, since int(num_frames / fps * fps) can fall one frame short).  The
+    output is written at the source's rate: its frames enter ffmpeg at that rate and none is interpolated.  height, width and num_frames come from the source (frames snapped down to 8k + 1; the size must be
+    divisible by 32, nothing is resized).  model_variant="distilled" runs the 8 distilled steps without guidance, any other variant
+    LTX2Scheduler over num_steps with classifier-free guidance at cfg_scale (the negative encoding as for keyframes).  The window is widened
+    to whole latent frames (8 pixel frames each; TemporalRegionMask); retake_composite puts the source's own frames back outside it, with a
+    4-frame fade.  Not combined with generate_audio, audio_path, keyframes, control_video, image_path, two_stage_distilled, upscale_spatial,
+    upscale_temporal, fp8_resident or another pipeline_type."""
+    retake_pipeline = retake_video is not None
+    retake_window = None
+    if retake_pipeline:                                                  # before any model is loaded
+        for k, v in dict(generate_audio=generate_audio, audio_path=audio_path, keyframes=keyframes, control_video=control_video,
+                         image_path=image_path, two_stage_distilled=two_stage_distilled, upscale_spatial=upscale_spatial,
+                         upscale_temporal=upscale_temporal, fp8_resident=fp8_resident,
+                         pipeline_type=None if pipeline_type == "text-to-video" else pipeline_type).items():
+            if v:
+                raise NotImplementedError(f"{k} with retake_video: RetakePipeline is video-only, conditions on its source clip alone and runs "
+                                          "one stage at the source's own size on dequantised weights")
+        from ltx_2_mlx_amd.pipelines import RetakeConfig, TemporalRegionMask, end_of_clip, get_video_metadata
+        retake_video = str(retake_video)
+        # an array or a directory carries no frame rate: it plays at output_fps; a video file at its own
+        retake_fps, src_frames, width, height = get_video_metadata(
+            retake_video, float(output_fps) if (os.path.isdir(retake_video) or retake_video.lower().endswith((".npy", ".npz"))) else None)
+        if src_frames < 1:
+            raise ValueError(f"Could not read any frames from {retake_video}")
+        num_frames = ((src_frames - 1) // 8) * 8 + 1
+        if height % 32 != 0 or width % 32 != 0:
+            raise ValueError(f"Source resolution ({width}x{height}) must be divisible by 32 (the source is not resized)")
+        retake_to_end = retake_end_time is None
+        if retake_to_end:
+            retake_end_time = end_of_clip(num_frames, retake_fps)        # not num_frames / fps: int(end * fps) must reach the last frame
+        RetakeConfig(start_time=retake_start_time, end_time=retake_end_time)          # its ValueError (start_time >= end_time)
+        latent_frames = (num_frames - 1) // 8 + 1
+        retake_window = TemporalRegionMask(retake_start_time, retake_end_time, retake_fps).frame_window(latent_frames)
+        if retake_window[0] >= retake_window[1]:
+            raise ValueError(f"the retake window {retake_start_time}s - {retake_end_time}s touches no frame of the source: it has "
+                             f"{num_frames} frames at {retake_fps:g} fps, {num_frames / retake_fps:.3f} s")
     kf_pipeline = pipeline_type == "keyframe-interpolation" and bool(keyframes)
     hq_pipeline = pipeline_type == "ti2vid-hq"
     ic_pipeline = pipeline_type == "ic-lora" and bool(control_video or image_path)
@@ -860,7 +904,7 @@ def generate_video(
     if upscale_temporal and (_av_branch or two_stage_distilled):         # before any model is loaded
         raise NotImplementedError("upscale_temporal with the " + ("AudioVideo pipeline (the reference's AV branch returns before its upscalers)" if _av_branch
                                   else "two-stage DistilledPipeline (it returns before the post-denoise upscalers)"))
-    if kf_pipeline or hq_pipeline or ic_pipeline:
+    if kf_pipeline or hq_pipeline or ic_pipeline or retake_pipeline:
         _need_cfg = False                   # guided by the pipeline itself (ic-lora: not at all); a missing negative encoding becomes zeros
     if _need_cfg and not _av_branch:
         raise NotImplementedError(f"cfg_scale={cfg_scale}: classifier-free guidance is built in OneStagePipeline (the AudioVideo / LTX-2.3 branch); the "
@@ -875,7 +919,7 @@ def generate_video(
     version = model_version if model_version is not None else (detect_model_version(weights_path) if have_ckpt else "")
     v2 = version.startswith("2.3")                      # reference :1073: V2.3 always uses the AV transformer and the dual text encodings
     use_av_encoder = generate_audio or v2
-    fps, speed = output_fps, output_speed
+    fps, speed, input_fps = output_fps, output_speed, NATIVE_FPS
     torch.manual_seed(seed)
     t_all = time.time()
     base = os.path.splitext(output_path)[0]
@@ -896,7 +940,7 @@ def generate_video(
         text_encoding, _ = encode_with_gemma(prompt, gemma_path, weights_path if have_ckpt else None, use_early_layers_only=early_layers_only,
                                              device=device, seed=seed)
         print("  Encoded with Gemma 3")
-        if (kf_pipeline or hq_pipeline) and cfg_scale != 1.0:
+        if (kf_pipeline or hq_pipeline or (retake_pipeline and model_variant != "distilled")) and cfg_scale != 1.0:
             negative_encoding, _ = encode_with_gemma(negative_prompt or "", gemma_path, weights_path if have_ckpt else None, device=device, seed=seed)
             print("  Encoded the negative prompt with Gemma 3")
     elif embedding_path:
@@ -989,12 +1033,12 @@ def generate_video(
         frames_np = frames.cpu().numpy()
         np.savez_compressed(base + ".npz", frames=frames_np)
         if audio is not None and save_mp4:
-            video_out, wav = save_video_with_audio(frames_np, audio[0], output_path, audio[1], fps=fps, speed=speed)
+            video_out, wav = save_video_with_audio(frames_np, audio[0], output_path, audio[1], fps=fps, speed=speed)      # never the retake route
             print(f"  video: {video_out}, audio: {wav}")
         elif audio is not None:
             print(f"  audio: {write_wav(base + '.wav', audio[0], audio[1])}")
         elif save_mp4:
-            print(f"  video: {save_video(frames_np, output_path, fps=fps, speed=speed)}")
+            print(f"  video: {save_video(frames_np, output_path, fps=fps, speed=speed, input_fps=input_fps)}")
         print(f"Done in {time.time() - t_all:.1f} s: {base}.npz{extra}")
         return frames
 
@@ -1088,6 +1132,36 @@ def generate_video(
         frames = _frames_from_video(pipe(text_encoding, None, conf, images=images, video_conditioning=videos))
         torch.cuda.synchronize()
         print(f"  ic-lora: {(time.time() - t0):.3f} s -> {tuple(frames.shape)}, DiT tokens per stage {pipe.token_counts}")
+        return finish(frames)
+
+    if retake_pipeline:
+        # === RETAKE PIPELINE (reference pipelines/retake.py; its own CLI never reaches it) ===
+        print("\n=== Using Retake Pipeline ===")
+        if model is None:
+            raise ValueError("Retake pipeline requires a loaded model")
+        if vae_decoder is None:
+            raise ValueError("Retake pipeline requires VAE decoder")
+        from ltx_2_mlx_amd.pipelines import RetakeConfig, RetakePipeline
+        distilled = model_variant == "distilled"
+        conf = RetakeConfig(start_time=retake_start_time, end_time=retake_end_time, distilled=distilled, num_inference_steps=num_steps,
+                            cfg_scale=cfg_scale, seed=seed, fps=retake_fps, use_hip_graph=use_hip_graph, composite_source=retake_composite,
+                            tiling_config=TilingConfig.default() if tiled_vae else None)
+        print(f"  Source: {retake_video}, {width}x{height}, {num_frames} frames @ {retake_fps:g} FPS")
+        print(f"  Retake region: {retake_start_time:g}s - {'the end of the clip' if retake_to_end else f'{retake_end_time:g}s'} -> latent frames [{retake_window[0]}, {retake_window[1]}) of "
+              f"{(num_frames - 1) // 8 + 1}, {((num_frames - 1) // 8 + 1) * (height // 32) * (width // 32)} DiT tokens"
+              + (", source frames kept outside it" if retake_composite else ""))
+        print("[3.5/5] VAE encoder")
+        if not have_ckpt:
+            print("  Warning: no checkpoint, the VAE encoder is random-initialised")
+        pipe = RetakePipeline(model, make_encoder(), vae_decoder)
+        if not distilled and cfg_scale > 1.0 and negative_encoding is None:
+            print("  Negative prompt: no encoding given, using zeros of the context's shape (the reference's null text encoding)")
+        print(f"[5/5] Running retake ({'8 distilled steps' if distilled else f'{num_steps} steps, cfg {cfg_scale}'})...")
+        t0 = time.time()
+        frames = _frames_from_video(pipe(retake_video, text_encoding, None, conf, negative_text_encoding=negative_encoding))
+        torch.cuda.synchronize()
+        fps = input_fps = retake_fps                                     # written at the source's rate: frames enter ffmpeg at it, none interpolated
+        print(f"  retake: {(time.time() - t0):.3f} s -> {tuple(frames.shape)}")
         return finish(frames)
 
     if two_stage_distilled:
@@ -1328,6 +1402,12 @@ def build_parser() -> argparse.ArgumentParser:
                    "encoded by the audio VAE encoder and stays frozen while the video is denoised; the original audio is muxed into the mp4")
     p.add_argument("--audio-start", type=float, default=0.0, help="seconds into --audio to start from")
     p.add_argument("--audio-duration", type=float, default=None, help="at most this many seconds of --audio (the rest of the video's length is silence)")
+    p.add_argument("--retake", type=str, default=None, help="RetakePipeline: keep this clip (.npy / .npz frames or an image directory at --fps; a video file with ffmpeg) "
+                   "and regenerate the seconds --retake-start .. --retake-end of it from the prompt; size and length come from the clip.  --model-variant distilled: "
+                   "8 steps, no guidance; dev: --steps steps at --cfg")
+    p.add_argument("--retake-start", type=float, default=0.0, help="start of the regenerated window in seconds (inclusive)")
+    p.add_argument("--retake-end", type=float, default=None, help="end of the regenerated window in seconds (exclusive); default: the end of the clip")
+    p.add_argument("--retake-keep-source", action="store_true", help="put the source's own frames back outside the window (4-frame fade outside it)")
     return p
 
 
@@ -1358,7 +1438,8 @@ def kwargs_from_args(a) -> dict:
         text_features_path=a.text_features, use_hip_graph=not a.no_hip_graph, two_stage_distilled=a.two_stage_distilled,
         fp8_resident=a.fp8_resident, fp8_compute=a.fp8_compute, model_version=a.model_version, compute_dtype="bfloat16" if a.bf16 else None, num_layers=a.layers, num_heads=a.heads,
         vae_base_channels=a.vae_base_channels, save_mp4=not a.no_video_file, decode_audio=a.decode_audio,
-        audio_path=a.audio, audio_start_time=a.audio_start, audio_max_duration=a.audio_duration)
+        audio_path=a.audio, audio_start_time=a.audio_start, audio_max_duration=a.audio_duration,
+        retake_video=a.retake, retake_start_time=a.retake_start, retake_end_time=a.retake_end, retake_composite=a.retake_keep_source)
 
 
 def main(argv=None):
