@@ -173,6 +173,7 @@ class LTXModel:
         self._clone: Optional["LTXModel"] = None       # clone_sharing_weights()
         self._twin: Optional["LTXModel"] = None        # VideoOnly engine over the SAME weight tensors (video-only inference on an AV model)
         self._sigma_dev: Dict[float, torch.Tensor] = {}  # device scalars of the step sigmas (no host-to-device copy inside the loop)
+        self._graph_owner: Optional[Tuple[str, "LTXModel"]] = None     # (kind of the last capture made through this object, the context that holds its graph)
         self._ctor = dict(num_attention_heads=num_attention_heads, attention_head_dim=attention_head_dim, in_channels=in_channels,
                           out_channels=out_channels, num_layers=num_layers, cross_attention_dim=cross_attention_dim, norm_eps=norm_eps,
                           caption_channels=caption_channels, positional_embedding_theta=positional_embedding_theta,
@@ -589,21 +590,49 @@ class LTXModel:
         return t
 
     # ------------------------------------------------------------------ fused sampling step / graph
+    def _step_inputs(self, latent: torch.Tensor, video: Modality, sigma: float) -> Tuple[torch.Tensor, int, Optional[torch.Tensor]]:
+        """What every fused video-only step does first: -> (timesteps, n_timesteps, the prompt AdaLN's sigma scalar or None), with this
+        context prepared for `video` and its context mask applied."""
+        ts, n_ts = self._timesteps(video)
+        assert latent.dtype == torch.float32 and latent.is_contiguous() and latent.dim() == 2
+        self._ensure_prepared(video, per_token=(n_ts != 1))
+        self._apply_context_masks(video)
+        return ts, n_ts, (self._sigma_scalar(sigma) if self.cross_attention_adaln else None)
+
+    def _capture_inputs(self, sigmas: Sequence[float], *mask_clean_pairs):
+        """What every capture_*_graph does first: -> (the sigmas as a c_float array, the step count, the current stream, n_el).  Capture
+        needs a non-default stream; every (denoise_mask, clean_latent) pair must be fp32 and contiguous, the mask one-dimensional.  n_el(t)
+        is a buffer's element count (0 for None): the engine checks it against the bound token count, as a wrong-length buffer would be an
+        out-of-bounds read on replay."""
+        arr = (C.c_float * len(sigmas))(*[float(s) for s in sigmas])
+        st = torch.cuda.current_stream()
+        if st.cuda_stream == 0:
+            raise RuntimeError("graph capture needs a non-default stream: use `with torch.cuda.stream(torch.cuda.Stream()):`")
+        for mk, cl in mask_clean_pairs:
+            if mk is not None:
+                assert cl is not None and mk.dtype == torch.float32 and cl.dtype == torch.float32 and mk.is_contiguous() and cl.is_contiguous() and mk.dim() == 1
+        return arr, len(sigmas) - 1, st, (lambda t: 0 if t is None else t.numel())
+
+    def _replay(self, kind: str, missing: str) -> None:
+        """Launch the graph of the last capture of `kind` made through this object, on the context that holds it."""
+        if self._graph_owner is None or self._graph_owner[0] != kind:
+            raise RuntimeError(missing)
+        owner = self._graph_owner[1]
+        nv.check(owner._L.ltx2_dit_graph_launch(owner._h, nv.stream()))
+
     def denoise_step_(self, latent: torch.Tensor, video: Modality, sigma: float, sigma_next: float,
                       denoise_mask: Optional[torch.Tensor] = None, clean_latent: Optional[torch.Tensor] = None,
                       audio_latent: Optional[torch.Tensor] = None, audio: Optional[Modality] = None,
                       audio_denoise_mask: Optional[torch.Tensor] = None, audio_clean_latent: Optional[torch.Tensor] = None) -> None:
         """In-place: latent (N, C) fp32 <- Euler(latent, post_process(x0)) -- forward + x0 + blend + step
         enqueued by ONE C call (ltx2_dit_denoise_step / _av; the AudioVideo form updates both latents)."""
-        ts, n_ts = self._timesteps(video)
-        assert latent.dtype == torch.float32 and latent.is_contiguous() and latent.dim() == 2
         if not self.is_av:
-            self._ensure_prepared(video, per_token=(n_ts != 1))
-            self._apply_context_masks(video)
-            sg = self._sigma_scalar(sigma) if self.cross_attention_adaln else None
+            ts, n_ts, sg = self._step_inputs(latent, video, sigma)
             nv.check(self._L.ltx2_dit_denoise_step(self._h, nv.ptr(latent), nv.ptr(ts), n_ts, nv.ptr(sg), nv.ptr(denoise_mask),
                                                     nv.ptr(clean_latent), float(sigma), float(sigma_next), None, nv.stream()))
             return
+        ts, n_ts = self._timesteps(video)
+        assert latent.dtype == torch.float32 and latent.is_contiguous() and latent.dim() == 2
         assert audio is not None and audio_latent is not None and audio_latent.dtype == torch.float32 and audio_latent.is_contiguous()
         ats, n_ats = self._timesteps(audio)
         self._ensure_prepared(video, per_token=(n_ts != 1 or n_ats != 1), audio=audio)
@@ -621,28 +650,22 @@ class LTXModel:
         loop of image-to-video runs -- per-token timesteps mask * sigma_i and the x0 / clean blend inside every captured step
         (ltx2_dit_graph_capture_cond; prepare(..., per_token=True) first).  The tensors must stay alive while the graph is replayed."""
         assert self._prep_key is not None, "call prepare() first"
-        arr = (C.c_float * len(sigmas))(*[float(s) for s in sigmas])
-        st = torch.cuda.current_stream()
-        if st.cuda_stream == 0:
-            raise RuntimeError("graph capture needs a non-default stream: use `with torch.cuda.stream(torch.cuda.Stream()):`")
+        arr, n, st, n_el = self._capture_inputs(sigmas, (denoise_mask, clean_latent), (audio_denoise_mask, audio_clean_latent))
         cond = denoise_mask is not None or audio_denoise_mask is not None
-        for mk, cl in ((denoise_mask, clean_latent), (audio_denoise_mask, audio_clean_latent)):
-            if mk is not None:
-                assert cl is not None and mk.dtype == torch.float32 and cl.dtype == torch.float32 and mk.is_contiguous() and cl.is_contiguous() and mk.dim() == 1
-        n_el = lambda t: 0 if t is None else t.numel()      # element counts: the engine checks them against the bound token count (a wrong-length buffer would be an out-of-bounds replay read)
         self._graph_refs = (latent, audio_latent, denoise_mask, clean_latent, audio_denoise_mask, audio_clean_latent)
+        self._graph_owner = ("denoise", self)
         if self.is_av:
             assert audio_latent is not None
             if cond:
-                nv.check(self._L.ltx2_dit_graph_capture_cond_av(self._h, nv.ptr(latent), nv.ptr(audio_latent), arr, len(sigmas) - 1, nv.ptr(denoise_mask), n_el(denoise_mask),
+                nv.check(self._L.ltx2_dit_graph_capture_cond_av(self._h, nv.ptr(latent), nv.ptr(audio_latent), arr, n, nv.ptr(denoise_mask), n_el(denoise_mask),
                                                                 nv.ptr(clean_latent), n_el(clean_latent), nv.ptr(audio_denoise_mask), n_el(audio_denoise_mask),
                                                                 nv.ptr(audio_clean_latent), n_el(audio_clean_latent), st.cuda_stream))
             else:
-                nv.check(self._L.ltx2_dit_graph_capture_av(self._h, nv.ptr(latent), nv.ptr(audio_latent), arr, len(sigmas) - 1, st.cuda_stream))
+                nv.check(self._L.ltx2_dit_graph_capture_av(self._h, nv.ptr(latent), nv.ptr(audio_latent), arr, n, st.cuda_stream))
         elif cond:
-            nv.check(self._L.ltx2_dit_graph_capture_cond(self._h, nv.ptr(latent), arr, len(sigmas) - 1, nv.ptr(denoise_mask), n_el(denoise_mask), nv.ptr(clean_latent), n_el(clean_latent), st.cuda_stream))
+            nv.check(self._L.ltx2_dit_graph_capture_cond(self._h, nv.ptr(latent), arr, n, nv.ptr(denoise_mask), n_el(denoise_mask), nv.ptr(clean_latent), n_el(clean_latent), st.cuda_stream))
         else:
-            nv.check(self._L.ltx2_dit_graph_capture(self._h, nv.ptr(latent), arr, len(sigmas) - 1, st.cuda_stream))
+            nv.check(self._L.ltx2_dit_graph_capture(self._h, nv.ptr(latent), arr, n, st.cuda_stream))
 
     # ------------------------------------------------------------------ classifier-free guidance (video-only engine)
     def _guided_pair(self, neg: "LTXModel") -> Tuple["LTXModel", "LTXModel"]:
@@ -657,11 +680,7 @@ class LTXModel:
         through `neg` (clone_sharing_weights(), prepared by the caller with the negative context), then x0 x 2 + CFGGuider.guide +
         post_process_latent + Euler in one kernel, all enqueued by ONE C call (ltx2_dit_guided_step)."""
         pos, ng = self._guided_pair(neg)
-        ts, n_ts = pos._timesteps(video)
-        assert latent.dtype == torch.float32 and latent.is_contiguous() and latent.dim() == 2
-        pos._ensure_prepared(video, per_token=(n_ts != 1))
-        pos._apply_context_masks(video)
-        sg = pos._sigma_scalar(sigma) if pos.cross_attention_adaln else None
+        ts, n_ts, sg = pos._step_inputs(latent, video, sigma)
         nv.check(pos._L.ltx2_dit_guided_step(pos._h, ng._h, nv.ptr(latent), nv.ptr(ts), n_ts, nv.ptr(sg), nv.ptr(denoise_mask), nv.ptr(clean_latent),
                                              float(cfg_scale), float(sigma), float(sigma_next), nv.stream()))
 
@@ -669,28 +688,19 @@ class LTXModel:
                              denoise_mask: Optional[torch.Tensor] = None, clean_latent: Optional[torch.Tensor] = None) -> None:
         """hipGraph-capture len(sigmas)-1 guided steps over `latent` (N, C fp32), a linear chain of forward(self), forward(neg) and the guided
         Euler kernel per step (ltx2_dit_graph_capture_guided).  Both contexts are prepared first (per_token=True when a mask is given); the
-        graph belongs to this context and replay_denoise_graph() replays it.  The tensors must stay alive while it is replayed."""
+        graph belongs to the positive VideoOnly context (this one, or an AudioVideo model's video twin) and replay_guided_graph() replays
+        it.  The tensors must stay alive while it is replayed."""
         pos, ng = self._guided_pair(neg)
         assert pos._prep_key is not None and ng._prep_key is not None, "call prepare() on both contexts first"
-        arr = (C.c_float * len(sigmas))(*[float(s) for s in sigmas])
-        st = torch.cuda.current_stream()
-        if st.cuda_stream == 0:
-            raise RuntimeError("graph capture needs a non-default stream: use `with torch.cuda.stream(torch.cuda.Stream()):`")
-        if denoise_mask is not None:
-            assert clean_latent is not None and denoise_mask.dtype == torch.float32 and clean_latent.dtype == torch.float32
-            assert denoise_mask.is_contiguous() and clean_latent.is_contiguous() and denoise_mask.dim() == 1
-        n_el = lambda t: 0 if t is None else t.numel()
+        arr, n, st, n_el = self._capture_inputs(sigmas, (denoise_mask, clean_latent))
         pos._graph_refs = (latent, denoise_mask, clean_latent, ng)
-        nv.check(pos._L.ltx2_dit_graph_capture_guided(pos._h, ng._h, nv.ptr(latent), arr, len(sigmas) - 1, nv.ptr(denoise_mask), n_el(denoise_mask),
+        nv.check(pos._L.ltx2_dit_graph_capture_guided(pos._h, ng._h, nv.ptr(latent), arr, n, nv.ptr(denoise_mask), n_el(denoise_mask),
                                                       nv.ptr(clean_latent), n_el(clean_latent), float(cfg_scale), st.cuda_stream))
-        self._guided_graph_owner = pos
+        self._graph_owner = ("guided", pos)
 
     def replay_guided_graph(self) -> None:
         """Replay the graph captured by capture_guided_graph (it belongs to the VideoOnly context that ran the capture)."""
-        owner = getattr(self, "_guided_graph_owner", None)
-        if owner is None:
-            raise RuntimeError("no guided graph captured")
-        nv.check(owner._L.ltx2_dit_graph_launch(owner._h, nv.stream()))
+        self._replay("guided", "no guided graph captured")
 
     # ------------------------------------------------------------------ res_2s second-order sampling (video-only engine)
     def _res2s_pair(self, neg: Optional["LTXModel"]) -> Tuple["LTXModel", Optional["LTXModel"]]:
@@ -708,18 +718,13 @@ class LTXModel:
         only for the final step (sigma_next <= 0.001), which is one pair of evaluations and latent = d.  Both contexts are prepared by the
         caller (neg with the negative context)."""
         pos, ng = self._res2s_pair(neg)
-        ts, n_ts = pos._timesteps(video)
-        assert latent.dtype == torch.float32 and latent.is_contiguous() and latent.dim() == 2
-        pos._ensure_prepared(video, per_token=(n_ts != 1))
-        pos._apply_context_masks(video)
+        ts, n_ts, sg = pos._step_inputs(latent, video, sigma)
         ts_sub = sg_sub = None
         if video_sub is not None:
             ts_sub, n_sub = pos._timesteps(video_sub)
             assert n_sub == n_ts, "both evaluations take one timestep, or one per token"
-        adaln = pos.cross_attention_adaln
-        sg = pos._sigma_scalar(sigma) if adaln else None
-        if adaln and video_sub is not None:
-            sg_sub = pos._sigma(video_sub)
+            if pos.cross_attention_adaln:
+                sg_sub = pos._sigma(video_sub)
         nv.check(pos._L.ltx2_dit_res2s_step(pos._h, None if ng is None else ng._h, nv.ptr(latent), nv.ptr(ts), n_ts, nv.ptr(sg), nv.ptr(ts_sub),
                                             nv.ptr(sg_sub), nv.ptr(denoise_mask), nv.ptr(clean_latent), float(cfg_scale), float(sigma),
                                             float(sigma_next), nv.stream()))
@@ -731,25 +736,15 @@ class LTXModel:
         replay_res2s_graph() replays it.  The tensors must stay alive while it is replayed."""
         pos, ng = self._res2s_pair(neg)
         assert pos._prep_key is not None and (ng is None or ng._prep_key is not None), "call prepare() on both contexts first"
-        arr = (C.c_float * len(sigmas))(*[float(s) for s in sigmas])
-        st = torch.cuda.current_stream()
-        if st.cuda_stream == 0:
-            raise RuntimeError("graph capture needs a non-default stream: use `with torch.cuda.stream(torch.cuda.Stream()):`")
-        if denoise_mask is not None:
-            assert clean_latent is not None and denoise_mask.dtype == torch.float32 and clean_latent.dtype == torch.float32
-            assert denoise_mask.is_contiguous() and clean_latent.is_contiguous() and denoise_mask.dim() == 1
-        n_el = lambda t: 0 if t is None else t.numel()
+        arr, n, st, n_el = self._capture_inputs(sigmas, (denoise_mask, clean_latent))
         pos._graph_refs = (latent, denoise_mask, clean_latent, ng)
-        nv.check(pos._L.ltx2_dit_graph_capture_res2s(pos._h, None if ng is None else ng._h, nv.ptr(latent), arr, len(sigmas) - 1, nv.ptr(denoise_mask),
+        nv.check(pos._L.ltx2_dit_graph_capture_res2s(pos._h, None if ng is None else ng._h, nv.ptr(latent), arr, n, nv.ptr(denoise_mask),
                                                      n_el(denoise_mask), nv.ptr(clean_latent), n_el(clean_latent), float(cfg_scale), st.cuda_stream))
-        self._res2s_graph_owner = pos
+        self._graph_owner = ("res2s", pos)
 
     def replay_res2s_graph(self) -> None:
         """Replay the graph captured by capture_res2s_graph (it belongs to the VideoOnly context that ran the capture)."""
-        owner = getattr(self, "_res2s_graph_owner", None)
-        if owner is None:
-            raise RuntimeError("no res_2s graph captured")
-        nv.check(owner._L.ltx2_dit_graph_launch(owner._h, nv.stream()))
+        self._replay("res2s", "no res_2s graph captured")
 
     def replace_weights(self, tensors: Dict[str, torch.Tensor]) -> None:
         """Re-register engine-layout tensors (names of weight_tensors()) in place of the ones held now -- the HQ pipeline's LoRA fusion for

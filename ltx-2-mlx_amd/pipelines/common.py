@@ -1,17 +1,22 @@
-"""Loop and conditioning helpers shared by the pipelines.  Mirrors reference LTX_2_MLX/pipelines/common.py:23-262."""
+"""Loop and conditioning helpers shared by the pipelines.  Mirrors reference LTX_2_MLX/pipelines/common.py:23-262.
+Additions of this codebase, without a counterpart there: the stage helpers (as_x0model, seeded_noiser, video_tools_for, conditioned_initial_state,
+stage_callback, final_latent, upscale_latent_x2, auto_tiling_config, decode_video) and the three device-resident loops with their helpers."""
 from __future__ import annotations
 
 import math
 import os
 from dataclasses import dataclass
-from typing import List, Optional
+from typing import Callable, List, Optional, Tuple
 
 import torch
 
+from ..components import GaussianNoiser
 from ..conditioning.latent import VideoConditionByLatentIndex
 from ..conditioning.tools import VideoLatentTools
-from ..model.transformer import Modality
-from ..types import LatentState
+from ..model.transformer import LTXModelType, Modality, X0Model
+from ..model.upscaler import SpatialUpscaler, upscale_latent
+from ..model.video_vae import TilingConfig, decode_latent, decode_tiled
+from ..types import LatentState, VideoLatentShape, VideoPixelShape
 
 
 @dataclass
@@ -73,6 +78,74 @@ def apply_conditionings(latent_state: LatentState, conditionings, video_tools: V
     return latent_state
 
 
+# ---------------------------------------------------------------------- the scaffolding of a stage, one copy for every pipeline
+def as_x0model(transformer) -> Tuple[X0Model, bool]:
+    """-> (the transformer as an X0Model, whether it is an AudioVideo model)."""
+    x0 = transformer if isinstance(transformer, X0Model) else X0Model(transformer)
+    return x0, getattr(x0.velocity_model, "model_type", None) == LTXModelType.AudioVideo
+
+
+def seeded_noiser(device, seed: int) -> GaussianNoiser:
+    """The one generator of a call: every stage draws from it in turn."""
+    return GaussianNoiser(generator=torch.Generator(device=device).manual_seed(seed))
+
+
+def video_tools_for(patchifier, num_frames: int, height: int, width: int, fps: float) -> VideoLatentTools:
+    """The latent tools of a stage that renders num_frames pixel frames of height x width."""
+    pix = VideoPixelShape(batch=1, frames=num_frames, height=height, width=width, fps=fps)
+    return VideoLatentTools(patchifier=patchifier, target_shape=VideoLatentShape.from_pixel_shape(pix, latent_channels=128), fps=fps)
+
+
+def conditioned_initial_state(tools: VideoLatentTools, conditionings, dtype: torch.dtype, device, initial_latent=None) -> LatentState:
+    """The patchified start of a stage, zeros on `device` or `initial_latent` (a second stage), with the conditionings applied in order."""
+    return apply_conditionings(tools.create_initial_state(dtype=dtype, initial_latent=initial_latent, device=device), conditionings, tools)
+
+
+def stage_callback(callback: Optional[Callable[[str, int, int], None]], name: str) -> Optional[Callable[[int, int], None]]:
+    """A pipeline's (stage, step, total) callback as the (step, total) callback of one stage's loop."""
+    return (lambda s, t: callback(name, s, t)) if callback else None
+
+
+def final_latent(tools, state: LatentState) -> torch.Tensor:
+    """The latent of a stage's last state: appended conditioning tokens cut off, unpatchified (video or audio tools)."""
+    return tools.unpatchify(tools.clear_conditioning(state)).latent
+
+
+def upscale_latent_x2(latent: torch.Tensor, spatial_upscaler, video_encoder, video_decoder) -> torch.Tensor:
+    """un_normalize -> spatial upscaler -> normalize (reference pipelines/distilled.py:394-405).  The statistics ship with the VAE weights:
+    the encoder's only when it actually carries loaded weights (an unloaded SimpleVideoEncoder holds the identity placeholder zeros / ones,
+    which would silently mis-scale stage 2), else the decoder's, which also serves when no encoder object is passed."""
+    stats = getattr(video_encoder, "per_channel_statistics", None)
+    if stats is not None and not getattr(video_encoder, "_loaded", True):
+        stats = None
+    stats = stats or getattr(video_decoder, "per_channel_statistics", None)
+    if stats is None:
+        raise ValueError("spatial_upscaler needs per_channel_statistics (un_normalize/normalize) from the video VAE")
+    if isinstance(spatial_upscaler, SpatialUpscaler):
+        return upscale_latent(latent, spatial_upscaler, stats.mean_of_means, stats.std_of_means)
+    return stats.normalize(spatial_upscaler(stats.un_normalize(latent)))
+
+
+def auto_tiling_config(tiling_config: Optional[TilingConfig], num_frames: int, height: int, width: int) -> Optional[TilingConfig]:
+    """The given tiling, or the default one above 4000 latent voxels (reference pipelines/distilled.py:86-98)."""
+    if tiling_config is not None:
+        return tiling_config
+    latent_frames = (num_frames - 1) // 8 + 1
+    if latent_frames * (height // 32) * (width // 32) > 4000:
+        return TilingConfig.default()
+    return None
+
+
+def decode_video(latent: torch.Tensor, video_decoder, tiling: Optional[TilingConfig]) -> torch.Tensor:
+    """The final decode: the latent itself without a decoder, the tiled decode's chunks joined in time with `tiling`, else decode_latent."""
+    if video_decoder is None:
+        return latent
+    if tiling:
+        chunks = list(decode_tiled(latent, video_decoder, tiling))
+        return torch.cat(chunks, dim=2) if len(chunks) > 1 else chunks[0]
+    return decode_latent(latent, video_decoder)
+
+
 def post_process_latent(denoised: torch.Tensor, denoise_mask: torch.Tensor, clean_latent: torch.Tensor) -> torch.Tensor:
     """Blend denoised output with the clean state: denoised*mask + clean*(1-mask)."""
     if denoise_mask.ndim == 2 and denoised.ndim == 3:
@@ -110,6 +183,34 @@ def _note_eager_once(why: str) -> None:
         print(f"  note: hipGraph replay skipped, the sampling loop runs eagerly: {why}", file=sys.stderr)
 
 
+def _capture_and_replay(capture: Callable[[], None], replay: Callable[[], None]) -> None:
+    """Capture a loop's graph on a side stream (capture needs a non-default one) and replay it there once, ordered after the work already
+    queued on the current stream and before whatever follows."""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        capture()
+        replay()
+    torch.cuda.current_stream().wait_stream(side)
+
+
+def _video_loop_inputs(model, video_state: LatentState):
+    """What the device-resident video loops step: -> (the video-only model, whether the mask is all ones, the fp32 latent (N, C), cloned as
+    it is stepped in place: never the caller's tensor, and the fp32 mask (N,) / clean latent (N, C), None when uniform)."""
+    if model.is_av:
+        model = model._video_twin()
+    uniform = bool((video_state.denoise_mask == 1).all())
+    lat = video_state.latent[0].float().clone(memory_format=torch.contiguous_format)
+    mask = None if uniform else video_state.denoise_mask[0].reshape(-1).float().contiguous()
+    clean = None if uniform else video_state.clean_latent[0].float().contiguous()
+    return model, uniform, lat, mask, clean
+
+
+def _with_latent(state: LatentState, lat: torch.Tensor) -> LatentState:
+    """The state with the stepped fp32 latent (N, C) written back in its own dtype."""
+    return state.replace(latent=lat[None].to(state.latent.dtype))
+
+
 def joint_denoise_loop(transformer, is_av_model: bool, video_state: LatentState, audio_state: Optional[LatentState], sigmas,
                        video_context: torch.Tensor, audio_context: Optional[torch.Tensor], stepper, callback=None,
                        use_hip_graph: bool = False, *, negative_video_context: Optional[torch.Tensor] = None,
@@ -141,7 +242,6 @@ def joint_denoise_loop(transformer, is_av_model: bool, video_state: LatentState,
     if need_cfg:
         if negative_video_context is None or (joint and negative_audio_context is None):
             raise ValueError("guidance needs the negative prompt's encoding(s)")
-        from ..model.transformer import X0Model
         neg = X0Model(model.clone_sharing_weights())
     if use_hip_graph and not (callback is None and not need_cfg):
         _note_eager_once("a step callback" if callback is not None else "classifier-free guidance (two evaluations per step)")
@@ -160,16 +260,8 @@ def joint_denoise_loop(transformer, is_av_model: bool, video_state: LatentState,
             model.prepare(video_context, video_state.positions, per_token=not uniform, audio_context=audio_context, audio_positions=audio_state.positions)
         else:
             model.prepare(video_context, video_state.positions, per_token=not uniform)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            model.capture_denoise_graph(lat, sig, audio_latent=alat, **cond)
-            model.replay_denoise_graph()
-        torch.cuda.current_stream().wait_stream(side)
-        video_state = video_state.replace(latent=lat[None].to(video_state.latent.dtype))
-        if joint:
-            audio_state = audio_state.replace(latent=alat[None].to(audio_state.latent.dtype))
-        return video_state, audio_state
+        _capture_and_replay(lambda: model.capture_denoise_graph(lat, sig, audio_latent=alat, **cond), model.replay_denoise_graph)
+        return _with_latent(video_state, lat), (_with_latent(audio_state, alat) if joint else audio_state)
     for i in range(n):
         vm = modality_from_state(video_state, video_context, sig[i], uniform=unif[0])
         if joint:
@@ -212,22 +304,13 @@ def guided_denoise_loop(transformer, video_state: LatentState, sigmas, context: 
         raise ValueError("guidance needs the negative prompt's encoding")
     sig = [float(s) for s in sigmas]
     n = len(sig) - 1
-    if model.is_av:
-        model = model._video_twin()
+    model, uniform, lat, mask, clean = _video_loop_inputs(model, video_state)
     neg = model.clone_sharing_weights()
-    uniform = bool((video_state.denoise_mask == 1).all())
-    lat = video_state.latent[0].float().clone(memory_format=torch.contiguous_format)      # stepped in place: never the caller's tensor
-    mask = None if uniform else video_state.denoise_mask[0].reshape(-1).float().contiguous()
-    clean = None if uniform else video_state.clean_latent[0].float().contiguous()
     model.prepare(context, video_state.positions, per_token=not uniform)
     neg.prepare(negative_context, video_state.positions, per_token=not uniform)
     if use_hip_graph and callback is None and n < 64:
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            model.capture_guided_graph(neg, lat, sig, guider.scale, denoise_mask=mask, clean_latent=clean)
-            model.replay_guided_graph()
-        torch.cuda.current_stream().wait_stream(side)
+        _capture_and_replay(lambda: model.capture_guided_graph(neg, lat, sig, guider.scale, denoise_mask=mask, clean_latent=clean),
+                            model.replay_guided_graph)
     else:
         for i in range(n):
             st = video_state.replace(latent=lat[None])
@@ -235,7 +318,7 @@ def guided_denoise_loop(transformer, video_state: LatentState, sigmas, context: 
                                denoise_mask=mask, clean_latent=clean)
             if callback:
                 callback(i + 1, n)
-    return video_state.replace(latent=lat[None].to(video_state.latent.dtype))
+    return _with_latent(video_state, lat)
 
 
 def res2s_denoise_loop(transformer, video_state: LatentState, sigmas, context: torch.Tensor, negative_context: Optional[torch.Tensor],
@@ -255,25 +338,15 @@ def res2s_denoise_loop(transformer, video_state: LatentState, sigmas, context: t
     if sig[-1] == 0.0:
         sig = sig[:-1] + [0.0011, 0.0]
     sig = torch.tensor(sig[: n + 1], dtype=torch.float32).tolist()             # the n steps read sigma_0 .. sigma_n only
-    model = transformer.velocity_model
-    if model.is_av:
-        model = model._video_twin()
+    model, uniform, lat, mask, clean = _video_loop_inputs(transformer.velocity_model, video_state)
     guide = (cfg_scale > 1.0 or audio_cfg_scale > 1.0) and negative_context is not None
     neg = model.clone_sharing_weights() if guide else None
-    uniform = bool((video_state.denoise_mask == 1).all())
-    lat = video_state.latent[0].float().clone(memory_format=torch.contiguous_format)      # stepped in place: never the caller's tensor
-    mask = None if uniform else video_state.denoise_mask[0].reshape(-1).float().contiguous()
-    clean = None if uniform else video_state.clean_latent[0].float().contiguous()
     model.prepare(context, video_state.positions, per_token=not uniform)
     if guide:
         neg.prepare(negative_context, video_state.positions, per_token=not uniform)
     if use_hip_graph and callback is None and n < 64:
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            model.capture_res2s_graph(neg, lat, sig, cfg_scale, denoise_mask=mask, clean_latent=clean)
-            model.replay_res2s_graph()
-        torch.cuda.current_stream().wait_stream(side)
+        _capture_and_replay(lambda: model.capture_res2s_graph(neg, lat, sig, cfg_scale, denoise_mask=mask, clean_latent=clean),
+                            model.replay_res2s_graph)
     else:
         for i in range(n):
             final = sig[i + 1] <= 0.001 or sig[i + 1] == sig[i]
@@ -285,4 +358,4 @@ def res2s_denoise_loop(transformer, video_state: LatentState, sigmas, context: t
                 break
             if callback:
                 callback(i + 1, n)
-    return video_state.replace(latent=lat[None].to(video_state.latent.dtype))
+    return _with_latent(video_state, lat)

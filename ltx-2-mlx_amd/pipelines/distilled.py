@@ -15,14 +15,13 @@ from typing import Callable, List, Optional, Sequence, Union
 
 import torch
 
-from ..components import (DISTILLED_SIGMA_VALUES, STAGE_2_DISTILLED_SIGMA_VALUES, AudioPatchifier, EulerDiffusionStep,
-                          GaussianNoiser, VideoLatentPatchifier)
-from ..conditioning.tools import AudioLatentTools, VideoLatentTools
-from ..model.transformer import LTXModel, LTXModelType, Modality, X0Model
-from ..model.upscaler import SpatialUpscaler, upscale_latent
-from ..model.video_vae import SimpleVideoDecoder, TilingConfig, decode_latent, decode_tiled
-from ..types import AudioLatentShape, LatentState, VideoLatentShape, VideoPixelShape
-from .common import apply_conditionings, create_image_conditionings, joint_denoise_loop
+from ..components import DISTILLED_SIGMA_VALUES, STAGE_2_DISTILLED_SIGMA_VALUES, AudioPatchifier, EulerDiffusionStep, VideoLatentPatchifier
+from ..conditioning.tools import AudioLatentTools
+from ..model.transformer import LTXModel, X0Model
+from ..model.video_vae import SimpleVideoDecoder, TilingConfig
+from ..types import AudioLatentShape, LatentState, VideoPixelShape
+from .common import (as_x0model, auto_tiling_config, conditioned_initial_state, create_image_conditionings, decode_video, final_latent,
+                     joint_denoise_loop, seeded_noiser, stage_callback, upscale_latent_x2, video_tools_for)
 
 
 @dataclass
@@ -45,12 +44,7 @@ class DistilledConfig:
     use_hip_graph: bool = False    # MI355X addition: replay the captured step loop (uniform sigma only)
 
     def _get_tiling_config(self) -> Optional[TilingConfig]:
-        if self.tiling_config is not None:
-            return self.tiling_config
-        latent_frames = (self.num_frames - 1) // 8 + 1
-        if latent_frames * (self.height // 32) * (self.width // 32) > 4000:
-            return TilingConfig.default()
-        return None
+        return auto_tiling_config(self.tiling_config, self.num_frames, self.height, self.width)
 
     def __post_init__(self):
         if self.num_frames % 8 != 1:
@@ -62,9 +56,7 @@ class DistilledConfig:
 class DistilledPipeline:
     def __init__(self, transformer: Union[LTXModel, X0Model], video_encoder=None, video_decoder: Optional[SimpleVideoDecoder] = None,
                  spatial_upscaler: Optional[Callable] = None, audio_decoder=None, vocoder=None):
-        self.transformer = transformer if isinstance(transformer, X0Model) else X0Model(transformer)
-        inner = self.transformer.velocity_model
-        self.is_av_model = getattr(inner, "model_type", None) == LTXModelType.AudioVideo
+        self.transformer, self.is_av_model = as_x0model(transformer)
         self.audio_decoder = audio_decoder
         self.vocoder = vocoder
         self.video_encoder = video_encoder
@@ -72,9 +64,6 @@ class DistilledPipeline:
         self.spatial_upscaler = spatial_upscaler
         self.patchifier = VideoLatentPatchifier(patch_size=1)
         self.diffusion_step = EulerDiffusionStep()
-
-    def _create_video_tools(self, target_shape: VideoLatentShape, fps: float) -> VideoLatentTools:
-        return VideoLatentTools(patchifier=self.patchifier, target_shape=target_shape, fps=fps)
 
     def _create_audio_tools(self, target_shape: AudioLatentShape) -> AudioLatentTools:
         return AudioLatentTools(patchifier=AudioPatchifier(patch_size=1), target_shape=target_shape)
@@ -103,79 +92,52 @@ class DistilledPipeline:
         vocoder were given (the reference's _decode_audio, distilled.py:188-196), the (B, 8, T_a, 16) latent without them."""
         images = images or []
         dev = self.transformer.velocity_model.device
-        gen = torch.Generator(device=dev).manual_seed(config.seed)
-        noiser = GaussianNoiser(generator=gen)
+        noiser = seeded_noiser(dev, config.seed)
         audio_active = self.is_av_model and (config.use_internal_audio_branch or config.audio_enabled)
         if config.audio_enabled and not self.is_av_model:
             raise ValueError("audio_enabled needs an AudioVideo transformer")
         actx = audio_encoding.to(dev) if audio_encoding is not None else None
 
-        def audio_shape(pix: VideoPixelShape) -> AudioLatentShape:
+        def audio_shape(height: int, width: int) -> AudioLatentShape:
+            pix = VideoPixelShape(batch=1, frames=config.num_frames, height=height, width=width, fps=config.fps)
             return AudioLatentShape.from_video_pixel_shape(pix, channels=config.audio_vae_channels, mel_bins=config.audio_mel_bins,
                                                            sample_rate=config.audio_sample_rate, hop_length=config.audio_hop_length,
                                                            audio_latent_downsample_factor=config.audio_downsample_factor)
 
-        s1 = VideoPixelShape(batch=1, frames=config.num_frames, height=config.height // 2, width=config.width // 2, fps=config.fps)
-        shape1 = VideoLatentShape.from_pixel_shape(s1, latent_channels=128)
-        tools = self._create_video_tools(shape1, config.fps)
-        state = tools.create_initial_state(dtype=config.dtype, device=dev)
+        h1, w1 = config.height // 2, config.width // 2
+        tools = video_tools_for(self.patchifier, config.num_frames, h1, w1, config.fps)
         # image conditioning at stage-1 resolution: encoded latent replaces the tokens of its latent frame and
         # lowers their denoise mask (reference pipelines/distilled.py:326-333)
-        state = apply_conditionings(state, create_image_conditionings(images, self.video_encoder, s1.height, s1.width, config.dtype), tools)
+        state = conditioned_initial_state(tools, create_image_conditionings(images, self.video_encoder, h1, w1, config.dtype), config.dtype, dev)
         state = noiser(state, noise_scale=1.0, noise=initial_noise)
         astate, atools = None, None
         if audio_active:
-            atools = self._create_audio_tools(audio_shape(s1))
+            atools = self._create_audio_tools(audio_shape(h1, w1))
             astate = noiser(atools.create_initial_state(dtype=config.dtype, device=dev), noise_scale=1.0, noise=initial_audio_noise)
             astate = astate.replace(latent=self._channelwise_normalize_audio(astate.latent))
-        cb1 = (lambda s, t: callback("stage1", s, t)) if callback else None
-        state, astate = self._denoise_loop_av(state, astate, DISTILLED_SIGMA_VALUES, text_encoding.to(dev), actx, callback=cb1,
-                                              use_hip_graph=config.use_hip_graph)
-        state = tools.unpatchify(tools.clear_conditioning(state))
-        final_latent = state.latent
-        audio_latent = atools.unpatchify(atools.clear_conditioning(astate)).latent if astate is not None else None
+        state, astate = self._denoise_loop_av(state, astate, DISTILLED_SIGMA_VALUES, text_encoding.to(dev), actx,
+                                              callback=stage_callback(callback, "stage1"), use_hip_graph=config.use_hip_graph)
+        latent = final_latent(tools, state)
+        audio_latent = final_latent(atools, astate) if astate is not None else None
 
         if self.spatial_upscaler is not None:
-            # un_normalize -> upscaler -> normalize (reference pipelines/distilled.py:394-405); the statistics
-            # ship with the VAE weights, so the decoder serves when no encoder object is passed
-            # the encoder's statistics only when it actually carries loaded weights (an unloaded SimpleVideoEncoder holds the
-            # identity placeholder zeros / ones, which would silently mis-scale stage 2); else the decoder's
-            enc_stats = getattr(self.video_encoder, "per_channel_statistics", None)
-            if enc_stats is not None and not getattr(self.video_encoder, "_loaded", True):
-                enc_stats = None
-            stats = enc_stats or getattr(self.video_decoder, "per_channel_statistics", None)
-            if stats is None:
-                raise ValueError("spatial_upscaler needs per_channel_statistics (un_normalize/normalize) from the video VAE")
-            if isinstance(self.spatial_upscaler, SpatialUpscaler):
-                up = upscale_latent(final_latent, self.spatial_upscaler, stats.mean_of_means, stats.std_of_means)
-            else:
-                up = stats.normalize(self.spatial_upscaler(stats.un_normalize(final_latent)))
-            s2 = VideoPixelShape(batch=1, frames=config.num_frames, height=config.height, width=config.width, fps=config.fps)
-            tools2 = self._create_video_tools(VideoLatentShape.from_pixel_shape(s2, latent_channels=128), config.fps)
-            state2 = tools2.create_initial_state(dtype=config.dtype, initial_latent=up)
-            state2 = apply_conditionings(state2, create_image_conditionings(images, self.video_encoder, s2.height, s2.width, config.dtype), tools2)
+            up = upscale_latent_x2(latent, self.spatial_upscaler, self.video_encoder, self.video_decoder)
+            tools2 = video_tools_for(self.patchifier, config.num_frames, config.height, config.width, config.fps)
+            conds2 = create_image_conditionings(images, self.video_encoder, config.height, config.width, config.dtype)
+            state2 = conditioned_initial_state(tools2, conds2, config.dtype, dev, initial_latent=up)
             sigma0 = float(STAGE_2_DISTILLED_SIGMA_VALUES[0])
             state2 = noiser(state2, noise_scale=sigma0, noise=stage2_noise)
             astate2, atools2 = None, None
             if audio_active:        # no spatial upscaling for audio: stage 1's latent is re-noised (reference :441-458)
-                atools2 = self._create_audio_tools(audio_shape(s2))
+                atools2 = self._create_audio_tools(audio_shape(config.height, config.width))
                 astate2 = noiser(atools2.create_initial_state(dtype=config.dtype, initial_latent=audio_latent), noise_scale=sigma0)
-            cb2 = (lambda s, t: callback("stage2", s, t)) if callback else None
             state2, astate2 = self._denoise_loop_av(state2, astate2, STAGE_2_DISTILLED_SIGMA_VALUES, text_encoding.to(dev), actx,
-                                                    callback=cb2, use_hip_graph=config.use_hip_graph)
-            final_latent = tools2.unpatchify(tools2.clear_conditioning(state2)).latent
+                                                    callback=stage_callback(callback, "stage2"), use_hip_graph=config.use_hip_graph)
+            latent = final_latent(tools2, state2)
             if astate2 is not None:
-                audio_latent = atools2.unpatchify(atools2.clear_conditioning(astate2)).latent
+                audio_latent = final_latent(atools2, astate2)
 
-        if self.video_decoder is None:
-            video = final_latent
-        else:
-            tiling = config._get_tiling_config()
-            if tiling:
-                chunks = list(decode_tiled(final_latent, self.video_decoder, tiling))
-                video = torch.cat(chunks, dim=2) if len(chunks) > 1 else chunks[0]
-            else:
-                video = decode_latent(final_latent, self.video_decoder)
+        video = decode_video(latent, self.video_decoder, config._get_tiling_config())
         if config.audio_enabled and audio_latent is not None:
             audio = self._decode_audio(audio_latent)
             return video, (audio if audio is not None else audio_latent)

@@ -28,13 +28,11 @@ import torch
 from .. import kernels as K
 from ..components import DISTILLED_SIGMA_VALUES, STAGE_2_DISTILLED_SIGMA_VALUES, EulerDiffusionStep, GaussianNoiser, VideoLatentPatchifier
 from ..conditioning.keyframe import VideoConditionByKeyframeIndex
-from ..conditioning.tools import VideoLatentTools
 from ..loader.lora_loader import LoRAConfig
-from ..model.transformer import LTXModel, LTXModelType, X0Model
-from ..model.upscaler import SpatialUpscaler, upscale_latent
-from ..model.video_vae import SimpleVideoDecoder, TilingConfig, decode_latent, decode_tiled
-from ..types import VideoLatentShape, VideoPixelShape
-from .common import ImageCondition, apply_conditionings, create_image_conditionings, joint_denoise_loop
+from ..model.transformer import LTXModel, X0Model
+from ..model.video_vae import SimpleVideoDecoder, TilingConfig
+from .common import (ImageCondition, as_x0model, conditioned_initial_state, create_image_conditionings, decode_video, final_latent,
+                     joint_denoise_loop, seeded_noiser, stage_callback, upscale_latent_x2, video_tools_for)
 from .ti2vid_hq import fused_lora
 
 IMAGE_SUFFIXES = (".png", ".jpg", ".jpeg", ".bmp", ".webp", ".tif", ".tiff")
@@ -210,9 +208,8 @@ class ICLoraPipeline:
         """base_transformer_weights is accepted for the reference's signature and unused: fused_lora keeps the touched tensors aside itself
         and registers them again after stage 1.  save_video / save_dir (MI355X additions): the writer and the directory of the save_control
         sidecar (create_video_conditionings)."""
-        self.transformer = transformer if isinstance(transformer, X0Model) else X0Model(transformer)
+        self.transformer, self.is_av_model = as_x0model(transformer)
         self._velocity_model = self.transformer.velocity_model
-        self.is_av_model = getattr(self._velocity_model, "model_type", None) == LTXModelType.AudioVideo
         self.video_encoder = video_encoder
         self.video_decoder = video_decoder
         self.spatial_upscaler = spatial_upscaler
@@ -222,26 +219,6 @@ class ICLoraPipeline:
         self.patchifier = VideoLatentPatchifier(patch_size=1)
         self.diffusion_step = EulerDiffusionStep()
         self.token_counts: List[int] = []        # DiT tokens of each stage of the last call
-
-    def _create_video_tools(self, target_shape: VideoLatentShape, fps: float) -> VideoLatentTools:
-        return VideoLatentTools(patchifier=self.patchifier, target_shape=target_shape, fps=fps)
-
-    def _upscale(self, latent: torch.Tensor) -> torch.Tensor:
-        """un_normalize -> upscaler -> normalize (reference :674-682); the encoder's statistics when it carries loaded weights (an
-        unloaded encoder holds identity placeholders), else the decoder's."""
-        stats = getattr(self.video_encoder, "per_channel_statistics", None)
-        if stats is not None and not getattr(self.video_encoder, "_loaded", True):
-            stats = None
-        stats = stats or getattr(self.video_decoder, "per_channel_statistics", None)
-        if stats is None:
-            raise ValueError("spatial_upscaler needs per_channel_statistics (un_normalize/normalize) from the video VAE")
-        if isinstance(self.spatial_upscaler, SpatialUpscaler):
-            return upscale_latent(latent, self.spatial_upscaler, stats.mean_of_means, stats.std_of_means)
-        return stats.normalize(self.spatial_upscaler(stats.un_normalize(latent)))
-
-    def _tools(self, config: ICLoraConfig, height: int, width: int) -> VideoLatentTools:
-        pix = VideoPixelShape(batch=1, frames=config.num_frames, height=height, width=width, fps=config.fps)
-        return self._create_video_tools(VideoLatentShape.from_pixel_shape(pix, latent_channels=128), config.fps)
 
     def _loop(self, state, sigmas, ctx, callback, config):
         # no guidance (reference :503-558): the existing conditioned loop; an AudioVideo model runs through its video twin
@@ -256,39 +233,37 @@ class ICLoraPipeline:
         if len(self.lora_configs) > 1:               # before anything is encoded
             raise NotImplementedError("more than one IC-LoRA at a time is not built: fused_lora fuses one adapter")
         dev = self._velocity_model.device
-        noiser = noiser or GaussianNoiser(generator=torch.Generator(device=dev).manual_seed(config.seed))
+        noiser = noiser or seeded_noiser(dev, config.seed)
         h1, w1 = config.height // 2, config.width // 2
-        tools = self._tools(config, h1, w1)
+        tools = video_tools_for(self.patchifier, config.num_frames, h1, w1, config.fps)
         # image conditionings first, control conditionings after them (reference :635)
         conds = create_image_conditionings(images or [], self.video_encoder, h1, w1, config.dtype) + \
             create_video_conditionings(video_conditioning or [], self.video_encoder, h1, w1, config.num_frames, config.dtype,
                                        save_video=self.save_video, fps=config.fps, save_dir=self.save_dir)
-        state = apply_conditionings(tools.create_initial_state(dtype=config.dtype, device=dev), conds, tools)
+        state = conditioned_initial_state(tools, conds, config.dtype, dev)
         self.token_counts.append(int(state.latent.shape[1]))
         sigmas = [float(s) for s in DISTILLED_SIGMA_VALUES[: config.stage_1_steps + 1]]
         state = noiser(state, noise_scale=1.0, noise=initial_noise)
-        cb1 = (lambda s, t: callback("stage1_iclora", s, t)) if callback else None
         lora = self.lora_configs
         with fused_lora(self._velocity_model, lora[0] if lora else None):
-            state = self._loop(state, sigmas, text_encoding.to(dev), cb1, config)
-        return tools.unpatchify(tools.clear_conditioning(state)).latent
+            state = self._loop(state, sigmas, text_encoding.to(dev), stage_callback(callback, "stage1_iclora"), config)
+        return final_latent(tools, state)
 
     def stage2_latent(self, stage1: torch.Tensor, text_encoding: torch.Tensor, config: ICLoraConfig,
                       images: Optional[List[ImageCondition]] = None, callback=None, *, stage2_noise: Optional[torch.Tensor] = None,
                       noiser: Optional[GaussianNoiser] = None) -> torch.Tensor:
         """Stage 2 from a stage-1 latent: x2 upscale, the base weights, image conditionings only -> (1, 128, F, H/32, W/32)."""
         dev = self._velocity_model.device
-        noiser = noiser or GaussianNoiser(generator=torch.Generator(device=dev).manual_seed(config.seed))
-        tools = self._tools(config, config.height, config.width)
-        state = tools.create_initial_state(dtype=config.dtype, initial_latent=self._upscale(stage1))
-        state = apply_conditionings(state, create_image_conditionings(images or [], self.video_encoder, config.height, config.width, config.dtype),
-                                    tools)
+        noiser = noiser or seeded_noiser(dev, config.seed)
+        tools = video_tools_for(self.patchifier, config.num_frames, config.height, config.width, config.fps)
+        upscaled = upscale_latent_x2(stage1, self.spatial_upscaler, self.video_encoder, self.video_decoder)
+        conds = create_image_conditionings(images or [], self.video_encoder, config.height, config.width, config.dtype)
+        state = conditioned_initial_state(tools, conds, config.dtype, dev, initial_latent=upscaled)
         self.token_counts.append(int(state.latent.shape[1]))
         sig2 = [float(s) for s in STAGE_2_DISTILLED_SIGMA_VALUES[: config.stage_2_steps + 1]]
         state = noiser(state, noise_scale=sig2[0], noise=stage2_noise)
-        cb2 = (lambda s, t: callback("stage2_refine", s, t)) if callback else None
-        state = self._loop(state, sig2, text_encoding.to(dev), cb2, config)
-        return tools.unpatchify(tools.clear_conditioning(state)).latent
+        state = self._loop(state, sig2, text_encoding.to(dev), stage_callback(callback, "stage2_refine"), config)
+        return final_latent(tools, state)
 
     def denoise_latent(self, text_encoding: torch.Tensor, config: ICLoraConfig, images: Optional[List[ImageCondition]] = None,
                        video_conditioning: Optional[List[VideoCondition]] = None, callback: Optional[Callable[[str, int, int], None]] = None,
@@ -299,7 +274,7 @@ class ICLoraPipeline:
         if self.spatial_upscaler is None:
             raise ValueError("ICLoraPipeline requires spatial_upscaler to be provided")
         dev = self._velocity_model.device
-        noiser = GaussianNoiser(generator=torch.Generator(device=dev).manual_seed(config.seed))
+        noiser = seeded_noiser(dev, config.seed)
         self.token_counts = []
         latent = self.stage1_latent(text_encoding, config, images, video_conditioning, callback, initial_noise=initial_noise, noiser=noiser)
         return self.stage2_latent(latent, text_encoding, config, images, callback, stage2_noise=stage2_noise, noiser=noiser)
@@ -312,12 +287,7 @@ class ICLoraPipeline:
         passes context_mask=None (reference pipelines/common.py:223-232)."""
         latent = self.denoise_latent(text_encoding, config, images, video_conditioning, callback, initial_noise=initial_noise,
                                      stage2_noise=stage2_noise)
-        if self.video_decoder is None:
-            return latent
-        if config.tiling_config:
-            chunks = list(decode_tiled(latent, self.video_decoder, config.tiling_config))
-            return torch.cat(chunks, dim=2) if len(chunks) > 1 else chunks[0]
-        return decode_latent(latent, self.video_decoder)
+        return decode_video(latent, self.video_decoder, config.tiling_config)           # no automatic tiling here
 
 
 def create_ic_lora_pipeline(transformer, video_encoder, video_decoder, spatial_upscaler, base_transformer_weights=None,

@@ -16,14 +16,12 @@ from typing import Callable, List, Optional, Union
 
 import torch
 
-from ..components import STAGE_2_DISTILLED_SIGMA_VALUES, CFGGuider, EulerDiffusionStep, GaussianNoiser, LTX2Scheduler, VideoLatentPatchifier
+from ..components import STAGE_2_DISTILLED_SIGMA_VALUES, CFGGuider, EulerDiffusionStep, LTX2Scheduler, VideoLatentPatchifier
 from ..conditioning.keyframe import VideoConditionByKeyframeIndex
-from ..conditioning.tools import VideoLatentTools
 from ..model.transformer import LTXModel, X0Model
-from ..model.upscaler import SpatialUpscaler, upscale_latent
-from ..model.video_vae import SimpleVideoDecoder, TilingConfig, decode_latent, decode_tiled
-from ..types import VideoLatentShape, VideoPixelShape
-from .common import apply_conditionings, guided_denoise_loop
+from ..model.video_vae import SimpleVideoDecoder, TilingConfig
+from .common import (as_x0model, conditioned_initial_state, decode_video, final_latent, guided_denoise_loop, seeded_noiser, stage_callback,
+                     upscale_latent_x2, video_tools_for)
 
 
 @dataclass
@@ -94,7 +92,7 @@ def create_keyframe_conditionings(keyframes: List[Keyframe], video_encoder, heig
 class KeyframeInterpolationPipeline:
     def __init__(self, transformer: Union[LTXModel, X0Model], video_encoder, video_decoder: Optional[SimpleVideoDecoder],
                  spatial_upscaler: Optional[Callable] = None):
-        self.transformer = transformer if isinstance(transformer, X0Model) else X0Model(transformer)
+        self.transformer, _ = as_x0model(transformer)
         self.video_encoder = video_encoder
         self.video_decoder = video_decoder
         self.spatial_upscaler = spatial_upscaler
@@ -102,28 +100,10 @@ class KeyframeInterpolationPipeline:
         self.diffusion_step = EulerDiffusionStep()
         self.token_counts: List[int] = []        # DiT tokens of each stage of the last call: F*H*W + K*H*W
 
-    def _create_video_tools(self, target_shape: VideoLatentShape, fps: float) -> VideoLatentTools:
-        return VideoLatentTools(patchifier=self.patchifier, target_shape=target_shape, fps=fps)
-
-    def _upscale(self, latent: torch.Tensor) -> torch.Tensor:
-        """un_normalize -> upscaler -> normalize (reference :418-426); the encoder's statistics when it carries loaded weights (an
-        unloaded encoder holds identity placeholders), else the decoder's."""
-        stats = getattr(self.video_encoder, "per_channel_statistics", None)
-        if stats is not None and not getattr(self.video_encoder, "_loaded", True):
-            stats = None
-        stats = stats or getattr(self.video_decoder, "per_channel_statistics", None)
-        if stats is None:
-            raise ValueError("spatial_upscaler needs per_channel_statistics (un_normalize/normalize) from the video VAE")
-        if isinstance(self.spatial_upscaler, SpatialUpscaler):
-            return upscale_latent(latent, self.spatial_upscaler, stats.mean_of_means, stats.std_of_means)
-        return stats.normalize(self.spatial_upscaler(stats.un_normalize(latent)))
-
     def _stage_state(self, keyframes, config, height, width, dev, initial_latent=None):
-        pix = VideoPixelShape(batch=1, frames=config.num_frames, height=height, width=width, fps=config.fps)
-        tools = self._create_video_tools(VideoLatentShape.from_pixel_shape(pix, latent_channels=128), config.fps)
-        state = tools.create_initial_state(dtype=config.dtype, device=dev) if initial_latent is None else \
-            tools.create_initial_state(dtype=config.dtype, initial_latent=initial_latent)
-        state = apply_conditionings(state, create_keyframe_conditionings(keyframes, self.video_encoder, height, width, config.dtype), tools)
+        tools = video_tools_for(self.patchifier, config.num_frames, height, width, config.fps)
+        conds = create_keyframe_conditionings(keyframes, self.video_encoder, height, width, config.dtype)
+        state = conditioned_initial_state(tools, conds, config.dtype, dev, initial_latent)
         self.token_counts.append(int(state.latent.shape[1]))
         return tools, state
 
@@ -141,27 +121,27 @@ class KeyframeInterpolationPipeline:
         ctx = text_encoding.to(dev)
         # no negative prompt: zeros of the context's shape (reference :326-330, create_null_text_encoding)
         nctx = torch.zeros_like(ctx) if negative_text_encoding is None else negative_text_encoding.to(dev)
-        noiser = GaussianNoiser(generator=torch.Generator(device=dev).manual_seed(config.seed))
+        noiser = seeded_noiser(dev, config.seed)
         self.token_counts = []
 
         div = 2 if config.use_two_stage else 1
         tools, state = self._stage_state(keyframes, config, config.height // div, config.width // div, dev)
         sigmas = LTX2Scheduler().execute(steps=config.num_inference_steps)
         state = noiser(state, noise_scale=1.0, noise=initial_noise)
-        cb1 = (lambda s, t: callback("stage1", s, t)) if callback else None
-        state = guided_denoise_loop(self.transformer, state, sigmas, ctx, nctx, CFGGuider(config.cfg_scale), self.diffusion_step, cb1,
-                                    config.use_hip_graph)
-        latent = tools.unpatchify(tools.clear_conditioning(state)).latent
+        state = guided_denoise_loop(self.transformer, state, sigmas, ctx, nctx, CFGGuider(config.cfg_scale), self.diffusion_step,
+                                    stage_callback(callback, "stage1"), config.use_hip_graph)
+        latent = final_latent(tools, state)
         if not config.use_two_stage:
             return latent
 
-        tools2, state2 = self._stage_state(keyframes, config, config.height, config.width, dev, initial_latent=self._upscale(latent))
+        upscaled = upscale_latent_x2(latent, self.spatial_upscaler, self.video_encoder, self.video_decoder)
+        tools2, state2 = self._stage_state(keyframes, config, config.height, config.width, dev, initial_latent=upscaled)
         sig2 = [float(s) for s in STAGE_2_DISTILLED_SIGMA_VALUES[: config.stage_2_steps + 1]]
         state2 = noiser(state2, noise_scale=sig2[0], noise=stage2_noise)
-        cb2 = (lambda s, t: callback("stage2", s, t)) if callback else None
         # refinement without guidance (reference :475-486, CFGGuider(1.0)): the existing conditioned loop, captured
-        state2 = guided_denoise_loop(self.transformer, state2, sig2, ctx, None, CFGGuider(1.0), self.diffusion_step, cb2, config.use_hip_graph)
-        return tools2.unpatchify(tools2.clear_conditioning(state2)).latent
+        state2 = guided_denoise_loop(self.transformer, state2, sig2, ctx, None, CFGGuider(1.0), self.diffusion_step,
+                                     stage_callback(callback, "stage2"), config.use_hip_graph)
+        return final_latent(tools2, state2)
 
     def __call__(self, text_encoding: torch.Tensor, text_mask: Optional[torch.Tensor], keyframes: List[Keyframe],
                  config: KeyframeInterpolationConfig, negative_text_encoding: Optional[torch.Tensor] = None,
@@ -171,12 +151,7 @@ class KeyframeInterpolationPipeline:
         here passes context_mask=None (reference pipelines/common.py:223-232)."""
         latent = self.denoise_latent(text_encoding, keyframes, config, negative_text_encoding, callback, initial_noise=initial_noise,
                                      stage2_noise=stage2_noise)
-        if self.video_decoder is None:
-            return latent
-        if config.tiling_config:
-            chunks = list(decode_tiled(latent, self.video_decoder, config.tiling_config))
-            return torch.cat(chunks, dim=2) if len(chunks) > 1 else chunks[0]
-        return decode_latent(latent, self.video_decoder)
+        return decode_video(latent, self.video_decoder, config.tiling_config)           # no automatic tiling here
 
 
 def create_keyframe_pipeline(transformer, video_encoder, video_decoder, spatial_upscaler=None) -> KeyframeInterpolationPipeline:

@@ -22,13 +22,13 @@ from typing import Callable, List, Optional, Tuple, Union
 
 import torch
 
-from ..components import (AudioPatchifier, CFGGuider, CFGStarRescalingGuider, EulerDiffusionStep, GaussianNoiser, LTX2Scheduler,
-                          VideoLatentPatchifier)
-from ..conditioning.tools import AudioLatentTools, VideoLatentTools
-from ..model.transformer import LTXModel, LTXModelType, X0Model
-from ..model.video_vae import SimpleVideoDecoder, TilingConfig, decode_latent, decode_tiled
-from ..types import AudioLatentShape, LatentState, VideoLatentShape, VideoPixelShape
-from .common import ImageCondition, apply_conditionings, create_image_conditionings, joint_denoise_loop
+from ..components import AudioPatchifier, CFGGuider, CFGStarRescalingGuider, EulerDiffusionStep, LTX2Scheduler, VideoLatentPatchifier
+from ..conditioning.tools import AudioLatentTools
+from ..model.transformer import LTXModel, X0Model
+from ..model.video_vae import SimpleVideoDecoder, TilingConfig
+from ..types import AudioLatentShape, VideoPixelShape
+from .common import (ImageCondition, as_x0model, auto_tiling_config, conditioned_initial_state, create_image_conditionings, decode_video,
+                     final_latent, joint_denoise_loop, seeded_noiser, video_tools_for)
 
 
 @dataclass
@@ -56,12 +56,7 @@ class OneStageCFGConfig:
     use_hip_graph: bool = False     # MI355X addition: replay the captured step loop (uniform sigma, no callback)
 
     def _get_tiling_config(self) -> Optional[TilingConfig]:
-        if self.tiling_config is not None:
-            return self.tiling_config
-        latent_frames = (self.num_frames - 1) // 8 + 1
-        if latent_frames * (self.height // 32) * (self.width // 32) > 4000:
-            return TilingConfig.default()
-        return None
+        return auto_tiling_config(self.tiling_config, self.num_frames, self.height, self.width)
 
     def __post_init__(self):
         if self.num_frames % 8 != 1:
@@ -73,9 +68,7 @@ class OneStageCFGConfig:
 class OneStagePipeline:
     def __init__(self, transformer: Union[LTXModel, X0Model], video_encoder=None, video_decoder: Optional[SimpleVideoDecoder] = None,
                  audio_decoder=None, vocoder=None):
-        self.transformer = transformer if isinstance(transformer, X0Model) else X0Model(transformer)
-        inner = self.transformer.velocity_model
-        self.is_av_model = getattr(inner, "model_type", None) == LTXModelType.AudioVideo
+        self.transformer, self.is_av_model = as_x0model(transformer)
         self.video_encoder = video_encoder
         self.video_decoder = video_decoder
         self.audio_decoder = audio_decoder
@@ -84,9 +77,6 @@ class OneStagePipeline:
         self.audio_patchifier = AudioPatchifier(patch_size=1)
         self.diffusion_step = EulerDiffusionStep()
         self.scheduler = LTX2Scheduler()
-
-    def _create_video_tools(self, target_shape: VideoLatentShape, fps: float) -> VideoLatentTools:
-        return VideoLatentTools(patchifier=self.patchifier, target_shape=target_shape, fps=fps)
 
     def _create_audio_tools(self, target_shape: AudioLatentShape) -> AudioLatentTools:
         return AudioLatentTools(patchifier=self.audio_patchifier, target_shape=target_shape)
@@ -139,18 +129,16 @@ class OneStagePipeline:
         self._require_no_guidance(stg_scale, guider_override, ge_gamma, sampler, temporal_upscaler, cross_attn_scale)
 
         dev = self.transformer.velocity_model.device
-        noiser = GaussianNoiser(generator=torch.Generator(device=dev).manual_seed(config.seed))
-        pixel_shape = VideoPixelShape(batch=1, frames=config.num_frames, height=config.height, width=config.width, fps=config.fps)
-        latent_shape = VideoLatentShape.from_pixel_shape(pixel_shape, latent_channels=128)
-        video_tools = self._create_video_tools(latent_shape, config.fps)
+        noiser = seeded_noiser(dev, config.seed)
+        video_tools = video_tools_for(self.patchifier, config.num_frames, config.height, config.width, config.fps)
         conditionings = create_image_conditionings(images, self.video_encoder, config.height, config.width, config.dtype)
-        video_state = video_tools.create_initial_state(dtype=config.dtype, device=dev)
-        video_state = apply_conditionings(video_state, conditionings, video_tools)
+        video_state = conditioned_initial_state(video_tools, conditionings, config.dtype, dev)
         sigmas = self.scheduler.execute(steps=config.num_inference_steps)        # no latent: the MAX_SHIFT_ANCHOR schedule (one_stage.py:837)
         video_state = noiser(video_state, noise_scale=1.0, noise=initial_noise)
 
         audio_state, audio_tools = None, None
         if internal_audio_active:
+            pixel_shape = VideoPixelShape(batch=1, frames=config.num_frames, height=config.height, width=config.width, fps=config.fps)
             audio_shape = AudioLatentShape.from_video_pixel_shape(
                 pixel_shape, channels=config.audio_vae_channels, mel_bins=config.audio_mel_bins, sample_rate=config.audio_sample_rate,
                 hop_length=config.audio_hop_length, audio_latent_downsample_factor=config.audio_downsample_factor)
@@ -175,22 +163,12 @@ class OneStagePipeline:
                                                       negative_video_context=negative_encoding.to(dev) if need_cfg else None,
                                                       negative_audio_context=nactx, video_guider=video_guider, audio_guider=audio_guider)
 
-        video_state = video_tools.unpatchify(video_tools.clear_conditioning(video_state))
-        final_video_latent = video_state.latent
-        if self.video_decoder is None:
-            video = final_video_latent
-        else:
-            tiling = config._get_tiling_config()
-            if tiling:
-                chunks = list(decode_tiled(final_video_latent, self.video_decoder, tiling))
-                video = torch.cat(chunks, dim=2) if len(chunks) > 1 else chunks[0]
-            else:
-                video = decode_latent(final_video_latent, self.video_decoder)
+        video = decode_video(final_latent(video_tools, video_state), self.video_decoder, config._get_tiling_config())
         audio = None
         if initial_audio_latent is not None:
-            audio = audio_tools.unpatchify(audio_tools.clear_conditioning(audio_state)).latent          # the latent given, kept by every step
+            audio = final_latent(audio_tools, audio_state)          # the latent given, kept by every step
         elif config.audio_enabled and audio_state is not None:
-            audio = audio_tools.unpatchify(audio_tools.clear_conditioning(audio_state)).latent
+            audio = final_latent(audio_tools, audio_state)
             if self.audio_decoder is not None and self.vocoder is not None:
                 audio = self._decode_audio(audio)
         return video, audio

@@ -27,10 +27,10 @@ import torch
 from .. import kernels as K
 from ..components import DISTILLED_SIGMA_VALUES, CFGGuider, EulerDiffusionStep, LTX2Scheduler, VideoLatentPatchifier
 from ..conditioning.tools import VideoLatentTools
-from ..model.transformer import LTXModel, LTXModelType, X0Model
-from ..model.video_vae import SimpleVideoDecoder, TilingConfig, decode_latent, decode_tiled
+from ..model.transformer import LTXModel, X0Model
+from ..model.video_vae import SimpleVideoDecoder, TilingConfig
 from ..types import LatentState, VideoLatentShape, VideoPixelShape
-from .common import guided_denoise_loop, joint_denoise_loop
+from .common import as_x0model, decode_video, final_latent, guided_denoise_loop, joint_denoise_loop, stage_callback
 from .ic_lora import IMAGE_SUFFIXES, load_control_frames, load_control_signal_tensor
 
 
@@ -165,8 +165,7 @@ class RetakePipeline:
     def __init__(self, transformer: Union[LTXModel, X0Model], video_encoder, video_decoder: Optional[SimpleVideoDecoder], audio_decoder=None,
                  vocoder=None):
         """audio_decoder / vocoder are accepted for the reference's signature and unused (no audio retake)."""
-        self.transformer = transformer if isinstance(transformer, X0Model) else X0Model(transformer)
-        self.is_av_model = getattr(self.transformer.velocity_model, "model_type", None) == LTXModelType.AudioVideo
+        self.transformer, self.is_av_model = as_x0model(transformer)
         self.video_encoder = video_encoder
         self.video_decoder = video_decoder
         self.audio_decoder = audio_decoder
@@ -179,9 +178,6 @@ class RetakePipeline:
         self.frame_window: Optional[Tuple[int, int]] = None
         self.pixel_window: Optional[Tuple[int, int]] = None
         self.token_count: int = 0
-
-    def _create_video_tools(self, target_shape: VideoLatentShape, fps: float) -> VideoLatentTools:
-        return VideoLatentTools(patchifier=self.patchifier, target_shape=target_shape, fps=fps)
 
     def _load_source(self, video_path: Optional[str], frames, config: RetakeConfig) -> Tuple[torch.Tensor, float]:
         """-> (uint8 (8k+1, H, W, 3) on the encoder's device, fps).  The frame count is snapped down to 8k + 1 (reference :327); the size
@@ -234,14 +230,14 @@ class RetakePipeline:
         if tuple(initial_noise.shape) != (1, tokens, 128):
             raise ValueError(f"initial_noise must be (1, {tokens}, 128), got {tuple(initial_noise.shape)}")
         clean, mask, latent = K.retake_prepare(encoded, initial_noise[0].to(dev, torch.float32).contiguous(), f0, f1, noise_scale=1.0)
-        tools = self._create_video_tools(shape, fps)
+        tools = VideoLatentTools(patchifier=self.patchifier, target_shape=shape, fps=fps)      # the source's own size and frame rate
         positions = tools.create_initial_state(dtype=torch.float32, device=dev).positions
         state = LatentState(latent=latent[None].to(config.dtype), denoise_mask=mask[None, :, None], positions=positions,
                             clean_latent=clean[None].to(config.dtype))
         self.source_frames, self.fps, self.frame_window, self.pixel_window, self.token_count = src, fps, (f0, f1), (p0, p1), tokens
 
         ctx = text_encoding.to(dev)
-        cb = (lambda s, t: callback("retake", s, t)) if callback else None
+        cb = stage_callback(callback, "retake")
         if config.distilled:
             state = joint_denoise_loop(self.transformer, self.is_av_model, state, None, [float(s) for s in DISTILLED_SIGMA_VALUES], ctx, None,
                                        self.stepper, cb, config.use_hip_graph)[0]
@@ -251,7 +247,7 @@ class RetakePipeline:
             nctx = torch.zeros_like(ctx) if negative_text_encoding is None else negative_text_encoding.to(dev)
             guider = CFGGuider(config.cfg_scale if config.cfg_scale > 1.0 else 1.0)
             state = guided_denoise_loop(self.transformer, state, sigmas, ctx, nctx, guider, self.stepper, cb, config.use_hip_graph)
-        return tools.unpatchify(tools.clear_conditioning(state)).latent
+        return final_latent(tools, state)
 
     def __call__(self, video_path: Optional[str], text_encoding: torch.Tensor, text_mask: Optional[torch.Tensor], config: RetakeConfig,
                  negative_text_encoding: Optional[torch.Tensor] = None, audio_encoding: Optional[torch.Tensor] = None,
@@ -263,11 +259,7 @@ class RetakePipeline:
                                      initial_noise=initial_noise)
         if self.video_decoder is None:
             return latent
-        if config.tiling_config:
-            chunks = list(decode_tiled(latent, self.video_decoder, config.tiling_config))
-            video = torch.cat(chunks, dim=2) if len(chunks) > 1 else chunks[0]
-        else:
-            video = decode_latent(latent, self.video_decoder)
+        video = decode_video(latent, self.video_decoder, config.tiling_config)             # no automatic tiling here
         if video.dtype != torch.uint8:                                                     # decode_tiled: float (1, 3, T, H, W) in [-1, 1]
             video = K.video_to_uint8(video[0] if video.dim() == 5 else video)
         if config.composite_source:

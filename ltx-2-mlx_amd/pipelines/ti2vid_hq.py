@@ -20,13 +20,11 @@ from typing import Callable, Dict, List, Optional, Tuple, Union
 import torch
 
 from ..components import STAGE_2_DISTILLED_SIGMA_VALUES, EulerDiffusionStep, GaussianNoiser, LTX2Scheduler, VideoLatentPatchifier
-from ..conditioning.tools import VideoLatentTools
 from ..loader.lora_loader import LoRAConfig, find_lora_keys_for_weight, fuse_lora_into_weights
-from ..model.transformer import LTXModel, LTXModelType, X0Model
-from ..model.upscaler import SpatialUpscaler, upscale_latent
-from ..model.video_vae import SimpleVideoDecoder, TilingConfig, decode_latent, decode_tiled
-from ..types import VideoLatentShape, VideoPixelShape
-from .common import ImageCondition, apply_conditionings, create_image_conditionings, joint_denoise_loop, res2s_denoise_loop
+from ..model.transformer import LTXModel, X0Model
+from ..model.video_vae import SimpleVideoDecoder, TilingConfig
+from .common import (ImageCondition, as_x0model, auto_tiling_config, conditioned_initial_state, create_image_conditionings, decode_video,
+                     final_latent, joint_denoise_loop, res2s_denoise_loop, seeded_noiser, stage_callback, upscale_latent_x2, video_tools_for)
 
 
 @dataclass
@@ -55,12 +53,7 @@ class TI2VidHQConfig:
     use_hip_graph: bool = True      # MI355X addition: replay each stage's loop from one captured graph (no callback, < 64 steps)
 
     def _get_tiling_config(self) -> Optional[TilingConfig]:
-        if self.tiling_config is not None:
-            return self.tiling_config
-        latent_frames = (self.num_frames - 1) // 8 + 1
-        if latent_frames * (self.height // 32) * (self.width // 32) > 4000:
-            return TilingConfig.default()
-        return None
+        return auto_tiling_config(self.tiling_config, self.num_frames, self.height, self.width)
 
     def __post_init__(self):
         if self.num_frames % 8 != 1:
@@ -131,9 +124,8 @@ def fused_lora(model, lora_config: Optional[LoRAConfig], fuse: Callable = fuse_l
 class TI2VidHQPipeline:
     def __init__(self, transformer: Union[LTXModel, X0Model], video_encoder, video_decoder: Optional[SimpleVideoDecoder],
                  spatial_upscaler: Optional[Callable], audio_decoder=None, vocoder=None):
-        self.transformer = transformer if isinstance(transformer, X0Model) else X0Model(transformer)
+        self.transformer, self.is_av_model = as_x0model(transformer)
         self._velocity_model = self.transformer.velocity_model
-        self.is_av_model = getattr(self._velocity_model, "model_type", None) == LTXModelType.AudioVideo
         self.video_encoder = video_encoder
         self.video_decoder = video_decoder
         self.spatial_upscaler = spatial_upscaler
@@ -142,29 +134,6 @@ class TI2VidHQPipeline:
         self.patchifier = VideoLatentPatchifier(patch_size=1)
         self.euler_step = EulerDiffusionStep()
 
-    def _create_video_tools(self, target_shape: VideoLatentShape, fps: float) -> VideoLatentTools:
-        return VideoLatentTools(patchifier=self.patchifier, target_shape=target_shape, fps=fps)
-
-    def _upscale(self, latent: torch.Tensor) -> torch.Tensor:
-        """un_normalize -> upscaler -> normalize (reference :443-448); the encoder's statistics when it carries loaded weights (an
-        unloaded encoder holds identity placeholders), else the decoder's."""
-        stats = getattr(self.video_encoder, "per_channel_statistics", None)
-        if stats is not None and not getattr(self.video_encoder, "_loaded", True):
-            stats = None
-        stats = stats or getattr(self.video_decoder, "per_channel_statistics", None)
-        if stats is None:
-            raise ValueError("spatial_upscaler needs per_channel_statistics (un_normalize/normalize) from the video VAE")
-        if isinstance(self.spatial_upscaler, SpatialUpscaler):
-            return upscale_latent(latent, self.spatial_upscaler, stats.mean_of_means, stats.std_of_means)
-        return stats.normalize(self.spatial_upscaler(stats.un_normalize(latent)))
-
-    def _stage_state(self, images, config, height, width, dev, initial_latent=None):
-        pix = VideoPixelShape(batch=1, frames=config.num_frames, height=height, width=width, fps=config.fps)
-        tools = self._create_video_tools(VideoLatentShape.from_pixel_shape(pix, latent_channels=128), config.fps)
-        state = tools.create_initial_state(dtype=config.dtype, device=dev) if initial_latent is None else \
-            tools.create_initial_state(dtype=config.dtype, initial_latent=initial_latent)
-        return tools, apply_conditionings(state, create_image_conditionings(images, self.video_encoder, height, width, config.dtype), tools)
-
     def stage1_latent(self, positive_encoding: torch.Tensor, negative_encoding: Optional[torch.Tensor], config: TI2VidHQConfig,
                       images: Optional[List[ImageCondition]] = None, callback=None, *, initial_noise: Optional[torch.Tensor] = None,
                       noiser: Optional[GaussianNoiser] = None) -> torch.Tensor:
@@ -172,15 +141,17 @@ class TI2VidHQPipeline:
         if config.audio_enabled:
             raise NotImplementedError("TI2VidHQPipeline is video-only here: the joint audio branch of the res_2s loop is not built")
         dev = self._velocity_model.device
-        noiser = noiser or GaussianNoiser(generator=torch.Generator(device=dev).manual_seed(config.seed))
-        tools, state = self._stage_state(images or [], config, config.height // 2, config.width // 2, dev)
+        noiser = noiser or seeded_noiser(dev, config.seed)
+        h1, w1 = config.height // 2, config.width // 2
+        tools = video_tools_for(self.patchifier, config.num_frames, h1, w1, config.fps)
+        conds = create_image_conditionings(images or [], self.video_encoder, h1, w1, config.dtype)
+        state = conditioned_initial_state(tools, conds, config.dtype, dev)
         sigmas = LTX2Scheduler().execute(steps=config.num_inference_steps)
         state = noiser(state, noise_scale=1.0, noise=initial_noise)
-        cb1 = (lambda s, t: callback("stage1_res2s", s, t)) if callback else None
         nctx = None if negative_encoding is None else negative_encoding.to(dev)
         state = res2s_denoise_loop(self.transformer, state, sigmas, positive_encoding.to(dev), nctx, config.cfg_scale, config.audio_cfg_scale,
-                                   cb1, config.use_hip_graph)
-        return tools.unpatchify(tools.clear_conditioning(state)).latent
+                                   stage_callback(callback, "stage1_res2s"), config.use_hip_graph)
+        return final_latent(tools, state)
 
     def denoise_latent(self, positive_encoding: torch.Tensor, negative_encoding: Optional[torch.Tensor], config: TI2VidHQConfig,
                        images: Optional[List[ImageCondition]] = None, callback: Optional[Callable[[str, int, int], None]] = None,
@@ -192,20 +163,21 @@ class TI2VidHQPipeline:
         images = images or []
         dev = self._velocity_model.device
         ctx = positive_encoding.to(dev)
-        noiser = GaussianNoiser(generator=torch.Generator(device=dev).manual_seed(config.seed))
+        noiser = seeded_noiser(dev, config.seed)
         latent = self.stage1_latent(ctx, negative_encoding, config, images, callback, initial_noise=initial_noise, noiser=noiser)
 
-        upscaled = self._upscale(latent)
+        upscaled = upscale_latent_x2(latent, self.spatial_upscaler, self.video_encoder, self.video_decoder)
         with fused_lora(self._velocity_model, config.distilled_lora_config):
-            tools2, state2 = self._stage_state(images, config, config.height, config.width, dev, initial_latent=upscaled)
+            tools2 = video_tools_for(self.patchifier, config.num_frames, config.height, config.width, config.fps)
+            conds2 = create_image_conditionings(images, self.video_encoder, config.height, config.width, config.dtype)
+            state2 = conditioned_initial_state(tools2, conds2, config.dtype, dev, initial_latent=upscaled)
             sig2 = [float(s) for s in STAGE_2_DISTILLED_SIGMA_VALUES]
             state2 = noiser(state2, noise_scale=sig2[0], noise=stage2_noise)
-            cb2 = (lambda s, t: callback("stage2", s, t)) if callback else None
             # refinement without guidance (reference :321-358, :499-503): the existing conditioned loop, captured; no audio state, so an
             # AudioVideo model runs through its video twin
-            state2 = joint_denoise_loop(self.transformer, self.is_av_model, state2, None, sig2, ctx, None, self.euler_step, cb2,
-                                        config.use_hip_graph)[0]
-        return tools2.unpatchify(tools2.clear_conditioning(state2)).latent
+            state2 = joint_denoise_loop(self.transformer, self.is_av_model, state2, None, sig2, ctx, None, self.euler_step,
+                                        stage_callback(callback, "stage2"), config.use_hip_graph)[0]
+        return final_latent(tools2, state2)
 
     def __call__(self, positive_encoding: torch.Tensor, negative_encoding: Optional[torch.Tensor], config: TI2VidHQConfig,
                  images: Optional[List[ImageCondition]] = None, callback: Optional[Callable[[str, int, int], None]] = None,
@@ -215,13 +187,7 @@ class TI2VidHQPipeline:
         signature and unused: this pipeline is video-only."""
         latent = self.denoise_latent(positive_encoding, negative_encoding, config, images, callback, initial_noise=initial_noise,
                                      stage2_noise=stage2_noise)
-        if self.video_decoder is None:
-            return latent
-        tiling = config._get_tiling_config()
-        if tiling:
-            chunks = list(decode_tiled(latent, self.video_decoder, tiling))
-            return torch.cat(chunks, dim=2) if len(chunks) > 1 else chunks[0]
-        return decode_latent(latent, self.video_decoder)
+        return decode_video(latent, self.video_decoder, config._get_tiling_config())
 
 
 def create_ti2vid_hq_pipeline(transformer, video_encoder, video_decoder, spatial_upscaler, audio_decoder=None, vocoder=None) -> TI2VidHQPipeline:

@@ -268,9 +268,9 @@ def ltx23_checkpoint(tmp_path_factory):
 
 
 def _spies(monkeypatch, generate):
-    import ltx_2_mlx_amd.pipelines.one_stage as one_stage
+    import ltx_2_mlx_amd.pipelines.common as common          # the pipelines' one final decode (decode_video) lives there
     seen = {"loads": 0, "latents": [], "batches": []}
-    real_load, real_batch, real_decode = generate._load_gemma, generate.encode_av_gemma_batch, one_stage.decode_latent
+    real_load, real_batch, real_decode = generate._load_gemma, generate.encode_av_gemma_batch, common.decode_latent
 
     def spy_load(*a, **k):
         seen["loads"] += 1
@@ -286,7 +286,7 @@ def _spies(monkeypatch, generate):
         return real_decode(latent, *a, **k)
     monkeypatch.setattr(generate, "_load_gemma", spy_load)
     monkeypatch.setattr(generate, "encode_av_gemma_batch", spy_batch)
-    monkeypatch.setattr(one_stage, "decode_latent", spy_decode)
+    monkeypatch.setattr(common, "decode_latent", spy_decode)
     return seen
 
 
