@@ -183,7 +183,7 @@ def _note_eager_once(why: str) -> None:
         print(f"  note: hipGraph replay skipped, the sampling loop runs eagerly: {why}", file=sys.stderr)
 
 
-def _capture_and_replay(capture: Callable[[], None], replay: Callable[[], None]) -> None:
+def capture_and_replay(capture: Callable[[], None], replay: Callable[[], None]) -> None:
     """Capture a loop's graph on a side stream (capture needs a non-default one) and replay it there once, ordered after the work already
     queued on the current stream and before whatever follows."""
     side = torch.cuda.Stream()
@@ -260,7 +260,7 @@ def joint_denoise_loop(transformer, is_av_model: bool, video_state: LatentState,
             model.prepare(video_context, video_state.positions, per_token=not uniform, audio_context=audio_context, audio_positions=audio_state.positions)
         else:
             model.prepare(video_context, video_state.positions, per_token=not uniform)
-        _capture_and_replay(lambda: model.capture_denoise_graph(lat, sig, audio_latent=alat, **cond), model.replay_denoise_graph)
+        capture_and_replay(lambda: model.capture_denoise_graph(lat, sig, audio_latent=alat, **cond), model.replay_denoise_graph)
         return _with_latent(video_state, lat), (_with_latent(audio_state, alat) if joint else audio_state)
     for i in range(n):
         vm = modality_from_state(video_state, video_context, sig[i], uniform=unif[0])
@@ -309,7 +309,7 @@ def guided_denoise_loop(transformer, video_state: LatentState, sigmas, context: 
     model.prepare(context, video_state.positions, per_token=not uniform)
     neg.prepare(negative_context, video_state.positions, per_token=not uniform)
     if use_hip_graph and callback is None and n < 64:
-        _capture_and_replay(lambda: model.capture_guided_graph(neg, lat, sig, guider.scale, denoise_mask=mask, clean_latent=clean),
+        capture_and_replay(lambda: model.capture_guided_graph(neg, lat, sig, guider.scale, denoise_mask=mask, clean_latent=clean),
                             model.replay_guided_graph)
     else:
         for i in range(n):
@@ -345,7 +345,7 @@ def res2s_denoise_loop(transformer, video_state: LatentState, sigmas, context: t
     if guide:
         neg.prepare(negative_context, video_state.positions, per_token=not uniform)
     if use_hip_graph and callback is None and n < 64:
-        _capture_and_replay(lambda: model.capture_res2s_graph(neg, lat, sig, cfg_scale, denoise_mask=mask, clean_latent=clean),
+        capture_and_replay(lambda: model.capture_res2s_graph(neg, lat, sig, cfg_scale, denoise_mask=mask, clean_latent=clean),
                             model.replay_res2s_graph)
     else:
         for i in range(n):

@@ -7,12 +7,13 @@ standard single-stage distilled loop (reference :1764-1984) followed by `decode_
 Gemma-3 encodes the prompt on the GPU when `--gemma-path` holds its weights (model/text_encoder/gemma3.py; reference
 encode_with_gemma :340-486, encode_av_gemma_batch :511-640; an LTX-2.3 checkpoint gets the V2 text encoder, create_av_text_encoder_v2_from_checkpoint
 :548-551).  Out of this path (and rejected with a clear message): STG guidance,
-CFG in the video-only loop.
-`--pipeline distilled --spatial-upscaler-weights W` runs the two-stage DistilledPipeline; adding `--generate-audio` runs it on
-the AudioVideo transformer and saves the audio LATENT beside the frames; `--decode-audio` (the default when the checkpoint holds the
-audio VAE decoder and vocoder) also decodes it to `<output>.wav` and muxes it into the mp4 (reference save_video_with_audio).
-`--audio FILE` (with `--generate-audio` or an LTX-2.3 checkpoint) generates the video TO that audio: the audio VAE encoder's latent stays
-frozen in the joint loop, and the original audio is muxed into the mp4.
+CFG in the video-only loop, the dev model's `--pipeline two-stage`.
+`generate_video` resolves its arguments once (`_resolve_request`: every refusal, before a model is loaded), loads the text encoding, the transformer and the VAE decoder, and
+runs ONE route, each a function of its own: retake (`--retake CLIP`), keyframe (`--pipeline keyframe-interpolation --keyframe path:frame[:strength]`), hq (`--ti2vid-hq`), ic_lora
+(`--pipeline ic-lora --control-video V` and / or `--image`), two_stage (`--two-stage-distilled --spatial-upscaler-weights W`; with `--generate-audio` on the AudioVideo transformer), av
+(`--generate-audio` or an LTX-2.3 checkpoint: the audio LATENT is saved beside the frames; `--decode-audio`, the default when the checkpoint holds the audio VAE decoder and vocoder, also
+decodes it to `<output>.wav` and muxes it into the mp4, reference save_video_with_audio; `--audio FILE` generates the video TO that audio: the audio VAE encoder's latent stays frozen in
+the joint loop, and the original audio is muxed into the mp4) and standard (everything else: the video-only loop, then `--upscale-spatial` / `--upscale-temporal`).
 `save_video` keeps the reference's ffmpeg settings (frames piped as raw RGB; PNG frames when no ffmpeg binary exists).  `--lora` fuses an adapter into the checkpoint weights at load.  `--image` conditions latent frame 0 on an image through the VAE encoder (the reference
 routes that through its pipelines, scripts/generate.py:1711-1731).  Without Gemma weights, text embeddings come from `--embedding file.npz` (keys
 `embedding`, `attention_mask`, as the reference's `load_text_embedding` :730-750) or the reference's
@@ -23,6 +24,7 @@ import argparse
 import os
 import sys
 import time
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -32,7 +34,7 @@ sys.path.insert(0, ROOT)
 
 from ltx_2_mlx_amd.components import DISTILLED_SIGMA_VALUES, VideoLatentPatchifier, get_pixel_coords, get_sigma_schedule  # noqa: E402
 from ltx_2_mlx_amd.model.transformer import LTXModel, Modality, X0Model  # noqa: E402
-from ltx_2_mlx_amd.model.video_vae import SimpleVideoDecoder, TilingConfig, decode_latent, decode_tiled, load_vae_decoder_weights  # noqa: E402
+from ltx_2_mlx_amd.model.video_vae import SimpleVideoDecoder, TilingConfig, load_vae_decoder_weights  # noqa: E402
 from ltx_2_mlx_amd.model.video_vae_encoder import SimpleVideoEncoder, load_vae_encoder_weights  # noqa: E402
 from ltx_2_mlx_amd.types import SpatioTemporalScaleFactors, VideoLatentShape  # noqa: E402
 
@@ -151,15 +153,6 @@ def save_video(frames, output_path: str, fps=24, speed: float = 1.0, input_fps=N
     if result.returncode != 0:
         raise RuntimeError(f"FFmpeg failed: {result.stderr.decode(errors='replace')}")
     return output_path
-
-
-def load_text_embedding(path: str, device="cuda"):
-    z = np.load(path)
-    emb = torch.from_numpy(z["embedding"]).float()
-    if emb.dim() == 2:
-        emb = emb[None]
-    mask = torch.from_numpy(z["attention_mask"]).float() if "attention_mask" in z else torch.ones(emb.shape[:2])
-    return emb.to(device), mask.to(device)
 
 
 def encode_text_features(path: str, weights_path=None, device="cuda", seed: int = 0):
@@ -608,6 +601,677 @@ def _frames_from_video(video):
     return K.video_to_uint8(video[0] if video.dim() == 5 else video)
 
 
+def _batched(t):
+    """An encoding stored without its batch axis gets one."""
+    return t[None] if t.dim() == 2 else t
+
+
+# ---- request resolution: everything generate_video decides before a model is loaded ----
+
+# route -> (the arguments it is not combined with, in the order they are refused; the tail of the refusal)
+_ROUTE_EXCLUDES = {
+    "retake": (("generate_audio", "audio_path", "keyframes", "control_video", "image_path", "two_stage_distilled", "upscale_spatial",
+                "upscale_temporal", "fp8_resident", "pipeline_type"),
+               "with retake_video: RetakePipeline is video-only, conditions on its source clip alone and runs one stage at the source's own "
+               "size on dequantised weights"),
+    "keyframe": (("generate_audio", "audio_path", "two_stage_distilled", "upscale_temporal", "image_path"),
+                 "with keyframes: the keyframe interpolation pipeline is video-only, conditions on its keyframes alone and ends with its own "
+                 "x2 spatial stage"),
+    "hq": (("generate_audio", "audio_path", "two_stage_distilled", "upscale_temporal", "keyframes"),
+           "with pipeline_type='ti2vid-hq': TI2VidHQPipeline is video-only (the joint audio branch of the res_2s loop is not built), "
+           "conditions on image_path alone and ends with its own x2 spatial stage"),
+    "ic_lora": (("generate_audio", "audio_path", "two_stage_distilled", "upscale_temporal", "keyframes"),
+                "with pipeline_type='ic-lora': ICLoraPipeline is video-only, conditions on its control video and image_path alone and ends "
+                "with its own x2 spatial stage"),
+}
+# route -> the _OUT_OF_PATH_DEFAULTS arguments that route takes itself
+_ROUTE_OWNS = {"keyframe": ("keyframes",), "hq": ("distilled_lora", "keyframes"),
+               "ic_lora": ("control_video", "save_control", "keyframes", "ic_lora_weights")}
+
+
+def _refuse_combinations(r):
+    names, tail = _ROUTE_EXCLUDES[r.route]
+    for k in names:
+        if getattr(r, k) and (k, getattr(r, k)) != ("pipeline_type", "text-to-video"):
+            raise NotImplementedError(f"{k} {tail}")
+
+
+def _lora_config(r, path, strength, what):
+    """The LoRAConfig of a route's own adapter (None without one); fusion needs dequantised weights and the file."""
+    if not path:
+        return None
+    if r.fp8_resident:
+        raise NotImplementedError("LoRA fusion needs dequantised weights: drop fp8_resident")
+    if not os.path.exists(path):
+        raise FileNotFoundError(f"{what} not found: {path}")
+    from ltx_2_mlx_amd.loader.lora_loader import LoRAConfig
+    return LoRAConfig(path, strength)
+
+
+def _need_spatial_upscaler(r):
+    if not r.spatial_upscaler_weights:
+        raise ValueError(f"pipeline_type={r.pipeline_type!r} needs --spatial-upscaler-weights (its second stage runs at twice the resolution)")
+
+
+def _resolve_retake(r):
+    """The source clip decides height, width, num_frames and the rate; the window is checked against it."""
+    from ltx_2_mlx_amd.pipelines import RetakeConfig, TemporalRegionMask, end_of_clip, get_video_metadata
+    r.retake_video = str(r.retake_video)
+    # an array or a directory carries no frame rate: it plays at output_fps; a video file at its own
+    plays_at_output_fps = os.path.isdir(r.retake_video) or r.retake_video.lower().endswith((".npy", ".npz"))
+    r.retake_fps, src_frames, r.width, r.height = get_video_metadata(r.retake_video, float(r.output_fps) if plays_at_output_fps else None)
+    if src_frames < 1:
+        raise ValueError(f"Could not read any frames from {r.retake_video}")
+    r.num_frames = ((src_frames - 1) // 8) * 8 + 1
+    if r.height % 32 != 0 or r.width % 32 != 0:
+        raise ValueError(f"Source resolution ({r.width}x{r.height}) must be divisible by 32 (the source is not resized)")
+    r.retake_to_end = r.retake_end_time is None
+    if r.retake_to_end:
+        r.retake_end_time = end_of_clip(r.num_frames, r.retake_fps)        # not num_frames / fps: int(end * fps) must reach the last frame
+    RetakeConfig(start_time=r.retake_start_time, end_time=r.retake_end_time)          # its ValueError (start_time >= end_time)
+    latent_frames = (r.num_frames - 1) // 8 + 1
+    r.retake_window = TemporalRegionMask(r.retake_start_time, r.retake_end_time, r.retake_fps).frame_window(latent_frames)
+    if r.retake_window[0] >= r.retake_window[1]:
+        raise ValueError(f"the retake window {r.retake_start_time}s - {r.retake_end_time}s touches no frame of the source: it has "
+                         f"{r.num_frames} frames at {r.retake_fps:g} fps, {r.num_frames / r.retake_fps:.3f} s")
+
+
+def _resolve_keyframe(r):
+    from ltx_2_mlx_amd.pipelines import KeyframeInterpolationConfig
+    KeyframeInterpolationConfig(height=r.height, width=r.width, num_frames=r.num_frames)          # its ValueErrors (8k + 1 frames, multiples of 64)
+    r.parsed_keyframes = [parse_keyframe(k) for k in r.keyframes]
+    for kf in r.parsed_keyframes:
+        if not 0 <= kf.frame_index < r.num_frames:
+            raise ValueError(f"keyframe frame_index {kf.frame_index} is outside [0, {r.num_frames})")
+        if kf.image is None and not os.path.exists(kf.image_path):
+            raise FileNotFoundError(f"keyframe image not found: {kf.image_path}")
+
+
+def _resolve_hq(r):
+    _need_spatial_upscaler(r)
+    from ltx_2_mlx_amd.pipelines import TI2VidHQConfig
+    TI2VidHQConfig(height=r.height, width=r.width, num_frames=r.num_frames)          # its ValueErrors (8k + 1 frames, multiples of 64)
+    r.hq_lora = _lora_config(r, r.distilled_lora, r.distilled_lora_scale, "distilled LoRA")
+
+
+def _resolve_ic_lora(r):
+    _need_spatial_upscaler(r)
+    from ltx_2_mlx_amd.pipelines import ControlType, ICLoraConfig
+    ICLoraConfig(height=r.height, width=r.width, num_frames=r.num_frames)          # its ValueErrors (8k + 1 frames, multiples of 64)
+    ControlType(r.control_type)                                                      # ValueError for anything but "canny" / "raw"
+    if r.control_video and not os.path.exists(r.control_video):
+        raise FileNotFoundError(f"control video not found: {r.control_video}")
+    lora = _lora_config(r, r.ic_lora_weights, 1.0, "IC-LoRA weights")
+    r.ic_loras = [lora] if lora else []
+
+
+_RESOLVE_ROUTE = {"keyframe": _resolve_keyframe, "hq": _resolve_hq, "ic_lora": _resolve_ic_lora}
+
+
+def _resolve_request(kw: dict):
+    """generate_video's keywords -> the request: those keywords as attributes, overwritten where validation decides otherwise (a retake's height / width / num_frames / retake_end_time, the forced
+    and defaulted guidance scales, compute_dtype), plus `route` (the ONE of keyframe, hq, ic_lora, retake, two_stage, av, standard that runs) and what validation derives: retake_fps /
+    retake_to_end / retake_window, parsed_keyframes, hq_lora / ic_loras, cdt, need_cfg, gemma_encodes, encode_negative, have_ckpt / version / v2 / av, toy, output_dir, and negative_encoding /
+    negative_audio_encoding of the embedding file.  Loads no model and touches no GPU; every refusal is raised here, in a fixed order.  Returns None (after saying so) when Gemma is asked for and
+    its weights are missing."""
+    r = SimpleNamespace(**kw, retake_fps=None, retake_to_end=False, retake_window=None, parsed_keyframes=[], hq_lora=None, ic_loras=[])
+    if r.retake_video is not None:
+        r.route = "retake"
+    elif r.pipeline_type == "keyframe-interpolation" and bool(r.keyframes):
+        r.route = "keyframe"
+    elif r.pipeline_type == "ti2vid-hq":
+        r.route = "hq"
+    elif r.pipeline_type == "ic-lora" and bool(r.control_video or r.image_path):
+        r.route = "ic_lora"
+    else:
+        r.route = None                                                   # two_stage, av or standard: decided below, once the checkpoint is looked at
+    if r.route == "retake":                                              # its refusals win over every other one
+        _refuse_combinations(r)
+        _resolve_retake(r)
+    # Gemma encodes the prompt (and the negative prompt) when its weights are there and no pre-computed encoding is given
+    r.gemma_encodes = bool(r.use_gemma and not (r.embedding_path or r.text_features_path) and r.gemma_path and os.path.exists(r.gemma_path))
+    for k, default in _OUT_OF_PATH_DEFAULTS.items():
+        if k in _ROUTE_OWNS.get(r.route, ()) or (k == "negative_prompt" and r.gemma_encodes):
+            continue
+        v = (r.enhance_prompt_flag and r.use_gemma) if k == "enhance_prompt_flag" else getattr(r, k)
+        if v != default:
+            raise NotImplementedError(f"{k}={v!r} is outside the MI355X hot path (see DESIGN.md); leave it at its default {default!r}")
+    if r.pipeline_type not in _PIPELINES_KNOWN:
+        raise ValueError(f"unknown pipeline_type {r.pipeline_type!r}; the reference knows {_PIPELINES_KNOWN}")
+    if r.pipeline_type not in _PIPELINES_BUILT and r.route not in _RESOLVE_ROUTE:
+        raise NotImplementedError(f"pipeline_type={r.pipeline_type!r} is outside the MI355X hot path (see DESIGN.md): 'two-stage' is the dev "
+                                  "model's CFG stage 1 + distilled-LoRA stage 2; for the distilled two-stage DistilledPipeline pass "
+                                  "two_stage_distilled=True (--two-stage-distilled); 'keyframe-interpolation' is built and needs its "
+                                  "images: pass keyframes / --keyframe path:frame_index[:strength]; 'ic-lora' is built and needs its control "
+                                  "video and / or an image: pass control_video / --control-video (--image)")
+    if r.route in _RESOLVE_ROUTE:
+        _refuse_combinations(r)
+        _RESOLVE_ROUTE[r.route](r)
+    r.output_dir = os.path.dirname(r.output_path)
+    if r.output_dir:
+        os.makedirs(r.output_dir, exist_ok=True)          # reference :1000-1003
+    if r.num_frames % 8 != 1:
+        raise ValueError(f"num_frames must be 8*k + 1, got {r.num_frames}")
+    if r.height % 32 != 0 or r.width % 32 != 0:
+        raise ValueError(f"Resolution ({r.height}x{r.width}) must be divisible by 32")
+    # use_fp16=True (the reference's default, :1006): float16 operands on libltx2hip_f16.so; compute_dtype="bfloat16" (MI355X extra,
+    # --bf16) selects the bfloat16 build the headline benchmark runs.  Accumulation and the residual stream are fp32 in both.
+    if r.compute_dtype is None:
+        if not r.use_fp16:
+            raise NotImplementedError("use_fp16=False (fp32 compute): the MI355X path computes with float16 or bfloat16 operands, fp32 accumulation and an "
+                                      "fp32 residual stream")
+        r.compute_dtype = "float16"
+    if r.compute_dtype not in ("float16", "bfloat16"):
+        raise ValueError(f"compute_dtype={r.compute_dtype!r}: float16 or bfloat16")
+    r.cdt = torch.float16 if r.compute_dtype == "float16" else torch.bfloat16
+    # printed here, not by generate_video: it has always come before the notes and the refusals below
+    print(f"Compute dtype: {r.compute_dtype} operands / fp32 accumulate / fp32 residual stream")
+    if r.use_gemma and not (r.embedding_path or r.text_features_path):
+        if not os.path.exists(r.gemma_path):              # the reference prints this and returns (:1085-1092)
+            print(f"\n  ERROR: Gemma weights not found at {r.gemma_path}\n  Use use_gemma=False (--no-gemma) for dummy embeddings, or pass "
+                  f"embedding_path / text_features_path")
+            return None
+    if r.model_variant == "distilled" and r.cfg_scale > 1.2:
+        print(f"  WARNING: Distilled model requires CFG=1.0 (no guidance). You requested {r.cfg_scale}.\n  Forcing CFG=1.0 (reference :1207-1216).")
+        r.cfg_scale, r.guidance_rescale, r.audio_cfg_scale, r.rescale_scale = 1.0, 0.0, 1.0, 0.0
+    # Guidance scales are resolved BEFORE any model is loaded (ADVICE r3): the AudioVideo branch's defaults for a non-distilled variant are
+    # audio_cfg_scale 7.0 / rescale 0.7 (reference :1713-1716), i.e. guidance even at --cfg 1.0, and guidance needs negative encodings.
+    if r.audio_cfg_scale is None:
+        r.audio_cfg_scale = 1.0 if r.model_variant == "distilled" else 7.0
+    if r.rescale_scale is None:
+        r.rescale_scale = 0.0 if r.model_variant == "distilled" else 0.7
+    r.negative_encoding = r.negative_audio_encoding = None
+    if r.embedding_path and os.path.exists(r.embedding_path):
+        with np.load(r.embedding_path) as z:                # optional entries of the pre-computed embedding file: the negative prompt's encodings
+            if "negative_embedding" in z:
+                r.negative_encoding = _batched(torch.from_numpy(z["negative_embedding"]).float())
+            if "negative_audio_embedding" in z:
+                r.negative_audio_encoding = _batched(torch.from_numpy(z["negative_audio_embedding"]).float())
+    # reference :1073: V2.3 always uses the AV transformer and the dual text encodings; generate_audio asks for them
+    r.have_ckpt = bool(r.weights_path) and os.path.exists(r.weights_path)
+    r.version = r.model_version if r.model_version is not None else (detect_model_version(r.weights_path) if r.have_ckpt else "")
+    r.v2 = str(r.version).startswith("2.3")
+    r.av = bool(r.generate_audio or r.v2)
+    # the video-only loop of the reference guides only for cfg_scale > 1 (:1935); OneStagePipeline's guiders are enabled for any scale != 1
+    r.need_cfg = (r.cfg_scale != 1.0 or r.audio_cfg_scale != 1.0) if r.av else r.cfg_scale > 1.0
+    if r.audio_path:
+        if r.two_stage_distilled:
+            raise NotImplementedError("audio_path (--audio) with two_stage_distilled: DistilledPipeline with a given audio latent is not built")
+        if not r.av:
+            raise ValueError("audio_path (--audio) needs the AudioVideo branch: pass generate_audio=True (--generate-audio) or an LTX-2.3 checkpoint; "
+                             "the video-only transformer has no audio stream to condition on")
+        if not os.path.exists(r.audio_path):
+            raise FileNotFoundError(f"audio file not found: {r.audio_path}")
+    if r.upscale_temporal and (r.av or r.two_stage_distilled):
+        raise NotImplementedError("upscale_temporal with the " + ("AudioVideo pipeline (the reference's AV branch returns before its upscalers)" if r.av
+                                  else "two-stage DistilledPipeline (it returns before the post-denoise upscalers)"))
+    if r.route is not None:
+        r.need_cfg = False                  # guided by the pipeline itself (ic-lora: not at all); a missing negative encoding becomes zeros
+    if r.need_cfg and not r.av:
+        raise NotImplementedError(f"cfg_scale={r.cfg_scale}: classifier-free guidance is built in OneStagePipeline (the AudioVideo / LTX-2.3 branch); the "
+                                  "standard video-only loop of this script runs the distilled model's cfg = 1")
+    if r.need_cfg and not r.gemma_encodes and (r.negative_encoding is None or r.negative_audio_encoding is None):
+        raise NotImplementedError(f"cfg_scale={r.cfg_scale} / audio_cfg_scale={r.audio_cfg_scale}: classifier-free guidance needs the NEGATIVE prompt's encodings: "
+                                  "let Gemma encode the prompts (gemma_path), add `negative_embedding` and `negative_audio_embedding` arrays to the --embedding "
+                                  "file, or pass cfg_scale=1.0, audio_cfg_scale=1.0 (what --model-variant distilled does)")
+    if r.low_memory or r.fast_mode:
+        print("  low_memory / fast_mode: no effect here (weights and caches stay resident in HBM, the loop is one hipGraph)")
+    # the routes that guide themselves take Gemma's encoding of the negative prompt when they will guide (retake: the dev variant only)
+    r.encode_negative = r.cfg_scale != 1.0 and (r.route in ("keyframe", "hq") or (r.route == "retake" and r.model_variant != "distilled"))
+    r.toy = r.vae_base_channels is not None and r.vae_base_channels != 128        # debug-size VAE: matching debug-size upscaler / encoder
+    if r.route is None:
+        r.route = "two_stage" if r.two_stage_distilled else "av" if r.av else "standard"
+    return r
+
+
+# ---- the session: what the three load stages leave behind, and the pieces the routes share ----
+
+def _encode_text(r):
+    """[1/5] -> (text_encoding, text_audio_encoding or None, negative_encoding, negative_audio_encoding): the negatives are the embedding file's unless Gemma encodes the negative prompt."""
+    print("[1/5] text encoding")
+    weights = r.weights_path if r.have_ckpt else None
+    audio, negative, negative_audio = None, r.negative_encoding, r.negative_audio_encoding
+    if r.text_features_path:
+        text, _ = encode_text_features(r.text_features_path, weights, r.device, r.seed)
+    elif r.gemma_encodes and r.av:
+        # prompt AND negative prompt under one Gemma load (reference :1096-1116); Gemma is freed before the transformer loads.  LTX-2.3
+        # gets the V2 encoder: encodings at the transformer's own widths (num_heads * 128 video, num_heads * 64 audio)
+        results = encode_av_gemma_batch([r.prompt, r.negative_prompt or ""], r.gemma_path, weights, device=r.device, seed=r.seed,
+                                        model_version=r.version, num_heads=r.num_heads)
+        text, audio, _ = results[0]
+        negative, negative_audio, _ = results[1]
+        print("  Encoded both prompts with Gemma 3 (AudioVideo, single load)")
+    elif r.gemma_encodes:
+        text, _ = encode_with_gemma(r.prompt, r.gemma_path, weights, use_early_layers_only=r.early_layers_only, device=r.device, seed=r.seed)
+        print("  Encoded with Gemma 3")
+        if r.encode_negative:
+            negative, _ = encode_with_gemma(r.negative_prompt or "", r.gemma_path, weights, device=r.device, seed=r.seed)
+            print("  Encoded the negative prompt with Gemma 3")
+    elif r.embedding_path:
+        with np.load(r.embedding_path) as z:              # keys as the reference's load_text_embedding (:730-750), plus the audio encoding
+            text = _batched(torch.from_numpy(z["embedding"]).float()).to(r.device)
+            if r.av and "audio_embedding" in z:
+                audio = _batched(torch.from_numpy(z["audio_embedding"]).float().to(r.device))
+            elif r.av:
+                print("  WARNING: Pre-computed embeddings don't include audio encoding. Audio quality may be degraded.")
+    else:
+        # dummy encodings (reference :1129-1138).  LTX-2.3 has no caption projection: its contexts arrive at the transformer
+        # widths (4096 video / 2048 audio) -- the reference's 3840-wide dummy would not fit that model at all
+        text, _ = create_dummy_text_encoding(r.prompt, embed_dim=r.num_heads * 128 if r.v2 else 3840, device=r.device)
+        if r.v2:
+            audio, _ = create_dummy_text_encoding(r.prompt + " (audio)", embed_dim=r.num_heads * 64, device=r.device)
+        print("  Using DUMMY encoding (test mode - output will be random)")
+    if r.av and audio is None:
+        audio = text                                    # reference :1080-1081, :1131-1132
+    return text, audio, negative, negative_audio
+
+
+def _load_model(r, text_encoding):
+    """[2/5] -> the X0Model of the video-only or the AudioVideo transformer; None in placeholder mode."""
+    print("[2/5] transformer")
+    if r.use_placeholder:
+        print("  Skipping model load (placeholder mode)")
+        return None
+    if r.av:
+        return X0Model(load_av_transformer(r.weights_path, num_layers=r.num_layers, compute_dtype=r.cdt, use_fp8=r.use_fp8, low_memory=r.low_memory,
+                                           caption_channels=None if r.v2 else text_encoding.shape[-1], cross_attention_adaln=r.v2,
+                                           apply_gated_attention=r.v2, num_heads=r.num_heads, seed=r.seed, device=r.device,
+                                           lora_path=r.lora_path, lora_strength=r.lora_strength, fp8_compute=r.fp8_compute))
+    return X0Model(load_transformer(r.weights_path, num_layers=r.num_layers, compute_dtype=r.cdt, use_fp8=r.use_fp8, low_memory=r.low_memory,
+                                    fast_mode=r.fast_mode, num_heads=r.num_heads, caption_channels=text_encoding.shape[-1], seed=r.seed,
+                                    device=r.device, lora_path=r.lora_path, lora_strength=r.lora_strength, fp8_resident=r.fp8_resident,
+                                    fp8_compute=r.fp8_compute))
+
+
+def _load_vae_decoder(r):
+    """[3/5] -> the decoder; None with skip_vae."""
+    print("[3/5] VAE decoder")
+    if r.skip_vae:
+        print("  VAE decoder skipped by user")
+        return None
+    return create_vae_decoder(r.weights_path, r.device, r.seed + 1, r.use_placeholder, r.vae_base_channels, compute_dtype=r.cdt)
+
+
+def make_encoder(r):
+    enc = SimpleVideoEncoder(device=r.device)
+    if r.have_ckpt:
+        load_vae_encoder_weights(enc, r.weights_path)
+    else:
+        enc.init_random_weights(seed=r.seed + 2)
+    return enc
+
+
+def _load_or_random(r, kind, weights=None):
+    """The "spatial" or "temporal" x2 latent upscaler: from `weights` (the request's by default), or random-initialised for "random" and (with a warning) for a missing file, then with one block
+    per stage at the debug width a toy VAE asks for."""
+    import ltx_2_mlx_amd.model.upscaler as U
+    cls, load, width_name, width, blocks_name, seed, kw = {
+        "spatial": (U.SpatialUpscaler, U.load_spatial_upscaler_weights, "mid_channels", 1024, "num_blocks_per_stage", r.seed + 2, {}),
+        "temporal": (U.TemporalUpscaler, U.load_temporal_upscaler_weights, "hidden_channels", 512, "num_res_blocks", r.seed + 4,
+                     dict(checkpoint_semantics=r.temporal_upscaler_checkpoint_semantics))}[kind]
+    weights = weights or getattr(r, kind + "_upscaler_weights")
+    kw = dict(kw, device=r.device, **{width_name: 64 if r.toy else width})
+    if weights == "random" or not os.path.exists(str(weights)):
+        if weights != "random":
+            print(f"  Warning: Weights not found at {weights}, using random init")
+        up = cls(**kw, **{blocks_name: 4 if kw[width_name] == width else 1})
+        up.init_random_weights(seed=seed)
+    else:
+        up = cls(**kw)
+        load(up, weights)
+    return up
+
+
+# route -> (without a model, without a VAE decoder, what placeholder mode is told instead of the first, whether the decoder is asked for first)
+_REQUIRES = {
+    "keyframe": ("Keyframe interpolation pipeline requires a loaded model", "Keyframe interpolation pipeline requires VAE decoder",
+                 "  Keyframe interpolation requires model - cannot use placeholder mode", False),
+    "hq": ("TI2Vid HQ pipeline requires a loaded model", "TI2Vid HQ pipeline requires VAE decoder", None, False),
+    "ic_lora": ("IC-LoRA pipeline requires a loaded model", "IC-LoRA pipeline requires VAE decoder", None, False),
+    "retake": ("Retake pipeline requires a loaded model", "Retake pipeline requires VAE decoder", None, False),
+    "two_stage": ("Two-stage pipeline requires a loaded model (cannot use placeholder mode)",
+                  "the two-stage pipeline needs the VAE weights (per-channel statistics): drop --skip-vae", None, True),
+    "av": (None, "AV pipeline requires VAE decoder", "  AV pipeline requires model - cannot use placeholder mode", False),
+}
+
+
+def _require(r, s) -> bool:
+    """The route's pipeline needs the model and the decoder: ValueError without one.  False where placeholder mode is told so instead and
+    generate_video returns None."""
+    no_model, no_decoder, placeholder_note, decoder_first = _REQUIRES[r.route]
+    if decoder_first and s.vae_decoder is None:
+        raise ValueError(no_decoder)
+    if s.model is None:
+        if placeholder_note and (r.use_placeholder or no_model is None):
+            print(placeholder_note)
+            return False
+        raise ValueError(no_model)
+    if s.vae_decoder is None:
+        raise ValueError(no_decoder)
+    return True
+
+
+def _banners(r, upscaler: bool):
+    """The load stages a conditioned route adds: the VAE encoder (random-initialised without a checkpoint), the spatial upscaler."""
+    print("[3.5/5] VAE encoder")
+    if not r.have_ckpt:
+        print("  Warning: no checkpoint, the VAE encoder is random-initialised")
+    if upscaler:
+        print("[3.6/5] spatial upscaler")
+
+
+def _negative_or_zeros_note(guided: bool, negative) -> bool:
+    """Says that a guided run without a negative encoding gets zeros; True when it does."""
+    if guided and negative is None:
+        print("  Negative prompt: no encoding given, using zeros of the context's shape (the reference's null text encoding)")
+        return True
+    return False
+
+
+def _image_conditions(r):
+    """image_path as the frame-0 condition of the routes that take one through their pipeline."""
+    if not r.image_path:
+        return []
+    from ltx_2_mlx_amd.pipelines import ImageCondition
+    print(f"  Image conditioning: {r.image_path} (strength={r.image_strength})")
+    return [ImageCondition(image_path=r.image_path, frame_index=0, strength=r.image_strength)]
+
+
+def _tiling(r):
+    return TilingConfig.default() if r.tiled_vae else None
+
+
+def _timed_run(label, run, tokens_of=None):
+    """Runs a pipeline and reports its time -> (uint8 frames, audio latent or None).  tokens_of: the pipeline whose per-stage token counts close the line."""
+    t0 = time.time()
+    out = run()
+    video, audio_latent = out if isinstance(out, tuple) else (out, None)
+    frames = _frames_from_video(video)
+    torch.cuda.synchronize()
+    print(f"  {label}: {(time.time() - t0):.3f} s -> {tuple(frames.shape)}" + (f", DiT tokens per stage {tokens_of.token_counts}" if tokens_of else ""))
+    return frames, audio_latent
+
+
+def decode_audio_latent(r, s, audio_latent):
+    """the latent is always kept as <stem>_audio_latent.npz; with decoders it also becomes the waveform (a sidecar .wav)"""
+    np.savez(s.base + "_audio_latent.npz", latent=audio_latent.float().cpu().numpy())
+    decoders = create_audio_decoders(r.decode_audio, r.weights_path if r.have_ckpt else None, device=r.device, seed=r.seed + 3)
+    if decoders is None:
+        return None
+    t0 = time.time()
+    waveform = decoders[1](decoders[0](audio_latent))
+    torch.cuda.synchronize()
+    print(f"  audio decode: {(time.time() - t0):.3f} s -> {tuple(waveform.shape)} at {decoders[1].output_sample_rate} Hz")
+    return waveform, decoders[1].output_sample_rate
+
+
+def finish(r, s, frames, audio=None, source_fps=None):
+    """Writes <stem>.npz and the video file -> frames.  audio: (waveform, rate) to mux in.  source_fps: a retake is written at its source's rate: the frames enter ffmpeg at it and none is
+    interpolated."""
+    fps, input_fps = (r.output_fps, NATIVE_FPS) if source_fps is None else (source_fps, source_fps)
+    frames_np = frames.cpu().numpy()
+    np.savez_compressed(s.base + ".npz", frames=frames_np)
+    if audio is not None and r.save_mp4:
+        video_out, wav = save_video_with_audio(frames_np, audio[0], r.output_path, audio[1], fps=fps, speed=r.output_speed)      # never the retake route
+        print(f"  video: {video_out}, audio: {wav}")
+    elif audio is not None:
+        print(f"  audio: {write_wav(s.base + '.wav', audio[0], audio[1])}")
+    elif r.save_mp4:
+        print(f"  video: {save_video(frames_np, r.output_path, fps=fps, speed=r.output_speed, input_fps=input_fps)}")
+    print(f"Done in {time.time() - s.t_all:.1f} s: {s.base}.npz")
+    return frames
+
+
+# ---- one function per route: (request, session) -> what finish returns ----
+
+def _run_keyframe(r, s):
+    """pipeline_type="keyframe-interpolation" with keyframes (a list of 'path:frame_index[:strength]' strings, one per --keyframe) runs KeyframeInterpolationPipeline (reference :1552-1637): stage
+    1 at half resolution over num_steps with classifier-free guidance at cfg_scale (model_variant="distilled" forces 1), x2 spatial upscale, 3 refinement steps; the VAE encoder and the spatial
+    upscaler are loaded (random-initialised with a warning when the file is missing).  The negative encoding is Gemma's of `negative_prompt or ""` when Gemma encodes, else `negative_embedding` of
+    the --embedding file, else zeros.  Not combined with generate_audio, audio_path, two_stage_distilled, upscale_temporal or image_path.  Without keyframes the pipeline_type raises
+    NotImplementedError."""
+    print("\n=== Using Keyframe Interpolation Pipeline ===")
+    for kf in r.parsed_keyframes:
+        print(f"  Keyframe: {kf.image_path} at frame {kf.frame_index} (strength={kf.strength})")
+    if not _require(r, s):
+        return None
+    from ltx_2_mlx_amd.pipelines import KeyframeInterpolationConfig, KeyframeInterpolationPipeline
+    conf = KeyframeInterpolationConfig(height=r.height, width=r.width, num_frames=r.num_frames, seed=r.seed, fps=24.0, num_inference_steps=r.num_steps,
+                                       cfg_scale=r.cfg_scale, use_hip_graph=r.use_hip_graph, tiling_config=_tiling(r))
+    _banners(r, upscaler=True)
+    pipe = KeyframeInterpolationPipeline(s.model, make_encoder(r), s.vae_decoder, spatial_upscaler=_load_or_random(
+        r, "spatial", r.spatial_upscaler_weights or "weights/ltx-2/ltx-2-spatial-upscaler-x2-1.0.safetensors"))
+    _negative_or_zeros_note(conf.cfg_scale != 1.0, s.negative_encoding)
+    print(f"[5/5] Running keyframe interpolation ({r.num_steps} steps)...")
+    frames, _ = _timed_run("keyframe interpolation",
+                           lambda: pipe(s.text_encoding, None, r.parsed_keyframes, conf, negative_text_encoding=s.negative_encoding), tokens_of=pipe)
+    return finish(r, s, frames)
+
+
+def _run_hq(r, s):
+    """pipeline_type="ti2vid-hq" (--ti2vid-hq) runs TI2VidHQPipeline (reference pipelines/ti2vid_hq.py; its own CLI never reaches it): num_steps res_2s second-order steps at half resolution with
+    classifier-free guidance at cfg_scale, the x2 spatial upscale (spatial_upscaler_weights is required, "random" for a random-initialised one) and 3 distilled steps, under distilled_lora when
+    given. image_path sits at frame 0.  The negative encoding as for keyframes.  Not combined with generate_audio, audio_path, two_stage_distilled, upscale_temporal or keyframes, nor
+    distilled_lora with fp8_resident."""
+    images = _image_conditions(r)
+    print("\n=== Using TI2Vid HQ Pipeline (res_2s) ===")
+    _require(r, s)
+    from ltx_2_mlx_amd.pipelines import TI2VidHQConfig, TI2VidHQPipeline
+    conf = TI2VidHQConfig(height=r.height, width=r.width, num_frames=r.num_frames, seed=r.seed, num_inference_steps=r.num_steps,
+                          cfg_scale=r.cfg_scale, audio_cfg_scale=r.audio_cfg_scale, distilled_lora_config=r.hq_lora, use_hip_graph=r.use_hip_graph,
+                          tiling_config=_tiling(r))
+    _banners(r, upscaler=True)
+    pipe = TI2VidHQPipeline(s.model, make_encoder(r), s.vae_decoder, _load_or_random(r, "spatial"))
+    negative = s.negative_encoding
+    if _negative_or_zeros_note(r.cfg_scale > 1.0 or r.audio_cfg_scale > 1.0, negative):
+        negative = torch.zeros_like(s.text_encoding)
+    print(f"[5/5] Running TI2Vid HQ ({r.num_steps} res_2s steps at {r.width // 2}x{r.height // 2}, then 3 at {r.width}x{r.height})...")
+    frames, _ = _timed_run("ti2vid-hq", lambda: pipe(s.text_encoding, negative, conf, images=images))
+    return finish(r, s, frames)
+
+
+def _run_ic_lora(r, s):
+    """pipeline_type="ic-lora" with control_video and / or image_path runs ICLoraPipeline (reference :1434-1549): the control video (a .npy / .npz array of uint8 frames, a directory of image
+    frames, or a video file when an ffmpeg binary exists) is preprocessed on the device (control_type "canny": Canny edges between canny_low and canny_high, written with save_control to `<control
+    video's base name>_canny.mp4` in output_path's directory; "raw": as it is), encoded and appended to the sequence at control_strength; stage 1 runs num_steps distilled steps at half resolution
+    under ic_lora_weights (a LoRA file fused for that stage only), then the x2 spatial upscale and 3 refinement steps on the base weights; the image sits at frame 0 with image_strength.
+    spatial_upscaler_weights is required ("random" for a random-initialised one).  Not combined with generate_audio, audio_path, two_stage_distilled, upscale_temporal or keyframes, nor
+    ic_lora_weights with fp8_resident.  Without a control video and an image the pipeline_type raises NotImplementedError."""
+    images = _image_conditions(r)
+    print("\n=== Using IC-LoRA Pipeline ===")
+    _require(r, s)
+    from ltx_2_mlx_amd.pipelines import ControlType, ICLoraConfig, ICLoraPipeline, VideoCondition
+    conf = ICLoraConfig(height=r.height, width=r.width, num_frames=r.num_frames, seed=r.seed, fps=24.0, stage_1_steps=r.num_steps,
+                        use_hip_graph=r.use_hip_graph, tiling_config=_tiling(r))
+    videos = []
+    if r.control_video:
+        print(f"  Control video: {r.control_video} (type={r.control_type}, strength={r.control_strength})")
+        videos = [VideoCondition(video_path=r.control_video, strength=r.control_strength, control_type=ControlType(r.control_type),
+                                 canny_low=r.canny_low, canny_high=r.canny_high, save_control=r.save_control)]
+    if not r.ic_loras:
+        print("  Warning: no --ic-lora-weights, stage 1 runs on the base weights")
+    _banners(r, upscaler=True)
+    pipe = ICLoraPipeline(s.model, make_encoder(r), s.vae_decoder, _load_or_random(r, "spatial"), lora_configs=r.ic_loras, save_video=save_video,
+                          save_dir=r.output_dir or ".")
+    print(f"[5/5] Running IC-LoRA ({r.num_steps} steps at {r.width // 2}x{r.height // 2}, then {conf.stage_2_steps} at {r.width}x{r.height})...")
+    frames, _ = _timed_run("ic-lora", lambda: pipe(s.text_encoding, None, conf, images=images, video_conditioning=videos), tokens_of=pipe)
+    return finish(r, s, frames)
+
+
+def _run_retake(r, s):
+    """retake_video (keyword-only; RetakePipeline, reference pipelines/retake.py, which the reference's own CLI never reaches): the source clip (a .npy / .npz array of uint8 frames or a directory
+    of image frames, played at output_fps; a video file when ffmpeg and ffprobe exist, at its own frame rate) is kept and the seconds [retake_start_time, retake_end_time) of it are regenerated
+    from the prompt (retake_end_time None: to the end of the clip, taken as half a frame past its last one, since int(num_frames / fps * fps) can fall one frame short).  The output is written at
+    the source's rate: its frames enter ffmpeg at that rate and none is interpolated.  height, width and num_frames come from the source (frames snapped down to 8k + 1; the size must be divisible
+    by 32, nothing is resized).  model_variant="distilled" runs the 8 distilled steps without guidance, any other variant LTX2Scheduler over num_steps with classifier-free guidance at cfg_scale
+    (the negative encoding as for keyframes).  The window is widened to whole latent frames (8 pixel frames each; TemporalRegionMask); retake_composite puts the source's own frames back outside
+    it, with a 4-frame fade.  Not combined with generate_audio, audio_path, keyframes, control_video, image_path, two_stage_distilled, upscale_spatial, upscale_temporal, fp8_resident or another
+    pipeline_type."""
+    print("\n=== Using Retake Pipeline ===")
+    _require(r, s)
+    from ltx_2_mlx_amd.pipelines import RetakeConfig, RetakePipeline
+    distilled = r.model_variant == "distilled"
+    conf = RetakeConfig(start_time=r.retake_start_time, end_time=r.retake_end_time, distilled=distilled, num_inference_steps=r.num_steps,
+                        cfg_scale=r.cfg_scale, seed=r.seed, fps=r.retake_fps, use_hip_graph=r.use_hip_graph, composite_source=r.retake_composite,
+                        tiling_config=_tiling(r))
+    latent_frames = (r.num_frames - 1) // 8 + 1
+    print(f"  Source: {r.retake_video}, {r.width}x{r.height}, {r.num_frames} frames @ {r.retake_fps:g} FPS")
+    print(f"  Retake region: {r.retake_start_time:g}s - {'the end of the clip' if r.retake_to_end else f'{r.retake_end_time:g}s'} -> latent frames "
+          f"[{r.retake_window[0]}, {r.retake_window[1]}) of {latent_frames}, {latent_frames * (r.height // 32) * (r.width // 32)} DiT tokens"
+          + (", source frames kept outside it" if r.retake_composite else ""))
+    _banners(r, upscaler=False)
+    pipe = RetakePipeline(s.model, make_encoder(r), s.vae_decoder)
+    _negative_or_zeros_note(not distilled and r.cfg_scale > 1.0, s.negative_encoding)
+    print(f"[5/5] Running retake ({'8 distilled steps' if distilled else f'{r.num_steps} steps, cfg {r.cfg_scale}'})...")
+    frames, _ = _timed_run("retake", lambda: pipe(r.retake_video, s.text_encoding, None, conf, negative_text_encoding=s.negative_encoding))
+    return finish(r, s, frames, source_fps=r.retake_fps)
+
+
+def _run_two_stage(r, s):
+    """MI355X extra: two_stage_distilled=True runs the reference's DistilledPipeline class (pipelines/distilled.py:274-505), which the reference's own CLI never wires: 8 steps at half resolution,
+    x2 latent upscale, 3 steps at full resolution, image conditioning at both resolutions, auto-tiled decode; with generate_audio on the AudioVideo transformer, the audio latent saved and decoded
+    as in the av route."""
+    images = _image_conditions(r)
+    if not r.spatial_upscaler_weights:
+        raise ValueError("two_stage_distilled needs --spatial-upscaler-weights (two-stage pipeline)")
+    _require(r, s)
+    from ltx_2_mlx_amd.pipelines import DistilledConfig, DistilledPipeline
+    pipe = DistilledPipeline(s.model, make_encoder(r) if images else s.vae_decoder, s.vae_decoder, spatial_upscaler=_load_or_random(r, "spatial"))
+    conf = DistilledConfig(height=r.height, width=r.width, num_frames=r.num_frames, seed=r.seed, fps=24.0, use_hip_graph=r.use_hip_graph,
+                           audio_enabled=r.generate_audio, tiling_config=_tiling(r))
+    print("[4/5] two-stage distilled pipeline (8 steps at half resolution, x2 upscale, 3 steps)" + (" with the audio branch" if r.av else ""))
+    frames, audio_latent = _timed_run("two-stage", lambda: pipe(s.text_encoding, None, conf, images=images, audio_encoding=s.text_audio_encoding))
+    return finish(r, s, frames, audio=decode_audio_latent(r, s, audio_latent) if audio_latent is not None else None)
+
+
+def _run_av(r, s):
+    """The AudioVideo route (reference :1638-1776): generate_audio=True or an LTX-2.3 checkpoint (always) runs the AudioVideo transformer through OneStagePipeline (fps 25, LTX2Scheduler over
+    num_steps), guided for any cfg_scale / audio_cfg_scale != 1. The audio latent is always written to `<stem>_audio_latent.npz`; decode_audio (keyword-only) turns it into a waveform through
+    AudioDecoder + the checkpoint's vocoder (create_vocoder_for_checkpoint) and writes `<stem>.wav`, muxed into the mp4 when an ffmpeg binary exists.  None decodes when the checkpoint holds
+    `audio_vae.decoder.*` and `vocoder.*` tensors, True always (random-initialised decoders without them), False never. audio_path (keyword-only): the video is generated TO this audio file.  It is
+    loaded (audio_start_time / audio_max_duration trim), cut or right-padded with silence to num_frames / fps seconds, turned into a log-mel and encoded by AudioEncoder; the latent stays frozen
+    through the denoise loop (denoise_mask = 0, reference pipelines/a2vid_two_stage.py:338-357) and is written to `<stem>_audio_latent.npz`; the original audio, not a decode of the latent, is
+    muxed into the mp4 when an ffmpeg binary exists."""
+    images = _image_conditions(r)
+    print("\n=== Using Audio-Video Pipeline ===")
+    if not _require(r, s):
+        return None
+    if r.upscale_spatial:
+        raise NotImplementedError("upscale_spatial with the AudioVideo pipeline (the reference's AV branch returns before its upscalers)")
+    from ltx_2_mlx_amd.pipelines import OneStageCFGConfig, OneStagePipeline
+    av_pipeline = OneStagePipeline(transformer=s.model, video_encoder=make_encoder(r) if images else None, video_decoder=s.vae_decoder)
+    av_config = OneStageCFGConfig(
+        height=r.height, width=r.width, num_frames=r.num_frames, seed=r.seed,
+        fps=25.0,  # matches the upstream frame_rate for the audio latent shape (reference :1704-1712)
+        num_inference_steps=r.num_steps, cfg_scale=r.cfg_scale,
+        audio_cfg_scale=r.audio_cfg_scale, rescale_scale=r.rescale_scale,
+        audio_enabled=r.generate_audio, use_hip_graph=r.use_hip_graph, tiling_config=_tiling(r))
+    given_audio = None
+    if r.audio_path:
+        print(f"  Encoding audio: {r.audio_path}")
+        given_audio = encode_audio_for_video(r.audio_path, r.num_frames, av_config.fps, r.weights_path if r.have_ckpt else None, device=r.device,
+                                             seed=r.seed + 5, start_time=r.audio_start_time, max_duration=r.audio_max_duration)
+    print(f"[5/5] Running audio-video generation ({r.num_steps} steps)...")
+    frames, audio_latent = _timed_run("audio-video pipeline", lambda: av_pipeline(
+        positive_encoding=s.text_encoding, negative_encoding=s.negative_encoding if r.need_cfg else None, config=av_config, images=images,
+        positive_audio_encoding=s.text_audio_encoding, negative_audio_encoding=s.negative_audio_encoding if r.need_cfg else None,
+        initial_audio_latent=given_audio[0] if given_audio else None))
+    if given_audio:
+        # the frozen latent is kept; the ORIGINAL audio goes into the mp4 (the reference returns the original waveform, not a decode)
+        import shutil
+        np.savez(s.base + "_audio_latent.npz", latent=audio_latent.float().cpu().numpy())
+        wav = np.repeat(given_audio[1], 2, axis=0) if given_audio[1].shape[0] == 1 else given_audio[1]
+        return finish(r, s, frames, audio=(wav, given_audio[2]) if (r.save_mp4 and shutil.which("ffmpeg")) else None)
+    return finish(r, s, frames, audio=decode_audio_latent(r, s, audio_latent) if audio_latent is not None else None)
+
+
+def _run_standard(r, s):
+    """The standard route (one-stage, video-only; reference :1778-2095): the distilled sigma table (LTX2Scheduler for another variant) in one captured hipGraph, or eagerly with
+    use_hip_graph=False, with image_path as an encoded frame 0, or as noise arithmetic in placeholder mode. upscale_spatial doubles the denoised latent before decoding (2W x 2H output);
+    upscale_temporal doubles it in time (F -> 2F - 1 latent frames, after the spatial upscale when both are set; same output fps).  temporal_upscaler_checkpoint_semantics (keyword-only): False
+    computes what the reference's TemporalUpscaler computes, True what the upstream PyTorch model does (see model/upscaler.py; which one the released weights want is not verified).
+    `<stem>_latent.npz` holds the latent that is decoded; without a VAE decoder it is all there is."""
+    from ltx_2_mlx_amd.pipelines.common import capture_and_replay, decode_video
+    device, model, vae_decoder = r.device, s.model, s.vae_decoder
+    print("[4/5] latent noise")
+    lf, lh, lw = (r.num_frames - 1) // 8 + 1, r.height // 32, r.width // 32
+    g = torch.Generator(device=device).manual_seed(r.seed)
+    latent = torch.randn(1, 128, lf, lh, lw, generator=g, device=device)
+    sigmas = DISTILLED_SIGMA_VALUES[:r.num_steps + 1] if r.model_variant == "distilled" else \
+        [float(x) for x in get_sigma_schedule(r.num_steps, distilled=False, latent=latent)]
+    patchifier = VideoLatentPatchifier(patch_size=1)
+    shape = VideoLatentShape(1, 128, lf, lh, lw)
+    coords = patchifier.get_patch_grid_bounds(shape, device=device)
+    positions = get_pixel_coords(coords, SpatioTemporalScaleFactors.default(), causal_fix=True).float()
+    positions = torch.cat([positions[:, 0:1] / 24.0, positions[:, 1:]], dim=1)          # fps = 24 on the CLI path (:1823)
+    print(f"[5/5] denoising ({len(sigmas) - 1} steps)")
+    t0 = time.time()
+    tok = patchifier.patchify(latent).contiguous()
+    if r.use_placeholder:
+        for i in range(len(sigmas) - 1):
+            tok = tok + 0.1 * torch.randn_like(tok) * (sigmas[i + 1] - sigmas[i])
+    elif r.image_path:
+        # image-to-video: encoded image replaces latent frame 0, its tokens keep (1 - strength) of the noise level
+        from ltx_2_mlx_amd.conditioning import VideoLatentTools
+        from ltx_2_mlx_amd.components import EulerDiffusionStep, GaussianNoiser
+        from ltx_2_mlx_amd.pipelines import ImageCondition, apply_conditionings, create_image_conditionings, joint_denoise_loop
+        tools = VideoLatentTools(patchifier, shape, fps=24.0)
+        st = tools.create_initial_state(device=device)
+        st = apply_conditionings(st, create_image_conditionings([ImageCondition(r.image_path, 0, r.image_strength)], make_encoder(r), r.height, r.width), tools)
+        st = GaussianNoiser()(st, noise_scale=1.0, noise=tok)
+        st, _ = joint_denoise_loop(model, False, st, None, sigmas, s.text_encoding, None, EulerDiffusionStep(), None, r.use_hip_graph)
+        tok = st.latent
+    elif r.use_hip_graph:
+        vm = model.velocity_model
+        vm.prepare(s.text_encoding, positions)
+        lat2d = tok[0].float().contiguous()
+        capture_and_replay(lambda: vm.capture_denoise_graph(lat2d, sigmas), vm.replay_denoise_graph)
+        tok = lat2d[None]
+    else:
+        for i in range(len(sigmas) - 1):
+            m = Modality(latent=tok, context=s.text_encoding, context_mask=None,
+                         timesteps=torch.tensor([sigmas[i]], device=device), positions=positions, enabled=True)
+            tok = euler_step_x0(tok, model(m), sigmas[i], sigmas[i + 1])
+    torch.cuda.synchronize()
+    print(f"  denoise: {(time.time() - t0):.3f} s")
+    latent = patchifier.unpatchify(tok, shape)
+    np.savez(s.base + "_latent.npz", latent=latent.float().cpu().numpy())
+
+    def upscaled(latent, kind, upscale):
+        """Post-denoise x2 latent upscale (reference :2000-2077): un-normalise with the VAE statistics, upscale, re-normalise.  Without a
+        decoder there are no statistics: zeros / ones, with a warning.  The saved latent follows."""
+        print(f"\nApplying 2x {kind} upscaling...\n  Input latent: {tuple(latent.shape)}")
+        up = _load_or_random(r, kind)
+        if vae_decoder is not None:
+            stats = vae_decoder.per_channel_statistics
+            latent = upscale(latent, up, stats.mean_of_means, stats.std_of_means)
+        else:
+            print("  WARNING: No VAE decoder for normalization - output may have wrong range")
+            latent = upscale(latent, up, torch.zeros(128, device=device), torch.ones(128, device=device))
+        print(f"  Upscaled latent: {tuple(latent.shape)}")
+        np.savez(s.base + "_latent.npz", latent=latent.float().cpu().numpy())
+        return latent
+
+    import ltx_2_mlx_amd.model.upscaler as U
+    if r.upscale_spatial and r.spatial_upscaler_weights:          # the decoded video is 2W x 2H
+        latent = upscaled(latent, "spatial", U.upscale_latent)
+    if r.upscale_temporal and r.temporal_upscaler_weights:        # F latent frames become 2F - 1, decoded to 8 * (2F - 2) + 1 video frames saved at the unchanged output fps (:2140)
+        latent = upscaled(latent, "temporal", U.upscale_latent_temporal)
+    if vae_decoder is None:
+        print(f"Done in {time.time() - s.t_all:.1f} s: {s.base}_latent.npz")
+        return None
+    t0 = time.time()
+    frames = _frames_from_video(decode_video(latent, vae_decoder, _tiling(r)))
+    torch.cuda.synchronize()
+    print(f"  decode: {(time.time() - t0):.3f} s -> {tuple(frames.shape)}")
+    return finish(r, s, frames)
+
+
+# today's precedence, top to bottom; _resolve_request names the one that runs
+_ROUTES = {"keyframe": _run_keyframe, "hq": _run_hq, "ic_lora": _run_ic_lora, "retake": _run_retake, "two_stage": _run_two_stage,
+           "av": _run_av, "standard": _run_standard}
+
+
 def generate_video(
     prompt: str,
     height: int = 480,
@@ -692,629 +1356,23 @@ def generate_video(
     retake_end_time=None,
     retake_composite: bool = False,
 ):
-    """Generate video from a text prompt: denoise loop + VAE decode on MI355X behind the reference's signature.
-
-    Routing follows the reference (scripts/generate.py:1064-2095): an LTX-2.3 checkpoint (`model_version` 2.3.* in the
-    safetensors metadata) or generate_audio=True runs the AudioVideo transformer through OneStagePipeline (fps 25,
-    LTX2Scheduler over num_steps); everything else the standard video-only loop on the distilled sigma table; the VAE decoder is
-    built from the checkpoint's `config.vae` record; upscale_spatial doubles the denoised latent before decoding (2W x 2H output).
-    pipeline_type "two-stage" raises NotImplementedError, and so do "keyframe-interpolation" without keyframes and "ic-lora" without a
-    control video or an image.
-    pipeline_type="ic-lora" with control_video and / or image_path runs ICLoraPipeline (reference :1434-1549): the control video (a .npy / .npz
-    array of uint8 frames, a directory of image frames, or a video file when an ffmpeg binary exists) is preprocessed on the device
-    (control_type "canny": Canny edges between canny_low and canny_high, written with save_control to `<control video's base name>_canny.mp4`
-    in output_path's directory; "raw": as it is), encoded and appended to the sequence at control_strength; stage 1 runs num_steps distilled steps at half resolution under
-    ic_lora_weights (a LoRA file fused for that stage only), then the x2 spatial upscale and 3 refinement steps on the base weights; the
-    image sits at frame 0 with image_strength.  spatial_upscaler_weights is required ("random" for a random-initialised one).  Not combined
-    with generate_audio, audio_path, two_stage_distilled, upscale_temporal or keyframes, nor ic_lora_weights with fp8_resident.
-    pipeline_type="keyframe-interpolation" with keyframes (a list of 'path:frame_index[:strength]' strings, one per --keyframe) runs
-    KeyframeInterpolationPipeline (reference :1552-1637): stage 1 at half resolution over num_steps with classifier-free guidance at cfg_scale
-    (model_variant="distilled" forces 1), x2 spatial upscale, 3 refinement steps; the VAE encoder and the spatial upscaler are loaded
-    (random-initialised with a warning when the file is missing).  The negative encoding is Gemma's of `negative_prompt or ""` when Gemma
-    encodes, else `negative_embedding` of the --embedding file, else zeros.  Not combined with generate_audio, audio_path,
-    two_stage_distilled, upscale_temporal or image_path.
-    MI355X extras: two_stage_distilled=True runs the reference's DistilledPipeline class (8 steps at half resolution, x2
-    upscale, 3 steps; pipelines/distilled.py:274-505), which the reference's own CLI never wires; model_version="2.3" builds
-    the LTX-2.3 architecture without a checkpoint (random init, for tests and benchmarks); fp8_resident keeps fp8 checkpoint
-    weights as codes in HBM; fp8_compute runs the video stream's projections fp8 x fp8 on the fp8 MFMA (BASELINE config 3; per-token /
-    per-channel e4m3fn scales, not bit-identical to dequantise-at-load); vae_base_channels overrides the checkpoint's decoder_base_channels; compute_dtype="bfloat16" runs the
-    bfloat16 build instead of the reference's float16 default (use_fp16=True).
-    Audio (generate_audio / LTX-2.3): the audio latent is always written to `<stem>_audio_latent.npz`; decode_audio (keyword-only) turns
-    it into a waveform through AudioDecoder + the checkpoint's vocoder (create_vocoder_for_checkpoint) and writes `<stem>.wav`, muxed
-    into the mp4 when an ffmpeg binary exists.  None decodes when the checkpoint holds `audio_vae.decoder.*` and `vocoder.*` tensors,
-    True always (random-initialised decoders without them), False never.
-    upscale_temporal (video-only branch) doubles the denoised latent in time before decoding (F -> 2F - 1 latent frames, after the spatial
-    upscale when both are set; same output fps).  temporal_upscaler_checkpoint_semantics (keyword-only): False computes what the reference's
-    TemporalUpscaler computes, True what the upstream PyTorch model does (see model/upscaler.py; which one the released weights want is
-    not verified).
-    audio_path (keyword-only; AudioVideo branch: generate_audio=True or LTX-2.3): the video is generated TO this audio file.  It is
-    loaded (audio_start_time / audio_max_duration trim), cut or right-padded with silence to num_frames / fps seconds, turned into a log-mel
-    and encoded by AudioEncoder; the latent stays frozen through the denoise loop (denoise_mask = 0, reference
-    pipelines/a2vid_two_stage.py:338-357) and is written to `<stem>_audio_latent.npz`; the original audio, not a decode of the latent,
-    is muxed into the mp4 when an ffmpeg binary exists.
-    retake_video (keyword-only; RetakePipeline, reference pipelines/retake.py, which the reference's own CLI never reaches): the source clip
-    (a .npy / .npz array of uint8 frames or a directory of image frames, played at output_fps; a video file when ffmpeg and ffprobe exist, at
-    its own frame rate) is kept and the seconds [retake_start_time, retake_end_time) of it are regenerated from the prompt (retake_end_time
-    None: to the end of the clip, taken as half a frame past its last one, since int(num_frames / fps * fps) can fall one frame short).  The
-    output is written at the source's rate: its frames enter ffmpeg at that rate and none is interpolated.  height, width and num_frames come from the source (frames snapped down to 8k + 1; the size must be
-    divisible by 32, nothing is resized).  model_variant="distilled" runs the 8 distilled steps without guidance, any other variant
-    LTX2Scheduler over num_steps with classifier-free guidance at cfg_scale (the negative encoding as for keyframes).  The window is widened
-    to whole latent frames (8 pixel frames each; TemporalRegionMask); retake_composite puts the source's own frames back outside it, with a
-    4-frame fade.  Not combined with generate_audio, audio_path, keyframes, control_video, image_path, two_stage_distilled, upscale_spatial,
-    upscale_temporal, fp8_resident or another pipeline_type."""
-    retake_pipeline = retake_video is not None
-    retake_window = None
-    if retake_pipeline:                                                  # before any model is loaded
-        for k, v in dict(generate_audio=generate_audio, audio_path=audio_path, keyframes=keyframes, control_video=control_video,
-                         image_path=image_path, two_stage_distilled=two_stage_distilled, upscale_spatial=upscale_spatial,
-                         upscale_temporal=upscale_temporal, fp8_resident=fp8_resident,
-                         pipeline_type=None if pipeline_type == "text-to-video" else pipeline_type).items():
-            if v:
-                raise NotImplementedError(f"{k} with retake_video: RetakePipeline is video-only, conditions on its source clip alone and runs "
-                                          "one stage at the source's own size on dequantised weights")
-        from ltx_2_mlx_amd.pipelines import RetakeConfig, TemporalRegionMask, end_of_clip, get_video_metadata
-        retake_video = str(retake_video)
-        # an array or a directory carries no frame rate: it plays at output_fps; a video file at its own
-        retake_fps, src_frames, width, height = get_video_metadata(
-            retake_video, float(output_fps) if (os.path.isdir(retake_video) or retake_video.lower().endswith((".npy", ".npz"))) else None)
-        if src_frames < 1:
-            raise ValueError(f"Could not read any frames from {retake_video}")
-        num_frames = ((src_frames - 1) // 8) * 8 + 1
-        if height % 32 != 0 or width % 32 != 0:
-            raise ValueError(f"Source resolution ({width}x{height}) must be divisible by 32 (the source is not resized)")
-        retake_to_end = retake_end_time is None
-        if retake_to_end:
-            retake_end_time = end_of_clip(num_frames, retake_fps)        # not num_frames / fps: int(end * fps) must reach the last frame
-        RetakeConfig(start_time=retake_start_time, end_time=retake_end_time)          # its ValueError (start_time >= end_time)
-        latent_frames = (num_frames - 1) // 8 + 1
-        retake_window = TemporalRegionMask(retake_start_time, retake_end_time, retake_fps).frame_window(latent_frames)
-        if retake_window[0] >= retake_window[1]:
-            raise ValueError(f"the retake window {retake_start_time}s - {retake_end_time}s touches no frame of the source: it has "
-                             f"{num_frames} frames at {retake_fps:g} fps, {num_frames / retake_fps:.3f} s")
-    kf_pipeline = pipeline_type == "keyframe-interpolation" and bool(keyframes)
-    hq_pipeline = pipeline_type == "ti2vid-hq"
-    ic_pipeline = pipeline_type == "ic-lora" and bool(control_video or image_path)
-    given = dict(early_layers_only=early_layers_only,
-                 enhance_prompt_flag=enhance_prompt_flag and use_gemma, cross_attn_scale=cross_attn_scale, distilled_lora=None if hq_pipeline else distilled_lora,
-                 stg_scale=stg_scale, apg_scale=apg_scale, control_video=None if ic_pipeline else control_video,
-                 save_control=False if ic_pipeline else save_control, ge_gamma=ge_gamma,
-                 keyframes=None if (kf_pipeline or hq_pipeline or ic_pipeline) else keyframes, ic_lora_weights=None if ic_pipeline else ic_lora_weights)
-    # Gemma encodes the prompt (and the negative prompt) when its weights are there and no pre-computed encoding is given
-    gemma_encodes = bool(use_gemma and not (embedding_path or text_features_path) and gemma_path and os.path.exists(gemma_path))
-    if negative_prompt is not None and not gemma_encodes:
-        given["negative_prompt"] = negative_prompt
-    for k, v in given.items():
-        if v != _OUT_OF_PATH_DEFAULTS[k]:
-            raise NotImplementedError(f"{k}={v!r} is outside the MI355X hot path (see DESIGN.md); leave it at its default {_OUT_OF_PATH_DEFAULTS[k]!r}")
-    if pipeline_type not in _PIPELINES_KNOWN:
-        raise ValueError(f"unknown pipeline_type {pipeline_type!r}; the reference knows {_PIPELINES_KNOWN}")
-    if pipeline_type not in _PIPELINES_BUILT and not kf_pipeline and not hq_pipeline and not ic_pipeline:
-        raise NotImplementedError(f"pipeline_type={pipeline_type!r} is outside the MI355X hot path (see DESIGN.md): 'two-stage' is the dev "
-                                  "model's CFG stage 1 + distilled-LoRA stage 2; for the distilled two-stage DistilledPipeline pass "
-                                  "two_stage_distilled=True (--two-stage-distilled); 'keyframe-interpolation' is built and needs its "
-                                  "images: pass keyframes / --keyframe path:frame_index[:strength]; 'ic-lora' is built and needs its control "
-                                  "video and / or an image: pass control_video / --control-video (--image)")
-    parsed_keyframes = []
-    if kf_pipeline:                                                      # before any model is loaded
-        for k, v in dict(generate_audio=generate_audio, audio_path=audio_path, two_stage_distilled=two_stage_distilled,
-                         upscale_temporal=upscale_temporal, image_path=image_path).items():
-            if v:
-                raise NotImplementedError(f"{k} with keyframes: the keyframe interpolation pipeline is video-only, conditions on its keyframes "
-                                          "alone and ends with its own x2 spatial stage")
-        from ltx_2_mlx_amd.pipelines import KeyframeInterpolationConfig
-        KeyframeInterpolationConfig(height=height, width=width, num_frames=num_frames)          # its ValueErrors (8k + 1 frames, multiples of 64)
-        parsed_keyframes = [parse_keyframe(k) for k in keyframes]
-        for kf in parsed_keyframes:
-            if not 0 <= kf.frame_index < num_frames:
-                raise ValueError(f"keyframe frame_index {kf.frame_index} is outside [0, {num_frames})")
-            if kf.image is None and not os.path.exists(kf.image_path):
-                raise FileNotFoundError(f"keyframe image not found: {kf.image_path}")
-    hq_lora = None
-    if hq_pipeline:                                                      # before any model is loaded
-        for k, v in dict(generate_audio=generate_audio, audio_path=audio_path, two_stage_distilled=two_stage_distilled,
-                         upscale_temporal=upscale_temporal, keyframes=keyframes).items():
-            if v:
-                raise NotImplementedError(f"{k} with pipeline_type='ti2vid-hq': TI2VidHQPipeline is video-only (the joint audio branch of the "
-                                          "res_2s loop is not built), conditions on image_path alone and ends with its own x2 spatial stage")
-        if not spatial_upscaler_weights:
-            raise ValueError("pipeline_type='ti2vid-hq' needs --spatial-upscaler-weights (its second stage runs at twice the resolution)")
-        from ltx_2_mlx_amd.pipelines import TI2VidHQConfig
-        TI2VidHQConfig(height=height, width=width, num_frames=num_frames)          # its ValueErrors (8k + 1 frames, multiples of 64)
-        if distilled_lora:
-            if fp8_resident:
-                raise NotImplementedError("LoRA fusion needs dequantised weights: drop fp8_resident")
-            if not os.path.exists(distilled_lora):
-                raise FileNotFoundError(f"distilled LoRA not found: {distilled_lora}")
-            from ltx_2_mlx_amd.loader.lora_loader import LoRAConfig
-            hq_lora = LoRAConfig(distilled_lora, distilled_lora_scale)
-    ic_loras = []
-    if ic_pipeline:                                                      # before any model is loaded
-        for k, v in dict(generate_audio=generate_audio, audio_path=audio_path, two_stage_distilled=two_stage_distilled,
-                         upscale_temporal=upscale_temporal, keyframes=keyframes).items():
-            if v:
-                raise NotImplementedError(f"{k} with pipeline_type='ic-lora': ICLoraPipeline is video-only, conditions on its control video and "
-                                          "image_path alone and ends with its own x2 spatial stage")
-        if not spatial_upscaler_weights:
-            raise ValueError("pipeline_type='ic-lora' needs --spatial-upscaler-weights (its second stage runs at twice the resolution)")
-        from ltx_2_mlx_amd.pipelines import ControlType, ICLoraConfig
-        ICLoraConfig(height=height, width=width, num_frames=num_frames)          # its ValueErrors (8k + 1 frames, multiples of 64)
-        ControlType(control_type)                                                # ValueError for anything but "canny" / "raw"
-        if control_video and not os.path.exists(control_video):
-            raise FileNotFoundError(f"control video not found: {control_video}")
-        if ic_lora_weights:
-            if fp8_resident:
-                raise NotImplementedError("LoRA fusion needs dequantised weights: drop fp8_resident")
-            if not os.path.exists(ic_lora_weights):
-                raise FileNotFoundError(f"IC-LoRA weights not found: {ic_lora_weights}")
-            from ltx_2_mlx_amd.loader.lora_loader import LoRAConfig
-            ic_loras = [LoRAConfig(ic_lora_weights, 1.0)]
-    output_dir = os.path.dirname(output_path)
-    if output_dir:
-        os.makedirs(output_dir, exist_ok=True)          # reference :1000-1003
-    if num_frames % 8 != 1:
-        raise ValueError(f"num_frames must be 8*k + 1, got {num_frames}")
-    if height % 32 != 0 or width % 32 != 0:
-        raise ValueError(f"Resolution ({height}x{width}) must be divisible by 32")
-    # use_fp16=True (the reference's default, :1006): float16 operands on libltx2hip_f16.so; compute_dtype="bfloat16" (MI355X extra,
-    # --bf16) selects the bfloat16 build the headline benchmark runs.  Accumulation and the residual stream are fp32 in both.
-    if compute_dtype is None:
-        if not use_fp16:
-            raise NotImplementedError("use_fp16=False (fp32 compute): the MI355X path computes with float16 or bfloat16 operands, fp32 accumulation and an "
-                                      "fp32 residual stream")
-        compute_dtype = "float16"
-    if compute_dtype not in ("float16", "bfloat16"):
-        raise ValueError(f"compute_dtype={compute_dtype!r}: float16 or bfloat16")
-    cdt = torch.float16 if compute_dtype == "float16" else torch.bfloat16
-    print(f"Compute dtype: {compute_dtype} operands / fp32 accumulate / fp32 residual stream")
-    if use_gemma and not (embedding_path or text_features_path):
-        if not os.path.exists(gemma_path):              # the reference prints this and returns (:1085-1092)
-            print(f"\n  ERROR: Gemma weights not found at {gemma_path}\n  Use use_gemma=False (--no-gemma) for dummy embeddings, or pass "
-                  f"embedding_path / text_features_path")
-            return None
-    if model_variant == "distilled" and cfg_scale > 1.2:
-        print(f"  WARNING: Distilled model requires CFG=1.0 (no guidance). You requested {cfg_scale}.\n  Forcing CFG=1.0 (reference :1207-1216).")
-        cfg_scale, guidance_rescale, audio_cfg_scale, rescale_scale = 1.0, 0.0, 1.0, 0.0
-    # Guidance scales are resolved BEFORE any model is loaded (ADVICE r3): the AudioVideo branch's defaults for a non-distilled variant are
-    # audio_cfg_scale 7.0 / rescale 0.7 (reference :1713-1716), i.e. guidance even at --cfg 1.0, and guidance needs negative encodings.
-    if audio_cfg_scale is None:
-        audio_cfg_scale = 1.0 if model_variant == "distilled" else 7.0
-    if rescale_scale is None:
-        rescale_scale = 0.0 if model_variant == "distilled" else 0.7
-    negative_encoding = negative_audio_encoding = None
-    if embedding_path and os.path.exists(embedding_path):
-        with np.load(embedding_path) as z:                # optional entries of the pre-computed embedding file: the negative prompt's encodings
-            if "negative_embedding" in z:
-                negative_encoding = torch.from_numpy(z["negative_embedding"]).float()
-                negative_encoding = negative_encoding[None] if negative_encoding.dim() == 2 else negative_encoding
-            if "negative_audio_embedding" in z:
-                negative_audio_encoding = torch.from_numpy(z["negative_audio_embedding"]).float()
-                negative_audio_encoding = negative_audio_encoding[None] if negative_audio_encoding.dim() == 2 else negative_audio_encoding
-    _av_branch = generate_audio or str(model_version or "").startswith("2.3") or \
-        (bool(weights_path) and os.path.exists(weights_path) and model_version is None and detect_model_version(weights_path).startswith("2.3"))
-    # the video-only loop of the reference guides only for cfg_scale > 1 (:1935); OneStagePipeline's guiders are enabled for any scale != 1
-    _need_cfg = (cfg_scale != 1.0 or audio_cfg_scale != 1.0) if _av_branch else cfg_scale > 1.0
-    if audio_path:                                                       # before any model is loaded
-        if two_stage_distilled:
-            raise NotImplementedError("audio_path (--audio) with two_stage_distilled: DistilledPipeline with a given audio latent is not built")
-        if not _av_branch:
-            raise ValueError("audio_path (--audio) needs the AudioVideo branch: pass generate_audio=True (--generate-audio) or an LTX-2.3 checkpoint; "
-                             "the video-only transformer has no audio stream to condition on")
-        if not os.path.exists(audio_path):
-            raise FileNotFoundError(f"audio file not found: {audio_path}")
-    if upscale_temporal and (_av_branch or two_stage_distilled):         # before any model is loaded
-        raise NotImplementedError("upscale_temporal with the " + ("AudioVideo pipeline (the reference's AV branch returns before its upscalers)" if _av_branch
-                                  else "two-stage DistilledPipeline (it returns before the post-denoise upscalers)"))
-    if kf_pipeline or hq_pipeline or ic_pipeline or retake_pipeline:
-        _need_cfg = False                   # guided by the pipeline itself (ic-lora: not at all); a missing negative encoding becomes zeros
-    if _need_cfg and not _av_branch:
-        raise NotImplementedError(f"cfg_scale={cfg_scale}: classifier-free guidance is built in OneStagePipeline (the AudioVideo / LTX-2.3 branch); the "
-                                  "standard video-only loop of this script runs the distilled model's cfg = 1")
-    if _need_cfg and not gemma_encodes and (negative_encoding is None or negative_audio_encoding is None):
-        raise NotImplementedError(f"cfg_scale={cfg_scale} / audio_cfg_scale={audio_cfg_scale}: classifier-free guidance needs the NEGATIVE prompt's encodings: "
-                                  "let Gemma encode the prompts (gemma_path), add `negative_embedding` and `negative_audio_embedding` arrays to the --embedding "
-                                  "file, or pass cfg_scale=1.0, audio_cfg_scale=1.0 (what --model-variant distilled does)")
-    if low_memory or fast_mode:
-        print("  low_memory / fast_mode: no effect here (weights and caches stay resident in HBM, the loop is one hipGraph)")
-    have_ckpt = bool(weights_path) and os.path.exists(weights_path)
-    version = model_version if model_version is not None else (detect_model_version(weights_path) if have_ckpt else "")
-    v2 = version.startswith("2.3")                      # reference :1073: V2.3 always uses the AV transformer and the dual text encodings
-    use_av_encoder = generate_audio or v2
-    fps, speed, input_fps = output_fps, output_speed, NATIVE_FPS
-    torch.manual_seed(seed)
-    t_all = time.time()
-    base = os.path.splitext(output_path)[0]
-
-    print("[1/5] text encoding")
-    text_audio_encoding = None
-    if text_features_path:
-        text_encoding, _ = encode_text_features(text_features_path, weights_path if have_ckpt else None, device, seed)
-    elif gemma_encodes and use_av_encoder:
-        # prompt AND negative prompt under one Gemma load (reference :1096-1116); Gemma is freed before the transformer loads.  LTX-2.3
-        # gets the V2 encoder: encodings at the transformer's own widths (num_heads * 128 video, num_heads * 64 audio)
-        results = encode_av_gemma_batch([prompt, negative_prompt or ""], gemma_path, weights_path if have_ckpt else None, device=device,
-                                        seed=seed, model_version=version, num_heads=num_heads)
-        text_encoding, text_audio_encoding, _ = results[0]
-        negative_encoding, negative_audio_encoding, _ = results[1]
-        print("  Encoded both prompts with Gemma 3 (AudioVideo, single load)")
-    elif gemma_encodes:
-        text_encoding, _ = encode_with_gemma(prompt, gemma_path, weights_path if have_ckpt else None, use_early_layers_only=early_layers_only,
-                                             device=device, seed=seed)
-        print("  Encoded with Gemma 3")
-        if (kf_pipeline or hq_pipeline or (retake_pipeline and model_variant != "distilled")) and cfg_scale != 1.0:
-            negative_encoding, _ = encode_with_gemma(negative_prompt or "", gemma_path, weights_path if have_ckpt else None, device=device, seed=seed)
-            print("  Encoded the negative prompt with Gemma 3")
-    elif embedding_path:
-        text_encoding, _ = load_text_embedding(embedding_path, device)
-        z = np.load(embedding_path)
-        if use_av_encoder and "audio_embedding" in z:
-            text_audio_encoding = torch.from_numpy(z["audio_embedding"]).float().to(device)
-            text_audio_encoding = text_audio_encoding[None] if text_audio_encoding.dim() == 2 else text_audio_encoding
-        elif use_av_encoder:
-            print("  WARNING: Pre-computed embeddings don't include audio encoding. Audio quality may be degraded.")
-    else:
-        # dummy encodings (reference :1129-1138).  LTX-2.3 has no caption projection: its contexts arrive at the transformer
-        # widths (4096 video / 2048 audio) -- the reference's 3840-wide dummy would not fit that model at all
-        text_encoding, _ = create_dummy_text_encoding(prompt, embed_dim=num_heads * 128 if v2 else 3840, device=device)
-        if v2:
-            text_audio_encoding, _ = create_dummy_text_encoding(prompt + " (audio)", embed_dim=num_heads * 64, device=device)
-        print("  Using DUMMY encoding (test mode - output will be random)")
-    if use_av_encoder and text_audio_encoding is None:
-        text_audio_encoding = text_encoding             # reference :1080-1081, :1131-1132
-
-    print("[2/5] transformer")
-    model = None
-    if use_placeholder:
-        print("  Skipping model load (placeholder mode)")
-    elif use_av_encoder:
-        model = X0Model(load_av_transformer(weights_path, num_layers=num_layers, compute_dtype=cdt, use_fp8=use_fp8, low_memory=low_memory,
-                                            caption_channels=None if v2 else text_encoding.shape[-1], cross_attention_adaln=v2,
-                                            apply_gated_attention=v2, num_heads=num_heads, seed=seed, device=device,
-                                            lora_path=lora_path, lora_strength=lora_strength, fp8_compute=fp8_compute))
-    else:
-        model = X0Model(load_transformer(weights_path, num_layers=num_layers, compute_dtype=cdt, use_fp8=use_fp8, low_memory=low_memory, fast_mode=fast_mode,
-                                         num_heads=num_heads, caption_channels=text_encoding.shape[-1], seed=seed, device=device,
-                                         lora_path=lora_path, lora_strength=lora_strength, fp8_resident=fp8_resident, fp8_compute=fp8_compute))
-    print("[3/5] VAE decoder")
-    vae_decoder = None
-    if not skip_vae:
-        vae_decoder = create_vae_decoder(weights_path, device, seed + 1, use_placeholder, vae_base_channels, compute_dtype=cdt)
-    else:
-        print("  VAE decoder skipped by user")
-    toy = vae_base_channels is not None and vae_base_channels != 128        # debug-size VAE: matching debug-size upscaler / encoder
-
-    def make_encoder():
-        enc = SimpleVideoEncoder(device=device)
-        if have_ckpt:
-            load_vae_encoder_weights(enc, weights_path)
-        else:
-            enc.init_random_weights(seed=seed + 2)
-        return enc
-
-    def make_upscaler():
-        from ltx_2_mlx_amd.model.upscaler import SpatialUpscaler, load_spatial_upscaler_weights
-        mid = 64 if toy else 1024
-        if spatial_upscaler_weights == "random" or not os.path.exists(str(spatial_upscaler_weights)):
-            if spatial_upscaler_weights != "random":
-                print(f"  Warning: Weights not found at {spatial_upscaler_weights}, using random init")
-            up = SpatialUpscaler(mid_channels=mid, num_blocks_per_stage=4 if mid == 1024 else 1, device=device)
-            up.init_random_weights(seed=seed + 2)
-        else:
-            up = SpatialUpscaler(mid_channels=mid, device=device)
-            load_spatial_upscaler_weights(up, spatial_upscaler_weights)
-        return up
-
-    def make_temporal_upscaler():
-        from ltx_2_mlx_amd.model.upscaler import TemporalUpscaler, load_temporal_upscaler_weights
-        hid = 64 if toy else 512
-        kw = dict(checkpoint_semantics=temporal_upscaler_checkpoint_semantics, device=device)
-        if temporal_upscaler_weights == "random" or not os.path.exists(str(temporal_upscaler_weights)):
-            if temporal_upscaler_weights != "random":
-                print(f"  Warning: Weights not found at {temporal_upscaler_weights}, using random init")
-            up = TemporalUpscaler(hidden_channels=hid, num_res_blocks=4 if hid == 512 else 1, **kw)
-            up.init_random_weights(seed=seed + 4)
-        else:
-            up = TemporalUpscaler(hidden_channels=hid, **kw)
-            load_temporal_upscaler_weights(up, temporal_upscaler_weights)
-        return up
-
-    def decode_audio_latent(audio_latent):
-        """the latent is always kept as <stem>_audio_latent.npz; with decoders it also becomes the waveform (a sidecar .wav)"""
-        np.savez(base + "_audio_latent.npz", latent=audio_latent.float().cpu().numpy())
-        decoders = create_audio_decoders(decode_audio, weights_path if have_ckpt else None, device=device, seed=seed + 3)
-        if decoders is None:
-            return None
-        t0 = time.time()
-        waveform = decoders[1](decoders[0](audio_latent))
-        torch.cuda.synchronize()
-        print(f"  audio decode: {(time.time() - t0):.3f} s -> {tuple(waveform.shape)} at {decoders[1].output_sample_rate} Hz")
-        return waveform, decoders[1].output_sample_rate
-
-    def finish(frames, extra="", audio=None):
-        frames_np = frames.cpu().numpy()
-        np.savez_compressed(base + ".npz", frames=frames_np)
-        if audio is not None and save_mp4:
-            video_out, wav = save_video_with_audio(frames_np, audio[0], output_path, audio[1], fps=fps, speed=speed)      # never the retake route
-            print(f"  video: {video_out}, audio: {wav}")
-        elif audio is not None:
-            print(f"  audio: {write_wav(base + '.wav', audio[0], audio[1])}")
-        elif save_mp4:
-            print(f"  video: {save_video(frames_np, output_path, fps=fps, speed=speed, input_fps=input_fps)}")
-        print(f"Done in {time.time() - t_all:.1f} s: {base}.npz{extra}")
-        return frames
-
-    images = []
-    if image_path and (two_stage_distilled or use_av_encoder or hq_pipeline or ic_pipeline):
-        from ltx_2_mlx_amd.pipelines import ImageCondition
-        print(f"  Image conditioning: {image_path} (strength={image_strength})")
-        images = [ImageCondition(image_path=image_path, frame_index=0, strength=image_strength)]
-
-    if kf_pipeline:
-        # === KEYFRAME INTERPOLATION PIPELINE (reference :1552-1637) ===
-        print("\n=== Using Keyframe Interpolation Pipeline ===")
-        for kf in parsed_keyframes:
-            print(f"  Keyframe: {kf.image_path} at frame {kf.frame_index} (strength={kf.strength})")
-        if model is None:
-            if use_placeholder:
-                print("  Keyframe interpolation requires model - cannot use placeholder mode")
-                return None
-            raise ValueError("Keyframe interpolation pipeline requires a loaded model")
-        if vae_decoder is None:
-            raise ValueError("Keyframe interpolation pipeline requires VAE decoder")
-        from ltx_2_mlx_amd.pipelines import KeyframeInterpolationConfig, KeyframeInterpolationPipeline
-        conf = KeyframeInterpolationConfig(height=height, width=width, num_frames=num_frames, seed=seed, fps=24.0, num_inference_steps=num_steps,
-                                           cfg_scale=cfg_scale, use_hip_graph=use_hip_graph, tiling_config=TilingConfig.default() if tiled_vae else None)
-        print("[3.5/5] VAE encoder")
-        if not have_ckpt:
-            print("  Warning: no checkpoint, the VAE encoder is random-initialised")
-        print("[3.6/5] spatial upscaler")
-        spatial_upscaler_weights = spatial_upscaler_weights or "weights/ltx-2/ltx-2-spatial-upscaler-x2-1.0.safetensors"
-        pipe = KeyframeInterpolationPipeline(model, make_encoder(), vae_decoder, spatial_upscaler=make_upscaler())
-        if conf.cfg_scale != 1.0 and negative_encoding is None:
-            print("  Negative prompt: no encoding given, using zeros of the context's shape (the reference's null text encoding)")
-        print(f"[5/5] Running keyframe interpolation ({num_steps} steps)...")
-        t0 = time.time()
-        frames = _frames_from_video(pipe(text_encoding, None, parsed_keyframes, conf, negative_text_encoding=negative_encoding))
-        torch.cuda.synchronize()
-        print(f"  keyframe interpolation: {(time.time() - t0):.3f} s -> {tuple(frames.shape)}, DiT tokens per stage {pipe.token_counts}")
-        return finish(frames)
-
-    if hq_pipeline:
-        # === HQ TWO-STAGE PIPELINE (reference pipelines/ti2vid_hq.py; its own CLI never reaches it) ===
-        print("\n=== Using TI2Vid HQ Pipeline (res_2s) ===")
-        if model is None:
-            raise ValueError("TI2Vid HQ pipeline requires a loaded model")
-        if vae_decoder is None:
-            raise ValueError("TI2Vid HQ pipeline requires VAE decoder")
-        from ltx_2_mlx_amd.pipelines import TI2VidHQConfig, TI2VidHQPipeline
-        conf = TI2VidHQConfig(height=height, width=width, num_frames=num_frames, seed=seed, num_inference_steps=num_steps,
-                              cfg_scale=cfg_scale, audio_cfg_scale=audio_cfg_scale, distilled_lora_config=hq_lora, use_hip_graph=use_hip_graph,
-                              tiling_config=TilingConfig.default() if tiled_vae else None)
-        print("[3.5/5] VAE encoder")
-        if not have_ckpt:
-            print("  Warning: no checkpoint, the VAE encoder is random-initialised")
-        print("[3.6/5] spatial upscaler")
-        pipe = TI2VidHQPipeline(model, make_encoder(), vae_decoder, make_upscaler())
-        if (cfg_scale > 1.0 or audio_cfg_scale > 1.0) and negative_encoding is None:
-            print("  Negative prompt: no encoding given, using zeros of the context's shape (the reference's null text encoding)")
-            negative_encoding = torch.zeros_like(text_encoding)
-        print(f"[5/5] Running TI2Vid HQ ({num_steps} res_2s steps at {width // 2}x{height // 2}, then 3 at {width}x{height})...")
-        t0 = time.time()
-        frames = _frames_from_video(pipe(text_encoding, negative_encoding, conf, images=images))
-        torch.cuda.synchronize()
-        print(f"  ti2vid-hq: {(time.time() - t0):.3f} s -> {tuple(frames.shape)}")
-        return finish(frames)
-
-    if ic_pipeline:
-        # === IC-LORA PIPELINE (reference :1434-1549) ===
-        print("\n=== Using IC-LoRA Pipeline ===")
-        if model is None:
-            raise ValueError("IC-LoRA pipeline requires a loaded model")
-        if vae_decoder is None:
-            raise ValueError("IC-LoRA pipeline requires VAE decoder")
-        from ltx_2_mlx_amd.pipelines import ControlType, ICLoraConfig, ICLoraPipeline, VideoCondition
-        conf = ICLoraConfig(height=height, width=width, num_frames=num_frames, seed=seed, fps=24.0, stage_1_steps=num_steps,
-                            use_hip_graph=use_hip_graph, tiling_config=TilingConfig.default() if tiled_vae else None)
-        videos = []
-        if control_video:
-            print(f"  Control video: {control_video} (type={control_type}, strength={control_strength})")
-            videos = [VideoCondition(video_path=control_video, strength=control_strength, control_type=ControlType(control_type),
-                                     canny_low=canny_low, canny_high=canny_high, save_control=save_control)]
-        if not ic_loras:
-            print("  Warning: no --ic-lora-weights, stage 1 runs on the base weights")
-        print("[3.5/5] VAE encoder")
-        if not have_ckpt:
-            print("  Warning: no checkpoint, the VAE encoder is random-initialised")
-        print("[3.6/5] spatial upscaler")
-        pipe = ICLoraPipeline(model, make_encoder(), vae_decoder, make_upscaler(), lora_configs=ic_loras, save_video=save_video,
-                              save_dir=output_dir or ".")
-        print(f"[5/5] Running IC-LoRA ({num_steps} steps at {width // 2}x{height // 2}, then {conf.stage_2_steps} at {width}x{height})...")
-        t0 = time.time()
-        frames = _frames_from_video(pipe(text_encoding, None, conf, images=images, video_conditioning=videos))
-        torch.cuda.synchronize()
-        print(f"  ic-lora: {(time.time() - t0):.3f} s -> {tuple(frames.shape)}, DiT tokens per stage {pipe.token_counts}")
-        return finish(frames)
-
-    if retake_pipeline:
-        # === RETAKE PIPELINE (reference pipelines/retake.py; its own CLI never reaches it) ===
-        print("\n=== Using Retake Pipeline ===")
-        if model is None:
-            raise ValueError("Retake pipeline requires a loaded model")
-        if vae_decoder is None:
-            raise ValueError("Retake pipeline requires VAE decoder")
-        from ltx_2_mlx_amd.pipelines import RetakeConfig, RetakePipeline
-        distilled = model_variant == "distilled"
-        conf = RetakeConfig(start_time=retake_start_time, end_time=retake_end_time, distilled=distilled, num_inference_steps=num_steps,
-                            cfg_scale=cfg_scale, seed=seed, fps=retake_fps, use_hip_graph=use_hip_graph, composite_source=retake_composite,
-                            tiling_config=TilingConfig.default() if tiled_vae else None)
-        print(f"  Source: {retake_video}, {width}x{height}, {num_frames} frames @ {retake_fps:g} FPS")
-        print(f"  Retake region: {retake_start_time:g}s - {'the end of the clip' if retake_to_end else f'{retake_end_time:g}s'} -> latent frames [{retake_window[0]}, {retake_window[1]}) of "
-              f"{(num_frames - 1) // 8 + 1}, {((num_frames - 1) // 8 + 1) * (height // 32) * (width // 32)} DiT tokens"
-              + (", source frames kept outside it" if retake_composite else ""))
-        print("[3.5/5] VAE encoder")
-        if not have_ckpt:
-            print("  Warning: no checkpoint, the VAE encoder is random-initialised")
-        pipe = RetakePipeline(model, make_encoder(), vae_decoder)
-        if not distilled and cfg_scale > 1.0 and negative_encoding is None:
-            print("  Negative prompt: no encoding given, using zeros of the context's shape (the reference's null text encoding)")
-        print(f"[5/5] Running retake ({'8 distilled steps' if distilled else f'{num_steps} steps, cfg {cfg_scale}'})...")
-        t0 = time.time()
-        frames = _frames_from_video(pipe(retake_video, text_encoding, None, conf, negative_text_encoding=negative_encoding))
-        torch.cuda.synchronize()
-        fps = input_fps = retake_fps                                     # written at the source's rate: frames enter ffmpeg at it, none interpolated
-        print(f"  retake: {(time.time() - t0):.3f} s -> {tuple(frames.shape)}")
-        return finish(frames)
-
-    if two_stage_distilled:
-        # MI355X extra: the reference's DistilledPipeline class (pipelines/distilled.py:274-505): 8 steps at half resolution, x2
-        # latent upscale, 3 steps at full resolution, image conditioning at both resolutions, auto-tiled decode
-        if not spatial_upscaler_weights:
-            raise ValueError("two_stage_distilled needs --spatial-upscaler-weights (two-stage pipeline)")
-        if vae_decoder is None:
-            raise ValueError("the two-stage pipeline needs the VAE weights (per-channel statistics): drop --skip-vae")
-        if model is None:
-            raise ValueError("Two-stage pipeline requires a loaded model (cannot use placeholder mode)")
-        from ltx_2_mlx_amd.pipelines import DistilledConfig, DistilledPipeline
-        pipe = DistilledPipeline(model, make_encoder() if images else vae_decoder, vae_decoder, spatial_upscaler=make_upscaler())
-        conf = DistilledConfig(height=height, width=width, num_frames=num_frames, seed=seed, fps=24.0, use_hip_graph=use_hip_graph,
-                               audio_enabled=generate_audio, tiling_config=TilingConfig.default() if tiled_vae else None)
-        print("[4/5] two-stage distilled pipeline (8 steps at half resolution, x2 upscale, 3 steps)" + (" with the audio branch" if use_av_encoder else ""))
-        t0 = time.time()
-        out = pipe(text_encoding, None, conf, images=images, audio_encoding=text_audio_encoding)
-        frames, audio_latent = out if generate_audio else (out, None)
-        frames = _frames_from_video(frames)
-        torch.cuda.synchronize()
-        print(f"  two-stage: {(time.time() - t0):.3f} s -> {tuple(frames.shape)}")
-        return finish(frames, audio=decode_audio_latent(audio_latent) if audio_latent is not None else None)
-
-    if use_av_encoder:
-        # === AUDIO-VIDEO PIPELINE (reference :1638-1776): OneStagePipeline on the AudioVideo transformer; LTX-2.3 always ===
-        print("\n=== Using Audio-Video Pipeline ===")
-        if model is None:
-            print("  AV pipeline requires model - cannot use placeholder mode")
-            return None
-        if vae_decoder is None:
-            raise ValueError("AV pipeline requires VAE decoder")
-        if upscale_spatial:
-            raise NotImplementedError("upscale_spatial with the AudioVideo pipeline (the reference's AV branch returns before its upscalers)")
-        from ltx_2_mlx_amd.pipelines import OneStageCFGConfig, OneStagePipeline
-        av_pipeline = OneStagePipeline(transformer=model, video_encoder=make_encoder() if images else None, video_decoder=vae_decoder)
-        av_config = OneStageCFGConfig(
-            height=height, width=width, num_frames=num_frames, seed=seed,
-            fps=25.0,  # matches the upstream frame_rate for the audio latent shape (reference :1704-1712)
-            num_inference_steps=num_steps, cfg_scale=cfg_scale,
-            audio_cfg_scale=audio_cfg_scale, rescale_scale=rescale_scale,
-            audio_enabled=generate_audio, use_hip_graph=use_hip_graph, tiling_config=TilingConfig.default() if tiled_vae else None)
-        given_audio = None
-        if audio_path:
-            print(f"  Encoding audio: {audio_path}")
-            given_audio = encode_audio_for_video(audio_path, num_frames, av_config.fps, weights_path if have_ckpt else None, device=device,
-                                                 seed=seed + 5, start_time=audio_start_time, max_duration=audio_max_duration)
-        print(f"[5/5] Running audio-video generation ({num_steps} steps)...")
-        t0 = time.time()
-        video, audio_latent = av_pipeline(positive_encoding=text_encoding, negative_encoding=negative_encoding if _need_cfg else None, config=av_config,
-                                          images=images, positive_audio_encoding=text_audio_encoding,
-                                          negative_audio_encoding=negative_audio_encoding if _need_cfg else None,
-                                          initial_audio_latent=given_audio[0] if given_audio else None)
-        frames = _frames_from_video(video)
-        torch.cuda.synchronize()
-        print(f"  audio-video pipeline: {(time.time() - t0):.3f} s -> {tuple(frames.shape)}")
-        if given_audio:
-            # the frozen latent is kept; the ORIGINAL audio goes into the mp4 (the reference returns the original waveform, not a decode)
-            import shutil
-            np.savez(base + "_audio_latent.npz", latent=audio_latent.float().cpu().numpy())
-            wav = np.repeat(given_audio[1], 2, axis=0) if given_audio[1].shape[0] == 1 else given_audio[1]
-            return finish(frames, audio=(wav, given_audio[2]) if (save_mp4 and shutil.which("ffmpeg")) else None)
-        return finish(frames, audio=decode_audio_latent(audio_latent) if audio_latent is not None else None)
-
-    # === STANDARD PIPELINE (one-stage, distilled, video-only; reference :1778-2095) ===
-    print("[4/5] latent noise")
-    lf, lh, lw = (num_frames - 1) // 8 + 1, height // 32, width // 32
-    g = torch.Generator(device=device).manual_seed(seed)
-    latent = torch.randn(1, 128, lf, lh, lw, generator=g, device=device)
-    sigmas = DISTILLED_SIGMA_VALUES[:num_steps + 1] if model_variant == "distilled" else \
-        [float(s) for s in get_sigma_schedule(num_steps, distilled=False, latent=latent)]
-    patchifier = VideoLatentPatchifier(patch_size=1)
-    shape = VideoLatentShape(1, 128, lf, lh, lw)
-    coords = patchifier.get_patch_grid_bounds(shape, device=device)
-    positions = get_pixel_coords(coords, SpatioTemporalScaleFactors.default(), causal_fix=True).float()
-    positions = torch.cat([positions[:, 0:1] / 24.0, positions[:, 1:]], dim=1)          # fps = 24 on the CLI path (:1823)
-    print(f"[5/5] denoising ({len(sigmas) - 1} steps)")
-    t0 = time.time()
-    tok = patchifier.patchify(latent).contiguous()
-    if use_placeholder:
-        for i in range(len(sigmas) - 1):
-            tok = tok + 0.1 * torch.randn_like(tok) * (sigmas[i + 1] - sigmas[i])
-    elif image_path:
-        # image-to-video: encoded image replaces latent frame 0, its tokens keep (1 - strength) of the noise level
-        from ltx_2_mlx_amd.conditioning import VideoLatentTools
-        from ltx_2_mlx_amd.components import EulerDiffusionStep, GaussianNoiser
-        from ltx_2_mlx_amd.pipelines import ImageCondition, apply_conditionings, create_image_conditionings, joint_denoise_loop
-        tools = VideoLatentTools(patchifier, shape, fps=24.0)
-        st = tools.create_initial_state(device=device)
-        st = apply_conditionings(st, create_image_conditionings([ImageCondition(image_path, 0, image_strength)], make_encoder(), height, width), tools)
-        st = GaussianNoiser()(st, noise_scale=1.0, noise=tok)
-        st, _ = joint_denoise_loop(model, False, st, None, sigmas, text_encoding, None, EulerDiffusionStep(), None, use_hip_graph)
-        tok = st.latent
-    elif use_hip_graph:
-        vm = model.velocity_model
-        vm.prepare(text_encoding, positions)
-        lat2d = tok[0].float().contiguous()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            vm.capture_denoise_graph(lat2d, sigmas)
-            vm.replay_denoise_graph()
-        torch.cuda.current_stream().wait_stream(side)
-        tok = lat2d[None]
-    else:
-        for i in range(len(sigmas) - 1):
-            m = Modality(latent=tok, context=text_encoding, context_mask=None,
-                         timesteps=torch.tensor([sigmas[i]], device=device), positions=positions, enabled=True)
-            tok = euler_step_x0(tok, model(m), sigmas[i], sigmas[i + 1])
-    torch.cuda.synchronize()
-    print(f"  denoise: {(time.time() - t0):.3f} s")
-    latent = patchifier.unpatchify(tok, shape)
-    np.savez(base + "_latent.npz", latent=latent.float().cpu().numpy())
-    if upscale_spatial and spatial_upscaler_weights:
-        # post-denoise 2x latent upscale (reference :2000-2037): un-normalise with the VAE statistics, upscale, re-normalise;
-        # the decoded video is 2W x 2H
-        from ltx_2_mlx_amd.model.upscaler import upscale_latent
-        print(f"\nApplying 2x spatial upscaling...\n  Input latent: {tuple(latent.shape)}")
-        up = make_upscaler()
-        if vae_decoder is not None:
-            stats = vae_decoder.per_channel_statistics
-            latent = upscale_latent(latent, up, stats.mean_of_means, stats.std_of_means)
-        else:
-            print("  WARNING: No VAE decoder for normalization - output may have wrong range")
-            latent = upscale_latent(latent, up, torch.zeros(128, device=device), torch.ones(128, device=device))
-        print(f"  Upscaled latent: {tuple(latent.shape)}")
-        np.savez(base + "_latent.npz", latent=latent.float().cpu().numpy())
-    if upscale_temporal and temporal_upscaler_weights:
-        # post-denoise 2x temporal latent upscale (reference :2039-2077), after the spatial one: the same un-normalise / re-normalise
-        # bracket; F latent frames become 2F - 1, decoded to 8 * (2F - 2) + 1 video frames saved at the unchanged output fps (:2140)
-        from ltx_2_mlx_amd.model.upscaler import upscale_latent_temporal
-        print(f"\nApplying 2x temporal upscaling...\n  Input latent: {tuple(latent.shape)}")
-        tup = make_temporal_upscaler()
-        if vae_decoder is not None:
-            stats = vae_decoder.per_channel_statistics
-            latent = upscale_latent_temporal(latent, tup, stats.mean_of_means, stats.std_of_means)
-        else:
-            print("  WARNING: No VAE decoder for normalization - output may have wrong range")
-            latent = upscale_latent_temporal(latent, tup, torch.zeros(128, device=device), torch.ones(128, device=device))
-        print(f"  Upscaled latent: {tuple(latent.shape)}")
-        np.savez(base + "_latent.npz", latent=latent.float().cpu().numpy())
-    frames = None
-    if vae_decoder is not None:
-        t0 = time.time()
-        if tiled_vae:
-            frames = _frames_from_video(next(decode_tiled(latent, vae_decoder, TilingConfig.default())))
-        else:
-            frames = decode_latent(latent, vae_decoder)
-        torch.cuda.synchronize()
-        print(f"  decode: {(time.time() - t0):.3f} s -> {tuple(frames.shape)}")
-        return finish(frames)
-    print(f"Done in {time.time() - t_all:.1f} s: {base}_latent.npz")
-    return frames
+    """Generate video from a text prompt: denoise loop + VAE decode on MI355X behind the reference's signature.  _resolve_request validates the arguments and names the one route that runs, before
+    any model is loaded; then the text encoding, the transformer and the VAE decoder (built from the checkpoint's `config.vae` record) are loaded and the route's function runs.  Precedence, each
+    documented on its function: retake_video (_run_retake; it refuses every other route), pipeline_type "keyframe-interpolation" with keyframes (_run_keyframe), "ti2vid-hq" (_run_hq), "ic-lora"
+    with a control video or an image (_run_ic_lora), two_stage_distilled (_run_two_stage), generate_audio or an LTX-2.3 checkpoint (_run_av), else the standard video-only loop (_run_standard).
+    pipeline_type "two-stage" raises NotImplementedError. MI355X extras for every route: model_version="2.3" builds the LTX-2.3 architecture without a checkpoint (random init, for tests and
+    benchmarks); fp8_resident keeps fp8 checkpoint weights as codes in HBM; fp8_compute runs the video stream's projections fp8 x fp8 on the fp8 MFMA (BASELINE config 3; per-token / per-channel
+    e4m3fn scales, not bit-identical to dequantise-at-load); vae_base_channels overrides the checkpoint's decoder_base_channels; compute_dtype="bfloat16" runs the bfloat16 build instead of the
+    reference's float16 default (use_fp16=True).  Returns the uint8 frames (T, H, W, 3); None where the reference returns early."""
+    r = _resolve_request(dict(locals()))
+    if r is None:
+        return None
+    torch.manual_seed(r.seed)
+    s = SimpleNamespace(t_all=time.time(), base=os.path.splitext(r.output_path)[0])
+    s.text_encoding, s.text_audio_encoding, s.negative_encoding, s.negative_audio_encoding = _encode_text(r)
+    s.model = _load_model(r, s.text_encoding)
+    s.vae_decoder = _load_vae_decoder(r)
+    return _ROUTES[r.route](r, s)
 
 
 def build_parser() -> argparse.ArgumentParser:

@@ -99,7 +99,7 @@ def test_capture_and_replay_runs_both_once_on_the_side_stream(monkeypatch):
     monkeypatch.setattr(torch.cuda, "Stream", Stream)
     monkeypatch.setattr(torch.cuda, "current_stream", lambda *a: Stream("current"))
     monkeypatch.setattr(torch.cuda, "stream", lambda s: s)
-    common._capture_and_replay(lambda: log.append("capture"), lambda: log.append("replay"))
+    common.capture_and_replay(lambda: log.append("capture"), lambda: log.append("replay"))
     assert log == [("side", "waits for", "current"), "enter", "capture", "replay", "exit", ("current", "waits for", "side")]
 
 
