@@ -317,6 +317,32 @@ int ltx2_res2s_combine(const float* x_mid, const float* vel_cond, const float* v
                        const float* clean, float cfg_scale, const float* anchor, const float* eps1, float h, float b1, float b2, float* out,
                        int rows, int C, void* stream);
 
+/* Guiders whose scalars are sums over the whole latent -- CFGStarRescalingGuider, LtxAPGGuider, LegacyStatefulAPGGuider (components/guiders.py:51-76,
+ * 105-205) -- as two passes over [rows][C] fp32.  Every fp32 operation is individually rounded (no FMA contraction); the sums are fp64.
+ * ltx2_guidance_sums, per element:
+ *   t = ts[row * ts_stride];  a = x - t*vel_cond;  b = x - t*vel_uncond;  g = a - b
+ *   running != NULL (momentum): first == 0: g = momentum*running + g;  then running = g   (first != 0: running = g, the old content is not read)
+ *   S_aa = sum a*a, S_ab = sum a*b, S_bb = sum b*b, S_gg = sum g*g, S_ga = sum g*a, each product exact in fp64, over ALL rows.
+ *   Order: per thread in loop order, across the wave, across the block; partials[block][5] fp64 in that order of sums, one row per block.
+ *   The number of blocks is ltx2_guidance_sums_blocks(rows, C), a function of the shape alone; partials is 8-byte aligned.
+ * ltx2_projected_euler_step: every block adds the partial rows in index order (all blocks hold the same sums), derives the scalars in fp64 and
+ * rounds each once to fp32:
+ *   mode 0 (CFG*):        coef = fp32(S_ab / (S_bb + 1e-8));                              g_out = a + (scale - 1)*(a - coef*b)
+ *   mode 1 (APG):         sf = norm_threshold > 0 ? min(1, norm_threshold / sqrt(S_gg)) : 1;  proj = fp32(sf*S_ga / (S_aa + 1e-8)) with the fp64 sf;
+ *                         sf = fp32(sf);  gs = g*sf;  par = proj*a;  apg = par*eta + (gs - par);   g_out = a + apg*(scale - 1)
+ *   mode 2 (legacy APG):  as mode 1 with the multiplier `scale`, and g read from `running` when it is set (running is refused in modes 0 and 1).
+ *   scale - 1 is formed in fp32.  proj comes from sf*S_ga; the reference reduces the fp32-rounded g*sf again, a relative difference of order 2^-24.
+ *   d = mask ? g_out*mask[row] + clean*(1 - mask[row]) : g_out;  out = x + ((x - d) * (1/sigma)) * (sigma_next - sigma)
+ * out may equal x.  scalars_out (may be NULL): block 0 stores the fp32 scalars it used, [0] = coef (mode 0), or [0] = sf, [1] = proj.
+ * 16-byte accesses when C % 4 == 0 and every [rows][C] operand is 16-byte aligned, element-wise otherwise.  ts_stride, mask and clean as in
+ * ltx2_guided_euler_step.  sigma == 0 -> LTX2_E_INVALID with message "Sigma can't be 0.0".  (additive entries of ABI version 3)           */
+int ltx2_guidance_sums_blocks(int rows, int C);
+int ltx2_guidance_sums(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, int64_t ts_stride, float* running, int first,
+                       float momentum, double* partials, int rows, int C, void* stream);
+int ltx2_projected_euler_step(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, int64_t ts_stride, const float* mask,
+                              const float* clean, const float* running, const double* partials, int mode, float scale, float eta,
+                              float norm_threshold, float sigma, float sigma_next, float* out, float* scalars_out, int rows, int C, void* stream);
+
 /* VAE elementwise glue (simple_decoder.py:492-498, 228-238/339-342, ops.py:109-125, :792-798)  */
 int ltx2_vae_prepare_latent(const float* latent, const float* std, const float* mean, const float* noise,
                             float noise_scale, void* out_bf16, int C, int64_t P, void* stream);
@@ -451,6 +477,20 @@ int ltx2_dit_guided_step(ltx2_dit* ctx, ltx2_dit* neg, float* latent, const floa
  * belongs to ctx: ltx2_dit_graph_launch(ctx) replays it.                                                                               */
 int ltx2_dit_graph_capture_guided(ltx2_dit* ctx, ltx2_dit* neg, float* latent, const float* host_sigmas, int n_steps,
                                   const float* mask, int64_t n_mask, const float* clean, int64_t n_clean, float cfg_scale, void* stream);
+/* ltx2_dit_guided_step with a guider whose scalars are sums over the whole latent: forward(ctx), forward(neg), ltx2_guidance_sums and
+ * ltx2_projected_euler_step in place on `latent`, in order on the caller's stream.  mode / scale / eta / norm_threshold as in
+ * ltx2_projected_euler_step; momentum != 0 (mode 2 only) keeps the running guidance in a [N][out_channels] fp32 buffer owned by ctx: first != 0
+ * starts it (the first step of a loop), first == 0 continues it and is LTX2_E_STATE when no first step has run for the bound N.  That buffer
+ * and the partials are allocated on first use for the bound N and freed with ctx.  The sums run over all N rows, appended conditioning tokens
+ * included.  Otherwise the validity rules of ltx2_dit_guided_step.  (additive entries of ABI version 3)                                  */
+int ltx2_dit_projected_step(ltx2_dit* ctx, ltx2_dit* neg, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev,
+                            const float* mask, const float* clean, int mode, float scale, float eta, float norm_threshold, float momentum, int first,
+                            float sigma, float sigma_next, void* stream);
+/* n_steps of that step as one captured linear chain, built like ltx2_dit_graph_capture_guided; first is 1 in step 0 only, and with momentum a
+ * memset node at the head of the chain clears the running guidance, so every replay starts alike.  The graph belongs to ctx.              */
+int ltx2_dit_graph_capture_projected(ltx2_dit* ctx, ltx2_dit* neg, float* latent, const float* host_sigmas, int n_steps, const float* mask,
+                                     int64_t n_mask, const float* clean, int64_t n_clean, int mode, float scale, float eta, float norm_threshold,
+                                     float momentum, void* stream);
 /* One res_2s step on the VideoOnly engine (pipelines/ti2vid_hq.py:185-273), enqueued in order on the caller's stream: forward(ctx) and
  * forward(neg) from `latent` at `timesteps`, ltx2_res2s_midpoint into workspaces owned by ctx, forward(ctx) and forward(neg) from x_mid at
  * `ts_sub` (the timesteps of the sub-sigma sqrt(sigma * sigma_next)), ltx2_res2s_combine into `latent`.  neg may be NULL: no guidance, two

@@ -90,6 +90,9 @@ SIGNATURES = {
     "ltx2_guided_euler_step": (i32, [vp, vp, vp, vp, i64, vp, vp, f32, f32, f32, vp, i32, i32, vp]),
     "ltx2_res2s_midpoint": (i32, [vp, vp, vp, vp, i64, vp, vp, f32, f32, i32, vp, vp, vp, i32, i32, vp]),
     "ltx2_res2s_combine": (i32, [vp, vp, vp, vp, i64, vp, vp, f32, vp, vp, f32, f32, f32, vp, i32, i32, vp]),
+    "ltx2_guidance_sums_blocks": (i32, [i32, i32]),
+    "ltx2_guidance_sums": (i32, [vp, vp, vp, vp, i64, vp, i32, f32, vp, i32, i32, vp]),
+    "ltx2_projected_euler_step": (i32, [vp, vp, vp, vp, i64, vp, vp, vp, vp, i32, f32, f32, f32, f32, f32, vp, vp, i32, i32, vp]),
     "ltx2_vae_prepare_latent": (i32, [vp, vp, vp, vp, f32, vp, i32, i64, vp]),
     "ltx2_pixnorm_mod_silu": (i32, [vp, vp, i64, i32, f32, vp, vp, i32, i32, vp]),
     "ltx2_vae_unpatchify": (i32, [vp, vp, i32, i32, i32, vp]),
@@ -116,6 +119,8 @@ SIGNATURES = {
     "ltx2_dit_graph_capture_cond_av": (i32, [vp, vp, vp, C.POINTER(f32), i32, vp, i64, vp, i64, vp, i64, vp, i64, vp]),
     "ltx2_dit_guided_step": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, f32, f32, f32, vp]),
     "ltx2_dit_graph_capture_guided": (i32, [vp, vp, vp, C.POINTER(f32), i32, vp, i64, vp, i64, f32, vp]),
+    "ltx2_dit_projected_step": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, i32, f32, f32, f32, f32, i32, f32, f32, vp]),
+    "ltx2_dit_graph_capture_projected": (i32, [vp, vp, vp, C.POINTER(f32), i32, vp, i64, vp, i64, i32, f32, f32, f32, f32, vp]),
     "ltx2_dit_res2s_step": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, f32, f32, f32, vp]),
     "ltx2_dit_graph_capture_res2s": (i32, [vp, vp, vp, C.POINTER(f32), i32, vp, i64, vp, i64, f32, vp]),
     "ltx2_dit_graph_launch": (i32, [vp, vp]),

@@ -1,10 +1,12 @@
-"""Classifier-free guidance on the denoised prediction (reference LTX_2_MLX/components/guiders.py:26-77, 290-306).
+"""Classifier-free guidance on the denoised prediction (reference LTX_2_MLX/components/guiders.py:26-77, 105-205, 290-306).
 
 Host-side glue of the guided single-stage loops: two x0 predictions (positive / negative prompt) per step are combined here in
-fp32 on the device (element-wise ops and two dot products over a (B, N, C) tensor).  STG / APG guiders are outside the path."""
+fp32 on the device (element-wise ops and dot products over a (B, N, C) tensor).  pipelines.common.projected_denoise_loop runs the
+same guiders as two kernels per step (csrc/guidance.hip).  STG guiders are outside the path."""
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, field
+from typing import Optional
 
 import torch
 
@@ -46,3 +48,59 @@ class CFGStarRescalingGuider:
 
     def enabled(self) -> bool:
         return self.scale != 1.0
+
+
+def _apg_delta(guidance: torch.Tensor, cond: torch.Tensor, eta: float, norm_threshold: float) -> torch.Tensor:
+    """The part the two APG guiders share (guiders.py:132-144 / :186-197): the guidance clipped to norm_threshold over the last three axes,
+    split into its components parallel and orthogonal to cond, the parallel one weighted by eta."""
+    if norm_threshold > 0:
+        guidance_norm = torch.sqrt((guidance * guidance).sum(dim=(-1, -2, -3), keepdim=True))
+        guidance = guidance * torch.minimum(torch.ones_like(guidance), norm_threshold / guidance_norm)
+    g_parallel = projection_coef(guidance, cond) * cond
+    return g_parallel * eta + (guidance - g_parallel)
+
+
+@dataclass(frozen=True)
+class LtxAPGGuider:
+    """Adaptive projected guidance (guiders.py:105-152): cond - uncond, norm-clipped, its component parallel to cond weighted by eta, the
+    whole scaled by scale - 1."""
+    scale: float
+    eta: float = 1.0
+    norm_threshold: float = 0.0
+
+    def delta(self, cond: torch.Tensor, uncond: torch.Tensor) -> torch.Tensor:
+        return _apg_delta(cond - uncond, cond, self.eta, self.norm_threshold) * (self.scale - 1)
+
+    def guide(self, cond: torch.Tensor, uncond: torch.Tensor) -> torch.Tensor:
+        return cond + self.delta(cond, uncond)
+
+    def enabled(self) -> bool:
+        return self.scale != 1.0
+
+
+@dataclass(frozen=False)
+class LegacyStatefulAPGGuider:
+    """APG with a running sum of the guidance (guiders.py:155-205): with momentum != 0 the first call keeps cond - uncond, every later one
+    momentum * running_avg + (cond - uncond); the result is scaled by `scale`, not scale - 1.  reset() forgets the running state: every
+    loop here calls it before its first step (the reference never does)."""
+    scale: float
+    eta: float
+    norm_threshold: float = 5.0
+    momentum: float = 0.0
+    running_avg: Optional[torch.Tensor] = field(default=None, repr=False)
+
+    def reset(self) -> None:
+        self.running_avg = None
+
+    def delta(self, cond: torch.Tensor, uncond: torch.Tensor) -> torch.Tensor:
+        guidance = cond - uncond
+        if self.momentum != 0:
+            self.running_avg = guidance if self.running_avg is None else self.momentum * self.running_avg + guidance
+            guidance = self.running_avg
+        return _apg_delta(guidance, cond, self.eta, self.norm_threshold) * self.scale
+
+    def guide(self, cond: torch.Tensor, uncond: torch.Tensor) -> torch.Tensor:
+        return cond + self.delta(cond, uncond)
+
+    def enabled(self) -> bool:
+        return self.scale != 0.0

@@ -299,6 +299,20 @@ int ltx2_res2s_combine(const float* x_mid, const float* vel_cond, const float* v
                                 (hipStream_t)stream);
 }
 
+int ltx2_guidance_sums_blocks(int rows, int C) { return guidance_sums_blocks(rows, C); }
+
+int ltx2_guidance_sums(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, int64_t ts_stride, float* running, int first,
+                       float momentum, double* partials, int rows, int C, void* stream) {
+    return guidance_sums_launch(x, vel_cond, vel_uncond, ts, (long)ts_stride, running, first, momentum, partials, rows, C, (hipStream_t)stream);
+}
+
+int ltx2_projected_euler_step(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, int64_t ts_stride, const float* mask,
+                              const float* clean, const float* running, const double* partials, int mode, float scale, float eta,
+                              float norm_threshold, float sigma, float sigma_next, float* out, float* scalars_out, int rows, int C, void* stream) {
+    return projected_euler_step_launch(x, vel_cond, vel_uncond, ts, (long)ts_stride, mask, clean, running, partials, mode, scale, eta, norm_threshold,
+                                       sigma, sigma_next, out, scalars_out, rows, C, (hipStream_t)stream);
+}
+
 int ltx2_vae_prepare_latent(const float* latent, const float* std, const float* mean, const float* noise,
                             float noise_scale, void* out_bf16, int C, int64_t P, void* stream) {
     LTX2_CHECK_ARG(latent && std && mean && out_bf16, "vae_prepare_latent: null operand");

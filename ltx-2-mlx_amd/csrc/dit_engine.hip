@@ -114,6 +114,10 @@ struct ltx2_dit {
     float* sigmas_dev = nullptr;       // 64 sigmas of a captured loop, then 64 sub-sigmas (the res_2s loop)
     float* r2s = nullptr;              // res_2s: x_mid | anchor | eps1, three [N][Cout] fp32 workspaces allocated on first use, freed with the context
     long r2s_each = 0;                 //   elements of each
+    double* pg_part = nullptr;         // projected guidance: the sums kernel's partials [pg_rows][5], allocated on first use for the bound N, freed with the context
+    int pg_rows = 0;
+    float* pg_run = nullptr;           //   and, for the legacy APG guider with momentum only, its running guidance [N][Cout] fp32
+    long pg_run_n = 0;
     // fp8-resident linear weights: the typed `const bf16*` fields of the weight structs then hold the CODES pointer; dense() looks it
     // up here to hand the GEMM (codes, per-row scale) instead of bf16 weights.  Per context (a second context over the same tensors
     // -- the video twin of an AudioVideo model -- keeps its own entries); rebuilt whenever the weights are resolved again.
@@ -1064,6 +1068,8 @@ void ltx2_dit_destroy(ltx2_dit* c) {
     for (hipEvent_t e : c->sync_ev) (void)hipEventDestroy(e);
     if (c->side) (void)hipStreamDestroy(c->side);
     if (c->r2s) (void)hipFree(c->r2s);
+    if (c->pg_part) (void)hipFree(c->pg_part);
+    if (c->pg_run) (void)hipFree(c->pg_run);
     if (c->exec) (void)hipGraphExecDestroy(c->exec);
     if (c->graph) (void)hipGraphDestroy(c->graph);
     for (hipEvent_t e : c->prof_ev) (void)hipEventDestroy(e);
@@ -1296,6 +1302,112 @@ int ltx2_dit_graph_capture_guided(ltx2_dit* c, ltx2_dit* neg, float* latent, con
     float* const lat[2] = {latent, nullptr};
     const Cond cond[2] = {{mask, (long)n_mask, clean, (long)n_clean}, {}};
     return capture_loop(c, neg, cfg_scale, lat, cond, host_sigmas, n_steps, (hipStream_t)stream);
+}
+
+// Guidance whose scalars are sums over the whole latent (CFG*, APG, legacy APG with momentum; csrc/guidance.hip): the guided step above with the
+// one element-wise pass replaced by the sums kernel and the projected step kernel.  Linear on the caller's stream as well.
+namespace {
+struct Projected {      // the guider of a projected step: mode 0 CFG*, 1 APG, 2 legacy APG
+    int mode;
+    float scale, eta, norm_threshold, momentum;
+    bool running() const { return mode == 2 && momentum != 0.f; }
+};
+
+int projected_check(const Projected& g, const char* who) {
+    LTX2_CHECK_ARG(g.mode >= 0 && g.mode <= 2, "%s: mode=%d is 0 (CFG*), 1 (APG) or 2 (legacy APG)", who, g.mode);
+    LTX2_CHECK_ARG(g.momentum == 0.f || g.mode == 2, "%s: momentum=%g belongs to mode 2 (legacy APG) alone", who, g.momentum);
+    return LTX2_OK;
+}
+
+// partials for the bound N and, with momentum, the running guidance; never called while a stream is capturing.  keep_running: the step continues a
+// loop (first == 0), so a missing or differently sized running buffer is an error, not something to allocate
+int projected_workspace(ltx2_dit* c, bool running, bool keep_running) {
+    const Mod& m = c->m[0];
+    const int rows = guidance_sums_blocks(m.N, m.Cout);
+    if (!c->pg_part || c->pg_rows != rows) {
+        if (c->pg_part) (void)hipFree(c->pg_part);
+        c->pg_part = nullptr;
+        c->pg_rows = 0;
+        if (hipMalloc((void**)&c->pg_part, 8L * 5 * rows) != hipSuccess) {
+            ltx2_set_error("dit_projected_step: allocating %ld bytes of workspace failed", 8L * 5 * rows);
+            return LTX2_E_HIP;
+        }
+        c->pg_rows = rows;
+    }
+    const long n = (long)m.N * m.Cout;
+    if (!running || (c->pg_run && c->pg_run_n == n)) return LTX2_OK;
+    if (keep_running) {
+        ltx2_set_error("dit_projected_step: first == 0 but no step with first != 0 has filled the running guidance for %d tokens", m.N);
+        return LTX2_E_STATE;
+    }
+    if (c->pg_run) (void)hipFree(c->pg_run);
+    c->pg_run = nullptr;
+    c->pg_run_n = 0;
+    if (hipMalloc((void**)&c->pg_run, 4L * n) != hipSuccess) {
+        ltx2_set_error("dit_projected_step: allocating %ld bytes of workspace failed", 4L * n);
+        return LTX2_E_HIP;
+    }
+    c->pg_run_n = n;
+    return LTX2_OK;
+}
+
+int projected_step(ltx2_dit* c, ltx2_dit* neg, const ModIn& in, const StepIo& io, const Projected& g, int first, float sigma, float sigma_next, hipStream_t st) {
+    LTX2_CHECK_ARG(sigma != 0.f, "Sigma can't be 0.0");
+    LTX2_CHECK_ARG((io.mask == nullptr) == (io.clean == nullptr), "dit_projected_step: mask and clean go together");
+    const Mod& m = c->m[0];
+    LTX2_CHECK_ARG(c->pg_part && c->pg_rows == guidance_sums_blocks(m.N, m.Cout) && (!g.running() || (c->pg_run && c->pg_run_n == (long)m.N * m.Cout)),
+                   "dit_projected_step: workspace missing");
+    const ModIn pos[1] = {{in.latent, in.ts, in.n_ts, in.sigma, m.vel}};
+    const ModIn ngt[1] = {{in.latent, in.ts, in.n_ts, in.sigma, neg->m[0].vel}};
+    TRY(forward(c, pos, st));
+    TRY(forward(neg, ngt, st));
+    float* run = g.running() ? c->pg_run : nullptr;
+    const long stride = in.n_ts == 1 ? 0 : 1;
+    TRY(guidance_sums_launch(in.latent, m.vel, neg->m[0].vel, in.ts, stride, run, first, g.momentum, c->pg_part, m.N, m.Cout, st));
+    return projected_euler_step_launch(in.latent, m.vel, neg->m[0].vel, in.ts, stride, io.mask, io.clean, run, c->pg_part, g.mode, g.scale, g.eta,
+                                       g.norm_threshold, sigma, sigma_next, io.latent, nullptr, m.N, m.Cout, st);
+}
+}  // namespace
+
+int ltx2_dit_projected_step(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev, const float* mask,
+                            const float* clean, int mode, float scale, float eta, float norm_threshold, float momentum, int first, float sigma,
+                            float sigma_next, void* stream) {
+    LTX2_CHECK_ARG(latent && timesteps, "dit_projected_step: null argument");
+    TRY(guided_ready(c, neg, n_timesteps, "dit_projected_step"));
+    const Projected g = {mode, scale, eta, norm_threshold, momentum};
+    TRY(projected_check(g, "dit_projected_step"));
+    TRY(projected_workspace(c, g.running(), first == 0));
+    const ModIn in = {latent, timesteps, n_timesteps, sigma_dev ? sigma_dev : timesteps, nullptr};
+    const StepIo io = {latent, mask, clean, nullptr};
+    return projected_step(c, neg, in, io, g, first, sigma, sigma_next, (hipStream_t)stream);
+}
+
+int ltx2_dit_graph_capture_projected(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* host_sigmas, int n_steps, const float* mask, int64_t n_mask,
+                                     const float* clean, int64_t n_clean, int mode, float scale, float eta, float norm_threshold, float momentum,
+                                     void* stream) {
+    LTX2_CHECK_ARG(latent && host_sigmas && n_steps > 0 && n_steps < 64, "dit_graph_capture_projected: bad argument");
+    TRY(guided_ready(c, neg, mask ? c->m[0].N : 1, "dit_graph_capture_projected"));
+    LTX2_CHECK_ARG((mask == nullptr) == (clean == nullptr), "dit_graph_capture_projected: mask and clean go together");
+    const Projected g = {mode, scale, eta, norm_threshold, momentum};
+    TRY(projected_check(g, "dit_graph_capture_projected"));
+    TRY(projected_workspace(c, g.running(), false));
+    hipStream_t st = (hipStream_t)stream;
+    const Cond cond = {mask, (long)n_mask, clean, (long)n_clean};
+    TRY(begin_capture(c, host_sigmas, n_steps, st));
+    int rc = LTX2_OK;
+    // the head of the chain: every replay starts from a cleared running guidance
+    if (g.running() && hipMemsetAsync(c->pg_run, 0, 4L * c->pg_run_n, st) != hipSuccess) {
+        ltx2_set_error("dit_graph_capture_projected: hipMemsetAsync failed");
+        rc = LTX2_E_HIP;
+    }
+    for (int i = 0; i < n_steps && rc == LTX2_OK; ++i) {
+        const float* s = c->sigmas_dev + i;
+        ModIn in = {latent, s, 1, s, nullptr};
+        StepIo io = {latent, nullptr, nullptr, nullptr};
+        rc = cond_modality(c, 0, cond, s, in, io, st);          // ts = mask * sigma_i into c's buffer; both contexts read it
+        if (rc == LTX2_OK) rc = projected_step(c, neg, in, io, g, i == 0, host_sigmas[i], host_sigmas[i + 1], st);
+    }
+    return end_capture(c, rc, st);
 }
 
 // The res_2s second-order step (reference pipelines/ti2vid_hq.py:185-273; HQ pipeline stage 1): per step two pairs of evaluations, the second

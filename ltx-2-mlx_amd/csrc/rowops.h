@@ -88,6 +88,17 @@ int res2s_combine_launch(const float* x_mid, const float* vel_cond, const float*
                          const float* clean, float cfg_scale, const float* anchor, const float* eps1, float h, float b1, float b2, float* out,
                          int rows, int C, hipStream_t stream);
 
+// Guiders whose scalars are sums over the whole latent (guidance.hip; the definitions: include/ltx2hip.h).  sums: five fp64 sums per block into
+// partials[guidance_sums_blocks(rows, C)][5], and with `running` the momentum update of the guidance; step: every block adds the partial rows in
+// index order, derives the fp32 scalars and runs the guided, mask-blended Euler step.  out may equal x.
+int guidance_sums_blocks(int rows, int C);
+int guidance_sums_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride, float* running, int first,
+                         float momentum, double* partials, int rows, int C, hipStream_t stream);
+int projected_euler_step_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride, const float* mask,
+                                const float* clean, const float* running, const double* partials, int mode, float scale, float eta,
+                                float norm_threshold, float sigma, float sigma_next, float* out, float* scalars_out, int rows, int C,
+                                hipStream_t stream);
+
 // ---- spatial upscaler (channels-last bf16 [P][C]) ----
 // y = [silu]( GroupNorm_G(x over (C/G, all positions)) * gamma + beta + res );  scratch: 2*G*(1 + ceil(P/16)) floats
 int groupnorm_silu_launch(const bf16* x, const bf16* res, bf16* y, long P, int C, int G, float eps, const float* gamma,

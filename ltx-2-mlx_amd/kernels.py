@@ -527,6 +527,60 @@ def guided_euler_step(x: torch.Tensor, vel_cond: torch.Tensor, vel_uncond: torch
     return out
 
 
+GUIDANCE_MODES = {"cfg_star": 0, "apg": 1, "legacy_apg": 2}      # `mode` of ltx2_projected_euler_step / ltx2_dit_projected_step
+
+
+def guidance_sums_blocks(rows: int, c: int, dtype: Optional[torch.dtype] = None) -> int:
+    """Rows of the fp64 [rows, 5] partials buffer that guidance_sums fills for an [N, C] latent (ltx2_guidance_sums_blocks)."""
+    return int(nv.lib(dtype).ltx2_guidance_sums_blocks(int(rows), int(c)))
+
+
+def _guidance_operands(x, vel_cond, vel_uncond, timesteps, partials, extra):
+    n, c = x.shape
+    timesteps = _c(timesteps.float())
+    if timesteps.numel() not in (1, n):
+        raise ValueError(f"timesteps has {timesteps.numel()} elements; expected 1 or N={n}")
+    for t in (x, vel_cond, vel_uncond) + tuple(extra):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.shape == x.shape)
+    assert partials.dtype == torch.float64 and partials.is_contiguous()
+    return n, c, timesteps
+
+
+def guidance_sums(x: torch.Tensor, vel_cond: torch.Tensor, vel_uncond: torch.Tensor, timesteps: torch.Tensor, partials: Optional[torch.Tensor] = None,
+                  running: Optional[torch.Tensor] = None, first: bool = True, momentum: float = 0.0, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """First pass of a projected guidance step over fp32 [N, C] (ltx2_guidance_sums): a = x - t*vc, b = x - t*vu, g = a - b (with `running`:
+    g = momentum*running + g unless `first`, stored back to running), and S_aa, S_ab, S_bb, S_gg, S_ga in fp64, one row per block.
+    -> partials, fp64 [guidance_sums_blocks(N, C), 5].  `dtype` picks the library build (the kernel is fp32 / fp64 in both)."""
+    if partials is None:
+        partials = torch.empty(guidance_sums_blocks(*x.shape, dtype=dtype), 5, device=x.device, dtype=torch.float64)
+    n, c, timesteps = _guidance_operands(x, vel_cond, vel_uncond, timesteps, partials, (running,))
+    assert partials.numel() >= 5 * guidance_sums_blocks(n, c, dtype)
+    nv.check(nv.lib(dtype).ltx2_guidance_sums(nv.ptr(x), nv.ptr(vel_cond), nv.ptr(vel_uncond), nv.ptr(timesteps), 0 if timesteps.numel() == 1 else 1,
+                                              nv.ptr(running), int(bool(first)), float(momentum), nv.ptr(partials), n, c, nv.stream()))
+    return partials
+
+
+def projected_euler_step(x: torch.Tensor, vel_cond: torch.Tensor, vel_uncond: torch.Tensor, timesteps: torch.Tensor, partials: torch.Tensor, mode: int,
+                         scale: float, eta: float, norm_threshold: float, sigma: float, sigma_next: float, mask: Optional[torch.Tensor] = None,
+                         clean: Optional[torch.Tensor] = None, running: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                         scalars_out: Optional[torch.Tensor] = None, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """Second pass (ltx2_projected_euler_step): the sums of `partials` added in every block, the guider's scalars from them (mode 0: CFG*'s coef;
+    1 / 2: APG's sf and proj), then x0 of both velocities, the guider, the mask / clean blend and the Euler update, every fp32 operation
+    individually rounded.  `out` may be `x`; `scalars_out` (fp32, 2 elements) receives the scalars used; `running` (mode 2): the guidance
+    guidance_sums left."""
+    if out is None:
+        out = torch.empty_like(x)
+    n, c, timesteps = _guidance_operands(x, vel_cond, vel_uncond, timesteps, partials, (clean, running, out))
+    assert partials.numel() >= 5 * guidance_sums_blocks(n, c, dtype)
+    assert (mask is None) == (clean is None) and (mask is None or (mask.numel() == n and mask.dtype == torch.float32 and mask.is_contiguous()))
+    assert scalars_out is None or (scalars_out.dtype == torch.float32 and scalars_out.numel() >= 2)
+    nv.check(nv.lib(dtype).ltx2_projected_euler_step(nv.ptr(x), nv.ptr(vel_cond), nv.ptr(vel_uncond), nv.ptr(timesteps), 0 if timesteps.numel() == 1 else 1,
+                                                     nv.ptr(mask), nv.ptr(clean), nv.ptr(running), nv.ptr(partials), int(mode), float(scale), float(eta),
+                                                     float(norm_threshold), float(sigma), float(sigma_next), nv.ptr(out), nv.ptr(scalars_out), n, c,
+                                                     nv.stream()))
+    return out
+
+
 def _res2s_operands(x, vel_cond, vel_uncond, timesteps, mask, clean, extra):
     n, c = x.shape
     timesteps = _c(timesteps.float())

@@ -702,6 +702,38 @@ class LTXModel:
         """Replay the graph captured by capture_guided_graph (it belongs to the VideoOnly context that ran the capture)."""
         self._replay("guided", "no guided graph captured")
 
+    # ------------------------------------------------------------------ guiders whose scalars are sums over the latent (video-only engine)
+    def projected_step_(self, neg: "LTXModel", latent: torch.Tensor, video: Modality, sigma: float, sigma_next: float, mode: int, scale: float,
+                        eta: float = 1.0, norm_threshold: float = 0.0, momentum: float = 0.0, first: bool = True,
+                        denoise_mask: Optional[torch.Tensor] = None, clean_latent: Optional[torch.Tensor] = None) -> None:
+        """In-place: latent (N, C) fp32 <- one guided Euler step under CFGStarRescalingGuider (mode 0), LtxAPGGuider (1) or
+        LegacyStatefulAPGGuider (2): both evaluations as guided_step_, then the sums kernel and the projected step kernel, all enqueued by ONE C
+        call (ltx2_dit_projected_step).  momentum != 0 (mode 2): the engine keeps the running guidance; `first` starts it anew."""
+        pos, ng = self._guided_pair(neg)
+        ts, n_ts, sg = pos._step_inputs(latent, video, sigma)
+        nv.check(pos._L.ltx2_dit_projected_step(pos._h, ng._h, nv.ptr(latent), nv.ptr(ts), n_ts, nv.ptr(sg), nv.ptr(denoise_mask), nv.ptr(clean_latent),
+                                                int(mode), float(scale), float(eta), float(norm_threshold), float(momentum), int(bool(first)),
+                                                float(sigma), float(sigma_next), nv.stream()))
+
+    def capture_projected_graph(self, neg: "LTXModel", latent: torch.Tensor, sigmas: Sequence[float], mode: int, scale: float, eta: float = 1.0,
+                                norm_threshold: float = 0.0, momentum: float = 0.0, denoise_mask: Optional[torch.Tensor] = None,
+                                clean_latent: Optional[torch.Tensor] = None) -> None:
+        """hipGraph-capture len(sigmas)-1 projected steps over `latent` (N, C fp32) as one linear chain (ltx2_dit_graph_capture_projected); with
+        momentum its head clears the running guidance, so every replay is a fresh loop.  Both contexts are prepared first (per_token=True when
+        a mask is given); the graph belongs to the positive VideoOnly context and replay_projected_graph() replays it."""
+        pos, ng = self._guided_pair(neg)
+        assert pos._prep_key is not None and ng._prep_key is not None, "call prepare() on both contexts first"
+        arr, n, st, n_el = self._capture_inputs(sigmas, (denoise_mask, clean_latent))
+        pos._graph_refs = (latent, denoise_mask, clean_latent, ng)
+        nv.check(pos._L.ltx2_dit_graph_capture_projected(pos._h, ng._h, nv.ptr(latent), arr, n, nv.ptr(denoise_mask), n_el(denoise_mask),
+                                                         nv.ptr(clean_latent), n_el(clean_latent), int(mode), float(scale), float(eta),
+                                                         float(norm_threshold), float(momentum), st.cuda_stream))
+        self._graph_owner = ("projected", pos)
+
+    def replay_projected_graph(self) -> None:
+        """Replay the graph captured by capture_projected_graph (it belongs to the VideoOnly context that ran the capture)."""
+        self._replay("projected", "no projected graph captured")
+
     # ------------------------------------------------------------------ res_2s second-order sampling (video-only engine)
     def _res2s_pair(self, neg: Optional["LTXModel"]) -> Tuple["LTXModel", Optional["LTXModel"]]:
         """(positive, negative or None) VideoOnly contexts of a res_2s step: an AudioVideo model is used through its video twin."""

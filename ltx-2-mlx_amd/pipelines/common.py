@@ -321,6 +321,63 @@ def guided_denoise_loop(transformer, video_state: LatentState, sigmas, context: 
     return _with_latent(video_state, lat)
 
 
+def projected_guider_args(guider) -> Optional[dict]:
+    """The (mode, scale, eta, norm_threshold, momentum) of LTXModel.projected_step_ for a guider whose scalars are sums over the latent; None
+    for every other object."""
+    from ..components.guiders import CFGStarRescalingGuider, LegacyStatefulAPGGuider, LtxAPGGuider
+    if type(guider) is CFGStarRescalingGuider:
+        return dict(mode=0, scale=guider.scale, eta=1.0, norm_threshold=0.0, momentum=0.0)
+    if type(guider) is LtxAPGGuider:
+        return dict(mode=1, scale=guider.scale, eta=guider.eta, norm_threshold=guider.norm_threshold, momentum=0.0)
+    if type(guider) is LegacyStatefulAPGGuider:
+        return dict(mode=2, scale=guider.scale, eta=guider.eta, norm_threshold=guider.norm_threshold, momentum=guider.momentum)
+    return None
+
+
+def reset_guider(guider) -> None:
+    """A stateful guider starts every loop without its running state (LegacyStatefulAPGGuider.reset; the reference never clears it)."""
+    if hasattr(guider, "reset"):
+        guider.reset()
+
+
+def projected_denoise_loop(transformer, video_state: LatentState, sigmas, context: torch.Tensor, negative_context: Optional[torch.Tensor],
+                           guider, stepper, callback=None, use_hip_graph: bool = True) -> LatentState:
+    """guided_denoise_loop for the guiders whose scalars are sums over the whole latent: an enabled CFGStarRescalingGuider, LtxAPGGuider or
+    LegacyStatefulAPGGuider runs every step as ONE C call -- forward(positive), forward(negative), the sums kernel, the projected step kernel
+    (LTXModel.projected_step_) -- and with no callback and fewer than 64 steps the whole loop is one captured graph.  The sums run over all
+    tokens of the state, appended conditioning tokens included, as the reference's guider sees the whole denoised tensor.  A stateful
+    guider's running guidance lives on the device for the loop and starts cleared.  A plain CFGGuider is handed to guided_denoise_loop;
+    anything else, or a guider that is not enabled, goes to joint_denoise_loop.  Returns the video state."""
+    from ..components.guiders import CFGGuider
+    reset_guider(guider)
+    model = transformer.velocity_model
+    if type(guider) is CFGGuider:
+        return guided_denoise_loop(transformer, video_state, sigmas, context, negative_context, guider, stepper, callback, use_hip_graph)
+    args = projected_guider_args(guider)
+    if args is None or not guider.enabled():
+        return joint_denoise_loop(transformer, model.is_av, video_state, None, sigmas, context, None, stepper, callback, use_hip_graph,
+                                  negative_video_context=negative_context, video_guider=guider)[0]
+    if negative_context is None:
+        raise ValueError("guidance needs the negative prompt's encoding")
+    sig = [float(s) for s in sigmas]
+    n = len(sig) - 1
+    model, uniform, lat, mask, clean = _video_loop_inputs(model, video_state)
+    neg = model.clone_sharing_weights()
+    model.prepare(context, video_state.positions, per_token=not uniform)
+    neg.prepare(negative_context, video_state.positions, per_token=not uniform)
+    if use_hip_graph and callback is None and n < 64:
+        capture_and_replay(lambda: model.capture_projected_graph(neg, lat, sig, denoise_mask=mask, clean_latent=clean, **args),
+                            model.replay_projected_graph)
+    else:
+        for i in range(n):
+            st = video_state.replace(latent=lat[None])
+            model.projected_step_(neg, lat, modality_from_state(st, context, sig[i], uniform=uniform), sig[i], sig[i + 1], first=(i == 0),
+                                  denoise_mask=mask, clean_latent=clean, **args)
+            if callback:
+                callback(i + 1, n)
+    return _with_latent(video_state, lat)
+
+
 def res2s_denoise_loop(transformer, video_state: LatentState, sigmas, context: torch.Tensor, negative_context: Optional[torch.Tensor],
                        cfg_scale: float, audio_cfg_scale: float = 7.0, callback=None, use_hip_graph: bool = True) -> LatentState:
     """The HQ pipeline's res_2s loop on the video-only model (reference pipelines/ti2vid_hq.py:153-273), without leaving the device: every

@@ -20,7 +20,7 @@ from ..components import STAGE_2_DISTILLED_SIGMA_VALUES, CFGGuider, EulerDiffusi
 from ..conditioning.keyframe import VideoConditionByKeyframeIndex
 from ..model.transformer import LTXModel, X0Model
 from ..model.video_vae import SimpleVideoDecoder, TilingConfig
-from .common import (as_x0model, conditioned_initial_state, decode_video, final_latent, guided_denoise_loop, seeded_noiser, stage_callback,
+from .common import (as_x0model, conditioned_initial_state, decode_video, final_latent, guided_denoise_loop, projected_denoise_loop, seeded_noiser, stage_callback,
                      upscale_latent_x2, video_tools_for)
 
 
@@ -109,9 +109,10 @@ class KeyframeInterpolationPipeline:
 
     def denoise_latent(self, text_encoding: torch.Tensor, keyframes: List[Keyframe], config: KeyframeInterpolationConfig,
                        negative_text_encoding: Optional[torch.Tensor] = None, callback: Optional[Callable[[str, int, int], None]] = None,
-                       *, initial_noise: Optional[torch.Tensor] = None, stage2_noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+                       *, initial_noise: Optional[torch.Tensor] = None, stage2_noise: Optional[torch.Tensor] = None, guider=None) -> torch.Tensor:
         """Both stages up to the final latent (1, 128, F, H/32, W/32).  initial_noise / stage2_noise (keyword-only, MI355X addition):
-        supplied N(0,1) tensors of the patchified shapes INCLUDING the appended tokens, so results can be compared with a restatement."""
+        supplied N(0,1) tensors of the patchified shapes INCLUDING the appended tokens, so results can be compared with a restatement.
+        guider (keyword-only): replaces CFGGuider(config.cfg_scale) in stage 1 and runs through projected_denoise_loop."""
         for kf in keyframes:
             if not 0 <= kf.frame_index < config.num_frames:
                 raise ValueError(f"keyframe frame_index {kf.frame_index} is outside [0, {config.num_frames})")
@@ -128,8 +129,9 @@ class KeyframeInterpolationPipeline:
         tools, state = self._stage_state(keyframes, config, config.height // div, config.width // div, dev)
         sigmas = LTX2Scheduler().execute(steps=config.num_inference_steps)
         state = noiser(state, noise_scale=1.0, noise=initial_noise)
-        state = guided_denoise_loop(self.transformer, state, sigmas, ctx, nctx, CFGGuider(config.cfg_scale), self.diffusion_step,
-                                    stage_callback(callback, "stage1"), config.use_hip_graph)
+        loop, stage1_guider = (guided_denoise_loop, CFGGuider(config.cfg_scale)) if guider is None else (projected_denoise_loop, guider)
+        state = loop(self.transformer, state, sigmas, ctx, nctx, stage1_guider, self.diffusion_step, stage_callback(callback, "stage1"),
+                     config.use_hip_graph)
         latent = final_latent(tools, state)
         if not config.use_two_stage:
             return latent
@@ -146,11 +148,12 @@ class KeyframeInterpolationPipeline:
     def __call__(self, text_encoding: torch.Tensor, text_mask: Optional[torch.Tensor], keyframes: List[Keyframe],
                  config: KeyframeInterpolationConfig, negative_text_encoding: Optional[torch.Tensor] = None,
                  negative_text_mask: Optional[torch.Tensor] = None, callback: Optional[Callable[[str, int, int], None]] = None,
-                 *, initial_noise: Optional[torch.Tensor] = None, stage2_noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 *, initial_noise: Optional[torch.Tensor] = None, stage2_noise: Optional[torch.Tensor] = None, guider=None) -> torch.Tensor:
         """-> uint8 frames (F, H, W, 3) (the final latent when no decoder is set).  The text masks are accepted and unused, as every loop
-        here passes context_mask=None (reference pipelines/common.py:223-232)."""
+        here passes context_mask=None (reference pipelines/common.py:223-232).  guider (keyword-only): the guider of stage 1 instead of
+        CFGGuider(config.cfg_scale), e.g. LtxAPGGuider."""
         latent = self.denoise_latent(text_encoding, keyframes, config, negative_text_encoding, callback, initial_noise=initial_noise,
-                                     stage2_noise=stage2_noise)
+                                     stage2_noise=stage2_noise, guider=guider)
         return decode_video(latent, self.video_decoder, config.tiling_config)           # no automatic tiling here
 
 

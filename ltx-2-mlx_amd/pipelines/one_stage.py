@@ -10,8 +10,10 @@ cfg_scale = audio_cfg_scale = 1, i.e. one transformer evaluation per step).
 
 Classifier-free guidance (round 3): `cfg_scale` / `audio_cfg_scale` != 1 evaluate the negative prompt too (a second engine context over the same
 weights) and combine the two predictions with CFGGuider or, for `rescale_scale > 0`, CFGStarRescalingGuider -- per modality, as :793-807.
+`guider_override` (one of CFGGuider, CFGStarRescalingGuider, LtxAPGGuider, LegacyStatefulAPGGuider) becomes the video guider; audio keeps its
+standard one (:795-805).  Without an audio state an enabled projected guider runs through pipelines.common.projected_denoise_loop.
 
-Outside the MI355X hot path, rejected with NotImplementedError: STG / APG guidance (`stg_scale`, `guider_override`), the Heun sampler, GE velocity correction, cross-attention scaling, the temporal upscaler.
+Outside the MI355X hot path, rejected with NotImplementedError: STG guidance (`stg_scale`), any other `guider_override`, the Heun sampler, GE velocity correction, cross-attention scaling, the temporal upscaler.
 With `audio_enabled`, the audio waveform is returned when an audio_decoder and a vocoder are given (model/audio_vae/), the audio
 LATENT otherwise.
 """
@@ -22,13 +24,14 @@ from typing import Callable, List, Optional, Tuple, Union
 
 import torch
 
-from ..components import AudioPatchifier, CFGGuider, CFGStarRescalingGuider, EulerDiffusionStep, LTX2Scheduler, VideoLatentPatchifier
+from ..components import (AudioPatchifier, CFGGuider, CFGStarRescalingGuider, EulerDiffusionStep, LegacyStatefulAPGGuider, LtxAPGGuider, LTX2Scheduler,
+                          VideoLatentPatchifier)
 from ..conditioning.tools import AudioLatentTools
 from ..model.transformer import LTXModel, X0Model
 from ..model.video_vae import SimpleVideoDecoder, TilingConfig
 from ..types import AudioLatentShape, VideoPixelShape
 from .common import (ImageCondition, as_x0model, auto_tiling_config, conditioned_initial_state, create_image_conditionings, decode_video,
-                     final_latent, joint_denoise_loop, seeded_noiser, video_tools_for)
+                     final_latent, joint_denoise_loop, projected_denoise_loop, projected_guider_args, reset_guider, seeded_noiser, video_tools_for)
 
 
 @dataclass
@@ -85,7 +88,7 @@ class OneStagePipeline:
     def _require_no_guidance(stg_scale, guider_override, ge_gamma, sampler, temporal_upscaler, cross_attn_scale):
         """Everything beyond classifier-free guidance and the Euler step is not built here.  The reference enables STG / GE only for
         values > 0 (pipelines/one_stage.py:867, :301): a zero or negative value is a no-op there and passes here."""
-        if guider_override is not None:
+        if guider_override is not None and type(guider_override) not in (CFGGuider, CFGStarRescalingGuider, LtxAPGGuider, LegacyStatefulAPGGuider):
             raise NotImplementedError("guider_override (APG / custom guiders) is outside the MI355X hot path")
         if stg_scale > 0:
             raise NotImplementedError("STG guidance is outside the MI355X hot path")
@@ -154,14 +157,22 @@ class OneStagePipeline:
         # one guider per modality (one_stage.py:793-807)
         mk = CFGStarRescalingGuider if config.rescale_scale > 0 else CFGGuider
         video_guider, audio_guider = mk(scale=config.cfg_scale), mk(scale=config.audio_cfg_scale)
+        if guider_override is not None:
+            video_guider = guider_override      # audio keeps its standard guider (one_stage.py:795-805)
+            reset_guider(video_guider)
         need_cfg = video_guider.enabled() or (internal_audio_active and audio_guider.enabled())
         if need_cfg and (negative_encoding is None or (internal_audio_active and negative_audio_encoding is None)):
             raise ValueError("cfg_scale / audio_cfg_scale != 1 need the negative prompt's encoding(s)")
         nactx = negative_audio_encoding.to(dev) if (need_cfg and internal_audio_active) else None
-        video_state, audio_state = joint_denoise_loop(self.transformer, self.is_av_model, video_state, audio_state, sigmas,
-                                                      positive_encoding.to(dev), actx, self.diffusion_step, callback, config.use_hip_graph,
-                                                      negative_video_context=negative_encoding.to(dev) if need_cfg else None,
-                                                      negative_audio_context=nactx, video_guider=video_guider, audio_guider=audio_guider)
+        if guider_override is not None and audio_state is None and video_guider.enabled() and projected_guider_args(video_guider) is not None:
+            # the override's sums and step on the device; the default guiders stay on the eager loop below
+            video_state = projected_denoise_loop(self.transformer, video_state, sigmas, positive_encoding.to(dev), negative_encoding.to(dev),
+                                                 video_guider, self.diffusion_step, callback, config.use_hip_graph)
+        else:
+            video_state, audio_state = joint_denoise_loop(self.transformer, self.is_av_model, video_state, audio_state, sigmas,
+                                                          positive_encoding.to(dev), actx, self.diffusion_step, callback, config.use_hip_graph,
+                                                          negative_video_context=negative_encoding.to(dev) if need_cfg else None,
+                                                          negative_audio_context=nactx, video_guider=video_guider, audio_guider=audio_guider)
 
         video = decode_video(final_latent(video_tools, video_state), self.video_decoder, config._get_tiling_config())
         audio = None

@@ -30,7 +30,7 @@ from ..conditioning.tools import VideoLatentTools
 from ..model.transformer import LTXModel, X0Model
 from ..model.video_vae import SimpleVideoDecoder, TilingConfig
 from ..types import LatentState, VideoLatentShape, VideoPixelShape
-from .common import as_x0model, decode_video, final_latent, guided_denoise_loop, joint_denoise_loop, stage_callback
+from .common import as_x0model, decode_video, final_latent, guided_denoise_loop, joint_denoise_loop, projected_denoise_loop, stage_callback
 from .ic_lora import IMAGE_SUFFIXES, load_control_frames, load_control_signal_tensor
 
 
@@ -203,10 +203,11 @@ class RetakePipeline:
 
     def denoise_latent(self, video_path: Optional[str], text_encoding: torch.Tensor, config: RetakeConfig,
                        negative_text_encoding: Optional[torch.Tensor] = None, callback: Optional[Callable[[str, int, int], None]] = None, *,
-                       frames=None, initial_noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+                       frames=None, initial_noise: Optional[torch.Tensor] = None, guider=None) -> torch.Tensor:
         """Up to the final latent (1, 128, F, H/32, W/32).  frames (keyword-only, MI355X addition): already loaded uint8 frames
         (F, H, W, 3) instead of a path.  initial_noise: a supplied N(0, 1) tensor (1, F*H*W/1024, 128) of the patchified shape, so results
-        can be compared with a restatement."""
+        can be compared with a restatement.  guider (keyword-only): replaces CFGGuider(config.cfg_scale) in the guided (not distilled) mode
+        and runs through projected_denoise_loop."""
         if self.video_encoder is None:
             raise ValueError("RetakePipeline needs a video_encoder")
         src, fps = self._load_source(video_path, frames, config)
@@ -245,18 +246,20 @@ class RetakePipeline:
             sigmas = LTX2Scheduler().execute(steps=config.num_inference_steps)
             # no negative prompt: zeros of the context's shape (reference :387-388); cfg_scale <= 1: no negative pass (:261)
             nctx = torch.zeros_like(ctx) if negative_text_encoding is None else negative_text_encoding.to(dev)
-            guider = CFGGuider(config.cfg_scale if config.cfg_scale > 1.0 else 1.0)
-            state = guided_denoise_loop(self.transformer, state, sigmas, ctx, nctx, guider, self.stepper, cb, config.use_hip_graph)
+            loop = guided_denoise_loop if guider is None else projected_denoise_loop
+            guider = CFGGuider(config.cfg_scale if config.cfg_scale > 1.0 else 1.0) if guider is None else guider
+            state = loop(self.transformer, state, sigmas, ctx, nctx, guider, self.stepper, cb, config.use_hip_graph)
         return final_latent(tools, state)
 
     def __call__(self, video_path: Optional[str], text_encoding: torch.Tensor, text_mask: Optional[torch.Tensor], config: RetakeConfig,
                  negative_text_encoding: Optional[torch.Tensor] = None, audio_encoding: Optional[torch.Tensor] = None,
                  negative_audio_encoding: Optional[torch.Tensor] = None, callback: Optional[Callable[[str, int, int], None]] = None, *,
-                 frames=None, initial_noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 frames=None, initial_noise: Optional[torch.Tensor] = None, guider=None) -> torch.Tensor:
         """-> uint8 frames (T, H, W, 3) (the final latent when no decoder is set).  text_mask is accepted and unused, as every loop here
-        passes context_mask=None (reference pipelines/common.py:223-232); so are the audio encodings (no audio retake)."""
+        passes context_mask=None (reference pipelines/common.py:223-232); so are the audio encodings (no audio retake).  guider
+        (keyword-only): the guider of the guided mode instead of CFGGuider(config.cfg_scale), e.g. LtxAPGGuider."""
         latent = self.denoise_latent(video_path, text_encoding, config, negative_text_encoding, callback, frames=frames,
-                                     initial_noise=initial_noise)
+                                     initial_noise=initial_noise, guider=guider)
         if self.video_decoder is None:
             return latent
         video = decode_video(latent, self.video_decoder, config.tiling_config)             # no automatic tiling here

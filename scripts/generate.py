@@ -624,9 +624,37 @@ _ROUTE_EXCLUDES = {
                 "with pipeline_type='ic-lora': ICLoraPipeline is video-only, conditions on its control video and image_path alone and ends "
                 "with its own x2 spatial stage"),
 }
-# route -> the _OUT_OF_PATH_DEFAULTS arguments that route takes itself
-_ROUTE_OWNS = {"keyframe": ("keyframes",), "hq": ("distilled_lora", "keyframes"),
-               "ic_lora": ("control_video", "save_control", "keyframes", "ic_lora_weights")}
+# route -> the _OUT_OF_PATH_DEFAULTS arguments that route takes itself.  apg_scale: the routes whose guided loop takes a guider (the AudioVideo route as
+# OneStagePipeline's guider_override, keyframe stage 1, retake's guided mode)
+_ROUTE_OWNS = {"keyframe": ("keyframes", "apg_scale"), "hq": ("distilled_lora", "keyframes"),
+               "ic_lora": ("control_video", "save_control", "keyframes", "ic_lora_weights"), "retake": ("apg_scale",), "av": ("apg_scale",)}
+
+
+def _owning_route(r):
+    """The route whose _ROUTE_OWNS entry decides about apg_scale, before the checkpoint has been looked at: the named one (a distilled retake runs
+    without guidance and owns no guider), else "av" when OneStagePipeline will run (generate_audio or an LTX-2.3 checkpoint, without two_stage_distilled)."""
+    if r.route == "retake":
+        return None if r.model_variant == "distilled" else "retake"
+    if r.route is not None or r.two_stage_distilled:
+        return r.route
+    have_ckpt = bool(r.weights_path) and os.path.exists(r.weights_path)
+    version = r.model_version if r.model_version is not None else (detect_model_version(r.weights_path) if have_ckpt else "")
+    return "av" if (r.generate_audio or str(version).startswith("2.3")) else None
+
+
+def _apg_guider(r):
+    """The guider of apg_scale / apg_eta / apg_norm_threshold / apg_momentum (reference :1226-1242, with its lines :1033-1036 and :1242); None at apg_scale 1."""
+    if r.apg_scale == 1.0:
+        return None
+    from ltx_2_mlx_amd.components import LegacyStatefulAPGGuider, LtxAPGGuider
+    print(f"APG guidance: scale={r.apg_scale}, eta={r.apg_eta}, norm_threshold={r.apg_norm_threshold}")
+    if r.apg_momentum > 0:
+        print(f"  Using stateful APG with momentum={r.apg_momentum}")
+        guider = LegacyStatefulAPGGuider(scale=r.apg_scale, eta=r.apg_eta, norm_threshold=r.apg_norm_threshold, momentum=r.apg_momentum)
+    else:
+        guider = LtxAPGGuider(scale=r.apg_scale, eta=r.apg_eta, norm_threshold=r.apg_norm_threshold)
+    print("  APG guidance enabled (replaces standard CFG)")
+    return guider
 
 
 def _refuse_combinations(r):
@@ -730,8 +758,9 @@ def _resolve_request(kw: dict):
         _resolve_retake(r)
     # Gemma encodes the prompt (and the negative prompt) when its weights are there and no pre-computed encoding is given
     r.gemma_encodes = bool(r.use_gemma and not (r.embedding_path or r.text_features_path) and r.gemma_path and os.path.exists(r.gemma_path))
+    owns = _ROUTE_OWNS.get(_owning_route(r) if r.apg_scale != 1.0 else r.route, ())
     for k, default in _OUT_OF_PATH_DEFAULTS.items():
-        if k in _ROUTE_OWNS.get(r.route, ()) or (k == "negative_prompt" and r.gemma_encodes):
+        if k in owns or (k == "negative_prompt" and r.gemma_encodes):
             continue
         v = (r.enhance_prompt_flag and r.use_gemma) if k == "enhance_prompt_flag" else getattr(r, k)
         if v != default:
@@ -780,6 +809,7 @@ def _resolve_request(kw: dict):
         r.audio_cfg_scale = 1.0 if r.model_variant == "distilled" else 7.0
     if r.rescale_scale is None:
         r.rescale_scale = 0.0 if r.model_variant == "distilled" else 0.7
+    r.apg_guider = _apg_guider(r)
     r.negative_encoding = r.negative_audio_encoding = None
     if r.embedding_path and os.path.exists(r.embedding_path):
         with np.load(r.embedding_path) as z:                # optional entries of the pre-computed embedding file: the negative prompt's encodings
@@ -793,7 +823,7 @@ def _resolve_request(kw: dict):
     r.v2 = str(r.version).startswith("2.3")
     r.av = bool(r.generate_audio or r.v2)
     # the video-only loop of the reference guides only for cfg_scale > 1 (:1935); OneStagePipeline's guiders are enabled for any scale != 1
-    r.need_cfg = (r.cfg_scale != 1.0 or r.audio_cfg_scale != 1.0) if r.av else r.cfg_scale > 1.0
+    r.need_cfg = (r.cfg_scale != 1.0 or r.audio_cfg_scale != 1.0 or r.apg_guider is not None) if r.av else r.cfg_scale > 1.0
     if r.audio_path:
         if r.two_stage_distilled:
             raise NotImplementedError("audio_path (--audio) with two_stage_distilled: DistilledPipeline with a given audio latent is not built")
@@ -817,7 +847,7 @@ def _resolve_request(kw: dict):
     if r.low_memory or r.fast_mode:
         print("  low_memory / fast_mode: no effect here (weights and caches stay resident in HBM, the loop is one hipGraph)")
     # the routes that guide themselves take Gemma's encoding of the negative prompt when they will guide (retake: the dev variant only)
-    r.encode_negative = r.cfg_scale != 1.0 and (r.route in ("keyframe", "hq") or (r.route == "retake" and r.model_variant != "distilled"))
+    r.encode_negative = (r.cfg_scale != 1.0 or r.apg_guider is not None) and (r.route in ("keyframe", "hq") or (r.route == "retake" and r.model_variant != "distilled"))
     r.toy = r.vae_base_channels is not None and r.vae_base_channels != 128        # debug-size VAE: matching debug-size upscaler / encoder
     if r.route is None:
         r.route = "two_stage" if r.two_stage_distilled else "av" if r.av else "standard"
@@ -1041,10 +1071,11 @@ def _run_keyframe(r, s):
     _banners(r, upscaler=True)
     pipe = KeyframeInterpolationPipeline(s.model, make_encoder(r), s.vae_decoder, spatial_upscaler=_load_or_random(
         r, "spatial", r.spatial_upscaler_weights or "weights/ltx-2/ltx-2-spatial-upscaler-x2-1.0.safetensors"))
-    _negative_or_zeros_note(conf.cfg_scale != 1.0, s.negative_encoding)
+    _negative_or_zeros_note(conf.cfg_scale != 1.0 or r.apg_guider is not None, s.negative_encoding)
     print(f"[5/5] Running keyframe interpolation ({r.num_steps} steps)...")
+    guider = dict(guider=r.apg_guider) if r.apg_guider is not None else {}
     frames, _ = _timed_run("keyframe interpolation",
-                           lambda: pipe(s.text_encoding, None, r.parsed_keyframes, conf, negative_text_encoding=s.negative_encoding), tokens_of=pipe)
+                           lambda: pipe(s.text_encoding, None, r.parsed_keyframes, conf, negative_text_encoding=s.negative_encoding, **guider), tokens_of=pipe)
     return finish(r, s, frames)
 
 
@@ -1121,9 +1152,10 @@ def _run_retake(r, s):
           + (", source frames kept outside it" if r.retake_composite else ""))
     _banners(r, upscaler=False)
     pipe = RetakePipeline(s.model, make_encoder(r), s.vae_decoder)
-    _negative_or_zeros_note(not distilled and r.cfg_scale > 1.0, s.negative_encoding)
+    _negative_or_zeros_note(not distilled and (r.cfg_scale > 1.0 or r.apg_guider is not None), s.negative_encoding)
     print(f"[5/5] Running retake ({'8 distilled steps' if distilled else f'{r.num_steps} steps, cfg {r.cfg_scale}'})...")
-    frames, _ = _timed_run("retake", lambda: pipe(r.retake_video, s.text_encoding, None, conf, negative_text_encoding=s.negative_encoding))
+    guider = dict(guider=r.apg_guider) if r.apg_guider is not None else {}
+    frames, _ = _timed_run("retake", lambda: pipe(r.retake_video, s.text_encoding, None, conf, negative_text_encoding=s.negative_encoding, **guider))
     return finish(r, s, frames, source_fps=r.retake_fps)
 
 
@@ -1175,7 +1207,7 @@ def _run_av(r, s):
     frames, audio_latent = _timed_run("audio-video pipeline", lambda: av_pipeline(
         positive_encoding=s.text_encoding, negative_encoding=s.negative_encoding if r.need_cfg else None, config=av_config, images=images,
         positive_audio_encoding=s.text_audio_encoding, negative_audio_encoding=s.negative_audio_encoding if r.need_cfg else None,
-        initial_audio_latent=given_audio[0] if given_audio else None))
+        initial_audio_latent=given_audio[0] if given_audio else None, **(dict(guider_override=r.apg_guider) if r.apg_guider is not None else {})))
     if given_audio:
         # the frozen latent is kept; the ORIGINAL audio goes into the mp4 (the reference returns the original waveform, not a decode)
         import shutil
