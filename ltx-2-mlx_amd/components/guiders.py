@@ -2,7 +2,7 @@
 
 Host-side glue of the guided single-stage loops: two x0 predictions (positive / negative prompt) per step are combined here in
 fp32 on the device (element-wise ops and dot products over a (B, N, C) tensor).  pipelines.common.projected_denoise_loop runs the
-same guiders as two kernels per step (csrc/guidance.hip).  STG guiders are outside the path."""
+same guiders as two kernels per step (csrc/sampler.hip).  STG guiders are outside the path."""
 from __future__ import annotations
 
 from dataclasses import dataclass, field

@@ -8,6 +8,7 @@
 #include "gemm.h"
 #include "gemma.h"
 #include "rowops.h"
+#include "sampler.h"
 
 static thread_local char g_err[512] = "";
 

@@ -138,6 +138,28 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// Individually rounded fp32 operations for the kernels that replace separate torch ops bit for bit.  HIP's __fmul_rn / __fadd_rn /
+// __fsub_rn are plain operators in the headers, and once inlined hipcc contracts them into FMAs like any other a * b + c (the tile blend
+// then differed from the three torch statements in the last bit); operators compiled under contract(off) carry no such licence.
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ float add_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+__device__ __forceinline__ float sub_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a - b;
+}
+
+// blocks of a grid-stride launch: one thread per element up to `cap` blocks
+inline int grid_for(long n, int block, int cap = 4096) {
+    long g = (n + block - 1) / block;
+    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
+}
+
 // Bijective XCD-aware remap of a 1-D block id: consecutive logical ids land on the same
 // XCD (observed placement: hardware block b -> XCD b % 8), so neighbouring tiles share an L2.
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {

@@ -216,19 +216,6 @@ __global__ __launch_bounds__(256) void frames_to_patches_kernel(const unsigned c
 // would fuse a*b + c into an FMA, which torch's separate statements are not), so the result is theirs bit for bit.
 // A block transposes a 32 x 32 tile through LDS as vae_prepare_latent_kernel does: reads run along positions, writes along channels.
 // ------------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float mul_rn(float a, float b) {
-#pragma clang fp contract(off)
-    return a * b;
-}
-__device__ __forceinline__ float add_rn(float a, float b) {
-#pragma clang fp contract(off)
-    return a + b;
-}
-__device__ __forceinline__ float sub_rn(float a, float b) {
-#pragma clang fp contract(off)
-    return a - b;
-}
-
 __global__ __launch_bounds__(256) void retake_prepare_kernel(const float* __restrict__ encoded, const float* __restrict__ noise, int C, long P,
                                                              long tok0, long tok1, float noise_scale, float* __restrict__ clean,
                                                              float* __restrict__ mask, float* __restrict__ latent) {

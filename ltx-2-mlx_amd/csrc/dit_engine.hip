@@ -26,6 +26,7 @@
 #include "attention.h"
 #include "gemm.h"
 #include "rowops.h"
+#include "sampler.h"
 
 #define TRY(expr)                       \
     do {                                \
@@ -1230,60 +1231,25 @@ int guided_ready(ltx2_dit* c, ltx2_dit* neg, int n_ts, const char* who) {
     return LTX2_OK;
 }
 
+// One evaluation of `latent` at (ts, sigma) through c into c's velocity buffer and, with a negative context, a second through neg into neg's
+int evaluate_pair(ltx2_dit* c, ltx2_dit* neg, const float* latent, const float* ts, int n_ts, const float* sigma, hipStream_t st) {
+    const ModIn pos[1] = {{latent, ts, n_ts, sigma, c->m[0].vel}};
+    TRY(forward(c, pos, st));
+    if (!neg) return LTX2_OK;
+    const ModIn ngt[1] = {{latent, ts, n_ts, sigma, neg->m[0].vel}};
+    return forward(neg, ngt, st);
+}
+
 // in: (latent, timesteps, sigma) of the step, read by both contexts; io: the latent it updates and its conditioning
 int guided_step(ltx2_dit* c, ltx2_dit* neg, const ModIn& in, const StepIo& io, float cfg_scale, float sigma, float sigma_next, hipStream_t st) {
     LTX2_CHECK_ARG(sigma != 0.f, "Sigma can't be 0.0");
     LTX2_CHECK_ARG((io.mask == nullptr) == (io.clean == nullptr), "dit_guided_step: mask and clean go together");
     const Mod& m = c->m[0];
-    const ModIn pos[1] = {{in.latent, in.ts, in.n_ts, in.sigma, m.vel}};
-    const ModIn ngt[1] = {{in.latent, in.ts, in.n_ts, in.sigma, neg->m[0].vel}};
-    TRY(forward(c, pos, st));
-    TRY(forward(neg, ngt, st));
+    TRY(evaluate_pair(c, neg, in.latent, in.ts, in.n_ts, in.sigma, st));
     return guided_euler_step_launch(in.latent, m.vel, neg->m[0].vel, in.ts, in.n_ts == 1 ? 0 : 1, io.mask, io.clean, cfg_scale, sigma, sigma_next, io.latent,
                                     m.N, m.Cout, st);
 }
-
-// The one captured sampling loop behind every ltx2_dit_graph_capture* entry: per step, sigma_i read on the device, each modality's timesteps (sigma_i, or
-// mask * sigma_i where it is conditioned), then a denoise step -- or, with a negative context, a guided step (VideoOnly: latent[0] / cond[0] only).
-// The event pool is rewound on step 0 only, so no event is re-recorded inside the capture; a guided step forms ts = mask * sigma_i in c's buffer and
-// both contexts read it.
-int capture_loop(ltx2_dit* c, ltx2_dit* neg, float cfg_scale, float* const latent[2], const Cond cond[2], const float* host_sigmas, int n_steps, hipStream_t st) {
-    const int nm = c->av ? 2 : 1;
-    TRY(begin_capture(c, host_sigmas, n_steps, st));
-    int rc = LTX2_OK;
-    for (int i = 0; i < n_steps && rc == LTX2_OK; ++i) {
-        const float* s = c->sigmas_dev + i;
-        ModIn in[2];
-        StepIo io[2];
-        for (int k = 0; k < nm && rc == LTX2_OK; ++k) {
-            in[k] = {latent[k], s, 1, s, nullptr};
-            io[k] = {latent[k], nullptr, nullptr, nullptr};
-            rc = cond_modality(c, k, cond[k], s, in[k], io[k], st);
-        }
-        if (rc != LTX2_OK) break;
-        rc = neg ? guided_step(c, neg, in[0], io[0], cfg_scale, host_sigmas[i], host_sigmas[i + 1], st)
-                 : denoise_step(c, in, io, host_sigmas[i], host_sigmas[i + 1], st, i == 0);
-    }
-    return end_capture(c, rc, st);
-}
 }  // namespace
-
-int ltx2_dit_graph_capture(ltx2_dit* c, float* latent, const float* host_sigmas, int n_steps, void* stream) {
-    LTX2_CHECK_ARG(latent && host_sigmas && n_steps > 0 && n_steps < 64, "dit_graph_capture: bad argument");
-    TRY(check_ready(c, "dit_graph_capture", false));
-    float* const lat[2] = {latent, nullptr};
-    const Cond none[2] = {};
-    return capture_loop(c, nullptr, 0.f, lat, none, host_sigmas, n_steps, (hipStream_t)stream);
-}
-
-int ltx2_dit_graph_capture_cond(ltx2_dit* c, float* latent, const float* host_sigmas, int n_steps, const float* mask, int64_t n_mask, const float* clean,
-                                int64_t n_clean, void* stream) {
-    LTX2_CHECK_ARG(latent && host_sigmas && n_steps > 0 && n_steps < 64, "dit_graph_capture_cond: bad argument");
-    TRY(check_ready(c, "dit_graph_capture_cond", false));
-    float* const lat[2] = {latent, nullptr};
-    const Cond cond[2] = {{mask, (long)n_mask, clean, (long)n_clean}, {}};
-    return capture_loop(c, nullptr, 0.f, lat, cond, host_sigmas, n_steps, (hipStream_t)stream);
-}
 
 int ltx2_dit_guided_step(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev,
                          const float* mask, const float* clean, float cfg_scale, float sigma, float sigma_next, void* stream) {
@@ -1294,17 +1260,7 @@ int ltx2_dit_guided_step(ltx2_dit* c, ltx2_dit* neg, float* latent, const float*
     return guided_step(c, neg, in, io, cfg_scale, sigma, sigma_next, (hipStream_t)stream);
 }
 
-int ltx2_dit_graph_capture_guided(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* host_sigmas, int n_steps, const float* mask,
-                                  int64_t n_mask, const float* clean, int64_t n_clean, float cfg_scale, void* stream) {
-    LTX2_CHECK_ARG(latent && host_sigmas && n_steps > 0 && n_steps < 64, "dit_graph_capture_guided: bad argument");
-    TRY(guided_ready(c, neg, mask ? c->m[0].N : 1, "dit_graph_capture_guided"));
-    LTX2_CHECK_ARG((mask == nullptr) == (clean == nullptr), "dit_graph_capture_guided: mask and clean go together");
-    float* const lat[2] = {latent, nullptr};
-    const Cond cond[2] = {{mask, (long)n_mask, clean, (long)n_clean}, {}};
-    return capture_loop(c, neg, cfg_scale, lat, cond, host_sigmas, n_steps, (hipStream_t)stream);
-}
-
-// Guidance whose scalars are sums over the whole latent (CFG*, APG, legacy APG with momentum; csrc/guidance.hip): the guided step above with the
+// Guidance whose scalars are sums over the whole latent (CFG*, APG, legacy APG with momentum; csrc/sampler.hip): the guided step above with the
 // one element-wise pass replaced by the sums kernel and the projected step kernel.  Linear on the caller's stream as well.
 namespace {
 struct Projected {      // the guider of a projected step: mode 0 CFG*, 1 APG, 2 legacy APG
@@ -1357,10 +1313,7 @@ int projected_step(ltx2_dit* c, ltx2_dit* neg, const ModIn& in, const StepIo& io
     const Mod& m = c->m[0];
     LTX2_CHECK_ARG(c->pg_part && c->pg_rows == guidance_sums_blocks(m.N, m.Cout) && (!g.running() || (c->pg_run && c->pg_run_n == (long)m.N * m.Cout)),
                    "dit_projected_step: workspace missing");
-    const ModIn pos[1] = {{in.latent, in.ts, in.n_ts, in.sigma, m.vel}};
-    const ModIn ngt[1] = {{in.latent, in.ts, in.n_ts, in.sigma, neg->m[0].vel}};
-    TRY(forward(c, pos, st));
-    TRY(forward(neg, ngt, st));
+    TRY(evaluate_pair(c, neg, in.latent, in.ts, in.n_ts, in.sigma, st));
     float* run = g.running() ? c->pg_run : nullptr;
     const long stride = in.n_ts == 1 ? 0 : 1;
     TRY(guidance_sums_launch(in.latent, m.vel, neg->m[0].vel, in.ts, stride, run, first, g.momentum, c->pg_part, m.N, m.Cout, st));
@@ -1380,34 +1333,6 @@ int ltx2_dit_projected_step(ltx2_dit* c, ltx2_dit* neg, float* latent, const flo
     const ModIn in = {latent, timesteps, n_timesteps, sigma_dev ? sigma_dev : timesteps, nullptr};
     const StepIo io = {latent, mask, clean, nullptr};
     return projected_step(c, neg, in, io, g, first, sigma, sigma_next, (hipStream_t)stream);
-}
-
-int ltx2_dit_graph_capture_projected(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* host_sigmas, int n_steps, const float* mask, int64_t n_mask,
-                                     const float* clean, int64_t n_clean, int mode, float scale, float eta, float norm_threshold, float momentum,
-                                     void* stream) {
-    LTX2_CHECK_ARG(latent && host_sigmas && n_steps > 0 && n_steps < 64, "dit_graph_capture_projected: bad argument");
-    TRY(guided_ready(c, neg, mask ? c->m[0].N : 1, "dit_graph_capture_projected"));
-    LTX2_CHECK_ARG((mask == nullptr) == (clean == nullptr), "dit_graph_capture_projected: mask and clean go together");
-    const Projected g = {mode, scale, eta, norm_threshold, momentum};
-    TRY(projected_check(g, "dit_graph_capture_projected"));
-    TRY(projected_workspace(c, g.running(), false));
-    hipStream_t st = (hipStream_t)stream;
-    const Cond cond = {mask, (long)n_mask, clean, (long)n_clean};
-    TRY(begin_capture(c, host_sigmas, n_steps, st));
-    int rc = LTX2_OK;
-    // the head of the chain: every replay starts from a cleared running guidance
-    if (g.running() && hipMemsetAsync(c->pg_run, 0, 4L * c->pg_run_n, st) != hipSuccess) {
-        ltx2_set_error("dit_graph_capture_projected: hipMemsetAsync failed");
-        rc = LTX2_E_HIP;
-    }
-    for (int i = 0; i < n_steps && rc == LTX2_OK; ++i) {
-        const float* s = c->sigmas_dev + i;
-        ModIn in = {latent, s, 1, s, nullptr};
-        StepIo io = {latent, nullptr, nullptr, nullptr};
-        rc = cond_modality(c, 0, cond, s, in, io, st);          // ts = mask * sigma_i into c's buffer; both contexts read it
-        if (rc == LTX2_OK) rc = projected_step(c, neg, in, io, g, i == 0, host_sigmas[i], host_sigmas[i + 1], st);
-    }
-    return end_capture(c, rc, st);
 }
 
 // The res_2s second-order step (reference pipelines/ti2vid_hq.py:185-273; HQ pipeline stage 1): per step two pairs of evaluations, the second
@@ -1482,16 +1407,7 @@ int res2s_step(ltx2_dit* c, ltx2_dit* neg, const ModIn& in, const float* ts_sub,
     float *x_mid = c->r2s, *anchor = c->r2s + c->r2s_each, *eps1 = c->r2s + 2 * c->r2s_each;
     const float* vu = neg ? neg->m[0].vel : nullptr;
     const long stride = in.n_ts == 1 ? 0 : 1;
-    auto evaluate = [&](const float* latent, const float* ts, const float* sg) -> int {
-        const ModIn pos[1] = {{latent, ts, in.n_ts, sg, m.vel}};
-        TRY(forward(c, pos, st));
-        if (neg) {
-            const ModIn ngt[1] = {{latent, ts, in.n_ts, sg, neg->m[0].vel}};
-            TRY(forward(neg, ngt, st));
-        }
-        return LTX2_OK;
-    };
-    TRY(evaluate(in.latent, in.ts, in.sigma));
+    TRY(evaluate_pair(c, neg, in.latent, in.ts, in.n_ts, in.sigma, st));
     if (p.last)
         return res2s_midpoint_launch(in.latent, m.vel, vu, in.ts, stride, io.mask, io.clean, cfg_scale, 0.f, 0, io.latent, nullptr, nullptr, m.N, m.Cout, st);
     TRY(res2s_midpoint_launch(in.latent, m.vel, vu, in.ts, stride, io.mask, io.clean, cfg_scale, p.c, p.n_bong, x_mid, anchor, eps1, m.N, m.Cout, st));
@@ -1501,8 +1417,55 @@ int res2s_step(ltx2_dit* c, ltx2_dit* neg, const ModIn& in, const float* ts_sub,
         ts_sub = m.ts_tok;
     }
     LTX2_CHECK_ARG(ts_sub && sub_sigma, "dit_res2s_step: the sub-sigma timesteps are missing");
-    TRY(evaluate(x_mid, ts_sub, sub_sigma));
+    TRY(evaluate_pair(c, neg, x_mid, ts_sub, in.n_ts, sub_sigma, st));
     return res2s_combine_launch(x_mid, m.vel, vu, ts_sub, stride, io.mask, io.clean, cfg_scale, anchor, eps1, p.h, p.b1, p.b2, io.latent, m.N, m.Cout, st);
+}
+
+// The one captured sampling loop behind every ltx2_dit_graph_capture* entry: per step, sigma_i read on the device, each modality's timesteps (sigma_i, or
+// mask * sigma_i where it is conditioned), then the step that LoopStep names.  All but the plain step run on VideoOnly contexts (latent[0] / cond[0]
+// only), form ts = mask * sigma_i in c's buffer and let both contexts read it.  The event pool is rewound on step 0 only, so no event is re-recorded
+// inside the capture.
+struct LoopStep {                           // all defaults: the plain denoise step
+    ltx2_dit* neg = nullptr;                // the negative prompt's context: a guided step, or guidance inside the two below
+    float cfg_scale = 0.f;
+    const Projected* projected = nullptr;   // the projected step with this guider
+    const Res2sPlan* res2s = nullptr;       // the res_2s step: one plan per step
+};
+
+int capture_loop(ltx2_dit* c, const LoopStep& step, float* const latent[2], const Cond cond[2], const float* host_sigmas, int n_steps, hipStream_t st) {
+    const int nm = c->av ? 2 : 1;
+    float sub[64];
+    for (int i = 0; step.res2s && i < n_steps; ++i) sub[i] = step.res2s[i].sub_sigma;
+    TRY(begin_capture(c, host_sigmas, n_steps, st, step.res2s ? sub : nullptr));
+    int rc = LTX2_OK;
+    // the head of the chain: every replay starts from a cleared running guidance
+    if (step.projected && step.projected->running() && hipMemsetAsync(c->pg_run, 0, 4L * c->pg_run_n, st) != hipSuccess) {
+        ltx2_set_error("dit_graph_capture_projected: hipMemsetAsync failed");
+        rc = LTX2_E_HIP;
+    }
+    for (int i = 0; i < n_steps && rc == LTX2_OK; ++i) {
+        const float *s = c->sigmas_dev + i, *ss = c->sigmas_dev + 64 + i;
+        const float sigma = host_sigmas[i], sigma_next = host_sigmas[i + 1];
+        ModIn in[2];
+        StepIo io[2];
+        for (int k = 0; k < nm && rc == LTX2_OK; ++k) {
+            in[k] = {latent[k], s, 1, s, nullptr};
+            io[k] = {latent[k], nullptr, nullptr, nullptr};
+            rc = cond_modality(c, k, cond[k], s, in[k], io[k], st);
+        }
+        if (rc != LTX2_OK) break;
+        if (step.res2s) {
+            rc = res2s_step(c, step.neg, in[0], ss, ss, &cond[0], io[0], step.cfg_scale, step.res2s[i], st);
+            if (step.res2s[i].last) break;                      // the reference's loop ends on its final step
+        } else if (step.projected) {
+            rc = projected_step(c, step.neg, in[0], io[0], *step.projected, i == 0, sigma, sigma_next, st);
+        } else if (step.neg) {
+            rc = guided_step(c, step.neg, in[0], io[0], step.cfg_scale, sigma, sigma_next, st);
+        } else {
+            rc = denoise_step(c, in, io, sigma, sigma_next, st, i == 0);
+        }
+    }
+    return end_capture(c, rc, st);
 }
 }  // namespace
 
@@ -1526,25 +1489,52 @@ int ltx2_dit_graph_capture_res2s(ltx2_dit* c, ltx2_dit* neg, float* latent, cons
     TRY(res2s_ready(c, neg, mask ? c->m[0].N : 1, "dit_graph_capture_res2s"));
     LTX2_CHECK_ARG((mask == nullptr) == (clean == nullptr), "dit_graph_capture_res2s: mask and clean go together");
     Res2sPlan plan[64];
-    float sub[64];
-    for (int i = 0; i < n_steps; ++i) {
-        TRY(res2s_plan(host_sigmas[i], host_sigmas[i + 1], plan[i]));
-        sub[i] = plan[i].sub_sigma;
-    }
+    for (int i = 0; i < n_steps; ++i) TRY(res2s_plan(host_sigmas[i], host_sigmas[i + 1], plan[i]));
     TRY(res2s_workspace(c));
-    hipStream_t st = (hipStream_t)stream;
-    const Cond cond = {mask, (long)n_mask, clean, (long)n_clean};
-    TRY(begin_capture(c, host_sigmas, n_steps, st, sub));
-    int rc = LTX2_OK;
-    for (int i = 0; i < n_steps && rc == LTX2_OK; ++i) {
-        const float *s = c->sigmas_dev + i, *ss = c->sigmas_dev + 64 + i;
-        ModIn in = {latent, s, 1, s, nullptr};
-        StepIo io = {latent, nullptr, nullptr, nullptr};
-        rc = cond_modality(c, 0, cond, s, in, io, st);          // ts = mask * sigma_i into c's buffer; both contexts read it
-        if (rc == LTX2_OK) rc = res2s_step(c, neg, in, ss, ss, &cond, io, cfg_scale, plan[i], st);
-        if (plan[i].last) break;                                // the reference's loop ends on its final step
-    }
-    return end_capture(c, rc, st);
+    float* const lat[2] = {latent, nullptr};
+    const Cond cond[2] = {{mask, (long)n_mask, clean, (long)n_clean}, {}};
+    return capture_loop(c, {neg, cfg_scale, nullptr, plan}, lat, cond, host_sigmas, n_steps, (hipStream_t)stream);
+}
+
+int ltx2_dit_graph_capture(ltx2_dit* c, float* latent, const float* host_sigmas, int n_steps, void* stream) {
+    LTX2_CHECK_ARG(latent && host_sigmas && n_steps > 0 && n_steps < 64, "dit_graph_capture: bad argument");
+    TRY(check_ready(c, "dit_graph_capture", false));
+    float* const lat[2] = {latent, nullptr};
+    const Cond none[2] = {};
+    return capture_loop(c, {}, lat, none, host_sigmas, n_steps, (hipStream_t)stream);
+}
+
+int ltx2_dit_graph_capture_cond(ltx2_dit* c, float* latent, const float* host_sigmas, int n_steps, const float* mask, int64_t n_mask, const float* clean,
+                                int64_t n_clean, void* stream) {
+    LTX2_CHECK_ARG(latent && host_sigmas && n_steps > 0 && n_steps < 64, "dit_graph_capture_cond: bad argument");
+    TRY(check_ready(c, "dit_graph_capture_cond", false));
+    float* const lat[2] = {latent, nullptr};
+    const Cond cond[2] = {{mask, (long)n_mask, clean, (long)n_clean}, {}};
+    return capture_loop(c, {}, lat, cond, host_sigmas, n_steps, (hipStream_t)stream);
+}
+
+int ltx2_dit_graph_capture_guided(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* host_sigmas, int n_steps, const float* mask,
+                                  int64_t n_mask, const float* clean, int64_t n_clean, float cfg_scale, void* stream) {
+    LTX2_CHECK_ARG(latent && host_sigmas && n_steps > 0 && n_steps < 64, "dit_graph_capture_guided: bad argument");
+    TRY(guided_ready(c, neg, mask ? c->m[0].N : 1, "dit_graph_capture_guided"));
+    LTX2_CHECK_ARG((mask == nullptr) == (clean == nullptr), "dit_graph_capture_guided: mask and clean go together");
+    float* const lat[2] = {latent, nullptr};
+    const Cond cond[2] = {{mask, (long)n_mask, clean, (long)n_clean}, {}};
+    return capture_loop(c, {neg, cfg_scale}, lat, cond, host_sigmas, n_steps, (hipStream_t)stream);
+}
+
+int ltx2_dit_graph_capture_projected(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* host_sigmas, int n_steps, const float* mask, int64_t n_mask,
+                                     const float* clean, int64_t n_clean, int mode, float scale, float eta, float norm_threshold, float momentum,
+                                     void* stream) {
+    LTX2_CHECK_ARG(latent && host_sigmas && n_steps > 0 && n_steps < 64, "dit_graph_capture_projected: bad argument");
+    TRY(guided_ready(c, neg, mask ? c->m[0].N : 1, "dit_graph_capture_projected"));
+    LTX2_CHECK_ARG((mask == nullptr) == (clean == nullptr), "dit_graph_capture_projected: mask and clean go together");
+    const Projected g = {mode, scale, eta, norm_threshold, momentum};
+    TRY(projected_check(g, "dit_graph_capture_projected"));
+    TRY(projected_workspace(c, g.running(), false));
+    float* const lat[2] = {latent, nullptr};
+    const Cond cond[2] = {{mask, (long)n_mask, clean, (long)n_clean}, {}};
+    return capture_loop(c, {neg, 0.f, &g}, lat, cond, host_sigmas, n_steps, (hipStream_t)stream);
 }
 
 int ltx2_dit_graph_capture_cond_av(ltx2_dit* c, float* v_latent, float* a_latent, const float* host_sigmas, int n_steps, const float* v_mask, int64_t n_v_mask,
@@ -1553,7 +1543,7 @@ int ltx2_dit_graph_capture_cond_av(ltx2_dit* c, float* v_latent, float* a_latent
     TRY(check_ready(c, "dit_graph_capture_cond_av", true));
     float* const lat[2] = {v_latent, a_latent};
     const Cond cond[2] = {{v_mask, (long)n_v_mask, v_clean, (long)n_v_clean}, {a_mask, (long)n_a_mask, a_clean, (long)n_a_clean}};
-    return capture_loop(c, nullptr, 0.f, lat, cond, host_sigmas, n_steps, (hipStream_t)stream);
+    return capture_loop(c, {}, lat, cond, host_sigmas, n_steps, (hipStream_t)stream);
 }
 
 int ltx2_dit_graph_capture_av(ltx2_dit* c, float* v_latent, float* a_latent, const float* host_sigmas, int n_steps,
@@ -1562,7 +1552,7 @@ int ltx2_dit_graph_capture_av(ltx2_dit* c, float* v_latent, float* a_latent, con
     TRY(check_ready(c, "dit_graph_capture_av", true));
     float* const lat[2] = {v_latent, a_latent};
     const Cond none[2] = {};
-    return capture_loop(c, nullptr, 0.f, lat, none, host_sigmas, n_steps, (hipStream_t)stream);
+    return capture_loop(c, {}, lat, none, host_sigmas, n_steps, (hipStream_t)stream);
 }
 
 int ltx2_dit_profile_begin(ltx2_dit* c, int epilogue) {

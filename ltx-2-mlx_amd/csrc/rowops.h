@@ -61,44 +61,6 @@ int quant_rows_fp8_launch(const bf16* x, long ldx, int rows, int K, unsigned cha
 // out_bf16 = bf16(f32(fp8_e4m3fn) * scale): checkpoint weights quantised with a per-tensor weight_scale
 int dequant_fp8_launch(const unsigned char* in, float scale, bf16* out, long n, hipStream_t stream);
 
-// x0[row][c] = latent[row][c] - ts(row) * vel[row][c]   (ts = ts_ptr[row*ts_stride] if ts_ptr else ts_scalar)
-int x0_from_velocity_launch(const float* latent, const float* vel, const float* ts_ptr, long ts_stride, float ts_scalar,
-                            float* x0, int rows, int C, hipStream_t stream);
-
-// x0' = mask ? x0*mask(row) + clean*(1-mask(row)) : x0 ;  out = x + (x - x0')/sigma * (sigma_next - sigma)
-int euler_step_launch(const float* x, const float* x0, const float* mask, const float* clean, float sigma,
-                      float sigma_next, float* out, int rows, int C, hipStream_t stream);
-
-// One classifier-free-guided step in one pass, every operation individually rounded (the separate fp32 torch ops, bit for bit):
-// a = x - t*vc, b = x - t*vu, g = a + (cfg_scale - 1)*(a - b), d = mask ? g*m + clean*(1 - m) : g, out = x + ((x - d)/sigma)*(sigma_next - sigma);
-// t = ts[row * ts_stride] with ts_stride 0 or 1; out may equal x
-int guided_euler_step_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride,
-                             const float* mask, const float* clean, float cfg_scale, float sigma, float sigma_next, float* out,
-                             int rows, int C, hipStream_t stream);
-
-// The res_2s second-order step as two passes, every operation individually rounded; d(x, vc, vu) = the guided, mask-blended x0 in the HQ pipeline's
-// order: a = x - t*vc, b = x - t*vu, g = b + cfg*(a - b) (g = a when vu is NULL), d = mask ? g*m + clean*(1 - m) : g.
-// midpoint: an = x, e = d - an, xm = an + c*e, n_bong x {an = xm - c*e, e = d - an}; stores x_mid, anchor, eps1 (x_mid may be x).
-// anchor == eps1 == NULL: the final-step form, x_mid = d and nothing else.
-int res2s_midpoint_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride, const float* mask,
-                          const float* clean, float cfg_scale, float c, int n_bong, float* x_mid, float* anchor, float* eps1, int rows, int C,
-                          hipStream_t stream);
-// combine: e2 = d(x_mid, vc, vu) - anchor, out = anchor + h*(b1*eps1 + b2*e2); out may be any [rows][C] operand
-int res2s_combine_launch(const float* x_mid, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride, const float* mask,
-                         const float* clean, float cfg_scale, const float* anchor, const float* eps1, float h, float b1, float b2, float* out,
-                         int rows, int C, hipStream_t stream);
-
-// Guiders whose scalars are sums over the whole latent (guidance.hip; the definitions: include/ltx2hip.h).  sums: five fp64 sums per block into
-// partials[guidance_sums_blocks(rows, C)][5], and with `running` the momentum update of the guidance; step: every block adds the partial rows in
-// index order, derives the fp32 scalars and runs the guided, mask-blended Euler step.  out may equal x.
-int guidance_sums_blocks(int rows, int C);
-int guidance_sums_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride, float* running, int first,
-                         float momentum, double* partials, int rows, int C, hipStream_t stream);
-int projected_euler_step_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride, const float* mask,
-                                const float* clean, const float* running, const double* partials, int mode, float scale, float eta,
-                                float norm_threshold, float sigma, float sigma_next, float* out, float* scalars_out, int rows, int C,
-                                hipStream_t stream);
-
 // ---- spatial upscaler (channels-last bf16 [P][C]) ----
 // y = [silu]( GroupNorm_G(x over (C/G, all positions)) * gamma + beta + res );  scratch: 2*G*(1 + ceil(P/16)) floats
 int groupnorm_silu_launch(const bf16* x, const bf16* res, bf16* y, long P, int C, int G, float eps, const float* gamma,

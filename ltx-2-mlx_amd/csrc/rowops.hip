@@ -896,32 +896,6 @@ __global__ void cast_f32_bf16_kernel(const float* __restrict__ in, bf16* __restr
     }
 }
 
-__global__ void x0_from_velocity_kernel(const float* __restrict__ latent, const float* __restrict__ vel,
-                                        const float* __restrict__ ts_ptr, long ts_stride, float ts_scalar,
-                                        float* __restrict__ x0, int rows, int C) {
-    const long n = (long)rows * C;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const long row = i / C;
-        const float ts = ts_ptr ? ts_ptr[row * ts_stride] : ts_scalar;
-        x0[i] = latent[i] - ts * vel[i];
-    }
-}
-
-__global__ void euler_step_kernel(const float* __restrict__ x, const float* __restrict__ x0,
-                                  const float* __restrict__ mask, const float* __restrict__ clean, float inv_sigma,
-                                  float dt, float* __restrict__ out, int rows, int C) {
-    const long n = (long)rows * C;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        float d = x0[i];
-        if (mask) {
-            const float m = mask[i / C];
-            d = d * m + clean[i] * (1.f - m);
-        }
-        const float xv = x[i];
-        out[i] = xv + (xv - d) * inv_sigma * dt;
-    }
-}
-
 // ---------------------------------- VAE glue ----------------------------------
 __global__ void vae_prepare_latent_kernel(const float* __restrict__ latent, const float* __restrict__ stdv,
                                           const float* __restrict__ meanv, const float* __restrict__ noise,
@@ -1046,22 +1020,6 @@ __global__ void video_to_uint8_kernel(const float* __restrict__ video, unsigned 
     }
 }
 
-// Individually rounded fp32 operations for the kernels below that replace separate torch ops bit for bit.  HIP's __fmul_rn / __fadd_rn /
-// __fsub_rn are plain operators in the headers, and once inlined hipcc contracts them into FMAs like any other a * b + c (the tile blend
-// then differed from the three torch statements in the last bit); operators compiled under contract(off) carry no such licence.
-__device__ __forceinline__ float mul_rn(float a, float b) {
-#pragma clang fp contract(off)
-    return a * b;
-}
-__device__ __forceinline__ float add_rn(float a, float b) {
-#pragma clang fp contract(off)
-    return a + b;
-}
-__device__ __forceinline__ float sub_rn(float a, float b) {
-#pragma clang fp contract(off)
-    return a - b;
-}
-
 // One temporal chunk of decode_latent -> uint8 frames, cross-faded with the previous chunk on the first `ov` frames
 // (simple_decoder.py:760-798): frame j of `cur` lands on output frame t_dst0 + j; for j < ov the value is
 // prev[prev_T - ov + j] * (1 - ramp[j]) + cur[j] * ramp[j] with torch.linspace's ramp, rounded exactly like the separate torch
@@ -1117,158 +1075,6 @@ __global__ void tile_blend_finish_kernel(float* __restrict__ out, const float* _
 #pragma unroll
         for (int c = 0; c < 3; ++c) out[c * plane + i] = __fdiv_rn(out[c * plane + i], d);
     }
-}
-
-// One classifier-free-guided sampling step in one pass (pipelines/one_stage.py:224-330): the two x0_from_velocity launches, CFGGuider.guide,
-// post_process_latent and the Euler update, every operation rounded on its own so the result is, bit for bit, the separate fp32 torch ops
-// in that order.  V elements per thread (V divides C, so a vector never straddles a row); x and out may be the same buffer.
-__device__ __forceinline__ float guided_euler_one(float x, float vc, float vu, float t, float s1, bool blend, float m, float one_minus_m,
-                                                  float cl, float inv, float dt) {
-    const float a = sub_rn(x, mul_rn(t, vc));
-    const float b = sub_rn(x, mul_rn(t, vu));
-    float d = add_rn(a, mul_rn(s1, sub_rn(a, b)));
-    if (blend) d = add_rn(mul_rn(d, m), mul_rn(cl, one_minus_m));
-    return add_rn(x, mul_rn(mul_rn(sub_rn(x, d), inv), dt));
-}
-
-template <int V>
-__global__ void guided_euler_step_kernel(const float* x, const float* __restrict__ vc, const float* __restrict__ vu,
-                                         const float* __restrict__ ts, long ts_stride, const float* __restrict__ mask,
-                                         const float* __restrict__ clean, float s1, float inv, float dt, float* out, long n, int C) {
-    const long nv = n / V;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
-        const long e = i * V, row = e / C;
-        const float t = ts[row * ts_stride];
-        const bool blend = mask != nullptr;
-        const float m = blend ? mask[row] : 1.f, om = sub_rn(1.0f, m);
-        if constexpr (V == 4) {
-            const float4 xv = *(const float4*)(x + e), c4 = *(const float4*)(vc + e), u4 = *(const float4*)(vu + e);
-            float4 cl = {0.f, 0.f, 0.f, 0.f};
-            if (blend) cl = *(const float4*)(clean + e);
-            float4 o;
-            o.x = guided_euler_one(xv.x, c4.x, u4.x, t, s1, blend, m, om, cl.x, inv, dt);
-            o.y = guided_euler_one(xv.y, c4.y, u4.y, t, s1, blend, m, om, cl.y, inv, dt);
-            o.z = guided_euler_one(xv.z, c4.z, u4.z, t, s1, blend, m, om, cl.z, inv, dt);
-            o.w = guided_euler_one(xv.w, c4.w, u4.w, t, s1, blend, m, om, cl.w, inv, dt);
-            *(float4*)(out + e) = o;
-        } else {
-            out[e] = guided_euler_one(x[e], vc[e], vu[e], t, s1, blend, m, om, blend ? clean[e] : 0.f, inv, dt);
-        }
-    }
-}
-
-// The res_2s second-order step (reference pipelines/ti2vid_hq.py:153-273) as two passes over [rows][C], every operation rounded on its own
-// like the guided Euler step above.  The guided, mask-blended x0 of one pair of velocities, in the HQ pipeline's own order (:315):
-// a = x - t*vc, b = x - t*vu, g = b + cfg*(a - b) (g = a without vu), d = blend ? g*m + clean*(1 - m) : g.
-__device__ __forceinline__ float res2s_denoised(float x, float vc, float vu, bool guide, float t, float cfg, bool blend, float m, float one_minus_m,
-                                                float cl) {
-    float d = sub_rn(x, mul_rn(t, vc));
-    if (guide) {
-        const float b = sub_rn(x, mul_rn(t, vu));
-        d = add_rn(b, mul_rn(cfg, sub_rn(d, b)));
-    }
-    if (blend) d = add_rn(mul_rn(d, m), mul_rn(cl, one_minus_m));
-    return d;
-}
-
-// anchor = x, eps1 = d - anchor, x_mid = anchor + c*eps1, then the "bong" iteration (:232-238) n_bong times in registers:
-// anchor = x_mid - c*eps1, eps1 = d - anchor.  anchor == nullptr: the final-step form, x_mid = d and nothing else.
-__device__ __forceinline__ void res2s_midpoint_one(float x, float d, float c, int n_bong, float& xm, float& an, float& e) {
-    an = x;
-    e = sub_rn(d, an);
-    xm = add_rn(an, mul_rn(c, e));
-    for (int k = 0; k < n_bong; ++k) {
-        an = sub_rn(xm, mul_rn(c, e));
-        e = sub_rn(d, an);
-    }
-}
-
-// No __restrict__ on the [rows][C] operands: x_mid may be x.  A thread reads its own V elements of every operand before it stores any.
-template <int V>
-__global__ void res2s_midpoint_kernel(const float* x, const float* vc, const float* vu, const float* __restrict__ ts, long ts_stride,
-                                      const float* __restrict__ mask, const float* clean, float cfg, float c, int n_bong, float* x_mid,
-                                      float* anchor, float* eps1, long n, int C) {
-    const long nv = n / V;
-    const bool guide = vu != nullptr, blend = mask != nullptr, last = anchor == nullptr;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
-        const long e = i * V, row = e / C;
-        const float t = ts[row * ts_stride];
-        const float m = blend ? mask[row] : 1.f, om = sub_rn(1.0f, m);
-        alignas(16) float xs[V], cs[V], us[V], cl[V], xm[V], an[V], ep[V];
-        if constexpr (V == 4) {
-            *(float4*)xs = *(const float4*)(x + e);
-            *(float4*)cs = *(const float4*)(vc + e);
-            *(float4*)us = guide ? *(const float4*)(vu + e) : float4{0.f, 0.f, 0.f, 0.f};
-            *(float4*)cl = blend ? *(const float4*)(clean + e) : float4{0.f, 0.f, 0.f, 0.f};
-        } else {
-            xs[0] = x[e];
-            cs[0] = vc[e];
-            us[0] = guide ? vu[e] : 0.f;
-            cl[0] = blend ? clean[e] : 0.f;
-        }
-#pragma unroll
-        for (int j = 0; j < V; ++j) {
-            const float d = res2s_denoised(xs[j], cs[j], us[j], guide, t, cfg, blend, m, om, cl[j]);
-            if (last) xm[j] = d;
-            else res2s_midpoint_one(xs[j], d, c, n_bong, xm[j], an[j], ep[j]);
-        }
-        if constexpr (V == 4) {
-            *(float4*)(x_mid + e) = *(const float4*)xm;
-            if (!last) {
-                *(float4*)(anchor + e) = *(const float4*)an;
-                *(float4*)(eps1 + e) = *(const float4*)ep;
-            }
-        } else {
-            x_mid[e] = xm[0];
-            if (!last) {
-                anchor[e] = an[0];
-                eps1[e] = ep[0];
-            }
-        }
-    }
-}
-
-// d2 from (x_mid, velocities at the sub-sigma) as above, e2 = d2 - anchor, out = anchor + h*(b1*eps1 + b2*e2).  out may be any [rows][C] operand.
-template <int V>
-__global__ void res2s_combine_kernel(const float* x_mid, const float* vc, const float* vu, const float* __restrict__ ts, long ts_stride,
-                                     const float* __restrict__ mask, const float* clean, float cfg, const float* anchor, const float* eps1,
-                                     float h, float b1, float b2, float* out, long n, int C) {
-    const long nv = n / V;
-    const bool guide = vu != nullptr, blend = mask != nullptr;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
-        const long e = i * V, row = e / C;
-        const float t = ts[row * ts_stride];
-        const float m = blend ? mask[row] : 1.f, om = sub_rn(1.0f, m);
-        alignas(16) float xs[V], cs[V], us[V], cl[V], an[V], ep[V], o[V];
-        if constexpr (V == 4) {
-            *(float4*)xs = *(const float4*)(x_mid + e);
-            *(float4*)cs = *(const float4*)(vc + e);
-            *(float4*)us = guide ? *(const float4*)(vu + e) : float4{0.f, 0.f, 0.f, 0.f};
-            *(float4*)cl = blend ? *(const float4*)(clean + e) : float4{0.f, 0.f, 0.f, 0.f};
-            *(float4*)an = *(const float4*)(anchor + e);
-            *(float4*)ep = *(const float4*)(eps1 + e);
-        } else {
-            xs[0] = x_mid[e];
-            cs[0] = vc[e];
-            us[0] = guide ? vu[e] : 0.f;
-            cl[0] = blend ? clean[e] : 0.f;
-            an[0] = anchor[e];
-            ep[0] = eps1[e];
-        }
-#pragma unroll
-        for (int j = 0; j < V; ++j) {
-            const float d2 = res2s_denoised(xs[j], cs[j], us[j], guide, t, cfg, blend, m, om, cl[j]);
-            const float e2 = sub_rn(d2, an[j]);
-            o[j] = add_rn(an[j], mul_rn(h, add_rn(mul_rn(b1, ep[j]), mul_rn(b2, e2))));
-        }
-        if constexpr (V == 4) *(float4*)(out + e) = *(const float4*)o;
-        else out[e] = o[0];
-    }
-}
-
-inline int grid_for(long n, int block, int cap = 4096) {
-    long g = (n + block - 1) / block;
-    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
 }
 
 }  // namespace
@@ -1540,84 +1346,6 @@ int cast_f32_bf16_launch(const float* in, bf16* out, long n, hipStream_t stream)
     LTX2_CHECK_ARG(n > 0, "cast: empty");
     hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3(grid_for((n + 3) / 4, 256)), dim3(256), 0, stream, in, out, n);
     LTX2_CHECK_LAUNCH("cast_f32_bf16_kernel");
-    return LTX2_OK;
-}
-
-int x0_from_velocity_launch(const float* latent, const float* vel, const float* ts_ptr, long ts_stride, float ts_scalar,
-                            float* x0, int rows, int C, hipStream_t stream) {
-    hipLaunchKernelGGL(x0_from_velocity_kernel, dim3(grid_for((long)rows * C, 256)), dim3(256), 0, stream, latent, vel,
-                       ts_ptr, ts_stride, ts_scalar, x0, rows, C);
-    LTX2_CHECK_LAUNCH("x0_from_velocity_kernel");
-    return LTX2_OK;
-}
-
-int euler_step_launch(const float* x, const float* x0, const float* mask, const float* clean, float sigma,
-                      float sigma_next, float* out, int rows, int C, hipStream_t stream) {
-    LTX2_CHECK_ARG(sigma != 0.f, "Sigma can't be 0.0");   // reference core_utils.py:54-55
-    LTX2_CHECK_ARG((mask == nullptr) == (clean == nullptr), "euler_step: mask and clean go together");
-    hipLaunchKernelGGL(euler_step_kernel, dim3(grid_for((long)rows * C, 256)), dim3(256), 0, stream, x, x0, mask, clean,
-                       1.0f / sigma, sigma_next - sigma, out, rows, C);
-    LTX2_CHECK_LAUNCH("euler_step_kernel");
-    return LTX2_OK;
-}
-
-int guided_euler_step_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride,
-                             const float* mask, const float* clean, float cfg_scale, float sigma, float sigma_next, float* out,
-                             int rows, int C, hipStream_t stream) {
-    LTX2_CHECK_ARG(sigma != 0.f, "Sigma can't be 0.0");   // reference core_utils.py:54-55
-    LTX2_CHECK_ARG(x && vel_cond && vel_uncond && ts && out && rows > 0 && C > 0, "guided_euler_step: null operand or empty shape");
-    LTX2_CHECK_ARG(ts_stride == 0 || ts_stride == 1, "guided_euler_step: ts_stride is 0 (one timestep) or 1 (one per row)");
-    LTX2_CHECK_ARG((mask == nullptr) == (clean == nullptr), "guided_euler_step: mask and clean go together");
-    const long n = (long)rows * C;
-    const float s1 = cfg_scale - 1.0f, inv = 1.0f / sigma, dt = sigma_next - sigma;
-    // 16-byte accesses need every [rows][C] operand on a 16-byte boundary as well as C % 4 == 0
-    const uintptr_t al = (uintptr_t)x | (uintptr_t)vel_cond | (uintptr_t)vel_uncond | (uintptr_t)out | (uintptr_t)clean;
-    if (C % 4 == 0 && (al & 15) == 0)
-        hipLaunchKernelGGL(guided_euler_step_kernel<4>, dim3(grid_for(n / 4, 256)), dim3(256), 0, stream, x, vel_cond, vel_uncond, ts, ts_stride,
-                           mask, clean, s1, inv, dt, out, n, C);
-    else
-        hipLaunchKernelGGL(guided_euler_step_kernel<1>, dim3(grid_for(n, 256)), dim3(256), 0, stream, x, vel_cond, vel_uncond, ts, ts_stride,
-                           mask, clean, s1, inv, dt, out, n, C);
-    LTX2_CHECK_LAUNCH("guided_euler_step_kernel");
-    return LTX2_OK;
-}
-
-int res2s_midpoint_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride, const float* mask,
-                          const float* clean, float cfg_scale, float c, int n_bong, float* x_mid, float* anchor, float* eps1, int rows, int C,
-                          hipStream_t stream) {
-    LTX2_CHECK_ARG(x && vel_cond && ts && x_mid && rows > 0 && C > 0, "res2s_midpoint: null operand or empty shape");
-    LTX2_CHECK_ARG(ts_stride == 0 || ts_stride == 1, "res2s_midpoint: ts_stride is 0 (one timestep) or 1 (one per row)");
-    LTX2_CHECK_ARG((mask == nullptr) == (clean == nullptr), "res2s_midpoint: mask and clean go together");
-    LTX2_CHECK_ARG((anchor == nullptr) == (eps1 == nullptr), "res2s_midpoint: anchor and eps1 go together (both NULL: the final-step form)");
-    LTX2_CHECK_ARG(n_bong >= 0, "res2s_midpoint: n_bong=%d", n_bong);
-    const long n = (long)rows * C;
-    // 16-byte accesses need every [rows][C] operand on a 16-byte boundary as well as C % 4 == 0 (a NULL operand contributes no bits)
-    const uintptr_t al = (uintptr_t)x | (uintptr_t)vel_cond | (uintptr_t)vel_uncond | (uintptr_t)clean | (uintptr_t)x_mid | (uintptr_t)anchor | (uintptr_t)eps1;
-    if (C % 4 == 0 && (al & 15) == 0)
-        hipLaunchKernelGGL(res2s_midpoint_kernel<4>, dim3(grid_for(n / 4, 256)), dim3(256), 0, stream, x, vel_cond, vel_uncond, ts, ts_stride, mask,
-                           clean, cfg_scale, c, n_bong, x_mid, anchor, eps1, n, C);
-    else
-        hipLaunchKernelGGL(res2s_midpoint_kernel<1>, dim3(grid_for(n, 256)), dim3(256), 0, stream, x, vel_cond, vel_uncond, ts, ts_stride, mask,
-                           clean, cfg_scale, c, n_bong, x_mid, anchor, eps1, n, C);
-    LTX2_CHECK_LAUNCH("res2s_midpoint_kernel");
-    return LTX2_OK;
-}
-
-int res2s_combine_launch(const float* x_mid, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride, const float* mask,
-                         const float* clean, float cfg_scale, const float* anchor, const float* eps1, float h, float b1, float b2, float* out,
-                         int rows, int C, hipStream_t stream) {
-    LTX2_CHECK_ARG(x_mid && vel_cond && ts && anchor && eps1 && out && rows > 0 && C > 0, "res2s_combine: null operand or empty shape");
-    LTX2_CHECK_ARG(ts_stride == 0 || ts_stride == 1, "res2s_combine: ts_stride is 0 (one timestep) or 1 (one per row)");
-    LTX2_CHECK_ARG((mask == nullptr) == (clean == nullptr), "res2s_combine: mask and clean go together");
-    const long n = (long)rows * C;
-    const uintptr_t al = (uintptr_t)x_mid | (uintptr_t)vel_cond | (uintptr_t)vel_uncond | (uintptr_t)clean | (uintptr_t)anchor | (uintptr_t)eps1 | (uintptr_t)out;
-    if (C % 4 == 0 && (al & 15) == 0)
-        hipLaunchKernelGGL(res2s_combine_kernel<4>, dim3(grid_for(n / 4, 256)), dim3(256), 0, stream, x_mid, vel_cond, vel_uncond, ts, ts_stride, mask,
-                           clean, cfg_scale, anchor, eps1, h, b1, b2, out, n, C);
-    else
-        hipLaunchKernelGGL(res2s_combine_kernel<1>, dim3(grid_for(n, 256)), dim3(256), 0, stream, x_mid, vel_cond, vel_uncond, ts, ts_stride, mask,
-                           clean, cfg_scale, anchor, eps1, h, b1, b2, out, n, C);
-    LTX2_CHECK_LAUNCH("res2s_combine_kernel");
     return LTX2_OK;
 }
 

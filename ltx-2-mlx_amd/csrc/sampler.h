@@ -1,0 +1,43 @@
+// The sampling step over fp32 [rows][C] latents: host launchers (sampler.hip; the definitions: include/ltx2hip.h).
+#pragma once
+#include "common.h"
+
+// x0[row][c] = latent[row][c] - ts(row) * vel[row][c]   (ts = ts_ptr[row*ts_stride] if ts_ptr else ts_scalar)
+int x0_from_velocity_launch(const float* latent, const float* vel, const float* ts_ptr, long ts_stride, float ts_scalar,
+                            float* x0, int rows, int C, hipStream_t stream);
+
+// x0' = mask ? x0*mask(row) + clean*(1-mask(row)) : x0 ;  out = x + (x - x0')/sigma * (sigma_next - sigma)
+int euler_step_launch(const float* x, const float* x0, const float* mask, const float* clean, float sigma,
+                      float sigma_next, float* out, int rows, int C, hipStream_t stream);
+
+// The steps below round every operation individually (the separate fp32 torch ops, bit for bit), read t = ts[row * ts_stride] with ts_stride 0 or
+// 1, blend with `clean` where `mask` is given (both or neither), and may write any output over any [rows][C] input.
+
+// One classifier-free-guided step in one pass:
+// a = x - t*vc, b = x - t*vu, g = a + (cfg_scale - 1)*(a - b), d = mask ? g*m + clean*(1 - m) : g, out = x + ((x - d)/sigma)*(sigma_next - sigma)
+int guided_euler_step_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride,
+                             const float* mask, const float* clean, float cfg_scale, float sigma, float sigma_next, float* out,
+                             int rows, int C, hipStream_t stream);
+
+// The res_2s second-order step as two passes; d(x, vc, vu) = the guided, mask-blended x0 in the HQ pipeline's order:
+// a = x - t*vc, b = x - t*vu, g = b + cfg*(a - b) (g = a when vu is NULL), d = mask ? g*m + clean*(1 - m) : g.
+// midpoint: an = x, e = d - an, xm = an + c*e, n_bong x {an = xm - c*e, e = d - an}; stores x_mid, anchor, eps1.
+// anchor == eps1 == NULL: the final-step form, x_mid = d and nothing else.
+int res2s_midpoint_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride, const float* mask,
+                          const float* clean, float cfg_scale, float c, int n_bong, float* x_mid, float* anchor, float* eps1, int rows, int C,
+                          hipStream_t stream);
+// combine: e2 = d(x_mid, vc, vu) - anchor, out = anchor + h*(b1*eps1 + b2*e2)
+int res2s_combine_launch(const float* x_mid, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride, const float* mask,
+                         const float* clean, float cfg_scale, const float* anchor, const float* eps1, float h, float b1, float b2, float* out,
+                         int rows, int C, hipStream_t stream);
+
+// Guiders whose scalars are sums over the whole latent.  sums: five fp64 sums per block into partials[guidance_sums_blocks(rows, C)][5], and with
+// `running` the momentum update of the guidance; step: every block adds the partial rows in index order, derives the fp32 scalars and runs the
+// guided, mask-blended Euler step.
+int guidance_sums_blocks(int rows, int C);
+int guidance_sums_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride, float* running, int first,
+                         float momentum, double* partials, int rows, int C, hipStream_t stream);
+int projected_euler_step_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride, const float* mask,
+                                const float* clean, const float* running, const double* partials, int mode, float scale, float eta,
+                                float norm_threshold, float sigma, float sigma_next, float* out, float* scalars_out, int rows, int C,
+                                hipStream_t stream);

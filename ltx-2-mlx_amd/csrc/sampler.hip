@@ -1,0 +1,387 @@
+// The device code of the sampling step over fp32 [rows][C] latents: the plain x0 / Euler pair, and the steps that replace a sequence of separate
+// fp32 torch ops bit for bit -- the classifier-free-guided Euler step (pipelines/one_stage.py:224-330), the two passes of the res_2s second-order
+// step (reference pipelines/ti2vid_hq.py:153-273) and the two passes of the guiders whose scalars are reductions over the whole latent
+// (CFGStarRescalingGuider, LtxAPGGuider, LegacyStatefulAPGGuider; reference components/guiders.py:51-76, 105-205).  All arithmetic is fp32 and
+// fp64, so the file compiles to the same code in both library builds.  The definitions are written out in include/ltx2hip.h.
+#include <hip/hip_runtime.h>
+
+#include "common.h"
+#include "sampler.h"
+
+namespace {
+
+// ---------------------------------- the plain step: contracted arithmetic, bounded (not bit-exact) against its reference ----------------------------------
+__global__ void x0_from_velocity_kernel(const float* __restrict__ latent, const float* __restrict__ vel,
+                                        const float* __restrict__ ts_ptr, long ts_stride, float ts_scalar,
+                                        float* __restrict__ x0, int rows, int C) {
+    const long n = (long)rows * C;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const long row = i / C;
+        const float ts = ts_ptr ? ts_ptr[row * ts_stride] : ts_scalar;
+        x0[i] = latent[i] - ts * vel[i];
+    }
+}
+
+__global__ void euler_step_kernel(const float* __restrict__ x, const float* __restrict__ x0,
+                                  const float* __restrict__ mask, const float* __restrict__ clean, float inv_sigma,
+                                  float dt, float* __restrict__ out, int rows, int C) {
+    const long n = (long)rows * C;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        float d = x0[i];
+        if (mask) {
+            const float m = mask[i / C];
+            d = d * m + clean[i] * (1.f - m);
+        }
+        const float xv = x[i];
+        out[i] = xv + (xv - d) * inv_sigma * dt;
+    }
+}
+
+// ---------------------------------- the individually rounded steps: one scaffold ----------------------------------
+// A step is an Op: NIN operands `in` and NOUT operands `out`, all [rows][C], and one(): the arithmetic of one element, a[k] read from in[k] and
+// o[k] stored to out[k], every operation rounded on its own (mul_rn / add_rn / sub_rn) in the order of the torch statements it replaces.  A NULL
+// `in` reads as zeros and a NULL `out` is not stored.  begin() / end() run once per thread around the loop with the thread's State.
+//
+// Aliasing: any `out` may be the same buffer as any `in` (the engine updates the latent in place).  So no [rows][C] operand is __restrict__, and a
+// thread loads its V elements of EVERY operand before it stores any; V divides C, so a vector never straddles a row.
+constexpr int BLOCK = 256, WAVES = BLOCK / 64;
+
+struct Rows {           // what every step reads per row, and the shape
+    const float* ts;    // t = ts[row * ts_stride]
+    long ts_stride;
+    const float* mask;  // m = mask[row], or NULL: m = 1 and no blend
+    long n;             // rows * C
+    int C;
+};
+struct Row {
+    float t, m, one_minus_m;
+    bool blend;
+};
+
+template <int V>
+__device__ __forceinline__ void load(const float* p, long e, float (&v)[V]) {
+    if constexpr (V == 4) *(float4*)v = p ? *(const float4*)(p + e) : float4{0.f, 0.f, 0.f, 0.f};
+    else v[0] = p ? p[e] : 0.f;
+}
+template <int V>
+__device__ __forceinline__ void store(float* p, long e, const float (&v)[V]) {
+    if (!p) return;
+    if constexpr (V == 4) *(float4*)(p + e) = *(const float4*)v;
+    else p[e] = v[0];
+}
+
+template <int V, class Op>
+__global__ __launch_bounds__(BLOCK) void step_rows_kernel(const Op op, const Rows r) {
+    typename Op::State st;
+    op.begin(st);
+    const bool blend = r.mask != nullptr;
+    const long nv = r.n / V;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
+        const long e = i * V, row = e / r.C;
+        const float m = blend ? r.mask[row] : 1.f;
+        const Row rw = {r.ts[row * r.ts_stride], m, sub_rn(1.0f, m), blend};
+        alignas(16) float in[Op::NIN][V], out[Op::NOUT][V];
+#pragma unroll
+        for (int k = 0; k < Op::NIN; ++k) load<V>(op.in[k], e, in[k]);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            float a[Op::NIN], o[Op::NOUT] = {};
+#pragma unroll
+            for (int k = 0; k < Op::NIN; ++k) a[k] = in[k][j];
+            op.one(st, rw, a, o);
+#pragma unroll
+            for (int k = 0; k < Op::NOUT; ++k) out[k][j] = o[k];
+        }
+#pragma unroll
+        for (int k = 0; k < Op::NOUT; ++k) store<V>(op.out[k], e, out[k]);
+    }
+    op.end(st);
+}
+
+struct StepOp {         // the defaults: no per-thread state, no prologue, no epilogue
+    struct State {};
+    template <class S>
+    __device__ __forceinline__ void begin(S&) const {}
+    template <class S>
+    __device__ __forceinline__ void end(S&) const {}
+};
+
+// The shared formulas.  x0 of one velocity at the row's timestep:
+__device__ __forceinline__ float denoised(float x, float v, float t) { return sub_rn(x, mul_rn(t, v)); }
+// CFGGuider.guide, from the conditional side: a + (cfg - 1)*(a - b)
+__device__ __forceinline__ float guide_from_cond(float a, float b, float cfg_minus_1) { return add_rn(a, mul_rn(cfg_minus_1, sub_rn(a, b))); }
+// the HQ pipeline's order (ti2vid_hq.py:315), from the unconditional side: b + cfg*(a - b) -- another rounding than the line above
+__device__ __forceinline__ float guide_from_uncond(float a, float b, float cfg) { return add_rn(b, mul_rn(cfg, sub_rn(a, b))); }
+// post_process_latent: d*m + clean*(1 - m) on a conditioned latent
+__device__ __forceinline__ float blend_clean(float d, float clean, const Row& r) {
+    return r.blend ? add_rn(mul_rn(d, r.m), mul_rn(clean, r.one_minus_m)) : d;
+}
+// x + ((x - d)/sigma)*(sigma_next - sigma) with inv = 1/sigma, dt = sigma_next - sigma
+__device__ __forceinline__ float euler(float x, float d, float inv, float dt) { return add_rn(x, mul_rn(mul_rn(sub_rn(x, d), inv), dt)); }
+
+struct GuidedEuler : StepOp {
+    enum { X, VC, VU, CLEAN, NIN };
+    enum { OUT, NOUT };
+    const float* in[NIN];
+    float* out[NOUT];
+    float s1, inv, dt;          // cfg_scale - 1, 1/sigma, sigma_next - sigma
+    __device__ __forceinline__ void one(State&, const Row& r, const float* a, float* o) const {
+        const float g = guide_from_cond(denoised(a[X], a[VC], r.t), denoised(a[X], a[VU], r.t), s1);
+        o[OUT] = euler(a[X], blend_clean(g, a[CLEAN], r), inv, dt);
+    }
+};
+
+// the guided, mask-blended x0 of one pair of velocities as the res_2s step forms it; no vu: no guidance
+__device__ __forceinline__ float res2s_denoised(const Row& r, float x, float vc, float vu, bool guide, float cfg, float clean) {
+    float d = denoised(x, vc, r.t);
+    if (guide) d = guide_from_uncond(d, denoised(x, vu, r.t), cfg);
+    return blend_clean(d, clean, r);
+}
+
+// anchor = x, eps1 = d - anchor, x_mid = anchor + c*eps1, then the "bong" iteration (:232-238) n_bong times in registers:
+// anchor = x_mid - c*eps1, eps1 = d - anchor.  No anchor / eps1 to store: the final-step form, x_mid = d and nothing else.
+struct Res2sMidpoint : StepOp {
+    enum { X, VC, VU, CLEAN, NIN };
+    enum { X_MID, ANCHOR, EPS1, NOUT };
+    const float* in[NIN];
+    float* out[NOUT];
+    float cfg, c;
+    int n_bong;
+    __device__ __forceinline__ void one(State&, const Row& r, const float* a, float* o) const {
+        const float d = res2s_denoised(r, a[X], a[VC], a[VU], in[VU] != nullptr, cfg, a[CLEAN]);
+        if (!out[ANCHOR]) {
+            o[X_MID] = d;
+            return;
+        }
+        float an = a[X], e = sub_rn(d, an);
+        const float xm = add_rn(an, mul_rn(c, e));
+        for (int k = 0; k < n_bong; ++k) {
+            an = sub_rn(xm, mul_rn(c, e));
+            e = sub_rn(d, an);
+        }
+        o[X_MID] = xm;
+        o[ANCHOR] = an;
+        o[EPS1] = e;
+    }
+};
+
+// d2 from (x_mid, velocities at the sub-sigma) as above, e2 = d2 - anchor, out = anchor + h*(b1*eps1 + b2*e2)
+struct Res2sCombine : StepOp {
+    enum { X_MID, VC, VU, CLEAN, ANCHOR, EPS1, NIN };
+    enum { OUT, NOUT };
+    const float* in[NIN];
+    float* out[NOUT];
+    float cfg, h, b1, b2;
+    __device__ __forceinline__ void one(State&, const Row& r, const float* a, float* o) const {
+        const float d2 = res2s_denoised(r, a[X_MID], a[VC], a[VU], in[VU] != nullptr, cfg, a[CLEAN]);
+        const float e2 = sub_rn(d2, a[ANCHOR]);
+        o[OUT] = add_rn(a[ANCHOR], mul_rn(h, add_rn(mul_rn(b1, a[EPS1]), mul_rn(b2, e2))));
+    }
+};
+
+constexpr int NSUM = 5;               // S_aa, S_ab, S_bb, S_gg, S_ga
+constexpr int SUMS_CAP = 1024;        // every block of the second pass reads all the rows of the first
+
+// rows of `partials`: a function of (rows, C) alone, whichever access width the operands' alignment allows
+inline int sums_blocks(long n) { return grid_for((n + 3) / 4, BLOCK, SUMS_CAP); }
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// a = x - t*vc, b = x - t*vu, g = a - b, with momentum g = momentum*running + g (in[RUN]: NULL on the first step) stored back to running; the five
+// sums per thread in loop order, then across the wave (xor tree), then across the block's waves in order.
+struct GuidanceSums : StepOp {
+    enum { X, VC, VU, RUN, NIN };
+    enum { RUN_OUT, NOUT };
+    struct State {
+        double s[NSUM];
+    };
+    const float* in[NIN];
+    float* out[NOUT];
+    float momentum;
+    double* partials;
+    __device__ __forceinline__ void begin(State& st) const {
+#pragma unroll
+        for (int k = 0; k < NSUM; ++k) st.s[k] = 0.0;
+    }
+    __device__ __forceinline__ void one(State& st, const Row& r, const float* v, float* o) const {
+        const float a = denoised(v[X], v[VC], r.t), b = denoised(v[X], v[VU], r.t);
+        float g = sub_rn(a, b);
+        if (in[RUN]) g = add_rn(mul_rn(momentum, v[RUN]), g);
+        o[RUN_OUT] = g;
+        const double da = a, db = b, dg = g;                   // each product of two fp32 values is exact in fp64
+        st.s[0] += da * da;
+        st.s[1] += da * db;
+        st.s[2] += db * db;
+        st.s[3] += dg * dg;
+        st.s[4] += dg * da;
+    }
+    __device__ __forceinline__ void end(State& st) const {
+        __shared__ double part[WAVES][NSUM];
+        const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+        for (int k = 0; k < NSUM; ++k) {
+            const double w = wave_sum_f64(st.s[k]);
+            if (lane == 0) part[wave][k] = w;
+        }
+        __syncthreads();
+        if (threadIdx.x < NSUM) {
+            double acc = part[0][threadIdx.x];
+            for (int w = 1; w < WAVES; ++w) acc += part[w][threadIdx.x];
+            partials[(long)blockIdx.x * NSUM + threadIdx.x] = acc;
+        }
+    }
+};
+
+// g_out of one element from (a, b, g) and the block's fp32 scalars: k0 = coef (mode 0) or sf (modes 1, 2), k1 = proj
+__device__ __forceinline__ float projected_one(int mode, float a, float b, float g, float k0, float k1, float mult, float eta) {
+    if (mode == 0) return add_rn(a, mul_rn(mult, sub_rn(a, mul_rn(k0, b))));
+    const float gsc = mul_rn(g, k0), par = mul_rn(k1, a);
+    const float apg = add_rn(mul_rn(par, eta), sub_rn(gsc, par));
+    return add_rn(a, mul_rn(apg, mult));
+}
+
+// Every block adds the partial rows in index order, so every block holds the same five sums and derives the same scalars; then the guided step
+// with g read from `running` (mode 2 with momentum) or formed as a - b.
+struct ProjectedEuler : StepOp {
+    enum { X, VC, VU, CLEAN, RUN, NIN };
+    enum { OUT, NOUT };
+    struct State {
+        float k0, k1;
+    };
+    const float* in[NIN];
+    float* out[NOUT];
+    const double* partials;
+    float* scalars_out;
+    int mode;             // 0 CFG*, 1 APG, 2 legacy APG
+    float mult;           // scale - 1 (modes 0, 1) or scale (mode 2)
+    float eta, thr, inv, dt;
+    int nb;               // rows of partials
+    __device__ __forceinline__ void begin(State& st) const {
+        __shared__ double sums[NSUM];
+        __shared__ float sc[2];
+        if (threadIdx.x < NSUM) {                                      // the partial rows in index order
+            double acc = 0.0;
+            for (int r = 0; r < nb; ++r) acc += partials[(long)r * NSUM + threadIdx.x];
+            sums[threadIdx.x] = acc;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {                                        // fp64 throughout, each scalar rounded once
+            float k0, k1 = 0.f;
+            if (mode == 0) {
+                k0 = (float)(sums[1] / (sums[2] + 1e-8));
+            } else {
+                double sf = 1.0;
+                if (thr > 0.f) sf = fmin(1.0, (double)thr / sqrt(sums[3]));
+                k0 = (float)sf;
+                k1 = (float)(sf * sums[4] / (sums[0] + 1e-8));
+            }
+            sc[0] = k0;
+            sc[1] = k1;
+            if (blockIdx.x == 0 && scalars_out) {
+                scalars_out[0] = k0;
+                if (mode != 0) scalars_out[1] = k1;
+            }
+        }
+        __syncthreads();
+        st.k0 = sc[0];
+        st.k1 = sc[1];
+    }
+    __device__ __forceinline__ void one(State& st, const Row& r, const float* v, float* o) const {
+        const float a = denoised(v[X], v[VC], r.t), b = denoised(v[X], v[VU], r.t);
+        const float g = in[RUN] ? v[RUN] : sub_rn(a, b);
+        const float d = projected_one(mode, a, b, g, st.k0, st.k1, mult, eta);
+        o[OUT] = euler(v[X], blend_clean(d, v[CLEAN], r), inv, dt);
+    }
+};
+
+// The checks every step shares, under the caller's name, and the launch.  present: the caller's required operands are all there.  16-byte accesses
+// need every [rows][C] operand on a 16-byte boundary as well as C % 4 == 0 (a NULL operand contributes no bits).  sums_grid: the grid of the sums
+// pass, which does not depend on the access width; 0: a step, one thread per vector under grid_for's cap.
+template <class Op>
+int launch_rows(const char* who, bool present, const Op& op, const float* ts, long ts_stride, const float* mask, const float* clean, int rows, int C,
+                int sums_grid, hipStream_t stream) {
+    LTX2_CHECK_ARG(present && ts && rows > 0 && C > 0, "%s: null operand or empty shape", who);
+    LTX2_CHECK_ARG(ts_stride == 0 || ts_stride == 1, "%s: ts_stride is 0 (one timestep) or 1 (one per row)", who);
+    LTX2_CHECK_ARG((mask == nullptr) == (clean == nullptr), "%s: mask and clean go together", who);
+    const Rows r = {ts, ts_stride, mask, (long)rows * C, C};
+    uintptr_t al = 0;
+    for (const float* p : op.in) al |= (uintptr_t)p;
+    for (const float* p : op.out) al |= (uintptr_t)p;
+    if (C % 4 == 0 && (al & 15) == 0)
+        hipLaunchKernelGGL((step_rows_kernel<4, Op>), dim3(sums_grid ? sums_grid : grid_for(r.n / 4, BLOCK)), dim3(BLOCK), 0, stream, op, r);
+    else
+        hipLaunchKernelGGL((step_rows_kernel<1, Op>), dim3(sums_grid ? sums_grid : grid_for(r.n, BLOCK)), dim3(BLOCK), 0, stream, op, r);
+    LTX2_CHECK_LAUNCH(who);
+    return LTX2_OK;
+}
+
+}  // namespace
+
+int x0_from_velocity_launch(const float* latent, const float* vel, const float* ts_ptr, long ts_stride, float ts_scalar,
+                            float* x0, int rows, int C, hipStream_t stream) {
+    hipLaunchKernelGGL(x0_from_velocity_kernel, dim3(grid_for((long)rows * C, 256)), dim3(256), 0, stream, latent, vel,
+                       ts_ptr, ts_stride, ts_scalar, x0, rows, C);
+    LTX2_CHECK_LAUNCH("x0_from_velocity_kernel");
+    return LTX2_OK;
+}
+
+int euler_step_launch(const float* x, const float* x0, const float* mask, const float* clean, float sigma,
+                      float sigma_next, float* out, int rows, int C, hipStream_t stream) {
+    LTX2_CHECK_ARG(sigma != 0.f, "Sigma can't be 0.0");   // reference core_utils.py:54-55
+    LTX2_CHECK_ARG((mask == nullptr) == (clean == nullptr), "euler_step: mask and clean go together");
+    hipLaunchKernelGGL(euler_step_kernel, dim3(grid_for((long)rows * C, 256)), dim3(256), 0, stream, x, x0, mask, clean,
+                       1.0f / sigma, sigma_next - sigma, out, rows, C);
+    LTX2_CHECK_LAUNCH("euler_step_kernel");
+    return LTX2_OK;
+}
+
+int guided_euler_step_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride,
+                             const float* mask, const float* clean, float cfg_scale, float sigma, float sigma_next, float* out,
+                             int rows, int C, hipStream_t stream) {
+    LTX2_CHECK_ARG(sigma != 0.f, "Sigma can't be 0.0");   // reference core_utils.py:54-55
+    const GuidedEuler op = {{}, {x, vel_cond, vel_uncond, clean}, {out}, cfg_scale - 1.0f, 1.0f / sigma, sigma_next - sigma};
+    return launch_rows("guided_euler_step", x && vel_cond && vel_uncond && out, op, ts, ts_stride, mask, clean, rows, C, 0, stream);
+}
+
+int res2s_midpoint_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride, const float* mask,
+                          const float* clean, float cfg_scale, float c, int n_bong, float* x_mid, float* anchor, float* eps1, int rows, int C,
+                          hipStream_t stream) {
+    LTX2_CHECK_ARG((anchor == nullptr) == (eps1 == nullptr), "res2s_midpoint: anchor and eps1 go together (both NULL: the final-step form)");
+    LTX2_CHECK_ARG(n_bong >= 0, "res2s_midpoint: n_bong=%d", n_bong);
+    const Res2sMidpoint op = {{}, {x, vel_cond, vel_uncond, clean}, {x_mid, anchor, eps1}, cfg_scale, c, n_bong};
+    return launch_rows("res2s_midpoint", x && vel_cond && x_mid, op, ts, ts_stride, mask, clean, rows, C, 0, stream);
+}
+
+int res2s_combine_launch(const float* x_mid, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride, const float* mask,
+                         const float* clean, float cfg_scale, const float* anchor, const float* eps1, float h, float b1, float b2, float* out,
+                         int rows, int C, hipStream_t stream) {
+    const Res2sCombine op = {{}, {x_mid, vel_cond, vel_uncond, clean, anchor, eps1}, {out}, cfg_scale, h, b1, b2};
+    return launch_rows("res2s_combine", x_mid && vel_cond && anchor && eps1 && out, op, ts, ts_stride, mask, clean, rows, C, 0, stream);
+}
+
+int guidance_sums_blocks(int rows, int C) { return (rows > 0 && C > 0) ? sums_blocks((long)rows * C) : 0; }
+
+int guidance_sums_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride, float* running, int first,
+                         float momentum, double* partials, int rows, int C, hipStream_t stream) {
+    LTX2_CHECK_ARG(((uintptr_t)partials & 7) == 0, "guidance_sums: partials must be 8-byte aligned");
+    const GuidanceSums op = {{}, {x, vel_cond, vel_uncond, first ? nullptr : running}, {running}, momentum, partials};
+    return launch_rows("guidance_sums", x && vel_cond && vel_uncond && partials, op, ts, ts_stride, nullptr, nullptr, rows, C,
+                       guidance_sums_blocks(rows, C), stream);
+}
+
+int projected_euler_step_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride, const float* mask,
+                                const float* clean, const float* running, const double* partials, int mode, float scale, float eta,
+                                float norm_threshold, float sigma, float sigma_next, float* out, float* scalars_out, int rows, int C,
+                                hipStream_t stream) {
+    LTX2_CHECK_ARG(sigma != 0.f, "Sigma can't be 0.0");   // reference core_utils.py:54-55
+    LTX2_CHECK_ARG(mode >= 0 && mode <= 2, "projected_euler_step: mode=%d is 0 (CFG*), 1 (APG) or 2 (legacy APG)", mode);
+    LTX2_CHECK_ARG(running == nullptr || mode == 2, "projected_euler_step: only mode 2 (legacy APG with momentum) reads a running buffer");
+    LTX2_CHECK_ARG(((uintptr_t)partials & 7) == 0, "projected_euler_step: partials must be 8-byte aligned");
+    const ProjectedEuler op = {{}, {x, vel_cond, vel_uncond, clean, running}, {out}, partials, scalars_out, mode, mode == 2 ? scale : scale - 1.0f,
+                               eta, norm_threshold, 1.0f / sigma, sigma_next - sigma, guidance_sums_blocks(rows, C)};
+    return launch_rows("projected_euler_step", x && vel_cond && vel_uncond && partials && out, op, ts, ts_stride, mask, clean, rows, C, 0, stream);
+}

@@ -505,22 +505,29 @@ def euler_step(x: torch.Tensor, x0: torch.Tensor, sigma: float, sigma_next: floa
     return out
 
 
+def _step_operands(x, timesteps, operands, mask=None):
+    """The checks the sampler-step wrappers share -> (N, C, timesteps as contiguous fp32): timesteps has 1 or N elements, every operand that is
+    given (None: an optional one left out) is fp32, contiguous and shaped like x, and a mask has N fp32 elements."""
+    n, c = x.shape
+    timesteps = _c(timesteps.float())
+    if timesteps.numel() not in (1, n):
+        raise ValueError(f"timesteps has {timesteps.numel()} elements; expected 1 or N={n}")
+    for t in (x,) + tuple(operands):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.shape == x.shape)
+    assert mask is None or (mask.dtype == torch.float32 and mask.is_contiguous() and mask.numel() == n)
+    return n, c, timesteps
+
+
 def guided_euler_step(x: torch.Tensor, vel_cond: torch.Tensor, vel_uncond: torch.Tensor, timesteps: torch.Tensor, cfg_scale: float, sigma: float,
                       sigma_next: float, mask: Optional[torch.Tensor] = None, clean: Optional[torch.Tensor] = None,
                       out: Optional[torch.Tensor] = None, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
     """One classifier-free-guided step over fp32 [N, C] (ltx2_guided_euler_step): x0 of both velocities, CFGGuider.guide, the mask / clean
     blend and the Euler update in one pass, every operation individually rounded.  timesteps: 1 or N elements; `out` may be `x`;
     `dtype` picks the library build (the kernel is fp32 in both)."""
-    n, c = x.shape
-    timesteps = _c(timesteps.float())
-    if timesteps.numel() not in (1, n):
-        raise ValueError(f"timesteps has {timesteps.numel()} elements; expected 1 or N={n}")
     if out is None:
         out = torch.empty_like(x)
-    for t in (x, vel_cond, vel_uncond, out) + ((mask, clean) if mask is not None else ()):
-        assert t is not None and t.dtype == torch.float32 and t.is_contiguous()
-    assert vel_cond.shape == x.shape and vel_uncond.shape == x.shape and out.shape == x.shape
-    assert mask is None or (mask.numel() == n and clean.shape == x.shape)
+    assert vel_cond is not None and vel_uncond is not None and (mask is None or clean is not None)
+    n, c, timesteps = _step_operands(x, timesteps, (vel_cond, vel_uncond, clean, out), mask)
     nv.check(nv.lib(dtype).ltx2_guided_euler_step(nv.ptr(x), nv.ptr(vel_cond), nv.ptr(vel_uncond), nv.ptr(timesteps), 0 if timesteps.numel() == 1 else 1,
                                                   nv.ptr(mask), nv.ptr(clean), float(cfg_scale), float(sigma), float(sigma_next), nv.ptr(out), n, c,
                                                   nv.stream()))
@@ -535,17 +542,6 @@ def guidance_sums_blocks(rows: int, c: int, dtype: Optional[torch.dtype] = None)
     return int(nv.lib(dtype).ltx2_guidance_sums_blocks(int(rows), int(c)))
 
 
-def _guidance_operands(x, vel_cond, vel_uncond, timesteps, partials, extra):
-    n, c = x.shape
-    timesteps = _c(timesteps.float())
-    if timesteps.numel() not in (1, n):
-        raise ValueError(f"timesteps has {timesteps.numel()} elements; expected 1 or N={n}")
-    for t in (x, vel_cond, vel_uncond) + tuple(extra):
-        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.shape == x.shape)
-    assert partials.dtype == torch.float64 and partials.is_contiguous()
-    return n, c, timesteps
-
-
 def guidance_sums(x: torch.Tensor, vel_cond: torch.Tensor, vel_uncond: torch.Tensor, timesteps: torch.Tensor, partials: Optional[torch.Tensor] = None,
                   running: Optional[torch.Tensor] = None, first: bool = True, momentum: float = 0.0, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
     """First pass of a projected guidance step over fp32 [N, C] (ltx2_guidance_sums): a = x - t*vc, b = x - t*vu, g = a - b (with `running`:
@@ -553,8 +549,8 @@ def guidance_sums(x: torch.Tensor, vel_cond: torch.Tensor, vel_uncond: torch.Ten
     -> partials, fp64 [guidance_sums_blocks(N, C), 5].  `dtype` picks the library build (the kernel is fp32 / fp64 in both)."""
     if partials is None:
         partials = torch.empty(guidance_sums_blocks(*x.shape, dtype=dtype), 5, device=x.device, dtype=torch.float64)
-    n, c, timesteps = _guidance_operands(x, vel_cond, vel_uncond, timesteps, partials, (running,))
-    assert partials.numel() >= 5 * guidance_sums_blocks(n, c, dtype)
+    n, c, timesteps = _step_operands(x, timesteps, (vel_cond, vel_uncond, running))
+    assert partials.dtype == torch.float64 and partials.is_contiguous() and partials.numel() >= 5 * guidance_sums_blocks(n, c, dtype)
     nv.check(nv.lib(dtype).ltx2_guidance_sums(nv.ptr(x), nv.ptr(vel_cond), nv.ptr(vel_uncond), nv.ptr(timesteps), 0 if timesteps.numel() == 1 else 1,
                                               nv.ptr(running), int(bool(first)), float(momentum), nv.ptr(partials), n, c, nv.stream()))
     return partials
@@ -570,28 +566,15 @@ def projected_euler_step(x: torch.Tensor, vel_cond: torch.Tensor, vel_uncond: to
     guidance_sums left."""
     if out is None:
         out = torch.empty_like(x)
-    n, c, timesteps = _guidance_operands(x, vel_cond, vel_uncond, timesteps, partials, (clean, running, out))
-    assert partials.numel() >= 5 * guidance_sums_blocks(n, c, dtype)
-    assert (mask is None) == (clean is None) and (mask is None or (mask.numel() == n and mask.dtype == torch.float32 and mask.is_contiguous()))
+    n, c, timesteps = _step_operands(x, timesteps, (vel_cond, vel_uncond, clean, running, out), mask)
+    assert partials.dtype == torch.float64 and partials.is_contiguous() and partials.numel() >= 5 * guidance_sums_blocks(n, c, dtype)
+    assert (mask is None) == (clean is None)
     assert scalars_out is None or (scalars_out.dtype == torch.float32 and scalars_out.numel() >= 2)
     nv.check(nv.lib(dtype).ltx2_projected_euler_step(nv.ptr(x), nv.ptr(vel_cond), nv.ptr(vel_uncond), nv.ptr(timesteps), 0 if timesteps.numel() == 1 else 1,
                                                      nv.ptr(mask), nv.ptr(clean), nv.ptr(running), nv.ptr(partials), int(mode), float(scale), float(eta),
                                                      float(norm_threshold), float(sigma), float(sigma_next), nv.ptr(out), nv.ptr(scalars_out), n, c,
                                                      nv.stream()))
     return out
-
-
-def _res2s_operands(x, vel_cond, vel_uncond, timesteps, mask, clean, extra):
-    n, c = x.shape
-    timesteps = _c(timesteps.float())
-    if timesteps.numel() not in (1, n):
-        raise ValueError(f"timesteps has {timesteps.numel()} elements; expected 1 or N={n}")
-    for t in (x, vel_cond) + tuple(extra) + ((vel_uncond,) if vel_uncond is not None else ()) + ((mask, clean) if mask is not None else ()):
-        assert t is not None and t.dtype == torch.float32 and t.is_contiguous()
-    for t in (vel_cond, vel_uncond, clean) + tuple(extra):
-        assert t is None or t.shape == x.shape
-    assert mask is None or mask.numel() == n
-    return n, c, timesteps
 
 
 def res2s_midpoint(x: torch.Tensor, vel_cond: torch.Tensor, vel_uncond: Optional[torch.Tensor], timesteps: torch.Tensor, cfg_scale: float, c: float,
@@ -609,7 +592,8 @@ def res2s_midpoint(x: torch.Tensor, vel_cond: torch.Tensor, vel_uncond: Optional
         eps1 = torch.empty_like(x) if eps1 is None else eps1
     else:
         anchor = eps1 = None
-    n, ch, timesteps = _res2s_operands(x, vel_cond, vel_uncond, timesteps, mask, clean, (x_mid,) + (() if final else (anchor, eps1)))
+    assert vel_cond is not None and (mask is None or clean is not None)
+    n, ch, timesteps = _step_operands(x, timesteps, (vel_cond, vel_uncond, clean, x_mid, anchor, eps1), mask)
     nv.check(nv.lib(dtype).ltx2_res2s_midpoint(nv.ptr(x), nv.ptr(vel_cond), nv.ptr(vel_uncond), nv.ptr(timesteps), 0 if timesteps.numel() == 1 else 1,
                                                nv.ptr(mask), nv.ptr(clean), float(cfg_scale), float(c), int(n_bong), nv.ptr(x_mid), nv.ptr(anchor),
                                                nv.ptr(eps1), n, ch, nv.stream()))
@@ -623,7 +607,8 @@ def res2s_combine(x_mid: torch.Tensor, vel_cond: torch.Tensor, vel_uncond: Optio
     e2 = d2 - anchor, out = anchor + h*(b1*eps1 + b2*e2), every operation individually rounded.  `out` may be any [N, C] operand."""
     if out is None:
         out = torch.empty_like(x_mid)
-    n, ch, timesteps = _res2s_operands(x_mid, vel_cond, vel_uncond, timesteps, mask, clean, (anchor, eps1, out))
+    assert vel_cond is not None and anchor is not None and eps1 is not None and (mask is None or clean is not None)
+    n, ch, timesteps = _step_operands(x_mid, timesteps, (vel_cond, vel_uncond, clean, anchor, eps1, out), mask)
     nv.check(nv.lib(dtype).ltx2_res2s_combine(nv.ptr(x_mid), nv.ptr(vel_cond), nv.ptr(vel_uncond), nv.ptr(timesteps), 0 if timesteps.numel() == 1 else 1,
                                               nv.ptr(mask), nv.ptr(clean), float(cfg_scale), nv.ptr(anchor), nv.ptr(eps1), float(h), float(b1), float(b2),
                                               nv.ptr(out), n, ch, nv.stream()))

@@ -56,6 +56,37 @@ def test_guided_euler_step_bit_for_bit(dev, build, rows, C):
             R.guided_euler_step(x, vc, vu, ts_row, None, None, 3.0, 0.0, 0.5)
 
 
+_off_case = {}
+
+
+@pytest.mark.parametrize("build", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("off", ["x", "vc", "vu", "clean", "out"])
+def test_guided_euler_step_each_operand_off_alignment(dev, build, off):
+    """9 x 8 with one [rows][C] operand 4 bytes off a 16-byte boundary: the element-wise form although C % 4 == 0, the same bits as the CPU
+    restatement (computed once), nothing written outside `out`."""
+    from ltx_2_mlx_amd import kernels as K
+    rows, C, sigma, sigma_next = 9, 8, 0.909375, 0.725
+    if not _off_case:
+        g = torch.Generator().manual_seed(rows * 131 + C)
+        for name in ("x", "vc", "vu", "clean"):
+            _off_case[name] = torch.randn(rows, C, generator=g)
+        _off_case["ts"] = torch.rand(rows, generator=g)
+        _off_case["mask"] = torch.tensor([0.0, 0.05, 1.0] * 3)
+        _off_case["ref"] = R.guided_euler_step(*(_off_case[k] for k in ("x", "vc", "vu", "ts", "mask", "clean")), 3.0, sigma, sigma_next)
+    t, n, d, bufs = _off_case, rows * C, {}, {}
+    for name in ("x", "vc", "vu", "clean", "out"):
+        o = 1 if name == off else 0
+        bufs[name] = torch.full((n + 64 + o,), SENTINEL, device=dev)
+        d[name] = bufs[name][o:o + n].view(rows, C)
+        assert d[name].data_ptr() % 16 == 4 * o
+        if name != "out":
+            d[name].copy_(t[name])
+    K.guided_euler_step(d["x"], d["vc"], d["vu"], t["ts"].to(dev), 3.0, sigma, sigma_next, mask=t["mask"].to(dev), clean=d["clean"], out=d["out"], dtype=build)
+    assert torch.equal(d["out"].cpu(), t["ref"]), f"{int((d['out'].cpu() != t['ref']).sum())} of {n} elements differ"
+    o = 1 if off == "out" else 0
+    assert bool((bufs["out"][:o] == SENTINEL).all()) and bool((bufs["out"][o + n:] == SENTINEL).all())
+
+
 # ------------------------------------------------------------------ shared tiny model + keyframe state (N = 72 + 2 * 24 = 120, S = 64)
 class Tiny:
     pass

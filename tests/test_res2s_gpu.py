@@ -130,6 +130,58 @@ def test_res2s_kernels_bit_for_bit(dev, build, rows, C):
             nv.check(L.ltx2_res2s_combine(p(xm), p(d["vc"]), None, p(d["ts_row"]), 2, None, None, 3.0, p(an), p(e), H, B1, B2, p(out), rows, C, nv.stream()))
 
 
+def _off_case():
+    """9 x 8 inputs and the CPU restatement of both passes (guided, blended, 100 bong iterations), computed once."""
+    t = _case(9, 8)
+    if "off" not in t["ref"]:
+        args = (t["vc"], t["vu"], t["ts_row"], t["mask"], t["clean"], 3.0)
+        xm, an, e = R.midpoint(t["x"], *args, CC, 100)
+        t["ref"]["off"] = dict(x_mid=xm, anchor=an, eps1=e, out=R.combine(xm, *args, an, e, H, B1, B2))
+    return t, t["ref"]["off"]
+
+
+def _placed(names, off, src, dev, rows, C):
+    """Sentinel-framed device buffers of the named [rows][C] operands, the one called `off` 4 bytes off a 16-byte boundary, filled from `src`
+    where it has the name -> ({name: view}, {name: (whole buffer, offset)})."""
+    views, bufs = {}, {}
+    for name in names:
+        o = 1 if name == off else 0
+        buf, w = _buf(rows * C, dev, o)
+        views[name], bufs[name] = w.view(rows, C), (buf, o)
+        assert views[name].data_ptr() % 16 == 4 * o
+        if name in src:
+            views[name].copy_(src[name])
+    return views, bufs
+
+
+@pytest.mark.parametrize("build", BUILDS)
+@pytest.mark.parametrize("off", ["x", "vc", "vu", "clean", "x_mid", "anchor", "eps1"])
+def test_res2s_midpoint_each_operand_off_alignment(dev, build, off):
+    """One [rows][C] operand of the midpoint pass 4 bytes off a 16-byte boundary: the element-wise form although C % 4 == 0, the same bits."""
+    from ltx_2_mlx_amd import kernels as K
+    t, ref = _off_case()
+    v, bufs = _placed(("x", "vc", "vu", "clean", "x_mid", "anchor", "eps1"), off, t, dev, 9, 8)
+    K.res2s_midpoint(v["x"], v["vc"], v["vu"], t["ts_row"].to(dev), 3.0, CC, 100, mask=t["mask"].to(dev), clean=v["clean"], x_mid=v["x_mid"],
+                     anchor=v["anchor"], eps1=v["eps1"], dtype=build)
+    for name in ("x_mid", "anchor", "eps1"):
+        assert torch.equal(v[name].cpu(), ref[name]), name
+        assert _intact(bufs[name][0], 72, bufs[name][1]), name
+
+
+@pytest.mark.parametrize("build", BUILDS)
+@pytest.mark.parametrize("off", ["x_mid", "vc", "vu", "clean", "anchor", "eps1", "out"])
+def test_res2s_combine_each_operand_off_alignment(dev, build, off):
+    """The same for the combine pass, from the restatement's x_mid, anchor and eps1."""
+    from ltx_2_mlx_amd import kernels as K
+    t, ref = _off_case()
+    src = dict(vc=t["vc"], vu=t["vu"], clean=t["clean"], x_mid=ref["x_mid"], anchor=ref["anchor"], eps1=ref["eps1"])
+    v, bufs = _placed(("x_mid", "vc", "vu", "clean", "anchor", "eps1", "out"), off, src, dev, 9, 8)
+    K.res2s_combine(v["x_mid"], v["vc"], v["vu"], t["ts_row"].to(dev), 3.0, v["anchor"], v["eps1"], H, B1, B2, mask=t["mask"].to(dev), clean=v["clean"],
+                    out=v["out"], dtype=build)
+    assert torch.equal(v["out"].cpu(), ref["out"])
+    assert _intact(bufs["out"][0], 72, bufs["out"][1])
+
+
 # ------------------------------------------------------------------ shared tiny model + a conditioned state (N = 72 + one conditioned frame of 24, S = 64)
 class Tiny:
     pass
