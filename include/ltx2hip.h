@@ -477,6 +477,22 @@ int ltx2_dit_guided_step(ltx2_dit* ctx, ltx2_dit* neg, float* latent, const floa
  * belongs to ctx: ltx2_dit_graph_launch(ctx) replays it.                                                                               */
 int ltx2_dit_graph_capture_guided(ltx2_dit* ctx, ltx2_dit* neg, float* latent, const float* host_sigmas, int n_steps,
                                   const float* mask, int64_t n_mask, const float* clean, int64_t n_clean, float cfg_scale, void* stream);
+/* The guided step on the AudioVideo engine with the audio latent FROZEN (audio-to-video; pipelines/a2vid_two_stage.py:225-271): what
+ * ltx2_dit_forward_av does on ctx and then on neg, both from the same latents and timestep pointers (sigma_dev is both modalities' sigma), each into
+ * its own context's velocity buffers, then ltx2_guided_euler_step in place on the VIDEO latent -- in order on the caller's stream, the audio stream's
+ * kernels on each context's side stream as in every AudioVideo forward.  a_latent is only read; the audio velocities are not read.
+ * LTX2_E_INVALID, before anything is launched, when either context is VideoOnly or not prepared, ctx == neg, the two differ in N, Na or
+ * out_channels, a timestep count is neither 1 nor its modality's token count, or one is > 1 and either workspace was not bound with per_token = 1.
+ * (additive entries of ABI version 3)                                                                                                     */
+int ltx2_dit_guided_step_av(ltx2_dit* ctx, ltx2_dit* neg, float* v_latent, const float* a_latent, const float* v_timesteps, int n_v_timesteps,
+                            const float* a_timesteps, int n_a_timesteps, const float* sigma_dev, const float* v_mask, const float* v_clean,
+                            float cfg_scale, float sigma, float sigma_next, void* stream);
+/* n_steps of that step as one captured graph owned by ctx (ltx2_dit_graph_launch(ctx) replays it), built like ltx2_dit_graph_capture_cond_av: a
+ * modality with a mask gets per-token timesteps mask * sigma_i formed on the device into ctx's buffer, which both contexts read.  The frozen audio
+ * passes its all-zero mask (no clean latent: it is never blended or stepped); v_mask may be NULL (v_clean then NULL too).                      */
+int ltx2_dit_graph_capture_guided_av(ltx2_dit* ctx, ltx2_dit* neg, float* v_latent, const float* a_latent, const float* host_sigmas, int n_steps,
+                                     const float* v_mask, int64_t n_v_mask, const float* v_clean, int64_t n_v_clean, const float* a_mask,
+                                     int64_t n_a_mask, float cfg_scale, void* stream);
 /* ltx2_dit_guided_step with a guider whose scalars are sums over the whole latent: forward(ctx), forward(neg), ltx2_guidance_sums and
  * ltx2_projected_euler_step in place on `latent`, in order on the caller's stream.  mode / scale / eta / norm_threshold as in
  * ltx2_projected_euler_step; momentum != 0 (mode 2 only) keeps the running guidance in a [N][out_channels] fp32 buffer owned by ctx: first != 0

@@ -119,6 +119,8 @@ SIGNATURES = {
     "ltx2_dit_graph_capture_cond_av": (i32, [vp, vp, vp, C.POINTER(f32), i32, vp, i64, vp, i64, vp, i64, vp, i64, vp]),
     "ltx2_dit_guided_step": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, f32, f32, f32, vp]),
     "ltx2_dit_graph_capture_guided": (i32, [vp, vp, vp, C.POINTER(f32), i32, vp, i64, vp, i64, f32, vp]),
+    "ltx2_dit_guided_step_av": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, f32, f32, f32, vp]),
+    "ltx2_dit_graph_capture_guided_av": (i32, [vp, vp, vp, vp, C.POINTER(f32), i32, vp, i64, vp, i64, vp, i64, f32, vp]),
     "ltx2_dit_projected_step": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, i32, f32, f32, f32, f32, i32, f32, f32, vp]),
     "ltx2_dit_graph_capture_projected": (i32, [vp, vp, vp, C.POINTER(f32), i32, vp, i64, vp, i64, i32, f32, f32, f32, f32, vp]),
     "ltx2_dit_res2s_step": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, f32, f32, f32, vp]),

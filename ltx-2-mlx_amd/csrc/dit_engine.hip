@@ -1197,13 +1197,14 @@ struct Cond {       // one modality's conditioning of a captured loop; mask == n
     long n_clean;
 };
 
-int cond_modality(ltx2_dit* c, int k, const Cond& cd, const float* sigma_i, ModIn& in, StepIo& io, hipStream_t st) {
+// blend = false: a modality that is evaluated but never stepped (the frozen audio of the AudioVideo guided loop): the timesteps alone, no clean latent
+int cond_modality(ltx2_dit* c, int k, const Cond& cd, const float* sigma_i, ModIn& in, StepIo& io, hipStream_t st, bool blend = true) {
     Mod& m = c->m[k];
     if (!cd.mask) return LTX2_OK;
-    LTX2_CHECK_ARG(cd.clean, "dit_graph_capture_cond: a denoise mask needs the clean latent");
+    LTX2_CHECK_ARG(cd.clean || !blend, "dit_graph_capture_cond: a denoise mask needs the clean latent");
     // the replayed kernels read N mask elements and N * C clean-latent elements on every step: a buffer of another modality's length would be an
     // out-of-bounds device read, not an error
-    LTX2_CHECK_ARG(cd.n_mask == m.N && cd.n_clean == (long)m.N * m.Cout, "dit_graph_capture_cond: modality %d has %d tokens x %d channels, got a mask of %ld and a clean latent of %ld elements", k, m.N, m.Cout, cd.n_mask, cd.n_clean);
+    LTX2_CHECK_ARG(cd.n_mask == m.N && (!blend || cd.n_clean == (long)m.N * m.Cout), "dit_graph_capture_cond: modality %d has %d tokens x %d channels, got a mask of %ld and a clean latent of %ld elements", k, m.N, m.Cout, cd.n_mask, cd.n_clean);
     if (!c->per_token || !m.ts_tok) {
         ltx2_set_error("dit_graph_capture_cond: the workspace was not bound for per-token timesteps");
         return LTX2_E_STATE;
@@ -1212,6 +1213,7 @@ int cond_modality(ltx2_dit* c, int k, const Cond& cd, const float* sigma_i, ModI
     LTX2_CHECK_LAUNCH("mask_sigma_kernel");
     in.ts = m.ts_tok;
     in.n_ts = m.N;
+    if (!blend) return LTX2_OK;
     io.mask = cd.mask;
     io.clean = cd.clean;
     return LTX2_OK;
@@ -1249,7 +1251,48 @@ int guided_step(ltx2_dit* c, ltx2_dit* neg, const ModIn& in, const StepIo& io, f
     return guided_euler_step_launch(in.latent, m.vel, neg->m[0].vel, in.ts, in.n_ts == 1 ? 0 : 1, io.mask, io.clean, cfg_scale, sigma, sigma_next, io.latent,
                                     m.N, m.Cout, st);
 }
+
+// The same on the AudioVideo engine with the audio latent frozen (audio-to-video; reference pipelines/a2vid_two_stage.py:225-271): both contexts
+// evaluate both modalities, the guidance and the Euler update touch the video latent alone.  Every count is checked here, before the first launch.
+int guided_ready_av(ltx2_dit* c, ltx2_dit* neg, int n_v_ts, int n_a_ts, const char* who) {
+    LTX2_CHECK_ARG(c && neg, "%s: null context", who);
+    LTX2_CHECK_ARG(c != neg, "%s: the negative prompt needs a context of its own (ctx == neg)", who);
+    LTX2_CHECK_ARG(c->av && neg->av, "%s: both contexts must be AudioVideo (the VideoOnly engine has ltx2_dit_guided_step)", who);
+    LTX2_CHECK_ARG(c->prepared && neg->prepared, "%s: ltx2_dit_prepare_av has not been called on both contexts", who);
+    LTX2_CHECK_ARG(c->m[0].N == neg->m[0].N && c->m[1].N == neg->m[1].N && c->m[0].Cout == neg->m[0].Cout,
+                   "%s: the contexts differ: %d video + %d audio tokens x %d channels against %d + %d x %d", who, c->m[0].N, c->m[1].N, c->m[0].Cout,
+                   neg->m[0].N, neg->m[1].N, neg->m[0].Cout);
+    LTX2_CHECK_ARG((n_v_ts == 1 || n_v_ts == c->m[0].N) && (n_a_ts == 1 || n_a_ts == c->m[1].N),
+                   "%s: n_v_timesteps=%d must be 1 or N=%d, n_a_timesteps=%d must be 1 or Na=%d", who, n_v_ts, c->m[0].N, n_a_ts, c->m[1].N);
+    LTX2_CHECK_ARG((n_v_ts == 1 && n_a_ts == 1) || (c->per_token && neg->per_token), "%s: a workspace was not bound for per-token timesteps", who);
+    return LTX2_OK;
+}
+
+// in[0] / in[1]: (latent, timesteps, sigma) of the video and the audio modality, read by both contexts; io: the VIDEO latent it updates and its conditioning
+int guided_step_av(ltx2_dit* c, ltx2_dit* neg, const ModIn in[2], const StepIo& io, float cfg_scale, float sigma, float sigma_next, hipStream_t st,
+                   bool rewind_events = true) {
+    LTX2_CHECK_ARG(sigma != 0.f, "Sigma can't be 0.0");
+    LTX2_CHECK_ARG((io.mask == nullptr) == (io.clean == nullptr), "dit_guided_step_av: mask and clean go together");
+    ltx2_dit* const both[2] = {c, neg};
+    for (ltx2_dit* e : both) {
+        const ModIn ev[2] = {{in[0].latent, in[0].ts, in[0].n_ts, in[0].sigma, e->m[0].vel}, {in[1].latent, in[1].ts, in[1].n_ts, in[1].sigma, e->m[1].vel}};
+        TRY(forward(e, ev, st, rewind_events));
+    }
+    const Mod& m = c->m[0];
+    return guided_euler_step_launch(in[0].latent, m.vel, neg->m[0].vel, in[0].ts, in[0].n_ts == 1 ? 0 : 1, io.mask, io.clean, cfg_scale, sigma, sigma_next,
+                                    io.latent, m.N, m.Cout, st);
+}
 }  // namespace
+
+int ltx2_dit_guided_step_av(ltx2_dit* c, ltx2_dit* neg, float* v_latent, const float* a_latent, const float* v_timesteps, int n_v_timesteps,
+                            const float* a_timesteps, int n_a_timesteps, const float* sigma_dev, const float* v_mask, const float* v_clean,
+                            float cfg_scale, float sigma, float sigma_next, void* stream) {
+    LTX2_CHECK_ARG(v_latent && a_latent && v_timesteps && a_timesteps && sigma_dev, "dit_guided_step_av: null argument");
+    TRY(guided_ready_av(c, neg, n_v_timesteps, n_a_timesteps, "dit_guided_step_av"));
+    const ModIn in[2] = {{v_latent, v_timesteps, n_v_timesteps, sigma_dev, nullptr}, {a_latent, a_timesteps, n_a_timesteps, sigma_dev, nullptr}};
+    const StepIo io = {v_latent, v_mask, v_clean, nullptr};
+    return guided_step_av(c, neg, in, io, cfg_scale, sigma, sigma_next, (hipStream_t)stream);
+}
 
 int ltx2_dit_guided_step(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev,
                          const float* mask, const float* clean, float cfg_scale, float sigma, float sigma_next, void* stream) {
@@ -1423,7 +1466,8 @@ int res2s_step(ltx2_dit* c, ltx2_dit* neg, const ModIn& in, const float* ts_sub,
 
 // The one captured sampling loop behind every ltx2_dit_graph_capture* entry: per step, sigma_i read on the device, each modality's timesteps (sigma_i, or
 // mask * sigma_i where it is conditioned), then the step that LoopStep names.  All but the plain step run on VideoOnly contexts (latent[0] / cond[0]
-// only), form ts = mask * sigma_i in c's buffer and let both contexts read it.  The event pool is rewound on step 0 only, so no event is re-recorded
+// only), form ts = mask * sigma_i in c's buffer and let both contexts read it; the guided step on AudioVideo contexts steps latent[0] alone and reads
+// latent[1] (cond[1]: its mask, for the timesteps only).  The event pool is rewound on step 0 only, so no event is re-recorded
 // inside the capture.
 struct LoopStep {                           // all defaults: the plain denoise step
     ltx2_dit* neg = nullptr;                // the negative prompt's context: a guided step, or guidance inside the two below
@@ -1451,7 +1495,7 @@ int capture_loop(ltx2_dit* c, const LoopStep& step, float* const latent[2], cons
         for (int k = 0; k < nm && rc == LTX2_OK; ++k) {
             in[k] = {latent[k], s, 1, s, nullptr};
             io[k] = {latent[k], nullptr, nullptr, nullptr};
-            rc = cond_modality(c, k, cond[k], s, in[k], io[k], st);
+            rc = cond_modality(c, k, cond[k], s, in[k], io[k], st, !(step.neg && c->av && k == 1));
         }
         if (rc != LTX2_OK) break;
         if (step.res2s) {
@@ -1459,6 +1503,8 @@ int capture_loop(ltx2_dit* c, const LoopStep& step, float* const latent[2], cons
             if (step.res2s[i].last) break;                      // the reference's loop ends on its final step
         } else if (step.projected) {
             rc = projected_step(c, step.neg, in[0], io[0], *step.projected, i == 0, sigma, sigma_next, st);
+        } else if (step.neg && c->av) {
+            rc = guided_step_av(c, step.neg, in, io[0], step.cfg_scale, sigma, sigma_next, st, i == 0);
         } else if (step.neg) {
             rc = guided_step(c, step.neg, in[0], io[0], step.cfg_scale, sigma, sigma_next, st);
         } else {
@@ -1544,6 +1590,17 @@ int ltx2_dit_graph_capture_cond_av(ltx2_dit* c, float* v_latent, float* a_latent
     float* const lat[2] = {v_latent, a_latent};
     const Cond cond[2] = {{v_mask, (long)n_v_mask, v_clean, (long)n_v_clean}, {a_mask, (long)n_a_mask, a_clean, (long)n_a_clean}};
     return capture_loop(c, {}, lat, cond, host_sigmas, n_steps, (hipStream_t)stream);
+}
+
+int ltx2_dit_graph_capture_guided_av(ltx2_dit* c, ltx2_dit* neg, float* v_latent, const float* a_latent, const float* host_sigmas, int n_steps,
+                                     const float* v_mask, int64_t n_v_mask, const float* v_clean, int64_t n_v_clean, const float* a_mask, int64_t n_a_mask,
+                                     float cfg_scale, void* stream) {
+    LTX2_CHECK_ARG(v_latent && a_latent && host_sigmas && n_steps > 0 && n_steps < 64, "dit_graph_capture_guided_av: bad argument");
+    TRY(guided_ready_av(c, neg, v_mask ? c->m[0].N : 1, a_mask ? c->m[1].N : 1, "dit_graph_capture_guided_av"));
+    LTX2_CHECK_ARG((v_mask == nullptr) == (v_clean == nullptr), "dit_graph_capture_guided_av: mask and clean go together");
+    float* const lat[2] = {v_latent, const_cast<float*>(a_latent)};        // the audio latent is read by both evaluations and never written
+    const Cond cond[2] = {{v_mask, (long)n_v_mask, v_clean, (long)n_v_clean}, {a_mask, (long)n_a_mask, nullptr, 0}};
+    return capture_loop(c, {neg, cfg_scale}, lat, cond, host_sigmas, n_steps, (hipStream_t)stream);
 }
 
 int ltx2_dit_graph_capture_av(ltx2_dit* c, float* v_latent, float* a_latent, const float* host_sigmas, int n_steps,

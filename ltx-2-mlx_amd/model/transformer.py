@@ -590,14 +590,22 @@ class LTXModel:
         return t
 
     # ------------------------------------------------------------------ fused sampling step / graph
-    def _step_inputs(self, latent: torch.Tensor, video: Modality, sigma: float) -> Tuple[torch.Tensor, int, Optional[torch.Tensor]]:
-        """What every fused video-only step does first: -> (timesteps, n_timesteps, the prompt AdaLN's sigma scalar or None), with this
-        context prepared for `video` and its context mask applied."""
+    def _step_inputs(self, latent: torch.Tensor, video: Modality, sigma: float, audio_latent: Optional[torch.Tensor] = None,
+                     audio: Optional[Modality] = None):
+        """What every fused step does first: -> (timesteps, n_timesteps, the prompt AdaLN's sigma scalar or None), with this context prepared
+        for `video` and its context mask applied.  On an AudioVideo context, with `audio`: -> (timesteps, n_timesteps, the sigma scalar both
+        modalities share, audio timesteps, n_audio_timesteps), prepared for both modalities."""
         ts, n_ts = self._timesteps(video)
         assert latent.dtype == torch.float32 and latent.is_contiguous() and latent.dim() == 2
-        self._ensure_prepared(video, per_token=(n_ts != 1))
-        self._apply_context_masks(video)
-        return ts, n_ts, (self._sigma_scalar(sigma) if self.cross_attention_adaln else None)
+        if not self.is_av:
+            self._ensure_prepared(video, per_token=(n_ts != 1))
+            self._apply_context_masks(video)
+            return ts, n_ts, (self._sigma_scalar(sigma) if self.cross_attention_adaln else None)
+        assert audio is not None and audio_latent is not None and audio_latent.dtype == torch.float32 and audio_latent.is_contiguous()
+        ats, n_ats = self._timesteps(audio)
+        self._ensure_prepared(video, per_token=(n_ts != 1 or n_ats != 1), audio=audio)
+        self._apply_context_masks(video, audio)
+        return ts, n_ts, self._sigma_scalar(sigma), ats, n_ats
 
     def _capture_inputs(self, sigmas: Sequence[float], *mask_clean_pairs):
         """What every capture_*_graph does first: -> (the sigmas as a c_float array, the step count, the current stream, n_el).  Capture
@@ -631,13 +639,7 @@ class LTXModel:
             nv.check(self._L.ltx2_dit_denoise_step(self._h, nv.ptr(latent), nv.ptr(ts), n_ts, nv.ptr(sg), nv.ptr(denoise_mask),
                                                     nv.ptr(clean_latent), float(sigma), float(sigma_next), None, nv.stream()))
             return
-        ts, n_ts = self._timesteps(video)
-        assert latent.dtype == torch.float32 and latent.is_contiguous() and latent.dim() == 2
-        assert audio is not None and audio_latent is not None and audio_latent.dtype == torch.float32 and audio_latent.is_contiguous()
-        ats, n_ats = self._timesteps(audio)
-        self._ensure_prepared(video, per_token=(n_ts != 1 or n_ats != 1), audio=audio)
-        self._apply_context_masks(video, audio)
-        sg = self._sigma_scalar(sigma)
+        ts, n_ts, sg, ats, n_ats = self._step_inputs(latent, video, sigma, audio_latent, audio)
         nv.check(self._L.ltx2_dit_denoise_step_av(self._h, nv.ptr(latent), nv.ptr(audio_latent), nv.ptr(ts), n_ts, nv.ptr(ats), n_ats,
                                                    nv.ptr(sg), nv.ptr(denoise_mask), nv.ptr(clean_latent), nv.ptr(audio_denoise_mask),
                                                    nv.ptr(audio_clean_latent), float(sigma), float(sigma_next), None, None, nv.stream()))
@@ -701,6 +703,48 @@ class LTXModel:
     def replay_guided_graph(self) -> None:
         """Replay the graph captured by capture_guided_graph (it belongs to the VideoOnly context that ran the capture)."""
         self._replay("guided", "no guided graph captured")
+
+    # ------------------------------------------------------------------ classifier-free guidance with a frozen audio latent (AudioVideo engine)
+    def _guided_av_pair(self, neg: "LTXModel") -> Tuple["LTXModel", "LTXModel"]:
+        if not isinstance(neg, LTXModel):
+            raise ValueError("guidance needs a second LTXModel context (clone_sharing_weights()) for the negative prompt")
+        if not (self.is_av and neg.is_av):
+            raise ValueError("guided_step_av_ runs on AudioVideo contexts (a VideoOnly model has guided_step_)")
+        return self, neg
+
+    def guided_step_av_(self, neg: "LTXModel", latent: torch.Tensor, audio_latent: torch.Tensor, video: Modality, audio: Modality, sigma: float,
+                        sigma_next: float, cfg_scale: float, denoise_mask: Optional[torch.Tensor] = None,
+                        clean_latent: Optional[torch.Tensor] = None) -> None:
+        """In-place on the VIDEO latent (N, C) fp32: one classifier-free-guided Euler step of the AudioVideo model with the audio latent
+        (Na, C) fp32 frozen -- both modalities through this context and through `neg` (clone_sharing_weights(), prepared by the caller with the
+        negative contexts), then x0 x 2 + CFGGuider.guide + post_process_latent + Euler on the video alone, all enqueued by ONE C call
+        (ltx2_dit_guided_step_av).  audio_latent is only read."""
+        pos, ng = self._guided_av_pair(neg)
+        ts, n_ts, sg, ats, n_ats = pos._step_inputs(latent, video, sigma, audio_latent, audio)
+        nv.check(pos._L.ltx2_dit_guided_step_av(pos._h, ng._h, nv.ptr(latent), nv.ptr(audio_latent), nv.ptr(ts), n_ts, nv.ptr(ats), n_ats, nv.ptr(sg),
+                                                nv.ptr(denoise_mask), nv.ptr(clean_latent), float(cfg_scale), float(sigma), float(sigma_next),
+                                                nv.stream()))
+
+    def capture_guided_av_graph(self, neg: "LTXModel", latent: torch.Tensor, audio_latent: torch.Tensor, sigmas: Sequence[float], cfg_scale: float,
+                                denoise_mask: Optional[torch.Tensor] = None, clean_latent: Optional[torch.Tensor] = None,
+                                audio_denoise_mask: Optional[torch.Tensor] = None) -> None:
+        """hipGraph-capture len(sigmas)-1 of those steps over `latent` (N, C fp32), reading `audio_latent` (Na, C fp32) on every replay
+        (ltx2_dit_graph_capture_guided_av).  audio_denoise_mask (Na,) fp32: the frozen audio's all-zero mask, its per-token timesteps.  Both
+        contexts are prepared first (per_token=True when a mask is given); the graph belongs to this context and replay_guided_av_graph()
+        replays it.  The tensors must stay alive while it is replayed."""
+        pos, ng = self._guided_av_pair(neg)
+        assert pos._prep_key is not None and ng._prep_key is not None, "call prepare() on both contexts first"
+        assert audio_latent.dtype == torch.float32 and audio_latent.is_contiguous()
+        arr, n, st, n_el = self._capture_inputs(sigmas, (denoise_mask, clean_latent), (audio_denoise_mask, audio_latent))
+        pos._graph_refs = (latent, audio_latent, denoise_mask, clean_latent, audio_denoise_mask, ng)
+        nv.check(pos._L.ltx2_dit_graph_capture_guided_av(pos._h, ng._h, nv.ptr(latent), nv.ptr(audio_latent), arr, n, nv.ptr(denoise_mask),
+                                                         n_el(denoise_mask), nv.ptr(clean_latent), n_el(clean_latent), nv.ptr(audio_denoise_mask),
+                                                         n_el(audio_denoise_mask), float(cfg_scale), st.cuda_stream))
+        self._graph_owner = ("guided_av", pos)
+
+    def replay_guided_av_graph(self) -> None:
+        """Replay the graph captured by capture_guided_av_graph."""
+        self._replay("guided_av", "no guided AudioVideo graph captured")
 
     # ------------------------------------------------------------------ guiders whose scalars are sums over the latent (video-only engine)
     def projected_step_(self, neg: "LTXModel", latent: torch.Tensor, video: Modality, sigma: float, sigma_next: float, mode: int, scale: float,

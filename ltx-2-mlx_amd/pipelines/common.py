@@ -194,10 +194,11 @@ def capture_and_replay(capture: Callable[[], None], replay: Callable[[], None]) 
     torch.cuda.current_stream().wait_stream(side)
 
 
-def _video_loop_inputs(model, video_state: LatentState):
-    """What the device-resident video loops step: -> (the video-only model, whether the mask is all ones, the fp32 latent (N, C), cloned as
-    it is stepped in place: never the caller's tensor, and the fp32 mask (N,) / clean latent (N, C), None when uniform)."""
-    if model.is_av:
+def _video_loop_inputs(model, video_state: LatentState, video_only: bool = True):
+    """What the device-resident video loops step: -> (the video-only model, or with video_only=False the model as it is, whether the mask is
+    all ones, the fp32 latent (N, C), cloned as it is stepped in place: never the caller's tensor, and the fp32 mask (N,) / clean latent
+    (N, C), None when uniform)."""
+    if model.is_av and video_only:
         model = model._video_twin()
     uniform = bool((video_state.denoise_mask == 1).all())
     lat = video_state.latent[0].float().clone(memory_format=torch.contiguous_format)
@@ -319,6 +320,50 @@ def guided_denoise_loop(transformer, video_state: LatentState, sigmas, context: 
             if callback:
                 callback(i + 1, n)
     return _with_latent(video_state, lat)
+
+
+def frozen_audio_guided_loop(transformer, video_state: LatentState, audio_state: LatentState, sigmas, video_context: torch.Tensor,
+                             audio_context: torch.Tensor, negative_video_context: Optional[torch.Tensor],
+                             negative_audio_context: Optional[torch.Tensor], cfg_scale: float, stepper, callback=None,
+                             use_hip_graph: bool = True) -> Tuple[LatentState, LatentState]:
+    """Audio-to-video sampling on the AudioVideo model (the reference's _video_only_denoise_loop, pipelines/a2vid_two_stage.py:225-271): the
+    audio state is a given latent with an all-zero denoise mask, fed to every evaluation and never stepped; classifier-free guidance,
+    post_process_latent and the Euler step act on the video alone.  With cfg_scale > 1 and a negative video context every step is ONE C call
+    -- both modalities through the positive and through the negative context, then the guided Euler kernel on the video latent
+    (LTXModel.guided_step_av_) -- and with no callback and fewer than 64 steps the whole loop is one captured graph.  The negative pass
+    takes `negative_audio_context or audio_context`, as the reference does.  Without guidance the loop is joint_denoise_loop's frozen-audio
+    path, unchanged.  `transformer` is an X0Model over an AudioVideo model.  Returns (video_state, the audio_state object it was given)."""
+    if not bool((audio_state.denoise_mask == 0).all()):
+        raise ValueError("frozen_audio_guided_loop: the audio state's denoise mask must be all zero (the audio latent is given, not sampled)")
+    model = transformer.velocity_model
+    if not model.is_av:
+        raise ValueError("frozen_audio_guided_loop requires an audio-video (AV) model")
+    if audio_context is None:
+        raise ValueError("AudioVideo model: audio_encoding (the audio text context) is required")
+    if not (cfg_scale > 1.0 and negative_video_context is not None):
+        video_state, _ = joint_denoise_loop(transformer, True, video_state, audio_state, sigmas, video_context, audio_context, stepper, callback, use_hip_graph)
+        return video_state, audio_state
+    sig = [float(s) for s in sigmas]
+    n = len(sig) - 1
+    model, uniform, lat, mask, clean = _video_loop_inputs(model, video_state, video_only=False)
+    alat = audio_state.latent[0].float().contiguous()
+    amask = audio_state.denoise_mask[0].reshape(-1).float().contiguous()
+    negative_audio_context = negative_audio_context if negative_audio_context is not None else audio_context
+    neg = model.clone_sharing_weights()
+    model.prepare(video_context, video_state.positions, per_token=True, audio_context=audio_context, audio_positions=audio_state.positions)
+    neg.prepare(negative_video_context, video_state.positions, per_token=True, audio_context=negative_audio_context, audio_positions=audio_state.positions)
+    if use_hip_graph and callback is None and n < 64:
+        capture_and_replay(lambda: model.capture_guided_av_graph(neg, lat, alat, sig, cfg_scale, denoise_mask=mask, clean_latent=clean,
+                                                                 audio_denoise_mask=amask), model.replay_guided_av_graph)
+    else:
+        for i in range(n):
+            st = video_state.replace(latent=lat[None])
+            model.guided_step_av_(neg, lat, alat, modality_from_state(st, video_context, sig[i], uniform=uniform),
+                                  audio_modality_from_state(audio_state, audio_context, sig[i]), sig[i], sig[i + 1], cfg_scale,
+                                  denoise_mask=mask, clean_latent=clean)
+            if callback:
+                callback(i + 1, n)
+    return _with_latent(video_state, lat), audio_state
 
 
 def projected_guider_args(guider) -> Optional[dict]:

@@ -9,7 +9,7 @@ encode_with_gemma :340-486, encode_av_gemma_batch :511-640; an LTX-2.3 checkpoin
 :548-551).  Out of this path (and rejected with a clear message): STG guidance,
 CFG in the video-only loop, the dev model's `--pipeline two-stage`.
 `generate_video` resolves its arguments once (`_resolve_request`: every refusal, before a model is loaded), loads the text encoding, the transformer and the VAE decoder, and
-runs ONE route, each a function of its own: retake (`--retake CLIP`), keyframe (`--pipeline keyframe-interpolation --keyframe path:frame[:strength]`), hq (`--ti2vid-hq`), ic_lora
+runs ONE route, each a function of its own: a2vid (`--a2vid-two-stage --audio FILE --spatial-upscaler-weights W`: the two-stage audio-to-video pipeline), retake (`--retake CLIP`), keyframe (`--pipeline keyframe-interpolation --keyframe path:frame[:strength]`), hq (`--ti2vid-hq`), ic_lora
 (`--pipeline ic-lora --control-video V` and / or `--image`), two_stage (`--two-stage-distilled --spatial-upscaler-weights W`; with `--generate-audio` on the AudioVideo transformer), av
 (`--generate-audio` or an LTX-2.3 checkpoint: the audio LATENT is saved beside the frames; `--decode-audio`, the default when the checkpoint holds the audio VAE decoder and vocoder, also
 decodes it to `<output>.wav` and muxes it into the mp4, reference save_video_with_audio; `--audio FILE` generates the video TO that audio: the audio VAE encoder's latent stays frozen in
@@ -36,6 +36,7 @@ from ltx_2_mlx_amd.components import DISTILLED_SIGMA_VALUES, VideoLatentPatchifi
 from ltx_2_mlx_amd.model.transformer import LTXModel, Modality, X0Model  # noqa: E402
 from ltx_2_mlx_amd.model.video_vae import SimpleVideoDecoder, TilingConfig, load_vae_decoder_weights  # noqa: E402
 from ltx_2_mlx_amd.model.video_vae_encoder import SimpleVideoEncoder, load_vae_encoder_weights  # noqa: E402
+from ltx_2_mlx_amd.pipelines.a2vid_two_stage import encode_audio_file, fit_audio_latent  # noqa: E402,F401
 from ltx_2_mlx_amd.types import SpatioTemporalScaleFactors, VideoLatentShape  # noqa: E402
 
 
@@ -419,36 +420,26 @@ def checkpoint_has_audio_encoder(checkpoint_path) -> bool:
         return any(k.startswith("audio_vae.encoder.") for k in st.keys())
 
 
-def fit_audio_latent(latent, frames: int):
-    """Encoded latent (1, C, T, F) -> exactly `frames` latent frames: a surplus trailing frame (the waveform's last, partly padded one) is
-    cropped; a latent that comes out short is an error, it is not padded."""
-    if latent.shape[2] < frames:
-        raise ValueError(f"the encoded audio has {latent.shape[2]} latent frames, the video needs {frames}")
-    return latent[:, :, :frames].contiguous()
-
-
-def encode_audio_for_video(audio_path, num_frames: int, fps: float, weights_path=None, device="cuda", seed=0, start_time: float = 0.0,
-                           max_duration=None):
-    """Audio file -> (frozen audio latent (1, 8, T_a, 16) for a num_frames / fps video, the fitted waveform [C, samples], its rate):
-    load_audio_file (start / duration trim, resample to 16 kHz), cut or right-padded with silence to the video's length,
-    AudioProcessor.waveform_to_mel, AudioEncoder.  Encoder weights from the checkpoint when it has `audio_vae.encoder.*`, random init
-    otherwise."""
-    from ltx_2_mlx_amd.model.audio_vae import AudioEncoder, AudioProcessor, encode_audio, load_audio_encoder_weights, load_audio_file
-    from ltx_2_mlx_amd.types import AudioLatentShape, VideoPixelShape
-    waveform, sr = load_audio_file(audio_path, 16000, start_time, max_duration)
-    print(f"  Audio: {waveform.shape[1] / sr:.1f}s, {sr}Hz, {waveform.shape[0]}ch")
-    proc = AudioProcessor(sample_rate=sr, device=device)
-    waveform = proc.fit_waveform(waveform[:2], proc.samples_for_video(num_frames, fps))
+def create_audio_encoder(weights_path=None, device="cuda", seed=0):
+    """The audio VAE encoder: weights from the checkpoint when it has `audio_vae.encoder.*`, random init otherwise."""
+    from ltx_2_mlx_amd.model.audio_vae import AudioEncoder, load_audio_encoder_weights
     enc = AudioEncoder(device=device)
     if checkpoint_has_audio_encoder(weights_path):
         load_audio_encoder_weights(enc, weights_path)
     else:
         print("  note: no audio_vae.encoder.* tensors in the checkpoint: RANDOM audio encoder (test mode)")
         enc.init_random_weights(seed=seed)
+    return enc
+
+
+def encode_audio_for_video(audio_path, num_frames: int, fps: float, weights_path=None, device="cuda", seed=0, start_time: float = 0.0,
+                           max_duration=None):
+    """Audio file -> (frozen audio latent (1, 8, T_a, 16) for a num_frames / fps video, the fitted waveform [C, samples], its rate):
+    create_audio_encoder, then pipelines.a2vid_two_stage.encode_audio_file (load_audio_file with the start / duration trim and the resample to
+    16 kHz, cut or right-padded with silence to the video's length, AudioProcessor.waveform_to_mel, AudioEncoder)."""
+    enc = create_audio_encoder(weights_path, device, seed)
     t0 = time.time()
-    latent = encode_audio(proc.waveform_to_mel(waveform, sr), enc)
-    target = AudioLatentShape.from_video_pixel_shape(VideoPixelShape(batch=1, frames=num_frames, height=32, width=32, fps=fps))
-    latent = fit_audio_latent(latent, target.frames)
+    latent, waveform, sr = encode_audio_file(audio_path, num_frames, fps, enc, start_time=start_time, max_duration=max_duration)
     torch.cuda.synchronize()
     print(f"  audio encode: {(time.time() - t0):.3f} s -> {tuple(latent.shape)}")
     return latent, waveform, sr
@@ -623,11 +614,14 @@ _ROUTE_EXCLUDES = {
     "ic_lora": (("generate_audio", "audio_path", "two_stage_distilled", "upscale_temporal", "keyframes"),
                 "with pipeline_type='ic-lora': ICLoraPipeline is video-only, conditions on its control video and image_path alone and ends "
                 "with its own x2 spatial stage"),
+    "a2vid": (("two_stage_distilled", "upscale_temporal", "retake_video"),          # keyframes / control_video: not owned, refused with the out-of-path defaults
+              "with a2vid_two_stage: A2VidPipelineTwoStage generates the video to audio_path on the AudioVideo model, conditions on image_path "
+              "alone and ends with its own x2 spatial stage"),
 }
 # route -> the _OUT_OF_PATH_DEFAULTS arguments that route takes itself.  apg_scale: the routes whose guided loop takes a guider (the AudioVideo route as
 # OneStagePipeline's guider_override, keyframe stage 1, retake's guided mode)
 _ROUTE_OWNS = {"keyframe": ("keyframes", "apg_scale"), "hq": ("distilled_lora", "keyframes"),
-               "ic_lora": ("control_video", "save_control", "keyframes", "ic_lora_weights"), "retake": ("apg_scale",), "av": ("apg_scale",)}
+               "ic_lora": ("control_video", "save_control", "keyframes", "ic_lora_weights"), "retake": ("apg_scale",), "av": ("apg_scale",), "a2vid": ("distilled_lora",)}
 
 
 def _owning_route(r):
@@ -733,7 +727,17 @@ def _resolve_ic_lora(r):
     r.ic_loras = [lora] if lora else []
 
 
-_RESOLVE_ROUTE = {"keyframe": _resolve_keyframe, "hq": _resolve_hq, "ic_lora": _resolve_ic_lora}
+def _resolve_a2vid(r):
+    if not r.audio_path:
+        raise ValueError("a2vid_two_stage needs audio_path (--audio): the video is generated to that audio track")
+    _need_spatial_upscaler(r)
+    from ltx_2_mlx_amd.pipelines import A2VidConfig
+    A2VidConfig(height=r.height, width=r.width, num_frames=r.num_frames)          # its ValueErrors (8k + 1 frames, multiples of 64)
+    r.a2vid_lora = _lora_config(r, r.distilled_lora, r.distilled_lora_scale, "distilled LoRA")
+    r.generate_audio = True          # the AudioVideo transformer and both text encodings, as generate_audio asks for them
+
+
+_RESOLVE_ROUTE = {"keyframe": _resolve_keyframe, "hq": _resolve_hq, "ic_lora": _resolve_ic_lora, "a2vid": _resolve_a2vid}
 
 
 def _resolve_request(kw: dict):
@@ -742,8 +746,10 @@ def _resolve_request(kw: dict):
     retake_to_end / retake_window, parsed_keyframes, hq_lora / ic_loras, cdt, need_cfg, gemma_encodes, encode_negative, have_ckpt / version / v2 / av, toy, output_dir, and negative_encoding /
     negative_audio_encoding of the embedding file.  Loads no model and touches no GPU; every refusal is raised here, in a fixed order.  Returns None (after saying so) when Gemma is asked for and
     its weights are missing."""
-    r = SimpleNamespace(**kw, retake_fps=None, retake_to_end=False, retake_window=None, parsed_keyframes=[], hq_lora=None, ic_loras=[])
-    if r.retake_video is not None:
+    r = SimpleNamespace(**kw, retake_fps=None, retake_to_end=False, retake_window=None, parsed_keyframes=[], hq_lora=None, ic_loras=[], a2vid_lora=None)
+    if r.a2vid_two_stage:
+        r.route = "a2vid"
+    elif r.retake_video is not None:
         r.route = "retake"
     elif r.pipeline_type == "keyframe-interpolation" and bool(r.keyframes):
         r.route = "keyframe"
@@ -824,7 +830,10 @@ def _resolve_request(kw: dict):
     r.av = bool(r.generate_audio or r.v2)
     # the video-only loop of the reference guides only for cfg_scale > 1 (:1935); OneStagePipeline's guiders are enabled for any scale != 1
     r.need_cfg = (r.cfg_scale != 1.0 or r.audio_cfg_scale != 1.0 or r.apg_guider is not None) if r.av else r.cfg_scale > 1.0
-    if r.audio_path:
+    if r.audio_path and r.route == "a2vid":
+        if not os.path.exists(r.audio_path):
+            raise FileNotFoundError(f"audio file not found: {r.audio_path}")
+    elif r.audio_path:
         if r.two_stage_distilled:
             raise NotImplementedError("audio_path (--audio) with two_stage_distilled: DistilledPipeline with a given audio latent is not built")
         if not r.av:
@@ -847,7 +856,7 @@ def _resolve_request(kw: dict):
     if r.low_memory or r.fast_mode:
         print("  low_memory / fast_mode: no effect here (weights and caches stay resident in HBM, the loop is one hipGraph)")
     # the routes that guide themselves take Gemma's encoding of the negative prompt when they will guide (retake: the dev variant only)
-    r.encode_negative = (r.cfg_scale != 1.0 or r.apg_guider is not None) and (r.route in ("keyframe", "hq") or (r.route == "retake" and r.model_variant != "distilled"))
+    r.encode_negative = (r.cfg_scale != 1.0 or r.apg_guider is not None) and (r.route in ("keyframe", "hq", "a2vid") or (r.route == "retake" and r.model_variant != "distilled"))
     r.toy = r.vae_base_channels is not None and r.vae_base_channels != 128        # debug-size VAE: matching debug-size upscaler / encoder
     if r.route is None:
         r.route = "two_stage" if r.two_stage_distilled else "av" if r.av else "standard"
@@ -962,6 +971,7 @@ _REQUIRES = {
     "two_stage": ("Two-stage pipeline requires a loaded model (cannot use placeholder mode)",
                   "the two-stage pipeline needs the VAE weights (per-channel statistics): drop --skip-vae", None, True),
     "av": (None, "AV pipeline requires VAE decoder", "  AV pipeline requires model - cannot use placeholder mode", False),
+    "a2vid": ("A2Vid pipeline requires a loaded model", "A2Vid pipeline requires VAE decoder", None, False),
 }
 
 
@@ -1159,6 +1169,38 @@ def _run_retake(r, s):
     return finish(r, s, frames, source_fps=r.retake_fps)
 
 
+def _run_a2vid(r, s):
+    """a2vid_two_stage=True (--a2vid-two-stage; keyword-only, the reference's own CLI never reaches pipelines/a2vid_two_stage.py) runs A2VidPipelineTwoStage on the AudioVideo transformer:
+    audio_path (required; audio_start_time / audio_max_duration trim) is cut or right-padded with silence to num_frames / 25 seconds and encoded by the audio VAE encoder; the latent stays frozen
+    through num_steps steps at half resolution with classifier-free guidance at cfg_scale on the video alone (model_variant="distilled" forces 1: the unguided captured loop), the x2 spatial
+    upscale (spatial_upscaler_weights is required, "random" for a random-initialised one) and 3 distilled steps, under distilled_lora when given.  image_path sits at frame 0.  The negative
+    encodings are Gemma's of `negative_prompt or ""` when Gemma encodes, else `negative_embedding` / `negative_audio_embedding` of the --embedding file, else zeros (video) and the positive
+    audio encoding (audio, as the reference's loop falls back).  Written: the video, `<stem>_audio_latent.npz` (the frozen latent), and the ORIGINAL audio muxed into the mp4 when an ffmpeg
+    binary exists.  Not combined with two_stage_distilled, upscale_temporal, keyframes, retake_video or control_video, nor distilled_lora with fp8_resident."""
+    images = _image_conditions(r)
+    print("\n=== Using A2Vid Two-Stage Pipeline ===")
+    _require(r, s)
+    from ltx_2_mlx_amd.pipelines import A2VidConfig, A2VidPipelineTwoStage
+    conf = A2VidConfig(height=r.height, width=r.width, num_frames=r.num_frames, seed=r.seed, num_inference_steps=r.num_steps, cfg_scale=r.cfg_scale,
+                       distilled_lora_config=r.a2vid_lora, use_hip_graph=r.use_hip_graph, tiling_config=_tiling(r), audio_start_time=r.audio_start_time,
+                       audio_max_duration=r.audio_max_duration)
+    _banners(r, upscaler=True)
+    print(f"  Encoding audio: {r.audio_path}")
+    latent, waveform, rate = encode_audio_for_video(r.audio_path, r.num_frames, conf.fps, r.weights_path if r.have_ckpt else None, device=r.device,
+                                                    seed=r.seed + 5, start_time=r.audio_start_time, max_duration=r.audio_max_duration)
+    pipe = A2VidPipelineTwoStage(s.model, make_encoder(r) if images else None, s.vae_decoder, _load_or_random(r, "spatial"))
+    negative = s.negative_encoding
+    if _negative_or_zeros_note(r.cfg_scale > 1.0, negative):
+        negative = torch.zeros_like(s.text_encoding)
+    print(f"[5/5] Running A2Vid ({r.num_steps} steps at {r.width // 2}x{r.height // 2}, cfg {r.cfg_scale}, then 3 at {r.width}x{r.height})...")
+    frames, _ = _timed_run("a2vid two-stage", lambda: pipe(None, s.text_encoding, negative, conf, images=images, positive_audio_encoding=s.text_audio_encoding,
+                                                           negative_audio_encoding=s.negative_audio_encoding, audio_latent=latent)[0], tokens_of=pipe)
+    import shutil
+    np.savez(s.base + "_audio_latent.npz", latent=pipe.audio_latent.float().cpu().numpy())
+    wav = np.repeat(waveform, 2, axis=0) if waveform.shape[0] == 1 else waveform
+    return finish(r, s, frames, audio=(wav, rate) if (r.save_mp4 and shutil.which("ffmpeg")) else None)
+
+
 def _run_two_stage(r, s):
     """MI355X extra: two_stage_distilled=True runs the reference's DistilledPipeline class (pipelines/distilled.py:274-505), which the reference's own CLI never wires: 8 steps at half resolution,
     x2 latent upscale, 3 steps at full resolution, image conditioning at both resolutions, auto-tiled decode; with generate_audio on the AudioVideo transformer, the audio latent saved and decoded
@@ -1300,7 +1342,7 @@ def _run_standard(r, s):
 
 
 # today's precedence, top to bottom; _resolve_request names the one that runs
-_ROUTES = {"keyframe": _run_keyframe, "hq": _run_hq, "ic_lora": _run_ic_lora, "retake": _run_retake, "two_stage": _run_two_stage,
+_ROUTES = {"a2vid": _run_a2vid, "keyframe": _run_keyframe, "hq": _run_hq, "ic_lora": _run_ic_lora, "retake": _run_retake, "two_stage": _run_two_stage,
            "av": _run_av, "standard": _run_standard}
 
 
@@ -1383,6 +1425,7 @@ def generate_video(
     audio_path=None,
     audio_start_time: float = 0.0,
     audio_max_duration=None,
+    a2vid_two_stage: bool = False,
     retake_video=None,
     retake_start_time: float = 0.0,
     retake_end_time=None,
@@ -1390,7 +1433,7 @@ def generate_video(
 ):
     """Generate video from a text prompt: denoise loop + VAE decode on MI355X behind the reference's signature.  _resolve_request validates the arguments and names the one route that runs, before
     any model is loaded; then the text encoding, the transformer and the VAE decoder (built from the checkpoint's `config.vae` record) are loaded and the route's function runs.  Precedence, each
-    documented on its function: retake_video (_run_retake; it refuses every other route), pipeline_type "keyframe-interpolation" with keyframes (_run_keyframe), "ti2vid-hq" (_run_hq), "ic-lora"
+    documented on its function: a2vid_two_stage (_run_a2vid; keyword-only, it refuses retake_video), retake_video (_run_retake; it refuses every other route), pipeline_type "keyframe-interpolation" with keyframes (_run_keyframe), "ti2vid-hq" (_run_hq), "ic-lora"
     with a control video or an image (_run_ic_lora), two_stage_distilled (_run_two_stage), generate_audio or an LTX-2.3 checkpoint (_run_av), else the standard video-only loop (_run_standard).
     pipeline_type "two-stage" raises NotImplementedError. MI355X extras for every route: model_version="2.3" builds the LTX-2.3 architecture without a checkpoint (random init, for tests and
     benchmarks); fp8_resident keeps fp8 checkpoint weights as codes in HBM; fp8_compute runs the video stream's projections fp8 x fp8 on the fp8 MFMA (BASELINE config 3; per-token / per-channel
@@ -1492,6 +1535,10 @@ def build_parser() -> argparse.ArgumentParser:
                    "encoded by the audio VAE encoder and stays frozen while the video is denoised; the original audio is muxed into the mp4")
     p.add_argument("--audio-start", type=float, default=0.0, help="seconds into --audio to start from")
     p.add_argument("--audio-duration", type=float, default=None, help="at most this many seconds of --audio (the rest of the video's length is silence)")
+    p.add_argument("--a2vid-two-stage", action="store_true", help="A2VidPipelineTwoStage: generate the video TO --audio at production quality on the AudioVideo model: --steps "
+                   "steps at half resolution with classifier-free guidance on the video alone and the encoded audio frozen, x2 latent upscale "
+                   "(--spatial-upscaler-weights), 3 distilled steps over the same frozen audio, optionally under --distilled-lora.  A flag of its own: "
+                   "the reference ships this pipeline but its command line never reaches it, so --pipeline keeps the reference's choices")
     p.add_argument("--retake", type=str, default=None, help="RetakePipeline: keep this clip (.npy / .npz frames or an image directory at --fps; a video file with ffmpeg) "
                    "and regenerate the seconds --retake-start .. --retake-end of it from the prompt; size and length come from the clip.  --model-variant distilled: "
                    "8 steps, no guidance; dev: --steps steps at --cfg")
@@ -1528,7 +1575,7 @@ def kwargs_from_args(a) -> dict:
         text_features_path=a.text_features, use_hip_graph=not a.no_hip_graph, two_stage_distilled=a.two_stage_distilled,
         fp8_resident=a.fp8_resident, fp8_compute=a.fp8_compute, model_version=a.model_version, compute_dtype="bfloat16" if a.bf16 else None, num_layers=a.layers, num_heads=a.heads,
         vae_base_channels=a.vae_base_channels, save_mp4=not a.no_video_file, decode_audio=a.decode_audio,
-        audio_path=a.audio, audio_start_time=a.audio_start, audio_max_duration=a.audio_duration,
+        audio_path=a.audio, audio_start_time=a.audio_start, audio_max_duration=a.audio_duration, a2vid_two_stage=a.a2vid_two_stage,
         retake_video=a.retake, retake_start_time=a.retake_start, retake_end_time=a.retake_end, retake_composite=a.retake_keep_source)
 
 
