@@ -316,6 +316,21 @@ int ltx2_res2s_midpoint(const float* x, const float* vel_cond, const float* vel_
 int ltx2_res2s_combine(const float* x_mid, const float* vel_cond, const float* vel_uncond, const float* ts, int64_t ts_stride, const float* mask,
                        const float* clean, float cfg_scale, const float* anchor, const float* eps1, float h, float b1, float b2, float* out,
                        int rows, int C, void* stream);
+/* The same two passes over TWO latents in ONE launch -- the video and the audio latent of a joint step (pipelines/ti2vid_hq.py:217-268), the
+ * audio one about a hundred rows.  The single forms' operands twice, v_ then a_; each segment has its own cfg_scale, ts / ts_stride,
+ * mask / clean and rows / C, while c / n_bong and h / b1 / b2 are shared.  Each segment's output equals the single entry's bit for bit.
+ * 16-byte accesses only when BOTH segments qualify.  The final-step form (anchor == eps1 == NULL) applies to both segments together.
+ * (additive entries of ABI version 3)                                                                                                  */
+int ltx2_res2s_midpoint_pair(const float* v_x, const float* v_vel_cond, const float* v_vel_uncond, const float* v_ts, int64_t v_ts_stride,
+                             const float* v_mask, const float* v_clean, float v_cfg_scale, float* v_x_mid, float* v_anchor, float* v_eps1, int v_rows,
+                             int v_C, const float* a_x, const float* a_vel_cond, const float* a_vel_uncond, const float* a_ts, int64_t a_ts_stride,
+                             const float* a_mask, const float* a_clean, float a_cfg_scale, float* a_x_mid, float* a_anchor, float* a_eps1, int a_rows,
+                             int a_C, float c, int n_bong, void* stream);
+int ltx2_res2s_combine_pair(const float* v_x_mid, const float* v_vel_cond, const float* v_vel_uncond, const float* v_ts, int64_t v_ts_stride,
+                            const float* v_mask, const float* v_clean, float v_cfg_scale, const float* v_anchor, const float* v_eps1, float* v_out,
+                            int v_rows, int v_C, const float* a_x_mid, const float* a_vel_cond, const float* a_vel_uncond, const float* a_ts,
+                            int64_t a_ts_stride, const float* a_mask, const float* a_clean, float a_cfg_scale, const float* a_anchor,
+                            const float* a_eps1, float* a_out, int a_rows, int a_C, float h, float b1, float b2, void* stream);
 
 /* Guiders whose scalars are sums over the whole latent -- CFGStarRescalingGuider, LtxAPGGuider, LegacyStatefulAPGGuider (components/guiders.py:51-76,
  * 105-205) -- as two passes over [rows][C] fp32.  Every fp32 operation is individually rounded (no FMA contraction); the sums are fp64.
@@ -524,6 +539,21 @@ int ltx2_dit_res2s_step(ltx2_dit* ctx, ltx2_dit* neg, float* latent, const float
  * same buffer after the midpoint kernel.  The graph belongs to ctx: ltx2_dit_graph_launch(ctx) replays it.                              */
 int ltx2_dit_graph_capture_res2s(ltx2_dit* ctx, ltx2_dit* neg, float* latent, const float* host_sigmas, int n_steps, const float* mask,
                                  int64_t n_mask, const float* clean, int64_t n_clean, float cfg_scale, void* stream);
+/* One JOINT res_2s step on the AudioVideo engine (pipelines/ti2vid_hq.py:153-319): both latents are stepped.  In order on the caller's stream:
+ * forward(ctx) and forward(neg) on both modalities (built as in ltx2_dit_guided_step_av), ltx2_res2s_midpoint_pair into workspaces owned by
+ * ctx, both contexts again from the two midpoint latents at the sub-sigma timesteps, ltx2_res2s_combine_pair into both latents in place.
+ * The video is guided by cfg_scale and the audio by audio_cfg_scale, both as uncond + s*(cond - uncond).  neg may be NULL: no guidance, two
+ * evaluations.  The plan (h, a21, b1, b2, n_bong, the final step) is that of ltx2_dit_res2s_step; on the final step both latents take d.
+ * n_v_timesteps (1 or N) counts v_timesteps and v_ts_sub, n_a_timesteps (1 or Na) a_timesteps and a_ts_sub; sigma_dev / sub_sigma_dev: one
+ * float each, shared by the modalities (sub_sigma_dev NULL: the first of v_ts_sub).  Workspace: 3 x (N*C + Na*Ca) fp32, allocated on first
+ * use for the bound shapes.  The step is enqueued eagerly only: there is no captured form of the joint loop.
+ * LTX2_E_INVALID, before anything is launched: the rules of ltx2_dit_guided_step_av (with neg NULL the same rules on ctx alone), a mask
+ * without its clean latent, sigma <= 0, sigma_next < 0.
+ * (additive entry of ABI version 3)                                                                                                    */
+int ltx2_dit_res2s_step_av(ltx2_dit* ctx, ltx2_dit* neg, float* v_latent, float* a_latent, const float* v_timesteps, int n_v_timesteps,
+                           const float* a_timesteps, int n_a_timesteps, const float* sigma_dev, const float* v_ts_sub, const float* a_ts_sub,
+                           const float* sub_sigma_dev, const float* v_mask, const float* v_clean, const float* a_mask, const float* a_clean,
+                           float cfg_scale, float audio_cfg_scale, float sigma, float sigma_next, void* stream);
 int ltx2_dit_graph_capture_av(ltx2_dit* ctx, float* v_latent, float* a_latent, const float* host_sigmas, int n_steps,
                               void* stream);
 int ltx2_dit_graph_launch(ltx2_dit* ctx, void* stream);

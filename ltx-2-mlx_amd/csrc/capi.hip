@@ -300,6 +300,26 @@ int ltx2_res2s_combine(const float* x_mid, const float* vel_cond, const float* v
                                 (hipStream_t)stream);
 }
 
+int ltx2_res2s_midpoint_pair(const float* v_x, const float* v_vel_cond, const float* v_vel_uncond, const float* v_ts, int64_t v_ts_stride,
+                             const float* v_mask, const float* v_clean, float v_cfg_scale, float* v_x_mid, float* v_anchor, float* v_eps1, int v_rows,
+                             int v_C, const float* a_x, const float* a_vel_cond, const float* a_vel_uncond, const float* a_ts, int64_t a_ts_stride,
+                             const float* a_mask, const float* a_clean, float a_cfg_scale, float* a_x_mid, float* a_anchor, float* a_eps1, int a_rows,
+                             int a_C, float c, int n_bong, void* stream) {
+    return res2s_midpoint_pair_launch(v_x, v_vel_cond, v_vel_uncond, v_ts, (long)v_ts_stride, v_mask, v_clean, v_cfg_scale, v_x_mid, v_anchor, v_eps1,
+                                      v_rows, v_C, a_x, a_vel_cond, a_vel_uncond, a_ts, (long)a_ts_stride, a_mask, a_clean, a_cfg_scale, a_x_mid,
+                                      a_anchor, a_eps1, a_rows, a_C, c, n_bong, (hipStream_t)stream);
+}
+
+int ltx2_res2s_combine_pair(const float* v_x_mid, const float* v_vel_cond, const float* v_vel_uncond, const float* v_ts, int64_t v_ts_stride,
+                            const float* v_mask, const float* v_clean, float v_cfg_scale, const float* v_anchor, const float* v_eps1, float* v_out,
+                            int v_rows, int v_C, const float* a_x_mid, const float* a_vel_cond, const float* a_vel_uncond, const float* a_ts,
+                            int64_t a_ts_stride, const float* a_mask, const float* a_clean, float a_cfg_scale, const float* a_anchor,
+                            const float* a_eps1, float* a_out, int a_rows, int a_C, float h, float b1, float b2, void* stream) {
+    return res2s_combine_pair_launch(v_x_mid, v_vel_cond, v_vel_uncond, v_ts, (long)v_ts_stride, v_mask, v_clean, v_cfg_scale, v_anchor, v_eps1, v_out,
+                                     v_rows, v_C, a_x_mid, a_vel_cond, a_vel_uncond, a_ts, (long)a_ts_stride, a_mask, a_clean, a_cfg_scale, a_anchor,
+                                     a_eps1, a_out, a_rows, a_C, h, b1, b2, (hipStream_t)stream);
+}
+
 int ltx2_guidance_sums_blocks(int rows, int C) { return guidance_sums_blocks(rows, C); }
 
 int ltx2_guidance_sums(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, int64_t ts_stride, float* running, int first,

@@ -113,8 +113,8 @@ struct ltx2_dit {
     long ws_bytes = 0;
     int per_token = 0;
     float* sigmas_dev = nullptr;       // 64 sigmas of a captured loop, then 64 sub-sigmas (the res_2s loop)
-    float* r2s = nullptr;              // res_2s: x_mid | anchor | eps1, three [N][Cout] fp32 workspaces allocated on first use, freed with the context
-    long r2s_each = 0;                 //   elements of each
+    float* r2s = nullptr;              // res_2s: x_mid | anchor | eps1, three fp32 workspaces allocated on first use, freed with the context
+    long r2s_each = 0;                 //   elements of each: [N][Cout], on an AudioVideo context [N][Cout] and [Na][Cout_a] together
     double* pg_part = nullptr;         // projected guidance: the sums kernel's partials [pg_rows][5], allocated on first use for the bound N, freed with the context
     int pg_rows = 0;
     float* pg_run = nullptr;           //   and, for the legacy APG guider with momentum only, its running guidance [N][Cout] fp32
@@ -1425,9 +1425,8 @@ int res2s_ready(ltx2_dit* c, ltx2_dit* neg, int n_ts, const char* who) {
     return LTX2_OK;
 }
 
-// x_mid | anchor | eps1 for the bound N; never called while a stream is capturing
-int res2s_workspace(ltx2_dit* c) {
-    const long each = align_up((long)c->m[0].N * c->m[0].Cout, 64);
+// three fp32 workspaces of `each` elements (x_mid | anchor | eps1); never called while a stream is capturing
+int res2s_workspace(ltx2_dit* c, long each) {
     if (c->r2s && c->r2s_each == each) return LTX2_OK;
     if (c->r2s) (void)hipFree(c->r2s);
     c->r2s = nullptr;
@@ -1439,6 +1438,8 @@ int res2s_workspace(ltx2_dit* c) {
     c->r2s_each = each;
     return LTX2_OK;
 }
+// VideoOnly contexts: `each` for the bound N
+long res2s_each(const ltx2_dit* c) { return align_up((long)c->m[0].N * c->m[0].Cout, 64); }
 
 // in: (latent, timesteps, sigma) of the step; ts_sub / sub_sigma: the same at the sub-sigma.  cond_sub: in a captured conditioned loop, the
 // mask from which ts_sub = mask * sub_sigma is formed into the buffer `in.ts` points at, after the midpoint kernel has read it (one stream, in order).
@@ -1462,6 +1463,70 @@ int res2s_step(ltx2_dit* c, ltx2_dit* neg, const ModIn& in, const float* ts_sub,
     LTX2_CHECK_ARG(ts_sub && sub_sigma, "dit_res2s_step: the sub-sigma timesteps are missing");
     TRY(evaluate_pair(c, neg, x_mid, ts_sub, in.n_ts, sub_sigma, st));
     return res2s_combine_launch(x_mid, m.vel, vu, ts_sub, stride, io.mask, io.clean, cfg_scale, anchor, eps1, p.h, p.b1, p.b2, io.latent, m.N, m.Cout, st);
+}
+
+// The JOINT res_2s step on AudioVideo contexts (reference pipelines/ti2vid_hq.py:153-319): both latents are stepped, the video under cfg_scale and
+// the audio under audio_cfg_scale.  guided_ready_av's rules, on c alone when there is no negative context.
+int res2s_ready_av(ltx2_dit* c, ltx2_dit* neg, int n_v_ts, int n_a_ts, const char* who) {
+    if (neg) return guided_ready_av(c, neg, n_v_ts, n_a_ts, who);
+    LTX2_CHECK_ARG(c, "%s: null context", who);
+    LTX2_CHECK_ARG(c->av, "%s: the context must be AudioVideo (the VideoOnly engine has ltx2_dit_res2s_step)", who);
+    LTX2_CHECK_ARG(c->prepared, "%s: ltx2_dit_prepare_av has not been called", who);
+    LTX2_CHECK_ARG((n_v_ts == 1 || n_v_ts == c->m[0].N) && (n_a_ts == 1 || n_a_ts == c->m[1].N),
+                   "%s: n_v_timesteps=%d must be 1 or N=%d, n_a_timesteps=%d must be 1 or Na=%d", who, n_v_ts, c->m[0].N, n_a_ts, c->m[1].N);
+    LTX2_CHECK_ARG((n_v_ts == 1 && n_a_ts == 1) || c->per_token, "%s: a workspace was not bound for per-token timesteps", who);
+    return LTX2_OK;
+}
+
+// AudioVideo contexts: x_mid | anchor | eps1 of the video latent, then of the audio latent, in the same workspace (such a context has no other use for
+// it); r2s_each is then the elements of one video plus one audio buffer
+long res2s_each_av(const ltx2_dit* c, int k) { return align_up((long)c->m[k].N * c->m[k].Cout, 64); }
+
+// both modalities of `in` through c into c's velocity buffers and, with a negative context, through neg into neg's
+int evaluate_pair_av(ltx2_dit* c, ltx2_dit* neg, const ModIn in[2], hipStream_t st, bool rewind_events) {
+    ltx2_dit* const both[2] = {c, neg};
+    for (ltx2_dit* e : both) {
+        if (!e) continue;
+        const ModIn ev[2] = {{in[0].latent, in[0].ts, in[0].n_ts, in[0].sigma, e->m[0].vel}, {in[1].latent, in[1].ts, in[1].n_ts, in[1].sigma, e->m[1].vel}};
+        TRY(forward(e, ev, st, rewind_events));
+    }
+    return LTX2_OK;
+}
+
+// in[k]: (latent, timesteps, sigma) of modality k; ts_sub[k] / sub_sigma: the same at the sub-sigma.  Every check stands before the first launch.
+int res2s_step_av(ltx2_dit* c, ltx2_dit* neg, const ModIn in[2], const float* const ts_sub[2], const float* sub_sigma, const StepIo io[2], float cfg_scale,
+                  float audio_cfg_scale, const Res2sPlan& p, hipStream_t st) {
+    const float cfg[2] = {cfg_scale, audio_cfg_scale};
+    const float* vu[2];
+    float *x_mid[2], *anchor[2], *eps1[2];
+    long stride[2];
+    LTX2_CHECK_ARG(c->r2s && c->r2s_each == res2s_each_av(c, 0) + res2s_each_av(c, 1), "dit_res2s_step_av: workspace missing");
+    float* base = c->r2s;
+    for (int k = 0; k < 2; ++k) {
+        LTX2_CHECK_ARG((io[k].mask == nullptr) == (io[k].clean == nullptr), "dit_res2s_step_av: mask and clean go together");
+        LTX2_CHECK_ARG(p.last || (sub_sigma && ts_sub[k]), "dit_res2s_step_av: the sub-sigma timesteps are missing");
+        const long each = res2s_each_av(c, k);
+        x_mid[k] = base;
+        anchor[k] = base + each;
+        eps1[k] = base + 2 * each;
+        base += 3 * each;
+        vu[k] = neg ? neg->m[k].vel : nullptr;
+        stride[k] = in[k].n_ts == 1 ? 0 : 1;
+    }
+    const Mod &v = c->m[0], &a = c->m[1];
+    TRY(evaluate_pair_av(c, neg, in, st, true));
+    if (p.last)
+        return res2s_midpoint_pair_launch(in[0].latent, v.vel, vu[0], in[0].ts, stride[0], io[0].mask, io[0].clean, cfg[0], io[0].latent, nullptr, nullptr, v.N,
+                                          v.Cout, in[1].latent, a.vel, vu[1], in[1].ts, stride[1], io[1].mask, io[1].clean, cfg[1], io[1].latent, nullptr,
+                                          nullptr, a.N, a.Cout, 0.f, 0, st);
+    TRY(res2s_midpoint_pair_launch(in[0].latent, v.vel, vu[0], in[0].ts, stride[0], io[0].mask, io[0].clean, cfg[0], x_mid[0], anchor[0], eps1[0], v.N, v.Cout,
+                                   in[1].latent, a.vel, vu[1], in[1].ts, stride[1], io[1].mask, io[1].clean, cfg[1], x_mid[1], anchor[1], eps1[1], a.N, a.Cout,
+                                   p.c, p.n_bong, st));
+    const ModIn mid[2] = {{x_mid[0], ts_sub[0], in[0].n_ts, sub_sigma, nullptr}, {x_mid[1], ts_sub[1], in[1].n_ts, sub_sigma, nullptr}};
+    TRY(evaluate_pair_av(c, neg, mid, st, true));
+    return res2s_combine_pair_launch(x_mid[0], v.vel, vu[0], ts_sub[0], stride[0], io[0].mask, io[0].clean, cfg[0], anchor[0], eps1[0], io[0].latent, v.N, v.Cout,
+                                     x_mid[1], a.vel, vu[1], ts_sub[1], stride[1], io[1].mask, io[1].clean, cfg[1], anchor[1], eps1[1], io[1].latent, a.N, a.Cout,
+                                     p.h, p.b1, p.b2, st);
 }
 
 // The one captured sampling loop behind every ltx2_dit_graph_capture* entry: per step, sigma_i read on the device, each modality's timesteps (sigma_i, or
@@ -1523,7 +1588,7 @@ int ltx2_dit_res2s_step(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* 
     Res2sPlan p;
     TRY(res2s_plan(sigma, sigma_next, p));
     LTX2_CHECK_ARG(p.last || ts_sub, "dit_res2s_step: ts_sub is needed unless the step is the final one");
-    TRY(res2s_workspace(c));
+    TRY(res2s_workspace(c, res2s_each(c)));
     const ModIn in = {latent, timesteps, n_timesteps, sigma_dev ? sigma_dev : timesteps, nullptr};
     const StepIo io = {latent, mask, clean, nullptr};
     return res2s_step(c, neg, in, ts_sub, sub_sigma_dev ? sub_sigma_dev : ts_sub, nullptr, io, cfg_scale, p, (hipStream_t)stream);
@@ -1536,10 +1601,27 @@ int ltx2_dit_graph_capture_res2s(ltx2_dit* c, ltx2_dit* neg, float* latent, cons
     LTX2_CHECK_ARG((mask == nullptr) == (clean == nullptr), "dit_graph_capture_res2s: mask and clean go together");
     Res2sPlan plan[64];
     for (int i = 0; i < n_steps; ++i) TRY(res2s_plan(host_sigmas[i], host_sigmas[i + 1], plan[i]));
-    TRY(res2s_workspace(c));
+    TRY(res2s_workspace(c, res2s_each(c)));
     float* const lat[2] = {latent, nullptr};
     const Cond cond[2] = {{mask, (long)n_mask, clean, (long)n_clean}, {}};
     return capture_loop(c, {neg, cfg_scale, nullptr, plan}, lat, cond, host_sigmas, n_steps, (hipStream_t)stream);
+}
+
+int ltx2_dit_res2s_step_av(ltx2_dit* c, ltx2_dit* neg, float* v_latent, float* a_latent, const float* v_timesteps, int n_v_timesteps,
+                           const float* a_timesteps, int n_a_timesteps, const float* sigma_dev, const float* v_ts_sub, const float* a_ts_sub,
+                           const float* sub_sigma_dev, const float* v_mask, const float* v_clean, const float* a_mask, const float* a_clean,
+                           float cfg_scale, float audio_cfg_scale, float sigma, float sigma_next, void* stream) {
+    LTX2_CHECK_ARG(v_latent && a_latent && v_timesteps && a_timesteps && sigma_dev, "dit_res2s_step_av: null argument");
+    TRY(res2s_ready_av(c, neg, n_v_timesteps, n_a_timesteps, "dit_res2s_step_av"));
+    LTX2_CHECK_ARG((v_mask == nullptr) == (v_clean == nullptr) && (a_mask == nullptr) == (a_clean == nullptr), "dit_res2s_step_av: mask and clean go together");
+    Res2sPlan p;
+    TRY(res2s_plan(sigma, sigma_next, p));
+    LTX2_CHECK_ARG(p.last || (v_ts_sub && a_ts_sub), "dit_res2s_step_av: v_ts_sub and a_ts_sub are needed unless the step is the final one");
+    TRY(res2s_workspace(c, res2s_each_av(c, 0) + res2s_each_av(c, 1)));
+    const ModIn in[2] = {{v_latent, v_timesteps, n_v_timesteps, sigma_dev, nullptr}, {a_latent, a_timesteps, n_a_timesteps, sigma_dev, nullptr}};
+    const StepIo io[2] = {{v_latent, v_mask, v_clean, nullptr}, {a_latent, a_mask, a_clean, nullptr}};
+    const float* const sub[2] = {v_ts_sub, a_ts_sub};
+    return res2s_step_av(c, neg, in, sub, sub_sigma_dev ? sub_sigma_dev : v_ts_sub, io, cfg_scale, audio_cfg_scale, p, (hipStream_t)stream);
 }
 
 int ltx2_dit_graph_capture(ltx2_dit* c, float* latent, const float* host_sigmas, int n_steps, void* stream) {

@@ -31,6 +31,20 @@ int res2s_combine_launch(const float* x_mid, const float* vel_cond, const float*
                          const float* clean, float cfg_scale, const float* anchor, const float* eps1, float h, float b1, float b2, float* out,
                          int rows, int C, hipStream_t stream);
 
+// Both passes over TWO latents in one launch (the video and the audio latent of a joint step): the single forms' operands given twice, v_ then
+// a_, each with its own cfg_scale, timesteps, mask / clean and shape; c / n_bong and h / b1 / b2 are shared.  Each segment's output is the single
+// launch's bit for bit.  16-byte accesses only when both segments allow them; the final-step form applies to both segments together.
+int res2s_midpoint_pair_launch(const float* v_x, const float* v_vel_cond, const float* v_vel_uncond, const float* v_ts, long v_ts_stride, const float* v_mask,
+                               const float* v_clean, float v_cfg_scale, float* v_x_mid, float* v_anchor, float* v_eps1, int v_rows, int v_C,
+                               const float* a_x, const float* a_vel_cond, const float* a_vel_uncond, const float* a_ts, long a_ts_stride, const float* a_mask,
+                               const float* a_clean, float a_cfg_scale, float* a_x_mid, float* a_anchor, float* a_eps1, int a_rows, int a_C,
+                               float c, int n_bong, hipStream_t stream);
+int res2s_combine_pair_launch(const float* v_x_mid, const float* v_vel_cond, const float* v_vel_uncond, const float* v_ts, long v_ts_stride, const float* v_mask,
+                              const float* v_clean, float v_cfg_scale, const float* v_anchor, const float* v_eps1, float* v_out, int v_rows, int v_C,
+                              const float* a_x_mid, const float* a_vel_cond, const float* a_vel_uncond, const float* a_ts, long a_ts_stride, const float* a_mask,
+                              const float* a_clean, float a_cfg_scale, const float* a_anchor, const float* a_eps1, float* a_out, int a_rows, int a_C,
+                              float h, float b1, float b2, hipStream_t stream);
+
 // Guiders whose scalars are sums over the whole latent.  sums: five fp64 sums per block into partials[guidance_sums_blocks(rows, C)][5], and with
 // `running` the momentum update of the guidance; step: every block adds the partial rows in index order, derives the fp32 scalars and runs the
 // guided, mask-blended Euler step.

@@ -1,6 +1,6 @@
 // The device code of the sampling step over fp32 [rows][C] latents: the plain x0 / Euler pair, and the steps that replace a sequence of separate
 // fp32 torch ops bit for bit -- the classifier-free-guided Euler step (pipelines/one_stage.py:224-330), the two passes of the res_2s second-order
-// step (reference pipelines/ti2vid_hq.py:153-273) and the two passes of the guiders whose scalars are reductions over the whole latent
+// step (reference pipelines/ti2vid_hq.py:153-273; over one latent, or over the video and the audio latent of the joint step in one launch) and the two passes of the guiders whose scalars are reductions over the whole latent
 // (CFGStarRescalingGuider, LtxAPGGuider, LegacyStatefulAPGGuider; reference components/guiders.py:51-76, 105-205).  All arithmetic is fp32 and
 // fp64, so the file compiles to the same code in both library builds.  The definitions are written out in include/ltx2hip.h.
 #include <hip/hip_runtime.h>
@@ -70,13 +70,14 @@ __device__ __forceinline__ void store(float* p, long e, const float (&v)[V]) {
     else p[e] = v[0];
 }
 
+// the loop of one block over the vectors of r, as block `block` of `blocks`
 template <int V, class Op>
-__global__ __launch_bounds__(BLOCK) void step_rows_kernel(const Op op, const Rows r) {
+__device__ __forceinline__ void step_rows(const Op& op, const Rows& r, long block, long blocks) {
     typename Op::State st;
     op.begin(st);
     const bool blend = r.mask != nullptr;
     const long nv = r.n / V;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
+    for (long i = block * blockDim.x + threadIdx.x; i < nv; i += blocks * blockDim.x) {
         const long e = i * V, row = e / r.C;
         const float m = blend ? r.mask[row] : 1.f;
         const Row rw = {r.ts[row * r.ts_stride], m, sub_rn(1.0f, m), blend};
@@ -96,6 +97,20 @@ __global__ __launch_bounds__(BLOCK) void step_rows_kernel(const Op op, const Row
         for (int k = 0; k < Op::NOUT; ++k) store<V>(op.out[k], e, out[k]);
     }
     op.end(st);
+}
+
+template <int V, class Op>
+__global__ __launch_bounds__(BLOCK) void step_rows_kernel(const Op op, const Rows r) {
+    step_rows<V>(op, r, blockIdx.x, gridDim.x);
+}
+
+// Two segments in one launch (the video and the audio latent of a joint step; the audio one is ~100 rows, a launch of its own nearly all latency):
+// blocks [0, blocks_a) are the grid of segment a, the rest the grid of segment b.  Each segment's elements see exactly what a launch of its own
+// gives them, so its output is the single launch's bit for bit.  For Ops without begin() / end() work across the block.
+template <int V, class Op>
+__global__ __launch_bounds__(BLOCK) void step_rows2_kernel(const Op a, const Rows ra, const Op b, const Rows rb, const int blocks_a) {
+    if ((int)blockIdx.x < blocks_a) step_rows<V>(a, ra, blockIdx.x, blocks_a);
+    else step_rows<V>(b, rb, (int)blockIdx.x - blocks_a, (int)gridDim.x - blocks_a);
 }
 
 struct StepOp {         // the defaults: no per-thread state, no prologue, no epilogue
@@ -301,20 +316,56 @@ struct ProjectedEuler : StepOp {
 // The checks every step shares, under the caller's name, and the launch.  present: the caller's required operands are all there.  16-byte accesses
 // need every [rows][C] operand on a 16-byte boundary as well as C % 4 == 0 (a NULL operand contributes no bits).  sums_grid: the grid of the sums
 // pass, which does not depend on the access width; 0: a step, one thread per vector under grid_for's cap.
-template <class Op>
-int launch_rows(const char* who, bool present, const Op& op, const float* ts, long ts_stride, const float* mask, const float* clean, int rows, int C,
-                int sums_grid, hipStream_t stream) {
+inline int check_rows(const char* who, bool present, const float* ts, long ts_stride, const float* mask, const float* clean, int rows, int C) {
     LTX2_CHECK_ARG(present && ts && rows > 0 && C > 0, "%s: null operand or empty shape", who);
     LTX2_CHECK_ARG(ts_stride == 0 || ts_stride == 1, "%s: ts_stride is 0 (one timestep) or 1 (one per row)", who);
     LTX2_CHECK_ARG((mask == nullptr) == (clean == nullptr), "%s: mask and clean go together", who);
-    const Rows r = {ts, ts_stride, mask, (long)rows * C, C};
+    return LTX2_OK;
+}
+
+template <class Op>
+bool vec4_ok(const Op& op, int C) {
     uintptr_t al = 0;
     for (const float* p : op.in) al |= (uintptr_t)p;
     for (const float* p : op.out) al |= (uintptr_t)p;
-    if (C % 4 == 0 && (al & 15) == 0)
+    return C % 4 == 0 && (al & 15) == 0;
+}
+
+template <class Op>
+int launch_rows(const char* who, bool present, const Op& op, const float* ts, long ts_stride, const float* mask, const float* clean, int rows, int C,
+                int sums_grid, hipStream_t stream) {
+    if (const int rc = check_rows(who, present, ts, ts_stride, mask, clean, rows, C); rc != LTX2_OK) return rc;
+    const Rows r = {ts, ts_stride, mask, (long)rows * C, C};
+    if (vec4_ok(op, C))
         hipLaunchKernelGGL((step_rows_kernel<4, Op>), dim3(sums_grid ? sums_grid : grid_for(r.n / 4, BLOCK)), dim3(BLOCK), 0, stream, op, r);
     else
         hipLaunchKernelGGL((step_rows_kernel<1, Op>), dim3(sums_grid ? sums_grid : grid_for(r.n, BLOCK)), dim3(BLOCK), 0, stream, op, r);
+    LTX2_CHECK_LAUNCH(who);
+    return LTX2_OK;
+}
+
+// One modality of a two-segment step: what launch_rows takes per call
+struct Seg {
+    const float* ts;
+    long ts_stride;
+    const float* mask;
+    const float* clean;
+    int rows, C;
+};
+
+// Both segments are checked as launch_rows checks one, before the one launch; 16-byte accesses only where BOTH segments allow them
+template <class Op>
+int launch_rows2(const char* who, bool present, const Op& a, const Seg& sa, const Op& b, const Seg& sb, hipStream_t stream) {
+    if (const int rc = check_rows(who, present, sa.ts, sa.ts_stride, sa.mask, sa.clean, sa.rows, sa.C); rc != LTX2_OK) return rc;
+    if (const int rc = check_rows(who, present, sb.ts, sb.ts_stride, sb.mask, sb.clean, sb.rows, sb.C); rc != LTX2_OK) return rc;
+    const Rows ra = {sa.ts, sa.ts_stride, sa.mask, (long)sa.rows * sa.C, sa.C}, rb = {sb.ts, sb.ts_stride, sb.mask, (long)sb.rows * sb.C, sb.C};
+    if (vec4_ok(a, sa.C) && vec4_ok(b, sb.C)) {
+        const int ga = grid_for(ra.n / 4, BLOCK), gb = grid_for(rb.n / 4, BLOCK);
+        hipLaunchKernelGGL((step_rows2_kernel<4, Op>), dim3(ga + gb), dim3(BLOCK), 0, stream, a, ra, b, rb, ga);
+    } else {
+        const int ga = grid_for(ra.n, BLOCK), gb = grid_for(rb.n, BLOCK);
+        hipLaunchKernelGGL((step_rows2_kernel<1, Op>), dim3(ga + gb), dim3(BLOCK), 0, stream, a, ra, b, rb, ga);
+    }
     LTX2_CHECK_LAUNCH(who);
     return LTX2_OK;
 }
@@ -361,6 +412,32 @@ int res2s_combine_launch(const float* x_mid, const float* vel_cond, const float*
                          int rows, int C, hipStream_t stream) {
     const Res2sCombine op = {{}, {x_mid, vel_cond, vel_uncond, clean, anchor, eps1}, {out}, cfg_scale, h, b1, b2};
     return launch_rows("res2s_combine", x_mid && vel_cond && anchor && eps1 && out, op, ts, ts_stride, mask, clean, rows, C, 0, stream);
+}
+
+int res2s_midpoint_pair_launch(const float* v_x, const float* v_vel_cond, const float* v_vel_uncond, const float* v_ts, long v_ts_stride, const float* v_mask,
+                               const float* v_clean, float v_cfg_scale, float* v_x_mid, float* v_anchor, float* v_eps1, int v_rows, int v_C,
+                               const float* a_x, const float* a_vel_cond, const float* a_vel_uncond, const float* a_ts, long a_ts_stride, const float* a_mask,
+                               const float* a_clean, float a_cfg_scale, float* a_x_mid, float* a_anchor, float* a_eps1, int a_rows, int a_C,
+                               float c, int n_bong, hipStream_t stream) {
+    LTX2_CHECK_ARG((v_anchor == nullptr) == (v_eps1 == nullptr) && (a_anchor == nullptr) == (a_eps1 == nullptr),
+                   "res2s_midpoint_pair: anchor and eps1 go together (both NULL: the final-step form)");
+    LTX2_CHECK_ARG((v_anchor == nullptr) == (a_anchor == nullptr), "res2s_midpoint_pair: the final-step form (anchor == eps1 == NULL) applies to both segments together");
+    LTX2_CHECK_ARG(n_bong >= 0, "res2s_midpoint_pair: n_bong=%d", n_bong);
+    const Res2sMidpoint v = {{}, {v_x, v_vel_cond, v_vel_uncond, v_clean}, {v_x_mid, v_anchor, v_eps1}, v_cfg_scale, c, n_bong};
+    const Res2sMidpoint a = {{}, {a_x, a_vel_cond, a_vel_uncond, a_clean}, {a_x_mid, a_anchor, a_eps1}, a_cfg_scale, c, n_bong};
+    return launch_rows2("res2s_midpoint_pair", v_x && v_vel_cond && v_x_mid && a_x && a_vel_cond && a_x_mid, v, {v_ts, v_ts_stride, v_mask, v_clean, v_rows, v_C},
+                        a, {a_ts, a_ts_stride, a_mask, a_clean, a_rows, a_C}, stream);
+}
+
+int res2s_combine_pair_launch(const float* v_x_mid, const float* v_vel_cond, const float* v_vel_uncond, const float* v_ts, long v_ts_stride, const float* v_mask,
+                              const float* v_clean, float v_cfg_scale, const float* v_anchor, const float* v_eps1, float* v_out, int v_rows, int v_C,
+                              const float* a_x_mid, const float* a_vel_cond, const float* a_vel_uncond, const float* a_ts, long a_ts_stride, const float* a_mask,
+                              const float* a_clean, float a_cfg_scale, const float* a_anchor, const float* a_eps1, float* a_out, int a_rows, int a_C,
+                              float h, float b1, float b2, hipStream_t stream) {
+    const Res2sCombine v = {{}, {v_x_mid, v_vel_cond, v_vel_uncond, v_clean, v_anchor, v_eps1}, {v_out}, v_cfg_scale, h, b1, b2};
+    const Res2sCombine a = {{}, {a_x_mid, a_vel_cond, a_vel_uncond, a_clean, a_anchor, a_eps1}, {a_out}, a_cfg_scale, h, b1, b2};
+    return launch_rows2("res2s_combine_pair", v_x_mid && v_vel_cond && v_anchor && v_eps1 && v_out && a_x_mid && a_vel_cond && a_anchor && a_eps1 && a_out, v,
+                        {v_ts, v_ts_stride, v_mask, v_clean, v_rows, v_C}, a, {a_ts, a_ts_stride, a_mask, a_clean, a_rows, a_C}, stream);
 }
 
 int guidance_sums_blocks(int rows, int C) { return (rows > 0 && C > 0) ? sums_blocks((long)rows * C) : 0; }

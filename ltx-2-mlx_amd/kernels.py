@@ -615,6 +615,46 @@ def res2s_combine(x_mid: torch.Tensor, vel_cond: torch.Tensor, vel_uncond: Optio
     return out
 
 
+def res2s_midpoint_pair(video: dict, audio: dict, c: float, n_bong: int, final: bool = False, dtype: Optional[torch.dtype] = None):
+    """res2s_midpoint over two latents in ONE launch (ltx2_res2s_midpoint_pair): `video` and `audio` each hold the single form's operands by
+    name -- x, vel_cond, timesteps, cfg_scale and optionally vel_uncond, mask, clean, x_mid, anchor, eps1 -- with shapes, scales, timesteps and
+    conditioning of their own; c, n_bong and `final` are shared.  -> ((x_mid, anchor, eps1) of the video, the same of the audio), each equal
+    to res2s_midpoint's bit for bit."""
+    args, outs = [], []
+    for seg in (video, audio):
+        x, vc, vu, mask, clean = seg["x"], seg["vel_cond"], seg.get("vel_uncond"), seg.get("mask"), seg.get("clean")
+        x_mid = seg["x_mid"] if seg.get("x_mid") is not None else torch.empty_like(x)
+        anchor = eps1 = None
+        if not final:
+            anchor = seg["anchor"] if seg.get("anchor") is not None else torch.empty_like(x)
+            eps1 = seg["eps1"] if seg.get("eps1") is not None else torch.empty_like(x)
+        assert vc is not None and (mask is None or clean is not None)
+        n, ch, ts = _step_operands(x, seg["timesteps"], (vc, vu, clean, x_mid, anchor, eps1), mask)
+        args += [nv.ptr(x), nv.ptr(vc), nv.ptr(vu), nv.ptr(ts), 0 if ts.numel() == 1 else 1, nv.ptr(mask), nv.ptr(clean), float(seg["cfg_scale"]),
+                 nv.ptr(x_mid), nv.ptr(anchor), nv.ptr(eps1), n, ch]
+        outs.append((x_mid, anchor, eps1, ts))
+    nv.check(nv.lib(dtype).ltx2_res2s_midpoint_pair(*args, float(c), int(n_bong), nv.stream()))
+    return outs[0][:3], outs[1][:3]
+
+
+def res2s_combine_pair(video: dict, audio: dict, h: float, b1: float, b2: float, dtype: Optional[torch.dtype] = None):
+    """res2s_combine over two latents in ONE launch (ltx2_res2s_combine_pair): `video` and `audio` each hold x_mid, vel_cond, timesteps,
+    cfg_scale, anchor, eps1 and optionally vel_uncond, mask, clean, out; h, b1, b2 are shared.  -> (video out, audio out), each equal to
+    res2s_combine's bit for bit; `out` may be any [N, C] operand of its segment."""
+    args, outs, keep = [], [], []
+    for seg in (video, audio):
+        xm, vc, vu, mask, clean, an, e1 = seg["x_mid"], seg["vel_cond"], seg.get("vel_uncond"), seg.get("mask"), seg.get("clean"), seg["anchor"], seg["eps1"]
+        out = seg["out"] if seg.get("out") is not None else torch.empty_like(xm)
+        assert vc is not None and an is not None and e1 is not None and (mask is None or clean is not None)
+        n, ch, ts = _step_operands(xm, seg["timesteps"], (vc, vu, clean, an, e1, out), mask)
+        args += [nv.ptr(xm), nv.ptr(vc), nv.ptr(vu), nv.ptr(ts), 0 if ts.numel() == 1 else 1, nv.ptr(mask), nv.ptr(clean), float(seg["cfg_scale"]),
+                 nv.ptr(an), nv.ptr(e1), nv.ptr(out), n, ch]
+        outs.append(out)
+        keep.append(ts)
+    nv.check(nv.lib(dtype).ltx2_res2s_combine_pair(*args, float(h), float(b1), float(b2), nv.stream()))
+    return outs[0], outs[1]
+
+
 def pixnorm_mod_silu(x: torch.Tensor, table: torch.Tensor, te: Optional[torch.Tensor], shift_row: int, scale_row: int,
                      eps: float = 1e-6) -> torch.Tensor:
     assert x.dtype in ACT16

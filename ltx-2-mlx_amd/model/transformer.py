@@ -822,6 +822,35 @@ class LTXModel:
         """Replay the graph captured by capture_res2s_graph (it belongs to the VideoOnly context that ran the capture)."""
         self._replay("res2s", "no res_2s graph captured")
 
+    # ------------------------------------------------------------------ joint audio+video res_2s sampling (AudioVideo engine)
+    def res2s_step_av_(self, neg: Optional["LTXModel"], latent: torch.Tensor, audio_latent: torch.Tensor, video: Modality, audio: Modality,
+                       video_sub: Optional[Modality], audio_sub: Optional[Modality], sigma: float, sigma_next: float, cfg_scale: float,
+                       audio_cfg_scale: float, denoise_mask: Optional[torch.Tensor] = None, clean_latent: Optional[torch.Tensor] = None,
+                       audio_denoise_mask: Optional[torch.Tensor] = None, audio_clean_latent: Optional[torch.Tensor] = None) -> None:
+        """In-place on BOTH latents, (N, C) and (Na, Ca) fp32: one joint res_2s step (reference pipelines/ti2vid_hq.py:153-319) by ONE C call
+        (ltx2_dit_res2s_step_av): both modalities through this context and through `neg` at `video` / `audio`'s timesteps, the midpoint
+        kernel over both latents in one launch, both contexts again from the midpoint latents at `video_sub` / `audio_sub`'s timesteps
+        (those of the sub-sigma sqrt(sigma * sigma_next)), the combine kernel likewise.  The video is guided by cfg_scale, the audio by
+        audio_cfg_scale; neg None: no guidance.  The sub modalities may be None only for the final step (sigma_next <= 0.001).  Both
+        contexts are prepared by the caller (neg with the negative contexts)."""
+        if neg is not None and not isinstance(neg, LTXModel):
+            raise ValueError("guidance needs a second LTXModel context (clone_sharing_weights()) for the negative prompt")
+        if not (self.is_av and (neg is None or neg.is_av)):
+            raise ValueError("res2s_step_av_ runs on AudioVideo contexts (a VideoOnly model has res2s_step_)")
+        assert (video_sub is None) == (audio_sub is None), "video_sub and audio_sub go together (both None: the final step)"
+        pos, ng = self, neg
+        ts, n_ts, sg, ats, n_ats = pos._step_inputs(latent, video, sigma, audio_latent, audio)
+        ts_sub = ats_sub = sg_sub = None
+        if video_sub is not None:
+            ts_sub, n_sub = pos._timesteps(video_sub)
+            ats_sub, n_asub = pos._timesteps(audio_sub)
+            assert n_sub == n_ts and n_asub == n_ats, "both evaluations take one timestep, or one per token"
+            sg_sub = pos._sigma(video_sub)
+        nv.check(pos._L.ltx2_dit_res2s_step_av(pos._h, None if ng is None else ng._h, nv.ptr(latent), nv.ptr(audio_latent), nv.ptr(ts), n_ts,
+                                               nv.ptr(ats), n_ats, nv.ptr(sg), nv.ptr(ts_sub), nv.ptr(ats_sub), nv.ptr(sg_sub), nv.ptr(denoise_mask),
+                                               nv.ptr(clean_latent), nv.ptr(audio_denoise_mask), nv.ptr(audio_clean_latent), float(cfg_scale),
+                                               float(audio_cfg_scale), float(sigma), float(sigma_next), nv.stream()))
+
     def replace_weights(self, tensors: Dict[str, torch.Tensor]) -> None:
         """Re-register engine-layout tensors (names of weight_tensors()) in place of the ones held now -- the HQ pipeline's LoRA fusion for
         its second stage and the restore after it.  Contexts built over the old tensors (video twin, clone) are rebuilt on demand."""

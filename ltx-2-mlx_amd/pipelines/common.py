@@ -434,7 +434,7 @@ def res2s_denoise_loop(transformer, video_state: LatentState, sigmas, context: t
     reference's condition, (cfg_scale > 1 or audio_cfg_scale > 1) and negative_context is not None.  The sigmas are rounded to fp32 (the
     engine's scalar type, 0.0011 included) and the latent is held in fp32 across the loop, as guided_denoise_loop holds it; the
     reference's per-step cast to the state dtype is not reproduced.  `transformer` is an X0Model; an AudioVideo model is used through its
-    video twin (the joint audio branch is not built).  Returns the video state."""
+    video twin (res2s_av_denoise_loop steps both modalities).  Returns the video state."""
     sig = [float(s) for s in sigmas]
     n = len(sig) - 1
     if sig[-1] == 0.0:
@@ -461,3 +461,61 @@ def res2s_denoise_loop(transformer, video_state: LatentState, sigmas, context: t
             if callback:
                 callback(i + 1, n)
     return _with_latent(video_state, lat)
+
+
+def res2s_av_denoise_loop(transformer, video_state: LatentState, audio_state: LatentState, sigmas, video_context: torch.Tensor,
+                          audio_context: torch.Tensor, negative_video_context: Optional[torch.Tensor],
+                          negative_audio_context: Optional[torch.Tensor], cfg_scale: float, audio_cfg_scale: float, callback=None,
+                          use_hip_graph: bool = True) -> Tuple[LatentState, LatentState]:
+    """The HQ pipeline's res_2s loop over BOTH modalities of an AudioVideo model (reference pipelines/ti2vid_hq.py:153-319): every step is ONE C
+    call -- two pairs of AudioVideo evaluations, the midpoint and the combine kernel over both latents in one launch each
+    (LTXModel.res2s_step_av_).  There is no captured form of this loop: use_hip_graph is accepted for the signature the other loops share,
+    changes nothing and is answered with the usual one-time note.  The video is guided by
+    cfg_scale and the audio by audio_cfg_scale, both as uncond + s * (cond - uncond), under the reference's condition
+    (cfg_scale > 1 or audio_cfg_scale > 1) and negative_video_context is not None.  A missing negative audio context falls back to the
+    negative video context (reference :303) where the two modalities' contexts have the same width; otherwise that is a ValueError.  Sigma
+    handling, step count, final-step break and the fp32-held latents are res2s_denoise_loop's.  Each modality takes the uniform or the
+    per-token form by its own mask.  `transformer` is an X0Model over an AudioVideo model.  Returns (video_state, audio_state)."""
+    model = transformer.velocity_model
+    if not model.is_av or audio_state is None:
+        raise ValueError("res2s_av_denoise_loop requires an audio-video (AV) model and an audio state")
+    if audio_context is None:
+        raise ValueError("AudioVideo model: audio_encoding (the audio text context) is required")
+    sig = [float(s) for s in sigmas]
+    n = len(sig) - 1
+    if sig[-1] == 0.0:
+        sig = sig[:-1] + [0.0011, 0.0]
+    sig = torch.tensor(sig[: n + 1], dtype=torch.float32).tolist()             # the n steps read sigma_0 .. sigma_n only
+    guide = (cfg_scale > 1.0 or audio_cfg_scale > 1.0) and negative_video_context is not None
+    if guide and negative_audio_context is None:
+        if negative_video_context.shape[-1] != audio_context.shape[-1]:
+            raise ValueError(f"negative_audio_context is missing and the negative video context (width {negative_video_context.shape[-1]}) cannot "
+                             f"stand in for it: the audio context has width {audio_context.shape[-1]}")
+        negative_audio_context = negative_video_context
+    model, uniform, lat, mask, clean = _video_loop_inputs(model, video_state, video_only=False)
+    _, a_uniform, alat, amask, aclean = _video_loop_inputs(model, audio_state, video_only=False)
+    per_token = not (uniform and a_uniform)
+    neg = model.clone_sharing_weights() if guide else None
+    model.prepare(video_context, video_state.positions, per_token=per_token, audio_context=audio_context, audio_positions=audio_state.positions)
+    if guide:
+        neg.prepare(negative_video_context, video_state.positions, per_token=per_token, audio_context=negative_audio_context,
+                    audio_positions=audio_state.positions)
+    cond = dict(denoise_mask=mask, clean_latent=clean, audio_denoise_mask=amask, audio_clean_latent=aclean)
+    if use_hip_graph:
+        _note_eager_once("the joint audio+video res_2s loop has no captured form")
+    for i in range(n):
+        final = sig[i + 1] <= 0.001 or sig[i + 1] == sig[i]
+        st, ast = video_state.replace(latent=lat[None]), audio_state.replace(latent=alat[None])
+        sub = asub = None
+        if not final:
+            s_sub = math.sqrt(sig[i] * sig[i + 1])
+            sub = modality_from_state(st, video_context, s_sub, uniform=uniform)
+            asub = audio_modality_from_state(ast, audio_context, s_sub, uniform=a_uniform)
+        model.res2s_step_av_(neg, lat, alat, modality_from_state(st, video_context, sig[i], uniform=uniform),
+                             audio_modality_from_state(ast, audio_context, sig[i], uniform=a_uniform), sub, asub, sig[i], sig[i + 1], cfg_scale,
+                             audio_cfg_scale, **cond)
+        if final:
+            break
+        if callback:
+            callback(i + 1, n)
+    return _with_latent(video_state, lat), _with_latent(audio_state, alat)

@@ -9,7 +9,7 @@ encode_with_gemma :340-486, encode_av_gemma_batch :511-640; an LTX-2.3 checkpoin
 :548-551).  Out of this path (and rejected with a clear message): STG guidance,
 CFG in the video-only loop, the dev model's `--pipeline two-stage`.
 `generate_video` resolves its arguments once (`_resolve_request`: every refusal, before a model is loaded), loads the text encoding, the transformer and the VAE decoder, and
-runs ONE route, each a function of its own: a2vid (`--a2vid-two-stage --audio FILE --spatial-upscaler-weights W`: the two-stage audio-to-video pipeline), retake (`--retake CLIP`), keyframe (`--pipeline keyframe-interpolation --keyframe path:frame[:strength]`), hq (`--ti2vid-hq`), ic_lora
+runs ONE route, each a function of its own: hq_av (`--ti2vid-hq-audio --spatial-upscaler-weights W`: TI2VidHQPipeline with sound, the joint res_2s loop on the AudioVideo model), a2vid (`--a2vid-two-stage --audio FILE --spatial-upscaler-weights W`: the two-stage audio-to-video pipeline), retake (`--retake CLIP`), keyframe (`--pipeline keyframe-interpolation --keyframe path:frame[:strength]`), hq (`--ti2vid-hq`), ic_lora
 (`--pipeline ic-lora --control-video V` and / or `--image`), two_stage (`--two-stage-distilled --spatial-upscaler-weights W`; with `--generate-audio` on the AudioVideo transformer), av
 (`--generate-audio` or an LTX-2.3 checkpoint: the audio LATENT is saved beside the frames; `--decode-audio`, the default when the checkpoint holds the audio VAE decoder and vocoder, also
 decodes it to `<output>.wav` and muxes it into the mp4, reference save_video_with_audio; `--audio FILE` generates the video TO that audio: the audio VAE encoder's latent stays frozen in
@@ -617,11 +617,15 @@ _ROUTE_EXCLUDES = {
     "a2vid": (("two_stage_distilled", "upscale_temporal", "retake_video"),          # keyframes / control_video: not owned, refused with the out-of-path defaults
               "with a2vid_two_stage: A2VidPipelineTwoStage generates the video to audio_path on the AudioVideo model, conditions on image_path "
               "alone and ends with its own x2 spatial stage"),
+    "hq_av": (("audio_path", "two_stage_distilled", "upscale_temporal", "keyframes", "retake_video", "a2vid_two_stage"),
+              "with ti2vid_hq_audio: TI2VidHQPipeline samples its own audio latent beside the video on the AudioVideo model, conditions on image_path "
+              "alone and ends with its own x2 spatial stage"),
 }
 # route -> the _OUT_OF_PATH_DEFAULTS arguments that route takes itself.  apg_scale: the routes whose guided loop takes a guider (the AudioVideo route as
 # OneStagePipeline's guider_override, keyframe stage 1, retake's guided mode)
 _ROUTE_OWNS = {"keyframe": ("keyframes", "apg_scale"), "hq": ("distilled_lora", "keyframes"),
-               "ic_lora": ("control_video", "save_control", "keyframes", "ic_lora_weights"), "retake": ("apg_scale",), "av": ("apg_scale",), "a2vid": ("distilled_lora",)}
+               "ic_lora": ("control_video", "save_control", "keyframes", "ic_lora_weights"), "retake": ("apg_scale",), "av": ("apg_scale",), "a2vid": ("distilled_lora",),
+               "hq_av": ("distilled_lora",)}
 
 
 def _owning_route(r):
@@ -737,7 +741,15 @@ def _resolve_a2vid(r):
     r.generate_audio = True          # the AudioVideo transformer and both text encodings, as generate_audio asks for them
 
 
-_RESOLVE_ROUTE = {"keyframe": _resolve_keyframe, "hq": _resolve_hq, "ic_lora": _resolve_ic_lora, "a2vid": _resolve_a2vid}
+def _resolve_hq_av(r):
+    _need_spatial_upscaler(r)
+    from ltx_2_mlx_amd.pipelines import TI2VidHQConfig
+    TI2VidHQConfig(height=r.height, width=r.width, num_frames=r.num_frames)          # its ValueErrors (8k + 1 frames, multiples of 64)
+    r.hq_lora = _lora_config(r, r.distilled_lora, r.distilled_lora_scale, "distilled LoRA")
+    r.generate_audio = True          # the AudioVideo transformer and both text encodings, as generate_audio asks for them
+
+
+_RESOLVE_ROUTE = {"keyframe": _resolve_keyframe, "hq": _resolve_hq, "ic_lora": _resolve_ic_lora, "a2vid": _resolve_a2vid, "hq_av": _resolve_hq_av}
 
 
 def _resolve_request(kw: dict):
@@ -747,7 +759,9 @@ def _resolve_request(kw: dict):
     negative_audio_encoding of the embedding file.  Loads no model and touches no GPU; every refusal is raised here, in a fixed order.  Returns None (after saying so) when Gemma is asked for and
     its weights are missing."""
     r = SimpleNamespace(**kw, retake_fps=None, retake_to_end=False, retake_window=None, parsed_keyframes=[], hq_lora=None, ic_loras=[], a2vid_lora=None)
-    if r.a2vid_two_stage:
+    if r.ti2vid_hq_audio:
+        r.route = "hq_av"
+    elif r.a2vid_two_stage:
         r.route = "a2vid"
     elif r.retake_video is not None:
         r.route = "retake"
@@ -856,7 +870,7 @@ def _resolve_request(kw: dict):
     if r.low_memory or r.fast_mode:
         print("  low_memory / fast_mode: no effect here (weights and caches stay resident in HBM, the loop is one hipGraph)")
     # the routes that guide themselves take Gemma's encoding of the negative prompt when they will guide (retake: the dev variant only)
-    r.encode_negative = (r.cfg_scale != 1.0 or r.apg_guider is not None) and (r.route in ("keyframe", "hq", "a2vid") or (r.route == "retake" and r.model_variant != "distilled"))
+    r.encode_negative = (r.cfg_scale != 1.0 or r.apg_guider is not None) and (r.route in ("keyframe", "hq", "a2vid", "hq_av") or (r.route == "retake" and r.model_variant != "distilled"))
     r.toy = r.vae_base_channels is not None and r.vae_base_channels != 128        # debug-size VAE: matching debug-size upscaler / encoder
     if r.route is None:
         r.route = "two_stage" if r.two_stage_distilled else "av" if r.av else "standard"
@@ -972,6 +986,7 @@ _REQUIRES = {
                   "the two-stage pipeline needs the VAE weights (per-channel statistics): drop --skip-vae", None, True),
     "av": (None, "AV pipeline requires VAE decoder", "  AV pipeline requires model - cannot use placeholder mode", False),
     "a2vid": ("A2Vid pipeline requires a loaded model", "A2Vid pipeline requires VAE decoder", None, False),
+    "hq_av": ("TI2Vid HQ pipeline requires a loaded model", "TI2Vid HQ pipeline requires VAE decoder", None, False),
 }
 
 
@@ -1109,6 +1124,34 @@ def _run_hq(r, s):
     print(f"[5/5] Running TI2Vid HQ ({r.num_steps} res_2s steps at {r.width // 2}x{r.height // 2}, then 3 at {r.width}x{r.height})...")
     frames, _ = _timed_run("ti2vid-hq", lambda: pipe(s.text_encoding, negative, conf, images=images))
     return finish(r, s, frames)
+
+
+def _run_hq_av(r, s):
+    """ti2vid_hq_audio=True (--ti2vid-hq-audio; keyword-only) runs TI2VidHQPipeline with sound on the AudioVideo transformer: num_steps joint res_2s steps at half resolution, the video guided
+    at cfg_scale and the audio at audio_cfg_scale, the x2 spatial upscale of the video (spatial_upscaler_weights is required, "random" for a random-initialised one), stage 1's audio latent
+    re-noised, and 3 joint distilled steps, under distilled_lora when given; both stages run one C call per step (use_hip_graph has no effect on this route).  image_path sits at frame 0.  The negative encodings are Gemma's of `negative_prompt or ""` when Gemma encodes, else
+    `negative_embedding` / `negative_audio_embedding` of the --embedding file, else zeros.  The audio latent is written to `<stem>_audio_latent.npz`; decode_audio turns it into `<stem>.wav`,
+    muxed into the mp4, as in the av route.  Not combined with audio_path, two_stage_distilled, upscale_temporal, keyframes, retake_video or a2vid_two_stage, nor distilled_lora with
+    fp8_resident.  pipeline_type="ti2vid-hq" without this flag stays the video-only run."""
+    images = _image_conditions(r)
+    print("\n=== Using TI2Vid HQ Pipeline (res_2s, audio + video) ===")
+    _require(r, s)
+    from ltx_2_mlx_amd.pipelines import TI2VidHQConfig, TI2VidHQPipeline
+    conf = TI2VidHQConfig(height=r.height, width=r.width, num_frames=r.num_frames, seed=r.seed, num_inference_steps=r.num_steps,
+                          cfg_scale=r.cfg_scale, audio_cfg_scale=r.audio_cfg_scale, distilled_lora_config=r.hq_lora, use_hip_graph=r.use_hip_graph,
+                          tiling_config=_tiling(r), audio_enabled=True)
+    _banners(r, upscaler=True)
+    pipe = TI2VidHQPipeline(s.model, make_encoder(r), s.vae_decoder, _load_or_random(r, "spatial"))
+    guided = r.cfg_scale > 1.0 or r.audio_cfg_scale > 1.0
+    negative, negative_audio = s.negative_encoding, s.negative_audio_encoding
+    if _negative_or_zeros_note(guided, negative):
+        negative = torch.zeros_like(s.text_encoding)
+    if _negative_or_zeros_note(guided, negative_audio):
+        negative_audio = torch.zeros_like(s.text_audio_encoding)
+    print(f"[5/5] Running TI2Vid HQ with audio ({r.num_steps} joint res_2s steps at {r.width // 2}x{r.height // 2}, then 3 at {r.width}x{r.height})...")
+    frames, _ = _timed_run("ti2vid-hq audio+video", lambda: pipe(s.text_encoding, negative, conf, images=images, positive_audio_encoding=s.text_audio_encoding,
+                                                                 negative_audio_encoding=negative_audio))
+    return finish(r, s, frames, audio=decode_audio_latent(r, s, pipe.audio_latent))
 
 
 def _run_ic_lora(r, s):
@@ -1342,7 +1385,7 @@ def _run_standard(r, s):
 
 
 # today's precedence, top to bottom; _resolve_request names the one that runs
-_ROUTES = {"a2vid": _run_a2vid, "keyframe": _run_keyframe, "hq": _run_hq, "ic_lora": _run_ic_lora, "retake": _run_retake, "two_stage": _run_two_stage,
+_ROUTES = {"hq_av": _run_hq_av, "a2vid": _run_a2vid, "keyframe": _run_keyframe, "hq": _run_hq, "ic_lora": _run_ic_lora, "retake": _run_retake, "two_stage": _run_two_stage,
            "av": _run_av, "standard": _run_standard}
 
 
@@ -1426,6 +1469,7 @@ def generate_video(
     audio_start_time: float = 0.0,
     audio_max_duration=None,
     a2vid_two_stage: bool = False,
+    ti2vid_hq_audio: bool = False,
     retake_video=None,
     retake_start_time: float = 0.0,
     retake_end_time=None,
@@ -1433,7 +1477,7 @@ def generate_video(
 ):
     """Generate video from a text prompt: denoise loop + VAE decode on MI355X behind the reference's signature.  _resolve_request validates the arguments and names the one route that runs, before
     any model is loaded; then the text encoding, the transformer and the VAE decoder (built from the checkpoint's `config.vae` record) are loaded and the route's function runs.  Precedence, each
-    documented on its function: a2vid_two_stage (_run_a2vid; keyword-only, it refuses retake_video), retake_video (_run_retake; it refuses every other route), pipeline_type "keyframe-interpolation" with keyframes (_run_keyframe), "ti2vid-hq" (_run_hq), "ic-lora"
+    documented on its function: ti2vid_hq_audio (_run_hq_av; keyword-only), a2vid_two_stage (_run_a2vid; keyword-only, it refuses retake_video), retake_video (_run_retake; it refuses every other route), pipeline_type "keyframe-interpolation" with keyframes (_run_keyframe), "ti2vid-hq" (_run_hq), "ic-lora"
     with a control video or an image (_run_ic_lora), two_stage_distilled (_run_two_stage), generate_audio or an LTX-2.3 checkpoint (_run_av), else the standard video-only loop (_run_standard).
     pipeline_type "two-stage" raises NotImplementedError. MI355X extras for every route: model_version="2.3" builds the LTX-2.3 architecture without a checkpoint (random init, for tests and
     benchmarks); fp8_resident keeps fp8 checkpoint weights as codes in HBM; fp8_compute runs the video stream's projections fp8 x fp8 on the fp8 MFMA (BASELINE config 3; per-token / per-channel
@@ -1535,6 +1579,9 @@ def build_parser() -> argparse.ArgumentParser:
                    "encoded by the audio VAE encoder and stays frozen while the video is denoised; the original audio is muxed into the mp4")
     p.add_argument("--audio-start", type=float, default=0.0, help="seconds into --audio to start from")
     p.add_argument("--audio-duration", type=float, default=None, help="at most this many seconds of --audio (the rest of the video's length is silence)")
+    p.add_argument("--ti2vid-hq-audio", action="store_true", help="TI2VidHQPipeline WITH sound on the AudioVideo model: --steps joint res_2s steps at half resolution (video guided "
+                   "at --cfg, audio at audio_cfg_scale), x2 spatial upscale, 3 joint distilled steps; needs --spatial-upscaler-weights; --decode-audio writes the .wav. "
+                   "(--ti2vid-hq / pipeline_type='ti2vid-hq' stays the video-only run and keeps refusing --generate-audio)")
     p.add_argument("--a2vid-two-stage", action="store_true", help="A2VidPipelineTwoStage: generate the video TO --audio at production quality on the AudioVideo model: --steps "
                    "steps at half resolution with classifier-free guidance on the video alone and the encoded audio frozen, x2 latent upscale "
                    "(--spatial-upscaler-weights), 3 distilled steps over the same frozen audio, optionally under --distilled-lora.  A flag of its own: "
@@ -1575,7 +1622,7 @@ def kwargs_from_args(a) -> dict:
         text_features_path=a.text_features, use_hip_graph=not a.no_hip_graph, two_stage_distilled=a.two_stage_distilled,
         fp8_resident=a.fp8_resident, fp8_compute=a.fp8_compute, model_version=a.model_version, compute_dtype="bfloat16" if a.bf16 else None, num_layers=a.layers, num_heads=a.heads,
         vae_base_channels=a.vae_base_channels, save_mp4=not a.no_video_file, decode_audio=a.decode_audio,
-        audio_path=a.audio, audio_start_time=a.audio_start, audio_max_duration=a.audio_duration, a2vid_two_stage=a.a2vid_two_stage,
+        audio_path=a.audio, audio_start_time=a.audio_start, audio_max_duration=a.audio_duration, a2vid_two_stage=a.a2vid_two_stage, ti2vid_hq_audio=a.ti2vid_hq_audio,
         retake_video=a.retake, retake_start_time=a.retake_start, retake_end_time=a.retake_end, retake_composite=a.retake_keep_source)
 
 
