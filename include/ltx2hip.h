@@ -298,6 +298,19 @@ int ltx2_guided_euler_step(const float* x, const float* vel_cond, const float* v
                            const float* mask, const float* clean, float cfg_scale, float sigma, float sigma_next,
                            float* out, int rows, int C, void* stream);
 
+/* ltx2_guided_euler_step with spatio-temporal guidance (STG) on top: STGGuider.guide applied to the CFG-guided x0 (pipelines/one_stage.py:284-297).
+ * vel_perturbed is the velocity of a forward whose chosen self-attentions were skipped (ltx2_dit_forward_perturbed).  Per element, every
+ * operation individually rounded, so the result equals the separate fp32 torch ops bit for bit:
+ *   t = ts[row * ts_stride];  a = x - t*vel_cond;  b = x - t*vel_uncond;  g = vel_uncond ? a + (cfg_scale - 1)*(a - b) : a
+ *   p = x - t*vel_perturbed;  s = g + stg_scale*(g - p)
+ *   d = mask ? s*mask[row] + clean*(1 - mask[row]) : s;  out = x + ((x - d) * (1/sigma)) * (sigma_next - sigma)
+ * vel_uncond may be NULL (the guider is not enabled: no CFG).  ts_stride, mask / clean as above; out may equal any input.  16-byte accesses when
+ * C % 4 == 0 and every [rows][C] operand is 16-byte aligned, element-wise otherwise.  sigma == 0 -> LTX2_E_INVALID with message
+ * "Sigma can't be 0.0".  (additive entry of ABI version 3)                                                                              */
+int ltx2_stg_euler_step(const float* x, const float* vel_cond, const float* vel_uncond, const float* vel_perturbed, const float* ts,
+                        int64_t ts_stride, const float* mask, const float* clean, float cfg_scale, float stg_scale, float sigma, float sigma_next,
+                        float* out, int rows, int C, void* stream);
+
 /* The res_2s second-order exponential-integrator step (pipelines/ti2vid_hq.py:153-273) as two passes over [rows][C] fp32, every operation
  * individually rounded (no FMA contraction), so each equals the separate fp32 array ops of the reference bit for bit.  The guided, blended
  * x0 of a pair of velocities, in the HQ pipeline's own order (:315, not CFGGuider's):
@@ -454,6 +467,23 @@ int ltx2_dit_forward_av(ltx2_dit* ctx, const float* v_latent, const float* v_tim
                         const float* v_sigma, const float* a_latent, const float* a_timesteps, int n_a_timesteps,
                         const float* a_sigma, float* v_velocity, float* a_velocity, void* stream);
 
+/* Spatio-temporal guidance (STG): the layers whose SELF-attention a perturbed forward skips, per modality (0 = video, 1 = audio: the reference's
+ * SKIP_VIDEO_SELF_ATTN / SKIP_AUDIO_SELF_ATTN, model/transformer/transformer.py:485-515, 538-543).  flags: a HOST array of n_layers bytes,
+ * non-zero = skip; n_layers must equal the model's; NULL clears the set.  A skipped self-attention is launches that do not happen (the residual
+ * stream is unchanged); the text cross-attention, the cross-modal attention and the feed-forward of that layer run as always.  On a VideoOnly
+ * context (and the video twin of an AudioVideo model) this is the AudioVideo block's video branch with audio absent.  The A2V / V2A cross-modal
+ * perturbations are not built.  The set is read by the perturbed entries alone: every other entry ignores it.
+ * ltx2_dit_forward_perturbed[_av]: the arguments and the program of ltx2_dit_forward[_av] with the stored set applied (an empty set: the same
+ * result bit for bit).  With "fold_norms" = 1 a layer whose self-attention is skipped runs its text cross-attention's pre-norm as a pass of
+ * its own (the skipped out-projection was the fold's producer); the AudioVideo stream / event schedule is that of the plain forward.
+ * (additive entries of ABI version 3)                                                                                                  */
+int ltx2_dit_set_stg_blocks(ltx2_dit* ctx, int modality, const unsigned char* flags, int n_layers);
+int ltx2_dit_forward_perturbed(ltx2_dit* ctx, const float* latent, const float* timesteps, int n_timesteps, const float* sigma,
+                               float* velocity, void* stream);
+int ltx2_dit_forward_perturbed_av(ltx2_dit* ctx, const float* v_latent, const float* v_timesteps, int n_v_timesteps,
+                                  const float* v_sigma, const float* a_latent, const float* a_timesteps, int n_a_timesteps,
+                                  const float* a_sigma, float* v_velocity, float* a_velocity, void* stream);
+
 /* One sampling step: forward -> x0 = latent - ts*v -> post_process -> Euler, latent updated in
  * place (pipelines/distilled.py:214-253; scripts/generate.py:1942-1979).  x0_out may be NULL.  */
 int ltx2_dit_denoise_step(ltx2_dit* ctx, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev,
@@ -492,6 +522,18 @@ int ltx2_dit_guided_step(ltx2_dit* ctx, ltx2_dit* neg, float* latent, const floa
  * belongs to ctx: ltx2_dit_graph_launch(ctx) replays it.                                                                               */
 int ltx2_dit_graph_capture_guided(ltx2_dit* ctx, ltx2_dit* neg, float* latent, const float* host_sigmas, int n_steps,
                                   const float* mask, int64_t n_mask, const float* clean, int64_t n_clean, float cfg_scale, void* stream);
+/* One STG step on the VideoOnly engine (pipelines/one_stage.py:267-326 with a CFGGuider and an STGGuider): forward(ctx), forward(neg) when neg is
+ * given (NULL: no CFG), a perturbed forward on ctx ITSELF (ltx2_dit_forward_perturbed: the set of ltx2_dit_set_stg_blocks) into vel_perturbed, the
+ * caller's [N][out_channels] fp32 scratch, then ltx2_stg_euler_step in place on `latent` -- in order on the caller's stream.  There is no third
+ * context: the perturbed pass reads ctx's per-prompt text K / V.  Validity as ltx2_dit_guided_step (with neg NULL the same rules on ctx alone).
+ * ltx2_dit_graph_capture_stg: n_steps as one captured linear chain owned by ctx, built like ltx2_dit_graph_capture_guided.  Step i is an STG step
+ * iff (i + 1) / n_steps <= stg_cutoff (decided on the host at capture, in double); later steps are the guided step, or the plain step when neg
+ * is NULL.  n_vel: the ELEMENT count of vel_perturbed, checked against N * out_channels.  (additive entries of ABI version 3)             */
+int ltx2_dit_stg_step(ltx2_dit* ctx, ltx2_dit* neg, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev, const float* mask,
+                      const float* clean, float* vel_perturbed, float cfg_scale, float stg_scale, float sigma, float sigma_next, void* stream);
+int ltx2_dit_graph_capture_stg(ltx2_dit* ctx, ltx2_dit* neg, float* latent, const float* host_sigmas, int n_steps, const float* mask, int64_t n_mask,
+                               const float* clean, int64_t n_clean, float* vel_perturbed, int64_t n_vel, float cfg_scale, float stg_scale,
+                               double stg_cutoff, void* stream);
 /* The guided step on the AudioVideo engine with the audio latent FROZEN (audio-to-video; pipelines/a2vid_two_stage.py:225-271): what
  * ltx2_dit_forward_av does on ctx and then on neg, both from the same latents and timestep pointers (sigma_dev is both modalities' sigma), each into
  * its own context's velocity buffers, then ltx2_guided_euler_step in place on the VIDEO latent -- in order on the caller's stream, the audio stream's

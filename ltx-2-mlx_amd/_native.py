@@ -88,6 +88,7 @@ SIGNATURES = {
     "ltx2_x0_from_velocity": (i32, [vp, vp, vp, i64, f32, vp, i32, i32, vp]),
     "ltx2_euler_step": (i32, [vp, vp, vp, vp, f32, f32, vp, i32, i32, vp]),
     "ltx2_guided_euler_step": (i32, [vp, vp, vp, vp, i64, vp, vp, f32, f32, f32, vp, i32, i32, vp]),
+    "ltx2_stg_euler_step": (i32, [vp, vp, vp, vp, vp, i64, vp, vp, f32, f32, f32, f32, vp, i32, i32, vp]),
     "ltx2_res2s_midpoint": (i32, [vp, vp, vp, vp, i64, vp, vp, f32, f32, i32, vp, vp, vp, i32, i32, vp]),
     "ltx2_res2s_combine": (i32, [vp, vp, vp, vp, i64, vp, vp, f32, vp, vp, f32, f32, f32, vp, i32, i32, vp]),
     "ltx2_res2s_midpoint_pair": (i32, [vp, vp, vp, vp, i64, vp, vp, f32, vp, vp, vp, i32, i32,
@@ -117,6 +118,11 @@ SIGNATURES = {
     "ltx2_dit_denoise_step_av": (i32, [vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp]),
     "ltx2_dit_graph_capture_av": (i32, [vp, vp, vp, C.POINTER(f32), i32, vp]),
     "ltx2_dit_forward": (i32, [vp, vp, vp, i32, vp, vp, vp]),
+    "ltx2_dit_set_stg_blocks": (i32, [vp, i32, C.c_char_p, i32]),
+    "ltx2_dit_forward_perturbed": (i32, [vp, vp, vp, i32, vp, vp, vp]),
+    "ltx2_dit_forward_perturbed_av": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp]),
+    "ltx2_dit_stg_step": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, f32, f32, f32, f32, vp]),
+    "ltx2_dit_graph_capture_stg": (i32, [vp, vp, vp, C.POINTER(f32), i32, vp, i64, vp, i64, vp, i64, f32, f32, C.c_double, vp]),
     "ltx2_dit_denoise_step": (i32, [vp, vp, vp, i32, vp, vp, vp, f32, f32, vp, vp]),
     "ltx2_dit_graph_capture": (i32, [vp, vp, C.POINTER(f32), i32, vp]),
     "ltx2_dit_graph_capture_cond": (i32, [vp, vp, C.POINTER(f32), i32, vp, i64, vp, i64, vp]),

@@ -2,7 +2,8 @@
 
 Host-side glue of the guided single-stage loops: two x0 predictions (positive / negative prompt) per step are combined here in
 fp32 on the device (element-wise ops and dot products over a (B, N, C) tensor).  pipelines.common.projected_denoise_loop runs the
-same guiders as two kernels per step (csrc/sampler.hip).  STG guiders are outside the path."""
+same guiders as two kernels per step (csrc/sampler.hip).  STGGuider (:80-102) pushes the guided prediction away from one made with chosen
+self-attentions skipped (components/perturbations.py); pipelines.common.stg_denoise_loop runs it inside one kernel per step."""
 from __future__ import annotations
 
 from dataclasses import dataclass, field
@@ -48,6 +49,22 @@ class CFGStarRescalingGuider:
 
     def enabled(self) -> bool:
         return self.scale != 1.0
+
+
+@dataclass(frozen=True)
+class STGGuider:
+    """pos + scale (pos - perturbed)  (guiders.py:80-102): `perturbed` is the prediction of a pass whose chosen attentions acted as a
+    passthrough.  scale 0 disables it."""
+    scale: float
+
+    def delta(self, pos_denoised: torch.Tensor, perturbed_denoised: torch.Tensor) -> torch.Tensor:
+        return self.scale * (pos_denoised - perturbed_denoised)
+
+    def guide(self, pos_denoised: torch.Tensor, perturbed_denoised: torch.Tensor) -> torch.Tensor:
+        return pos_denoised + self.delta(pos_denoised, perturbed_denoised)
+
+    def enabled(self) -> bool:
+        return self.scale != 0.0
 
 
 def _apg_delta(guidance: torch.Tensor, cond: torch.Tensor, eta: float, norm_threshold: float) -> torch.Tensor:

@@ -286,6 +286,13 @@ int ltx2_guided_euler_step(const float* x, const float* vel_cond, const float* v
                                     (hipStream_t)stream);
 }
 
+int ltx2_stg_euler_step(const float* x, const float* vel_cond, const float* vel_uncond, const float* vel_perturbed, const float* ts, int64_t ts_stride,
+                        const float* mask, const float* clean, float cfg_scale, float stg_scale, float sigma, float sigma_next, float* out, int rows,
+                        int C, void* stream) {
+    return stg_euler_step_launch(x, vel_cond, vel_uncond, vel_perturbed, ts, (long)ts_stride, mask, clean, cfg_scale, stg_scale, sigma, sigma_next, out,
+                                 rows, C, (hipStream_t)stream);
+}
+
 int ltx2_res2s_midpoint(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, int64_t ts_stride, const float* mask,
                         const float* clean, float cfg_scale, float c, int n_bong, float* x_mid, float* anchor, float* eps1, int rows, int C,
                         void* stream) {

@@ -126,6 +126,7 @@ struct ltx2_dit {
     bool adaln_combine = true;         // ltx2_dit_set_option("adaln_combine"): round 4, see forward()
     bool text_kv_ahead = true;         // ltx2_dit_set_option("text_kv_ahead"): round 5, AudioVideo V2.3 -- the video stream's sigma-modulated text K / V of layer l are projected on the SIDE stream at the top of the layer
     hipEvent_t text_kv_ev = nullptr;   //   (they depend on the prompt and sigma only); the main stream waits on this event in front of its text cross-attention
+    std::vector<unsigned char> stg[2]; // ltx2_dit_set_stg_blocks: per modality, the layers whose self-attention a PERTURBED forward leaves out (empty: none)
     int fold_norms = 1;                // ltx2_dit_set_option("fold_norms"): round 6, see block_attention(): 0 = every norm a pass of its own (round 5), 1 = the text cross-attention's
                                        //   plain RMS pre-norm rides on attn1.to_out's epilogue
     bool fp8_compute = false;          // ltx2_dit_set_option("fp8_compute"): fp8-resident weights x per-token fp8 activations on the fp8 MFMA
@@ -590,7 +591,10 @@ AdaRows ada_rows(const ltx2_dit* c, const Mod& m, const BlockW& w, int l) {
 }
 
 // Self-attention, text cross-attention of one modality (transformer.py:503-554 / 191-226)
-int block_attention(ltx2_dit* c, int k, int l, long es, hipStream_t st, int fold = 0) {
+// skip_self (a perturbed forward, STG; transformer.py:485-515): the self-attention sub-block is launches that do not happen -- the residual stream is
+// unchanged, so its norm, gate logits, QKV projection, QK-norm + RoPE, V^T, attention and out-projection are all left out.  Its out-projection is also
+// the fold's producer: such a layer runs its text cross-attention unfolded.  Only kernels are skipped, never an event record or wait.
+int block_attention(ltx2_dit* c, int k, int l, long es, hipStream_t st, int fold = 0, bool skip_self = false) {
     Mod& m = c->m[k];
     const BlockW& w = c->layers[l].m[k];
     const int N = m.N, D = m.D, H = m.H, hd = m.hd;
@@ -600,24 +604,24 @@ int block_attention(ltx2_dit* c, int k, int l, long es, hipStream_t st, int fold
     // self-attention: AdaLN rows (shift, scale, gate) = sst[0:3] + emb[0:3]
     // fp8 compute: the norm kernels hand the following GEMM per-token e4m3fn codes directly (and skip the bf16 copy nobody else reads)
     const bool q1 = k == 0 && f8_route(c, w.self.qkv_w, N, 3 * D, D, EPI_BF16);
-    const int fl = k == 0 ? fold : 0;
-    TRY(norm_mod_launch(m.x, D, (q1 && !c->gated) ? nullptr : m.h, D, N, D, eps, 0, tab + D, tab, ada.E(1), ada.E(0), es, st, q1 ? m.a8 : nullptr, D,
-                        q1 ? m.a8s : nullptr));
-    TRY(gate_logits(c, m, w.self, m.h, D, N, H, st));
-    bool vt_done = false;           // the QKV GEMM's epilogue writes V^T itself where it can (gemm_v4.hip)
-    {
-        GemmParams p = gemm_dense_params(m.h, D, w.self.qkv_w, w.self.qkv_b, m.qkv, 3 * D, N, 3 * D, D);
-        gemm_set_vt(p, m.vt, 2 * D, m.Npad, hd);
-        TRY(dense(c, p, EPI_BF16, st, q1, &vt_done));
-    }
-    {
-        const int offs[2] = {0, D};
-        const float* wts[2] = {w.self.qn, w.self.kn};
-        TRY(qknorm_rope_launch(m.qkv, 3 * D, N, D, hd, 2, offs, wts, eps, m.cosb, m.sinb, st));
-    }
-    if (!vt_done) TRY(vt_transpose_launch(m.qkv + 2 * D, 3 * D, m.vt, N, m.Npad, H, st, hd));
-    TRY(attend(attn_params(m.qkv, 3 * D, m.qkv + D, 3 * D, m.vt, m.Npad, m.att, D, N, N, H, hd, scale_log2e(hd)), glog(c, m), st));
-    {
+    const int fl = (k == 0 && !skip_self) ? fold : 0;
+    if (!skip_self) {
+        TRY(norm_mod_launch(m.x, D, (q1 && !c->gated) ? nullptr : m.h, D, N, D, eps, 0, tab + D, tab, ada.E(1), ada.E(0), es, st, q1 ? m.a8 : nullptr, D,
+                            q1 ? m.a8s : nullptr));
+        TRY(gate_logits(c, m, w.self, m.h, D, N, H, st));
+        bool vt_done = false;           // the QKV GEMM's epilogue writes V^T itself where it can (gemm_v4.hip)
+        {
+            GemmParams p = gemm_dense_params(m.h, D, w.self.qkv_w, w.self.qkv_b, m.qkv, 3 * D, N, 3 * D, D);
+            gemm_set_vt(p, m.vt, 2 * D, m.Npad, hd);
+            TRY(dense(c, p, EPI_BF16, st, q1, &vt_done));
+        }
+        {
+            const int offs[2] = {0, D};
+            const float* wts[2] = {w.self.qn, w.self.kn};
+            TRY(qknorm_rope_launch(m.qkv, 3 * D, N, D, hd, 2, offs, wts, eps, m.cosb, m.sinb, st));
+        }
+        if (!vt_done) TRY(vt_transpose_launch(m.qkv + 2 * D, 3 * D, m.vt, N, m.Npad, H, st, hd));
+        TRY(attend(attn_params(m.qkv, 3 * D, m.qkv + D, 3 * D, m.vt, m.Npad, m.att, D, N, N, H, hd, scale_log2e(hd)), glog(c, m), st));
         GemmParams p = gemm_dense_params(m.att, D, w.self.o_w, w.self.o_b, m.x, D, N, D, D);
         gemm_set_gate(p, ada.E(2), es, tab + 2 * D);
         // the new residual rows also leave as the cross-attention query projection's operand (plain RMS norm: no scale, no shift): their shadow into h, its partial sums into rss
@@ -788,8 +792,10 @@ struct ModIn {
     float* velocity;
 };
 
-int forward(ltx2_dit* c, const ModIn* in, hipStream_t st, bool rewind_events = true) {
+// perturbed: the layers of c->stg[k] run without their self-attention (block_attention()); everything else, the schedule included, is the same program
+int forward(ltx2_dit* c, const ModIn* in, hipStream_t st, bool rewind_events = true, bool perturbed = false) {
     const int nm = c->av ? 2 : 1;
+    const auto skip = [&](int k, int l) { return perturbed && !c->stg[k].empty() && c->stg[k][l] != 0; };
     if (rewind_events) c->sync_next = 0;
     long es[2] = {0, 0}, ee[2] = {0, 0};
     for (int k = 0; k < nm; ++k) {
@@ -839,9 +845,9 @@ int forward(ltx2_dit* c, const ModIn* in, hipStream_t st, bool rewind_events = t
                 c->text_kv_ev = event_record(c, sa);
                 if (!c->text_kv_ev) return LTX2_E_HIP;
             }
-            TRY(block_attention(c, 1, l, es[1], sa));
+            TRY(block_attention(c, 1, l, es[1], sa, 0, skip(1, l)));
         }
-        TRY(block_attention(c, 0, l, es[0], st, fold));
+        TRY(block_attention(c, 0, l, es[0], st, fold, skip(0, l)));
         if (c->av) {
             TRY(block_cross_modal(c, l, st, sa));      // main: the video side; side: the audio side (events inside)
             TRY(block_ffn(c, 1, l, es[1], sa));
@@ -1166,6 +1172,36 @@ int ltx2_dit_forward_av(ltx2_dit* c, const float* v_latent, const float* v_times
     return forward(c, in, (hipStream_t)stream);
 }
 
+int ltx2_dit_set_stg_blocks(ltx2_dit* c, int modality, const unsigned char* flags, int n_layers) {
+    LTX2_CHECK_ARG(c && (modality == 0 || (modality == 1 && c->av)), "dit_set_stg_blocks: bad context / modality");
+    if (!flags) {
+        c->stg[modality].clear();
+        return LTX2_OK;
+    }
+    LTX2_CHECK_ARG(n_layers == c->cfg.num_layers, "dit_set_stg_blocks: n_layers=%d, the model has %d", n_layers, c->cfg.num_layers);
+    c->stg[modality].assign(flags, flags + n_layers);
+    return LTX2_OK;
+}
+
+int ltx2_dit_forward_perturbed(ltx2_dit* c, const float* latent, const float* timesteps, int n_timesteps, const float* sigma,
+                               float* velocity, void* stream) {
+    LTX2_CHECK_ARG(latent && timesteps && velocity, "dit_forward_perturbed: null argument");
+    TRY(check_ready(c, "dit_forward_perturbed", false));
+    ModIn in[1] = {{latent, timesteps, n_timesteps, sigma ? sigma : timesteps, velocity}};
+    return forward(c, in, (hipStream_t)stream, true, true);
+}
+
+int ltx2_dit_forward_perturbed_av(ltx2_dit* c, const float* v_latent, const float* v_timesteps, int n_v_timesteps,
+                                  const float* v_sigma, const float* a_latent, const float* a_timesteps, int n_a_timesteps,
+                                  const float* a_sigma, float* v_velocity, float* a_velocity, void* stream) {
+    LTX2_CHECK_ARG(v_latent && v_timesteps && v_sigma && a_latent && a_timesteps && a_sigma && v_velocity && a_velocity,
+                   "dit_forward_perturbed_av: null argument");
+    TRY(check_ready(c, "dit_forward_perturbed_av", true));
+    ModIn in[2] = {{v_latent, v_timesteps, n_v_timesteps, v_sigma, v_velocity},
+                   {a_latent, a_timesteps, n_a_timesteps, a_sigma, a_velocity}};
+    return forward(c, in, (hipStream_t)stream, true, true);
+}
+
 int ltx2_dit_denoise_step(ltx2_dit* c, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev,
                           const float* mask, const float* clean, float sigma, float sigma_next, float* x0_out, void* stream) {
     LTX2_CHECK_ARG(latent && timesteps, "dit_denoise_step: null argument");
@@ -1252,6 +1288,30 @@ int guided_step(ltx2_dit* c, ltx2_dit* neg, const ModIn& in, const StepIo& io, f
                                     m.N, m.Cout, st);
 }
 
+// Spatio-temporal guidance on top (pipelines/one_stage.py:284-297): a third evaluation, on c ITSELF with the self-attentions of c->stg[0] skipped (no third
+// context: its text K / V would be a second copy of c's), into the caller's scratch; then the one element-wise pass.  neg may be NULL: no CFG.
+int stg_ready(ltx2_dit* c, ltx2_dit* neg, int n_ts, const char* who) {
+    if (neg) return guided_ready(c, neg, n_ts, who);
+    LTX2_CHECK_ARG(c, "%s: null context", who);
+    LTX2_CHECK_ARG(!c->av, "%s: the STG step runs on VideoOnly contexts (the video twin of an AudioVideo model)", who);
+    LTX2_CHECK_ARG(c->prepared, "%s: ltx2_dit_prepare has not been called", who);
+    LTX2_CHECK_ARG(n_ts == 1 || c->per_token, "%s: a workspace was not bound for per-token timesteps", who);
+    return LTX2_OK;
+}
+
+int stg_step(ltx2_dit* c, ltx2_dit* neg, const ModIn& in, const StepIo& io, float* vel_perturbed, float cfg_scale, float stg_scale, float sigma,
+             float sigma_next, hipStream_t st) {
+    LTX2_CHECK_ARG(sigma != 0.f, "Sigma can't be 0.0");
+    LTX2_CHECK_ARG((io.mask == nullptr) == (io.clean == nullptr), "dit_stg_step: mask and clean go together");
+    LTX2_CHECK_ARG(vel_perturbed, "dit_stg_step: vel_perturbed (an [N][out_channels] fp32 scratch) is required");
+    const Mod& m = c->m[0];
+    TRY(evaluate_pair(c, neg, in.latent, in.ts, in.n_ts, in.sigma, st));
+    const ModIn pert[1] = {{in.latent, in.ts, in.n_ts, in.sigma, vel_perturbed}};
+    TRY(forward(c, pert, st, true, true));
+    return stg_euler_step_launch(in.latent, m.vel, neg ? neg->m[0].vel : nullptr, vel_perturbed, in.ts, in.n_ts == 1 ? 0 : 1, io.mask, io.clean, cfg_scale,
+                                 stg_scale, sigma, sigma_next, io.latent, m.N, m.Cout, st);
+}
+
 // The same on the AudioVideo engine with the audio latent frozen (audio-to-video; reference pipelines/a2vid_two_stage.py:225-271): both contexts
 // evaluate both modalities, the guidance and the Euler update touch the video latent alone.  Every count is checked here, before the first launch.
 int guided_ready_av(ltx2_dit* c, ltx2_dit* neg, int n_v_ts, int n_a_ts, const char* who) {
@@ -1292,6 +1352,15 @@ int ltx2_dit_guided_step_av(ltx2_dit* c, ltx2_dit* neg, float* v_latent, const f
     const ModIn in[2] = {{v_latent, v_timesteps, n_v_timesteps, sigma_dev, nullptr}, {a_latent, a_timesteps, n_a_timesteps, sigma_dev, nullptr}};
     const StepIo io = {v_latent, v_mask, v_clean, nullptr};
     return guided_step_av(c, neg, in, io, cfg_scale, sigma, sigma_next, (hipStream_t)stream);
+}
+
+int ltx2_dit_stg_step(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev, const float* mask,
+                      const float* clean, float* vel_perturbed, float cfg_scale, float stg_scale, float sigma, float sigma_next, void* stream) {
+    LTX2_CHECK_ARG(latent && timesteps, "dit_stg_step: null argument");
+    TRY(stg_ready(c, neg, n_timesteps, "dit_stg_step"));
+    const ModIn in = {latent, timesteps, n_timesteps, sigma_dev ? sigma_dev : timesteps, nullptr};
+    const StepIo io = {latent, mask, clean, nullptr};
+    return stg_step(c, neg, in, io, vel_perturbed, cfg_scale, stg_scale, sigma, sigma_next, (hipStream_t)stream);
 }
 
 int ltx2_dit_guided_step(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev,
@@ -1539,6 +1608,9 @@ struct LoopStep {                           // all defaults: the plain denoise s
     float cfg_scale = 0.f;
     const Projected* projected = nullptr;   // the projected step with this guider
     const Res2sPlan* res2s = nullptr;       // the res_2s step: one plan per step
+    float* stg_vel = nullptr;               // the STG step into this scratch on the first stg_steps steps, then the guided (neg) or the plain step
+    float stg_scale = 0.f;
+    int stg_steps = 0;
 };
 
 int capture_loop(ltx2_dit* c, const LoopStep& step, float* const latent[2], const Cond cond[2], const float* host_sigmas, int n_steps, hipStream_t st) {
@@ -1568,6 +1640,8 @@ int capture_loop(ltx2_dit* c, const LoopStep& step, float* const latent[2], cons
             if (step.res2s[i].last) break;                      // the reference's loop ends on its final step
         } else if (step.projected) {
             rc = projected_step(c, step.neg, in[0], io[0], *step.projected, i == 0, sigma, sigma_next, st);
+        } else if (step.stg_vel && i < step.stg_steps) {
+            rc = stg_step(c, step.neg, in[0], io[0], step.stg_vel, step.cfg_scale, step.stg_scale, sigma, sigma_next, st);
         } else if (step.neg && c->av) {
             rc = guided_step_av(c, step.neg, in, io[0], step.cfg_scale, sigma, sigma_next, st, i == 0);
         } else if (step.neg) {
@@ -1649,6 +1723,29 @@ int ltx2_dit_graph_capture_guided(ltx2_dit* c, ltx2_dit* neg, float* latent, con
     float* const lat[2] = {latent, nullptr};
     const Cond cond[2] = {{mask, (long)n_mask, clean, (long)n_clean}, {}};
     return capture_loop(c, {neg, cfg_scale}, lat, cond, host_sigmas, n_steps, (hipStream_t)stream);
+}
+
+int ltx2_dit_graph_capture_stg(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* host_sigmas, int n_steps, const float* mask, int64_t n_mask,
+                               const float* clean, int64_t n_clean, float* vel_perturbed, int64_t n_vel, float cfg_scale, float stg_scale, double stg_cutoff,
+                               void* stream) {
+    LTX2_CHECK_ARG(c && latent && host_sigmas && vel_perturbed && n_steps > 0 && n_steps < 64, "dit_graph_capture_stg: bad argument");
+    TRY(stg_ready(c, neg, mask ? c->m[0].N : 1, "dit_graph_capture_stg"));
+    LTX2_CHECK_ARG((mask == nullptr) == (clean == nullptr), "dit_graph_capture_stg: mask and clean go together");
+    // every replayed STG step writes N * out_channels velocities there
+    LTX2_CHECK_ARG(n_vel == (int64_t)c->m[0].N * c->m[0].Cout, "dit_graph_capture_stg: vel_perturbed has %ld elements, %d tokens x %d channels are needed", (long)n_vel,
+                   c->m[0].N, c->m[0].Cout);
+    // step i is an STG step iff (i + 1) / n_steps <= stg_cutoff (one_stage.py:289-294), in double as Python divides; the fractions grow with i
+    int stg_steps = 0;
+    while (stg_steps < n_steps && (double)(stg_steps + 1) / (double)n_steps <= stg_cutoff) ++stg_steps;
+    float* const lat[2] = {latent, nullptr};
+    const Cond cond[2] = {{mask, (long)n_mask, clean, (long)n_clean}, {}};
+    LoopStep step;
+    step.neg = neg;
+    step.cfg_scale = cfg_scale;
+    step.stg_vel = vel_perturbed;
+    step.stg_scale = stg_scale;
+    step.stg_steps = stg_steps;
+    return capture_loop(c, step, lat, cond, host_sigmas, n_steps, (hipStream_t)stream);
 }
 
 int ltx2_dit_graph_capture_projected(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* host_sigmas, int n_steps, const float* mask, int64_t n_mask,

@@ -19,6 +19,12 @@ int guided_euler_step_launch(const float* x, const float* vel_cond, const float*
                              const float* mask, const float* clean, float cfg_scale, float sigma, float sigma_next, float* out,
                              int rows, int C, hipStream_t stream);
 
+// The same step with spatio-temporal guidance on top (STGGuider.guide applied to the CFG-guided x0; vel_perturbed: the velocity of the pass whose
+// self-attentions were skipped): g as above (g = a when vel_uncond is NULL), p = x - t*vp, s = g + stg_scale*(g - p), then d and out from s
+int stg_euler_step_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* vel_perturbed, const float* ts, long ts_stride,
+                          const float* mask, const float* clean, float cfg_scale, float stg_scale, float sigma, float sigma_next, float* out, int rows,
+                          int C, hipStream_t stream);
+
 // The res_2s second-order step as two passes; d(x, vc, vu) = the guided, mask-blended x0 in the HQ pipeline's order:
 // a = x - t*vc, b = x - t*vu, g = b + cfg*(a - b) (g = a when vu is NULL), d = mask ? g*m + clean*(1 - m) : g.
 // midpoint: an = x, e = d - an, xm = an + c*e, n_bong x {an = xm - c*e, e = d - an}; stores x_mid, anchor, eps1.

@@ -1,5 +1,5 @@
 // The device code of the sampling step over fp32 [rows][C] latents: the plain x0 / Euler pair, and the steps that replace a sequence of separate
-// fp32 torch ops bit for bit -- the classifier-free-guided Euler step (pipelines/one_stage.py:224-330), the two passes of the res_2s second-order
+// fp32 torch ops bit for bit -- the classifier-free-guided Euler step (pipelines/one_stage.py:224-330), the same with STG guidance on top, the two passes of the res_2s second-order
 // step (reference pipelines/ti2vid_hq.py:153-273; over one latent, or over the video and the audio latent of the joint step in one launch) and the two passes of the guiders whose scalars are reductions over the whole latent
 // (CFGStarRescalingGuider, LtxAPGGuider, LegacyStatefulAPGGuider; reference components/guiders.py:51-76, 105-205).  All arithmetic is fp32 and
 // fp64, so the file compiles to the same code in both library builds.  The definitions are written out in include/ltx2hip.h.
@@ -143,6 +143,22 @@ struct GuidedEuler : StepOp {
     __device__ __forceinline__ void one(State&, const Row& r, const float* a, float* o) const {
         const float g = guide_from_cond(denoised(a[X], a[VC], r.t), denoised(a[X], a[VU], r.t), s1);
         o[OUT] = euler(a[X], blend_clean(g, a[CLEAN], r), inv, dt);
+    }
+};
+
+// STGGuider.guide on top of the CFG-guided x0 (pipelines/one_stage.py:284-297): g as GuidedEuler forms it (g = a with no vu: the guider is not
+// enabled), p = x - t*vp from the pass whose self-attentions were skipped, s = g + stg*(g - p)
+struct StgEuler : StepOp {
+    enum { X, VC, VU, VP, CLEAN, NIN };
+    enum { OUT, NOUT };
+    const float* in[NIN];
+    float* out[NOUT];
+    float s1, stg, inv, dt;     // cfg_scale - 1, stg_scale, 1/sigma, sigma_next - sigma
+    __device__ __forceinline__ void one(State&, const Row& r, const float* a, float* o) const {
+        float g = denoised(a[X], a[VC], r.t);
+        if (in[VU]) g = guide_from_cond(g, denoised(a[X], a[VU], r.t), s1);
+        const float s = add_rn(g, mul_rn(stg, sub_rn(g, denoised(a[X], a[VP], r.t))));
+        o[OUT] = euler(a[X], blend_clean(s, a[CLEAN], r), inv, dt);
     }
 };
 
@@ -396,6 +412,14 @@ int guided_euler_step_launch(const float* x, const float* vel_cond, const float*
     LTX2_CHECK_ARG(sigma != 0.f, "Sigma can't be 0.0");   // reference core_utils.py:54-55
     const GuidedEuler op = {{}, {x, vel_cond, vel_uncond, clean}, {out}, cfg_scale - 1.0f, 1.0f / sigma, sigma_next - sigma};
     return launch_rows("guided_euler_step", x && vel_cond && vel_uncond && out, op, ts, ts_stride, mask, clean, rows, C, 0, stream);
+}
+
+int stg_euler_step_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* vel_perturbed, const float* ts, long ts_stride,
+                          const float* mask, const float* clean, float cfg_scale, float stg_scale, float sigma, float sigma_next, float* out, int rows,
+                          int C, hipStream_t stream) {
+    LTX2_CHECK_ARG(sigma != 0.f, "Sigma can't be 0.0");   // reference core_utils.py:54-55
+    const StgEuler op = {{}, {x, vel_cond, vel_uncond, vel_perturbed, clean}, {out}, cfg_scale - 1.0f, stg_scale, 1.0f / sigma, sigma_next - sigma};
+    return launch_rows("stg_euler_step", x && vel_cond && vel_perturbed && out, op, ts, ts_stride, mask, clean, rows, C, 0, stream);
 }
 
 int res2s_midpoint_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride, const float* mask,

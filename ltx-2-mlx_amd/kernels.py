@@ -534,6 +534,22 @@ def guided_euler_step(x: torch.Tensor, vel_cond: torch.Tensor, vel_uncond: torch
     return out
 
 
+def stg_euler_step(x: torch.Tensor, vel_cond: torch.Tensor, vel_uncond: Optional[torch.Tensor], vel_perturbed: torch.Tensor, timesteps: torch.Tensor,
+                   cfg_scale: float, stg_scale: float, sigma: float, sigma_next: float, mask: Optional[torch.Tensor] = None,
+                   clean: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """guided_euler_step with STGGuider.guide on top (ltx2_stg_euler_step): x0 of the three velocities, CFGGuider.guide (vel_uncond None: no CFG),
+    g + stg_scale * (g - perturbed), the mask / clean blend and the Euler update in one pass, every operation individually rounded.
+    timesteps: 1 or N elements; `out` may be any input; `dtype` picks the library build (the kernel is fp32 in both)."""
+    if out is None:
+        out = torch.empty_like(x)
+    assert vel_cond is not None and vel_perturbed is not None and (mask is None or clean is not None)
+    n, c, timesteps = _step_operands(x, timesteps, (vel_cond, vel_uncond, vel_perturbed, clean, out), mask)
+    nv.check(nv.lib(dtype).ltx2_stg_euler_step(nv.ptr(x), nv.ptr(vel_cond), nv.ptr(vel_uncond), nv.ptr(vel_perturbed), nv.ptr(timesteps),
+                                               0 if timesteps.numel() == 1 else 1, nv.ptr(mask), nv.ptr(clean), float(cfg_scale), float(stg_scale),
+                                               float(sigma), float(sigma_next), nv.ptr(out), n, c, nv.stream()))
+    return out
+
+
 GUIDANCE_MODES = {"cfg_star": 0, "apg": 1, "legacy_apg": 2}      # `mode` of ltx2_projected_euler_step / ltx2_dit_projected_step
 
 

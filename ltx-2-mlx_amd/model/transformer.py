@@ -9,6 +9,7 @@ cross-attention K/V, RoPE tables) is computed once per (context, positions) pair
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 from dataclasses import dataclass
@@ -173,6 +174,7 @@ class LTXModel:
         self._clone: Optional["LTXModel"] = None       # clone_sharing_weights()
         self._twin: Optional["LTXModel"] = None        # VideoOnly engine over the SAME weight tensors (video-only inference on an AV model)
         self._sigma_dev: Dict[float, torch.Tensor] = {}  # device scalars of the step sigmas (no host-to-device copy inside the loop)
+        self._stg: Dict[int, Optional[bytes]] = {0: None, 1: None}     # per modality, the engine's STG skip flags (set_stg_blocks); None: no set
         self._graph_owner: Optional[Tuple[str, "LTXModel"]] = None     # (kind of the last capture made through this object, the context that holds its graph)
         self._ctor = dict(num_attention_heads=num_attention_heads, attention_head_dim=attention_head_dim, in_channels=in_channels,
                           out_channels=out_channels, num_layers=num_layers, cross_attention_dim=cross_attention_dim, norm_eps=norm_eps,
@@ -193,8 +195,68 @@ class LTXModel:
             t = LTXModel(model_type=LTXModelType.VideoOnly, **self._ctor)
             for k, v in self._w.items():
                 t._register(k, v)
+            t._put_stg_flags(0, self._stg[0])
             self._twin = t
         return self._twin
+
+    # ------------------------------------------------------------------ STG: the self-attentions a perturbed forward skips
+    def _set_ctx_flags(self, modality: int, flags: Optional[bytes]) -> None:
+        """This context's set alone (self._stg mirrors what the engine holds)."""
+        if self._stg[modality] != flags:
+            nv.check(self._L.ltx2_dit_set_stg_blocks(self._h, modality, flags, 0 if flags is None else len(flags)))
+            self._stg[modality] = flags
+
+    def _put_stg_flags(self, modality: int, flags: Optional[bytes]) -> None:
+        self._set_ctx_flags(modality, flags)
+        if modality == 0 and self._twin is not None:
+            self._twin._put_stg_flags(0, flags)
+
+    @contextlib.contextmanager
+    def _stg_override(self, flags: Tuple[Optional[bytes], Optional[bytes]]):
+        """The sets of one __call__(..., perturbations=...) on this context, for the duration of the call: the engine reads them while it
+        enqueues, so the sets of set_stg_blocks are put back as soon as the call returns."""
+        prev = dict(self._stg)
+        try:
+            for k in ((0, 1) if self.is_av else (0,)):
+                self._set_ctx_flags(k, flags[k])
+            yield
+        finally:
+            for k, f in prev.items():
+                self._set_ctx_flags(k, f)
+
+    def set_stg_blocks(self, blocks: Optional[Sequence[int]], modality: int = 0) -> None:
+        """The layers whose self-attention the perturbed forward (__call__(..., perturbations=...), stg_step_, the captured STG loop) skips:
+        modality 0 video, 1 audio (AudioVideo models).  None: every layer; an empty list clears the set.  An AudioVideo model hands the video
+        set on to its video twin.  The plain forward and every other step ignore it (ltx2_dit_set_stg_blocks)."""
+        if modality not in (0, 1) or (modality == 1 and not self.is_av):
+            raise ValueError(f"modality={modality}: 0 (video), or 1 (audio) on an AudioVideo model")
+        idx = list(range(self.num_layers)) if blocks is None else [int(b) for b in blocks]
+        bad = [b for b in idx if not 0 <= b < self.num_layers]
+        if bad:
+            raise ValueError(f"stg_blocks {bad} out of range: the model has {self.num_layers} layers")
+        flags = bytearray(self.num_layers)
+        for b in idx:
+            flags[b] = 1
+        self._put_stg_flags(modality, bytes(flags) if idx else None)
+
+    def _perturbation_flags(self, perturbations) -> Optional[Tuple[Optional[bytes], Optional[bytes]]]:
+        """A BatchedPerturbationConfig of batch 1 -> (video flags, audio flags) for ltx2_dit_set_stg_blocks; None: nothing is perturbed."""
+        from ..components.perturbations import BatchedPerturbationConfig, PerturbationType as PT
+        if perturbations is None:
+            return None
+        if not isinstance(perturbations, BatchedPerturbationConfig):
+            raise TypeError("perturbations must be a BatchedPerturbationConfig")
+        if len(perturbations.perturbations) != 1:
+            raise ValueError("batch must be 1 (one PerturbationConfig)")
+        L = range(self.num_layers)
+        for kind in (PT.SKIP_A2V_CROSS_ATTN, PT.SKIP_V2A_CROSS_ATTN):
+            if any(perturbations.any_in_batch(kind, l) for l in L):
+                raise NotImplementedError(f"{kind.name}: the cross-modal perturbations are not built (they would cut into the AudioVideo stream schedule)")
+        out = []
+        for kind in (PT.SKIP_VIDEO_SELF_ATTN, PT.SKIP_AUDIO_SELF_ATTN):
+            f = bytes(1 if perturbations.all_in_batch(kind, l) else 0 for l in L)
+            out.append(f if any(f) else None)
+        return None if out == [None, None] else (out[0], out[1])
 
     def clone_sharing_weights(self) -> "LTXModel":
         """A second engine context of the SAME model over the SAME weight tensors (nothing is copied): its own workspace and per-prompt
@@ -525,8 +587,6 @@ class LTXModel:
     def _check_inputs(self, video, audio, perturbations):
         if video is None:
             raise ValueError("Video modality required for video-enabled model")     # model.py:823-824
-        if perturbations is not None:
-            raise NotImplementedError("STG perturbations are outside the distilled hot path (cfg forced to 1)")
         for m in (video, audio):
             if m is not None and m.context_mask is not None:
                 cm = m.context_mask
@@ -541,7 +601,11 @@ class LTXModel:
             raise ValueError("audio modality passed to a VideoOnly model")
 
     def __call__(self, video: Optional[Modality] = None, audio: Optional[Modality] = None, perturbations=None):
+        """perturbations: a BatchedPerturbationConfig of batch 1 -- the forward then skips the self-attentions it names (the engine's perturbed
+        entries; the config holds for this call alone, the sets of set_stg_blocks are back when it returns).  None or an empty config: the plain
+        forward."""
         self._check_inputs(video, audio, perturbations)
+        flags = self._perturbation_flags(perturbations)
         if self.is_av and (audio is None or not audio.enabled or audio.latent.shape[1] == 0):     # transformer.py:480: run_ax needs audio.enabled and tokens
             # video-only inference on an AudioVideo model (model.py:829-840, 866-874): (video velocity, empty audio output)
             v = self._video_twin()(video, None, perturbations=perturbations)
@@ -554,7 +618,11 @@ class LTXModel:
             self._apply_context_masks(video)
             # prompt AdaLN (V2.3) takes Modality.sigma, not timesteps[0]: with image conditioning timesteps = mask * sigma
             sg = self._sigma(video) if self.cross_attention_adaln else None
-            nv.check(self._L.ltx2_dit_forward(self._h, nv.ptr(lat), nv.ptr(ts), n_ts, nv.ptr(sg), nv.ptr(out), nv.stream()))
+            if flags is None:
+                nv.check(self._L.ltx2_dit_forward(self._h, nv.ptr(lat), nv.ptr(ts), n_ts, nv.ptr(sg), nv.ptr(out), nv.stream()))
+            else:
+                with self._stg_override(flags):
+                    nv.check(self._L.ltx2_dit_forward_perturbed(self._h, nv.ptr(lat), nv.ptr(ts), n_ts, nv.ptr(sg), nv.ptr(out), nv.stream()))
             return out[None]
         ats, n_ats = self._timesteps(audio)
         self._ensure_prepared(video, per_token=(n_ts != 1 or n_ats != 1), audio=audio)
@@ -562,8 +630,12 @@ class LTXModel:
         alat = audio.latent[0].to(self.device, torch.float32).contiguous()
         aout = torch.empty(alat.shape[0], self.AUDIO_OUT_CHANNELS, device=self.device, dtype=torch.float32)
         vs, as_ = self._sigma(video), self._sigma(audio)
-        nv.check(self._L.ltx2_dit_forward_av(self._h, nv.ptr(lat), nv.ptr(ts), n_ts, nv.ptr(vs), nv.ptr(alat), nv.ptr(ats), n_ats,
-                                              nv.ptr(as_), nv.ptr(out), nv.ptr(aout), nv.stream()))
+        args = (self._h, nv.ptr(lat), nv.ptr(ts), n_ts, nv.ptr(vs), nv.ptr(alat), nv.ptr(ats), n_ats, nv.ptr(as_), nv.ptr(out), nv.ptr(aout), nv.stream())
+        if flags is None:
+            nv.check(self._L.ltx2_dit_forward_av(*args))
+        else:
+            with self._stg_override(flags):
+                nv.check(self._L.ltx2_dit_forward_perturbed_av(*args))
         return out[None], aout[None]
 
     def _apply_context_masks(self, video: Modality, audio: Optional[Modality] = None) -> None:
@@ -704,6 +776,41 @@ class LTXModel:
         """Replay the graph captured by capture_guided_graph (it belongs to the VideoOnly context that ran the capture)."""
         self._replay("guided", "no guided graph captured")
 
+    # ------------------------------------------------------------------ spatio-temporal guidance on top of CFG (video-only engine)
+    def stg_step_(self, neg: Optional["LTXModel"], latent: torch.Tensor, video: Modality, sigma: float, sigma_next: float, cfg_scale: float,
+                  stg_scale: float, vel_perturbed: torch.Tensor, denoise_mask: Optional[torch.Tensor] = None,
+                  clean_latent: Optional[torch.Tensor] = None) -> None:
+        """In-place: latent (N, C) fp32 <- one Euler step under CFGGuider and STGGuider by ONE C call (ltx2_dit_stg_step): forward(self),
+        forward(neg) (neg None: no CFG), a perturbed forward on this context itself -- the self-attentions of set_stg_blocks skipped -- into
+        vel_perturbed (N, C fp32, the caller's scratch), then x0 x 3 + both guiders + post_process_latent + Euler in one kernel."""
+        pos, ng = self._video_pair(neg)
+        ts, n_ts, sg = pos._step_inputs(latent, video, sigma)
+        assert vel_perturbed.dtype == torch.float32 and vel_perturbed.is_contiguous() and vel_perturbed.shape == latent.shape
+        nv.check(pos._L.ltx2_dit_stg_step(pos._h, None if ng is None else ng._h, nv.ptr(latent), nv.ptr(ts), n_ts, nv.ptr(sg), nv.ptr(denoise_mask),
+                                          nv.ptr(clean_latent), nv.ptr(vel_perturbed), float(cfg_scale), float(stg_scale), float(sigma),
+                                          float(sigma_next), nv.stream()))
+
+    def capture_stg_graph(self, neg: Optional["LTXModel"], latent: torch.Tensor, sigmas: Sequence[float], cfg_scale: float, stg_scale: float,
+                          vel_perturbed: torch.Tensor, stg_cutoff: float = 1.0, denoise_mask: Optional[torch.Tensor] = None,
+                          clean_latent: Optional[torch.Tensor] = None) -> None:
+        """hipGraph-capture len(sigmas)-1 steps over `latent` (N, C fp32) as one linear chain (ltx2_dit_graph_capture_stg): step i is an STG
+        step while (i + 1) / n <= stg_cutoff, then the guided step (the plain one when neg is None).  Both contexts are prepared first
+        (per_token=True when a mask is given); the graph belongs to the positive VideoOnly context and replay_stg_graph() replays it.  The
+        tensors must stay alive while it is replayed."""
+        pos, ng = self._video_pair(neg)
+        assert pos._prep_key is not None and (ng is None or ng._prep_key is not None), "call prepare() on both contexts first"
+        assert vel_perturbed.dtype == torch.float32 and vel_perturbed.is_contiguous()
+        arr, n, st, n_el = self._capture_inputs(sigmas, (denoise_mask, clean_latent))
+        pos._graph_refs = (latent, denoise_mask, clean_latent, vel_perturbed, ng)
+        nv.check(pos._L.ltx2_dit_graph_capture_stg(pos._h, None if ng is None else ng._h, nv.ptr(latent), arr, n, nv.ptr(denoise_mask),
+                                                   n_el(denoise_mask), nv.ptr(clean_latent), n_el(clean_latent), nv.ptr(vel_perturbed),
+                                                   n_el(vel_perturbed), float(cfg_scale), float(stg_scale), float(stg_cutoff), st.cuda_stream))
+        self._graph_owner = ("stg", pos)
+
+    def replay_stg_graph(self) -> None:
+        """Replay the graph captured by capture_stg_graph (it belongs to the VideoOnly context that ran the capture)."""
+        self._replay("stg", "no STG graph captured")
+
     # ------------------------------------------------------------------ classifier-free guidance with a frozen audio latent (AudioVideo engine)
     def _guided_av_pair(self, neg: "LTXModel") -> Tuple["LTXModel", "LTXModel"]:
         if not isinstance(neg, LTXModel):
@@ -779,8 +886,9 @@ class LTXModel:
         self._replay("projected", "no projected graph captured")
 
     # ------------------------------------------------------------------ res_2s second-order sampling (video-only engine)
-    def _res2s_pair(self, neg: Optional["LTXModel"]) -> Tuple["LTXModel", Optional["LTXModel"]]:
-        """(positive, negative or None) VideoOnly contexts of a res_2s step: an AudioVideo model is used through its video twin."""
+    def _video_pair(self, neg: Optional["LTXModel"]) -> Tuple["LTXModel", Optional["LTXModel"]]:
+        """(positive, negative or None) VideoOnly contexts of a step that may run without guidance (res_2s, STG): an AudioVideo model is used
+        through its video twin."""
         if neg is None:
             return (self._video_twin() if self.is_av else self), None
         return self._guided_pair(neg)
@@ -793,7 +901,7 @@ class LTXModel:
         timesteps (those of the sub-sigma sqrt(sigma * sigma_next)), the combine kernel.  neg None: no guidance.  video_sub may be None
         only for the final step (sigma_next <= 0.001), which is one pair of evaluations and latent = d.  Both contexts are prepared by the
         caller (neg with the negative context)."""
-        pos, ng = self._res2s_pair(neg)
+        pos, ng = self._video_pair(neg)
         ts, n_ts, sg = pos._step_inputs(latent, video, sigma)
         ts_sub = sg_sub = None
         if video_sub is not None:
@@ -810,7 +918,7 @@ class LTXModel:
         """hipGraph-capture len(sigmas)-1 res_2s steps over `latent` (N, C fp32) as one linear chain (ltx2_dit_graph_capture_res2s).  Both
         contexts are prepared first (per_token=True when a mask is given); the graph belongs to the positive VideoOnly context and
         replay_res2s_graph() replays it.  The tensors must stay alive while it is replayed."""
-        pos, ng = self._res2s_pair(neg)
+        pos, ng = self._video_pair(neg)
         assert pos._prep_key is not None and (ng is None or ng._prep_key is not None), "call prepare() on both contexts first"
         arr, n, st, n_el = self._capture_inputs(sigmas, (denoise_mask, clean_latent))
         pos._graph_refs = (latent, denoise_mask, clean_latent, ng)

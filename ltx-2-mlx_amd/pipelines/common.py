@@ -215,16 +215,24 @@ def _with_latent(state: LatentState, lat: torch.Tensor) -> LatentState:
 def joint_denoise_loop(transformer, is_av_model: bool, video_state: LatentState, audio_state: Optional[LatentState], sigmas,
                        video_context: torch.Tensor, audio_context: Optional[torch.Tensor], stepper, callback=None,
                        use_hip_graph: bool = False, *, negative_video_context: Optional[torch.Tensor] = None,
-                       negative_audio_context: Optional[torch.Tensor] = None, video_guider=None, audio_guider=None):
+                       negative_audio_context: Optional[torch.Tensor] = None, video_guider=None, audio_guider=None, stg_guider=None,
+                       stg_perturbations=None, stg_cutoff: float = 1.0):
     """The guidance-free sampling loop every pipeline here shares (reference pipelines/distilled.py:198-271 and the
     `need_cfg == False` branch of pipelines/one_stage.py:466-568 / :224-330).  Per step and modality:
     Modality(timesteps = denoise_mask * sigma) -> X0Model -> post_process_latent -> EulerDiffusionStep.
     Two equivalent executions: (a) API-faithful, one X0Model call + stepper.step per step; (b) hipGraph replay of the fused
     steps (ltx2_dit_graph_*) when the denoise masks are uniform and no callback needs intermediate states.
+    stg_guider / stg_perturbations / stg_cutoff (pipelines/one_stage.py:289-297, :516-526): while (step + 1) / n <= stg_cutoff a further
+    evaluation of the positive prompt with `stg_perturbations` (a BatchedPerturbationConfig) and STGGuider.guide on the guided VIDEO
+    prediction; the perturbed audio output is dropped.  Always the eager execution.
     `transformer` is an X0Model; returns (video_state, audio_state)."""
     sig = [float(s) for s in sigmas]
     n = len(sig) - 1
     model = transformer.velocity_model
+    stg = stg_guider is not None and stg_guider.enabled() and stg_perturbations is not None
+    if stg and use_hip_graph:
+        _note_eager_once("STG guidance on the eager loop (a projected video guider, or joint audio+video)")
+        use_hip_graph = False
     joint = is_av_model and audio_state is not None
     if joint and audio_context is None:
         raise ValueError("AudioVideo model: audio_encoding (the audio text context) is required")
@@ -265,8 +273,9 @@ def joint_denoise_loop(transformer, is_av_model: bool, video_state: LatentState,
         return _with_latent(video_state, lat), (_with_latent(audio_state, alat) if joint else audio_state)
     for i in range(n):
         vm = modality_from_state(video_state, video_context, sig[i], uniform=unif[0])
+        am = audio_modality_from_state(audio_state, audio_context, sig[i], uniform=unif[1]) if joint else None
         if joint:
-            vx0, ax0 = transformer(vm, audio_modality_from_state(audio_state, audio_context, sig[i], uniform=unif[1]))
+            vx0, ax0 = transformer(vm, am)
         else:
             out = transformer(vm)
             vx0, ax0 = (out[0] if isinstance(out, tuple) else out), None
@@ -278,6 +287,9 @@ def joint_denoise_loop(transformer, is_av_model: bool, video_state: LatentState,
             else:
                 nvx0 = neg(nvm)
             vx0 = video_guider.guide(vx0, nvx0) if video_guider is not None else vx0
+        if stg and (i + 1) / n <= stg_cutoff:
+            pout = transformer(vm, am, perturbations=stg_perturbations) if joint else transformer(vm, perturbations=stg_perturbations)
+            vx0 = stg_guider.guide(vx0, pout[0] if isinstance(pout, tuple) else pout)
         vx0 = post_process_latent(vx0, video_state.denoise_mask, video_state.clean_latent)
         video_state = video_state.replace(latent=stepper.step(sample=video_state.latent, denoised_sample=vx0, sigmas=sig, step_index=i))
         if joint:
@@ -317,6 +329,55 @@ def guided_denoise_loop(transformer, video_state: LatentState, sigmas, context: 
             st = video_state.replace(latent=lat[None])
             model.guided_step_(neg, lat, modality_from_state(st, context, sig[i], uniform=uniform), sig[i], sig[i + 1], guider.scale,
                                denoise_mask=mask, clean_latent=clean)
+            if callback:
+                callback(i + 1, n)
+    return _with_latent(video_state, lat)
+
+
+def stg_denoise_loop(transformer, video_state: LatentState, sigmas, context: torch.Tensor, negative_context: Optional[torch.Tensor], guider,
+                     stg_guider, stg_blocks: Optional[List[int]], stg_cutoff: float, stepper, callback=None, use_hip_graph: bool = True) -> LatentState:
+    """guided_denoise_loop with spatio-temporal guidance on top (pipelines/one_stage.py:267-326): while (step + 1) / n <= stg_cutoff a third
+    evaluation of the positive prompt with the video self-attention of `stg_blocks` (None: every block) skipped, and STGGuider.guide on the
+    CFG-guided prediction.  With a plain CFGGuider, or a guider that is not enabled (then no negative evaluation), every step is ONE C call
+    -- the two or three evaluations, then x0 x 3 + both guiders + post_process_latent + Euler in one kernel (LTXModel.stg_step_) -- and with
+    no callback and fewer than 64 steps the whole loop is one captured graph.  The perturbed pass runs on the positive context itself.  Any
+    other enabled guider class goes through joint_denoise_loop's eager STG path; an STG guider that is not enabled through
+    guided_denoise_loop.  `transformer` is an X0Model; an AudioVideo model is used through its video twin.  Returns the video state."""
+    from ..components.guiders import CFGGuider
+    from ..components.perturbations import create_batched_stg_config
+    model = transformer.velocity_model
+    if stg_guider is None or not stg_guider.enabled():
+        return guided_denoise_loop(transformer, video_state, sigmas, context, negative_context, guider, stepper, callback, use_hip_graph)
+    cfg = guider is not None and guider.enabled()
+    if cfg and type(guider) is not CFGGuider:
+        return joint_denoise_loop(transformer, model.is_av, video_state, None, sigmas, context, None, stepper, callback, use_hip_graph,
+                                  negative_video_context=negative_context, video_guider=guider, stg_guider=stg_guider,
+                                  stg_perturbations=create_batched_stg_config(1, blocks=stg_blocks), stg_cutoff=stg_cutoff)[0]
+    if cfg and negative_context is None:
+        raise ValueError("guidance needs the negative prompt's encoding")
+    sig = [float(s) for s in sigmas]
+    n = len(sig) - 1
+    model, uniform, lat, mask, clean = _video_loop_inputs(model, video_state)
+    model.set_stg_blocks(stg_blocks)
+    neg = model.clone_sharing_weights() if cfg else None
+    model.prepare(context, video_state.positions, per_token=not uniform)
+    if cfg:
+        neg.prepare(negative_context, video_state.positions, per_token=not uniform)
+    cfg_scale = guider.scale if cfg else 1.0
+    vel_p = torch.empty_like(lat)
+    if use_hip_graph and callback is None and n < 64:
+        capture_and_replay(lambda: model.capture_stg_graph(neg, lat, sig, cfg_scale, stg_guider.scale, vel_p, stg_cutoff, denoise_mask=mask,
+                                                           clean_latent=clean), model.replay_stg_graph)
+    else:
+        for i in range(n):
+            st = video_state.replace(latent=lat[None])
+            vm = modality_from_state(st, context, sig[i], uniform=uniform)
+            if (i + 1) / n <= stg_cutoff:
+                model.stg_step_(neg, lat, vm, sig[i], sig[i + 1], cfg_scale, stg_guider.scale, vel_p, denoise_mask=mask, clean_latent=clean)
+            elif cfg:
+                model.guided_step_(neg, lat, vm, sig[i], sig[i + 1], cfg_scale, denoise_mask=mask, clean_latent=clean)
+            else:
+                model.denoise_step_(lat, vm, sig[i], sig[i + 1], denoise_mask=mask, clean_latent=clean)
             if callback:
                 callback(i + 1, n)
     return _with_latent(video_state, lat)

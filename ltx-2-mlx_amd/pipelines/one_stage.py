@@ -13,7 +13,13 @@ weights) and combine the two predictions with CFGGuider or, for `rescale_scale >
 `guider_override` (one of CFGGuider, CFGStarRescalingGuider, LtxAPGGuider, LegacyStatefulAPGGuider) becomes the video guider; audio keeps its
 standard one (:795-805).  Without an audio state an enabled projected guider runs through pipelines.common.projected_denoise_loop.
 
-Outside the MI355X hot path, rejected with NotImplementedError: STG guidance (`stg_scale`), any other `guider_override`, the Heun sampler, GE velocity correction, cross-attention scaling, the temporal upscaler.
+Spatio-temporal guidance: `stg_scale` > 0 adds, while (step + 1) / steps <= `stg_cutoff`, a third evaluation of the positive prompt with the video
+self-attention of `stg_blocks` (None: every block) skipped, and STGGuider pushes the guided video prediction away from it (:284-297, :516-526).
+Without an audio state and with a plain CFGGuider (or none enabled) the loop is pipelines.common.stg_denoise_loop: one C call per step, one
+captured graph per loop.  With CFG* (the config default) or a projected override, and on the joint audio+video branch, it is the eager loop:
+three evaluations, the guiders in torch.  Only the video is STG-guided.
+
+Outside the MI355X hot path, rejected with NotImplementedError: any other `guider_override`, the Heun sampler, GE velocity correction, cross-attention scaling, the temporal upscaler.
 With `audio_enabled`, the audio waveform is returned when an audio_decoder and a vocoder are given (model/audio_vae/), the audio
 LATENT otherwise.
 """
@@ -25,13 +31,13 @@ from typing import Callable, List, Optional, Tuple, Union
 import torch
 
 from ..components import (AudioPatchifier, CFGGuider, CFGStarRescalingGuider, EulerDiffusionStep, LegacyStatefulAPGGuider, LtxAPGGuider, LTX2Scheduler,
-                          VideoLatentPatchifier)
+                          STGGuider, VideoLatentPatchifier, create_batched_stg_config)
 from ..conditioning.tools import AudioLatentTools
 from ..model.transformer import LTXModel, X0Model
 from ..model.video_vae import SimpleVideoDecoder, TilingConfig
 from ..types import AudioLatentShape, VideoPixelShape
 from .common import (ImageCondition, as_x0model, auto_tiling_config, conditioned_initial_state, create_image_conditionings, decode_video,
-                     final_latent, joint_denoise_loop, projected_denoise_loop, projected_guider_args, reset_guider, seeded_noiser, video_tools_for)
+                     final_latent, joint_denoise_loop, projected_denoise_loop, projected_guider_args, reset_guider, seeded_noiser, stg_denoise_loop, video_tools_for)
 
 
 @dataclass
@@ -129,7 +135,17 @@ class OneStagePipeline:
             raise ValueError("audio_enabled needs an AudioVideo transformer")
         if initial_audio_latent is not None and not internal_audio_active:
             raise ValueError("initial_audio_latent needs an AudioVideo transformer (the audio branch carries the frozen latent)")
-        self._require_no_guidance(stg_scale, guider_override, ge_gamma, sampler, temporal_upscaler, cross_attn_scale)
+        # STG is validated here; the gate below then sees the remaining options (it refuses every stg_scale > 0 on its own)
+        stg_guider = None
+        if stg_scale > 0:
+            layers = self.transformer.velocity_model.num_layers
+            bad = [b for b in (stg_blocks or []) if not 0 <= int(b) < layers]
+            if bad:
+                raise ValueError(f"stg_blocks {bad} out of range: the model has {layers} layers")
+            if not 0.0 <= stg_cutoff <= 1.0:
+                raise ValueError(f"stg_cutoff={stg_cutoff} must lie in [0, 1]")
+            stg_guider = STGGuider(scale=stg_scale)
+        self._require_no_guidance(0.0, guider_override, ge_gamma, sampler, temporal_upscaler, cross_attn_scale)
 
         dev = self.transformer.velocity_model.device
         noiser = seeded_noiser(dev, config.seed)
@@ -164,7 +180,12 @@ class OneStagePipeline:
         if need_cfg and (negative_encoding is None or (internal_audio_active and negative_audio_encoding is None)):
             raise ValueError("cfg_scale / audio_cfg_scale != 1 need the negative prompt's encoding(s)")
         nactx = negative_audio_encoding.to(dev) if (need_cfg and internal_audio_active) else None
-        if guider_override is not None and audio_state is None and video_guider.enabled() and projected_guider_args(video_guider) is not None:
+        if stg_guider is not None and audio_state is None and (type(video_guider) is CFGGuider or not video_guider.enabled()):
+            # forward x 2 or 3 and one kernel per step, on the device
+            video_state = stg_denoise_loop(self.transformer, video_state, sigmas, positive_encoding.to(dev),
+                                           negative_encoding.to(dev) if video_guider.enabled() else None, video_guider, stg_guider, stg_blocks, stg_cutoff,
+                                           self.diffusion_step, callback, config.use_hip_graph)
+        elif stg_guider is None and guider_override is not None and audio_state is None and video_guider.enabled() and projected_guider_args(video_guider) is not None:
             # the override's sums and step on the device; the default guiders stay on the eager loop below
             video_state = projected_denoise_loop(self.transformer, video_state, sigmas, positive_encoding.to(dev), negative_encoding.to(dev),
                                                  video_guider, self.diffusion_step, callback, config.use_hip_graph)
@@ -172,7 +193,9 @@ class OneStagePipeline:
             video_state, audio_state = joint_denoise_loop(self.transformer, self.is_av_model, video_state, audio_state, sigmas,
                                                           positive_encoding.to(dev), actx, self.diffusion_step, callback, config.use_hip_graph,
                                                           negative_video_context=negative_encoding.to(dev) if need_cfg else None,
-                                                          negative_audio_context=nactx, video_guider=video_guider, audio_guider=audio_guider)
+                                                          negative_audio_context=nactx, video_guider=video_guider, audio_guider=audio_guider,
+                                                          **(dict(stg_guider=stg_guider, stg_perturbations=create_batched_stg_config(1, blocks=stg_blocks),
+                                                                  stg_cutoff=stg_cutoff) if stg_guider is not None else {}))
 
         video = decode_video(final_latent(video_tools, video_state), self.video_decoder, config._get_tiling_config())
         audio = None

@@ -6,8 +6,8 @@ scripts/generate.py (argparse block :2364-2641, `generate_video` :933-997) for t
 standard single-stage distilled loop (reference :1764-1984) followed by `decode_latent` (:2080-2091).
 Gemma-3 encodes the prompt on the GPU when `--gemma-path` holds its weights (model/text_encoder/gemma3.py; reference
 encode_with_gemma :340-486, encode_av_gemma_batch :511-640; an LTX-2.3 checkpoint gets the V2 text encoder, create_av_text_encoder_v2_from_checkpoint
-:548-551).  Out of this path (and rejected with a clear message): STG guidance,
-CFG in the video-only loop, the dev model's `--pipeline two-stage`.
+:548-551).  `--stg-scale S [--stg-blocks ... --stg-cutoff F]` adds spatio-temporal guidance on the av route (OneStagePipeline).  Out of this path (and rejected
+with a clear message): STG guidance on every other route, CFG in the video-only loop, the dev model's `--pipeline two-stage`.
 `generate_video` resolves its arguments once (`_resolve_request`: every refusal, before a model is loaded), loads the text encoding, the transformer and the VAE decoder, and
 runs ONE route, each a function of its own: hq_av (`--ti2vid-hq-audio --spatial-upscaler-weights W`: TI2VidHQPipeline with sound, the joint res_2s loop on the AudioVideo model), a2vid (`--a2vid-two-stage --audio FILE --spatial-upscaler-weights W`: the two-stage audio-to-video pipeline), retake (`--retake CLIP`), keyframe (`--pipeline keyframe-interpolation --keyframe path:frame[:strength]`), hq (`--ti2vid-hq`), ic_lora
 (`--pipeline ic-lora --control-video V` and / or `--image`), two_stage (`--two-stage-distilled --spatial-upscaler-weights W`; with `--generate-audio` on the AudioVideo transformer), av
@@ -25,6 +25,7 @@ import os
 import sys
 import time
 from types import SimpleNamespace
+from typing import List, Optional
 
 import numpy as np
 import torch
@@ -622,14 +623,14 @@ _ROUTE_EXCLUDES = {
               "alone and ends with its own x2 spatial stage"),
 }
 # route -> the _OUT_OF_PATH_DEFAULTS arguments that route takes itself.  apg_scale: the routes whose guided loop takes a guider (the AudioVideo route as
-# OneStagePipeline's guider_override, keyframe stage 1, retake's guided mode)
+# OneStagePipeline's guider_override, keyframe stage 1, retake's guided mode).  stg_scale: OneStagePipeline alone (the AudioVideo route)
 _ROUTE_OWNS = {"keyframe": ("keyframes", "apg_scale"), "hq": ("distilled_lora", "keyframes"),
-               "ic_lora": ("control_video", "save_control", "keyframes", "ic_lora_weights"), "retake": ("apg_scale",), "av": ("apg_scale",), "a2vid": ("distilled_lora",),
+               "ic_lora": ("control_video", "save_control", "keyframes", "ic_lora_weights"), "retake": ("apg_scale",), "av": ("apg_scale", "stg_scale"), "a2vid": ("distilled_lora",),
                "hq_av": ("distilled_lora",)}
 
 
 def _owning_route(r):
-    """The route whose _ROUTE_OWNS entry decides about apg_scale, before the checkpoint has been looked at: the named one (a distilled retake runs
+    """The route whose _ROUTE_OWNS entry decides about apg_scale and stg_scale, before the checkpoint has been looked at: the named one (a distilled retake runs
     without guidance and owns no guider), else "av" when OneStagePipeline will run (generate_audio or an LTX-2.3 checkpoint, without two_stage_distilled)."""
     if r.route == "retake":
         return None if r.model_variant == "distilled" else "retake"
@@ -653,6 +654,19 @@ def _apg_guider(r):
         guider = LtxAPGGuider(scale=r.apg_scale, eta=r.apg_eta, norm_threshold=r.apg_norm_threshold)
     print("  APG guidance enabled (replaces standard CFG)")
     return guider
+
+
+def _check_stg(r):
+    """stg_scale > 0 (the reference enables STG for nothing else, :1246): the mode that is built, block indices of this model, a cutoff that is a fraction of the steps."""
+    if not r.stg_scale > 0:
+        return
+    if r.stg_mode != "video":
+        raise NotImplementedError(f"stg_mode={r.stg_mode!r}: STG skips the video self-attention (the reference prints the mode and does the same); leave it at 'video'")
+    bad = [b for b in (r.stg_blocks or []) if not 0 <= int(b) < r.num_layers]
+    if bad:
+        raise ValueError(f"stg_blocks {bad} out of range: the model has {r.num_layers} layers")
+    if not 0.0 <= r.stg_cutoff <= 1.0:
+        raise ValueError(f"stg_cutoff={r.stg_cutoff} must lie in [0, 1]: the fraction of the steps that STG guides")
 
 
 def _refuse_combinations(r):
@@ -778,7 +792,7 @@ def _resolve_request(kw: dict):
         _resolve_retake(r)
     # Gemma encodes the prompt (and the negative prompt) when its weights are there and no pre-computed encoding is given
     r.gemma_encodes = bool(r.use_gemma and not (r.embedding_path or r.text_features_path) and r.gemma_path and os.path.exists(r.gemma_path))
-    owns = _ROUTE_OWNS.get(_owning_route(r) if r.apg_scale != 1.0 else r.route, ())
+    owns = _ROUTE_OWNS.get(_owning_route(r) if (r.apg_scale != 1.0 or r.stg_scale != 0.0) else r.route, ())
     for k, default in _OUT_OF_PATH_DEFAULTS.items():
         if k in owns or (k == "negative_prompt" and r.gemma_encodes):
             continue
@@ -787,6 +801,7 @@ def _resolve_request(kw: dict):
             raise NotImplementedError(f"{k}={v!r} is outside the MI355X hot path (see DESIGN.md); leave it at its default {default!r}")
     if r.pipeline_type not in _PIPELINES_KNOWN:
         raise ValueError(f"unknown pipeline_type {r.pipeline_type!r}; the reference knows {_PIPELINES_KNOWN}")
+    _check_stg(r)
     if r.pipeline_type not in _PIPELINES_BUILT and r.route not in _RESOLVE_ROUTE:
         raise NotImplementedError(f"pipeline_type={r.pipeline_type!r} is outside the MI355X hot path (see DESIGN.md): 'two-stage' is the dev "
                                   "model's CFG stage 1 + distilled-LoRA stage 2; for the distilled two-stage DistilledPipeline pass "
@@ -829,6 +844,8 @@ def _resolve_request(kw: dict):
         r.audio_cfg_scale = 1.0 if r.model_variant == "distilled" else 7.0
     if r.rescale_scale is None:
         r.rescale_scale = 0.0 if r.model_variant == "distilled" else 0.7
+    if r.stg_scale > 0:
+        print(f"STG guidance: scale={r.stg_scale}, mode={r.stg_mode}")           # the settings banner's line (reference :1031-1032); the second one: _run_av
     r.apg_guider = _apg_guider(r)
     r.negative_encoding = r.negative_audio_encoding = None
     if r.embedding_path and os.path.exists(r.embedding_path):
@@ -1288,11 +1305,15 @@ def _run_av(r, s):
         print(f"  Encoding audio: {r.audio_path}")
         given_audio = encode_audio_for_video(r.audio_path, r.num_frames, av_config.fps, r.weights_path if r.have_ckpt else None, device=r.device,
                                              seed=r.seed + 5, start_time=r.audio_start_time, max_duration=r.audio_max_duration)
+    stg = {}
+    if r.stg_scale > 0:
+        print(f"  STG guidance enabled (scale={r.stg_scale})")
+        stg = dict(stg_scale=r.stg_scale, stg_blocks=r.stg_blocks, stg_cutoff=r.stg_cutoff)
     print(f"[5/5] Running audio-video generation ({r.num_steps} steps)...")
     frames, audio_latent = _timed_run("audio-video pipeline", lambda: av_pipeline(
         positive_encoding=s.text_encoding, negative_encoding=s.negative_encoding if r.need_cfg else None, config=av_config, images=images,
         positive_audio_encoding=s.text_audio_encoding, negative_audio_encoding=s.negative_audio_encoding if r.need_cfg else None,
-        initial_audio_latent=given_audio[0] if given_audio else None, **(dict(guider_override=r.apg_guider) if r.apg_guider is not None else {})))
+        initial_audio_latent=given_audio[0] if given_audio else None, **(dict(guider_override=r.apg_guider) if r.apg_guider is not None else {}), **stg))
     if given_audio:
         # the frozen latent is kept; the ORIGINAL audio goes into the mp4 (the reference returns the original waveform, not a decode)
         import shutil
@@ -1451,6 +1472,8 @@ def generate_video(
     negative_prompt=None,
     *,
     # MI355X additions (keyword-only; the reference has no counterpart)
+    stg_blocks: Optional[List[int]] = None,        # with stg_scale: what OneStagePipeline takes beside it (the reference's CLI leaves them at these defaults)
+    stg_cutoff: float = 1.0,
     use_hip_graph: bool = True,
     num_layers: int = 48,
     num_heads: int = 32,
@@ -1592,6 +1615,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--retake-start", type=float, default=0.0, help="start of the regenerated window in seconds (inclusive)")
     p.add_argument("--retake-end", type=float, default=None, help="end of the regenerated window in seconds (exclusive); default: the end of the clip")
     p.add_argument("--retake-keep-source", action="store_true", help="put the source's own frames back outside the window (4-frame fade outside it)")
+    p.add_argument("--stg-blocks", type=int, nargs="+", default=None, help="with --stg-scale: the blocks whose video self-attention the perturbed pass skips (default: all)")
+    p.add_argument("--stg-cutoff", type=float, default=1.0, help="with --stg-scale: STG guides the first fraction of the steps, (step + 1) / steps <= cutoff")
     return p
 
 
@@ -1623,7 +1648,8 @@ def kwargs_from_args(a) -> dict:
         fp8_resident=a.fp8_resident, fp8_compute=a.fp8_compute, model_version=a.model_version, compute_dtype="bfloat16" if a.bf16 else None, num_layers=a.layers, num_heads=a.heads,
         vae_base_channels=a.vae_base_channels, save_mp4=not a.no_video_file, decode_audio=a.decode_audio,
         audio_path=a.audio, audio_start_time=a.audio_start, audio_max_duration=a.audio_duration, a2vid_two_stage=a.a2vid_two_stage, ti2vid_hq_audio=a.ti2vid_hq_audio,
-        retake_video=a.retake, retake_start_time=a.retake_start, retake_end_time=a.retake_end, retake_composite=a.retake_keep_source)
+        retake_video=a.retake, retake_start_time=a.retake_start, retake_end_time=a.retake_end, retake_composite=a.retake_keep_source,
+        stg_blocks=a.stg_blocks, stg_cutoff=a.stg_cutoff)
 
 
 def main(argv=None):
