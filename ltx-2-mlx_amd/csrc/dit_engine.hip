@@ -1255,126 +1255,95 @@ int cond_modality(ltx2_dit* c, int k, const Cond& cd, const float* sigma_i, ModI
     return LTX2_OK;
 }
 
-// Classifier-free guidance on the VideoOnly engine (keyframe interpolation's stage 1): two evaluations per step, the positive prompt through `c`
-// and the negative one through `neg` (a second context over the same weights), then ONE element-wise pass.  Everything goes onto the caller's
-// stream in order: each evaluation already fills the device, so a captured loop is a linear chain.
-int guided_ready(ltx2_dit* c, ltx2_dit* neg, int n_ts, const char* who) {
-    LTX2_CHECK_ARG(c && neg, "%s: null context", who);
+// ---- The shared path of every guided and every second-order step -------------------------------------------------------------------------------------
+// A step entry, or the capture entry of a loop of such steps, asks step_ready() once, before anything is enqueued.  The step then evaluates its inputs
+// through the positive prompt's context `c` and, where there is one, through `neg` (the negative prompt: a second context over the same weights, with its
+// own text K / V) by evaluate(), and runs its one or two element-wise passes (csrc/sampler.hip).  Everything goes onto the caller's stream in order: each
+// evaluation already fills the device, so a captured loop is a linear chain.  VideoOnly contexts (an AudioVideo model's video twin) have one modality,
+// in[0] / io[0]; AudioVideo contexts two.
+
+// n_ts[k]: the timesteps the step passes for modality k.  neg may be NULL: no guidance (the entries that need one check that themselves).
+int step_ready(ltx2_dit* c, ltx2_dit* neg, bool want_av, const int n_ts[2], const char* who) {
+    LTX2_CHECK_ARG(c, "%s: null context", who);
     LTX2_CHECK_ARG(c != neg, "%s: the negative prompt needs a context of its own (ctx == neg)", who);
-    LTX2_CHECK_ARG(!c->av && !neg->av, "%s: guidance runs on VideoOnly contexts (the video twin of an AudioVideo model)", who);
-    LTX2_CHECK_ARG(c->prepared && neg->prepared, "%s: ltx2_dit_prepare has not been called on both contexts", who);
-    LTX2_CHECK_ARG(c->m[0].N == neg->m[0].N && c->m[0].Cout == neg->m[0].Cout, "%s: the contexts differ: %d tokens x %d channels against %d x %d", who,
-                   c->m[0].N, c->m[0].Cout, neg->m[0].N, neg->m[0].Cout);
-    LTX2_CHECK_ARG(n_ts == 1 || (c->per_token && neg->per_token), "%s: a workspace was not bound for per-token timesteps", who);
+    LTX2_CHECK_ARG(c->av == want_av && (!neg || neg->av == want_av), "%s: %s", who,
+                   want_av ? "every context must be AudioVideo (the VideoOnly engine has the entry without _av)"
+                           : "the step runs on VideoOnly contexts (the video twin of an AudioVideo model)");
+    LTX2_CHECK_ARG(c->prepared && (!neg || neg->prepared), "%s: ltx2_dit_prepare%s has not been called on every context", who, want_av ? "_av" : "");
+    const int nm = want_av ? 2 : 1;
+    for (int k = 0; neg && k < nm; ++k)
+        LTX2_CHECK_ARG(c->m[k].N == neg->m[k].N && c->m[k].Cout == neg->m[k].Cout, "%s: the contexts differ in modality %d: %d tokens x %d channels against %d x %d",
+                       who, k, c->m[k].N, c->m[k].Cout, neg->m[k].N, neg->m[k].Cout);
+    bool per_token = false;
+    for (int k = 0; k < nm; ++k) {
+        LTX2_CHECK_ARG(n_ts[k] == 1 || n_ts[k] == c->m[k].N, "%s: n_timesteps=%d of modality %d must be 1 or %s=%d", who, n_ts[k], k, k ? "Na" : "N", c->m[k].N);
+        per_token = per_token || n_ts[k] != 1;
+    }
+    LTX2_CHECK_ARG(!per_token || (c->per_token && (!neg || neg->per_token)), "%s: a workspace was not bound for per-token timesteps", who);
     return LTX2_OK;
 }
 
-// One evaluation of `latent` at (ts, sigma) through c into c's velocity buffer and, with a negative context, a second through neg into neg's
-int evaluate_pair(ltx2_dit* c, ltx2_dit* neg, const float* latent, const float* ts, int n_ts, const float* sigma, hipStream_t st) {
-    const ModIn pos[1] = {{latent, ts, n_ts, sigma, c->m[0].vel}};
-    TRY(forward(c, pos, st));
-    if (!neg) return LTX2_OK;
-    const ModIn ngt[1] = {{latent, ts, n_ts, sigma, neg->m[0].vel}};
-    return forward(neg, ngt, st);
+// One evaluation of in[k] = (latent, timesteps, sigma) of every modality through c into c's velocity buffers and, with a negative context, a second
+// through neg into neg's.  rewind_events: forward()'s; only an AudioVideo forward takes events, so inside a capture those loops pass i == 0.
+int evaluate(ltx2_dit* c, ltx2_dit* neg, const ModIn* in, hipStream_t st, bool rewind_events = true) {
+    ltx2_dit* const both[2] = {c, neg};
+    for (ltx2_dit* e : both) {
+        if (!e) continue;
+        ModIn ev[2] = {};
+        for (int k = 0; k < (c->av ? 2 : 1); ++k) {
+            ev[k] = in[k];
+            ev[k].velocity = e->m[k].vel;
+        }
+        TRY(forward(e, ev, st, rewind_events));
+    }
+    return LTX2_OK;
 }
 
-// in: (latent, timesteps, sigma) of the step, read by both contexts; io: the latent it updates and its conditioning
-int guided_step(ltx2_dit* c, ltx2_dit* neg, const ModIn& in, const StepIo& io, float cfg_scale, float sigma, float sigma_next, hipStream_t st) {
+// What the step entries build from their arguments: (latent, timesteps, sigma) of one modality and the latent the step updates with its conditioning
+struct StepArgs {
+    ModIn in;
+    StepIo io;
+};
+
+StepArgs step_args(float* latent, const float* ts, int n_ts, const float* sigma_dev, const float* mask, const float* clean) {
+    return {{latent, ts, n_ts, sigma_dev ? sigma_dev : ts, nullptr}, {latent, mask, clean, nullptr}};
+}
+
+// What every Euler-type step checks of its scalars and its nm conditionings
+int step_check(float sigma, const StepIo* io, int nm, const char* who) {
     LTX2_CHECK_ARG(sigma != 0.f, "Sigma can't be 0.0");
-    LTX2_CHECK_ARG((io.mask == nullptr) == (io.clean == nullptr), "dit_guided_step: mask and clean go together");
+    for (int k = 0; k < nm; ++k) LTX2_CHECK_ARG((io[k].mask == nullptr) == (io[k].clean == nullptr), "%s: mask and clean go together", who);
+    return LTX2_OK;
+}
+
+// Classifier-free guidance (keyframe interpolation's stage 1; on AudioVideo contexts audio-to-video, reference pipelines/a2vid_two_stage.py:225-271): two
+// evaluations per step, then ONE element-wise pass over modality 0.  An audio latent in[1] is evaluated by both contexts and never stepped.
+// io: the video latent the step updates and its conditioning
+int guided_step(ltx2_dit* c, ltx2_dit* neg, const ModIn* in, const StepIo& io, float cfg_scale, float sigma, float sigma_next, hipStream_t st,
+                bool rewind_events = true) {
+    TRY(step_check(sigma, &io, 1, "dit_guided_step"));
     const Mod& m = c->m[0];
-    TRY(evaluate_pair(c, neg, in.latent, in.ts, in.n_ts, in.sigma, st));
-    return guided_euler_step_launch(in.latent, m.vel, neg->m[0].vel, in.ts, in.n_ts == 1 ? 0 : 1, io.mask, io.clean, cfg_scale, sigma, sigma_next, io.latent,
-                                    m.N, m.Cout, st);
+    TRY(evaluate(c, neg, in, st, rewind_events));
+    return guided_euler_step_launch(in[0].latent, m.vel, neg->m[0].vel, in[0].ts, in[0].n_ts == 1 ? 0 : 1, io.mask, io.clean, cfg_scale, sigma, sigma_next,
+                                    io.latent, m.N, m.Cout, st);
 }
 
 // Spatio-temporal guidance on top (pipelines/one_stage.py:284-297): a third evaluation, on c ITSELF with the self-attentions of c->stg[0] skipped (no third
 // context: its text K / V would be a second copy of c's), into the caller's scratch; then the one element-wise pass.  neg may be NULL: no CFG.
-int stg_ready(ltx2_dit* c, ltx2_dit* neg, int n_ts, const char* who) {
-    if (neg) return guided_ready(c, neg, n_ts, who);
-    LTX2_CHECK_ARG(c, "%s: null context", who);
-    LTX2_CHECK_ARG(!c->av, "%s: the STG step runs on VideoOnly contexts (the video twin of an AudioVideo model)", who);
-    LTX2_CHECK_ARG(c->prepared, "%s: ltx2_dit_prepare has not been called", who);
-    LTX2_CHECK_ARG(n_ts == 1 || c->per_token, "%s: a workspace was not bound for per-token timesteps", who);
-    return LTX2_OK;
-}
-
 int stg_step(ltx2_dit* c, ltx2_dit* neg, const ModIn& in, const StepIo& io, float* vel_perturbed, float cfg_scale, float stg_scale, float sigma,
              float sigma_next, hipStream_t st) {
-    LTX2_CHECK_ARG(sigma != 0.f, "Sigma can't be 0.0");
-    LTX2_CHECK_ARG((io.mask == nullptr) == (io.clean == nullptr), "dit_stg_step: mask and clean go together");
+    TRY(step_check(sigma, &io, 1, "dit_stg_step"));
     LTX2_CHECK_ARG(vel_perturbed, "dit_stg_step: vel_perturbed (an [N][out_channels] fp32 scratch) is required");
     const Mod& m = c->m[0];
-    TRY(evaluate_pair(c, neg, in.latent, in.ts, in.n_ts, in.sigma, st));
+    TRY(evaluate(c, neg, &in, st));
     const ModIn pert[1] = {{in.latent, in.ts, in.n_ts, in.sigma, vel_perturbed}};
     TRY(forward(c, pert, st, true, true));
     return stg_euler_step_launch(in.latent, m.vel, neg ? neg->m[0].vel : nullptr, vel_perturbed, in.ts, in.n_ts == 1 ? 0 : 1, io.mask, io.clean, cfg_scale,
                                  stg_scale, sigma, sigma_next, io.latent, m.N, m.Cout, st);
 }
 
-// The same on the AudioVideo engine with the audio latent frozen (audio-to-video; reference pipelines/a2vid_two_stage.py:225-271): both contexts
-// evaluate both modalities, the guidance and the Euler update touch the video latent alone.  Every count is checked here, before the first launch.
-int guided_ready_av(ltx2_dit* c, ltx2_dit* neg, int n_v_ts, int n_a_ts, const char* who) {
-    LTX2_CHECK_ARG(c && neg, "%s: null context", who);
-    LTX2_CHECK_ARG(c != neg, "%s: the negative prompt needs a context of its own (ctx == neg)", who);
-    LTX2_CHECK_ARG(c->av && neg->av, "%s: both contexts must be AudioVideo (the VideoOnly engine has ltx2_dit_guided_step)", who);
-    LTX2_CHECK_ARG(c->prepared && neg->prepared, "%s: ltx2_dit_prepare_av has not been called on both contexts", who);
-    LTX2_CHECK_ARG(c->m[0].N == neg->m[0].N && c->m[1].N == neg->m[1].N && c->m[0].Cout == neg->m[0].Cout,
-                   "%s: the contexts differ: %d video + %d audio tokens x %d channels against %d + %d x %d", who, c->m[0].N, c->m[1].N, c->m[0].Cout,
-                   neg->m[0].N, neg->m[1].N, neg->m[0].Cout);
-    LTX2_CHECK_ARG((n_v_ts == 1 || n_v_ts == c->m[0].N) && (n_a_ts == 1 || n_a_ts == c->m[1].N),
-                   "%s: n_v_timesteps=%d must be 1 or N=%d, n_a_timesteps=%d must be 1 or Na=%d", who, n_v_ts, c->m[0].N, n_a_ts, c->m[1].N);
-    LTX2_CHECK_ARG((n_v_ts == 1 && n_a_ts == 1) || (c->per_token && neg->per_token), "%s: a workspace was not bound for per-token timesteps", who);
-    return LTX2_OK;
-}
-
-// in[0] / in[1]: (latent, timesteps, sigma) of the video and the audio modality, read by both contexts; io: the VIDEO latent it updates and its conditioning
-int guided_step_av(ltx2_dit* c, ltx2_dit* neg, const ModIn in[2], const StepIo& io, float cfg_scale, float sigma, float sigma_next, hipStream_t st,
-                   bool rewind_events = true) {
-    LTX2_CHECK_ARG(sigma != 0.f, "Sigma can't be 0.0");
-    LTX2_CHECK_ARG((io.mask == nullptr) == (io.clean == nullptr), "dit_guided_step_av: mask and clean go together");
-    ltx2_dit* const both[2] = {c, neg};
-    for (ltx2_dit* e : both) {
-        const ModIn ev[2] = {{in[0].latent, in[0].ts, in[0].n_ts, in[0].sigma, e->m[0].vel}, {in[1].latent, in[1].ts, in[1].n_ts, in[1].sigma, e->m[1].vel}};
-        TRY(forward(e, ev, st, rewind_events));
-    }
-    const Mod& m = c->m[0];
-    return guided_euler_step_launch(in[0].latent, m.vel, neg->m[0].vel, in[0].ts, in[0].n_ts == 1 ? 0 : 1, io.mask, io.clean, cfg_scale, sigma, sigma_next,
-                                    io.latent, m.N, m.Cout, st);
-}
-}  // namespace
-
-int ltx2_dit_guided_step_av(ltx2_dit* c, ltx2_dit* neg, float* v_latent, const float* a_latent, const float* v_timesteps, int n_v_timesteps,
-                            const float* a_timesteps, int n_a_timesteps, const float* sigma_dev, const float* v_mask, const float* v_clean,
-                            float cfg_scale, float sigma, float sigma_next, void* stream) {
-    LTX2_CHECK_ARG(v_latent && a_latent && v_timesteps && a_timesteps && sigma_dev, "dit_guided_step_av: null argument");
-    TRY(guided_ready_av(c, neg, n_v_timesteps, n_a_timesteps, "dit_guided_step_av"));
-    const ModIn in[2] = {{v_latent, v_timesteps, n_v_timesteps, sigma_dev, nullptr}, {a_latent, a_timesteps, n_a_timesteps, sigma_dev, nullptr}};
-    const StepIo io = {v_latent, v_mask, v_clean, nullptr};
-    return guided_step_av(c, neg, in, io, cfg_scale, sigma, sigma_next, (hipStream_t)stream);
-}
-
-int ltx2_dit_stg_step(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev, const float* mask,
-                      const float* clean, float* vel_perturbed, float cfg_scale, float stg_scale, float sigma, float sigma_next, void* stream) {
-    LTX2_CHECK_ARG(latent && timesteps, "dit_stg_step: null argument");
-    TRY(stg_ready(c, neg, n_timesteps, "dit_stg_step"));
-    const ModIn in = {latent, timesteps, n_timesteps, sigma_dev ? sigma_dev : timesteps, nullptr};
-    const StepIo io = {latent, mask, clean, nullptr};
-    return stg_step(c, neg, in, io, vel_perturbed, cfg_scale, stg_scale, sigma, sigma_next, (hipStream_t)stream);
-}
-
-int ltx2_dit_guided_step(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev,
-                         const float* mask, const float* clean, float cfg_scale, float sigma, float sigma_next, void* stream) {
-    LTX2_CHECK_ARG(latent && timesteps, "dit_guided_step: null argument");
-    TRY(guided_ready(c, neg, n_timesteps, "dit_guided_step"));
-    const ModIn in = {latent, timesteps, n_timesteps, sigma_dev ? sigma_dev : timesteps, nullptr};
-    const StepIo io = {latent, mask, clean, nullptr};
-    return guided_step(c, neg, in, io, cfg_scale, sigma, sigma_next, (hipStream_t)stream);
-}
-
 // Guidance whose scalars are sums over the whole latent (CFG*, APG, legacy APG with momentum; csrc/sampler.hip): the guided step above with the
-// one element-wise pass replaced by the sums kernel and the projected step kernel.  Linear on the caller's stream as well.
-namespace {
+// one element-wise pass replaced by the sums kernel and the projected step kernel.
 struct Projected {      // the guider of a projected step: mode 0 CFG*, 1 APG, 2 legacy APG
     int mode;
     float scale, eta, norm_threshold, momentum;
@@ -1420,36 +1389,21 @@ int projected_workspace(ltx2_dit* c, bool running, bool keep_running) {
 }
 
 int projected_step(ltx2_dit* c, ltx2_dit* neg, const ModIn& in, const StepIo& io, const Projected& g, int first, float sigma, float sigma_next, hipStream_t st) {
-    LTX2_CHECK_ARG(sigma != 0.f, "Sigma can't be 0.0");
-    LTX2_CHECK_ARG((io.mask == nullptr) == (io.clean == nullptr), "dit_projected_step: mask and clean go together");
+    TRY(step_check(sigma, &io, 1, "dit_projected_step"));
     const Mod& m = c->m[0];
     LTX2_CHECK_ARG(c->pg_part && c->pg_rows == guidance_sums_blocks(m.N, m.Cout) && (!g.running() || (c->pg_run && c->pg_run_n == (long)m.N * m.Cout)),
                    "dit_projected_step: workspace missing");
-    TRY(evaluate_pair(c, neg, in.latent, in.ts, in.n_ts, in.sigma, st));
+    TRY(evaluate(c, neg, &in, st));
     float* run = g.running() ? c->pg_run : nullptr;
     const long stride = in.n_ts == 1 ? 0 : 1;
     TRY(guidance_sums_launch(in.latent, m.vel, neg->m[0].vel, in.ts, stride, run, first, g.momentum, c->pg_part, m.N, m.Cout, st));
     return projected_euler_step_launch(in.latent, m.vel, neg->m[0].vel, in.ts, stride, io.mask, io.clean, run, c->pg_part, g.mode, g.scale, g.eta,
                                        g.norm_threshold, sigma, sigma_next, io.latent, nullptr, m.N, m.Cout, st);
 }
-}  // namespace
 
-int ltx2_dit_projected_step(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev, const float* mask,
-                            const float* clean, int mode, float scale, float eta, float norm_threshold, float momentum, int first, float sigma,
-                            float sigma_next, void* stream) {
-    LTX2_CHECK_ARG(latent && timesteps, "dit_projected_step: null argument");
-    TRY(guided_ready(c, neg, n_timesteps, "dit_projected_step"));
-    const Projected g = {mode, scale, eta, norm_threshold, momentum};
-    TRY(projected_check(g, "dit_projected_step"));
-    TRY(projected_workspace(c, g.running(), first == 0));
-    const ModIn in = {latent, timesteps, n_timesteps, sigma_dev ? sigma_dev : timesteps, nullptr};
-    const StepIo io = {latent, mask, clean, nullptr};
-    return projected_step(c, neg, in, io, g, first, sigma, sigma_next, (hipStream_t)stream);
-}
-
-// The res_2s second-order step (reference pipelines/ti2vid_hq.py:185-273; HQ pipeline stage 1): per step two pairs of evaluations, the second
-// from a midpoint latent at the geometric-mean sub-sigma, and two element-wise passes.  Linear on the caller's stream like the guided step.
-namespace {
+// The res_2s second-order step (reference pipelines/ti2vid_hq.py:153-319; HQ pipeline stage 1): per step two pairs of evaluations, the second
+// from a midpoint latent at the geometric-mean sub-sigma, and two element-wise passes.  On AudioVideo contexts the JOINT step: both latents are stepped,
+// the video under cfg_scale and the audio under audio_cfg_scale, each pass one launch over both.
 // phi_j(z) and the res_2s coefficients exactly as components/res2s.py computes them, in double
 double res2s_phi(int j, double z) {
     double fact = 1;
@@ -1485,16 +1439,8 @@ int res2s_plan(float sigma_f, float sigma_next_f, Res2sPlan& p) {
     return LTX2_OK;
 }
 
-int res2s_ready(ltx2_dit* c, ltx2_dit* neg, int n_ts, const char* who) {
-    if (neg) return guided_ready(c, neg, n_ts, who);
-    LTX2_CHECK_ARG(c, "%s: null context", who);
-    LTX2_CHECK_ARG(!c->av, "%s: the res_2s step runs on VideoOnly contexts (the video twin of an AudioVideo model)", who);
-    LTX2_CHECK_ARG(c->prepared, "%s: ltx2_dit_prepare has not been called", who);
-    LTX2_CHECK_ARG(n_ts == 1 || c->per_token, "%s: a workspace was not bound for per-token timesteps", who);
-    return LTX2_OK;
-}
-
-// three fp32 workspaces of `each` elements (x_mid | anchor | eps1); never called while a stream is capturing
+// three fp32 buffers per modality, x_mid | anchor | eps1 of res2s_each(c, k) elements, the video's then the audio's (such a context has no other use for
+// the workspace); r2s_each is res2s_total(c).  Never called while a stream is capturing
 int res2s_workspace(ltx2_dit* c, long each) {
     if (c->r2s && c->r2s_each == each) return LTX2_OK;
     if (c->r2s) (void)hipFree(c->r2s);
@@ -1507,92 +1453,55 @@ int res2s_workspace(ltx2_dit* c, long each) {
     c->r2s_each = each;
     return LTX2_OK;
 }
-// VideoOnly contexts: `each` for the bound N
-long res2s_each(const ltx2_dit* c) { return align_up((long)c->m[0].N * c->m[0].Cout, 64); }
+long res2s_each(const ltx2_dit* c, int k) { return align_up((long)c->m[k].N * c->m[k].Cout, 64); }
+long res2s_total(const ltx2_dit* c) { return res2s_each(c, 0) + (c->av ? res2s_each(c, 1) : 0); }
 
-// in: (latent, timesteps, sigma) of the step; ts_sub / sub_sigma: the same at the sub-sigma.  cond_sub: in a captured conditioned loop, the
-// mask from which ts_sub = mask * sub_sigma is formed into the buffer `in.ts` points at, after the midpoint kernel has read it (one stream, in order).
-int res2s_step(ltx2_dit* c, ltx2_dit* neg, const ModIn& in, const float* ts_sub, const float* sub_sigma, const Cond* cond_sub, const StepIo& io,
-               float cfg_scale, const Res2sPlan& p, hipStream_t st) {
-    LTX2_CHECK_ARG((io.mask == nullptr) == (io.clean == nullptr), "dit_res2s_step: mask and clean go together");
-    LTX2_CHECK_ARG(c->r2s && c->r2s_each >= (long)c->m[0].N * c->m[0].Cout, "dit_res2s_step: workspace missing");
-    const Mod& m = c->m[0];
-    float *x_mid = c->r2s, *anchor = c->r2s + c->r2s_each, *eps1 = c->r2s + 2 * c->r2s_each;
-    const float* vu = neg ? neg->m[0].vel : nullptr;
-    const long stride = in.n_ts == 1 ? 0 : 1;
-    TRY(evaluate_pair(c, neg, in.latent, in.ts, in.n_ts, in.sigma, st));
-    if (p.last)
-        return res2s_midpoint_launch(in.latent, m.vel, vu, in.ts, stride, io.mask, io.clean, cfg_scale, 0.f, 0, io.latent, nullptr, nullptr, m.N, m.Cout, st);
-    TRY(res2s_midpoint_launch(in.latent, m.vel, vu, in.ts, stride, io.mask, io.clean, cfg_scale, p.c, p.n_bong, x_mid, anchor, eps1, m.N, m.Cout, st));
-    if (cond_sub && cond_sub->mask) {
-        hipLaunchKernelGGL(mask_sigma_kernel, dim3((m.N + 255) / 256), dim3(256), 0, st, cond_sub->mask, sub_sigma, m.ts_tok, m.N);
-        LTX2_CHECK_LAUNCH("mask_sigma_kernel");
-        ts_sub = m.ts_tok;
-    }
-    LTX2_CHECK_ARG(ts_sub && sub_sigma, "dit_res2s_step: the sub-sigma timesteps are missing");
-    TRY(evaluate_pair(c, neg, x_mid, ts_sub, in.n_ts, sub_sigma, st));
-    return res2s_combine_launch(x_mid, m.vel, vu, ts_sub, stride, io.mask, io.clean, cfg_scale, anchor, eps1, p.h, p.b1, p.b2, io.latent, m.N, m.Cout, st);
-}
-
-// The JOINT res_2s step on AudioVideo contexts (reference pipelines/ti2vid_hq.py:153-319): both latents are stepped, the video under cfg_scale and
-// the audio under audio_cfg_scale.  guided_ready_av's rules, on c alone when there is no negative context.
-int res2s_ready_av(ltx2_dit* c, ltx2_dit* neg, int n_v_ts, int n_a_ts, const char* who) {
-    if (neg) return guided_ready_av(c, neg, n_v_ts, n_a_ts, who);
-    LTX2_CHECK_ARG(c, "%s: null context", who);
-    LTX2_CHECK_ARG(c->av, "%s: the context must be AudioVideo (the VideoOnly engine has ltx2_dit_res2s_step)", who);
-    LTX2_CHECK_ARG(c->prepared, "%s: ltx2_dit_prepare_av has not been called", who);
-    LTX2_CHECK_ARG((n_v_ts == 1 || n_v_ts == c->m[0].N) && (n_a_ts == 1 || n_a_ts == c->m[1].N),
-                   "%s: n_v_timesteps=%d must be 1 or N=%d, n_a_timesteps=%d must be 1 or Na=%d", who, n_v_ts, c->m[0].N, n_a_ts, c->m[1].N);
-    LTX2_CHECK_ARG((n_v_ts == 1 && n_a_ts == 1) || c->per_token, "%s: a workspace was not bound for per-token timesteps", who);
-    return LTX2_OK;
-}
-
-// AudioVideo contexts: x_mid | anchor | eps1 of the video latent, then of the audio latent, in the same workspace (such a context has no other use for
-// it); r2s_each is then the elements of one video plus one audio buffer
-long res2s_each_av(const ltx2_dit* c, int k) { return align_up((long)c->m[k].N * c->m[k].Cout, 64); }
-
-// both modalities of `in` through c into c's velocity buffers and, with a negative context, through neg into neg's
-int evaluate_pair_av(ltx2_dit* c, ltx2_dit* neg, const ModIn in[2], hipStream_t st, bool rewind_events) {
-    ltx2_dit* const both[2] = {c, neg};
-    for (ltx2_dit* e : both) {
-        if (!e) continue;
-        const ModIn ev[2] = {{in[0].latent, in[0].ts, in[0].n_ts, in[0].sigma, e->m[0].vel}, {in[1].latent, in[1].ts, in[1].n_ts, in[1].sigma, e->m[1].vel}};
-        TRY(forward(e, ev, st, rewind_events));
-    }
-    return LTX2_OK;
-}
-
-// in[k]: (latent, timesteps, sigma) of modality k; ts_sub[k] / sub_sigma: the same at the sub-sigma.  Every check stands before the first launch.
-int res2s_step_av(ltx2_dit* c, ltx2_dit* neg, const ModIn in[2], const float* const ts_sub[2], const float* sub_sigma, const StepIo io[2], float cfg_scale,
-                  float audio_cfg_scale, const Res2sPlan& p, hipStream_t st) {
+// in[k]: (latent, timesteps, sigma) of modality k; v_ts_sub / a_ts_sub / sub_sigma: the same at the sub-sigma.  cond_sub: in a captured conditioned
+// loop, the masks from which ts_sub = mask * sub_sigma is formed into the buffer `in[k].ts` points at, after the midpoint kernel has read it (one
+// stream, in order).  Every check stands before the first launch.
+int res2s_step(ltx2_dit* c, ltx2_dit* neg, const ModIn* in, const float* v_ts_sub, const float* a_ts_sub, const float* sub_sigma, const Cond* cond_sub,
+               const StepIo* io, float cfg_scale, float audio_cfg_scale, const Res2sPlan& p, hipStream_t st) {
+    const int nm = c->av ? 2 : 1;
     const float cfg[2] = {cfg_scale, audio_cfg_scale};
-    const float* vu[2];
-    float *x_mid[2], *anchor[2], *eps1[2];
-    long stride[2];
-    LTX2_CHECK_ARG(c->r2s && c->r2s_each == res2s_each_av(c, 0) + res2s_each_av(c, 1), "dit_res2s_step_av: workspace missing");
+    const float *ts_sub[2] = {v_ts_sub, a_ts_sub}, *vu[2] = {};
+    float *x_mid[2] = {}, *anchor[2] = {}, *eps1[2] = {};
+    long stride[2] = {};
+    LTX2_CHECK_ARG(c->r2s && c->r2s_each == res2s_total(c), "dit_res2s_step: workspace missing");
     float* base = c->r2s;
-    for (int k = 0; k < 2; ++k) {
-        LTX2_CHECK_ARG((io[k].mask == nullptr) == (io[k].clean == nullptr), "dit_res2s_step_av: mask and clean go together");
-        LTX2_CHECK_ARG(p.last || (sub_sigma && ts_sub[k]), "dit_res2s_step_av: the sub-sigma timesteps are missing");
-        const long each = res2s_each_av(c, k);
-        x_mid[k] = base;
-        anchor[k] = base + each;
-        eps1[k] = base + 2 * each;
+    for (int k = 0; k < nm; ++k) {
+        LTX2_CHECK_ARG((io[k].mask == nullptr) == (io[k].clean == nullptr), "dit_res2s_step: mask and clean go together");
+        if (cond_sub && cond_sub[k].mask) ts_sub[k] = c->m[k].ts_tok;
+        LTX2_CHECK_ARG(p.last || (sub_sigma && ts_sub[k]), "dit_res2s_step: the sub-sigma timesteps are missing");
+        const long each = res2s_each(c, k);
+        x_mid[k] = p.last ? io[k].latent : base;                // the final step (p.c == 0, p.n_bong == 0): latent = d, nothing kept
+        anchor[k] = p.last ? nullptr : base + each;
+        eps1[k] = p.last ? nullptr : base + 2 * each;
         base += 3 * each;
         vu[k] = neg ? neg->m[k].vel : nullptr;
         stride[k] = in[k].n_ts == 1 ? 0 : 1;
     }
     const Mod &v = c->m[0], &a = c->m[1];
-    TRY(evaluate_pair_av(c, neg, in, st, true));
-    if (p.last)
-        return res2s_midpoint_pair_launch(in[0].latent, v.vel, vu[0], in[0].ts, stride[0], io[0].mask, io[0].clean, cfg[0], io[0].latent, nullptr, nullptr, v.N,
-                                          v.Cout, in[1].latent, a.vel, vu[1], in[1].ts, stride[1], io[1].mask, io[1].clean, cfg[1], io[1].latent, nullptr,
-                                          nullptr, a.N, a.Cout, 0.f, 0, st);
-    TRY(res2s_midpoint_pair_launch(in[0].latent, v.vel, vu[0], in[0].ts, stride[0], io[0].mask, io[0].clean, cfg[0], x_mid[0], anchor[0], eps1[0], v.N, v.Cout,
-                                   in[1].latent, a.vel, vu[1], in[1].ts, stride[1], io[1].mask, io[1].clean, cfg[1], x_mid[1], anchor[1], eps1[1], a.N, a.Cout,
-                                   p.c, p.n_bong, st));
-    const ModIn mid[2] = {{x_mid[0], ts_sub[0], in[0].n_ts, sub_sigma, nullptr}, {x_mid[1], ts_sub[1], in[1].n_ts, sub_sigma, nullptr}};
-    TRY(evaluate_pair_av(c, neg, mid, st, true));
+    TRY(evaluate(c, neg, in, st));
+    if (nm == 1)
+        TRY(res2s_midpoint_launch(in[0].latent, v.vel, vu[0], in[0].ts, stride[0], io[0].mask, io[0].clean, cfg[0], p.c, p.n_bong, x_mid[0], anchor[0], eps1[0],
+                                  v.N, v.Cout, st));
+    else
+        TRY(res2s_midpoint_pair_launch(in[0].latent, v.vel, vu[0], in[0].ts, stride[0], io[0].mask, io[0].clean, cfg[0], x_mid[0], anchor[0], eps1[0], v.N, v.Cout,
+                                       in[1].latent, a.vel, vu[1], in[1].ts, stride[1], io[1].mask, io[1].clean, cfg[1], x_mid[1], anchor[1], eps1[1], a.N, a.Cout,
+                                       p.c, p.n_bong, st));
+    if (p.last) return LTX2_OK;
+    ModIn mid[2] = {};
+    for (int k = 0; k < nm; ++k) {
+        if (cond_sub && cond_sub[k].mask) {
+            hipLaunchKernelGGL(mask_sigma_kernel, dim3((c->m[k].N + 255) / 256), dim3(256), 0, st, cond_sub[k].mask, sub_sigma, c->m[k].ts_tok, c->m[k].N);
+            LTX2_CHECK_LAUNCH("mask_sigma_kernel");
+        }
+        mid[k] = {x_mid[k], ts_sub[k], in[k].n_ts, sub_sigma, nullptr};
+    }
+    TRY(evaluate(c, neg, mid, st));
+    if (nm == 1)
+        return res2s_combine_launch(x_mid[0], v.vel, vu[0], ts_sub[0], stride[0], io[0].mask, io[0].clean, cfg[0], anchor[0], eps1[0], p.h, p.b1, p.b2, io[0].latent,
+                                    v.N, v.Cout, st);
     return res2s_combine_pair_launch(x_mid[0], v.vel, vu[0], ts_sub[0], stride[0], io[0].mask, io[0].clean, cfg[0], anchor[0], eps1[0], io[0].latent, v.N, v.Cout,
                                      x_mid[1], a.vel, vu[1], ts_sub[1], stride[1], io[1].mask, io[1].clean, cfg[1], anchor[1], eps1[1], io[1].latent, a.N, a.Cout,
                                      p.h, p.b1, p.b2, st);
@@ -1636,49 +1545,94 @@ int capture_loop(ltx2_dit* c, const LoopStep& step, float* const latent[2], cons
         }
         if (rc != LTX2_OK) break;
         if (step.res2s) {
-            rc = res2s_step(c, step.neg, in[0], ss, ss, &cond[0], io[0], step.cfg_scale, step.res2s[i], st);
+            rc = res2s_step(c, step.neg, in, ss, ss, ss, cond, io, step.cfg_scale, step.cfg_scale, step.res2s[i], st);
             if (step.res2s[i].last) break;                      // the reference's loop ends on its final step
         } else if (step.projected) {
             rc = projected_step(c, step.neg, in[0], io[0], *step.projected, i == 0, sigma, sigma_next, st);
         } else if (step.stg_vel && i < step.stg_steps) {
             rc = stg_step(c, step.neg, in[0], io[0], step.stg_vel, step.cfg_scale, step.stg_scale, sigma, sigma_next, st);
         } else if (step.neg && c->av) {
-            rc = guided_step_av(c, step.neg, in, io[0], step.cfg_scale, sigma, sigma_next, st, i == 0);
+            rc = guided_step(c, step.neg, in, io[0], step.cfg_scale, sigma, sigma_next, st, i == 0);
         } else if (step.neg) {
-            rc = guided_step(c, step.neg, in[0], io[0], step.cfg_scale, sigma, sigma_next, st);
+            rc = guided_step(c, step.neg, in, io[0], step.cfg_scale, sigma, sigma_next, st, i == 0);
         } else {
             rc = denoise_step(c, in, io, sigma, sigma_next, st, i == 0);
         }
     }
     return end_capture(c, rc, st);
 }
+
+// The latents and the conditioning of a guided capture entry's loop, and what each such entry checks first
+struct LoopIo {
+    float* lat[2];
+    Cond cond[2];
+};
+
+int capture_ready(ltx2_dit* c, ltx2_dit* neg, bool need_neg, bool want_av, const LoopIo& lo, const float* host_sigmas, int n_steps, const char* who) {
+    LTX2_CHECK_ARG(c && lo.lat[0] && (!want_av || lo.lat[1]) && host_sigmas && n_steps > 0 && n_steps < 64, "%s: bad argument", who);
+    LTX2_CHECK_ARG(neg || !need_neg, "%s: null context", who);
+    const int n_ts[2] = {lo.cond[0].mask ? c->m[0].N : 1, lo.cond[1].mask ? c->m[1].N : 1};
+    TRY(step_ready(c, neg, want_av, n_ts, who));
+    LTX2_CHECK_ARG((lo.cond[0].mask == nullptr) == (lo.cond[0].clean == nullptr), "%s: mask and clean go together", who);
+    return LTX2_OK;
+}
 }  // namespace
+
+int ltx2_dit_guided_step(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev,
+                         const float* mask, const float* clean, float cfg_scale, float sigma, float sigma_next, void* stream) {
+    LTX2_CHECK_ARG(neg && latent && timesteps, "dit_guided_step: null argument");
+    const int n_ts[2] = {n_timesteps, 1};
+    TRY(step_ready(c, neg, false, n_ts, "dit_guided_step"));
+    const StepArgs v = step_args(latent, timesteps, n_timesteps, sigma_dev, mask, clean);
+    return guided_step(c, neg, &v.in, v.io, cfg_scale, sigma, sigma_next, (hipStream_t)stream);
+}
+
+int ltx2_dit_guided_step_av(ltx2_dit* c, ltx2_dit* neg, float* v_latent, const float* a_latent, const float* v_timesteps, int n_v_timesteps,
+                            const float* a_timesteps, int n_a_timesteps, const float* sigma_dev, const float* v_mask, const float* v_clean,
+                            float cfg_scale, float sigma, float sigma_next, void* stream) {
+    LTX2_CHECK_ARG(neg && v_latent && a_latent && v_timesteps && a_timesteps && sigma_dev, "dit_guided_step_av: null argument");
+    const int n_ts[2] = {n_v_timesteps, n_a_timesteps};
+    TRY(step_ready(c, neg, true, n_ts, "dit_guided_step_av"));
+    const StepArgs v = step_args(v_latent, v_timesteps, n_v_timesteps, sigma_dev, v_mask, v_clean);
+    // the audio latent is read by both evaluations and never written
+    const ModIn in[2] = {v.in, step_args(const_cast<float*>(a_latent), a_timesteps, n_a_timesteps, sigma_dev, nullptr, nullptr).in};
+    return guided_step(c, neg, in, v.io, cfg_scale, sigma, sigma_next, (hipStream_t)stream);
+}
+
+int ltx2_dit_stg_step(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev, const float* mask,
+                      const float* clean, float* vel_perturbed, float cfg_scale, float stg_scale, float sigma, float sigma_next, void* stream) {
+    LTX2_CHECK_ARG(latent && timesteps, "dit_stg_step: null argument");
+    const int n_ts[2] = {n_timesteps, 1};
+    TRY(step_ready(c, neg, false, n_ts, "dit_stg_step"));
+    const StepArgs v = step_args(latent, timesteps, n_timesteps, sigma_dev, mask, clean);
+    return stg_step(c, neg, v.in, v.io, vel_perturbed, cfg_scale, stg_scale, sigma, sigma_next, (hipStream_t)stream);
+}
+
+int ltx2_dit_projected_step(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev, const float* mask,
+                            const float* clean, int mode, float scale, float eta, float norm_threshold, float momentum, int first, float sigma,
+                            float sigma_next, void* stream) {
+    LTX2_CHECK_ARG(neg && latent && timesteps, "dit_projected_step: null argument");
+    const int n_ts[2] = {n_timesteps, 1};
+    TRY(step_ready(c, neg, false, n_ts, "dit_projected_step"));
+    const Projected g = {mode, scale, eta, norm_threshold, momentum};
+    TRY(projected_check(g, "dit_projected_step"));
+    TRY(projected_workspace(c, g.running(), first == 0));
+    const StepArgs v = step_args(latent, timesteps, n_timesteps, sigma_dev, mask, clean);
+    return projected_step(c, neg, v.in, v.io, g, first, sigma, sigma_next, (hipStream_t)stream);
+}
 
 int ltx2_dit_res2s_step(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev,
                         const float* ts_sub, const float* sub_sigma_dev, const float* mask, const float* clean, float cfg_scale, float sigma,
                         float sigma_next, void* stream) {
     LTX2_CHECK_ARG(latent && timesteps, "dit_res2s_step: null argument");
-    TRY(res2s_ready(c, neg, n_timesteps, "dit_res2s_step"));
+    const int n_ts[2] = {n_timesteps, 1};
+    TRY(step_ready(c, neg, false, n_ts, "dit_res2s_step"));
     Res2sPlan p;
     TRY(res2s_plan(sigma, sigma_next, p));
     LTX2_CHECK_ARG(p.last || ts_sub, "dit_res2s_step: ts_sub is needed unless the step is the final one");
-    TRY(res2s_workspace(c, res2s_each(c)));
-    const ModIn in = {latent, timesteps, n_timesteps, sigma_dev ? sigma_dev : timesteps, nullptr};
-    const StepIo io = {latent, mask, clean, nullptr};
-    return res2s_step(c, neg, in, ts_sub, sub_sigma_dev ? sub_sigma_dev : ts_sub, nullptr, io, cfg_scale, p, (hipStream_t)stream);
-}
-
-int ltx2_dit_graph_capture_res2s(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* host_sigmas, int n_steps, const float* mask,
-                                 int64_t n_mask, const float* clean, int64_t n_clean, float cfg_scale, void* stream) {
-    LTX2_CHECK_ARG(latent && host_sigmas && n_steps > 0 && n_steps < 64, "dit_graph_capture_res2s: bad argument");
-    TRY(res2s_ready(c, neg, mask ? c->m[0].N : 1, "dit_graph_capture_res2s"));
-    LTX2_CHECK_ARG((mask == nullptr) == (clean == nullptr), "dit_graph_capture_res2s: mask and clean go together");
-    Res2sPlan plan[64];
-    for (int i = 0; i < n_steps; ++i) TRY(res2s_plan(host_sigmas[i], host_sigmas[i + 1], plan[i]));
-    TRY(res2s_workspace(c, res2s_each(c)));
-    float* const lat[2] = {latent, nullptr};
-    const Cond cond[2] = {{mask, (long)n_mask, clean, (long)n_clean}, {}};
-    return capture_loop(c, {neg, cfg_scale, nullptr, plan}, lat, cond, host_sigmas, n_steps, (hipStream_t)stream);
+    TRY(res2s_workspace(c, res2s_total(c)));
+    const StepArgs v = step_args(latent, timesteps, n_timesteps, sigma_dev, mask, clean);
+    return res2s_step(c, neg, &v.in, ts_sub, nullptr, sub_sigma_dev ? sub_sigma_dev : ts_sub, nullptr, &v.io, cfg_scale, 0.f, p, (hipStream_t)stream);
 }
 
 int ltx2_dit_res2s_step_av(ltx2_dit* c, ltx2_dit* neg, float* v_latent, float* a_latent, const float* v_timesteps, int n_v_timesteps,
@@ -1686,16 +1640,17 @@ int ltx2_dit_res2s_step_av(ltx2_dit* c, ltx2_dit* neg, float* v_latent, float* a
                            const float* sub_sigma_dev, const float* v_mask, const float* v_clean, const float* a_mask, const float* a_clean,
                            float cfg_scale, float audio_cfg_scale, float sigma, float sigma_next, void* stream) {
     LTX2_CHECK_ARG(v_latent && a_latent && v_timesteps && a_timesteps && sigma_dev, "dit_res2s_step_av: null argument");
-    TRY(res2s_ready_av(c, neg, n_v_timesteps, n_a_timesteps, "dit_res2s_step_av"));
-    LTX2_CHECK_ARG((v_mask == nullptr) == (v_clean == nullptr) && (a_mask == nullptr) == (a_clean == nullptr), "dit_res2s_step_av: mask and clean go together");
+    const int n_ts[2] = {n_v_timesteps, n_a_timesteps};
+    TRY(step_ready(c, neg, true, n_ts, "dit_res2s_step_av"));
     Res2sPlan p;
     TRY(res2s_plan(sigma, sigma_next, p));
     LTX2_CHECK_ARG(p.last || (v_ts_sub && a_ts_sub), "dit_res2s_step_av: v_ts_sub and a_ts_sub are needed unless the step is the final one");
-    TRY(res2s_workspace(c, res2s_each_av(c, 0) + res2s_each_av(c, 1)));
-    const ModIn in[2] = {{v_latent, v_timesteps, n_v_timesteps, sigma_dev, nullptr}, {a_latent, a_timesteps, n_a_timesteps, sigma_dev, nullptr}};
-    const StepIo io[2] = {{v_latent, v_mask, v_clean, nullptr}, {a_latent, a_mask, a_clean, nullptr}};
-    const float* const sub[2] = {v_ts_sub, a_ts_sub};
-    return res2s_step_av(c, neg, in, sub, sub_sigma_dev ? sub_sigma_dev : v_ts_sub, io, cfg_scale, audio_cfg_scale, p, (hipStream_t)stream);
+    TRY(res2s_workspace(c, res2s_total(c)));
+    const StepArgs v = step_args(v_latent, v_timesteps, n_v_timesteps, sigma_dev, v_mask, v_clean);
+    const StepArgs a = step_args(a_latent, a_timesteps, n_a_timesteps, sigma_dev, a_mask, a_clean);
+    const ModIn in[2] = {v.in, a.in};
+    const StepIo io[2] = {v.io, a.io};
+    return res2s_step(c, neg, in, v_ts_sub, a_ts_sub, sub_sigma_dev ? sub_sigma_dev : v_ts_sub, nullptr, io, cfg_scale, audio_cfg_scale, p, (hipStream_t)stream);
 }
 
 int ltx2_dit_graph_capture(ltx2_dit* c, float* latent, const float* host_sigmas, int n_steps, void* stream) {
@@ -1717,49 +1672,51 @@ int ltx2_dit_graph_capture_cond(ltx2_dit* c, float* latent, const float* host_si
 
 int ltx2_dit_graph_capture_guided(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* host_sigmas, int n_steps, const float* mask,
                                   int64_t n_mask, const float* clean, int64_t n_clean, float cfg_scale, void* stream) {
-    LTX2_CHECK_ARG(latent && host_sigmas && n_steps > 0 && n_steps < 64, "dit_graph_capture_guided: bad argument");
-    TRY(guided_ready(c, neg, mask ? c->m[0].N : 1, "dit_graph_capture_guided"));
-    LTX2_CHECK_ARG((mask == nullptr) == (clean == nullptr), "dit_graph_capture_guided: mask and clean go together");
-    float* const lat[2] = {latent, nullptr};
-    const Cond cond[2] = {{mask, (long)n_mask, clean, (long)n_clean}, {}};
-    return capture_loop(c, {neg, cfg_scale}, lat, cond, host_sigmas, n_steps, (hipStream_t)stream);
+    const LoopIo lo = {{latent, nullptr}, {{mask, (long)n_mask, clean, (long)n_clean}, {}}};
+    TRY(capture_ready(c, neg, true, false, lo, host_sigmas, n_steps, "dit_graph_capture_guided"));
+    return capture_loop(c, {neg, cfg_scale}, lo.lat, lo.cond, host_sigmas, n_steps, (hipStream_t)stream);
 }
 
 int ltx2_dit_graph_capture_stg(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* host_sigmas, int n_steps, const float* mask, int64_t n_mask,
                                const float* clean, int64_t n_clean, float* vel_perturbed, int64_t n_vel, float cfg_scale, float stg_scale, double stg_cutoff,
                                void* stream) {
-    LTX2_CHECK_ARG(c && latent && host_sigmas && vel_perturbed && n_steps > 0 && n_steps < 64, "dit_graph_capture_stg: bad argument");
-    TRY(stg_ready(c, neg, mask ? c->m[0].N : 1, "dit_graph_capture_stg"));
-    LTX2_CHECK_ARG((mask == nullptr) == (clean == nullptr), "dit_graph_capture_stg: mask and clean go together");
+    LTX2_CHECK_ARG(vel_perturbed, "dit_graph_capture_stg: bad argument");
+    const LoopIo lo = {{latent, nullptr}, {{mask, (long)n_mask, clean, (long)n_clean}, {}}};
+    TRY(capture_ready(c, neg, false, false, lo, host_sigmas, n_steps, "dit_graph_capture_stg"));
     // every replayed STG step writes N * out_channels velocities there
     LTX2_CHECK_ARG(n_vel == (int64_t)c->m[0].N * c->m[0].Cout, "dit_graph_capture_stg: vel_perturbed has %ld elements, %d tokens x %d channels are needed", (long)n_vel,
                    c->m[0].N, c->m[0].Cout);
     // step i is an STG step iff (i + 1) / n_steps <= stg_cutoff (one_stage.py:289-294), in double as Python divides; the fractions grow with i
     int stg_steps = 0;
     while (stg_steps < n_steps && (double)(stg_steps + 1) / (double)n_steps <= stg_cutoff) ++stg_steps;
-    float* const lat[2] = {latent, nullptr};
-    const Cond cond[2] = {{mask, (long)n_mask, clean, (long)n_clean}, {}};
     LoopStep step;
     step.neg = neg;
     step.cfg_scale = cfg_scale;
     step.stg_vel = vel_perturbed;
     step.stg_scale = stg_scale;
     step.stg_steps = stg_steps;
-    return capture_loop(c, step, lat, cond, host_sigmas, n_steps, (hipStream_t)stream);
+    return capture_loop(c, step, lo.lat, lo.cond, host_sigmas, n_steps, (hipStream_t)stream);
 }
 
 int ltx2_dit_graph_capture_projected(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* host_sigmas, int n_steps, const float* mask, int64_t n_mask,
                                      const float* clean, int64_t n_clean, int mode, float scale, float eta, float norm_threshold, float momentum,
                                      void* stream) {
-    LTX2_CHECK_ARG(latent && host_sigmas && n_steps > 0 && n_steps < 64, "dit_graph_capture_projected: bad argument");
-    TRY(guided_ready(c, neg, mask ? c->m[0].N : 1, "dit_graph_capture_projected"));
-    LTX2_CHECK_ARG((mask == nullptr) == (clean == nullptr), "dit_graph_capture_projected: mask and clean go together");
+    const LoopIo lo = {{latent, nullptr}, {{mask, (long)n_mask, clean, (long)n_clean}, {}}};
+    TRY(capture_ready(c, neg, true, false, lo, host_sigmas, n_steps, "dit_graph_capture_projected"));
     const Projected g = {mode, scale, eta, norm_threshold, momentum};
     TRY(projected_check(g, "dit_graph_capture_projected"));
     TRY(projected_workspace(c, g.running(), false));
-    float* const lat[2] = {latent, nullptr};
-    const Cond cond[2] = {{mask, (long)n_mask, clean, (long)n_clean}, {}};
-    return capture_loop(c, {neg, 0.f, &g}, lat, cond, host_sigmas, n_steps, (hipStream_t)stream);
+    return capture_loop(c, {neg, 0.f, &g}, lo.lat, lo.cond, host_sigmas, n_steps, (hipStream_t)stream);
+}
+
+int ltx2_dit_graph_capture_res2s(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* host_sigmas, int n_steps, const float* mask,
+                                 int64_t n_mask, const float* clean, int64_t n_clean, float cfg_scale, void* stream) {
+    const LoopIo lo = {{latent, nullptr}, {{mask, (long)n_mask, clean, (long)n_clean}, {}}};
+    TRY(capture_ready(c, neg, false, false, lo, host_sigmas, n_steps, "dit_graph_capture_res2s"));
+    Res2sPlan plan[64];
+    for (int i = 0; i < n_steps; ++i) TRY(res2s_plan(host_sigmas[i], host_sigmas[i + 1], plan[i]));
+    TRY(res2s_workspace(c, res2s_total(c)));
+    return capture_loop(c, {neg, cfg_scale, nullptr, plan}, lo.lat, lo.cond, host_sigmas, n_steps, (hipStream_t)stream);
 }
 
 int ltx2_dit_graph_capture_cond_av(ltx2_dit* c, float* v_latent, float* a_latent, const float* host_sigmas, int n_steps, const float* v_mask, int64_t n_v_mask,
@@ -1774,12 +1731,10 @@ int ltx2_dit_graph_capture_cond_av(ltx2_dit* c, float* v_latent, float* a_latent
 int ltx2_dit_graph_capture_guided_av(ltx2_dit* c, ltx2_dit* neg, float* v_latent, const float* a_latent, const float* host_sigmas, int n_steps,
                                      const float* v_mask, int64_t n_v_mask, const float* v_clean, int64_t n_v_clean, const float* a_mask, int64_t n_a_mask,
                                      float cfg_scale, void* stream) {
-    LTX2_CHECK_ARG(v_latent && a_latent && host_sigmas && n_steps > 0 && n_steps < 64, "dit_graph_capture_guided_av: bad argument");
-    TRY(guided_ready_av(c, neg, v_mask ? c->m[0].N : 1, a_mask ? c->m[1].N : 1, "dit_graph_capture_guided_av"));
-    LTX2_CHECK_ARG((v_mask == nullptr) == (v_clean == nullptr), "dit_graph_capture_guided_av: mask and clean go together");
-    float* const lat[2] = {v_latent, const_cast<float*>(a_latent)};        // the audio latent is read by both evaluations and never written
-    const Cond cond[2] = {{v_mask, (long)n_v_mask, v_clean, (long)n_v_clean}, {a_mask, (long)n_a_mask, nullptr, 0}};
-    return capture_loop(c, {neg, cfg_scale}, lat, cond, host_sigmas, n_steps, (hipStream_t)stream);
+    // the audio latent is read by both evaluations and never written: its mask gives the timesteps only
+    const LoopIo lo = {{v_latent, const_cast<float*>(a_latent)}, {{v_mask, (long)n_v_mask, v_clean, (long)n_v_clean}, {a_mask, (long)n_a_mask, nullptr, 0}}};
+    TRY(capture_ready(c, neg, true, true, lo, host_sigmas, n_steps, "dit_graph_capture_guided_av"));
+    return capture_loop(c, {neg, cfg_scale}, lo.lat, lo.cond, host_sigmas, n_steps, (hipStream_t)stream);
 }
 
 int ltx2_dit_graph_capture_av(ltx2_dit* c, float* v_latent, float* a_latent, const float* host_sigmas, int n_steps,

@@ -741,19 +741,37 @@ class LTXModel:
         else:
             nv.check(self._L.ltx2_dit_graph_capture(self._h, nv.ptr(latent), arr, n, st.cuda_stream))
 
-    # ------------------------------------------------------------------ classifier-free guidance (video-only engine)
-    def _guided_pair(self, neg: "LTXModel") -> Tuple["LTXModel", "LTXModel"]:
-        """(positive, negative) VideoOnly contexts of a guided step: an AudioVideo model is used through its video twin."""
-        if not isinstance(neg, LTXModel):
+    # ------------------------------------------------------------------ guided and second-order steps: what they share
+    def _contexts(self, neg: Optional["LTXModel"], av: bool = False, optional: bool = False) -> Tuple["LTXModel", Optional["LTXModel"]]:
+        """(positive, negative) contexts of a guided step.  av=False: VideoOnly contexts, an AudioVideo model used through its video twin;
+        av=True: AudioVideo contexts, as they are.  optional: neg may be None (a step that also runs without guidance) and is returned so."""
+        if not (isinstance(neg, LTXModel) or (optional and neg is None)):
             raise ValueError("guidance needs a second LTXModel context (clone_sharing_weights()) for the negative prompt")
-        return (self._video_twin() if self.is_av else self), (neg._video_twin() if neg.is_av else neg)
+        if av:
+            if not (self.is_av and (neg is None or neg.is_av)):
+                raise ValueError("the *_av_ steps run on AudioVideo contexts (a VideoOnly model has the step without _av)")
+            return self, neg
+        return (self._video_twin() if self.is_av else self), (neg._video_twin() if neg is not None and neg.is_av else neg)
 
+    def _capture(self, kind: str, pos: "LTXModel", ng: Optional["LTXModel"], symbol: str, refs: tuple, sigmas: Sequence[float], mask_clean_pairs, *tail) -> None:
+        """What every guided capture_*_graph does: the C call `symbol`(pos, ng, the latents `refs`, sigmas, n, the video conditioning
+        mask_clean_pairs[0], *tail, stream) -- a tensor or None goes as (pointer, element count), further pairs are only checked (the frozen
+        audio's mask travels in tail) -- with the graph, and every tensor it reads, kept by `pos` and replayed as `kind`."""
+        assert pos._prep_key is not None and (ng is None or ng._prep_key is not None), "call prepare() on both contexts first"
+        arr, n, st, n_el = self._capture_inputs(sigmas, *mask_clean_pairs)
+        is_buf = lambda a: a is None or isinstance(a, torch.Tensor)      # noqa: E731
+        args = [x for a in (*mask_clean_pairs[0], *tail) for x in ((nv.ptr(a), n_el(a)) if is_buf(a) else (a,))]
+        pos._graph_refs = (*refs, *(t for pair in mask_clean_pairs for t in pair), *(a for a in tail if is_buf(a)), ng)
+        nv.check(getattr(pos._L, symbol)(pos._h, None if ng is None else ng._h, *(nv.ptr(t) for t in refs), arr, n, *args, st.cuda_stream))
+        self._graph_owner = (kind, pos)
+
+    # ------------------------------------------------------------------ classifier-free guidance (video-only engine)
     def guided_step_(self, neg: "LTXModel", latent: torch.Tensor, video: Modality, sigma: float, sigma_next: float, cfg_scale: float,
                      denoise_mask: Optional[torch.Tensor] = None, clean_latent: Optional[torch.Tensor] = None) -> None:
         """In-place: latent (N, C) fp32 <- one classifier-free-guided Euler step -- the positive prompt through this context, the negative one
         through `neg` (clone_sharing_weights(), prepared by the caller with the negative context), then x0 x 2 + CFGGuider.guide +
         post_process_latent + Euler in one kernel, all enqueued by ONE C call (ltx2_dit_guided_step)."""
-        pos, ng = self._guided_pair(neg)
+        pos, ng = self._contexts(neg)
         ts, n_ts, sg = pos._step_inputs(latent, video, sigma)
         nv.check(pos._L.ltx2_dit_guided_step(pos._h, ng._h, nv.ptr(latent), nv.ptr(ts), n_ts, nv.ptr(sg), nv.ptr(denoise_mask), nv.ptr(clean_latent),
                                              float(cfg_scale), float(sigma), float(sigma_next), nv.stream()))
@@ -764,13 +782,8 @@ class LTXModel:
         Euler kernel per step (ltx2_dit_graph_capture_guided).  Both contexts are prepared first (per_token=True when a mask is given); the
         graph belongs to the positive VideoOnly context (this one, or an AudioVideo model's video twin) and replay_guided_graph() replays
         it.  The tensors must stay alive while it is replayed."""
-        pos, ng = self._guided_pair(neg)
-        assert pos._prep_key is not None and ng._prep_key is not None, "call prepare() on both contexts first"
-        arr, n, st, n_el = self._capture_inputs(sigmas, (denoise_mask, clean_latent))
-        pos._graph_refs = (latent, denoise_mask, clean_latent, ng)
-        nv.check(pos._L.ltx2_dit_graph_capture_guided(pos._h, ng._h, nv.ptr(latent), arr, n, nv.ptr(denoise_mask), n_el(denoise_mask),
-                                                      nv.ptr(clean_latent), n_el(clean_latent), float(cfg_scale), st.cuda_stream))
-        self._graph_owner = ("guided", pos)
+        pos, ng = self._contexts(neg)
+        self._capture("guided", pos, ng, "ltx2_dit_graph_capture_guided", (latent,), sigmas, [(denoise_mask, clean_latent)], float(cfg_scale))
 
     def replay_guided_graph(self) -> None:
         """Replay the graph captured by capture_guided_graph (it belongs to the VideoOnly context that ran the capture)."""
@@ -783,7 +796,7 @@ class LTXModel:
         """In-place: latent (N, C) fp32 <- one Euler step under CFGGuider and STGGuider by ONE C call (ltx2_dit_stg_step): forward(self),
         forward(neg) (neg None: no CFG), a perturbed forward on this context itself -- the self-attentions of set_stg_blocks skipped -- into
         vel_perturbed (N, C fp32, the caller's scratch), then x0 x 3 + both guiders + post_process_latent + Euler in one kernel."""
-        pos, ng = self._video_pair(neg)
+        pos, ng = self._contexts(neg, optional=True)
         ts, n_ts, sg = pos._step_inputs(latent, video, sigma)
         assert vel_perturbed.dtype == torch.float32 and vel_perturbed.is_contiguous() and vel_perturbed.shape == latent.shape
         nv.check(pos._L.ltx2_dit_stg_step(pos._h, None if ng is None else ng._h, nv.ptr(latent), nv.ptr(ts), n_ts, nv.ptr(sg), nv.ptr(denoise_mask),
@@ -797,28 +810,16 @@ class LTXModel:
         step while (i + 1) / n <= stg_cutoff, then the guided step (the plain one when neg is None).  Both contexts are prepared first
         (per_token=True when a mask is given); the graph belongs to the positive VideoOnly context and replay_stg_graph() replays it.  The
         tensors must stay alive while it is replayed."""
-        pos, ng = self._video_pair(neg)
-        assert pos._prep_key is not None and (ng is None or ng._prep_key is not None), "call prepare() on both contexts first"
+        pos, ng = self._contexts(neg, optional=True)
         assert vel_perturbed.dtype == torch.float32 and vel_perturbed.is_contiguous()
-        arr, n, st, n_el = self._capture_inputs(sigmas, (denoise_mask, clean_latent))
-        pos._graph_refs = (latent, denoise_mask, clean_latent, vel_perturbed, ng)
-        nv.check(pos._L.ltx2_dit_graph_capture_stg(pos._h, None if ng is None else ng._h, nv.ptr(latent), arr, n, nv.ptr(denoise_mask),
-                                                   n_el(denoise_mask), nv.ptr(clean_latent), n_el(clean_latent), nv.ptr(vel_perturbed),
-                                                   n_el(vel_perturbed), float(cfg_scale), float(stg_scale), float(stg_cutoff), st.cuda_stream))
-        self._graph_owner = ("stg", pos)
+        self._capture("stg", pos, ng, "ltx2_dit_graph_capture_stg", (latent,), sigmas, [(denoise_mask, clean_latent)], vel_perturbed,
+                      float(cfg_scale), float(stg_scale), float(stg_cutoff))
 
     def replay_stg_graph(self) -> None:
         """Replay the graph captured by capture_stg_graph (it belongs to the VideoOnly context that ran the capture)."""
         self._replay("stg", "no STG graph captured")
 
     # ------------------------------------------------------------------ classifier-free guidance with a frozen audio latent (AudioVideo engine)
-    def _guided_av_pair(self, neg: "LTXModel") -> Tuple["LTXModel", "LTXModel"]:
-        if not isinstance(neg, LTXModel):
-            raise ValueError("guidance needs a second LTXModel context (clone_sharing_weights()) for the negative prompt")
-        if not (self.is_av and neg.is_av):
-            raise ValueError("guided_step_av_ runs on AudioVideo contexts (a VideoOnly model has guided_step_)")
-        return self, neg
-
     def guided_step_av_(self, neg: "LTXModel", latent: torch.Tensor, audio_latent: torch.Tensor, video: Modality, audio: Modality, sigma: float,
                         sigma_next: float, cfg_scale: float, denoise_mask: Optional[torch.Tensor] = None,
                         clean_latent: Optional[torch.Tensor] = None) -> None:
@@ -826,7 +827,7 @@ class LTXModel:
         (Na, C) fp32 frozen -- both modalities through this context and through `neg` (clone_sharing_weights(), prepared by the caller with the
         negative contexts), then x0 x 2 + CFGGuider.guide + post_process_latent + Euler on the video alone, all enqueued by ONE C call
         (ltx2_dit_guided_step_av).  audio_latent is only read."""
-        pos, ng = self._guided_av_pair(neg)
+        pos, ng = self._contexts(neg, av=True)
         ts, n_ts, sg, ats, n_ats = pos._step_inputs(latent, video, sigma, audio_latent, audio)
         nv.check(pos._L.ltx2_dit_guided_step_av(pos._h, ng._h, nv.ptr(latent), nv.ptr(audio_latent), nv.ptr(ts), n_ts, nv.ptr(ats), n_ats, nv.ptr(sg),
                                                 nv.ptr(denoise_mask), nv.ptr(clean_latent), float(cfg_scale), float(sigma), float(sigma_next),
@@ -839,15 +840,10 @@ class LTXModel:
         (ltx2_dit_graph_capture_guided_av).  audio_denoise_mask (Na,) fp32: the frozen audio's all-zero mask, its per-token timesteps.  Both
         contexts are prepared first (per_token=True when a mask is given); the graph belongs to this context and replay_guided_av_graph()
         replays it.  The tensors must stay alive while it is replayed."""
-        pos, ng = self._guided_av_pair(neg)
-        assert pos._prep_key is not None and ng._prep_key is not None, "call prepare() on both contexts first"
+        pos, ng = self._contexts(neg, av=True)
         assert audio_latent.dtype == torch.float32 and audio_latent.is_contiguous()
-        arr, n, st, n_el = self._capture_inputs(sigmas, (denoise_mask, clean_latent), (audio_denoise_mask, audio_latent))
-        pos._graph_refs = (latent, audio_latent, denoise_mask, clean_latent, audio_denoise_mask, ng)
-        nv.check(pos._L.ltx2_dit_graph_capture_guided_av(pos._h, ng._h, nv.ptr(latent), nv.ptr(audio_latent), arr, n, nv.ptr(denoise_mask),
-                                                         n_el(denoise_mask), nv.ptr(clean_latent), n_el(clean_latent), nv.ptr(audio_denoise_mask),
-                                                         n_el(audio_denoise_mask), float(cfg_scale), st.cuda_stream))
-        self._graph_owner = ("guided_av", pos)
+        self._capture("guided_av", pos, ng, "ltx2_dit_graph_capture_guided_av", (latent, audio_latent), sigmas,
+                      [(denoise_mask, clean_latent), (audio_denoise_mask, audio_latent)], audio_denoise_mask, float(cfg_scale))
 
     def replay_guided_av_graph(self) -> None:
         """Replay the graph captured by capture_guided_av_graph."""
@@ -860,7 +856,7 @@ class LTXModel:
         """In-place: latent (N, C) fp32 <- one guided Euler step under CFGStarRescalingGuider (mode 0), LtxAPGGuider (1) or
         LegacyStatefulAPGGuider (2): both evaluations as guided_step_, then the sums kernel and the projected step kernel, all enqueued by ONE C
         call (ltx2_dit_projected_step).  momentum != 0 (mode 2): the engine keeps the running guidance; `first` starts it anew."""
-        pos, ng = self._guided_pair(neg)
+        pos, ng = self._contexts(neg)
         ts, n_ts, sg = pos._step_inputs(latent, video, sigma)
         nv.check(pos._L.ltx2_dit_projected_step(pos._h, ng._h, nv.ptr(latent), nv.ptr(ts), n_ts, nv.ptr(sg), nv.ptr(denoise_mask), nv.ptr(clean_latent),
                                                 int(mode), float(scale), float(eta), float(norm_threshold), float(momentum), int(bool(first)),
@@ -872,27 +868,15 @@ class LTXModel:
         """hipGraph-capture len(sigmas)-1 projected steps over `latent` (N, C fp32) as one linear chain (ltx2_dit_graph_capture_projected); with
         momentum its head clears the running guidance, so every replay is a fresh loop.  Both contexts are prepared first (per_token=True when
         a mask is given); the graph belongs to the positive VideoOnly context and replay_projected_graph() replays it."""
-        pos, ng = self._guided_pair(neg)
-        assert pos._prep_key is not None and ng._prep_key is not None, "call prepare() on both contexts first"
-        arr, n, st, n_el = self._capture_inputs(sigmas, (denoise_mask, clean_latent))
-        pos._graph_refs = (latent, denoise_mask, clean_latent, ng)
-        nv.check(pos._L.ltx2_dit_graph_capture_projected(pos._h, ng._h, nv.ptr(latent), arr, n, nv.ptr(denoise_mask), n_el(denoise_mask),
-                                                         nv.ptr(clean_latent), n_el(clean_latent), int(mode), float(scale), float(eta),
-                                                         float(norm_threshold), float(momentum), st.cuda_stream))
-        self._graph_owner = ("projected", pos)
+        pos, ng = self._contexts(neg)
+        self._capture("projected", pos, ng, "ltx2_dit_graph_capture_projected", (latent,), sigmas, [(denoise_mask, clean_latent)], int(mode),
+                      float(scale), float(eta), float(norm_threshold), float(momentum))
 
     def replay_projected_graph(self) -> None:
         """Replay the graph captured by capture_projected_graph (it belongs to the VideoOnly context that ran the capture)."""
         self._replay("projected", "no projected graph captured")
 
     # ------------------------------------------------------------------ res_2s second-order sampling (video-only engine)
-    def _video_pair(self, neg: Optional["LTXModel"]) -> Tuple["LTXModel", Optional["LTXModel"]]:
-        """(positive, negative or None) VideoOnly contexts of a step that may run without guidance (res_2s, STG): an AudioVideo model is used
-        through its video twin."""
-        if neg is None:
-            return (self._video_twin() if self.is_av else self), None
-        return self._guided_pair(neg)
-
     def res2s_step_(self, neg: Optional["LTXModel"], latent: torch.Tensor, video: Modality, video_sub: Optional[Modality], sigma: float,
                     sigma_next: float, cfg_scale: float, denoise_mask: Optional[torch.Tensor] = None,
                     clean_latent: Optional[torch.Tensor] = None) -> None:
@@ -901,7 +885,7 @@ class LTXModel:
         timesteps (those of the sub-sigma sqrt(sigma * sigma_next)), the combine kernel.  neg None: no guidance.  video_sub may be None
         only for the final step (sigma_next <= 0.001), which is one pair of evaluations and latent = d.  Both contexts are prepared by the
         caller (neg with the negative context)."""
-        pos, ng = self._video_pair(neg)
+        pos, ng = self._contexts(neg, optional=True)
         ts, n_ts, sg = pos._step_inputs(latent, video, sigma)
         ts_sub = sg_sub = None
         if video_sub is not None:
@@ -918,13 +902,8 @@ class LTXModel:
         """hipGraph-capture len(sigmas)-1 res_2s steps over `latent` (N, C fp32) as one linear chain (ltx2_dit_graph_capture_res2s).  Both
         contexts are prepared first (per_token=True when a mask is given); the graph belongs to the positive VideoOnly context and
         replay_res2s_graph() replays it.  The tensors must stay alive while it is replayed."""
-        pos, ng = self._video_pair(neg)
-        assert pos._prep_key is not None and (ng is None or ng._prep_key is not None), "call prepare() on both contexts first"
-        arr, n, st, n_el = self._capture_inputs(sigmas, (denoise_mask, clean_latent))
-        pos._graph_refs = (latent, denoise_mask, clean_latent, ng)
-        nv.check(pos._L.ltx2_dit_graph_capture_res2s(pos._h, None if ng is None else ng._h, nv.ptr(latent), arr, n, nv.ptr(denoise_mask),
-                                                     n_el(denoise_mask), nv.ptr(clean_latent), n_el(clean_latent), float(cfg_scale), st.cuda_stream))
-        self._graph_owner = ("res2s", pos)
+        pos, ng = self._contexts(neg, optional=True)
+        self._capture("res2s", pos, ng, "ltx2_dit_graph_capture_res2s", (latent,), sigmas, [(denoise_mask, clean_latent)], float(cfg_scale))
 
     def replay_res2s_graph(self) -> None:
         """Replay the graph captured by capture_res2s_graph (it belongs to the VideoOnly context that ran the capture)."""
@@ -941,12 +920,8 @@ class LTXModel:
         (those of the sub-sigma sqrt(sigma * sigma_next)), the combine kernel likewise.  The video is guided by cfg_scale, the audio by
         audio_cfg_scale; neg None: no guidance.  The sub modalities may be None only for the final step (sigma_next <= 0.001).  Both
         contexts are prepared by the caller (neg with the negative contexts)."""
-        if neg is not None and not isinstance(neg, LTXModel):
-            raise ValueError("guidance needs a second LTXModel context (clone_sharing_weights()) for the negative prompt")
-        if not (self.is_av and (neg is None or neg.is_av)):
-            raise ValueError("res2s_step_av_ runs on AudioVideo contexts (a VideoOnly model has res2s_step_)")
+        pos, ng = self._contexts(neg, av=True, optional=True)
         assert (video_sub is None) == (audio_sub is None), "video_sub and audio_sub go together (both None: the final step)"
-        pos, ng = self, neg
         ts, n_ts, sg, ats, n_ats = pos._step_inputs(latent, video, sigma, audio_latent, audio)
         ts_sub = ats_sub = sg_sub = None
         if video_sub is not None:

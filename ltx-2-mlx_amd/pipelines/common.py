@@ -212,6 +212,48 @@ def _with_latent(state: LatentState, lat: torch.Tensor) -> LatentState:
     return state.replace(latent=lat[None].to(state.latent.dtype))
 
 
+def _prepare_contexts(model, guided: bool, per_token: bool, positions, context, negative_context, audio_positions=None, audio_context=None,
+                      negative_audio_context=None):
+    """What every device-resident loop prepares: the positive context on `model` and, when guided, the negative one on a clone over the same
+    weights, both with the same per_token.  -> the clone, or None."""
+    neg = model.clone_sharing_weights() if guided else None
+    model.prepare(context, positions, per_token=per_token, audio_context=audio_context, audio_positions=audio_positions)
+    if guided:
+        neg.prepare(negative_context, positions, per_token=per_token, audio_context=negative_audio_context, audio_positions=audio_positions)
+    return neg
+
+
+def _run_steps(n: int, callback, use_hip_graph: bool, capture: Optional[Callable[[], None]], replay: Optional[Callable[[], None]],
+               step: Callable[[int], None], final: Optional[Callable[[int], bool]] = None) -> None:
+    """How every device-resident loop runs its n steps: with no callback and fewer than 64 of them as one captured graph, replayed once
+    (capture None: the loop has no captured form); otherwise step(i) and the callback n times.  final(i): step i is the loop's last one
+    (res_2s), after it the loop ends without a callback."""
+    if capture is not None and use_hip_graph and callback is None and n < 64:
+        capture_and_replay(capture, replay)
+        return
+    for i in range(n):
+        step(i)
+        if final is not None and final(i):
+            break
+        if callback:
+            callback(i + 1, n)
+
+
+def _res2s_sigmas(sigmas) -> Tuple[int, List[float]]:
+    """The res_2s loops' sigma handling, the reference's verbatim: -> (the step count len(sigmas) - 1, taken BEFORE a trailing 0.0 is
+    replaced by [0.0011, 0.0]; the sigma_0 .. sigma_n those steps read, rounded to fp32, the engine's scalar type)."""
+    sig = [float(s) for s in sigmas]
+    n = len(sig) - 1
+    if sig[-1] == 0.0:
+        sig = sig[:-1] + [0.0011, 0.0]
+    return n, torch.tensor(sig[: n + 1], dtype=torch.float32).tolist()
+
+
+def _res2s_final(sig: List[float], i: int) -> bool:
+    """Step i takes the reference's final-step branch: latent = denoised, no sub-sigma evaluation."""
+    return sig[i + 1] <= 0.001 or sig[i + 1] == sig[i]
+
+
 def joint_denoise_loop(transformer, is_av_model: bool, video_state: LatentState, audio_state: Optional[LatentState], sigmas,
                        video_context: torch.Tensor, audio_context: Optional[torch.Tensor], stepper, callback=None,
                        use_hip_graph: bool = False, *, negative_video_context: Optional[torch.Tensor] = None,
@@ -318,19 +360,11 @@ def guided_denoise_loop(transformer, video_state: LatentState, sigmas, context: 
     sig = [float(s) for s in sigmas]
     n = len(sig) - 1
     model, uniform, lat, mask, clean = _video_loop_inputs(model, video_state)
-    neg = model.clone_sharing_weights()
-    model.prepare(context, video_state.positions, per_token=not uniform)
-    neg.prepare(negative_context, video_state.positions, per_token=not uniform)
-    if use_hip_graph and callback is None and n < 64:
-        capture_and_replay(lambda: model.capture_guided_graph(neg, lat, sig, guider.scale, denoise_mask=mask, clean_latent=clean),
-                            model.replay_guided_graph)
-    else:
-        for i in range(n):
-            st = video_state.replace(latent=lat[None])
-            model.guided_step_(neg, lat, modality_from_state(st, context, sig[i], uniform=uniform), sig[i], sig[i + 1], guider.scale,
-                               denoise_mask=mask, clean_latent=clean)
-            if callback:
-                callback(i + 1, n)
+    neg = _prepare_contexts(model, True, not uniform, video_state.positions, context, negative_context)
+    cond = dict(denoise_mask=mask, clean_latent=clean)
+    vm = lambda i: modality_from_state(video_state.replace(latent=lat[None]), context, sig[i], uniform=uniform)      # noqa: E731
+    _run_steps(n, callback, use_hip_graph, lambda: model.capture_guided_graph(neg, lat, sig, guider.scale, **cond), model.replay_guided_graph,
+               lambda i: model.guided_step_(neg, lat, vm(i), sig[i], sig[i + 1], guider.scale, **cond))
     return _with_latent(video_state, lat)
 
 
@@ -359,27 +393,22 @@ def stg_denoise_loop(transformer, video_state: LatentState, sigmas, context: tor
     n = len(sig) - 1
     model, uniform, lat, mask, clean = _video_loop_inputs(model, video_state)
     model.set_stg_blocks(stg_blocks)
-    neg = model.clone_sharing_weights() if cfg else None
-    model.prepare(context, video_state.positions, per_token=not uniform)
-    if cfg:
-        neg.prepare(negative_context, video_state.positions, per_token=not uniform)
+    neg = _prepare_contexts(model, cfg, not uniform, video_state.positions, context, negative_context)
     cfg_scale = guider.scale if cfg else 1.0
     vel_p = torch.empty_like(lat)
-    if use_hip_graph and callback is None and n < 64:
-        capture_and_replay(lambda: model.capture_stg_graph(neg, lat, sig, cfg_scale, stg_guider.scale, vel_p, stg_cutoff, denoise_mask=mask,
-                                                           clean_latent=clean), model.replay_stg_graph)
-    else:
-        for i in range(n):
-            st = video_state.replace(latent=lat[None])
-            vm = modality_from_state(st, context, sig[i], uniform=uniform)
-            if (i + 1) / n <= stg_cutoff:
-                model.stg_step_(neg, lat, vm, sig[i], sig[i + 1], cfg_scale, stg_guider.scale, vel_p, denoise_mask=mask, clean_latent=clean)
-            elif cfg:
-                model.guided_step_(neg, lat, vm, sig[i], sig[i + 1], cfg_scale, denoise_mask=mask, clean_latent=clean)
-            else:
-                model.denoise_step_(lat, vm, sig[i], sig[i + 1], denoise_mask=mask, clean_latent=clean)
-            if callback:
-                callback(i + 1, n)
+    cond = dict(denoise_mask=mask, clean_latent=clean)
+
+    def step(i):
+        vm = modality_from_state(video_state.replace(latent=lat[None]), context, sig[i], uniform=uniform)
+        if (i + 1) / n <= stg_cutoff:
+            model.stg_step_(neg, lat, vm, sig[i], sig[i + 1], cfg_scale, stg_guider.scale, vel_p, **cond)
+        elif cfg:
+            model.guided_step_(neg, lat, vm, sig[i], sig[i + 1], cfg_scale, **cond)
+        else:
+            model.denoise_step_(lat, vm, sig[i], sig[i + 1], **cond)
+
+    _run_steps(n, callback, use_hip_graph, lambda: model.capture_stg_graph(neg, lat, sig, cfg_scale, stg_guider.scale, vel_p, stg_cutoff, **cond),
+               model.replay_stg_graph, step)
     return _with_latent(video_state, lat)
 
 
@@ -410,20 +439,14 @@ def frozen_audio_guided_loop(transformer, video_state: LatentState, audio_state:
     alat = audio_state.latent[0].float().contiguous()
     amask = audio_state.denoise_mask[0].reshape(-1).float().contiguous()
     negative_audio_context = negative_audio_context if negative_audio_context is not None else audio_context
-    neg = model.clone_sharing_weights()
-    model.prepare(video_context, video_state.positions, per_token=True, audio_context=audio_context, audio_positions=audio_state.positions)
-    neg.prepare(negative_video_context, video_state.positions, per_token=True, audio_context=negative_audio_context, audio_positions=audio_state.positions)
-    if use_hip_graph and callback is None and n < 64:
-        capture_and_replay(lambda: model.capture_guided_av_graph(neg, lat, alat, sig, cfg_scale, denoise_mask=mask, clean_latent=clean,
-                                                                 audio_denoise_mask=amask), model.replay_guided_av_graph)
-    else:
-        for i in range(n):
-            st = video_state.replace(latent=lat[None])
-            model.guided_step_av_(neg, lat, alat, modality_from_state(st, video_context, sig[i], uniform=uniform),
-                                  audio_modality_from_state(audio_state, audio_context, sig[i]), sig[i], sig[i + 1], cfg_scale,
-                                  denoise_mask=mask, clean_latent=clean)
-            if callback:
-                callback(i + 1, n)
+    neg = _prepare_contexts(model, True, True, video_state.positions, video_context, negative_video_context, audio_state.positions, audio_context,
+                            negative_audio_context)
+    cond = dict(denoise_mask=mask, clean_latent=clean)
+    vm = lambda i: modality_from_state(video_state.replace(latent=lat[None]), video_context, sig[i], uniform=uniform)      # noqa: E731
+    _run_steps(n, callback, use_hip_graph, lambda: model.capture_guided_av_graph(neg, lat, alat, sig, cfg_scale, audio_denoise_mask=amask, **cond),
+               model.replay_guided_av_graph,
+               lambda i: model.guided_step_av_(neg, lat, alat, vm(i), audio_modality_from_state(audio_state, audio_context, sig[i]), sig[i], sig[i + 1],
+                                               cfg_scale, **cond))
     return _with_latent(video_state, lat), audio_state
 
 
@@ -468,19 +491,11 @@ def projected_denoise_loop(transformer, video_state: LatentState, sigmas, contex
     sig = [float(s) for s in sigmas]
     n = len(sig) - 1
     model, uniform, lat, mask, clean = _video_loop_inputs(model, video_state)
-    neg = model.clone_sharing_weights()
-    model.prepare(context, video_state.positions, per_token=not uniform)
-    neg.prepare(negative_context, video_state.positions, per_token=not uniform)
-    if use_hip_graph and callback is None and n < 64:
-        capture_and_replay(lambda: model.capture_projected_graph(neg, lat, sig, denoise_mask=mask, clean_latent=clean, **args),
-                            model.replay_projected_graph)
-    else:
-        for i in range(n):
-            st = video_state.replace(latent=lat[None])
-            model.projected_step_(neg, lat, modality_from_state(st, context, sig[i], uniform=uniform), sig[i], sig[i + 1], first=(i == 0),
-                                  denoise_mask=mask, clean_latent=clean, **args)
-            if callback:
-                callback(i + 1, n)
+    neg = _prepare_contexts(model, True, not uniform, video_state.positions, context, negative_context)
+    cond = dict(denoise_mask=mask, clean_latent=clean, **args)
+    vm = lambda i: modality_from_state(video_state.replace(latent=lat[None]), context, sig[i], uniform=uniform)      # noqa: E731
+    _run_steps(n, callback, use_hip_graph, lambda: model.capture_projected_graph(neg, lat, sig, **cond), model.replay_projected_graph,
+               lambda i: model.projected_step_(neg, lat, vm(i), sig[i], sig[i + 1], first=(i == 0), **cond))
     return _with_latent(video_state, lat)
 
 
@@ -496,31 +511,19 @@ def res2s_denoise_loop(transformer, video_state: LatentState, sigmas, context: t
     engine's scalar type, 0.0011 included) and the latent is held in fp32 across the loop, as guided_denoise_loop holds it; the
     reference's per-step cast to the state dtype is not reproduced.  `transformer` is an X0Model; an AudioVideo model is used through its
     video twin (res2s_av_denoise_loop steps both modalities).  Returns the video state."""
-    sig = [float(s) for s in sigmas]
-    n = len(sig) - 1
-    if sig[-1] == 0.0:
-        sig = sig[:-1] + [0.0011, 0.0]
-    sig = torch.tensor(sig[: n + 1], dtype=torch.float32).tolist()             # the n steps read sigma_0 .. sigma_n only
+    n, sig = _res2s_sigmas(sigmas)
     model, uniform, lat, mask, clean = _video_loop_inputs(transformer.velocity_model, video_state)
     guide = (cfg_scale > 1.0 or audio_cfg_scale > 1.0) and negative_context is not None
-    neg = model.clone_sharing_weights() if guide else None
-    model.prepare(context, video_state.positions, per_token=not uniform)
-    if guide:
-        neg.prepare(negative_context, video_state.positions, per_token=not uniform)
-    if use_hip_graph and callback is None and n < 64:
-        capture_and_replay(lambda: model.capture_res2s_graph(neg, lat, sig, cfg_scale, denoise_mask=mask, clean_latent=clean),
-                            model.replay_res2s_graph)
-    else:
-        for i in range(n):
-            final = sig[i + 1] <= 0.001 or sig[i + 1] == sig[i]
-            st = video_state.replace(latent=lat[None])
-            sub = None if final else modality_from_state(st, context, math.sqrt(sig[i] * sig[i + 1]), uniform=uniform)
-            model.res2s_step_(neg, lat, modality_from_state(st, context, sig[i], uniform=uniform), sub, sig[i], sig[i + 1], cfg_scale,
-                              denoise_mask=mask, clean_latent=clean)
-            if final:
-                break
-            if callback:
-                callback(i + 1, n)
+    neg = _prepare_contexts(model, guide, not uniform, video_state.positions, context, negative_context)
+    cond = dict(denoise_mask=mask, clean_latent=clean)
+    final = lambda i: _res2s_final(sig, i)      # noqa: E731
+
+    def step(i):
+        st = video_state.replace(latent=lat[None])
+        sub = None if final(i) else modality_from_state(st, context, math.sqrt(sig[i] * sig[i + 1]), uniform=uniform)
+        model.res2s_step_(neg, lat, modality_from_state(st, context, sig[i], uniform=uniform), sub, sig[i], sig[i + 1], cfg_scale, **cond)
+
+    _run_steps(n, callback, use_hip_graph, lambda: model.capture_res2s_graph(neg, lat, sig, cfg_scale, **cond), model.replay_res2s_graph, step, final)
     return _with_latent(video_state, lat)
 
 
@@ -542,11 +545,7 @@ def res2s_av_denoise_loop(transformer, video_state: LatentState, audio_state: La
         raise ValueError("res2s_av_denoise_loop requires an audio-video (AV) model and an audio state")
     if audio_context is None:
         raise ValueError("AudioVideo model: audio_encoding (the audio text context) is required")
-    sig = [float(s) for s in sigmas]
-    n = len(sig) - 1
-    if sig[-1] == 0.0:
-        sig = sig[:-1] + [0.0011, 0.0]
-    sig = torch.tensor(sig[: n + 1], dtype=torch.float32).tolist()             # the n steps read sigma_0 .. sigma_n only
+    n, sig = _res2s_sigmas(sigmas)
     guide = (cfg_scale > 1.0 or audio_cfg_scale > 1.0) and negative_video_context is not None
     if guide and negative_audio_context is None:
         if negative_video_context.shape[-1] != audio_context.shape[-1]:
@@ -555,28 +554,23 @@ def res2s_av_denoise_loop(transformer, video_state: LatentState, audio_state: La
         negative_audio_context = negative_video_context
     model, uniform, lat, mask, clean = _video_loop_inputs(model, video_state, video_only=False)
     _, a_uniform, alat, amask, aclean = _video_loop_inputs(model, audio_state, video_only=False)
-    per_token = not (uniform and a_uniform)
-    neg = model.clone_sharing_weights() if guide else None
-    model.prepare(video_context, video_state.positions, per_token=per_token, audio_context=audio_context, audio_positions=audio_state.positions)
-    if guide:
-        neg.prepare(negative_video_context, video_state.positions, per_token=per_token, audio_context=negative_audio_context,
-                    audio_positions=audio_state.positions)
+    neg = _prepare_contexts(model, guide, not (uniform and a_uniform), video_state.positions, video_context, negative_video_context,
+                            audio_state.positions, audio_context, negative_audio_context)
     cond = dict(denoise_mask=mask, clean_latent=clean, audio_denoise_mask=amask, audio_clean_latent=aclean)
+    final = lambda i: _res2s_final(sig, i)      # noqa: E731
     if use_hip_graph:
         _note_eager_once("the joint audio+video res_2s loop has no captured form")
-    for i in range(n):
-        final = sig[i + 1] <= 0.001 or sig[i + 1] == sig[i]
+
+    def step(i):
         st, ast = video_state.replace(latent=lat[None]), audio_state.replace(latent=alat[None])
         sub = asub = None
-        if not final:
+        if not final(i):
             s_sub = math.sqrt(sig[i] * sig[i + 1])
             sub = modality_from_state(st, video_context, s_sub, uniform=uniform)
             asub = audio_modality_from_state(ast, audio_context, s_sub, uniform=a_uniform)
         model.res2s_step_av_(neg, lat, alat, modality_from_state(st, video_context, sig[i], uniform=uniform),
                              audio_modality_from_state(ast, audio_context, sig[i], uniform=a_uniform), sub, asub, sig[i], sig[i + 1], cfg_scale,
                              audio_cfg_scale, **cond)
-        if final:
-            break
-        if callback:
-            callback(i + 1, n)
+
+    _run_steps(n, callback, use_hip_graph, None, None, step, final)
     return _with_latent(video_state, lat), _with_latent(audio_state, alat)
