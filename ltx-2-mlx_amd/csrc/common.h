@@ -132,10 +132,40 @@ __device__ __forceinline__ float dpp_f32(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
+}
+
+// Reductions over a block of 256 threads (four waves) through `red` in LDS, in a fixed order: the wave's shuffles, then the four
+// wave values left to right.  Every thread gets the result.
+// Two sums at once (float or double), red[8].  RED_BUSY: other waves may still read `red` from the block's last reduction (a row
+// loop), so a barrier precedes the writes; a kernel that reduces once per block passes false and has the closing barrier alone.
+template <bool RED_BUSY = true, class T>
+__device__ __forceinline__ void block_sum2_256(T& a, T& b, T* red) {
+    a = wave_sum(a);
+    b = wave_sum(b);
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (RED_BUSY) __syncthreads();
+    if (lane == 0) {
+        red[wv] = a;
+        red[4 + wv] = b;
+    }
+    __syncthreads();
+    a = red[0] + red[1] + red[2] + red[3];
+    b = red[4] + red[5] + red[6] + red[7];
+}
+// One maximum, red[4]; RED_BUSY as above, false by default: the stand-alone quantiser reduces once and has no barrier in front.
+template <bool RED_BUSY = false>
+__device__ __forceinline__ float block_max_256(float v, float* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    if (RED_BUSY) __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
 
 // Individually rounded fp32 operations for the kernels that replace separate torch ops bit for bit.  HIP's __fmul_rn / __fadd_rn /

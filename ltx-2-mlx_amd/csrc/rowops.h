@@ -1,7 +1,11 @@
-// HBM-bound row / elementwise kernels of the DiT step and the VAE decoder: host launchers.
+// HBM-bound row / elementwise kernels: host launchers.  One header for three translation units:
+//   rowops.hip     the DiT step's row kernels and small utilities
+//   groupnorm.hip  the GroupNorms of the spatial and temporal upscalers
+//   vae_glue.hip   the VAE decoder's and encoder's norm / activation / layout glue
 #pragma once
 #include "common.h"
 
+// ---- rowops.hip: DiT step ----
 // out_bf16[row][:] = norm(x_f32[row][:]) * (1 + scale) + shift
 //   norm  = RMS (layer_norm == 0) or mean-centred LayerNorm without affine (layer_norm == 1)
 //   scale = scale_tab[d] + scale_emb[row*emb_stride + d]   (either pointer may be null -> 0)
@@ -15,10 +19,11 @@ int norm_mod_launch(const float* x, long ldx, bf16* out, long ldo, int rows, int
 
 // out_g[row][:] = rms_norm(x[row][:]) * (1 + scale_tab[g] + scale_emb[g]) + shift_tab[g] + shift_emb[g] for g = 0, 1 (row-invariant tables; any
 // pointer may be null): two modulations of one normalised stream from ONE read of x (the AudioVideo block's cross-modal attention inputs)
-// comb[l][i] = tab[l][i] + emb[i] for l < layers, i < n (round 4: every layer's AdaLN rows for one step in one launch)
-int adaln_combine_launch(const float* tab, const float* emb, float* out, int layers, long n, hipStream_t stream);
 int norm_mod2_launch(const float* x, long ldx, bf16* out0, bf16* out1, long ldo, int rows, int D, float eps, const float* const* scale_tab,
                      const float* const* shift_tab, const float* const* scale_emb, const float* const* shift_emb, hipStream_t stream);
+
+// comb[l][i] = tab[l][i] + emb[i] for l < layers, i < n (round 4: every layer's AdaLN rows for one step in one launch)
+int adaln_combine_launch(const float* tab, const float* emb, float* out, int layers, long n, hipStream_t stream);
 
 // In-place on bf16 rows: for each of nseg segments (q, k) at column offsets seg_off[i] of width D:
 //   y = x * rsqrt(mean(x^2) + eps) * weight_i ;  then (if cos != null) SPLIT RoPE per head:
@@ -61,7 +66,7 @@ int quant_rows_fp8_launch(const bf16* x, long ldx, int rows, int K, unsigned cha
 // out_bf16 = bf16(f32(fp8_e4m3fn) * scale): checkpoint weights quantised with a per-tensor weight_scale
 int dequant_fp8_launch(const unsigned char* in, float scale, bf16* out, long n, hipStream_t stream);
 
-// ---- spatial upscaler (channels-last bf16 [P][C]) ----
+// ---- groupnorm.hip: spatial upscaler (channels-last bf16 [P][C]) ----
 // y = [silu]( GroupNorm_G(x over (C/G, all positions)) * gamma + beta + res );  scratch: 2*G*(1 + ceil(P/16)) floats
 int groupnorm_silu_launch(const bf16* x, const bf16* res, bf16* y, long P, int C, int G, float eps, const float* gamma,
                           const float* beta, float* scratch, int act, hipStream_t stream);
@@ -69,13 +74,8 @@ int groupnorm_silu_launch(const bf16* x, const bf16* res, bf16* y, long P, int C
 // mlx.nn.GroupNorm's default) or c / (C/G).  One launch, fp64 statistics in LDS; scratch is unused and may be null.
 int groupnorm_frames_silu_launch(const bf16* x, const bf16* res, bf16* y, int frames, long P_frame, int C, int G, int interleaved,
                                  float eps, const float* gamma, const float* beta, float* scratch, int act, hipStream_t stream);
-// VAE encoder downsample tail: out = space_to_depth(y) + group_mean(space_to_depth(x))   (see ltx2hip.h)
-int s2d_downsample_launch(const bf16* y, const bf16* x, bf16* out, int T, int H, int W, int Cc, int Cin, int st, int sh, int sw,
-                          hipStream_t stream);
-// out fp32 [C][P] = (x[P][C] - mean[c]) / std[c]
-int latent_normalize_nchw_launch(const bf16* x, const float* mean, const float* stdv, float* out, int C, long P, hipStream_t stream);
 
-// ---- VAE decoder elementwise ops (channels-last bf16 activations [P][C]) ----
+// ---- vae_glue.hip: VAE decoder elementwise ops (channels-last bf16 activations [P][C]) ----
 // latent fp32 NCTHW [C][P] -> bf16 [P][C]: v = latent*std[c] + mean[c]; if noise_scale>0: v = noise*ns + (1-ns)*v
 int vae_prepare_latent_launch(const float* latent, const float* std, const float* mean, const float* noise,
                               float noise_scale, bf16* out, int C, long P, hipStream_t stream);
@@ -86,8 +86,9 @@ int pixnorm_mod_silu_launch(const bf16* x, bf16* y, long P, int C, float eps, co
 // implicit-GEMM conv of gemm_v4.hip reads
 int pixnorm_mod_silu_padded_launch(const bf16* x, bf16* y, int T, int H, int W, int C, float eps, const float* tab, const float* te,
                                    int shift_row, int scale_row, int pad_front, hipStream_t stream);
-// conv_out [T][H][W][48] bf16 -> video fp32 [3][T][4H][4W]  (reference ops.unpatchify packing (c, r_w, r_h))
+// y = x copied into the same padded volume, no arithmetic
 int pad_volume_launch(const bf16* x, bf16* y, int T, int H, int W, int C, int pad_front, hipStream_t stream);
+// conv_out [T][H][W][48] bf16 -> video fp32 [3][T][4H][4W]  (reference ops.unpatchify packing (c, r_w, r_h))
 int vae_unpatchify_launch(const bf16* x, float* video, int T, int H, int W, hipStream_t stream);
 // video fp32 [3][T][H][W] -> frames uint8 [T][H][W][3] = trunc(clip((v+1)/2,0,1)*255)
 int video_to_uint8_launch(const float* video, unsigned char* frames, int T, int H, int W, hipStream_t stream);
@@ -96,3 +97,9 @@ int video_chunk_to_uint8_launch(const float* cur, const float* prev, const float
 int tile_blend_accumulate_launch(const float* tile, int dt, int dh, int dw, int nt, int nh, int nw, const float* mt, const float* mh,
                                  const float* mw, float* out, float* wsum, int OT, int OH, int OW, int t0, int h0, int w0, hipStream_t stream);
 int tile_blend_finish_launch(float* out, const float* wsum, long plane, hipStream_t stream);
+// ---- vae_glue.hip: VAE encoder ----
+// downsample tail: out = space_to_depth(y) + group_mean(space_to_depth(x))   (see ltx2hip.h)
+int s2d_downsample_launch(const bf16* y, const bf16* x, bf16* out, int T, int H, int W, int Cc, int Cin, int st, int sh, int sw,
+                          hipStream_t stream);
+// out fp32 [C][P] = (x[P][C] - mean[c]) / std[c]
+int latent_normalize_nchw_launch(const bf16* x, const float* mean, const float* stdv, float* out, int C, long P, hipStream_t stream);

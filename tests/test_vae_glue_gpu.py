@@ -1,4 +1,4 @@
-"""Leaf tests of the VAE glue kernels of csrc/rowops.hip and the plain sampler step of csrc/sampler.hip: tile blend, chunk cross-fade, uint8
+"""Leaf tests of the VAE glue kernels of csrc/vae_glue.hip, the cast of csrc/rowops.hip and the plain sampler step of csrc/sampler.hip: tile blend, chunk cross-fade, uint8
 conversion, unpatchify, latent (un)normalise, space-to-depth downsample, fp32 -> 16-bit cast, x0 / Euler step.
 
 These kernels are index arithmetic (LDS transposes, space-to-depth channel orders, tile offsets, grid-stride loops, ragged tails), and most
