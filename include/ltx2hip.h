@@ -371,6 +371,44 @@ int ltx2_projected_euler_step(const float* x, const float* vel_cond, const float
                               const float* clean, const float* running, const double* partials, int mode, float scale, float eta,
                               float norm_threshold, float sigma, float sigma_next, float* out, float* scalars_out, int rows, int C, void* stream);
 
+/* MultiModalGuider.calculate (components/guiders.py:244-273) and the Euler step behind it, the stage-1 step of the two-stage pipeline
+ * (pipelines/two_stage.py:366-390), over [rows][C] fp32.  Every fp32 operation is individually rounded, in the reference's order, so the
+ * un-rescaled step equals the separate fp32 array ops bit for bit.  Per element, t = ts[row * ts_stride]:
+ *   a = x - t*vel_cond;  u, p, m the same from vel_uncond (negative prompt), vel_perturbed (self-attentions skipped: ltx2_dit_forward_perturbed_av)
+ *   and vel_isolated (cross-modal attentions skipped: ltx2_dit_forward_isolated_av)
+ *   pred = a;  vel_uncond:    pred = pred + (cfg_scale - 1)*(a - u)
+ *              vel_perturbed: pred = pred + stg_scale*(a - p)
+ *              vel_isolated:  pred = pred + (modality_scale - 1)*(a - m)
+ *   d = mask ? pred*mask[row] + clean*(1 - mask[row]) : pred;  out = x + ((x - d) * (1/sigma)) * (sigma_next - sigma)
+ * A term is there exactly when its velocity is non-NULL, whatever its scale (the reference adds the term of every pass that ran).  The scale
+ * differences are formed in fp32.  ltx2_mm_guided_euler_step_pair: two latents in ONE launch, v_ then a_, each with its own operands, scales and
+ * shape; each segment's output equals the single entry's bit for bit; 16-byte accesses only when BOTH segments qualify.
+ * With MultiModalGuiderParams.rescale_scale != 0 the step is two passes:
+ * ltx2_mm_guidance_sums: S_a = sum a, S_aa = sum a*a, S_p = sum pred, S_pp = sum pred*pred in fp64 over ALL rows, in the order of
+ *   ltx2_guidance_sums, into partials[ltx2_guidance_sums_blocks(rows, C)][4] (8-byte aligned); pred_out (may be NULL) receives pred.
+ * ltx2_mm_rescaled_euler_step: every block adds the partial rows in index order and derives in fp64, n = rows*C,
+ *   var = (S2 - S1*S1/n)/n (the population variance, as mx.var);  f = rescale_scale*sqrt((var_a + 1e-8)/(var_p + 1e-8)) + (1 - rescale_scale),
+ *   rounded once to fp32; block 0 stores f to scalars_out (may be NULL); then the step above with pred*f in place of pred.
+ * out may equal x (any input).  ts_stride, mask / clean, the access width and sigma == 0 as in ltx2_guided_euler_step.
+ * (additive entries of ABI version 3)                                                                                                  */
+int ltx2_mm_guided_euler_step(const float* x, const float* vel_cond, const float* vel_uncond, const float* vel_perturbed, const float* vel_isolated,
+                              const float* ts, int64_t ts_stride, const float* mask, const float* clean, float cfg_scale, float stg_scale,
+                              float modality_scale, float sigma, float sigma_next, float* out, int rows, int C, void* stream);
+int ltx2_mm_guided_euler_step_pair(const float* v_x, const float* v_vel_cond, const float* v_vel_uncond, const float* v_vel_perturbed,
+                                   const float* v_vel_isolated, const float* v_ts, int64_t v_ts_stride, const float* v_mask, const float* v_clean,
+                                   float v_cfg_scale, float v_stg_scale, float v_modality_scale, float* v_out, int v_rows, int v_C, const float* a_x,
+                                   const float* a_vel_cond, const float* a_vel_uncond, const float* a_vel_perturbed, const float* a_vel_isolated,
+                                   const float* a_ts, int64_t a_ts_stride, const float* a_mask, const float* a_clean, float a_cfg_scale,
+                                   float a_stg_scale, float a_modality_scale, float* a_out, int a_rows, int a_C, float sigma, float sigma_next,
+                                   void* stream);
+int ltx2_mm_guidance_sums(const float* x, const float* vel_cond, const float* vel_uncond, const float* vel_perturbed, const float* vel_isolated,
+                          const float* ts, int64_t ts_stride, float cfg_scale, float stg_scale, float modality_scale, double* partials, float* pred_out,
+                          int rows, int C, void* stream);
+int ltx2_mm_rescaled_euler_step(const float* x, const float* vel_cond, const float* vel_uncond, const float* vel_perturbed, const float* vel_isolated,
+                                const float* ts, int64_t ts_stride, const float* mask, const float* clean, const double* partials, float cfg_scale,
+                                float stg_scale, float modality_scale, float rescale_scale, float sigma, float sigma_next, float* out,
+                                float* scalars_out, int rows, int C, void* stream);
+
 /* VAE elementwise glue (simple_decoder.py:492-498, 228-238/339-342, ops.py:109-125, :792-798)  */
 int ltx2_vae_prepare_latent(const float* latent, const float* std, const float* mean, const float* noise,
                             float noise_scale, void* out_bf16, int C, int64_t P, void* stream);
@@ -483,6 +521,14 @@ int ltx2_dit_forward_perturbed(ltx2_dit* ctx, const float* latent, const float* 
 int ltx2_dit_forward_perturbed_av(ltx2_dit* ctx, const float* v_latent, const float* v_timesteps, int n_v_timesteps,
                                   const float* v_sigma, const float* a_latent, const float* a_timesteps, int n_a_timesteps,
                                   const float* a_sigma, float* v_velocity, float* a_velocity, void* stream);
+/* The modality-isolated forward (the reference's SKIP_A2V_CROSS_ATTN and SKIP_V2A_CROSS_ATTN over every block together, pipelines/two_stage.py:356-364):
+ * the arguments and the program of ltx2_dit_forward_av with the cross-modal attention of EVERY layer left out -- launches that do not happen, both
+ * residual streams unchanged there -- so each modality's velocity depends on its own latent alone.  Both stream joins per layer, the early text
+ * K / V and the output heads are those of the plain forward.  A per-layer set or a single direction is not built.  LTX2_E_INVALID on a VideoOnly
+ * context.  (additive entry of ABI version 3)                                                                                           */
+int ltx2_dit_forward_isolated_av(ltx2_dit* ctx, const float* v_latent, const float* v_timesteps, int n_v_timesteps,
+                                 const float* v_sigma, const float* a_latent, const float* a_timesteps, int n_a_timesteps,
+                                 const float* a_sigma, float* v_velocity, float* a_velocity, void* stream);
 
 /* One sampling step: forward -> x0 = latent - ts*v -> post_process -> Euler, latent updated in
  * place (pipelines/distilled.py:214-253; scripts/generate.py:1942-1979).  x0_out may be NULL.  */
@@ -596,6 +642,24 @@ int ltx2_dit_res2s_step_av(ltx2_dit* ctx, ltx2_dit* neg, float* v_latent, float*
                            const float* a_timesteps, int n_a_timesteps, const float* sigma_dev, const float* v_ts_sub, const float* a_ts_sub,
                            const float* sub_sigma_dev, const float* v_mask, const float* v_clean, const float* a_mask, const float* a_clean,
                            float cfg_scale, float audio_cfg_scale, float sigma, float sigma_next, void* stream);
+/* One step of the two-stage pipeline's stage 1 on the AudioVideo engine (pipelines/two_stage.py:314-401): BOTH latents are stepped under
+ * MultiModalGuider.calculate, each modality with its own scales.  In order on the caller's stream: forward(ctx) and, with neg, forward(neg) on both
+ * modalities (as ltx2_dit_guided_step_av builds them); with the perturbed scratch pair, ltx2_dit_forward_perturbed_av on ctx into it; with the
+ * isolated scratch pair, ltx2_dit_forward_isolated_av on ctx into it; then the element-wise passes in place: when both rescale scales are 0 ONE
+ * ltx2_mm_guided_euler_step_pair, otherwise per modality ltx2_mm_guided_euler_step or ltx2_mm_guidance_sums + ltx2_mm_rescaled_euler_step.  A
+ * pass that did not run contributes no term: neg NULL, a NULL scratch pair.  The scratch buffers are the caller's, [N][out_channels] and
+ * [Na][audio_out_channels] fp32, a pair both NULL or both set; n_*: their ELEMENT counts, checked against the bound shapes.  The partials of a
+ * modality that rescales are allocated on first use for the bound shapes, before anything is enqueued, and freed with ctx.  The step is
+ * enqueued eagerly only: there is no captured form of the joint loop.
+ * LTX2_E_INVALID, before anything is launched: the rules of ltx2_dit_guided_step_av (with neg NULL the same rules on ctx alone), a mask without
+ * its clean latent, sigma == 0, a scratch of the wrong length or half a pair, a perturbed scratch with both sets of ltx2_dit_set_stg_blocks empty.
+ * (additive entry of ABI version 3)                                                                                                    */
+int ltx2_dit_mm_guided_step_av(ltx2_dit* ctx, ltx2_dit* neg, float* v_latent, float* a_latent, const float* v_timesteps, int n_v_timesteps,
+                               const float* a_timesteps, int n_a_timesteps, const float* sigma_dev, const float* v_mask, const float* v_clean,
+                               const float* a_mask, const float* a_clean, float* v_vel_isolated, int64_t n_v_isolated, float* a_vel_isolated,
+                               int64_t n_a_isolated, float* v_vel_perturbed, int64_t n_v_perturbed, float* a_vel_perturbed, int64_t n_a_perturbed,
+                               float v_cfg_scale, float v_stg_scale, float v_modality_scale, float v_rescale_scale, float a_cfg_scale, float a_stg_scale,
+                               float a_modality_scale, float a_rescale_scale, float sigma, float sigma_next, void* stream);
 int ltx2_dit_graph_capture_av(ltx2_dit* ctx, float* v_latent, float* a_latent, const float* host_sigmas, int n_steps,
                               void* stream);
 int ltx2_dit_graph_launch(ltx2_dit* ctx, void* stream);

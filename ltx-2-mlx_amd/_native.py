@@ -98,6 +98,11 @@ SIGNATURES = {
     "ltx2_guidance_sums_blocks": (i32, [i32, i32]),
     "ltx2_guidance_sums": (i32, [vp, vp, vp, vp, i64, vp, i32, f32, vp, i32, i32, vp]),
     "ltx2_projected_euler_step": (i32, [vp, vp, vp, vp, i64, vp, vp, vp, vp, i32, f32, f32, f32, f32, f32, vp, vp, i32, i32, vp]),
+    "ltx2_mm_guided_euler_step": (i32, [vp, vp, vp, vp, vp, vp, i64, vp, vp, f32, f32, f32, f32, f32, vp, i32, i32, vp]),
+    "ltx2_mm_guided_euler_step_pair": (i32, [vp, vp, vp, vp, vp, vp, i64, vp, vp, f32, f32, f32, vp, i32, i32,
+                                             vp, vp, vp, vp, vp, vp, i64, vp, vp, f32, f32, f32, vp, i32, i32, f32, f32, vp]),
+    "ltx2_mm_guidance_sums": (i32, [vp, vp, vp, vp, vp, vp, i64, f32, f32, f32, vp, vp, i32, i32, vp]),
+    "ltx2_mm_rescaled_euler_step": (i32, [vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, f32, f32, f32, f32, f32, f32, vp, vp, i32, i32, vp]),
     "ltx2_vae_prepare_latent": (i32, [vp, vp, vp, vp, f32, vp, i32, i64, vp]),
     "ltx2_pixnorm_mod_silu": (i32, [vp, vp, i64, i32, f32, vp, vp, i32, i32, vp]),
     "ltx2_vae_unpatchify": (i32, [vp, vp, i32, i32, i32, vp]),
@@ -121,6 +126,9 @@ SIGNATURES = {
     "ltx2_dit_set_stg_blocks": (i32, [vp, i32, C.c_char_p, i32]),
     "ltx2_dit_forward_perturbed": (i32, [vp, vp, vp, i32, vp, vp, vp]),
     "ltx2_dit_forward_perturbed_av": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp]),
+    "ltx2_dit_forward_isolated_av": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp]),
+    "ltx2_dit_mm_guided_step_av": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64,
+                                         f32, f32, f32, f32, f32, f32, f32, f32, f32, f32, vp]),
     "ltx2_dit_stg_step": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, f32, f32, f32, f32, vp]),
     "ltx2_dit_graph_capture_stg": (i32, [vp, vp, vp, C.POINTER(f32), i32, vp, i64, vp, i64, vp, i64, f32, f32, C.c_double, vp]),
     "ltx2_dit_denoise_step": (i32, [vp, vp, vp, i32, vp, vp, vp, f32, f32, vp, vp]),

@@ -6,6 +6,7 @@ same guiders as two kernels per step (csrc/sampler.hip).  STGGuider (:80-102) pu
 self-attentions skipped (components/perturbations.py); pipelines.common.stg_denoise_loop runs it inside one kernel per step."""
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass, field
 from typing import Optional
 
@@ -121,3 +122,53 @@ class LegacyStatefulAPGGuider:
 
     def enabled(self) -> bool:
         return self.scale != 0.0
+
+
+@dataclass(frozen=True)
+class MultiModalGuiderParams:
+    """One modality's scales of the multi-modal guider (guiders.py:211-224)."""
+    cfg_scale: float = 1.0
+    stg_scale: float = 0.0
+    stg_blocks: Optional[list] = field(default_factory=list)
+    rescale_scale: float = 0.0
+    modality_scale: float = 1.0
+    skip_step: int = 0
+
+
+@dataclass(frozen=True)
+class MultiModalGuider:
+    """CFG + STG + modality-isolated guidance on one modality's prediction (guiders.py:227-287).  Up to four transformer passes per step: cond,
+    uncond (negative prompt), ptb (self-attentions skipped), mod (cross-modal attentions skipped).  pipelines.common.multimodal_denoise_loop
+    runs calculate, post_process_latent and the Euler step of both modalities as one kernel per step (csrc/sampler.hip)."""
+    params: MultiModalGuiderParams
+    negative_context: Optional[torch.Tensor] = None
+
+    def calculate(self, cond: torch.Tensor, uncond_text, uncond_perturbed, uncond_modality) -> torch.Tensor:
+        """Separate fp32 ops in the reference's order.  A float (0.0) in place of a prediction: that pass did not run and its term is left
+        out; a pass that ran contributes its term whatever its scale."""
+        p = self.params
+        pred = cond
+        if isinstance(uncond_text, torch.Tensor):
+            pred = pred + (p.cfg_scale - 1) * (cond - uncond_text)
+        if isinstance(uncond_perturbed, torch.Tensor):
+            pred = pred + p.stg_scale * (cond - uncond_perturbed)
+        if isinstance(uncond_modality, torch.Tensor):
+            pred = pred + (p.modality_scale - 1) * (cond - uncond_modality)
+        if p.rescale_scale != 0:
+            factor = torch.sqrt(cond.var(unbiased=False) + 1e-8) / torch.sqrt(pred.var(unbiased=False) + 1e-8)
+            pred = pred * (p.rescale_scale * factor + (1 - p.rescale_scale))
+        return pred
+
+    def do_unconditional_generation(self) -> bool:
+        return not math.isclose(self.params.cfg_scale, 1.0)
+
+    def do_perturbed_generation(self) -> bool:
+        return not math.isclose(self.params.stg_scale, 0.0)
+
+    def do_isolated_modality_generation(self) -> bool:
+        return not math.isclose(self.params.modality_scale, 1.0)
+
+    def should_skip_step(self, step: int) -> bool:
+        if self.params.skip_step == 0:
+            return False
+        return step % (self.params.skip_step + 1) != 0

@@ -341,6 +341,41 @@ int ltx2_projected_euler_step(const float* x, const float* vel_cond, const float
                                        sigma, sigma_next, out, scalars_out, rows, C, (hipStream_t)stream);
 }
 
+int ltx2_mm_guided_euler_step(const float* x, const float* vel_cond, const float* vel_uncond, const float* vel_perturbed, const float* vel_isolated,
+                              const float* ts, int64_t ts_stride, const float* mask, const float* clean, float cfg_scale, float stg_scale,
+                              float modality_scale, float sigma, float sigma_next, float* out, int rows, int C, void* stream) {
+    return mm_guided_euler_step_launch(x, vel_cond, vel_uncond, vel_perturbed, vel_isolated, ts, (long)ts_stride, mask, clean, cfg_scale, stg_scale,
+                                       modality_scale, sigma, sigma_next, out, rows, C, (hipStream_t)stream);
+}
+
+int ltx2_mm_guided_euler_step_pair(const float* v_x, const float* v_vel_cond, const float* v_vel_uncond, const float* v_vel_perturbed,
+                                   const float* v_vel_isolated, const float* v_ts, int64_t v_ts_stride, const float* v_mask, const float* v_clean,
+                                   float v_cfg_scale, float v_stg_scale, float v_modality_scale, float* v_out, int v_rows, int v_C, const float* a_x,
+                                   const float* a_vel_cond, const float* a_vel_uncond, const float* a_vel_perturbed, const float* a_vel_isolated,
+                                   const float* a_ts, int64_t a_ts_stride, const float* a_mask, const float* a_clean, float a_cfg_scale,
+                                   float a_stg_scale, float a_modality_scale, float* a_out, int a_rows, int a_C, float sigma, float sigma_next,
+                                   void* stream) {
+    return mm_guided_euler_step_pair_launch(v_x, v_vel_cond, v_vel_uncond, v_vel_perturbed, v_vel_isolated, v_ts, (long)v_ts_stride, v_mask, v_clean,
+                                            v_cfg_scale, v_stg_scale, v_modality_scale, v_out, v_rows, v_C, a_x, a_vel_cond, a_vel_uncond, a_vel_perturbed,
+                                            a_vel_isolated, a_ts, (long)a_ts_stride, a_mask, a_clean, a_cfg_scale, a_stg_scale, a_modality_scale, a_out,
+                                            a_rows, a_C, sigma, sigma_next, (hipStream_t)stream);
+}
+
+int ltx2_mm_guidance_sums(const float* x, const float* vel_cond, const float* vel_uncond, const float* vel_perturbed, const float* vel_isolated,
+                          const float* ts, int64_t ts_stride, float cfg_scale, float stg_scale, float modality_scale, double* partials, float* pred_out,
+                          int rows, int C, void* stream) {
+    return mm_guidance_sums_launch(x, vel_cond, vel_uncond, vel_perturbed, vel_isolated, ts, (long)ts_stride, cfg_scale, stg_scale, modality_scale, partials,
+                                   pred_out, rows, C, (hipStream_t)stream);
+}
+
+int ltx2_mm_rescaled_euler_step(const float* x, const float* vel_cond, const float* vel_uncond, const float* vel_perturbed, const float* vel_isolated,
+                                const float* ts, int64_t ts_stride, const float* mask, const float* clean, const double* partials, float cfg_scale,
+                                float stg_scale, float modality_scale, float rescale_scale, float sigma, float sigma_next, float* out,
+                                float* scalars_out, int rows, int C, void* stream) {
+    return mm_rescaled_euler_step_launch(x, vel_cond, vel_uncond, vel_perturbed, vel_isolated, ts, (long)ts_stride, mask, clean, partials, cfg_scale,
+                                         stg_scale, modality_scale, rescale_scale, sigma, sigma_next, out, scalars_out, rows, C, (hipStream_t)stream);
+}
+
 int ltx2_vae_prepare_latent(const float* latent, const float* std, const float* mean, const float* noise,
                             float noise_scale, void* out_bf16, int C, int64_t P, void* stream) {
     LTX2_CHECK_ARG(latent && std && mean && out_bf16, "vae_prepare_latent: null operand");

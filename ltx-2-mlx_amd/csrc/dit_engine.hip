@@ -119,6 +119,8 @@ struct ltx2_dit {
     int pg_rows = 0;
     float* pg_run = nullptr;           //   and, for the legacy APG guider with momentum only, its running guidance [N][Cout] fp32
     long pg_run_n = 0;
+    double* mm_part[2] = {};           // multi-modal guidance with rescale: each modality's partials [mm_rows[k]][4], allocated on first use for the bound shapes, freed with the context
+    int mm_rows[2] = {};
     // fp8-resident linear weights: the typed `const bf16*` fields of the weight structs then hold the CODES pointer; dense() looks it
     // up here to hand the GEMM (codes, per-row scale) instead of bf16 weights.  Per context (a second context over the same tensors
     // -- the video twin of an AudioVideo model -- keeps its own entries); rebuilt whenever the weights are resolved again.
@@ -793,7 +795,10 @@ struct ModIn {
 };
 
 // perturbed: the layers of c->stg[k] run without their self-attention (block_attention()); everything else, the schedule included, is the same program
-int forward(ltx2_dit* c, const ModIn* in, hipStream_t st, bool rewind_events = true, bool perturbed = false) {
+// isolated (AudioVideo; the reference's SKIP_A2V_CROSS_ATTN + SKIP_V2A_CROSS_ATTN over every block): no layer runs block_cross_modal().  That call
+// records and waits all four of its events itself, so leaving the WHOLE call out leaves no wait on an unrecorded event; both joins per layer, the
+// early text K / V, the cross-modal AdaLN chains at the top (without a consumer in this pass) and the output heads are the same program
+int forward(ltx2_dit* c, const ModIn* in, hipStream_t st, bool rewind_events = true, bool perturbed = false, bool isolated = false) {
     const int nm = c->av ? 2 : 1;
     const auto skip = [&](int k, int l) { return perturbed && !c->stg[k].empty() && c->stg[k][l] != 0; };
     if (rewind_events) c->sync_next = 0;
@@ -849,7 +854,7 @@ int forward(ltx2_dit* c, const ModIn* in, hipStream_t st, bool rewind_events = t
         }
         TRY(block_attention(c, 0, l, es[0], st, fold, skip(0, l)));
         if (c->av) {
-            TRY(block_cross_modal(c, l, st, sa));      // main: the video side; side: the audio side (events inside)
+            if (!isolated) TRY(block_cross_modal(c, l, st, sa));      // main: the video side; side: the audio side (events inside)
             TRY(block_ffn(c, 1, l, es[1], sa));
         }
         TRY(block_ffn(c, 0, l, es[0], st));
@@ -1077,6 +1082,8 @@ void ltx2_dit_destroy(ltx2_dit* c) {
     if (c->r2s) (void)hipFree(c->r2s);
     if (c->pg_part) (void)hipFree(c->pg_part);
     if (c->pg_run) (void)hipFree(c->pg_run);
+    for (double* p : c->mm_part)
+        if (p) (void)hipFree(p);
     if (c->exec) (void)hipGraphExecDestroy(c->exec);
     if (c->graph) (void)hipGraphDestroy(c->graph);
     for (hipEvent_t e : c->prof_ev) (void)hipEventDestroy(e);
@@ -1200,6 +1207,17 @@ int ltx2_dit_forward_perturbed_av(ltx2_dit* c, const float* v_latent, const floa
     ModIn in[2] = {{v_latent, v_timesteps, n_v_timesteps, v_sigma, v_velocity},
                    {a_latent, a_timesteps, n_a_timesteps, a_sigma, a_velocity}};
     return forward(c, in, (hipStream_t)stream, true, true);
+}
+
+int ltx2_dit_forward_isolated_av(ltx2_dit* c, const float* v_latent, const float* v_timesteps, int n_v_timesteps,
+                                 const float* v_sigma, const float* a_latent, const float* a_timesteps, int n_a_timesteps,
+                                 const float* a_sigma, float* v_velocity, float* a_velocity, void* stream) {
+    LTX2_CHECK_ARG(v_latent && v_timesteps && v_sigma && a_latent && a_timesteps && a_sigma && v_velocity && a_velocity,
+                   "dit_forward_isolated_av: null argument");
+    TRY(check_ready(c, "dit_forward_isolated_av", true));
+    ModIn in[2] = {{v_latent, v_timesteps, n_v_timesteps, v_sigma, v_velocity},
+                   {a_latent, a_timesteps, n_a_timesteps, a_sigma, a_velocity}};
+    return forward(c, in, (hipStream_t)stream, true, false, true);
 }
 
 int ltx2_dit_denoise_step(ltx2_dit* c, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev,
@@ -1399,6 +1417,66 @@ int projected_step(ltx2_dit* c, ltx2_dit* neg, const ModIn& in, const StepIo& io
     TRY(guidance_sums_launch(in.latent, m.vel, neg->m[0].vel, in.ts, stride, run, first, g.momentum, c->pg_part, m.N, m.Cout, st));
     return projected_euler_step_launch(in.latent, m.vel, neg->m[0].vel, in.ts, stride, io.mask, io.clean, run, c->pg_part, g.mode, g.scale, g.eta,
                                        g.norm_threshold, sigma, sigma_next, io.latent, nullptr, m.N, m.Cout, st);
+}
+
+// Multi-modal guidance on AudioVideo contexts (the reference's two-stage pipeline, pipelines/two_stage.py:314-401; MultiModalGuider.calculate): per step
+// up to four evaluations of BOTH modalities -- c, neg (NULL: no CFG term), c with the self-attentions of c->stg skipped into the caller's ptb scratch
+// (NULL: no STG term), c with every cross-modal attention skipped into the caller's mod scratch (NULL: no modality term) -- and then both latents stepped,
+// each modality under its own scales.  Without rescale that is ONE launch over both latents; a modality with rescale takes its sums and its step launch.
+struct MmGuide {        // one modality's MultiModalGuiderParams
+    float cfg, stg, mod, rescale;
+};
+
+// each modality's partials, for the modalities that rescale; never called while a stream is capturing
+int mm_workspace(ltx2_dit* c, const MmGuide g[2]) {
+    for (int k = 0; k < 2; ++k) {
+        const int rows = guidance_sums_blocks(c->m[k].N, c->m[k].Cout);
+        if (g[k].rescale == 0.f || (c->mm_part[k] && c->mm_rows[k] == rows)) continue;
+        if (c->mm_part[k]) (void)hipFree(c->mm_part[k]);
+        c->mm_part[k] = nullptr;
+        c->mm_rows[k] = 0;
+        if (hipMalloc((void**)&c->mm_part[k], 8L * 4 * rows) != hipSuccess) {
+            ltx2_set_error("dit_mm_guided_step_av: allocating %ld bytes of workspace failed", 8L * 4 * rows);
+            return LTX2_E_HIP;
+        }
+        c->mm_rows[k] = rows;
+    }
+    return LTX2_OK;
+}
+
+int mm_guided_step(ltx2_dit* c, ltx2_dit* neg, const ModIn* in, const StepIo* io, float* const mod[2], float* const ptb[2], const MmGuide g[2], float sigma,
+                   float sigma_next, hipStream_t st) {
+    for (int k = 0; k < 2; ++k)      // (the entry has checked the scalars, the conditionings and the scratch buffers)
+        LTX2_CHECK_ARG(g[k].rescale == 0.f || (c->mm_part[k] && c->mm_rows[k] == guidance_sums_blocks(c->m[k].N, c->m[k].Cout)),
+                       "dit_mm_guided_step_av: workspace missing");
+    TRY(evaluate(c, neg, in, st));
+    if (ptb[0]) {
+        const ModIn p[2] = {{in[0].latent, in[0].ts, in[0].n_ts, in[0].sigma, ptb[0]}, {in[1].latent, in[1].ts, in[1].n_ts, in[1].sigma, ptb[1]}};
+        TRY(forward(c, p, st, true, true));
+    }
+    if (mod[0]) {
+        const ModIn q[2] = {{in[0].latent, in[0].ts, in[0].n_ts, in[0].sigma, mod[0]}, {in[1].latent, in[1].ts, in[1].n_ts, in[1].sigma, mod[1]}};
+        TRY(forward(c, q, st, true, false, true));
+    }
+    const Mod* m[2] = {&c->m[0], &c->m[1]};
+    const float* vu[2] = {neg ? neg->m[0].vel : nullptr, neg ? neg->m[1].vel : nullptr};
+    const long stride[2] = {in[0].n_ts == 1 ? 0 : 1, in[1].n_ts == 1 ? 0 : 1};
+    if (g[0].rescale == 0.f && g[1].rescale == 0.f)
+        return mm_guided_euler_step_pair_launch(in[0].latent, m[0]->vel, vu[0], ptb[0], mod[0], in[0].ts, stride[0], io[0].mask, io[0].clean, g[0].cfg, g[0].stg,
+                                                g[0].mod, io[0].latent, m[0]->N, m[0]->Cout, in[1].latent, m[1]->vel, vu[1], ptb[1], mod[1], in[1].ts, stride[1],
+                                                io[1].mask, io[1].clean, g[1].cfg, g[1].stg, g[1].mod, io[1].latent, m[1]->N, m[1]->Cout, sigma, sigma_next, st);
+    for (int k = 0; k < 2; ++k) {
+        if (g[k].rescale == 0.f) {
+            TRY(mm_guided_euler_step_launch(in[k].latent, m[k]->vel, vu[k], ptb[k], mod[k], in[k].ts, stride[k], io[k].mask, io[k].clean, g[k].cfg, g[k].stg,
+                                            g[k].mod, sigma, sigma_next, io[k].latent, m[k]->N, m[k]->Cout, st));
+            continue;
+        }
+        TRY(mm_guidance_sums_launch(in[k].latent, m[k]->vel, vu[k], ptb[k], mod[k], in[k].ts, stride[k], g[k].cfg, g[k].stg, g[k].mod, c->mm_part[k], nullptr,
+                                    m[k]->N, m[k]->Cout, st));
+        TRY(mm_rescaled_euler_step_launch(in[k].latent, m[k]->vel, vu[k], ptb[k], mod[k], in[k].ts, stride[k], io[k].mask, io[k].clean, c->mm_part[k], g[k].cfg,
+                                          g[k].stg, g[k].mod, g[k].rescale, sigma, sigma_next, io[k].latent, nullptr, m[k]->N, m[k]->Cout, st));
+    }
+    return LTX2_OK;
 }
 
 // The res_2s second-order step (reference pipelines/ti2vid_hq.py:153-319; HQ pipeline stage 1): per step two pairs of evaluations, the second
@@ -1651,6 +1729,41 @@ int ltx2_dit_res2s_step_av(ltx2_dit* c, ltx2_dit* neg, float* v_latent, float* a
     const ModIn in[2] = {v.in, a.in};
     const StepIo io[2] = {v.io, a.io};
     return res2s_step(c, neg, in, v_ts_sub, a_ts_sub, sub_sigma_dev ? sub_sigma_dev : v_ts_sub, nullptr, io, cfg_scale, audio_cfg_scale, p, (hipStream_t)stream);
+}
+
+int ltx2_dit_mm_guided_step_av(ltx2_dit* c, ltx2_dit* neg, float* v_latent, float* a_latent, const float* v_timesteps, int n_v_timesteps,
+                               const float* a_timesteps, int n_a_timesteps, const float* sigma_dev, const float* v_mask, const float* v_clean,
+                               const float* a_mask, const float* a_clean, float* v_vel_isolated, int64_t n_v_isolated, float* a_vel_isolated,
+                               int64_t n_a_isolated, float* v_vel_perturbed, int64_t n_v_perturbed, float* a_vel_perturbed, int64_t n_a_perturbed,
+                               float v_cfg_scale, float v_stg_scale, float v_modality_scale, float v_rescale_scale, float a_cfg_scale, float a_stg_scale,
+                               float a_modality_scale, float a_rescale_scale, float sigma, float sigma_next, void* stream) {
+    LTX2_CHECK_ARG(v_latent && a_latent && v_timesteps && a_timesteps && sigma_dev, "dit_mm_guided_step_av: null argument");
+    const int n_ts[2] = {n_v_timesteps, n_a_timesteps};
+    TRY(step_ready(c, neg, true, n_ts, "dit_mm_guided_step_av"));
+    float* const mod[2] = {v_vel_isolated, a_vel_isolated};
+    float* const ptb[2] = {v_vel_perturbed, a_vel_perturbed};
+    const int64_t n_mod[2] = {n_v_isolated, n_a_isolated}, n_ptb[2] = {n_v_perturbed, n_a_perturbed};
+    // the passes write, and the step kernels read, N * out_channels elements of each scratch: another length would be an out-of-bounds access, not an
+    // error (the comment at cond_modality())
+    for (int k = 0; k < 2; ++k) {
+        const int64_t need = (int64_t)c->m[k].N * c->m[k].Cout;
+        LTX2_CHECK_ARG((!mod[k] || n_mod[k] == need) && (!ptb[k] || n_ptb[k] == need),
+                       "dit_mm_guided_step_av: modality %d has %d tokens x %d channels, got an isolated scratch of %ld and a perturbed scratch of %ld elements", k,
+                       c->m[k].N, c->m[k].Cout, (long)(mod[k] ? n_mod[k] : need), (long)(ptb[k] ? n_ptb[k] : need));
+    }
+    const MmGuide g[2] = {{v_cfg_scale, v_stg_scale, v_modality_scale, v_rescale_scale}, {a_cfg_scale, a_stg_scale, a_modality_scale, a_rescale_scale}};
+    const StepArgs v = step_args(v_latent, v_timesteps, n_v_timesteps, sigma_dev, v_mask, v_clean);
+    const StepArgs a = step_args(a_latent, a_timesteps, n_a_timesteps, sigma_dev, a_mask, a_clean);
+    const ModIn in[2] = {v.in, a.in};
+    const StepIo io[2] = {v.io, a.io};
+    // every refusal of the step itself stands before the workspace is touched and before anything is enqueued
+    TRY(step_check(sigma, io, 2, "dit_mm_guided_step_av"));
+    LTX2_CHECK_ARG((mod[0] == nullptr) == (mod[1] == nullptr) && (ptb[0] == nullptr) == (ptb[1] == nullptr),
+                   "dit_mm_guided_step_av: a pass writes both modalities' velocities: its video and audio scratch go together");
+    LTX2_CHECK_ARG(!ptb[0] || !c->stg[0].empty() || !c->stg[1].empty(),
+                   "dit_mm_guided_step_av: a perturbed scratch is given but no self-attention is marked (ltx2_dit_set_stg_blocks)");
+    TRY(mm_workspace(c, g));
+    return mm_guided_step(c, neg, in, io, mod, ptb, g, sigma, sigma_next, (hipStream_t)stream);
 }
 
 int ltx2_dit_graph_capture(ltx2_dit* c, float* latent, const float* host_sigmas, int n_steps, void* stream) {

@@ -61,3 +61,28 @@ int projected_euler_step_launch(const float* x, const float* vel_cond, const flo
                                 const float* clean, const float* running, const double* partials, int mode, float scale, float eta,
                                 float norm_threshold, float sigma, float sigma_next, float* out, float* scalars_out, int rows, int C,
                                 hipStream_t stream);
+
+// MultiModalGuider.calculate (reference components/guiders.py:244-273) and the step behind it.  With a = x - t*vc and u, p, m formed the same way from
+// vel_uncond (negative prompt), vel_perturbed (self-attentions skipped) and vel_isolated (cross-modal attentions skipped), each term present exactly
+// when its velocity is non-NULL:
+//   pred = a [+ (cfg_scale - 1)*(a - u)] [+ stg_scale*(a - p)] [+ (modality_scale - 1)*(a - m)];  d = mask ? pred*m + clean*(1 - m) : pred;  out = euler(x, d)
+int mm_guided_euler_step_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* vel_perturbed, const float* vel_isolated,
+                                const float* ts, long ts_stride, const float* mask, const float* clean, float cfg_scale, float stg_scale,
+                                float modality_scale, float sigma, float sigma_next, float* out, int rows, int C, hipStream_t stream);
+// the same over the video and the audio latent in one launch, each with its own scales; each segment's output is the single launch's bit for bit
+int mm_guided_euler_step_pair_launch(const float* v_x, const float* v_vel_cond, const float* v_vel_uncond, const float* v_vel_perturbed,
+                                     const float* v_vel_isolated, const float* v_ts, long v_ts_stride, const float* v_mask, const float* v_clean,
+                                     float v_cfg_scale, float v_stg_scale, float v_modality_scale, float* v_out, int v_rows, int v_C, const float* a_x,
+                                     const float* a_vel_cond, const float* a_vel_uncond, const float* a_vel_perturbed, const float* a_vel_isolated,
+                                     const float* a_ts, long a_ts_stride, const float* a_mask, const float* a_clean, float a_cfg_scale, float a_stg_scale,
+                                     float a_modality_scale, float* a_out, int a_rows, int a_C, float sigma, float sigma_next, hipStream_t stream);
+// With rescale_scale != 0, two passes.  sums: the fp64 sums of a, a*a, pred, pred*pred per block into partials[guidance_sums_blocks(rows, C)][4]
+// (pred_out, may be NULL: pred itself).  step: every block adds the partial rows in index order, var = (S2 - S1*S1/n)/n,
+// f = fp32(rescale_scale*sqrt((var_a + 1e-8)/(var_p + 1e-8)) + (1 - rescale_scale)) in fp64, block 0 stores f to scalars_out; then the step above with pred*f
+int mm_guidance_sums_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* vel_perturbed, const float* vel_isolated,
+                            const float* ts, long ts_stride, float cfg_scale, float stg_scale, float modality_scale, double* partials, float* pred_out,
+                            int rows, int C, hipStream_t stream);
+int mm_rescaled_euler_step_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* vel_perturbed, const float* vel_isolated,
+                                  const float* ts, long ts_stride, const float* mask, const float* clean, const double* partials, float cfg_scale,
+                                  float stg_scale, float modality_scale, float rescale_scale, float sigma, float sigma_next, float* out,
+                                  float* scalars_out, int rows, int C, hipStream_t stream);

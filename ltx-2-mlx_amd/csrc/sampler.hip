@@ -1,7 +1,8 @@
 // The device code of the sampling step over fp32 [rows][C] latents: the plain x0 / Euler pair, and the steps that replace a sequence of separate
 // fp32 torch ops bit for bit -- the classifier-free-guided Euler step (pipelines/one_stage.py:224-330), the same with STG guidance on top, the two passes of the res_2s second-order
 // step (reference pipelines/ti2vid_hq.py:153-273; over one latent, or over the video and the audio latent of the joint step in one launch) and the two passes of the guiders whose scalars are reductions over the whole latent
-// (CFGStarRescalingGuider, LtxAPGGuider, LegacyStatefulAPGGuider; reference components/guiders.py:51-76, 105-205).  All arithmetic is fp32 and
+// (CFGStarRescalingGuider, LtxAPGGuider, LegacyStatefulAPGGuider; reference components/guiders.py:51-76, 105-205), and the multi-modal guided step
+// (MultiModalGuider.calculate, :244-273: CFG, STG and modality-isolated terms, with or without the variance rescale).  All arithmetic is fp32 and
 // fp64, so the file compiles to the same code in both library builds.  The definitions are written out in include/ltx2hip.h.
 #include <hip/hip_runtime.h>
 
@@ -222,6 +223,35 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
     return v;
 }
 
+// The N sums of a block in the order every sums pass shares -- per thread in loop order (s), across the wave (xor tree), across the block's waves in
+// order -- into row blockIdx.x of partials[blocks][N]
+template <int N>
+__device__ __forceinline__ void block_sums_store(const double (&s)[N], double* partials) {
+    __shared__ double part[WAVES][N];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        const double w = wave_sum_f64(s[k]);
+        if (lane == 0) part[wave][k] = w;
+    }
+    __syncthreads();
+    if (threadIdx.x < N) {
+        double acc = part[0][threadIdx.x];
+        for (int w = 1; w < WAVES; ++w) acc += part[w][threadIdx.x];
+        partials[(long)blockIdx.x * N + threadIdx.x] = acc;
+    }
+}
+
+// The nb rows of partials[nb][N] added in index order into sums[N] (shared memory; the caller synchronises): every block holds the same sums
+template <int N>
+__device__ __forceinline__ void partial_rows_sum(const double* partials, int nb, double* sums) {
+    if (threadIdx.x < N) {
+        double acc = 0.0;
+        for (int r = 0; r < nb; ++r) acc += partials[(long)r * N + threadIdx.x];
+        sums[threadIdx.x] = acc;
+    }
+}
+
 // a = x - t*vc, b = x - t*vu, g = a - b, with momentum g = momentum*running + g (in[RUN]: NULL on the first step) stored back to running; the five
 // sums per thread in loop order, then across the wave (xor tree), then across the block's waves in order.
 struct GuidanceSums : StepOp {
@@ -250,21 +280,7 @@ struct GuidanceSums : StepOp {
         st.s[3] += dg * dg;
         st.s[4] += dg * da;
     }
-    __device__ __forceinline__ void end(State& st) const {
-        __shared__ double part[WAVES][NSUM];
-        const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-        for (int k = 0; k < NSUM; ++k) {
-            const double w = wave_sum_f64(st.s[k]);
-            if (lane == 0) part[wave][k] = w;
-        }
-        __syncthreads();
-        if (threadIdx.x < NSUM) {
-            double acc = part[0][threadIdx.x];
-            for (int w = 1; w < WAVES; ++w) acc += part[w][threadIdx.x];
-            partials[(long)blockIdx.x * NSUM + threadIdx.x] = acc;
-        }
-    }
+    __device__ __forceinline__ void end(State& st) const { block_sums_store<NSUM>(st.s, partials); }
 };
 
 // g_out of one element from (a, b, g) and the block's fp32 scalars: k0 = coef (mode 0) or sf (modes 1, 2), k1 = proj
@@ -294,11 +310,7 @@ struct ProjectedEuler : StepOp {
     __device__ __forceinline__ void begin(State& st) const {
         __shared__ double sums[NSUM];
         __shared__ float sc[2];
-        if (threadIdx.x < NSUM) {                                      // the partial rows in index order
-            double acc = 0.0;
-            for (int r = 0; r < nb; ++r) acc += partials[(long)r * NSUM + threadIdx.x];
-            sums[threadIdx.x] = acc;
-        }
+        partial_rows_sum<NSUM>(partials, nb, sums);
         __syncthreads();
         if (threadIdx.x == 0) {                                        // fp64 throughout, each scalar rounded once
             float k0, k1 = 0.f;
@@ -326,6 +338,100 @@ struct ProjectedEuler : StepOp {
         const float g = in[RUN] ? v[RUN] : sub_rn(a, b);
         const float d = projected_one(mode, a, b, g, st.k0, st.k1, mult, eta);
         o[OUT] = euler(v[X], blend_clean(d, v[CLEAN], r), inv, dt);
+    }
+};
+
+// MultiModalGuider.calculate (reference components/guiders.py:244-273) from the conditional x0 `a` and the x0 of the passes that ran: u (negative prompt),
+// p (self-attentions skipped), m (cross-modal attentions skipped); a term is there exactly when its velocity is
+struct MmTerms {
+    float cfg1, stg, mod1;      // cfg_scale - 1, stg_scale, modality_scale - 1
+};
+__device__ __forceinline__ float mm_pred(const MmTerms& k, const Row& r, float x, float a, float vu, float vp, float vm, bool has_u, bool has_p, bool has_m) {
+    float pred = a;
+    if (has_u) pred = add_rn(pred, mul_rn(k.cfg1, sub_rn(a, denoised(x, vu, r.t))));
+    if (has_p) pred = add_rn(pred, mul_rn(k.stg, sub_rn(a, denoised(x, vp, r.t))));
+    if (has_m) pred = add_rn(pred, mul_rn(k.mod1, sub_rn(a, denoised(x, vm, r.t))));
+    return pred;
+}
+
+// the multi-modal guided step without rescale: pred, the mask / clean blend, Euler
+struct MmGuidedEuler : StepOp {
+    enum { X, VC, VU, VP, VM, CLEAN, NIN };
+    enum { OUT, NOUT };
+    const float* in[NIN];
+    float* out[NOUT];
+    MmTerms k;
+    float inv, dt;              // 1/sigma, sigma_next - sigma
+    __device__ __forceinline__ void one(State&, const Row& r, const float* v, float* o) const {
+        const float a = denoised(v[X], v[VC], r.t);
+        const float pred = mm_pred(k, r, v[X], a, v[VU], v[VP], v[VM], in[VU] != nullptr, in[VP] != nullptr, in[VM] != nullptr);
+        o[OUT] = euler(v[X], blend_clean(pred, v[CLEAN], r), inv, dt);
+    }
+};
+
+constexpr int NMM = 4;                // S_a, S_aa, S_p, S_pp
+
+// with rescale, pass 1: the fp64 sums of a, a*a, pred, pred*pred over ALL rows in GuidanceSums' order; pred is stored where the caller asks for it
+struct MmGuidanceSums : StepOp {
+    enum { X, VC, VU, VP, VM, NIN };
+    enum { PRED, NOUT };
+    struct State {
+        double s[NMM];
+    };
+    const float* in[NIN];
+    float* out[NOUT];
+    MmTerms k;
+    double* partials;
+    __device__ __forceinline__ void begin(State& st) const {
+#pragma unroll
+        for (int j = 0; j < NMM; ++j) st.s[j] = 0.0;
+    }
+    __device__ __forceinline__ void one(State& st, const Row& r, const float* v, float* o) const {
+        const float a = denoised(v[X], v[VC], r.t);
+        const float pred = mm_pred(k, r, v[X], a, v[VU], v[VP], v[VM], in[VU] != nullptr, in[VP] != nullptr, in[VM] != nullptr);
+        o[PRED] = pred;
+        const double da = a, dp = pred;                        // each product of two fp32 values is exact in fp64
+        st.s[0] += da;
+        st.s[1] += da * da;
+        st.s[2] += dp;
+        st.s[3] += dp * dp;
+    }
+    __device__ __forceinline__ void end(State& st) const { block_sums_store<NMM>(st.s, partials); }
+};
+
+// pass 2: every block adds the partial rows in index order and derives, in fp64, the population variances var = (S2 - S1*S1/n)/n (as mx.var) and
+// f = rescale*sqrt((var_a + 1e-8)/(var_p + 1e-8)) + (1 - rescale), rounded once to fp32; then the step with pred*f
+struct MmRescaledEuler : StepOp {
+    enum { X, VC, VU, VP, VM, CLEAN, NIN };
+    enum { OUT, NOUT };
+    struct State {
+        float f;
+    };
+    const float* in[NIN];
+    float* out[NOUT];
+    MmTerms k;
+    const double* partials;
+    float* scalars_out;
+    double rescale, n;          // rescale_scale; rows * C
+    float inv, dt;
+    int nb;                     // rows of partials
+    __device__ __forceinline__ void begin(State& st) const {
+        __shared__ double sums[NMM];
+        __shared__ float sf;
+        partial_rows_sum<NMM>(partials, nb, sums);
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const double var_a = (sums[1] - sums[0] * sums[0] / n) / n, var_p = (sums[3] - sums[2] * sums[2] / n) / n;
+            sf = (float)(rescale * sqrt((var_a + 1e-8) / (var_p + 1e-8)) + (1.0 - rescale));
+            if (blockIdx.x == 0 && scalars_out) scalars_out[0] = sf;
+        }
+        __syncthreads();
+        st.f = sf;
+    }
+    __device__ __forceinline__ void one(State& st, const Row& r, const float* v, float* o) const {
+        const float a = denoised(v[X], v[VC], r.t);
+        const float pred = mm_pred(k, r, v[X], a, v[VU], v[VP], v[VM], in[VU] != nullptr, in[VP] != nullptr, in[VM] != nullptr);
+        o[OUT] = euler(v[X], blend_clean(mul_rn(pred, st.f), v[CLEAN], r), inv, dt);
     }
 };
 
@@ -485,4 +591,50 @@ int projected_euler_step_launch(const float* x, const float* vel_cond, const flo
     const ProjectedEuler op = {{}, {x, vel_cond, vel_uncond, clean, running}, {out}, partials, scalars_out, mode, mode == 2 ? scale : scale - 1.0f,
                                eta, norm_threshold, 1.0f / sigma, sigma_next - sigma, guidance_sums_blocks(rows, C)};
     return launch_rows("projected_euler_step", x && vel_cond && vel_uncond && partials && out, op, ts, ts_stride, mask, clean, rows, C, 0, stream);
+}
+
+int mm_guided_euler_step_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* vel_perturbed, const float* vel_isolated,
+                                const float* ts, long ts_stride, const float* mask, const float* clean, float cfg_scale, float stg_scale,
+                                float modality_scale, float sigma, float sigma_next, float* out, int rows, int C, hipStream_t stream) {
+    LTX2_CHECK_ARG(sigma != 0.f, "Sigma can't be 0.0");   // reference core_utils.py:54-55
+    const MmGuidedEuler op = {{}, {x, vel_cond, vel_uncond, vel_perturbed, vel_isolated, clean}, {out}, {cfg_scale - 1.0f, stg_scale, modality_scale - 1.0f},
+                              1.0f / sigma, sigma_next - sigma};
+    return launch_rows("mm_guided_euler_step", x && vel_cond && out, op, ts, ts_stride, mask, clean, rows, C, 0, stream);
+}
+
+int mm_guided_euler_step_pair_launch(const float* v_x, const float* v_vel_cond, const float* v_vel_uncond, const float* v_vel_perturbed,
+                                     const float* v_vel_isolated, const float* v_ts, long v_ts_stride, const float* v_mask, const float* v_clean,
+                                     float v_cfg_scale, float v_stg_scale, float v_modality_scale, float* v_out, int v_rows, int v_C, const float* a_x,
+                                     const float* a_vel_cond, const float* a_vel_uncond, const float* a_vel_perturbed, const float* a_vel_isolated,
+                                     const float* a_ts, long a_ts_stride, const float* a_mask, const float* a_clean, float a_cfg_scale, float a_stg_scale,
+                                     float a_modality_scale, float* a_out, int a_rows, int a_C, float sigma, float sigma_next, hipStream_t stream) {
+    LTX2_CHECK_ARG(sigma != 0.f, "Sigma can't be 0.0");   // reference core_utils.py:54-55
+    const float inv = 1.0f / sigma, dt = sigma_next - sigma;
+    const MmGuidedEuler v = {{}, {v_x, v_vel_cond, v_vel_uncond, v_vel_perturbed, v_vel_isolated, v_clean}, {v_out},
+                             {v_cfg_scale - 1.0f, v_stg_scale, v_modality_scale - 1.0f}, inv, dt};
+    const MmGuidedEuler a = {{}, {a_x, a_vel_cond, a_vel_uncond, a_vel_perturbed, a_vel_isolated, a_clean}, {a_out},
+                             {a_cfg_scale - 1.0f, a_stg_scale, a_modality_scale - 1.0f}, inv, dt};
+    return launch_rows2("mm_guided_euler_step_pair", v_x && v_vel_cond && v_out && a_x && a_vel_cond && a_out, v,
+                        {v_ts, v_ts_stride, v_mask, v_clean, v_rows, v_C}, a, {a_ts, a_ts_stride, a_mask, a_clean, a_rows, a_C}, stream);
+}
+
+int mm_guidance_sums_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* vel_perturbed, const float* vel_isolated,
+                            const float* ts, long ts_stride, float cfg_scale, float stg_scale, float modality_scale, double* partials, float* pred_out,
+                            int rows, int C, hipStream_t stream) {
+    LTX2_CHECK_ARG(((uintptr_t)partials & 7) == 0, "mm_guidance_sums: partials must be 8-byte aligned");
+    const MmGuidanceSums op = {{}, {x, vel_cond, vel_uncond, vel_perturbed, vel_isolated}, {pred_out}, {cfg_scale - 1.0f, stg_scale, modality_scale - 1.0f},
+                               partials};
+    return launch_rows("mm_guidance_sums", x && vel_cond && partials, op, ts, ts_stride, nullptr, nullptr, rows, C, guidance_sums_blocks(rows, C), stream);
+}
+
+int mm_rescaled_euler_step_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* vel_perturbed, const float* vel_isolated,
+                                  const float* ts, long ts_stride, const float* mask, const float* clean, const double* partials, float cfg_scale,
+                                  float stg_scale, float modality_scale, float rescale_scale, float sigma, float sigma_next, float* out,
+                                  float* scalars_out, int rows, int C, hipStream_t stream) {
+    LTX2_CHECK_ARG(sigma != 0.f, "Sigma can't be 0.0");   // reference core_utils.py:54-55
+    LTX2_CHECK_ARG(((uintptr_t)partials & 7) == 0, "mm_rescaled_euler_step: partials must be 8-byte aligned");
+    const MmRescaledEuler op = {{}, {x, vel_cond, vel_uncond, vel_perturbed, vel_isolated, clean}, {out},
+                                {cfg_scale - 1.0f, stg_scale, modality_scale - 1.0f}, partials, scalars_out, (double)rescale_scale, (double)rows * C,
+                                1.0f / sigma, sigma_next - sigma, guidance_sums_blocks(rows, C)};
+    return launch_rows("mm_rescaled_euler_step", x && vel_cond && partials && out, op, ts, ts_stride, mask, clean, rows, C, 0, stream);
 }

@@ -593,6 +593,76 @@ def projected_euler_step(x: torch.Tensor, vel_cond: torch.Tensor, vel_uncond: to
     return out
 
 
+def _mm_args(seg: dict, out_key: str = "out"):
+    """One latent's operands of the multi-modal guided steps, by name -- x, vel_cond, timesteps and optionally vel_uncond, vel_perturbed,
+    vel_isolated, mask, clean, out -- as the C entries take them -> (pointer / stride arguments up to `clean`, out, N, C, the tensors to keep)."""
+    x, vc, vu, vp, vm = seg["x"], seg["vel_cond"], seg.get("vel_uncond"), seg.get("vel_perturbed"), seg.get("vel_isolated")
+    mask, clean = seg.get("mask"), seg.get("clean")
+    out = seg[out_key] if seg.get(out_key) is not None else torch.empty_like(x)
+    assert vc is not None and (mask is None) == (clean is None)
+    n, c, ts = _step_operands(x, seg["timesteps"], (vc, vu, vp, vm, clean, out), mask)
+    return [nv.ptr(x), nv.ptr(vc), nv.ptr(vu), nv.ptr(vp), nv.ptr(vm), nv.ptr(ts), 0 if ts.numel() == 1 else 1, nv.ptr(mask), nv.ptr(clean)], out, n, c, ts
+
+
+def mm_guided_euler_step(x: torch.Tensor, vel_cond: torch.Tensor, timesteps: torch.Tensor, cfg_scale: float, stg_scale: float, modality_scale: float,
+                         sigma: float, sigma_next: float, vel_uncond: Optional[torch.Tensor] = None, vel_perturbed: Optional[torch.Tensor] = None,
+                         vel_isolated: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, clean: Optional[torch.Tensor] = None,
+                         out: Optional[torch.Tensor] = None, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """One step under MultiModalGuider.calculate without rescale over fp32 [N, C] (ltx2_mm_guided_euler_step): x0 of the velocities given, the
+    CFG / STG / modality terms of those that are not None, the mask / clean blend and the Euler update in one pass, every operation
+    individually rounded.  timesteps: 1 or N elements; `out` may be any input; `dtype` picks the library build (the kernel is fp32 in both)."""
+    args, out, n, c, _ts = _mm_args(dict(x=x, vel_cond=vel_cond, vel_uncond=vel_uncond, vel_perturbed=vel_perturbed, vel_isolated=vel_isolated,
+                                         timesteps=timesteps, mask=mask, clean=clean, out=out))
+    nv.check(nv.lib(dtype).ltx2_mm_guided_euler_step(*args, float(cfg_scale), float(stg_scale), float(modality_scale), float(sigma), float(sigma_next),
+                                                     nv.ptr(out), n, c, nv.stream()))
+    return out
+
+
+def mm_guided_euler_step_pair(video: dict, audio: dict, sigma: float, sigma_next: float, dtype: Optional[torch.dtype] = None):
+    """mm_guided_euler_step over two latents in ONE launch (ltx2_mm_guided_euler_step_pair): `video` and `audio` each hold the single form's
+    operands by name -- x, vel_cond, timesteps, cfg_scale, stg_scale, modality_scale and optionally vel_uncond, vel_perturbed, vel_isolated,
+    mask, clean, out.  -> (video out, audio out), each equal to mm_guided_euler_step's bit for bit."""
+    args, outs, keep = [], [], []
+    for seg in (video, audio):
+        a, out, n, c, ts = _mm_args(seg)
+        args += a + [float(seg["cfg_scale"]), float(seg["stg_scale"]), float(seg["modality_scale"]), nv.ptr(out), n, c]
+        outs.append(out)
+        keep.append(ts)
+    nv.check(nv.lib(dtype).ltx2_mm_guided_euler_step_pair(*args, float(sigma), float(sigma_next), nv.stream()))
+    return outs[0], outs[1]
+
+
+def mm_guidance_sums(x: torch.Tensor, vel_cond: torch.Tensor, timesteps: torch.Tensor, cfg_scale: float, stg_scale: float, modality_scale: float,
+                     vel_uncond: Optional[torch.Tensor] = None, vel_perturbed: Optional[torch.Tensor] = None, vel_isolated: Optional[torch.Tensor] = None,
+                     partials: Optional[torch.Tensor] = None, pred_out: Optional[torch.Tensor] = None, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """First pass of the rescaled multi-modal step (ltx2_mm_guidance_sums): the fp64 sums of a, a*a, pred, pred*pred, one row per block.
+    -> partials, fp64 [guidance_sums_blocks(N, C), 4]; `pred_out` (fp32 [N, C]) receives MultiModalGuider.calculate's un-rescaled prediction."""
+    if partials is None:
+        partials = torch.empty(guidance_sums_blocks(*x.shape, dtype=dtype), 4, device=x.device, dtype=torch.float64)
+    n, c, timesteps = _step_operands(x, timesteps, (vel_cond, vel_uncond, vel_perturbed, vel_isolated, pred_out))
+    assert vel_cond is not None and partials.dtype == torch.float64 and partials.is_contiguous() and partials.numel() >= 4 * guidance_sums_blocks(n, c, dtype)
+    nv.check(nv.lib(dtype).ltx2_mm_guidance_sums(nv.ptr(x), nv.ptr(vel_cond), nv.ptr(vel_uncond), nv.ptr(vel_perturbed), nv.ptr(vel_isolated), nv.ptr(timesteps),
+                                                 0 if timesteps.numel() == 1 else 1, float(cfg_scale), float(stg_scale), float(modality_scale), nv.ptr(partials),
+                                                 nv.ptr(pred_out), n, c, nv.stream()))
+    return partials
+
+
+def mm_rescaled_euler_step(x: torch.Tensor, vel_cond: torch.Tensor, timesteps: torch.Tensor, partials: torch.Tensor, cfg_scale: float, stg_scale: float,
+                           modality_scale: float, rescale_scale: float, sigma: float, sigma_next: float, vel_uncond: Optional[torch.Tensor] = None,
+                           vel_perturbed: Optional[torch.Tensor] = None, vel_isolated: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
+                           clean: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, scalars_out: Optional[torch.Tensor] = None,
+                           dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """Second pass (ltx2_mm_rescaled_euler_step): the sums of `partials` added in every block, the rescale factor f from them in fp64, then
+    mm_guided_euler_step's pass with pred * f.  `scalars_out` (fp32, 1 element) receives f; `out` may be `x`."""
+    args, out, n, c, _ts = _mm_args(dict(x=x, vel_cond=vel_cond, vel_uncond=vel_uncond, vel_perturbed=vel_perturbed, vel_isolated=vel_isolated,
+                                         timesteps=timesteps, mask=mask, clean=clean, out=out))
+    assert partials.dtype == torch.float64 and partials.is_contiguous() and partials.numel() >= 4 * guidance_sums_blocks(n, c, dtype)
+    assert scalars_out is None or (scalars_out.dtype == torch.float32 and scalars_out.numel() >= 1)
+    nv.check(nv.lib(dtype).ltx2_mm_rescaled_euler_step(*args, nv.ptr(partials), float(cfg_scale), float(stg_scale), float(modality_scale), float(rescale_scale),
+                                                       float(sigma), float(sigma_next), nv.ptr(out), nv.ptr(scalars_out), n, c, nv.stream()))
+    return out
+
+
 def res2s_midpoint(x: torch.Tensor, vel_cond: torch.Tensor, vel_uncond: Optional[torch.Tensor], timesteps: torch.Tensor, cfg_scale: float, c: float,
                    n_bong: int, mask: Optional[torch.Tensor] = None, clean: Optional[torch.Tensor] = None, x_mid: Optional[torch.Tensor] = None,
                    anchor: Optional[torch.Tensor] = None, eps1: Optional[torch.Tensor] = None, final: bool = False,

@@ -934,6 +934,53 @@ class LTXModel:
                                                nv.ptr(clean_latent), nv.ptr(audio_denoise_mask), nv.ptr(audio_clean_latent), float(cfg_scale),
                                                float(audio_cfg_scale), float(sigma), float(sigma_next), nv.stream()))
 
+    # ------------------------------------------------------------------ multi-modal guidance: CFG + STG + modality isolation (AudioVideo engine)
+    def forward_isolated(self, video: Modality, audio: Modality) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The modality-isolated forward (ltx2_dit_forward_isolated_av; the reference's SKIP_A2V_CROSS_ATTN + SKIP_V2A_CROSS_ATTN over every
+        block, pipelines/two_stage.py:356-364): __call__(video, audio) with no cross-modal attention in any layer, so each modality's
+        velocity depends on its own latent alone.  -> (video velocity (1, N, C), audio velocity (1, Na, Ca)).  AudioVideo models only."""
+        if not self.is_av:
+            raise ValueError("forward_isolated runs on an AudioVideo model (a VideoOnly model has no cross-modal attention to skip)")
+        if audio is None:
+            raise ValueError("forward_isolated needs the audio modality")
+        self._check_inputs(video, audio, None)
+        ts, n_ts = self._timesteps(video)
+        ats, n_ats = self._timesteps(audio)
+        self._ensure_prepared(video, per_token=(n_ts != 1 or n_ats != 1), audio=audio)
+        self._apply_context_masks(video, audio)
+        lat = video.latent[0].to(self.device, torch.float32).contiguous()
+        alat = audio.latent[0].to(self.device, torch.float32).contiguous()
+        out = torch.empty(lat.shape[0], self.out_channels, device=self.device, dtype=torch.float32)
+        aout = torch.empty(alat.shape[0], self.AUDIO_OUT_CHANNELS, device=self.device, dtype=torch.float32)
+        vs, as_ = self._sigma(video), self._sigma(audio)
+        nv.check(self._L.ltx2_dit_forward_isolated_av(self._h, nv.ptr(lat), nv.ptr(ts), n_ts, nv.ptr(vs), nv.ptr(alat), nv.ptr(ats), n_ats, nv.ptr(as_),
+                                                      nv.ptr(out), nv.ptr(aout), nv.stream()))
+        return out[None], aout[None]
+
+    def mm_guided_step_av_(self, neg: Optional["LTXModel"], latent: torch.Tensor, audio_latent: torch.Tensor, video: Modality, audio: Modality,
+                           sigma: float, sigma_next: float, video_params, audio_params, isolated: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                           perturbed: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, denoise_mask: Optional[torch.Tensor] = None,
+                           clean_latent: Optional[torch.Tensor] = None, audio_denoise_mask: Optional[torch.Tensor] = None,
+                           audio_clean_latent: Optional[torch.Tensor] = None) -> None:
+        """In-place on BOTH latents, (N, C) and (Na, Ca) fp32: one step of the two-stage pipeline's stage 1 (reference
+        pipelines/two_stage.py:314-401) by ONE C call (ltx2_dit_mm_guided_step_av): both modalities through this context, through `neg` (None:
+        no CFG term), through this context with the self-attentions of set_stg_blocks skipped into the `perturbed` scratch pair (None: no
+        STG term) and with every cross-modal attention skipped into the `isolated` pair (None: no modality term); then
+        MultiModalGuider.calculate with video_params / audio_params (MultiModalGuiderParams), post_process_latent and the Euler step of both
+        latents -- one launch, or per modality a sums and a step launch where rescale_scale != 0.  A scratch pair is (video (N, C), audio
+        (Na, Ca)) fp32.  Both contexts are prepared by the caller (neg with the negative contexts)."""
+        pos, ng = self._contexts(neg, av=True, optional=True)
+        ts, n_ts, sg, ats, n_ats = pos._step_inputs(latent, video, sigma, audio_latent, audio)
+        bufs = []
+        for pair in (isolated, perturbed):
+            for t in (pair or (None, None)):
+                assert t is None or (t.dtype == torch.float32 and t.is_contiguous())
+                bufs += [nv.ptr(t), 0 if t is None else t.numel()]
+        scales = [float(s) for p in (video_params, audio_params) for s in (p.cfg_scale, p.stg_scale, p.modality_scale, p.rescale_scale)]
+        nv.check(pos._L.ltx2_dit_mm_guided_step_av(pos._h, None if ng is None else ng._h, nv.ptr(latent), nv.ptr(audio_latent), nv.ptr(ts), n_ts,
+                                                   nv.ptr(ats), n_ats, nv.ptr(sg), nv.ptr(denoise_mask), nv.ptr(clean_latent), nv.ptr(audio_denoise_mask),
+                                                   nv.ptr(audio_clean_latent), *bufs, *scales, float(sigma), float(sigma_next), nv.stream()))
+
     def replace_weights(self, tensors: Dict[str, torch.Tensor]) -> None:
         """Re-register engine-layout tensors (names of weight_tensors()) in place of the ones held now -- the HQ pipeline's LoRA fusion for
         its second stage and the restore after it.  Contexts built over the old tensors (video twin, clone) are rebuilt on demand."""
@@ -979,6 +1026,11 @@ class X0Model:
                 return self._denoise(video, out[0]), out[1]
             return self._denoise(video, out[0]), self._denoise(audio, out[1])
         return self._denoise(video, out)
+
+    def forward_isolated(self, video: Modality, audio: Modality) -> Tuple[torch.Tensor, torch.Tensor]:
+        """x0 of both modalities from LTXModel.forward_isolated (no cross-modal attention in any layer)."""
+        v, a = self.velocity_model.forward_isolated(video, audio)
+        return self._denoise(video, v), self._denoise(audio, a)
 
 
 # aliases kept by the reference for backward compatibility (model.py:939-941)

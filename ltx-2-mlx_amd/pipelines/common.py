@@ -574,3 +574,89 @@ def res2s_av_denoise_loop(transformer, video_state: LatentState, audio_state: La
 
     _run_steps(n, callback, use_hip_graph, None, None, step, final)
     return _with_latent(video_state, lat), _with_latent(audio_state, alat)
+
+
+def multimodal_denoise_loop(transformer, video_state: LatentState, audio_state: LatentState, sigmas, video_context: torch.Tensor,
+                            audio_context: torch.Tensor, negative_video_context: Optional[torch.Tensor],
+                            negative_audio_context: Optional[torch.Tensor], video_guider, audio_guider, callback=None,
+                            fused: bool = True) -> Tuple[LatentState, LatentState]:
+    """Stage 1 of the two-stage pipeline on the AudioVideo model (the reference's _denoise_loop_cfg_av, pipelines/two_stage.py:314-401): per step
+    up to four evaluations of both modalities -- the positive prompt; the negative prompt when either MultiModalGuider
+    do_unconditional_generation(); the positive prompt with the self-attentions of the guiders' stg_blocks skipped when either
+    do_perturbed_generation() (the reference's loop never asks for it; its guider has the term); the positive prompt with every cross-modal
+    attention skipped when either do_isolated_modality_generation() -- then MultiModalGuider.calculate, post_process_latent and the Euler
+    step on both latents.  A pass that ran contributes its term to BOTH modalities, whatever their scales, as the reference hands both
+    guiders the same predictions.
+    fused=True: every step is ONE C call (LTXModel.mm_guided_step_av_): the evaluations, then one kernel over both latents (with
+    rescale_scale != 0, a sums and a step kernel per modality).  There is no captured form of this loop.  The latents are held in fp32
+    across the loop, as the other device-resident loops hold them.
+    fused=False: the eager composition, the reference's statements one by one: X0Model calls through the C entries, calculate,
+    post_process_latent and EulerDiffusionStep.
+    skip_step is not read (the reference's loop does not call should_skip_step).  `transformer` is an X0Model over an AudioVideo model.
+    Returns (video_state, audio_state)."""
+    from ..components import EulerDiffusionStep
+    model = transformer.velocity_model
+    if not model.is_av or audio_state is None:
+        raise ValueError("multimodal_denoise_loop requires an audio-video (AV) model and an audio state")
+    if audio_context is None:
+        raise ValueError("AudioVideo model: audio_encoding (the audio text context) is required")
+    sig = [float(s) for s in sigmas]
+    n = len(sig) - 1
+    guiders = (video_guider, audio_guider)
+    need_u = any(g.do_unconditional_generation() for g in guiders)
+    need_p = any(g.do_perturbed_generation() for g in guiders)
+    need_m = any(g.do_isolated_modality_generation() for g in guiders)
+    if need_u and (negative_video_context is None or negative_audio_context is None):
+        raise ValueError("guidance needs the negative prompt's encoding(s)")
+    if need_p:
+        blocks = [g.params.stg_blocks for g in guiders]
+        if all(b is not None and len(b) == 0 for b in blocks):
+            raise ValueError("stg_scale != 0 needs stg_blocks on at least one guider (None: every block)")
+        for k, b in enumerate(blocks):
+            model.set_stg_blocks(b, modality=k)
+    if not fused:
+        from ..components.perturbations import BatchedPerturbationConfig, Perturbation, PerturbationConfig, PerturbationType as PT
+        stepper = EulerDiffusionStep()
+        neg = X0Model(model.clone_sharing_weights()) if need_u else None
+        ptb = None
+        if need_p:
+            kinds = (PT.SKIP_VIDEO_SELF_ATTN, PT.SKIP_AUDIO_SELF_ATTN)
+            ptb = BatchedPerturbationConfig([PerturbationConfig([Perturbation(type=kinds[k], blocks=g.params.stg_blocks) for k, g in enumerate(guiders)
+                                                                 if g.params.stg_blocks is None or len(g.params.stg_blocks)])])
+        unif = [bool((st.denoise_mask == 1).all()) for st in (video_state, audio_state)]
+        for i in range(n):
+            vm = modality_from_state(video_state, video_context, sig[i], uniform=unif[0])
+            am = audio_modality_from_state(audio_state, audio_context, sig[i], uniform=unif[1])
+            cond = transformer(vm, am)
+            unc = ptd = mod = (0.0, 0.0)
+            if need_u:
+                unc = neg(modality_from_state(video_state, negative_video_context, sig[i], uniform=unif[0]),
+                          audio_modality_from_state(audio_state, negative_audio_context, sig[i], uniform=unif[1]))
+            if need_p:
+                ptd = transformer(vm, am, perturbations=ptb)
+            if need_m:
+                mod = transformer.forward_isolated(vm, am)
+            states = []
+            for k, st in enumerate((video_state, audio_state)):
+                d = post_process_latent(guiders[k].calculate(cond[k], unc[k], ptd[k], mod[k]), st.denoise_mask, st.clean_latent)
+                states.append(st.replace(latent=stepper.step(sample=st.latent, denoised_sample=d, sigmas=sig, step_index=i)))
+            video_state, audio_state = states
+            if callback:
+                callback(i + 1, n)
+        return video_state, audio_state
+    model, uniform, lat, mask, clean = _video_loop_inputs(model, video_state, video_only=False)
+    _, a_uniform, alat, amask, aclean = _video_loop_inputs(model, audio_state, video_only=False)
+    neg = _prepare_contexts(model, need_u, not (uniform and a_uniform), video_state.positions, video_context, negative_video_context,
+                            audio_state.positions, audio_context, negative_audio_context)
+    scratch = lambda: (lat.new_empty(lat.shape[0], model.out_channels), alat.new_empty(alat.shape[0], model.AUDIO_OUT_CHANNELS))      # noqa: E731
+    cond = dict(isolated=scratch() if need_m else None, perturbed=scratch() if need_p else None, denoise_mask=mask, clean_latent=clean,
+                audio_denoise_mask=amask, audio_clean_latent=aclean)
+
+    def step(i):
+        st, ast = video_state.replace(latent=lat[None]), audio_state.replace(latent=alat[None])
+        model.mm_guided_step_av_(neg, lat, alat, modality_from_state(st, video_context, sig[i], uniform=uniform),
+                                 audio_modality_from_state(ast, audio_context, sig[i], uniform=a_uniform), sig[i], sig[i + 1], video_guider.params,
+                                 audio_guider.params, **cond)
+
+    _run_steps(n, callback, False, None, None, step)
+    return _with_latent(video_state, lat), _with_latent(audio_state, alat)

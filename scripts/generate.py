@@ -9,7 +9,7 @@ encode_with_gemma :340-486, encode_av_gemma_batch :511-640; an LTX-2.3 checkpoin
 :548-551).  `--stg-scale S [--stg-blocks ... --stg-cutoff F]` adds spatio-temporal guidance on the av route (OneStagePipeline).  Out of this path (and rejected
 with a clear message): STG guidance on every other route, CFG in the video-only loop, the dev model's `--pipeline two-stage`.
 `generate_video` resolves its arguments once (`_resolve_request`: every refusal, before a model is loaded), loads the text encoding, the transformer and the VAE decoder, and
-runs ONE route, each a function of its own: hq_av (`--ti2vid-hq-audio --spatial-upscaler-weights W`: TI2VidHQPipeline with sound, the joint res_2s loop on the AudioVideo model), a2vid (`--a2vid-two-stage --audio FILE --spatial-upscaler-weights W`: the two-stage audio-to-video pipeline), retake (`--retake CLIP`), keyframe (`--pipeline keyframe-interpolation --keyframe path:frame[:strength]`), hq (`--ti2vid-hq`), ic_lora
+runs ONE route, each a function of its own: two_stage_cfg (`--two-stage-cfg --spatial-upscaler-weights W`: TwoStagePipeline, CFG + modality-isolated guidance on the AudioVideo model), hq_av (`--ti2vid-hq-audio --spatial-upscaler-weights W`: TI2VidHQPipeline with sound, the joint res_2s loop on the AudioVideo model), a2vid (`--a2vid-two-stage --audio FILE --spatial-upscaler-weights W`: the two-stage audio-to-video pipeline), retake (`--retake CLIP`), keyframe (`--pipeline keyframe-interpolation --keyframe path:frame[:strength]`), hq (`--ti2vid-hq`), ic_lora
 (`--pipeline ic-lora --control-video V` and / or `--image`), two_stage (`--two-stage-distilled --spatial-upscaler-weights W`; with `--generate-audio` on the AudioVideo transformer), av
 (`--generate-audio` or an LTX-2.3 checkpoint: the audio LATENT is saved beside the frames; `--decode-audio`, the default when the checkpoint holds the audio VAE decoder and vocoder, also
 decodes it to `<output>.wav` and muxes it into the mp4, reference save_video_with_audio; `--audio FILE` generates the video TO that audio: the audio VAE encoder's latent stays frozen in
@@ -621,12 +621,15 @@ _ROUTE_EXCLUDES = {
     "hq_av": (("audio_path", "two_stage_distilled", "upscale_temporal", "keyframes", "retake_video", "a2vid_two_stage"),
               "with ti2vid_hq_audio: TI2VidHQPipeline samples its own audio latent beside the video on the AudioVideo model, conditions on image_path "
               "alone and ends with its own x2 spatial stage"),
+    "two_stage_cfg": (("ti2vid_hq_audio", "a2vid_two_stage", "retake_video", "keyframes", "two_stage_distilled", "upscale_temporal", "audio_path"),
+                      "with two_stage_cfg: TwoStagePipeline samples its own audio latent beside the video on the AudioVideo model, conditions on image_path "
+                      "alone and ends with its own x2 spatial stage"),
 }
 # route -> the _OUT_OF_PATH_DEFAULTS arguments that route takes itself.  apg_scale: the routes whose guided loop takes a guider (the AudioVideo route as
 # OneStagePipeline's guider_override, keyframe stage 1, retake's guided mode).  stg_scale: OneStagePipeline alone (the AudioVideo route)
 _ROUTE_OWNS = {"keyframe": ("keyframes", "apg_scale"), "hq": ("distilled_lora", "keyframes"),
                "ic_lora": ("control_video", "save_control", "keyframes", "ic_lora_weights"), "retake": ("apg_scale",), "av": ("apg_scale", "stg_scale"), "a2vid": ("distilled_lora",),
-               "hq_av": ("distilled_lora",)}
+               "hq_av": ("distilled_lora",), "two_stage_cfg": ("distilled_lora",)}
 
 
 def _owning_route(r):
@@ -763,7 +766,15 @@ def _resolve_hq_av(r):
     r.generate_audio = True          # the AudioVideo transformer and both text encodings, as generate_audio asks for them
 
 
-_RESOLVE_ROUTE = {"keyframe": _resolve_keyframe, "hq": _resolve_hq, "ic_lora": _resolve_ic_lora, "a2vid": _resolve_a2vid, "hq_av": _resolve_hq_av}
+def _resolve_two_stage_cfg(r):
+    _need_spatial_upscaler(r)
+    from ltx_2_mlx_amd.pipelines import TwoStageCFGConfig
+    TwoStageCFGConfig(height=r.height, width=r.width, num_frames=r.num_frames)          # its ValueErrors (8k + 1 frames, multiples of 64)
+    r.two_stage_lora = _lora_config(r, r.distilled_lora, r.distilled_lora_scale, "distilled LoRA")
+    r.generate_audio = True          # the AudioVideo transformer and both text encodings, as generate_audio asks for them
+
+
+_RESOLVE_ROUTE = {"two_stage_cfg": _resolve_two_stage_cfg, "keyframe": _resolve_keyframe, "hq": _resolve_hq, "ic_lora": _resolve_ic_lora, "a2vid": _resolve_a2vid, "hq_av": _resolve_hq_av}
 
 
 def _resolve_request(kw: dict):
@@ -772,8 +783,10 @@ def _resolve_request(kw: dict):
     retake_to_end / retake_window, parsed_keyframes, hq_lora / ic_loras, cdt, need_cfg, gemma_encodes, encode_negative, have_ckpt / version / v2 / av, toy, output_dir, and negative_encoding /
     negative_audio_encoding of the embedding file.  Loads no model and touches no GPU; every refusal is raised here, in a fixed order.  Returns None (after saying so) when Gemma is asked for and
     its weights are missing."""
-    r = SimpleNamespace(**kw, retake_fps=None, retake_to_end=False, retake_window=None, parsed_keyframes=[], hq_lora=None, ic_loras=[], a2vid_lora=None)
-    if r.ti2vid_hq_audio:
+    r = SimpleNamespace(**kw, retake_fps=None, retake_to_end=False, retake_window=None, parsed_keyframes=[], hq_lora=None, ic_loras=[], a2vid_lora=None, two_stage_lora=None)
+    if r.two_stage_cfg:
+        r.route = "two_stage_cfg"
+    elif r.ti2vid_hq_audio:
         r.route = "hq_av"
     elif r.a2vid_two_stage:
         r.route = "a2vid"
@@ -887,7 +900,7 @@ def _resolve_request(kw: dict):
     if r.low_memory or r.fast_mode:
         print("  low_memory / fast_mode: no effect here (weights and caches stay resident in HBM, the loop is one hipGraph)")
     # the routes that guide themselves take Gemma's encoding of the negative prompt when they will guide (retake: the dev variant only)
-    r.encode_negative = (r.cfg_scale != 1.0 or r.apg_guider is not None) and (r.route in ("keyframe", "hq", "a2vid", "hq_av") or (r.route == "retake" and r.model_variant != "distilled"))
+    r.encode_negative = (r.cfg_scale != 1.0 or r.apg_guider is not None) and (r.route in ("keyframe", "hq", "a2vid", "hq_av", "two_stage_cfg") or (r.route == "retake" and r.model_variant != "distilled"))
     r.toy = r.vae_base_channels is not None and r.vae_base_channels != 128        # debug-size VAE: matching debug-size upscaler / encoder
     if r.route is None:
         r.route = "two_stage" if r.two_stage_distilled else "av" if r.av else "standard"
@@ -1004,6 +1017,7 @@ _REQUIRES = {
     "av": (None, "AV pipeline requires VAE decoder", "  AV pipeline requires model - cannot use placeholder mode", False),
     "a2vid": ("A2Vid pipeline requires a loaded model", "A2Vid pipeline requires VAE decoder", None, False),
     "hq_av": ("TI2Vid HQ pipeline requires a loaded model", "TI2Vid HQ pipeline requires VAE decoder", None, False),
+    "two_stage_cfg": ("Two-stage pipeline requires a loaded model", "Two-stage pipeline requires VAE decoder", None, False),
 }
 
 
@@ -1167,6 +1181,40 @@ def _run_hq_av(r, s):
         negative_audio = torch.zeros_like(s.text_audio_encoding)
     print(f"[5/5] Running TI2Vid HQ with audio ({r.num_steps} joint res_2s steps at {r.width // 2}x{r.height // 2}, then 3 at {r.width}x{r.height})...")
     frames, _ = _timed_run("ti2vid-hq audio+video", lambda: pipe(s.text_encoding, negative, conf, images=images, positive_audio_encoding=s.text_audio_encoding,
+                                                                 negative_audio_encoding=negative_audio))
+    return finish(r, s, frames, audio=decode_audio_latent(r, s, pipe.audio_latent))
+
+
+def _run_two_stage_cfg(r, s):
+    """two_stage_cfg=True (--two-stage-cfg; keyword-only) runs TwoStagePipeline, the reference's `--pipeline two-stage` on an AudioVideo checkpoint (reference :1276-1431): steps_stage1 joint
+    steps at half resolution, each the positive prompt, the negative prompt and the modality-isolated pass, the video guided at `cfg_stage1 or cfg_scale`, the audio at audio_cfg_scale (default
+    7), both at modality_scale (--modality-scale, default 3) and, with two_stage_rescale != 0, rescaled; the x2 spatial upscale of the video (spatial_upscaler_weights is required, "random"
+    for a random-initialised one), stage 1's audio latent re-noised, and 3 joint distilled steps, under distilled_lora when given; both stages run one C call per step.  image_path sits at
+    frame 0.  The negative encodings as in the hq_av route.  The audio latent is written to `<stem>_audio_latent.npz`; decode_audio turns it into `<stem>.wav`, muxed into the mp4, as in the av
+    route.  Not combined with ti2vid_hq_audio, a2vid_two_stage, retake_video, keyframes, two_stage_distilled, upscale_temporal or audio_path, nor distilled_lora with fp8_resident.
+    pipeline_type="two-stage" without this flag keeps its refusal."""
+    images = _image_conditions(r)
+    cfg = r.cfg_stage1 or r.cfg_scale
+    print("\n=== Using Two-Stage Pipeline ===")
+    print(f"  Stage 1: {r.steps_stage1} steps at {r.height // 2}x{r.width // 2} with CFG {cfg}")
+    if r.guidance_rescale > 0:
+        print(f"  Guidance rescale: {r.guidance_rescale}")
+    print(f"  Stage 2: 3 steps at {r.height}x{r.width} (distilled refinement)")
+    print("  Audio generation: ENABLED")
+    _require(r, s)
+    from ltx_2_mlx_amd.pipelines import TwoStageCFGConfig, TwoStagePipeline
+    conf = TwoStageCFGConfig(height=r.height, width=r.width, num_frames=r.num_frames, seed=r.seed, num_inference_steps=r.steps_stage1, cfg_scale=cfg,
+                             audio_cfg_scale=r.audio_cfg_scale, guidance_rescale=r.guidance_rescale, modality_scale=r.modality_scale,
+                             rescale_scale=r.two_stage_rescale, distilled_lora_config=r.two_stage_lora, tiling_config=_tiling(r))
+    _banners(r, upscaler=True)
+    pipe = TwoStagePipeline(s.model, make_encoder(r), s.vae_decoder, _load_or_random(r, "spatial"))
+    negative, negative_audio = s.negative_encoding, s.negative_audio_encoding
+    if _negative_or_zeros_note(True, negative):
+        negative = torch.zeros_like(s.text_encoding)
+    if _negative_or_zeros_note(True, negative_audio):
+        negative_audio = torch.zeros_like(s.text_audio_encoding)
+    print(f"[5/5] Running the two-stage pipeline ({r.steps_stage1} guided joint steps at {r.width // 2}x{r.height // 2}, then 3 at {r.width}x{r.height})...")
+    frames, _ = _timed_run("two-stage audio+video", lambda: pipe(s.text_encoding, negative, conf, images=images, positive_audio_encoding=s.text_audio_encoding,
                                                                  negative_audio_encoding=negative_audio))
     return finish(r, s, frames, audio=decode_audio_latent(r, s, pipe.audio_latent))
 
@@ -1406,7 +1454,7 @@ def _run_standard(r, s):
 
 
 # today's precedence, top to bottom; _resolve_request names the one that runs
-_ROUTES = {"hq_av": _run_hq_av, "a2vid": _run_a2vid, "keyframe": _run_keyframe, "hq": _run_hq, "ic_lora": _run_ic_lora, "retake": _run_retake, "two_stage": _run_two_stage,
+_ROUTES = {"two_stage_cfg": _run_two_stage_cfg, "hq_av": _run_hq_av, "a2vid": _run_a2vid, "keyframe": _run_keyframe, "hq": _run_hq, "ic_lora": _run_ic_lora, "retake": _run_retake, "two_stage": _run_two_stage,
            "av": _run_av, "standard": _run_standard}
 
 
@@ -1493,6 +1541,9 @@ def generate_video(
     audio_max_duration=None,
     a2vid_two_stage: bool = False,
     ti2vid_hq_audio: bool = False,
+    two_stage_cfg: bool = False,
+    modality_scale: float = 3.0,
+    two_stage_rescale: float = 0.0,
     retake_video=None,
     retake_start_time: float = 0.0,
     retake_end_time=None,
@@ -1500,7 +1551,7 @@ def generate_video(
 ):
     """Generate video from a text prompt: denoise loop + VAE decode on MI355X behind the reference's signature.  _resolve_request validates the arguments and names the one route that runs, before
     any model is loaded; then the text encoding, the transformer and the VAE decoder (built from the checkpoint's `config.vae` record) are loaded and the route's function runs.  Precedence, each
-    documented on its function: ti2vid_hq_audio (_run_hq_av; keyword-only), a2vid_two_stage (_run_a2vid; keyword-only, it refuses retake_video), retake_video (_run_retake; it refuses every other route), pipeline_type "keyframe-interpolation" with keyframes (_run_keyframe), "ti2vid-hq" (_run_hq), "ic-lora"
+    documented on its function: two_stage_cfg (_run_two_stage_cfg; keyword-only, with modality_scale and two_stage_rescale), ti2vid_hq_audio (_run_hq_av; keyword-only), a2vid_two_stage (_run_a2vid; keyword-only, it refuses retake_video), retake_video (_run_retake; it refuses every other route), pipeline_type "keyframe-interpolation" with keyframes (_run_keyframe), "ti2vid-hq" (_run_hq), "ic-lora"
     with a control video or an image (_run_ic_lora), two_stage_distilled (_run_two_stage), generate_audio or an LTX-2.3 checkpoint (_run_av), else the standard video-only loop (_run_standard).
     pipeline_type "two-stage" raises NotImplementedError. MI355X extras for every route: model_version="2.3" builds the LTX-2.3 architecture without a checkpoint (random init, for tests and
     benchmarks); fp8_resident keeps fp8 checkpoint weights as codes in HBM; fp8_compute runs the video stream's projections fp8 x fp8 on the fp8 MFMA (BASELINE config 3; per-token / per-channel
@@ -1605,6 +1656,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--ti2vid-hq-audio", action="store_true", help="TI2VidHQPipeline WITH sound on the AudioVideo model: --steps joint res_2s steps at half resolution (video guided "
                    "at --cfg, audio at audio_cfg_scale), x2 spatial upscale, 3 joint distilled steps; needs --spatial-upscaler-weights; --decode-audio writes the .wav. "
                    "(--ti2vid-hq / pipeline_type='ti2vid-hq' stays the video-only run and keeps refusing --generate-audio)")
+    p.add_argument("--two-stage-cfg", action="store_true", help="TwoStagePipeline (the reference's --pipeline two-stage on an AudioVideo checkpoint): --steps-stage1 joint steps at half "
+                   "resolution under CFG (video --cfg-stage1 or --cfg, audio 7) and modality-isolated guidance (--modality-scale), x2 spatial upscale, 3 joint distilled steps; needs "
+                   "--spatial-upscaler-weights; --decode-audio writes the .wav.  (--pipeline two-stage itself keeps its refusal)")
+    p.add_argument("--modality-scale", type=float, default=3.0, help="modality_scale of --two-stage-cfg: guidance away from the pass without audio<->video cross-attention")
     p.add_argument("--a2vid-two-stage", action="store_true", help="A2VidPipelineTwoStage: generate the video TO --audio at production quality on the AudioVideo model: --steps "
                    "steps at half resolution with classifier-free guidance on the video alone and the encoded audio frozen, x2 latent upscale "
                    "(--spatial-upscaler-weights), 3 distilled steps over the same frozen audio, optionally under --distilled-lora.  A flag of its own: "
@@ -1648,6 +1703,7 @@ def kwargs_from_args(a) -> dict:
         fp8_resident=a.fp8_resident, fp8_compute=a.fp8_compute, model_version=a.model_version, compute_dtype="bfloat16" if a.bf16 else None, num_layers=a.layers, num_heads=a.heads,
         vae_base_channels=a.vae_base_channels, save_mp4=not a.no_video_file, decode_audio=a.decode_audio,
         audio_path=a.audio, audio_start_time=a.audio_start, audio_max_duration=a.audio_duration, a2vid_two_stage=a.a2vid_two_stage, ti2vid_hq_audio=a.ti2vid_hq_audio,
+        two_stage_cfg=a.two_stage_cfg, modality_scale=a.modality_scale,
         retake_video=a.retake, retake_start_time=a.retake_start, retake_end_time=a.retake_end, retake_composite=a.retake_keep_source,
         stg_blocks=a.stg_blocks, stg_cutoff=a.stg_cutoff)
 
