@@ -298,6 +298,17 @@ int ltx2_guided_euler_step(const float* x, const float* vel_cond, const float* v
                            const float* mask, const float* clean, float cfg_scale, float sigma, float sigma_next,
                            float* out, int rows, int C, void* stream);
 
+/* ltx2_guided_euler_step over TWO latents in ONE launch (the video and the audio latent of a joint guided step; the audio one is ~100 rows, a
+ * launch of its own nearly all latency): v_ then a_, each with its own operands, cfg_scale, timesteps, mask / clean and shape; sigma and
+ * sigma_next are shared.  The per-element arithmetic is ltx2_guided_euler_step's, so each segment's output equals the single launch's bit for
+ * bit.  16-byte accesses only when both segments allow them.  sigma == 0 -> LTX2_E_INVALID with message "Sigma can't be 0.0".
+ * (additive entry of ABI version 3)                                                                                                      */
+int ltx2_guided_euler_step_pair(const float* v_x, const float* v_vel_cond, const float* v_vel_uncond, const float* v_ts, int64_t v_ts_stride,
+                                const float* v_mask, const float* v_clean, float v_cfg_scale, float* v_out, int v_rows, int v_C, const float* a_x,
+                                const float* a_vel_cond, const float* a_vel_uncond, const float* a_ts, int64_t a_ts_stride, const float* a_mask,
+                                const float* a_clean, float a_cfg_scale, float* a_out, int a_rows, int a_C, float sigma, float sigma_next,
+                                void* stream);
+
 /* ltx2_guided_euler_step with spatio-temporal guidance (STG) on top: STGGuider.guide applied to the CFG-guided x0 (pipelines/one_stage.py:284-297).
  * vel_perturbed is the velocity of a forward whose chosen self-attentions were skipped (ltx2_dit_forward_perturbed).  Per element, every
  * operation individually rounded, so the result equals the separate fp32 torch ops bit for bit:
@@ -596,6 +607,23 @@ int ltx2_dit_guided_step_av(ltx2_dit* ctx, ltx2_dit* neg, float* v_latent, const
 int ltx2_dit_graph_capture_guided_av(ltx2_dit* ctx, ltx2_dit* neg, float* v_latent, const float* a_latent, const float* host_sigmas, int n_steps,
                                      const float* v_mask, int64_t n_v_mask, const float* v_clean, int64_t n_v_clean, const float* a_mask,
                                      int64_t n_a_mask, float cfg_scale, void* stream);
+/* The guided step on the AudioVideo engine with BOTH latents stepped (a retake with sound; the reference's pipelines/retake.py:234-291 run with an
+ * audio state): forward_av on ctx, then on neg, exactly as ltx2_dit_guided_step_av builds them, then ONE ltx2_guided_euler_step_pair in place on both
+ * latents, the video under cfg_scale and the audio under audio_cfg_scale.  Each modality may carry a denoise mask with its clean latent (both or
+ * neither).  LTX2_E_INVALID, before anything is launched: the rules of ltx2_dit_guided_step_av, a mask without its clean latent (or the reverse),
+ * sigma == 0.
+ * ltx2_dit_graph_capture_guided_joint_av: n_steps (< 64) of that step as one captured graph owned by ctx (ltx2_dit_graph_launch(ctx) replays it),
+ * built like ltx2_dit_graph_capture_guided_av: a modality with a mask gets per-token timesteps mask * sigma_i formed on the device into ctx's buffer,
+ * which both contexts read, and its x0 blended with its clean latent; n_*: ELEMENT counts, checked against the bound shapes.
+ * (additive entries of ABI version 3)                                                                                                       */
+int ltx2_dit_guided_step_joint_av(ltx2_dit* ctx, ltx2_dit* neg, float* v_latent, float* a_latent, const float* v_timesteps, int n_v_timesteps,
+                                  const float* a_timesteps, int n_a_timesteps, const float* sigma_dev, const float* v_mask, const float* v_clean,
+                                  const float* a_mask, const float* a_clean, float cfg_scale, float audio_cfg_scale, float sigma, float sigma_next,
+                                  void* stream);
+int ltx2_dit_graph_capture_guided_joint_av(ltx2_dit* ctx, ltx2_dit* neg, float* v_latent, float* a_latent, const float* host_sigmas, int n_steps,
+                                           const float* v_mask, int64_t n_v_mask, const float* v_clean, int64_t n_v_clean, const float* a_mask,
+                                           int64_t n_a_mask, const float* a_clean, int64_t n_a_clean, float cfg_scale, float audio_cfg_scale,
+                                           void* stream);
 /* ltx2_dit_guided_step with a guider whose scalars are sums over the whole latent: forward(ctx), forward(neg), ltx2_guidance_sums and
  * ltx2_projected_euler_step in place on `latent`, in order on the caller's stream.  mode / scale / eta / norm_threshold as in
  * ltx2_projected_euler_step; momentum != 0 (mode 2 only) keeps the running guidance in a [N][out_channels] fp32 buffer owned by ctx: first != 0
@@ -855,6 +883,22 @@ int ltx2_retake_prepare(const float* encoded, const float* noise, int C, int F, 
  * 16-byte aligned, one byte per lane otherwise and for the last T*H*W*3 % 16 bytes. */
 #define LTX2_RETAKE_MAX_RAMP 65535
 int ltx2_retake_composite(const uint8_t* decoded, const uint8_t* source, int T, int H, int W, int p0, int p1, int ramp, uint8_t* out, void* stream);
+/* The same glue for the clip's sound track.  encoded: the audio VAE encoder's latent, fp32 [C][T][M] (checkpoints: C = 8, M = 16); noise: token-major
+ * fp32 [T][C*M].  One pass writes
+ *   clean[t][c*M + m] = encoded[c][t][m]                             (AudioPatchifier.patchify),
+ *   mask[t]           = 1.0f on the latent frames [a0, a1), 0.0f elsewhere,
+ *   latent[t][j]      = noise[t][j] * sm + clean[t][j] * (1.0f - sm),  sm = mask[t] * noise_scale,
+ * rounded as ltx2_retake_prepare rounds (no FMA): the separate fp32 torch statements, bit for bit.  0 <= a0 <= a1 <= T; out of place. */
+int ltx2_retake_prepare_audio(const float* encoded, const float* noise, int C, int T, int M, int a0, int a1, float noise_scale, float* clean,
+                              float* mask, float* latent, void* stream);
+/* fp32 waveforms [channels][S] at one rate: out = decoded on the samples [s0, s1).  A sample outside the window lies at distance d = s0 - s
+ * (before) or s - s1 + 1 (after), as in ltx2_retake_composite; with R = ramp + 1 and a = max(R - d, 0) it is
+ *   (decoded * (float)a + source * (float)(R - a)) / (float)R
+ * as two multiplies, one add and one IEEE divide, each rounded on its own (no FMA); a == 0 (ramp = 0: every sample outside) is the source's own
+ * bits.  0 <= s0 <= s1 <= S, 0 <= ramp <= LTX2_RETAKE_AUDIO_MAX_RAMP (R stays exact in fp32); out may not overlap an input. */
+#define LTX2_RETAKE_AUDIO_MAX_RAMP 16777215
+int ltx2_retake_composite_audio(const float* decoded, const float* source, int channels, int64_t S, int64_t s0, int64_t s1, int ramp, float* out,
+                                void* stream);
 
 #ifdef __cplusplus
 }

@@ -31,6 +31,7 @@ AUDIO_ACT_NONE, AUDIO_ACT_TANH, AUDIO_ACT_CLIP, AUDIO_ACT_LOG, AUDIO_ACT_SILU = 
 VAE_MAX_BLOCKS = 16
 CANNY_TILE_H, CANNY_TILE_W, CANNY_FLAG_BYTES = 32, 64, 16      # LTX2_CANNY_TILE_H / _W / LTX2_CANNY_FLAG_BYTES
 RETAKE_MAX_RAMP = 65535                                        # LTX2_RETAKE_MAX_RAMP
+RETAKE_AUDIO_MAX_RAMP = 16777215                               # LTX2_RETAKE_AUDIO_MAX_RAMP
 
 vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_float
 
@@ -88,6 +89,8 @@ SIGNATURES = {
     "ltx2_x0_from_velocity": (i32, [vp, vp, vp, i64, f32, vp, i32, i32, vp]),
     "ltx2_euler_step": (i32, [vp, vp, vp, vp, f32, f32, vp, i32, i32, vp]),
     "ltx2_guided_euler_step": (i32, [vp, vp, vp, vp, i64, vp, vp, f32, f32, f32, vp, i32, i32, vp]),
+    "ltx2_guided_euler_step_pair": (i32, [vp, vp, vp, vp, i64, vp, vp, f32, vp, i32, i32,
+                                          vp, vp, vp, vp, i64, vp, vp, f32, vp, i32, i32, f32, f32, vp]),
     "ltx2_stg_euler_step": (i32, [vp, vp, vp, vp, vp, i64, vp, vp, f32, f32, f32, f32, vp, i32, i32, vp]),
     "ltx2_res2s_midpoint": (i32, [vp, vp, vp, vp, i64, vp, vp, f32, f32, i32, vp, vp, vp, i32, i32, vp]),
     "ltx2_res2s_combine": (i32, [vp, vp, vp, vp, i64, vp, vp, f32, vp, vp, f32, f32, f32, vp, i32, i32, vp]),
@@ -139,6 +142,8 @@ SIGNATURES = {
     "ltx2_dit_graph_capture_guided": (i32, [vp, vp, vp, C.POINTER(f32), i32, vp, i64, vp, i64, f32, vp]),
     "ltx2_dit_guided_step_av": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, f32, f32, f32, vp]),
     "ltx2_dit_graph_capture_guided_av": (i32, [vp, vp, vp, vp, C.POINTER(f32), i32, vp, i64, vp, i64, vp, i64, f32, vp]),
+    "ltx2_dit_guided_step_joint_av": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, f32, f32, f32, f32, vp]),
+    "ltx2_dit_graph_capture_guided_joint_av": (i32, [vp, vp, vp, vp, C.POINTER(f32), i32, vp, i64, vp, i64, vp, i64, vp, i64, f32, f32, vp]),
     "ltx2_dit_projected_step": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, i32, f32, f32, f32, f32, i32, f32, f32, vp]),
     "ltx2_dit_graph_capture_projected": (i32, [vp, vp, vp, C.POINTER(f32), i32, vp, i64, vp, i64, i32, f32, f32, f32, f32, vp]),
     "ltx2_dit_res2s_step": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, f32, f32, f32, vp]),
@@ -181,6 +186,8 @@ SIGNATURES = {
     # source-clip glue of the retake pipeline (additive)
     "ltx2_retake_prepare": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp]),
     "ltx2_retake_composite": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "ltx2_retake_prepare_audio": (i32, [vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp]),
+    "ltx2_retake_composite_audio": (i32, [vp, vp, i32, i64, i64, i64, i32, vp, vp]),
 }
 
 _libs: dict = {}

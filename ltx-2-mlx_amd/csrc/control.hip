@@ -2,7 +2,8 @@
 // operand of the VAE encoder, with their ltx2_canny_* / ltx2_frames_to_patches C entry points (declared in include/ltx2hip.h).
 // Canny is integer arithmetic throughout (the definition is written out in the header); only frames_to_patches depends on LTX2_F16.
 // The source-clip glue of the retake pipeline (pipelines/retake.py) lives here too: ltx2_retake_prepare (the encoded clip -> clean tokens,
-// temporal mask and noised latent in one pass) and ltx2_retake_composite (the untouched frames put back, in integers).
+// temporal mask and noised latent in one pass) and ltx2_retake_composite (the untouched frames put back, in integers), with their twins for
+// the clip's sound track: ltx2_retake_prepare_audio (the audio encoder's latent) and ltx2_retake_composite_audio (fp32 waveforms).
 #include <math.h>
 
 #include "../../include/ltx2hip.h"
@@ -307,6 +308,53 @@ __global__ __launch_bounds__(256) void retake_composite_kernel(const unsigned ch
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------
+// Retake with sound: the audio encoder's latent [C][T][M] -> token-major clean [T][C*M] (AudioPatchifier.patchify), mask [T] (1 on the
+// latent frames [a0, a1)) and latent = noise*sm + clean*(1 - sm), sm = mask*noise_scale, rounded as retake_prepare_kernel rounds.  One
+// lane per output element; the whole track is a few thousand floats (C*M = 128 per 40 ms), so there is no tile to stage: a row of M
+// consecutive lanes reads M consecutive floats and writes M consecutive floats.
+// ------------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void retake_prepare_audio_kernel(const float* __restrict__ encoded, const float* __restrict__ noise, int C, int T,
+                                                                   int M, int a0, int a1, float noise_scale, float* __restrict__ clean,
+                                                                   float* __restrict__ mask, float* __restrict__ latent) {
+    const long row = (long)C * M, n = row * T;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const int t = (int)(i / row), r = (int)(i - (long)t * row), c = r / M, m = r - c * M;
+        const float mk = (t >= a0 && t < a1) ? 1.f : 0.f;
+        const float sm = mul_rn(mk, noise_scale), om = sub_rn(1.0f, sm);
+        const float v = encoded[((long)c * T + t) * M + m];
+        if (r == 0) mask[t] = mk;
+        clean[i] = v;
+        latent[i] = add_rn(mul_rn(noise[i], sm), mul_rn(v, om));
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Retake with sound: fp32 waveforms [channels][S].  out = decoded on the samples [s0, s1); a sample at distance d outside the window (as
+// composite_weight measures it) is (decoded*a + source*(R - a)) / R with R = ramp + 1, a = max(R - d, 0): two multiplies, one add and one
+// IEEE divide, each rounded on its own.  a == 0 takes the source's own bits (the formula would turn a source -0.0f into +0.0f and let a
+// decoded inf or NaN through a zero weight).  R <= 2^24, so (float)a and (float)(R - a) are exact.
+// ------------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void retake_composite_audio_kernel(const float* __restrict__ decoded, const float* __restrict__ source,
+                                                                     float* __restrict__ out, long S, long total, long s0, long s1, unsigned R) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const long s = i % S;
+        float o;
+        if (s >= s0 && s < s1) {
+            o = decoded[i];
+        } else {
+            const long d = s < s0 ? s0 - s : s - s1 + 1;
+            if (d >= (long)R) {
+                o = source[i];
+            } else {
+                const unsigned a = R - (unsigned)d;
+                o = __fdiv_rn(add_rn(mul_rn(decoded[i], (float)a), mul_rn(source[i], (float)(R - a))), (float)R);
+            }
+        }
+        out[i] = o;
+    }
+}
+
 bool ranges_overlap(const void* a, int64_t na, const void* b, int64_t nb) {
     const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
     return a0 < b0 + (uintptr_t)nb && b0 < a0 + (uintptr_t)na;
@@ -431,6 +479,44 @@ int ltx2_retake_composite(const uint8_t* decoded, const uint8_t* source, int T, 
     hipLaunchKernelGGL(retake_composite_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, (hipStream_t)stream, decoded, source,
                        out, (long)frame_bytes, (long)nvec, (long)total, p0, p1, (unsigned)(ramp + 1));
     LTX2_CHECK_LAUNCH("retake_composite_kernel");
+    return LTX2_OK;
+}
+
+int ltx2_retake_prepare_audio(const float* encoded, const float* noise, int C, int T, int M, int a0, int a1, float noise_scale, float* clean,
+                              float* mask, float* latent, void* stream) {
+    LTX2_CHECK_ARG(encoded && noise && clean && mask && latent, "retake_prepare_audio: null operand");
+    LTX2_CHECK_ARG(C > 0 && T > 0 && M > 0 && (int64_t)C * M <= 0x7fffffffLL, "retake_prepare_audio: C %d T %d M %d", C, T, M);
+    LTX2_CHECK_ARG(0 <= a0 && a0 <= a1 && a1 <= T, "retake_prepare_audio: latent-frame window [%d, %d) is not within 0 <= a0 <= a1 <= T = %d", a0, a1, T);
+    LTX2_CHECK_ARG(noise_scale == noise_scale && fabsf(noise_scale) <= 1e9f, "retake_prepare_audio: noise_scale %f", noise_scale);
+    const int64_t n = (int64_t)C * M * T, nb = n * (int64_t)sizeof(float), mb = T * (int64_t)sizeof(float);
+    const void* ins[2] = {encoded, noise};
+    void* outs[3] = {clean, mask, latent};
+    const int64_t obytes[3] = {nb, mb, nb};
+    for (int o = 0; o < 3; ++o) {
+        for (int i = 0; i < 2; ++i)
+            LTX2_CHECK_ARG(!ranges_overlap(outs[o], obytes[o], ins[i], nb), "retake_prepare_audio: an output overlaps an input (out of place only)");
+        for (int q = o + 1; q < 3; ++q)
+            LTX2_CHECK_ARG(!ranges_overlap(outs[o], obytes[o], outs[q], obytes[q]), "retake_prepare_audio: two outputs overlap");
+    }
+    hipLaunchKernelGGL(retake_prepare_audio_kernel, dim3(grid_for(n, 256, 16384)), dim3(256), 0, (hipStream_t)stream, encoded, noise, C, T, M, a0, a1,
+                       noise_scale, clean, mask, latent);
+    LTX2_CHECK_LAUNCH("retake_prepare_audio_kernel");
+    return LTX2_OK;
+}
+
+int ltx2_retake_composite_audio(const float* decoded, const float* source, int channels, int64_t S, int64_t s0, int64_t s1, int ramp, float* out,
+                                void* stream) {
+    LTX2_CHECK_ARG(decoded && source && out, "retake_composite_audio: null operand");
+    LTX2_CHECK_ARG(channels > 0 && S > 0 && S <= 0x7fffffffffffLL / channels, "retake_composite_audio: channels %d S %ld", channels, (long)S);
+    LTX2_CHECK_ARG(0 <= s0 && s0 <= s1 && s1 <= S, "retake_composite_audio: sample window [%ld, %ld) is not within 0 <= s0 <= s1 <= S = %ld", (long)s0,
+                   (long)s1, (long)S);
+    LTX2_CHECK_ARG(ramp >= 0 && ramp <= LTX2_RETAKE_AUDIO_MAX_RAMP, "retake_composite_audio: ramp %d (0 .. %d)", ramp, LTX2_RETAKE_AUDIO_MAX_RAMP);
+    const int64_t total = S * channels, bytes = total * (int64_t)sizeof(float);
+    LTX2_CHECK_ARG(!ranges_overlap(out, bytes, decoded, bytes) && !ranges_overlap(out, bytes, source, bytes),
+                   "retake_composite_audio: out overlaps an input (out of place only)");
+    hipLaunchKernelGGL(retake_composite_audio_kernel, dim3(grid_for(total, 256, 16384)), dim3(256), 0, (hipStream_t)stream, decoded, source, out,
+                       (long)S, (long)total, (long)s0, (long)s1, (unsigned)(ramp + 1));
+    LTX2_CHECK_LAUNCH("retake_composite_audio_kernel");
     return LTX2_OK;
 }
 

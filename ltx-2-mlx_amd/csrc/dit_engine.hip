@@ -1346,6 +1346,18 @@ int guided_step(ltx2_dit* c, ltx2_dit* neg, const ModIn* in, const StepIo& io, f
                                     io.latent, m.N, m.Cout, st);
 }
 
+// The same on AudioVideo contexts with BOTH latents stepped (a retake with sound; the reference's pipelines/retake.py:234-291 run with an audio state):
+// the two evaluations, then ONE element-wise launch over both latents, the video under cfg[0] and the audio under cfg[1].
+int guided_step_joint(ltx2_dit* c, ltx2_dit* neg, const ModIn* in, const StepIo* io, const float cfg[2], float sigma, float sigma_next, hipStream_t st,
+                      bool rewind_events = true) {
+    TRY(step_check(sigma, io, 2, "dit_guided_step_joint_av"));
+    const Mod &v = c->m[0], &a = c->m[1];
+    TRY(evaluate(c, neg, in, st, rewind_events));
+    return guided_euler_step_pair_launch(in[0].latent, v.vel, neg->m[0].vel, in[0].ts, in[0].n_ts == 1 ? 0 : 1, io[0].mask, io[0].clean, cfg[0], io[0].latent,
+                                         v.N, v.Cout, in[1].latent, a.vel, neg->m[1].vel, in[1].ts, in[1].n_ts == 1 ? 0 : 1, io[1].mask, io[1].clean, cfg[1],
+                                         io[1].latent, a.N, a.Cout, sigma, sigma_next, st);
+}
+
 // Spatio-temporal guidance on top (pipelines/one_stage.py:284-297): a third evaluation, on c ITSELF with the self-attentions of c->stg[0] skipped (no third
 // context: its text K / V would be a second copy of c's), into the caller's scratch; then the one element-wise pass.  neg may be NULL: no CFG.
 int stg_step(ltx2_dit* c, ltx2_dit* neg, const ModIn& in, const StepIo& io, float* vel_perturbed, float cfg_scale, float stg_scale, float sigma,
@@ -1588,7 +1600,7 @@ int res2s_step(ltx2_dit* c, ltx2_dit* neg, const ModIn* in, const float* v_ts_su
 // The one captured sampling loop behind every ltx2_dit_graph_capture* entry: per step, sigma_i read on the device, each modality's timesteps (sigma_i, or
 // mask * sigma_i where it is conditioned), then the step that LoopStep names.  All but the plain step run on VideoOnly contexts (latent[0] / cond[0]
 // only), form ts = mask * sigma_i in c's buffer and let both contexts read it; the guided step on AudioVideo contexts steps latent[0] alone and reads
-// latent[1] (cond[1]: its mask, for the timesteps only).  The event pool is rewound on step 0 only, so no event is re-recorded
+// latent[1] (cond[1]: its mask, for the timesteps only), unless it is the joint one, which steps and blends both.  The event pool is rewound on step 0 only, so no event is re-recorded
 // inside the capture.
 struct LoopStep {                           // all defaults: the plain denoise step
     ltx2_dit* neg = nullptr;                // the negative prompt's context: a guided step, or guidance inside the two below
@@ -1598,6 +1610,8 @@ struct LoopStep {                           // all defaults: the plain denoise s
     float* stg_vel = nullptr;               // the STG step into this scratch on the first stg_steps steps, then the guided (neg) or the plain step
     float stg_scale = 0.f;
     int stg_steps = 0;
+    bool joint = false;                     // the guided step on AudioVideo contexts steps BOTH latents, the audio one under audio_cfg_scale
+    float audio_cfg_scale = 0.f;
 };
 
 int capture_loop(ltx2_dit* c, const LoopStep& step, float* const latent[2], const Cond cond[2], const float* host_sigmas, int n_steps, hipStream_t st) {
@@ -1619,7 +1633,7 @@ int capture_loop(ltx2_dit* c, const LoopStep& step, float* const latent[2], cons
         for (int k = 0; k < nm && rc == LTX2_OK; ++k) {
             in[k] = {latent[k], s, 1, s, nullptr};
             io[k] = {latent[k], nullptr, nullptr, nullptr};
-            rc = cond_modality(c, k, cond[k], s, in[k], io[k], st, !(step.neg && c->av && k == 1));
+            rc = cond_modality(c, k, cond[k], s, in[k], io[k], st, !(step.neg && c->av && k == 1 && !step.joint));
         }
         if (rc != LTX2_OK) break;
         if (step.res2s) {
@@ -1629,6 +1643,9 @@ int capture_loop(ltx2_dit* c, const LoopStep& step, float* const latent[2], cons
             rc = projected_step(c, step.neg, in[0], io[0], *step.projected, i == 0, sigma, sigma_next, st);
         } else if (step.stg_vel && i < step.stg_steps) {
             rc = stg_step(c, step.neg, in[0], io[0], step.stg_vel, step.cfg_scale, step.stg_scale, sigma, sigma_next, st);
+        } else if (step.neg && step.joint) {
+            const float cfg[2] = {step.cfg_scale, step.audio_cfg_scale};
+            rc = guided_step_joint(c, step.neg, in, io, cfg, sigma, sigma_next, st, i == 0);
         } else if (step.neg && c->av) {
             rc = guided_step(c, step.neg, in, io[0], step.cfg_scale, sigma, sigma_next, st, i == 0);
         } else if (step.neg) {
@@ -1646,12 +1663,15 @@ struct LoopIo {
     Cond cond[2];
 };
 
-int capture_ready(ltx2_dit* c, ltx2_dit* neg, bool need_neg, bool want_av, const LoopIo& lo, const float* host_sigmas, int n_steps, const char* who) {
+// joint: both latents are stepped, so the audio's mask and clean latent go together as the video's do (otherwise the audio's mask gives timesteps only)
+int capture_ready(ltx2_dit* c, ltx2_dit* neg, bool need_neg, bool want_av, const LoopIo& lo, const float* host_sigmas, int n_steps, const char* who,
+                  bool joint = false) {
     LTX2_CHECK_ARG(c && lo.lat[0] && (!want_av || lo.lat[1]) && host_sigmas && n_steps > 0 && n_steps < 64, "%s: bad argument", who);
     LTX2_CHECK_ARG(neg || !need_neg, "%s: null context", who);
     const int n_ts[2] = {lo.cond[0].mask ? c->m[0].N : 1, lo.cond[1].mask ? c->m[1].N : 1};
     TRY(step_ready(c, neg, want_av, n_ts, who));
-    LTX2_CHECK_ARG((lo.cond[0].mask == nullptr) == (lo.cond[0].clean == nullptr), "%s: mask and clean go together", who);
+    for (int k = 0; k < (joint ? 2 : 1); ++k)
+        LTX2_CHECK_ARG((lo.cond[k].mask == nullptr) == (lo.cond[k].clean == nullptr), "%s: mask and clean go together", who);
     return LTX2_OK;
 }
 }  // namespace
@@ -1675,6 +1695,21 @@ int ltx2_dit_guided_step_av(ltx2_dit* c, ltx2_dit* neg, float* v_latent, const f
     // the audio latent is read by both evaluations and never written
     const ModIn in[2] = {v.in, step_args(const_cast<float*>(a_latent), a_timesteps, n_a_timesteps, sigma_dev, nullptr, nullptr).in};
     return guided_step(c, neg, in, v.io, cfg_scale, sigma, sigma_next, (hipStream_t)stream);
+}
+
+int ltx2_dit_guided_step_joint_av(ltx2_dit* c, ltx2_dit* neg, float* v_latent, float* a_latent, const float* v_timesteps, int n_v_timesteps,
+                                  const float* a_timesteps, int n_a_timesteps, const float* sigma_dev, const float* v_mask, const float* v_clean,
+                                  const float* a_mask, const float* a_clean, float cfg_scale, float audio_cfg_scale, float sigma, float sigma_next,
+                                  void* stream) {
+    LTX2_CHECK_ARG(neg && v_latent && a_latent && v_timesteps && a_timesteps && sigma_dev, "dit_guided_step_joint_av: null argument");
+    const int n_ts[2] = {n_v_timesteps, n_a_timesteps};
+    TRY(step_ready(c, neg, true, n_ts, "dit_guided_step_joint_av"));
+    const StepArgs v = step_args(v_latent, v_timesteps, n_v_timesteps, sigma_dev, v_mask, v_clean);
+    const StepArgs a = step_args(a_latent, a_timesteps, n_a_timesteps, sigma_dev, a_mask, a_clean);
+    const ModIn in[2] = {v.in, a.in};
+    const StepIo io[2] = {v.io, a.io};
+    const float cfg[2] = {cfg_scale, audio_cfg_scale};
+    return guided_step_joint(c, neg, in, io, cfg, sigma, sigma_next, (hipStream_t)stream);
 }
 
 int ltx2_dit_stg_step(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev, const float* mask,
@@ -1848,6 +1883,19 @@ int ltx2_dit_graph_capture_guided_av(ltx2_dit* c, ltx2_dit* neg, float* v_latent
     const LoopIo lo = {{v_latent, const_cast<float*>(a_latent)}, {{v_mask, (long)n_v_mask, v_clean, (long)n_v_clean}, {a_mask, (long)n_a_mask, nullptr, 0}}};
     TRY(capture_ready(c, neg, true, true, lo, host_sigmas, n_steps, "dit_graph_capture_guided_av"));
     return capture_loop(c, {neg, cfg_scale}, lo.lat, lo.cond, host_sigmas, n_steps, (hipStream_t)stream);
+}
+
+int ltx2_dit_graph_capture_guided_joint_av(ltx2_dit* c, ltx2_dit* neg, float* v_latent, float* a_latent, const float* host_sigmas, int n_steps,
+                                           const float* v_mask, int64_t n_v_mask, const float* v_clean, int64_t n_v_clean, const float* a_mask,
+                                           int64_t n_a_mask, const float* a_clean, int64_t n_a_clean, float cfg_scale, float audio_cfg_scale, void* stream) {
+    const LoopIo lo = {{v_latent, a_latent}, {{v_mask, (long)n_v_mask, v_clean, (long)n_v_clean}, {a_mask, (long)n_a_mask, a_clean, (long)n_a_clean}}};
+    TRY(capture_ready(c, neg, true, true, lo, host_sigmas, n_steps, "dit_graph_capture_guided_joint_av", true));
+    LoopStep step;
+    step.neg = neg;
+    step.cfg_scale = cfg_scale;
+    step.joint = true;
+    step.audio_cfg_scale = audio_cfg_scale;
+    return capture_loop(c, step, lo.lat, lo.cond, host_sigmas, n_steps, (hipStream_t)stream);
 }
 
 int ltx2_dit_graph_capture_av(ltx2_dit* c, float* v_latent, float* a_latent, const float* host_sigmas, int n_steps,

@@ -19,6 +19,14 @@ int guided_euler_step_launch(const float* x, const float* vel_cond, const float*
                              const float* mask, const float* clean, float cfg_scale, float sigma, float sigma_next, float* out,
                              int rows, int C, hipStream_t stream);
 
+// The same step over the video and the audio latent in ONE launch (the joint guided loop of a retake with sound), v_ then a_, each with its own
+// operands, cfg_scale, timesteps, mask / clean and shape; sigma / sigma_next are shared.  Each segment's output is the single launch's bit for bit.
+int guided_euler_step_pair_launch(const float* v_x, const float* v_vel_cond, const float* v_vel_uncond, const float* v_ts, long v_ts_stride,
+                                  const float* v_mask, const float* v_clean, float v_cfg_scale, float* v_out, int v_rows, int v_C, const float* a_x,
+                                  const float* a_vel_cond, const float* a_vel_uncond, const float* a_ts, long a_ts_stride, const float* a_mask,
+                                  const float* a_clean, float a_cfg_scale, float* a_out, int a_rows, int a_C, float sigma, float sigma_next,
+                                  hipStream_t stream);
+
 // The same step with spatio-temporal guidance on top (STGGuider.guide applied to the CFG-guided x0; vel_perturbed: the velocity of the pass whose
 // self-attentions were skipped): g as above (g = a when vel_uncond is NULL), p = x - t*vp, s = g + stg_scale*(g - p), then d and out from s
 int stg_euler_step_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* vel_perturbed, const float* ts, long ts_stride,

@@ -520,6 +520,19 @@ int guided_euler_step_launch(const float* x, const float* vel_cond, const float*
     return launch_rows("guided_euler_step", x && vel_cond && vel_uncond && out, op, ts, ts_stride, mask, clean, rows, C, 0, stream);
 }
 
+int guided_euler_step_pair_launch(const float* v_x, const float* v_vel_cond, const float* v_vel_uncond, const float* v_ts, long v_ts_stride,
+                                  const float* v_mask, const float* v_clean, float v_cfg_scale, float* v_out, int v_rows, int v_C, const float* a_x,
+                                  const float* a_vel_cond, const float* a_vel_uncond, const float* a_ts, long a_ts_stride, const float* a_mask,
+                                  const float* a_clean, float a_cfg_scale, float* a_out, int a_rows, int a_C, float sigma, float sigma_next,
+                                  hipStream_t stream) {
+    LTX2_CHECK_ARG(sigma != 0.f, "Sigma can't be 0.0");   // reference core_utils.py:54-55
+    const float inv = 1.0f / sigma, dt = sigma_next - sigma;
+    const GuidedEuler v = {{}, {v_x, v_vel_cond, v_vel_uncond, v_clean}, {v_out}, v_cfg_scale - 1.0f, inv, dt};
+    const GuidedEuler a = {{}, {a_x, a_vel_cond, a_vel_uncond, a_clean}, {a_out}, a_cfg_scale - 1.0f, inv, dt};
+    return launch_rows2("guided_euler_step_pair", v_x && v_vel_cond && v_vel_uncond && v_out && a_x && a_vel_cond && a_vel_uncond && a_out, v,
+                        {v_ts, v_ts_stride, v_mask, v_clean, v_rows, v_C}, a, {a_ts, a_ts_stride, a_mask, a_clean, a_rows, a_C}, stream);
+}
+
 int stg_euler_step_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* vel_perturbed, const float* ts, long ts_stride,
                           const float* mask, const float* clean, float cfg_scale, float stg_scale, float sigma, float sigma_next, float* out, int rows,
                           int C, hipStream_t stream) {

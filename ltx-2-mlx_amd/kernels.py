@@ -534,6 +534,24 @@ def guided_euler_step(x: torch.Tensor, vel_cond: torch.Tensor, vel_uncond: torch
     return out
 
 
+def guided_euler_step_pair(video: dict, audio: dict, sigma: float, sigma_next: float, dtype: Optional[torch.dtype] = None):
+    """guided_euler_step over two latents in ONE launch (ltx2_guided_euler_step_pair): `video` and `audio` each hold the single form's
+    operands by name -- x, vel_cond, vel_uncond, timesteps, cfg_scale and optionally mask, clean, out.  -> (video out, audio out), each
+    equal to guided_euler_step's bit for bit."""
+    args, outs, held = [], [], []
+    for seg in (video, audio):
+        x, vc, vu, mask, clean = seg["x"], seg["vel_cond"], seg["vel_uncond"], seg.get("mask"), seg.get("clean")
+        out = seg["out"] if seg.get("out") is not None else torch.empty_like(x)
+        assert vc is not None and vu is not None and (mask is None) == (clean is None)
+        n, c, ts = _step_operands(x, seg["timesteps"], (vc, vu, clean, out), mask)
+        args += [nv.ptr(x), nv.ptr(vc), nv.ptr(vu), nv.ptr(ts), 0 if ts.numel() == 1 else 1, nv.ptr(mask), nv.ptr(clean), float(seg["cfg_scale"]),
+                 nv.ptr(out), n, c]
+        outs.append(out)
+        held.append(ts)          # _step_operands may have made a contiguous fp32 copy: args holds its address only, so it must outlive the launch call
+    nv.check(nv.lib(dtype).ltx2_guided_euler_step_pair(*args, float(sigma), float(sigma_next), nv.stream()))
+    return outs[0], outs[1]
+
+
 def stg_euler_step(x: torch.Tensor, vel_cond: torch.Tensor, vel_uncond: Optional[torch.Tensor], vel_perturbed: torch.Tensor, timesteps: torch.Tensor,
                    cfg_scale: float, stg_scale: float, sigma: float, sigma_next: float, mask: Optional[torch.Tensor] = None,
                    clean: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
@@ -907,6 +925,59 @@ def retake_composite(decoded: torch.Tensor, source: torch.Tensor, p0: int, p1: i
         raise ValueError(f"retake_composite: ramp {ramp} (0 .. {nv.RETAKE_MAX_RAMP})")
     out = _out_like(out, "retake_composite", decoded.shape, torch.uint8, dev)
     nv.check(nv.lib().ltx2_retake_composite(nv.ptr(decoded), nv.ptr(source), T, H, W, p0, p1, ramp, nv.ptr(out), nv.stream()))
+    return out
+
+
+def retake_prepare_audio(encoded: torch.Tensor, noise: torch.Tensor, a0: int, a1: int, noise_scale: float = 1.0,
+                         out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None):
+    """retake_prepare for the clip's sound track (ltx2_retake_prepare_audio): the audio encoder's latent fp32 (1, C, T, M), noise fp32
+    (T, C*M), the latent-frame window 0 <= a0 <= a1 <= T -> (clean (T, C*M), mask (T,), latent (T, C*M)), fp32:
+    clean = AudioPatchifier.patchify(encoded), mask = 1 on the frames [a0, a1), latent = noise*sm + clean*(1 - sm) with sm = mask*noise_scale,
+    bit for bit what those torch statements give.  out: the three output tensors, exactly those shapes; nothing may overlap."""
+    if not isinstance(encoded, torch.Tensor):
+        raise ValueError("retake_prepare_audio: encoded must be a tensor")
+    if encoded.dim() != 4 or encoded.shape[0] != 1 or not encoded.is_cuda:
+        raise ValueError(f"retake_prepare_audio: encoded must be a GPU tensor (1, C, T, M), got {tuple(encoded.shape)} on {encoded.device}")
+    _, ch, T, M = encoded.shape
+    dev = encoded.device
+    _dense(encoded, "retake_prepare_audio", "encoded", torch.float32, encoded.shape, dev)
+    _dense(noise, "retake_prepare_audio", "noise", torch.float32, (T, ch * M), dev)
+    a0, a1 = int(a0), int(a1)
+    if not 0 <= a0 <= a1 <= T:
+        raise ValueError(f"retake_prepare_audio: latent-frame window [{a0}, {a1}) is not within 0 <= a0 <= a1 <= T = {T}")
+    if out is not None and len(out) != 3:
+        raise ValueError("retake_prepare_audio: out must be the three tensors (clean, mask, latent)")
+    oc, om, ol = out if out is not None else (None, None, None)
+    oc = _out_like(oc, "retake_prepare_audio (clean)", (T, ch * M), torch.float32, dev)
+    om = _out_like(om, "retake_prepare_audio (mask)", (T,), torch.float32, dev)
+    ol = _out_like(ol, "retake_prepare_audio (latent)", (T, ch * M), torch.float32, dev)
+    nv.check(nv.lib().ltx2_retake_prepare_audio(nv.ptr(encoded), nv.ptr(noise), ch, T, M, a0, a1, float(noise_scale), nv.ptr(oc), nv.ptr(om),
+                                                nv.ptr(ol), nv.stream()))
+    return oc, om, ol
+
+
+def retake_composite_audio(decoded: torch.Tensor, source: torch.Tensor, s0: int, s1: int, ramp: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp32 waveforms (channels, S) at one rate -> fp32 (channels, S): `decoded` on the samples [s0, s1), a linear fade into `source` over
+    `ramp` samples outside the window and the source's own bits beyond it (ltx2_retake_composite_audio; individually rounded fp32
+    arithmetic).  out may not alias an input."""
+    for name, t in (("decoded", decoded), ("source", source)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"retake_composite_audio: {name} must be a tensor")
+        if t.dtype != torch.float32 or t.dim() != 2 or not t.is_cuda:
+            raise ValueError(f"retake_composite_audio: {name} must be a float32 GPU tensor (channels, S), got {t.dtype} {tuple(t.shape)} on {t.device}")
+    dev = decoded.device
+    _dense(decoded, "retake_composite_audio", "decoded", torch.float32, decoded.shape, dev)
+    _dense(source, "retake_composite_audio", "source", torch.float32, decoded.shape, dev)
+    ch, S = decoded.shape
+    s0, s1, ramp = int(s0), int(s1), int(ramp)
+    if ch < 1 or S < 1:
+        raise ValueError(f"retake_composite_audio: empty waveform {tuple(decoded.shape)}")
+    if not 0 <= s0 <= s1 <= S:
+        raise ValueError(f"retake_composite_audio: sample window [{s0}, {s1}) is not within 0 <= s0 <= s1 <= S = {S}")
+    if not 0 <= ramp <= nv.RETAKE_AUDIO_MAX_RAMP:
+        raise ValueError(f"retake_composite_audio: ramp {ramp} (0 .. {nv.RETAKE_AUDIO_MAX_RAMP})")
+    out = _out_like(out, "retake_composite_audio", decoded.shape, torch.float32, dev)
+    nv.check(nv.lib().ltx2_retake_composite_audio(nv.ptr(decoded), nv.ptr(source), ch, S, s0, s1, ramp, nv.ptr(out), nv.stream()))
     return out
 
 

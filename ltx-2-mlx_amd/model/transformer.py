@@ -849,6 +849,39 @@ class LTXModel:
         """Replay the graph captured by capture_guided_av_graph."""
         self._replay("guided_av", "no guided AudioVideo graph captured")
 
+    # ------------------------------------------------------------------ classifier-free guidance on both latents (AudioVideo engine)
+    def guided_step_joint_av_(self, neg: "LTXModel", latent: torch.Tensor, audio_latent: torch.Tensor, video: Modality, audio: Modality, sigma: float,
+                              sigma_next: float, cfg_scale: float, audio_cfg_scale: float, denoise_mask: Optional[torch.Tensor] = None,
+                              clean_latent: Optional[torch.Tensor] = None, audio_denoise_mask: Optional[torch.Tensor] = None,
+                              audio_clean_latent: Optional[torch.Tensor] = None) -> None:
+        """In-place on BOTH latents, (N, C) and (Na, Ca) fp32: one classifier-free-guided Euler step of the AudioVideo model (a retake with
+        sound) by ONE C call (ltx2_dit_guided_step_joint_av): both modalities through this context and through `neg`, then x0 x 2 +
+        CFGGuider.guide + post_process_latent + Euler over both latents in one launch, the video under cfg_scale and the audio under
+        audio_cfg_scale.  Both contexts are prepared by the caller (neg with the negative contexts)."""
+        pos, ng = self._contexts(neg, av=True)
+        ts, n_ts, sg, ats, n_ats = pos._step_inputs(latent, video, sigma, audio_latent, audio)
+        nv.check(pos._L.ltx2_dit_guided_step_joint_av(pos._h, ng._h, nv.ptr(latent), nv.ptr(audio_latent), nv.ptr(ts), n_ts, nv.ptr(ats), n_ats,
+                                                      nv.ptr(sg), nv.ptr(denoise_mask), nv.ptr(clean_latent), nv.ptr(audio_denoise_mask),
+                                                      nv.ptr(audio_clean_latent), float(cfg_scale), float(audio_cfg_scale), float(sigma),
+                                                      float(sigma_next), nv.stream()))
+
+    def capture_guided_joint_graph(self, neg: "LTXModel", latent: torch.Tensor, audio_latent: torch.Tensor, sigmas: Sequence[float], cfg_scale: float,
+                                   audio_cfg_scale: float, denoise_mask: Optional[torch.Tensor] = None, clean_latent: Optional[torch.Tensor] = None,
+                                   audio_denoise_mask: Optional[torch.Tensor] = None, audio_clean_latent: Optional[torch.Tensor] = None) -> None:
+        """hipGraph-capture len(sigmas)-1 of those steps over both latents, updated in place on replay
+        (ltx2_dit_graph_capture_guided_joint_av).  A modality with a denoise mask (and its clean latent) gets its per-token timesteps
+        mask * sigma_i formed on the device.  Both contexts are prepared first (per_token=True when a mask is given); the graph belongs to
+        this context and replay_guided_joint_graph() replays it.  The tensors must stay alive while it is replayed."""
+        pos, ng = self._contexts(neg, av=True)
+        assert audio_latent.dtype == torch.float32 and audio_latent.is_contiguous()
+        self._capture("guided_joint", pos, ng, "ltx2_dit_graph_capture_guided_joint_av", (latent, audio_latent), sigmas,
+                      [(denoise_mask, clean_latent), (audio_denoise_mask, audio_clean_latent)], audio_denoise_mask, audio_clean_latent,
+                      float(cfg_scale), float(audio_cfg_scale))
+
+    def replay_guided_joint_graph(self) -> None:
+        """Replay the graph captured by capture_guided_joint_graph."""
+        self._replay("guided_joint", "no joint guided graph captured")
+
     # ------------------------------------------------------------------ guiders whose scalars are sums over the latent (video-only engine)
     def projected_step_(self, neg: "LTXModel", latent: torch.Tensor, video: Modality, sigma: float, sigma_next: float, mode: int, scale: float,
                         eta: float = 1.0, norm_threshold: float = 0.0, momentum: float = 0.0, first: bool = True,

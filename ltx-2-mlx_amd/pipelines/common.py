@@ -450,6 +450,45 @@ def frozen_audio_guided_loop(transformer, video_state: LatentState, audio_state:
     return _with_latent(video_state, lat), audio_state
 
 
+def joint_guided_denoise_loop(transformer, video_state: LatentState, audio_state: LatentState, sigmas, video_context: torch.Tensor,
+                              audio_context: torch.Tensor, negative_video_context: Optional[torch.Tensor],
+                              negative_audio_context: Optional[torch.Tensor], cfg_scale: float, audio_cfg_scale: float, stepper, callback=None,
+                              use_hip_graph: bool = True) -> Tuple[LatentState, LatentState]:
+    """Classifier-free guidance over BOTH modalities of an AudioVideo model without leaving the device (the reference's RetakePipeline._denoise_loop,
+    pipelines/retake.py:234-291, run with an audio state): per step both modalities through the positive and through the negative contexts,
+    then CFGGuider.guide, post_process_latent and the Euler step on both latents, the video under cfg_scale and the audio under
+    audio_cfg_scale.  Every step is ONE C call (LTXModel.guided_step_joint_av_: the evaluations, then one kernel over both latents) and with no
+    callback and fewer than 64 steps the whole loop is one captured graph.  Each modality takes the uniform or the per-token form by its
+    own mask.  The guidance is CFGGuider's a + (s - 1)*(a - b), as guided_denoise_loop forms it; the reference's line writes the same
+    quantity as b + s*(a - b).  When neither scale exceeds 1, or a negative context is missing, there is no negative pass: the loop is
+    joint_denoise_loop's, captured for the masked joint case.  `transformer` is an X0Model over an AudioVideo model.  Returns (video_state,
+    audio_state)."""
+    model = transformer.velocity_model
+    if not model.is_av or audio_state is None:
+        raise ValueError("joint_guided_denoise_loop requires an audio-video (AV) model and an audio state")
+    if audio_context is None:
+        raise ValueError("AudioVideo model: audio_encoding (the audio text context) is required")
+    if not (cfg_scale > 1.0 or audio_cfg_scale > 1.0) or negative_video_context is None or negative_audio_context is None:
+        return joint_denoise_loop(transformer, True, video_state, audio_state, sigmas, video_context, audio_context, stepper, callback, use_hip_graph)
+    sig = [float(s) for s in sigmas]
+    n = len(sig) - 1
+    model, uniform, lat, mask, clean = _video_loop_inputs(model, video_state, video_only=False)
+    _, a_uniform, alat, amask, aclean = _video_loop_inputs(model, audio_state, video_only=False)
+    neg = _prepare_contexts(model, True, not (uniform and a_uniform), video_state.positions, video_context, negative_video_context,
+                            audio_state.positions, audio_context, negative_audio_context)
+    cond = dict(denoise_mask=mask, clean_latent=clean, audio_denoise_mask=amask, audio_clean_latent=aclean)
+
+    def step(i):
+        st, ast = video_state.replace(latent=lat[None]), audio_state.replace(latent=alat[None])
+        model.guided_step_joint_av_(neg, lat, alat, modality_from_state(st, video_context, sig[i], uniform=uniform),
+                                    audio_modality_from_state(ast, audio_context, sig[i], uniform=a_uniform), sig[i], sig[i + 1], cfg_scale,
+                                    audio_cfg_scale, **cond)
+
+    _run_steps(n, callback, use_hip_graph, lambda: model.capture_guided_joint_graph(neg, lat, alat, sig, cfg_scale, audio_cfg_scale, **cond),
+               model.replay_guided_joint_graph, step)
+    return _with_latent(video_state, lat), _with_latent(audio_state, alat)
+
+
 def projected_guider_args(guider) -> Optional[dict]:
     """The (mode, scale, eta, norm_threshold, momentum) of LTXModel.projected_step_ for a guider whose scalars are sums over the latent; None
     for every other object."""

@@ -10,7 +10,11 @@ Both are one captured graph when there is no callback.  The source stays on the 
 SimpleVideoEncoder.encode_patches -> kernels.retake_prepare (patchify, mask and noise blend in one pass); with composite_source the
 frames outside the window are put back from the source by kernels.retake_composite.  The reference reads the file with ffmpeg and resizes
 nothing; load_control_frames reads arrays, image directories and (through an ffmpeg binary) video files, at the source's own size.
-Audio retake (the joint loop with an audio mask) is not built: the reference's audio state is always None too.
+Retake with sound (MI355X addition; the reference's audio state is always None, its _denoise_loop :234-291 is written for one): given the clip's
+sound track (audio_path= / audio_latent=) on an AudioVideo model, the track is encoded by the audio VAE encoder, kernels.retake_prepare_audio
+builds its state with the mask on the audio tokens whose seconds meet the window, and BOTH latents run through the joint loops
+(joint_denoise_loop distilled, joint_guided_denoise_loop otherwise: one C call per step or one captured graph); decoded, the waveform outside the
+window can be put back from the source by kernels.retake_composite_audio.  Without an audio argument nothing here changes.
 """
 from __future__ import annotations
 
@@ -26,19 +30,23 @@ import torch
 
 from .. import kernels as K
 from ..components import DISTILLED_SIGMA_VALUES, CFGGuider, EulerDiffusionStep, LTX2Scheduler, VideoLatentPatchifier
-from ..conditioning.tools import VideoLatentTools
+from ..components.patchifiers import AudioPatchifier
+from ..conditioning.tools import AudioLatentTools, VideoLatentTools
 from ..model.transformer import LTXModel, X0Model
 from ..model.video_vae import SimpleVideoDecoder, TilingConfig
-from ..types import LatentState, VideoLatentShape, VideoPixelShape
-from .common import as_x0model, decode_video, final_latent, guided_denoise_loop, joint_denoise_loop, projected_denoise_loop, stage_callback
+from ..types import AudioLatentShape, LatentState, VideoLatentShape, VideoPixelShape
+from .common import (as_x0model, decode_video, final_latent, guided_denoise_loop, joint_denoise_loop, joint_guided_denoise_loop,
+                     projected_denoise_loop, stage_callback)
 from .ic_lora import IMAGE_SUFFIXES, load_control_frames, load_control_signal_tensor
 
 
 @dataclass
 class RetakeConfig:
-    """Configuration of the retake pipeline (reference :47-64).  regenerate_audio is kept for the signature and has no effect, as in the
-    reference, whose audio state is always None.  regenerate_video=False leaves the mask all ones, as create_initial_state makes it: the
-    whole clip is regenerated."""
+    """Configuration of the retake pipeline (reference :47-64).  Without a sound track (no audio_path= / audio_latent=): regenerate_audio is
+    kept for the signature and has no effect, as in the reference, whose audio state is always None, and regenerate_video=False leaves the
+    mask all ones, as create_initial_state makes it: the whole clip is regenerated.
+    With a sound track the two flags mean what they say, which differs on purpose from that quirk: regenerate_video=False FREEZES the whole
+    picture (mask 0: the window is re-dubbed), regenerate_audio=False freezes the whole track, both False is a ValueError."""
     start_time: float               # seconds, inclusive
     end_time: float                 # seconds, exclusive
     regenerate_video: bool = True
@@ -54,12 +62,17 @@ class RetakeConfig:
     use_hip_graph: bool = True      # replay the loop from one captured graph (no callback; the guided loop: fewer than 64 steps)
     composite_source: bool = False  # put the source's own frames back outside the window (kernels.retake_composite)
     composite_ramp: int = 4         # frames of linear fade on each side, OUTSIDE the window
+    audio_cfg_scale: Optional[float] = None     # guidance scale of the audio latent; None: cfg_scale, the reference's single scale
+    composite_source_audio: bool = False        # put the source track's own samples back outside the window (kernels.retake_composite_audio)
+    audio_composite_ramp_ms: float = 20.0       # milliseconds of linear fade on each side, OUTSIDE the window
 
     def __post_init__(self):
         if self.start_time >= self.end_time:
             raise ValueError(f"start_time ({self.start_time}) must be < end_time ({self.end_time})")
         if self.composite_ramp < 0:
             raise ValueError(f"composite_ramp ({self.composite_ramp}) must be >= 0")
+        if self.audio_composite_ramp_ms < 0:
+            raise ValueError(f"audio_composite_ramp_ms ({self.audio_composite_ramp_ms}) must be >= 0")
 
 
 def _is_array_or_dir(path: str) -> bool:
@@ -157,19 +170,31 @@ def end_of_clip(num_frames: int, fps: float) -> float:
     return (num_frames + 0.5) / fps
 
 
+def audio_token_window(t0: float, t1: float, tokens: int, sample_rate: int = 16000, hop_length: int = 160, downsample: int = 4) -> Tuple[int, int]:
+    """The contiguous audio tokens [a0, a1) whose [start, end) seconds (AudioPatchifier.get_patch_grid_bounds: causal, token k spans
+    max(4k - 3, 0) .. 4k + 1 mel frames of hop_length / sample_rate seconds each) intersect [t0, t1), on the host in double precision.
+    A token that only touches the window with its end (end == t0) or its start (start == t1) is outside.  (0, 0) when none is touched."""
+    sec = lambda k: max(downsample * k + 1 - downsample, 0) * hop_length / sample_rate      # noqa: E731
+    hit = [k for k in range(tokens) if sec(k) < t1 and sec(k + 1) > t0]
+    return (hit[0], hit[-1] + 1) if hit else (0, 0)
+
+
 def _snap(num_frames: int) -> int:
     return ((num_frames - 1) // 8) * 8 + 1
 
 
 class RetakePipeline:
     def __init__(self, transformer: Union[LTXModel, X0Model], video_encoder, video_decoder: Optional[SimpleVideoDecoder], audio_decoder=None,
-                 vocoder=None):
-        """audio_decoder / vocoder are accepted for the reference's signature and unused (no audio retake)."""
+                 vocoder=None, audio_encoder=None, audio_processor=None):
+        """audio_decoder / vocoder turn the retaken audio latent into a waveform; audio_encoder (+ an AudioProcessor, built on demand;
+        MI355X additions, as in create_a2vid_pipeline) encodes audio_path.  All four are unused without a sound track."""
         self.transformer, self.is_av_model = as_x0model(transformer)
         self.video_encoder = video_encoder
         self.video_decoder = video_decoder
         self.audio_decoder = audio_decoder
         self.vocoder = vocoder
+        self.audio_encoder = audio_encoder
+        self.audio_processor = audio_processor
         self.patchifier = VideoLatentPatchifier(patch_size=1)
         self.stepper = EulerDiffusionStep()
         # of the last call: the source on the device (uint8), its frame rate, the latent-frame and pixel-frame windows, the DiT tokens
@@ -178,6 +203,10 @@ class RetakePipeline:
         self.frame_window: Optional[Tuple[int, int]] = None
         self.pixel_window: Optional[Tuple[int, int]] = None
         self.token_count: int = 0
+        # of the last call with a sound track: the audio tokens [a0, a1) regenerated, the same span in samples of the decoded waveform, the latent
+        self.audio_window: Optional[Tuple[int, int]] = None
+        self.audio_sample_window: Optional[Tuple[int, int]] = None
+        self.audio_latent: Optional[torch.Tensor] = None
 
     def _load_source(self, video_path: Optional[str], frames, config: RetakeConfig) -> Tuple[torch.Tensor, float]:
         """-> (uint8 (8k+1, H, W, 3) on the encoder's device, fps).  The frame count is snapped down to 8k + 1 (reference :327); the size
@@ -201,13 +230,64 @@ class RetakePipeline:
             x = torch.from_numpy(load_control_frames(video_path, h, w, n))
         return x[:n].to(dev).contiguous(), fps
 
+    def _audio_state(self, audio_path, audio_latent, n_pix: int, fps: float, seconds: Tuple[float, float], config: RetakeConfig,
+                     initial_audio_noise, gen, dev) -> Tuple[AudioLatentTools, LatentState]:
+        """The sound track's state: the track encoded for the clip's snapped length (or audio_latent as given), the mask on the tokens whose
+        seconds meet `seconds`, noise at scale 1 on those (kernels.retake_prepare_audio), the positions of AudioLatentTools."""
+        shape = AudioLatentShape.from_video_pixel_shape(VideoPixelShape(batch=1, frames=n_pix, height=32, width=32, fps=fps))
+        if audio_latent is None:
+            if self.audio_encoder is None:
+                raise ValueError("RetakePipeline needs an audio_encoder to encode audio_path (or pass audio_latent)")
+            from .a2vid_two_stage import encode_audio_file
+            print(f"  Loading audio: {audio_path}")
+            audio_latent = encode_audio_file(audio_path, n_pix, fps, self.audio_encoder, self.audio_processor)[0]
+        if tuple(audio_latent.shape) != shape.to_tuple():
+            raise ValueError(f"audio_latent is {tuple(audio_latent.shape)}, the clip ({n_pix} frames at {fps:g} fps) needs {shape.to_tuple()}")
+        encoded = audio_latent.to(dev, torch.float32).contiguous()
+        patchifier = AudioPatchifier(patch_size=1)
+        a0, a1 = (0, 0)
+        if config.regenerate_audio:
+            a0, a1 = audio_token_window(seconds[0], seconds[1], shape.frames, patchifier.sample_rate, patchifier.hop_length,
+                                        patchifier.audio_latent_downsample_factor)
+            if a0 >= a1:
+                raise ValueError(f"the retake window {seconds[0]:.3f}s - {seconds[1]:.3f}s touches no audio token of the source track: it has "
+                                 f"{shape.frames} latent frames, {n_pix / fps:.3f} s")
+        width = shape.channels * shape.mel_bins
+        if initial_audio_noise is None:
+            initial_audio_noise = torch.randn((1, shape.frames, width), generator=gen(), device=dev, dtype=torch.float32)
+        if tuple(initial_audio_noise.shape) != (1, shape.frames, width):
+            raise ValueError(f"initial_audio_noise must be (1, {shape.frames}, {width}), got {tuple(initial_audio_noise.shape)}")
+        clean, mask, latent = K.retake_prepare_audio(encoded, initial_audio_noise[0].to(dev, torch.float32).contiguous(), a0, a1, noise_scale=1.0)
+        tools = AudioLatentTools(patchifier=patchifier, target_shape=shape)
+        positions = tools.create_initial_state(dtype=torch.float32, device=dev).positions
+        self.audio_window = (a0, a1)
+        return tools, LatentState(latent=latent[None].to(config.dtype), denoise_mask=mask[None, :, None], positions=positions,
+                                  clean_latent=clean[None].to(config.dtype))
+
     def denoise_latent(self, video_path: Optional[str], text_encoding: torch.Tensor, config: RetakeConfig,
                        negative_text_encoding: Optional[torch.Tensor] = None, callback: Optional[Callable[[str, int, int], None]] = None, *,
-                       frames=None, initial_noise: Optional[torch.Tensor] = None, guider=None) -> torch.Tensor:
+                       frames=None, initial_noise: Optional[torch.Tensor] = None, guider=None, audio_path: Optional[str] = None,
+                       audio_latent: Optional[torch.Tensor] = None, initial_audio_noise: Optional[torch.Tensor] = None,
+                       audio_encoding: Optional[torch.Tensor] = None, negative_audio_encoding: Optional[torch.Tensor] = None):
         """Up to the final latent (1, 128, F, H/32, W/32).  frames (keyword-only, MI355X addition): already loaded uint8 frames
         (F, H, W, 3) instead of a path.  initial_noise: a supplied N(0, 1) tensor (1, F*H*W/1024, 128) of the patchified shape, so results
         can be compared with a restatement.  guider (keyword-only): replaces CFGGuider(config.cfg_scale) in the guided (not distilled) mode
-        and runs through projected_denoise_loop."""
+        and runs through projected_denoise_loop.
+        audio_path / audio_latent (keyword-only): the clip's sound track, a file or its encoded latent (1, 8, T_a, 16); with one of them, on
+        an AudioVideo model with audio_encoding, both modalities are retaken and the result is (video latent, audio latent (1, 8, T_a, 16)).
+        The audio window is the tokens whose seconds meet those of the widened pixel window (p0 / fps, p1 / fps) when the video is
+        regenerated, so picture and sound change over the same seconds, else (start_time, end_time).  Here regenerate_video=False freezes
+        the whole picture and regenerate_audio=False the whole track (RetakeConfig).  initial_audio_noise: (1, T_a, 128)."""
+        with_audio = audio_path is not None or audio_latent is not None
+        if with_audio:
+            if not self.is_av_model:
+                raise ValueError("a retake with a sound track requires an audio-video (AV) model")
+            if audio_encoding is None:
+                raise ValueError("AudioVideo model: audio_encoding (the audio text context) is required")
+            if guider is not None:
+                raise NotImplementedError("a guider override on the joint audio+video retake loop is not built (plain classifier-free guidance only)")
+            if not (config.regenerate_video or config.regenerate_audio):
+                raise ValueError("regenerate_video and regenerate_audio are both False: nothing to retake")
         if self.video_encoder is None:
             raise ValueError("RetakePipeline needs a video_encoder")
         src, fps = self._load_source(video_path, frames, config)
@@ -221,13 +301,21 @@ class RetakePipeline:
                 raise ValueError(f"the retake window {config.start_time}s - {config.end_time}s touches no frame of the source: it has "
                                  f"{n_pix} frames at {fps:g} fps, {n_pix / fps:.3f} s")
             p0, p1 = region.pixel_window(shape.frames, n_pix)
+        elif with_audio:
+            (f0, f1), (p0, p1) = (0, 0), (0, 0)                                            # the picture is frozen: the window is re-dubbed
         else:
             (f0, f1), (p0, p1) = (0, shape.frames), (0, n_pix)
         dev = encoded.device
         tokens = shape.frames * shape.height * shape.width
+        seeded = []
+
+        def gen():                                                                         # the one generator of a call: video noise first, then audio
+            if not seeded:
+                seeded.append(torch.Generator(device=dev).manual_seed(config.seed))
+            return seeded[0]
+
         if initial_noise is None:
-            initial_noise = torch.randn((1, tokens, 128), generator=torch.Generator(device=dev).manual_seed(config.seed), device=dev,
-                                        dtype=torch.float32)
+            initial_noise = torch.randn((1, tokens, 128), generator=gen(), device=dev, dtype=torch.float32)
         if tuple(initial_noise.shape) != (1, tokens, 128):
             raise ValueError(f"initial_noise must be (1, {tokens}, 128), got {tuple(initial_noise.shape)}")
         clean, mask, latent = K.retake_prepare(encoded, initial_noise[0].to(dev, torch.float32).contiguous(), f0, f1, noise_scale=1.0)
@@ -239,6 +327,22 @@ class RetakePipeline:
 
         ctx = text_encoding.to(dev)
         cb = stage_callback(callback, "retake")
+        if with_audio:
+            seconds = (p0 / fps, p1 / fps) if config.regenerate_video else (float(config.start_time), float(config.end_time))
+            atools, astate = self._audio_state(audio_path, audio_latent, n_pix, fps, seconds, config, initial_audio_noise, gen, dev)
+            actx = audio_encoding.to(dev)
+            if config.distilled:
+                state, astate = joint_denoise_loop(self.transformer, True, state, astate, [float(s) for s in DISTILLED_SIGMA_VALUES], ctx, actx,
+                                                   self.stepper, cb, config.use_hip_graph)
+            else:
+                sigmas = LTX2Scheduler().execute(steps=config.num_inference_steps)
+                # no negative prompt: zeros of the context's shape, for either modality (reference :387-388)
+                nctx = torch.zeros_like(ctx) if negative_text_encoding is None else negative_text_encoding.to(dev)
+                nactx = torch.zeros_like(actx) if negative_audio_encoding is None else negative_audio_encoding.to(dev)
+                audio_cfg = config.cfg_scale if config.audio_cfg_scale is None else config.audio_cfg_scale
+                state, astate = joint_guided_denoise_loop(self.transformer, state, astate, sigmas, ctx, actx, nctx, nactx, config.cfg_scale, audio_cfg,
+                                                          self.stepper, cb, config.use_hip_graph)
+            return final_latent(tools, state), final_latent(atools, astate)
         if config.distilled:
             state = joint_denoise_loop(self.transformer, self.is_av_model, state, None, [float(s) for s in DISTILLED_SIGMA_VALUES], ctx, None,
                                        self.stepper, cb, config.use_hip_graph)[0]
@@ -251,24 +355,58 @@ class RetakePipeline:
             state = loop(self.transformer, state, sigmas, ctx, nctx, guider, self.stepper, cb, config.use_hip_graph)
         return final_latent(tools, state)
 
+    def _decode_audio(self, audio_latent: torch.Tensor, audio_path: Optional[str], config: RetakeConfig) -> torch.Tensor:
+        """The retaken audio latent -> waveform (2, S) fp32 at the vocoder's output_sample_rate; with composite_source_audio the source track,
+        loaded at that rate and cut or right-padded with silence to S, is put back outside the audio window's samples."""
+        from ..model.audio_vae import AudioProcessor, load_audio_file
+        waveform = self.vocoder(self.audio_decoder(audio_latent))[0].contiguous()
+        rate, samples = int(self.vocoder.output_sample_rate), int(waveform.shape[1])
+        a0, a1 = self.audio_window
+        p = AudioPatchifier(patch_size=1)
+        sec = lambda k: max(p.audio_latent_downsample_factor * k + 1 - p.audio_latent_downsample_factor, 0) * p.hop_length / p.sample_rate      # noqa: E731
+        self.audio_sample_window = (min(samples, int(round(sec(a0) * rate))), min(samples, int(round(sec(a1) * rate)))) if a0 < a1 else (0, 0)
+        if not config.composite_source_audio:
+            return waveform
+        if audio_path is None:
+            raise ValueError("composite_source_audio needs the source track itself: pass audio_path (audio_latent alone carries no waveform)")
+        source, _ = load_audio_file(audio_path, rate)
+        source = AudioProcessor.fit_waveform(np.asarray(source, dtype=np.float32)[:2], samples)
+        if source.shape[0] < waveform.shape[0]:                                            # mono: the one channel on both
+            source = np.repeat(source[:1], waveform.shape[0], axis=0)
+        source = torch.from_numpy(np.ascontiguousarray(source)).to(waveform.device)
+        ramp = int(round(config.audio_composite_ramp_ms * rate / 1000.0))
+        return K.retake_composite_audio(waveform, source, *self.audio_sample_window, ramp)
+
     def __call__(self, video_path: Optional[str], text_encoding: torch.Tensor, text_mask: Optional[torch.Tensor], config: RetakeConfig,
                  negative_text_encoding: Optional[torch.Tensor] = None, audio_encoding: Optional[torch.Tensor] = None,
                  negative_audio_encoding: Optional[torch.Tensor] = None, callback: Optional[Callable[[str, int, int], None]] = None, *,
-                 frames=None, initial_noise: Optional[torch.Tensor] = None, guider=None) -> torch.Tensor:
+                 frames=None, initial_noise: Optional[torch.Tensor] = None, guider=None, audio_path: Optional[str] = None,
+                 audio_latent: Optional[torch.Tensor] = None, initial_audio_noise: Optional[torch.Tensor] = None):
         """-> uint8 frames (T, H, W, 3) (the final latent when no decoder is set).  text_mask is accepted and unused, as every loop here
-        passes context_mask=None (reference pipelines/common.py:223-232); so are the audio encodings (no audio retake).  guider
-        (keyword-only): the guider of the guided mode instead of CFGGuider(config.cfg_scale), e.g. LtxAPGGuider."""
-        latent = self.denoise_latent(video_path, text_encoding, config, negative_text_encoding, callback, frames=frames,
-                                     initial_noise=initial_noise, guider=guider)
+        passes context_mask=None (reference pipelines/common.py:223-232); so are the audio encodings without a sound track.  guider
+        (keyword-only): the guider of the guided mode instead of CFGGuider(config.cfg_scale), e.g. LtxAPGGuider.
+        audio_path / audio_latent (keyword-only): the clip's sound track (denoise_latent) -> (frames, audio): the audio is the waveform
+        (2, S) fp32 at the vocoder's output_sample_rate when audio_decoder and vocoder are set, else the audio latent (1, 8, T_a, 16).
+        audio_window, audio_sample_window and audio_latent of the call are kept as attributes."""
+        with_audio = audio_path is not None or audio_latent is not None
+        self.audio_window = self.audio_sample_window = self.audio_latent = None
+        out = self.denoise_latent(video_path, text_encoding, config, negative_text_encoding, callback, frames=frames, initial_noise=initial_noise,
+                                  guider=guider, audio_path=audio_path, audio_latent=audio_latent, initial_audio_noise=initial_audio_noise,
+                                  audio_encoding=audio_encoding, negative_audio_encoding=negative_audio_encoding)
+        latent, audio = out if with_audio else (out, None)
+        self.audio_latent = audio
+        if with_audio and self.audio_decoder is not None and self.vocoder is not None:
+            audio = self._decode_audio(audio, audio_path, config)
         if self.video_decoder is None:
-            return latent
+            return (latent, audio) if with_audio else latent
         video = decode_video(latent, self.video_decoder, config.tiling_config)             # no automatic tiling here
         if video.dtype != torch.uint8:                                                     # decode_tiled: float (1, 3, T, H, W) in [-1, 1]
             video = K.video_to_uint8(video[0] if video.dim() == 5 else video)
         if config.composite_source:
             video = K.retake_composite(video.contiguous(), self.source_frames, *self.pixel_window, config.composite_ramp)
-        return video
+        return (video, audio) if with_audio else video
 
 
-def create_retake_pipeline(transformer, video_encoder, video_decoder, audio_decoder=None, vocoder=None) -> RetakePipeline:
-    return RetakePipeline(transformer, video_encoder, video_decoder, audio_decoder, vocoder)
+def create_retake_pipeline(transformer, video_encoder, video_decoder, audio_decoder=None, vocoder=None, audio_encoder=None,
+                           audio_processor=None) -> RetakePipeline:
+    return RetakePipeline(transformer, video_encoder, video_decoder, audio_decoder, vocoder, audio_encoder, audio_processor)

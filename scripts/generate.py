@@ -71,20 +71,21 @@ def audio_filters(speed: float = 1.0):
     return out
 
 
-def ffmpeg_av_command(width: int, height: int, wav_path: str, sample_rate: int, output_path: str, fps: int = 24, speed: float = 1.0):
+def ffmpeg_av_command(width: int, height: int, wav_path: str, sample_rate: int, output_path: str, fps: int = 24, speed: float = 1.0, input_fps=None):
     """The reference's audio mux settings (:2323-2355: libx264 crf 18, aac 320k at the vocoder's rate, -shortest); the frames arrive as
-    raw RGB on stdin."""
-    cmd = ["ffmpeg", "-y", "-f", "rawvideo", "-pix_fmt", "rgb24", "-s", f"{width}x{height}", "-framerate", str(NATIVE_FPS), "-i", "-",
+    raw RGB on stdin.  input_fps: the rate the frames are played at (a retake source's own; None: the native 24 fps)."""
+    input_fps = NATIVE_FPS if input_fps is None else input_fps
+    cmd = ["ffmpeg", "-y", "-f", "rawvideo", "-pix_fmt", "rgb24", "-s", f"{width}x{height}", "-framerate", f"{input_fps:g}", "-i", "-",
            "-i", wav_path]
-    if video_filters(fps, speed):
-        cmd += ["-vf", ",".join(video_filters(fps, speed))]
+    if video_filters(fps, speed, input_fps):
+        cmd += ["-vf", ",".join(video_filters(fps, speed, input_fps))]
     if audio_filters(speed):
         cmd += ["-af", ",".join(audio_filters(speed))]
     return cmd + ["-c:v", "libx264", "-c:a", "aac", "-b:a", "320k", "-ar", str(sample_rate), "-pix_fmt", "yuv420p", "-crf", "18", "-shortest",
                   "-loglevel", "error", output_path]
 
 
-def save_video_with_audio(frames, audio_waveform, output_path: str, audio_sample_rate: int, fps: int = 24, speed: float = 1.0):
+def save_video_with_audio(frames, audio_waveform, output_path: str, audio_sample_rate: int, fps: int = 24, speed: float = 1.0, input_fps=None):
     """Writes `<output stem>.wav` (the reference's sidecar) and muxes it into output_path with ffmpeg; without an ffmpeg binary the
     frames go to PNGs as in save_video and the .wav stays beside them.  Returns (video path or frames dir, wav path)."""
     import shutil
@@ -93,10 +94,10 @@ def save_video_with_audio(frames, audio_waveform, output_path: str, audio_sample
     n = (audio_waveform.shape[-1])
     print(f"    Sidecar WAV: {wav_path} ({n} samples, {n / audio_sample_rate:.2f} s at {audio_sample_rate} Hz)")
     if shutil.which("ffmpeg") is None:
-        return save_video(frames, output_path, fps=fps, speed=speed), wav_path
+        return save_video(frames, output_path, fps=fps, speed=speed, **({} if input_fps is None else dict(input_fps=input_fps))), wav_path
     frames = np.ascontiguousarray(np.asarray(frames))
     t, h, w, _ = frames.shape
-    result = subprocess.run(ffmpeg_av_command(w, h, wav_path, audio_sample_rate, output_path, fps, speed), input=frames.tobytes(), capture_output=True)
+    result = subprocess.run(ffmpeg_av_command(w, h, wav_path, audio_sample_rate, output_path, fps, speed, input_fps), input=frames.tobytes(), capture_output=True)
     if result.returncode != 0:
         raise RuntimeError(f"FFmpeg failed: {result.stderr.decode(errors='replace')}")
     return output_path, wav_path
@@ -606,6 +607,10 @@ _ROUTE_EXCLUDES = {
                 "upscale_temporal", "fp8_resident", "pipeline_type"),
                "with retake_video: RetakePipeline is video-only, conditions on its source clip alone and runs one stage at the source's own "
                "size on dequantised weights"),
+    "retake_av": (("audio_path", "keyframes", "control_video", "image_path", "two_stage_distilled", "upscale_spatial", "upscale_temporal", "fp8_resident",
+                   "pipeline_type"),
+                  "with retake_video and retake_audio: RetakePipeline conditions on its source clip and sound track alone and runs one stage at the "
+                  "source's own size on dequantised weights"),
     "keyframe": (("generate_audio", "audio_path", "two_stage_distilled", "upscale_temporal", "image_path"),
                  "with keyframes: the keyframe interpolation pipeline is video-only, conditions on its keyframes alone and ends with its own "
                  "x2 spatial stage"),
@@ -629,7 +634,8 @@ _ROUTE_EXCLUDES = {
 # OneStagePipeline's guider_override, keyframe stage 1, retake's guided mode).  stg_scale: OneStagePipeline alone (the AudioVideo route)
 _ROUTE_OWNS = {"keyframe": ("keyframes", "apg_scale"), "hq": ("distilled_lora", "keyframes"),
                "ic_lora": ("control_video", "save_control", "keyframes", "ic_lora_weights"), "retake": ("apg_scale",), "av": ("apg_scale", "stg_scale"), "a2vid": ("distilled_lora",),
-               "hq_av": ("distilled_lora",), "two_stage_cfg": ("distilled_lora",)}
+               "hq_av": ("distilled_lora",), "two_stage_cfg": ("distilled_lora",),
+               "retake_av": ()}          # no guider override on the joint audio+video loop: apg_scale keeps its out-of-path refusal
 
 
 def _owning_route(r):
@@ -774,6 +780,17 @@ def _resolve_two_stage_cfg(r):
     r.generate_audio = True          # the AudioVideo transformer and both text encodings, as generate_audio asks for them
 
 
+def _resolve_retake_av(r):
+    """The silent route's checks on the clip and the window, then the sound track: it must exist; the AudioVideo transformer and both text encodings, as generate_audio asks for them."""
+    _resolve_retake(r)
+    r.retake_audio = str(r.retake_audio)
+    if not os.path.exists(r.retake_audio):
+        raise FileNotFoundError(f"retake audio track not found: {r.retake_audio}")
+    if r.retake_audio_cfg is not None and not r.retake_audio_cfg >= 0.0:
+        raise ValueError(f"retake_audio_cfg={r.retake_audio_cfg} must be >= 0")
+    r.generate_audio = True
+
+
 _RESOLVE_ROUTE = {"two_stage_cfg": _resolve_two_stage_cfg, "keyframe": _resolve_keyframe, "hq": _resolve_hq, "ic_lora": _resolve_ic_lora, "a2vid": _resolve_a2vid, "hq_av": _resolve_hq_av}
 
 
@@ -784,12 +801,16 @@ def _resolve_request(kw: dict):
     negative_audio_encoding of the embedding file.  Loads no model and touches no GPU; every refusal is raised here, in a fixed order.  Returns None (after saying so) when Gemma is asked for and
     its weights are missing."""
     r = SimpleNamespace(**kw, retake_fps=None, retake_to_end=False, retake_window=None, parsed_keyframes=[], hq_lora=None, ic_loras=[], a2vid_lora=None, two_stage_lora=None)
+    if r.retake_audio is not None and r.retake_video is None:
+        raise ValueError("retake_audio (--retake-audio) is the sound track of retake_video (--retake): pass the clip as well")
     if r.two_stage_cfg:
         r.route = "two_stage_cfg"
     elif r.ti2vid_hq_audio:
         r.route = "hq_av"
     elif r.a2vid_two_stage:
         r.route = "a2vid"
+    elif r.retake_video is not None and r.retake_audio is not None:
+        r.route = "retake_av"
     elif r.retake_video is not None:
         r.route = "retake"
     elif r.pipeline_type == "keyframe-interpolation" and bool(r.keyframes):
@@ -803,6 +824,9 @@ def _resolve_request(kw: dict):
     if r.route == "retake":                                              # its refusals win over every other one
         _refuse_combinations(r)
         _resolve_retake(r)
+    elif r.route == "retake_av":
+        _refuse_combinations(r)
+        _resolve_retake_av(r)
     # Gemma encodes the prompt (and the negative prompt) when its weights are there and no pre-computed encoding is given
     r.gemma_encodes = bool(r.use_gemma and not (r.embedding_path or r.text_features_path) and r.gemma_path and os.path.exists(r.gemma_path))
     owns = _ROUTE_OWNS.get(_owning_route(r) if (r.apg_scale != 1.0 or r.stg_scale != 0.0) else r.route, ())
@@ -1012,6 +1036,7 @@ _REQUIRES = {
     "hq": ("TI2Vid HQ pipeline requires a loaded model", "TI2Vid HQ pipeline requires VAE decoder", None, False),
     "ic_lora": ("IC-LoRA pipeline requires a loaded model", "IC-LoRA pipeline requires VAE decoder", None, False),
     "retake": ("Retake pipeline requires a loaded model", "Retake pipeline requires VAE decoder", None, False),
+    "retake_av": ("Retake pipeline requires a loaded model", "Retake pipeline requires VAE decoder", None, False),
     "two_stage": ("Two-stage pipeline requires a loaded model (cannot use placeholder mode)",
                   "the two-stage pipeline needs the VAE weights (per-channel statistics): drop --skip-vae", None, True),
     "av": (None, "AV pipeline requires VAE decoder", "  AV pipeline requires model - cannot use placeholder mode", False),
@@ -1098,7 +1123,8 @@ def finish(r, s, frames, audio=None, source_fps=None):
     frames_np = frames.cpu().numpy()
     np.savez_compressed(s.base + ".npz", frames=frames_np)
     if audio is not None and r.save_mp4:
-        video_out, wav = save_video_with_audio(frames_np, audio[0], r.output_path, audio[1], fps=fps, speed=r.output_speed)      # never the retake route
+        at_source_rate = {} if source_fps is None else dict(input_fps=input_fps)          # the retake route with sound
+        video_out, wav = save_video_with_audio(frames_np, audio[0], r.output_path, audio[1], fps=fps, speed=r.output_speed, **at_source_rate)
         print(f"  video: {video_out}, audio: {wav}")
     elif audio is not None:
         print(f"  audio: {write_wav(s.base + '.wav', audio[0], audio[1])}")
@@ -1275,6 +1301,46 @@ def _run_retake(r, s):
     guider = dict(guider=r.apg_guider) if r.apg_guider is not None else {}
     frames, _ = _timed_run("retake", lambda: pipe(r.retake_video, s.text_encoding, None, conf, negative_text_encoding=s.negative_encoding, **guider))
     return finish(r, s, frames, source_fps=r.retake_fps)
+
+
+def _run_retake_av(r, s):
+    """retake_video with retake_audio (both keyword-only): the silent route's retake (_run_retake: the clip, the window, the variants, the output at the source's rate) on the AudioVideo
+    transformer, with the clip's sound track -- any file load_audio_file reads -- encoded by the audio VAE encoder and retaken over the same seconds as the picture: the audio tokens whose
+    seconds meet the widened pixel window.  model_variant="distilled" runs the 8 joint distilled steps; any other variant LTX2Scheduler over num_steps with classifier-free guidance on both
+    latents, the video at cfg_scale and the audio at retake_audio_cfg (None: cfg_scale), one HIP step per step in one captured graph.  The negative encodings as in the hq_av route.  The audio
+    latent is written to `<stem>_audio_latent.npz`; decode_audio turns it into `<stem>.wav`, muxed into the mp4.  retake_composite puts the source's own frames back outside the window AND
+    the source track's own samples (20 ms fade outside it).  Not combined with audio_path, keyframes, control_video, image_path, two_stage_distilled, upscale_spatial, upscale_temporal,
+    fp8_resident, apg_scale or another pipeline_type."""
+    print("\n=== Using Retake Pipeline (picture and sound) ===")
+    _require(r, s)
+    from ltx_2_mlx_amd.pipelines import RetakeConfig, RetakePipeline
+    distilled = r.model_variant == "distilled"
+    conf = RetakeConfig(start_time=r.retake_start_time, end_time=r.retake_end_time, distilled=distilled, num_inference_steps=r.num_steps,
+                        cfg_scale=r.cfg_scale, seed=r.seed, fps=r.retake_fps, use_hip_graph=r.use_hip_graph, composite_source=r.retake_composite,
+                        tiling_config=_tiling(r), audio_cfg_scale=r.retake_audio_cfg, composite_source_audio=r.retake_composite)
+    latent_frames = (r.num_frames - 1) // 8 + 1
+    print(f"  Source: {r.retake_video}, {r.width}x{r.height}, {r.num_frames} frames @ {r.retake_fps:g} FPS; sound track: {r.retake_audio}")
+    print(f"  Retake region: {r.retake_start_time:g}s - {'the end of the clip' if r.retake_to_end else f'{r.retake_end_time:g}s'} -> latent frames "
+          f"[{r.retake_window[0]}, {r.retake_window[1]}) of {latent_frames}, {latent_frames * (r.height // 32) * (r.width // 32)} DiT tokens"
+          + (", source frames and samples kept outside it" if r.retake_composite else ""))
+    _banners(r, upscaler=False)
+    weights = r.weights_path if r.have_ckpt else None
+    decoders = create_audio_decoders(r.decode_audio, weights, device=r.device, seed=r.seed + 3) or (None, None)
+    pipe = RetakePipeline(s.model, make_encoder(r), s.vae_decoder, decoders[0], decoders[1], audio_encoder=create_audio_encoder(weights, r.device, seed=r.seed + 5))
+    audio_cfg = r.cfg_scale if r.retake_audio_cfg is None else r.retake_audio_cfg
+    guided = not distilled and (r.cfg_scale > 1.0 or audio_cfg > 1.0)
+    negative, negative_audio = s.negative_encoding, s.negative_audio_encoding
+    if _negative_or_zeros_note(guided, negative):
+        negative = torch.zeros_like(s.text_encoding)
+    if _negative_or_zeros_note(guided, negative_audio):
+        negative_audio = torch.zeros_like(s.text_audio_encoding)
+    print(f"[5/5] Running retake with sound ({'8 joint distilled steps' if distilled else f'{r.num_steps} joint steps, cfg {r.cfg_scale} / {audio_cfg}'})...")
+    frames, audio = _timed_run("retake audio+video", lambda: pipe(r.retake_video, s.text_encoding, None, conf, negative_text_encoding=negative,
+                                                                  audio_encoding=s.text_audio_encoding, negative_audio_encoding=negative_audio,
+                                                                  audio_path=r.retake_audio))
+    np.savez(s.base + "_audio_latent.npz", latent=pipe.audio_latent.float().cpu().numpy())
+    print(f"  audio tokens [{pipe.audio_window[0]}, {pipe.audio_window[1]}) retaken" + (f", samples {list(pipe.audio_sample_window)} of the waveform" if decoders[0] else ""))
+    return finish(r, s, frames, audio=(audio, decoders[1].output_sample_rate) if decoders[0] is not None else None, source_fps=r.retake_fps)
 
 
 def _run_a2vid(r, s):
@@ -1454,7 +1520,8 @@ def _run_standard(r, s):
 
 
 # today's precedence, top to bottom; _resolve_request names the one that runs
-_ROUTES = {"two_stage_cfg": _run_two_stage_cfg, "hq_av": _run_hq_av, "a2vid": _run_a2vid, "keyframe": _run_keyframe, "hq": _run_hq, "ic_lora": _run_ic_lora, "retake": _run_retake, "two_stage": _run_two_stage,
+_ROUTES = {"two_stage_cfg": _run_two_stage_cfg, "hq_av": _run_hq_av, "a2vid": _run_a2vid, "keyframe": _run_keyframe, "hq": _run_hq, "ic_lora": _run_ic_lora, "retake_av": _run_retake_av,
+           "retake": _run_retake, "two_stage": _run_two_stage,
            "av": _run_av, "standard": _run_standard}
 
 
@@ -1544,6 +1611,8 @@ def generate_video(
     two_stage_cfg: bool = False,
     modality_scale: float = 3.0,
     two_stage_rescale: float = 0.0,
+    retake_audio: Optional[str] = None,
+    retake_audio_cfg: Optional[float] = None,
     retake_video=None,
     retake_start_time: float = 0.0,
     retake_end_time=None,
@@ -1551,7 +1620,7 @@ def generate_video(
 ):
     """Generate video from a text prompt: denoise loop + VAE decode on MI355X behind the reference's signature.  _resolve_request validates the arguments and names the one route that runs, before
     any model is loaded; then the text encoding, the transformer and the VAE decoder (built from the checkpoint's `config.vae` record) are loaded and the route's function runs.  Precedence, each
-    documented on its function: two_stage_cfg (_run_two_stage_cfg; keyword-only, with modality_scale and two_stage_rescale), ti2vid_hq_audio (_run_hq_av; keyword-only), a2vid_two_stage (_run_a2vid; keyword-only, it refuses retake_video), retake_video (_run_retake; it refuses every other route), pipeline_type "keyframe-interpolation" with keyframes (_run_keyframe), "ti2vid-hq" (_run_hq), "ic-lora"
+    documented on its function: two_stage_cfg (_run_two_stage_cfg; keyword-only, with modality_scale and two_stage_rescale), ti2vid_hq_audio (_run_hq_av; keyword-only), a2vid_two_stage (_run_a2vid; keyword-only, it refuses retake_video), retake_video with retake_audio (_run_retake_av; keyword-only, the clip's sound track is retaken with the picture), retake_video (_run_retake; it refuses every other route), pipeline_type "keyframe-interpolation" with keyframes (_run_keyframe), "ti2vid-hq" (_run_hq), "ic-lora"
     with a control video or an image (_run_ic_lora), two_stage_distilled (_run_two_stage), generate_audio or an LTX-2.3 checkpoint (_run_av), else the standard video-only loop (_run_standard).
     pipeline_type "two-stage" raises NotImplementedError. MI355X extras for every route: model_version="2.3" builds the LTX-2.3 architecture without a checkpoint (random init, for tests and
     benchmarks); fp8_resident keeps fp8 checkpoint weights as codes in HBM; fp8_compute runs the video stream's projections fp8 x fp8 on the fp8 MFMA (BASELINE config 3; per-token / per-channel
@@ -1670,6 +1739,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--retake-start", type=float, default=0.0, help="start of the regenerated window in seconds (inclusive)")
     p.add_argument("--retake-end", type=float, default=None, help="end of the regenerated window in seconds (exclusive); default: the end of the clip")
     p.add_argument("--retake-keep-source", action="store_true", help="put the source's own frames back outside the window (4-frame fade outside it)")
+    p.add_argument("--retake-audio", type=str, default=None, help="with --retake: the clip's sound track (a .wav, or any file ffmpeg / soundfile reads); picture AND sound "
+                   "are regenerated over the same seconds on the AudioVideo model; --decode-audio writes the .wav and muxes it; --retake-keep-source also puts the track's own "
+                   "samples back outside the window")
+    p.add_argument("--retake-audio-cfg", type=float, default=None, help="with --retake-audio: guidance scale of the audio latent (default: --cfg)")
     p.add_argument("--stg-blocks", type=int, nargs="+", default=None, help="with --stg-scale: the blocks whose video self-attention the perturbed pass skips (default: all)")
     p.add_argument("--stg-cutoff", type=float, default=1.0, help="with --stg-scale: STG guides the first fraction of the steps, (step + 1) / steps <= cutoff")
     return p
@@ -1704,6 +1777,7 @@ def kwargs_from_args(a) -> dict:
         vae_base_channels=a.vae_base_channels, save_mp4=not a.no_video_file, decode_audio=a.decode_audio,
         audio_path=a.audio, audio_start_time=a.audio_start, audio_max_duration=a.audio_duration, a2vid_two_stage=a.a2vid_two_stage, ti2vid_hq_audio=a.ti2vid_hq_audio,
         two_stage_cfg=a.two_stage_cfg, modality_scale=a.modality_scale,
+        retake_audio=a.retake_audio, retake_audio_cfg=a.retake_audio_cfg,
         retake_video=a.retake, retake_start_time=a.retake_start, retake_end_time=a.retake_end, retake_composite=a.retake_keep_source,
         stg_blocks=a.stg_blocks, stg_cutoff=a.stg_cutoff)
 
