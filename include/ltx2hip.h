@@ -381,6 +381,30 @@ int ltx2_guidance_sums(const float* x, const float* vel_cond, const float* vel_u
 int ltx2_projected_euler_step(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, int64_t ts_stride, const float* mask,
                               const float* clean, const float* running, const double* partials, int mode, float scale, float eta,
                               float norm_threshold, float sigma, float sigma_next, float* out, float* scalars_out, int rows, int C, void* stream);
+/* The same two passes over TWO latents in ONE launch each -- the video and the audio latent of a joint guided step, the audio one about a hundred
+ * rows.  The single forms' operands twice, v_ then a_: each segment has its own operands, ts / ts_stride, running / first / momentum and partials
+ * region partials[ltx2_guidance_sums_blocks(rows, C)][5], and in the step its own mode, scale, eta, norm_threshold, mask / clean, scalars_out and
+ * rows / C; sigma and sigma_next are shared.  A segment's blocks number their partial rows from 0 and add their own rows in index order, the
+ * scalars are derived in fp64 and rounded once, every fp32 operation is individually rounded: each segment's partials, running, scalars_out and
+ * out equal the single entries' bit for bit at the same access width.  16-byte accesses only when BOTH segments qualify (the order of the
+ * fp64 sums, and so their last bits, depends on the access width; the step's element-wise part does not).
+ * ltx2_guidance_sums_pair: a segment with partials == NULL is left out (its guider reads no sums); both NULL -> LTX2_E_INVALID.
+ * ltx2_projected_euler_step_pair: a segment's mode is 0, 1, 2 as in ltx2_projected_euler_step, or one of two guiders without sums, for which
+ *   partials may be NULL, nothing is stored to scalars_out and running is refused:
+ *   mode 3 (CFG):  g_out = a + (scale - 1)*(a - b), ltx2_guided_euler_step's arithmetic;   mode 4 (off): g_out = a (vel_uncond may be NULL).
+ *   The single entry keeps refusing modes 3 and 4.  sigma == 0 -> LTX2_E_INVALID with message "Sigma can't be 0.0".
+ * (additive entries of ABI version 3)                                                                                                   */
+int ltx2_guidance_sums_pair(const float* v_x, const float* v_vel_cond, const float* v_vel_uncond, const float* v_ts, int64_t v_ts_stride,
+                            float* v_running, int v_first, float v_momentum, double* v_partials, int v_rows, int v_C, const float* a_x,
+                            const float* a_vel_cond, const float* a_vel_uncond, const float* a_ts, int64_t a_ts_stride, float* a_running, int a_first,
+                            float a_momentum, double* a_partials, int a_rows, int a_C, void* stream);
+int ltx2_projected_euler_step_pair(const float* v_x, const float* v_vel_cond, const float* v_vel_uncond, const float* v_ts, int64_t v_ts_stride,
+                                   const float* v_mask, const float* v_clean, const float* v_running, const double* v_partials, int v_mode,
+                                   float v_scale, float v_eta, float v_norm_threshold, float* v_out, float* v_scalars_out, int v_rows, int v_C,
+                                   const float* a_x, const float* a_vel_cond, const float* a_vel_uncond, const float* a_ts, int64_t a_ts_stride,
+                                   const float* a_mask, const float* a_clean, const float* a_running, const double* a_partials, int a_mode,
+                                   float a_scale, float a_eta, float a_norm_threshold, float* a_out, float* a_scalars_out, int a_rows, int a_C,
+                                   float sigma, float sigma_next, void* stream);
 
 /* MultiModalGuider.calculate (components/guiders.py:244-273) and the Euler step behind it, the stage-1 step of the two-stage pipeline
  * (pipelines/two_stage.py:366-390), over [rows][C] fp32.  Every fp32 operation is individually rounded, in the reference's order, so the
@@ -638,6 +662,31 @@ int ltx2_dit_projected_step(ltx2_dit* ctx, ltx2_dit* neg, float* latent, const f
 int ltx2_dit_graph_capture_projected(ltx2_dit* ctx, ltx2_dit* neg, float* latent, const float* host_sigmas, int n_steps, const float* mask,
                                      int64_t n_mask, const float* clean, int64_t n_clean, int mode, float scale, float eta, float norm_threshold,
                                      float momentum, void* stream);
+/* The projected step on the AudioVideo engine with BOTH latents stepped, each modality under its own guider (OneStagePipeline's joint branch:
+ * a CFGStarRescalingGuider per modality by default, pipelines/one_stage.py:466-568).  In order on the caller's stream: forward_av on ctx, then on
+ * neg, scheduled exactly as ltx2_dit_guided_step_joint_av schedules them; ONE ltx2_guidance_sums_pair over the modalities whose guider reads
+ * sums (none does: no launch); ONE ltx2_projected_euler_step_pair in place on both latents.  v_mode / a_mode and their scale / eta /
+ * norm_threshold as in ltx2_projected_euler_step_pair (3: plain CFG, 4: the modality is not guided).  momentum != 0 (mode 2 only) keeps that
+ * modality's running guidance in the CALLER's buffer, [N][out_channels] resp. [Na][audio_out_channels] fp32 (n_*_running: its ELEMENT count,
+ * checked against the bound shape); without momentum the buffer is NULL.  first != 0 starts the running guidance (the first step of a loop).
+ * The partials are allocated on first use for the bound shapes, before anything is enqueued, and freed with ctx.  The sums run over all rows
+ * of a modality, appended conditioning tokens included.  LTX2_E_INVALID, before anything is launched: the rules of
+ * ltx2_dit_guided_step_joint_av, a mode outside 0..4, momentum outside mode 2, a running buffer that is missing, unasked for or of another length.
+ * ltx2_dit_graph_capture_projected_joint_av: n_steps (< 64) of that step as one captured graph owned by ctx (ltx2_dit_graph_launch(ctx) replays
+ * it), built like ltx2_dit_graph_capture_guided_joint_av; first is 1 in step 0 only, and a memset node at the head of the chain clears each
+ * running buffer, so every replay starts alike.  (additive entries of ABI version 3)                                                       */
+int ltx2_dit_projected_step_joint_av(ltx2_dit* ctx, ltx2_dit* neg, float* v_latent, float* a_latent, const float* v_timesteps, int n_v_timesteps,
+                                     const float* a_timesteps, int n_a_timesteps, const float* sigma_dev, const float* v_mask, const float* v_clean,
+                                     const float* a_mask, const float* a_clean, int v_mode, float v_scale, float v_eta, float v_norm_threshold,
+                                     float v_momentum, float* v_running, int64_t n_v_running, int a_mode, float a_scale, float a_eta,
+                                     float a_norm_threshold, float a_momentum, float* a_running, int64_t n_a_running, int first, float sigma,
+                                     float sigma_next, void* stream);
+int ltx2_dit_graph_capture_projected_joint_av(ltx2_dit* ctx, ltx2_dit* neg, float* v_latent, float* a_latent, const float* host_sigmas, int n_steps,
+                                              const float* v_mask, int64_t n_v_mask, const float* v_clean, int64_t n_v_clean, const float* a_mask,
+                                              int64_t n_a_mask, const float* a_clean, int64_t n_a_clean, int v_mode, float v_scale, float v_eta,
+                                              float v_norm_threshold, float v_momentum, float* v_running, int64_t n_v_running, int a_mode,
+                                              float a_scale, float a_eta, float a_norm_threshold, float a_momentum, float* a_running,
+                                              int64_t n_a_running, void* stream);
 /* One res_2s step on the VideoOnly engine (pipelines/ti2vid_hq.py:185-273), enqueued in order on the caller's stream: forward(ctx) and
  * forward(neg) from `latent` at `timesteps`, ltx2_res2s_midpoint into workspaces owned by ctx, forward(ctx) and forward(neg) from x_mid at
  * `ts_sub` (the timesteps of the sub-sigma sqrt(sigma * sigma_next)), ltx2_res2s_combine into `latent`.  neg may be NULL: no guidance, two

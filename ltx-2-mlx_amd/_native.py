@@ -101,6 +101,9 @@ SIGNATURES = {
     "ltx2_guidance_sums_blocks": (i32, [i32, i32]),
     "ltx2_guidance_sums": (i32, [vp, vp, vp, vp, i64, vp, i32, f32, vp, i32, i32, vp]),
     "ltx2_projected_euler_step": (i32, [vp, vp, vp, vp, i64, vp, vp, vp, vp, i32, f32, f32, f32, f32, f32, vp, vp, i32, i32, vp]),
+    "ltx2_guidance_sums_pair": (i32, [vp, vp, vp, vp, i64, vp, i32, f32, vp, i32, i32, vp, vp, vp, vp, i64, vp, i32, f32, vp, i32, i32, vp]),
+    "ltx2_projected_euler_step_pair": (i32, [vp, vp, vp, vp, i64, vp, vp, vp, vp, i32, f32, f32, f32, vp, vp, i32, i32,
+                                             vp, vp, vp, vp, i64, vp, vp, vp, vp, i32, f32, f32, f32, vp, vp, i32, i32, f32, f32, vp]),
     "ltx2_mm_guided_euler_step": (i32, [vp, vp, vp, vp, vp, vp, i64, vp, vp, f32, f32, f32, f32, f32, vp, i32, i32, vp]),
     "ltx2_mm_guided_euler_step_pair": (i32, [vp, vp, vp, vp, vp, vp, i64, vp, vp, f32, f32, f32, vp, i32, i32,
                                              vp, vp, vp, vp, vp, vp, i64, vp, vp, f32, f32, f32, vp, i32, i32, f32, f32, vp]),
@@ -146,6 +149,10 @@ SIGNATURES = {
     "ltx2_dit_graph_capture_guided_joint_av": (i32, [vp, vp, vp, vp, C.POINTER(f32), i32, vp, i64, vp, i64, vp, i64, vp, i64, f32, f32, vp]),
     "ltx2_dit_projected_step": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, i32, f32, f32, f32, f32, i32, f32, f32, vp]),
     "ltx2_dit_graph_capture_projected": (i32, [vp, vp, vp, C.POINTER(f32), i32, vp, i64, vp, i64, i32, f32, f32, f32, f32, vp]),
+    "ltx2_dit_projected_step_joint_av": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, i32, f32, f32, f32, f32, vp, i64,
+                                               i32, f32, f32, f32, f32, vp, i64, i32, f32, f32, vp]),
+    "ltx2_dit_graph_capture_projected_joint_av": (i32, [vp, vp, vp, vp, C.POINTER(f32), i32, vp, i64, vp, i64, vp, i64, vp, i64,
+                                                        i32, f32, f32, f32, f32, vp, i64, i32, f32, f32, f32, f32, vp, i64, vp]),
     "ltx2_dit_res2s_step": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, f32, f32, f32, vp]),
     "ltx2_dit_graph_capture_res2s": (i32, [vp, vp, vp, C.POINTER(f32), i32, vp, i64, vp, i64, f32, vp]),
     "ltx2_dit_res2s_step_av": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, f32, f32, vp]),

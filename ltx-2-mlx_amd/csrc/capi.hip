@@ -351,6 +351,28 @@ int ltx2_projected_euler_step(const float* x, const float* vel_cond, const float
                                        sigma, sigma_next, out, scalars_out, rows, C, (hipStream_t)stream);
 }
 
+int ltx2_guidance_sums_pair(const float* v_x, const float* v_vel_cond, const float* v_vel_uncond, const float* v_ts, int64_t v_ts_stride, float* v_running,
+                            int v_first, float v_momentum, double* v_partials, int v_rows, int v_C, const float* a_x, const float* a_vel_cond,
+                            const float* a_vel_uncond, const float* a_ts, int64_t a_ts_stride, float* a_running, int a_first, float a_momentum,
+                            double* a_partials, int a_rows, int a_C, void* stream) {
+    return guidance_sums_pair_launch(v_x, v_vel_cond, v_vel_uncond, v_ts, (long)v_ts_stride, v_running, v_first, v_momentum, v_partials, v_rows, v_C, a_x,
+                                     a_vel_cond, a_vel_uncond, a_ts, (long)a_ts_stride, a_running, a_first, a_momentum, a_partials, a_rows, a_C,
+                                     (hipStream_t)stream);
+}
+
+int ltx2_projected_euler_step_pair(const float* v_x, const float* v_vel_cond, const float* v_vel_uncond, const float* v_ts, int64_t v_ts_stride,
+                                   const float* v_mask, const float* v_clean, const float* v_running, const double* v_partials, int v_mode,
+                                   float v_scale, float v_eta, float v_norm_threshold, float* v_out, float* v_scalars_out, int v_rows, int v_C,
+                                   const float* a_x, const float* a_vel_cond, const float* a_vel_uncond, const float* a_ts, int64_t a_ts_stride,
+                                   const float* a_mask, const float* a_clean, const float* a_running, const double* a_partials, int a_mode,
+                                   float a_scale, float a_eta, float a_norm_threshold, float* a_out, float* a_scalars_out, int a_rows, int a_C,
+                                   float sigma, float sigma_next, void* stream) {
+    return projected_euler_step_pair_launch(v_x, v_vel_cond, v_vel_uncond, v_ts, (long)v_ts_stride, v_mask, v_clean, v_running, v_partials, v_mode, v_scale,
+                                            v_eta, v_norm_threshold, v_out, v_scalars_out, v_rows, v_C, a_x, a_vel_cond, a_vel_uncond, a_ts,
+                                            (long)a_ts_stride, a_mask, a_clean, a_running, a_partials, a_mode, a_scale, a_eta, a_norm_threshold, a_out,
+                                            a_scalars_out, a_rows, a_C, sigma, sigma_next, (hipStream_t)stream);
+}
+
 int ltx2_mm_guided_euler_step(const float* x, const float* vel_cond, const float* vel_uncond, const float* vel_perturbed, const float* vel_isolated,
                               const float* ts, int64_t ts_stride, const float* mask, const float* clean, float cfg_scale, float stg_scale,
                               float modality_scale, float sigma, float sigma_next, float* out, int rows, int C, void* stream) {

@@ -121,6 +121,8 @@ struct ltx2_dit {
     long pg_run_n = 0;
     double* mm_part[2] = {};           // multi-modal guidance with rescale: each modality's partials [mm_rows[k]][4], allocated on first use for the bound shapes, freed with the context
     int mm_rows[2] = {};
+    double* pgj_part[2] = {};          // joint projected guidance: each modality's partials [pgj_rows[k]][5], for the modalities whose guider reads sums; allocated on first use, freed with the context
+    int pgj_rows[2] = {};
     // fp8-resident linear weights: the typed `const bf16*` fields of the weight structs then hold the CODES pointer; dense() looks it
     // up here to hand the GEMM (codes, per-row scale) instead of bf16 weights.  Per context (a second context over the same tensors
     // -- the video twin of an AudioVideo model -- keeps its own entries); rebuilt whenever the weights are resolved again.
@@ -1084,6 +1086,8 @@ void ltx2_dit_destroy(ltx2_dit* c) {
     if (c->pg_run) (void)hipFree(c->pg_run);
     for (double* p : c->mm_part)
         if (p) (void)hipFree(p);
+    for (double* p : c->pgj_part)
+        if (p) (void)hipFree(p);
     if (c->exec) (void)hipGraphExecDestroy(c->exec);
     if (c->graph) (void)hipGraphDestroy(c->graph);
     for (hipEvent_t e : c->prof_ev) (void)hipEventDestroy(e);
@@ -1431,6 +1435,64 @@ int projected_step(ltx2_dit* c, ltx2_dit* neg, const ModIn& in, const StepIo& io
                                        g.norm_threshold, sigma, sigma_next, io.latent, nullptr, m.N, m.Cout, st);
 }
 
+// The same on AudioVideo contexts with BOTH latents stepped, each under its own guider (OneStagePipeline's joint branch with its default guiders, a
+// CFGStarRescalingGuider per modality; pipelines/one_stage.py:466-568): the two evaluations of guided_step_joint, then ONE sums launch over the
+// modalities whose guider reads sums and ONE step launch over both latents.  A modality's guider is one of projected_step's, plain CFG
+// (PROJECTED_CFG) or none (PROJECTED_OFF).  run[k]: the caller's running guidance of a legacy APG guider with momentum, else NULL.
+bool projected_sums(const Projected& g) { return g.mode < PROJECTED_CFG; }
+
+int projected_joint_check(const Projected g[2], float* const run[2], const int64_t n_run[2], const ltx2_dit* c, const char* who) {
+    for (int k = 0; k < 2; ++k) {
+        LTX2_CHECK_ARG(g[k].mode >= 0 && g[k].mode <= PROJECTED_OFF, "%s: mode=%d of modality %d is 0 (CFG*), 1 (APG), 2 (legacy APG), 3 (CFG) or 4 (off)", who,
+                       g[k].mode, k);
+        LTX2_CHECK_ARG(g[k].momentum == 0.f || g[k].mode == 2, "%s: momentum=%g belongs to mode 2 (legacy APG) alone", who, g[k].momentum);
+        // the sums kernel writes, and the step kernel reads, N * out_channels elements there on every step (the comment at cond_modality())
+        const int64_t need = (int64_t)c->m[k].N * c->m[k].Cout;
+        LTX2_CHECK_ARG(g[k].running() ? (run[k] && n_run[k] == need) : !run[k],
+                       "%s: modality %d %s a running buffer of %d tokens x %d channels, got %ld elements", who, k,
+                       g[k].running() ? "needs" : "(no momentum) takes no", c->m[k].N, c->m[k].Cout, (long)(run[k] ? n_run[k] : 0));
+    }
+    return LTX2_OK;
+}
+
+// each modality's partials, for the modalities whose guider reads sums; never called while a stream is capturing
+int projected_joint_workspace(ltx2_dit* c, const Projected g[2]) {
+    for (int k = 0; k < 2; ++k) {
+        const int rows = guidance_sums_blocks(c->m[k].N, c->m[k].Cout);
+        if (!projected_sums(g[k]) || (c->pgj_part[k] && c->pgj_rows[k] == rows)) continue;
+        if (c->pgj_part[k]) (void)hipFree(c->pgj_part[k]);
+        c->pgj_part[k] = nullptr;
+        c->pgj_rows[k] = 0;
+        if (hipMalloc((void**)&c->pgj_part[k], 8L * 5 * rows) != hipSuccess) {
+            ltx2_set_error("dit_projected_step_joint_av: allocating %ld bytes of workspace failed", 8L * 5 * rows);
+            return LTX2_E_HIP;
+        }
+        c->pgj_rows[k] = rows;
+    }
+    return LTX2_OK;
+}
+
+int projected_step_joint(ltx2_dit* c, ltx2_dit* neg, const ModIn* in, const StepIo* io, const Projected g[2], float* const run[2], int first, float sigma,
+                         float sigma_next, hipStream_t st, bool rewind_events = true) {
+    TRY(step_check(sigma, io, 2, "dit_projected_step_joint_av"));
+    const Mod &v = c->m[0], &a = c->m[1];
+    double* part[2];
+    for (int k = 0; k < 2; ++k) {
+        part[k] = projected_sums(g[k]) ? c->pgj_part[k] : nullptr;
+        LTX2_CHECK_ARG(!projected_sums(g[k]) || (part[k] && c->pgj_rows[k] == guidance_sums_blocks(c->m[k].N, c->m[k].Cout)),
+                       "dit_projected_step_joint_av: workspace missing");
+    }
+    TRY(evaluate(c, neg, in, st, rewind_events));
+    const long stride[2] = {in[0].n_ts == 1 ? 0 : 1, in[1].n_ts == 1 ? 0 : 1};
+    if (part[0] || part[1])
+        TRY(guidance_sums_pair_launch(in[0].latent, v.vel, neg->m[0].vel, in[0].ts, stride[0], run[0], first, g[0].momentum, part[0], v.N, v.Cout, in[1].latent,
+                                      a.vel, neg->m[1].vel, in[1].ts, stride[1], run[1], first, g[1].momentum, part[1], a.N, a.Cout, st));
+    return projected_euler_step_pair_launch(in[0].latent, v.vel, neg->m[0].vel, in[0].ts, stride[0], io[0].mask, io[0].clean, run[0], part[0], g[0].mode,
+                                            g[0].scale, g[0].eta, g[0].norm_threshold, io[0].latent, nullptr, v.N, v.Cout, in[1].latent, a.vel,
+                                            neg->m[1].vel, in[1].ts, stride[1], io[1].mask, io[1].clean, run[1], part[1], g[1].mode, g[1].scale, g[1].eta,
+                                            g[1].norm_threshold, io[1].latent, nullptr, a.N, a.Cout, sigma, sigma_next, st);
+}
+
 // Multi-modal guidance on AudioVideo contexts (the reference's two-stage pipeline, pipelines/two_stage.py:314-401; MultiModalGuider.calculate): per step
 // up to four evaluations of BOTH modalities -- c, neg (NULL: no CFG term), c with the self-attentions of c->stg skipped into the caller's ptb scratch
 // (NULL: no STG term), c with every cross-modal attention skipped into the caller's mod scratch (NULL: no modality term) -- and then both latents stepped,
@@ -1612,6 +1674,8 @@ struct LoopStep {                           // all defaults: the plain denoise s
     int stg_steps = 0;
     bool joint = false;                     // the guided step on AudioVideo contexts steps BOTH latents, the audio one under audio_cfg_scale
     float audio_cfg_scale = 0.f;
+    const Projected* projected_joint = nullptr;     // with joint: each modality under its own guider, [2]
+    float* const* running_joint = nullptr;          //   and its running guidance, [2] (NULL where the guider keeps none)
 };
 
 int capture_loop(ltx2_dit* c, const LoopStep& step, float* const latent[2], const Cond cond[2], const float* host_sigmas, int n_steps, hipStream_t st) {
@@ -1625,6 +1689,11 @@ int capture_loop(ltx2_dit* c, const LoopStep& step, float* const latent[2], cons
         ltx2_set_error("dit_graph_capture_projected: hipMemsetAsync failed");
         rc = LTX2_E_HIP;
     }
+    for (int k = 0; step.projected_joint && k < 2 && rc == LTX2_OK; ++k)
+        if (step.projected_joint[k].running() && hipMemsetAsync(step.running_joint[k], 0, 4L * c->m[k].N * c->m[k].Cout, st) != hipSuccess) {
+            ltx2_set_error("dit_graph_capture_projected_joint_av: hipMemsetAsync failed");
+            rc = LTX2_E_HIP;
+        }
     for (int i = 0; i < n_steps && rc == LTX2_OK; ++i) {
         const float *s = c->sigmas_dev + i, *ss = c->sigmas_dev + 64 + i;
         const float sigma = host_sigmas[i], sigma_next = host_sigmas[i + 1];
@@ -1643,6 +1712,8 @@ int capture_loop(ltx2_dit* c, const LoopStep& step, float* const latent[2], cons
             rc = projected_step(c, step.neg, in[0], io[0], *step.projected, i == 0, sigma, sigma_next, st);
         } else if (step.stg_vel && i < step.stg_steps) {
             rc = stg_step(c, step.neg, in[0], io[0], step.stg_vel, step.cfg_scale, step.stg_scale, sigma, sigma_next, st);
+        } else if (step.projected_joint) {
+            rc = projected_step_joint(c, step.neg, in, io, step.projected_joint, step.running_joint, i == 0, sigma, sigma_next, st, i == 0);
         } else if (step.neg && step.joint) {
             const float cfg[2] = {step.cfg_scale, step.audio_cfg_scale};
             rc = guided_step_joint(c, step.neg, in, io, cfg, sigma, sigma_next, st, i == 0);
@@ -1732,6 +1803,28 @@ int ltx2_dit_projected_step(ltx2_dit* c, ltx2_dit* neg, float* latent, const flo
     TRY(projected_workspace(c, g.running(), first == 0));
     const StepArgs v = step_args(latent, timesteps, n_timesteps, sigma_dev, mask, clean);
     return projected_step(c, neg, v.in, v.io, g, first, sigma, sigma_next, (hipStream_t)stream);
+}
+
+int ltx2_dit_projected_step_joint_av(ltx2_dit* c, ltx2_dit* neg, float* v_latent, float* a_latent, const float* v_timesteps, int n_v_timesteps,
+                                     const float* a_timesteps, int n_a_timesteps, const float* sigma_dev, const float* v_mask, const float* v_clean,
+                                     const float* a_mask, const float* a_clean, int v_mode, float v_scale, float v_eta, float v_norm_threshold,
+                                     float v_momentum, float* v_running, int64_t n_v_running, int a_mode, float a_scale, float a_eta,
+                                     float a_norm_threshold, float a_momentum, float* a_running, int64_t n_a_running, int first, float sigma,
+                                     float sigma_next, void* stream) {
+    LTX2_CHECK_ARG(neg && v_latent && a_latent && v_timesteps && a_timesteps && sigma_dev, "dit_projected_step_joint_av: null argument");
+    const int n_ts[2] = {n_v_timesteps, n_a_timesteps};
+    TRY(step_ready(c, neg, true, n_ts, "dit_projected_step_joint_av"));
+    const Projected g[2] = {{v_mode, v_scale, v_eta, v_norm_threshold, v_momentum}, {a_mode, a_scale, a_eta, a_norm_threshold, a_momentum}};
+    float* const run[2] = {v_running, a_running};
+    const int64_t n_run[2] = {n_v_running, n_a_running};
+    TRY(projected_joint_check(g, run, n_run, c, "dit_projected_step_joint_av"));
+    const StepArgs v = step_args(v_latent, v_timesteps, n_v_timesteps, sigma_dev, v_mask, v_clean);
+    const StepArgs a = step_args(a_latent, a_timesteps, n_a_timesteps, sigma_dev, a_mask, a_clean);
+    const ModIn in[2] = {v.in, a.in};
+    const StepIo io[2] = {v.io, a.io};
+    TRY(step_check(sigma, io, 2, "dit_projected_step_joint_av"));        // every refusal stands before the workspace is touched
+    TRY(projected_joint_workspace(c, g));
+    return projected_step_joint(c, neg, in, io, g, run, first, sigma, sigma_next, (hipStream_t)stream);
 }
 
 int ltx2_dit_res2s_step(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev,
@@ -1895,6 +1988,27 @@ int ltx2_dit_graph_capture_guided_joint_av(ltx2_dit* c, ltx2_dit* neg, float* v_
     step.cfg_scale = cfg_scale;
     step.joint = true;
     step.audio_cfg_scale = audio_cfg_scale;
+    return capture_loop(c, step, lo.lat, lo.cond, host_sigmas, n_steps, (hipStream_t)stream);
+}
+
+int ltx2_dit_graph_capture_projected_joint_av(ltx2_dit* c, ltx2_dit* neg, float* v_latent, float* a_latent, const float* host_sigmas, int n_steps,
+                                              const float* v_mask, int64_t n_v_mask, const float* v_clean, int64_t n_v_clean, const float* a_mask,
+                                              int64_t n_a_mask, const float* a_clean, int64_t n_a_clean, int v_mode, float v_scale, float v_eta,
+                                              float v_norm_threshold, float v_momentum, float* v_running, int64_t n_v_running, int a_mode,
+                                              float a_scale, float a_eta, float a_norm_threshold, float a_momentum, float* a_running,
+                                              int64_t n_a_running, void* stream) {
+    const LoopIo lo = {{v_latent, a_latent}, {{v_mask, (long)n_v_mask, v_clean, (long)n_v_clean}, {a_mask, (long)n_a_mask, a_clean, (long)n_a_clean}}};
+    TRY(capture_ready(c, neg, true, true, lo, host_sigmas, n_steps, "dit_graph_capture_projected_joint_av", true));
+    const Projected g[2] = {{v_mode, v_scale, v_eta, v_norm_threshold, v_momentum}, {a_mode, a_scale, a_eta, a_norm_threshold, a_momentum}};
+    float* const run[2] = {v_running, a_running};
+    const int64_t n_run[2] = {n_v_running, n_a_running};
+    TRY(projected_joint_check(g, run, n_run, c, "dit_graph_capture_projected_joint_av"));
+    TRY(projected_joint_workspace(c, g));
+    LoopStep step;
+    step.neg = neg;
+    step.joint = true;
+    step.projected_joint = g;
+    step.running_joint = run;
     return capture_loop(c, step, lo.lat, lo.cond, host_sigmas, n_steps, (hipStream_t)stream);
 }
 

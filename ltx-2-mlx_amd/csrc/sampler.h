@@ -70,6 +70,26 @@ int projected_euler_step_launch(const float* x, const float* vel_cond, const flo
                                 float norm_threshold, float sigma, float sigma_next, float* out, float* scalars_out, int rows, int C,
                                 hipStream_t stream);
 
+// Both passes over TWO latents in one launch (the video and the audio latent of a joint step), v_ then a_, each segment with its own operands,
+// timesteps, running / first / momentum, partials region partials[guidance_sums_blocks(rows, C)][5], and in the step its own mode, scale, eta,
+// norm_threshold, mask / clean and scalars_out; sigma / sigma_next are shared.  A segment's blocks index its own partials from 0 and add its own
+// rows in index order, so its partials, running, scalars and output are the single launch's bit for bit at the same access width (16-byte only
+// when both segments allow it; the order of the fp64 sums depends on the width).  The step's segments also take two guiders without sums,
+// which read no partials (NULL) and report no scalars: PROJECTED_CFG, g_out = a + (scale - 1)*(a - b) as guided_euler_step, and PROJECTED_OFF,
+// g_out = a (vel_uncond may be NULL).  sums: a segment with partials == NULL is left out (the other one's single launch); not both.
+constexpr int PROJECTED_CFG = 3, PROJECTED_OFF = 4;
+int guidance_sums_pair_launch(const float* v_x, const float* v_vel_cond, const float* v_vel_uncond, const float* v_ts, long v_ts_stride, float* v_running,
+                              int v_first, float v_momentum, double* v_partials, int v_rows, int v_C, const float* a_x, const float* a_vel_cond,
+                              const float* a_vel_uncond, const float* a_ts, long a_ts_stride, float* a_running, int a_first, float a_momentum,
+                              double* a_partials, int a_rows, int a_C, hipStream_t stream);
+int projected_euler_step_pair_launch(const float* v_x, const float* v_vel_cond, const float* v_vel_uncond, const float* v_ts, long v_ts_stride,
+                                     const float* v_mask, const float* v_clean, const float* v_running, const double* v_partials, int v_mode,
+                                     float v_scale, float v_eta, float v_norm_threshold, float* v_out, float* v_scalars_out, int v_rows, int v_C,
+                                     const float* a_x, const float* a_vel_cond, const float* a_vel_uncond, const float* a_ts, long a_ts_stride,
+                                     const float* a_mask, const float* a_clean, const float* a_running, const double* a_partials, int a_mode,
+                                     float a_scale, float a_eta, float a_norm_threshold, float* a_out, float* a_scalars_out, int a_rows, int a_C,
+                                     float sigma, float sigma_next, hipStream_t stream);
+
 // MultiModalGuider.calculate (reference components/guiders.py:244-273) and the step behind it.  With a = x - t*vc and u, p, m formed the same way from
 // vel_uncond (negative prompt), vel_perturbed (self-attentions skipped) and vel_isolated (cross-modal attentions skipped), each term present exactly
 // when its velocity is non-NULL:

@@ -41,7 +41,8 @@ __global__ void euler_step_kernel(const float* __restrict__ x, const float* __re
 // ---------------------------------- the individually rounded steps: one scaffold ----------------------------------
 // A step is an Op: NIN operands `in` and NOUT operands `out`, all [rows][C], and one(): the arithmetic of one element, a[k] read from in[k] and
 // o[k] stored to out[k], every operation rounded on its own (mul_rn / add_rn / sub_rn) in the order of the torch statements it replaces.  A NULL
-// `in` reads as zeros and a NULL `out` is not stored.  begin() / end() run once per thread around the loop with the thread's State.
+// `in` reads as zeros and a NULL `out` is not stored.  begin() / end() run once per thread around the loop with the thread's State and the block's
+// index within its own grid (a segment's index in a two-segment launch).
 //
 // Aliasing: any `out` may be the same buffer as any `in` (the engine updates the latent in place).  So no [rows][C] operand is __restrict__, and a
 // thread loads its V elements of EVERY operand before it stores any; V divides C, so a vector never straddles a row.
@@ -75,7 +76,7 @@ __device__ __forceinline__ void store(float* p, long e, const float (&v)[V]) {
 template <int V, class Op>
 __device__ __forceinline__ void step_rows(const Op& op, const Rows& r, long block, long blocks) {
     typename Op::State st;
-    op.begin(st);
+    op.begin(st, block);
     const bool blend = r.mask != nullptr;
     const long nv = r.n / V;
     for (long i = block * blockDim.x + threadIdx.x; i < nv; i += blocks * blockDim.x) {
@@ -97,7 +98,7 @@ __device__ __forceinline__ void step_rows(const Op& op, const Rows& r, long bloc
 #pragma unroll
         for (int k = 0; k < Op::NOUT; ++k) store<V>(op.out[k], e, out[k]);
     }
-    op.end(st);
+    op.end(st, block);
 }
 
 template <int V, class Op>
@@ -107,7 +108,7 @@ __global__ __launch_bounds__(BLOCK) void step_rows_kernel(const Op op, const Row
 
 // Two segments in one launch (the video and the audio latent of a joint step; the audio one is ~100 rows, a launch of its own nearly all latency):
 // blocks [0, blocks_a) are the grid of segment a, the rest the grid of segment b.  Each segment's elements see exactly what a launch of its own
-// gives them, so its output is the single launch's bit for bit.  For Ops without begin() / end() work across the block.
+// gives them -- begin() / end() included, which take the block's index within its segment -- so its output is the single launch's bit for bit.
 template <int V, class Op>
 __global__ __launch_bounds__(BLOCK) void step_rows2_kernel(const Op a, const Rows ra, const Op b, const Rows rb, const int blocks_a) {
     if ((int)blockIdx.x < blocks_a) step_rows<V>(a, ra, blockIdx.x, blocks_a);
@@ -117,9 +118,9 @@ __global__ __launch_bounds__(BLOCK) void step_rows2_kernel(const Op a, const Row
 struct StepOp {         // the defaults: no per-thread state, no prologue, no epilogue
     struct State {};
     template <class S>
-    __device__ __forceinline__ void begin(S&) const {}
+    __device__ __forceinline__ void begin(S&, long) const {}
     template <class S>
-    __device__ __forceinline__ void end(S&) const {}
+    __device__ __forceinline__ void end(S&, long) const {}
 };
 
 // The shared formulas.  x0 of one velocity at the row's timestep:
@@ -224,9 +225,9 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
 }
 
 // The N sums of a block in the order every sums pass shares -- per thread in loop order (s), across the wave (xor tree), across the block's waves in
-// order -- into row blockIdx.x of partials[blocks][N]
+// order -- into row `block` of partials[blocks][N]
 template <int N>
-__device__ __forceinline__ void block_sums_store(const double (&s)[N], double* partials) {
+__device__ __forceinline__ void block_sums_store(const double (&s)[N], double* partials, long block) {
     __shared__ double part[WAVES][N];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #pragma unroll
@@ -238,7 +239,7 @@ __device__ __forceinline__ void block_sums_store(const double (&s)[N], double* p
     if (threadIdx.x < N) {
         double acc = part[0][threadIdx.x];
         for (int w = 1; w < WAVES; ++w) acc += part[w][threadIdx.x];
-        partials[(long)blockIdx.x * N + threadIdx.x] = acc;
+        partials[block * N + threadIdx.x] = acc;
     }
 }
 
@@ -264,7 +265,7 @@ struct GuidanceSums : StepOp {
     float* out[NOUT];
     float momentum;
     double* partials;
-    __device__ __forceinline__ void begin(State& st) const {
+    __device__ __forceinline__ void begin(State& st, long) const {
 #pragma unroll
         for (int k = 0; k < NSUM; ++k) st.s[k] = 0.0;
     }
@@ -280,7 +281,7 @@ struct GuidanceSums : StepOp {
         st.s[3] += dg * dg;
         st.s[4] += dg * da;
     }
-    __device__ __forceinline__ void end(State& st) const { block_sums_store<NSUM>(st.s, partials); }
+    __device__ __forceinline__ void end(State& st, long block) const { block_sums_store<NSUM>(st.s, partials, block); }
 };
 
 // g_out of one element from (a, b, g) and the block's fp32 scalars: k0 = coef (mode 0) or sf (modes 1, 2), k1 = proj
@@ -292,7 +293,8 @@ __device__ __forceinline__ float projected_one(int mode, float a, float b, float
 }
 
 // Every block adds the partial rows in index order, so every block holds the same five sums and derives the same scalars; then the guided step
-// with g read from `running` (mode 2 with momentum) or formed as a - b.
+// with g read from `running` (mode 2 with momentum) or formed as a - b.  The two-segment launch also takes a segment whose guider has no sums:
+// PROJECTED_CFG (CFGGuider.guide, GuidedEuler's arithmetic) and PROJECTED_OFF (d = a); such a segment reads no partials and reports no scalars.
 struct ProjectedEuler : StepOp {
     enum { X, VC, VU, CLEAN, RUN, NIN };
     enum { OUT, NOUT };
@@ -303,13 +305,17 @@ struct ProjectedEuler : StepOp {
     float* out[NOUT];
     const double* partials;
     float* scalars_out;
-    int mode;             // 0 CFG*, 1 APG, 2 legacy APG
-    float mult;           // scale - 1 (modes 0, 1) or scale (mode 2)
+    int mode;             // 0 CFG*, 1 APG, 2 legacy APG, PROJECTED_CFG, PROJECTED_OFF
+    float mult;           // scale - 1 (modes 0, 1, PROJECTED_CFG) or scale (mode 2)
     float eta, thr, inv, dt;
     int nb;               // rows of partials
-    __device__ __forceinline__ void begin(State& st) const {
+    __device__ __forceinline__ void begin(State& st, long block) const {
         __shared__ double sums[NSUM];
         __shared__ float sc[2];
+        if (mode >= PROJECTED_CFG) {                                   // the same in every thread of the block: no barrier is skipped by some
+            st.k0 = st.k1 = 0.f;
+            return;
+        }
         partial_rows_sum<NSUM>(partials, nb, sums);
         __syncthreads();
         if (threadIdx.x == 0) {                                        // fp64 throughout, each scalar rounded once
@@ -324,7 +330,7 @@ struct ProjectedEuler : StepOp {
             }
             sc[0] = k0;
             sc[1] = k1;
-            if (blockIdx.x == 0 && scalars_out) {
+            if (block == 0 && scalars_out) {
                 scalars_out[0] = k0;
                 if (mode != 0) scalars_out[1] = k1;
             }
@@ -336,7 +342,7 @@ struct ProjectedEuler : StepOp {
     __device__ __forceinline__ void one(State& st, const Row& r, const float* v, float* o) const {
         const float a = denoised(v[X], v[VC], r.t), b = denoised(v[X], v[VU], r.t);
         const float g = in[RUN] ? v[RUN] : sub_rn(a, b);
-        const float d = projected_one(mode, a, b, g, st.k0, st.k1, mult, eta);
+        const float d = mode == PROJECTED_OFF ? a : mode == PROJECTED_CFG ? guide_from_cond(a, b, mult) : projected_one(mode, a, b, g, st.k0, st.k1, mult, eta);
         o[OUT] = euler(v[X], blend_clean(d, v[CLEAN], r), inv, dt);
     }
 };
@@ -382,7 +388,7 @@ struct MmGuidanceSums : StepOp {
     float* out[NOUT];
     MmTerms k;
     double* partials;
-    __device__ __forceinline__ void begin(State& st) const {
+    __device__ __forceinline__ void begin(State& st, long) const {
 #pragma unroll
         for (int j = 0; j < NMM; ++j) st.s[j] = 0.0;
     }
@@ -396,7 +402,7 @@ struct MmGuidanceSums : StepOp {
         st.s[2] += dp;
         st.s[3] += dp * dp;
     }
-    __device__ __forceinline__ void end(State& st) const { block_sums_store<NMM>(st.s, partials); }
+    __device__ __forceinline__ void end(State& st, long block) const { block_sums_store<NMM>(st.s, partials, block); }
 };
 
 // pass 2: every block adds the partial rows in index order and derives, in fp64, the population variances var = (S2 - S1*S1/n)/n (as mx.var) and
@@ -415,7 +421,7 @@ struct MmRescaledEuler : StepOp {
     double rescale, n;          // rescale_scale; rows * C
     float inv, dt;
     int nb;                     // rows of partials
-    __device__ __forceinline__ void begin(State& st) const {
+    __device__ __forceinline__ void begin(State& st, long block) const {
         __shared__ double sums[NMM];
         __shared__ float sf;
         partial_rows_sum<NMM>(partials, nb, sums);
@@ -423,7 +429,7 @@ struct MmRescaledEuler : StepOp {
         if (threadIdx.x == 0) {
             const double var_a = (sums[1] - sums[0] * sums[0] / n) / n, var_p = (sums[3] - sums[2] * sums[2] / n) / n;
             sf = (float)(rescale * sqrt((var_a + 1e-8) / (var_p + 1e-8)) + (1.0 - rescale));
-            if (blockIdx.x == 0 && scalars_out) scalars_out[0] = sf;
+            if (block == 0 && scalars_out) scalars_out[0] = sf;
         }
         __syncthreads();
         st.f = sf;
@@ -475,17 +481,19 @@ struct Seg {
     int rows, C;
 };
 
-// Both segments are checked as launch_rows checks one, before the one launch; 16-byte accesses only where BOTH segments allow them
+// Both segments are checked as launch_rows checks one, before the one launch; 16-byte accesses only where BOTH segments allow them.
+// sums_a / sums_b: each segment's grid in a sums pass (launch_rows' sums_grid); 0: a step
 template <class Op>
-int launch_rows2(const char* who, bool present, const Op& a, const Seg& sa, const Op& b, const Seg& sb, hipStream_t stream) {
+int launch_rows2(const char* who, bool present, const Op& a, const Seg& sa, const Op& b, const Seg& sb, hipStream_t stream, int sums_a = 0,
+                 int sums_b = 0) {
     if (const int rc = check_rows(who, present, sa.ts, sa.ts_stride, sa.mask, sa.clean, sa.rows, sa.C); rc != LTX2_OK) return rc;
     if (const int rc = check_rows(who, present, sb.ts, sb.ts_stride, sb.mask, sb.clean, sb.rows, sb.C); rc != LTX2_OK) return rc;
     const Rows ra = {sa.ts, sa.ts_stride, sa.mask, (long)sa.rows * sa.C, sa.C}, rb = {sb.ts, sb.ts_stride, sb.mask, (long)sb.rows * sb.C, sb.C};
     if (vec4_ok(a, sa.C) && vec4_ok(b, sb.C)) {
-        const int ga = grid_for(ra.n / 4, BLOCK), gb = grid_for(rb.n / 4, BLOCK);
+        const int ga = sums_a ? sums_a : grid_for(ra.n / 4, BLOCK), gb = sums_b ? sums_b : grid_for(rb.n / 4, BLOCK);
         hipLaunchKernelGGL((step_rows2_kernel<4, Op>), dim3(ga + gb), dim3(BLOCK), 0, stream, a, ra, b, rb, ga);
     } else {
-        const int ga = grid_for(ra.n, BLOCK), gb = grid_for(rb.n, BLOCK);
+        const int ga = sums_a ? sums_a : grid_for(ra.n, BLOCK), gb = sums_b ? sums_b : grid_for(rb.n, BLOCK);
         hipLaunchKernelGGL((step_rows2_kernel<1, Op>), dim3(ga + gb), dim3(BLOCK), 0, stream, a, ra, b, rb, ga);
     }
     LTX2_CHECK_LAUNCH(who);
@@ -604,6 +612,63 @@ int projected_euler_step_launch(const float* x, const float* vel_cond, const flo
     const ProjectedEuler op = {{}, {x, vel_cond, vel_uncond, clean, running}, {out}, partials, scalars_out, mode, mode == 2 ? scale : scale - 1.0f,
                                eta, norm_threshold, 1.0f / sigma, sigma_next - sigma, guidance_sums_blocks(rows, C)};
     return launch_rows("projected_euler_step", x && vel_cond && vel_uncond && partials && out, op, ts, ts_stride, mask, clean, rows, C, 0, stream);
+}
+
+int guidance_sums_pair_launch(const float* v_x, const float* v_vel_cond, const float* v_vel_uncond, const float* v_ts, long v_ts_stride, float* v_running,
+                              int v_first, float v_momentum, double* v_partials, int v_rows, int v_C, const float* a_x, const float* a_vel_cond,
+                              const float* a_vel_uncond, const float* a_ts, long a_ts_stride, float* a_running, int a_first, float a_momentum,
+                              double* a_partials, int a_rows, int a_C, hipStream_t stream) {
+    LTX2_CHECK_ARG(v_partials || a_partials, "guidance_sums_pair: both partials are NULL (a segment without sums passes NULL, not both)");
+    // a segment whose guider reads no sums: the other segment's single launch, which is what its blocks of the pair launch would be
+    if (!a_partials)
+        return guidance_sums_launch(v_x, v_vel_cond, v_vel_uncond, v_ts, v_ts_stride, v_running, v_first, v_momentum, v_partials, v_rows, v_C, stream);
+    if (!v_partials)
+        return guidance_sums_launch(a_x, a_vel_cond, a_vel_uncond, a_ts, a_ts_stride, a_running, a_first, a_momentum, a_partials, a_rows, a_C, stream);
+    LTX2_CHECK_ARG((((uintptr_t)v_partials | (uintptr_t)a_partials) & 7) == 0, "guidance_sums_pair: partials must be 8-byte aligned");
+    const GuidanceSums v = {{}, {v_x, v_vel_cond, v_vel_uncond, v_first ? nullptr : v_running}, {v_running}, v_momentum, v_partials};
+    const GuidanceSums a = {{}, {a_x, a_vel_cond, a_vel_uncond, a_first ? nullptr : a_running}, {a_running}, a_momentum, a_partials};
+    return launch_rows2("guidance_sums_pair", v_x && v_vel_cond && v_vel_uncond && a_x && a_vel_cond && a_vel_uncond, v,
+                        {v_ts, v_ts_stride, nullptr, nullptr, v_rows, v_C}, a, {a_ts, a_ts_stride, nullptr, nullptr, a_rows, a_C}, stream,
+                        guidance_sums_blocks(v_rows, v_C), guidance_sums_blocks(a_rows, a_C));
+}
+
+namespace {
+// one segment of projected_euler_step_pair: the single form's checks, with the two guiders that read no sums admitted
+int projected_segment(const char* seg, const float* vel_uncond, const float* running, const double* partials, int mode, float scale, float eta,
+                      float norm_threshold, float inv, float dt, int rows, int C, ProjectedEuler& op) {
+    LTX2_CHECK_ARG(mode >= 0 && mode <= PROJECTED_OFF, "projected_euler_step_pair: %s mode=%d is 0 (CFG*), 1 (APG), 2 (legacy APG), 3 (CFG) or 4 (off)", seg, mode);
+    LTX2_CHECK_ARG(running == nullptr || mode == 2, "projected_euler_step_pair: only mode 2 (legacy APG with momentum) reads a running buffer (%s)", seg);
+    LTX2_CHECK_ARG(mode >= PROJECTED_CFG || partials, "projected_euler_step_pair: %s mode=%d reads partials", seg, mode);
+    LTX2_CHECK_ARG(((uintptr_t)partials & 7) == 0, "projected_euler_step_pair: partials must be 8-byte aligned");
+    LTX2_CHECK_ARG(mode == PROJECTED_OFF || vel_uncond, "projected_euler_step_pair: null operand or empty shape");
+    op.partials = mode >= PROJECTED_CFG ? nullptr : partials;
+    if (mode >= PROJECTED_CFG) op.scalars_out = nullptr;
+    op.mode = mode;
+    op.mult = mode == 2 ? scale : scale - 1.0f;
+    op.eta = eta;
+    op.thr = norm_threshold;
+    op.inv = inv;
+    op.dt = dt;
+    op.nb = guidance_sums_blocks(rows, C);
+    return LTX2_OK;
+}
+}  // namespace
+
+int projected_euler_step_pair_launch(const float* v_x, const float* v_vel_cond, const float* v_vel_uncond, const float* v_ts, long v_ts_stride,
+                                     const float* v_mask, const float* v_clean, const float* v_running, const double* v_partials, int v_mode,
+                                     float v_scale, float v_eta, float v_norm_threshold, float* v_out, float* v_scalars_out, int v_rows, int v_C,
+                                     const float* a_x, const float* a_vel_cond, const float* a_vel_uncond, const float* a_ts, long a_ts_stride,
+                                     const float* a_mask, const float* a_clean, const float* a_running, const double* a_partials, int a_mode,
+                                     float a_scale, float a_eta, float a_norm_threshold, float* a_out, float* a_scalars_out, int a_rows, int a_C,
+                                     float sigma, float sigma_next, hipStream_t stream) {
+    LTX2_CHECK_ARG(sigma != 0.f, "Sigma can't be 0.0");   // reference core_utils.py:54-55
+    const float inv = 1.0f / sigma, dt = sigma_next - sigma;
+    ProjectedEuler v = {{}, {v_x, v_vel_cond, v_vel_uncond, v_clean, v_running}, {v_out}, nullptr, v_scalars_out};
+    ProjectedEuler a = {{}, {a_x, a_vel_cond, a_vel_uncond, a_clean, a_running}, {a_out}, nullptr, a_scalars_out};
+    if (const int rc = projected_segment("video", v_vel_uncond, v_running, v_partials, v_mode, v_scale, v_eta, v_norm_threshold, inv, dt, v_rows, v_C, v); rc != LTX2_OK) return rc;
+    if (const int rc = projected_segment("audio", a_vel_uncond, a_running, a_partials, a_mode, a_scale, a_eta, a_norm_threshold, inv, dt, a_rows, a_C, a); rc != LTX2_OK) return rc;
+    return launch_rows2("projected_euler_step_pair", v_x && v_vel_cond && v_out && a_x && a_vel_cond && a_out, v,
+                        {v_ts, v_ts_stride, v_mask, v_clean, v_rows, v_C}, a, {a_ts, a_ts_stride, a_mask, a_clean, a_rows, a_C}, stream);
 }
 
 int mm_guided_euler_step_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* vel_perturbed, const float* vel_isolated,

@@ -611,6 +611,57 @@ def projected_euler_step(x: torch.Tensor, vel_cond: torch.Tensor, vel_uncond: to
     return out
 
 
+PAIR_GUIDANCE_MODES = dict(GUIDANCE_MODES, cfg=3, off=4)         # a segment's `mode` in ltx2_projected_euler_step_pair: two guiders without sums on top
+
+
+def guidance_sums_pair(video: dict, audio: dict, dtype: Optional[torch.dtype] = None):
+    """guidance_sums over two latents in ONE launch (ltx2_guidance_sums_pair): `video` and `audio` each hold the single form's operands by name
+    -- x, vel_cond, vel_uncond, timesteps and optionally partials, running, first (True), momentum (0.0).  A segment given as None is left out
+    (its guider reads no sums; not both).  -> (video partials, audio partials), each equal to guidance_sums's bit for bit (None for a segment
+    left out)."""
+    args, parts, held = [], [], []
+    for seg in (video, audio):
+        if seg is None:
+            args += [None, None, None, None, 0, None, 1, 0.0, None, 0, 0]
+            parts.append(None)
+            continue
+        x, vc, vu, running = seg["x"], seg["vel_cond"], seg["vel_uncond"], seg.get("running")
+        part = seg.get("partials")
+        if part is None:
+            part = torch.empty(guidance_sums_blocks(*x.shape, dtype=dtype), 5, device=x.device, dtype=torch.float64)
+        assert vc is not None and vu is not None
+        n, c, ts = _step_operands(x, seg["timesteps"], (vc, vu, running))
+        assert part.dtype == torch.float64 and part.is_contiguous() and part.numel() >= 5 * guidance_sums_blocks(n, c, dtype)
+        args += [nv.ptr(x), nv.ptr(vc), nv.ptr(vu), nv.ptr(ts), 0 if ts.numel() == 1 else 1, nv.ptr(running), int(bool(seg.get("first", True))),
+                 float(seg.get("momentum", 0.0)), nv.ptr(part), n, c]
+        parts.append(part)
+        held.append(ts)          # _step_operands may have made a contiguous fp32 copy: args holds its address only, so it must outlive the launch call
+    nv.check(nv.lib(dtype).ltx2_guidance_sums_pair(*args, nv.stream()))
+    return parts[0], parts[1]
+
+
+def projected_euler_step_pair(video: dict, audio: dict, sigma: float, sigma_next: float, dtype: Optional[torch.dtype] = None):
+    """projected_euler_step over two latents in ONE launch (ltx2_projected_euler_step_pair): `video` and `audio` each hold the single form's
+    operands by name -- x, vel_cond, timesteps, mode, scale and optionally vel_uncond (mode 4 alone does without), partials (modes 0 - 2), eta
+    (1.0), norm_threshold (0.0), mask, clean, running, out, scalars_out.  mode: 0 - 2 as projected_euler_step, 3 = CFGGuider's
+    a + (scale - 1)*(a - b), 4 = not guided.  -> (video out, audio out), each equal to the single-launch step's bit for bit."""
+    args, outs, held = [], [], []
+    for seg in (video, audio):
+        x, vc, vu, mask, clean, running = seg["x"], seg["vel_cond"], seg.get("vel_uncond"), seg.get("mask"), seg.get("clean"), seg.get("running")
+        part, sc, mode = seg.get("partials"), seg.get("scalars_out"), int(seg["mode"])
+        out = seg["out"] if seg.get("out") is not None else torch.empty_like(x)
+        assert vc is not None and (mask is None) == (clean is None)
+        n, c, ts = _step_operands(x, seg["timesteps"], (vc, vu, clean, running, out), mask)
+        assert part is None or (part.dtype == torch.float64 and part.is_contiguous() and part.numel() >= 5 * guidance_sums_blocks(n, c, dtype))
+        assert sc is None or (sc.dtype == torch.float32 and sc.numel() >= 2)
+        args += [nv.ptr(x), nv.ptr(vc), nv.ptr(vu), nv.ptr(ts), 0 if ts.numel() == 1 else 1, nv.ptr(mask), nv.ptr(clean), nv.ptr(running), nv.ptr(part), mode,
+                 float(seg["scale"]), float(seg.get("eta", 1.0)), float(seg.get("norm_threshold", 0.0)), nv.ptr(out), nv.ptr(sc), n, c]
+        outs.append(out)
+        held.append(ts)          # as above
+    nv.check(nv.lib(dtype).ltx2_projected_euler_step_pair(*args, float(sigma), float(sigma_next), nv.stream()))
+    return outs[0], outs[1]
+
+
 def _mm_args(seg: dict, out_key: str = "out"):
     """One latent's operands of the multi-modal guided steps, by name -- x, vel_cond, timesteps and optionally vel_uncond, vel_perturbed,
     vel_isolated, mask, clean, out -- as the C entries take them -> (pointer / stride arguments up to `clean`, out, N, C, the tensors to keep)."""

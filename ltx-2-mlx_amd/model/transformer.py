@@ -909,6 +909,54 @@ class LTXModel:
         """Replay the graph captured by capture_projected_graph (it belongs to the VideoOnly context that ran the capture)."""
         self._replay("projected", "no projected graph captured")
 
+    # ------------------------------------------------------------------ a guider per modality on both latents (AudioVideo engine)
+    @staticmethod
+    def _joint_guider_args(guider: dict, running: Optional[torch.Tensor], latent: torch.Tensor) -> tuple:
+        """One modality's guider of the joint projected step as the C entries take it: (mode, scale, eta, norm_threshold, momentum, running).
+        `guider`: mode (0 - 2 as projected_step_, 3 plain CFG, 4 not guided), scale and optionally eta, norm_threshold, momentum; `running`:
+        the fp32 buffer of `latent`'s shape that mode 2 with momentum keeps its guidance in, None otherwise."""
+        assert running is None or (running.dtype == torch.float32 and running.is_contiguous() and running.shape == latent.shape)
+        return (int(guider["mode"]), float(guider["scale"]), float(guider.get("eta", 1.0)), float(guider.get("norm_threshold", 0.0)),
+                float(guider.get("momentum", 0.0)), running)
+
+    def projected_step_joint_av_(self, neg: "LTXModel", latent: torch.Tensor, audio_latent: torch.Tensor, video: Modality, audio: Modality, sigma: float,
+                                 sigma_next: float, video_guider: dict, audio_guider: dict, first: bool = True,
+                                 running: Optional[torch.Tensor] = None, audio_running: Optional[torch.Tensor] = None,
+                                 denoise_mask: Optional[torch.Tensor] = None, clean_latent: Optional[torch.Tensor] = None,
+                                 audio_denoise_mask: Optional[torch.Tensor] = None, audio_clean_latent: Optional[torch.Tensor] = None) -> None:
+        """In-place on BOTH latents, (N, C) and (Na, Ca) fp32: one guided Euler step of the AudioVideo model with a guider per modality by ONE C
+        call (ltx2_dit_projected_step_joint_av): both modalities through this context and through `neg`, then one sums launch over the
+        modalities whose guider reads sums and one step launch over both latents.  video_guider / audio_guider: dict(mode, scale[, eta,
+        norm_threshold, momentum]) as pipelines.common.projected_guider_args gives it, mode 3 for a plain CFGGuider, mode 4 for none.
+        running / audio_running: the buffer a mode-2 guider with momentum keeps its guidance in; `first` starts it anew."""
+        pos, ng = self._contexts(neg, av=True)
+        ts, n_ts, sg, ats, n_ats = pos._step_inputs(latent, video, sigma, audio_latent, audio)
+        per = [x for *g, run in (self._joint_guider_args(video_guider, running, latent), self._joint_guider_args(audio_guider, audio_running, audio_latent))
+               for x in (*g, nv.ptr(run), 0 if run is None else run.numel())]
+        nv.check(pos._L.ltx2_dit_projected_step_joint_av(pos._h, ng._h, nv.ptr(latent), nv.ptr(audio_latent), nv.ptr(ts), n_ts, nv.ptr(ats), n_ats,
+                                                         nv.ptr(sg), nv.ptr(denoise_mask), nv.ptr(clean_latent), nv.ptr(audio_denoise_mask),
+                                                         nv.ptr(audio_clean_latent), *per, int(bool(first)), float(sigma), float(sigma_next),
+                                                         nv.stream()))
+
+    def capture_projected_joint_graph(self, neg: "LTXModel", latent: torch.Tensor, audio_latent: torch.Tensor, sigmas: Sequence[float],
+                                      video_guider: dict, audio_guider: dict, running: Optional[torch.Tensor] = None,
+                                      audio_running: Optional[torch.Tensor] = None, denoise_mask: Optional[torch.Tensor] = None,
+                                      clean_latent: Optional[torch.Tensor] = None, audio_denoise_mask: Optional[torch.Tensor] = None,
+                                      audio_clean_latent: Optional[torch.Tensor] = None) -> None:
+        """hipGraph-capture len(sigmas)-1 of those steps over both latents, updated in place on replay
+        (ltx2_dit_graph_capture_projected_joint_av); its head clears each running buffer, so every replay is a fresh loop.  Both contexts are
+        prepared first (per_token=True when a mask is given); the graph belongs to this context and replay_projected_joint_graph() replays it.
+        The tensors must stay alive while it is replayed."""
+        pos, ng = self._contexts(neg, av=True)
+        assert audio_latent.dtype == torch.float32 and audio_latent.is_contiguous()
+        self._capture("projected_joint", pos, ng, "ltx2_dit_graph_capture_projected_joint_av", (latent, audio_latent), sigmas,
+                      [(denoise_mask, clean_latent), (audio_denoise_mask, audio_clean_latent)], audio_denoise_mask, audio_clean_latent,
+                      *self._joint_guider_args(video_guider, running, latent), *self._joint_guider_args(audio_guider, audio_running, audio_latent))
+
+    def replay_projected_joint_graph(self) -> None:
+        """Replay the graph captured by capture_projected_joint_graph."""
+        self._replay("projected_joint", "no joint projected graph captured")
+
     # ------------------------------------------------------------------ res_2s second-order sampling (video-only engine)
     def res2s_step_(self, neg: Optional["LTXModel"], latent: torch.Tensor, video: Modality, video_sub: Optional[Modality], sigma: float,
                     sigma_next: float, cfg_scale: float, denoise_mask: Optional[torch.Tensor] = None,

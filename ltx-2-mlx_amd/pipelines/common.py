@@ -538,6 +538,64 @@ def projected_denoise_loop(transformer, video_state: LatentState, sigmas, contex
     return _with_latent(video_state, lat)
 
 
+def joint_guider_args(guider) -> Optional[dict]:
+    """One modality's guider of LTXModel.projected_step_joint_av_: projected_guider_args for the guiders it knows, mode 3 for a plain CFGGuider,
+    mode 4 for a guider that is None or not enabled (whatever its class); None for an enabled guider of any other class."""
+    from ..components.guiders import CFGGuider
+    if guider is None or not guider.enabled():
+        return dict(mode=4, scale=1.0)
+    if type(guider) is CFGGuider:
+        return dict(mode=3, scale=guider.scale)
+    return projected_guider_args(guider)
+
+
+def joint_projected_denoise_loop(transformer, video_state: LatentState, audio_state: LatentState, sigmas, video_context: torch.Tensor,
+                                 audio_context: torch.Tensor, negative_video_context: Optional[torch.Tensor],
+                                 negative_audio_context: Optional[torch.Tensor], video_guider, audio_guider, stepper, callback=None,
+                                 use_hip_graph: bool = True) -> Tuple[LatentState, LatentState]:
+    """joint_guided_denoise_loop with a guider object per modality (the reference's _denoise_loop_cfg_av, pipelines/one_stage.py:466-568, whose
+    default guiders are a CFGStarRescalingGuider each): per step both modalities through the positive and through the negative contexts, then each
+    modality's guider, post_process_latent and the Euler step on both latents.  Every step is ONE C call (LTXModel.projected_step_joint_av_: the
+    evaluations, one sums kernel over the modalities whose guider reads sums, one step kernel over both latents) and with no callback and fewer
+    than 64 steps the whole loop is one captured graph.  Each guider is a CFGGuider, a guider projected_guider_args knows
+    (CFGStarRescalingGuider, LtxAPGGuider, LegacyStatefulAPGGuider) or not enabled; a stateful guider's running guidance lives on the device
+    for the loop and starts cleared.  The sums run over all tokens of a modality, on the device in fp64 (the torch guiders reduce in fp32).
+    When neither guider is enabled, or a negative context is missing, the loop is joint_denoise_loop's; an enabled guider of another class is
+    a ValueError.  `transformer` is an X0Model over an AudioVideo model.  Returns (video_state, audio_state)."""
+    model = transformer.velocity_model
+    if not model.is_av or audio_state is None:
+        raise ValueError("joint_projected_denoise_loop requires an audio-video (AV) model and an audio state")
+    if audio_context is None:
+        raise ValueError("AudioVideo model: audio_encoding (the audio text context) is required")
+    guiders = (video_guider, audio_guider)
+    for g in guiders:
+        reset_guider(g)
+    args = [joint_guider_args(g) for g in guiders]
+    if any(a is None for a in args):
+        raise ValueError("joint_projected_denoise_loop: a guider is a CFGGuider, a CFGStarRescalingGuider, an LtxAPGGuider, a LegacyStatefulAPGGuider or not enabled")
+    if all(a["mode"] == 4 for a in args) or negative_video_context is None or negative_audio_context is None:
+        return joint_denoise_loop(transformer, True, video_state, audio_state, sigmas, video_context, audio_context, stepper, callback, use_hip_graph,
+                                  negative_video_context=negative_video_context, negative_audio_context=negative_audio_context,
+                                  video_guider=video_guider, audio_guider=audio_guider)
+    sig = [float(s) for s in sigmas]
+    n = len(sig) - 1
+    model, uniform, lat, mask, clean = _video_loop_inputs(model, video_state, video_only=False)
+    _, a_uniform, alat, amask, aclean = _video_loop_inputs(model, audio_state, video_only=False)
+    neg = _prepare_contexts(model, True, not (uniform and a_uniform), video_state.positions, video_context, negative_video_context,
+                            audio_state.positions, audio_context, negative_audio_context)
+    run, arun = (torch.zeros_like(t) if a.get("momentum") else None for a, t in zip(args, (lat, alat)))
+    cond = dict(video_guider=args[0], audio_guider=args[1], running=run, audio_running=arun, denoise_mask=mask, clean_latent=clean,
+                audio_denoise_mask=amask, audio_clean_latent=aclean)
+
+    def step(i):
+        st, ast = video_state.replace(latent=lat[None]), audio_state.replace(latent=alat[None])
+        model.projected_step_joint_av_(neg, lat, alat, modality_from_state(st, video_context, sig[i], uniform=uniform),
+                                       audio_modality_from_state(ast, audio_context, sig[i], uniform=a_uniform), sig[i], sig[i + 1], first=(i == 0), **cond)
+
+    _run_steps(n, callback, use_hip_graph, lambda: model.capture_projected_joint_graph(neg, lat, alat, sig, **cond), model.replay_projected_joint_graph, step)
+    return _with_latent(video_state, lat), _with_latent(audio_state, alat)
+
+
 def res2s_denoise_loop(transformer, video_state: LatentState, sigmas, context: torch.Tensor, negative_context: Optional[torch.Tensor],
                        cfg_scale: float, audio_cfg_scale: float = 7.0, callback=None, use_hip_graph: bool = True) -> LatentState:
     """The HQ pipeline's res_2s loop on the video-only model (reference pipelines/ti2vid_hq.py:153-273), without leaving the device: every

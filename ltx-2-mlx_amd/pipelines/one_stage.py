@@ -12,6 +12,11 @@ Classifier-free guidance (round 3): `cfg_scale` / `audio_cfg_scale` != 1 evaluat
 weights) and combine the two predictions with CFGGuider or, for `rescale_scale > 0`, CFGStarRescalingGuider -- per modality, as :793-807.
 `guider_override` (one of CFGGuider, CFGStarRescalingGuider, LtxAPGGuider, LegacyStatefulAPGGuider) becomes the video guider; audio keeps its
 standard one (:795-805).  Without an audio state an enabled projected guider runs through pipelines.common.projected_denoise_loop.
+The joint audio+video branch -- the route of an LTX-2.3 dev checkpoint and of `--generate-audio --model-variant dev`, by default a
+CFGStarRescalingGuider per modality -- stays on the eager loop (two X0Model calls, the guiders in torch).  Its device form exists,
+pipelines.common.joint_projected_denoise_loop (one C call per step: both evaluations, one sums kernel, one step kernel over both latents; one
+captured graph per loop), but measured at the bench geometry it is not faster (profiles/joint_projected_step.md: 204.1 ms per step as C calls
+and 219.6 with the capture against 202.4 eager), so this pipeline does not take it.
 
 Spatio-temporal guidance: `stg_scale` > 0 adds, while (step + 1) / steps <= `stg_cutoff`, a third evaluation of the positive prompt with the video
 self-attention of `stg_blocks` (None: every block) skipped, and STGGuider pushes the guided video prediction away from it (:284-297, :516-526).
