@@ -356,6 +356,48 @@ int ltx2_res2s_combine_pair(const float* v_x_mid, const float* v_vel_cond, const
                             int64_t a_ts_stride, const float* a_mask, const float* a_clean, float a_cfg_scale, const float* a_anchor,
                             const float* a_eps1, float* a_out, int a_rows, int a_C, float h, float b1, float b2, void* stream);
 
+/* The Heun sampler of OneStagePipeline (pipelines/one_stage.py:334-464, components/diffusion_steps.py:132-190) as two passes over [rows][C] fp32,
+ * with the GE velocity correction (:300-307) in the first.  Every operation individually rounded (no FMA contraction), so each equals the separate
+ * fp32 torch ops bit for bit.  With inv = 1/sigma, inv_next = 1/sigma_next, dt = sigma_next - sigma formed in fp32 on the host:
+ * ltx2_heun_predict:
+ *   t = ts[row * ts_stride];  a = x - t*vel_cond;  b = x - t*vel_uncond;  g = a + (cfg_scale - 1)*(a - b)   (g = a when vel_uncond is NULL)
+ *   prev != NULL (GE; goes with ge_gamma > 0):  cur = (x - g)*inv;  first == 0: g = x - (ge_gamma*(cur - prev) + prev)*sigma;  then prev = cur
+ *     (the UNcorrected velocity; first != 0: the old content of prev is not read)
+ *   d = mask ? g*mask[row] + clean*(1 - mask[row]) : g;  xp = x + ((x - d)*inv)*dt
+ *   xp == NULL: the final-step form (sigma_next == 0: the step ends with d), d alone is written.  d == NULL: xp alone, which is the Euler step
+ *   with GE -- ltx2_ge_euler_step is that form, `out` being xp.  d / xp may equal x.
+ * ltx2_heun_correct:  d2 as d, without GE, from (xp, the velocities and ts at sigma_next);  v1 = (x - d)*inv;  v2 = (xp - d2)*inv_next;
+ *   out = x + (0.5*(v1 + v2))*dt.  out may equal any [rows][C] operand.
+ * ts_stride: 0 = one timestep, 1 = one per row.  mask [rows] and clean [rows][C] are both NULL or both set.  16-byte accesses when C % 4 == 0
+ * and every [rows][C] operand is 16-byte aligned, element-wise otherwise.  LTX2_E_INVALID: sigma <= 0, for the corrector sigma_next <= 0,
+ * ge_gamma < 0, a GE state without ge_gamma > 0 or the reverse.
+ * The _pair entries: the same over TWO latents in ONE launch (the video and the audio latent of the joint loop, :570-729), v_ then a_, each
+ * with its own cfg_scale, ts / ts_stride, mask / clean and rows / C; GE acts on the video alone, as the reference keeps prev_velocity for the
+ * video alone.  Each segment's output equals the single entry's bit for bit; 16-byte accesses only when BOTH segments qualify; the
+ * predictor's form (d, xp or both) applies to both segments together.  (additive entries of ABI version 3)                              */
+int ltx2_heun_predict(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, int64_t ts_stride, const float* mask,
+                      const float* clean, float cfg_scale, float ge_gamma, float* prev, int first, float sigma, float sigma_next, float* d, float* xp,
+                      int rows, int C, void* stream);
+int ltx2_heun_correct(const float* x, const float* d, const float* xp, const float* vel_cond, const float* vel_uncond, const float* ts, int64_t ts_stride,
+                      const float* mask, const float* clean, float cfg_scale, float sigma, float sigma_next, float* out, int rows, int C, void* stream);
+int ltx2_ge_euler_step(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, int64_t ts_stride, const float* mask,
+                       const float* clean, float cfg_scale, float ge_gamma, float* prev, int first, float sigma, float sigma_next, float* out, int rows,
+                       int C, void* stream);
+int ltx2_heun_predict_pair(const float* v_x, const float* v_vel_cond, const float* v_vel_uncond, const float* v_ts, int64_t v_ts_stride, const float* v_mask,
+                           const float* v_clean, float v_cfg_scale, float ge_gamma, float* v_prev, int first, float* v_d, float* v_xp, int v_rows, int v_C,
+                           const float* a_x, const float* a_vel_cond, const float* a_vel_uncond, const float* a_ts, int64_t a_ts_stride, const float* a_mask,
+                           const float* a_clean, float a_cfg_scale, float* a_d, float* a_xp, int a_rows, int a_C, float sigma, float sigma_next,
+                           void* stream);
+int ltx2_heun_correct_pair(const float* v_x, const float* v_d, const float* v_xp, const float* v_vel_cond, const float* v_vel_uncond, const float* v_ts,
+                           int64_t v_ts_stride, const float* v_mask, const float* v_clean, float v_cfg_scale, float* v_out, int v_rows, int v_C,
+                           const float* a_x, const float* a_d, const float* a_xp, const float* a_vel_cond, const float* a_vel_uncond, const float* a_ts,
+                           int64_t a_ts_stride, const float* a_mask, const float* a_clean, float a_cfg_scale, float* a_out, int a_rows, int a_C, float sigma,
+                           float sigma_next, void* stream);
+int ltx2_ge_euler_step_pair(const float* v_x, const float* v_vel_cond, const float* v_vel_uncond, const float* v_ts, int64_t v_ts_stride, const float* v_mask,
+                            const float* v_clean, float v_cfg_scale, float ge_gamma, float* v_prev, int first, float* v_out, int v_rows, int v_C,
+                            const float* a_x, const float* a_vel_cond, const float* a_vel_uncond, const float* a_ts, int64_t a_ts_stride, const float* a_mask,
+                            const float* a_clean, float a_cfg_scale, float* a_out, int a_rows, int a_C, float sigma, float sigma_next, void* stream);
+
 /* Guiders whose scalars are sums over the whole latent -- CFGStarRescalingGuider, LtxAPGGuider, LegacyStatefulAPGGuider (components/guiders.py:51-76,
  * 105-205) -- as two passes over [rows][C] fp32.  Every fp32 operation is individually rounded (no FMA contraction); the sums are fp64.
  * ltx2_guidance_sums, per element:
@@ -719,6 +761,39 @@ int ltx2_dit_res2s_step_av(ltx2_dit* ctx, ltx2_dit* neg, float* v_latent, float*
                            const float* a_timesteps, int n_a_timesteps, const float* sigma_dev, const float* v_ts_sub, const float* a_ts_sub,
                            const float* sub_sigma_dev, const float* v_mask, const float* v_clean, const float* a_mask, const float* a_clean,
                            float cfg_scale, float audio_cfg_scale, float sigma, float sigma_next, void* stream);
+/* One Heun step on the VideoOnly engine (pipelines/one_stage.py:366-459 under a CFGGuider, or none), enqueued in order on the caller's stream:
+ * forward(ctx) and forward(neg) from `latent` at `timesteps`, ltx2_heun_predict into workspaces owned by ctx, forward(ctx) and forward(neg) from
+ * the predictor xp at `ts_next` (the timesteps of sigma_next), ltx2_heun_correct into `latent`.  neg may be NULL: no guidance, two evaluations.
+ * sigma_next == 0: the reference's last step, one pair of evaluations and latent = d (ts_next is not read).  ge_gamma > 0: the GE velocity
+ * correction on the first evaluation, its state kept in ctx's workspace; first != 0 starts it (the first step of a loop), first == 0 continues it
+ * and is LTX2_E_STATE unless one of these step entries has run on ctx with ge_gamma > 0 and first != 0 since the workspace was allocated for the
+ * bound shapes (a step without GE, or a capture, allocates it and fills no velocity).  n_timesteps (1 or N) counts both `timesteps` and `ts_next`; sigma_dev /
+ * sigma_next_dev as sigma_dev in ltx2_dit_denoise_step (NULL: the first timestep).  The workspace (3 x N*C fp32; on an AudioVideo context
+ * 2 x Na*Ca more) is allocated on first use for the bound shapes, before anything is enqueued, and freed with ctx.
+ * LTX2_E_INVALID, before anything is launched: the rules of ltx2_dit_guided_step (with neg NULL the same rules on ctx alone), sigma <= 0,
+ * sigma_next < 0, ge_gamma < 0, ts_next missing while sigma_next > 0.
+ * ltx2_dit_heun_step_av: the JOINT step on the AudioVideo engine (:600-724): both latents are stepped, each pass ONE launch over both
+ * (ltx2_heun_predict_pair / ltx2_heun_correct_pair), the video under cfg_scale and the audio under audio_cfg_scale; GE acts on the video alone.
+ * sigma_dev / sigma_next_dev: one float each, shared by the modalities (sigma_next_dev NULL: the first of v_ts_next).  Enqueued eagerly only:
+ * there is no captured form of the joint loop.
+ * ltx2_dit_ge_step: the Euler step with GE on the VideoOnly engine (:267-326): the evaluations of ltx2_dit_guided_step (neg NULL: one), then
+ * ONE ltx2_ge_euler_step in place on `latent`; ge_gamma > 0, `first` as above.
+ * ltx2_dit_graph_capture_heun: n_steps (< 64) Heun steps as one captured linear chain owned by ctx (ltx2_dit_graph_launch(ctx) replays it), built
+ * like ltx2_dit_graph_capture_guided.  sigma_{i+1} is read on the device beside sigma_i; with a mask, mask * sigma_i is formed into ctx's buffer
+ * before the first pair of evaluations and mask * sigma_{i+1} into the same buffer after the predictor.  A step whose sigma_next is 0 takes the
+ * final-step form, decided on the host at capture.  first is 1 in step 0 only, and with ge_gamma > 0 a memset node at the head of the chain
+ * clears the GE velocity, so every replay starts alike.  (additive entries of ABI version 3)                                             */
+int ltx2_dit_heun_step(ltx2_dit* ctx, ltx2_dit* neg, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev,
+                       const float* ts_next, const float* sigma_next_dev, const float* mask, const float* clean, float cfg_scale, float ge_gamma,
+                       int first, float sigma, float sigma_next, void* stream);
+int ltx2_dit_heun_step_av(ltx2_dit* ctx, ltx2_dit* neg, float* v_latent, float* a_latent, const float* v_timesteps, int n_v_timesteps,
+                          const float* a_timesteps, int n_a_timesteps, const float* sigma_dev, const float* v_ts_next, const float* a_ts_next,
+                          const float* sigma_next_dev, const float* v_mask, const float* v_clean, const float* a_mask, const float* a_clean,
+                          float cfg_scale, float audio_cfg_scale, float ge_gamma, int first, float sigma, float sigma_next, void* stream);
+int ltx2_dit_ge_step(ltx2_dit* ctx, ltx2_dit* neg, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev, const float* mask,
+                     const float* clean, float cfg_scale, float ge_gamma, int first, float sigma, float sigma_next, void* stream);
+int ltx2_dit_graph_capture_heun(ltx2_dit* ctx, ltx2_dit* neg, float* latent, const float* host_sigmas, int n_steps, const float* mask, int64_t n_mask,
+                                const float* clean, int64_t n_clean, float cfg_scale, float ge_gamma, void* stream);
 /* One step of the two-stage pipeline's stage 1 on the AudioVideo engine (pipelines/two_stage.py:314-401): BOTH latents are stepped under
  * MultiModalGuider.calculate, each modality with its own scales.  In order on the caller's stream: forward(ctx) and, with neg, forward(neg) on both
  * modalities (as ltx2_dit_guided_step_av builds them); with the perturbed scratch pair, ltx2_dit_forward_perturbed_av on ctx into it; with the

@@ -98,6 +98,15 @@ SIGNATURES = {
                                        vp, vp, vp, vp, i64, vp, vp, f32, vp, vp, vp, i32, i32, f32, i32, vp]),
     "ltx2_res2s_combine_pair": (i32, [vp, vp, vp, vp, i64, vp, vp, f32, vp, vp, vp, i32, i32,
                                       vp, vp, vp, vp, i64, vp, vp, f32, vp, vp, vp, i32, i32, f32, f32, f32, vp]),
+    "ltx2_heun_predict": (i32, [vp, vp, vp, vp, i64, vp, vp, f32, f32, vp, i32, f32, f32, vp, vp, i32, i32, vp]),
+    "ltx2_heun_correct": (i32, [vp, vp, vp, vp, vp, vp, i64, vp, vp, f32, f32, f32, vp, i32, i32, vp]),
+    "ltx2_ge_euler_step": (i32, [vp, vp, vp, vp, i64, vp, vp, f32, f32, vp, i32, f32, f32, vp, i32, i32, vp]),
+    "ltx2_heun_predict_pair": (i32, [vp, vp, vp, vp, i64, vp, vp, f32, f32, vp, i32, vp, vp, i32, i32,
+                                     vp, vp, vp, vp, i64, vp, vp, f32, vp, vp, i32, i32, f32, f32, vp]),
+    "ltx2_heun_correct_pair": (i32, [vp, vp, vp, vp, vp, vp, i64, vp, vp, f32, vp, i32, i32,
+                                     vp, vp, vp, vp, vp, vp, i64, vp, vp, f32, vp, i32, i32, f32, f32, vp]),
+    "ltx2_ge_euler_step_pair": (i32, [vp, vp, vp, vp, i64, vp, vp, f32, f32, vp, i32, vp, i32, i32,
+                                      vp, vp, vp, vp, i64, vp, vp, f32, vp, i32, i32, f32, f32, vp]),
     "ltx2_guidance_sums_blocks": (i32, [i32, i32]),
     "ltx2_guidance_sums": (i32, [vp, vp, vp, vp, i64, vp, i32, f32, vp, i32, i32, vp]),
     "ltx2_projected_euler_step": (i32, [vp, vp, vp, vp, i64, vp, vp, vp, vp, i32, f32, f32, f32, f32, f32, vp, vp, i32, i32, vp]),
@@ -156,6 +165,10 @@ SIGNATURES = {
     "ltx2_dit_res2s_step": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, f32, f32, f32, vp]),
     "ltx2_dit_graph_capture_res2s": (i32, [vp, vp, vp, C.POINTER(f32), i32, vp, i64, vp, i64, f32, vp]),
     "ltx2_dit_res2s_step_av": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, f32, f32, vp]),
+    "ltx2_dit_heun_step": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, f32, f32, i32, f32, f32, vp]),
+    "ltx2_dit_heun_step_av": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, f32, i32, f32, f32, vp]),
+    "ltx2_dit_ge_step": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, f32, f32, i32, f32, f32, vp]),
+    "ltx2_dit_graph_capture_heun": (i32, [vp, vp, vp, C.POINTER(f32), i32, vp, i64, vp, i64, f32, f32, vp]),
     "ltx2_dit_graph_launch": (i32, [vp, vp]),
     "ltx2_dit_set_context_mask": (i32, [vp, i32, vp, i32, vp]),
     "ltx2_dit_set_option": (i32, [vp, C.c_char_p, i32]),

@@ -337,6 +337,55 @@ int ltx2_res2s_combine_pair(const float* v_x_mid, const float* v_vel_cond, const
                                      a_eps1, a_out, a_rows, a_C, h, b1, b2, (hipStream_t)stream);
 }
 
+int ltx2_heun_predict(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, int64_t ts_stride, const float* mask,
+                      const float* clean, float cfg_scale, float ge_gamma, float* prev, int first, float sigma, float sigma_next, float* d, float* xp,
+                      int rows, int C, void* stream) {
+    return heun_predict_launch(x, vel_cond, vel_uncond, ts, (long)ts_stride, mask, clean, cfg_scale, ge_gamma, prev, first, sigma, sigma_next, d, xp, rows, C,
+                               (hipStream_t)stream);
+}
+
+int ltx2_heun_correct(const float* x, const float* d, const float* xp, const float* vel_cond, const float* vel_uncond, const float* ts, int64_t ts_stride,
+                      const float* mask, const float* clean, float cfg_scale, float sigma, float sigma_next, float* out, int rows, int C, void* stream) {
+    return heun_correct_launch(x, d, xp, vel_cond, vel_uncond, ts, (long)ts_stride, mask, clean, cfg_scale, sigma, sigma_next, out, rows, C,
+                               (hipStream_t)stream);
+}
+
+int ltx2_ge_euler_step(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, int64_t ts_stride, const float* mask,
+                       const float* clean, float cfg_scale, float ge_gamma, float* prev, int first, float sigma, float sigma_next, float* out, int rows,
+                       int C, void* stream) {
+    return ge_euler_step_launch(x, vel_cond, vel_uncond, ts, (long)ts_stride, mask, clean, cfg_scale, ge_gamma, prev, first, sigma, sigma_next, out, rows, C,
+                                (hipStream_t)stream);
+}
+
+int ltx2_heun_predict_pair(const float* v_x, const float* v_vel_cond, const float* v_vel_uncond, const float* v_ts, int64_t v_ts_stride, const float* v_mask,
+                           const float* v_clean, float v_cfg_scale, float ge_gamma, float* v_prev, int first, float* v_d, float* v_xp, int v_rows, int v_C,
+                           const float* a_x, const float* a_vel_cond, const float* a_vel_uncond, const float* a_ts, int64_t a_ts_stride, const float* a_mask,
+                           const float* a_clean, float a_cfg_scale, float* a_d, float* a_xp, int a_rows, int a_C, float sigma, float sigma_next,
+                           void* stream) {
+    return heun_predict_pair_launch(v_x, v_vel_cond, v_vel_uncond, v_ts, (long)v_ts_stride, v_mask, v_clean, v_cfg_scale, ge_gamma, v_prev, first, v_d, v_xp,
+                                    v_rows, v_C, a_x, a_vel_cond, a_vel_uncond, a_ts, (long)a_ts_stride, a_mask, a_clean, a_cfg_scale, a_d, a_xp, a_rows, a_C,
+                                    sigma, sigma_next, (hipStream_t)stream);
+}
+
+int ltx2_heun_correct_pair(const float* v_x, const float* v_d, const float* v_xp, const float* v_vel_cond, const float* v_vel_uncond, const float* v_ts,
+                           int64_t v_ts_stride, const float* v_mask, const float* v_clean, float v_cfg_scale, float* v_out, int v_rows, int v_C,
+                           const float* a_x, const float* a_d, const float* a_xp, const float* a_vel_cond, const float* a_vel_uncond, const float* a_ts,
+                           int64_t a_ts_stride, const float* a_mask, const float* a_clean, float a_cfg_scale, float* a_out, int a_rows, int a_C, float sigma,
+                           float sigma_next, void* stream) {
+    return heun_correct_pair_launch(v_x, v_d, v_xp, v_vel_cond, v_vel_uncond, v_ts, (long)v_ts_stride, v_mask, v_clean, v_cfg_scale, v_out, v_rows, v_C, a_x,
+                                    a_d, a_xp, a_vel_cond, a_vel_uncond, a_ts, (long)a_ts_stride, a_mask, a_clean, a_cfg_scale, a_out, a_rows, a_C, sigma,
+                                    sigma_next, (hipStream_t)stream);
+}
+
+int ltx2_ge_euler_step_pair(const float* v_x, const float* v_vel_cond, const float* v_vel_uncond, const float* v_ts, int64_t v_ts_stride, const float* v_mask,
+                            const float* v_clean, float v_cfg_scale, float ge_gamma, float* v_prev, int first, float* v_out, int v_rows, int v_C,
+                            const float* a_x, const float* a_vel_cond, const float* a_vel_uncond, const float* a_ts, int64_t a_ts_stride, const float* a_mask,
+                            const float* a_clean, float a_cfg_scale, float* a_out, int a_rows, int a_C, float sigma, float sigma_next, void* stream) {
+    return ge_euler_step_pair_launch(v_x, v_vel_cond, v_vel_uncond, v_ts, (long)v_ts_stride, v_mask, v_clean, v_cfg_scale, ge_gamma, v_prev, first, v_out,
+                                     v_rows, v_C, a_x, a_vel_cond, a_vel_uncond, a_ts, (long)a_ts_stride, a_mask, a_clean, a_cfg_scale, a_out, a_rows, a_C,
+                                     sigma, sigma_next, (hipStream_t)stream);
+}
+
 int ltx2_guidance_sums_blocks(int rows, int C) { return guidance_sums_blocks(rows, C); }
 
 int ltx2_guidance_sums(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, int64_t ts_stride, float* running, int first,

@@ -115,6 +115,9 @@ struct ltx2_dit {
     float* sigmas_dev = nullptr;       // 64 sigmas of a captured loop, then 64 sub-sigmas (the res_2s loop)
     float* r2s = nullptr;              // res_2s: x_mid | anchor | eps1, three fp32 workspaces allocated on first use, freed with the context
     long r2s_each = 0;                 //   elements of each: [N][Cout], on an AudioVideo context [N][Cout] and [Na][Cout_a] together
+    float* heun = nullptr;             // Heun / GE: the video's prev | d | xp, then on an AudioVideo context the audio's d | xp; fp32, allocated on first use, freed with the context
+    long heun_n = 0;                   //   elements in all: heun_total(c)
+    bool heun_prev = false;            //   a step entry with GE and first != 0 has been enqueued since the workspace was allocated: prev holds a velocity
     double* pg_part = nullptr;         // projected guidance: the sums kernel's partials [pg_rows][5], allocated on first use for the bound N, freed with the context
     int pg_rows = 0;
     float* pg_run = nullptr;           //   and, for the legacy APG guider with momentum only, its running guidance [N][Cout] fp32
@@ -1082,6 +1085,7 @@ void ltx2_dit_destroy(ltx2_dit* c) {
     for (hipEvent_t e : c->sync_ev) (void)hipEventDestroy(e);
     if (c->side) (void)hipStreamDestroy(c->side);
     if (c->r2s) (void)hipFree(c->r2s);
+    if (c->heun) (void)hipFree(c->heun);
     if (c->pg_part) (void)hipFree(c->pg_part);
     if (c->pg_run) (void)hipFree(c->pg_run);
     for (double* p : c->mm_part)
@@ -1659,6 +1663,106 @@ int res2s_step(ltx2_dit* c, ltx2_dit* neg, const ModIn* in, const float* v_ts_su
                                      p.h, p.b1, p.b2, st);
 }
 
+// The Heun sampler and the GE velocity correction of OneStagePipeline (reference pipelines/one_stage.py:300-307, 334-464, 570-729) under a plain CFGGuider
+// or none.  Heun: per step two pairs of evaluations, the second from the Euler predictor xp at sigma_next, and two element-wise passes; when sigma_next == 0
+// one pair and latent = d.  On AudioVideo contexts the JOINT step, each pass one launch over both latents.  GE (ge_gamma > 0) corrects the VIDEO's guided
+// x0 of the first evaluation from the previous step's velocity, kept in the workspace.
+// The workspace: the video's prev | d | xp, then on an AudioVideo context the audio's d | xp, each of heun_each(c, k) elements.  keep_prev: the step
+// continues a GE loop (first == 0), so it is an error unless a step entry with GE and first != 0 has filled prev in this very workspace (a step
+// without GE, or a capture, allocates it and leaves prev unfilled).  Never called while a stream is capturing
+long heun_each(const ltx2_dit* c, int k) { return align_up((long)c->m[k].N * c->m[k].Cout, 64); }
+long heun_total(const ltx2_dit* c) { return 3 * heun_each(c, 0) + (c->av ? 2 * heun_each(c, 1) : 0); }
+
+int heun_workspace(ltx2_dit* c, bool keep_prev) {
+    const long n = heun_total(c);
+    const bool have = c->heun && c->heun_n == n;
+    if (keep_prev && !(have && c->heun_prev)) {
+        ltx2_set_error("dit_heun_step: first == 0 but no step with first != 0 has filled the GE velocity for %d tokens", c->m[0].N);
+        return LTX2_E_STATE;
+    }
+    if (have) return LTX2_OK;
+    if (c->heun) (void)hipFree(c->heun);
+    c->heun = nullptr;
+    c->heun_n = 0;
+    c->heun_prev = false;
+    if (hipMalloc((void**)&c->heun, 4L * n) != hipSuccess) {
+        ltx2_set_error("dit_heun_step: allocating %ld bytes of workspace failed", 4L * n);
+        return LTX2_E_HIP;
+    }
+    c->heun_n = n;
+    return LTX2_OK;
+}
+
+int heun_check(const ltx2_dit* c, const StepIo* io, float ge_gamma, float sigma, float sigma_next, const char* who) {
+    LTX2_CHECK_ARG(sigma > 0.f && sigma_next >= 0.f, "%s: sigma=%g must be > 0 and sigma_next=%g >= 0", who, sigma, sigma_next);
+    LTX2_CHECK_ARG(ge_gamma >= 0.f, "%s: ge_gamma=%g must be >= 0 (0: no GE)", who, ge_gamma);
+    for (int k = 0; k < (c->av ? 2 : 1); ++k) LTX2_CHECK_ARG((io[k].mask == nullptr) == (io[k].clean == nullptr), "%s: mask and clean go together", who);
+    return LTX2_OK;
+}
+
+// in[k]: (latent, timesteps, sigma) of modality k; ts_next / sigma_next_dev: the same at sigma_next.  cond_next: in a captured conditioned loop, the masks
+// from which mask * sigma_next is formed into the buffer `in[k].ts` points at, after the predictor has read it (one stream, in order).  Every check
+// stands before the first launch.
+int heun_step(ltx2_dit* c, ltx2_dit* neg, const ModIn* in, const float* const ts_next_in[2], const float* sigma_next_dev, const Cond* cond_next,
+              const StepIo* io, const float cfg[2], float ge_gamma, int first, float sigma, float sigma_next, hipStream_t st) {
+    const int nm = c->av ? 2 : 1;
+    const bool last = sigma_next == 0.f;
+    TRY(heun_check(c, io, ge_gamma, sigma, sigma_next, "dit_heun_step"));
+    LTX2_CHECK_ARG(c->heun && c->heun_n == heun_total(c), "dit_heun_step: workspace missing");
+    float* const prev = ge_gamma > 0.f ? c->heun : nullptr;
+    float* d[2] = {c->heun + heun_each(c, 0), c->heun + 3 * heun_each(c, 0)};
+    float* xp[2] = {d[0] + heun_each(c, 0), d[1] + (c->av ? heun_each(c, 1) : 0)};
+    const float *ts_next[2] = {ts_next_in[0], ts_next_in[1]}, *vu[2] = {};
+    long stride[2] = {};
+    for (int k = 0; k < nm; ++k) {
+        if (cond_next && cond_next[k].mask) ts_next[k] = c->m[k].ts_tok;
+        LTX2_CHECK_ARG(last || (sigma_next_dev && ts_next[k]), "dit_heun_step: the timesteps of sigma_next are missing");
+        vu[k] = neg ? neg->m[k].vel : nullptr;
+        stride[k] = in[k].n_ts == 1 ? 0 : 1;
+        if (last) {                                         // the step ends with latent = d
+            d[k] = io[k].latent;
+            xp[k] = nullptr;
+        }
+    }
+    const Mod &v = c->m[0], &a = c->m[1];
+    TRY(evaluate(c, neg, in, st));
+    if (nm == 1)
+        TRY(heun_predict_launch(in[0].latent, v.vel, vu[0], in[0].ts, stride[0], io[0].mask, io[0].clean, cfg[0], ge_gamma, prev, first, sigma, sigma_next, d[0],
+                                xp[0], v.N, v.Cout, st));
+    else
+        TRY(heun_predict_pair_launch(in[0].latent, v.vel, vu[0], in[0].ts, stride[0], io[0].mask, io[0].clean, cfg[0], ge_gamma, prev, first, d[0], xp[0], v.N,
+                                     v.Cout, in[1].latent, a.vel, vu[1], in[1].ts, stride[1], io[1].mask, io[1].clean, cfg[1], d[1], xp[1], a.N, a.Cout, sigma,
+                                     sigma_next, st));
+    if (last) return LTX2_OK;
+    ModIn at_next[2] = {};
+    for (int k = 0; k < nm; ++k) {
+        if (cond_next && cond_next[k].mask) {
+            hipLaunchKernelGGL(mask_sigma_kernel, dim3((c->m[k].N + 255) / 256), dim3(256), 0, st, cond_next[k].mask, sigma_next_dev, c->m[k].ts_tok, c->m[k].N);
+            LTX2_CHECK_LAUNCH("mask_sigma_kernel");
+        }
+        at_next[k] = {xp[k], ts_next[k], in[k].n_ts, sigma_next_dev, nullptr};
+    }
+    TRY(evaluate(c, neg, at_next, st));
+    if (nm == 1)
+        return heun_correct_launch(in[0].latent, d[0], xp[0], v.vel, vu[0], ts_next[0], stride[0], io[0].mask, io[0].clean, cfg[0], sigma, sigma_next, io[0].latent,
+                                   v.N, v.Cout, st);
+    return heun_correct_pair_launch(in[0].latent, d[0], xp[0], v.vel, vu[0], ts_next[0], stride[0], io[0].mask, io[0].clean, cfg[0], io[0].latent, v.N, v.Cout,
+                                    in[1].latent, d[1], xp[1], a.vel, vu[1], ts_next[1], stride[1], io[1].mask, io[1].clean, cfg[1], io[1].latent, a.N, a.Cout,
+                                    sigma, sigma_next, st);
+}
+
+// The Euler step with GE on VideoOnly contexts (:267-326): the evaluations of guided_step (neg NULL: one), then ONE element-wise pass
+int ge_step(ltx2_dit* c, ltx2_dit* neg, const ModIn& in, const StepIo& io, float cfg_scale, float ge_gamma, int first, float sigma, float sigma_next,
+            hipStream_t st) {
+    TRY(heun_check(c, &io, ge_gamma, sigma, sigma_next, "dit_ge_step"));
+    LTX2_CHECK_ARG(ge_gamma > 0.f, "dit_ge_step: ge_gamma=%g must be > 0 (without GE the step is ltx2_dit_guided_step or ltx2_dit_denoise_step)", ge_gamma);
+    LTX2_CHECK_ARG(c->heun && c->heun_n == heun_total(c), "dit_ge_step: workspace missing");
+    const Mod& m = c->m[0];
+    TRY(evaluate(c, neg, &in, st));
+    return ge_euler_step_launch(in.latent, m.vel, neg ? neg->m[0].vel : nullptr, in.ts, in.n_ts == 1 ? 0 : 1, io.mask, io.clean, cfg_scale, ge_gamma, c->heun, first,
+                                sigma, sigma_next, io.latent, m.N, m.Cout, st);
+}
+
 // The one captured sampling loop behind every ltx2_dit_graph_capture* entry: per step, sigma_i read on the device, each modality's timesteps (sigma_i, or
 // mask * sigma_i where it is conditioned), then the step that LoopStep names.  All but the plain step run on VideoOnly contexts (latent[0] / cond[0]
 // only), form ts = mask * sigma_i in c's buffer and let both contexts read it; the guided step on AudioVideo contexts steps latent[0] alone and reads
@@ -1676,6 +1780,8 @@ struct LoopStep {                           // all defaults: the plain denoise s
     float audio_cfg_scale = 0.f;
     const Projected* projected_joint = nullptr;     // with joint: each modality under its own guider, [2]
     float* const* running_joint = nullptr;          //   and its running guidance, [2] (NULL where the guider keeps none)
+    bool heun = false;                      // the Heun step under cfg_scale (neg NULL: not guided), with GE where ge_gamma > 0
+    float ge_gamma = 0.f;
 };
 
 int capture_loop(ltx2_dit* c, const LoopStep& step, float* const latent[2], const Cond cond[2], const float* host_sigmas, int n_steps, hipStream_t st) {
@@ -1694,6 +1800,10 @@ int capture_loop(ltx2_dit* c, const LoopStep& step, float* const latent[2], cons
             ltx2_set_error("dit_graph_capture_projected_joint_av: hipMemsetAsync failed");
             rc = LTX2_E_HIP;
         }
+    if (step.heun && step.ge_gamma > 0.f && rc == LTX2_OK && hipMemsetAsync(c->heun, 0, 4L * heun_each(c, 0), st) != hipSuccess) {     // the GE velocity
+        ltx2_set_error("dit_graph_capture_heun: hipMemsetAsync failed");
+        rc = LTX2_E_HIP;
+    }
     for (int i = 0; i < n_steps && rc == LTX2_OK; ++i) {
         const float *s = c->sigmas_dev + i, *ss = c->sigmas_dev + 64 + i;
         const float sigma = host_sigmas[i], sigma_next = host_sigmas[i + 1];
@@ -1708,6 +1818,10 @@ int capture_loop(ltx2_dit* c, const LoopStep& step, float* const latent[2], cons
         if (step.res2s) {
             rc = res2s_step(c, step.neg, in, ss, ss, ss, cond, io, step.cfg_scale, step.cfg_scale, step.res2s[i], st);
             if (step.res2s[i].last) break;                      // the reference's loop ends on its final step
+        } else if (step.heun) {                                 // sigma_{i+1} follows sigma_i on the device; the final-step form where it is 0
+            const float* const next[2] = {s + 1, s + 1};
+            const float cfg[2] = {step.cfg_scale, step.cfg_scale};
+            rc = heun_step(c, step.neg, in, next, s + 1, cond, io, cfg, step.ge_gamma, i == 0, sigma, sigma_next, st);
         } else if (step.projected) {
             rc = projected_step(c, step.neg, in[0], io[0], *step.projected, i == 0, sigma, sigma_next, st);
         } else if (step.stg_vel && i < step.stg_steps) {
@@ -1857,6 +1971,75 @@ int ltx2_dit_res2s_step_av(ltx2_dit* c, ltx2_dit* neg, float* v_latent, float* a
     const ModIn in[2] = {v.in, a.in};
     const StepIo io[2] = {v.io, a.io};
     return res2s_step(c, neg, in, v_ts_sub, a_ts_sub, sub_sigma_dev ? sub_sigma_dev : v_ts_sub, nullptr, io, cfg_scale, audio_cfg_scale, p, (hipStream_t)stream);
+}
+
+int ltx2_dit_heun_step(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev, const float* ts_next,
+                       const float* sigma_next_dev, const float* mask, const float* clean, float cfg_scale, float ge_gamma, int first, float sigma,
+                       float sigma_next, void* stream) {
+    LTX2_CHECK_ARG(latent && timesteps, "dit_heun_step: null argument");
+    const int n_ts[2] = {n_timesteps, 1};
+    TRY(step_ready(c, neg, false, n_ts, "dit_heun_step"));
+    const StepArgs v = step_args(latent, timesteps, n_timesteps, sigma_dev, mask, clean);
+    TRY(heun_check(c, &v.io, ge_gamma, sigma, sigma_next, "dit_heun_step"));
+    LTX2_CHECK_ARG(sigma_next == 0.f || ts_next, "dit_heun_step: ts_next is needed unless sigma_next is 0");
+    TRY(heun_workspace(c, ge_gamma > 0.f && first == 0));
+    const float* const next[2] = {ts_next, nullptr};
+    const float cfg[2] = {cfg_scale, 0.f};
+    TRY(heun_step(c, neg, &v.in, next, sigma_next_dev ? sigma_next_dev : ts_next, nullptr, &v.io, cfg, ge_gamma, first, sigma, sigma_next, (hipStream_t)stream));
+    c->heun_prev = c->heun_prev || (ge_gamma > 0.f && first != 0);
+    return LTX2_OK;
+}
+
+int ltx2_dit_heun_step_av(ltx2_dit* c, ltx2_dit* neg, float* v_latent, float* a_latent, const float* v_timesteps, int n_v_timesteps,
+                          const float* a_timesteps, int n_a_timesteps, const float* sigma_dev, const float* v_ts_next, const float* a_ts_next,
+                          const float* sigma_next_dev, const float* v_mask, const float* v_clean, const float* a_mask, const float* a_clean,
+                          float cfg_scale, float audio_cfg_scale, float ge_gamma, int first, float sigma, float sigma_next, void* stream) {
+    LTX2_CHECK_ARG(v_latent && a_latent && v_timesteps && a_timesteps && sigma_dev, "dit_heun_step_av: null argument");
+    const int n_ts[2] = {n_v_timesteps, n_a_timesteps};
+    TRY(step_ready(c, neg, true, n_ts, "dit_heun_step_av"));
+    const StepArgs v = step_args(v_latent, v_timesteps, n_v_timesteps, sigma_dev, v_mask, v_clean);
+    const StepArgs a = step_args(a_latent, a_timesteps, n_a_timesteps, sigma_dev, a_mask, a_clean);
+    const ModIn in[2] = {v.in, a.in};
+    const StepIo io[2] = {v.io, a.io};
+    TRY(heun_check(c, io, ge_gamma, sigma, sigma_next, "dit_heun_step_av"));
+    LTX2_CHECK_ARG(sigma_next == 0.f || (v_ts_next && a_ts_next), "dit_heun_step_av: v_ts_next and a_ts_next are needed unless sigma_next is 0");
+    TRY(heun_workspace(c, ge_gamma > 0.f && first == 0));
+    const float* const next[2] = {v_ts_next, a_ts_next};
+    const float cfg[2] = {cfg_scale, audio_cfg_scale};
+    TRY(heun_step(c, neg, in, next, sigma_next_dev ? sigma_next_dev : v_ts_next, nullptr, io, cfg, ge_gamma, first, sigma, sigma_next, (hipStream_t)stream));
+    c->heun_prev = c->heun_prev || (ge_gamma > 0.f && first != 0);
+    return LTX2_OK;
+}
+
+int ltx2_dit_ge_step(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev, const float* mask,
+                     const float* clean, float cfg_scale, float ge_gamma, int first, float sigma, float sigma_next, void* stream) {
+    LTX2_CHECK_ARG(latent && timesteps, "dit_ge_step: null argument");
+    const int n_ts[2] = {n_timesteps, 1};
+    TRY(step_ready(c, neg, false, n_ts, "dit_ge_step"));
+    const StepArgs v = step_args(latent, timesteps, n_timesteps, sigma_dev, mask, clean);
+    TRY(heun_check(c, &v.io, ge_gamma, sigma, sigma_next, "dit_ge_step"));
+    LTX2_CHECK_ARG(ge_gamma > 0.f, "dit_ge_step: ge_gamma=%g must be > 0 (without GE the step is ltx2_dit_guided_step or ltx2_dit_denoise_step)", ge_gamma);
+    TRY(heun_workspace(c, first == 0));
+    TRY(ge_step(c, neg, v.in, v.io, cfg_scale, ge_gamma, first, sigma, sigma_next, (hipStream_t)stream));
+    c->heun_prev = c->heun_prev || first != 0;
+    return LTX2_OK;
+}
+
+int ltx2_dit_graph_capture_heun(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* host_sigmas, int n_steps, const float* mask, int64_t n_mask,
+                                const float* clean, int64_t n_clean, float cfg_scale, float ge_gamma, void* stream) {
+    const LoopIo lo = {{latent, nullptr}, {{mask, (long)n_mask, clean, (long)n_clean}, {}}};
+    TRY(capture_ready(c, neg, false, false, lo, host_sigmas, n_steps, "dit_graph_capture_heun"));
+    LTX2_CHECK_ARG(ge_gamma >= 0.f, "dit_graph_capture_heun: ge_gamma=%g must be >= 0 (0: no GE)", ge_gamma);
+    for (int i = 0; i < n_steps; ++i)
+        LTX2_CHECK_ARG(host_sigmas[i] > 0.f && host_sigmas[i + 1] >= 0.f, "dit_graph_capture_heun: sigma=%g must be > 0 and sigma_next=%g >= 0", host_sigmas[i],
+                       host_sigmas[i + 1]);
+    TRY(heun_workspace(c, false));
+    LoopStep step;
+    step.neg = neg;
+    step.cfg_scale = cfg_scale;
+    step.heun = true;
+    step.ge_gamma = ge_gamma;
+    return capture_loop(c, step, lo.lat, lo.cond, host_sigmas, n_steps, (hipStream_t)stream);
 }
 
 int ltx2_dit_mm_guided_step_av(ltx2_dit* c, ltx2_dit* neg, float* v_latent, float* a_latent, const float* v_timesteps, int n_v_timesteps,

@@ -59,6 +59,39 @@ int res2s_combine_pair_launch(const float* v_x_mid, const float* v_vel_cond, con
                               const float* a_clean, float a_cfg_scale, const float* a_anchor, const float* a_eps1, float* a_out, int a_rows, int a_C,
                               float h, float b1, float b2, hipStream_t stream);
 
+// The Heun sampler as two passes (reference pipelines/one_stage.py:334-464), with the GE velocity correction (:300-307) in the first; inv = 1/sigma:
+// predict: a = x - t*vc, b = x - t*vu, g = a + (cfg_scale - 1)*(a - b) (g = a when vu is NULL); with a GE state `prev` (ge_gamma > 0, else NULL):
+//   cur = (x - g)*inv, unless `first` g = x - (ge_gamma*(cur - prev) + prev)*sigma, prev = cur; d = mask ? g*m + clean*(1 - m) : g,
+//   xp = x + ((x - d)*inv)*(sigma_next - sigma); stores d, xp, prev.  xp NULL: the final-step form (sigma_next == 0: the step ends with d), d alone.
+//   d NULL: the Euler step with GE, xp being the new latent (ge_euler_step_launch).
+int heun_predict_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride, const float* mask,
+                        const float* clean, float cfg_scale, float ge_gamma, float* prev, int first, float sigma, float sigma_next, float* d, float* xp,
+                        int rows, int C, hipStream_t stream);
+// correct: d2 = the guided, mask-blended x0 of (xp, vc, vu at sigma_next; ts = its timesteps), v1 = (x - d)*inv, v2 = (xp - d2)*(1/sigma_next),
+//   out = x + (0.5*(v1 + v2))*(sigma_next - sigma)
+int heun_correct_launch(const float* x, const float* d, const float* xp, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride,
+                        const float* mask, const float* clean, float cfg_scale, float sigma, float sigma_next, float* out, int rows, int C,
+                        hipStream_t stream);
+int ge_euler_step_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride, const float* mask,
+                         const float* clean, float cfg_scale, float ge_gamma, float* prev, int first, float sigma, float sigma_next, float* out, int rows,
+                         int C, hipStream_t stream);
+// The three over the video and the audio latent in ONE launch, v_ then a_; GE acts on the video alone (the reference keeps prev_velocity for it only).
+// Each segment's output is the single launch's bit for bit; the predictor's form (d, xp or both) applies to both segments together.
+int heun_predict_pair_launch(const float* v_x, const float* v_vel_cond, const float* v_vel_uncond, const float* v_ts, long v_ts_stride, const float* v_mask,
+                             const float* v_clean, float v_cfg_scale, float ge_gamma, float* v_prev, int first, float* v_d, float* v_xp, int v_rows, int v_C,
+                             const float* a_x, const float* a_vel_cond, const float* a_vel_uncond, const float* a_ts, long a_ts_stride, const float* a_mask,
+                             const float* a_clean, float a_cfg_scale, float* a_d, float* a_xp, int a_rows, int a_C, float sigma, float sigma_next,
+                             hipStream_t stream);
+int heun_correct_pair_launch(const float* v_x, const float* v_d, const float* v_xp, const float* v_vel_cond, const float* v_vel_uncond, const float* v_ts,
+                             long v_ts_stride, const float* v_mask, const float* v_clean, float v_cfg_scale, float* v_out, int v_rows, int v_C,
+                             const float* a_x, const float* a_d, const float* a_xp, const float* a_vel_cond, const float* a_vel_uncond, const float* a_ts,
+                             long a_ts_stride, const float* a_mask, const float* a_clean, float a_cfg_scale, float* a_out, int a_rows, int a_C, float sigma,
+                             float sigma_next, hipStream_t stream);
+int ge_euler_step_pair_launch(const float* v_x, const float* v_vel_cond, const float* v_vel_uncond, const float* v_ts, long v_ts_stride, const float* v_mask,
+                              const float* v_clean, float v_cfg_scale, float ge_gamma, float* v_prev, int first, float* v_out, int v_rows, int v_C,
+                              const float* a_x, const float* a_vel_cond, const float* a_vel_uncond, const float* a_ts, long a_ts_stride, const float* a_mask,
+                              const float* a_clean, float a_cfg_scale, float* a_out, int a_rows, int a_C, float sigma, float sigma_next, hipStream_t stream);
+
 // Guiders whose scalars are sums over the whole latent.  sums: five fp64 sums per block into partials[guidance_sums_blocks(rows, C)][5], and with
 // `running` the momentum update of the guidance; step: every block adds the partial rows in index order, derives the fp32 scalars and runs the
 // guided, mask-blended Euler step.

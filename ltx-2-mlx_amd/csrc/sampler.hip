@@ -2,7 +2,8 @@
 // fp32 torch ops bit for bit -- the classifier-free-guided Euler step (pipelines/one_stage.py:224-330), the same with STG guidance on top, the two passes of the res_2s second-order
 // step (reference pipelines/ti2vid_hq.py:153-273; over one latent, or over the video and the audio latent of the joint step in one launch) and the two passes of the guiders whose scalars are reductions over the whole latent
 // (CFGStarRescalingGuider, LtxAPGGuider, LegacyStatefulAPGGuider; reference components/guiders.py:51-76, 105-205), and the multi-modal guided step
-// (MultiModalGuider.calculate, :244-273: CFG, STG and modality-isolated terms, with or without the variance rescale).  All arithmetic is fp32 and
+// (MultiModalGuider.calculate, :244-273: CFG, STG and modality-isolated terms, with or without the variance rescale), and the two passes of the Heun
+// sampler with the GE velocity correction (pipelines/one_stage.py:300-307, 334-464).  All arithmetic is fp32 and
 // fp64, so the file compiles to the same code in both library builds.  The definitions are written out in include/ltx2hip.h.
 #include <hip/hip_runtime.h>
 
@@ -209,6 +210,47 @@ struct Res2sCombine : StepOp {
         const float d2 = res2s_denoised(r, a[X_MID], a[VC], a[VU], in[VU] != nullptr, cfg, a[CLEAN]);
         const float e2 = sub_rn(d2, a[ANCHOR]);
         o[OUT] = add_rn(a[ANCHOR], mul_rn(h, add_rn(mul_rn(b1, a[EPS1]), mul_rn(b2, e2))));
+    }
+};
+
+// The Heun sampler's first pass (reference pipelines/one_stage.py:334-424), and with no `d` stored the Euler step with the GE velocity correction
+// (:300-326): g as GuidedEuler forms it (g = a with no vu).  GE, where the state `prev` is given (out[PREV_OUT]): cur = (x - g)/sigma, and unless
+// the step is the loop's first (in[PREV] NULL) tot = gamma*(cur - prev) + prev, g = x - tot*sigma; prev = cur, the UNcorrected velocity.  Then
+// d = the mask / clean blend of g and the predictor xp = x + ((x - d)/sigma)*dt, which is GuidedEuler's output.  No xp to store: the final-step
+// form (sigma_next == 0), d alone.
+struct HeunPredict : StepOp {
+    enum { X, VC, VU, CLEAN, PREV, NIN };
+    enum { D, XP, PREV_OUT, NOUT };
+    const float* in[NIN];
+    float* out[NOUT];
+    float s1, inv, dt, sigma, gamma;    // cfg_scale - 1, 1/sigma, sigma_next - sigma, sigma, ge_gamma
+    __device__ __forceinline__ void one(State&, const Row& r, const float* a, float* o) const {
+        float g = denoised(a[X], a[VC], r.t);
+        if (in[VU]) g = guide_from_cond(g, denoised(a[X], a[VU], r.t), s1);
+        if (out[PREV_OUT]) {
+            const float cur = mul_rn(sub_rn(a[X], g), inv);
+            if (in[PREV]) g = sub_rn(a[X], mul_rn(add_rn(mul_rn(gamma, sub_rn(cur, a[PREV])), a[PREV]), sigma));
+            o[PREV_OUT] = cur;
+        }
+        const float d = blend_clean(g, a[CLEAN], r);
+        o[D] = d;
+        o[XP] = euler(a[X], d, inv, dt);
+    }
+};
+
+// The Heun corrector (:426-453; HeunDiffusionStep.step): d2 from (xp, velocities at sigma_next) as above, without GE, v1 = (x - d)/sigma,
+// v2 = (xp - d2)/sigma_next, out = x + (0.5*(v1 + v2))*dt
+struct HeunCorrect : StepOp {
+    enum { X, D, XP, VC, VU, CLEAN, NIN };
+    enum { OUT, NOUT };
+    const float* in[NIN];
+    float* out[NOUT];
+    float s1, inv, inv_next, dt;        // cfg_scale - 1, 1/sigma, 1/sigma_next, sigma_next - sigma
+    __device__ __forceinline__ void one(State&, const Row& r, const float* a, float* o) const {
+        float g = denoised(a[XP], a[VC], r.t);
+        if (in[VU]) g = guide_from_cond(g, denoised(a[XP], a[VU], r.t), s1);
+        const float v1 = mul_rn(sub_rn(a[X], a[D]), inv), v2 = mul_rn(sub_rn(a[XP], blend_clean(g, a[CLEAN], r)), inv_next);
+        o[OUT] = add_rn(a[X], mul_rn(mul_rn(0.5f, add_rn(v1, v2)), dt));
     }
 };
 
@@ -715,4 +757,78 @@ int mm_rescaled_euler_step_launch(const float* x, const float* vel_cond, const f
                                 {cfg_scale - 1.0f, stg_scale, modality_scale - 1.0f}, partials, scalars_out, (double)rescale_scale, (double)rows * C,
                                 1.0f / sigma, sigma_next - sigma, guidance_sums_blocks(rows, C)};
     return launch_rows("mm_rescaled_euler_step", x && vel_cond && partials && out, op, ts, ts_stride, mask, clean, rows, C, 0, stream);
+}
+
+namespace {
+// one segment of the predictor: the checks of its outputs and GE state, and the Op.  d NULL: the Euler step with GE (xp is the new latent)
+int heun_predict_segment(const char* who, const float* x, const float* vel_cond, const float* vel_uncond, const float* clean, float cfg_scale,
+                         float ge_gamma, float* prev, int first, float sigma, float sigma_next, float* d, float* xp, HeunPredict& op) {
+    LTX2_CHECK_ARG(d || xp, "%s: d and xp are both NULL", who);
+    LTX2_CHECK_ARG(ge_gamma >= 0.f && (prev != nullptr) == (ge_gamma > 0.f), "%s: a GE state goes with ge_gamma > 0 (ge_gamma=%g)", who, ge_gamma);
+    op = {{}, {x, vel_cond, vel_uncond, clean, first ? nullptr : prev}, {d, xp, prev}, cfg_scale - 1.0f, 1.0f / sigma, sigma_next - sigma, sigma, ge_gamma};
+    return LTX2_OK;
+}
+}  // namespace
+
+int heun_predict_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride, const float* mask,
+                        const float* clean, float cfg_scale, float ge_gamma, float* prev, int first, float sigma, float sigma_next, float* d, float* xp,
+                        int rows, int C, hipStream_t stream) {
+    LTX2_CHECK_ARG(sigma > 0.f, "heun_predict: sigma=%g must be > 0", sigma);
+    HeunPredict op;
+    if (const int rc = heun_predict_segment("heun_predict", x, vel_cond, vel_uncond, clean, cfg_scale, ge_gamma, prev, first, sigma, sigma_next, d, xp, op); rc != LTX2_OK) return rc;
+    return launch_rows("heun_predict", x && vel_cond, op, ts, ts_stride, mask, clean, rows, C, 0, stream);
+}
+
+int heun_predict_pair_launch(const float* v_x, const float* v_vel_cond, const float* v_vel_uncond, const float* v_ts, long v_ts_stride, const float* v_mask,
+                             const float* v_clean, float v_cfg_scale, float ge_gamma, float* v_prev, int first, float* v_d, float* v_xp, int v_rows, int v_C,
+                             const float* a_x, const float* a_vel_cond, const float* a_vel_uncond, const float* a_ts, long a_ts_stride, const float* a_mask,
+                             const float* a_clean, float a_cfg_scale, float* a_d, float* a_xp, int a_rows, int a_C, float sigma, float sigma_next,
+                             hipStream_t stream) {
+    LTX2_CHECK_ARG(sigma > 0.f, "heun_predict_pair: sigma=%g must be > 0", sigma);
+    LTX2_CHECK_ARG((v_d == nullptr) == (a_d == nullptr) && (v_xp == nullptr) == (a_xp == nullptr),
+                   "heun_predict_pair: the form (d, xp, or both) applies to both segments together");
+    HeunPredict v, a;
+    if (const int rc = heun_predict_segment("heun_predict_pair", v_x, v_vel_cond, v_vel_uncond, v_clean, v_cfg_scale, ge_gamma, v_prev, first, sigma, sigma_next, v_d, v_xp, v); rc != LTX2_OK) return rc;
+    if (const int rc = heun_predict_segment("heun_predict_pair", a_x, a_vel_cond, a_vel_uncond, a_clean, a_cfg_scale, 0.f, nullptr, 1, sigma, sigma_next, a_d, a_xp, a); rc != LTX2_OK) return rc;
+    return launch_rows2("heun_predict_pair", v_x && v_vel_cond && a_x && a_vel_cond, v, {v_ts, v_ts_stride, v_mask, v_clean, v_rows, v_C}, a,
+                        {a_ts, a_ts_stride, a_mask, a_clean, a_rows, a_C}, stream);
+}
+
+int heun_correct_launch(const float* x, const float* d, const float* xp, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride,
+                        const float* mask, const float* clean, float cfg_scale, float sigma, float sigma_next, float* out, int rows, int C,
+                        hipStream_t stream) {
+    LTX2_CHECK_ARG(sigma > 0.f && sigma_next > 0.f, "heun_correct: sigma=%g and sigma_next=%g must be > 0 (sigma_next == 0: the step ends with d)", sigma, sigma_next);
+    const HeunCorrect op = {{}, {x, d, xp, vel_cond, vel_uncond, clean}, {out}, cfg_scale - 1.0f, 1.0f / sigma, 1.0f / sigma_next, sigma_next - sigma};
+    return launch_rows("heun_correct", x && d && xp && vel_cond && out, op, ts, ts_stride, mask, clean, rows, C, 0, stream);
+}
+
+int heun_correct_pair_launch(const float* v_x, const float* v_d, const float* v_xp, const float* v_vel_cond, const float* v_vel_uncond, const float* v_ts,
+                             long v_ts_stride, const float* v_mask, const float* v_clean, float v_cfg_scale, float* v_out, int v_rows, int v_C,
+                             const float* a_x, const float* a_d, const float* a_xp, const float* a_vel_cond, const float* a_vel_uncond, const float* a_ts,
+                             long a_ts_stride, const float* a_mask, const float* a_clean, float a_cfg_scale, float* a_out, int a_rows, int a_C, float sigma,
+                             float sigma_next, hipStream_t stream) {
+    LTX2_CHECK_ARG(sigma > 0.f && sigma_next > 0.f, "heun_correct_pair: sigma=%g and sigma_next=%g must be > 0 (sigma_next == 0: the step ends with d)", sigma, sigma_next);
+    const float inv = 1.0f / sigma, inv_next = 1.0f / sigma_next, dt = sigma_next - sigma;
+    const HeunCorrect v = {{}, {v_x, v_d, v_xp, v_vel_cond, v_vel_uncond, v_clean}, {v_out}, v_cfg_scale - 1.0f, inv, inv_next, dt};
+    const HeunCorrect a = {{}, {a_x, a_d, a_xp, a_vel_cond, a_vel_uncond, a_clean}, {a_out}, a_cfg_scale - 1.0f, inv, inv_next, dt};
+    return launch_rows2("heun_correct_pair", v_x && v_d && v_xp && v_vel_cond && v_out && a_x && a_d && a_xp && a_vel_cond && a_out, v,
+                        {v_ts, v_ts_stride, v_mask, v_clean, v_rows, v_C}, a, {a_ts, a_ts_stride, a_mask, a_clean, a_rows, a_C}, stream);
+}
+
+int ge_euler_step_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride, const float* mask,
+                         const float* clean, float cfg_scale, float ge_gamma, float* prev, int first, float sigma, float sigma_next, float* out, int rows,
+                         int C, hipStream_t stream) {
+    LTX2_CHECK_ARG(out && prev, "ge_euler_step: null operand or empty shape");
+    return heun_predict_launch(x, vel_cond, vel_uncond, ts, ts_stride, mask, clean, cfg_scale, ge_gamma, prev, first, sigma, sigma_next, nullptr, out, rows, C,
+                               stream);
+}
+
+int ge_euler_step_pair_launch(const float* v_x, const float* v_vel_cond, const float* v_vel_uncond, const float* v_ts, long v_ts_stride, const float* v_mask,
+                              const float* v_clean, float v_cfg_scale, float ge_gamma, float* v_prev, int first, float* v_out, int v_rows, int v_C,
+                              const float* a_x, const float* a_vel_cond, const float* a_vel_uncond, const float* a_ts, long a_ts_stride, const float* a_mask,
+                              const float* a_clean, float a_cfg_scale, float* a_out, int a_rows, int a_C, float sigma, float sigma_next, hipStream_t stream) {
+    LTX2_CHECK_ARG(v_out && a_out && v_prev, "ge_euler_step_pair: null operand or empty shape");
+    return heun_predict_pair_launch(v_x, v_vel_cond, v_vel_uncond, v_ts, v_ts_stride, v_mask, v_clean, v_cfg_scale, ge_gamma, v_prev, first, nullptr, v_out,
+                                    v_rows, v_C, a_x, a_vel_cond, a_vel_uncond, a_ts, a_ts_stride, a_mask, a_clean, a_cfg_scale, nullptr, a_out, a_rows, a_C, sigma,
+                                    sigma_next, stream);
 }

@@ -810,6 +810,106 @@ def res2s_combine_pair(video: dict, audio: dict, h: float, b1: float, b2: float,
     return outs[0], outs[1]
 
 
+def heun_predict(x: torch.Tensor, vel_cond: torch.Tensor, vel_uncond: Optional[torch.Tensor], timesteps: torch.Tensor, cfg_scale: float, sigma: float,
+                 sigma_next: float, ge_gamma: float = 0.0, prev: Optional[torch.Tensor] = None, first: bool = True,
+                 mask: Optional[torch.Tensor] = None, clean: Optional[torch.Tensor] = None, d: Optional[torch.Tensor] = None,
+                 xp: Optional[torch.Tensor] = None, final: bool = False, dtype: Optional[torch.dtype] = None):
+    """First pass of a Heun step over fp32 [N, C] (ltx2_heun_predict): the CFG-guided x0 of the two velocities (vel_uncond None: no
+    guidance), the GE velocity correction where `prev` is given (ge_gamma > 0; read unless `first`, then overwritten with the uncorrected
+    velocity), the mask / clean blend `d` and the Euler predictor `xp`, every operation individually rounded.  -> (d, xp); final=True: the
+    sigma_next == 0 form -> (d, None).  d / xp may be `x`.  timesteps: 1 or N elements; `dtype` picks the library build."""
+    d = torch.empty_like(x) if d is None else d
+    xp = None if final else (torch.empty_like(x) if xp is None else xp)
+    assert vel_cond is not None and (mask is None or clean is not None)
+    n, c, timesteps = _step_operands(x, timesteps, (vel_cond, vel_uncond, clean, prev, d, xp), mask)
+    nv.check(nv.lib(dtype).ltx2_heun_predict(nv.ptr(x), nv.ptr(vel_cond), nv.ptr(vel_uncond), nv.ptr(timesteps), 0 if timesteps.numel() == 1 else 1,
+                                             nv.ptr(mask), nv.ptr(clean), float(cfg_scale), float(ge_gamma), nv.ptr(prev), int(bool(first)), float(sigma),
+                                             float(sigma_next), nv.ptr(d), nv.ptr(xp), n, c, nv.stream()))
+    return d, xp
+
+
+def heun_correct(x: torch.Tensor, d: torch.Tensor, xp: torch.Tensor, vel_cond: torch.Tensor, vel_uncond: Optional[torch.Tensor], timesteps: torch.Tensor,
+                 cfg_scale: float, sigma: float, sigma_next: float, mask: Optional[torch.Tensor] = None, clean: Optional[torch.Tensor] = None,
+                 out: Optional[torch.Tensor] = None, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """Second pass of a Heun step (ltx2_heun_correct): d2 from (xp, velocities and timesteps at sigma_next) as in heun_predict without GE,
+    out = x + (0.5*((x - d)/sigma + (xp - d2)/sigma_next))*(sigma_next - sigma), every operation individually rounded.  `out` may be any
+    [N, C] operand."""
+    out = torch.empty_like(x) if out is None else out
+    assert d is not None and xp is not None and vel_cond is not None and (mask is None or clean is not None)
+    n, c, timesteps = _step_operands(x, timesteps, (d, xp, vel_cond, vel_uncond, clean, out), mask)
+    nv.check(nv.lib(dtype).ltx2_heun_correct(nv.ptr(x), nv.ptr(d), nv.ptr(xp), nv.ptr(vel_cond), nv.ptr(vel_uncond), nv.ptr(timesteps),
+                                             0 if timesteps.numel() == 1 else 1, nv.ptr(mask), nv.ptr(clean), float(cfg_scale), float(sigma),
+                                             float(sigma_next), nv.ptr(out), n, c, nv.stream()))
+    return out
+
+
+def ge_euler_step(x: torch.Tensor, vel_cond: torch.Tensor, vel_uncond: Optional[torch.Tensor], timesteps: torch.Tensor, cfg_scale: float, ge_gamma: float,
+                  prev: torch.Tensor, first: bool, sigma: float, sigma_next: float, mask: Optional[torch.Tensor] = None,
+                  clean: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """One guided Euler step with the GE velocity correction over fp32 [N, C] (ltx2_ge_euler_step): heun_predict's pass with the predictor
+    as the new latent.  `prev` (fp32 [N, C]) is read unless `first` and overwritten with the uncorrected velocity; `out` may be `x`."""
+    out = torch.empty_like(x) if out is None else out
+    assert vel_cond is not None and prev is not None and (mask is None or clean is not None)
+    n, c, timesteps = _step_operands(x, timesteps, (vel_cond, vel_uncond, clean, prev, out), mask)
+    nv.check(nv.lib(dtype).ltx2_ge_euler_step(nv.ptr(x), nv.ptr(vel_cond), nv.ptr(vel_uncond), nv.ptr(timesteps), 0 if timesteps.numel() == 1 else 1,
+                                              nv.ptr(mask), nv.ptr(clean), float(cfg_scale), float(ge_gamma), nv.ptr(prev), int(bool(first)), float(sigma),
+                                              float(sigma_next), nv.ptr(out), n, c, nv.stream()))
+    return out
+
+
+def _heun_segment(seg: dict, outputs: tuple):
+    """One latent's operands of the Heun / GE pair launches, by name -> (x, vel_cond, vel_uncond, timesteps, stride, mask, clean pointers,
+    cfg_scale), the output tensors named in `outputs` (made where absent, None where the name maps to None in seg with key present), N, C, ts."""
+    x, vc, vu, mask, clean = seg["x"], seg["vel_cond"], seg.get("vel_uncond"), seg.get("mask"), seg.get("clean")
+    outs = [seg[k] if k in seg else torch.empty_like(x) for k in outputs]
+    assert vc is not None and (mask is None) == (clean is None)
+    n, c, ts = _step_operands(x, seg["timesteps"], (vc, vu, clean, seg.get("prev"), seg.get("d"), seg.get("xp"), *outs), mask)
+    return [nv.ptr(x), nv.ptr(vc), nv.ptr(vu), nv.ptr(ts), 0 if ts.numel() == 1 else 1, nv.ptr(mask), nv.ptr(clean), float(seg["cfg_scale"])], outs, n, c, ts
+
+
+def heun_predict_pair(video: dict, audio: dict, sigma: float, sigma_next: float, ge_gamma: float = 0.0, first: bool = True, final: bool = False,
+                      dtype: Optional[torch.dtype] = None):
+    """heun_predict over two latents in ONE launch (ltx2_heun_predict_pair): `video` and `audio` each hold x, vel_cond, timesteps, cfg_scale
+    and optionally vel_uncond, mask, clean, d, xp; the video alone may hold `prev` (GE acts on it alone).  -> ((d, xp) of the video, the same
+    of the audio), each equal to heun_predict's bit for bit; final=True: xp is None in both."""
+    keep = []
+    if final:
+        video, audio = dict(video, xp=None), dict(audio, xp=None)
+    va, (vd, vxp), vn, vc_, ts = _heun_segment(video, ("d", "xp"))
+    keep.append(ts)
+    aa, (ad, axp), an, ac, ts = _heun_segment(audio, ("d", "xp"))
+    keep.append(ts)
+    nv.check(nv.lib(dtype).ltx2_heun_predict_pair(*va, float(ge_gamma), nv.ptr(video.get("prev")), int(bool(first)), nv.ptr(vd), nv.ptr(vxp), vn, vc_,
+                                                  *aa, nv.ptr(ad), nv.ptr(axp), an, ac, float(sigma), float(sigma_next), nv.stream()))
+    return (vd, vxp), (ad, axp)
+
+
+def heun_correct_pair(video: dict, audio: dict, sigma: float, sigma_next: float, dtype: Optional[torch.dtype] = None):
+    """heun_correct over two latents in ONE launch (ltx2_heun_correct_pair): `video` and `audio` each hold x, d, xp, vel_cond, timesteps,
+    cfg_scale and optionally vel_uncond, mask, clean, out.  -> (video out, audio out), each equal to heun_correct's bit for bit."""
+    args, outs, keep = [], [], []
+    for seg in (video, audio):
+        a, (out,), n, c, ts = _heun_segment(seg, ("out",))
+        assert seg["d"] is not None and seg["xp"] is not None
+        args += [a[0], nv.ptr(seg["d"]), nv.ptr(seg["xp"]), *a[1:], nv.ptr(out), n, c]
+        outs.append(out)
+        keep.append(ts)
+    nv.check(nv.lib(dtype).ltx2_heun_correct_pair(*args, float(sigma), float(sigma_next), nv.stream()))
+    return outs[0], outs[1]
+
+
+def ge_euler_step_pair(video: dict, audio: dict, ge_gamma: float, first: bool, sigma: float, sigma_next: float, dtype: Optional[torch.dtype] = None):
+    """ge_euler_step over the video latent and the plain guided Euler step over the audio latent in ONE launch (ltx2_ge_euler_step_pair):
+    `video` holds x, vel_cond, timesteps, cfg_scale, prev and optionally vel_uncond, mask, clean, out; `audio` the same without prev.
+    -> (video out, audio out), each equal to the single launch's bit for bit."""
+    va, (vout,), vn, vc_, vts = _heun_segment(video, ("out",))
+    aa, (aout,), an, ac, ats = _heun_segment(audio, ("out",))
+    nv.check(nv.lib(dtype).ltx2_ge_euler_step_pair(*va, float(ge_gamma), nv.ptr(video["prev"]), int(bool(first)), nv.ptr(vout), vn, vc_,
+                                                   *aa, nv.ptr(aout), an, ac, float(sigma), float(sigma_next), nv.stream()))
+    del vts, ats
+    return vout, aout
+
+
 def pixnorm_mod_silu(x: torch.Tensor, table: torch.Tensor, te: Optional[torch.Tensor], shift_row: int, scale_row: int,
                      eps: float = 1e-6) -> torch.Tensor:
     assert x.dtype in ACT16

@@ -1015,6 +1015,72 @@ class LTXModel:
                                                nv.ptr(clean_latent), nv.ptr(audio_denoise_mask), nv.ptr(audio_clean_latent), float(cfg_scale),
                                                float(audio_cfg_scale), float(sigma), float(sigma_next), nv.stream()))
 
+    # ------------------------------------------------------------------ Heun sampling and the GE velocity correction (OneStagePipeline)
+    def heun_step_(self, neg: Optional["LTXModel"], latent: torch.Tensor, video: Modality, video_next: Optional[Modality], sigma: float,
+                   sigma_next: float, cfg_scale: float, ge_gamma: float = 0.0, first: bool = True, denoise_mask: Optional[torch.Tensor] = None,
+                   clean_latent: Optional[torch.Tensor] = None) -> None:
+        """In-place: latent (N, C) fp32 <- one Heun step (reference pipelines/one_stage.py:366-459 under a CFGGuider) by ONE C call
+        (ltx2_dit_heun_step): forward(self) and forward(neg) at `video`'s timesteps, the predictor kernel, both again from the predicted
+        latent at `video_next`'s timesteps (those of sigma_next), the corrector kernel.  neg None: no guidance.  video_next may be None only
+        when sigma_next == 0, which is one pair of evaluations and latent = d.  ge_gamma > 0: the GE velocity correction, its state kept by
+        the engine; `first` starts it anew.  Both contexts are prepared by the caller (neg with the negative context)."""
+        pos, ng = self._contexts(neg, optional=True)
+        ts, n_ts, sg = pos._step_inputs(latent, video, sigma)
+        ts_next = sg_next = None
+        if video_next is not None:
+            ts_next, n_next = pos._timesteps(video_next)
+            assert n_next == n_ts, "both evaluations take one timestep, or one per token"
+            if pos.cross_attention_adaln:
+                sg_next = pos._sigma(video_next)
+        nv.check(pos._L.ltx2_dit_heun_step(pos._h, None if ng is None else ng._h, nv.ptr(latent), nv.ptr(ts), n_ts, nv.ptr(sg), nv.ptr(ts_next),
+                                           nv.ptr(sg_next), nv.ptr(denoise_mask), nv.ptr(clean_latent), float(cfg_scale), float(ge_gamma),
+                                           int(bool(first)), float(sigma), float(sigma_next), nv.stream()))
+
+    def capture_heun_graph(self, neg: Optional["LTXModel"], latent: torch.Tensor, sigmas: Sequence[float], cfg_scale: float, ge_gamma: float = 0.0,
+                           denoise_mask: Optional[torch.Tensor] = None, clean_latent: Optional[torch.Tensor] = None) -> None:
+        """hipGraph-capture len(sigmas)-1 Heun steps over `latent` (N, C fp32) as one linear chain (ltx2_dit_graph_capture_heun); with GE its
+        head clears the kept velocity, so every replay is a fresh loop.  Both contexts are prepared first (per_token=True when a mask is
+        given); the graph belongs to the positive VideoOnly context and replay_heun_graph() replays it."""
+        pos, ng = self._contexts(neg, optional=True)
+        self._capture("heun", pos, ng, "ltx2_dit_graph_capture_heun", (latent,), sigmas, [(denoise_mask, clean_latent)], float(cfg_scale), float(ge_gamma))
+
+    def replay_heun_graph(self) -> None:
+        """Replay the graph captured by capture_heun_graph (it belongs to the VideoOnly context that ran the capture)."""
+        self._replay("heun", "no Heun graph captured")
+
+    def heun_step_av_(self, neg: Optional["LTXModel"], latent: torch.Tensor, audio_latent: torch.Tensor, video: Modality, audio: Modality,
+                      video_next: Optional[Modality], audio_next: Optional[Modality], sigma: float, sigma_next: float, cfg_scale: float,
+                      audio_cfg_scale: float, ge_gamma: float = 0.0, first: bool = True, denoise_mask: Optional[torch.Tensor] = None,
+                      clean_latent: Optional[torch.Tensor] = None, audio_denoise_mask: Optional[torch.Tensor] = None,
+                      audio_clean_latent: Optional[torch.Tensor] = None) -> None:
+        """In-place on BOTH latents, (N, C) and (Na, Ca) fp32: one joint Heun step (reference pipelines/one_stage.py:600-724) by ONE C call
+        (ltx2_dit_heun_step_av): each kernel one launch over both latents, the video under cfg_scale and the audio under audio_cfg_scale,
+        GE on the video alone.  The *_next modalities may be None only when sigma_next == 0."""
+        pos, ng = self._contexts(neg, av=True, optional=True)
+        assert (video_next is None) == (audio_next is None), "video_next and audio_next go together (both None: sigma_next == 0)"
+        ts, n_ts, sg, ats, n_ats = pos._step_inputs(latent, video, sigma, audio_latent, audio)
+        ts_next = ats_next = sg_next = None
+        if video_next is not None:
+            ts_next, n_next = pos._timesteps(video_next)
+            ats_next, n_anext = pos._timesteps(audio_next)
+            assert n_next == n_ts and n_anext == n_ats, "both evaluations take one timestep, or one per token"
+            sg_next = pos._sigma(video_next)
+        nv.check(pos._L.ltx2_dit_heun_step_av(pos._h, None if ng is None else ng._h, nv.ptr(latent), nv.ptr(audio_latent), nv.ptr(ts), n_ts,
+                                              nv.ptr(ats), n_ats, nv.ptr(sg), nv.ptr(ts_next), nv.ptr(ats_next), nv.ptr(sg_next), nv.ptr(denoise_mask),
+                                              nv.ptr(clean_latent), nv.ptr(audio_denoise_mask), nv.ptr(audio_clean_latent), float(cfg_scale),
+                                              float(audio_cfg_scale), float(ge_gamma), int(bool(first)), float(sigma), float(sigma_next), nv.stream()))
+
+    def ge_step_(self, neg: Optional["LTXModel"], latent: torch.Tensor, video: Modality, sigma: float, sigma_next: float, cfg_scale: float,
+                 ge_gamma: float, first: bool = True, denoise_mask: Optional[torch.Tensor] = None, clean_latent: Optional[torch.Tensor] = None) -> None:
+        """In-place: latent (N, C) fp32 <- one Euler step with the GE velocity correction (reference pipelines/one_stage.py:267-326 under a
+        CFGGuider; neg None: no guidance) by ONE C call (ltx2_dit_ge_step).  The engine keeps the previous step's velocity; `first` starts it
+        anew."""
+        pos, ng = self._contexts(neg, optional=True)
+        ts, n_ts, sg = pos._step_inputs(latent, video, sigma)
+        nv.check(pos._L.ltx2_dit_ge_step(pos._h, None if ng is None else ng._h, nv.ptr(latent), nv.ptr(ts), n_ts, nv.ptr(sg), nv.ptr(denoise_mask),
+                                         nv.ptr(clean_latent), float(cfg_scale), float(ge_gamma), int(bool(first)), float(sigma), float(sigma_next),
+                                         nv.stream()))
+
     # ------------------------------------------------------------------ multi-modal guidance: CFG + STG + modality isolation (AudioVideo engine)
     def forward_isolated(self, video: Modality, audio: Modality) -> Tuple[torch.Tensor, torch.Tensor]:
         """The modality-isolated forward (ltx2_dit_forward_isolated_av; the reference's SKIP_A2V_CROSS_ATTN + SKIP_V2A_CROSS_ATTN over every

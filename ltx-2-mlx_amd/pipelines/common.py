@@ -673,6 +673,148 @@ def res2s_av_denoise_loop(transformer, video_state: LatentState, audio_state: La
     return _with_latent(video_state, lat), _with_latent(audio_state, alat)
 
 
+def heun_device_form(video_guider, audio_guider=None) -> bool:
+    """Whether the Heun / GE loops can run their device form under these guiders: each a plain CFGGuider, None or not enabled."""
+    from ..components.guiders import CFGGuider
+    return all(g is None or not g.enabled() or type(g) is CFGGuider for g in (video_guider, audio_guider))
+
+
+def _heun_ge_loop(heun: bool, transformer, video_state: LatentState, audio_state: Optional[LatentState], sigmas, video_context: torch.Tensor,
+                  audio_context: Optional[torch.Tensor], negative_video_context: Optional[torch.Tensor], negative_audio_context: Optional[torch.Tensor],
+                  video_guider, audio_guider, ge_gamma: float, callback, use_hip_graph: bool, fused: bool):
+    """heun_denoise_loop (heun=True) and ge_denoise_loop (heun=False)."""
+    from ..components import EulerDiffusionStep, HeunDiffusionStep
+    model = transformer.velocity_model
+    joint = audio_state is not None
+    if joint and not model.is_av:
+        raise ValueError("an audio state needs an audio-video (AV) model")
+    if joint and audio_context is None:
+        raise ValueError("AudioVideo model: audio_encoding (the audio text context) is required")
+    if ge_gamma < 0 or (not heun and not ge_gamma > 0):
+        raise ValueError(f"ge_gamma={ge_gamma}: the GE loop needs ge_gamma > 0, the Heun loop ge_gamma >= 0")
+    sig = [float(s) for s in sigmas]
+    n = len(sig) - 1
+    guiders = [video_guider] + ([audio_guider] if joint else [])
+    need_cfg = any(g is not None and g.enabled() for g in guiders)
+    if need_cfg and (negative_video_context is None or (joint and negative_audio_context is None)):
+        raise ValueError("guidance needs the negative prompt's encoding(s)")
+    for g in guiders:
+        reset_guider(g)
+    if fused:
+        if not heun_device_form(*guiders):
+            raise ValueError("the device form runs under a plain CFGGuider (or none) per modality; call with fused=False for any other guider")
+        if joint and not heun:
+            raise ValueError("Euler + GE has no device form on the joint audio+video loop; call with fused=False")
+        scale = [g.scale if (g is not None and g.enabled()) else 1.0 for g in guiders]
+        model, uniform, lat, mask, clean = _video_loop_inputs(model, video_state, video_only=not joint)
+        cond = dict(denoise_mask=mask, clean_latent=clean)
+        modality = lambda st, ctx, s, u: None if s == 0 else modality_from_state(st, ctx, s, uniform=u)       # noqa: E731  (sigma_next == 0: no second evaluation)
+        if not joint:
+            neg = _prepare_contexts(model, need_cfg, not uniform, video_state.positions, video_context, negative_video_context)
+
+            def step(i):
+                st = video_state.replace(latent=lat[None])
+                vm = modality_from_state(st, video_context, sig[i], uniform=uniform)
+                if heun:
+                    model.heun_step_(neg, lat, vm, modality(st, video_context, sig[i + 1], uniform), sig[i], sig[i + 1], scale[0], ge_gamma, i == 0, **cond)
+                else:
+                    model.ge_step_(neg, lat, vm, sig[i], sig[i + 1], scale[0], ge_gamma, i == 0, **cond)
+
+            capture = (lambda: model.capture_heun_graph(neg, lat, sig, scale[0], ge_gamma, **cond)) if heun else None
+            _run_steps(n, callback, use_hip_graph, capture, model.replay_heun_graph if heun else None, step)
+            return _with_latent(video_state, lat), None
+        _, a_uniform, alat, amask, aclean = _video_loop_inputs(model, audio_state, video_only=False)
+        neg = _prepare_contexts(model, need_cfg, not (uniform and a_uniform), video_state.positions, video_context, negative_video_context,
+                                audio_state.positions, audio_context, negative_audio_context)
+        cond.update(audio_denoise_mask=amask, audio_clean_latent=aclean)
+        if use_hip_graph:
+            _note_eager_once("the joint audio+video Heun loop has no captured form")
+
+        def step(i):
+            st, ast = video_state.replace(latent=lat[None]), audio_state.replace(latent=alat[None])
+            model.heun_step_av_(neg, lat, alat, modality_from_state(st, video_context, sig[i], uniform=uniform),
+                                audio_modality_from_state(ast, audio_context, sig[i], uniform=a_uniform), modality(st, video_context, sig[i + 1], uniform),
+                                modality(ast, audio_context, sig[i + 1], a_uniform), sig[i], sig[i + 1], scale[0], scale[1], ge_gamma, i == 0, **cond)
+
+        _run_steps(n, callback, use_hip_graph, None, None, step)
+        return _with_latent(video_state, lat), _with_latent(audio_state, alat)
+
+    # the eager form: the reference's statements one by one
+    if model.is_av and not joint:
+        model = model._video_twin()
+    pos_model, neg_model = transformer, (X0Model(model.clone_sharing_weights()) if need_cfg else None)
+    states = [video_state] + ([audio_state] if joint else [])
+    contexts, neg_contexts = [video_context, audio_context], [negative_video_context, negative_audio_context]
+    unif = [bool((st.denoise_mask == 1).all()) for st in states]
+    euler, heun_stepper = EulerDiffusionStep(), HeunDiffusionStep()
+    prev_velocity = None
+
+    def denoised(sts, s):
+        """the guided x0 of every state at sigma s, before post_process_latent"""
+        mods = [modality_from_state(st, c, s, uniform=u) for st, c, u in zip(sts, contexts, unif)]
+        out = pos_model(*mods)
+        out = list(out) if isinstance(out, tuple) else [out]
+        if need_cfg:
+            nout = neg_model(*[modality_from_state(st, c, s, uniform=u) for st, c, u in zip(sts, neg_contexts, unif)])
+            nout = list(nout) if isinstance(nout, tuple) else [nout]
+            out = [g.guide(p, q) if g is not None else p for g, p, q in zip(guiders, out, nout)]
+        return out[:len(sts)]
+
+    blend = lambda ds: [post_process_latent(d, st.denoise_mask, st.clean_latent) for d, st in zip(ds, states)]       # noqa: E731
+    for i in range(n):
+        s, sn = sig[i], sig[i + 1]
+        d = denoised(states, s)
+        if ge_gamma > 0 and s > 0:
+            cur = (states[0].latent - d[0]) / s
+            if prev_velocity is not None:
+                d[0] = states[0].latent - (ge_gamma * (cur - prev_velocity) + prev_velocity) * s
+            prev_velocity = cur
+        d = blend(d)
+        if not heun:
+            states = [st.replace(latent=euler.step(sample=st.latent, denoised_sample=x0, sigmas=sig, step_index=i)) for st, x0 in zip(states, d)]
+        elif sn == 0:
+            states = [st.replace(latent=x0) for st, x0 in zip(states, d)]
+        else:
+            predicted = [st.replace(latent=heun_stepper.step(sample=st.latent, denoised_sample=x0, sigmas=sig, step_index=i)) for st, x0 in zip(states, d)]
+            d2 = blend(denoised(predicted, sn))
+            states = [st.replace(latent=heun_stepper.step(sample=st.latent, denoised_sample=x0, sigmas=sig, step_index=i, denoised_at_predicted=x2))
+                      for st, x0, x2 in zip(states, d, d2)]
+        if callback:
+            callback(i + 1, n)
+    return states[0], (states[1] if joint else None)
+
+
+def heun_denoise_loop(transformer, video_state: LatentState, audio_state: Optional[LatentState], sigmas, video_context: torch.Tensor,
+                      audio_context: Optional[torch.Tensor], negative_video_context: Optional[torch.Tensor],
+                      negative_audio_context: Optional[torch.Tensor], video_guider, audio_guider=None, ge_gamma: float = 0.0, callback=None,
+                      use_hip_graph: bool = True, fused: bool = True) -> Tuple[LatentState, Optional[LatentState]]:
+    """OneStagePipeline's Heun loops (the reference's _denoise_loop_heun and _denoise_loop_heun_av, pipelines/one_stage.py:334-464, 570-729): per
+    step the guided x0 at sigma, on the video the GE velocity correction when ge_gamma > 0, post_process_latent, the Euler predictor, and unless
+    sigma_next == 0 (then latent = x0) a second guided evaluation of the predicted latent at sigma_next and HeunDiffusionStep's corrector.
+    audio_state None: the video-only loop (an AudioVideo model through its video twin); otherwise both latents are stepped, each under its own
+    guider, GE on the video alone.  The negative prompt is evaluated when either guider is enabled().
+    fused=True: each guider is a plain CFGGuider, None or not enabled (heun_device_form).  Every step is ONE C call (LTXModel.heun_step_ /
+    heun_step_av_: the evaluations, the predictor and the corrector kernel), the latents held in fp32 across the loop; the video-only loop with
+    no callback and fewer than 64 steps is one captured graph.  The joint loop has no captured form.
+    fused=False: the reference's statements one by one, for any guider: X0Model calls, the torch guiders, post_process_latent and
+    HeunDiffusionStep.  `transformer` is an X0Model.  Returns (video_state, audio_state or None)."""
+    return _heun_ge_loop(True, transformer, video_state, audio_state, sigmas, video_context, audio_context, negative_video_context, negative_audio_context,
+                         video_guider, audio_guider, ge_gamma, callback, use_hip_graph, fused)
+
+
+def ge_denoise_loop(transformer, video_state: LatentState, audio_state: Optional[LatentState], sigmas, video_context: torch.Tensor,
+                    audio_context: Optional[torch.Tensor], negative_video_context: Optional[torch.Tensor],
+                    negative_audio_context: Optional[torch.Tensor], video_guider, audio_guider=None, ge_gamma: float = 0.0, callback=None,
+                    use_hip_graph: bool = True, fused: bool = True) -> Tuple[LatentState, Optional[LatentState]]:
+    """OneStagePipeline's Euler loops with the GE velocity correction (ge_gamma > 0; the reference's _denoise_loop_cfg and _denoise_loop_cfg_av,
+    pipelines/one_stage.py:224-330, 466-568): from the second step on the video's guided x0 is rebuilt from ge_gamma * (v - v_prev) + v_prev.
+    fused=True: the video-only loop under a plain CFGGuider (or none), every step ONE C call (LTXModel.ge_step_); there is no captured form
+    (use_hip_graph changes nothing) and no device form of the joint loop.  fused=False: the reference's statements one by one, for any guider
+    and for the joint loop.  Arguments and result as heun_denoise_loop."""
+    return _heun_ge_loop(False, transformer, video_state, audio_state, sigmas, video_context, audio_context, negative_video_context, negative_audio_context,
+                         video_guider, audio_guider, ge_gamma, callback, use_hip_graph, fused)
+
+
 def multimodal_denoise_loop(transformer, video_state: LatentState, audio_state: LatentState, sigmas, video_context: torch.Tensor,
                             audio_context: torch.Tensor, negative_video_context: Optional[torch.Tensor],
                             negative_audio_context: Optional[torch.Tensor], video_guider, audio_guider, callback=None,

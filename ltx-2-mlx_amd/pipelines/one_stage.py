@@ -24,7 +24,15 @@ Without an audio state and with a plain CFGGuider (or none enabled) the loop is 
 captured graph per loop.  With CFG* (the config default) or a projected override, and on the joint audio+video branch, it is the eager loop:
 three evaluations, the guiders in torch.  Only the video is STG-guided.
 
-Outside the MI355X hot path, rejected with NotImplementedError: any other `guider_override`, the Heun sampler, GE velocity correction, cross-attention scaling, the temporal upscaler.
+`sampler="heun"` runs the reference's predictor-corrector loops (:334-464, :570-729) and `ge_gamma` > 0 its GE velocity correction on the video's
+guided prediction (:300-307), in either sampler.  Under a plain CFGGuider per modality (or none enabled) the loop is
+pipelines.common.heun_denoise_loop / ge_denoise_loop's device form: one C call per step (the two pairs of evaluations, a predictor and a corrector
+kernel), the video-only Heun loop one captured graph; the joint audio+video Heun loop has no captured form, and Euler + GE on the joint branch has no
+device form.  With CFG* (the config default) or a projected override it is the eager form: the reference's statements through X0Model, the torch
+guiders and HeunDiffusionStep.  An unknown `sampler` is a ValueError.
+
+Outside the MI355X hot path, rejected with NotImplementedError: any other `guider_override`, the Heun sampler or GE velocity correction beside STG
+(`stg_scale` > 0), cross-attention scaling, the temporal upscaler.
 With `audio_enabled`, the audio waveform is returned when an audio_decoder and a vocoder are given (model/audio_vae/), the audio
 LATENT otherwise.
 """
@@ -42,7 +50,7 @@ from ..model.transformer import LTXModel, X0Model
 from ..model.video_vae import SimpleVideoDecoder, TilingConfig
 from ..types import AudioLatentShape, VideoPixelShape
 from .common import (ImageCondition, as_x0model, auto_tiling_config, conditioned_initial_state, create_image_conditionings, decode_video,
-                     final_latent, joint_denoise_loop, projected_denoise_loop, projected_guider_args, reset_guider, seeded_noiser, stg_denoise_loop, video_tools_for)
+                     final_latent, ge_denoise_loop, heun_denoise_loop, heun_device_form, joint_denoise_loop, projected_denoise_loop, projected_guider_args, reset_guider, seeded_noiser, stg_denoise_loop, video_tools_for)
 
 
 @dataclass
@@ -150,7 +158,14 @@ class OneStagePipeline:
             if not 0.0 <= stg_cutoff <= 1.0:
                 raise ValueError(f"stg_cutoff={stg_cutoff} must lie in [0, 1]")
             stg_guider = STGGuider(scale=stg_scale)
-        self._require_no_guidance(0.0, guider_override, ge_gamma, sampler, temporal_upscaler, cross_attn_scale)
+        if sampler not in ("euler", "heun"):
+            raise ValueError(f"sampler={sampler!r}: 'euler' or 'heun'")
+        # Heun and GE are built without STG; beside it they stay refused, so the gate sees them only then
+        heun, ge = sampler == "heun", ge_gamma > 0
+        if stg_guider is None:
+            self._require_no_guidance(0.0, guider_override, 0.0, "euler", temporal_upscaler, cross_attn_scale)
+        else:
+            self._require_no_guidance(0.0, guider_override, ge_gamma, sampler, temporal_upscaler, cross_attn_scale)
 
         dev = self.transformer.velocity_model.device
         noiser = seeded_noiser(dev, config.seed)
@@ -185,7 +200,15 @@ class OneStagePipeline:
         if need_cfg and (negative_encoding is None or (internal_audio_active and negative_audio_encoding is None)):
             raise ValueError("cfg_scale / audio_cfg_scale != 1 need the negative prompt's encoding(s)")
         nactx = negative_audio_encoding.to(dev) if (need_cfg and internal_audio_active) else None
-        if stg_guider is not None and audio_state is None and (type(video_guider) is CFGGuider or not video_guider.enabled()):
+        if heun or ge:
+            # on the device under plain CFG (or none); CFG* and the projected overrides through the eager statements.  Euler + GE has no device form
+            # of the joint loop
+            loop = heun_denoise_loop if heun else ge_denoise_loop
+            fused = heun_device_form(video_guider, audio_guider if audio_state is not None else None) and (heun or audio_state is None)
+            video_state, audio_state = loop(self.transformer, video_state, audio_state, sigmas, positive_encoding.to(dev), actx,
+                                            negative_encoding.to(dev) if need_cfg else None, nactx, video_guider,
+                                            audio_guider if audio_state is not None else None, max(float(ge_gamma), 0.0), callback, config.use_hip_graph, fused)
+        elif stg_guider is not None and audio_state is None and (type(video_guider) is CFGGuider or not video_guider.enabled()):
             # forward x 2 or 3 and one kernel per step, on the device
             video_state = stg_denoise_loop(self.transformer, video_state, sigmas, positive_encoding.to(dev),
                                            negative_encoding.to(dev) if video_guider.enabled() else None, video_guider, stg_guider, stg_blocks, stg_cutoff,

@@ -6,8 +6,9 @@ scripts/generate.py (argparse block :2364-2641, `generate_video` :933-997) for t
 standard single-stage distilled loop (reference :1764-1984) followed by `decode_latent` (:2080-2091).
 Gemma-3 encodes the prompt on the GPU when `--gemma-path` holds its weights (model/text_encoder/gemma3.py; reference
 encode_with_gemma :340-486, encode_av_gemma_batch :511-640; an LTX-2.3 checkpoint gets the V2 text encoder, create_av_text_encoder_v2_from_checkpoint
-:548-551).  `--stg-scale S [--stg-blocks ... --stg-cutoff F]` adds spatio-temporal guidance on the av route (OneStagePipeline).  Out of this path (and rejected
-with a clear message): STG guidance on every other route, CFG in the video-only loop, the dev model's `--pipeline two-stage`.
+:548-551).  `--stg-scale S [--stg-blocks ... --stg-cutoff F]` adds spatio-temporal guidance on the av route (OneStagePipeline);
+`--sampler heun` and `--ge-gamma G` run its Heun loop and its GE velocity correction there.  Out of this path (and rejected
+with a clear message): STG guidance, Heun and GE on every other route and Heun / GE beside STG, CFG in the video-only loop, the dev model's `--pipeline two-stage`.
 `generate_video` resolves its arguments once (`_resolve_request`: every refusal, before a model is loaded), loads the text encoding, the transformer and the VAE decoder, and
 runs ONE route, each a function of its own: two_stage_cfg (`--two-stage-cfg --spatial-upscaler-weights W`: TwoStagePipeline, CFG + modality-isolated guidance on the AudioVideo model), hq_av (`--ti2vid-hq-audio --spatial-upscaler-weights W`: TI2VidHQPipeline with sound, the joint res_2s loop on the AudioVideo model), a2vid (`--a2vid-two-stage --audio FILE --spatial-upscaler-weights W`: the two-stage audio-to-video pipeline), retake (`--retake CLIP`), keyframe (`--pipeline keyframe-interpolation --keyframe path:frame[:strength]`), hq (`--ti2vid-hq`), ic_lora
 (`--pipeline ic-lora --control-video V` and / or `--image`), two_stage (`--two-stage-distilled --spatial-upscaler-weights W`; with `--generate-audio` on the AudioVideo transformer), av
@@ -631,9 +632,10 @@ _ROUTE_EXCLUDES = {
                       "alone and ends with its own x2 spatial stage"),
 }
 # route -> the _OUT_OF_PATH_DEFAULTS arguments that route takes itself.  apg_scale: the routes whose guided loop takes a guider (the AudioVideo route as
-# OneStagePipeline's guider_override, keyframe stage 1, retake's guided mode).  stg_scale: OneStagePipeline alone (the AudioVideo route)
+# OneStagePipeline's guider_override, keyframe stage 1, retake's guided mode).  stg_scale and ge_gamma: OneStagePipeline alone (the AudioVideo route), and not
+# together (_check_sampler)
 _ROUTE_OWNS = {"keyframe": ("keyframes", "apg_scale"), "hq": ("distilled_lora", "keyframes"),
-               "ic_lora": ("control_video", "save_control", "keyframes", "ic_lora_weights"), "retake": ("apg_scale",), "av": ("apg_scale", "stg_scale"), "a2vid": ("distilled_lora",),
+               "ic_lora": ("control_video", "save_control", "keyframes", "ic_lora_weights"), "retake": ("apg_scale",), "av": ("apg_scale", "stg_scale", "ge_gamma"), "a2vid": ("distilled_lora",),
                "hq_av": ("distilled_lora",), "two_stage_cfg": ("distilled_lora",),
                "retake_av": ()}          # no guider override on the joint audio+video loop: apg_scale keeps its out-of-path refusal
 
@@ -676,6 +678,17 @@ def _check_stg(r):
         raise ValueError(f"stg_blocks {bad} out of range: the model has {r.num_layers} layers")
     if not 0.0 <= r.stg_cutoff <= 1.0:
         raise ValueError(f"stg_cutoff={r.stg_cutoff} must lie in [0, 1]: the fraction of the steps that STG guides")
+
+
+def _check_sampler(r, owner):
+    """sampler='heun' runs in OneStagePipeline alone (the AudioVideo route), and not beside STG."""
+    if r.sampler == "euler":
+        return
+    if owner != "av":
+        raise NotImplementedError(f"sampler={r.sampler!r} is built on the AudioVideo route alone (OneStagePipeline: generate_audio or an LTX-2.3 checkpoint); "
+                                  "leave it at its default 'euler'")
+    if r.stg_scale > 0:
+        raise NotImplementedError(f"sampler={r.sampler!r} beside stg_scale={r.stg_scale!r} is outside the MI355X hot path (see DESIGN.md)")
 
 
 def _refuse_combinations(r):
@@ -829,7 +842,13 @@ def _resolve_request(kw: dict):
         _resolve_retake_av(r)
     # Gemma encodes the prompt (and the negative prompt) when its weights are there and no pre-computed encoding is given
     r.gemma_encodes = bool(r.use_gemma and not (r.embedding_path or r.text_features_path) and r.gemma_path and os.path.exists(r.gemma_path))
-    owns = _ROUTE_OWNS.get(_owning_route(r) if (r.apg_scale != 1.0 or r.stg_scale != 0.0) else r.route, ())
+    if r.sampler not in ("euler", "heun"):
+        raise ValueError(f"sampler={r.sampler!r}: 'euler' or 'heun'")
+    asks_av = r.apg_scale != 1.0 or r.stg_scale != 0.0 or r.ge_gamma != 0.0 or r.sampler != "euler"
+    owner = _owning_route(r) if asks_av else r.route
+    owns = _ROUTE_OWNS.get(owner, ())
+    if r.stg_scale > 0:
+        owns = tuple(k for k in owns if k != "ge_gamma")          # GE beside STG is not built: its out-of-path refusal
     for k, default in _OUT_OF_PATH_DEFAULTS.items():
         if k in owns or (k == "negative_prompt" and r.gemma_encodes):
             continue
@@ -839,6 +858,7 @@ def _resolve_request(kw: dict):
     if r.pipeline_type not in _PIPELINES_KNOWN:
         raise ValueError(f"unknown pipeline_type {r.pipeline_type!r}; the reference knows {_PIPELINES_KNOWN}")
     _check_stg(r)
+    _check_sampler(r, owner)
     if r.pipeline_type not in _PIPELINES_BUILT and r.route not in _RESOLVE_ROUTE:
         raise NotImplementedError(f"pipeline_type={r.pipeline_type!r} is outside the MI355X hot path (see DESIGN.md): 'two-stage' is the dev "
                                   "model's CFG stage 1 + distilled-LoRA stage 2; for the distilled two-stage DistilledPipeline pass "
@@ -883,6 +903,8 @@ def _resolve_request(kw: dict):
         r.rescale_scale = 0.0 if r.model_variant == "distilled" else 0.7
     if r.stg_scale > 0:
         print(f"STG guidance: scale={r.stg_scale}, mode={r.stg_mode}")           # the settings banner's line (reference :1031-1032); the second one: _run_av
+    if r.sampler == "heun" or r.ge_gamma > 0:
+        print(f"Sampler: {r.sampler}" + (" (2x model evals per step)" if r.sampler == "heun" else "") + (f", GE gamma={r.ge_gamma}" if r.ge_gamma > 0 else ""))
     r.apg_guider = _apg_guider(r)
     r.negative_encoding = r.negative_audio_encoding = None
     if r.embedding_path and os.path.exists(r.embedding_path):
@@ -1423,6 +1445,8 @@ def _run_av(r, s):
     if r.stg_scale > 0:
         print(f"  STG guidance enabled (scale={r.stg_scale})")
         stg = dict(stg_scale=r.stg_scale, stg_blocks=r.stg_blocks, stg_cutoff=r.stg_cutoff)
+    if r.sampler == "heun" or r.ge_gamma > 0:
+        stg.update(sampler=r.sampler, ge_gamma=r.ge_gamma)
     print(f"[5/5] Running audio-video generation ({r.num_steps} steps)...")
     frames, audio_latent = _timed_run("audio-video pipeline", lambda: av_pipeline(
         positive_encoding=s.text_encoding, negative_encoding=s.negative_encoding if r.need_cfg else None, config=av_config, images=images,
@@ -1589,6 +1613,7 @@ def generate_video(
     # MI355X additions (keyword-only; the reference has no counterpart)
     stg_blocks: Optional[List[int]] = None,        # with stg_scale: what OneStagePipeline takes beside it (the reference's CLI leaves them at these defaults)
     stg_cutoff: float = 1.0,
+    sampler: str = "euler",                        # "heun": OneStagePipeline's predictor-corrector loop (the reference's own CLI never reaches it)
     use_hip_graph: bool = True,
     num_layers: int = 48,
     num_heads: int = 32,
@@ -1745,6 +1770,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--retake-audio-cfg", type=float, default=None, help="with --retake-audio: guidance scale of the audio latent (default: --cfg)")
     p.add_argument("--stg-blocks", type=int, nargs="+", default=None, help="with --stg-scale: the blocks whose video self-attention the perturbed pass skips (default: all)")
     p.add_argument("--stg-cutoff", type=float, default=1.0, help="with --stg-scale: STG guides the first fraction of the steps, (step + 1) / steps <= cutoff")
+    p.add_argument("--sampler", type=str, choices=["euler", "heun"], default="euler", help="on the AudioVideo route (OneStagePipeline): heun runs the second-order "
+                   "predictor-corrector loop, two guided evaluations per step; --ge-gamma adds the GE velocity correction to either sampler")
     return p
 
 
@@ -1779,7 +1806,7 @@ def kwargs_from_args(a) -> dict:
         two_stage_cfg=a.two_stage_cfg, modality_scale=a.modality_scale,
         retake_audio=a.retake_audio, retake_audio_cfg=a.retake_audio_cfg,
         retake_video=a.retake, retake_start_time=a.retake_start, retake_end_time=a.retake_end, retake_composite=a.retake_keep_source,
-        stg_blocks=a.stg_blocks, stg_cutoff=a.stg_cutoff)
+        stg_blocks=a.stg_blocks, stg_cutoff=a.stg_cutoff, sampler=a.sampler)
 
 
 def main(argv=None):
