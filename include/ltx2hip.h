@@ -31,6 +31,7 @@ extern "C" {
 #define LTX2_E_INVALID (-1) /* bad argument / unsupported shape  (Python side raises ValueError) */
 #define LTX2_E_HIP (-2)     /* HIP runtime error                   (RuntimeError) */
 #define LTX2_E_STATE (-3)   /* call order, missing weight, small workspace (RuntimeError) */
+#define LTX2_E_UNSUPPORTED (-4) /* a valid request for a form that is not built  (NotImplementedError) */
 
 #define LTX2_DTYPE_BF16 0
 #define LTX2_DTYPE_F32 1
@@ -486,6 +487,27 @@ int ltx2_mm_rescaled_euler_step(const float* x, const float* vel_cond, const flo
                                 float stg_scale, float modality_scale, float rescale_scale, float sigma, float sigma_next, float* out,
                                 float* scalars_out, int rows, int C, void* stream);
 
+/* Classifier-free guidance with the per-channel rescale of the reference's standard one-stage loop (scripts/generate.py:1926-1931, rescale_noise_cfg
+ * :688-727) over fp32 [rows][C] (rows = F*H*W tokens: the reference's [1, C, F, H, W] with statistics over axes 2, 3, 4).  Every fp32 operation is
+ * rounded on its own, in the reference's statement order.  With a = x - t*vc, b = x - t*vu, g = b + cfg_scale*(a - b) (from the unconditional side:
+ * another rounding than ltx2_guided_euler_step's a + (cfg_scale - 1)*(a - b)):
+ * ltx2_channel_guidance_stats: per channel c, over all rows, mean and sqrt(mean((. - mean)^2) + 1e-8) of g[:, c] and of a[:, c], accumulated in
+ *   fp64 and rounded once, into fp32 stats[4][C] = mean_g, std_g, mean_a, std_a.  Two launches and no atomics: per block of rows the sums of
+ *   (v - v0) and (v - v0)^2, v0 the channel's value in row 0, into partials[ltx2_channel_guidance_stats_blocks(rows, C)][4][C] (fp64, 8-byte
+ *   aligned; the last row holds the shifts), then one thread per channel adds the rows in index order: mean = v0 + S1/n,
+ *   var = max((S2 - S1*S1/n)/n, 0).  The result is the same bits from run to run.  DESIGN.md derives the bound against the fp64 two-pass formula.
+ * ltx2_rescaled_guided_euler_step: gr = ((g - mean_g)/std_g)*std_a + mean_a, g' = r*gr + (1 - r)*g with r = fp32(guidance_rescale) and
+ *   (1 - r) = fp32(1 - guidance_rescale), out = x + ((x - g')*(1/sigma))*(sigma_next - sigma).  stats == NULL: g' = g (guidance without rescale, in
+ *   this route's operation order).  out may equal x.  There is no mask / clean operand: the route has no conditioning.
+ * ts_stride, the access width and sigma == 0 as in ltx2_guided_euler_step (stats and partials are read and written element-wise at any width).
+ * (additive entries of ABI version 3)                                                                                                      */
+int ltx2_channel_guidance_stats_blocks(int rows, int C);
+int ltx2_channel_guidance_stats(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, int64_t ts_stride, float cfg_scale,
+                                double* partials, float* stats, int rows, int C, void* stream);
+int ltx2_rescaled_guided_euler_step(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, int64_t ts_stride,
+                                    const float* stats, float cfg_scale, double guidance_rescale, float sigma, float sigma_next, float* out, int rows,
+                                    int C, void* stream);
+
 /* VAE elementwise glue (simple_decoder.py:492-498, 228-238/339-342, ops.py:109-125, :792-798)  */
 int ltx2_vae_prepare_latent(const float* latent, const float* std, const float* mean, const float* noise,
                             float noise_scale, void* out_bf16, int C, int64_t P, void* stream);
@@ -593,6 +615,12 @@ int ltx2_dit_forward_av(ltx2_dit* ctx, const float* v_latent, const float* v_tim
  * its own (the skipped out-projection was the fold's producer); the AudioVideo stream / event schedule is that of the plain forward.
  * (additive entries of ABI version 3)                                                                                                  */
 int ltx2_dit_set_stg_blocks(ltx2_dit* ctx, int modality, const unsigned char* flags, int n_layers);
+/* The reference's set_cross_attn_scale (scripts/generate.py:1174-1176): in every forward of ctx from now on, the output of the text cross-attention of
+ * the layers l >= start_layer enters the residual stream multiplied by `scale` -- a row-invariant gate table of the out-projection's gated-residual
+ * epilogue, no further kernel.  scale == 1 removes it.  Per context: set it on the negative prompt's context as well.  LTX2_E_UNSUPPORTED on a gated
+ * text cross-attention (cross_attention_adaln: LTX-2.3) and on AudioVideo contexts, whose gate is per row.  It synchronises the device (a copy of
+ * the table) and is not for use while a stream is capturing.  (additive entry of ABI version 3)                                            */
+int ltx2_dit_set_cross_attn_scale(ltx2_dit* ctx, float scale, int start_layer);
 int ltx2_dit_forward_perturbed(ltx2_dit* ctx, const float* latent, const float* timesteps, int n_timesteps, const float* sigma,
                                float* velocity, void* stream);
 int ltx2_dit_forward_perturbed_av(ltx2_dit* ctx, const float* v_latent, const float* v_timesteps, int n_v_timesteps,
@@ -645,6 +673,15 @@ int ltx2_dit_guided_step(ltx2_dit* ctx, ltx2_dit* neg, float* latent, const floa
  * belongs to ctx: ltx2_dit_graph_launch(ctx) replays it.                                                                               */
 int ltx2_dit_graph_capture_guided(ltx2_dit* ctx, ltx2_dit* neg, float* latent, const float* host_sigmas, int n_steps,
                                   const float* mask, int64_t n_mask, const float* clean, int64_t n_clean, float cfg_scale, void* stream);
+/* ltx2_dit_guided_step in the standard one-stage loop's form (scripts/generate.py:1895-1976): forward(ctx), forward(neg), with guidance_rescale > 0
+ * ltx2_channel_guidance_stats into ctx's own workspace (allocated before anything is enqueued, for the bound shape, and freed with ctx), then
+ * ltx2_rescaled_guided_euler_step in place on `latent`.  No mask / clean: that loop has no conditioning.  Validity as ltx2_dit_guided_step.
+ * ltx2_dit_graph_capture_rescaled_guided: n_steps of it as one captured linear chain owned by ctx, with uniform timesteps sigma_i.
+ * (additive entries of ABI version 3)                                                                                                      */
+int ltx2_dit_rescaled_guided_step(ltx2_dit* ctx, ltx2_dit* neg, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev,
+                                  float cfg_scale, double guidance_rescale, float sigma, float sigma_next, void* stream);
+int ltx2_dit_graph_capture_rescaled_guided(ltx2_dit* ctx, ltx2_dit* neg, float* latent, const float* host_sigmas, int n_steps, float cfg_scale,
+                                           double guidance_rescale, void* stream);
 /* One STG step on the VideoOnly engine (pipelines/one_stage.py:267-326 with a CFGGuider and an STGGuider): forward(ctx), forward(neg) when neg is
  * given (NULL: no CFG), a perturbed forward on ctx ITSELF (ltx2_dit_forward_perturbed: the set of ltx2_dit_set_stg_blocks) into vel_perturbed, the
  * caller's [N][out_channels] fp32 scratch, then ltx2_stg_euler_step in place on `latent` -- in order on the caller's stream.  There is no third

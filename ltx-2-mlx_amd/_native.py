@@ -19,7 +19,7 @@ LIB_PATH = os.environ.get("LTX2HIP_LIB") or os.path.join(_HERE, "lib", "libltx2h
 LIB_PATH_F16 = os.environ.get("LTX2HIP_LIB_F16") or os.path.join(_HERE, "lib", "libltx2hip_f16.so")
 
 ABI_VERSION = 3         # LTX2_ABI_VERSION of include/ltx2hip.h these signatures were written against
-OK, E_INVALID, E_HIP, E_STATE = 0, -1, -2, -3
+OK, E_INVALID, E_HIP, E_STATE, E_UNSUPPORTED = 0, -1, -2, -3, -4
 DTYPE_BF16, DTYPE_F32, DTYPE_FP8_E4M3FN = 0, 1, 2
 MODEL_VIDEO_ONLY, MODEL_AUDIO_VIDEO = 0, 1
 EPI_BF16, EPI_GELU_BF16, EPI_SILU_BF16, EPI_F32, EPI_RESID_GATE_F32, EPI_ADD_BF16 = range(6)
@@ -118,6 +118,9 @@ SIGNATURES = {
                                              vp, vp, vp, vp, vp, vp, i64, vp, vp, f32, f32, f32, vp, i32, i32, f32, f32, vp]),
     "ltx2_mm_guidance_sums": (i32, [vp, vp, vp, vp, vp, vp, i64, f32, f32, f32, vp, vp, i32, i32, vp]),
     "ltx2_mm_rescaled_euler_step": (i32, [vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, f32, f32, f32, f32, f32, f32, vp, vp, i32, i32, vp]),
+    "ltx2_channel_guidance_stats_blocks": (i32, [i32, i32]),
+    "ltx2_channel_guidance_stats": (i32, [vp, vp, vp, vp, i64, f32, vp, vp, i32, i32, vp]),
+    "ltx2_rescaled_guided_euler_step": (i32, [vp, vp, vp, vp, i64, vp, f32, C.c_double, f32, f32, vp, i32, i32, vp]),
     "ltx2_vae_prepare_latent": (i32, [vp, vp, vp, vp, f32, vp, i32, i64, vp]),
     "ltx2_pixnorm_mod_silu": (i32, [vp, vp, i64, i32, f32, vp, vp, i32, i32, vp]),
     "ltx2_vae_unpatchify": (i32, [vp, vp, i32, i32, i32, vp]),
@@ -139,6 +142,7 @@ SIGNATURES = {
     "ltx2_dit_graph_capture_av": (i32, [vp, vp, vp, C.POINTER(f32), i32, vp]),
     "ltx2_dit_forward": (i32, [vp, vp, vp, i32, vp, vp, vp]),
     "ltx2_dit_set_stg_blocks": (i32, [vp, i32, C.c_char_p, i32]),
+    "ltx2_dit_set_cross_attn_scale": (i32, [vp, f32, i32]),
     "ltx2_dit_forward_perturbed": (i32, [vp, vp, vp, i32, vp, vp, vp]),
     "ltx2_dit_forward_perturbed_av": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp]),
     "ltx2_dit_forward_isolated_av": (i32, [vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp]),
@@ -152,6 +156,8 @@ SIGNATURES = {
     "ltx2_dit_graph_capture_cond_av": (i32, [vp, vp, vp, C.POINTER(f32), i32, vp, i64, vp, i64, vp, i64, vp, i64, vp]),
     "ltx2_dit_guided_step": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, f32, f32, f32, vp]),
     "ltx2_dit_graph_capture_guided": (i32, [vp, vp, vp, C.POINTER(f32), i32, vp, i64, vp, i64, f32, vp]),
+    "ltx2_dit_rescaled_guided_step": (i32, [vp, vp, vp, vp, i32, vp, f32, C.c_double, f32, f32, vp]),
+    "ltx2_dit_graph_capture_rescaled_guided": (i32, [vp, vp, vp, C.POINTER(f32), i32, f32, C.c_double, vp]),
     "ltx2_dit_guided_step_av": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, f32, f32, f32, vp]),
     "ltx2_dit_graph_capture_guided_av": (i32, [vp, vp, vp, vp, C.POINTER(f32), i32, vp, i64, vp, i64, vp, i64, f32, vp]),
     "ltx2_dit_guided_step_joint_av": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, f32, f32, f32, f32, vp]),
@@ -264,12 +270,14 @@ def last_error() -> str:
 
 def check(rc: int) -> None:
     """Map C-ABI status codes onto the exception types the reference raises (ValueError
-    for bad arguments such as sigma == 0; RuntimeError otherwise)."""
+    for bad arguments such as sigma == 0; NotImplementedError for a form that is not built; RuntimeError otherwise)."""
     if rc == OK:
         return
     msg = last_error()
     if rc == E_INVALID:
         raise ValueError(msg)
+    if rc == E_UNSUPPORTED:
+        raise NotImplementedError(msg)
     raise RuntimeError(f"libltx2hip error {rc}: {msg}")
 
 

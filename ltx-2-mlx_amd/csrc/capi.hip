@@ -457,6 +457,20 @@ int ltx2_mm_rescaled_euler_step(const float* x, const float* vel_cond, const flo
                                          stg_scale, modality_scale, rescale_scale, sigma, sigma_next, out, scalars_out, rows, C, (hipStream_t)stream);
 }
 
+int ltx2_channel_guidance_stats_blocks(int rows, int C) { return channel_guidance_stats_blocks(rows, C); }
+
+int ltx2_channel_guidance_stats(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, int64_t ts_stride, float cfg_scale,
+                                double* partials, float* stats, int rows, int C, void* stream) {
+    return channel_guidance_stats_launch(x, vel_cond, vel_uncond, ts, (long)ts_stride, cfg_scale, partials, stats, rows, C, (hipStream_t)stream);
+}
+
+int ltx2_rescaled_guided_euler_step(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, int64_t ts_stride,
+                                    const float* stats, float cfg_scale, double guidance_rescale, float sigma, float sigma_next, float* out, int rows,
+                                    int C, void* stream) {
+    return rescaled_guided_euler_step_launch(x, vel_cond, vel_uncond, ts, (long)ts_stride, stats, cfg_scale, guidance_rescale, sigma, sigma_next, out, rows,
+                                             C, (hipStream_t)stream);
+}
+
 int ltx2_vae_prepare_latent(const float* latent, const float* std, const float* mean, const float* noise,
                             float noise_scale, void* out_bf16, int C, int64_t P, void* stream) {
     LTX2_CHECK_ARG(latent && std && mean && out_bf16, "vae_prepare_latent: null operand");

@@ -32,6 +32,7 @@ typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 #define LTX2_E_INVALID (-1)    // bad argument / unsupported shape
 #define LTX2_E_HIP (-2)        // HIP runtime error
 #define LTX2_E_STATE (-3)      // call order / missing weight / workspace too small
+#define LTX2_E_UNSUPPORTED (-4)    // a valid request for a form that is not built
 
 // thread-local last-error string, readable through ltx2_last_error()
 void ltx2_set_error(const char* fmt, ...);

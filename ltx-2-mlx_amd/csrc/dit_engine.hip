@@ -126,6 +126,12 @@ struct ltx2_dit {
     int mm_rows[2] = {};
     double* pgj_part[2] = {};          // joint projected guidance: each modality's partials [pgj_rows[k]][5], for the modalities whose guider reads sums; allocated on first use, freed with the context
     int pgj_rows[2] = {};
+    double* cs_part = nullptr;         // CFG with the per-channel rescale: the statistics' partials [cs_rows][4][Cout], then the fp32 statistics [4][Cout] behind them (cs_stats);
+    float* cs_stats = nullptr;         //   one allocation, made on first use for the bound shape, freed with the context
+    int cs_rows = 0, cs_C = 0;
+    float* xattn_gate = nullptr;       // ltx2_dit_set_cross_attn_scale: [D] fp32 holding the scale, the gate table of the text cross-attention's to_out in layers >= xattn_start;
+    int xattn_start = 0;               //   allocated by the first scale != 1, freed with the context
+    bool xattn_on = false;
     // fp8-resident linear weights: the typed `const bf16*` fields of the weight structs then hold the CODES pointer; dense() looks it
     // up here to hand the GEMM (codes, per-row scale) instead of bf16 weights.  Per context (a second context over the same tensors
     // -- the video twin of an AudioVideo model -- keeps its own entries); rebuilt whenever the weights are resolved again.
@@ -682,6 +688,7 @@ int block_attention(ltx2_dit* c, int k, int l, long es, hipStream_t st, int fold
     }
     GemmParams po = gemm_dense_params(m.att, D, w.text.o_w, w.text.o_b, m.x, D, N, D, D);
     if (c->v2) gemm_set_gate(po, ada.E(8), es, tab + 8 * D);
+    else if (c->xattn_on && l >= c->xattn_start) gemm_set_gate(po, nullptr, 0, c->xattn_gate);      // cross_attn_scale: a row-invariant gate table
     return dense(c, po, EPI_RESID_GATE_F32, st);
 }
 
@@ -1092,6 +1099,8 @@ void ltx2_dit_destroy(ltx2_dit* c) {
         if (p) (void)hipFree(p);
     for (double* p : c->pgj_part)
         if (p) (void)hipFree(p);
+    if (c->cs_part) (void)hipFree(c->cs_part);
+    if (c->xattn_gate) (void)hipFree(c->xattn_gate);
     if (c->exec) (void)hipGraphExecDestroy(c->exec);
     if (c->graph) (void)hipGraphDestroy(c->graph);
     for (hipEvent_t e : c->prof_ev) (void)hipEventDestroy(e);
@@ -1195,6 +1204,30 @@ int ltx2_dit_set_stg_blocks(ltx2_dit* c, int modality, const unsigned char* flag
     }
     LTX2_CHECK_ARG(n_layers == c->cfg.num_layers, "dit_set_stg_blocks: n_layers=%d, the model has %d", n_layers, c->cfg.num_layers);
     c->stg[modality].assign(flags, flags + n_layers);
+    return LTX2_OK;
+}
+
+int ltx2_dit_set_cross_attn_scale(ltx2_dit* c, float scale, int start_layer) {
+    LTX2_CHECK_ARG(c && start_layer >= 0, "dit_set_cross_attn_scale: bad argument");
+    if (c->av || c->v2) {       // there the text cross-attention's gate is per row (AdaLN row 8), not a table; scaling it is not built
+        ltx2_set_error("dit_set_cross_attn_scale: built for the VideoOnly LTX-2.0 model alone (a gated text cross-attention and AudioVideo models are not)");
+        return LTX2_E_UNSUPPORTED;
+    }
+    c->xattn_on = false;
+    if (scale == 1.0f) return LTX2_OK;          // the launch goes without a table again; the buffer stays until the context goes (a captured graph may name it)
+    const int D = c->m[0].D;
+    if (!c->xattn_gate && hipMalloc((void**)&c->xattn_gate, 4L * D) != hipSuccess) {
+        c->xattn_gate = nullptr;
+        ltx2_set_error("dit_set_cross_attn_scale: allocating %ld bytes failed", 4L * D);
+        return LTX2_E_HIP;
+    }
+    const std::vector<float> table(D, scale);
+    if (hipMemcpy(c->xattn_gate, table.data(), 4L * D, hipMemcpyHostToDevice) != hipSuccess) {
+        ltx2_set_error("dit_set_cross_attn_scale: hipMemcpy failed");
+        return LTX2_E_HIP;
+    }
+    c->xattn_start = start_layer;
+    c->xattn_on = true;
     return LTX2_OK;
 }
 
@@ -1364,6 +1397,44 @@ int guided_step_joint(ltx2_dit* c, ltx2_dit* neg, const ModIn* in, const StepIo*
     return guided_euler_step_pair_launch(in[0].latent, v.vel, neg->m[0].vel, in[0].ts, in[0].n_ts == 1 ? 0 : 1, io[0].mask, io[0].clean, cfg[0], io[0].latent,
                                          v.N, v.Cout, in[1].latent, a.vel, neg->m[1].vel, in[1].ts, in[1].n_ts == 1 ? 0 : 1, io[1].mask, io[1].clean, cfg[1],
                                          io[1].latent, a.N, a.Cout, sigma, sigma_next, st);
+}
+
+// Classifier-free guidance with the per-channel rescale (the standard one-stage loop of the reference's scripts/generate.py:1935-1960, rescale_noise_cfg
+// :688-727): the two evaluations of guided_step, then with guidance_rescale > 0 the statistics' two launches, then ONE element-wise pass.  No mask / clean:
+// that loop has no conditioning.  The workspace: the partials and the statistics for the bound shape; never called while a stream is capturing
+int rescaled_workspace(ltx2_dit* c) {
+    const Mod& m = c->m[0];
+    const int rows = channel_guidance_stats_blocks(m.N, m.Cout);
+    if (c->cs_part && c->cs_rows == rows && c->cs_C == m.Cout) return LTX2_OK;
+    if (c->cs_part) (void)hipFree(c->cs_part);
+    c->cs_part = nullptr;
+    c->cs_stats = nullptr;
+    c->cs_rows = c->cs_C = 0;
+    const long bytes = 8L * rows * 4 * m.Cout + 4L * 4 * m.Cout;
+    if (hipMalloc((void**)&c->cs_part, bytes) != hipSuccess) {
+        c->cs_part = nullptr;
+        ltx2_set_error("dit_rescaled_guided_step: allocating %ld bytes of workspace failed", bytes);
+        return LTX2_E_HIP;
+    }
+    c->cs_stats = (float*)(c->cs_part + (long)rows * 4 * m.Cout);
+    c->cs_rows = rows;
+    c->cs_C = m.Cout;
+    return LTX2_OK;
+}
+
+int rescaled_guided_step(ltx2_dit* c, ltx2_dit* neg, const ModIn& in, const StepIo& io, float cfg_scale, double guidance_rescale, float sigma,
+                         float sigma_next, hipStream_t st) {
+    TRY(step_check(sigma, &io, 1, "dit_rescaled_guided_step"));
+    const Mod& m = c->m[0];
+    const bool rescale = guidance_rescale > 0.0;          // the reference's condition (:1930)
+    LTX2_CHECK_ARG(!rescale || (c->cs_part && c->cs_rows == channel_guidance_stats_blocks(m.N, m.Cout) && c->cs_C == m.Cout),
+                   "dit_rescaled_guided_step: workspace missing");
+    TRY(evaluate(c, neg, &in, st));
+    const long stride = in.n_ts == 1 ? 0 : 1;
+    if (rescale)
+        TRY(channel_guidance_stats_launch(in.latent, m.vel, neg->m[0].vel, in.ts, stride, cfg_scale, c->cs_part, c->cs_stats, m.N, m.Cout, st));
+    return rescaled_guided_euler_step_launch(in.latent, m.vel, neg->m[0].vel, in.ts, stride, rescale ? c->cs_stats : nullptr, cfg_scale, guidance_rescale,
+                                             sigma, sigma_next, io.latent, m.N, m.Cout, st);
 }
 
 // Spatio-temporal guidance on top (pipelines/one_stage.py:284-297): a third evaluation, on c ITSELF with the self-attentions of c->stg[0] skipped (no third
@@ -1782,6 +1853,8 @@ struct LoopStep {                           // all defaults: the plain denoise s
     float* const* running_joint = nullptr;          //   and its running guidance, [2] (NULL where the guider keeps none)
     bool heun = false;                      // the Heun step under cfg_scale (neg NULL: not guided), with GE where ge_gamma > 0
     float ge_gamma = 0.f;
+    bool rescaled = false;                  // the guided step of the standard one-stage loop: CFG in its order, the per-channel rescale at guidance_rescale > 0
+    double guidance_rescale = 0.0;
 };
 
 int capture_loop(ltx2_dit* c, const LoopStep& step, float* const latent[2], const Cond cond[2], const float* host_sigmas, int n_steps, hipStream_t st) {
@@ -1822,6 +1895,8 @@ int capture_loop(ltx2_dit* c, const LoopStep& step, float* const latent[2], cons
             const float* const next[2] = {s + 1, s + 1};
             const float cfg[2] = {step.cfg_scale, step.cfg_scale};
             rc = heun_step(c, step.neg, in, next, s + 1, cond, io, cfg, step.ge_gamma, i == 0, sigma, sigma_next, st);
+        } else if (step.rescaled) {
+            rc = rescaled_guided_step(c, step.neg, in[0], io[0], step.cfg_scale, step.guidance_rescale, sigma, sigma_next, st);
         } else if (step.projected) {
             rc = projected_step(c, step.neg, in[0], io[0], *step.projected, i == 0, sigma, sigma_next, st);
         } else if (step.stg_vel && i < step.stg_steps) {
@@ -1868,6 +1943,31 @@ int ltx2_dit_guided_step(ltx2_dit* c, ltx2_dit* neg, float* latent, const float*
     TRY(step_ready(c, neg, false, n_ts, "dit_guided_step"));
     const StepArgs v = step_args(latent, timesteps, n_timesteps, sigma_dev, mask, clean);
     return guided_step(c, neg, &v.in, v.io, cfg_scale, sigma, sigma_next, (hipStream_t)stream);
+}
+
+int ltx2_dit_rescaled_guided_step(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev,
+                                  float cfg_scale, double guidance_rescale, float sigma, float sigma_next, void* stream) {
+    LTX2_CHECK_ARG(neg && latent && timesteps, "dit_rescaled_guided_step: null argument");
+    const int n_ts[2] = {n_timesteps, 1};
+    TRY(step_ready(c, neg, false, n_ts, "dit_rescaled_guided_step"));
+    LTX2_CHECK_ARG(sigma != 0.f, "Sigma can't be 0.0");          // before the workspace is touched
+    if (guidance_rescale > 0.0) TRY(rescaled_workspace(c));
+    const StepArgs v = step_args(latent, timesteps, n_timesteps, sigma_dev, nullptr, nullptr);
+    return rescaled_guided_step(c, neg, v.in, v.io, cfg_scale, guidance_rescale, sigma, sigma_next, (hipStream_t)stream);
+}
+
+int ltx2_dit_graph_capture_rescaled_guided(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* host_sigmas, int n_steps, float cfg_scale,
+                                           double guidance_rescale, void* stream) {
+    const LoopIo lo = {{latent, nullptr}, {}};
+    TRY(capture_ready(c, neg, true, false, lo, host_sigmas, n_steps, "dit_graph_capture_rescaled_guided"));
+    for (int i = 0; i < n_steps; ++i) LTX2_CHECK_ARG(host_sigmas[i] != 0.f, "Sigma can't be 0.0");
+    if (guidance_rescale > 0.0) TRY(rescaled_workspace(c));
+    LoopStep step;
+    step.neg = neg;
+    step.cfg_scale = cfg_scale;
+    step.rescaled = true;
+    step.guidance_rescale = guidance_rescale;
+    return capture_loop(c, step, lo.lat, lo.cond, host_sigmas, n_steps, (hipStream_t)stream);
 }
 
 int ltx2_dit_guided_step_av(ltx2_dit* c, ltx2_dit* neg, float* v_latent, const float* a_latent, const float* v_timesteps, int n_v_timesteps,

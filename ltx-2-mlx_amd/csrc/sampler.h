@@ -147,3 +147,18 @@ int mm_rescaled_euler_step_launch(const float* x, const float* vel_cond, const f
                                   const float* ts, long ts_stride, const float* mask, const float* clean, const double* partials, float cfg_scale,
                                   float stg_scale, float modality_scale, float rescale_scale, float sigma, float sigma_next, float* out,
                                   float* scalars_out, int rows, int C, hipStream_t stream);
+
+// Classifier-free guidance with the per-channel rescale of the standard one-stage loop (reference scripts/generate.py:688-727, :1935-1960).  With
+// a = x - t*vc, b = x - t*vu, g = b + cfg_scale*(a - b), every operation rounded on its own:
+// stats: per channel c, over all rows, mean and sqrt(mean((. - mean)^2) + 1e-8) of g[:, c] and of a[:, c] into fp32 stats[4][C] = mean_g, std_g,
+//   mean_a, std_a.  Two launches: fp64 sums of (v - v0) and (v - v0)^2 (v0: the channel's value in row 0) per block of rows into
+//   partials[channel_guidance_stats_blocks(rows, C)][4][C] (the last row holds the shifts), then one thread per channel adds the rows in index
+//   order: mean = v0 + S1/n, var = max((S2 - S1*S1/n)/n, 0).  No atomics: the same bits from run to run.
+// step: gr = ((g - mean_g)/std_g)*std_a + mean_a, g' = r*gr + (1 - r)*g with r = fp32(guidance_rescale) and (1 - r) = fp32(1 - guidance_rescale)
+//   (stats NULL: g' = g), out = x + ((x - g')*(1/sigma))*(sigma_next - sigma).  out may be x.  No mask / clean: the route has no conditioning.
+int channel_guidance_stats_blocks(int rows, int C);
+int channel_guidance_stats_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride, float cfg_scale,
+                                  double* partials, float* stats, int rows, int C, hipStream_t stream);
+int rescaled_guided_euler_step_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride, const float* stats,
+                                      float cfg_scale, double guidance_rescale, float sigma, float sigma_next, float* out, int rows, int C,
+                                      hipStream_t stream);

@@ -3,7 +3,8 @@
 // step (reference pipelines/ti2vid_hq.py:153-273; over one latent, or over the video and the audio latent of the joint step in one launch) and the two passes of the guiders whose scalars are reductions over the whole latent
 // (CFGStarRescalingGuider, LtxAPGGuider, LegacyStatefulAPGGuider; reference components/guiders.py:51-76, 105-205), and the multi-modal guided step
 // (MultiModalGuider.calculate, :244-273: CFG, STG and modality-isolated terms, with or without the variance rescale), and the two passes of the Heun
-// sampler with the GE velocity correction (pipelines/one_stage.py:300-307, 334-464).  All arithmetic is fp32 and
+// sampler with the GE velocity correction (pipelines/one_stage.py:300-307, 334-464), and the guided step of the standard one-stage loop with its
+// per-channel rescale and the two kernels of its statistics (reference scripts/generate.py:688-727, 1895-1976).  All arithmetic is fp32 and
 // fp64, so the file compiles to the same code in both library builds.  The definitions are written out in include/ltx2hip.h.
 #include <hip/hip_runtime.h>
 
@@ -59,6 +60,7 @@ struct Rows {           // what every step reads per row, and the shape
 struct Row {
     float t, m, one_minus_m;
     bool blend;
+    int col;            // the element's channel (only the step with per-channel statistics reads it)
 };
 
 template <int V>
@@ -83,7 +85,8 @@ __device__ __forceinline__ void step_rows(const Op& op, const Rows& r, long bloc
     for (long i = block * blockDim.x + threadIdx.x; i < nv; i += blocks * blockDim.x) {
         const long e = i * V, row = e / r.C;
         const float m = blend ? r.mask[row] : 1.f;
-        const Row rw = {r.ts[row * r.ts_stride], m, sub_rn(1.0f, m), blend};
+        Row rw = {r.ts[row * r.ts_stride], m, sub_rn(1.0f, m), blend, 0};
+        const int col = (int)(e - row * r.C);
         alignas(16) float in[Op::NIN][V], out[Op::NOUT][V];
 #pragma unroll
         for (int k = 0; k < Op::NIN; ++k) load<V>(op.in[k], e, in[k]);
@@ -92,6 +95,7 @@ __device__ __forceinline__ void step_rows(const Op& op, const Rows& r, long bloc
             float a[Op::NIN], o[Op::NOUT] = {};
 #pragma unroll
             for (int k = 0; k < Op::NIN; ++k) a[k] = in[k][j];
+            rw.col = col + j;
             op.one(st, rw, a, o);
 #pragma unroll
             for (int k = 0; k < Op::NOUT; ++k) out[k][j] = o[k];
@@ -483,6 +487,133 @@ struct MmRescaledEuler : StepOp {
     }
 };
 
+// ---------------------------------- classifier-free guidance with the per-channel rescale (the standard one-stage loop) ----------------------------------
+// rescale_noise_cfg of the reference's scripts/generate.py:688-727: statistics over the rows (the tokens) per channel, not over the whole latent.
+__device__ __forceinline__ float div_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a / b;
+}
+
+constexpr int NCS = 4;                // per channel: the sums S1_g, S2_g, S1_a, S2_a, and the statistics mean_g, std_g, mean_a, std_a
+constexpr int CS_ROWS = 64, CS_CAP = 256;       // a block takes at least CS_ROWS rows, and there are at most CS_CAP blocks
+
+// blocks along the rows: a function of the shape alone, whichever access width the operands' alignment allows
+inline int channel_blocks(int rows) { return grid_for(rows, CS_ROWS, CS_CAP); }
+
+// Pass 1.  Block (bx, by) takes the rows [rows*bx/nb, rows*(bx+1)/nb) and the `lanes` column groups (V channels each) from by*lanes on: a thread
+// owns one column group and every (BLOCK / lanes)-th row of the chunk.  With a = x - t*vc, b = x - t*vu, g = b + cfg*(a - b) as the step forms them
+// and the shifts g0, a0 = the channel's values in row 0, it adds (v - v0) and (v - v0)^2 in fp64 in row order, then the block's row lanes in lane
+// order, into partials[bx][4][C].  Block row 0 also stores the shifts into partials[nb][0][C] (g0) and partials[nb][2][C] (a0).  No atomics.
+template <int V>
+__global__ __launch_bounds__(BLOCK) void channel_sums_kernel(const float* __restrict__ x, const float* __restrict__ vc, const float* __restrict__ vu,
+                                                             const float* __restrict__ ts, long ts_stride, float cfg, double* __restrict__ partials,
+                                                             int rows, int C, int lanes) {
+    __shared__ double part[BLOCK * V];
+    const int cl = threadIdx.x % lanes, rl = threadIdx.x / lanes, row_lanes = BLOCK / lanes;
+    const int col = ((int)blockIdx.y * lanes + cl) * V;
+    const bool active = col < C;
+    const int nb = gridDim.x;
+    const long r0 = (long)rows * blockIdx.x / nb, r1 = (long)rows * (blockIdx.x + 1) / nb;
+    double s[NCS][V] = {}, g0[V] = {}, a0[V] = {};
+    auto form = [&](long row, float (&g)[V], float (&a)[V]) {
+        const float t = ts[row * ts_stride];
+        alignas(16) float xv[V], cv[V], uv[V];
+        load<V>(x, row * C + col, xv);
+        load<V>(vc, row * C + col, cv);
+        load<V>(vu, row * C + col, uv);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            a[j] = denoised(xv[j], cv[j], t);
+            g[j] = guide_from_uncond(a[j], denoised(xv[j], uv[j], t), cfg);
+        }
+    };
+    if (active) {
+        float g[V], a[V];
+        form(0, g, a);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            g0[j] = g[j];
+            a0[j] = a[j];
+        }
+        for (long row = r0 + rl; row < r1; row += row_lanes) {
+            form(row, g, a);
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                const double dg = (double)g[j] - g0[j], da = (double)a[j] - a0[j];
+                s[0][j] += dg;
+                s[1][j] += dg * dg;
+                s[2][j] += da;
+                s[3][j] += da * da;
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < NCS; ++k) {
+#pragma unroll
+        for (int j = 0; j < V; ++j) part[threadIdx.x * V + j] = s[k][j];
+        __syncthreads();
+        if (active && rl == 0) {
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                double acc = part[cl * V + j];
+                for (int q = 1; q < row_lanes; ++q) acc += part[(q * lanes + cl) * V + j];
+                partials[((long)blockIdx.x * NCS + k) * C + col + j] = acc;
+            }
+        }
+        __syncthreads();
+    }
+    if (active && rl == 0 && blockIdx.x == 0) {
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            partials[((long)nb * NCS + 0) * C + col + j] = g0[j];
+            partials[((long)nb * NCS + 2) * C + col + j] = a0[j];
+        }
+    }
+}
+
+// Pass 2, one thread per channel: the nb partial rows added in index order, then in fp64 mean = v0 + S1/n, var = max((S2 - S1*S1/n)/n, 0),
+// std = sqrt(var + 1e-8), each rounded once to fp32 into stats[4][C] = mean_g, std_g, mean_a, std_a
+__global__ __launch_bounds__(BLOCK) void channel_stats_kernel(const double* __restrict__ partials, float* __restrict__ stats, int nb, int rows, int C) {
+    const int c = blockIdx.x * BLOCK + threadIdx.x;
+    if (c >= C) return;
+    double s[NCS];
+#pragma unroll
+    for (int k = 0; k < NCS; ++k) {
+        double acc = 0.0;
+        for (int b = 0; b < nb; ++b) acc += partials[((long)b * NCS + k) * C + c];
+        s[k] = acc;
+    }
+    const double n = rows;
+#pragma unroll
+    for (int k = 0; k < NCS; k += 2) {
+        const double v0 = partials[((long)nb * NCS + k) * C + c];
+        stats[(long)k * C + c] = (float)(v0 + s[k] / n);
+        stats[(long)(k + 1) * C + c] = (float)sqrt(fmax((s[k + 1] - s[k] * s[k] / n) / n, 0.0) + 1e-8);
+    }
+}
+
+// The guided step with the rescale, the reference's statements in order (scripts/generate.py:1935-1960, rescale_noise_cfg :715-725, euler_step_x0):
+// a = x - t*vc, b = x - t*vu, g = b + cfg*(a - b); with stats: gr = ((g - mean_g)/std_g)*std_a + mean_a, g = r*gr + (1 - r)*g; then the Euler step
+struct RescaledGuidedEuler : StepOp {
+    enum { X, VC, VU, NIN };
+    enum { OUT, NOUT };
+    const float* in[NIN];
+    float* out[NOUT];
+    const float* stats;         // [4][C], or NULL: no rescale
+    float cfg, r, one_minus_r, inv, dt;     // cfg_scale, guidance_rescale, 1 - guidance_rescale, 1/sigma, sigma_next - sigma
+    int C;
+    __device__ __forceinline__ void one(State&, const Row& rw, const float* v, float* o) const {
+        const float a = denoised(v[X], v[VC], rw.t);
+        float g = guide_from_uncond(a, denoised(v[X], v[VU], rw.t), cfg);
+        if (stats) {
+            const float* s = stats + rw.col;
+            const float gr = add_rn(mul_rn(div_rn(sub_rn(g, s[0]), s[C]), s[3L * C]), s[2L * C]);
+            g = add_rn(mul_rn(r, gr), mul_rn(one_minus_r, g));
+        }
+        o[OUT] = euler(v[X], g, inv, dt);
+    }
+};
+
 // The checks every step shares, under the caller's name, and the launch.  present: the caller's required operands are all there.  16-byte accesses
 // need every [rows][C] operand on a 16-byte boundary as well as C % 4 == 0 (a NULL operand contributes no bits).  sums_grid: the grid of the sums
 // pass, which does not depend on the access width; 0: a step, one thread per vector under grid_for's cap.
@@ -757,6 +888,38 @@ int mm_rescaled_euler_step_launch(const float* x, const float* vel_cond, const f
                                 {cfg_scale - 1.0f, stg_scale, modality_scale - 1.0f}, partials, scalars_out, (double)rescale_scale, (double)rows * C,
                                 1.0f / sigma, sigma_next - sigma, guidance_sums_blocks(rows, C)};
     return launch_rows("mm_rescaled_euler_step", x && vel_cond && partials && out, op, ts, ts_stride, mask, clean, rows, C, 0, stream);
+}
+
+int channel_guidance_stats_blocks(int rows, int C) { return (rows > 0 && C > 0) ? channel_blocks(rows) + 1 : 0; }
+
+int channel_guidance_stats_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride, float cfg_scale,
+                                  double* partials, float* stats, int rows, int C, hipStream_t stream) {
+    LTX2_CHECK_ARG(x && vel_cond && vel_uncond && ts && partials && stats && rows > 0 && C > 0, "channel_guidance_stats: null operand or empty shape");
+    LTX2_CHECK_ARG(ts_stride == 0 || ts_stride == 1, "channel_guidance_stats: ts_stride is 0 (one timestep) or 1 (one per row)");
+    LTX2_CHECK_ARG(((uintptr_t)partials & 7) == 0 && ((uintptr_t)stats & 3) == 0, "channel_guidance_stats: partials must be 8-byte and stats 4-byte aligned");
+    const bool v4 = C % 4 == 0 && (((uintptr_t)x | (uintptr_t)vel_cond | (uintptr_t)vel_uncond) & 15) == 0;
+    const int groups = v4 ? C / 4 : C, nb = channel_blocks(rows);
+    int lanes = 1;              // column groups per block: the power of two that covers them, BLOCK at the most; the other threads are row lanes
+    while (lanes < groups && lanes < BLOCK) lanes <<= 1;
+    const dim3 grid(nb, (groups + lanes - 1) / lanes);
+    if (v4)
+        hipLaunchKernelGGL((channel_sums_kernel<4>), grid, dim3(BLOCK), 0, stream, x, vel_cond, vel_uncond, ts, ts_stride, cfg_scale, partials, rows, C, lanes);
+    else
+        hipLaunchKernelGGL((channel_sums_kernel<1>), grid, dim3(BLOCK), 0, stream, x, vel_cond, vel_uncond, ts, ts_stride, cfg_scale, partials, rows, C, lanes);
+    LTX2_CHECK_LAUNCH("channel_sums_kernel");
+    hipLaunchKernelGGL(channel_stats_kernel, dim3((C + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, stream, partials, stats, nb, rows, C);
+    LTX2_CHECK_LAUNCH("channel_stats_kernel");
+    return LTX2_OK;
+}
+
+int rescaled_guided_euler_step_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride, const float* stats,
+                                      float cfg_scale, double guidance_rescale, float sigma, float sigma_next, float* out, int rows, int C,
+                                      hipStream_t stream) {
+    LTX2_CHECK_ARG(sigma != 0.f, "Sigma can't be 0.0");   // reference core_utils.py:54-55
+    LTX2_CHECK_ARG(((uintptr_t)stats & 3) == 0, "rescaled_guided_euler_step: stats must be 4-byte aligned");
+    const RescaledGuidedEuler op = {{}, {x, vel_cond, vel_uncond}, {out}, stats, cfg_scale, (float)guidance_rescale, (float)(1.0 - guidance_rescale),
+                                    1.0f / sigma, sigma_next - sigma, C};
+    return launch_rows("rescaled_guided_euler_step", x && vel_cond && vel_uncond && out, op, ts, ts_stride, nullptr, nullptr, rows, C, 0, stream);
 }
 
 namespace {

@@ -568,6 +568,49 @@ def stg_euler_step(x: torch.Tensor, vel_cond: torch.Tensor, vel_uncond: Optional
     return out
 
 
+def channel_guidance_stats_blocks(rows: int, c: int, dtype: Optional[torch.dtype] = None) -> int:
+    """Rows of the fp64 [rows, 4, C] workspace that channel_guidance_stats fills for an [N, C] latent (ltx2_channel_guidance_stats_blocks)."""
+    return int(nv.lib(dtype).ltx2_channel_guidance_stats_blocks(int(rows), int(c)))
+
+
+def channel_guidance_stats(x: torch.Tensor, vel_cond: torch.Tensor, vel_uncond: torch.Tensor, timesteps: torch.Tensor, cfg_scale: float,
+                           partials: Optional[torch.Tensor] = None, stats: Optional[torch.Tensor] = None,
+                           dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """The per-channel statistics of the standard loop's guidance rescale over fp32 [N, C] (ltx2_channel_guidance_stats): with a = x - t*vc,
+    b = x - t*vu, g = b + cfg_scale*(a - b), over all rows the mean and sqrt(mean((. - mean)^2) + 1e-8) of g and of a per channel, accumulated
+    in fp64 without atomics.  -> stats, fp32 [4, C] = mean_g, std_g, mean_a, std_a.  `partials`: the fp64 workspace
+    [channel_guidance_stats_blocks(N, C), 4, C]; `dtype` picks the library build (the kernels are fp32 / fp64 in both)."""
+    n, c, timesteps = _step_operands(x, timesteps, (vel_cond, vel_uncond))
+    assert vel_cond is not None and vel_uncond is not None
+    if partials is None:
+        partials = torch.empty(channel_guidance_stats_blocks(n, c, dtype), 4, c, device=x.device, dtype=torch.float64)
+    if stats is None:
+        stats = torch.empty(4, c, device=x.device, dtype=torch.float32)
+    assert partials.dtype == torch.float64 and partials.is_contiguous() and partials.numel() >= 4 * c * channel_guidance_stats_blocks(n, c, dtype)
+    assert stats.dtype == torch.float32 and stats.is_contiguous() and stats.numel() == 4 * c
+    nv.check(nv.lib(dtype).ltx2_channel_guidance_stats(nv.ptr(x), nv.ptr(vel_cond), nv.ptr(vel_uncond), nv.ptr(timesteps),
+                                                       0 if timesteps.numel() == 1 else 1, float(cfg_scale), nv.ptr(partials), nv.ptr(stats), n, c,
+                                                       nv.stream()))
+    return stats
+
+
+def rescaled_guided_euler_step(x: torch.Tensor, vel_cond: torch.Tensor, vel_uncond: torch.Tensor, timesteps: torch.Tensor, cfg_scale: float,
+                               guidance_rescale: float, sigma: float, sigma_next: float, stats: Optional[torch.Tensor] = None,
+                               out: Optional[torch.Tensor] = None, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """One guided step of the standard one-stage loop over fp32 [N, C] (ltx2_rescaled_guided_euler_step): g = b + cfg_scale*(a - b), with `stats`
+    (channel_guidance_stats) gr = ((g - mean_g)/std_g)*std_a + mean_a and g = r*gr + (1 - r)*g, then the Euler update, every operation
+    individually rounded.  stats None: guidance without rescale.  timesteps: 1 or N elements; `out` may be `x`."""
+    if out is None:
+        out = torch.empty_like(x)
+    assert vel_cond is not None and vel_uncond is not None
+    n, c, timesteps = _step_operands(x, timesteps, (vel_cond, vel_uncond, out))
+    assert stats is None or (stats.dtype == torch.float32 and stats.is_contiguous() and stats.numel() == 4 * c)
+    nv.check(nv.lib(dtype).ltx2_rescaled_guided_euler_step(nv.ptr(x), nv.ptr(vel_cond), nv.ptr(vel_uncond), nv.ptr(timesteps),
+                                                           0 if timesteps.numel() == 1 else 1, nv.ptr(stats), float(cfg_scale), float(guidance_rescale),
+                                                           float(sigma), float(sigma_next), nv.ptr(out), n, c, nv.stream()))
+    return out
+
+
 GUIDANCE_MODES = {"cfg_star": 0, "apg": 1, "legacy_apg": 2}      # `mode` of ltx2_projected_euler_step / ltx2_dit_projected_step
 
 

@@ -175,6 +175,7 @@ class LTXModel:
         self._twin: Optional["LTXModel"] = None        # VideoOnly engine over the SAME weight tensors (video-only inference on an AV model)
         self._sigma_dev: Dict[float, torch.Tensor] = {}  # device scalars of the step sigmas (no host-to-device copy inside the loop)
         self._stg: Dict[int, Optional[bytes]] = {0: None, 1: None}     # per modality, the engine's STG skip flags (set_stg_blocks); None: no set
+        self._xattn: Tuple[float, int] = (1.0, 0)                      # set_cross_attn_scale: (scale, start_layer); a clone is given the same
         self._graph_owner: Optional[Tuple[str, "LTXModel"]] = None     # (kind of the last capture made through this object, the context that holds its graph)
         self._ctor = dict(num_attention_heads=num_attention_heads, attention_head_dim=attention_head_dim, in_channels=in_channels,
                           out_channels=out_channels, num_layers=num_layers, cross_attention_dim=cross_attention_dim, norm_eps=norm_eps,
@@ -266,8 +267,20 @@ class LTXModel:
             t = LTXModel(model_type=self.model_type, **self._ctor, **extra)
             for k, v in self._w.items():
                 t._register(k, v)
+            if self._xattn[0] != 1.0:
+                t.set_cross_attn_scale(*self._xattn)
             self._clone = t
         return self._clone
+
+    def set_cross_attn_scale(self, scale: float, start_layer: int = 40) -> None:
+        """The reference's LTXModel.set_cross_attn_scale: from now on the text cross-attention output of the layers >= start_layer is multiplied by
+        `scale` before it joins the residual stream (ltx2_dit_set_cross_attn_scale: a gate table of the out-projection's epilogue, no further
+        kernel); 1.0 removes it.  The context of clone_sharing_weights() follows.  NotImplementedError on an AudioVideo model and on a gated
+        text cross-attention (LTX-2.3): their gate is per row."""
+        nv.check(self._L.ltx2_dit_set_cross_attn_scale(self._h, float(scale), int(start_layer)))
+        self._xattn = (float(scale), int(start_layer))
+        if self._clone is not None:
+            self._clone.set_cross_attn_scale(scale, start_layer)
 
     def __del__(self):
         try:
@@ -788,6 +801,34 @@ class LTXModel:
     def replay_guided_graph(self) -> None:
         """Replay the graph captured by capture_guided_graph (it belongs to the VideoOnly context that ran the capture)."""
         self._replay("guided", "no guided graph captured")
+
+    # ------------------------------------------------------------------ CFG with the per-channel rescale: the standard one-stage loop (video-only engine)
+    def rescaled_guided_step_(self, neg: "LTXModel", latent: torch.Tensor, video: Modality, sigma: float, sigma_next: float, cfg_scale: float,
+                              guidance_rescale: float) -> None:
+        """In-place: latent (N, C) fp32 <- one guided step of the reference's standard one-stage loop by ONE C call
+        (ltx2_dit_rescaled_guided_step): forward(self), forward(neg), g = uncond + cfg_scale*(cond - uncond) on the x0 predictions, with
+        guidance_rescale > 0 the per-channel statistics and rescale_noise_cfg, then the Euler update.  No conditioning on this route."""
+        pos, ng = self._contexts(neg)
+        ts, n_ts, sg = pos._step_inputs(latent, video, sigma)
+        nv.check(pos._L.ltx2_dit_rescaled_guided_step(pos._h, ng._h, nv.ptr(latent), nv.ptr(ts), n_ts, nv.ptr(sg), float(cfg_scale), float(guidance_rescale),
+                                                      float(sigma), float(sigma_next), nv.stream()))
+
+    def capture_rescaled_guided_graph(self, neg: "LTXModel", latent: torch.Tensor, sigmas: Sequence[float], cfg_scale: float,
+                                      guidance_rescale: float) -> None:
+        """hipGraph-capture len(sigmas)-1 of those steps over `latent` (N, C fp32) with uniform timesteps, one linear chain
+        (ltx2_dit_graph_capture_rescaled_guided).  Both contexts are prepared first; the graph belongs to the positive VideoOnly context and
+        replay_rescaled_guided_graph() replays it.  The latent must stay alive while it is replayed."""
+        pos, ng = self._contexts(neg)
+        assert pos._prep_key is not None and ng._prep_key is not None, "call prepare() on both contexts first"
+        arr, n, st, _ = self._capture_inputs(sigmas)
+        pos._graph_refs = (latent, ng)
+        nv.check(pos._L.ltx2_dit_graph_capture_rescaled_guided(pos._h, ng._h, nv.ptr(latent), arr, n, float(cfg_scale), float(guidance_rescale),
+                                                               st.cuda_stream))
+        self._graph_owner = ("rescaled_guided", pos)
+
+    def replay_rescaled_guided_graph(self) -> None:
+        """Replay the graph captured by capture_rescaled_guided_graph (it belongs to the VideoOnly context that ran the capture)."""
+        self._replay("rescaled_guided", "no rescaled guided graph captured")
 
     # ------------------------------------------------------------------ spatio-temporal guidance on top of CFG (video-only engine)
     def stg_step_(self, neg: Optional["LTXModel"], latent: torch.Tensor, video: Modality, sigma: float, sigma_next: float, cfg_scale: float,

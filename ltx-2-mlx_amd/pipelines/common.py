@@ -368,6 +368,63 @@ def guided_denoise_loop(transformer, video_state: LatentState, sigmas, context: 
     return _with_latent(video_state, lat)
 
 
+def rescale_noise_cfg(noise_cfg: torch.Tensor, noise_pred_text: torch.Tensor, guidance_rescale: float = 0.7) -> torch.Tensor:
+    """The reference's rescale_noise_cfg (scripts/generate.py:688-727) on token-layout predictions (B, N, C): per channel, over the tokens (its
+    axes 2, 3, 4 of (B, C, F, H, W)), the guided prediction is given the conditional one's mean and standard deviation, then blended with
+    itself by guidance_rescale.  Its statements in order."""
+    cfg_mean = noise_cfg.mean(dim=1, keepdim=True)
+    cfg_std = torch.sqrt(((noise_cfg - cfg_mean) ** 2).mean(dim=1, keepdim=True) + 1e-8)
+    text_mean = noise_pred_text.mean(dim=1, keepdim=True)
+    text_std = torch.sqrt(((noise_pred_text - text_mean) ** 2).mean(dim=1, keepdim=True) + 1e-8)
+    rescaled = (noise_cfg - cfg_mean) / cfg_std * text_std + text_mean
+    return guidance_rescale * rescaled + (1 - guidance_rescale) * noise_cfg
+
+
+def standard_cfg_denoise_loop(transformer, video_state: LatentState, sigmas, context: torch.Tensor, negative_context: Optional[torch.Tensor],
+                              cfg_scale: float, guidance_rescale: float, callback=None, use_hip_graph: bool = True, fused: bool = True) -> LatentState:
+    """The guided branch of the reference's standard one-stage loop (scripts/generate.py:1895-1976: the dev video-only model under classifier-free
+    guidance): per step the positive and the negative prompt, g = uncond + cfg_scale*(cond - uncond) on the x0 predictions, with
+    guidance_rescale > 0 rescale_noise_cfg(g, cond, guidance_rescale), then the x0 Euler step.  fused=True: every step is ONE C call
+    (LTXModel.rescaled_guided_step_: the two forwards, the per-channel statistics, the step kernel) and with no callback and fewer than 64
+    steps the loop is one captured graph.  fused=False: the reference's statements one by one in torch through X0Model, the comparison form.
+    cfg_scale <= 1 is the unguided loop (joint_denoise_loop), as the reference guides only above 1.  The route has no conditioning: the
+    denoise mask must be all ones.  `transformer` is an X0Model of a video-only model.  Returns the video state."""
+    from ..components import EulerDiffusionStep
+    model = transformer.velocity_model
+    if model.is_av:
+        raise ValueError("standard_cfg_denoise_loop runs the video-only model (AudioVideo models are guided by OneStagePipeline)")
+    if not cfg_scale > 1.0:
+        return joint_denoise_loop(transformer, False, video_state, None, sigmas, context, None, EulerDiffusionStep(), callback, use_hip_graph)[0]
+    if negative_context is None:
+        raise ValueError("guidance needs the negative prompt's encoding")
+    if not bool((video_state.denoise_mask == 1).all()):
+        raise ValueError("standard_cfg_denoise_loop has no conditioning (the reference's standard loop has none): the denoise mask must be all ones")
+    sig = [float(s) for s in sigmas]
+    n = len(sig) - 1
+    if not fused:
+        from .. import kernels as K
+        neg = X0Model(model.clone_sharing_weights())
+        c = video_state.latent.shape[-1]
+        for i in range(n):
+            cond = transformer(modality_from_state(video_state, context, sig[i], uniform=True))
+            uncond = neg(modality_from_state(video_state, negative_context, sig[i], uniform=True))
+            denoised = uncond + cfg_scale * (cond - uncond)
+            if guidance_rescale > 0:
+                denoised = rescale_noise_cfg(denoised, cond, guidance_rescale)
+            lat = video_state.latent
+            video_state = video_state.replace(latent=K.euler_step(lat.reshape(-1, c).float(), denoised.reshape(-1, c).float(), sig[i], sig[i + 1])
+                                              .reshape(lat.shape).to(lat.dtype))
+            if callback:
+                callback(i + 1, n)
+        return video_state
+    model, _, lat, _, _ = _video_loop_inputs(model, video_state)
+    neg = _prepare_contexts(model, True, False, video_state.positions, context, negative_context)
+    vm = lambda i: modality_from_state(video_state.replace(latent=lat[None]), context, sig[i], uniform=True)      # noqa: E731
+    _run_steps(n, callback, use_hip_graph, lambda: model.capture_rescaled_guided_graph(neg, lat, sig, cfg_scale, guidance_rescale),
+               model.replay_rescaled_guided_graph, lambda i: model.rescaled_guided_step_(neg, lat, vm(i), sig[i], sig[i + 1], cfg_scale, guidance_rescale))
+    return _with_latent(video_state, lat)
+
+
 def stg_denoise_loop(transformer, video_state: LatentState, sigmas, context: torch.Tensor, negative_context: Optional[torch.Tensor], guider,
                      stg_guider, stg_blocks: Optional[List[int]], stg_cutoff: float, stepper, callback=None, use_hip_graph: bool = True) -> LatentState:
     """guided_denoise_loop with spatio-temporal guidance on top (pipelines/one_stage.py:267-326): while (step + 1) / n <= stg_cutoff a third

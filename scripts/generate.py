@@ -630,13 +630,16 @@ _ROUTE_EXCLUDES = {
     "two_stage_cfg": (("ti2vid_hq_audio", "a2vid_two_stage", "retake_video", "keyframes", "two_stage_distilled", "upscale_temporal", "audio_path"),
                       "with two_stage_cfg: TwoStagePipeline samples its own audio latent beside the video on the AudioVideo model, conditions on image_path "
                       "alone and ends with its own x2 spatial stage"),
+    "standard_cfg": (("generate_audio", "audio_path", "two_stage_distilled", "two_stage_cfg", "ti2vid_hq_audio", "a2vid_two_stage", "retake_video", "image_path"),
+                     "with standard_cfg: the guided standard loop is video-only and has no conditioning code (the reference's standard loop has none); it runs one stage "
+                     "on the video-only dev model"),
 }
 # route -> the _OUT_OF_PATH_DEFAULTS arguments that route takes itself.  apg_scale: the routes whose guided loop takes a guider (the AudioVideo route as
 # OneStagePipeline's guider_override, keyframe stage 1, retake's guided mode).  stg_scale and ge_gamma: OneStagePipeline alone (the AudioVideo route), and not
 # together (_check_sampler)
 _ROUTE_OWNS = {"keyframe": ("keyframes", "apg_scale"), "hq": ("distilled_lora", "keyframes"),
                "ic_lora": ("control_video", "save_control", "keyframes", "ic_lora_weights"), "retake": ("apg_scale",), "av": ("apg_scale", "stg_scale", "ge_gamma"), "a2vid": ("distilled_lora",),
-               "hq_av": ("distilled_lora",), "two_stage_cfg": ("distilled_lora",),
+               "hq_av": ("distilled_lora",), "two_stage_cfg": ("distilled_lora",), "standard_cfg": ("negative_prompt", "cross_attn_scale"),
                "retake_av": ()}          # no guider override on the joint audio+video loop: apg_scale keeps its out-of-path refusal
 
 
@@ -804,7 +807,13 @@ def _resolve_retake_av(r):
     r.generate_audio = True
 
 
-_RESOLVE_ROUTE = {"two_stage_cfg": _resolve_two_stage_cfg, "keyframe": _resolve_keyframe, "hq": _resolve_hq, "ic_lora": _resolve_ic_lora, "a2vid": _resolve_a2vid, "hq_av": _resolve_hq_av}
+def _resolve_standard_cfg(r):
+    if r.pipeline_type not in _PIPELINES_BUILT:
+        raise NotImplementedError(f"pipeline_type={r.pipeline_type!r} with standard_cfg: the guided standard loop is the reference's one-stage text-to-video route; "
+                                  "leave pipeline_type at 'text-to-video'")
+
+
+_RESOLVE_ROUTE = {"standard_cfg": _resolve_standard_cfg, "two_stage_cfg": _resolve_two_stage_cfg, "keyframe": _resolve_keyframe, "hq": _resolve_hq, "ic_lora": _resolve_ic_lora, "a2vid": _resolve_a2vid, "hq_av": _resolve_hq_av}
 
 
 def _resolve_request(kw: dict):
@@ -816,7 +825,9 @@ def _resolve_request(kw: dict):
     r = SimpleNamespace(**kw, retake_fps=None, retake_to_end=False, retake_window=None, parsed_keyframes=[], hq_lora=None, ic_loras=[], a2vid_lora=None, two_stage_lora=None)
     if r.retake_audio is not None and r.retake_video is None:
         raise ValueError("retake_audio (--retake-audio) is the sound track of retake_video (--retake): pass the clip as well")
-    if r.two_stage_cfg:
+    if r.standard_cfg:
+        r.route = "standard_cfg"
+    elif r.two_stage_cfg:
         r.route = "two_stage_cfg"
     elif r.ti2vid_hq_audio:
         r.route = "hq_av"
@@ -852,6 +863,8 @@ def _resolve_request(kw: dict):
     for k, default in _OUT_OF_PATH_DEFAULTS.items():
         if k in owns or (k == "negative_prompt" and r.gemma_encodes):
             continue
+        if k == "cross_attn_scale" and r.route is None and not r.two_stage_distilled and _owning_route(r) is None:
+            continue                                  # the plain standard route applies it too, as the reference does (:1174)
         v = (r.enhance_prompt_flag and r.use_gemma) if k == "enhance_prompt_flag" else getattr(r, k)
         if v != default:
             raise NotImplementedError(f"{k}={v!r} is outside the MI355X hot path (see DESIGN.md); leave it at its default {default!r}")
@@ -892,6 +905,9 @@ def _resolve_request(kw: dict):
             print(f"\n  ERROR: Gemma weights not found at {r.gemma_path}\n  Use use_gemma=False (--no-gemma) for dummy embeddings, or pass "
                   f"embedding_path / text_features_path")
             return None
+    if r.route == "standard_cfg" and r.model_variant == "distilled":
+        print("  standard_cfg with model_variant='distilled': the reference forces cfg = 1 and guidance_rescale = 0 for the distilled variant; running the plain loop")
+        r.cfg_scale, r.guidance_rescale = 1.0, 0.0
     if r.model_variant == "distilled" and r.cfg_scale > 1.2:
         print(f"  WARNING: Distilled model requires CFG=1.0 (no guidance). You requested {r.cfg_scale}.\n  Forcing CFG=1.0 (reference :1207-1216).")
         r.cfg_scale, r.guidance_rescale, r.audio_cfg_scale, r.rescale_scale = 1.0, 0.0, 1.0, 0.0
@@ -918,6 +934,9 @@ def _resolve_request(kw: dict):
     r.version = r.model_version if r.model_version is not None else (detect_model_version(r.weights_path) if r.have_ckpt else "")
     r.v2 = str(r.version).startswith("2.3")
     r.av = bool(r.generate_audio or r.v2)
+    if r.route == "standard_cfg" and r.v2:
+        raise NotImplementedError(f"standard_cfg with an LTX-{r.version} / AudioVideo checkpoint: the guided standard loop runs the video-only dev model; "
+                                  "LTX-2.3 and AudioVideo checkpoints are guided by OneStagePipeline (drop standard_cfg)")
     # the video-only loop of the reference guides only for cfg_scale > 1 (:1935); OneStagePipeline's guiders are enabled for any scale != 1
     r.need_cfg = (r.cfg_scale != 1.0 or r.audio_cfg_scale != 1.0 or r.apg_guider is not None) if r.av else r.cfg_scale > 1.0
     if r.audio_path and r.route == "a2vid":
@@ -946,7 +965,8 @@ def _resolve_request(kw: dict):
     if r.low_memory or r.fast_mode:
         print("  low_memory / fast_mode: no effect here (weights and caches stay resident in HBM, the loop is one hipGraph)")
     # the routes that guide themselves take Gemma's encoding of the negative prompt when they will guide (retake: the dev variant only)
-    r.encode_negative = (r.cfg_scale != 1.0 or r.apg_guider is not None) and (r.route in ("keyframe", "hq", "a2vid", "hq_av", "two_stage_cfg") or (r.route == "retake" and r.model_variant != "distilled"))
+    r.encode_negative = (r.cfg_scale != 1.0 or r.apg_guider is not None) and (r.route in ("keyframe", "hq", "a2vid", "hq_av", "two_stage_cfg") or (r.route == "retake" and r.model_variant != "distilled")
+                                                                                  or (r.route == "standard_cfg" and r.cfg_scale > 1.0))
     r.toy = r.vae_base_channels is not None and r.vae_base_channels != 128        # debug-size VAE: matching debug-size upscaler / encoder
     if r.route is None:
         r.route = "two_stage" if r.two_stage_distilled else "av" if r.av else "standard"
@@ -1466,7 +1486,8 @@ def _run_standard(r, s):
     use_hip_graph=False, with image_path as an encoded frame 0, or as noise arithmetic in placeholder mode. upscale_spatial doubles the denoised latent before decoding (2W x 2H output);
     upscale_temporal doubles it in time (F -> 2F - 1 latent frames, after the spatial upscale when both are set; same output fps).  temporal_upscaler_checkpoint_semantics (keyword-only): False
     computes what the reference's TemporalUpscaler computes, True what the upstream PyTorch model does (see model/upscaler.py; which one the released weights want is not verified).
-    `<stem>_latent.npz` holds the latent that is decoded; without a VAE decoder it is all there is."""
+    `<stem>_latent.npz` holds the latent that is decoded; without a VAE decoder it is all there is.  cross_attn_scale != 1 scales the text cross-attention output of layers 40 and up
+    (reference :1174-1176).  standard_cfg=True (--standard-cfg) runs the loop's guided branch instead (:1895-1976): see the branch below; everything after the loop is shared."""
     from ltx_2_mlx_amd.pipelines.common import capture_and_replay, decode_video
     device, model, vae_decoder = r.device, s.model, s.vae_decoder
     print("[4/5] latent noise")
@@ -1483,9 +1504,26 @@ def _run_standard(r, s):
     print(f"[5/5] denoising ({len(sigmas) - 1} steps)")
     t0 = time.time()
     tok = patchifier.patchify(latent).contiguous()
+    if r.cross_attn_scale != 1.0 and not r.use_placeholder:          # reference :1174-1176
+        model.velocity_model.set_cross_attn_scale(r.cross_attn_scale, start_layer=40)
+        print(f"  Applied cross-attention scale {r.cross_attn_scale}x for layers 40-{r.num_layers - 1}" if r.num_layers > 40 else
+              f"  cross-attention scale {r.cross_attn_scale}x applies from layer 40 on: this model has {r.num_layers} layers, none is scaled")
     if r.use_placeholder:
         for i in range(len(sigmas) - 1):
             tok = tok + 0.1 * torch.randn_like(tok) * (sigmas[i + 1] - sigmas[i])
+    elif r.route == "standard_cfg":
+        # standard_cfg=True (--standard-cfg; keyword-only): the guided branch of the reference's standard loop (:1895-1976) for the dev video-only model: the positive and the negative prompt every
+        # step, uncond + cfg_scale*(cond - uncond) on the x0 predictions and, with guidance_rescale > 0 (default 0.7), rescale_noise_cfg, each step one C call and the loop one captured graph.
+        # The negative encoding is Gemma's of `negative_prompt or ""`, else `negative_embedding` of the --embedding file, else zeros.  model_variant="distilled" arrives here at cfg = 1: the plain loop
+        from ltx_2_mlx_amd.pipelines.common import standard_cfg_denoise_loop
+        from ltx_2_mlx_amd.types import LatentState
+        negative = s.negative_encoding
+        if _negative_or_zeros_note(r.cfg_scale > 1.0, negative):
+            negative = torch.zeros_like(s.text_encoding)
+        print(f"  Standard CFG loop: cfg={r.cfg_scale}" + (f", guidance rescale={r.guidance_rescale}" if r.cfg_scale > 1.0 and r.guidance_rescale > 0 else ""))
+        st = LatentState(latent=tok, denoise_mask=torch.ones(1, tok.shape[1], 1, device=device), positions=positions, clean_latent=torch.zeros_like(tok))
+        tok = standard_cfg_denoise_loop(model, st, sigmas, s.text_encoding, negative.to(device) if negative is not None else None, r.cfg_scale, r.guidance_rescale,
+                                        use_hip_graph=r.use_hip_graph).latent
     elif r.image_path:
         # image-to-video: encoded image replaces latent frame 0, its tokens keep (1 - strength) of the noise level
         from ltx_2_mlx_amd.conditioning import VideoLatentTools
@@ -1546,7 +1584,7 @@ def _run_standard(r, s):
 # today's precedence, top to bottom; _resolve_request names the one that runs
 _ROUTES = {"two_stage_cfg": _run_two_stage_cfg, "hq_av": _run_hq_av, "a2vid": _run_a2vid, "keyframe": _run_keyframe, "hq": _run_hq, "ic_lora": _run_ic_lora, "retake_av": _run_retake_av,
            "retake": _run_retake, "two_stage": _run_two_stage,
-           "av": _run_av, "standard": _run_standard}
+           "av": _run_av, "standard": _run_standard, "standard_cfg": _run_standard}
 
 
 def generate_video(
@@ -1634,6 +1672,7 @@ def generate_video(
     a2vid_two_stage: bool = False,
     ti2vid_hq_audio: bool = False,
     two_stage_cfg: bool = False,
+    standard_cfg: bool = False,                    # the dev video-only model under CFG with the per-channel rescale: the guided branch of the reference's standard loop
     modality_scale: float = 3.0,
     two_stage_rescale: float = 0.0,
     retake_audio: Optional[str] = None,
@@ -1645,7 +1684,7 @@ def generate_video(
 ):
     """Generate video from a text prompt: denoise loop + VAE decode on MI355X behind the reference's signature.  _resolve_request validates the arguments and names the one route that runs, before
     any model is loaded; then the text encoding, the transformer and the VAE decoder (built from the checkpoint's `config.vae` record) are loaded and the route's function runs.  Precedence, each
-    documented on its function: two_stage_cfg (_run_two_stage_cfg; keyword-only, with modality_scale and two_stage_rescale), ti2vid_hq_audio (_run_hq_av; keyword-only), a2vid_two_stage (_run_a2vid; keyword-only, it refuses retake_video), retake_video with retake_audio (_run_retake_av; keyword-only, the clip's sound track is retaken with the picture), retake_video (_run_retake; it refuses every other route), pipeline_type "keyframe-interpolation" with keyframes (_run_keyframe), "ti2vid-hq" (_run_hq), "ic-lora"
+    documented on its function: standard_cfg (the guided branch of _run_standard; keyword-only, the dev video-only model under cfg_scale, guidance_rescale and cross_attn_scale, without conditioning), two_stage_cfg (_run_two_stage_cfg; keyword-only, with modality_scale and two_stage_rescale), ti2vid_hq_audio (_run_hq_av; keyword-only), a2vid_two_stage (_run_a2vid; keyword-only, it refuses retake_video), retake_video with retake_audio (_run_retake_av; keyword-only, the clip's sound track is retaken with the picture), retake_video (_run_retake; it refuses every other route), pipeline_type "keyframe-interpolation" with keyframes (_run_keyframe), "ti2vid-hq" (_run_hq), "ic-lora"
     with a control video or an image (_run_ic_lora), two_stage_distilled (_run_two_stage), generate_audio or an LTX-2.3 checkpoint (_run_av), else the standard video-only loop (_run_standard).
     pipeline_type "two-stage" raises NotImplementedError. MI355X extras for every route: model_version="2.3" builds the LTX-2.3 architecture without a checkpoint (random init, for tests and
     benchmarks); fp8_resident keeps fp8 checkpoint weights as codes in HBM; fp8_compute runs the video stream's projections fp8 x fp8 on the fp8 MFMA (BASELINE config 3; per-token / per-channel
@@ -1753,6 +1792,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--two-stage-cfg", action="store_true", help="TwoStagePipeline (the reference's --pipeline two-stage on an AudioVideo checkpoint): --steps-stage1 joint steps at half "
                    "resolution under CFG (video --cfg-stage1 or --cfg, audio 7) and modality-isolated guidance (--modality-scale), x2 spatial upscale, 3 joint distilled steps; needs "
                    "--spatial-upscaler-weights; --decode-audio writes the .wav.  (--pipeline two-stage itself keeps its refusal)")
+    p.add_argument("--standard-cfg", action="store_true", help="the reference's standard one-stage loop for the dev video-only model (--model-variant dev): positive and negative prompt "
+                   "every step, CFG at --cfg on the x0 predictions, the per-channel --guidance-rescale (default 0.7), --cross-attn-scale on layers 40-47; no conditioning "
+                   "(--image is refused).  (--model-variant dev --cfg 3 without this flag keeps its refusal)")
     p.add_argument("--modality-scale", type=float, default=3.0, help="modality_scale of --two-stage-cfg: guidance away from the pass without audio<->video cross-attention")
     p.add_argument("--a2vid-two-stage", action="store_true", help="A2VidPipelineTwoStage: generate the video TO --audio at production quality on the AudioVideo model: --steps "
                    "steps at half resolution with classifier-free guidance on the video alone and the encoded audio frozen, x2 latent upscale "
@@ -1803,7 +1845,7 @@ def kwargs_from_args(a) -> dict:
         fp8_resident=a.fp8_resident, fp8_compute=a.fp8_compute, model_version=a.model_version, compute_dtype="bfloat16" if a.bf16 else None, num_layers=a.layers, num_heads=a.heads,
         vae_base_channels=a.vae_base_channels, save_mp4=not a.no_video_file, decode_audio=a.decode_audio,
         audio_path=a.audio, audio_start_time=a.audio_start, audio_max_duration=a.audio_duration, a2vid_two_stage=a.a2vid_two_stage, ti2vid_hq_audio=a.ti2vid_hq_audio,
-        two_stage_cfg=a.two_stage_cfg, modality_scale=a.modality_scale,
+        two_stage_cfg=a.two_stage_cfg, modality_scale=a.modality_scale, standard_cfg=a.standard_cfg,
         retake_audio=a.retake_audio, retake_audio_cfg=a.retake_audio_cfg,
         retake_video=a.retake, retake_start_time=a.retake_start, retake_end_time=a.retake_end, retake_composite=a.retake_keep_source,
         stg_blocks=a.stg_blocks, stg_cutoff=a.stg_cutoff, sampler=a.sampler)
