@@ -323,6 +323,19 @@ int ltx2_stg_euler_step(const float* x, const float* vel_cond, const float* vel_
                         int64_t ts_stride, const float* mask, const float* clean, float cfg_scale, float stg_scale, float sigma, float sigma_next,
                         float* out, int rows, int C, void* stream);
 
+/* ltx2_stg_euler_step over TWO latents in ONE launch (the video and the audio latent of a joint STG step), on the two-segment scaffold of
+ * ltx2_guided_euler_step_pair: v_ then a_, each with its own operands, cfg_scale, stg_scale, timesteps, mask / clean and shape; sigma and sigma_next
+ * are shared.  The per-element arithmetic is ltx2_stg_euler_step's, so each segment's output equals the single launch's bit for bit.  Per segment,
+ * independently: vel_uncond may be NULL (no CFG on that modality) and vel_perturbed may be NULL -- then s = g, ltx2_guided_euler_step's arithmetic
+ * (a modality that is not STG-guided, a step past the cutoff); both NULL: out = x + ((x - d) * (1/sigma)) * (sigma_next - sigma) with d from
+ * a = x - t*vel_cond alone.  16-byte accesses only when both segments allow them, element-wise otherwise.  sigma == 0 -> LTX2_E_INVALID with message
+ * "Sigma can't be 0.0".  (additive entry of ABI version 3)                                                                                */
+int ltx2_stg_euler_step_pair(const float* v_x, const float* v_vel_cond, const float* v_vel_uncond, const float* v_vel_perturbed, const float* v_ts,
+                             int64_t v_ts_stride, const float* v_mask, const float* v_clean, float v_cfg_scale, float v_stg_scale, float* v_out,
+                             int v_rows, int v_C, const float* a_x, const float* a_vel_cond, const float* a_vel_uncond, const float* a_vel_perturbed,
+                             const float* a_ts, int64_t a_ts_stride, const float* a_mask, const float* a_clean, float a_cfg_scale, float a_stg_scale,
+                             float* a_out, int a_rows, int a_C, float sigma, float sigma_next, void* stream);
+
 /* The res_2s second-order exponential-integrator step (pipelines/ti2vid_hq.py:153-273) as two passes over [rows][C] fp32, every operation
  * individually rounded (no FMA contraction), so each equals the separate fp32 array ops of the reference bit for bit.  The guided, blended
  * x0 of a pair of velocities, in the HQ pipeline's own order (:315, not CFGGuider's):
@@ -727,6 +740,20 @@ int ltx2_dit_graph_capture_guided_joint_av(ltx2_dit* ctx, ltx2_dit* neg, float* 
                                            const float* v_mask, int64_t n_v_mask, const float* v_clean, int64_t n_v_clean, const float* a_mask,
                                            int64_t n_a_mask, const float* a_clean, int64_t n_a_clean, float cfg_scale, float audio_cfg_scale,
                                            void* stream);
+/* The STG step on the AudioVideo engine with BOTH latents stepped and an STG term per modality (OneStagePipeline's joint branch with stg_scale and / or
+ * stg_audio_scale): forward_av on ctx and, when neg is given (NULL: neither modality has CFG), on neg, exactly as ltx2_dit_guided_step_joint_av builds
+ * them; then ltx2_dit_forward_perturbed_av on ctx ITSELF (the sets of ltx2_dit_set_stg_blocks, per modality; no third context) into the caller's
+ * scratch pair, v_vel_perturbed [N][out_channels] and a_vel_perturbed [Na][audio_out_channels] fp32, both required; then ONE
+ * ltx2_stg_euler_step_pair in place on both latents, the video under cfg_scale / stg_scale and the audio under audio_cfg_scale / audio_stg_scale.
+ * A modality whose STG scale is 0 hands the kernel no perturbed velocity: it takes the guided step's arithmetic.  n_v_vel / n_a_vel: the ELEMENT
+ * counts of the scratch buffers.  LTX2_E_INVALID, before anything is launched: the rules of ltx2_dit_guided_step_joint_av (with neg NULL the same
+ * rules on ctx alone), a missing scratch or one whose element count is not N * out_channels / Na * audio_out_channels, a non-zero STG scale on a
+ * modality whose set is empty, both STG scales 0 (that is ltx2_dit_guided_step_joint_av).  There is no captured form: the loop is one C call per
+ * step.  (additive entry of ABI version 3)                                                                                                  */
+int ltx2_dit_stg_step_joint_av(ltx2_dit* ctx, ltx2_dit* neg, float* v_latent, float* a_latent, const float* v_timesteps, int n_v_timesteps,
+                               const float* a_timesteps, int n_a_timesteps, const float* sigma_dev, const float* v_mask, const float* v_clean,
+                               const float* a_mask, const float* a_clean, float* v_vel_perturbed, int64_t n_v_vel, float* a_vel_perturbed, int64_t n_a_vel,
+                               float cfg_scale, float audio_cfg_scale, float stg_scale, float audio_stg_scale, float sigma, float sigma_next, void* stream);
 /* ltx2_dit_guided_step with a guider whose scalars are sums over the whole latent: forward(ctx), forward(neg), ltx2_guidance_sums and
  * ltx2_projected_euler_step in place on `latent`, in order on the caller's stream.  mode / scale / eta / norm_threshold as in
  * ltx2_projected_euler_step; momentum != 0 (mode 2 only) keeps the running guidance in a [N][out_channels] fp32 buffer owned by ctx: first != 0

@@ -92,6 +92,8 @@ SIGNATURES = {
     "ltx2_guided_euler_step_pair": (i32, [vp, vp, vp, vp, i64, vp, vp, f32, vp, i32, i32,
                                           vp, vp, vp, vp, i64, vp, vp, f32, vp, i32, i32, f32, f32, vp]),
     "ltx2_stg_euler_step": (i32, [vp, vp, vp, vp, vp, i64, vp, vp, f32, f32, f32, f32, vp, i32, i32, vp]),
+    "ltx2_stg_euler_step_pair": (i32, [vp, vp, vp, vp, vp, i64, vp, vp, f32, f32, vp, i32, i32,
+                                       vp, vp, vp, vp, vp, i64, vp, vp, f32, f32, vp, i32, i32, f32, f32, vp]),
     "ltx2_res2s_midpoint": (i32, [vp, vp, vp, vp, i64, vp, vp, f32, f32, i32, vp, vp, vp, i32, i32, vp]),
     "ltx2_res2s_combine": (i32, [vp, vp, vp, vp, i64, vp, vp, f32, vp, vp, f32, f32, f32, vp, i32, i32, vp]),
     "ltx2_res2s_midpoint_pair": (i32, [vp, vp, vp, vp, i64, vp, vp, f32, vp, vp, vp, i32, i32,
@@ -149,6 +151,7 @@ SIGNATURES = {
     "ltx2_dit_mm_guided_step_av": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64,
                                          f32, f32, f32, f32, f32, f32, f32, f32, f32, f32, vp]),
     "ltx2_dit_stg_step": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, f32, f32, f32, f32, vp]),
+    "ltx2_dit_stg_step_joint_av": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, i64, vp, i64, f32, f32, f32, f32, f32, f32, vp]),
     "ltx2_dit_graph_capture_stg": (i32, [vp, vp, vp, C.POINTER(f32), i32, vp, i64, vp, i64, vp, i64, f32, f32, C.c_double, vp]),
     "ltx2_dit_denoise_step": (i32, [vp, vp, vp, i32, vp, vp, vp, f32, f32, vp, vp]),
     "ltx2_dit_graph_capture": (i32, [vp, vp, C.POINTER(f32), i32, vp]),

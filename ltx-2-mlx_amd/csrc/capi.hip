@@ -303,6 +303,16 @@ int ltx2_stg_euler_step(const float* x, const float* vel_cond, const float* vel_
                                  rows, C, (hipStream_t)stream);
 }
 
+int ltx2_stg_euler_step_pair(const float* v_x, const float* v_vel_cond, const float* v_vel_uncond, const float* v_vel_perturbed, const float* v_ts,
+                             int64_t v_ts_stride, const float* v_mask, const float* v_clean, float v_cfg_scale, float v_stg_scale, float* v_out,
+                             int v_rows, int v_C, const float* a_x, const float* a_vel_cond, const float* a_vel_uncond, const float* a_vel_perturbed,
+                             const float* a_ts, int64_t a_ts_stride, const float* a_mask, const float* a_clean, float a_cfg_scale, float a_stg_scale,
+                             float* a_out, int a_rows, int a_C, float sigma, float sigma_next, void* stream) {
+    return stg_euler_step_pair_launch(v_x, v_vel_cond, v_vel_uncond, v_vel_perturbed, v_ts, (long)v_ts_stride, v_mask, v_clean, v_cfg_scale, v_stg_scale,
+                                      v_out, v_rows, v_C, a_x, a_vel_cond, a_vel_uncond, a_vel_perturbed, a_ts, (long)a_ts_stride, a_mask, a_clean,
+                                      a_cfg_scale, a_stg_scale, a_out, a_rows, a_C, sigma, sigma_next, (hipStream_t)stream);
+}
+
 int ltx2_res2s_midpoint(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, int64_t ts_stride, const float* mask,
                         const float* clean, float cfg_scale, float c, int n_bong, float* x_mid, float* anchor, float* eps1, int rows, int C,
                         void* stream) {

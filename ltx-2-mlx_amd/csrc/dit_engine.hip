@@ -1451,6 +1451,23 @@ int stg_step(ltx2_dit* c, ltx2_dit* neg, const ModIn& in, const StepIo& io, floa
                                  stg_scale, sigma, sigma_next, io.latent, m.N, m.Cout, st);
 }
 
+// The same on AudioVideo contexts with BOTH latents stepped and an STG term per modality: the evaluations of guided_step_joint (neg NULL: no CFG), the
+// perturbed AudioVideo forward on c itself -- the self-attentions of c->stg[0] and c->stg[1] skipped -- into the caller's scratch pair ptb, then ONE
+// element-wise launch over both latents.  A modality whose stg scale is 0 hands the kernel no perturbed velocity: the guided step's arithmetic.
+// (the entry has checked the scratch lengths, the sets and the scales)
+int stg_step_joint(ltx2_dit* c, ltx2_dit* neg, const ModIn* in, const StepIo* io, float* const ptb[2], const float cfg[2], const float stg[2], float sigma,
+                   float sigma_next, hipStream_t st) {
+    TRY(step_check(sigma, io, 2, "dit_stg_step_joint_av"));
+    const Mod &v = c->m[0], &a = c->m[1];
+    TRY(evaluate(c, neg, in, st));
+    const ModIn pert[2] = {{in[0].latent, in[0].ts, in[0].n_ts, in[0].sigma, ptb[0]}, {in[1].latent, in[1].ts, in[1].n_ts, in[1].sigma, ptb[1]}};
+    TRY(forward(c, pert, st, true, true));
+    return stg_euler_step_pair_launch(in[0].latent, v.vel, neg ? neg->m[0].vel : nullptr, stg[0] != 0.f ? ptb[0] : nullptr, in[0].ts, in[0].n_ts == 1 ? 0 : 1,
+                                      io[0].mask, io[0].clean, cfg[0], stg[0], io[0].latent, v.N, v.Cout, in[1].latent, a.vel,
+                                      neg ? neg->m[1].vel : nullptr, stg[1] != 0.f ? ptb[1] : nullptr, in[1].ts, in[1].n_ts == 1 ? 0 : 1, io[1].mask,
+                                      io[1].clean, cfg[1], stg[1], io[1].latent, a.N, a.Cout, sigma, sigma_next, st);
+}
+
 // Guidance whose scalars are sums over the whole latent (CFG*, APG, legacy APG with momentum; csrc/sampler.hip): the guided step above with the
 // one element-wise pass replaced by the sums kernel and the projected step kernel.
 struct Projected {      // the guider of a projected step: mode 0 CFG*, 1 APG, 2 legacy APG
@@ -2004,6 +2021,38 @@ int ltx2_dit_stg_step(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* ti
     TRY(step_ready(c, neg, false, n_ts, "dit_stg_step"));
     const StepArgs v = step_args(latent, timesteps, n_timesteps, sigma_dev, mask, clean);
     return stg_step(c, neg, v.in, v.io, vel_perturbed, cfg_scale, stg_scale, sigma, sigma_next, (hipStream_t)stream);
+}
+
+int ltx2_dit_stg_step_joint_av(ltx2_dit* c, ltx2_dit* neg, float* v_latent, float* a_latent, const float* v_timesteps, int n_v_timesteps,
+                               const float* a_timesteps, int n_a_timesteps, const float* sigma_dev, const float* v_mask, const float* v_clean,
+                               const float* a_mask, const float* a_clean, float* v_vel_perturbed, int64_t n_v_vel, float* a_vel_perturbed, int64_t n_a_vel,
+                               float cfg_scale, float audio_cfg_scale, float stg_scale, float audio_stg_scale, float sigma, float sigma_next, void* stream) {
+    LTX2_CHECK_ARG(v_latent && a_latent && v_timesteps && a_timesteps && sigma_dev, "dit_stg_step_joint_av: null argument");
+    const int n_ts[2] = {n_v_timesteps, n_a_timesteps};
+    TRY(step_ready(c, neg, true, n_ts, "dit_stg_step_joint_av"));
+    float* const ptb[2] = {v_vel_perturbed, a_vel_perturbed};
+    const int64_t n_ptb[2] = {n_v_vel, n_a_vel};
+    const float cfg[2] = {cfg_scale, audio_cfg_scale}, stg[2] = {stg_scale, audio_stg_scale};
+    LTX2_CHECK_ARG(ptb[0] && ptb[1], "dit_stg_step_joint_av: v_vel_perturbed and a_vel_perturbed (fp32 scratch, [N][out_channels] and [Na][audio_out_channels]) "
+                                     "are both required: the perturbed pass writes both modalities' velocities");
+    LTX2_CHECK_ARG(stg[0] != 0.f || stg[1] != 0.f, "dit_stg_step_joint_av: both STG scales are 0: that is ltx2_dit_guided_step_joint_av (ltx2_dit_denoise_step_av "
+                                                   "without a negative context)");
+    for (int k = 0; k < 2; ++k) {
+        // the perturbed pass writes, and the step kernel reads, N * out_channels elements of each scratch: another length would be an out-of-bounds
+        // access, not an error (the comment at cond_modality())
+        const int64_t need = (int64_t)c->m[k].N * c->m[k].Cout;
+        LTX2_CHECK_ARG(n_ptb[k] == need, "dit_stg_step_joint_av: modality %d has %d tokens x %d channels, got a perturbed scratch of %ld elements", k, c->m[k].N,
+                       c->m[k].Cout, (long)n_ptb[k]);
+        bool any = false;
+        for (unsigned char f : c->stg[k]) any = any || f != 0;
+        LTX2_CHECK_ARG(stg[k] == 0.f || any, "dit_stg_step_joint_av: the %s STG scale is %g but no %s self-attention is marked (ltx2_dit_set_stg_blocks, modality %d)",
+                       k ? "audio" : "video", (double)stg[k], k ? "audio" : "video", k);
+    }
+    const StepArgs v = step_args(v_latent, v_timesteps, n_v_timesteps, sigma_dev, v_mask, v_clean);
+    const StepArgs a = step_args(a_latent, a_timesteps, n_a_timesteps, sigma_dev, a_mask, a_clean);
+    const ModIn in[2] = {v.in, a.in};
+    const StepIo io[2] = {v.io, a.io};
+    return stg_step_joint(c, neg, in, io, ptb, cfg, stg, sigma, sigma_next, (hipStream_t)stream);
 }
 
 int ltx2_dit_projected_step(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev, const float* mask,

@@ -33,6 +33,15 @@ int stg_euler_step_launch(const float* x, const float* vel_cond, const float* ve
                           const float* mask, const float* clean, float cfg_scale, float stg_scale, float sigma, float sigma_next, float* out, int rows,
                           int C, hipStream_t stream);
 
+// The same step over the video and the audio latent in ONE launch (the joint STG loop), v_ then a_ as in guided_euler_step_pair_launch, each with its
+// own cfg_scale and stg_scale.  Per segment vel_uncond may be NULL (no CFG) and vel_perturbed may be NULL (no STG term: s = g, the guided step's
+// arithmetic).  Each segment's output is the single launch's bit for bit.
+int stg_euler_step_pair_launch(const float* v_x, const float* v_vel_cond, const float* v_vel_uncond, const float* v_vel_perturbed, const float* v_ts,
+                               long v_ts_stride, const float* v_mask, const float* v_clean, float v_cfg_scale, float v_stg_scale, float* v_out, int v_rows,
+                               int v_C, const float* a_x, const float* a_vel_cond, const float* a_vel_uncond, const float* a_vel_perturbed,
+                               const float* a_ts, long a_ts_stride, const float* a_mask, const float* a_clean, float a_cfg_scale, float a_stg_scale,
+                               float* a_out, int a_rows, int a_C, float sigma, float sigma_next, hipStream_t stream);
+
 // The res_2s second-order step as two passes; d(x, vc, vu) = the guided, mask-blended x0 in the HQ pipeline's order:
 // a = x - t*vc, b = x - t*vu, g = b + cfg*(a - b) (g = a when vu is NULL), d = mask ? g*m + clean*(1 - m) : g.
 // midpoint: an = x, e = d - an, xm = an + c*e, n_bong x {an = xm - c*e, e = d - an}; stores x_mid, anchor, eps1.

@@ -154,7 +154,8 @@ struct GuidedEuler : StepOp {
 };
 
 // STGGuider.guide on top of the CFG-guided x0 (pipelines/one_stage.py:284-297): g as GuidedEuler forms it (g = a with no vu: the guider is not
-// enabled), p = x - t*vp from the pass whose self-attentions were skipped, s = g + stg*(g - p)
+// enabled), p = x - t*vp from the pass whose self-attentions were skipped, s = g + stg*(g - p).  No vp (the pair form alone allows it: a modality
+// that is not STG-guided, a step past the cutoff): s = g, GuidedEuler's arithmetic
 struct StgEuler : StepOp {
     enum { X, VC, VU, VP, CLEAN, NIN };
     enum { OUT, NOUT };
@@ -164,8 +165,8 @@ struct StgEuler : StepOp {
     __device__ __forceinline__ void one(State&, const Row& r, const float* a, float* o) const {
         float g = denoised(a[X], a[VC], r.t);
         if (in[VU]) g = guide_from_cond(g, denoised(a[X], a[VU], r.t), s1);
-        const float s = add_rn(g, mul_rn(stg, sub_rn(g, denoised(a[X], a[VP], r.t))));
-        o[OUT] = euler(a[X], blend_clean(s, a[CLEAN], r), inv, dt);
+        if (in[VP]) g = add_rn(g, mul_rn(stg, sub_rn(g, denoised(a[X], a[VP], r.t))));
+        o[OUT] = euler(a[X], blend_clean(g, a[CLEAN], r), inv, dt);
     }
 };
 
@@ -720,6 +721,19 @@ int stg_euler_step_launch(const float* x, const float* vel_cond, const float* ve
     LTX2_CHECK_ARG(sigma != 0.f, "Sigma can't be 0.0");   // reference core_utils.py:54-55
     const StgEuler op = {{}, {x, vel_cond, vel_uncond, vel_perturbed, clean}, {out}, cfg_scale - 1.0f, stg_scale, 1.0f / sigma, sigma_next - sigma};
     return launch_rows("stg_euler_step", x && vel_cond && vel_perturbed && out, op, ts, ts_stride, mask, clean, rows, C, 0, stream);
+}
+
+int stg_euler_step_pair_launch(const float* v_x, const float* v_vel_cond, const float* v_vel_uncond, const float* v_vel_perturbed, const float* v_ts,
+                               long v_ts_stride, const float* v_mask, const float* v_clean, float v_cfg_scale, float v_stg_scale, float* v_out, int v_rows,
+                               int v_C, const float* a_x, const float* a_vel_cond, const float* a_vel_uncond, const float* a_vel_perturbed,
+                               const float* a_ts, long a_ts_stride, const float* a_mask, const float* a_clean, float a_cfg_scale, float a_stg_scale,
+                               float* a_out, int a_rows, int a_C, float sigma, float sigma_next, hipStream_t stream) {
+    LTX2_CHECK_ARG(sigma != 0.f, "Sigma can't be 0.0");   // reference core_utils.py:54-55
+    const float inv = 1.0f / sigma, dt = sigma_next - sigma;
+    const StgEuler v = {{}, {v_x, v_vel_cond, v_vel_uncond, v_vel_perturbed, v_clean}, {v_out}, v_cfg_scale - 1.0f, v_stg_scale, inv, dt};
+    const StgEuler a = {{}, {a_x, a_vel_cond, a_vel_uncond, a_vel_perturbed, a_clean}, {a_out}, a_cfg_scale - 1.0f, a_stg_scale, inv, dt};
+    return launch_rows2("stg_euler_step_pair", v_x && v_vel_cond && v_out && a_x && a_vel_cond && a_out, v,
+                        {v_ts, v_ts_stride, v_mask, v_clean, v_rows, v_C}, a, {a_ts, a_ts_stride, a_mask, a_clean, a_rows, a_C}, stream);
 }
 
 int res2s_midpoint_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride, const float* mask,

@@ -568,6 +568,24 @@ def stg_euler_step(x: torch.Tensor, vel_cond: torch.Tensor, vel_uncond: Optional
     return out
 
 
+def stg_euler_step_pair(video: dict, audio: dict, sigma: float, sigma_next: float, dtype: Optional[torch.dtype] = None):
+    """stg_euler_step over two latents in ONE launch (ltx2_stg_euler_step_pair): `video` and `audio` each hold the single form's operands by
+    name -- x, vel_cond, timesteps, cfg_scale, stg_scale and optionally vel_uncond (None: no CFG on that modality), vel_perturbed (None: no
+    STG term, guided_euler_step's arithmetic), mask, clean, out.  -> (video out, audio out), each equal to the single launch's bit for bit."""
+    args, outs, held = [], [], []
+    for seg in (video, audio):
+        x, vc, vu, vp, mask, clean = seg["x"], seg["vel_cond"], seg.get("vel_uncond"), seg.get("vel_perturbed"), seg.get("mask"), seg.get("clean")
+        out = seg["out"] if seg.get("out") is not None else torch.empty_like(x)
+        assert vc is not None and (mask is None) == (clean is None)
+        n, c, ts = _step_operands(x, seg["timesteps"], (vc, vu, vp, clean, out), mask)
+        args += [nv.ptr(x), nv.ptr(vc), nv.ptr(vu), nv.ptr(vp), nv.ptr(ts), 0 if ts.numel() == 1 else 1, nv.ptr(mask), nv.ptr(clean),
+                 float(seg["cfg_scale"]), float(seg["stg_scale"]), nv.ptr(out), n, c]
+        outs.append(out)
+        held.append(ts)          # _step_operands may have made a contiguous fp32 copy: args holds its address only, so it must outlive the launch call
+    nv.check(nv.lib(dtype).ltx2_stg_euler_step_pair(*args, float(sigma), float(sigma_next), nv.stream()))
+    return outs[0], outs[1]
+
+
 def channel_guidance_stats_blocks(rows: int, c: int, dtype: Optional[torch.dtype] = None) -> int:
     """Rows of the fp64 [rows, 4, C] workspace that channel_guidance_stats fills for an [N, C] latent (ltx2_channel_guidance_stats_blocks)."""
     return int(nv.lib(dtype).ltx2_channel_guidance_stats_blocks(int(rows), int(c)))

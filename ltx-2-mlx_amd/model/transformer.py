@@ -923,6 +923,28 @@ class LTXModel:
         """Replay the graph captured by capture_guided_joint_graph."""
         self._replay("guided_joint", "no joint guided graph captured")
 
+    # ------------------------------------------------------------------ spatio-temporal guidance on both latents (AudioVideo engine)
+    def stg_step_joint_av_(self, neg: Optional["LTXModel"], latent: torch.Tensor, audio_latent: torch.Tensor, video: Modality, audio: Modality,
+                           sigma: float, sigma_next: float, cfg_scale: float, audio_cfg_scale: float, stg_scale: float, audio_stg_scale: float,
+                           vel_perturbed: torch.Tensor, audio_vel_perturbed: torch.Tensor, denoise_mask: Optional[torch.Tensor] = None,
+                           clean_latent: Optional[torch.Tensor] = None, audio_denoise_mask: Optional[torch.Tensor] = None,
+                           audio_clean_latent: Optional[torch.Tensor] = None) -> None:
+        """In-place on BOTH latents, (N, C) and (Na, Ca) fp32: one Euler step of the AudioVideo model under a CFGGuider and an STGGuider per modality
+        by ONE C call (ltx2_dit_stg_step_joint_av): both modalities through this context and through `neg` (None: no CFG on either), a perturbed
+        forward on this context itself -- the video self-attentions of set_stg_blocks(..., 0) and the audio ones of set_stg_blocks(..., 1)
+        skipped -- into vel_perturbed / audio_vel_perturbed (fp32 scratch of the latents' shapes), then x0 x 3 + both guiders +
+        post_process_latent + Euler over both latents in one launch.  A modality whose STG scale is 0 is stepped as guided_step_joint_av_ steps
+        it.  Both contexts are prepared by the caller (neg with the negative contexts).  There is no captured form."""
+        pos, ng = self._contexts(neg, av=True, optional=True)
+        ts, n_ts, sg, ats, n_ats = pos._step_inputs(latent, video, sigma, audio_latent, audio)
+        for scratch in (vel_perturbed, audio_vel_perturbed):
+            assert scratch.dtype == torch.float32 and scratch.is_contiguous()
+        nv.check(pos._L.ltx2_dit_stg_step_joint_av(pos._h, None if ng is None else ng._h, nv.ptr(latent), nv.ptr(audio_latent), nv.ptr(ts), n_ts,
+                                                   nv.ptr(ats), n_ats, nv.ptr(sg), nv.ptr(denoise_mask), nv.ptr(clean_latent),
+                                                   nv.ptr(audio_denoise_mask), nv.ptr(audio_clean_latent), nv.ptr(vel_perturbed), vel_perturbed.numel(),
+                                                   nv.ptr(audio_vel_perturbed), audio_vel_perturbed.numel(), float(cfg_scale), float(audio_cfg_scale),
+                                                   float(stg_scale), float(audio_stg_scale), float(sigma), float(sigma_next), nv.stream()))
+
     # ------------------------------------------------------------------ guiders whose scalars are sums over the latent (video-only engine)
     def projected_step_(self, neg: "LTXModel", latent: torch.Tensor, video: Modality, sigma: float, sigma_next: float, mode: int, scale: float,
                         eta: float = 1.0, norm_threshold: float = 0.0, momentum: float = 0.0, first: bool = True,

@@ -469,6 +469,97 @@ def stg_denoise_loop(transformer, video_state: LatentState, sigmas, context: tor
     return _with_latent(video_state, lat)
 
 
+def joint_stg_perturbations(stg_blocks: Optional[List[int]], video: bool, audio: bool):
+    """The BatchedPerturbationConfig (batch 1) of the joint STG loop: the video and / or the audio self-attention of `stg_blocks` (None: every
+    block) skipped."""
+    from ..components.perturbations import BatchedPerturbationConfig, Perturbation, PerturbationConfig, PerturbationType as PT
+    kinds = ([PT.SKIP_VIDEO_SELF_ATTN] if video else []) + ([PT.SKIP_AUDIO_SELF_ATTN] if audio else [])
+    return BatchedPerturbationConfig([PerturbationConfig([Perturbation(k, stg_blocks) for k in kinds])])
+
+
+def joint_stg_denoise_loop(transformer, video_state: LatentState, audio_state: LatentState, sigmas, video_context: torch.Tensor,
+                           audio_context: torch.Tensor, negative_video_context: Optional[torch.Tensor],
+                           negative_audio_context: Optional[torch.Tensor], video_guider, audio_guider, stg_guider, audio_stg_guider,
+                           stg_blocks: Optional[List[int]], stg_cutoff: float, callback=None, use_hip_graph: bool = True,
+                           fused: bool = True) -> Tuple[LatentState, LatentState]:
+    """Spatio-temporal guidance over BOTH modalities of an AudioVideo model (the joint branch of OneStagePipeline, pipelines/one_stage.py:466-568
+    with :516-526, and an STG term on the audio as the two-stage pipeline's multimodal guider applies one): while (step + 1) / n <= stg_cutoff --
+    decided in double on the host, as stg_denoise_loop decides it -- a third evaluation of the positive prompts with the video self-attention of
+    `stg_blocks` (None: every block) skipped when stg_guider is enabled and the audio self-attention of the same blocks when audio_stg_guider
+    is, and each enabled STG guider pushes its modality's CFG-guided prediction away from it.  video_guider / audio_guider: a plain CFGGuider,
+    None or not enabled, per modality; when neither is enabled there is no negative evaluation.  At least one STG guider is enabled.
+    fused=True: every step is ONE C call (LTXModel.stg_step_joint_av_: the two or three evaluations, then one kernel over both latents); the
+    steps past the cutoff are guided_step_joint_av_, or the plain joint step without CFG.  There is no captured form of this loop:
+    use_hip_graph is accepted for the signature the other loops share and answered with the usual one-time note.
+    fused=False: the same loop from the existing parts, the comparison form -- the X0Model calls through the same forward entries, the
+    guiders, post_process_latent and EulerDiffusionStep in torch.
+    Both latents are held in fp32 across the loop in either form; each modality takes the uniform or the per-token form by its own mask.
+    `transformer` is an X0Model over an AudioVideo model.  Returns (video_state, audio_state)."""
+    from ..components import EulerDiffusionStep
+    model = transformer.velocity_model
+    if not model.is_av or audio_state is None:
+        raise ValueError("joint_stg_denoise_loop requires an audio-video (AV) model and an audio state")
+    if audio_context is None:
+        raise ValueError("AudioVideo model: audio_encoding (the audio text context) is required")
+    guiders, stg_guiders = (video_guider, audio_guider), (stg_guider, audio_stg_guider)
+    if not heun_device_form(*guiders):
+        raise ValueError("joint_stg_denoise_loop runs under a plain CFGGuider (or none) per modality")
+    stg = [g.scale if (g is not None and g.enabled()) else 0.0 for g in stg_guiders]
+    if not any(stg):
+        raise ValueError("joint_stg_denoise_loop: neither STG guider is enabled; that loop is joint_projected_denoise_loop")
+    on = [g is not None and g.enabled() for g in guiders]
+    need_cfg = any(on)
+    if need_cfg and (negative_video_context is None or negative_audio_context is None):
+        raise ValueError("guidance needs the negative prompt's encoding(s)")
+    scale = [g.scale if e else 1.0 for g, e in zip(guiders, on)]
+    sig = [float(s) for s in sigmas]
+    n = len(sig) - 1
+    model, uniform, lat, mask, clean = _video_loop_inputs(model, video_state, video_only=False)
+    _, a_uniform, alat, amask, aclean = _video_loop_inputs(model, audio_state, video_only=False)
+    states = lambda: (video_state.replace(latent=lat[None]), audio_state.replace(latent=alat[None]))      # noqa: E731
+    modalities = lambda st, ast, vc, ac, s: (modality_from_state(st, vc, s, uniform=uniform),      # noqa: E731
+                                             audio_modality_from_state(ast, ac, s, uniform=a_uniform))
+    if not fused:
+        neg = X0Model(model.clone_sharing_weights()) if need_cfg else None
+        perturbations = joint_stg_perturbations(stg_blocks, stg[0] != 0.0, stg[1] != 0.0)
+        stepper = EulerDiffusionStep()
+        for i in range(n):
+            st, ast = states()
+            pair = modalities(st, ast, video_context, audio_context, sig[i])
+            x0 = list(transformer(*pair))
+            if need_cfg:
+                nx0 = neg(*modalities(st, ast, negative_video_context, negative_audio_context, sig[i]))
+                x0 = [g.guide(p, q) if e else p for g, e, p, q in zip(guiders, on, x0, nx0)]
+            if (i + 1) / n <= stg_cutoff:
+                px0 = transformer(*pair, perturbations=perturbations)
+                x0 = [g.guide(p, q) if s != 0.0 else p for g, s, p, q in zip(stg_guiders, stg, x0, px0)]
+            lat = stepper.step(sample=st.latent, denoised_sample=post_process_latent(x0[0], st.denoise_mask, st.clean_latent), sigmas=sig, step_index=i)[0]
+            alat = stepper.step(sample=ast.latent, denoised_sample=post_process_latent(x0[1], ast.denoise_mask, ast.clean_latent), sigmas=sig, step_index=i)[0]
+            if callback:
+                callback(i + 1, n)
+        return _with_latent(video_state, lat), _with_latent(audio_state, alat)
+    for k in (0, 1):
+        model.set_stg_blocks(stg_blocks if stg[k] != 0.0 else [], k)
+    neg = _prepare_contexts(model, need_cfg, not (uniform and a_uniform), video_state.positions, video_context, negative_video_context,
+                            audio_state.positions, audio_context, negative_audio_context)
+    cond = dict(denoise_mask=mask, clean_latent=clean, audio_denoise_mask=amask, audio_clean_latent=aclean)
+    vel_p, avel_p = torch.empty_like(lat), torch.empty_like(alat)
+    if use_hip_graph:
+        _note_eager_once("the joint audio+video STG loop has no captured form")
+
+    def step(i):
+        vm, am = modalities(*states(), video_context, audio_context, sig[i])
+        if (i + 1) / n <= stg_cutoff:
+            model.stg_step_joint_av_(neg, lat, alat, vm, am, sig[i], sig[i + 1], scale[0], scale[1], stg[0], stg[1], vel_p, avel_p, **cond)
+        elif need_cfg:
+            model.guided_step_joint_av_(neg, lat, alat, vm, am, sig[i], sig[i + 1], scale[0], scale[1], **cond)
+        else:
+            model.denoise_step_(lat, vm, sig[i], sig[i + 1], audio_latent=alat, audio=am, **cond)
+
+    _run_steps(n, callback, use_hip_graph, None, None, step)
+    return _with_latent(video_state, lat), _with_latent(audio_state, alat)
+
+
 def frozen_audio_guided_loop(transformer, video_state: LatentState, audio_state: LatentState, sigmas, video_context: torch.Tensor,
                              audio_context: torch.Tensor, negative_video_context: Optional[torch.Tensor],
                              negative_audio_context: Optional[torch.Tensor], cfg_scale: float, stepper, callback=None,

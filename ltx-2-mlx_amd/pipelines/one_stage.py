@@ -21,8 +21,12 @@ and 219.6 with the capture against 202.4 eager), so this pipeline does not take 
 Spatio-temporal guidance: `stg_scale` > 0 adds, while (step + 1) / steps <= `stg_cutoff`, a third evaluation of the positive prompt with the video
 self-attention of `stg_blocks` (None: every block) skipped, and STGGuider pushes the guided video prediction away from it (:284-297, :516-526).
 Without an audio state and with a plain CFGGuider (or none enabled) the loop is pipelines.common.stg_denoise_loop: one C call per step, one
-captured graph per loop.  With CFG* (the config default) or a projected override, and on the joint audio+video branch, it is the eager loop:
-three evaluations, the guiders in torch.  Only the video is STG-guided.
+captured graph per loop.  With CFG* (the config default) or a projected override, with or without an audio state, it is the eager loop: three
+evaluations, the guiders in torch; there only the video is STG-guided.
+With an audio state and a plain CFGGuider per modality (or none enabled) the loop is pipelines.common.joint_stg_denoise_loop: one C call per step
+(LTXModel.stg_step_joint_av_: the evaluations, then one kernel over both latents), no captured form.  `stg_audio_scale` > 0 (this loop alone)
+STG-guides the audio latent too: the perturbed evaluation also skips the audio self-attention of `stg_blocks`, and an STGGuider of that scale acts
+on the CFG-guided audio prediction.  With `stg_audio_scale` 0 the audio gets plain CFG, as on the eager loop.
 
 `sampler="heun"` runs the reference's predictor-corrector loops (:334-464, :570-729) and `ge_gamma` > 0 its GE velocity correction on the video's
 guided prediction (:300-307), in either sampler.  Under a plain CFGGuider per modality (or none enabled) the loop is
@@ -50,7 +54,7 @@ from ..model.transformer import LTXModel, X0Model
 from ..model.video_vae import SimpleVideoDecoder, TilingConfig
 from ..types import AudioLatentShape, VideoPixelShape
 from .common import (ImageCondition, as_x0model, auto_tiling_config, conditioned_initial_state, create_image_conditionings, decode_video,
-                     final_latent, ge_denoise_loop, heun_denoise_loop, heun_device_form, joint_denoise_loop, projected_denoise_loop, projected_guider_args, reset_guider, seeded_noiser, stg_denoise_loop, video_tools_for)
+                     final_latent, ge_denoise_loop, heun_denoise_loop, heun_device_form, joint_denoise_loop, joint_stg_denoise_loop, projected_denoise_loop, projected_guider_args, reset_guider, seeded_noiser, stg_denoise_loop, video_tools_for)
 
 
 @dataclass
@@ -125,7 +129,7 @@ class OneStagePipeline:
                  positive_audio_encoding: Optional[torch.Tensor] = None, negative_audio_encoding: Optional[torch.Tensor] = None,
                  stg_scale: float = 0.0, stg_blocks: Optional[List[int]] = None, stg_cutoff: float = 1.0, guider_override=None,
                  ge_gamma: float = 0.0, sampler: str = "euler", temporal_upscaler=None, cross_attn_scale: float = 1.0,
-                 cross_attn_start_block: int = 40, *, initial_noise: Optional[torch.Tensor] = None,
+                 cross_attn_start_block: int = 40, *, stg_audio_scale: float = 0.0, initial_noise: Optional[torch.Tensor] = None,
                  initial_audio_noise: Optional[torch.Tensor] = None,
                  initial_audio_latent: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         """-> (video, audio): video uint8 frames (F, H, W, 3) (or the final latent when no decoder is set); audio = the
@@ -138,7 +142,10 @@ class OneStagePipeline:
         initial_audio_latent (keyword-only): an encoded audio latent (1, 8, T_a, 16) (model/audio_vae AudioEncoder) the video is generated
         TO: the audio state starts from it with denoise_mask = 0 and is not noised, so every step leaves it as it is and only the video is
         denoised (reference pipelines/a2vid_two_stage.py:338-357).  Needs an AudioVideo transformer.  The returned audio is then this
-        latent, never VAE-decoded (the reference returns the original waveform)."""
+        latent, never VAE-decoded (the reference returns the original waveform).
+        stg_audio_scale (keyword-only, MI355X addition): > 0 adds an STG term of that scale to the AUDIO prediction, from the same perturbed
+        evaluation, which then skips the audio self-attention of `stg_blocks` as well; stg_blocks / stg_cutoff hold for both modalities.  Needs
+        an audio state (ValueError without one) and a plain CFGGuider per modality or none enabled (NotImplementedError under CFG* / APG)."""
         images = images or []
         internal_audio_active = self.is_av_model and (config.use_internal_audio_branch or config.audio_enabled)
         if config.audio_enabled or internal_audio_active:
@@ -149,20 +156,23 @@ class OneStagePipeline:
         if initial_audio_latent is not None and not internal_audio_active:
             raise ValueError("initial_audio_latent needs an AudioVideo transformer (the audio branch carries the frozen latent)")
         # STG is validated here; the gate below then sees the remaining options (it refuses every stg_scale > 0 on its own)
-        stg_guider = None
-        if stg_scale > 0:
+        stg_guider = audio_stg_guider = None
+        if stg_audio_scale > 0 and not internal_audio_active:
+            raise ValueError("stg_audio_scale > 0 needs an audio state (an AudioVideo transformer with its audio branch active)")
+        if stg_scale > 0 or stg_audio_scale > 0:
             layers = self.transformer.velocity_model.num_layers
             bad = [b for b in (stg_blocks or []) if not 0 <= int(b) < layers]
             if bad:
                 raise ValueError(f"stg_blocks {bad} out of range: the model has {layers} layers")
             if not 0.0 <= stg_cutoff <= 1.0:
                 raise ValueError(f"stg_cutoff={stg_cutoff} must lie in [0, 1]")
-            stg_guider = STGGuider(scale=stg_scale)
+            stg_guider = STGGuider(scale=stg_scale) if stg_scale > 0 else None
+            audio_stg_guider = STGGuider(scale=stg_audio_scale) if stg_audio_scale > 0 else None
         if sampler not in ("euler", "heun"):
             raise ValueError(f"sampler={sampler!r}: 'euler' or 'heun'")
         # Heun and GE are built without STG; beside it they stay refused, so the gate sees them only then
         heun, ge = sampler == "heun", ge_gamma > 0
-        if stg_guider is None:
+        if stg_guider is None and audio_stg_guider is None:
             self._require_no_guidance(0.0, guider_override, 0.0, "euler", temporal_upscaler, cross_attn_scale)
         else:
             self._require_no_guidance(0.0, guider_override, ge_gamma, sampler, temporal_upscaler, cross_attn_scale)
@@ -208,6 +218,14 @@ class OneStagePipeline:
             video_state, audio_state = loop(self.transformer, video_state, audio_state, sigmas, positive_encoding.to(dev), actx,
                                             negative_encoding.to(dev) if need_cfg else None, nactx, video_guider,
                                             audio_guider if audio_state is not None else None, max(float(ge_gamma), 0.0), callback, config.use_hip_graph, fused)
+        elif (stg_guider is not None or audio_stg_guider is not None) and audio_state is not None and heun_device_form(video_guider, audio_guider):
+            # both latents: forward_av x 2 or 3 (one of them perturbed) and one kernel over both per step, on the device
+            video_state, audio_state = joint_stg_denoise_loop(self.transformer, video_state, audio_state, sigmas, positive_encoding.to(dev), actx,
+                                                              negative_encoding.to(dev) if need_cfg else None, nactx, video_guider, audio_guider,
+                                                              stg_guider, audio_stg_guider, stg_blocks, stg_cutoff, callback, config.use_hip_graph)
+        elif audio_stg_guider is not None:
+            raise NotImplementedError("stg_audio_scale > 0 runs under a plain CFGGuider per modality (rescale_scale = 0, no projected guider_override) or "
+                                      "none enabled: beside CFG* / APG the eager loop STG-guides the video alone")
         elif stg_guider is not None and audio_state is None and (type(video_guider) is CFGGuider or not video_guider.enabled()):
             # forward x 2 or 3 and one kernel per step, on the device
             video_state = stg_denoise_loop(self.transformer, video_state, sigmas, positive_encoding.to(dev),

@@ -6,7 +6,7 @@ scripts/generate.py (argparse block :2364-2641, `generate_video` :933-997) for t
 standard single-stage distilled loop (reference :1764-1984) followed by `decode_latent` (:2080-2091).
 Gemma-3 encodes the prompt on the GPU when `--gemma-path` holds its weights (model/text_encoder/gemma3.py; reference
 encode_with_gemma :340-486, encode_av_gemma_batch :511-640; an LTX-2.3 checkpoint gets the V2 text encoder, create_av_text_encoder_v2_from_checkpoint
-:548-551).  `--stg-scale S [--stg-blocks ... --stg-cutoff F]` adds spatio-temporal guidance on the av route (OneStagePipeline);
+:548-551).  `--stg-scale S [--stg-blocks ... --stg-cutoff F]` adds spatio-temporal guidance on the av route (OneStagePipeline), `--stg-audio-scale S` an STG term on the audio latent too (plain CFG or none);
 `--sampler heun` and `--ge-gamma G` run its Heun loop and its GE velocity correction there.  Out of this path (and rejected
 with a clear message): STG guidance, Heun and GE on every other route and Heun / GE beside STG, CFG in the video-only loop, the dev model's `--pipeline two-stage`.
 `generate_video` resolves its arguments once (`_resolve_request`: every refusal, before a model is loaded), loads the text encoding, the transformer and the VAE decoder, and
@@ -564,7 +564,7 @@ def euler_step_x0(sample, denoised, sigma, sigma_next):
 _OUT_OF_PATH_DEFAULTS = dict(
     early_layers_only=False, enhance_prompt_flag=False,
     cross_attn_scale=1.0, distilled_lora=None, stg_scale=0.0, apg_scale=1.0, control_video=None, save_control=False,
-    ge_gamma=0.0, keyframes=None, ic_lora_weights=None, negative_prompt=None)
+    ge_gamma=0.0, keyframes=None, ic_lora_weights=None, negative_prompt=None, stg_audio_scale=0.0)
 # pipelines whose algorithm is not built: "two-stage" is the dev model's CFG stage 1 + distilled-LoRA stage 2 (TwoStageCFGConfig,
 # reference :1276-1431).  "keyframe-interpolation" (:1552-1637) is built, but only WITH keyframes, and "ic-lora" (:1434-1549) only WITH a
 # control video and / or an image: without them they are refused like "two-stage" (the reference raises ValueError there)
@@ -635,10 +635,10 @@ _ROUTE_EXCLUDES = {
                      "on the video-only dev model"),
 }
 # route -> the _OUT_OF_PATH_DEFAULTS arguments that route takes itself.  apg_scale: the routes whose guided loop takes a guider (the AudioVideo route as
-# OneStagePipeline's guider_override, keyframe stage 1, retake's guided mode).  stg_scale and ge_gamma: OneStagePipeline alone (the AudioVideo route), and not
-# together (_check_sampler)
+# OneStagePipeline's guider_override, keyframe stage 1, retake's guided mode).  stg_scale, stg_audio_scale and ge_gamma: OneStagePipeline alone (the AudioVideo
+# route), and GE not beside STG (_check_sampler)
 _ROUTE_OWNS = {"keyframe": ("keyframes", "apg_scale"), "hq": ("distilled_lora", "keyframes"),
-               "ic_lora": ("control_video", "save_control", "keyframes", "ic_lora_weights"), "retake": ("apg_scale",), "av": ("apg_scale", "stg_scale", "ge_gamma"), "a2vid": ("distilled_lora",),
+               "ic_lora": ("control_video", "save_control", "keyframes", "ic_lora_weights"), "retake": ("apg_scale",), "av": ("apg_scale", "stg_scale", "stg_audio_scale", "ge_gamma"), "a2vid": ("distilled_lora",),
                "hq_av": ("distilled_lora",), "two_stage_cfg": ("distilled_lora",), "standard_cfg": ("negative_prompt", "cross_attn_scale"),
                "retake_av": ()}          # no guider override on the joint audio+video loop: apg_scale keeps its out-of-path refusal
 
@@ -671,8 +671,11 @@ def _apg_guider(r):
 
 
 def _check_stg(r):
-    """stg_scale > 0 (the reference enables STG for nothing else, :1246): the mode that is built, block indices of this model, a cutoff that is a fraction of the steps."""
-    if not r.stg_scale > 0:
+    """stg_scale > 0 (the reference enables STG for nothing else, :1246) or stg_audio_scale > 0: the mode that is built, block indices of this model, a cutoff that is a
+    fraction of the steps.  stg_audio_scale is a number, not a negative one; it needs no stg_scale beside it (the audio alone may be STG-guided)."""
+    if r.stg_audio_scale < 0:
+        raise ValueError(f"stg_audio_scale={r.stg_audio_scale} must not be negative (0: the audio latent is not STG-guided)")
+    if not (r.stg_scale > 0 or r.stg_audio_scale > 0):
         return
     if r.stg_mode != "video":
         raise NotImplementedError(f"stg_mode={r.stg_mode!r}: STG skips the video self-attention (the reference prints the mode and does the same); leave it at 'video'")
@@ -692,6 +695,8 @@ def _check_sampler(r, owner):
                                   "leave it at its default 'euler'")
     if r.stg_scale > 0:
         raise NotImplementedError(f"sampler={r.sampler!r} beside stg_scale={r.stg_scale!r} is outside the MI355X hot path (see DESIGN.md)")
+    if r.stg_audio_scale > 0:
+        raise NotImplementedError(f"sampler={r.sampler!r} beside stg_audio_scale={r.stg_audio_scale!r} is outside the MI355X hot path (see DESIGN.md)")
 
 
 def _refuse_combinations(r):
@@ -855,10 +860,10 @@ def _resolve_request(kw: dict):
     r.gemma_encodes = bool(r.use_gemma and not (r.embedding_path or r.text_features_path) and r.gemma_path and os.path.exists(r.gemma_path))
     if r.sampler not in ("euler", "heun"):
         raise ValueError(f"sampler={r.sampler!r}: 'euler' or 'heun'")
-    asks_av = r.apg_scale != 1.0 or r.stg_scale != 0.0 or r.ge_gamma != 0.0 or r.sampler != "euler"
+    asks_av = r.apg_scale != 1.0 or r.stg_scale != 0.0 or r.stg_audio_scale != 0.0 or r.ge_gamma != 0.0 or r.sampler != "euler"
     owner = _owning_route(r) if asks_av else r.route
     owns = _ROUTE_OWNS.get(owner, ())
-    if r.stg_scale > 0:
+    if r.stg_scale > 0 or r.stg_audio_scale > 0:
         owns = tuple(k for k in owns if k != "ge_gamma")          # GE beside STG is not built: its out-of-path refusal
     for k, default in _OUT_OF_PATH_DEFAULTS.items():
         if k in owns or (k == "negative_prompt" and r.gemma_encodes):
@@ -919,9 +924,14 @@ def _resolve_request(kw: dict):
         r.rescale_scale = 0.0 if r.model_variant == "distilled" else 0.7
     if r.stg_scale > 0:
         print(f"STG guidance: scale={r.stg_scale}, mode={r.stg_mode}")           # the settings banner's line (reference :1031-1032); the second one: _run_av
+    if r.stg_audio_scale > 0:
+        print(f"Audio STG guidance: scale={r.stg_audio_scale} (the audio self-attention of the STG blocks is skipped too)")
     if r.sampler == "heun" or r.ge_gamma > 0:
         print(f"Sampler: {r.sampler}" + (" (2x model evals per step)" if r.sampler == "heun" else "") + (f", GE gamma={r.ge_gamma}" if r.ge_gamma > 0 else ""))
     r.apg_guider = _apg_guider(r)
+    if r.stg_audio_scale > 0 and (r.apg_guider is not None or (r.rescale_scale > 0 and (r.cfg_scale != 1.0 or r.audio_cfg_scale != 1.0))):
+        raise NotImplementedError(f"stg_audio_scale={r.stg_audio_scale!r} runs under plain CFG (rescale_scale=0.0, apg_scale=1.0) or without guidance: beside "
+                                  "CFG* / APG the eager loop STG-guides the video alone")
     r.negative_encoding = r.negative_audio_encoding = None
     if r.embedding_path and os.path.exists(r.embedding_path):
         with np.load(r.embedding_path) as z:                # optional entries of the pre-computed embedding file: the negative prompt's encodings
@@ -1465,6 +1475,8 @@ def _run_av(r, s):
     if r.stg_scale > 0:
         print(f"  STG guidance enabled (scale={r.stg_scale})")
         stg = dict(stg_scale=r.stg_scale, stg_blocks=r.stg_blocks, stg_cutoff=r.stg_cutoff)
+    if r.stg_audio_scale > 0:
+        stg.update(stg_audio_scale=r.stg_audio_scale, stg_blocks=r.stg_blocks, stg_cutoff=r.stg_cutoff)
     if r.sampler == "heun" or r.ge_gamma > 0:
         stg.update(sampler=r.sampler, ge_gamma=r.ge_gamma)
     print(f"[5/5] Running audio-video generation ({r.num_steps} steps)...")
@@ -1651,7 +1663,8 @@ def generate_video(
     # MI355X additions (keyword-only; the reference has no counterpart)
     stg_blocks: Optional[List[int]] = None,        # with stg_scale: what OneStagePipeline takes beside it (the reference's CLI leaves them at these defaults)
     stg_cutoff: float = 1.0,
-    sampler: str = "euler",                        # "heun": OneStagePipeline's predictor-corrector loop (the reference's own CLI never reaches it)
+    stg_audio_scale: float = 0.0,                  # > 0: the AudioVideo route STG-guides the audio latent too (OneStagePipeline's stg_audio_scale; plain CFG or none)
+    sampler: str = "euler",                       # "heun": OneStagePipeline's predictor-corrector loop (the reference's own CLI never reaches it)
     use_hip_graph: bool = True,
     num_layers: int = 48,
     num_heads: int = 32,
@@ -1812,6 +1825,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--retake-audio-cfg", type=float, default=None, help="with --retake-audio: guidance scale of the audio latent (default: --cfg)")
     p.add_argument("--stg-blocks", type=int, nargs="+", default=None, help="with --stg-scale: the blocks whose video self-attention the perturbed pass skips (default: all)")
     p.add_argument("--stg-cutoff", type=float, default=1.0, help="with --stg-scale: STG guides the first fraction of the steps, (step + 1) / steps <= cutoff")
+    p.add_argument("--stg-audio-scale", type=float, default=0.0,
+                   help="AudioVideo route, plain CFG (rescale_scale=0) or no guidance (--model-variant distilled): STG-guide the audio latent too, at this scale (the perturbed pass then skips the audio "
+                        "self-attention of --stg-blocks as well); with or without --stg-scale")
     p.add_argument("--sampler", type=str, choices=["euler", "heun"], default="euler", help="on the AudioVideo route (OneStagePipeline): heun runs the second-order "
                    "predictor-corrector loop, two guided evaluations per step; --ge-gamma adds the GE velocity correction to either sampler")
     return p
@@ -1848,7 +1864,7 @@ def kwargs_from_args(a) -> dict:
         two_stage_cfg=a.two_stage_cfg, modality_scale=a.modality_scale, standard_cfg=a.standard_cfg,
         retake_audio=a.retake_audio, retake_audio_cfg=a.retake_audio_cfg,
         retake_video=a.retake, retake_start_time=a.retake_start, retake_end_time=a.retake_end, retake_composite=a.retake_keep_source,
-        stg_blocks=a.stg_blocks, stg_cutoff=a.stg_cutoff, sampler=a.sampler)
+        stg_blocks=a.stg_blocks, stg_cutoff=a.stg_cutoff, stg_audio_scale=a.stg_audio_scale, sampler=a.sampler)
 
 
 def main(argv=None):
