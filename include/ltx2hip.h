@@ -310,6 +310,40 @@ int ltx2_guided_euler_step_pair(const float* v_x, const float* v_vel_cond, const
                                 const float* a_clean, float a_cfg_scale, float* a_out, int a_rows, int a_C, float sigma, float sigma_next,
                                 void* stream);
 
+/* Counter-based noise for the stochastic sampler: Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85).
+ * Quad q has the counter (lo32(q), hi32(q), step, stream_id) and the key (lo32(seed), hi32(seed)); its four words r0..r3 serve the elements
+ * 4q .. 4q+3 of a latent.  seed_dev: a device pointer to one 64-bit word (8-byte aligned), read when the kernel runs -- a captured graph serves
+ * any seed.  stream_id: 0 the video latent, 1 the audio latent.
+ *   ltx2_philox_bits:   out[n_quads][4], the raw words (the hook for the Random123 known-answer vectors).
+ *   ltx2_philox_normal: out[n] fp32 N(0,1): u_k = ((r_k >> 9) + 0.5)*2^-23 (exact, inside (0, 1)); z0 = sqrt(-2 ln u0)*cos(2 pi u1),
+ *                       z1 = sqrt(-2 ln u0)*sin(2 pi u1), z2 / z3 from (u2, u3); accurate logf / sincospif, every operation rounded on its own.
+ * The values are a function of (seed, step, stream_id, element index) alone: not of the grid, the access width or n.
+ * (additive entries of ABI version 3)                                                                                                      */
+int ltx2_philox_bits(uint32_t* out, int64_t n_quads, const uint64_t* seed_dev, uint32_t step, uint32_t stream_id, void* stream);
+int ltx2_philox_normal(float* out, int64_t n, const uint64_t* seed_dev, uint32_t step, uint32_t stream_id, void* stream);
+
+/* The Euler-ancestral step (EulerAncestralDiffusionStep, reference components/diffusion_steps.py:70-129) in ONE pass with the noise made in the
+ * kernel.  sigma_up / sigma_down: _get_ancestral_step(sigma, sigma_next, eta) evaluated by the caller in double.  Per element:
+ *   d as ltx2_guided_euler_step forms it;  r = x + ((x - d) * (1/sigma)) * (sigma_down - sigma);  out = r + ((z * sigma_up) * m)
+ * with z = the ltx2_philox_normal value of element row*C + c under (seed, step, stream 0) and m = mask[row] (1 without a mask).  The mask on the
+ * noise is a departure from the reference, which adds noise to conditioned tokens too; with m = 1 the arithmetic is the reference's.
+ * vel_uncond NULL: no guidance, and r in the arithmetic of ltx2_x0_from_velocity + ltx2_euler_step.  sigma_up == 0: no noise is evaluated and
+ * out = r, ltx2_guided_euler_step's bits for sigma_next = sigma_down.  out may equal any input.  LTX2_E_INVALID: sigma == 0 ("Sigma can't be
+ * 0.0"), a negative sigma_up / sigma_down, seed_dev NULL or off its 8-byte boundary, and the rules of ltx2_guided_euler_step.
+ * _pair: the video latent (stream 0) then the audio latent (stream 1) in one launch, each segment the single launch's bits.
+ * _x0: from a ready x0; d = clean ? x0*m + clean*(1 - m) : x0.  A mask WITHOUT a clean latent scales the noise alone (the caller has blended x0).
+ * (additive entries of ABI version 3)                                                                                                      */
+int ltx2_ancestral_euler_step(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, int64_t ts_stride, const float* mask,
+                              const float* clean, float cfg_scale, float sigma, float sigma_up, float sigma_down, const uint64_t* seed_dev,
+                              uint32_t step, float* out, int rows, int C, void* stream);
+int ltx2_ancestral_euler_step_pair(const float* v_x, const float* v_vel_cond, const float* v_vel_uncond, const float* v_ts, int64_t v_ts_stride,
+                                   const float* v_mask, const float* v_clean, float v_cfg_scale, float* v_out, int v_rows, int v_C, const float* a_x,
+                                   const float* a_vel_cond, const float* a_vel_uncond, const float* a_ts, int64_t a_ts_stride, const float* a_mask,
+                                   const float* a_clean, float a_cfg_scale, float* a_out, int a_rows, int a_C, float sigma, float sigma_up,
+                                   float sigma_down, const uint64_t* seed_dev, uint32_t step, void* stream);
+int ltx2_ancestral_euler_step_x0(const float* x, const float* x0, const float* mask, const float* clean, float sigma, float sigma_up, float sigma_down,
+                                 const uint64_t* seed_dev, uint32_t step, uint32_t stream_id, float* out, int rows, int C, void* stream);
+
 /* ltx2_guided_euler_step with spatio-temporal guidance (STG) on top: STGGuider.guide applied to the CFG-guided x0 (pipelines/one_stage.py:284-297).
  * vel_perturbed is the velocity of a forward whose chosen self-attentions were skipped (ltx2_dit_forward_perturbed).  Per element, every
  * operation individually rounded, so the result equals the separate fp32 torch ops bit for bit:
@@ -740,6 +774,27 @@ int ltx2_dit_graph_capture_guided_joint_av(ltx2_dit* ctx, ltx2_dit* neg, float* 
                                            const float* v_mask, int64_t n_v_mask, const float* v_clean, int64_t n_v_clean, const float* a_mask,
                                            int64_t n_a_mask, const float* a_clean, int64_t n_a_clean, float cfg_scale, float audio_cfg_scale,
                                            void* stream);
+/* The Euler-ancestral step on the engine: ltx2_dit_guided_step (VideoOnly contexts) and ltx2_dit_guided_step_joint_av (AudioVideo contexts, both
+ * latents stepped) with ltx2_ancestral_euler_step / _pair in place of the guided Euler kernel.  neg NULL: no guidance, one evaluation.  The same
+ * forwards and the same validity rules; besides, LTX2_E_INVALID for a negative sigma_up / sigma_down and a NULL or misaligned seed_dev.
+ * ltx2_dit_graph_capture_ancestral / _joint_av: n_steps (< 64) as one captured linear chain owned by ctx; step i bakes in step = i and
+ * host_sigma_up[i] / host_sigma_down[i] (n_steps values each), seed_dev stays a pointer: writing another seed and replaying gives that seed's
+ * result.  (additive entries of ABI version 3)                                                                                            */
+int ltx2_dit_ancestral_step(ltx2_dit* ctx, ltx2_dit* neg, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev,
+                            const float* mask, const float* clean, float cfg_scale, float sigma, float sigma_up, float sigma_down,
+                            const uint64_t* seed_dev, uint32_t step, void* stream);
+int ltx2_dit_ancestral_step_joint_av(ltx2_dit* ctx, ltx2_dit* neg, float* v_latent, float* a_latent, const float* v_timesteps, int n_v_timesteps,
+                                     const float* a_timesteps, int n_a_timesteps, const float* sigma_dev, const float* v_mask, const float* v_clean,
+                                     const float* a_mask, const float* a_clean, float cfg_scale, float audio_cfg_scale, float sigma, float sigma_up,
+                                     float sigma_down, const uint64_t* seed_dev, uint32_t step, void* stream);
+int ltx2_dit_graph_capture_ancestral(ltx2_dit* ctx, ltx2_dit* neg, float* latent, const float* host_sigmas, int n_steps, const float* mask, int64_t n_mask,
+                                     const float* clean, int64_t n_clean, float cfg_scale, const float* host_sigma_up, const float* host_sigma_down,
+                                     const uint64_t* seed_dev, void* stream);
+int ltx2_dit_graph_capture_ancestral_joint_av(ltx2_dit* ctx, ltx2_dit* neg, float* v_latent, float* a_latent, const float* host_sigmas, int n_steps,
+                                              const float* v_mask, int64_t n_v_mask, const float* v_clean, int64_t n_v_clean, const float* a_mask,
+                                              int64_t n_a_mask, const float* a_clean, int64_t n_a_clean, float cfg_scale, float audio_cfg_scale,
+                                              const float* host_sigma_up, const float* host_sigma_down,
+                                              const uint64_t* seed_dev, void* stream);
 /* The STG step on the AudioVideo engine with BOTH latents stepped and an STG term per modality (OneStagePipeline's joint branch with stg_scale and / or
  * stg_audio_scale): forward_av on ctx and, when neg is given (NULL: neither modality has CFG), on neg, exactly as ltx2_dit_guided_step_joint_av builds
  * them; then ltx2_dit_forward_perturbed_av on ctx ITSELF (the sets of ltx2_dit_set_stg_blocks, per modality; no third context) into the caller's

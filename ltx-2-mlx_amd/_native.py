@@ -33,7 +33,7 @@ CANNY_TILE_H, CANNY_TILE_W, CANNY_FLAG_BYTES = 32, 64, 16      # LTX2_CANNY_TILE
 RETAKE_MAX_RAMP = 65535                                        # LTX2_RETAKE_MAX_RAMP
 RETAKE_AUDIO_MAX_RAMP = 16777215                               # LTX2_RETAKE_AUDIO_MAX_RAMP
 
-vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_float
+vp, i32, i64, f32, u32 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint32
 
 
 class DitConfig(C.Structure):
@@ -91,6 +91,12 @@ SIGNATURES = {
     "ltx2_guided_euler_step": (i32, [vp, vp, vp, vp, i64, vp, vp, f32, f32, f32, vp, i32, i32, vp]),
     "ltx2_guided_euler_step_pair": (i32, [vp, vp, vp, vp, i64, vp, vp, f32, vp, i32, i32,
                                           vp, vp, vp, vp, i64, vp, vp, f32, vp, i32, i32, f32, f32, vp]),
+    "ltx2_philox_bits": (i32, [vp, i64, vp, u32, u32, vp]),
+    "ltx2_philox_normal": (i32, [vp, i64, vp, u32, u32, vp]),
+    "ltx2_ancestral_euler_step": (i32, [vp, vp, vp, vp, i64, vp, vp, f32, f32, f32, f32, vp, u32, vp, i32, i32, vp]),
+    "ltx2_ancestral_euler_step_pair": (i32, [vp, vp, vp, vp, i64, vp, vp, f32, vp, i32, i32,
+                                             vp, vp, vp, vp, i64, vp, vp, f32, vp, i32, i32, f32, f32, f32, vp, u32, vp]),
+    "ltx2_ancestral_euler_step_x0": (i32, [vp, vp, vp, vp, f32, f32, f32, vp, u32, u32, vp, i32, i32, vp]),
     "ltx2_stg_euler_step": (i32, [vp, vp, vp, vp, vp, i64, vp, vp, f32, f32, f32, f32, vp, i32, i32, vp]),
     "ltx2_stg_euler_step_pair": (i32, [vp, vp, vp, vp, vp, i64, vp, vp, f32, f32, vp, i32, i32,
                                        vp, vp, vp, vp, vp, i64, vp, vp, f32, f32, vp, i32, i32, f32, f32, vp]),
@@ -165,6 +171,11 @@ SIGNATURES = {
     "ltx2_dit_graph_capture_guided_av": (i32, [vp, vp, vp, vp, C.POINTER(f32), i32, vp, i64, vp, i64, vp, i64, f32, vp]),
     "ltx2_dit_guided_step_joint_av": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, f32, f32, f32, f32, vp]),
     "ltx2_dit_graph_capture_guided_joint_av": (i32, [vp, vp, vp, vp, C.POINTER(f32), i32, vp, i64, vp, i64, vp, i64, vp, i64, f32, f32, vp]),
+    "ltx2_dit_ancestral_step": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, f32, f32, f32, f32, vp, u32, vp]),
+    "ltx2_dit_ancestral_step_joint_av": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, f32, f32, f32, f32, f32, vp, u32, vp]),
+    "ltx2_dit_graph_capture_ancestral": (i32, [vp, vp, vp, C.POINTER(f32), i32, vp, i64, vp, i64, f32, C.POINTER(f32), C.POINTER(f32), vp, vp]),
+    "ltx2_dit_graph_capture_ancestral_joint_av": (i32, [vp, vp, vp, vp, C.POINTER(f32), i32, vp, i64, vp, i64, vp, i64, vp, i64, f32, f32,
+                                                        C.POINTER(f32), C.POINTER(f32), vp, vp]),
     "ltx2_dit_projected_step": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, i32, f32, f32, f32, f32, i32, f32, f32, vp]),
     "ltx2_dit_graph_capture_projected": (i32, [vp, vp, vp, C.POINTER(f32), i32, vp, i64, vp, i64, i32, f32, f32, f32, f32, vp]),
     "ltx2_dit_projected_step_joint_av": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, i32, f32, f32, f32, f32, vp, i64,

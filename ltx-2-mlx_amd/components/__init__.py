@@ -1,4 +1,4 @@
-from .diffusion_steps import EulerDiffusionStep, HeunDiffusionStep, to_denoised, to_velocity
+from .diffusion_steps import EulerAncestralDiffusionStep, EulerDiffusionStep, HeunDiffusionStep, to_denoised, to_velocity
 from .guiders import (CFGGuider, CFGStarRescalingGuider, LegacyStatefulAPGGuider, LtxAPGGuider, MultiModalGuider, MultiModalGuiderParams, STGGuider,
                       projection_coef)
 from .noisers import GaussianNoiser
@@ -10,6 +10,6 @@ from .schedulers import (DISTILLED_SIGMA_VALUES, STAGE_2_DISTILLED_SIGMA_VALUES,
                          get_sigma_schedule)
 
 __all__ = ["CFGGuider", "CFGStarRescalingGuider", "LtxAPGGuider", "LegacyStatefulAPGGuider", "STGGuider", "MultiModalGuider", "MultiModalGuiderParams", "projection_coef", "PerturbationType", "Perturbation", "PerturbationConfig",
-           "BatchedPerturbationConfig", "create_stg_perturbation", "create_batched_stg_config", "EulerDiffusionStep", "HeunDiffusionStep", "to_denoised", "to_velocity", "GaussianNoiser", "AudioPatchifier", "VideoLatentPatchifier",
+           "BatchedPerturbationConfig", "create_stg_perturbation", "create_batched_stg_config", "EulerDiffusionStep", "EulerAncestralDiffusionStep", "HeunDiffusionStep", "to_denoised", "to_velocity", "GaussianNoiser", "AudioPatchifier", "VideoLatentPatchifier",
            "get_pixel_coords", "DISTILLED_SIGMA_VALUES", "STAGE_2_DISTILLED_SIGMA_VALUES", "LTX2Scheduler",
            "get_sigma_schedule", "phi", "get_res2s_coefficients"]

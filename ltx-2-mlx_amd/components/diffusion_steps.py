@@ -51,3 +51,43 @@ class HeunDiffusionStep:
             return predicted.to(sample.dtype)
         velocity_at_predicted = to_velocity(predicted.to(sample.dtype), sigma_next, denoised_at_predicted).float()
         return (sample_f32 + (0.5 * (velocity + velocity_at_predicted)) * dt).to(sample.dtype)
+
+
+class EulerAncestralDiffusionStep:
+    """The reference's stochastic sampler (components/diffusion_steps.py:70-129, its note: ComfyUI's euler_ancestral_cfg_pp): the Euler step to
+    sigma_down, then sigma_up * N(0,1) on top.  Without `noise` the step is ONE kernel (ltx2_ancestral_euler_step_x0) whose noise is Philox4x32-10
+    under (seed, step_index, stream_id, element index) -- no host generator, the same values however the step is launched.  With a given `noise`
+    tensor the step is the reference's statements in torch, on whatever device the tensors live.  `eta` scales the noise (the reference's step
+    always takes 1.0); eta = 0 is the Euler step."""
+
+    def __init__(self, eta: float = 1.0, seed: int = 0):
+        self.eta = float(eta)
+        self.seed = int(seed)
+        self._seed_word = None
+
+    @staticmethod
+    def _get_ancestral_step(sigma_from: float, sigma_to: float, eta: float = 1.0):
+        """(sigma_up, sigma_down) of a step from sigma_from to sigma_to, in double: sigma_up = min(sigma_to, eta * sigma_to *
+        sqrt(1 - sigma_to^2 / sigma_from^2)) written as the reference writes it, sigma_down^2 = sigma_to^2 - sigma_up^2; (0, 0) at sigma_to = 0."""
+        if sigma_to == 0.0:
+            return 0.0, 0.0
+        variance = sigma_to ** 2 * (sigma_from ** 2 - sigma_to ** 2) / sigma_from ** 2
+        sigma_up = min(sigma_to, eta * variance ** 0.5)
+        return sigma_up, (sigma_to ** 2 - sigma_up ** 2) ** 0.5
+
+    def step(self, sample: torch.Tensor, denoised_sample: torch.Tensor, sigmas, step_index: int, noise: Optional[torch.Tensor] = None,
+             stream_id: int = 0) -> torch.Tensor:
+        sigma, sigma_next = _sig(sigmas[step_index]), _sig(sigmas[step_index + 1])
+        sigma_up, sigma_down = self._get_ancestral_step(sigma, sigma_next, self.eta)
+        if noise is not None:
+            result = sample.float() + to_velocity(sample, sigma, denoised_sample).float() * (sigma_down - sigma)
+            if sigma_up > 0:
+                result = result + noise.float() * sigma_up
+            return result.to(sample.dtype)
+        if self._seed_word is None or self._seed_word.device != sample.device:
+            self._seed_word = K.seed_word(self.seed, sample.device)
+        shp = sample.shape
+        c = shp[-1]
+        out = K.ancestral_euler_step_x0(sample.float().reshape(-1, c).contiguous(), denoised_sample.float().reshape(-1, c).contiguous(), sigma, sigma_up,
+                                        sigma_down, self._seed_word, step_index, stream_id)
+        return out.reshape(shp).to(sample.dtype)

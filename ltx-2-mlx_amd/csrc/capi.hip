@@ -296,6 +296,36 @@ int ltx2_guided_euler_step_pair(const float* v_x, const float* v_vel_cond, const
                                          sigma_next, (hipStream_t)stream);
 }
 
+int ltx2_philox_bits(uint32_t* out, int64_t n_quads, const uint64_t* seed_dev, uint32_t step, uint32_t stream_id, void* stream) {
+    return philox_bits_launch(out, (long)n_quads, seed_dev, step, stream_id, (hipStream_t)stream);
+}
+
+int ltx2_philox_normal(float* out, int64_t n, const uint64_t* seed_dev, uint32_t step, uint32_t stream_id, void* stream) {
+    return philox_normal_launch(out, (long)n, seed_dev, step, stream_id, (hipStream_t)stream);
+}
+
+int ltx2_ancestral_euler_step(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, int64_t ts_stride, const float* mask,
+                              const float* clean, float cfg_scale, float sigma, float sigma_up, float sigma_down, const uint64_t* seed_dev,
+                              uint32_t step, float* out, int rows, int C, void* stream) {
+    return ancestral_euler_step_launch(x, vel_cond, vel_uncond, ts, (long)ts_stride, mask, clean, cfg_scale, sigma, sigma_up, sigma_down, seed_dev, step,
+                                       out, rows, C, (hipStream_t)stream);
+}
+
+int ltx2_ancestral_euler_step_pair(const float* v_x, const float* v_vel_cond, const float* v_vel_uncond, const float* v_ts, int64_t v_ts_stride,
+                                   const float* v_mask, const float* v_clean, float v_cfg_scale, float* v_out, int v_rows, int v_C, const float* a_x,
+                                   const float* a_vel_cond, const float* a_vel_uncond, const float* a_ts, int64_t a_ts_stride, const float* a_mask,
+                                   const float* a_clean, float a_cfg_scale, float* a_out, int a_rows, int a_C, float sigma, float sigma_up,
+                                   float sigma_down, const uint64_t* seed_dev, uint32_t step, void* stream) {
+    return ancestral_euler_step_pair_launch(v_x, v_vel_cond, v_vel_uncond, v_ts, (long)v_ts_stride, v_mask, v_clean, v_cfg_scale, v_out, v_rows, v_C, a_x,
+                                            a_vel_cond, a_vel_uncond, a_ts, (long)a_ts_stride, a_mask, a_clean, a_cfg_scale, a_out, a_rows, a_C, sigma,
+                                            sigma_up, sigma_down, seed_dev, step, (hipStream_t)stream);
+}
+
+int ltx2_ancestral_euler_step_x0(const float* x, const float* x0, const float* mask, const float* clean, float sigma, float sigma_up, float sigma_down,
+                                 const uint64_t* seed_dev, uint32_t step, uint32_t stream_id, float* out, int rows, int C, void* stream) {
+    return ancestral_euler_step_x0_launch(x, x0, mask, clean, sigma, sigma_up, sigma_down, seed_dev, step, stream_id, out, rows, C, (hipStream_t)stream);
+}
+
 int ltx2_stg_euler_step(const float* x, const float* vel_cond, const float* vel_uncond, const float* vel_perturbed, const float* ts, int64_t ts_stride,
                         const float* mask, const float* clean, float cfg_scale, float stg_scale, float sigma, float sigma_next, float* out, int rows,
                         int C, void* stream) {

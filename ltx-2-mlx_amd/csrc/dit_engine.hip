@@ -1399,6 +1399,32 @@ int guided_step_joint(ltx2_dit* c, ltx2_dit* neg, const ModIn* in, const StepIo*
                                          io[1].latent, a.N, a.Cout, sigma, sigma_next, st);
 }
 
+// The Euler-ancestral step (reference components/diffusion_steps.py:70-129) on VideoOnly contexts (in[0] / io[0]) or, on AudioVideo contexts, over BOTH
+// latents: the evaluations of guided_step / guided_step_joint (neg NULL: one, no guidance), then ONE element-wise launch that also makes the noise
+// (csrc/sampler.hip), the video latent from Philox stream 0 and the audio latent from stream 1.  Every refusal stands before anything is enqueued.
+struct Ancestral {
+    float up, down;             // _get_ancestral_step(sigma, sigma_next, eta), evaluated by the caller in double
+    const uint64_t* seed;       // device, one 64-bit word
+    uint32_t step;
+};
+
+int ancestral_step(ltx2_dit* c, ltx2_dit* neg, const ModIn* in, const StepIo* io, const float cfg[2], float sigma, const Ancestral& an, hipStream_t st,
+                   bool rewind_events = true) {
+    const char* who = c->av ? "dit_ancestral_step_joint_av" : "dit_ancestral_step";
+    TRY(step_check(sigma, io, c->av ? 2 : 1, who));
+    LTX2_CHECK_ARG(an.up >= 0.f && an.down >= 0.f, "%s: sigma_up=%g and sigma_down=%g must be >= 0", who, an.up, an.down);
+    LTX2_CHECK_ARG(an.seed && ((uintptr_t)an.seed & 7) == 0, "%s: seed_dev is a device pointer to one 8-byte aligned 64-bit word", who);
+    const Mod &v = c->m[0], &a = c->m[1];
+    TRY(evaluate(c, neg, in, st, rewind_events));
+    if (!c->av)
+        return ancestral_euler_step_launch(in[0].latent, v.vel, neg ? neg->m[0].vel : nullptr, in[0].ts, in[0].n_ts == 1 ? 0 : 1, io[0].mask, io[0].clean,
+                                           cfg[0], sigma, an.up, an.down, an.seed, an.step, io[0].latent, v.N, v.Cout, st);
+    return ancestral_euler_step_pair_launch(in[0].latent, v.vel, neg ? neg->m[0].vel : nullptr, in[0].ts, in[0].n_ts == 1 ? 0 : 1, io[0].mask, io[0].clean,
+                                            cfg[0], io[0].latent, v.N, v.Cout, in[1].latent, a.vel, neg ? neg->m[1].vel : nullptr, in[1].ts,
+                                            in[1].n_ts == 1 ? 0 : 1, io[1].mask, io[1].clean, cfg[1], io[1].latent, a.N, a.Cout, sigma, an.up, an.down,
+                                            an.seed, an.step, st);
+}
+
 // Classifier-free guidance with the per-channel rescale (the standard one-stage loop of the reference's scripts/generate.py:1935-1960, rescale_noise_cfg
 // :688-727): the two evaluations of guided_step, then with guidance_rescale > 0 the statistics' two launches, then ONE element-wise pass.  No mask / clean:
 // that loop has no conditioning.  The workspace: the partials and the statistics for the bound shape; never called while a stream is capturing
@@ -1872,6 +1898,9 @@ struct LoopStep {                           // all defaults: the plain denoise s
     float ge_gamma = 0.f;
     bool rescaled = false;                  // the guided step of the standard one-stage loop: CFG in its order, the per-channel rescale at guidance_rescale > 0
     double guidance_rescale = 0.0;
+    const float* ancestral_up = nullptr;    // the Euler-ancestral step (neg NULL: not guided; on AudioVideo contexts over both latents, with `joint`):
+    const float* ancestral_down = nullptr;  //   sigma_up / sigma_down per step (host), and the seed word (device), which stays a pointer in the graph
+    const uint64_t* ancestral_seed = nullptr;
 };
 
 int capture_loop(ltx2_dit* c, const LoopStep& step, float* const latent[2], const Cond cond[2], const float* host_sigmas, int n_steps, hipStream_t st) {
@@ -1912,6 +1941,9 @@ int capture_loop(ltx2_dit* c, const LoopStep& step, float* const latent[2], cons
             const float* const next[2] = {s + 1, s + 1};
             const float cfg[2] = {step.cfg_scale, step.cfg_scale};
             rc = heun_step(c, step.neg, in, next, s + 1, cond, io, cfg, step.ge_gamma, i == 0, sigma, sigma_next, st);
+        } else if (step.ancestral_up) {
+            const float cfg[2] = {step.cfg_scale, step.audio_cfg_scale};
+            rc = ancestral_step(c, step.neg, in, io, cfg, sigma, {step.ancestral_up[i], step.ancestral_down[i], step.ancestral_seed, (uint32_t)i}, st, i == 0);
         } else if (step.rescaled) {
             rc = rescaled_guided_step(c, step.neg, in[0], io[0], step.cfg_scale, step.guidance_rescale, sigma, sigma_next, st);
         } else if (step.projected) {
@@ -2012,6 +2044,76 @@ int ltx2_dit_guided_step_joint_av(ltx2_dit* c, ltx2_dit* neg, float* v_latent, f
     const StepIo io[2] = {v.io, a.io};
     const float cfg[2] = {cfg_scale, audio_cfg_scale};
     return guided_step_joint(c, neg, in, io, cfg, sigma, sigma_next, (hipStream_t)stream);
+}
+
+int ltx2_dit_ancestral_step(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev, const float* mask,
+                            const float* clean, float cfg_scale, float sigma, float sigma_up, float sigma_down, const uint64_t* seed_dev, uint32_t step,
+                            void* stream) {
+    LTX2_CHECK_ARG(latent && timesteps, "dit_ancestral_step: null argument");
+    const int n_ts[2] = {n_timesteps, 1};
+    TRY(step_ready(c, neg, false, n_ts, "dit_ancestral_step"));
+    const StepArgs v = step_args(latent, timesteps, n_timesteps, sigma_dev, mask, clean);
+    const float cfg[2] = {cfg_scale, 0.f};
+    return ancestral_step(c, neg, &v.in, &v.io, cfg, sigma, {sigma_up, sigma_down, seed_dev, step}, (hipStream_t)stream);
+}
+
+int ltx2_dit_ancestral_step_joint_av(ltx2_dit* c, ltx2_dit* neg, float* v_latent, float* a_latent, const float* v_timesteps, int n_v_timesteps,
+                                     const float* a_timesteps, int n_a_timesteps, const float* sigma_dev, const float* v_mask, const float* v_clean,
+                                     const float* a_mask, const float* a_clean, float cfg_scale, float audio_cfg_scale, float sigma, float sigma_up,
+                                     float sigma_down, const uint64_t* seed_dev, uint32_t step, void* stream) {
+    LTX2_CHECK_ARG(v_latent && a_latent && v_timesteps && a_timesteps && sigma_dev, "dit_ancestral_step_joint_av: null argument");
+    const int n_ts[2] = {n_v_timesteps, n_a_timesteps};
+    TRY(step_ready(c, neg, true, n_ts, "dit_ancestral_step_joint_av"));
+    const StepArgs v = step_args(v_latent, v_timesteps, n_v_timesteps, sigma_dev, v_mask, v_clean);
+    const StepArgs a = step_args(a_latent, a_timesteps, n_a_timesteps, sigma_dev, a_mask, a_clean);
+    const ModIn in[2] = {v.in, a.in};
+    const StepIo io[2] = {v.io, a.io};
+    const float cfg[2] = {cfg_scale, audio_cfg_scale};
+    return ancestral_step(c, neg, in, io, cfg, sigma, {sigma_up, sigma_down, seed_dev, step}, (hipStream_t)stream);
+}
+
+namespace {
+// what both ancestral capture entries check of their per-step scalars and their seed, before the capture begins
+int ancestral_capture_check(const float* up, const float* down, int n_steps, const uint64_t* seed_dev, const char* who) {
+    LTX2_CHECK_ARG(up && down, "%s: bad argument", who);
+    for (int i = 0; i < n_steps; ++i) LTX2_CHECK_ARG(up[i] >= 0.f && down[i] >= 0.f, "%s: sigma_up=%g and sigma_down=%g must be >= 0", who, up[i], down[i]);
+    LTX2_CHECK_ARG(seed_dev && ((uintptr_t)seed_dev & 7) == 0, "%s: seed_dev is a device pointer to one 8-byte aligned 64-bit word", who);
+    return LTX2_OK;
+}
+}  // namespace
+
+int ltx2_dit_graph_capture_ancestral(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* host_sigmas, int n_steps, const float* mask, int64_t n_mask,
+                                     const float* clean, int64_t n_clean, float cfg_scale, const float* host_sigma_up, const float* host_sigma_down,
+                                     const uint64_t* seed_dev, void* stream) {
+    const LoopIo lo = {{latent, nullptr}, {{mask, (long)n_mask, clean, (long)n_clean}, {}}};
+    TRY(capture_ready(c, neg, false, false, lo, host_sigmas, n_steps, "dit_graph_capture_ancestral"));
+    TRY(ancestral_capture_check(host_sigma_up, host_sigma_down, n_steps, seed_dev, "dit_graph_capture_ancestral"));
+    LoopStep step;
+    step.neg = neg;
+    step.cfg_scale = cfg_scale;
+    step.ancestral_up = host_sigma_up;
+    step.ancestral_down = host_sigma_down;
+    step.ancestral_seed = seed_dev;
+    return capture_loop(c, step, lo.lat, lo.cond, host_sigmas, n_steps, (hipStream_t)stream);
+}
+
+int ltx2_dit_graph_capture_ancestral_joint_av(ltx2_dit* c, ltx2_dit* neg, float* v_latent, float* a_latent, const float* host_sigmas, int n_steps,
+                                              const float* v_mask, int64_t n_v_mask, const float* v_clean, int64_t n_v_clean, const float* a_mask,
+                                              int64_t n_a_mask, const float* a_clean, int64_t n_a_clean, float cfg_scale, float audio_cfg_scale,
+                                              const float* host_sigma_up, const float* host_sigma_down, const uint64_t* seed_dev,
+                                              void* stream) {
+    const LoopIo lo = {{v_latent, a_latent}, {{v_mask, (long)n_v_mask, v_clean, (long)n_v_clean}, {a_mask, (long)n_a_mask, a_clean, (long)n_a_clean}}};
+    TRY(capture_ready(c, neg, false, true, lo, host_sigmas, n_steps, "dit_graph_capture_ancestral_joint_av", true));
+    TRY(ancestral_capture_check(host_sigma_up, host_sigma_down, n_steps, seed_dev, "dit_graph_capture_ancestral_joint_av"));
+    LoopStep step;
+    step.neg = neg;
+    step.cfg_scale = cfg_scale;
+    step.joint = true;
+    step.audio_cfg_scale = audio_cfg_scale;
+    step.ancestral_up = host_sigma_up;
+    step.ancestral_down = host_sigma_down;
+    step.ancestral_seed = seed_dev;
+    return capture_loop(c, step, lo.lat, lo.cond, host_sigmas, n_steps, (hipStream_t)stream);
 }
 
 int ltx2_dit_stg_step(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev, const float* mask,

@@ -171,3 +171,27 @@ int channel_guidance_stats_launch(const float* x, const float* vel_cond, const f
 int rescaled_guided_euler_step_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride, const float* stats,
                                       float cfg_scale, double guidance_rescale, float sigma, float sigma_next, float* out, int rows, int C,
                                       hipStream_t stream);
+
+// Counter-based noise: Philox4x32-10 with counter (lo32(q), hi32(q), step, stream_id) and key (lo32(seed), hi32(seed)) for quad q, whose four
+// words serve the elements 4q .. 4q+3; seed_dev: one 64-bit word in device memory, read when the kernel runs.  bits: out[n_quads][4], the raw
+// words.  normal: out[n], u_k = ((r_k >> 9) + 0.5)*2^-23, z0 = sqrt(-2 ln u0)*cos(2 pi u1), z1 = sqrt(-2 ln u0)*sin(2 pi u1), z2 / z3 from
+// (u2, u3).  The values depend on (seed, step, stream_id, element index) alone.
+int philox_bits_launch(uint32_t* out, long n_quads, const uint64_t* seed_dev, uint32_t step, uint32_t stream_id, hipStream_t stream);
+int philox_normal_launch(float* out, long n, const uint64_t* seed_dev, uint32_t step, uint32_t stream_id, hipStream_t stream);
+
+// The Euler-ancestral step (reference components/diffusion_steps.py:70-129; sigma_up / sigma_down from _get_ancestral_step on the host):
+// d as guided_euler_step_launch forms it, r = x + ((x - d)/sigma)*(sigma_down - sigma), out = r + ((z*sigma_up)*m) with z the element's
+// philox_normal value (stream 0) and m the row's mask (1 without one).  vel_uncond NULL: no guidance, and r in the plain step's arithmetic
+// (x0_from_velocity_launch, euler_step_launch).  sigma_up == 0: no noise is evaluated, out = r.
+int ancestral_euler_step_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride, const float* mask,
+                                const float* clean, float cfg_scale, float sigma, float sigma_up, float sigma_down, const uint64_t* seed_dev,
+                                uint32_t step, float* out, int rows, int C, hipStream_t stream);
+// over the video (stream 0) and the audio latent (stream 1) in ONE launch, v_ then a_; each segment's output is the single launch's bit for bit
+int ancestral_euler_step_pair_launch(const float* v_x, const float* v_vel_cond, const float* v_vel_uncond, const float* v_ts, long v_ts_stride,
+                                     const float* v_mask, const float* v_clean, float v_cfg_scale, float* v_out, int v_rows, int v_C, const float* a_x,
+                                     const float* a_vel_cond, const float* a_vel_uncond, const float* a_ts, long a_ts_stride, const float* a_mask,
+                                     const float* a_clean, float a_cfg_scale, float* a_out, int a_rows, int a_C, float sigma, float sigma_up,
+                                     float sigma_down, const uint64_t* seed_dev, uint32_t step, hipStream_t stream);
+// from a ready x0, every operation rounded on its own: d = clean ? x0*m + clean*(1 - m) : x0.  A mask without a clean latent scales the noise alone.
+int ancestral_euler_step_x0_launch(const float* x, const float* x0, const float* mask, const float* clean, float sigma, float sigma_up, float sigma_down,
+                                   const uint64_t* seed_dev, uint32_t step, uint32_t stream_id, float* out, int rows, int C, hipStream_t stream);

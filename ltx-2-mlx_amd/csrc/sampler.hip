@@ -14,6 +14,11 @@
 namespace {
 
 // ---------------------------------- the plain step: contracted arithmetic, bounded (not bit-exact) against its reference ----------------------------------
+// Its two fused operations, written out so that no compiler decision stands between the kernels below and the unguided ancestral step, which
+// shares them: x0 = fma(-t, v, x) and x + ((x - d)*inv)*dt with the last product and sum fused.  The mask / clean blend is rounded per operation.
+__device__ __forceinline__ float plain_denoised(float x, float v, float t) { return fmaf(-t, v, x); }
+__device__ __forceinline__ float plain_euler(float x, float d, float inv, float dt) { return fmaf(mul_rn(sub_rn(x, d), inv), dt, x); }
+
 __global__ void x0_from_velocity_kernel(const float* __restrict__ latent, const float* __restrict__ vel,
                                         const float* __restrict__ ts_ptr, long ts_stride, float ts_scalar,
                                         float* __restrict__ x0, int rows, int C) {
@@ -21,7 +26,7 @@ __global__ void x0_from_velocity_kernel(const float* __restrict__ latent, const 
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
         const long row = i / C;
         const float ts = ts_ptr ? ts_ptr[row * ts_stride] : ts_scalar;
-        x0[i] = latent[i] - ts * vel[i];
+        x0[i] = plain_denoised(latent[i], vel[i], ts);
     }
 }
 
@@ -33,10 +38,9 @@ __global__ void euler_step_kernel(const float* __restrict__ x, const float* __re
         float d = x0[i];
         if (mask) {
             const float m = mask[i / C];
-            d = d * m + clean[i] * (1.f - m);
+            d = add_rn(mul_rn(d, m), mul_rn(clean[i], sub_rn(1.f, m)));
         }
-        const float xv = x[i];
-        out[i] = xv + (xv - d) * inv_sigma * dt;
+        out[i] = plain_euler(x[i], d, inv_sigma, dt);
     }
 }
 
@@ -61,6 +65,7 @@ struct Row {
     float t, m, one_minus_m;
     bool blend;
     int col;            // the element's channel (only the step with per-channel statistics reads it)
+    long e;             // the element's index row*C + col (only the steps with noise read it)
 };
 
 template <int V>
@@ -85,7 +90,7 @@ __device__ __forceinline__ void step_rows(const Op& op, const Rows& r, long bloc
     for (long i = block * blockDim.x + threadIdx.x; i < nv; i += blocks * blockDim.x) {
         const long e = i * V, row = e / r.C;
         const float m = blend ? r.mask[row] : 1.f;
-        Row rw = {r.ts[row * r.ts_stride], m, sub_rn(1.0f, m), blend, 0};
+        Row rw = {Op::reads_t ? r.ts[row * r.ts_stride] : 0.f, m, sub_rn(1.0f, m), blend, 0, 0};
         const int col = (int)(e - row * r.C);
         alignas(16) float in[Op::NIN][V], out[Op::NOUT][V];
 #pragma unroll
@@ -96,6 +101,7 @@ __device__ __forceinline__ void step_rows(const Op& op, const Rows& r, long bloc
 #pragma unroll
             for (int k = 0; k < Op::NIN; ++k) a[k] = in[k][j];
             rw.col = col + j;
+            rw.e = e + j;
             op.one(st, rw, a, o);
 #pragma unroll
             for (int k = 0; k < Op::NOUT; ++k) out[k][j] = o[k];
@@ -120,8 +126,9 @@ __global__ __launch_bounds__(BLOCK) void step_rows2_kernel(const Op a, const Row
     else step_rows<V>(b, rb, (int)blockIdx.x - blocks_a, (int)gridDim.x - blocks_a);
 }
 
-struct StepOp {         // the defaults: no per-thread state, no prologue, no epilogue
+struct StepOp {         // the defaults: no per-thread state, no prologue, no epilogue; the row's timestep is loaded
     struct State {};
+    static constexpr bool reads_t = true;
     template <class S>
     __device__ __forceinline__ void begin(S&, long) const {}
     template <class S>
@@ -615,13 +622,160 @@ struct RescaledGuidedEuler : StepOp {
     }
 };
 
+// ---------------------------------- counter-based noise and the Euler-ancestral step ----------------------------------
+// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3"; the Random123 known-answer vectors): ten rounds of two 32x32->64
+// multiplies, the key bumped by the Weyl constants between rounds.
+__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int round = 0; round < 10; ++round) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
+        c[1] = (uint32_t)p1;
+        c[3] = (uint32_t)p0;
+        c[0] = n0;
+        c[2] = n2;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+}
+
+// Where a latent's noise comes from: a pure function of (seed, step, stream, element index).  seed: one 64-bit word in device memory, read when the
+// kernel runs, so one captured graph serves any seed; stream: 0 the video latent, 1 the audio latent
+struct Noise {
+    const uint64_t* seed;
+    uint32_t step, stream;
+};
+
+// The four words of quad q: counter (lo32(q), hi32(q), step, stream), key (lo32(seed), hi32(seed)); they serve the elements 4q .. 4q+3
+__device__ __forceinline__ void philox_quad(long q, uint64_t seed, const Noise& nz, uint32_t (&r)[4]) {
+    r[0] = (uint32_t)(uint64_t)q;
+    r[1] = (uint32_t)((uint64_t)q >> 32);
+    r[2] = nz.step;
+    r[3] = nz.stream;
+    philox4x32_10(r, (uint32_t)seed, (uint32_t)(seed >> 32));
+}
+
+// The four N(0,1) values of quad q, the ONE function every caller shares (the fill and the fused step give the same bits): uniforms
+// u_k = ((r_k >> 9) + 0.5)*2^-23, exact in fp32 and inside (0, 1); Box-Muller on (u0, u1) and on (u2, u3) with the accurate logf / sincospif
+// (the angle 2*u is exact, so no rounded 2*pi*u enters), every operation rounded on its own
+__device__ __forceinline__ void philox_normal_quad(long q, uint64_t seed, const Noise& nz, float (&z)[4]) {
+#pragma clang fp contract(off)
+    uint32_t r[4];
+    philox_quad(q, seed, nz, r);
+    float u[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) u[k] = ((float)(r[k] >> 9) + 0.5f) * 0x1p-23f;
+#pragma unroll
+    for (int k = 0; k < 4; k += 2) {
+        const float rad = sqrtf(-2.0f * logf(u[k]));
+        float sn, cs;
+        sincospif(2.0f * u[k + 1], &sn, &cs);
+        z[k] = rad * cs;
+        z[k + 1] = rad * sn;
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void philox_bits_kernel(uint32_t* __restrict__ out, long n_quads, const Noise nz) {
+    const uint64_t seed = *nz.seed;
+    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < n_quads; q += (long)gridDim.x * blockDim.x) {
+        uint32_t r[4];
+        philox_quad(q, seed, nz, r);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) out[4 * q + k] = r[k];
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void philox_normal_kernel(float* __restrict__ out, long n, const Noise nz) {
+    const uint64_t seed = *nz.seed;
+    const long n_quads = (n + 3) / 4;
+    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < n_quads; q += (long)gridDim.x * blockDim.x) {
+        float z[4];
+        philox_normal_quad(q, seed, nz, z);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (4 * q + k < n) out[4 * q + k] = z[k];
+    }
+}
+
+// The stochastic part of EulerAncestralDiffusionStep (reference components/diffusion_steps.py:70-129): r, the Euler step to sigma_down, plus
+// z*sigma_up scaled by the row's mask -- a conditioned token (m = 0) stays on its clean value, where the reference would add noise to it too;
+// with m = 1 the arithmetic is the reference's.  A thread keeps the quad it evaluated last: with 16-byte accesses that is one Philox per four
+// elements; an element-wise thread evaluates quad e >> 2 and keeps lane e & 3, so the values do not depend on the access width or the grid.
+// up == 0: no Philox is evaluated and r comes back as it is.
+struct NoiseState {
+    uint64_t seed;
+    long q;
+    float z[4];
+};
+struct AncestralOp : StepOp {
+    using State = NoiseState;
+    __device__ __forceinline__ void begin_noise(State& st, const Noise& nz, float up) const {
+        st.seed = up != 0.f ? *nz.seed : 0;
+        st.q = -1;
+    }
+    __device__ __forceinline__ float ancestral(State& st, const Noise& nz, const Row& r, float stepped, float up) const {
+        if (up == 0.f) return stepped;
+        const long q = r.e >> 2;
+        if (q != st.q) {
+            philox_normal_quad(q, st.seed, nz, st.z);
+            st.q = q;
+        }
+        const int lane = (int)(r.e & 3);
+        const float z = lane == 0 ? st.z[0] : lane == 1 ? st.z[1] : lane == 2 ? st.z[2] : st.z[3];
+        return add_rn(stepped, mul_rn(mul_rn(z, up), r.m));
+    }
+};
+
+// g as GuidedEuler forms it and its Euler step with dt = sigma_down - sigma, then the noise.  No vu: the plain step's arithmetic, through the
+// helpers x0_from_velocity_kernel and euler_step_kernel are written with (plain_denoised, plain_euler), so the unguided step at sigma_up == 0 is
+// the plain denoise step's bit for bit
+struct AncestralEuler : AncestralOp {
+    enum { X, VC, VU, CLEAN, NIN };
+    enum { OUT, NOUT };
+    const float* in[NIN];
+    float* out[NOUT];
+    float s1, inv, dt, up;      // cfg_scale - 1, 1/sigma, sigma_down - sigma, sigma_up
+    Noise nz;
+    __device__ __forceinline__ void begin(State& st, long) const { begin_noise(st, nz, up); }
+    __device__ __forceinline__ void one(State& st, const Row& r, const float* a, float* o) const {
+        float stepped;
+        if (in[VU]) {
+            const float g = guide_from_cond(denoised(a[X], a[VC], r.t), denoised(a[X], a[VU], r.t), s1);
+            stepped = euler(a[X], blend_clean(g, a[CLEAN], r), inv, dt);
+        } else {
+            stepped = plain_euler(a[X], blend_clean(plain_denoised(a[X], a[VC], r.t), a[CLEAN], r), inv, dt);
+        }
+        o[OUT] = ancestral(st, nz, r, stepped, up);
+    }
+};
+
+// The same from a ready x0 (EulerAncestralDiffusionStep.step).  A mask without a clean latent: x0 is taken as it is -- the caller has blended
+// it already -- and the mask scales the noise alone
+struct AncestralFromX0 : AncestralOp {
+    static constexpr bool reads_t = false;      // no velocity, no timestep: Rows.ts stays NULL
+    enum { X, X0, CLEAN, NIN };
+    enum { OUT, NOUT };
+    const float* in[NIN];
+    float* out[NOUT];
+    float inv, dt, up;
+    Noise nz;
+    __device__ __forceinline__ void begin(State& st, long) const { begin_noise(st, nz, up); }
+    __device__ __forceinline__ void one(State& st, const Row& r, const float* a, float* o) const {
+        const float d = in[CLEAN] ? blend_clean(a[X0], a[CLEAN], r) : a[X0];
+        o[OUT] = ancestral(st, nz, r, euler(a[X], d, inv, dt), up);
+    }
+};
+
 // The checks every step shares, under the caller's name, and the launch.  present: the caller's required operands are all there.  16-byte accesses
 // need every [rows][C] operand on a 16-byte boundary as well as C % 4 == 0 (a NULL operand contributes no bits).  sums_grid: the grid of the sums
 // pass, which does not depend on the access width; 0: a step, one thread per vector under grid_for's cap.
-inline int check_rows(const char* who, bool present, const float* ts, long ts_stride, const float* mask, const float* clean, int rows, int C) {
-    LTX2_CHECK_ARG(present && ts && rows > 0 && C > 0, "%s: null operand or empty shape", who);
+// mask_alone: the ancestral step from a ready x0 -- it also takes a mask without a clean latent, and reads no timesteps (Op::reads_t is false)
+inline int check_rows(const char* who, bool present, const float* ts, long ts_stride, const float* mask, const float* clean, int rows, int C,
+                      bool mask_alone = false) {
+    LTX2_CHECK_ARG(present && (ts || mask_alone) && rows > 0 && C > 0, "%s: null operand or empty shape", who);
     LTX2_CHECK_ARG(ts_stride == 0 || ts_stride == 1, "%s: ts_stride is 0 (one timestep) or 1 (one per row)", who);
-    LTX2_CHECK_ARG((mask == nullptr) == (clean == nullptr), "%s: mask and clean go together", who);
+    LTX2_CHECK_ARG(mask_alone ? (mask || !clean) : (mask == nullptr) == (clean == nullptr), "%s: %s", who,
+                   mask_alone ? "a clean latent needs its mask" : "mask and clean go together");
     return LTX2_OK;
 }
 
@@ -635,8 +789,8 @@ bool vec4_ok(const Op& op, int C) {
 
 template <class Op>
 int launch_rows(const char* who, bool present, const Op& op, const float* ts, long ts_stride, const float* mask, const float* clean, int rows, int C,
-                int sums_grid, hipStream_t stream) {
-    if (const int rc = check_rows(who, present, ts, ts_stride, mask, clean, rows, C); rc != LTX2_OK) return rc;
+                int sums_grid, hipStream_t stream, bool mask_alone = false) {
+    if (const int rc = check_rows(who, present, ts, ts_stride, mask, clean, rows, C, mask_alone); rc != LTX2_OK) return rc;
     const Rows r = {ts, ts_stride, mask, (long)rows * C, C};
     if (vec4_ok(op, C))
         hipLaunchKernelGGL((step_rows_kernel<4, Op>), dim3(sums_grid ? sums_grid : grid_for(r.n / 4, BLOCK)), dim3(BLOCK), 0, stream, op, r);
@@ -1008,4 +1162,57 @@ int ge_euler_step_pair_launch(const float* v_x, const float* v_vel_cond, const f
     return heun_predict_pair_launch(v_x, v_vel_cond, v_vel_uncond, v_ts, v_ts_stride, v_mask, v_clean, v_cfg_scale, ge_gamma, v_prev, first, nullptr, v_out,
                                     v_rows, v_C, a_x, a_vel_cond, a_vel_uncond, a_ts, a_ts_stride, a_mask, a_clean, a_cfg_scale, nullptr, a_out, a_rows, a_C, sigma,
                                     sigma_next, stream);
+}
+
+namespace {
+// what the ancestral steps check of their scalars and their seed
+int ancestral_check(const char* who, float sigma, float sigma_up, float sigma_down, const uint64_t* seed_dev) {
+    LTX2_CHECK_ARG(sigma != 0.f, "Sigma can't be 0.0");   // reference core_utils.py:54-55
+    LTX2_CHECK_ARG(sigma_up >= 0.f && sigma_down >= 0.f, "%s: sigma_up=%g and sigma_down=%g must be >= 0", who, sigma_up, sigma_down);
+    LTX2_CHECK_ARG(seed_dev && ((uintptr_t)seed_dev & 7) == 0, "%s: seed_dev is a device pointer to one 8-byte aligned 64-bit word", who);
+    return LTX2_OK;
+}
+}  // namespace
+
+int philox_bits_launch(uint32_t* out, long n_quads, const uint64_t* seed_dev, uint32_t step, uint32_t stream_id, hipStream_t stream) {
+    LTX2_CHECK_ARG(out && n_quads > 0 && seed_dev && ((uintptr_t)seed_dev & 7) == 0, "philox_bits: null operand, empty shape or a seed off its 8-byte boundary");
+    hipLaunchKernelGGL(philox_bits_kernel, dim3(grid_for(n_quads, BLOCK)), dim3(BLOCK), 0, stream, out, n_quads, Noise{seed_dev, step, stream_id});
+    LTX2_CHECK_LAUNCH("philox_bits_kernel");
+    return LTX2_OK;
+}
+
+int philox_normal_launch(float* out, long n, const uint64_t* seed_dev, uint32_t step, uint32_t stream_id, hipStream_t stream) {
+    LTX2_CHECK_ARG(out && n > 0 && seed_dev && ((uintptr_t)seed_dev & 7) == 0, "philox_normal: null operand, empty shape or a seed off its 8-byte boundary");
+    hipLaunchKernelGGL(philox_normal_kernel, dim3(grid_for((n + 3) / 4, BLOCK)), dim3(BLOCK), 0, stream, out, n, Noise{seed_dev, step, stream_id});
+    LTX2_CHECK_LAUNCH("philox_normal_kernel");
+    return LTX2_OK;
+}
+
+int ancestral_euler_step_launch(const float* x, const float* vel_cond, const float* vel_uncond, const float* ts, long ts_stride, const float* mask,
+                                const float* clean, float cfg_scale, float sigma, float sigma_up, float sigma_down, const uint64_t* seed_dev,
+                                uint32_t step, float* out, int rows, int C, hipStream_t stream) {
+    if (const int rc = ancestral_check("ancestral_euler_step", sigma, sigma_up, sigma_down, seed_dev); rc != LTX2_OK) return rc;
+    const AncestralEuler op = {{}, {x, vel_cond, vel_uncond, clean}, {out}, cfg_scale - 1.0f, 1.0f / sigma, sigma_down - sigma, sigma_up, {seed_dev, step, 0}};
+    return launch_rows("ancestral_euler_step", x && vel_cond && out, op, ts, ts_stride, mask, clean, rows, C, 0, stream);
+}
+
+int ancestral_euler_step_pair_launch(const float* v_x, const float* v_vel_cond, const float* v_vel_uncond, const float* v_ts, long v_ts_stride,
+                                     const float* v_mask, const float* v_clean, float v_cfg_scale, float* v_out, int v_rows, int v_C, const float* a_x,
+                                     const float* a_vel_cond, const float* a_vel_uncond, const float* a_ts, long a_ts_stride, const float* a_mask,
+                                     const float* a_clean, float a_cfg_scale, float* a_out, int a_rows, int a_C, float sigma, float sigma_up,
+                                     float sigma_down, const uint64_t* seed_dev, uint32_t step, hipStream_t stream) {
+    if (const int rc = ancestral_check("ancestral_euler_step_pair", sigma, sigma_up, sigma_down, seed_dev); rc != LTX2_OK) return rc;
+    const float inv = 1.0f / sigma, dt = sigma_down - sigma;
+    const AncestralEuler v = {{}, {v_x, v_vel_cond, v_vel_uncond, v_clean}, {v_out}, v_cfg_scale - 1.0f, inv, dt, sigma_up, {seed_dev, step, 0}};
+    const AncestralEuler a = {{}, {a_x, a_vel_cond, a_vel_uncond, a_clean}, {a_out}, a_cfg_scale - 1.0f, inv, dt, sigma_up, {seed_dev, step, 1}};
+    return launch_rows2("ancestral_euler_step_pair", v_x && v_vel_cond && v_out && a_x && a_vel_cond && a_out, v,
+                        {v_ts, v_ts_stride, v_mask, v_clean, v_rows, v_C}, a, {a_ts, a_ts_stride, a_mask, a_clean, a_rows, a_C}, stream);
+}
+
+int ancestral_euler_step_x0_launch(const float* x, const float* x0, const float* mask, const float* clean, float sigma, float sigma_up, float sigma_down,
+                                   const uint64_t* seed_dev, uint32_t step, uint32_t stream_id, float* out, int rows, int C, hipStream_t stream) {
+    if (const int rc = ancestral_check("ancestral_euler_step_x0", sigma, sigma_up, sigma_down, seed_dev); rc != LTX2_OK) return rc;
+    const AncestralFromX0 op = {{}, {x, x0, clean}, {out}, 1.0f / sigma, sigma_down - sigma, sigma_up, {seed_dev, step, stream_id}};
+    static_assert(!AncestralFromX0::reads_t, "the launch below passes no timesteps");
+    return launch_rows("ancestral_euler_step_x0", x && x0 && out, op, nullptr, 0, mask, clean, rows, C, 0, stream, true);
 }

@@ -552,6 +552,85 @@ def guided_euler_step_pair(video: dict, audio: dict, sigma: float, sigma_next: f
     return outs[0], outs[1]
 
 
+def seed_word(seed: int, device) -> torch.Tensor:
+    """The noise seed as the kernels read it: one 64-bit word on the device (the low 64 bits of `seed`, stored as int64)."""
+    s = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return torch.tensor([s - (1 << 64) if s >= (1 << 63) else s], dtype=torch.int64, device=device)
+
+
+def _seed_ptr(seed: torch.Tensor):
+    assert seed.dtype == torch.int64 and seed.numel() == 1 and seed.is_cuda, "seed: one int64 word on the device (kernels.seed_word)"
+    return nv.ptr(seed)
+
+
+def philox_bits(n_quads: int, seed: torch.Tensor, step: int, stream_id: int, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """The raw Philox4x32-10 words (ltx2_philox_bits) -> (n_quads, 4) int32, to be read as uint32: row q has the counter
+    (lo32(q), hi32(q), step, stream_id) and the key (lo32(seed), hi32(seed))."""
+    out = torch.empty(int(n_quads), 4, dtype=torch.int32, device=seed.device)
+    nv.check(nv.lib(dtype).ltx2_philox_bits(nv.ptr(out), int(n_quads), _seed_ptr(seed), int(step), int(stream_id), nv.stream()))
+    return out
+
+
+def philox_normal(n: int, seed: torch.Tensor, step: int, stream_id: int, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """n fp32 N(0,1) values (ltx2_philox_normal): element e is lane e & 3 of quad e >> 2, Box-Muller on the quad's uniforms.  A function of
+    (seed, step, stream_id, e) alone: the noise the ancestral step kernels add, bit for bit."""
+    out = torch.empty(int(n), dtype=torch.float32, device=seed.device)
+    nv.check(nv.lib(dtype).ltx2_philox_normal(nv.ptr(out), int(n), _seed_ptr(seed), int(step), int(stream_id), nv.stream()))
+    return out
+
+
+def ancestral_euler_step(x: torch.Tensor, vel_cond: torch.Tensor, vel_uncond: Optional[torch.Tensor], timesteps: torch.Tensor, cfg_scale: float,
+                         sigma: float, sigma_up: float, sigma_down: float, seed: torch.Tensor, step: int, mask: Optional[torch.Tensor] = None,
+                         clean: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """One Euler-ancestral step over fp32 [N, C] (ltx2_ancestral_euler_step): guided_euler_step to sigma_down, then + (z * sigma_up) * mask with
+    z = philox_normal(N*C, seed, step, 0) made inside the kernel.  vel_uncond None: no guidance, the plain step's arithmetic (x0_from_velocity,
+    euler_step).  `out` may be `x`."""
+    if out is None:
+        out = torch.empty_like(x)
+    assert vel_cond is not None and (mask is None) == (clean is None)
+    n, c, timesteps = _step_operands(x, timesteps, (vel_cond, vel_uncond, clean, out), mask)
+    nv.check(nv.lib(dtype).ltx2_ancestral_euler_step(nv.ptr(x), nv.ptr(vel_cond), nv.ptr(vel_uncond), nv.ptr(timesteps), 0 if timesteps.numel() == 1 else 1,
+                                                     nv.ptr(mask), nv.ptr(clean), float(cfg_scale), float(sigma), float(sigma_up), float(sigma_down),
+                                                     _seed_ptr(seed), int(step), nv.ptr(out), n, c, nv.stream()))
+    return out
+
+
+def ancestral_euler_step_pair(video: dict, audio: dict, sigma: float, sigma_up: float, sigma_down: float, seed: torch.Tensor, step: int,
+                              dtype: Optional[torch.dtype] = None):
+    """ancestral_euler_step over two latents in ONE launch (ltx2_ancestral_euler_step_pair): `video` (noise stream 0) and `audio` (stream 1) each
+    hold x, vel_cond, timesteps, cfg_scale and optionally vel_uncond, mask, clean, out.  -> (video out, audio out), each the single launch's
+    bits (the audio's: a single launch on stream 1, which philox_normal(..., stream_id=1) and the torch ops restate)."""
+    args, outs, held = [], [], []
+    for seg in (video, audio):
+        x, vc, vu, mask, clean = seg["x"], seg["vel_cond"], seg.get("vel_uncond"), seg.get("mask"), seg.get("clean")
+        out = seg["out"] if seg.get("out") is not None else torch.empty_like(x)
+        assert vc is not None and (mask is None) == (clean is None)
+        n, c, ts = _step_operands(x, seg["timesteps"], (vc, vu, clean, out), mask)
+        args += [nv.ptr(x), nv.ptr(vc), nv.ptr(vu), nv.ptr(ts), 0 if ts.numel() == 1 else 1, nv.ptr(mask), nv.ptr(clean), float(seg["cfg_scale"]),
+                 nv.ptr(out), n, c]
+        outs.append(out)
+        held.append(ts)          # as in guided_euler_step_pair: the copy must outlive the launch call
+    nv.check(nv.lib(dtype).ltx2_ancestral_euler_step_pair(*args, float(sigma), float(sigma_up), float(sigma_down), _seed_ptr(seed), int(step), nv.stream()))
+    return outs[0], outs[1]
+
+
+def ancestral_euler_step_x0(x: torch.Tensor, x0: torch.Tensor, sigma: float, sigma_up: float, sigma_down: float, seed: torch.Tensor, step: int,
+                            stream_id: int = 0, mask: Optional[torch.Tensor] = None, clean: Optional[torch.Tensor] = None,
+                            out: Optional[torch.Tensor] = None, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """The Euler-ancestral step from a ready x0 over fp32 [N, C] (ltx2_ancestral_euler_step_x0), every operation individually rounded.  With
+    `clean`, x0 is blended by `mask` first; a mask WITHOUT clean scales the noise alone (x0 is taken as already blended)."""
+    if out is None:
+        out = torch.empty_like(x)
+    assert x0 is not None and (clean is None or mask is not None)
+    n, c = x.shape
+    for t in (x, x0, clean, out):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.shape == x.shape)
+    assert mask is None or (mask.dtype == torch.float32 and mask.is_contiguous() and mask.numel() == n)
+    nv.check(nv.lib(dtype).ltx2_ancestral_euler_step_x0(nv.ptr(x), nv.ptr(x0), nv.ptr(mask), nv.ptr(clean), float(sigma), float(sigma_up), float(sigma_down),
+                                                        _seed_ptr(seed), int(step), int(stream_id), nv.ptr(out), n, c, nv.stream()))
+    return out
+
+
 def stg_euler_step(x: torch.Tensor, vel_cond: torch.Tensor, vel_uncond: Optional[torch.Tensor], vel_perturbed: torch.Tensor, timesteps: torch.Tensor,
                    cfg_scale: float, stg_scale: float, sigma: float, sigma_next: float, mask: Optional[torch.Tensor] = None,
                    clean: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, dtype: Optional[torch.dtype] = None) -> torch.Tensor:

@@ -923,6 +923,57 @@ class LTXModel:
         """Replay the graph captured by capture_guided_joint_graph."""
         self._replay("guided_joint", "no joint guided graph captured")
 
+    # ------------------------------------------------------------------ the Euler-ancestral step: noise made inside the step kernel
+    def ancestral_step_(self, neg: Optional["LTXModel"], latent: torch.Tensor, video: Modality, sigma: float, sigma_up: float, sigma_down: float,
+                        seed: torch.Tensor, step: int, cfg_scale: float = 1.0, denoise_mask: Optional[torch.Tensor] = None,
+                        clean_latent: Optional[torch.Tensor] = None, audio_latent: Optional[torch.Tensor] = None, audio: Optional[Modality] = None,
+                        audio_cfg_scale: float = 1.0, audio_denoise_mask: Optional[torch.Tensor] = None,
+                        audio_clean_latent: Optional[torch.Tensor] = None) -> None:
+        """In-place: one Euler-ancestral step by ONE C call (ltx2_dit_ancestral_step; with `audio_latent` / `audio` on an AudioVideo context
+        ltx2_dit_ancestral_step_joint_av over both latents) -- the evaluations of guided_step_ / guided_step_joint_av_ (neg None: one, no
+        guidance), then one kernel that steps to sigma_down and adds sigma_up * N(0,1) made from (seed, step, modality, element).  `seed`:
+        kernels.seed_word, read on the device when the kernel runs."""
+        joint = audio_latent is not None
+        pos, ng = self._contexts(neg, av=joint, optional=True)
+        assert seed.dtype == torch.int64 and seed.numel() == 1 and seed.is_cuda
+        ngh = None if ng is None else ng._h
+        if not joint:
+            ts, n_ts, sg = pos._step_inputs(latent, video, sigma)
+            nv.check(pos._L.ltx2_dit_ancestral_step(pos._h, ngh, nv.ptr(latent), nv.ptr(ts), n_ts, nv.ptr(sg), nv.ptr(denoise_mask), nv.ptr(clean_latent),
+                                                    float(cfg_scale), float(sigma), float(sigma_up), float(sigma_down), nv.ptr(seed), int(step), nv.stream()))
+            return
+        ts, n_ts, sg, ats, n_ats = pos._step_inputs(latent, video, sigma, audio_latent, audio)
+        nv.check(pos._L.ltx2_dit_ancestral_step_joint_av(pos._h, ngh, nv.ptr(latent), nv.ptr(audio_latent), nv.ptr(ts), n_ts, nv.ptr(ats), n_ats, nv.ptr(sg),
+                                                         nv.ptr(denoise_mask), nv.ptr(clean_latent), nv.ptr(audio_denoise_mask), nv.ptr(audio_clean_latent),
+                                                         float(cfg_scale), float(audio_cfg_scale), float(sigma), float(sigma_up), float(sigma_down),
+                                                         nv.ptr(seed), int(step), nv.stream()))
+
+    def capture_ancestral_graph(self, neg: Optional["LTXModel"], latent: torch.Tensor, sigmas: Sequence[float], sigma_up: Sequence[float],
+                                sigma_down: Sequence[float], seed: torch.Tensor, cfg_scale: float = 1.0, denoise_mask: Optional[torch.Tensor] = None,
+                                clean_latent: Optional[torch.Tensor] = None, audio_latent: Optional[torch.Tensor] = None, audio_cfg_scale: float = 1.0,
+                                audio_denoise_mask: Optional[torch.Tensor] = None, audio_clean_latent: Optional[torch.Tensor] = None) -> None:
+        """hipGraph-capture len(sigmas)-1 of those steps as one linear chain (ltx2_dit_graph_capture_ancestral / _joint_av): step i bakes in
+        step = i, sigma_up[i] and sigma_down[i]; `seed` stays a pointer, so writing another seed into the tensor and replaying gives that
+        seed's result.  The contexts are prepared first; the graph belongs to the positive context and replay_ancestral_graph() replays it."""
+        joint = audio_latent is not None
+        pos, ng = self._contexts(neg, av=joint, optional=True)
+        n = len(sigmas) - 1
+        assert len(sigma_up) == n and len(sigma_down) == n and seed.dtype == torch.int64 and seed.numel() == 1 and seed.is_cuda
+        up, down = ((C.c_float * n)(*[float(v) for v in arr]) for arr in (sigma_up, sigma_down))
+        if not joint:
+            self._capture("ancestral", pos, ng, "ltx2_dit_graph_capture_ancestral", (latent,), sigmas, [(denoise_mask, clean_latent)], float(cfg_scale),
+                          up, down, nv.ptr(seed))
+        else:
+            assert audio_latent.dtype == torch.float32 and audio_latent.is_contiguous()
+            self._capture("ancestral", pos, ng, "ltx2_dit_graph_capture_ancestral_joint_av", (latent, audio_latent), sigmas,
+                          [(denoise_mask, clean_latent), (audio_denoise_mask, audio_clean_latent)], audio_denoise_mask, audio_clean_latent,
+                          float(cfg_scale), float(audio_cfg_scale), up, down, nv.ptr(seed))
+        pos._graph_refs = (*pos._graph_refs, seed)
+
+    def replay_ancestral_graph(self) -> None:
+        """Replay the graph captured by capture_ancestral_graph (it belongs to the context that ran the capture)."""
+        self._replay("ancestral", "no ancestral graph captured")
+
     # ------------------------------------------------------------------ spatio-temporal guidance on both latents (AudioVideo engine)
     def stg_step_joint_av_(self, neg: Optional["LTXModel"], latent: torch.Tensor, audio_latent: torch.Tensor, video: Modality, audio: Modality,
                            sigma: float, sigma_next: float, cfg_scale: float, audio_cfg_scale: float, stg_scale: float, audio_stg_scale: float,

@@ -821,6 +821,100 @@ def res2s_av_denoise_loop(transformer, video_state: LatentState, audio_state: La
     return _with_latent(video_state, lat), _with_latent(audio_state, alat)
 
 
+def _ancestral_parts(x, vel_cond, vel_uncond, ts, cfg_scale, mask, clean, sigma, sigma_up, sigma_down, noise):
+    """One modality's Euler-ancestral step from separate ops, the statements ltx2_ancestral_euler_step fuses, on fp32 (N, C): under guidance
+    every fp32 torch op on its own; without, x0_from_velocity and euler_step (the plain step's kernels) with the blend in torch."""
+    import numpy as np
+    from .. import kernels as K
+    m = None if mask is None else mask.reshape(-1, 1)
+    blend = lambda d: d if m is None else d * m + clean * (1 - m)      # noqa: E731
+    if vel_uncond is None:
+        stepped = K.euler_step(x, blend(K.x0_from_velocity(x, vel_cond, ts)), sigma, sigma_down)
+    else:
+        t = ts.reshape(-1, 1) if ts.numel() > 1 else ts.reshape(1, 1)
+        a, b = x - t * vel_cond, x - t * vel_uncond
+        d = blend(a + float(np.float32(cfg_scale) - np.float32(1)) * (a - b))      # the kernel's fp32 scalars: cfg_scale - 1, 1/sigma, sigma_down - sigma
+        inv, dt = float(np.float32(1) / np.float32(sigma)), float(np.float32(sigma_down) - np.float32(sigma))
+        stepped = x + ((x - d) * inv) * dt
+    if sigma_up == 0:
+        return stepped
+    scaled = noise.reshape(x.shape) * float(np.float32(sigma_up))
+    return stepped + (scaled if m is None else scaled * m)
+
+
+def ancestral_denoise_loop(transformer, video_state: LatentState, audio_state: Optional[LatentState], sigmas, video_context: torch.Tensor,
+                           audio_context: Optional[torch.Tensor] = None, negative_video_context: Optional[torch.Tensor] = None,
+                           negative_audio_context: Optional[torch.Tensor] = None, cfg_scale: float = 1.0, audio_cfg_scale: float = 1.0,
+                           eta: float = 1.0, seed: int = 0, callback=None, use_hip_graph: bool = True,
+                           fused: bool = True) -> Tuple[LatentState, Optional[LatentState]]:
+    """The Euler-ancestral sampler (the reference's EulerAncestralDiffusionStep, components/diffusion_steps.py:70-129, as its DistilledPipeline
+    runs stage 1) without leaving the device: per step the Euler step to sigma_down, then sigma_up * N(0,1) on top, with (sigma_up, sigma_down) =
+    _get_ancestral_step(sigma_i, sigma_{i+1}, eta) in double on the host.  The noise is made INSIDE the step kernel: Philox4x32-10 under (seed,
+    step, modality, element index), the video latent from stream 0 and the audio latent from stream 1, scaled by the denoise mask so that
+    conditioned tokens stay clean (the reference would add noise to them too; with an all-ones mask the arithmetic is the reference's).
+    Video alone (audio_state None; an AudioVideo model through its video twin) or both latents of an AudioVideo model.  Classifier-free guidance
+    (CFGGuider's arithmetic, as guided_denoise_loop / joint_guided_denoise_loop) when a scale is not 1 and the negative context(s) are given.
+    fused=True: every step is ONE C call (LTXModel.ancestral_step_) and with no callback and fewer than 64 steps the loop is one captured graph
+    that reads the seed from device memory.  fused=False: the comparison form -- the same forwards, then separate ops and
+    kernels.philox_normal; it gives the same bits.  eta = 0 gives the Euler loops' bits (joint_denoise_loop; under guidance
+    guided_denoise_loop / joint_guided_denoise_loop).  `transformer` is an X0Model.  Returns (video_state, audio_state or None)."""
+    from .. import kernels as K
+    from ..components import EulerAncestralDiffusionStep
+    model = transformer.velocity_model
+    joint = audio_state is not None
+    if joint and not model.is_av:
+        raise ValueError("an audio state needs an audio-video (AV) model")
+    if joint and audio_context is None:
+        raise ValueError("AudioVideo model: audio_encoding (the audio text context) is required")
+    if eta < 0:
+        raise ValueError(f"eta={eta} must be >= 0")
+    guided = (cfg_scale != 1.0 or (joint and audio_cfg_scale != 1.0)) and negative_video_context is not None and (not joint or negative_audio_context is not None)
+    sig = [float(s) for s in sigmas]
+    n = len(sig) - 1
+    steps = [EulerAncestralDiffusionStep._get_ancestral_step(sig[i], sig[i + 1], eta) for i in range(n)]
+    up, down = [s[0] for s in steps], [s[1] for s in steps]
+    model, uniform, lat, mask, clean = _video_loop_inputs(model, video_state, video_only=not joint)
+    a_uniform, alat, amask, aclean = True, None, None, None
+    if joint:
+        _, a_uniform, alat, amask, aclean = _video_loop_inputs(model, audio_state, video_only=False)
+    seed_dev = K.seed_word(seed, lat.device)
+    neg = _prepare_contexts(model, guided, not (uniform and a_uniform), video_state.positions, video_context, negative_video_context,
+                            audio_state.positions if joint else None, audio_context if joint else None, negative_audio_context if joint else None)
+    cond = dict(denoise_mask=mask, clean_latent=clean)
+    if joint:
+        cond.update(audio_denoise_mask=amask, audio_clean_latent=aclean)
+
+    def modalities(vc, ac, s):
+        vm = modality_from_state(video_state.replace(latent=lat[None]), vc, s, uniform=uniform)
+        return (vm, audio_modality_from_state(audio_state.replace(latent=alat[None]), ac, s, uniform=a_uniform)) if joint else (vm,)
+
+    if fused:
+        def step(i):
+            mods = modalities(video_context, audio_context, sig[i])
+            model.ancestral_step_(neg, lat, mods[0], sig[i], up[i], down[i], seed_dev, i, cfg_scale, audio_latent=alat,
+                                  audio=mods[1] if joint else None, audio_cfg_scale=audio_cfg_scale, **cond)
+
+        _run_steps(n, callback, use_hip_graph, lambda: model.capture_ancestral_graph(neg, lat, sig, up, down, seed_dev, cfg_scale, audio_latent=alat,
+                                                                                      audio_cfg_scale=audio_cfg_scale, **cond),
+                   model.replay_ancestral_graph, step)
+    else:
+        def velocities(m, mods):
+            out = m(*mods)
+            return [v[0] for v in (out if isinstance(out, tuple) else (out,))][:len(mods)]
+
+        segments = [(lat, cfg_scale, mask, clean, 0)] + ([(alat, audio_cfg_scale, amask, aclean, 1)] if joint else [])
+        for i in range(n):
+            mods = modalities(video_context, audio_context, sig[i])
+            vc = velocities(model, mods)
+            vu = velocities(neg, modalities(negative_video_context, negative_audio_context, sig[i])) if guided else [None, None]
+            for k, (x, scale, mk, cl, stream_id) in enumerate(segments):
+                noise = K.philox_normal(x.numel(), seed_dev, i, stream_id) if up[i] != 0 else None
+                x.copy_(_ancestral_parts(x, vc[k], vu[k], mods[k].timesteps.reshape(-1).float(), scale, mk, cl, sig[i], up[i], down[i], noise))
+            if callback:
+                callback(i + 1, n)
+    return _with_latent(video_state, lat), (_with_latent(audio_state, alat) if joint else None)
+
+
 def heun_device_form(video_guider, audio_guider=None) -> bool:
     """Whether the Heun / GE loops can run their device form under these guiders: each a plain CFGGuider, None or not enabled."""
     from ..components.guiders import CFGGuider

@@ -21,7 +21,7 @@ from ..model.transformer import LTXModel, X0Model
 from ..model.video_vae import SimpleVideoDecoder, TilingConfig
 from ..types import AudioLatentShape, LatentState, VideoPixelShape
 from .common import (as_x0model, auto_tiling_config, conditioned_initial_state, create_image_conditionings, decode_video, final_latent,
-                     joint_denoise_loop, seeded_noiser, stage_callback, upscale_latent_x2, video_tools_for)
+                     ancestral_denoise_loop, joint_denoise_loop, seeded_noiser, stage_callback, upscale_latent_x2, video_tools_for)
 
 
 @dataclass
@@ -42,6 +42,8 @@ class DistilledConfig:
     audio_downsample_factor: int = 4
     audio_output_sample_rate: int = 24000
     use_hip_graph: bool = False    # MI355X addition: replay the captured step loop (uniform sigma only)
+    sampler: str = "euler"         # "euler_ancestral": stage 1 through EulerAncestralDiffusionStep's loop (reference pipelines/distilled.py:140-143);
+    ancestral_eta: float = 1.0     #   stage 2 stays plain Euler, as the reference's constructor comments say.  The noise seed is `seed`.
 
     def _get_tiling_config(self) -> Optional[TilingConfig]:
         return auto_tiling_config(self.tiling_config, self.num_frames, self.height, self.width)
@@ -51,6 +53,8 @@ class DistilledConfig:
             raise ValueError(f"num_frames must be 8*k + 1, got {self.num_frames}. Valid values: 1, 9, 17, 25, 33, ..., 121")
         if self.height % 64 != 0 or self.width % 64 != 0:
             raise ValueError(f"Resolution ({self.height}x{self.width}) must be divisible by 64 for two-stage pipeline.")
+        if self.sampler not in ("euler", "euler_ancestral"):
+            raise ValueError(f"sampler={self.sampler!r}: the distilled pipeline runs 'euler' or 'euler_ancestral'")
 
 
 class DistilledPipeline:
@@ -115,8 +119,13 @@ class DistilledPipeline:
             atools = self._create_audio_tools(audio_shape(h1, w1))
             astate = noiser(atools.create_initial_state(dtype=config.dtype, device=dev), noise_scale=1.0, noise=initial_audio_noise)
             astate = astate.replace(latent=self._channelwise_normalize_audio(astate.latent))
-        state, astate = self._denoise_loop_av(state, astate, DISTILLED_SIGMA_VALUES, text_encoding.to(dev), actx,
-                                              callback=stage_callback(callback, "stage1"), use_hip_graph=config.use_hip_graph)
+        if config.sampler == "euler_ancestral":
+            state, astate = ancestral_denoise_loop(self.transformer, state, astate, DISTILLED_SIGMA_VALUES, text_encoding.to(dev), actx,
+                                                   eta=config.ancestral_eta, seed=config.seed, callback=stage_callback(callback, "stage1"),
+                                                   use_hip_graph=config.use_hip_graph)
+        else:
+            state, astate = self._denoise_loop_av(state, astate, DISTILLED_SIGMA_VALUES, text_encoding.to(dev), actx,
+                                                  callback=stage_callback(callback, "stage1"), use_hip_graph=config.use_hip_graph)
         latent = final_latent(tools, state)
         audio_latent = final_latent(atools, astate) if astate is not None else None
 

@@ -53,7 +53,7 @@ from ..conditioning.tools import AudioLatentTools
 from ..model.transformer import LTXModel, X0Model
 from ..model.video_vae import SimpleVideoDecoder, TilingConfig
 from ..types import AudioLatentShape, VideoPixelShape
-from .common import (ImageCondition, as_x0model, auto_tiling_config, conditioned_initial_state, create_image_conditionings, decode_video,
+from .common import (ImageCondition, ancestral_denoise_loop, as_x0model, auto_tiling_config, conditioned_initial_state, create_image_conditionings, decode_video,
                      final_latent, ge_denoise_loop, heun_denoise_loop, heun_device_form, joint_denoise_loop, joint_stg_denoise_loop, projected_denoise_loop, projected_guider_args, reset_guider, seeded_noiser, stg_denoise_loop, video_tools_for)
 
 
@@ -131,7 +131,8 @@ class OneStagePipeline:
                  ge_gamma: float = 0.0, sampler: str = "euler", temporal_upscaler=None, cross_attn_scale: float = 1.0,
                  cross_attn_start_block: int = 40, *, stg_audio_scale: float = 0.0, initial_noise: Optional[torch.Tensor] = None,
                  initial_audio_noise: Optional[torch.Tensor] = None,
-                 initial_audio_latent: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+                 initial_audio_latent: Optional[torch.Tensor] = None,
+                 ancestral_eta: float = 1.0) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         """-> (video, audio): video uint8 frames (F, H, W, 3) (or the final latent when no decoder is set); audio = the
         waveform (B, 2, samples) when config.audio_enabled and both audio_decoder and vocoder were given (the reference's
         _decode_audio), the audio LATENT (B, 8, T_a, 16) when config.audio_enabled without them, else None.
@@ -145,7 +146,11 @@ class OneStagePipeline:
         latent, never VAE-decoded (the reference returns the original waveform).
         stg_audio_scale (keyword-only, MI355X addition): > 0 adds an STG term of that scale to the AUDIO prediction, from the same perturbed
         evaluation, which then skips the audio self-attention of `stg_blocks` as well; stg_blocks / stg_cutoff hold for both modalities.  Needs
-        an audio state (ValueError without one) and a plain CFGGuider per modality or none enabled (NotImplementedError under CFG* / APG)."""
+        an audio state (ValueError without one) and a plain CFGGuider per modality or none enabled (NotImplementedError under CFG* / APG).
+        sampler="euler_ancestral" with ancestral_eta (keyword-only, MI355X addition): the reference's EulerAncestralDiffusionStep
+        (components/diffusion_steps.py:70-129) through pipelines.common.ancestral_denoise_loop, the noise made in the step kernel under
+        config.seed.  Runs under a plain CFGGuider per modality (rescale_scale = 0) or with no guidance; NotImplementedError beside CFG* / APG,
+        STG, GE, cross_attn_scale and a temporal upscaler."""
         images = images or []
         internal_audio_active = self.is_av_model and (config.use_internal_audio_branch or config.audio_enabled)
         if config.audio_enabled or internal_audio_active:
@@ -168,11 +173,21 @@ class OneStagePipeline:
                 raise ValueError(f"stg_cutoff={stg_cutoff} must lie in [0, 1]")
             stg_guider = STGGuider(scale=stg_scale) if stg_scale > 0 else None
             audio_stg_guider = STGGuider(scale=stg_audio_scale) if stg_audio_scale > 0 else None
-        if sampler not in ("euler", "heun"):
-            raise ValueError(f"sampler={sampler!r}: 'euler' or 'heun'")
+        if sampler not in ("euler", "heun", "euler_ancestral"):
+            raise ValueError(f"sampler={sampler!r}: 'euler', 'heun' or 'euler_ancestral'")
         # Heun and GE are built without STG; beside it they stay refused, so the gate sees them only then
-        heun, ge = sampler == "heun", ge_gamma > 0
-        if stg_guider is None and audio_stg_guider is None:
+        heun, ge, ancestral = sampler == "heun", ge_gamma > 0, sampler == "euler_ancestral"
+        if ancestral:
+            # the ancestral step is built for the Euler step under plain CFG alone: the gate sees every other option, then GE and the guider classes
+            self._require_no_guidance(max(stg_scale, stg_audio_scale), guider_override, ge_gamma, "euler", temporal_upscaler, cross_attn_scale)
+            if guider_override is not None and type(guider_override) is not CFGGuider:
+                raise NotImplementedError("sampler='euler_ancestral' beside CFG* / APG (a projected guider_override) is outside the MI355X hot path")
+            if config.rescale_scale > 0 and guider_override is None and (config.cfg_scale != 1.0 or (internal_audio_active and config.audio_cfg_scale != 1.0)):
+                raise NotImplementedError("sampler='euler_ancestral' beside CFG* (rescale_scale > 0) is outside the MI355X hot path: it runs under a plain "
+                                          "CFGGuider per modality (rescale_scale = 0) or with no guidance")
+            if ancestral_eta < 0:
+                raise ValueError(f"ancestral_eta={ancestral_eta} must be >= 0")
+        elif stg_guider is None and audio_stg_guider is None:
             self._require_no_guidance(0.0, guider_override, 0.0, "euler", temporal_upscaler, cross_attn_scale)
         else:
             self._require_no_guidance(0.0, guider_override, ge_gamma, sampler, temporal_upscaler, cross_attn_scale)
@@ -210,7 +225,14 @@ class OneStagePipeline:
         if need_cfg and (negative_encoding is None or (internal_audio_active and negative_audio_encoding is None)):
             raise ValueError("cfg_scale / audio_cfg_scale != 1 need the negative prompt's encoding(s)")
         nactx = negative_audio_encoding.to(dev) if (need_cfg and internal_audio_active) else None
-        if heun or ge:
+        if ancestral:
+            # one kernel per step steps to sigma_down and adds the Philox noise; both latents when there is an audio state
+            video_state, audio_state = ancestral_denoise_loop(
+                self.transformer, video_state, audio_state, sigmas, positive_encoding.to(dev), actx, negative_encoding.to(dev) if need_cfg else None,
+                nactx, video_guider.scale if video_guider.enabled() else 1.0,
+                audio_guider.scale if (audio_state is not None and audio_guider.enabled()) else 1.0, ancestral_eta, config.seed, callback,
+                config.use_hip_graph)
+        elif heun or ge:
             # on the device under plain CFG (or none); CFG* and the projected overrides through the eager statements.  Euler + GE has no device form
             # of the joint loop
             loop = heun_denoise_loop if heun else ge_denoise_loop

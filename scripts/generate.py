@@ -687,8 +687,25 @@ def _check_stg(r):
 
 
 def _check_sampler(r, owner):
-    """sampler='heun' runs in OneStagePipeline alone (the AudioVideo route), and not beside STG."""
+    """sampler='heun' runs in OneStagePipeline alone (the AudioVideo route), and not beside STG.  sampler='euler_ancestral' runs there too -- under plain
+    CFG or without guidance, not beside STG, GE, APG or cross_attn_scale -- and in stage 1 of two_stage_distilled (DistilledPipeline)."""
+    if r.ancestral_eta < 0:
+        raise ValueError(f"ancestral_eta={r.ancestral_eta} must not be negative (0: the Euler step)")
     if r.sampler == "euler":
+        if r.ancestral_eta != 1.0:
+            raise ValueError(f"ancestral_eta={r.ancestral_eta!r} goes with sampler='euler_ancestral'")
+        return
+    if r.sampler == "euler_ancestral" and r.two_stage_distilled and r.route is None:
+        return
+    if r.sampler == "euler_ancestral":
+        if owner != "av":
+            raise NotImplementedError(f"sampler={r.sampler!r} is built on the AudioVideo route (OneStagePipeline: generate_audio or an LTX-2.3 checkpoint) and "
+                                      "for two_stage_distilled (DistilledPipeline's stage 1); leave it at its default 'euler'")
+        for k, off in (("stg_scale", 0.0), ("stg_audio_scale", 0.0), ("ge_gamma", 0.0), ("apg_scale", 1.0), ("cross_attn_scale", 1.0)):
+            if (getattr(r, k) > 0) if off == 0.0 else (getattr(r, k) != off):
+                raise NotImplementedError(f"sampler={r.sampler!r} beside {k}={getattr(r, k)!r} is outside the MI355X hot path (see DESIGN.md)")
+        if r.upscale_temporal:
+            raise NotImplementedError(f"sampler={r.sampler!r} beside upscale_temporal is outside the MI355X hot path (see DESIGN.md)")
         return
     if owner != "av":
         raise NotImplementedError(f"sampler={r.sampler!r} is built on the AudioVideo route alone (OneStagePipeline: generate_audio or an LTX-2.3 checkpoint); "
@@ -858,8 +875,8 @@ def _resolve_request(kw: dict):
         _resolve_retake_av(r)
     # Gemma encodes the prompt (and the negative prompt) when its weights are there and no pre-computed encoding is given
     r.gemma_encodes = bool(r.use_gemma and not (r.embedding_path or r.text_features_path) and r.gemma_path and os.path.exists(r.gemma_path))
-    if r.sampler not in ("euler", "heun"):
-        raise ValueError(f"sampler={r.sampler!r}: 'euler' or 'heun'")
+    if r.sampler not in ("euler", "heun", "euler_ancestral"):
+        raise ValueError(f"sampler={r.sampler!r}: 'euler', 'heun' or 'euler_ancestral'")
     asks_av = r.apg_scale != 1.0 or r.stg_scale != 0.0 or r.stg_audio_scale != 0.0 or r.ge_gamma != 0.0 or r.sampler != "euler"
     owner = _owning_route(r) if asks_av else r.route
     owns = _ROUTE_OWNS.get(owner, ())
@@ -926,6 +943,10 @@ def _resolve_request(kw: dict):
         print(f"STG guidance: scale={r.stg_scale}, mode={r.stg_mode}")           # the settings banner's line (reference :1031-1032); the second one: _run_av
     if r.stg_audio_scale > 0:
         print(f"Audio STG guidance: scale={r.stg_audio_scale} (the audio self-attention of the STG blocks is skipped too)")
+    if r.sampler == "euler_ancestral" and r.rescale_scale > 0 and not r.two_stage_distilled and (r.cfg_scale != 1.0 or r.audio_cfg_scale != 1.0):
+        raise NotImplementedError(f"sampler={r.sampler!r} runs under plain CFG (rescale_scale=0.0) or without guidance: beside CFG* it is outside the MI355X hot path")
+    if r.sampler == "euler_ancestral":
+        print(f"Sampler: {r.sampler}, eta={r.ancestral_eta} (noise seed {r.seed}, made in the step kernel)")
     if r.sampler == "heun" or r.ge_gamma > 0:
         print(f"Sampler: {r.sampler}" + (" (2x model evals per step)" if r.sampler == "heun" else "") + (f", GE gamma={r.ge_gamma}" if r.ge_gamma > 0 else ""))
     r.apg_guider = _apg_guider(r)
@@ -1438,7 +1459,8 @@ def _run_two_stage(r, s):
     from ltx_2_mlx_amd.pipelines import DistilledConfig, DistilledPipeline
     pipe = DistilledPipeline(s.model, make_encoder(r) if images else s.vae_decoder, s.vae_decoder, spatial_upscaler=_load_or_random(r, "spatial"))
     conf = DistilledConfig(height=r.height, width=r.width, num_frames=r.num_frames, seed=r.seed, fps=24.0, use_hip_graph=r.use_hip_graph,
-                           audio_enabled=r.generate_audio, tiling_config=_tiling(r))
+                           audio_enabled=r.generate_audio, tiling_config=_tiling(r),
+                           **(dict(sampler=r.sampler, ancestral_eta=r.ancestral_eta) if r.sampler == "euler_ancestral" else {}))
     print("[4/5] two-stage distilled pipeline (8 steps at half resolution, x2 upscale, 3 steps)" + (" with the audio branch" if r.av else ""))
     frames, audio_latent = _timed_run("two-stage", lambda: pipe(s.text_encoding, None, conf, images=images, audio_encoding=s.text_audio_encoding))
     return finish(r, s, frames, audio=decode_audio_latent(r, s, audio_latent) if audio_latent is not None else None)
@@ -1479,6 +1501,8 @@ def _run_av(r, s):
         stg.update(stg_audio_scale=r.stg_audio_scale, stg_blocks=r.stg_blocks, stg_cutoff=r.stg_cutoff)
     if r.sampler == "heun" or r.ge_gamma > 0:
         stg.update(sampler=r.sampler, ge_gamma=r.ge_gamma)
+    if r.sampler == "euler_ancestral":
+        stg.update(sampler=r.sampler, ancestral_eta=r.ancestral_eta)
     print(f"[5/5] Running audio-video generation ({r.num_steps} steps)...")
     frames, audio_latent = _timed_run("audio-video pipeline", lambda: av_pipeline(
         positive_encoding=s.text_encoding, negative_encoding=s.negative_encoding if r.need_cfg else None, config=av_config, images=images,
@@ -1664,7 +1688,8 @@ def generate_video(
     stg_blocks: Optional[List[int]] = None,        # with stg_scale: what OneStagePipeline takes beside it (the reference's CLI leaves them at these defaults)
     stg_cutoff: float = 1.0,
     stg_audio_scale: float = 0.0,                  # > 0: the AudioVideo route STG-guides the audio latent too (OneStagePipeline's stg_audio_scale; plain CFG or none)
-    sampler: str = "euler",                       # "heun": OneStagePipeline's predictor-corrector loop (the reference's own CLI never reaches it)
+    sampler: str = "euler",                       # "heun": OneStagePipeline's predictor-corrector loop (the reference's own CLI never reaches it); "euler_ancestral"
+    ancestral_eta: float = 1.0,                    # with sampler="euler_ancestral": the noise scale of EulerAncestralDiffusionStep (0: the Euler step); the noise seed is `seed`
     use_hip_graph: bool = True,
     num_layers: int = 48,
     num_heads: int = 32,
@@ -1828,8 +1853,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--stg-audio-scale", type=float, default=0.0,
                    help="AudioVideo route, plain CFG (rescale_scale=0) or no guidance (--model-variant distilled): STG-guide the audio latent too, at this scale (the perturbed pass then skips the audio "
                         "self-attention of --stg-blocks as well); with or without --stg-scale")
-    p.add_argument("--sampler", type=str, choices=["euler", "heun"], default="euler", help="on the AudioVideo route (OneStagePipeline): heun runs the second-order "
-                   "predictor-corrector loop, two guided evaluations per step; --ge-gamma adds the GE velocity correction to either sampler")
+    p.add_argument("--sampler", type=str, choices=["euler", "heun", "euler_ancestral"], default="euler", help="on the AudioVideo route (OneStagePipeline): heun runs "
+                   "the second-order predictor-corrector loop, two guided evaluations per step; --ge-gamma adds the GE velocity correction to either sampler; "
+                   "euler_ancestral (also with --two-stage-distilled, stage 1) adds fresh noise per step, made in the step kernel from --seed")
+    p.add_argument("--ancestral-eta", type=float, default=1.0, help="with --sampler euler_ancestral: the noise scale eta (1.0: the reference's step, 0: the Euler step)")
     return p
 
 
@@ -1864,7 +1891,7 @@ def kwargs_from_args(a) -> dict:
         two_stage_cfg=a.two_stage_cfg, modality_scale=a.modality_scale, standard_cfg=a.standard_cfg,
         retake_audio=a.retake_audio, retake_audio_cfg=a.retake_audio_cfg,
         retake_video=a.retake, retake_start_time=a.retake_start, retake_end_time=a.retake_end, retake_composite=a.retake_keep_source,
-        stg_blocks=a.stg_blocks, stg_cutoff=a.stg_cutoff, stg_audio_scale=a.stg_audio_scale, sampler=a.sampler)
+        stg_blocks=a.stg_blocks, stg_cutoff=a.stg_cutoff, stg_audio_scale=a.stg_audio_scale, sampler=a.sampler, ancestral_eta=a.ancestral_eta)
 
 
 def main(argv=None):
