@@ -555,6 +555,23 @@ int ltx2_rescaled_guided_euler_step(const float* x, const float* vel_cond, const
                                     const float* stats, float cfg_scale, double guidance_rescale, float sigma, float sigma_next, float* out, int rows,
                                     int C, void* stream);
 
+/* First-block cache: the three kernels over the fp32 residual stream, taken as n elements.
+ * ltx2_fbc_head_metric: r = h1 - h0 (one fp32 subtraction per element), num = sum |r - head_prev| and den = sum |head_prev| in fp64, and
+ *   record = {double num, double den, int32 skip, int32 0} (24 bytes of device memory, 8-byte aligned) with
+ *   skip = (threshold > 0 && den > 0 && num < (double)threshold * den): no division, den == 0 and threshold == 0 never skip, +inf always does.
+ *   Two launches and no atomics: ltx2_fbc_metric_blocks(n) blocks (one per 8192 elements, 1024 at the most) of 256 threads, thread t of block b adding
+ *   the quads (4 consecutive elements) b*256 + t, + blocks*256, ... in index order, a fixed binary tree over the block into partials[block][2]
+ *   (fp64, 8-byte aligned), then one block of 256 threads that adds the partials t, t + 256, ... and runs the same tree.  The same inputs give the
+ *   same record on every run; 16-byte accesses where every operand is 16-byte aligned, element-wise ones otherwise, with the same sums.
+ *   head_prev NULL reads as zeros.  h1_save (may be NULL) receives a copy of h1 and may be the buffer h0 itself; nothing else may alias.
+ * ltx2_fbc_store_tail: tail = hL - h1.   ltx2_fbc_apply_tail: h = h + tail in place.  One rounded fp32 operation per element.
+ * (additive entries of ABI version 3)                                                                                                      */
+int ltx2_fbc_metric_blocks(int64_t n);
+int ltx2_fbc_head_metric(const float* h0, const float* h1, const float* head_prev, float* r, float* h1_save, double* partials, void* record,
+                         float threshold, int64_t n, void* stream);
+int ltx2_fbc_store_tail(const float* hL, const float* h1, float* tail, int64_t n, void* stream);
+int ltx2_fbc_apply_tail(float* h, const float* tail, int64_t n, void* stream);
+
 /* VAE elementwise glue (simple_decoder.py:492-498, 228-238/339-342, ops.py:109-125, :792-798)  */
 int ltx2_vae_prepare_latent(const float* latent, const float* std, const float* mean, const float* noise,
                             float noise_scale, void* out_bf16, int C, int64_t P, void* stream);
@@ -729,6 +746,38 @@ int ltx2_dit_rescaled_guided_step(ltx2_dit* ctx, ltx2_dit* neg, float* latent, c
                                   float cfg_scale, double guidance_rescale, float sigma, float sigma_next, void* stream);
 int ltx2_dit_graph_capture_rescaled_guided(ltx2_dit* ctx, ltx2_dit* neg, float* latent, const float* host_sigmas, int n_steps, float cfg_scale,
                                            double guidance_rescale, void* stream);
+/* First-block cache on the VideoOnly engine (opt-in).  A slot belongs to one kind of evaluation within a step (the positive
+ * or the negative pass) and holds head_prev and tail, [N][D] fp32 each, and a valid flag; the context holds two more buffers (the scratch r, the
+ * saved h1), so (2*n_slots + 2) * N*D*4 bytes in all, allocated by the first cached pass for the bound shape.  A cached pass in slot s: h0 enters
+ * block 0, which gives h1; ltx2_fbc_head_metric forms r = h1 - h0 and, with a valid slot, the decision against head_prev; the record is read back
+ * by one 24-byte copy on the pass's stream and a wait for it.  Skip: h = h1 + tail, the slot unchanged.  Otherwise blocks 1..L-1 run, then
+ * tail = hL - h1, head_prev = r (a pointer swap) and valid = 1.  Then the output head.  A pass whose slot is not valid, or was named by
+ * ltx2_dit_fbc_force_next since its last pass, computes in full and reads nothing back.  A cached pass cannot be captured (LTX2_E_STATE).
+ * ltx2_dit_fbc_configure: n_slots 0..8 (0: off, the buffers freed) and threshold >= 0; every slot starts invalid with zero counts.  The cache's
+ *   state is kept beside the context, not in it: a caller that turned it on calls ltx2_dit_fbc_configure(ctx, 0, 0) before ltx2_dit_destroy(ctx).
+ * ltx2_dit_fbc_reset: every slot invalid, counts zero, forcing cleared -- a loop calls it at its start.
+ * ltx2_dit_fbc_force_next: the next pass in `slot` (-1: in every slot) computes in full -- a loop calls it before its last step.
+ * ltx2_dit_fbc_stats: the slot's passes and skips since the reset, and the sums of its last pass that read a record (any output may be NULL).
+ * ltx2_dit_forward_fbc: ltx2_dit_forward through ctx's slot.  pass_kind other than LTX2_FBC_PASS_PLAIN, and an AudioVideo context, return
+ *   LTX2_E_UNSUPPORTED: the perturbed (STG) and the modality-isolated pass have no cached form.
+ * ltx2_dit_denoise_step_fbc: ltx2_dit_denoise_step without mask / clean / x0_out through ctx's slot.
+ * ltx2_dit_rescaled_guided_step_fbc: ltx2_dit_rescaled_guided_step with forward(ctx) in ctx's slot_pos and forward(neg) in ctx's slot_neg (the
+ *   slots of `neg` itself are not touched).  With the cache off none of this runs and every other entry is what it was.
+ * (additive entries of ABI version 3)                                                                                                      */
+#define LTX2_FBC_PASS_PLAIN 0
+#define LTX2_FBC_PASS_PERTURBED 1
+#define LTX2_FBC_PASS_ISOLATED 2
+int ltx2_dit_fbc_configure(ltx2_dit* ctx, int n_slots, float threshold);
+int ltx2_dit_fbc_reset(ltx2_dit* ctx);
+int ltx2_dit_fbc_force_next(ltx2_dit* ctx, int slot);
+int ltx2_dit_fbc_stats(const ltx2_dit* ctx, int slot, int64_t* evaluations, int64_t* skips, double* last_num, double* last_den);
+int ltx2_dit_forward_fbc(ltx2_dit* ctx, int slot, int pass_kind, const float* latent, const float* timesteps, int n_timesteps, const float* sigma,
+                         float* velocity, void* stream);
+int ltx2_dit_denoise_step_fbc(ltx2_dit* ctx, int slot, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev, float sigma,
+                              float sigma_next, void* stream);
+int ltx2_dit_rescaled_guided_step_fbc(ltx2_dit* ctx, ltx2_dit* neg, int slot_pos, int slot_neg, float* latent, const float* timesteps,
+                                      int n_timesteps, const float* sigma_dev, float cfg_scale, double guidance_rescale, float sigma,
+                                      float sigma_next, void* stream);
 /* One STG step on the VideoOnly engine (pipelines/one_stage.py:267-326 with a CFGGuider and an STGGuider): forward(ctx), forward(neg) when neg is
  * given (NULL: no CFG), a perturbed forward on ctx ITSELF (ltx2_dit_forward_perturbed: the set of ltx2_dit_set_stg_blocks) into vel_perturbed, the
  * caller's [N][out_channels] fp32 scratch, then ltx2_stg_euler_step in place on `latent` -- in order on the caller's stream.  There is no third

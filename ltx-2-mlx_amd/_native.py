@@ -129,6 +129,18 @@ SIGNATURES = {
     "ltx2_channel_guidance_stats_blocks": (i32, [i32, i32]),
     "ltx2_channel_guidance_stats": (i32, [vp, vp, vp, vp, i64, f32, vp, vp, i32, i32, vp]),
     "ltx2_rescaled_guided_euler_step": (i32, [vp, vp, vp, vp, i64, vp, f32, C.c_double, f32, f32, vp, i32, i32, vp]),
+    # first-block cache (additive entries of ABI version 3)
+    "ltx2_fbc_metric_blocks": (i32, [i64]),
+    "ltx2_fbc_head_metric": (i32, [vp, vp, vp, vp, vp, vp, vp, f32, i64, vp]),
+    "ltx2_fbc_store_tail": (i32, [vp, vp, vp, i64, vp]),
+    "ltx2_fbc_apply_tail": (i32, [vp, vp, i64, vp]),
+    "ltx2_dit_fbc_configure": (i32, [vp, i32, f32]),
+    "ltx2_dit_fbc_reset": (i32, [vp]),
+    "ltx2_dit_fbc_force_next": (i32, [vp, i32]),
+    "ltx2_dit_fbc_stats": (i32, [vp, i32, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "ltx2_dit_forward_fbc": (i32, [vp, i32, i32, vp, vp, i32, vp, vp, vp]),
+    "ltx2_dit_denoise_step_fbc": (i32, [vp, i32, vp, vp, i32, vp, f32, f32, vp]),
+    "ltx2_dit_rescaled_guided_step_fbc": (i32, [vp, vp, i32, i32, vp, vp, i32, vp, f32, C.c_double, f32, f32, vp]),
     "ltx2_vae_prepare_latent": (i32, [vp, vp, vp, vp, f32, vp, i32, i64, vp]),
     "ltx2_pixnorm_mod_silu": (i32, [vp, vp, i64, i32, f32, vp, vp, i32, i32, vp]),
     "ltx2_vae_unpatchify": (i32, [vp, vp, i32, i32, i32, vp]),

@@ -5,6 +5,7 @@
 
 #include "../../include/ltx2hip.h"
 #include "attention.h"
+#include "fbc.h"
 #include "gemm.h"
 #include "gemma.h"
 #include "rowops.h"
@@ -510,6 +511,19 @@ int ltx2_rescaled_guided_euler_step(const float* x, const float* vel_cond, const
     return rescaled_guided_euler_step_launch(x, vel_cond, vel_uncond, ts, (long)ts_stride, stats, cfg_scale, guidance_rescale, sigma, sigma_next, out, rows,
                                              C, (hipStream_t)stream);
 }
+
+int ltx2_fbc_metric_blocks(int64_t n) { return fbc_metric_blocks((long)n); }
+
+int ltx2_fbc_head_metric(const float* h0, const float* h1, const float* head_prev, float* r, float* h1_save, double* partials, void* record,
+                         float threshold, int64_t n, void* stream) {
+    return fbc_head_metric_launch(h0, h1, head_prev, r, h1_save, partials, (FbcRecord*)record, threshold, (long)n, (hipStream_t)stream);
+}
+
+int ltx2_fbc_store_tail(const float* hL, const float* h1, float* tail, int64_t n, void* stream) {
+    return fbc_store_tail_launch(hL, h1, tail, (long)n, (hipStream_t)stream);
+}
+
+int ltx2_fbc_apply_tail(float* h, const float* tail, int64_t n, void* stream) { return fbc_apply_tail_launch(h, tail, (long)n, (hipStream_t)stream); }
 
 int ltx2_vae_prepare_latent(const float* latent, const float* std, const float* mean, const float* noise,
                             float noise_scale, void* out_bf16, int C, int64_t P, void* stream) {

@@ -24,6 +24,7 @@
 
 #include "../../include/ltx2hip.h"
 #include "attention.h"
+#include "fbc.h"
 #include "gemm.h"
 #include "rowops.h"
 #include "sampler.h"
@@ -1984,6 +1985,293 @@ int capture_ready(ltx2_dit* c, ltx2_dit* neg, bool need_neg, bool want_av, const
     return LTX2_OK;
 }
 }  // namespace
+
+namespace {
+// ---------------------------------- first-block cache (VideoOnly contexts, opt-in) ----------------------------------
+// Everything of it is below this line: with the cache off no line of it runs, and forward() and every other entry are what they were.
+// A slot: one kind of evaluation within a step (the positive or the negative pass).
+struct FbcSlot {
+    float *head_prev = nullptr, *tail = nullptr;
+    bool valid = false, force = false;      // force: the next evaluation computes whatever the metric says (consumed by it)
+    int64_t evals = 0, skips = 0;
+    double num = 0.0, den = 0.0;            // the last metric read back (an evaluation that was forced, or had no valid state, reads none)
+};
+// A context's cache, kept beside the context (fbc_states) so that ltx2_dit itself is unchanged: per slot head_prev | tail, then the shared scratch r
+// and the saved h1, each [N][D] fp32, then the metric's partials and its record -- ONE allocation, made on first use for the bound shape and
+// freed by ltx2_dit_fbc_configure(ctx, 0, 0), which a caller issues before ltx2_dit_destroy.  A pass through another context (the negative
+// prompt's) uses the slots of the context the step was called on.
+struct FbcState {
+    int D = 0;
+    std::vector<FbcSlot> fbc_slots;
+    float fbc_threshold = 0.f;
+    float* fbc_buf = nullptr;
+    long fbc_n = 0;                    //   elements of each buffer the allocation was made for
+    float *fbc_r = nullptr, *fbc_save = nullptr;
+    double* fbc_part = nullptr;
+    FbcRecord* fbc_rec = nullptr;
+    FbcRecord* fbc_host = nullptr;     //   pinned: where the step's stream copies the record for the host's decision
+};
+std::unordered_map<const ltx2_dit*, FbcState> fbc_states;
+FbcState* fbc_state(const ltx2_dit* c) {
+    auto it = fbc_states.find(c);
+    return it == fbc_states.end() ? nullptr : &it->second;
+}
+
+// The cut between layer 0 and layer 1.  h0 is copied aside in front of layer 0 (the blocks update the stream in place); behind it fbc_head_metric
+// forms r = h1 - h0, the sums against the slot's head_prev and the decision, and overwrites the saved h0 with h1.  The record comes back by one
+// 24-byte copy on `st` and a wait for it -- the pass is eager, never captured.  A skip adds the slot's tail to the stream and leaves the loop;
+// otherwise layers 1..L-1 run, tail = hL - h1 is stored and r becomes head_prev by a pointer swap.
+struct FbcPass {
+    FbcState* owner;        // the state of the context that holds the slots (c itself, or the positive context of a guided step)
+    int slot;
+};
+
+int fbc_workspace(FbcState* o, long n) {
+    if (o->fbc_buf && o->fbc_n == n) return LTX2_OK;
+    if (o->fbc_buf) (void)hipFree(o->fbc_buf);
+    o->fbc_buf = nullptr;
+    o->fbc_n = 0;
+    const long slots = (long)o->fbc_slots.size(), each = align_up(4L * n), nb = fbc_metric_blocks(n);
+    const long bytes = (2 * slots + 2) * each + align_up(16L * nb) + align_up((long)sizeof(FbcRecord));
+    if (hipMalloc((void**)&o->fbc_buf, bytes) != hipSuccess) {
+        o->fbc_buf = nullptr;
+        ltx2_set_error("dit_fbc: allocating %ld bytes of cache buffers failed", bytes);
+        return LTX2_E_HIP;
+    }
+    if (!o->fbc_host && hipHostMalloc((void**)&o->fbc_host, sizeof(FbcRecord)) != hipSuccess) {
+        o->fbc_host = nullptr;
+        ltx2_set_error("dit_fbc: allocating the pinned record failed");
+        return LTX2_E_HIP;
+    }
+    char* p = (char*)o->fbc_buf;
+    for (FbcSlot& s : o->fbc_slots) {
+        s.head_prev = (float*)p;
+        s.tail = (float*)(p + each);
+        s.valid = false;            // the buffers are new: nothing to compare with
+        p += 2 * each;
+    }
+    o->fbc_r = (float*)p;
+    o->fbc_save = (float*)(p + each);
+    o->fbc_part = (double*)(p + 2 * each);
+    o->fbc_rec = (FbcRecord*)(p + 2 * each + align_up(16L * nb));
+    o->fbc_n = n;
+    return LTX2_OK;
+}
+
+// everything a cached pass refuses, before anything is enqueued; allocates the buffers for c's bound shape
+int fbc_ready(ltx2_dit* c, const FbcPass& f, hipStream_t st, const char* who) {
+    FbcState* o = f.owner;
+    if (c->av) {
+        ltx2_set_error("%s: the first-block cache is built for the VideoOnly model alone (AudioVideo contexts are not)", who);
+        return LTX2_E_UNSUPPORTED;
+    }
+    LTX2_CHECK_ARG(o && !o->fbc_slots.empty(), "%s: the first-block cache is off (ltx2_dit_fbc_configure)", who);
+    LTX2_CHECK_ARG(f.slot >= 0 && f.slot < (int)o->fbc_slots.size(), "%s: slot=%d, %d configured", who, f.slot, (int)o->fbc_slots.size());
+    LTX2_CHECK_ARG(c->cfg.num_layers >= 2 && c->m[0].D == o->D, "%s: the model needs 2 layers at least, and one width in both contexts", who);
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
+        ltx2_set_error("%s: a cached pass reads its decision back on the host and cannot be captured into a graph", who);
+        return LTX2_E_STATE;
+    }
+    return fbc_workspace(o, (long)c->m[0].N * c->m[0].D);
+}
+
+int fbc_before_head(ltx2_dit* c, const FbcPass& f, hipStream_t st) {
+    const Mod& m = c->m[0];
+    if (hipMemcpyAsync(f.owner->fbc_save, m.x, 4L * m.N * m.D, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+        ltx2_set_error("dit_fbc: saving the residual stream failed");
+        return LTX2_E_HIP;
+    }
+    return LTX2_OK;
+}
+
+int fbc_after_head(ltx2_dit* c, const FbcPass& f, hipStream_t st, bool& skip) {
+    FbcState* o = f.owner;
+    FbcSlot& s = o->fbc_slots[f.slot];
+    const Mod& m = c->m[0];
+    const long n = (long)m.N * m.D;
+    skip = false;
+    TRY(fbc_head_metric_launch(o->fbc_save, m.x, s.valid ? s.head_prev : nullptr, o->fbc_r, o->fbc_save, o->fbc_part, o->fbc_rec, o->fbc_threshold, n, st));
+    const bool forced = s.force;
+    s.force = false;
+    s.evals += 1;
+    if (!s.valid || forced) return LTX2_OK;
+    if (hipMemcpyAsync(o->fbc_host, o->fbc_rec, sizeof(FbcRecord), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+        ltx2_set_error("dit_fbc: reading the decision back failed");
+        return LTX2_E_HIP;
+    }
+    s.num = o->fbc_host->num;
+    s.den = o->fbc_host->den;
+    if (o->fbc_host->skip == 0) return LTX2_OK;
+    TRY(fbc_apply_tail_launch(m.x, s.tail, n, st));
+    s.skips += 1;
+    skip = true;
+    return LTX2_OK;
+}
+
+int fbc_after_tail(ltx2_dit* c, const FbcPass& f, hipStream_t st) {
+    FbcState* o = f.owner;
+    FbcSlot& s = o->fbc_slots[f.slot];
+    const Mod& m = c->m[0];
+    TRY(fbc_store_tail_launch(m.x, o->fbc_save, s.tail, (long)m.N * m.D, st));
+    std::swap(s.head_prev, o->fbc_r);           // r becomes head_prev; the old head_prev is the next scratch
+    s.valid = true;
+    return LTX2_OK;
+}
+
+// forward() for one VideoOnly modality and a plain pass, cut behind layer 0: the same launches in the same order, with the cache's three steps
+// around layer 0 and behind the last layer.  Every refusal stands before anything is enqueued.
+int forward_fbc(ltx2_dit* c, const ModIn* in, hipStream_t st, const FbcPass& f, const char* who) {
+    TRY(fbc_ready(c, f, st, who));
+    c->sync_next = 0;
+    Mod& m = c->m[0];
+    const ModW& w = c->mw[0];
+    LTX2_CHECK_ARG(in[0].n_ts == 1 || in[0].n_ts == m.N, "%s: n_timesteps=%d must be 1 or N=%d", who, in[0].n_ts, m.N);
+    LTX2_CHECK_ARG(in[0].n_ts == 1 || c->per_token, "%s: workspace was not sized for per-token timesteps", who);
+    long es = 0, ee = 0;
+    TRY(cast_f32_bf16_launch(in[0].latent, m.lat, (long)m.N * m.Cin, st));
+    TRY(dense(c, gemm_dense_params(m.lat, m.Cin, w.patch_w, w.patch_b, m.x, m.D, m.N, m.D, m.Cin), EPI_F32, st));
+    TRY(adaln_chain(c, m, w.ada, in[0].ts, 1, in[0].n_ts, c->cfg.timestep_scale, m.emb, m.e_f, st));
+    if (in[0].n_ts > 1) {
+        es = (long)w.ada.rows * m.D;
+        ee = m.D;
+    } else if (c->adaln_combine) {
+        TRY(adaln_combine_launch(m.sst_all, m.emb, m.comb, c->cfg.num_layers, (long)w.ada.rows * m.D, st));
+    }
+    m.use_comb = in[0].n_ts == 1 && c->adaln_combine;
+    if (c->v2) TRY(adaln_chain(c, m, w.prompt, in[0].sigma, 0, 1, c->cfg.timestep_scale, m.prompt_emb, nullptr, st));
+    const int fold = (m.use_comb && c->fold_norms >= 1 && m.fold_max >= 1) ? 1 : 0;
+    c->text_kv_ev = nullptr;
+    bool skipped = false;
+    for (int l = 0; l < c->cfg.num_layers && !skipped; ++l) {
+        if (l == 0) TRY(fbc_before_head(c, f, st));
+        TRY(block_attention(c, 0, l, es, st, fold, false));
+        TRY(block_ffn(c, 0, l, es, st));
+        if (l == 0) TRY(fbc_after_head(c, f, st, skipped));
+    }
+    if (!skipped) TRY(fbc_after_tail(c, f, st));
+    TRY(norm_mod_launch(m.x, m.D, m.h, m.D, m.N, m.D, c->cfg.norm_eps, 1, w.sst_out + m.D, w.sst_out, m.e_f, m.e_f, ee, st));
+    return dense(c, gemm_dense_params(m.h, m.D, w.proj_w, w.proj_b, in[0].velocity, m.Cout, m.N, m.Cout, m.D), EPI_F32, st);
+}
+}  // namespace
+
+int ltx2_dit_fbc_configure(ltx2_dit* c, int n_slots, float threshold) {
+    LTX2_CHECK_ARG(c, "dit_fbc_configure: null context");
+    LTX2_CHECK_ARG(n_slots >= 0 && n_slots <= 8, "dit_fbc_configure: n_slots=%d, 0 (off) to 8", n_slots);
+    LTX2_CHECK_ARG(threshold >= 0.f, "dit_fbc_configure: threshold=%g must be >= 0", threshold);      // (a NaN fails it too)
+    if (n_slots > 0 && c->av) {
+        ltx2_set_error("dit_fbc_configure: the first-block cache is built for the VideoOnly model alone (AudioVideo contexts are not)");
+        return LTX2_E_UNSUPPORTED;
+    }
+    LTX2_CHECK_ARG(n_slots == 0 || c->cfg.num_layers >= 2, "dit_fbc_configure: a model of one layer has no tail to reuse");
+    if (FbcState* o = fbc_state(c)) {          // (hipFree waits for the passes that may still be reading the buffers)
+        if ((o->fbc_buf && hipFree(o->fbc_buf) != hipSuccess) || (o->fbc_host && hipHostFree(o->fbc_host) != hipSuccess)) {
+            ltx2_set_error("dit_fbc_configure: freeing the cache buffers failed");
+            return LTX2_E_HIP;
+        }
+        fbc_states.erase(c);
+    }
+    if (n_slots == 0) return LTX2_OK;
+    FbcState& s = fbc_states[c];
+    s.D = c->m[0].D;
+    s.fbc_slots.assign(n_slots, FbcSlot{});
+    s.fbc_threshold = threshold;
+    return LTX2_OK;
+}
+
+int ltx2_dit_fbc_reset(ltx2_dit* c) {
+    LTX2_CHECK_ARG(c, "dit_fbc_reset: null context");
+    FbcState* o = fbc_state(c);
+    if (!o) return LTX2_OK;
+    for (FbcSlot& s : o->fbc_slots) {
+        s.valid = s.force = false;
+        s.evals = s.skips = 0;
+        s.num = s.den = 0.0;
+    }
+    return LTX2_OK;
+}
+
+int ltx2_dit_fbc_force_next(ltx2_dit* c, int slot) {
+    FbcState* o = c ? fbc_state(c) : nullptr;
+    const int n = o ? (int)o->fbc_slots.size() : 0;
+    LTX2_CHECK_ARG(c && slot >= -1 && slot < n, "dit_fbc_force_next: bad context / slot (%d configured)", n);
+    for (int k = 0; k < n; ++k)
+        if (slot < 0 || slot == k) o->fbc_slots[k].force = true;
+    return LTX2_OK;
+}
+
+int ltx2_dit_fbc_stats(const ltx2_dit* c, int slot, int64_t* evaluations, int64_t* skips, double* last_num, double* last_den) {
+    const FbcState* o = c ? fbc_state(c) : nullptr;
+    LTX2_CHECK_ARG(o && slot >= 0 && slot < (int)o->fbc_slots.size(), "dit_fbc_stats: bad context / slot");
+    const FbcSlot& s = o->fbc_slots[slot];
+    if (evaluations) *evaluations = s.evals;
+    if (skips) *skips = s.skips;
+    if (last_num) *last_num = s.num;
+    if (last_den) *last_den = s.den;
+    return LTX2_OK;
+}
+
+int ltx2_dit_forward_fbc(ltx2_dit* c, int slot, int pass_kind, const float* latent, const float* timesteps, int n_timesteps, const float* sigma,
+                         float* velocity, void* stream) {
+    LTX2_CHECK_ARG(c && latent && timesteps && velocity, "dit_forward_fbc: null argument");
+    LTX2_CHECK_ARG(pass_kind >= LTX2_FBC_PASS_PLAIN && pass_kind <= LTX2_FBC_PASS_ISOLATED, "dit_forward_fbc: bad pass_kind %d", pass_kind);
+    if (c->av || pass_kind != LTX2_FBC_PASS_PLAIN) {
+        ltx2_set_error("dit_forward_fbc: the first-block cache is built for the plain pass of the VideoOnly model alone (%s is not)",
+                       c->av ? "an AudioVideo model" : pass_kind == LTX2_FBC_PASS_PERTURBED ? "a perturbed (STG) pass" : "a modality-isolated pass");
+        return LTX2_E_UNSUPPORTED;
+    }
+    TRY(check_ready(c, "dit_forward_fbc", false));
+    ModIn in[1] = {{latent, timesteps, n_timesteps, sigma ? sigma : timesteps, velocity}};
+    return forward_fbc(c, in, (hipStream_t)stream, {fbc_state(c), slot}, "dit_forward_fbc");
+}
+
+int ltx2_dit_denoise_step_fbc(ltx2_dit* c, int slot, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev, float sigma,
+                              float sigma_next, void* stream) {
+    LTX2_CHECK_ARG(c && latent && timesteps, "dit_denoise_step_fbc: null argument");
+    if (c->av) {
+        ltx2_set_error("dit_denoise_step_fbc: the first-block cache is built for the VideoOnly model alone (AudioVideo contexts are not)");
+        return LTX2_E_UNSUPPORTED;
+    }
+    TRY(check_ready(c, "dit_denoise_step_fbc", false));
+    LTX2_CHECK_ARG(sigma != 0.f, "Sigma can't be 0.0");
+    hipStream_t st = (hipStream_t)stream;
+    Mod& m = c->m[0];
+    ModIn in[1] = {{latent, timesteps, n_timesteps, sigma_dev ? sigma_dev : timesteps, m.vel}};
+    TRY(forward_fbc(c, in, st, {fbc_state(c), slot}, "dit_denoise_step_fbc"));
+    TRY(x0_from_velocity_launch(latent, m.vel, timesteps, n_timesteps == 1 ? 0 : 1, 0.f, m.x0, m.N, m.Cout, st));
+    return euler_step_launch(latent, m.x0, nullptr, nullptr, sigma, sigma_next, latent, m.N, m.Cout, st);
+}
+
+int ltx2_dit_rescaled_guided_step_fbc(ltx2_dit* c, ltx2_dit* neg, int slot_pos, int slot_neg, float* latent, const float* timesteps, int n_timesteps,
+                                      const float* sigma_dev, float cfg_scale, double guidance_rescale, float sigma, float sigma_next, void* stream) {
+    LTX2_CHECK_ARG(c && neg && latent && timesteps, "dit_rescaled_guided_step_fbc: null argument");
+    if (c->av || neg->av) {
+        ltx2_set_error("dit_rescaled_guided_step_fbc: the first-block cache is built for the VideoOnly model alone (AudioVideo contexts are not)");
+        return LTX2_E_UNSUPPORTED;
+    }
+    const int n_ts[2] = {n_timesteps, 1};
+    TRY(step_ready(c, neg, false, n_ts, "dit_rescaled_guided_step_fbc"));
+    LTX2_CHECK_ARG(sigma != 0.f, "Sigma can't be 0.0");          // before the workspace is touched
+    LTX2_CHECK_ARG(slot_pos != slot_neg, "dit_rescaled_guided_step_fbc: the two passes need a slot each (both are %d)", slot_pos);
+    // both passes' refusals before the first is enqueued
+    const char* who = "dit_rescaled_guided_step_fbc";
+    hipStream_t st = (hipStream_t)stream;
+    const FbcPass pp = {fbc_state(c), slot_pos}, pn = {fbc_state(c), slot_neg};
+    TRY(fbc_ready(c, pp, st, who));
+    TRY(fbc_ready(neg, pn, st, who));
+    const bool rescale = guidance_rescale > 0.0;
+    if (rescale) TRY(rescaled_workspace(c));
+    // rescaled_guided_step() with its two evaluations through the slots
+    Mod& m = c->m[0];
+    ModIn in[1] = {{latent, timesteps, n_timesteps, sigma_dev ? sigma_dev : timesteps, m.vel}};
+    TRY(forward_fbc(c, in, st, pp, who));
+    in[0].velocity = neg->m[0].vel;
+    TRY(forward_fbc(neg, in, st, pn, who));
+    const long stride = n_timesteps == 1 ? 0 : 1;
+    if (rescale) TRY(channel_guidance_stats_launch(latent, m.vel, neg->m[0].vel, timesteps, stride, cfg_scale, c->cs_part, c->cs_stats, m.N, m.Cout, st));
+    return rescaled_guided_euler_step_launch(latent, m.vel, neg->m[0].vel, timesteps, stride, rescale ? c->cs_stats : nullptr, cfg_scale, guidance_rescale,
+                                             sigma, sigma_next, latent, m.N, m.Cout, st);
+}
 
 int ltx2_dit_guided_step(ltx2_dit* c, ltx2_dit* neg, float* latent, const float* timesteps, int n_timesteps, const float* sigma_dev,
                          const float* mask, const float* clean, float cfg_scale, float sigma, float sigma_next, void* stream) {

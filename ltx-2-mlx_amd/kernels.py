@@ -708,7 +708,47 @@ def rescaled_guided_euler_step(x: torch.Tensor, vel_cond: torch.Tensor, vel_unco
     return out
 
 
-GUIDANCE_MODES = {"cfg_star": 0, "apg": 1, "legacy_apg": 2}      # `mode` of ltx2_projected_euler_step / ltx2_dit_projected_step
+def _fbc_operands(*ts: Optional[torch.Tensor]) -> int:
+    n = ts[0].numel()
+    for t in ts:
+        assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n)
+    return n
+
+
+def fbc_head_metric(h0: torch.Tensor, h1: torch.Tensor, head_prev: Optional[torch.Tensor], threshold: float, r: Optional[torch.Tensor] = None,
+                    h1_save: Optional[torch.Tensor] = None, dtype: Optional[torch.dtype] = None) -> Tuple[torch.Tensor, float, float, int]:
+    """The first-block cache's metric over fp32 tensors of one shape (ltx2_fbc_head_metric): r = h1 - h0, num = sum |r - head_prev| and
+    den = sum |head_prev| in fp64 in a fixed order without atomics, skip = (threshold > 0 and den > 0 and num < threshold*den).  head_prev None
+    reads as zeros; h1_save receives a copy of h1 and may be h0 itself.  -> (r, num, den, skip); reading the record back waits for the stream."""
+    if r is None:
+        r = torch.empty_like(h0)
+    n = _fbc_operands(h0, h1, head_prev, r, h1_save)
+    L = nv.lib(dtype)
+    partials = torch.empty(int(L.ltx2_fbc_metric_blocks(n)), 2, device=h0.device, dtype=torch.float64)
+    rec = torch.zeros(3, device=h0.device, dtype=torch.float64)
+    nv.check(L.ltx2_fbc_head_metric(nv.ptr(h0), nv.ptr(h1), nv.ptr(head_prev), nv.ptr(r), nv.ptr(h1_save), nv.ptr(partials), nv.ptr(rec),
+                                    float(threshold), n, nv.stream()))
+    host = rec.cpu()
+    return r, float(host[0]), float(host[1]), int(host[2:3].view(torch.int32)[0])
+
+
+def fbc_store_tail(h_last: torch.Tensor, h1: torch.Tensor, tail: Optional[torch.Tensor] = None, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """tail = h_last - h1 over fp32 tensors of one shape (ltx2_fbc_store_tail), one rounded subtraction per element."""
+    if tail is None:
+        tail = torch.empty_like(h_last)
+    n = _fbc_operands(h_last, h1, tail)
+    nv.check(nv.lib(dtype).ltx2_fbc_store_tail(nv.ptr(h_last), nv.ptr(h1), nv.ptr(tail), n, nv.stream()))
+    return tail
+
+
+def fbc_apply_tail(h: torch.Tensor, tail: torch.Tensor, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """h += tail in place over fp32 tensors of one shape (ltx2_fbc_apply_tail), one rounded addition per element."""
+    n = _fbc_operands(h, tail)
+    nv.check(nv.lib(dtype).ltx2_fbc_apply_tail(nv.ptr(h), nv.ptr(tail), n, nv.stream()))
+    return h
+
+
+GUIDANCE_MODES = {"cfg_star": 0, "apg": 1, "legacy_apg": 2}    # `mode` of ltx2_projected_euler_step / ltx2_dit_projected_step
 
 
 def guidance_sums_blocks(rows: int, c: int, dtype: Optional[torch.dtype] = None) -> int:

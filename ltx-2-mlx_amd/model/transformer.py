@@ -285,6 +285,8 @@ class LTXModel:
     def __del__(self):
         try:
             if getattr(self, "_h", None):
+                if getattr(self, "_fbc", (0.0, 0))[1]:          # the first-block cache's buffers live beside the context: freed before it
+                    self._L.ltx2_dit_fbc_configure(self._h, 0, 0.0)
                 self._L.ltx2_dit_destroy(self._h)
                 self._h = None
         except Exception:
@@ -829,6 +831,71 @@ class LTXModel:
     def replay_rescaled_guided_graph(self) -> None:
         """Replay the graph captured by capture_rescaled_guided_graph (it belongs to the VideoOnly context that ran the capture)."""
         self._replay("rescaled_guided", "no rescaled guided graph captured")
+
+    # ------------------------------------------------------------------ first-block cache (video-only engine, opt-in; DESIGN.md section 1)
+    def enable_first_block_cache(self, threshold: float, slots: int = 2) -> None:
+        """Turn the first-block cache on for this context (ltx2_dit_fbc_configure): `slots` cache slots, one per kind of evaluation within a
+        step, and the threshold t of the skip test sum|r - head_prev| < t * sum|head_prev| on block 0's residual r.  The cached entries
+        (forward_cached, denoise_step_cached_, rescaled_guided_step_cached_) then reuse the stored residual of blocks 1..L-1 where the test
+        holds; every other entry is untouched.  slots=0 turns it off and frees the buffers ((2*slots + 2) fp32 [N, D] buffers).  A negative
+        threshold is a ValueError; an AudioVideo model is refused."""
+        if not float(threshold) >= 0.0:
+            raise ValueError(f"first_block_cache threshold={threshold!r} must be >= 0")
+        if self.is_av:
+            raise NotImplementedError("the first-block cache is built for the video-only model alone (AudioVideo / LTX-2.3 joint models are outside it)")
+        nv.check(self._L.ltx2_dit_fbc_configure(self._h, int(slots), float(threshold)))
+        self._fbc = (float(threshold), int(slots))
+
+    def reset_first_block_cache(self) -> None:
+        """Every slot invalid, its counts zero (ltx2_dit_fbc_reset): what a loop does at its start."""
+        nv.check(self._L.ltx2_dit_fbc_reset(self._h))
+
+    def force_first_block_cache(self, slot: int = -1) -> None:
+        """The next cached evaluation in `slot` (-1: in every slot) computes in full (ltx2_dit_fbc_force_next): a loop's last step."""
+        nv.check(self._L.ltx2_dit_fbc_force_next(self._h, int(slot)))
+
+    def first_block_cache_stats(self) -> List[Dict[str, float]]:
+        """Per slot: evaluations and skips since the last reset, and num / den of the last evaluation that read its metric back."""
+        out = []
+        for k in range(getattr(self, "_fbc", (0.0, 0))[1]):
+            ev, sk, num, den = C.c_int64(), C.c_int64(), C.c_double(), C.c_double()
+            nv.check(self._L.ltx2_dit_fbc_stats(self._h, k, C.byref(ev), C.byref(sk), C.byref(num), C.byref(den)))
+            out.append(dict(evaluations=ev.value, skips=sk.value, last_num=num.value, last_den=den.value))
+        return out
+
+    def forward_cached(self, video: Modality, slot: int = 0, perturbations=None) -> torch.Tensor:
+        """__call__(video) of the video-only model through cache slot `slot` (ltx2_dit_forward_fbc).  A perturbed (STG) pass has no cached form."""
+        self._check_inputs(video, None, perturbations)
+        if self.is_av:
+            raise NotImplementedError("the first-block cache is built for the video-only model alone (AudioVideo / LTX-2.3 joint models are outside it)")
+        kind = 0 if self._perturbation_flags(perturbations) is None else 1
+        ts, n_ts = self._timesteps(video)
+        lat = video.latent[0].to(self.device, torch.float32).contiguous()
+        out = torch.empty(lat.shape[0], self.out_channels, device=self.device, dtype=torch.float32)
+        self._ensure_prepared(video, per_token=(n_ts != 1))
+        self._apply_context_masks(video)
+        sg = self._sigma(video) if self.cross_attention_adaln else None
+        nv.check(self._L.ltx2_dit_forward_fbc(self._h, int(slot), kind, nv.ptr(lat), nv.ptr(ts), n_ts, nv.ptr(sg), nv.ptr(out), nv.stream()))
+        return out[None]
+
+    def denoise_step_cached_(self, latent: torch.Tensor, video: Modality, sigma: float, sigma_next: float, slot: int = 0) -> None:
+        """denoise_step_ of the video-only model without conditioning, its forward through cache slot `slot` (ltx2_dit_denoise_step_fbc)."""
+        if self.is_av:
+            raise NotImplementedError("the first-block cache is built for the video-only model alone (AudioVideo / LTX-2.3 joint models are outside it)")
+        ts, n_ts, sg = self._step_inputs(latent, video, sigma)
+        nv.check(self._L.ltx2_dit_denoise_step_fbc(self._h, int(slot), nv.ptr(latent), nv.ptr(ts), n_ts, nv.ptr(sg), float(sigma), float(sigma_next),
+                                                    nv.stream()))
+
+    def rescaled_guided_step_cached_(self, neg: "LTXModel", latent: torch.Tensor, video: Modality, sigma: float, sigma_next: float, cfg_scale: float,
+                                     guidance_rescale: float, slots: Tuple[int, int] = (0, 1)) -> None:
+        """rescaled_guided_step_ with the positive pass through this context's cache slot slots[0] and the negative pass, on `neg`, through this
+        context's slot slots[1] (ltx2_dit_rescaled_guided_step_fbc).  Eager only: each pass reads its decision back."""
+        if self.is_av or neg.is_av:
+            raise NotImplementedError("the first-block cache is built for the video-only model alone (AudioVideo / LTX-2.3 joint models are outside it)")
+        pos, ng = self._contexts(neg)
+        ts, n_ts, sg = pos._step_inputs(latent, video, sigma)
+        nv.check(pos._L.ltx2_dit_rescaled_guided_step_fbc(pos._h, ng._h, int(slots[0]), int(slots[1]), nv.ptr(latent), nv.ptr(ts), n_ts, nv.ptr(sg),
+                                                          float(cfg_scale), float(guidance_rescale), float(sigma), float(sigma_next), nv.stream()))
 
     # ------------------------------------------------------------------ spatio-temporal guidance on top of CFG (video-only engine)
     def stg_step_(self, neg: Optional["LTXModel"], latent: torch.Tensor, video: Modality, sigma: float, sigma_next: float, cfg_scale: float,

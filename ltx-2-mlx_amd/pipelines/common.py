@@ -381,18 +381,36 @@ def rescale_noise_cfg(noise_cfg: torch.Tensor, noise_pred_text: torch.Tensor, gu
 
 
 def standard_cfg_denoise_loop(transformer, video_state: LatentState, sigmas, context: torch.Tensor, negative_context: Optional[torch.Tensor],
-                              cfg_scale: float, guidance_rescale: float, callback=None, use_hip_graph: bool = True, fused: bool = True) -> LatentState:
+                              cfg_scale: float, guidance_rescale: float, callback=None, use_hip_graph: bool = True, fused: bool = True,
+                              first_block_cache: float = 0.0) -> LatentState:
     """The guided branch of the reference's standard one-stage loop (scripts/generate.py:1895-1976: the dev video-only model under classifier-free
     guidance): per step the positive and the negative prompt, g = uncond + cfg_scale*(cond - uncond) on the x0 predictions, with
     guidance_rescale > 0 rescale_noise_cfg(g, cond, guidance_rescale), then the x0 Euler step.  fused=True: every step is ONE C call
     (LTXModel.rescaled_guided_step_: the two forwards, the per-channel statistics, the step kernel) and with no callback and fewer than 64
     steps the loop is one captured graph.  fused=False: the reference's statements one by one in torch through X0Model, the comparison form.
     cfg_scale <= 1 is the unguided loop (joint_denoise_loop), as the reference guides only above 1.  The route has no conditioning: the
-    denoise mask must be all ones.  `transformer` is an X0Model of a video-only model.  Returns the video state."""
+    denoise mask must be all ones.  `transformer` is an X0Model of a video-only model.  Returns the video state.
+    first_block_cache = t > 0 (an MI355X addition): the fused loop with every evaluation through the first-block cache at
+    threshold t, the positive pass in slot 0 and the negative one in slot 1 -- eager, one C call per step, as each evaluation reads its decision
+    back; with cfg_scale <= 1 the plain loop through slot 0.  The model's cache is left off afterwards; first_block_cache_last_stats() holds the
+    loop's counts.  A negative threshold is a ValueError."""
     from ..components import EulerDiffusionStep
     model = transformer.velocity_model
+    if not float(first_block_cache) >= 0.0:
+        raise ValueError(f"first_block_cache={first_block_cache!r} must be >= 0 (0: off)")
     if model.is_av:
+        if first_block_cache > 0:
+            raise NotImplementedError("first_block_cache is built for the video-only model alone (AudioVideo / LTX-2.3 joint models are outside it)")
         raise ValueError("standard_cfg_denoise_loop runs the video-only model (AudioVideo models are guided by OneStagePipeline)")
+    if first_block_cache > 0:
+        if not fused:
+            raise NotImplementedError("first_block_cache runs the fused loop (fused=False is the torch comparison form)")
+        if not bool((video_state.denoise_mask == 1).all()):
+            raise ValueError("standard_cfg_denoise_loop has no conditioning (the reference's standard loop has none): the denoise mask must be all ones")
+        if cfg_scale > 1.0 and negative_context is None:
+            raise ValueError("guidance needs the negative prompt's encoding")
+        return _first_block_cache_loop(model, video_state, sigmas, context, negative_context if cfg_scale > 1.0 else None, cfg_scale,
+                                       guidance_rescale, float(first_block_cache), callback, use_hip_graph)
     if not cfg_scale > 1.0:
         return joint_denoise_loop(transformer, False, video_state, None, sigmas, context, None, EulerDiffusionStep(), callback, use_hip_graph)[0]
     if negative_context is None:
@@ -422,6 +440,52 @@ def standard_cfg_denoise_loop(transformer, video_state: LatentState, sigmas, con
     vm = lambda i: modality_from_state(video_state.replace(latent=lat[None]), context, sig[i], uniform=True)      # noqa: E731
     _run_steps(n, callback, use_hip_graph, lambda: model.capture_rescaled_guided_graph(neg, lat, sig, cfg_scale, guidance_rescale),
                model.replay_rescaled_guided_graph, lambda i: model.rescaled_guided_step_(neg, lat, vm(i), sig[i], sig[i + 1], cfg_scale, guidance_rescale))
+    return _with_latent(video_state, lat)
+
+
+_fbc_last_stats: List[dict] = []
+
+
+def first_block_cache_last_stats() -> List[dict]:
+    """Per slot, the counts of the last loop that ran with first_block_cache > 0 (LTXModel.first_block_cache_stats() at its end)."""
+    return [dict(d) for d in _fbc_last_stats]
+
+
+def first_block_cache_summary(stats: List[dict], threshold: float) -> str:
+    """The one line a run with the cache on prints."""
+    k, m = sum(d["skips"] for d in stats), sum(d["evaluations"] for d in stats)
+    return f"first-block cache: {k} of {m} evaluations reused the tail (threshold {threshold:g})"
+
+
+def _first_block_cache_loop(model, video_state: LatentState, sigmas, context, negative_context, cfg_scale: float, guidance_rescale: float,
+                            threshold: float, callback, use_hip_graph: bool) -> LatentState:
+    """The standard loop with the first-block cache on: negative_context None is the plain loop (slot 0), otherwise the guided one (slots 0 and
+    1).  The driver's three rules: every slot is reset at the start, the last step is forced to compute (the first one computes anyway: its
+    slots are not valid), and the counts are read at the end.  The cache is configured on the positive context alone."""
+    sig = [float(s) for s in sigmas]
+    n = len(sig) - 1
+    guided = negative_context is not None
+    if use_hip_graph:
+        _note_eager_once("the first-block cache reads a decision back per evaluation")
+    model, _, lat, _, _ = _video_loop_inputs(model, video_state)
+    neg = _prepare_contexts(model, guided, False, video_state.positions, context, negative_context)
+    vm = lambda i: modality_from_state(video_state.replace(latent=lat[None]), context, sig[i], uniform=True)      # noqa: E731
+    model.enable_first_block_cache(threshold, slots=2 if guided else 1)
+    try:
+        model.reset_first_block_cache()
+        for i in range(n):
+            if i == n - 1:
+                model.force_first_block_cache(-1)
+            if guided:
+                model.rescaled_guided_step_cached_(neg, lat, vm(i), sig[i], sig[i + 1], cfg_scale, guidance_rescale, slots=(0, 1))
+            else:
+                model.denoise_step_cached_(lat, vm(i), sig[i], sig[i + 1], slot=0)
+            if callback:
+                callback(i + 1, n)
+        torch.cuda.synchronize()
+        _fbc_last_stats[:] = model.first_block_cache_stats()
+    finally:
+        model.enable_first_block_cache(0.0, slots=0)
     return _with_latent(video_state, lat)
 
 

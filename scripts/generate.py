@@ -686,6 +686,31 @@ def _check_stg(r):
         raise ValueError(f"stg_cutoff={r.stg_cutoff} must lie in [0, 1]: the fraction of the steps that STG guides")
 
 
+def _check_first_block_cache(r, final: bool):
+    """first_block_cache = t > 0 (--first-block-cache T): the first-block cache of the video-only standard loops (_run_standard: the plain loop and the standard_cfg one).  A negative
+    threshold is a ValueError.  final=False, before the checkpoint is looked at: the named routes, STG, Heun / ancestral, GE and APG refuse it; final=True, once the route is known: the
+    AudioVideo / LTX-2.3 route, the two-stage route and a conditioned (image_path) or placeholder standard run do."""
+    t = r.first_block_cache
+    if not float(t) >= 0.0:
+        raise ValueError(f"first_block_cache={t!r} must be >= 0 (0: off)")
+    if t == 0:
+        return
+    tail = "the first-block cache is built for the video-only standard loops alone (the plain loop and standard_cfg; see DESIGN.md)"
+    if not final:
+        if r.route not in (None, "standard_cfg"):
+            raise NotImplementedError(f"first_block_cache={t!r} on the {r.route} route: {tail}")
+        for k, off in (("stg_scale", 0.0), ("stg_audio_scale", 0.0), ("ge_gamma", 0.0), ("apg_scale", 1.0), ("sampler", "euler")):
+            if getattr(r, k) != off:
+                raise NotImplementedError(f"first_block_cache={t!r} beside {k}={getattr(r, k)!r}: {tail}")
+        if r.two_stage_distilled:
+            raise NotImplementedError(f"first_block_cache={t!r} with two_stage_distilled: {tail}")
+        return
+    if r.route not in ("standard", "standard_cfg"):
+        raise NotImplementedError(f"first_block_cache={t!r} on the {'AudioVideo / LTX-2.3' if r.route == 'av' else r.route} route: {tail}")
+    if r.image_path or r.use_placeholder:
+        raise NotImplementedError(f"first_block_cache={t!r} with {'image_path' if r.image_path else 'use_placeholder'}: {tail}; the loop it caches has no conditioning")
+
+
 def _check_sampler(r, owner):
     """sampler='heun' runs in OneStagePipeline alone (the AudioVideo route), and not beside STG.  sampler='euler_ancestral' runs there too -- under plain
     CFG or without guidance, not beside STG, GE, APG or cross_attn_scale -- and in stage 1 of two_stage_distilled (DistilledPipeline)."""
@@ -867,6 +892,7 @@ def _resolve_request(kw: dict):
         r.route = "ic_lora"
     else:
         r.route = None                                                   # two_stage, av or standard: decided below, once the checkpoint is looked at
+    _check_first_block_cache(r, final=False)                             # an MI355X extra of two routes: refused by name before a named route looks at its files
     if r.route == "retake":                                              # its refusals win over every other one
         _refuse_combinations(r)
         _resolve_retake(r)
@@ -1001,6 +1027,7 @@ def _resolve_request(kw: dict):
     r.toy = r.vae_base_channels is not None and r.vae_base_channels != 128        # debug-size VAE: matching debug-size upscaler / encoder
     if r.route is None:
         r.route = "two_stage" if r.two_stage_distilled else "av" if r.av else "standard"
+    _check_first_block_cache(r, final=True)
     return r
 
 
@@ -1517,6 +1544,17 @@ def _run_av(r, s):
     return finish(r, s, frames, audio=decode_audio_latent(r, s, audio_latent) if audio_latent is not None else None)
 
 
+def _first_block_cache_kw(r):
+    """The keyword only when the cache is on: with it off the loop is called exactly as before."""
+    return dict(first_block_cache=r.first_block_cache) if r.first_block_cache > 0 else {}
+
+
+def _first_block_cache_report(r):
+    if r.first_block_cache > 0:
+        from ltx_2_mlx_amd.pipelines.common import first_block_cache_last_stats, first_block_cache_summary
+        print("  " + first_block_cache_summary(first_block_cache_last_stats(), r.first_block_cache))
+
+
 def _run_standard(r, s):
     """The standard route (one-stage, video-only; reference :1778-2095): the distilled sigma table (LTX2Scheduler for another variant) in one captured hipGraph, or eagerly with
     use_hip_graph=False, with image_path as an encoded frame 0, or as noise arithmetic in placeholder mode. upscale_spatial doubles the denoised latent before decoding (2W x 2H output);
@@ -1559,7 +1597,15 @@ def _run_standard(r, s):
         print(f"  Standard CFG loop: cfg={r.cfg_scale}" + (f", guidance rescale={r.guidance_rescale}" if r.cfg_scale > 1.0 and r.guidance_rescale > 0 else ""))
         st = LatentState(latent=tok, denoise_mask=torch.ones(1, tok.shape[1], 1, device=device), positions=positions, clean_latent=torch.zeros_like(tok))
         tok = standard_cfg_denoise_loop(model, st, sigmas, s.text_encoding, negative.to(device) if negative is not None else None, r.cfg_scale, r.guidance_rescale,
-                                        use_hip_graph=r.use_hip_graph).latent
+                                        use_hip_graph=r.use_hip_graph, **_first_block_cache_kw(r)).latent
+        _first_block_cache_report(r)
+    elif r.first_block_cache > 0:
+        # first_block_cache > 0 on the plain route: the same loop at cfg = 1 (no negative prompt), every forward through cache slot 0, eager
+        from ltx_2_mlx_amd.pipelines.common import standard_cfg_denoise_loop
+        from ltx_2_mlx_amd.types import LatentState
+        st = LatentState(latent=tok, denoise_mask=torch.ones(1, tok.shape[1], 1, device=device), positions=positions, clean_latent=torch.zeros_like(tok))
+        tok = standard_cfg_denoise_loop(model, st, sigmas, s.text_encoding, None, 1.0, 0.0, use_hip_graph=r.use_hip_graph, **_first_block_cache_kw(r)).latent
+        _first_block_cache_report(r)
     elif r.image_path:
         # image-to-video: encoded image replaces latent frame 0, its tokens keep (1 - strength) of the noise level
         from ltx_2_mlx_amd.conditioning import VideoLatentTools
@@ -1711,6 +1757,7 @@ def generate_video(
     ti2vid_hq_audio: bool = False,
     two_stage_cfg: bool = False,
     standard_cfg: bool = False,                    # the dev video-only model under CFG with the per-channel rescale: the guided branch of the reference's standard loop
+    first_block_cache: float = 0.0,                # > 0: the video-only standard loops reuse the residual of blocks 1..L-1 where block 0's residual moved less than this threshold (eager loop)
     modality_scale: float = 3.0,
     two_stage_rescale: float = 0.0,
     retake_audio: Optional[str] = None,
@@ -1830,6 +1877,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--two-stage-cfg", action="store_true", help="TwoStagePipeline (the reference's --pipeline two-stage on an AudioVideo checkpoint): --steps-stage1 joint steps at half "
                    "resolution under CFG (video --cfg-stage1 or --cfg, audio 7) and modality-isolated guidance (--modality-scale), x2 spatial upscale, 3 joint distilled steps; needs "
                    "--spatial-upscaler-weights; --decode-audio writes the .wav.  (--pipeline two-stage itself keeps its refusal)")
+    p.add_argument("--first-block-cache", type=float, default=0.0, metavar="T",
+                   help="first-block cache of the video-only standard loops (plain and --standard-cfg): reuse the residual of blocks 1..L-1 on steps whose block-0 residual moved "
+                        "less than T (relative L1); 0 is off.  The loop then runs eagerly.  Not verified with real weights")
     p.add_argument("--standard-cfg", action="store_true", help="the reference's standard one-stage loop for the dev video-only model (--model-variant dev): positive and negative prompt "
                    "every step, CFG at --cfg on the x0 predictions, the per-channel --guidance-rescale (default 0.7), --cross-attn-scale on layers 40-47; no conditioning "
                    "(--image is refused).  (--model-variant dev --cfg 3 without this flag keeps its refusal)")
@@ -1888,7 +1938,7 @@ def kwargs_from_args(a) -> dict:
         fp8_resident=a.fp8_resident, fp8_compute=a.fp8_compute, model_version=a.model_version, compute_dtype="bfloat16" if a.bf16 else None, num_layers=a.layers, num_heads=a.heads,
         vae_base_channels=a.vae_base_channels, save_mp4=not a.no_video_file, decode_audio=a.decode_audio,
         audio_path=a.audio, audio_start_time=a.audio_start, audio_max_duration=a.audio_duration, a2vid_two_stage=a.a2vid_two_stage, ti2vid_hq_audio=a.ti2vid_hq_audio,
-        two_stage_cfg=a.two_stage_cfg, modality_scale=a.modality_scale, standard_cfg=a.standard_cfg,
+        two_stage_cfg=a.two_stage_cfg, modality_scale=a.modality_scale, standard_cfg=a.standard_cfg, first_block_cache=a.first_block_cache,
         retake_audio=a.retake_audio, retake_audio_cfg=a.retake_audio_cfg,
         retake_video=a.retake, retake_start_time=a.retake_start, retake_end_time=a.retake_end, retake_composite=a.retake_keep_source,
         stg_blocks=a.stg_blocks, stg_cutoff=a.stg_cutoff, stg_audio_scale=a.stg_audio_scale, sampler=a.sampler, ancestral_eta=a.ancestral_eta)
