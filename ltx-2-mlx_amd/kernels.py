@@ -518,6 +518,40 @@ def _step_operands(x, timesteps, operands, mask=None):
     return n, c, timesteps
 
 
+def _segment(seg: dict, layout: tuple, required: tuple = ("vel_cond",), outputs: tuple = ("out",), null: tuple = (), like: str = "x",
+             both: bool = True):
+    """One latent's share of a C entry's arguments from its operands by name.  `layout`: the entry's per-segment arguments in ABI order, up to
+    (N, C), which follow: a str names a [N, C] fp32 tensor -- "timesteps" stands for the pointer and its stride, "mask" for the [N] mask --
+    and a tuple (key, cast[, default]) any other argument (no default: seg must hold it).  A tensor that seg leaves out is NULL, unless it is
+    in `required` (asserted) or in `outputs`: those are made like seg[like], except the ones in `null`, which stay NULL.  both: mask and
+    clean go together; else a mask needs its clean latent.  -> (arguments, {output name: tensor}, the tensors to keep alive across the call:
+    _step_operands may have made a contiguous fp32 copy of the timesteps, and the arguments hold its address only)."""
+    x = seg[like]
+    outs = {k: None if k in null else seg[k] if seg.get(k) is not None else torch.empty_like(x) for k in outputs}
+    tensors = {k: outs[k] if k in outs else seg.get(k) for k in layout if isinstance(k, str) and k != "timesteps"}
+    mask, clean = tensors.get("mask"), tensors.get("clean")
+    assert all(tensors[k] is not None for k in required) and ((mask is None) == (clean is None) if both else (mask is None or clean is not None))
+    n, c, ts = _step_operands(x, seg["timesteps"], tuple(t for k, t in tensors.items() if k not in (like, "mask")), mask)
+    args = []
+    for k in layout:
+        if k == "timesteps":
+            args += [nv.ptr(ts), 0 if ts.numel() == 1 else 1]
+        elif isinstance(k, str):
+            args.append(nv.ptr(tensors[k]))
+        else:
+            args.append(k[1](seg[k[0]] if len(k) == 2 else seg.get(k[0], k[2])))
+    return args + [n, c], outs, ts
+
+
+def _segments(segs, layout: tuple, **kw):
+    """_segment over the (video, audio) pair of a *_pair wrapper -> (the flat argument list, [outputs of each], the tensors to keep alive)."""
+    packed = [_segment(seg, layout, **kw) for seg in segs]
+    return [a for p in packed for a in p[0]], [p[1] for p in packed], [p[2] for p in packed]
+
+
+_GUIDED = ("x", "vel_cond", "vel_uncond", "timesteps", "mask", "clean", ("cfg_scale", float), "out")
+
+
 def guided_euler_step(x: torch.Tensor, vel_cond: torch.Tensor, vel_uncond: torch.Tensor, timesteps: torch.Tensor, cfg_scale: float, sigma: float,
                       sigma_next: float, mask: Optional[torch.Tensor] = None, clean: Optional[torch.Tensor] = None,
                       out: Optional[torch.Tensor] = None, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
@@ -538,18 +572,9 @@ def guided_euler_step_pair(video: dict, audio: dict, sigma: float, sigma_next: f
     """guided_euler_step over two latents in ONE launch (ltx2_guided_euler_step_pair): `video` and `audio` each hold the single form's
     operands by name -- x, vel_cond, vel_uncond, timesteps, cfg_scale and optionally mask, clean, out.  -> (video out, audio out), each
     equal to guided_euler_step's bit for bit."""
-    args, outs, held = [], [], []
-    for seg in (video, audio):
-        x, vc, vu, mask, clean = seg["x"], seg["vel_cond"], seg["vel_uncond"], seg.get("mask"), seg.get("clean")
-        out = seg["out"] if seg.get("out") is not None else torch.empty_like(x)
-        assert vc is not None and vu is not None and (mask is None) == (clean is None)
-        n, c, ts = _step_operands(x, seg["timesteps"], (vc, vu, clean, out), mask)
-        args += [nv.ptr(x), nv.ptr(vc), nv.ptr(vu), nv.ptr(ts), 0 if ts.numel() == 1 else 1, nv.ptr(mask), nv.ptr(clean), float(seg["cfg_scale"]),
-                 nv.ptr(out), n, c]
-        outs.append(out)
-        held.append(ts)          # _step_operands may have made a contiguous fp32 copy: args holds its address only, so it must outlive the launch call
+    args, outs, _held = _segments((video, audio), _GUIDED, required=("vel_cond", "vel_uncond"))
     nv.check(nv.lib(dtype).ltx2_guided_euler_step_pair(*args, float(sigma), float(sigma_next), nv.stream()))
-    return outs[0], outs[1]
+    return outs[0]["out"], outs[1]["out"]
 
 
 def seed_word(seed: int, device) -> torch.Tensor:
@@ -600,18 +625,9 @@ def ancestral_euler_step_pair(video: dict, audio: dict, sigma: float, sigma_up: 
     """ancestral_euler_step over two latents in ONE launch (ltx2_ancestral_euler_step_pair): `video` (noise stream 0) and `audio` (stream 1) each
     hold x, vel_cond, timesteps, cfg_scale and optionally vel_uncond, mask, clean, out.  -> (video out, audio out), each the single launch's
     bits (the audio's: a single launch on stream 1, which philox_normal(..., stream_id=1) and the torch ops restate)."""
-    args, outs, held = [], [], []
-    for seg in (video, audio):
-        x, vc, vu, mask, clean = seg["x"], seg["vel_cond"], seg.get("vel_uncond"), seg.get("mask"), seg.get("clean")
-        out = seg["out"] if seg.get("out") is not None else torch.empty_like(x)
-        assert vc is not None and (mask is None) == (clean is None)
-        n, c, ts = _step_operands(x, seg["timesteps"], (vc, vu, clean, out), mask)
-        args += [nv.ptr(x), nv.ptr(vc), nv.ptr(vu), nv.ptr(ts), 0 if ts.numel() == 1 else 1, nv.ptr(mask), nv.ptr(clean), float(seg["cfg_scale"]),
-                 nv.ptr(out), n, c]
-        outs.append(out)
-        held.append(ts)          # as in guided_euler_step_pair: the copy must outlive the launch call
+    args, outs, _held = _segments((video, audio), _GUIDED)
     nv.check(nv.lib(dtype).ltx2_ancestral_euler_step_pair(*args, float(sigma), float(sigma_up), float(sigma_down), _seed_ptr(seed), int(step), nv.stream()))
-    return outs[0], outs[1]
+    return outs[0]["out"], outs[1]["out"]
 
 
 def ancestral_euler_step_x0(x: torch.Tensor, x0: torch.Tensor, sigma: float, sigma_up: float, sigma_down: float, seed: torch.Tensor, step: int,
@@ -651,18 +667,10 @@ def stg_euler_step_pair(video: dict, audio: dict, sigma: float, sigma_next: floa
     """stg_euler_step over two latents in ONE launch (ltx2_stg_euler_step_pair): `video` and `audio` each hold the single form's operands by
     name -- x, vel_cond, timesteps, cfg_scale, stg_scale and optionally vel_uncond (None: no CFG on that modality), vel_perturbed (None: no
     STG term, guided_euler_step's arithmetic), mask, clean, out.  -> (video out, audio out), each equal to the single launch's bit for bit."""
-    args, outs, held = [], [], []
-    for seg in (video, audio):
-        x, vc, vu, vp, mask, clean = seg["x"], seg["vel_cond"], seg.get("vel_uncond"), seg.get("vel_perturbed"), seg.get("mask"), seg.get("clean")
-        out = seg["out"] if seg.get("out") is not None else torch.empty_like(x)
-        assert vc is not None and (mask is None) == (clean is None)
-        n, c, ts = _step_operands(x, seg["timesteps"], (vc, vu, vp, clean, out), mask)
-        args += [nv.ptr(x), nv.ptr(vc), nv.ptr(vu), nv.ptr(vp), nv.ptr(ts), 0 if ts.numel() == 1 else 1, nv.ptr(mask), nv.ptr(clean),
-                 float(seg["cfg_scale"]), float(seg["stg_scale"]), nv.ptr(out), n, c]
-        outs.append(out)
-        held.append(ts)          # _step_operands may have made a contiguous fp32 copy: args holds its address only, so it must outlive the launch call
+    layout = ("x", "vel_cond", "vel_uncond", "vel_perturbed", "timesteps", "mask", "clean", ("cfg_scale", float), ("stg_scale", float), "out")
+    args, outs, _held = _segments((video, audio), layout)
     nv.check(nv.lib(dtype).ltx2_stg_euler_step_pair(*args, float(sigma), float(sigma_next), nv.stream()))
-    return outs[0], outs[1]
+    return outs[0]["out"], outs[1]["out"]
 
 
 def channel_guidance_stats_blocks(rows: int, c: int, dtype: Optional[torch.dtype] = None) -> int:
@@ -799,23 +807,21 @@ def guidance_sums_pair(video: dict, audio: dict, dtype: Optional[torch.dtype] = 
     -- x, vel_cond, vel_uncond, timesteps and optionally partials, running, first (True), momentum (0.0).  A segment given as None is left out
     (its guider reads no sums; not both).  -> (video partials, audio partials), each equal to guidance_sums's bit for bit (None for a segment
     left out)."""
+    layout = ("x", "vel_cond", "vel_uncond", "timesteps", "running", ("first", lambda f: int(bool(f)), True), ("momentum", float, 0.0), ("partials", nv.ptr))
     args, parts, held = [], [], []
     for seg in (video, audio):
         if seg is None:
             args += [None, None, None, None, 0, None, 1, 0.0, None, 0, 0]
             parts.append(None)
             continue
-        x, vc, vu, running = seg["x"], seg["vel_cond"], seg["vel_uncond"], seg.get("running")
         part = seg.get("partials")
         if part is None:
-            part = torch.empty(guidance_sums_blocks(*x.shape, dtype=dtype), 5, device=x.device, dtype=torch.float64)
-        assert vc is not None and vu is not None
-        n, c, ts = _step_operands(x, seg["timesteps"], (vc, vu, running))
-        assert part.dtype == torch.float64 and part.is_contiguous() and part.numel() >= 5 * guidance_sums_blocks(n, c, dtype)
-        args += [nv.ptr(x), nv.ptr(vc), nv.ptr(vu), nv.ptr(ts), 0 if ts.numel() == 1 else 1, nv.ptr(running), int(bool(seg.get("first", True))),
-                 float(seg.get("momentum", 0.0)), nv.ptr(part), n, c]
+            part = torch.empty(guidance_sums_blocks(*seg["x"].shape, dtype=dtype), 5, device=seg["x"].device, dtype=torch.float64)
+        a, _, ts = _segment(dict(seg, partials=part), layout, required=("vel_cond", "vel_uncond"), outputs=())
+        assert part.dtype == torch.float64 and part.is_contiguous() and part.numel() >= 5 * guidance_sums_blocks(a[-2], a[-1], dtype)
+        args += a
         parts.append(part)
-        held.append(ts)          # _step_operands may have made a contiguous fp32 copy: args holds its address only, so it must outlive the launch call
+        held.append(ts)
     nv.check(nv.lib(dtype).ltx2_guidance_sums_pair(*args, nv.stream()))
     return parts[0], parts[1]
 
@@ -825,32 +831,25 @@ def projected_euler_step_pair(video: dict, audio: dict, sigma: float, sigma_next
     operands by name -- x, vel_cond, timesteps, mode, scale and optionally vel_uncond (mode 4 alone does without), partials (modes 0 - 2), eta
     (1.0), norm_threshold (0.0), mask, clean, running, out, scalars_out.  mode: 0 - 2 as projected_euler_step, 3 = CFGGuider's
     a + (scale - 1)*(a - b), 4 = not guided.  -> (video out, audio out), each equal to the single-launch step's bit for bit."""
-    args, outs, held = [], [], []
+    layout = ("x", "vel_cond", "vel_uncond", "timesteps", "mask", "clean", "running", ("partials", nv.ptr, None), ("mode", int), ("scale", float),
+              ("eta", float, 1.0), ("norm_threshold", float, 0.0), "out", ("scalars_out", nv.ptr, None))
+    args, outs, _held = _segments((video, audio), layout)
     for seg in (video, audio):
-        x, vc, vu, mask, clean, running = seg["x"], seg["vel_cond"], seg.get("vel_uncond"), seg.get("mask"), seg.get("clean"), seg.get("running")
-        part, sc, mode = seg.get("partials"), seg.get("scalars_out"), int(seg["mode"])
-        out = seg["out"] if seg.get("out") is not None else torch.empty_like(x)
-        assert vc is not None and (mask is None) == (clean is None)
-        n, c, ts = _step_operands(x, seg["timesteps"], (vc, vu, clean, running, out), mask)
+        part, sc, (n, c) = seg.get("partials"), seg.get("scalars_out"), seg["x"].shape
         assert part is None or (part.dtype == torch.float64 and part.is_contiguous() and part.numel() >= 5 * guidance_sums_blocks(n, c, dtype))
         assert sc is None or (sc.dtype == torch.float32 and sc.numel() >= 2)
-        args += [nv.ptr(x), nv.ptr(vc), nv.ptr(vu), nv.ptr(ts), 0 if ts.numel() == 1 else 1, nv.ptr(mask), nv.ptr(clean), nv.ptr(running), nv.ptr(part), mode,
-                 float(seg["scale"]), float(seg.get("eta", 1.0)), float(seg.get("norm_threshold", 0.0)), nv.ptr(out), nv.ptr(sc), n, c]
-        outs.append(out)
-        held.append(ts)          # as above
     nv.check(nv.lib(dtype).ltx2_projected_euler_step_pair(*args, float(sigma), float(sigma_next), nv.stream()))
-    return outs[0], outs[1]
+    return outs[0]["out"], outs[1]["out"]
 
 
-def _mm_args(seg: dict, out_key: str = "out"):
+_MM = ("x", "vel_cond", "vel_uncond", "vel_perturbed", "vel_isolated", "timesteps", "mask", "clean")
+
+
+def _mm_args(seg: dict):
     """One latent's operands of the multi-modal guided steps, by name -- x, vel_cond, timesteps and optionally vel_uncond, vel_perturbed,
     vel_isolated, mask, clean, out -- as the C entries take them -> (pointer / stride arguments up to `clean`, out, N, C, the tensors to keep)."""
-    x, vc, vu, vp, vm = seg["x"], seg["vel_cond"], seg.get("vel_uncond"), seg.get("vel_perturbed"), seg.get("vel_isolated")
-    mask, clean = seg.get("mask"), seg.get("clean")
-    out = seg[out_key] if seg.get(out_key) is not None else torch.empty_like(x)
-    assert vc is not None and (mask is None) == (clean is None)
-    n, c, ts = _step_operands(x, seg["timesteps"], (vc, vu, vp, vm, clean, out), mask)
-    return [nv.ptr(x), nv.ptr(vc), nv.ptr(vu), nv.ptr(vp), nv.ptr(vm), nv.ptr(ts), 0 if ts.numel() == 1 else 1, nv.ptr(mask), nv.ptr(clean)], out, n, c, ts
+    (*args, _out, n, c), outs, ts = _segment(seg, _MM + ("out",))
+    return args, outs["out"], n, c, ts
 
 
 def mm_guided_euler_step(x: torch.Tensor, vel_cond: torch.Tensor, timesteps: torch.Tensor, cfg_scale: float, stg_scale: float, modality_scale: float,
@@ -871,14 +870,9 @@ def mm_guided_euler_step_pair(video: dict, audio: dict, sigma: float, sigma_next
     """mm_guided_euler_step over two latents in ONE launch (ltx2_mm_guided_euler_step_pair): `video` and `audio` each hold the single form's
     operands by name -- x, vel_cond, timesteps, cfg_scale, stg_scale, modality_scale and optionally vel_uncond, vel_perturbed, vel_isolated,
     mask, clean, out.  -> (video out, audio out), each equal to mm_guided_euler_step's bit for bit."""
-    args, outs, keep = [], [], []
-    for seg in (video, audio):
-        a, out, n, c, ts = _mm_args(seg)
-        args += a + [float(seg["cfg_scale"]), float(seg["stg_scale"]), float(seg["modality_scale"]), nv.ptr(out), n, c]
-        outs.append(out)
-        keep.append(ts)
+    args, outs, _held = _segments((video, audio), _MM + (("cfg_scale", float), ("stg_scale", float), ("modality_scale", float), "out"))
     nv.check(nv.lib(dtype).ltx2_mm_guided_euler_step_pair(*args, float(sigma), float(sigma_next), nv.stream()))
-    return outs[0], outs[1]
+    return outs[0]["out"], outs[1]["out"]
 
 
 def mm_guidance_sums(x: torch.Tensor, vel_cond: torch.Tensor, timesteps: torch.Tensor, cfg_scale: float, stg_scale: float, modality_scale: float,
@@ -955,39 +949,20 @@ def res2s_midpoint_pair(video: dict, audio: dict, c: float, n_bong: int, final: 
     name -- x, vel_cond, timesteps, cfg_scale and optionally vel_uncond, mask, clean, x_mid, anchor, eps1 -- with shapes, scales, timesteps and
     conditioning of their own; c, n_bong and `final` are shared.  -> ((x_mid, anchor, eps1) of the video, the same of the audio), each equal
     to res2s_midpoint's bit for bit."""
-    args, outs = [], []
-    for seg in (video, audio):
-        x, vc, vu, mask, clean = seg["x"], seg["vel_cond"], seg.get("vel_uncond"), seg.get("mask"), seg.get("clean")
-        x_mid = seg["x_mid"] if seg.get("x_mid") is not None else torch.empty_like(x)
-        anchor = eps1 = None
-        if not final:
-            anchor = seg["anchor"] if seg.get("anchor") is not None else torch.empty_like(x)
-            eps1 = seg["eps1"] if seg.get("eps1") is not None else torch.empty_like(x)
-        assert vc is not None and (mask is None or clean is not None)
-        n, ch, ts = _step_operands(x, seg["timesteps"], (vc, vu, clean, x_mid, anchor, eps1), mask)
-        args += [nv.ptr(x), nv.ptr(vc), nv.ptr(vu), nv.ptr(ts), 0 if ts.numel() == 1 else 1, nv.ptr(mask), nv.ptr(clean), float(seg["cfg_scale"]),
-                 nv.ptr(x_mid), nv.ptr(anchor), nv.ptr(eps1), n, ch]
-        outs.append((x_mid, anchor, eps1, ts))
+    names = ("x_mid", "anchor", "eps1")
+    args, outs, _held = _segments((video, audio), _GUIDED[:-1] + names, outputs=names, null=names[1:] if final else (), both=False)
     nv.check(nv.lib(dtype).ltx2_res2s_midpoint_pair(*args, float(c), int(n_bong), nv.stream()))
-    return outs[0][:3], outs[1][:3]
+    return tuple(outs[0][k] for k in names), tuple(outs[1][k] for k in names)
 
 
 def res2s_combine_pair(video: dict, audio: dict, h: float, b1: float, b2: float, dtype: Optional[torch.dtype] = None):
     """res2s_combine over two latents in ONE launch (ltx2_res2s_combine_pair): `video` and `audio` each hold x_mid, vel_cond, timesteps,
     cfg_scale, anchor, eps1 and optionally vel_uncond, mask, clean, out; h, b1, b2 are shared.  -> (video out, audio out), each equal to
     res2s_combine's bit for bit; `out` may be any [N, C] operand of its segment."""
-    args, outs, keep = [], [], []
-    for seg in (video, audio):
-        xm, vc, vu, mask, clean, an, e1 = seg["x_mid"], seg["vel_cond"], seg.get("vel_uncond"), seg.get("mask"), seg.get("clean"), seg["anchor"], seg["eps1"]
-        out = seg["out"] if seg.get("out") is not None else torch.empty_like(xm)
-        assert vc is not None and an is not None and e1 is not None and (mask is None or clean is not None)
-        n, ch, ts = _step_operands(xm, seg["timesteps"], (vc, vu, clean, an, e1, out), mask)
-        args += [nv.ptr(xm), nv.ptr(vc), nv.ptr(vu), nv.ptr(ts), 0 if ts.numel() == 1 else 1, nv.ptr(mask), nv.ptr(clean), float(seg["cfg_scale"]),
-                 nv.ptr(an), nv.ptr(e1), nv.ptr(out), n, ch]
-        outs.append(out)
-        keep.append(ts)
+    layout = ("x_mid",) + _GUIDED[1:-1] + ("anchor", "eps1", "out")
+    args, outs, _held = _segments((video, audio), layout, required=("vel_cond", "anchor", "eps1"), like="x_mid", both=False)
     nv.check(nv.lib(dtype).ltx2_res2s_combine_pair(*args, float(h), float(b1), float(b2), nv.stream()))
-    return outs[0], outs[1]
+    return outs[0]["out"], outs[1]["out"]
 
 
 def heun_predict(x: torch.Tensor, vel_cond: torch.Tensor, vel_uncond: Optional[torch.Tensor], timesteps: torch.Tensor, cfg_scale: float, sigma: float,
@@ -1037,14 +1012,7 @@ def ge_euler_step(x: torch.Tensor, vel_cond: torch.Tensor, vel_uncond: Optional[
     return out
 
 
-def _heun_segment(seg: dict, outputs: tuple):
-    """One latent's operands of the Heun / GE pair launches, by name -> (x, vel_cond, vel_uncond, timesteps, stride, mask, clean pointers,
-    cfg_scale), the output tensors named in `outputs` (made where absent, None where the name maps to None in seg with key present), N, C, ts."""
-    x, vc, vu, mask, clean = seg["x"], seg["vel_cond"], seg.get("vel_uncond"), seg.get("mask"), seg.get("clean")
-    outs = [seg[k] if k in seg else torch.empty_like(x) for k in outputs]
-    assert vc is not None and (mask is None) == (clean is None)
-    n, c, ts = _step_operands(x, seg["timesteps"], (vc, vu, clean, seg.get("prev"), seg.get("d"), seg.get("xp"), *outs), mask)
-    return [nv.ptr(x), nv.ptr(vc), nv.ptr(vu), nv.ptr(ts), 0 if ts.numel() == 1 else 1, nv.ptr(mask), nv.ptr(clean), float(seg["cfg_scale"])], outs, n, c, ts
+_GE = (("ge_gamma", float), "prev", ("first", lambda f: int(bool(f))))     # the video's GE arguments, behind cfg_scale: dict(video, ge_gamma=..., first=...)
 
 
 def heun_predict_pair(video: dict, audio: dict, sigma: float, sigma_next: float, ge_gamma: float = 0.0, first: bool = True, final: bool = False,
@@ -1052,42 +1020,29 @@ def heun_predict_pair(video: dict, audio: dict, sigma: float, sigma_next: float,
     """heun_predict over two latents in ONE launch (ltx2_heun_predict_pair): `video` and `audio` each hold x, vel_cond, timesteps, cfg_scale
     and optionally vel_uncond, mask, clean, d, xp; the video alone may hold `prev` (GE acts on it alone).  -> ((d, xp) of the video, the same
     of the audio), each equal to heun_predict's bit for bit; final=True: xp is None in both."""
-    keep = []
-    if final:
-        video, audio = dict(video, xp=None), dict(audio, xp=None)
-    va, (vd, vxp), vn, vc_, ts = _heun_segment(video, ("d", "xp"))
-    keep.append(ts)
-    aa, (ad, axp), an, ac, ts = _heun_segment(audio, ("d", "xp"))
-    keep.append(ts)
-    nv.check(nv.lib(dtype).ltx2_heun_predict_pair(*va, float(ge_gamma), nv.ptr(video.get("prev")), int(bool(first)), nv.ptr(vd), nv.ptr(vxp), vn, vc_,
-                                                  *aa, nv.ptr(ad), nv.ptr(axp), an, ac, float(sigma), float(sigma_next), nv.stream()))
-    return (vd, vxp), (ad, axp)
+    kw = dict(outputs=("d", "xp"), null=("xp",) if final else ())
+    va, v, _vts = _segment(dict(video, ge_gamma=ge_gamma, first=first), _GUIDED[:-1] + _GE + ("d", "xp"), **kw)
+    aa, a, _ats = _segment(audio, _GUIDED[:-1] + ("d", "xp"), **kw)
+    nv.check(nv.lib(dtype).ltx2_heun_predict_pair(*va, *aa, float(sigma), float(sigma_next), nv.stream()))
+    return (v["d"], v["xp"]), (a["d"], a["xp"])
 
 
 def heun_correct_pair(video: dict, audio: dict, sigma: float, sigma_next: float, dtype: Optional[torch.dtype] = None):
     """heun_correct over two latents in ONE launch (ltx2_heun_correct_pair): `video` and `audio` each hold x, d, xp, vel_cond, timesteps,
     cfg_scale and optionally vel_uncond, mask, clean, out.  -> (video out, audio out), each equal to heun_correct's bit for bit."""
-    args, outs, keep = [], [], []
-    for seg in (video, audio):
-        a, (out,), n, c, ts = _heun_segment(seg, ("out",))
-        assert seg["d"] is not None and seg["xp"] is not None
-        args += [a[0], nv.ptr(seg["d"]), nv.ptr(seg["xp"]), *a[1:], nv.ptr(out), n, c]
-        outs.append(out)
-        keep.append(ts)
+    args, outs, _held = _segments((video, audio), ("x", "d", "xp") + _GUIDED[1:], required=("d", "xp", "vel_cond"))
     nv.check(nv.lib(dtype).ltx2_heun_correct_pair(*args, float(sigma), float(sigma_next), nv.stream()))
-    return outs[0], outs[1]
+    return outs[0]["out"], outs[1]["out"]
 
 
 def ge_euler_step_pair(video: dict, audio: dict, ge_gamma: float, first: bool, sigma: float, sigma_next: float, dtype: Optional[torch.dtype] = None):
     """ge_euler_step over the video latent and the plain guided Euler step over the audio latent in ONE launch (ltx2_ge_euler_step_pair):
     `video` holds x, vel_cond, timesteps, cfg_scale, prev and optionally vel_uncond, mask, clean, out; `audio` the same without prev.
     -> (video out, audio out), each equal to the single launch's bit for bit."""
-    va, (vout,), vn, vc_, vts = _heun_segment(video, ("out",))
-    aa, (aout,), an, ac, ats = _heun_segment(audio, ("out",))
-    nv.check(nv.lib(dtype).ltx2_ge_euler_step_pair(*va, float(ge_gamma), nv.ptr(video["prev"]), int(bool(first)), nv.ptr(vout), vn, vc_,
-                                                   *aa, nv.ptr(aout), an, ac, float(sigma), float(sigma_next), nv.stream()))
-    del vts, ats
-    return vout, aout
+    va, v, _vts = _segment(dict(video, ge_gamma=ge_gamma, first=first), _GUIDED[:-1] + _GE + ("out",), required=("vel_cond", "prev"))
+    aa, a, _ats = _segment(audio, _GUIDED)
+    nv.check(nv.lib(dtype).ltx2_ge_euler_step_pair(*va, *aa, float(sigma), float(sigma_next), nv.stream()))
+    return v["out"], a["out"]
 
 
 def pixnorm_mod_silu(x: torch.Tensor, table: torch.Tensor, te: Optional[torch.Tensor], shift_row: int, scale_row: int,
